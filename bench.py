@@ -33,12 +33,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  One leg uses the caller's stream + three
-# stage streams (CRN), or + two side streams (FullSubNet / training layer wavefront): with earlier legs' streams in
-# the round-robin, two of a leg's own streams can land on one queue and serialise (training leg 289 -> 306 utt/s, student +1 %, CRN_ELU
-# +2 % with 8 queues; the headline itself is unchanged).  Read by the runtime at initialisation, inherited by the rank processes.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 FP32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4 dense peak
 BF16_DENSE_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 / fp16 MFMA peak (spec)
 
@@ -169,6 +163,29 @@ def host_cpu_share():
 
 def progress(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write what the timed path computed in its last step as DIR/<name>.npy (float32, or float64 where the
+    path returns float64), at most DUMP_MAX_BYTES in all.  An array over its share of the budget is replaced by a fixed,
+    seeded sample of its rows (sorted indices, the same for every build), so two builds can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in arrays.items()}
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            if a.ndim < 2 or a[0].nbytes > share:  # sample single elements
+                a = a.reshape(-1)
+            keep = max(1, share // a[0].nbytes)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            progress(f"dump: {name} sampled to {keep} of {a.shape[0]} rows (seeded)")
+            a = a[rows]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+    progress(f"dump: {', '.join(sorted(arrays))} -> {dirname}")
 
 
 def cpu_baseline(cfg, sd, variant=0, seconds_budget=20.0):
@@ -314,7 +331,7 @@ def timed_region(fn, steps, warmup, world, backend):
 # ---------------------------------------------------------------------------------------------------------------
 # workloads
 # ---------------------------------------------------------------------------------------------------------------
-def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_model=None):
+def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_model=None, dump_dir=None):
     """BASELINE configs[3]: TemporalCRN data-parallel training, utterances sharded across ranks, ONE flat fp32 gradient
     all-reduce (24.5 MB) per optimizer step.  A step = forward + backward over `--utts` 3 s utterances per GPU (two
     micro-batches, grad accumulation 2 like config.yaml:99), all-reduce, clip, Adam.  value = utterances/s over all ranks."""
@@ -346,7 +363,7 @@ def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_m
                            ((0.06, 0.06, 0.06), (0.15, 0.15, 0.15)), ((0.0, 0.0, 0.3), (1.0, 1.0, 0.7)), num_src=1, num_mic=3)
         _, dry = synth.synth_utterances(64, L, 1, seed=3000 + rank)
         dry_pool = torch.from_numpy(dry).cuda()
-        noise_pool = torch.randn(64, L, device="cuda") * 0.1
+        noise_pool = torch.randn(64, L, device="cuda", generator=torch.Generator(device="cuda").manual_seed(4000 + rank)) * 0.1
         rng = np.random.default_rng(17 + rank)
 
         def make_batch():
@@ -369,6 +386,7 @@ def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_m
                 pending["ready"] = e1
                 gen_ms.append((e0, e1))
 
+        gen_stream.wait_stream(torch.cuda.current_stream())  # the pools above are written on this stream
         prefetch()
 
     def step():
@@ -383,6 +401,9 @@ def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_m
     progress(f"train: {warmup} + {steps} steps, kernels = {args.train_kernels}, loss = {args.train_loss}")
     dt = timed_region(step, steps, warmup, world, backend)
     assert np.isfinite(last["loss"])
+    if dump_dir and rank == 0:  # the step's loss, the reduced + clipped gradient it applied, and the parameters it left
+        dump_outputs(dump_dir, {"loss": np.array([last["loss"]], np.float64), "grad": bucket.flat.cpu().numpy(),
+                                "params": torch.cat([p.detach().reshape(-1) for p in bucket.params]).cpu().numpy()})
     value = world * U * steps / dt
     roofline = None
     if args.train_kernels == "hip":  # one extra profiled step: events around every hand-written launch on the launch stream
@@ -429,14 +450,14 @@ def train_line(args, rank, local_rank, train_model="crn"):
 
 def bench_train(args, rank, local_rank, world, backend):
     import torch.distributed as dist
-    result = train_measure(args, rank, local_rank, world, backend, args.steps, args.warmup)
+    result = train_measure(args, rank, local_rank, world, backend, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if rank == 0:
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()
 
 
-def fullsubnet_measure(args, rank, local_rank, world, backend, B, dtype, steps, warmup):
+def fullsubnet_measure(args, rank, local_rank, world, backend, B, dtype, steps, warmup, dump_dir=None):
     """BASELINE configs[2]: FullSubNet (fb + sb 2-layer LSTM) streaming inference, reference config.yaml:153-172."""
     import torch
     from speech_enhancement_mi_amd import engine, synth
@@ -452,6 +473,8 @@ def fullsubnet_measure(args, rank, local_rank, world, backend, B, dtype, steps, 
     progress(f"FullSubNet: {warmup} + {steps} steps, B={B}, {dtype}")
     dt = timed_region(lambda: eng.realtime_process(mix, out=out), steps, warmup, world, backend)
     assert bool(torch.isfinite(out).all())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"enhanced": out.cpu().numpy()})
     value = world * B * nseg * steps / dt
     tf = value / world * eng.flops_per_frame / 1e12
     terms = {"f32": 6.0, "bf16x3": 3.0}[dtype]
@@ -481,16 +504,17 @@ def fullsubnet_line(args, rank, local_rank, B, dtype, steps, warmup):
 
 def bench_fullsubnet(args, rank, local_rank, world, backend):
     import torch.distributed as dist
-    result = fullsubnet_measure(args, rank, local_rank, world, backend, args.batch, args.dtype, args.steps, args.warmup)
+    result = fullsubnet_measure(args, rank, local_rank, world, backend, args.batch, args.dtype, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if rank == 0:
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()
 
 
-def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank, world, backend, label_progress=""):
+def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank, world, backend, label_progress="", keep_output=False):
     """One CRN-family streaming workload: timed region + one extra profiled step (HIP events on the launch stream around every
-    launch).  Returns (value frames/s, ms_per_step, roofline dict, cfg, sd, variant, eng-derived info)."""
+    launch).  Returns (value frames/s, ms_per_step, roofline dict, cfg, sd, variant, eng-derived info); keep_output: info["output"]
+    = the enhanced waveforms [B, L] of the last timed step, copied to the host before the profiled step."""
     import torch
     from speech_enhancement_mi_amd import engine, synth
     cfg = crn_cfg(nfft, model)
@@ -510,6 +534,7 @@ def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank,
     progress(f"{label_progress}timed region: {warmup} + {steps} steps ({model}, B={B}, {nfft}-pt, {dtype})")
     dt = timed_region(lambda: eng.realtime_process(mix, out=out), steps, warmup, world, backend)
     assert bool(torch.isfinite(out).all()), "non-finite output"
+    host_out = out.cpu().numpy() if keep_output else None
     frames = world * B * nseg * steps
     value = frames / dt
     progress(f"{label_progress}{value:.0f} frames/s; profiled step")
@@ -560,7 +585,7 @@ def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank,
                                      frac_of_executed_pipe=(terms * v["flops"] / (v["ms"] * 1e-3) / 1e12 / BF16_DENSE_PEAK_TFLOPS if v["ms"] > 0 else 0.0))
                              for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1]["ms"])},
                     labels={r["label"]: dict(ms=round(r["ms"], 3), launches=r["launches"]) for r in recs})
-    info = dict(cfg=cfg, sd=sd, variant=variant, label=label, nseg=nseg, mflop_per_frame=eng.flops_per_frame / 1e6, dt=dt)
+    info = dict(cfg=cfg, sd=sd, variant=variant, label=label, nseg=nseg, mflop_per_frame=eng.flops_per_frame / 1e6, dt=dt, output=host_out)
     eng.close()
     del mix, out
     torch.cuda.empty_cache()
@@ -614,7 +639,10 @@ def secondary_lines(args, rank, local_rank):
 def bench_crn(args, rank, local_rank, world, backend):
     import torch.distributed as dist
     B = args.batch
-    value, ms_per_step, roofline, info = measure_crn(args.model, args.nfft, B, args.dtype, args.seconds, args.steps, args.warmup, rank, local_rank, world, backend)
+    value, ms_per_step, roofline, info = measure_crn(args.model, args.nfft, B, args.dtype, args.seconds, args.steps, args.warmup, rank, local_rank, world, backend,
+                                                     keep_output=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"enhanced": info.pop("output")})
     cfg, sd, variant, label, nseg = info["cfg"], info["sd"], info["variant"], info["label"], info["nseg"]
     dt = info["dt"]
     result = dict(metric=f"streaming frames/sec @ b{B} ({label}, 3200-samp 16 kHz)", value=value, unit="frames/s",
@@ -665,6 +693,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="headline line only: skip the FullSubNet / student / CRN_ELU / training legs")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB in all; a seeded row sample of a larger output)")
     ap.add_argument("--dtype", choices=sorted(PRECISIONS), default="f32",
                     help="f32 = fp32-accurate contractions (headline); bf16x3 = 3-term split-bf16 (inside the 1e-4 parity bar; BASELINE config 5: "
                          "--model student --dtype bf16x3 --batch 1024); f16 = fp16 MFMA operands (outside the parity bar)")
@@ -681,6 +712,8 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: become the parent of N ranks BEFORE anything touches the GPU
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
