@@ -139,7 +139,8 @@ int se_profile(se_engine *e, int enable);
 int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap, double *ms_total,
                     int64_t *launches, double *flops_per_launch);
 
-int se_abi_version(void);  /* 4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*) */
+int se_abi_version(void);  /* 4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
+                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -174,6 +175,21 @@ int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t
 /* host copies of "fb_out" [B*T, F], "mean_fb" [B], "mean_sb" [B] after the last forward */
 int fsn_read_tap(fsn_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream);
 double fsn_flops_per_frame(const fsn_engine *e);
+/* Training (train_fullsubnet.py:137-145: autograd over realtime_process(train=False), fullsubnet.py:903-961).  All pointers are DEVICE
+ * pointers; the calls enqueue on `stream`.  nseg = N windows of the chunk.
+ * fsn_train_ws_bytes: workspace size for (batch, nseg): the activations of every LSTM step (gates, c, h) of all windows, laid out
+ *   [T][N * rows][.] so that step t of every window is one slab, plus the backward's scratch (about 31 GB at 8 utterances x 3 s).
+ * fsn_train_fwd: spec = se_sig_stft of the chunk [nseg][batch * M][T][F][2]; runs the windows in the engine's own order (CumLayerNorm
+ *   updates, full band, unfold, sub band; fullsubnet.py:769-824), carries the state like fsn_realtime_process (flag = 0 resets it,
+ *   fullsubnet.py:912-915), writes crm_out [nseg][batch][2][F][T] (pred_crm) and saves what the backward needs into ws.
+ * fsn_train_bwd: dcrm [nseg][batch][2][F][T] = d loss / d crm of the same (batch, nseg, ws) -> the gradient of every fb_model.* /
+ *   sb_model.* parameter in checkpoint layout, grads[] in state_dict order: per model (fb, then sb) weight_ih_l, weight_hh_l, bias_ih_l,
+ *   bias_hh_l of each layer, then fc_output_layer.weight, fc_output_layer.bias; ngrads = 2 (4 num_layers + 2).  The BPTT stops at
+ *   every window seam (the state is detached, fullsubnet.py:819-820) and the CumLayerNorm means are detached (fullsubnet.py:200).
+ *   Deterministic: no float atomics, identical gradients run to run. */
+int64_t fsn_train_ws_bytes(fsn_engine *e, int batch, int nseg);
+int fsn_train_fwd(fsn_engine *e, const float *spec, int batch, int nseg, int flag, void *ws, float *crm_out, void *stream);
+int fsn_train_bwd(fsn_engine *e, const float *dcrm, int batch, int nseg, void *ws, float *const *grads, int ngrads, void *stream);
 
 /* ---- training loss (reference CRN.py:593-617 compute_loss) ------------------------------------------------
  * SI-SNR term, utility.cal_si_snr (utility.py:207-223), device-resident: separated / source [B, L] fp32 device tensors,

@@ -120,6 +120,8 @@ struct LstmStepArgs {
     float *hseq;       // optional second copy of h (row stride ldseq), nullptr = off
     long ldseq;
     int R, H;
+    // training forward only (k_lstm_step_x6<PL, true>): post-activation gates i, f, g, o [R][4H], c_t [R][H] and h_t [R][H] of this step
+    float *gsave, *csave, *hsave;
 #ifdef SE_LSTM_STAMPS
     unsigned long long *stamps;  // diagnostic build only: per-segment cycle sums of one wave (never read by the kernel)
 #endif
@@ -130,9 +132,11 @@ struct LstmStepArgs {
 #endif
 
 // PL = operand planes: 3 = fp32-accurate (six products), 2 = "bf16x3" (hi, mid: three products, fsn_config.precision = 2)
+// SAVE = the training forward's instantiation (fsn_train_fwd): also writes the activations the backward needs (gsave / csave / hsave);
+// the inference instantiations (SAVE = false) compile to the same code as without the flag
 // (A variant that staged [x_t | h_{t-1}] from pre-split planes written by the producers - a pure copy, no VALU split in the loop - was
 //  7 % / 4 % slower: 1.5x the operand bytes, and the split was never the wait, see k_lstm_step_big's header.)
-template <int PL>
+template <int PL, bool SAVE = false>
 __global__ __launch_bounds__(256) void k_lstm_step_x6(LstmStepArgs a) {
     __shared__ __align__(16) __bf16 Ap[PL][kGemmBM * kXLd];
     __shared__ __align__(16) __bf16 Wl[PL][kGemmBN * kXLd];
@@ -265,6 +269,12 @@ __global__ __launch_bounds__(256) void k_lstm_step_x6(LstmStepArgs a) {
         a.c[idx] = cn;
         a.hout[idx] = hn;
         if (a.hseq) a.hseq[(long)m * a.ldseq + j] = hn;
+        if constexpr (SAVE) {
+            float *g = a.gsave + (long)m * 4 * H;
+            g[j] = ig; g[H + j] = fg; g[2 * H + j] = gg; g[3 * H + j] = og;
+            a.csave[idx] = cn;
+            a.hsave[idx] = hn;
+        }
     }
 }
 
@@ -523,3 +533,4 @@ __global__ __launch_bounds__(256) void k_fsn_sbfc(const float *h, const float *w
 }  // namespace se
 
 #include "fsn_mask.hip.h"
+#include "fsn_train.hip.h"

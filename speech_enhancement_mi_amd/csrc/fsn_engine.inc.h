@@ -15,6 +15,8 @@ struct fsn_engine {
         DevBuf fcw, fcw_x, fcb;
         DevBuf h[4][2], c[4];       // state
         int hcur[4]{};
+        DevBuf whh_t[4], wih_t[4];  // training backward (fp32): W_hh^T [H][4H], W_ih^T [in][4H] (layers >= 1)
+        DevBuf wcol, fcw_t;         // sub-band: column SI - 1 of W_ih_l0 [4H]; full-band: fc weight^T [H][Fp] (zero padded)
     } fb, sb;
     int B = 0;
     DevBuf spec, maskspec, mag, fb_seq, fb_out, sbin, mask, part_fb, part_sb, mean_fb, mean_sb, denom_fb, denom_sb, yseg;
@@ -27,8 +29,27 @@ struct fsn_engine {
     // one-workgroup-per-CU tiles, the second fills the first one's last round
     hipStream_t side2 = nullptr;
     std::vector<hipEvent_t> ev_l0, ev_l1;  // per time step: layer 0 / layer 1 (+ its output layer) done
+    // fsn_train_fwd: where the stages save the activations of window `tr_n` (fsn_train.inc.h); null in inference
+    const struct FsnTrainLayout *tr = nullptr;
+    float *tr_ws = nullptr;
+    int tr_n = 0;
+    bool train_ready = false;  // the fp32 transposed weights of the backward are uploaded
     int pipeline = 1;     // SE_FSN_PIPELINE=0: one stream, stage after stage (read at fsn_create)
     int lstm_big = 1;     // SE_FSN_BIG=0: keep the 128 x 128 step tiles where the 256-row x 64-unit tile would be picked (read at fsn_create)
+};
+
+// Float offsets into the workspace of fsn_train_fwd / fsn_train_bwd (include/se_engine.h).  Model index 0 = full band (S = N*B rows per
+// step), 1 = sub band (S = N*B*F rows).  Every saved tensor is [T][S][.]: step t of ALL N windows is one contiguous slab, window n's
+// rows at n*B (*F) inside it, so one backward launch per step covers every window (the state is detached at each seam).
+struct FsnTrainLayout {
+    int B = 0, N = 0;
+    long S[2]{};
+    size_t gates[2][4]{}, cs[2][4]{}, hs[2][4]{};  // gates i, f, g, o [T][S][4H]; c, h [T + 1][S][H], slot 0 = the state entering the window
+    size_t xs[2]{};                                // layer-0 inputs: full band [T][S][Kp] (normalised |X|), sub band [T][S][SI]
+    size_t fbo = 0;                                // full-band output after the ReLU [T][S][F]
+    size_t denom = 0;                              // sub-band CumLayerNorm denominators of every window [N][B]
+    size_t dg = 0, dcf = 0, dx = 0, dm = 0, dpre = 0, wsum = 0, csum = 0, tmp = 0;  // backward scratch
+    size_t total = 0;
 };
 
 namespace {
@@ -125,9 +146,40 @@ int fsn_prepare(fsn_engine *e) {
     return 0;
 }
 
-int fsn_lstm_step(fsn_engine *e, fsn_engine::Model &m, int l, const float *x, long ldx, int K1, int K1p, int R, float *hseq, long ldseq, hipStream_t st) {
+// training forward, before window e->tr_n's LSTM: its layer-0 input (element (r, t, k) at x[r*sR + t*sT + k], W columns) -> xs[mi] and
+// each layer's entering state (h, c) -> slot 0 of hs / cs
+int fsn_train_save_window(fsn_engine *e, int mi, const float *x, long sR, long sT, int W, int R, hipStream_t st) {
+    const FsnTrainLayout &L = *e->tr;
+    fsn_engine::Model &m = mi ? e->sb : e->fb;
+    const long S = L.S[mi], r0 = (long)e->tr_n * R;
+    hipLaunchKernelGGL(k_fsn_save_rows, dim3(2048), dim3(256), 0, st, x, sR, sT, W, R, e->T, e->tr_ws + L.xs[mi] + r0 * W, S * W);
+    FHIP(e, hipGetLastError());
+    for (int l = 0; l < e->NL; l++) {
+        const size_t n = (size_t)R * m.H;
+        FHIP(e, hipMemcpyAsync(e->tr_ws + L.hs[mi][l] + r0 * m.H, m.h[l][m.hcur[l]].p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        FHIP(e, hipMemcpyAsync(e->tr_ws + L.cs[mi][l] + r0 * m.H, m.c[l].p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    return 0;
+}
+
+// t >= 0 and e->tr set (fsn_train_fwd): step t of window e->tr_n, saving gates, c_t and h_t into the training workspace
+int fsn_lstm_step(fsn_engine *e, fsn_engine::Model &m, int l, const float *x, long ldx, int K1, int K1p, int R, float *hseq, long ldseq, hipStream_t st,
+                  int t = -1) {
     const int hc = m.hcur[l];
     LstmStepArgs a{x, ldx, K1, K1p, m.h[l][hc].p, reinterpret_cast<const __bf16 *>(m.Wp[l].p), m.bias[l].p, m.c[l].p, m.h[l][hc ^ 1].p, hseq, ldseq, R, m.H};
+    if (e->tr && t >= 0) {  // all training steps take the 128 x 128 tile (at R = B*F = 1 608 per window the step is latency-bound anyway)
+        const FsnTrainLayout &L = *e->tr;
+        const int mi = &m == &e->sb ? 1 : 0;
+        const long S = L.S[mi], r0 = (long)e->tr_n * R, H = m.H;
+        a.gsave = e->tr_ws + L.gates[mi][l] + ((long)t * S + r0) * 4 * H;
+        a.csave = e->tr_ws + L.cs[mi][l] + ((long)(t + 1) * S + r0) * H;
+        a.hsave = e->tr_ws + L.hs[mi][l] + ((long)(t + 1) * S + r0) * H;
+        const dim3 grid((m.H + 31) / 32, (R + kGemmBM - 1) / kGemmBM);
+        if (e->c.precision == 2) hipLaunchKernelGGL((k_lstm_step_x6<2, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_lstm_step_x6<3, true>), grid, dim3(256), 0, st, a);
+        m.hcur[l] = hc ^ 1;
+        return 0;
+    }
 #ifdef SE_LSTM_STAMPS
     static unsigned long long *stamps = nullptr;
     static int nlaunch = 0;
@@ -183,12 +235,16 @@ int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long 
         hipLaunchKernelGGL(k_fsn_scale, dim3(16, B), dim3(256), 0, st, e->mag.p, (long)T * Kp, e->denom_fb.p);
         FHIP(e, hipGetLastError());
     }
+    if (e->tr) {  // training forward: the layer-0 input and the state entering the window
+        int rc = fsn_train_save_window(e, 0, e->mag.p, (long)T * Kp, Kp, Kp, B, st);
+        if (rc) return rc;
+    }
     for (int t = 0; t < T; t++) {  // full-band LSTM (2 layers interleaved per step), fullsubnet.py:789
         for (int l = 0; l < e->NL; l++) {
             const bool last = l + 1 == e->NL;
-            if (l == 0) fsn_lstm_step(e, e->fb, 0, e->mag.p + (long)t * Kp, (long)T * Kp, Kp, Kp, B, last ? e->fb_seq.p + (long)t * e->fb.H : nullptr, (long)T * e->fb.H, st);
+            if (l == 0) fsn_lstm_step(e, e->fb, 0, e->mag.p + (long)t * Kp, (long)T * Kp, Kp, Kp, B, last ? e->fb_seq.p + (long)t * e->fb.H : nullptr, (long)T * e->fb.H, st, t);
             else fsn_lstm_step(e, e->fb, l, e->fb.h[l - 1][e->fb.hcur[l - 1]].p, e->fb.H, e->fb.H, (e->fb.H + 31) & ~31, B,
-                               last ? e->fb_seq.p + (long)t * e->fb.H : nullptr, (long)T * e->fb.H, st);
+                               last ? e->fb_seq.p + (long)t * e->fb.H : nullptr, (long)T * e->fb.H, st, t);
         }
     }
     FHIP(e, hipGetLastError());
@@ -197,6 +253,12 @@ int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long 
         hipLaunchKernelGGL(k_gemm_x<3>, dim3((F + kGemmBN - 1) / kGemmBN, (B * T + kGemmBM - 1) / kGemmBM), dim3(256), 0, st, g);
     }
     FHIP(e, hipGetLastError());
+    if (e->tr) {  // fb_out [B*T][F] -> [T][S][F] (its sign is the ReLU's derivative)
+        const FsnTrainLayout &L = *e->tr;
+        hipLaunchKernelGGL(k_fsn_save_rows, dim3(1024), dim3(256), 0, st, e->fb_out.p, (long)T * F, (long)F, F, B, T,
+                           e->tr_ws + L.fbo + (long)e->tr_n * B * F, L.S[0] * F);
+        FHIP(e, hipGetLastError());
+    }
     return 0;
 }
 
@@ -218,6 +280,11 @@ int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long 
         hipLaunchKernelGGL(k_fsn_scale_sb, dim3(2048), dim3(256), 0, st, e->sbin.p, B, T, F, SI, e->denom_sb.p);
         FHIP(e, hipGetLastError());
     }
+    if (e->tr) {  // training forward: the normalised sub-band input, this window's denominators, the state entering the window
+        FHIP(e, hipMemcpyAsync(e->tr_ws + e->tr->denom + (long)e->tr_n * B, e->denom_sb.p, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+        int rc = fsn_train_save_window(e, 1, e->sbin.p, SI, (long)R * SI, SI, R, st);
+        if (rc) return rc;
+    }
     // two layers (the reference configuration) on two streams: layer 0 of step t + 1 next to layer 1 of step t.  h of layer 0 ping-pongs
     // between two buffers: step t + 2 of layer 0 overwrites what layer 1 of step t reads, hence ev_l1[t].
     const bool wave = consumed != nullptr && e->side2 && e->NL == 2 && (int)e->ev_l0.size() >= T;
@@ -226,8 +293,8 @@ int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long 
             hipStream_t sl = wave && l == 1 ? e->side2 : st;
             if (wave && l == 0 && t >= 2) FHIP(e, hipStreamWaitEvent(st, e->ev_l1[t - 2], 0));
             if (wave && l == 1) FHIP(e, hipStreamWaitEvent(sl, e->ev_l0[t], 0));
-            if (l == 0) fsn_lstm_step(e, e->sb, 0, e->sbin.p + (long)t * R * SI, SI, SI, (SI + 31) & ~31, R, nullptr, 0, sl);
-            else fsn_lstm_step(e, e->sb, l, e->sb.h[l - 1][e->sb.hcur[l - 1]].p, e->sb.H, e->sb.H, (e->sb.H + 31) & ~31, R, nullptr, 0, sl);
+            if (l == 0) fsn_lstm_step(e, e->sb, 0, e->sbin.p + (long)t * R * SI, SI, SI, (SI + 31) & ~31, R, nullptr, 0, sl, t);
+            else fsn_lstm_step(e, e->sb, l, e->sb.h[l - 1][e->sb.hcur[l - 1]].p, e->sb.H, e->sb.H, (e->sb.H + 31) & ~31, R, nullptr, 0, sl, t);
             if (wave && l == 0) FHIP(e, hipEventRecord(e->ev_l0[t], st));
         }
         const int ll = e->NL - 1;
@@ -340,8 +407,11 @@ void fsn_destroy(fsn_engine *e) {
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
     for (fsn_engine::Model *m : {&e->fb, &e->sb}) {
-        for (int l = 0; l < 4; l++) { dev_free(m->Wp[l]); dev_free(m->bias[l]); dev_free(m->h[l][0]); dev_free(m->h[l][1]); dev_free(m->c[l]); }
-        dev_free(m->fcw); dev_free(m->fcw_x); dev_free(m->fcb);
+        for (int l = 0; l < 4; l++) {
+            dev_free(m->Wp[l]); dev_free(m->bias[l]); dev_free(m->h[l][0]); dev_free(m->h[l][1]); dev_free(m->c[l]);
+            dev_free(m->whh_t[l]); dev_free(m->wih_t[l]);
+        }
+        dev_free(m->fcw); dev_free(m->fcw_x); dev_free(m->fcb); dev_free(m->wcol); dev_free(m->fcw_t);
     }
     for (DevBuf *b : {&e->spec, &e->maskspec, &e->mag, &e->fb_seq, &e->fb_out, &e->sbin, &e->mask, &e->part_fb, &e->part_sb, &e->mean_fb,
                       &e->mean_sb, &e->denom_fb, &e->denom_sb, &e->yseg})
@@ -375,6 +445,7 @@ int fsn_load_param(fsn_engine *e, const char *key, const float *host_data, const
     for (int i = 0; i < ndim; i++) cnt *= (size_t)shape[i];
     e->params[k].assign(host_data, host_data + cnt);
     e->weights_ready = false;
+    e->train_ready = false;
     return SE_OK;
 }
 

@@ -1,0 +1,223 @@
+// fsn_train.inc.h - FullSubNet training behind fsn_train_ws_bytes / fsn_train_fwd / fsn_train_bwd (include/se_engine.h); included at
+// the end of se_engine.hip after fsn_engine.inc.h and train_ops.inc.h.
+// Reference: train_fullsubnet.py:137-145 (autograd over realtime_process(train=False), fullsubnet.py:903-961, one forward per window,
+// fullsubnet.py:769-824).  The LSTM state (fh, sh) is detached after every window (fullsubnet.py:819-820), so the BPTT of window n
+// starts from window n - 1's state as a constant, and the N windows' sequences are independent in the backward: each BPTT step is ONE
+// launch over S = N x rows sequences (k_lstm_bwd_step).  Both CumLayerNorms divide by a detached running mean (fullsubnet.py:200):
+// their gradient is 1 / (mean + EPS) of the window.  Weight gradients: se_train_gemm_tn_det + se_train_colsum (fixed order, no
+// float atomics); input gradients: se_train_gemm (fp32-exact MFMA).
+
+namespace {
+
+int fsn_train_plan(const fsn_engine *e, int B, int N, FsnTrainLayout &L) {
+    const long T = e->T, F = e->F, Hf = e->fb.H, Hs = e->sb.H, Kp = e->Kp, SI = e->SI, Fp = (F + 7) & ~7L;
+    L = FsnTrainLayout{};
+    L.B = B; L.N = N;
+    L.S[0] = (long)N * B;
+    L.S[1] = (long)N * B * F;
+    size_t off = 0;
+    auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
+    const long Hm[2] = {Hf, Hs};
+    for (int mi = 0; mi < 2; mi++)
+        for (int l = 0; l < e->NL; l++) {
+            const long S = L.S[mi], H = Hm[mi];
+            L.gates[mi][l] = take((size_t)T * S * 4 * H);
+            L.cs[mi][l] = take((size_t)(T + 1) * S * H);
+            L.hs[mi][l] = take((size_t)(T + 1) * S * H);
+        }
+    L.xs[0] = take((size_t)T * L.S[0] * Kp);
+    L.xs[1] = take((size_t)T * L.S[1] * SI);
+    L.fbo = take((size_t)T * L.S[0] * F);
+    L.denom = take((size_t)N * B);
+    const size_t sh = std::max((size_t)L.S[0] * Hf, (size_t)L.S[1] * Hs);
+    L.dg = take((size_t)T * std::max((size_t)L.S[0] * 4 * Hf, (size_t)L.S[1] * 4 * Hs));
+    L.dcf = take(sh);
+    L.dx = take((size_t)T * sh);
+    L.dm = take((size_t)T * L.S[1] * 2);
+    L.dpre = take((size_t)T * L.S[0] * Fp);
+    const size_t nw = std::max({(size_t)4 * Hf * Kp, (size_t)4 * Hf * Hf, (size_t)4 * Hs * SI, (size_t)4 * Hs * Hs, (size_t)Fp * Hf, (size_t)2 * Hs});
+    L.wsum = take(64 * nw);
+    L.csum = take((size_t)((T * L.S[1] + 63) / 64 + (T * L.S[0] + 63) / 64) * std::max({4 * Hf, 4 * Hs, Fp}));
+    L.tmp = take(nw);
+    L.total = off;
+    return 0;
+}
+
+int fsn_prepare_train(fsn_engine *e) {
+    int rc = fsn_prepare(e);
+    if (rc) return rc;
+    if (e->train_ready) return 0;
+    struct { fsn_engine::Model *m; const char *name; } models[2] = {{&e->fb, "fb_model"}, {&e->sb, "sb_model"}};
+    for (auto &mm : models) {
+        fsn_engine::Model &m = *mm.m;
+        const int H = m.H;
+        for (int l = 0; l < e->NL; l++) {
+            const std::string p = std::string(mm.name) + ".sequence_model.", s = std::to_string(l);
+            const int in = l == 0 ? m.in : H;
+            auto *wih = fparam(e, p + "weight_ih_l" + s, 4 * (size_t)H * in);
+            auto *whh = fparam(e, p + "weight_hh_l" + s, 4 * (size_t)H * H);
+            if (!wih || !whh) return SE_ERR_PARAM_MISSING;
+            std::vector<float> t((size_t)H * 4 * H);
+            for (int r = 0; r < 4 * H; r++)
+                for (int k = 0; k < H; k++) t[(size_t)k * 4 * H + r] = (*whh)[(size_t)r * H + k];
+            if ((rc = fupload(e, m.whh_t[l], t))) return rc;
+            if (l > 0) {
+                for (int r = 0; r < 4 * H; r++)
+                    for (int k = 0; k < H; k++) t[(size_t)k * 4 * H + r] = (*wih)[(size_t)r * H + k];
+                if ((rc = fupload(e, m.wih_t[l], t))) return rc;
+            } else if (&m == &e->sb) {  // the sub-band input's last column is fb_out (fb_num_neighbors = 0): the only one with a gradient
+                std::vector<float> col(4 * (size_t)H);
+                for (int r = 0; r < 4 * H; r++) col[r] = (*wih)[(size_t)r * in + in - 1];
+                if ((rc = fupload(e, m.wcol, col))) return rc;
+            }
+        }
+    }
+    const int F = e->F, Fp = (F + 7) & ~7, Hf = e->fb.H;
+    auto *fw = fparam(e, "fb_model.fc_output_layer.weight", (size_t)F * Hf);
+    if (!fw) return SE_ERR_PARAM_MISSING;
+    std::vector<float> t((size_t)Hf * Fp, 0.0f);
+    for (int f = 0; f < F; f++)
+        for (int k = 0; k < Hf; k++) t[(size_t)k * Fp + f] = (*fw)[(size_t)f * Hf + k];
+    if ((rc = fupload(e, e->fb.fcw_t, t))) return rc;
+    e->train_ready = true;
+    return 0;
+}
+
+int tchk(fsn_engine *e, int rc) { return rc ? ffail(e, rc, "%s", se_train_last_error()) : 0; }
+
+// all T steps of layer l of model mi, last step first; dG of every step stays in L.dg for the weight gradients
+int fsn_bptt(fsn_engine *e, const FsnTrainLayout &L, float *ws, int mi, int l, const float *dout, const float *dm, const float *wfc, hipStream_t st) {
+    const fsn_engine::Model &m = mi ? e->sb : e->fb;
+    const long S = L.S[mi], H = m.H, T = e->T;
+    const dim3 grid((unsigned)((H + kLbwBN - 1) / kLbwBN), (unsigned)((S + kLbwBM - 1) / kLbwBM));
+    for (long t = T - 1; t >= 0; t--) {
+        LstmBwdArgs a{};
+        a.dgn = t + 1 < T ? ws + L.dg + (t + 1) * S * 4 * H : nullptr;
+        a.whh_t = m.whh_t[l].p;
+        a.dout = dout ? dout + t * S * H : nullptr;
+        a.dm = dm ? dm + t * S * 2 : nullptr;
+        a.wfc = wfc;
+        a.gates = ws + L.gates[mi][l] + t * S * 4 * H;
+        a.cprev = ws + L.cs[mi][l] + t * S * H;
+        a.ccur = ws + L.cs[mi][l] + (t + 1) * S * H;
+        a.dcf = ws + L.dcf;
+        a.dg = ws + L.dg + t * S * 4 * H;
+        a.S = (int)S; a.H = (int)H;
+        hipLaunchKernelGGL(k_lstm_bwd_step, grid, dim3(256), 0, st, a);
+    }
+    FHIP(e, hipGetLastError());
+    return 0;
+}
+
+// out[rows][cols] (dense) = the leading block of sum_r A[r][:Na]^T X[r][:Nb]
+int fsn_wgrad(fsn_engine *e, const FsnTrainLayout &L, float *ws, const float *A, const float *X, long R, int Na, int Nb, float *out, int rows, int cols,
+              hipStream_t st) {
+    int ns = 0, rc;
+    if ((rc = tchk(e, se_train_gemm_tn_det(A, X, ws + L.wsum, &ns, R, Na, Nb, st)))) return rc;
+    if ((rc = tchk(e, se_train_colsum(ws + L.wsum, ws + L.tmp, Na * Nb, nullptr, nullptr, 0, nullptr, nullptr, 0, ns, 0, st)))) return rc;
+    FHIP(e, hipMemcpy2DAsync(out, (size_t)cols * sizeof(float), ws + L.tmp, (size_t)Nb * sizeof(float), (size_t)cols * sizeof(float), rows,
+                             hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// out1 (and out2, may be null) [n] = column sums of x [R][ld], first n columns
+int fsn_bgrad(fsn_engine *e, const FsnTrainLayout &L, float *ws, const float *x, long R, int ld, int n, float *out1, float *out2, hipStream_t st) {
+    int rc;
+    if ((rc = tchk(e, se_train_colsum_tall(x, R, ld, ws + L.csum, ws + L.tmp, 0, st)))) return rc;
+    for (float *o : {out1, out2})
+        if (o) FHIP(e, hipMemcpyAsync(o, ws + L.tmp, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fsn_train_ws_bytes(fsn_engine *e, int batch, int nseg) {
+    if (!e || batch <= 0 || nseg <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    FsnTrainLayout L;
+    fsn_train_plan(e, batch, nseg, L);
+    return (int64_t)(L.total * sizeof(float));
+}
+
+int fsn_train_fwd(fsn_engine *e, const float *spec, int batch, int nseg, int flag, void *ws, float *crm_out, void *stream) {
+    if (!e || !spec || !ws || !crm_out || batch <= 0 || nseg <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    FHIP(e, hipSetDevice(e->device));
+    int rc;
+    if (!flag) { if ((rc = fsn_reset_on(e, batch, st))) return rc; }
+    else if (e->B != batch) return ffail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
+    if ((rc = fsn_prepare(e))) return rc;
+    FsnTrainLayout L;
+    fsn_train_plan(e, batch, nseg, L);
+    const long M = e->M, T = e->T, F = e->F;
+    e->tr = &L;
+    e->tr_ws = static_cast<float *>(ws);
+    for (int n = 0; n < nseg && !rc; n++) {  // the engine's own per-window order: norm update, full band, unfold, sub band
+        e->tr_n = n;
+        const float *sp = spec + (size_t)n * batch * M * T * F * 2;
+        rc = fsn_stage_fb(e, sp, sp + 1, 2 * M * T * F, 2 * T * F, 2 * F, 2, st);
+        if (!rc) rc = fsn_stage_sb(e, sp, sp + 1, 2 * M * T * F, 2 * F, 2, crm_out + (size_t)n * batch * 2 * F * T, nullptr, 0, 0, 0, st, nullptr);
+    }
+    e->tr = nullptr;
+    e->tr_ws = nullptr;
+    return rc;
+}
+
+int fsn_train_bwd(fsn_engine *e, const float *dcrm, int batch, int nseg, void *wsp, float *const *grads, int ngrads, void *stream) {
+    if (!e || !dcrm || !wsp || !grads || batch <= 0 || nseg <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    const int NL = e->NL;
+    if (ngrads != 2 * (4 * NL + 2)) return ffail(e, SE_ERR_ARG, "expected %d gradient pointers, got %d", 2 * (4 * NL + 2), ngrads);
+    for (int i = 0; i < ngrads; i++)
+        if (!grads[i]) return ffail(e, SE_ERR_ARG, "gradient pointer %d is null", i);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    FHIP(e, hipSetDevice(e->device));
+    int rc;
+    if ((rc = fsn_prepare_train(e))) return rc;
+    FsnTrainLayout L;
+    fsn_train_plan(e, batch, nseg, L);
+    float *ws = static_cast<float *>(wsp);
+    const int B = batch, N = nseg, T = e->T, F = e->F, Fp = (F + 7) & ~7, Hf = e->fb.H, Hs = e->sb.H;
+    const long S0 = L.S[0], S1 = L.S[1], R0 = (long)T * S0, R1 = (long)T * S1;
+    float *const *gfb = grads, *const *gsb = grads + 4 * NL + 2;  // per model: (W_ih, W_hh, b_ih, b_hh) x layers, fc weight, fc bias
+
+    // sub band: Linear(H -> 2) (no activation) over the last layer, then the layers top down
+    hipLaunchKernelGGL(k_fsn_gather_dm, dim3(2048), dim3(256), 0, st, dcrm, ws + L.dm, N, B, F, T);
+    FHIP(e, hipGetLastError());
+    if ((rc = fsn_wgrad(e, L, ws, ws + L.dm, ws + L.hs[1][NL - 1] + S1 * Hs, R1, 2, Hs, gsb[4 * NL], 2, Hs, st))) return rc;
+    if ((rc = fsn_bgrad(e, L, ws, ws + L.dm, R1, 2, 2, gsb[4 * NL + 1], nullptr, st))) return rc;
+    for (int l = NL - 1; l >= 0; l--) {
+        const bool top = l == NL - 1;
+        if ((rc = fsn_bptt(e, L, ws, 1, l, top ? nullptr : ws + L.dx, top ? ws + L.dm : nullptr, e->sb.fcw.p, st))) return rc;
+        const float *dg = ws + L.dg;
+        const float *x = l == 0 ? ws + L.xs[1] : ws + L.hs[1][l - 1] + S1 * Hs;
+        const int in = l == 0 ? e->SI : Hs;
+        if ((rc = fsn_wgrad(e, L, ws, dg, x, R1, 4 * Hs, in, gsb[4 * l], 4 * Hs, in, st))) return rc;
+        if ((rc = fsn_wgrad(e, L, ws, dg, ws + L.hs[1][l], R1, 4 * Hs, Hs, gsb[4 * l + 1], 4 * Hs, Hs, st))) return rc;
+        if ((rc = fsn_bgrad(e, L, ws, dg, R1, 4 * Hs, 4 * Hs, gsb[4 * l + 2], gsb[4 * l + 3], st))) return rc;
+        if (l > 0) {
+            if ((rc = tchk(e, se_train_gemm(dg, e->sb.wih_t[l].p, nullptr, ws + L.dx, (int)R1, Hs, 4 * Hs, 0, st)))) return rc;
+        } else {  // d fb_out through the sub-band CumLayerNorm and the full-band ReLU
+            FHIP(e, hipMemsetAsync(ws + L.dpre, 0, (size_t)R0 * Fp * sizeof(float), st));
+            hipLaunchKernelGGL(k_fsn_dfb, dim3(4096), dim3(256), 0, st, dg, e->sb.wcol.p, ws + L.denom, ws + L.fbo, ws + L.dpre, N, B, F, T, 4 * Hs, Fp);
+            FHIP(e, hipGetLastError());
+        }
+    }
+    // full band: Linear(H -> F) + ReLU over the last layer, then the layers top down (the input |X| carries no gradient)
+    if ((rc = fsn_wgrad(e, L, ws, ws + L.dpre, ws + L.hs[0][NL - 1] + S0 * Hf, R0, Fp, Hf, gfb[4 * NL], F, Hf, st))) return rc;
+    if ((rc = fsn_bgrad(e, L, ws, ws + L.dpre, R0, Fp, F, gfb[4 * NL + 1], nullptr, st))) return rc;
+    if ((rc = tchk(e, se_train_gemm(ws + L.dpre, e->fb.fcw_t.p, nullptr, ws + L.dx, (int)R0, Hf, Fp, 0, st)))) return rc;
+    for (int l = NL - 1; l >= 0; l--) {
+        if ((rc = fsn_bptt(e, L, ws, 0, l, ws + L.dx, nullptr, nullptr, st))) return rc;
+        const float *dg = ws + L.dg;
+        const float *x = l == 0 ? ws + L.xs[0] : ws + L.hs[0][l - 1] + S0 * Hf;
+        const int ld = l == 0 ? e->Kp : Hf, in = l == 0 ? e->fb.in : Hf;
+        if ((rc = fsn_wgrad(e, L, ws, dg, x, R0, 4 * Hf, ld, gfb[4 * l], 4 * Hf, in, st))) return rc;
+        if ((rc = fsn_wgrad(e, L, ws, dg, ws + L.hs[0][l], R0, 4 * Hf, Hf, gfb[4 * l + 1], 4 * Hf, Hf, st))) return rc;
+        if ((rc = fsn_bgrad(e, L, ws, dg, R0, 4 * Hf, 4 * Hf, gfb[4 * l + 2], gfb[4 * l + 3], st))) return rc;
+        if (l > 0 && (rc = tchk(e, se_train_gemm(dg, e->fb.wih_t[l].p, nullptr, ws + L.dx, (int)R0, Hf, 4 * Hf, 0, st)))) return rc;
+    }
+    return SE_OK;
+}
+
+}  // extern "C"

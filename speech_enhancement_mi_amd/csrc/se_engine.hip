@@ -2159,3 +2159,4 @@ int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap,
 
 #include "fsn_engine.inc.h"
 #include "train_ops.inc.h"
+#include "fsn_train.inc.h"

@@ -21,7 +21,7 @@ EXPORTS = [
     "se_realtime_process", "se_realtime_process_ragged", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
     "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
-    "fsn_read_tap", "fsn_flops_per_frame", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
+    "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
     "se_train_last_error", "se_train_conv_layout_query", "se_train_conv", "se_train_conv_wgrad", "se_train_gemm", "se_train_gemm_tn", "se_train_gru_step",
     "se_train_gru_bwd_gates", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd",
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
@@ -101,6 +101,10 @@ def load_library():
     L.fsn_read_tap.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
     L.fsn_flops_per_frame.argtypes = [vp]
     L.fsn_flops_per_frame.restype = C.c_double
+    L.fsn_train_ws_bytes.argtypes = [vp, C.c_int, C.c_int]
+    L.fsn_train_ws_bytes.restype = C.c_int64
+    L.fsn_train_fwd.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, vp, fp, vp]
+    L.fsn_train_bwd.argtypes = [vp, fp, C.c_int, C.c_int, vp, C.POINTER(vp), C.c_int, vp]
     L.se_loss_sisnr_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp]
     L.se_loss_stoi_ws_floats.argtypes = [C.c_int, C.c_int64]
     L.se_loss_stoi_ws_floats.restype = C.c_int64
@@ -427,3 +431,24 @@ class FsnEngine:
     @property
     def flops_per_frame(self):
         return float(self.lib.fsn_flops_per_frame(self._h))
+
+    # ---- training (fsn_train_*): device tensors, enqueued on the current stream ----
+    def train_ws_bytes(self, batch, nseg):
+        n = int(self.lib.fsn_train_ws_bytes(self._h, int(batch), int(nseg)))
+        self._check(0 if n > 0 else n)
+        return n
+
+    def train_fwd(self, spec, batch, nseg, flag, ws):
+        """spec [nseg, batch*M, T, F, 2] (se_sig_stft) -> crm [nseg, batch, 2, F, T]; activations saved into ws (uint8 device tensor)."""
+        import torch
+        crm = torch.empty((nseg, batch, 2, self.F, self.T), dtype=torch.float32, device=spec.device)
+        self._check(self.lib.fsn_train_fwd(self._h, Engine._dev(spec, (nseg, batch * self.M, self.T, self.F, 2)), int(batch), int(nseg), int(bool(flag)),
+                                           C.c_void_p(ws.data_ptr()), Engine._dev(crm), Engine._stream()))
+        self.batch = int(batch)
+        return crm
+
+    def train_bwd(self, dcrm, batch, nseg, ws, grads):
+        """dcrm [nseg, batch, 2, F, T] -> writes every parameter gradient into `grads` (device tensors, state_dict order)."""
+        ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        self._check(self.lib.fsn_train_bwd(self._h, Engine._dev(dcrm, (nseg, batch, 2, self.F, self.T)), int(batch), int(nseg), C.c_void_p(ws.data_ptr()),
+                                           ptrs, len(grads), Engine._stream()))

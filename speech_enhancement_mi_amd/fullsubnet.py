@@ -7,7 +7,9 @@ Compute runs on the MI355X engine through the fsn_* / se_sig_* C ABI; the torch 
   * train=True (fullsubnet.py:921-927): ONE forward over all N*T frames of the chunk (one CumLayerNorm update, the LSTMs run
     through the N*T frames without a per-window seam), then mask / iSTFT / over_add per window; returns the reference's
     4-tuple `(pred_source, pred_crm [N,B,2,F,T], s [N,B,2,F,T], x [N,B,2,F,T])`.  Forward only: the tensors carry no
-    autograd graph (no LSTM backward kernels exist; FullSubNet training is outside SURVEY.md 8's rows)."""
+    autograd graph.
+Training (what train_fullsubnet.py:137-145 differentiates, realtime_process(train=False)): fsn_training.TrainableFullSubNet, the same
+model with a differentiable `pred_source` (LSTM backward kernels: fsn_train_fwd / fsn_train_bwd)."""
 from __future__ import annotations
 
 import torch
