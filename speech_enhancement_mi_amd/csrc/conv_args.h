@@ -30,9 +30,6 @@ struct ConvArgs {
     int CC, nchunk, tiles_per_wg, St;
     int relu_lo, relu_hi;  // GEMM rows in [relu_lo, relu_hi) get the activation `act`
     int act;               // 1 = ReLU (CRN.py), 2 = ELU (CRN_ELU.py:226,280)
-    // gate_pairs: GEMM rows (2c, 2c+1) hold conv_trans_c and conv_gated_c of the gated 1x1 pair
-    // (CRN_ELU.py:240: out = conv_trans(out) * sigmoid(conv_gated(out))); the epilogue writes channel c = trans * sigmoid(gated)
-    int gate_pairs;
     int Cy, cy0;           // channels of y per stream and channel offset of this launch (row -> channel cy0 + row[/2])
     // par_rows: GEMM rows (2c, 2c+1) are the EVEN and ODD output-frequency parity of channel c of a transposed convolution
     // whose two tap sets were merged into one launch (weights are zero where a parity does not use a tap): row 2c+p is
@@ -47,16 +44,6 @@ struct ConvArgs {
     // follows every block (CRN.py:135-149); nullptr = off.  One slot per workgroup -> deterministic.
     float *stats;
     int stats_nslot, stats_slot0, stats_lo, stats_hi;
-    // Decoder skip gate fused into the 1x1 skip convolution (k_conv_x6 only; CRN.py:387-396).  GEMM rows (2c, 2c+1) hold
-    // residualmask_c and residual_c of the skip tensor; the epilogue writes
-    //     out_c = m * act(residual_c) + (1 - m) * pad(gLN(ydec_c)),   m = sigmoid(gLN(residualmask_c))
-    // where the statistics of residualmask come from a stats-only pass of the same convolution (y == nullptr) and those
-    // of ydec (the transposed convolution of this block) from its epilogue partials.  blend == 0: off.
-    int blend;
-    const float *bl_ydec;                    // [B][Cy][T][bl_Fo]
-    const float *bl_nw, *bl_nb, *bl_mnw, *bl_mnb;  // [Cy] norm / residualnorm affine
-    SlabStats bl_sy, bl_su;
-    int bl_Fo;
 };
 
 constexpr int kPatchPerThread = 16;   // patch elements staged per thread per chunk  (chunk patch <= 4096 floats)
@@ -67,9 +54,6 @@ constexpr int kX6PosPerThread = 4;  // (patch position, octet) items per thread:
 struct ConvX6Args {
     ConvArgs c;        // geometry, x / xprev / bias / y / stats exactly as for k_conv_igemm (c.w unused, c.CC == 8)
     const uint4 *wx;   // [nchunk][nstep][3][MT][64] fragments of 16 B
-#ifdef SE_X6_TRACE
-    int trace_slot;
-#endif
 };
 
 }  // namespace se

@@ -30,13 +30,6 @@ __device__ __forceinline__ uint4 pack_bf16x8(const __bf16 (&v)[8]) {
     return __builtin_bit_cast(uint4, t);
 }
 
-#ifdef SE_X6_TRACE
-__device__ unsigned long long g_x6_trace[16];
-#define X6T(i) do { const unsigned long long _n = __builtin_readcyclecounter(); if (tid == 0) tr[i] += _n - tlast; tlast = _n; } while (0)
-#else
-#define X6T(i)
-#endif
-
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // PL = operand planes: 3 = fp32-accurate bf16x6 (six cross terms per product); 2 = bf16x3 (hi, mid planes; three cross terms
@@ -51,13 +44,6 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void k_conv_x6(ConvX6Args xa)
     constexpr int NPAIR = (NTAP * CO + 1) / 2;  // K steps per chunk
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y;
-    BlendStats bs{0.f, 1.f, 0.f, 1.f};
-    if (NTAP == 1 && a.blend) {  // fused decoder skip gate: this stream's norm statistics (LDS is still free)
-        float *sm = reinterpret_cast<float *>(planes);
-        slab_mean_inv(a.bl_sy, b, sm, bs.my, bs.iy);
-        slab_mean_inv(a.bl_su, b, sm + 2, bs.mu, bs.iu);
-        __syncthreads();
-    }
     const int P = a.T * a.FP;
     const int p0 = blockIdx.x * a.tiles_per_wg * 32;
     if (p0 >= P) return;
@@ -133,11 +119,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void k_conv_x6(ConvX6Args xa)
     const uint4 *wxw = xa.wx + (long)mt * 64 + l31 * 2 + half;  // + (((ch*NPAIR + pr)*3 + plane)*MT) * 64
     const long wx_plane = (long)MT * 64, wx_pair = PL * wx_plane, wx_chunk = NPAIR * wx_pair;
 
-#ifdef SE_X6_TRACE
-    unsigned long long tr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     for (int ch = 0; ch < a.nchunk; ch++) {
-        X6T(0);
         // The weight fragments of the chunk's first K step are requested before the staging phase where registers allow
         // (<= 9 taps), which hides their latency: requested after the second barrier they cost 6-13 k exposed cycles per
         // workgroup (phase trace); the 15-tap instances are at the register limit and spill when the request moves up.
@@ -149,11 +131,6 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void k_conv_x6(ConvX6Args xa)
             for (int p = 0; p < PL; p++) fa_n[p] = wc[p * wx_plane];
         }
         __syncthreads();  // previous chunk fully consumed
-        X6T(1);
-#ifdef SE_X6_TRACE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        X6T(2);
-#endif
 #pragma unroll
         for (int k = 0; k < kX6PosPerThread; k++) {
             const int item = tid + 256 * k;
@@ -175,17 +152,11 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void k_conv_x6(ConvX6Args xa)
                 }
             }
         }
-        X6T(3);
         __syncthreads();
-        X6T(4);
         if (!kEarlyA) {
 #pragma unroll
             for (int p = 0; p < PL; p++) fa_n[p] = wc[p * wx_plane];
         }
-#ifdef SE_X6_TRACE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        X6T(5);
-#endif
 #pragma unroll
         for (int pr = 0; pr < NPAIR; pr++) {
             uint4 fa[PL];
@@ -223,35 +194,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void k_conv_x6(ConvX6Args xa)
             }
         }
     }
-    X6T(0);
     __syncthreads();
-    X6T(1);
-#ifdef SE_X6_TRACE
-    {
-        int pos_t[NT], pos_m[NT];
-        bool lane_ok[NT];
-#pragma unroll
-        for (int i = 0; i < NT; i++) {
-            const int p = p0 + (cg + i * NCG) * 32 + l31;
-            lane_ok[i] = p < p1;
-            const int pc = lane_ok[i] ? p : (p1 - 1);
-            pos_t[i] = pc / a.FP;
-            pos_m[i] = pc - pos_t[i] * a.FP;
-        }
-        ConvArgs a2 = a;
-        a2.stats = nullptr;
-        conv_epilogue<NT>(a2, acc, lane_ok, pos_t, pos_m, mt, half, reinterpret_cast<float *>(planes), b, NTAP == 1 ? &bs : nullptr);
-        X6T(6);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        X6T(7);
-        if (a.stats) conv_stats_store(a, 0.f, 0.f, reinterpret_cast<float *>(planes), b);
-        X6T(8);
-    }
-    if (tid == 0 && xa.trace_slot >= 0) {
-        for (int i = 0; i < 9; i++) atomicAdd(&g_x6_trace[i], tr[i]);
-        atomicAdd(&g_x6_trace[15], 1ull);
-    }
-#else
     int pos_t[NT], pos_m[NT];
     bool lane_ok[NT];
 #pragma unroll
@@ -262,8 +205,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 3 : 2) void k_conv_x6(ConvX6Args xa)
         pos_t[i] = pc / a.FP;
         pos_m[i] = pc - pos_t[i] * a.FP;
     }
-    conv_epilogue<NT>(a, acc, lane_ok, pos_t, pos_m, mt, half, reinterpret_cast<float *>(planes), b, NTAP == 1 ? &bs : nullptr);
-#endif
+    conv_epilogue<NT>(a, acc, lane_ok, pos_t, pos_m, mt, half, reinterpret_cast<float *>(planes), b);
 }
 
 }  // namespace se

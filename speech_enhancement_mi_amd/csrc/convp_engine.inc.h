@@ -113,7 +113,7 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
     ConvPArgs &a = pl.a;
     a.C8 = C8; a.Ci = Ci; a.Co = Co; a.CoPad = CoPad; a.T = T; a.Fi = Fi; a.FP = FP;
     a.s = s; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.ntap = ntap;
-    a.deint = (s == 2 && e->convp_deint) ? 1 : 0;
+    a.deint = s == 2 ? 1 : 0;
     a.Sh = (St + 1) / 2;
     for (int t = 0; t < ntap; t++) {
         a.rowgrp[t] = taps[t][2];
@@ -252,15 +252,6 @@ void free_state_p(se_engine *e) {
     dev_free(S.preR);
     delete e->cp;
     e->cp = nullptr;
-}
-
-bool convp_supported(const se_engine *e) {
-    // (CRN_ELU / student: the three 5-channel pre-conv blocks stay on their fp32 vector-ALU kernel and hand over to the plane
-    //  path with one conversion; the gated 1x1 pair of every encoder block is a k_conv_p epilogue, kPOutGate)
-    if (e->variant && e->Ch[0] > 8) return false;
-    for (int i = 0; i <= e->L; i++)
-        if (e->Ch[i] > 128) return false;
-    return true;
 }
 
 int prepare_weights_p(se_engine *e) {
@@ -416,7 +407,7 @@ int prepare_weights_p(se_engine *e) {
                 if (!mnw || !mnb || !nw || !nb) return SE_ERR_PARAM_MISSING;
                 SkipPPlan &sk = pv.sk;
                 const int PL = operand_planes(e->precision), C8 = (Co + 7) / 8, MTh = (Co + 31) / 32, KP = (C8 + 1) / 2, Cp = MTh * 32;
-                sk.active = e->skip_stream != 0 && MTh <= 2 && (KP == 1 || KP == 2 || KP == 4);
+                sk.active = MTh <= 2 && (KP == 1 || KP == 2 || KP == 4);
                 if (sk.active) {
                     std::vector<uint16_t> wx((size_t)2 * MTh * KP * PL * 32 * 16, 0);
                     for (int m2 = 0; m2 < 2 * MTh; m2++)
@@ -498,7 +489,7 @@ int alloc_state_p(se_engine *e, hipStream_t st) {
         HIPCHECK(e, hipMemsetAsync(S.decR[j].p, 0, nR * sizeof(float), st));
         if (lvl > 0 && (rc = dev_alloc(e, S.decP[j], (size_t)B * ((Co + 7) / 8) * PL * T * e->F[lvl] * 4))) return rc;
     }
-    // statistics slabs are shared with the first-generation path; make sure they hold the new grids
+    // statistics slabs of the norms (se_engine::enc_stats / dec_stats / skip_stats): one slot per workgroup of this batch's grids
     for (int i = 0; i < L; i++) {
         PLevel &pv = S.pv[i];
         if ((rc = dev_alloc(e, e->enc_stats[i], (size_t)B * 2 * (pv.enc.grid_x + (pv.gate[0].active ? pv.gate[0].grid_x : 0) + (pv.gate[1].active ? pv.gate[1].grid_x : 0) + 1)))) return rc;
@@ -545,7 +536,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
             launch_k_gln_p(PL, dim3((TF + 1023) / 1024, 1, Ba), st, g);
             HIPCHECK(e, hipGetLastError());
         }
-    } else if (e->variant) {  // the same blocks on their fp32 vector-ALU kernel (first generation), then one conversion into the P layout
+    } else if (e->variant) {  // the same blocks on their fp32 vector-ALU kernel (stage_features_pre), then one conversion into the P layout
         if ((rc = stage_features_pre(e, cur, spec, sB, sM, sT, sF, st))) return rc;
         ProfScope ps(e, "k_f32_to_p", "feat_to_p", 0, st);
         const int TF = T * e->F[0];
@@ -604,7 +595,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
             g.y = reinterpret_cast<uint4 *>(e->gruinP[cur].p);
             g.y_plane = (long)B * T * g.C8 * Fo;
             launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g);
-        } else {  // last level feeds the fp32 GEMM of the bottleneck: [T][C*F] rows (gln_ew mode 1 of the first generation)
+        } else {  // last level feeds the fp32 GEMM of the bottleneck (launch_gemm): [T][C*F] rows
             GlnEwArgs ge{nullptr, e->gru_in[cur].p, g.w, g.b, g.st, 3, Co, T, Fo, nullptr};
             ge.x = S.encR[i].p;
             const long n = (long)Co * T * Fo;
@@ -643,8 +634,8 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
             const uint4 *res = reinterpret_cast<const uint4 *>(S.xinP[lvl].p);
             const unsigned res_bytes = (unsigned)((size_t)S.slot_elems[lvl] * kRing * 16);
             // one workgroup per stream: below ~100 streams most CUs would idle, the two k_conv_p launches (statistics, gate) spread
-            // over positions instead (B = 1: 24 vs 45 us per level).  SE_SKIP_STREAM=2 keeps the streaming kernel at any batch.
-            if (pv.sk.active && (B >= e->skip_min_batch || e->skip_stream == 2)) {
+            // over positions instead (B = 1: 24 vs 45 us per level).  SE_SKIP_MIN_BATCH moves the crossover.
+            if (pv.sk.active && B >= e->skip_min_batch) {
                 SkipPArgs a = pv.sk.a;
                 a.x = res + (long)cur * S.slot_elems[lvl];
                 a.ydec = S.decR[j].p;

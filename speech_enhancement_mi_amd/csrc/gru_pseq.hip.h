@@ -307,7 +307,6 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
                 for (int r = 0; r < 4; r++) {
                     const int row = mt * 16 + kq * 4 + r;
                     if (row >= B) continue;
-                    const long ro = pseq_row(row, s, a.Tseg, a.ldN, a.ldB);
                     const int u = u0 + l15;
                     float dh = pin[mt][r][0];
                     if (!cut) dh += dhz[mt][r] + gown[mt][r];

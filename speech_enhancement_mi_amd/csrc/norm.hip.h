@@ -4,15 +4,10 @@
 // over every non-batch element (two passes, like the reference), y = (x - mu) / (sqrt(var + 1e-8) + 1e-8) * w + b.
 // One workgroup (1024 threads = 16 wavefronts) owns one stream's tensor (<= ~180 KB, L2 resident after
 // the first pass); reductions are wavefront shuffles + one LDS hop, combined in double.
-// Fused variants:
+// Fused variants (fp32 layout; the plane path's norms are in conv_p.hip.h):
 //   k_featurize  - |X|, arctan phase differences (CRN.py:463-467)
-//   k_gln           - exact two-pass norm + affine + re-layout, one workgroup per stream (used for the FC output, whose
-//                     producer is a GEMM without per-stream partial statistics)
-//   k_gln_ew        - norm + affine (+ residual add, + re-layout) from the producing conv's partial statistics
-//   k_dec_blend_ew  - decoder skip gate: m = sigmoid(gLN(conv_mask(res))), out = m*act(conv_res(res)) + (1-m)*pad(gLN(y))
-//                     (CRN.py:387-396)
-//   k_final_mask_ew - gLN of the last decoder block, decompress_cIRM (utility.py:439-442), complex multiply
-//                     with the mic-0 spectrum (CRN.py:491-495)
+//   k_gln_ew     - norm + affine (+ residual add, + re-layout) from the producing conv's partial statistics
+//   k_gln_r2t    - the same from the plane path's R layout into the bottleneck GEMM's [T][C*F] rows
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fft_lds.h"
@@ -79,47 +74,6 @@ __global__ void k_featurize(FeatArgs a) {
         const float ang = a.atan2_phase ? atan2f(v.y, v.x) : atanf(v.y / (v.x + kEps) + kEps);
         if (m == 0) ang0 = ang;
         else o[(long)(a.M + m - 1) * TF] = ang0 - ang;
-    }
-}
-
-#endif  // norm kernels
-
-// ---- gLN with optional re-layout ---------------------------------------------------------------
-struct GlnArgs {
-    const float *x;  // per stream n contiguous floats
-    float *y;
-    const float *w, *b;
-    long n;
-    int mode;  // 0: [C][T][F] -> same, affine per C | 1: [C][T][F] -> [T][C*F], affine per C
-               // 2: [T][D=C*F] -> [C][T][F], affine per D (GlobalLayerNorm(last=True), CRN.py:127-129)
-    int C, T, F;
-    int eps_mode;
-};
-
-#if !defined(SE_AUX_KERNELS) && !defined(SE_NO_NORM_KERNELS)
-__global__ __launch_bounds__(1024) void k_gln(GlnArgs a) {
-    __shared__ double red[16];
-    const float *x = a.x + (long)blockIdx.x * a.n;
-    float *y = a.y + (long)blockIdx.x * a.n;
-    float mean, inv;
-    stream_stats(x, a.n, red, mean, inv, a.eps_mode);
-    const int TF = a.T * a.F, F = a.F, T = a.T, C = a.C;
-    if (a.mode == 0) {
-        for (long i = threadIdx.x; i < a.n; i += blockDim.x) {
-            const int c = (int)(i / TF);
-            y[i] = (x[i] - mean) * inv * a.w[c] + a.b[c];
-        }
-    } else if (a.mode == 1) {
-        for (long i = threadIdx.x; i < a.n; i += blockDim.x) {
-            const int c = (int)(i / TF), r = (int)(i - (long)c * TF), t = r / F, f = r - t * F;
-            y[((long)t * C + c) * F + f] = (x[i] - mean) * inv * a.w[c] + a.b[c];
-        }
-    } else {
-        const int D = C * F;
-        for (long i = threadIdx.x; i < a.n; i += blockDim.x) {
-            const int t = (int)(i / D), d = (int)(i - (long)t * D), c = d / F, f = d - c * F;
-            y[((long)c * T + t) * F + f] = (x[i] - mean) * inv * a.w[d] + a.b[d];
-        }
     }
 }
 
@@ -242,81 +196,5 @@ __global__ __launch_bounds__(256) void k_gln_r2t(GlnEwArgs a, long x_stream) {
     }
 }
 #endif  // norm kernels
-
-struct BlendEwArgs {
-    const float *y, *uv;
-    float *out;
-    const float *nw, *nb, *mnw, *mnb;
-    SlabStats sy, su;
-    int Co, T, Fo, Fr;
-};
-
-#if !defined(SE_AUX_KERNELS) && !defined(SE_NO_NORM_KERNELS)
-__global__ __launch_bounds__(256) void k_dec_blend_ew(BlendEwArgs a) {
-    __shared__ float sm[4];
-    const int b = blockIdx.y;
-    float my, iy, mu, iu;
-    slab_mean_inv(a.sy, b, sm, my, iy);
-    slab_mean_inv(a.su, b, sm + 2, mu, iu);
-    const long ny = (long)a.Co * a.T * a.Fo, nu = (long)a.Co * a.T * a.Fr;
-    const float *y = a.y + b * ny;
-    const float *u = a.uv + (long)b * 2 * nu;
-    const float *v = u + nu;
-    float *o = a.out + b * nu;
-    const int TFr = a.T * a.Fr;
-    const float invTFr = 1.0f / (float)TFr, invFr = 1.0f / (float)a.Fr;
-    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < nu; i += (long)gridDim.x * blockDim.x * 4) {
-        const float4 u4 = *reinterpret_cast<const float4 *>(u + i);
-        const float4 v4 = *reinterpret_cast<const float4 *>(v + i);
-        const float uu[4] = {u4.x, u4.y, u4.z, u4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-        float r4[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            int c = min((int)(((float)(i + k) + 0.5f) * invTFr), a.Co - 1);
-            const int r = (int)(i + k) - c * TFr;
-            int t = min((int)(((float)r + 0.5f) * invFr), a.T - 1);
-            const int f = r - t * a.Fr;
-            const float yv = f < a.Fo ? (y[((long)c * a.T + t) * a.Fo + f] - my) * iy * a.nw[c] + a.nb[c] : 0.0f;
-            const float un = (uu[k] - mu) * iu * a.mnw[c] + a.mnb[c];
-            const float m = 1.0f / (1.0f + expf(-un));
-            r4[k] = m * vv[k] + (1.0f - m) * yv;
-        }
-        *reinterpret_cast<float4 *>(o + i) = make_float4(r4[0], r4[1], r4[2], r4[3]);
-    }
-}
-
-#endif  // norm kernels
-
-struct MaskEwArgs {
-    const float *y;
-    const float *nw, *nb;
-    SlabStats st;
-    const cf2 *spec;
-    long sB, sT, sF;
-    cf2 *out;
-    long oB, oT, oF;
-    int T, F;
-};
-
-void launch_k_final_mask_ew(dim3 grid, hipStream_t st, const MaskEwArgs &a);  // defined in se_aux.hip
-
-#ifdef SE_AUX_KERNELS
-__global__ __launch_bounds__(256) void k_final_mask_ew(MaskEwArgs a) {
-    __shared__ float sm[2];
-    const int b = blockIdx.y;
-    float mean, inv;
-    slab_mean_inv(a.st, b, sm, mean, inv);
-    const int TF = a.T * a.F;
-    const float *y = a.y + (long)b * 2 * TF;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < TF; i += gridDim.x * blockDim.x) {
-        const int t = i / a.F, f = i - t * a.F;
-        const float mr = decompress_cirm((y[i] - mean) * inv * a.nw[0] + a.nb[0]);
-        const float mi = decompress_cirm((y[TF + i] - mean) * inv * a.nw[1] + a.nb[1]);
-        const cf2 n = a.spec[(long)b * a.sB + (long)t * a.sT + (long)f * a.sF];
-        a.out[(long)b * a.oB + (long)t * a.oT + (long)f * a.oF] = cf2{mr * n.x - mi * n.y, mi * n.x + mr * n.y};
-    }
-}
-
-#endif  // SE_AUX_KERNELS
 
 }  // namespace se

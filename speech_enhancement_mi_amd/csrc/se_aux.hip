@@ -1,4 +1,4 @@
-// se_aux.hip - the kernels of the path that do COMPLEX arithmetic (LDS FFTs of the STFT / iSTFT, mask application),
+// se_aux.hip - the kernels of the path that do COMPLEX arithmetic (LDS FFTs of the STFT / iSTFT, FullSubNet's mask application),
 // compiled as their own translation unit with -fno-slp-vectorize.
 //
 // Why: with SLP vectorisation hipcc turns the (re, im) float pairs of these kernels into packed-FP32 VALU instructions
@@ -7,8 +7,8 @@
 // this engine's MFMA kernels launched from another stream (signal / window / twiddle tables in LDS intact,
 // a redundant re-execution of one radix-4 pass inside the kernel differs, scalar-FMA and integer LDS victims never fail,
 // plain op_sel_hi-only packed ops as in k_conv_small never failed either).  Built without SLP the same kernels contain
-// no packed-FP32 instruction, cost the same time (STFT 56 vs 57 us) and are exact under co-execution
-// (tests/manual_coexec_fft.py: 0 of 800 launches differ).
+// no packed-FP32 instruction, cost the same time (STFT 56 vs 57 us) and are exact under co-execution (0 of 800 launches
+// differed; tests/test_gpu_parity.py::test_fft_kernels_exact_under_coexecution and tests/test_isa_inventory.py keep it so).
 #include <hip/hip_runtime.h>
 #define SE_AUX_KERNELS 1
 #include "fft_lds.h"
@@ -25,8 +25,6 @@ void launch_k_istft(dim3 grid, size_t lds, hipStream_t st, const IstftArgs &a) {
 void launch_k_overlap_avg(dim3 grid, hipStream_t st, const float *yseg, float *out, int Nseg, int K, long L, long skip, const long *Lrow) {
     hipLaunchKernelGGL(k_overlap_avg, grid, dim3(256), 0, st, yseg, out, Nseg, K, L, skip, Lrow);
 }
-
-void launch_k_final_mask_ew(dim3 grid, hipStream_t st, const MaskEwArgs &a) { hipLaunchKernelGGL(k_final_mask_ew, grid, dim3(256), 0, st, a); }
 
 void launch_k_fsn_mask(dim3 grid, hipStream_t st, const FsnMaskArgs &a) { hipLaunchKernelGGL(k_fsn_mask, grid, dim3(256), 0, st, a); }
 

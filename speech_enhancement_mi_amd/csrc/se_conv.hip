@@ -11,16 +11,16 @@
 
 namespace se {
 
-int conv_x6_launch_pl1(int ntap, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
-int conv_x6_launch_pl2(int ntap, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
-int conv_x6_launch_pl3(int ntap, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
+int conv_x6_launch_pl1(int ntap, int NT, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
+int conv_x6_launch_pl2(int ntap, int NT, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
+int conv_x6_launch_pl3(int ntap, int NT, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
 void conv_x6_set_attributes_pl1();
 void conv_x6_set_attributes_pl2();
 void conv_x6_set_attributes_pl3();
 
-int conv_x6_launch(int ntap, int NT, int CO, int PL, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa) {
-    return PL == 1 ? conv_x6_launch_pl1(ntap, NT, CO, grid, lds, st, xa)
-                   : (PL == 2 ? conv_x6_launch_pl2(ntap, NT, CO, grid, lds, st, xa) : conv_x6_launch_pl3(ntap, NT, CO, grid, lds, st, xa));
+int conv_x6_launch(int ntap, int NT, int PL, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa) {
+    return PL == 1 ? conv_x6_launch_pl1(ntap, NT, grid, lds, st, xa)
+                   : (PL == 2 ? conv_x6_launch_pl2(ntap, NT, grid, lds, st, xa) : conv_x6_launch_pl3(ntap, NT, grid, lds, st, xa));
 }
 
 int conv_igemm_launch(int ntap, int NT, int CoPad, dim3 grid, size_t lds, hipStream_t st, const ConvArgs &a) {

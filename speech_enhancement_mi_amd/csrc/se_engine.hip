@@ -1,14 +1,16 @@
 // se_engine.hip - persistent stream-batch engine behind the C ABI of include/se_engine.h.
 //
 // One engine owns, on one MI355X: all weights (re-laid-out once for the kernels), all per-stream
-// state for B streams (ping-pong activation tensors that double as the reference's conv time buffers,
+// state for B streams (ring slots of activation tensors that double as the reference's conv time buffers,
 // GRU hidden state) and a fixed kernel sequence that advances every stream by one K-sample window:
 //
-//   k_stft -> k_featurize -> 4x (k_conv_igemm + k_gln) -> 2x (k_gemm_tn + T x k_gru_step) -> k_gemm_tn
-//   -> k_gln -> 4x (k_conv_igemm even/odd [+ 1x1 skip GEMM + k_dec_blend]) -> k_final_mask -> k_istft
+//   k_stft -> [CRN_ELU / student: 3x pre-conv block] -> encoder and decoder on the plane path (convp_engine.inc.h:
+//   k_conv_p, k_gln_p, k_skip_p, k_final_mask_p) around the bottleneck (GEMMs + T x k_gru_step per layer) -> k_istft
 //
-// Reference: TemporalCRN.forward / realtime_process (CRN.py:454-496, 560-589).  No CPU fallback exists:
-// every entry point fails with SE_ERR_HIP if the device path is unavailable.
+// k_conv_x6 / k_conv_igemm / k_conv_small (plan_conv, launch_conv) run the student's feature-tap re-runs, the
+// fp32 / bf16x3 pre-conv blocks and (k_conv_igemm) the training path; k_gemm_x / k_gemm_tn are the bottleneck GEMMs where
+// the plane GEMM k_gemm_p does not apply.  Reference: TemporalCRN.forward / realtime_process (CRN.py:454-496, 560-589).
+// No CPU fallback exists: every entry point fails with SE_ERR_HIP if the device path is unavailable.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -54,7 +56,6 @@ struct ConvPlan {
     DevBuf w, bias;
     bool active = false;
     bool x6 = false;  // bf16x6 kernel (k_conv_x6) instead of the fp32-MFMA k_conv_igemm
-    int CO = 1;       // k_conv_x6: channel octets staged per chunk
     DevBuf wx;
     DevBuf gatew;     // k_conv_small: fused gated 1x1 pair weights
     // k_conv_x6 tilings that fit (index = tiles per wave - 1); the weights do not depend on the tiling, so the one that
@@ -64,11 +65,8 @@ struct ConvPlan {
 };
 
 struct Level {  // one encoder/decoder level
-    ConvPlan enc;
-    ConvPlan dec_even, dec_odd, skip;
-    ConvPlan skipm;        // fused skip gate: statistics-only pass of the residualmask convolution
-    bool skip_fused = false;
-    ConvPlan gate[2];      // CRN_ELU encoder: conv_trans/conv_gated 1x1 pair, <= 64 output channels per launch
+    ConvPlan enc;          // feature tap ft0 re-runs lv[L-1].enc
+    ConvPlan dec_even, dec_odd;  // feature taps ft2.. re-run decoder blocks
     ConvPlan pre;          // CRN_ELU preconv block i (levels 0..2): 5x5 frequency-dilated conv with the gated pair fused in
     DevBuf enc_nw, enc_nb, dec_nw, dec_nb, dec_mnw, dec_mnb, pre_nw, pre_nb;
 };
@@ -85,12 +83,8 @@ struct se_engine {
     std::map<std::string, std::vector<float>> params;  // host copies by canonical key
     std::map<std::string, std::vector<int64_t>> shapes;
     bool weights_ready = false;
-    size_t conv_lds_budget = 48 * 1024;
     int gru_direct = -1;      // SE_GRU_DIRECT: 1 = always k_gru_step (W_hh streamed from L2), 0 = always k_gru_step2 (LDS slice),
                               // default -1 = k_gru_step in the overlapped (pipelined) bottleneck stage, k_gru_step2 otherwise
-    int gru_seq = 0;          // SE_GRU_SEQ=1: one launch per layer (k_gru_seq, in-launch hand-off between steps) instead of one per
-                              // time step (k_gru_step2).  Measured SLOWER on MI355X (17 us vs 13.5 us per step at B=256): off by default
-    DevBuf gru_sync;          // [0,64) group counters, [64] timeout word of k_gru_seq
 
     // constant tables
     DevBuf window, env, tw;
@@ -100,38 +94,30 @@ struct se_engine {
     Level lv[SE_MAX_LEVELS];  // enc i at lv[i]; decoder j at lv[j] (dec_* members)
     DevBuf wih[4], whh[4], bih[4], bhh[4], fcw, fcb, gnw, gnb;
     DevBuf wih_x[4], fcw_x;  // bf16x3 planes [3][N][K] of the GEMM weights (k_gemm_bf16x6)
-    int gemm_mode = 6;        // SE_GEMM_MODE: 0 = fp32 MFMA (k_gemm_tn), 6 = bf16x6 (default)
     int variant = 0, act = 1, eps_mode = 0, atan2_phase = 0, npre = 0;  // derived from se_config.variant
     int precision = 0;        // se_config.precision: 0 = bf16x6 (3 operand planes), 1 = fp16 operands (1 plane), 2 = bf16x3 (2 planes)
     int num_cu = 256;         // compute units of the device (MI355X: 256)
-    int dec_merge = 1;        // SE_DEC_MERGE=0: narrow decoder blocks as two parity launches like the wide ones
-    int skip_fuse = 1;        // SE_SKIP_FUSE=0: skip convolution writes both tensors, k_dec_blend_ew applies the gate
-    int conv_small16 = 1;     // SE_CONV_SMALL16=0: first encoder block on k_conv_igemm instead of the vector-ALU kernel
-    int conv_geo_fixed = 0;   // SE_CONV_GEO_FIXED=1: always the largest k_conv_x6 tiling (no per-batch selection)
-    int conv_mode = 6;        // SE_CONV_MODE: 0 = fp32 MFMA (k_conv_igemm), 6 = bf16x6 where Cin % 8 == 0 (default)
 
     // state + activations for B streams
     int B = 0;
     int parity = 0;  // index of the "current" half of the encoder-private ping-pong buffers (pin)
     // Buffers that cross the three stages of a segment (encoder -> recurrent bottleneck -> decoder) live in a ring of
     // kRing slots, so that in se_realtime_process the encoder of segment n+1.. can run on its own HIP stream while the
-    // latency-bound GRU recurrence of segment n and the decoder of segment n-1 are still in flight.  slot = segment % kRing;
-    // xin[i][slot-1] doubles as the causal time history of the level-i convolution (CRN.py:333-334).
+    // latency-bound GRU recurrence of segment n and the decoder of segment n-1 are still in flight.  slot = segment % kRing.
+    // The plane path's activation rings are in se_convp_state; the fp32 tensors here are the output of the vector-ALU pre-conv
+    // blocks (xin[0]), the fp32 GRU input (gru_in) and the operands of the feature-tap re-runs (xin, dec_in, dec_out).
     int slot = 0;
     DevBuf spec[kRing], maskspec;
     DevBuf spec_all, mask_all;         // pipelined se_realtime_process: spectra / masked spectra of one chunk of segments
     DevBuf xin[SE_MAX_LEVELS][kRing];  // encoder level inputs (xin[0] = features)
-    DevBuf enc_raw[SE_MAX_LEVELS];
     DevBuf gru_in[kRing], gi0[kRing], gil[4], seqr[4][kRing], hbuf[4][2], fc_out, dec_in[kRing];  // gi0 / seqr cross stage streams: rings
     int pipeline = 1;                  // SE_PIPELINE=0: one stream, stages back to back
     hipStream_t stage_stream[3]{};      // encoder (+ GRU input projection) / decoder (fc + norm first) / recurrence (all layers)
     hipEvent_t ev_enc[kRing]{}, ev_gru[kRing]{}, ev_dec[kRing]{}, ev_fork{}, ev_join{};
-    int gru_lag = 1;                    // SE_GRU_LAG=0: layers back to back on the recurrence stream (NL * T launches per segment)
     bool stage_ready = false;
     int hcur[4]{};
-    DevBuf dec_raw[SE_MAX_LEVELS], dec_uv[SE_MAX_LEVELS], dec_out[SE_MAX_LEVELS];
+    DevBuf dec_out[SE_MAX_LEVELS];
     DevBuf enc_stats[SE_MAX_LEVELS], dec_stats[SE_MAX_LEVELS], skip_stats[SE_MAX_LEVELS];  // [B][slots][2] norm partials
-    DevBuf enc_g[SE_MAX_LEVELS];           // CRN_ELU: gated encoder output before the norm
     DevBuf pin[3][2], pre_g, pre_stats[3];  // CRN_ELU preconv chain (inputs ping-ponged: they carry 4 history columns)
     DevBuf yseg;
     DevBuf ragged_len;       // se_realtime_process_ragged: per-stream lengths (int64) on the device
@@ -142,12 +128,10 @@ struct se_engine {
     int Bact = 0;
     int bact_slot[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // launch batch of the segment living in each ring slot (the lagged GRU rounds mix segments)
     std::vector<int> ragged_nseg;  // per stream: segments it takes part in (empty: all)
-    // second-generation convolution path (conv_p.hip.h): activations as split-bf16 planes; SE_PATH=0 selects the first generation
+    // plane-layout convolution path (conv_p.hip.h, convp_engine.inc.h): activations as split-bf16 planes
     struct se_convp_state *cp = nullptr;
-    int path = 1;
-    bool use_p = false;
-    // second-generation bottleneck GEMMs (k_gemm_p): A operands arrive as split-bf16 planes from their producers
-    bool gemm_p = false;      // decided in ensure_ready: plane path active, K dimensions multiples of 32 (SE_GEMM_P=0 disables);
+    // plane-layout bottleneck GEMMs (k_gemm_p): A operands arrive as split-bf16 planes from their producers
+    bool gemm_p = false;      // decided in ensure_ready: K dimensions multiples of 32 (SE_GEMM_P=0 disables);
                               // off for batches of <= 64 GEMM rows (se_reset), which run on the skinny fp32 kernel instead
     bool gemm_p_cap = false;
     // measured crossovers (profiles: B = 16 / 32 / 64 / 128, 512-pt): the skinny kernel wins up to 640 GEMM rows (B = 32:
@@ -155,13 +139,10 @@ struct se_engine {
     int skinny_rows = 800;    // SE_GEMM_SKINNY_ROWS: bottleneck GEMMs with up to this many rows run on the skinny fp32 kernel
     int skip_min_batch = 96;  // SE_SKIP_MIN_BATCH: the streaming skip kernel needs at least this many streams
     int gemm_p_env = 1;
-    int convp_deint = 1;      // SE_CONVP_DEINT=0: stride-2 convolutions keep interleaved LDS patch rows (2-way ds_read_b128 bank conflicts)
-    int gemm_band = 0;        // SE_GEMM_BAND: 0 (default) = banded tile->XCD map where no equal 8-block split exists, 1 = always banded, -1 = never
     DevBuf gruinP[kRing], seqP[4][kRing];  // [PL][B*T][D'] / [PL][B*T][H] bf16 planes
     DevBuf wih_xp;                          // W_ih0 planes with K in the engine's feature order (k_gemm_p)
     int dbg_skip = 0;         // SE_DBG_SKIP bit mask, TIMING EXPERIMENTS ONLY (results are wrong): 1 = no GRU step launches, 2 = no bottleneck
                               // GEMMs, 4 = no encoder convolutions, 8 = no decoder
-    int skip_stream = 1;      // SE_SKIP_STREAM=0: decoder skip gate as two k_conv_p launches instead of the streaming k_skip_p
 
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool prof_on = false;
@@ -318,8 +299,7 @@ const std::vector<float> *param(se_engine *e, const std::string &key, size_t exp
 template <class WSel>
 int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy, int s, int os, int oo, int colpad,
               int tlo_off, int ngroup, int dil, int St, const std::vector<std::array<int, 4>> &taps /*kf,kt,rowgrp,coloff*/,
-              WSel wsel, const std::vector<float> &bias, int relu_lo, int relu_hi, int act = 1, int gate_pairs = 0, int Cy = -1,
-              int cy0 = 0) {
+              WSel wsel, const std::vector<float> &bias, int relu_lo, int relu_hi, int act, int Cy = -1) {
     if (Cy < 0) Cy = Co;
     pl.a.par_rows = 0;
     pl.x6 = false;
@@ -331,13 +311,13 @@ int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy
     // vector-ALU variant: one thread per position, direct global reads, weights [tap][ci][CW] in LDS.  Also taken by the first
     // encoder block (5 -> 16 channels at full frequency resolution): K = 75 is too shallow for the matrix pipe to matter and
     // the patch halo of the MFMA kernels costs more than the arithmetic
-    if ((Co <= 8 || (Co <= 16 && Ci <= 8 && e->conv_small16)) && !gate_pairs) {
+    if (Co <= 8 || (Co <= 16 && Ci <= 8)) {
         const int CW = Co <= 4 ? 4 : (Co <= 8 ? 8 : 16);
         ConvArgs &a = pl.a;
         a.Ci = Ci; a.Co = Co; a.CoPad = CW; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
         a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = 0;
         a.ntap = ntap; a.CC = Ci; a.nchunk = 1; a.tiles_per_wg = 8; a.St = St;
-        a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.gate_pairs = 0; a.Cy = Cy; a.cy0 = cy0;
+        a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Cy; a.cy0 = 0;
         for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; }
         pl.NT = 0;  // marks the small kernel
         pl.grid_x = (P + 255) / 256;
@@ -356,44 +336,34 @@ int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy
     const int MT = CoPad / 32;
     if (MT == 3) return fail(e, SE_ERR_ARG, "conv output channels %d need 3 row tiles (unsupported)", Co);
     const int NCG = 4 / MT, NTmax = 4;
-    if (e->conv_mode == 6 && (Ci % 8 == 0 || Ci >= 5)) {  // ---- bf16x6 path: K step = 2 taps x 8 channels (Cin zero-padded to 8s) ----
-        // channel octets per chunk: 1x1 convolutions take up to 4 (32 channels) so that both halves of every K step carry
-        // real channels and a chunk holds several K steps; multi-tap convolutions already have NTAP entries per octet
-        int CO = 1;
-        if (ntap == 1) { const int oct = (Ci + 7) / 8; CO = oct >= 4 ? 4 : (oct >= 2 ? 2 : 1); }
-        if (const char *s = getenv("SE_X6_CO")) CO = std::max(1, std::min(CO, atoi(s)));
+    if (Ci % 8 == 0 || Ci >= 5) {  // ---- bf16x6 path: K step = 2 taps x 8 channels (Cin zero-padded to 8s), one octet per chunk ----
         int tpw = 0, n_wg = 0, NT = 0, Rmax = 0, grouped = 0;
-        for (; CO >= 1; CO >>= 1) {
-            for (int k = 0; k < 4; k++) pl.geo[k] = ConvPlan::Geo{};
-            NT = 0;
-            for (int ntmax = 1; ntmax <= NTmax; ntmax++) {  // ends on the largest tiling that fits = the default geometry
-                const int c_wg = (tiles + NCG * ntmax - 1) / (NCG * ntmax);
-                const int c_tpw = (tiles + c_wg - 1) / c_wg;
-                const int c_NT = (c_tpw + NCG - 1) / NCG;
-                int rows_pos = (c_tpw * 32 + FP - 1) / FP + 1;
-                if (rows_pos > T) rows_pos = T;
-                const int c_grouped = ngroup * rows_pos < rows_pos + (ngroup - 1) * dil;
-                const int c_Rmax = c_grouped ? ngroup * rows_pos : rows_pos + (ngroup - 1) * dil;
-                if ((size_t)CO * c_Rmax * St > 256 * kX6PosPerThread) continue;
-                ConvPlan::Geo &g = pl.geo[c_NT - 1];
-                g.NT = c_NT; g.tpw = c_tpw; g.n_wg = c_wg; g.grouped = c_grouped;
-                g.lds = std::max<size_t>((size_t)operand_planes(e->precision) * CO * c_Rmax * St * 16, 64);
-                tpw = c_tpw; n_wg = c_wg; NT = c_NT; Rmax = c_Rmax; grouped = c_grouped;
-            }
-            if (NT > 0) break;
+        for (int k = 0; k < 4; k++) pl.geo[k] = ConvPlan::Geo{};
+        for (int ntmax = 1; ntmax <= NTmax; ntmax++) {  // ends on the largest tiling that fits = the default geometry
+            const int c_wg = (tiles + NCG * ntmax - 1) / (NCG * ntmax);
+            const int c_tpw = (tiles + c_wg - 1) / c_wg;
+            const int c_NT = (c_tpw + NCG - 1) / NCG;
+            int rows_pos = (c_tpw * 32 + FP - 1) / FP + 1;
+            if (rows_pos > T) rows_pos = T;
+            const int c_grouped = ngroup * rows_pos < rows_pos + (ngroup - 1) * dil;
+            const int c_Rmax = c_grouped ? ngroup * rows_pos : rows_pos + (ngroup - 1) * dil;
+            if ((size_t)c_Rmax * St > 256 * kX6PosPerThread) continue;
+            ConvPlan::Geo &g = pl.geo[c_NT - 1];
+            g.NT = c_NT; g.tpw = c_tpw; g.n_wg = c_wg; g.grouped = c_grouped;
+            g.lds = std::max<size_t>((size_t)operand_planes(e->precision) * c_Rmax * St * 16, 64);
+            tpw = c_tpw; n_wg = c_wg; NT = c_NT; Rmax = c_Rmax; grouped = c_grouped;
         }
         if (NT > 0) {
-            const int nstep = (ntap * CO + 1) / 2, nchunk = (Ci + 8 * CO - 1) / (8 * CO);
+            const int nstep = (ntap + 1) / 2, nchunk = (Ci + 7) / 8;
             ConvArgs &a = pl.a;
             a.Ci = Ci; a.Co = Co; a.CoPad = CoPad; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
             a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = grouped;
-            a.ntap = ntap; a.CC = 8 * CO; a.nchunk = nchunk; a.tiles_per_wg = tpw; a.St = St;
-            a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.gate_pairs = gate_pairs; a.Cy = Cy; a.cy0 = cy0;
+            a.ntap = ntap; a.CC = 8; a.nchunk = nchunk; a.tiles_per_wg = tpw; a.St = St;
+            a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Cy; a.cy0 = 0;
             for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; }
-            pl.NT = NT; pl.grid_x = n_wg; pl.x6 = true; pl.CO = CO;
-            pl.lds = std::max<size_t>((size_t)operand_planes(e->precision) * CO * Rmax * St * 16, 64);
-            // weights: [chunk][step][plane][mtile][co 32][k 16], k = half*8 + c <-> entry 2*step+half = (tap, octet) tap-major,
-            // channel chunk*8*CO + octet*8 + c
+            pl.NT = NT; pl.grid_x = n_wg; pl.x6 = true;
+            pl.lds = std::max<size_t>((size_t)operand_planes(e->precision) * Rmax * St * 16, 64);
+            // weights: [chunk][step][plane][mtile][co 32][k 16], k = half*8 + c <-> tap 2*step+half, channel chunk*8 + c
             const int PL = operand_planes(e->precision);
             std::vector<uint16_t> wx((size_t)nchunk * nstep * PL * MT * 32 * 16, 0);
             for (int ch = 0; ch < nchunk; ch++)
@@ -401,8 +371,7 @@ int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy
                     for (int m = 0; m < MT; m++)
                         for (int r = 0; r < 32; r++)
                             for (int k = 0; k < 16; k++) {
-                                const int en = 2 * st + k / 8, tp = en / CO, oc = en % CO;
-                                const int ci = (ch * CO + oc) * 8 + k % 8, co = m * 32 + r;
+                                const int tp = 2 * st + k / 8, ci = ch * 8 + k % 8, co = m * 32 + r;
                                 if (tp >= ntap || co >= Co || ci >= Ci) continue;
                                 const float x = wsel(ci, co, taps[tp][0], taps[tp][1]);
                                 const uint16_t h = bf16_rne(x);
@@ -430,7 +399,7 @@ int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy
     auto bytes = [&](int cc) { return sizeof(float) * ((size_t)ntap * cc * CoPad + (size_t)cc * Rmax * St); };
     int CC = CiPad;
     auto fits = [&](int cc) {
-        return bytes(cc) <= e->conv_lds_budget && (size_t)cc * Rmax * St <= 256 * kPatchPerThread &&
+        return bytes(cc) <= 48 * 1024 && (size_t)cc * Rmax * St <= 256 * kPatchPerThread &&
                (size_t)ntap * cc * CoPad <= 256 * 4 * kWeightPerThread;
     };
     while (CC > 2 && !fits(CC)) CC -= 2;
@@ -443,7 +412,7 @@ int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy
     a.Ci = Ci; a.Co = Co; a.CoPad = CoPad; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
     a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = grouped;
     a.ntap = ntap; a.CC = CC; a.nchunk = nchunk; a.tiles_per_wg = tpw; a.St = St;
-    a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.gate_pairs = gate_pairs; a.Cy = Cy; a.cy0 = cy0;
+    a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Cy; a.cy0 = 0;
     for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; }
     pl.NT = NT;
     pl.grid_x = n_wg;
@@ -462,8 +431,33 @@ int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy
     return dev_upload(e, pl.bias, bias);
 }
 
+// The CRN geometries the engine accepts, stated in one place and checked before any planning (se_reset and every other entry
+// point that plans fails with SE_ERR_ARG and the message).  A convolution's output channels are GEMM rows in tiles of 32, of
+// which a workgroup's four waves take 1, 2 or 4 (never 3).  Finer limits of the kernels' own tilings are reported by
+// plan_conv / plan_conv_p from the same call.
+bool crn_geometry_supported(const se_engine *e, std::string *why) {
+    char msg[256];
+    auto refuse = [&](const char *fmt, int a, int b) { snprintf(msg, sizeof(msg), fmt, a, b); *why = msg; return false; };
+    auto rows_ok = [](int rows) { const int tiles = (rows + 31) / 32; return tiles <= 4 && tiles != 3; };
+    if (e->Ch[0] > 128) return refuse("%d microphones give %d feature channels: at most 128 are supported (num_inputs <= 64)", e->M, e->Ch[0]);
+    if (e->variant && e->Ch[0] > 8) return refuse("the pre-conv blocks support up to 8 feature channels (num_inputs <= 4), got %d inputs = %d channels", e->M, e->Ch[0]);
+    for (int i = 0; i < e->L; i++) {
+        const int C = e->Ch[i + 1];
+        if (!rows_ok(C)) return refuse("encoder block %d has %d channels: up to 64 or 97-128 are supported (GEMM rows in 1, 2 or 4 tiles of 32)", i, C);
+        // decoder skip connection (levels 1..L-1): residualmask / residual stacked as 2 C rows of one 1x1 GEMM
+        if (i + 1 < e->L && !rows_ok(2 * C))
+            return refuse("the skip connection of level %d has %d channels: its 1x1 pair needs 2 GEMM rows per channel, so up to 32 or 49-64 channels are supported", i + 1, C);
+        // CRN_ELU / student: the gated 1x1 pair (conv_trans, conv_gated) as 2 rows per channel, in halves above 64 channels
+        if (e->variant && !(C > 64 ? rows_ok(2 * ((C + 1) / 2)) && rows_ok(2 * (C / 2)) : rows_ok(2 * C)))
+            return refuse("encoder block %d has %d channels: its gated 1x1 pair needs 2 GEMM rows per channel and up to 64 channels per launch; 33-48 channels per launch are not supported", i, C);
+    }
+    return true;
+}
+
 int prepare_weights(se_engine *e) {
     if (e->weights_ready) return 0;
+    std::string why;
+    if (!crn_geometry_supported(e, &why)) return fail(e, SE_ERR_ARG, "%s", why.c_str());
     const int L = e->L, H = e->H, D = e->D;
     for (int i = 0; i < L; i++) {
         const int Ci = e->Ch[i], Co = e->Ch[i + 1], Fi = e->F[i], Fo = e->F[i + 1], d = 1 << i;
@@ -482,27 +476,6 @@ int prepare_weights(se_engine *e) {
                            *b, 0, Co, e->act);
         if (rc) return rc;
         e->lv[i].enc.flops = 2.0 * Co * Ci * 15 * Fo * e->T;
-        e->lv[i].gate[0].active = e->lv[i].gate[1].active = false;
-        if (e->variant) {  // conv_trans / conv_gated 1x1 pair (CRN_ELU.py:223-224,240), <= 64 output channels per launch
-            auto *tw = param(e, p + "conv_trans.weight", (size_t)Co * Co);
-            auto *tb = param(e, p + "conv_trans.bias", Co);
-            auto *gw = param(e, p + "conv_gated.weight", (size_t)Co * Co);
-            auto *gb = param(e, p + "conv_gated.bias", Co);
-            if (!tw || !tb || !gw || !gb) return SE_ERR_PARAM_MISSING;
-            const float *twp = tw->data(), *gwp = gw->data();
-            const int nparts = Co > 64 ? 2 : 1, cpart = (Co + nparts - 1) / nparts;
-            std::vector<std::array<int, 4>> t1 = {{0, 0, 0, 0}};
-            for (int part = 0; part < nparts; part++) {
-                const int c0 = part * cpart, cn = std::min(cpart, Co - c0);
-                std::vector<float> bias2(2 * cn);
-                for (int c = 0; c < cn; c++) { bias2[2 * c] = (*tb)[c0 + c]; bias2[2 * c + 1] = (*gb)[c0 + c]; }
-                rc = plan_conv(e, e->lv[i].gate[part], Co, 2 * cn, Fo, Fo, Fo, 1, 1, 0, 0, 0, 1, 0, Fo, t1,
-                               [=](int ci, int row, int, int) { const int c = c0 + row / 2; return (row & 1) ? gwp[(size_t)c * Co + ci] : twp[(size_t)c * Co + ci]; },
-                               bias2, 0, 0, 0, /*gate_pairs=*/1, /*Cy=*/Co, /*cy0=*/c0);
-                if (rc) return rc;
-                e->lv[i].gate[part].flops = 2.0 * 2 * cn * Co * Fo * e->T;
-            }
-        }
         if ((rc = dev_upload(e, e->lv[i].enc_nw, *nw))) return rc;
         if ((rc = dev_upload(e, e->lv[i].enc_nb, *nb))) return rc;
     }
@@ -524,7 +497,7 @@ int prepare_weights(se_engine *e) {
             for (int kt = 0; kt < 3; kt++) to.push_back({kf, kt, 2 - kt, 1 + (3 - kf) / 2});
         int rc = 0;
         bool merged = false;
-        if (e->dec_merge && Co > 4 && Co <= 16 && e->conv_mode == 6) {
+        if (Co > 4 && Co <= 16) {
             // narrow block: both parities in ONE 15-tap launch, rows (2c, 2c+1) = (even, odd) parity of channel c (ConvArgs::par_rows)
             std::vector<std::array<int, 4>> tu;
             for (int kf = 0; kf < 5; kf++)
@@ -533,7 +506,7 @@ int prepare_weights(se_engine *e) {
             for (int c = 0; c < Co; c++) bias2[2 * c] = bias2[2 * c + 1] = (*b)[c];
             rc = plan_conv(e, e->lv[j].dec_even, Ci, 2 * Co, Fi, Fi, Fo, 1, 2, 0, 1, 0, 3, d, Fi + 2, tu,
                            [=](int ci, int row, int kf, int kt) { return ((row & 1) == (kf & 1)) ? wsel(ci, row >> 1, kf, kt) : 0.0f; },
-                           bias2, 0, 2 * Co, e->act, 0, /*Cy=*/Co, 0);
+                           bias2, 0, 2 * Co, e->act, /*Cy=*/Co);
             if (rc) return rc;
             merged = e->lv[j].dec_even.x6;
             if (merged) { e->lv[j].dec_even.a.par_rows = 1; e->lv[j].dec_odd.active = false; e->lv[j].dec_odd.grid_x = 0; }
@@ -549,46 +522,10 @@ int prepare_weights(se_engine *e) {
         e->lv[j].dec_odd.flops = merged ? 0.0 : 2.0 * Ci * Co * 6 * Fi * e->T;
         if ((rc = dev_upload(e, e->lv[j].dec_nw, *nw))) return rc;
         if ((rc = dev_upload(e, e->lv[j].dec_nb, *nb))) return rc;
-        if (lvl > 0) {  // skip path exists (CRN.py:485-487)
-            auto *mw = param(e, p + "residualmask.weight", (size_t)Co * Co);
-            auto *mb = param(e, p + "residualmask.bias", Co);
-            auto *rw = param(e, p + "residual.weight", (size_t)Co * Co);
-            auto *rb = param(e, p + "residual.bias", Co);
+        if (lvl > 0) {  // skip path (CRN.py:485-487): the residualnorm affine of the gate (the 1x1 pair is planned in prepare_weights_p)
             auto *mnw = param(e, p + "residualnorm.weight", Co);
             auto *mnb = param(e, p + "residualnorm.bias", Co);
-            if (!mw || !mb || !rw || !rb || !mnw || !mnb) return SE_ERR_PARAM_MISSING;
-            const float *mwp = mw->data(), *rwp = rw->data();
-            std::vector<float> bias2(2 * Co);
-            for (int c = 0; c < Co; c++) { bias2[c] = (*mb)[c]; bias2[Co + c] = (*rb)[c]; }
-            std::vector<std::array<int, 4>> t1 = {{0, 0, 0, 0}};
-            const int Fr = e->F[lvl];
-            // Fused form (k_conv_x6 only): rows (2c, 2c+1) = (residualmask_c, residual_c), gate applied in the epilogue, preceded
-            // by a statistics-only pass of the residualmask rows.  Falls back to the two-tensor form + k_dec_blend_ew otherwise.
-            e->lv[j].skip_fused = false;
-            e->lv[j].skipm.active = false;
-            if (e->skip_fuse) {
-                std::vector<float> biasp(2 * Co);
-                for (int c = 0; c < Co; c++) { biasp[2 * c] = (*mb)[c]; biasp[2 * c + 1] = (*rb)[c]; }
-                rc = plan_conv(e, e->lv[j].skip, Co, 2 * Co, Fr, Fr, Fr, 1, 1, 0, 0, 0, 1, 0, Fr, t1,
-                               [=](int ci, int row, int, int) { const int c = row >> 1; return (row & 1) ? rwp[(size_t)c * Co + ci] : mwp[(size_t)c * Co + ci]; },
-                               biasp, 0, 0, e->act, /*gate_pairs=*/0, /*Cy=*/Co, /*cy0=*/0);
-                if (rc) return rc;
-                if (e->lv[j].skip.x6) {
-                    rc = plan_conv(e, e->lv[j].skipm, Co, Co, Fr, Fr, Fr, 1, 1, 0, 0, 0, 1, 0, Fr, t1,
-                                   [=](int ci, int co, int, int) { return mwp[(size_t)co * Co + ci]; }, *mb, 0, 0, e->act);
-                    if (rc) return rc;
-                    e->lv[j].skip_fused = e->lv[j].skipm.x6;
-                    e->lv[j].skipm.flops = 0;  // recomputation, not algorithmic work (SURVEY 8d accounting counts the skip GEMM once)
-                }
-            }
-            if (!e->lv[j].skip_fused) {
-                e->lv[j].skipm.active = false;
-                rc = plan_conv(e, e->lv[j].skip, Co, 2 * Co, Fr, Fr, Fr, 1, 1, 0, 0, 0, 1, 0, Fr, t1,
-                               [=](int ci, int co, int, int) { return co < Co ? mwp[(size_t)co * Co + ci] : rwp[(size_t)(co - Co) * Co + ci]; },
-                               bias2, Co, 2 * Co, e->act);
-                if (rc) return rc;
-            }
-            e->lv[j].skip.flops = 2.0 * 2 * Co * Co * Fr * e->T;
+            if (!mnw || !mnb) return SE_ERR_PARAM_MISSING;
             if ((rc = dev_upload(e, e->lv[j].dec_mnw, *mnw))) return rc;
             if ((rc = dev_upload(e, e->lv[j].dec_mnb, *mnb))) return rc;
         }
@@ -605,7 +542,6 @@ int prepare_weights(se_engine *e) {
         auto *nw = param(e, p + "norm.weight", C0);
         auto *nb = param(e, p + "norm.bias", C0);
         if (!w || !b || !tw || !tb || !gw || !gb || !nw || !nb) return SE_ERR_PARAM_MISSING;
-        if (C0 > 8) return fail(e, SE_ERR_ARG, "preconv blocks support up to 8 feature channels (num_inputs <= 4)");
         std::vector<std::array<int, 4>> taps;
         for (int kf = 0; kf < 5; kf++)
             for (int kt = 0; kt < 5; kt++) taps.push_back({kf, kt, kt, kf * fd});
@@ -672,41 +608,24 @@ void select_conv_geometry(se_engine *e, ConvPlan &pl) {
         const double cost = rounds * (g.NT + 0.28);
         if (pick < 0 || cost <= best) { best = cost; pick = k; }
     }
-    if (e->conv_geo_fixed) for (int k = 3; k >= 0; k--) if (pl.geo[k].NT) { pick = k; break; }
-    if (const char *s = getenv("SE_CONV_NT")) { const int k = atoi(s) - 1; if (k >= 0 && k < 4 && pl.geo[k].NT) pick = k; }
     const ConvPlan::Geo &g = pl.geo[pick];
     pl.NT = g.NT; pl.grid_x = g.n_wg; pl.lds = g.lds;
     pl.a.tiles_per_wg = g.tpw; pl.a.grouped = g.grouped;
 }
 
-struct ConvBlend {  // operands of the fused decoder skip gate (ConvArgs::blend)
-    const float *ydec, *nw, *nb, *mnw, *mnb;
-    SlabStats sy, su;
-    int Fo;
-};
-
 int launch_conv(se_engine *e, const ConvPlan &pl, const float *x, const float *xprev, float *y, hipStream_t st, const char *label,
-                float *stats = nullptr, int nslot = 0, int slot0 = 0, int stats_lo = 0, int stats_hi = 0, const ConvBlend *blend = nullptr) {
+                float *stats = nullptr, int nslot = 0, int slot0 = 0, int stats_lo = 0, int stats_hi = 0) {
     if (!pl.active) return 0;
     // algorithmic MACs of this launch as SURVEY.md 8d counts them are attributed by the caller via pl.flops
     ProfScope ps(e, pl.x6 ? "k_conv_x6" : (pl.NT == 0 ? "k_conv_small" : "k_conv_igemm"), label, pl.flops * e->B, st);
     ConvArgs a = pl.a;
     a.x = x; a.xprev = xprev; a.y = y; a.w = pl.w.p; a.bias = pl.bias.p; a.gatew = pl.gatew.p;
     a.stats = stats; a.stats_nslot = nslot; a.stats_slot0 = slot0; a.stats_lo = stats_lo; a.stats_hi = stats_hi;
-    a.blend = 0;
-    if (blend) {
-        if (!pl.x6 || a.ntap != 1) return fail(e, SE_ERR_ARG, "fused skip gate needs the 1x1 k_conv_x6 path");
-        a.blend = 1; a.bl_ydec = blend->ydec; a.bl_nw = blend->nw; a.bl_nb = blend->nb; a.bl_mnw = blend->mnw; a.bl_mnb = blend->mnb;
-        a.bl_sy = blend->sy; a.bl_su = blend->su; a.bl_Fo = blend->Fo;
-    }
     dim3 grid(pl.grid_x, e->B);
     if (pl.x6) {
         ConvX6Args xa{a, reinterpret_cast<const uint4 *>(pl.wx.p)};
-#ifdef SE_X6_TRACE
-        { const char *want = getenv("SE_X6_TRACE_LABEL"); xa.trace_slot = (want && label && strcmp(want, label) == 0) ? 0 : -1; }
-#endif
-        if (conv_x6_launch(a.ntap, pl.NT, pl.CO, operand_planes(e->precision), grid, pl.lds, st, xa))
-            return fail(e, SE_ERR_ARG, "no x6 conv kernel instance for %d taps x %d tiles x %d octets", a.ntap, pl.NT, pl.CO);
+        if (conv_x6_launch(a.ntap, pl.NT, operand_planes(e->precision), grid, pl.lds, st, xa))
+            return fail(e, SE_ERR_ARG, "no x6 conv kernel instance for %d taps x %d tiles", a.ntap, pl.NT);
         HIPCHECK(e, hipGetLastError());
         return 0;
     }
@@ -718,13 +637,13 @@ int launch_conv(se_engine *e, const ConvPlan &pl, const float *x, const float *x
 
 int launch_gemm(se_engine *e, const float *A, long lda, const float *W, long ldw, const float *bias, float *C, long ldc,
                 int Mr, int Nc, int Kd, int relu, hipStream_t st, const char *label, const float *Wx = nullptr) {
-    if (Mr <= e->skinny_rows && lda == Kd && ldw == Kd && Kd % 8 == 0 && e->gemm_mode == 6) {  // few rows: 32 x 32 tiles, K split over the waves (fp32-exact MFMA)
+    if (Mr <= e->skinny_rows && lda == Kd && ldw == Kd && Kd % 8 == 0) {  // few rows: 32 x 32 tiles, K split over the waves (fp32-exact MFMA)
         ProfScope ps(e, "k_gemm_skinny", label, 2.0 * Mr * Nc * Kd, st);
         if (se_train_gemm(A, W, bias, C, Mr, Nc, Kd, relu, st)) return fail(e, SE_ERR_HIP, "skinny GEMM launch failed: %s", se_train_last_error());
         return 0;
     }
     dim3 ggrid((Nc + kGemmBN - 1) / kGemmBN, (Mr + kGemmBM - 1) / kGemmBM);
-    if (Wx && e->gemm_mode == 6 && Kd % 8 == 0 && Kd >= 8 && lda % 4 == 0 && ldw == Kd) {
+    if (Wx && Kd % 8 == 0 && Kd >= 8 && lda % 4 == 0 && ldw == Kd) {
         ProfScope ps(e, e->precision == 1 ? "k_gemm_f16" : (e->precision == 2 ? "k_gemm_bf16x3" : "k_gemm_bf16x6"), label, 2.0 * Mr * Nc * Kd, st);
         GemmX6Args g{A, reinterpret_cast<const __bf16 *>(Wx), bias, C, Mr, Nc, Kd, lda, ldc, relu};
         if (e->precision == 1) hipLaunchKernelGGL(k_gemm_x<1>, ggrid, dim3(256), 0, st, g);
@@ -758,7 +677,7 @@ int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *b
         if (!gx || bytes < best) { gx = cx; gy = 8 / cx; best = bytes; }
     }
     int nblocks = nrt * nct;
-    if (e->gemm_band >= 0 && (!gx || e->gemm_band == 1) && nrt * nct >= 16) {
+    if (!gx && nrt * nct >= 16) {
         // no equal 8-block split divides the tile grid (B = 256: 21 x 12 tiles): block id -> XCD is id mod 8, so plain row-major order
         // hands every row tile of A to all eight L2s.  Banded: XCD x takes the `per` consecutive tiles [x per, (x + 1) per)
         const int per = (nrt * nct + 7) / 8;
@@ -774,15 +693,6 @@ int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *b
     if (PL == 1) hipLaunchKernelGGL(k_gemm_p<1>, grid, dim3(512), lds, st, g);
     else if (PL == 2) hipLaunchKernelGGL(k_gemm_p<2>, grid, dim3(512), lds, st, g);
     else hipLaunchKernelGGL(k_gemm_p<3>, grid, dim3(512), lds, st, g);
-    HIPCHECK(e, hipGetLastError());
-    return 0;
-}
-
-int launch_gln(se_engine *e, const float *x, float *y, const float *w, const float *b, long n, int mode, int C, int T,
-               int F, hipStream_t st) {
-    ProfScope ps(e, "k_gln", "gln", 0, st);
-    GlnArgs g{x, y, w, b, n, mode, C, T, F, e->eps_mode};
-    hipLaunchKernelGGL(k_gln, dim3(e->B), dim3(1024), 0, st, g);
     HIPCHECK(e, hipGetLastError());
     return 0;
 }
@@ -805,10 +715,10 @@ int launch_gln_ew(se_engine *e, const float *x, float *y, const float *w, const 
     return 0;
 }
 
-// TemporalCRN.forward on device in three stages; each reads/writes the ring slot `cur` (history from slot `prev`).
-// spec: (b, m, t, f) strides; out: (b, t, f) strides (cf2 units).
-// Stage 1: features + (CRN_ELU pre-convs) + encoder  ->  xin[*][cur], gru_in[cur]
-// features (CRN.py:463-467) and, for CRN_ELU / the student, the three frequency-dilated pre-conv blocks -> xin[0][cur] (fp32)
+// TemporalCRN.forward on device in three stages (stage_encoder_p, the bottleneck below, stage_decoder_p); each reads/writes the
+// ring slot `cur` (history from slot `prev`).  spec: (b, m, t, f) strides; out: (b, t, f) strides (cf2 units).
+// CRN_ELU / student with the pre-conv blocks on the vector-ALU kernel (convp_engine.inc.h: all but fp16 operands): features
+// (CRN.py:463-467) and the three frequency-dilated pre-conv blocks -> xin[0][cur] (fp32)
 int stage_features_pre(se_engine *e, int cur, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st) {
     const int T = e->T, B = e->B;
     int rc;
@@ -816,8 +726,7 @@ int stage_features_pre(se_engine *e, int cur, const cf2 *spec, long sB, long sM,
     const int pcur = e->parity, pprev = pcur ^ 1;
     {
         ProfScope ps(e, "k_featurize", "featurize", 0, st);
-        float *dst = e->npre ? e->pin[0][pcur].p : e->xin[0][cur].p;
-        FeatArgs f{spec, sB, sM, sT, sF, dst, e->M, T, e->F[0], e->atan2_phase};
+        FeatArgs f{spec, sB, sM, sT, sF, e->pin[0][pcur].p, e->M, T, e->F[0], e->atan2_phase};
         const int TF = T * e->F[0];
         hipLaunchKernelGGL(k_featurize, dim3((TF + 255) / 256, B), dim3(256), 0, st, f);
         HIPCHECK(e, hipGetLastError());
@@ -835,38 +744,9 @@ int stage_features_pre(se_engine *e, int cur, const cf2 *spec, long sB, long sM,
     return 0;
 }
 
-int stage_encoder(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st) {
-    const int L = e->L, T = e->T;
-    int rc;
-    if ((rc = stage_features_pre(e, cur, spec, sB, sM, sT, sF, st))) return rc;
-    for (int i = 0; i < L; i++) {  // encoder (CRN.py:471-474; CRN_ELU.py:233-247)
-        const int Co = e->Ch[i + 1], Fo = e->F[i + 1];
-        const long n = (long)Co * T * Fo;
-        const float *normed_src = e->enc_raw[i].p;
-        int ns = e->lv[i].enc.grid_x;
-        if (!e->variant) {
-            if ((rc = launch_conv(e, e->lv[i].enc, e->xin[i][cur].p, e->xin[i][prev].p, e->enc_raw[i].p, st, ("enc" + std::to_string(i)).c_str(),
-                                  e->enc_stats[i].p, ns, 0, 0, Co))) return rc;
-        } else {
-            if ((rc = launch_conv(e, e->lv[i].enc, e->xin[i][cur].p, e->xin[i][prev].p, e->enc_raw[i].p, st, ("enc" + std::to_string(i)).c_str()))) return rc;
-            const int n0 = e->lv[i].gate[0].grid_x, n1 = e->lv[i].gate[1].active ? e->lv[i].gate[1].grid_x : 0;
-            ns = n0 + n1;
-            if ((rc = launch_conv(e, e->lv[i].gate[0], e->enc_raw[i].p, nullptr, e->enc_g[i].p, st, ("gate" + std::to_string(i)).c_str(),
-                                  e->enc_stats[i].p, ns, 0, 0, Co))) return rc;
-            if (n1 && (rc = launch_conv(e, e->lv[i].gate[1], e->enc_raw[i].p, nullptr, e->enc_g[i].p, st, ("gate" + std::to_string(i)).c_str(),
-                                        e->enc_stats[i].p, ns, n0, 0, Co))) return rc;
-            normed_src = e->enc_g[i].p;
-        }
-        if (i + 1 < L) rc = launch_gln_ew(e, normed_src, e->xin[i + 1][cur].p, e->lv[i].enc_nw.p, e->lv[i].enc_nb.p, e->enc_stats[i].p, ns, n, 0, Co, T, Fo, st);
-        else rc = launch_gln_ew(e, normed_src, e->gru_in[cur].p, e->lv[i].enc_nw.p, e->lv[i].enc_nb.p, e->enc_stats[i].p, ns, n, 1, Co, T, Fo, st);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
 uint4 *decin_p(se_engine *e, int slot);  // convp_engine.inc.h: decoder-input ring slot of the plane path
 
-// Stage 2: the recurrent bottleneck (CRN.py:476-481, 256-282)  gru_in[cur] -> dec_in[cur]
+// Stage 2: the recurrent bottleneck (CRN.py:476-481, 256-282)  gruinP[cur] (or gru_in[cur]) -> decinP[cur]
 // The bottleneck is cut where its data dependencies are (CRN.py:256-282):
 //   stage_gru_proj0  x W_ih0^T for all T frames: depends only on the encoder output, so it runs on the ENCODER stream
 //   stage_gru_layer  layer l: (l > 0: input projection of layer l-1's sequence) + T dependent step launches; each layer has
@@ -899,24 +779,6 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
                                    ("gru_ih" + std::to_string(l)).c_str(), e->wih_x[l].p))) return rc;
     }
     float *seq = e->seqr[l][cur].p;
-    const int ngroup = (B + 31) / 32, nhid = (H + 15) / 16;
-    const bool use_seq = e->gru_seq && e->gru_direct <= 0 && (H == 512 || H == 128) && nhid <= 256;
-    if (use_seq) {
-        // groups per launch: all workgroups of a launch must be able to become resident (<= 256 CUs, one per CU)
-        const int gmax = std::max(1, 256 / nhid);
-        for (int g0 = 0; g0 < ngroup; g0 += gmax) {
-            const int ng = std::min(gmax, ngroup - g0), rows0 = g0 * 32, rows = std::min(B - rows0, ng * 32);
-            const int hc = e->hcur[l];
-            HIPCHECK(e, hipMemsetAsync(e->gru_sync.p, 0, 64 * sizeof(unsigned), st));
-            GruSeqArgs g{gi + (long)rows0 * T * 3 * H, e->hbuf[l][hc].p + (long)rows0 * H, e->hbuf[l][hc].p + (long)rows0 * H,
-                         e->hbuf[l][hc ^ 1].p + (long)rows0 * H, e->whh[l].p, e->bhh[l].p, seq + (long)rows0 * T * H,
-                         reinterpret_cast<unsigned *>(e->gru_sync.p), reinterpret_cast<unsigned *>(e->gru_sync.p) + 64, rows, H, T};
-            ProfScope ps(e, "k_gru_seq", "gru_seq", 2.0 * rows * 3 * H * H * T, st);
-            if (H == 512) hipLaunchKernelGGL(k_gru_seq<16>, dim3(nhid, ng), dim3(256), (size_t)192 * H, st, g);
-            else hipLaunchKernelGGL(k_gru_seq<4>, dim3(nhid, ng), dim3(256), (size_t)192 * H, st, g);
-        }
-        if (T & 1) e->hcur[l] ^= 1;  // the last step (t = T-1) wrote P1 when T is odd, P0 when even
-    } else
     for (int t = 0; t < T && !(e->dbg_skip & 1); t++) {
         const int hc = e->hcur[l];
         GruStepArgs g{gi + (long)t * 3 * H, (long)T * 3 * H, e->hbuf[l][hc].p, e->whh[l].p, e->bhh[l].p,
@@ -995,15 +857,13 @@ int stage_gru_out(se_engine *e, int cur, hipStream_t st) {
     if (e->dbg_skip & 2) {}
     else if (e->gemm_p) { if ((rc = launch_gemm_p(e, e->seqP[e->NL - 1][cur].p, e->fcw_x.p, e->fcb.p, e->fc_out.p, D, Ba * T, D, H, e->act, st, "gru_fc"))) return rc; }
     else if ((rc = launch_gemm(e, e->seqr[e->NL - 1][cur].p, H, e->fcw.p, H, e->fcb.p, e->fc_out.p, D, Ba * T, D, H, e->act, st, "gru_fc", e->fcw_x.p))) return rc;
-    if (e->use_p) {  // decoder input in the plane layout
-        const int PL = operand_planes(e->precision), C = e->Ch[L], C8 = (C + 7) / 8;
-        ProfScope ps(e, "k_gln2_p", "gln", 0, st);
-        Gln2PArgs g{e->fc_out.p, e->gnw.p, e->gnb.p, decin_p(e, cur), (long)C8 * PL * T * e->F[L], T, e->F[L], C, C8, e->eps_mode};
-        launch_k_gln2_p(PL, dim3(Ba), st, g);
-        HIPCHECK(e, hipGetLastError());
-        return 0;
-    }
-    return launch_gln(e, e->fc_out.p, e->dec_in[cur].p, e->gnw.p, e->gnb.p, (long)T * D, 2, e->Ch[L], T, e->F[L], st);
+    // decoder input in the plane layout
+    const int PL = operand_planes(e->precision), C = e->Ch[L], C8 = (C + 7) / 8;
+    ProfScope ps(e, "k_gln2_p", "gln", 0, st);
+    Gln2PArgs g{e->fc_out.p, e->gnw.p, e->gnb.p, decin_p(e, cur), (long)C8 * PL * T * e->F[L], T, e->F[L], C, C8, e->eps_mode};
+    launch_k_gln2_p(PL, dim3(Ba), st, g);
+    HIPCHECK(e, hipGetLastError());
+    return 0;
 }
 
 // single-stream form: all bottleneck stages back to back
@@ -1015,54 +875,6 @@ int stage_bottleneck(se_engine *e, int cur, hipStream_t st, bool overlapped = fa
     return stage_gru_out(e, cur, st);
 }
 
-// Stage 3: decoder (CRN.py:483-489) + mask application  dec_in[cur], xin[*][cur], spec -> out
-int stage_decoder(se_engine *e, int cur, const cf2 *spec, long sB, long sT, long sF, cf2 *out, long oB, long oT, long oF, hipStream_t st) {
-    const int L = e->L, T = e->T, B = e->B;
-    int rc;
-    const float *x = e->dec_in[cur].p;
-    for (int j = 0; j < L; j++) {
-        const int lvl = L - 1 - j;
-        const int Co = lvl == 0 ? 2 : e->Ch[lvl], Fi = e->F[lvl + 1], Fo = 2 * Fi - 1;
-        const int ne = e->lv[j].dec_even.active ? e->lv[j].dec_even.grid_x : 0, no = e->lv[j].dec_odd.active ? e->lv[j].dec_odd.grid_x : 0;
-        if ((rc = launch_conv(e, e->lv[j].dec_even, x, nullptr, e->dec_raw[j].p, st, ("dec" + std::to_string(j) + "_even").c_str(),
-                              e->dec_stats[j].p, ne + no, 0, 0, Co))) return rc;
-        if ((rc = launch_conv(e, e->lv[j].dec_odd, x, nullptr, e->dec_raw[j].p, st, ("dec" + std::to_string(j) + "_odd").c_str(),
-                              e->dec_stats[j].p, ne + no, ne, 0, Co))) return rc;
-        const SlabStats sy{e->dec_stats[j].p, ne + no, (long)Co * T * Fo, e->eps_mode};
-        if (lvl > 0) {
-            const int Fr = e->F[lvl];
-            const long nu = (long)Co * T * Fr;
-            if (e->lv[j].skip_fused) {
-                const int nm = e->lv[j].skipm.grid_x;
-                if ((rc = launch_conv(e, e->lv[j].skipm, e->xin[lvl][cur].p, nullptr, nullptr, st, ("skipstat" + std::to_string(j)).c_str(),
-                                      e->skip_stats[j].p, nm, 0, 0, Co))) return rc;
-                ConvBlend bl{e->dec_raw[j].p, e->lv[j].dec_nw.p, e->lv[j].dec_nb.p, e->lv[j].dec_mnw.p, e->lv[j].dec_mnb.p, sy,
-                             SlabStats{e->skip_stats[j].p, nm, nu, e->eps_mode}, Fo};
-                if ((rc = launch_conv(e, e->lv[j].skip, e->xin[lvl][cur].p, nullptr, e->dec_out[j].p, st, ("skip" + std::to_string(j)).c_str(),
-                                      nullptr, 0, 0, 0, 0, &bl))) return rc;
-            } else {
-                const int nk = e->lv[j].skip.grid_x;
-                if ((rc = launch_conv(e, e->lv[j].skip, e->xin[lvl][cur].p, nullptr, e->dec_uv[j].p, st, ("skip" + std::to_string(j)).c_str(),
-                                      e->skip_stats[j].p, nk, 0, 0, Co))) return rc;
-                if (nu % 4) return fail(e, SE_ERR_ARG, "decoder tensor size %ld not a multiple of 4", nu);
-                BlendEwArgs bl{e->dec_raw[j].p, e->dec_uv[j].p, e->dec_out[j].p, e->lv[j].dec_nw.p, e->lv[j].dec_nb.p,
-                               e->lv[j].dec_mnw.p, e->lv[j].dec_mnb.p, sy, SlabStats{e->skip_stats[j].p, nk, nu, e->eps_mode}, Co, T, Fo, Fr};
-                ProfScope ps(e, "k_dec_blend_ew", "dec_blend", 0, st);
-                hipLaunchKernelGGL(k_dec_blend_ew, dim3((unsigned)((nu / 4 + 1023) / 1024), B), dim3(256), 0, st, bl);
-                HIPCHECK(e, hipGetLastError());
-            }
-            x = e->dec_out[j].p;
-        } else {
-            if (Fo != e->F[0]) return fail(e, SE_ERR_ARG, "decoder output has %d bins, spectrum has %d", Fo, e->F[0]);
-            MaskEwArgs m{e->dec_raw[j].p, e->lv[j].dec_nw.p, e->lv[j].dec_nb.p, sy, spec, sB, sT, sF, out, oB, oT, oF, T, e->F[0]};
-            ProfScope ps(e, "k_final_mask_ew", "final_mask", 0, st);
-            launch_k_final_mask_ew(dim3((T * e->F[0] + 1023) / 1024, B), st, m);
-            HIPCHECK(e, hipGetLastError());
-        }
-    }
-    return 0;
-}
-
 }  // namespace
 
 #include "convp_engine.inc.h"
@@ -1071,11 +883,11 @@ namespace {
 
 int run_encoder(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st) {
     if (e->dbg_skip & 4) return 0;
-    return e->use_p ? stage_encoder_p(e, cur, prev, spec, sB, sM, sT, sF, st) : stage_encoder(e, cur, prev, spec, sB, sM, sT, sF, st);
+    return stage_encoder_p(e, cur, prev, spec, sB, sM, sT, sF, st);
 }
 int run_decoder(se_engine *e, int cur, const cf2 *spec, long sB, long sT, long sF, cf2 *out, long oB, long oT, long oF, hipStream_t st) {
     if (e->dbg_skip & 8) return 0;
-    return e->use_p ? stage_decoder_p(e, cur, spec, sB, sT, sF, out, oB, oT, oF, st) : stage_decoder(e, cur, spec, sB, sT, sF, out, oB, oT, oF, st);
+    return stage_decoder_p(e, cur, spec, sB, sT, sF, out, oB, oT, oF, st);
 }
 
 int forward_dev(se_engine *e, const cf2 *spec, long sB, long sM, long sT, long sF, cf2 *out, long oB, long oT, long oF,
@@ -1127,11 +939,10 @@ int ensure_ready(se_engine *e) {
     int rc = prepare_weights(e);
     if (rc) return rc;
     if (replanned) {
-        e->use_p = e->path != 0 && convp_supported(e);
-        if (e->use_p && (rc = prepare_weights_p(e))) return rc;
+        if ((rc = prepare_weights_p(e))) return rc;
         // capability only: whether THIS batch takes the plane GEMMs is select_gemm_route()'s decision (a batch on the skinny route
         // never allocated gruinP / seqP, so a weight reload must not switch the plane route back on behind its back)
-        e->gemm_p_cap = e->use_p && e->gemm_p_env && !e->gru_seq && e->D % 32 == 0 && e->H % 32 == 0 && e->Ch[e->L] % 8 == 0;
+        e->gemm_p_cap = e->gemm_p_env && e->D % 32 == 0 && e->H % 32 == 0 && e->Ch[e->L] % 8 == 0;
         select_gemm_route(e);
         if (e->gemm_p_cap) {  // W_ih0 with its K axis in the engine's feature order k' = (o * F + f) * 8 + c  (reference d = (8 o + c) * F + f)
             const int Fl = e->F[e->L], D = e->D, H = e->H;
@@ -1144,11 +955,11 @@ int ensure_ready(se_engine *e) {
                 }
             if ((rc = upload_split3(e, e->wih_xp, wp))) return rc;
         }
-        if (e->use_p && e->B > 0) select_all_p(e);
+        if (e->B > 0) select_all_p(e);
     }
     if (replanned && e->B > 0)  // new weights re-made the plans with their default tiling: restore the per-batch choice
         for (int i = 0; i < SE_MAX_LEVELS; i++)
-            for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].skip, &e->lv[i].skipm, &e->lv[i].gate[0], &e->lv[i].gate[1], &e->lv[i].pre})
+            for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].pre})
                 select_conv_geometry(e, *p);
     return 0;
 }
@@ -1253,27 +1064,14 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     e->plan.N = cfg->n_fft;
     e->plan.npass = fft_plan(cfg->n_fft / 2, e->plan.radices);
     if (!e->plan.npass || e->plan.npass > kMaxRadices) return bail(SE_ERR_ARG, "n_fft must factor into 2s and 5s");
-    if (const char *s = getenv("SE_CONV_LDS_KB")) e->conv_lds_budget = (size_t)atoi(s) * 1024;
     if (const char *s = getenv("SE_GRU_DIRECT")) e->gru_direct = atoi(s) != 0 ? 1 : 0;
-    if (const char *s = getenv("SE_GRU_SEQ")) e->gru_seq = atoi(s);
-    if (const char *s = getenv("SE_GEMM_MODE")) e->gemm_mode = atoi(s);
-    if (const char *s = getenv("SE_CONV_MODE")) e->conv_mode = atoi(s);
-    if (const char *s = getenv("SE_CONV_GEO_FIXED")) e->conv_geo_fixed = atoi(s);
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
-    if (const char *s = getenv("SE_CONV_SMALL16")) e->conv_small16 = atoi(s);
-    if (const char *s = getenv("SE_SKIP_FUSE")) e->skip_fuse = atoi(s);
-    if (const char *s = getenv("SE_DEC_MERGE")) e->dec_merge = atoi(s);
-    if (const char *s = getenv("SE_PATH")) e->path = atoi(s);
-    if (const char *s = getenv("SE_SKIP_STREAM")) e->skip_stream = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
     if (const char *s = getenv("SE_DBG_SKIP")) { e->dbg_skip = atoi(s); fprintf(stderr, "se_engine: SE_DBG_SKIP=%d - stages are skipped, results are WRONG (timing experiment)\n", e->dbg_skip); }
 #else
     if (getenv("SE_DBG_SKIP")) return bail(SE_ERR_ARG, "SE_DBG_SKIP is set but this library was built without -DSE_DEBUG_KNOBS: refusing to run (the knob drops whole stages and produces wrong audio)");
 #endif
-    if (const char *s = getenv("SE_GRU_LAG")) e->gru_lag = atoi(s);
     if (const char *s = getenv("SE_GEMM_P")) e->gemm_p_env = atoi(s);
-    if (const char *s = getenv("SE_GEMM_BAND")) e->gemm_band = atoi(s);
-    if (const char *s = getenv("SE_CONVP_DEINT")) e->convp_deint = atoi(s);
     if (const char *s = getenv("SE_GEMM_SKINNY_ROWS")) e->skinny_rows = atoi(s);
     if (const char *s = getenv("SE_SKIP_MIN_BATCH")) e->skip_min_batch = atoi(s);
     e->cp = new se_convp_state();
@@ -1307,8 +1105,6 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 1536 * 2 * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 1536 * 3 * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 512);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_seq<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 512);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_seq<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 128);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 128);
     *out = e;
     return SE_OK;
@@ -1318,12 +1114,11 @@ void se_destroy(se_engine *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    conv_x6_trace_dump();
 #ifdef SE_CP_TRACE
     g_cp_trace_sites.dump();
 #endif
     DevBuf *singles[] = {&e->window, &e->env, &e->tw, &e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
-                         &e->gru_sync, &e->fcw_x, &e->wih_xp, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
+                         &e->fcw_x, &e->wih_xp, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
     for (DevBuf *b : singles) dev_free(*b);
     for (int r = 0; r < kRing; r++) {
         dev_free(e->spec[r]); dev_free(e->gru_in[r]); dev_free(e->dec_in[r]); dev_free(e->gi0[r]); dev_free(e->gruinP[r]);
@@ -1342,12 +1137,10 @@ void se_destroy(se_engine *e) {
     }
     for (int i = 0; i < SE_MAX_LEVELS; i++) {
         Level &l = e->lv[i];
-        for (ConvPlan *p : {&l.enc, &l.dec_even, &l.dec_odd, &l.skip, &l.skipm}) { dev_free(p->w); dev_free(p->bias); dev_free(p->wx); }
+        for (ConvPlan *p : {&l.enc, &l.dec_even, &l.dec_odd, &l.pre}) { dev_free(p->w); dev_free(p->bias); dev_free(p->wx); dev_free(p->gatew); }
         for (DevBuf *b : {&l.enc_nw, &l.enc_nb, &l.dec_nw, &l.dec_nb, &l.dec_mnw, &l.dec_mnb}) dev_free(*b);
-        dev_free(e->enc_raw[i]);
-        dev_free(e->dec_raw[i]); dev_free(e->dec_uv[i]); dev_free(e->dec_out[i]);
-        dev_free(e->enc_stats[i]); dev_free(e->dec_stats[i]); dev_free(e->skip_stats[i]); dev_free(e->enc_g[i]);
-        for (ConvPlan *p : {&l.gate[0], &l.gate[1], &l.pre}) { dev_free(p->w); dev_free(p->bias); dev_free(p->wx); dev_free(p->gatew); }
+        dev_free(e->dec_out[i]);
+        dev_free(e->enc_stats[i]); dev_free(e->dec_stats[i]); dev_free(e->skip_stats[i]);
         dev_free(l.pre_nw); dev_free(l.pre_nb);
         if (i < 3) { dev_free(e->pin[i][0]); dev_free(e->pin[i][1]); dev_free(e->pre_stats[i]); }
     }
@@ -1402,7 +1195,7 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
     // walking K = 2048 alone (124 us at B = 1); the skinny 32 x 32-tile fp32 kernel (K split over the waves) takes 24
     select_gemm_route(e);
     for (int i = 0; i < SE_MAX_LEVELS; i++)
-        for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].skip, &e->lv[i].skipm, &e->lv[i].gate[0], &e->lv[i].gate[1], &e->lv[i].pre})
+        for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].pre})
             select_conv_geometry(e, *p);
     size_t spec_n = (size_t)B * e->M * T * F0 * 2;
     if ((rc = dev_alloc(e, e->maskspec, (size_t)B * T * F0 * 2))) return rc;
@@ -1413,18 +1206,8 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
         for (int r = 0; r < kRing; r++)
             if ((rc = dev_alloc(e, e->xin[i][r], nin))) return rc;
         HIPCHECK(e, hipMemsetAsync(e->xin[i][0].p, 0, nin * sizeof(float), st));  // slot 0 = the all-zero history of the first segment
-        if ((rc = dev_alloc(e, e->enc_raw[i], (size_t)B * e->Ch[i + 1] * T * e->F[i + 1]))) return rc;
-        if ((rc = dev_alloc(e, e->enc_stats[i], (size_t)B * 2 * (e->lv[i].enc.grid_x + e->lv[i].gate[0].grid_x + e->lv[i].gate[1].grid_x + 1)))) return rc;
-        if (e->variant && (rc = dev_alloc(e, e->enc_g[i], (size_t)B * e->Ch[i + 1] * T * e->F[i + 1]))) return rc;
-        if ((rc = dev_alloc(e, e->dec_stats[i], (size_t)B * 2 * (e->lv[i].dec_even.grid_x + e->lv[i].dec_odd.grid_x + 1)))) return rc;
-        if ((rc = dev_alloc(e, e->skip_stats[i], (size_t)B * 2 * (std::max(e->lv[i].skip.grid_x, e->lv[i].skipm.grid_x) + 1)))) return rc;
         const int lvl = L - 1 - i;  // decoder index i
-        const int Co = lvl == 0 ? 2 : e->Ch[lvl], Fo = 2 * e->F[lvl + 1] - 1, Fr = e->F[lvl];
-        if ((rc = dev_alloc(e, e->dec_raw[i], (size_t)B * Co * T * Fo))) return rc;
-        if (lvl > 0) {
-            if ((rc = dev_alloc(e, e->dec_uv[i], (size_t)B * 2 * Co * T * Fr))) return rc;
-            if ((rc = dev_alloc(e, e->dec_out[i], (size_t)B * Co * T * Fr))) return rc;
-        }
+        if (lvl > 0 && (rc = dev_alloc(e, e->dec_out[i], (size_t)B * e->Ch[lvl] * T * e->F[lvl]))) return rc;
     }
     for (int i = 0; i < e->npre; i++) {
         const size_t nf = (size_t)B * e->Ch[0] * T * F0;
@@ -1456,12 +1239,8 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
             if ((rc = dev_alloc(e, e->hbuf[l][p], (size_t)B * H))) return rc;
             HIPCHECK(e, hipMemsetAsync(e->hbuf[l][p].p, 0, (size_t)B * H * sizeof(float), st));
         }
-    if (e->use_p) {
-        select_all_p(e);
-        if ((rc = alloc_state_p(e, st))) return rc;
-    }
-    if ((rc = dev_alloc(e, e->gru_sync, 128))) return rc;
-    HIPCHECK(e, hipMemsetAsync(e->gru_sync.p, 0, 128 * sizeof(float), st));
+    select_all_p(e);
+    if ((rc = alloc_state_p(e, st))) return rc;
     for (int l = 0; l < 4; l++) e->hcur[l] = 0;
     e->parity = 0;
     e->slot = 0;
@@ -1483,17 +1262,12 @@ int se_reset_stream(se_engine *e, int stream_index, void *stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int T = e->T, H = e->H, b = stream_index;
     // conv time buffers = the tail of the current ring slot (the next window reads it as history)
-    for (int i = 0; i < e->L; i++) {
-        if (e->use_p) {  // plane path: [slot][b][C8][PL][T][F] pieces of 16 bytes
-            const size_t per16 = (size_t)(e->cp->slot_elems[i] / e->B);
-            HIPCHECK(e, hipMemsetAsync(e->cp->xinP[i].p + ((size_t)e->slot * e->cp->slot_elems[i] + per16 * b) * 4, 0, per16 * 16, st));
-            continue;
-        }
-        const size_t per = (size_t)e->Ch[i] * T * e->F[i];
-        HIPCHECK(e, hipMemsetAsync(e->xin[i][e->slot].p + per * b, 0, per * sizeof(float), st));
+    for (int i = 0; i < e->L; i++) {  // [slot][b][C8][PL][T][F] pieces of 16 bytes
+        const size_t per16 = (size_t)(e->cp->slot_elems[i] / e->B);
+        HIPCHECK(e, hipMemsetAsync(e->cp->xinP[i].p + ((size_t)e->slot * e->cp->slot_elems[i] + per16 * b) * 4, 0, per16 * 16, st));
     }
     for (int i = 0; i < e->npre; i++) {
-        if (e->use_p && e->cp->pre_p) {
+        if (e->cp->pre_p) {
             const size_t per16 = (size_t)(e->cp->pslot_elems / e->B);
             HIPCHECK(e, hipMemsetAsync(e->cp->pinP[i].p + ((size_t)e->slot * e->cp->pslot_elems + per16 * b) * 4, 0, per16 * 16, st));
             continue;
@@ -1516,165 +1290,11 @@ int se_forward(se_engine *e, const float *x, float *y, void *stream) {
                        static_cast<hipStream_t>(stream));
 }
 
-#ifdef SE_DBG_STFT
-// k_stft with self-checks (co-execution study): counters[0] = sig words changed during the kernel, [1] = window/twiddle
-// words changed, [2] = output values that differ when the FFT of the same round is recomputed, [3] = rounds checked
-__device__ unsigned long long g_stft_dbg[8];
-// redundant-execution checks: the same FP32 chain twice in registers (VALU), and the same LDS butterfly pass twice
-__global__ __launch_bounds__(256) void k_dbg_redundant(int iters) {
-    extern __shared__ __align__(16) float lv[];
-    const int tid = threadIdx.x;
-    unsigned bad_valu = 0, bad_lds = 0;
-    for (int it = 0; it < iters; it++) {
-        float a0 = 1.0f + tid * 1e-3f + it, b0 = 0.5f + tid * 1e-4f;
-        float a1 = a0, b1 = b0;
-        asm volatile("" : "+v"(a1), "+v"(b1));
-        float x0 = a0, x1 = a1, y0 = b0, y1 = b1;
-#pragma unroll 16
-        for (int k = 0; k < 128; k++) {
-            x0 = fmaf(x0, 0.999f, y0); y0 = fmaf(y0, 1.001f, -x0 * 1e-3f);
-            x1 = fmaf(x1, 0.999f, y1); y1 = fmaf(y1, 1.001f, -x1 * 1e-3f);
-            asm volatile("" : "+v"(x1), "+v"(y1));
-        }
-        bad_valu += (x0 != x1) || (y0 != y1);
-        // LDS: write per-thread values, barrier, read a permuted neighbour's, combine, twice into two buffers, compare
-        float *A = lv, *B = lv + 4096, *C = lv + 8192;
-        for (int i = tid; i < 4096; i += 256) A[i] = x0 + i;
-        __syncthreads();
-        for (int i = tid; i < 4096; i += 256) {
-            const int j = (i * 5 + 1) & 4095, k2 = (i * 13 + 7) & 4095;
-            B[i] = A[j] * 1.25f + A[k2];
-        }
-        __syncthreads();
-        for (int i = tid; i < 4096; i += 256) {
-            const int j = (i * 5 + 1) & 4095, k2 = (i * 13 + 7) & 4095;
-            C[i] = A[j] * 1.25f + A[k2];
-        }
-        __syncthreads();
-        for (int i = tid; i < 4096; i += 256) bad_lds += B[i] != C[i];
-        __syncthreads();
-    }
-    if (bad_valu) atomicAdd(&g_stft_dbg[4], (unsigned long long)bad_valu);
-    if (bad_lds) atomicAdd(&g_stft_dbg[5], (unsigned long long)bad_lds);
-    if (tid == 0) atomicAdd(&g_stft_dbg[6], 1ull);
-}
-__global__ __launch_bounds__(256) void k_stft_dbg(StftArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int N = a.plan.N, N2 = N / 2, K = a.K, T = a.T, F = a.F, pad = N / 2;
-    float *sig = reinterpret_cast<float *>(smem);
-    float *win = sig + K + N;
-    cf2 *tw = reinterpret_cast<cf2 *>(win + N);
-    cf2 *bufA = tw + N;
-    cf2 *bufB = bufA + kFftBatch * N2;
-    const int row = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
-    const float *src = a.src + (long)(row / a.M) * a.strideB + (long)(row % a.M) * a.strideM;
-    for (int i = tid; i < K + N; i += nth) {
-        const long k = (long)i - pad + a.off;
-        sig[i] = (i >= pad && i < pad + K && k >= 0 && k < a.L) ? src[k] : 0.0f;
-    }
-    for (int i = tid; i < N; i += nth) { win[i] = a.window[i]; tw[i] = a.tw[i]; }
-    __syncthreads();
-    unsigned bad_out = 0, bad_fill = 0, bad_p1 = 0;
-    cf2 *bufC = bufB + kFftBatch * N2;  // third buffer for the redundant fill / first pass (launch adds its bytes)
-    for (int t0 = 0; t0 < T; t0 += kFftBatch) {
-        const int nf = min(kFftBatch, T - t0);
-        // redundant fill: A and C from the same sig / win
-        for (int i = tid; i < nf * N2; i += nth) {
-            const int f = i / N2, n = i - f * N2;
-            const float *sp = sig + (t0 + f) * a.hop + 2 * n;
-            bufA[i] = cf2{win[2 * n] * sp[0], win[2 * n + 1] * sp[1]};
-        }
-        for (int i = tid; i < nf * N2; i += nth) {
-            const int f = i / N2, n = i - f * N2;
-            const float *sp = sig + (t0 + f) * a.hop + 2 * n;
-            bufC[i] = cf2{win[2 * n] * sp[0], win[2 * n + 1] * sp[1]};
-        }
-        __syncthreads();
-        for (int i = tid; i < nf * N2; i += nth) bad_fill += (bufA[i].x != bufC[i].x) || (bufA[i].y != bufC[i].y);
-        __syncthreads();
-        // redundant first pass: A -> B and A -> C
-        const int R0 = a.plan.radices[0];
-        if (R0 == 4) {
-            fft_pass<4>(bufA, bufB, N2, N2, nf, 1, tw, tid, nth, 2);
-            __syncthreads();
-            fft_pass<4>(bufA, bufC, N2, N2, nf, 1, tw, tid, nth, 2);
-            __syncthreads();
-            for (int i = tid; i < nf * N2; i += nth) bad_p1 += (bufB[i].x != bufC[i].x) || (bufB[i].y != bufC[i].y);
-            __syncthreads();
-        }
-        cf2 first[12];  // this thread's outputs of the first computation (nf*F / 256 <= 12)
-        for (int rep = 0; rep < 2; rep++) {
-            for (int i = tid; i < nf * N2; i += nth) {
-                const int f = i / N2, n = i - f * N2;
-                const float *sp = sig + (t0 + f) * a.hop + 2 * n;
-                bufA[i] = cf2{win[2 * n] * sp[0], win[2 * n + 1] * sp[1]};
-            }
-            __syncthreads();
-            const cf2 *Z = fft_run(bufA, bufB, a.plan, nf, tw);
-            int q = 0;
-            for (int i = tid; i < nf * F; i += nth, q++) {
-                const int f = i / F, k = i - f * F;
-                const cf2 v = rfft_post(Z + f * N2, k, N2, tw);
-                if (rep == 0) {
-                    if (q < 12) first[q] = v;
-                    a.spec[(long)row * a.sR + (long)(t0 + f) * a.sT + (long)k * a.sF] = v;
-                } else if (q < 12) {
-                    bad_out += (v.x != first[q].x) || (v.y != first[q].y);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (bad_fill) atomicAdd(&g_stft_dbg[4], (unsigned long long)bad_fill);
-    if (bad_p1) atomicAdd(&g_stft_dbg[5], (unsigned long long)bad_p1);
-    unsigned bad_sig = 0, bad_tab = 0;
-    for (int i = tid; i < K + N; i += nth) {
-        const long k = (long)i - pad + a.off;
-        const float want = (i >= pad && i < pad + K && k >= 0 && k < a.L) ? src[k] : 0.0f;
-        bad_sig += sig[i] != want;
-    }
-    for (int i = tid; i < N; i += nth) bad_tab += (win[i] != a.window[i]) || (tw[i].x != a.tw[i].x) || (tw[i].y != a.tw[i].y);
-    if (bad_sig) atomicAdd(&g_stft_dbg[0], (unsigned long long)bad_sig);
-    if (bad_tab) atomicAdd(&g_stft_dbg[1], (unsigned long long)bad_tab);
-    if (bad_out) atomicAdd(&g_stft_dbg[2], (unsigned long long)bad_out);
-    if (tid == 0) atomicAdd(&g_stft_dbg[3], 1ull);
-}
-#endif
 
 int se_stft(se_engine *e, const float *seg, int n, float *spec, void *stream) {
     if (!e || !seg || !spec || n <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     HIPCHECK(e, hipSetDevice(e->device));
     const long F = e->F[0], T = e->T;
-#ifdef SE_DBG_STFT
-    if (getenv("SE_DBG_REDUNDANT")) {
-        hipLaunchKernelGGL(k_dbg_redundant, dim3(n), dim3(256), 3 * 4096 * 4, static_cast<hipStream_t>(stream), 20);
-        static int calls2 = 0;
-        if (++calls2 % 1000 == 0) {
-            (void)hipDeviceSynchronize();
-            unsigned long long t[8];
-            (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_stft_dbg), sizeof(t));
-            fprintf(stderr, "[redundant dbg] after %d calls: VALU chain mismatches %llu, LDS pass mismatches %llu, workgroups %llu\n", calls2, t[4], t[5], t[6]);
-        }
-        return SE_OK;
-    }
-    if (getenv("SE_DBG_STFT_RUN")) {
-        StftArgs a{};
-        a.src = seg; a.strideB = e->K; a.strideM = 0; a.M = 1; a.off = 0; a.L = e->K;
-        a.K = e->K; a.T = e->T; a.F = e->F[0]; a.hop = e->c.hop;
-        a.spec = reinterpret_cast<cf2 *>(spec); a.sR = F * T; a.sT = 1; a.sF = T;
-        a.window = e->window.p; a.tw = reinterpret_cast<const cf2 *>(e->tw.p); a.plan = e->plan;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft_dbg), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(stft_lds_bytes(e->K, e->N) + sizeof(cf2) * kFftBatch * (e->N / 2)));
-        hipLaunchKernelGGL(k_stft_dbg, dim3(n), dim3(256), stft_lds_bytes(e->K, e->N) + sizeof(cf2) * kFftBatch * (e->N / 2), static_cast<hipStream_t>(stream), a);
-        static int calls = 0;
-        if (++calls % 1000 == 0 || getenv("SE_DBG_STFT_PRINT")) {
-            (void)hipDeviceSynchronize();
-            unsigned long long t[8];
-            (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_stft_dbg), sizeof(t));
-            fprintf(stderr, "[stft dbg] after %d calls: sig words changed %llu, table words changed %llu, recomputed outputs differing %llu, workgroups %llu, redundant fill mismatches %llu, redundant first-pass mismatches %llu\n", calls, t[0], t[1], t[2], t[3], t[4], t[5]);
-        }
-        return SE_OK;
-    }
-#endif
     return launch_stft(e, seg, e->K, 0, 1, 0, e->K, n, reinterpret_cast<cf2 *>(spec), F * T, 1, T, static_cast<hipStream_t>(stream));
 }
 
@@ -1743,7 +1363,7 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
     }
     // launch batch of segment n: with non-increasing lengths the streams still running are a prefix of the batch (see se_engine::Bact)
     static const bool compact_env = [] { const char *v = getenv("SE_RAGGED_COMPACT"); return !(v && v[0] == '0'); }();
-    const bool compact = compact_env && !e->ragged_nseg.empty() && e->use_p && e->gemm_p && e->variant == 0;
+    const bool compact = compact_env && !e->ragged_nseg.empty() && e->gemm_p && e->variant == 0;
     auto bact_of = [&](long n) {
         if (!compact) return e->B;
         int c = 0;
@@ -1772,7 +1392,7 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
         if ((rc = dev_alloc(e, e->spec_all, spec_n * CH)) || (rc = dev_alloc(e, e->mask_all, mask_n * CH))) return rc;
         // layer l of a recurrence round works on segment (round - l); SE_GRU_DIRECT=0 pins the LDS-slice step kernel, which has
         // no multi-layer form: layers then run back to back
-        const bool lagged = e->gru_lag && e->gru_direct != 0 && !e->gru_seq;
+        const bool lagged = e->gru_direct != 0;
         const int NL = e->NL, lag = lagged ? NL - 1 : 0;
         for (long c0 = 0; c0 < Nseg; c0 += CH) {
             const long cn = std::min(CH, Nseg - c0);
@@ -1897,10 +1517,8 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
     if (e->B <= 0) return fail(e, SE_ERR_STATE, "no forward has run");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int L = e->L, T = e->T, B = e->B, cur = e->slot;
-    const float *src = nullptr;
     int C = 0, F = 0, idx = -1;
-    bool gru_layout = false;
-    if (e->use_p && strncmp(name, "ft", 2)) {  // plane path: operand tensors are split-bf16 planes, summed back on the host
+    if (strncmp(name, "ft", 2)) {  // operand tensors are split-bf16 planes, summed back on the host
         se_convp_state &S = *e->cp;
         const float *psrc = nullptr;
         if (!strcmp(name, "feat")) { psrc = S.xinP[0].p + (size_t)cur * S.slot_elems[0] * 4; C = e->Ch[0]; F = e->F[0]; }
@@ -1913,39 +1531,38 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
             if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
             return p_to_host(e, psrc, C, F, host_out, st, true);
         }
-        if (e->gemm_p && sscanf(name, "enc%d", &idx) == 1 && idx == L - 1) {  // the GRU input lives as GEMM A planes [PL][B*T][(o*F+f)*8+c]
-            const int Cl = e->Ch[L], Fl = e->F[L], PLn = operand_planes(e->precision), D = e->D;
-            const size_t n = (size_t)B * Cl * T * Fl;
-            if (count) *count = (int64_t)n;
-            if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
-            std::vector<uint16_t> h((size_t)PLn * B * T * D);
-            HIPCHECK(e, hipStreamSynchronize(st));
-            HIPCHECK(e, hipMemcpy(h.data(), e->gruinP[cur].p, h.size() * 2, hipMemcpyDeviceToHost));
+        if (sscanf(name, "enc%d", &idx) != 1 || idx != L - 1) return fail(e, SE_ERR_KEY, "unknown tap %s", name);
+        // the GRU input: GEMM A planes [PL][B*T][(o*F+f)*8+c] (k_gemm_p) or fp32 rows [B][T][C*F]
+        const int Cl = e->Ch[L], Fl = e->F[L], PLn = operand_planes(e->precision), D = e->D;
+        const size_t n = (size_t)B * Cl * T * Fl;
+        if (count) *count = (int64_t)n;
+        if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
+        HIPCHECK(e, hipStreamSynchronize(st));
+        if (!e->gemm_p) {
+            std::vector<float> h(n);
+            HIPCHECK(e, hipMemcpy(h.data(), e->gru_in[cur].p, n * sizeof(float), hipMemcpyDeviceToHost));
             for (int b = 0; b < B; b++)
                 for (int c = 0; c < Cl; c++)
                     for (int t = 0; t < T; t++)
-                        for (int f = 0; f < Fl; f++) {
-                            float v = 0;
-                            for (int pl = 0; pl < PLn; pl++) {
-                                const uint16_t u = h[((size_t)pl * B * T + (size_t)b * T + t) * D + ((size_t)(c >> 3) * Fl + f) * 8 + (c & 7)];
-                                if (PLn == 1) { _Float16 hv; memcpy(&hv, &u, 2); v += (float)hv; } else v += bf16_to_f32(u);
-                            }
-                            host_out[(((size_t)b * Cl + c) * Fl + f) * T + t] = v;
-                        }
+                        for (int f = 0; f < Fl; f++) host_out[(((size_t)b * Cl + c) * Fl + f) * T + t] = h[(((size_t)b * T + t) * Cl + c) * Fl + f];
             return SE_OK;
         }
-        idx = -1;  // enc{L-1} (the fp32 GRU input) and unknown names fall through
+        std::vector<uint16_t> h((size_t)PLn * B * T * D);
+        HIPCHECK(e, hipMemcpy(h.data(), e->gruinP[cur].p, h.size() * 2, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; b++)
+            for (int c = 0; c < Cl; c++)
+                for (int t = 0; t < T; t++)
+                    for (int f = 0; f < Fl; f++) {
+                        float v = 0;
+                        for (int pl = 0; pl < PLn; pl++) {
+                            const uint16_t u = h[((size_t)pl * B * T + (size_t)b * T + t) * D + ((size_t)(c >> 3) * Fl + f) * 8 + (c & 7)];
+                            if (PLn == 1) { _Float16 hv; memcpy(&hv, &u, 2); v += (float)hv; } else v += bf16_to_f32(u);
+                        }
+                        host_out[(((size_t)b * Cl + c) * Fl + f) * T + t] = v;
+                    }
+        return SE_OK;
     }
-    if (!strcmp(name, "feat")) { src = e->xin[0][cur].p; C = e->Ch[0]; F = e->F[0]; }
-    else if (!strcmp(name, "gru")) { src = e->dec_in[cur].p; C = e->Ch[L]; F = e->F[L]; }
-    else if (sscanf(name, "enc%d", &idx) == 1 && idx >= 0 && idx < L) {
-        C = e->Ch[idx + 1]; F = e->F[idx + 1];
-        if (idx + 1 < L) src = e->xin[idx + 1][cur].p;
-        else { src = e->gru_in[cur].p; gru_layout = true; }
-    } else if (sscanf(name, "dec%d", &idx) == 1 && idx >= 0 && idx < L - 1) {
-        const int lvl = L - 1 - idx;
-        src = e->dec_out[idx].p; C = e->Ch[lvl]; F = e->F[lvl];
-    } else if (sscanf(name, "ft%d", &idx) == 1 && idx >= 0 && idx <= L) {
+    if (sscanf(name, "ft%d", &idx) == 1 && idx >= 0 && idx <= L) {
         // Pre-activation feature maps of the distillation student (distillation_crn.py:222-228, 126-128, 262-264, 467-477):
         // ft0 = last encoder block's convolution output, ft1 = fc_output_layer output ([B, T, D] memory viewed as [B, C, F, T],
         // distillation_crn.py:364), ft2.. = transposed-convolution outputs of decoder blocks 0..L-2 (before activation, norm and
@@ -1955,8 +1572,8 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         int rc = ensure_ready(e);
         if (rc) return rc;
         DevBuf tmp;
-        // On the plane path the operands of the re-run live in the P layout: k_tap_p_to_f32 sums the planes back into the
-        // first-generation fp32 buffers the re-run reads (a tap is a training / debugging aid, not part of the hot path).
+        // The operands of the re-run live in the P layout: k_tap_p_to_f32 sums the planes back into the fp32 buffers the
+        // re-run reads (a tap is a training / debugging aid, not part of the hot path).
         auto p_to_f32 = [&](const float *psrc, int C_, int F_, float *dst) -> int { return tap_p_to_f32_dev(e, psrc, C_, F_, dst, st); };
         auto finish = [&](int C_, int F_, bool raw_flat) -> int {
             const size_t n_ = (size_t)B * C_ * T * F_;
@@ -1983,11 +1600,9 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         };
         if (idx == 0) {
             const int i = L - 1, Co = e->Ch[L], Fo = e->F[L];
-            if (e->use_p) {
-                se_convp_state &S = *e->cp;
-                if ((rc = p_to_f32(S.xinP[i].p + (size_t)cur * S.slot_elems[i] * 4, e->Ch[i], e->F[i], e->xin[i][cur].p)) ||
-                    (rc = p_to_f32(S.xinP[i].p + (size_t)prev * S.slot_elems[i] * 4, e->Ch[i], e->F[i], e->xin[i][prev].p))) return rc;
-            }
+            se_convp_state &S = *e->cp;
+            if ((rc = p_to_f32(S.xinP[i].p + (size_t)cur * S.slot_elems[i] * 4, e->Ch[i], e->F[i], e->xin[i][cur].p)) ||
+                (rc = p_to_f32(S.xinP[i].p + (size_t)prev * S.slot_elems[i] * 4, e->Ch[i], e->F[i], e->xin[i][prev].p))) return rc;
             if ((rc = dev_alloc(e, tmp, (size_t)B * Co * T * Fo))) return rc;
             ConvPlan pl = e->lv[i].enc;
             pl.a.relu_lo = pl.a.relu_hi = 0;
@@ -2004,33 +1619,16 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         if (lvl <= 0) return fail(e, SE_ERR_KEY, "unknown tap %s", name);
         const int Co = e->Ch[lvl], Fo = 2 * e->F[lvl + 1] - 1;
         if ((rc = dev_alloc(e, tmp, (size_t)B * Co * T * Fo))) return rc;
-        const float *xin = j == 0 ? e->dec_in[cur].p : e->dec_out[j - 1].p;
-        if (e->use_p) {
-            se_convp_state &S = *e->cp;
-            const int Cin = e->Ch[lvl + 1], Fin = e->F[lvl + 1];
-            if ((rc = p_to_f32(j == 0 ? S.decinP[cur].p : S.decP[j - 1].p, Cin, Fin, const_cast<float *>(xin)))) { dev_free(tmp); return rc; }
-        }
+        float *xin = j == 0 ? e->dec_in[cur].p : e->dec_out[j - 1].p;
+        se_convp_state &S = *e->cp;
+        if ((rc = p_to_f32(j == 0 ? S.decinP[cur].p : S.decP[j - 1].p, e->Ch[lvl + 1], e->F[lvl + 1], xin))) { dev_free(tmp); return rc; }
         ConvPlan pe = e->lv[j].dec_even, po = e->lv[j].dec_odd;
         pe.a.relu_lo = pe.a.relu_hi = 0;
         po.a.relu_lo = po.a.relu_hi = 0;
         if ((rc = launch_conv(e, pe, xin, nullptr, tmp.p, st, "tap_ft")) || (rc = launch_conv(e, po, xin, nullptr, tmp.p, st, "tap_ft"))) { dev_free(tmp); return rc; }
         return finish(Co, Fo, false);
-    } else return fail(e, SE_ERR_KEY, "unknown tap %s", name);
-    const size_t n = (size_t)B * C * T * F;
-    if (count) *count = (int64_t)n;
-    if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
-    if (!host_out) return fail(e, SE_ERR_KEY, "tap %s has no device form", name);
-    std::vector<float> h(n);
-    HIPCHECK(e, hipStreamSynchronize(st));
-    HIPCHECK(e, hipMemcpy(h.data(), src, n * sizeof(float), hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++)
-        for (int c = 0; c < C; c++)
-            for (int t = 0; t < T; t++)
-                for (int f = 0; f < F; f++) {
-                    const size_t si = gru_layout ? (((size_t)b * T + t) * C + c) * F + f : (((size_t)b * C + c) * T + t) * F + f;
-                    host_out[(((size_t)b * C + c) * F + f) * T + t] = h[si];
-                }
-    return SE_OK;
+    }
+    return fail(e, SE_ERR_KEY, "unknown tap %s", name);
 }
 
 int se_export_state(se_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream) {
@@ -2056,14 +1654,14 @@ int se_export_state(se_engine *e, const char *name, float *host_out, int64_t cap
         if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
         std::vector<float> h(nsrc);
         HIPCHECK(e, hipStreamSynchronize(st));
-        if (e->use_p && !is_pbuf) {
+        if (!is_pbuf) {
             int rc = p_to_host(e, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4, C, F, h.data(), st, false);
             if (rc) return rc;
-        } else if (e->use_p && e->cp->pre_p) {
+        } else if (e->cp->pre_p) {
             int rc = p_to_host(e, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4, C, F, h.data(), st, false);
             if (rc) return rc;
         } else
-        HIPCHECK(e, hipMemcpy(h.data(), (is_pbuf ? e->pin[idx][e->parity] : e->xin[idx][e->slot]).p, nsrc * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHECK(e, hipMemcpy(h.data(), e->pin[idx][e->parity].p, nsrc * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t bc = 0; bc < (size_t)B * C; bc++)
             for (int f = 0; f < F; f++)
                 for (int p = 0; p < P; p++) host_out[(bc * F + f) * P + p] = h[(bc * T + (T - P + p)) * F + f];
@@ -2094,9 +1692,9 @@ int se_import_state(se_engine *e, const char *name, const float *host_in, int64_
         for (size_t bc = 0; bc < (size_t)B * C; bc++)
             for (int f = 0; f < F; f++)
                 for (int p = 0; p < P; p++) h[(bc * T + (T - P + p)) * F + f] = host_in[(bc * F + f) * P + p];
-        if (e->use_p && !is_pbuf) return host_to_p(e, h, C, F, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4);
-        if (e->use_p && e->cp->pre_p) return host_to_p(e, h, C, F, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4);
-        HIPCHECK(e, hipMemcpy((is_pbuf ? e->pin[idx][e->parity] : e->xin[idx][e->slot]).p, h.data(), nsrc * sizeof(float), hipMemcpyHostToDevice));
+        if (!is_pbuf) return host_to_p(e, h, C, F, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4);
+        if (e->cp->pre_p) return host_to_p(e, h, C, F, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4);
+        HIPCHECK(e, hipMemcpy(e->pin[idx][e->parity].p, h.data(), nsrc * sizeof(float), hipMemcpyHostToDevice));
         return SE_OK;
     }
     return fail(e, SE_ERR_KEY, "unknown state %s", name);

@@ -85,8 +85,8 @@ int train_conv_geometry(int kind, int Ci, int Co, int T, int Fi, int Fy, int dil
     a.Ci = Ci; a.Co = Co; a.CoPad = CoPad; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
     a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = grouped;
     a.ntap = ntap; a.CC = CC; a.nchunk = nchunk; a.tiles_per_wg = tpw; a.St = St;
-    a.relu_lo = 0; a.relu_hi = 0; a.act = 0; a.gate_pairs = 0; a.Cy = Co; a.cy0 = 0; a.par_rows = 0; a.gatew = nullptr;
-    a.stats = nullptr; a.blend = 0;
+    a.relu_lo = 0; a.relu_hi = 0; a.act = 0; a.Cy = Co; a.cy0 = 0; a.par_rows = 0; a.gatew = nullptr;
+    a.stats = nullptr;
     for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; g.tap_kf[t] = taps[t][0]; g.tap_kt[t] = taps[t][1]; }
     g.NT = NT; g.grid_x = n_wg; g.lds = bytes(CC);
     return 0;

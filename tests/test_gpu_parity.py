@@ -397,6 +397,24 @@ def test_variant_dropin_classes(vgolden):
     assert rel_rms(y2.cpu().numpy(), vgolden["student_full400_out"]) < TOL
 
 
+# ---- which CRN geometries se_reset accepts (crn_geometry_supported in se_engine.hip) ----------------------------------------
+@pytest.mark.parametrize("cfg,variant,accepted", [
+    (TINY, 0, True), (FULL400, 0, True), (FULL512, 0, True), (STUDENT400, 2, True),
+    (dict(FULL400, num_channels=[2, 2, 2, 2], hidden=16), 0, True),
+    (dict(FULL400, num_channels=[128, 128, 128, 128]), 0, False),  # a skip connection's 1x1 pair: 2 x 128 GEMM rows
+    (dict(FULL400, num_channels=[16, 32, 64, 40]), 1, False),      # CRN_ELU gated pair of 40 channels: 80 rows = 3 row tiles
+    (dict(FULL400, num_channels=[16, 32, 64, 40]), 0, True),       # the same channels without the gated pair
+    (dict(FULL400, num_inputs=5), 1, False),                       # pre-conv blocks: at most 8 feature channels
+], ids=["tiny", "full400", "full512", "student400", "ch2_tiny", "crn_128x4", "elu_c40", "crn_c40", "elu_5_inputs"])
+def test_crn_geometry_acceptance(cfg, variant, accepted):
+    e = _engine_v(cfg, variant)
+    if accepted:
+        e.reset(2)
+    else:
+        with pytest.raises(RuntimeError, match=r"se_engine error -1:"):  # SE_ERR_ARG
+            e.reset(2)
+
+
 # ---- a14 / a15: FullSubNet ----------------------------------------------------------------------------------------------
 from conftest import FSN_FULL, FSN_TINY, fsn_spec  # noqa: E402
 
