@@ -140,7 +140,7 @@ int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap,
                     int64_t *launches, double *flops_per_launch);
 
 int se_abi_version(void);  /* 4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
-                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd */
+                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_* */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -337,6 +337,29 @@ int se_train_conv_w(int kind, const float *x, const float *xprev, const float *w
 int se_train_conv_wgrad_det(const float *G, const float *S, const float *Sprev, float *ws, int *nsplit_out, int B, int Ca, int Cb, int T, int Fm,
                             int Fs, int dil, int ntap, void *stream);
 int se_train_gemm_tn_det(const float *A, const float *B, float *ws, int *nsplit_out, int64_t R, int Na, int Nb, void *stream);
+
+/* ---- distillation training (reference distillation_crn.py:504-572; csrc/se_distill.hip; ABI-4 additions) ---------------------
+ * se_train_add_csum: dst[S][C][X] += src, then part[S][C] = per-(row, channel) sums of the result (fold with se_train_colsum):
+ * injects a feature-map gradient into a pre-activation gradient and gives the bias gradient slab.
+ * se_distill_*: the feature loss  sum_i mean((v_i - t'_i)^2 * mask_i) / nmaps  with v = BatchNorm2d(W s) (1x1 connector, no
+ * bias), t' = max(t, margin_c), margin_c = sum(t[t<0]) / (count(t<0) + 1e-8) per channel, mask = 1 - (v <= t' & t' <= 0).
+ * Every map is [S][C][X] (X contiguous per row and channel; teacher and student in the same layout).  training != 0: batch
+ * statistics, running_mean / running_var (momentum 0.1, unbiased variance) and num_batches_tracked are updated on the device;
+ * training == 0: the running statistics normalise (nn.BatchNorm2d eval).  Cs <= 64, Ct <= 128, nmaps <= 8.
+ * fwd writes loss[0] = the total and loss[1 + i] = the mean of map i; ws (se_distill_ws_bytes) carries the statistics to bwd, which
+ * takes the upstream gradient gout[0] from device memory and writes ds, dw, dgamma, dbeta (ds may be null: no input gradient).
+ * No float atomics: results are bit-reproducible. */
+typedef struct {
+    const float *s, *t, *w, *gamma, *beta;      /* student [S][Cs][X], teacher [S][Ct][X], W [Ct][Cs], BN affine [Ct] */
+    float *running_mean, *running_var;          /* [Ct] */
+    int64_t *num_batches_tracked;               /* [1] */
+    float *ds, *dw, *dgamma, *dbeta;            /* gradients: [S][Cs][X], [Ct][Cs], [Ct], [Ct] */
+    int Cs, Ct, X, pad_;
+} se_distill_map;
+int se_train_add_csum(float *dst, const float *src, float *part, int S, int C, int64_t X, void *stream);
+int64_t se_distill_ws_bytes(const se_distill_map *maps, int nmaps, int S);
+int se_distill_fwd(const se_distill_map *maps, int nmaps, int S, int training, void *ws, float *loss, void *stream);
+int se_distill_bwd(const se_distill_map *maps, int nmaps, int S, int training, void *ws, const float *gout, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -141,11 +141,14 @@ def transpose(w):
 
 
 class CRNFunction(torch.autograd.Function):
-    """pred = realtime_process(mixture) for the CRN.py (variant 0) and CRN_ELU.py (variant 1, the model train.py:16 trains) networks.
-    forward(ctx, model, mixture, flag, *params)."""
+    """pred = realtime_process(mixture) for the CRN.py (variant 0), CRN_ELU.py (variant 1, the model train.py:16 trains) and
+    distillation_crn.py (variant 2) networks.  forward(ctx, model, mixture, flag, *params).  features=True (CRNFeatFunction, variant 2):
+    the five distillation feature maps are extra outputs in the training layout - f0, f2..f4 [S][C][T][F] before activation, f1 the
+    fc output [S*T][D] - and the backward adds their gradients (None: skipped) into the pre-activation gradients, bias gradients
+    included."""
 
     @staticmethod
-    def forward(ctx, model, mixture, flag, *params):
+    def forward(ctx, model, mixture, flag, *params, features=False):
         lib = K._lib()
         K._need_gpu(mixture, params[0])
         dev = mixture.device
@@ -177,9 +180,12 @@ class CRNFunction(torch.autograd.Function):
         spec = _new(N, B * M, T, F0, 2, dev=dev)
         _run("k_stft", 0.0, lib.se_sig_stft, sig, _p(mixture), B, M, L, off0, P, N, _p(spec), st())
         V = model._VARIANT            # 0 = CRN.py (ReLU); 1 = CRN_ELU.py (ELU, gated 1x1 pair per block, three 5x5 pre-conv blocks, atan2 phase)
-        if V not in (0, 1):
-            raise NotImplementedError("the training kernels cover CRN.py and CRN_ELU.py (the student is trained by distillation, out of scope)")
+        if V not in (0, 1, 2):        # 2 = distillation_crn.py: variant 1 with arctan phase and gLN denominator sqrt(var) + EPS
+            raise NotImplementedError(f"no training kernels for variant {V}")
+        if features and V != 2:
+            raise ValueError("feature maps exist for the distillation_crn.py architecture (variant 2) only")
         act = 2 if V else 1
+        em = 1 if V == 2 else 0       # eps_mode of every gLN
 
         def first_slab(t, key, idx):   # slab 0 = the carried state of a flag=True continuation, zeros after a reset
             t[0].copy_(state[key][idx]) if state is not None and state.get(key) is not None else t[0].zero_()
@@ -190,7 +196,7 @@ class CRNFunction(torch.autograd.Function):
             conv_w(3, _p(a_t), None, blk.conv_trans.weight, Co, 1, blk.conv_trans.bias, tg, S, Co, Co, T, Fo, Fo, 0, 0, 2 * Co, 0)
             conv_w(3, _p(a_t), None, blk.conv_gated.weight, Co, 1, blk.conv_gated.bias, tg, S, Co, Co, T, Fo, Fo, 0, 0, 2 * Co, Co)
             stt = _new(S, 2, dev=dev)
-            _run("k_tgate_fwd", 0.0, lib.se_train_gate_fwd, _p(tg), _p(blk.norm.weight), _p(blk.norm.bias), y_ptr, *ys, _p(stt), S, Co, T, Fo, 0, st())
+            _run("k_tgate_fwd", 0.0, lib.se_train_gate_fwd, _p(tg), _p(blk.norm.weight), _p(blk.norm.bias), y_ptr, *ys, _p(stt), S, Co, T, Fo, em, st())
             return tg, stt
 
         xin = []
@@ -198,7 +204,7 @@ class CRNFunction(torch.autograd.Function):
         x_full = _new(N + 1, B, C0, T, F0, dev=dev)
         slab0 = B * C0 * T * F0
         first_slab(x_full, "pbuf" if V else "buf", 0)
-        _run("k_tfeat", 0.0, lib.se_train_feat, _p(spec), _p(x_full, slab0), S, M, T, F0, 1 if V else 0, st())
+        _run("k_tfeat", 0.0, lib.se_train_feat, _p(spec), _p(x_full, slab0), S, M, T, F0, 1 if V == 1 else 0, st())
         pre = []
         if V:  # x = block(x) + x, three times (CRN_ELU.py:375-376)
             cur = x_full
@@ -223,6 +229,9 @@ class CRNFunction(torch.autograd.Function):
             y = _new(S, Co, T, Fo, dev=dev)   # variant 0: the pre-activation; variant 1: ELU(conv), all the backward needs
             conv_w(0, _p(xin[i], slab), _p(xin[i]), blk.conv.weight, Ci * 15, 15, blk.conv.bias, y, S, Ci, Co, T, Fi, Fo, d, 2 if V else 0)
             ys.append(y)
+            if features and i == Lv - 1:  # f0: the same convolution without activation
+                f0 = _new(S, Co, T, Fo, dev=dev)
+                conv_w(0, _p(xin[i], slab), _p(xin[i]), blk.conv.weight, Ci * 15, 15, blk.conv.bias, f0, S, Ci, Co, T, Fi, Fo, d, 0)
             if i < Lv - 1:
                 nxt = _new(N + 1, B, Co, T, Fo, dev=dev)
                 first_slab(nxt, "buf", i + 1)
@@ -237,7 +246,7 @@ class CRNFunction(torch.autograd.Function):
                 enc_tg.append(tg)
                 stats_e.append(stt)
             else:
-                stats_e.append(gln_fwd(y, (Co * T * Fo, T * Fo, Fo), y_ptr, ysd, blk.norm.weight, blk.norm.bias, S, Co, T, Fo, Fo, 0, 1))
+                stats_e.append(gln_fwd(y, (Co * T * Fo, T * Fo, Fo), y_ptr, ysd, blk.norm.weight, blk.norm.bias, S, Co, T, Fo, Fo, 0, 1, em))
         CL, FL = ch[Lv], Fq[Lv]
         D = CL * FL
         g = model.gru.sequence_model
@@ -293,7 +302,7 @@ class CRNFunction(torch.autograd.Function):
         fc = model.gru.fc_output_layer
         o_fc = K._gemm(layer_in, fc.weight, fc.bias)  # [R, D] pre-activation
         xd = _new(S, CL, T, FL, dev=dev)
-        st_fc = gln_fwd(o_fc, (T * D, FL, D), _p(xd), (CL * T * FL, T * FL, FL), model.gru.norm.weight, model.gru.norm.bias, S, CL, T, FL, FL, 1, act)
+        st_fc = gln_fwd(o_fc, (T * D, FL, D), _p(xd), (CL * T * FL, T * FL, FL), model.gru.norm.weight, model.gru.norm.bias, S, CL, T, FL, FL, 1, act, em)
         dec = []
         x_in = xd
         Ci, Fi = CL, FL
@@ -309,7 +318,7 @@ class CRNFunction(torch.autograd.Function):
                 if Fr < Fy or Cr != Co:
                     raise RuntimeError("decoder / skip geometry outside the reference's (CRN.py:389-392 crop branch is never taken)")
                 z = _new(S, Co, T, Fr, dev=dev)
-                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(z), (Co * T * Fr, T * Fr, Fr), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fr, 0, act)
+                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(z), (Co * T * Fr, T * Fr, Fr), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fr, 0, act, em)
                 wuv = _new(2 * Co, Cr, dev=dev)
                 buv = _new(2 * Co, dev=dev)
                 wuv[:Co].copy_(blk.residual.weight.view(Co, Cr)); wuv[Co:].copy_(blk.residualmask.weight.view(Co, Cr))
@@ -320,12 +329,12 @@ class CRNFunction(torch.autograd.Function):
                 out = _new(S, Co, T, Fr, dev=dev)
                 st_uv = _new(S, 2, dev=dev)
                 _run("k_tskip_fwd", 0.0, lib.se_train_skip_fwd, _p(uv), _p(z), _p(blk.residualnorm.weight), _p(blk.residualnorm.bias), _p(out), _p(st_uv),
-                     S, Co, T, Fr, act, 0, st())
+                     S, Co, T, Fr, act, em, st())
                 rec.update(z=z, uv=uv, wuv=wuv, st_uv=st_uv, k=k, Cr=Cr, Fr=Fr)
                 x_in, Ci, Fi = out, Co, Fr
             else:
                 xl = _new(S, Co, T, Fy, dev=dev)
-                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(xl), (Co * T * Fy, T * Fy, Fy), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fy, 0, act)
+                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(xl), (Co * T * Fy, T * Fy, Fy), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fy, 0, act, em)
                 rec["xl"] = xl
                 if Co != 2 or Fy != F0:
                     raise RuntimeError("last decoder block must produce the 2-channel mask at full resolution")
@@ -342,20 +351,30 @@ class CRNFunction(torch.autograd.Function):
         model._state = dict(buf=[xin[i][N] for i in range(Lv)], h=hTs, pbuf=[r["cur"][N] for r in pre] if V else None)
         ctx.model = model
         ctx.dims = dict(B=B, M=M, L=Lout, N=N, S=S, T=T, F0=F0, Ks=Ks, skip=skip, ch=ch, Fq=Fq, Lv=Lv, H=H, NL=NL, D=D, CL=CL, FL=FL, n_fft=n_fft, sig=sig)
-        ctx.sv = dict(V=V, act=act, pre=pre, enc_tg=enc_tg, spec=spec, xin=xin, ys=ys, stats_e=stats_e, seq=seq, outs=outs, gates=gates, h0s=h0s, o_fc=o_fc, st_fc=st_fc, dec=dec, xl=xl)
+        ctx.sv = dict(V=V, act=act, em=em, pre=pre, enc_tg=enc_tg, spec=spec, xin=xin, ys=ys, stats_e=stats_e, seq=seq, outs=outs, gates=gates, h0s=h0s, o_fc=o_fc, st_fc=st_fc, dec=dec, xl=xl)
+        if features:
+            return (pred, f0, o_fc) + tuple(r["yd"] for r in dec[:Lv - 1])
         return pred
 
     @staticmethod
-    def backward(ctx, dpred):
+    def backward(ctx, dpred, *dfeats):
         lib = K._lib()
         model, q, sv = ctx.model, ctx.dims, ctx.sv
+        if dpred is None:  # features=True and only the feature maps reach the loss
+            dpred = torch.zeros(q["B"], q["L"], device=sv["spec"].device)
         B, M, L, N, S, T, F0, Ks, skip = q["B"], q["M"], q["L"], q["N"], q["S"], q["T"], q["F0"], q["Ks"], q["skip"]
         ch, Fq, Lv, H, NL, D, CL, FL, sig = q["ch"], q["Fq"], q["Lv"], q["H"], q["NL"], q["D"], q["CL"], q["FL"], q["sig"]
         dev = dpred.device
         st = K._st
         dpred = dpred.contiguous()
         grads = {}
-        V, act = sv["V"], sv["act"]
+        V, act, em = sv["V"], sv["act"], sv["em"]
+        dfeats = [None if g is None else g.contiguous() for g in dfeats] + [None] * (2 + Lv - 1 - len(dfeats))
+
+        def inject(dpre, gf, Cc, X):  # dpre += d feature map; -> the bias gradient (per-channel sums of the result)
+            part = _new(S, Cc, dev=dev)
+            _run("k_add_csum", 0.0, lib.se_train_add_csum, _p(dpre), _p(gf), _p(part), S, Cc, X, st())
+            return colsum3(S, (part, Cc))[0]
         zero_bias = torch.zeros(256, device=dev)
 
         gseg = _new(S, Ks, dev=dev)
@@ -376,7 +395,7 @@ class CRNFunction(torch.autograd.Function):
                 dz = _new(S, Co, T, Fr, dev=dev)
                 pw, pb, pbias = _new(S, Co, dev=dev), _new(S, Co, dev=dev), _new(S, 2 * Co, dev=dev)
                 _run("k_tskip_bwd", 0.0, lib.se_train_skip_bwd, _p(dout), _p(rec["uv"]), _p(rec["z"]), _p(blk.residualnorm.weight), _p(blk.residualnorm.bias),
-                     _p(rec["st_uv"]), _p(duv), _p(dz), _p(pw), _p(pb), _p(pbias), S, Co, T, Fr, act, 0, st())
+                     _p(rec["st_uv"]), _p(duv), _p(dz), _p(pw), _p(pb), _p(pbias), S, Co, T, Fr, act, em, st())
                 dnw, dnb, dbuv = colsum3(S, (pw, Co), (pb, Co), (pbias, 2 * Co))
                 grads[pre + "residualnorm.weight"], grads[pre + "residualnorm.bias"] = dnw, dnb
                 grads[pre + "residual.bias"], grads[pre + "residualmask.bias"] = dbuv[:Co], dbuv[Co:]
@@ -389,7 +408,9 @@ class CRNFunction(torch.autograd.Function):
                 dy_ptr, ds = _p(dz), (Co * T * Fr, T * Fr, Fr)
             else:
                 dy_ptr, ds = _p(dout), (Co * T * Fy, T * Fy, Fy)
-            dyd, dw, db, dpre = gln_bwd(dy_ptr, ds, rec["yd"], (Co * T * Fy, T * Fy, Fy), blk.norm.weight, rec["st"], S, Co, T, Fy, 0, act)
+            dyd, dw, db, dpre = gln_bwd(dy_ptr, ds, rec["yd"], (Co * T * Fy, T * Fy, Fy), blk.norm.weight, rec["st"], S, Co, T, Fy, 0, act, em)
+            if j < Lv - 1 and dfeats[2 + j] is not None:
+                dpre = inject(dyd, dfeats[2 + j], Co, T * Fy)
             grads[pre + "norm.weight"], grads[pre + "norm.bias"], grads[pre + "conv.bias"] = dw, db, dpre
             grads[pre + "conv.weight"] = wgrad(rec["x_in"], dyd, None, S, Ci, Co, T, Fi, Fy, d, 15)
             din = _new(S, Ci, T, Fi, dev=dev)
@@ -398,7 +419,10 @@ class CRNFunction(torch.autograd.Function):
         # bottleneck: gLN(last) + ReLU + fc, then the GRU layers in reverse
         R = S * T
         fc = model.gru.fc_output_layer
-        do_fc, dw, db, dpre = gln_bwd(_p(dout), (CL * T * FL, T * FL, FL), sv["o_fc"], (T * D, FL, D), model.gru.norm.weight, sv["st_fc"], S, CL, T, FL, 1, act)
+        do_fc, dw, db, dpre = gln_bwd(_p(dout), (CL * T * FL, T * FL, FL), sv["o_fc"], (T * D, FL, D), model.gru.norm.weight, sv["st_fc"], S, CL, T, FL, 1, act, em)
+        if dfeats[1] is not None:
+            _run("k_tadd", 0.0, lib.se_train_add, _p(do_fc), _p(dfeats[1]), do_fc.numel(), st())
+            dpre = colsum_tall(do_fc)
         grads["gru.norm.weight"], grads["gru.norm.bias"], grads["gru.fc_output_layer.bias"] = dw, db, dpre
         top = sv["outs"][NL - 1]
         grads["gru.fc_output_layer.weight"] = gemm_tn(do_fc, top)
@@ -426,7 +450,7 @@ class CRNFunction(torch.autograd.Function):
             """through gLN + gated pair + ELU: returns dy of the convolution that produced a_t (in place in a fresh tensor)."""
             dtg = _new(S, 2 * Co, T, Fo, dev=dev)
             pw, pb, pbias = _new(S, Co, dev=dev), _new(S, Co, dev=dev), _new(S, 2 * Co, dev=dev)
-            _run("k_tgate_bwd", 0.0, lib.se_train_gate_bwd, dy_ptr, *ds, _p(tg), _p(blk.norm.weight), _p(stt), _p(dtg), _p(pw), _p(pb), _p(pbias), S, Co, T, Fo, 0, st())
+            _run("k_tgate_bwd", 0.0, lib.se_train_gate_bwd, dy_ptr, *ds, _p(tg), _p(blk.norm.weight), _p(stt), _p(dtg), _p(pw), _p(pb), _p(pbias), S, Co, T, Fo, em, st())
             dnw, dnb, dbtg = colsum3(S, (pw, Co), (pb, Co), (pbias, 2 * Co))
             grads[pre + "norm.weight"], grads[pre + "norm.bias"] = dnw, dnb
             grads[pre + "conv_trans.bias"], grads[pre + "conv_gated.bias"] = dbtg[:Co], dbtg[Co:]
@@ -450,8 +474,10 @@ class CRNFunction(torch.autograd.Function):
             pre = f"convlist.{i}."
             if V:
                 dy = gate_pair_bwd(dy_ptr, ds, sv["ys"][i], sv["enc_tg"][i], sv["stats_e"][i], blk, Co, Fo, pre)
+                if i == Lv - 1 and dfeats[0] is not None:
+                    grads[pre + "conv.bias"] = inject(dy, dfeats[0], Co, T * Fo)
             else:
-                dy, dw, db, dpre = gln_bwd(dy_ptr, ds, sv["ys"][i], (Co * T * Fo, T * Fo, Fo), blk.norm.weight, sv["stats_e"][i], S, Co, T, Fo, 0, 1)
+                dy, dw, db, dpre = gln_bwd(dy_ptr, ds, sv["ys"][i], (Co * T * Fo, T * Fo, Fo), blk.norm.weight, sv["stats_e"][i], S, Co, T, Fo, 0, 1, em)
                 grads[pre + "norm.weight"], grads[pre + "norm.bias"], grads[pre + "conv.bias"] = dw, db, dpre
             slab = B * Ci * T * Fi
             grads[pre + "conv.weight"] = wgrad(dy, _p(sv["xin"][i], slab), _p(sv["xin"][i]), S, Co, Ci, T, Fo, Fi, d, 15)
@@ -490,6 +516,24 @@ class CRNFunction(torch.autograd.Function):
         return (None, None, None, *out)
 
 
-def realtime_process_fused(model, mixture, flag=False):
+class CRNFeatFunction(torch.autograd.Function):
+    """CRNFunction with features=True: (pred, f0, f1, f2, ...)."""
+
+    @staticmethod
+    def forward(ctx, model, mixture, flag, *params):
+        ctx.set_materialize_grads(False)
+        return CRNFunction.forward(ctx, model, mixture, flag, *params, features=True)
+
+    @staticmethod
+    def backward(ctx, dpred, *dfeats):
+        return CRNFunction.backward(ctx, dpred, *dfeats)
+
+
+def realtime_process_fused(model, mixture, flag=False, features=False):
     params = [p for _, p in model.named_parameters()]
-    return CRNFunction.apply(model, mixture, bool(flag), *params)
+    if not features:
+        return CRNFunction.apply(model, mixture, bool(flag), *params)
+    pred, f0, f1, *fd = CRNFeatFunction.apply(model, mixture, bool(flag), *params)
+    S, C, T, F = f0.shape
+    # the reference layout [N*B, C, F, T] as views: f1 is the fc output [S*T][D] reshaped (not permuted), like distillation_crn.py:368
+    return pred, [f0.transpose(2, 3), f1.view(S, C, F, T)] + [f.transpose(2, 3) for f in fd]

@@ -20,17 +20,20 @@ import torch.nn.functional as Fn
 
 from .crn import TemporalCRN
 from .crn_elu import TemporalCRN as TemporalCRNELU
+from .distillation_crn import TemporalCRN as TemporalStudentCRN
 from .losses import cal_si_snr
 
 EPS = 1e-8
 
 
-def _gln(x, w, b):
-    """GlobalLayerNorm(time=False), CRN.py:135-149: per-sample stats over all non-batch dims."""
+def _gln(x, w, b, eps_mode=0):
+    """GlobalLayerNorm(time=False), CRN.py:135-149: per-sample stats over all non-batch dims.  eps_mode 1: the denominator
+    sqrt(var) + EPS of distillation_crn.py:51 (variant 2)."""
     dims = tuple(range(1, x.dim()))
     mean = x.mean(dims, keepdim=True)
     var = ((x - mean) ** 2).mean(dims, keepdim=True)
-    return (x - mean) / (torch.sqrt(var + EPS) + EPS) * w + b
+    sd = torch.sqrt(var) if eps_mode else torch.sqrt(var + EPS)
+    return (x - mean) / (sd + EPS) * w + b
 
 
 class _TrainableMixin:
@@ -81,13 +84,15 @@ class _TrainableMixin:
         y = torch.istft(spec.reshape(-1, *spec.shape[-2:]), self._nfft, self._hop, self._win, w, center=True, normalized=False, onesided=True)
         return y.reshape(*shp, y.shape[-1])
 
-    # ---- one segment, CRN.py:454-496 (variant 0) / CRN_ELU.py:367-407 (variant 1) ----
-    def _forward_segment(self, X, state):
-        """X [B, M, F, T] complex; state = dict(buf=[...], h=tensor|None, pbuf=[...]) (detached, like CRN.py:281,334)."""
+    # ---- one segment, CRN.py:454-496 (variant 0) / CRN_ELU.py:367-407 (variant 1) / distillation_crn.py:337-380 (variant 2) ----
+    def _forward_segment(self, X, state, feats=None):
+        """X [B, M, F, T] complex; state = dict(buf=[...], h=tensor|None, pbuf=[...]) (detached, like CRN.py:281,334).
+        feats: a list that receives the five distillation feature maps [B, C, F, T] (distillation_crn.py:451-477)."""
         V = self._VARIANT
+        em = 1 if V == 2 else 0  # gLN denominator sqrt(var) + EPS (distillation_crn.py:51)
         actf = Fn.elu if V else torch.relu
         re, im = X.real, X.imag
-        ang = torch.atan2(im, re) if V else torch.atan(im / (re + EPS) + EPS)
+        ang = torch.atan2(im, re) if V == 1 else torch.atan(im / (re + EPS) + EPS)
         mag = torch.sqrt(re ** 2 + im ** 2 + 1e-10)
         x = torch.cat([mag, ang[:, :1] - ang[:, 1:]], dim=1)
 
@@ -101,7 +106,7 @@ class _TrainableMixin:
                 buf = state["pbuf"][k] if state.get("pbuf") is not None else x.new_zeros(x.shape[0], x.shape[1], x.shape[2], 4)
                 y = Fn.conv2d(torch.cat([buf, x], dim=-1), blk.conv.weight, blk.conv.bias, stride=(1, 1), padding=(2 * fd, 0), dilation=(fd, 1))
                 new_pbuf.append(x[..., -4:].detach())
-                x = _gln(gated(blk, actf(y)), blk.norm.weight, blk.norm.bias) + x
+                x = _gln(gated(blk, actf(y)), blk.norm.weight, blk.norm.bias, em) + x
         residuals = [x]
         new_buf = []
         for i, blk in enumerate(self.convlist):
@@ -111,26 +116,33 @@ class _TrainableMixin:
             inp = torch.cat([buf, x], dim=-1)
             y = Fn.conv2d(inp, blk.conv.weight, blk.conv.bias, stride=(2, 1), padding=(2, 0), dilation=(1, d))
             new_buf.append(x[..., -P:].detach())
-            x = _gln(gated(blk, actf(y)) if V else actf(y), blk.norm.weight, blk.norm.bias)
+            x = _gln(gated(blk, actf(y)) if V else actf(y), blk.norm.weight, blk.norm.bias, em)
             residuals.append(x)
+        if feats is not None:
+            feats.append(y)  # ft0: the last encoder convolution before ELU
         B, C, Fq, T = x.shape
         seq = x.reshape(B, C * Fq, T).permute(0, 2, 1)
         o, h = self.gru.sequence_model(seq, state["h"])
-        o = actf(self.gru.fc_output_layer(o))
-        o = _gln(o.unsqueeze(1), self.gru.norm.weight, self.gru.norm.bias).squeeze(1)
+        o = self.gru.fc_output_layer(o)
+        if feats is not None:
+            feats.append(o.reshape(B, C, Fq, T))  # ft1: [B, T, D] reshaped, not permuted (distillation_crn.py:368)
+        o = actf(o)
+        o = _gln(o.unsqueeze(1), self.gru.norm.weight, self.gru.norm.bias, em).squeeze(1)
         x = o.permute(0, 2, 1).reshape(B, C, Fq, T)
         L = len(self.deconvlist)
         for j, blk in enumerate(self.deconvlist):
             d = 2 ** j
             y = Fn.conv_transpose2d(x, blk.conv.weight, blk.conv.bias, stride=(2, 1), padding=(2, 0), dilation=(1, d))[..., -T:]
-            y = _gln(actf(y), blk.norm.weight, blk.norm.bias)
+            if feats is not None and j < L - 1:
+                feats.append(y)  # ft2..: the transposed-convolution outputs before activation
+            y = _gln(actf(y), blk.norm.weight, blk.norm.bias, em)
             if j < L - 1:
                 res = residuals[-2 - j]
                 if res.shape[2] > y.shape[2]:
                     y = Fn.pad(y, (0, 0, 0, res.shape[2] - y.shape[2]))
                 elif res.shape[2] < y.shape[2]:
                     y = y[:, :, :res.shape[2]]
-                m = torch.sigmoid(_gln(Fn.conv2d(res, blk.residualmask.weight, blk.residualmask.bias), blk.residualnorm.weight, blk.residualnorm.bias))
+                m = torch.sigmoid(_gln(Fn.conv2d(res, blk.residualmask.weight, blk.residualmask.bias), blk.residualnorm.weight, blk.residualnorm.bias, em))
                 y = m * actf(Fn.conv2d(res, blk.residual.weight, blk.residual.bias)) + (1.0 - m) * y
             x = y
         m = x.clamp(-9.9, 9.9)  # decompress_cIRM, utility.py:439-442 (the clamp has zero gradient outside, like the reference's masks)
@@ -138,13 +150,16 @@ class _TrainableMixin:
         Y = torch.complex(m[:, 0] * re[:, 0] - m[:, 1] * im[:, 0], m[:, 1] * re[:, 0] + m[:, 0] * im[:, 0])
         return Y, dict(buf=new_buf, h=h.detach(), pbuf=new_pbuf if V else None)
 
-    def realtime_process_train(self, mixture, flag=False):
-        """Differentiable realtime_process (CRN.py:560-589): [B, M, L] -> [B, L]."""
+    def realtime_process_train(self, mixture, flag=False, features=False):
+        """Differentiable realtime_process (CRN.py:560-589): [B, M, L] -> [B, L].  features=True (variant 2): returns (pred, [ft0..ft4])
+        with the five distillation feature maps [N*B, C, F, T], window-major (distillation_crn.py:451-477)."""
+        if features and self._VARIANT != 2:
+            raise ValueError("feature maps exist for the distillation_crn.py architecture (variant 2) only")
         if self._hip:  # every stage forward and backward on the hand-written kernels, one autograd node (train_net.py)
             from .train_net import realtime_process_fused
             if self._hip_state_from_torch:
                 raise RuntimeError("flag=True continuation across a use_hip_kernels() switch is not supported: start with flag=False")
-            return realtime_process_fused(self, mixture, flag)
+            return realtime_process_fused(self, mixture, flag, features=features)
         K = self.segment_length
         P = K // 2
         if not flag:
@@ -154,9 +169,13 @@ class _TrainableMixin:
         X = self._stft(seg)  # [B, M, N, F, T]
         state = self._state
         outs = []
+        fts = [] if features else None
         for n in range(X.shape[2]):
-            Y, state = self._forward_segment(X[:, :, n], state)
+            f = [] if features else None
+            Y, state = self._forward_segment(X[:, :, n], state, f)
             outs.append(self._istft(Y))
+            if features:
+                fts.append(f)
         y = torch.stack(outs, dim=1)  # [B, N, K]
         self._state = state
         B, N, _ = y.shape
@@ -165,7 +184,10 @@ class _TrainableMixin:
         out = (s1 + s2) / 2
         if gap > 0:
             out = out[:, :-gap]
-        return out if flag else out[:, P:]
+        out = out if flag else out[:, P:]
+        if features:
+            return out, [torch.cat([f[k] for f in fts], dim=0) for k in range(len(fts[0]))]
+        return out
 
 
 class TrainableCRN(_TrainableMixin, TemporalCRN):
@@ -174,6 +196,12 @@ class TrainableCRN(_TrainableMixin, TemporalCRN):
 
 class TrainableCRNELU(_TrainableMixin, TemporalCRNELU):
     """CRN_ELU.py TemporalCRN (variant 1) - the model the reference's train.py imports and trains (train.py:16)."""
+
+
+class TrainableStudentCRN(_TrainableMixin, TemporalStudentCRN):
+    """distillation_crn.py TemporalCRN (variant 2: arctan phase, gLN denominator sqrt(var) + EPS), the teacher and the student of
+    distillation_crn.DistillationCRN.  realtime_process stays the inference engine (weights re-uploaded after every optimizer step);
+    realtime_process_train(..., features=True) is the differentiable forward with the five feature maps."""
 
 
 def si_snr_loss(pred, source, length=None):
