@@ -140,7 +140,7 @@ int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap,
                     int64_t *launches, double *flops_per_launch);
 
 int se_abi_version(void);  /* 4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
-                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_* */
+                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -360,6 +360,23 @@ int se_train_add_csum(float *dst, const float *src, float *part, int S, int C, i
 int64_t se_distill_ws_bytes(const se_distill_map *maps, int nmaps, int S);
 int se_distill_fwd(const se_distill_map *maps, int nmaps, int S, int training, void *ws, float *loss, void *stream);
 int se_distill_bwd(const se_distill_map *maps, int nmaps, int S, int training, void *ws, const float *gout, void *stream);
+
+/* ---- GeneralBeamformer inference head (reference GeneralBeamformer.py:336-373; csrc/se_gbf.hip; ABI-4 additions) -------------
+ * Segment-major streams S = N x B as the se_train_* calls; M = 3 microphones (the head's linear layers are 9 -> H -> 6).
+ * S = Nc x B must hold whole segments: the GRU rows are STREAM-major [B][F][Nc][T] (one [B F][Nc T] sequence set per call, the ldN = 0
+ * addressing of se_train_gru_pseq_fwd, which any number of streams accepts).
+ * se_gbf_psd_fwd: xl [S][4M*9][T][F] (last decoder output, channel ((s*2 + ri)*M + m)*9 + k), spec [S][M][T][F][2] -> the GRU input
+ *   rows of both sequence models [B][F][Nc][T][16]: gLN(Phi) over F*T*9 per stream with affine [F*T] (ln_S / ln_N), columns 9..15 zero.
+ * se_gbf_seq_fwd: last-layer GRU outputs hS / hN (rows [B][F][Nc][T] of H) -> phi [S][F][T][9] = SequenceModel_S * SequenceModel_N (fc H -> 9,
+ *   ReLU, gLN over T x 9 per sequence); yS / yN (may be NULL) receive the two factors.
+ * se_gbf_bf_fwd: phi -> Y [S][T][F][2] = sum_m w_m X_m with w = linear.3(gLN_F(ReLU(linear.0(phi)))); wout [S][F][T][6] may be NULL.
+ * No atomics; reductions in a fixed order independent of S. */
+int se_gbf_psd_fwd(const float *xl, const float *spec, const float *wS, const float *bS, const float *wN, const float *bN, float *rowsS, float *rowsN,
+                   int S, int B, int M, int T, int F, void *stream);
+int se_gbf_seq_fwd(const float *hS, const float *hN, const float *fcS_w, const float *fcS_b, const float *nS_w, const float *nS_b, const float *fcN_w,
+                   const float *fcN_b, const float *nN_w, const float *nN_b, float *phi, float *yS, float *yN, int S, int B, int F, int T, int H, void *stream);
+int se_gbf_bf_fwd(const float *phi, const float *spec, const float *w0, const float *b0, const float *g, const float *beta, const float *w3,
+                  const float *b3, float *Y, float *wout, int S, int M, int T, int F, int H, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -1,0 +1,445 @@
+"""Drop-in `GeneralBeamformer` (reference GeneralBeamformer.py:266-388, built by train.py / predict.py from config.yaml's
+`GeneralBeamformer:` block).
+
+Same constructor, state_dict keys and shapes (the `convlist.i.conv.*` / `net.0.*` aliases and the unused `residual*` modules of the
+last decoder block included), same entry points:
+
+    forward(x[B, M, F, T, 2]) -> [B, F, T, 2]          one segment, stateful (GeneralBeamformer.py:318-373)
+    realtime_process(mixture[B, M, L], flag) -> [B, L]  GeneralBeamformer.py:449-496
+    reset(), compute_loss(source, pred_source, length)
+
+Two interchangeable paths:
+  * the torch restatement (`forward`, and `realtime_process` on the CPU, with grad enabled, or after use_hip_kernels(False)): plain
+    torch ops, differentiable, so train.py can train the model through autograd.  The GRU cell is written out (no nn.GRU forward,
+    no MIOpen RNN); the nn.GRU modules only own the parameters;
+  * the kernel path (`realtime_process` of a GPU tensor with grad disabled): every segment of a call at once, segment-major as in
+    train_net.CRNFunction - U-Net on the se_train_* kernels, the two GRUs as persistent launches, the beamforming head on
+    csrc/se_gbf.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as Fn
+from torch import nn
+
+from . import train_ops as K
+from .train_net import _new, _p, _run, _sig, conv_w, gln_fwd
+
+EPS = 1e-8
+_DEFAULT_MAX_SEGMENTS = 8
+
+
+class _Norm(nn.Module):  # GlobalLayerNorm parameter holder, GeneralBeamformer.py:22-34
+    def __init__(self, dim, last=False):
+        super().__init__()
+        shape = (1, 1, 1, dim) if last else (1, dim, 1, 1)
+        self.weight = nn.Parameter(torch.ones(shape))
+        self.bias = nn.Parameter(torch.zeros(shape))
+
+    def forward(self, x):
+        return _gln(x, self)
+
+
+def _gln(x, norm):
+    """GlobalLayerNorm(time=False): per-sample statistics over every non-batch dim, denominator sqrt(var + EPS) + EPS."""
+    dims = tuple(range(1, x.dim()))
+    mean = x.mean(dims, keepdim=True)
+    var = ((x - mean) ** 2).mean(dims, keepdim=True)
+    return (x - mean) / (torch.sqrt(var + EPS) + EPS) * norm.weight + norm.bias
+
+
+class _Conv(nn.Module):  # TemporalConv2d, GeneralBeamformer.py:155-205
+    def __init__(self, cin, cout, k, dil, dropout):
+        super().__init__()
+        self.padding = (k - 1) * dil
+        self.conv = nn.Conv2d(cin, cout, (5, k), stride=(2, 1), padding=(2, 0), dilation=(1, dil))
+        self.dropout = nn.Dropout(dropout)
+        self.net = nn.Sequential(self.conv, self.dropout)
+        self.norm = _Norm(cout)
+
+
+class _Deconv(nn.Module):  # TemporalConvTranspose2d, GeneralBeamformer.py:208-263
+    def __init__(self, cin, cout, k, dil, dropout):
+        super().__init__()
+        self.conv = nn.ConvTranspose2d(cin, cout, (5, k), stride=(2, 1), padding=(2, 0), dilation=(1, dil))
+        self.dropout = nn.Dropout(dropout)
+        self.net = nn.Sequential(self.conv, self.dropout)
+        self.residualmask = nn.Conv2d(cout, cout, (1, 1))
+        self.residualnorm = _Norm(cout)
+        self.residual = nn.Conv2d(cout, cout, (1, 1))
+        self.norm = _Norm(cout)
+
+
+class _SequenceModel(nn.Module):  # SequenceModel(9, hidden, num_layers, GRU, ReLU), GeneralBeamformer.py:64-152
+    def __init__(self, size, hidden, num_layers):
+        super().__init__()
+        self.sequence_model = nn.GRU(size, hidden, num_layers, batch_first=True)
+        self.fc_output_layer = nn.Linear(hidden, size)
+        self.norm = _Norm(size, last=True)
+
+
+def _gru(x, g, h0):
+    """nn.GRU (batch_first) written out: x [N, T, In], h0 [layers, N, H] or None -> (out [N, T, H], hT [layers, N, H])."""
+    H = g.hidden_size
+    hs = []
+    for l in range(g.num_layers):
+        gi = x @ getattr(g, f"weight_ih_l{l}").t() + getattr(g, f"bias_ih_l{l}")
+        w_hh, b_hh = getattr(g, f"weight_hh_l{l}"), getattr(g, f"bias_hh_l{l}")
+        h = h0[l] if h0 is not None else x.new_zeros(x.shape[0], H)
+        outs = []
+        for t in range(x.shape[1]):
+            gh = h @ w_hh.t() + b_hh
+            r = torch.sigmoid(gi[:, t, :H] + gh[:, :H])
+            z = torch.sigmoid(gi[:, t, H:2 * H] + gh[:, H:2 * H])
+            n = torch.tanh(gi[:, t, 2 * H:] + r * gh[:, 2 * H:])
+            h = (1.0 - z) * n + z * h
+            outs.append(h)
+        x = torch.stack(outs, dim=1)
+        hs.append(h)
+    return x, torch.stack(hs)
+
+
+class GeneralBeamformer(nn.Module):
+    def __init__(self, num_channels, num_freqs, hidden, segment_length, num_layers=1, num_inputs=3, kernel_size=3, dropout=0.0,
+                 sample_rate=16000, win_length=25, hop_length=10, n_fft=400):
+        super().__init__()
+        self.segment_length = segment_length
+        self.num_freqs = num_freqs
+        self.num_time = segment_length // 160 + 1
+        self._cfg = dict(num_channels=list(num_channels), hidden=hidden, num_layers=num_layers, num_inputs=num_inputs,
+                         kernel_size=kernel_size, sample_rate=sample_rate, win_length=win_length, hop_length=hop_length, n_fft=n_fft)
+        self._win = int(round(sample_rate / 1000.0 * win_length))
+        self._hop = int(round(sample_rate / 1000.0 * hop_length))
+        L = len(num_channels)
+        convs, deconvs = [], []
+        for i in range(L):
+            cin = (2 * num_inputs - 1) if i == 0 else num_channels[i - 1]
+            convs.append(_Conv(cin, num_channels[i], kernel_size, 2 ** i, dropout))
+            cout = 4 * num_inputs * 9 if i == 0 else cin
+            deconvs.insert(0, _Deconv(num_channels[i], cout, kernel_size, 2 ** (L - i - 1), dropout))
+        self.convlist = nn.ModuleList(convs)
+        self.deconvlist = nn.ModuleList(deconvs)
+        self.ln_S = _Norm(num_freqs * self.num_time)
+        self.ln_N = _Norm(num_freqs * self.num_time)
+        self.gru_S = _SequenceModel(num_inputs * num_inputs, hidden, num_layers)
+        self.gru_N = _SequenceModel(num_inputs * num_inputs, hidden, num_layers)
+        self.linear = nn.Sequential(nn.Linear(9, hidden), nn.ReLU(), _Norm(num_freqs), nn.Linear(hidden, 6))
+        self.max_segments = _DEFAULT_MAX_SEGMENTS  # segments per kernel-path pass: bounds peak memory; the state carries across passes
+        self._hip = True
+        self._tstate = None   # restatement: dict(buf=[...], hS, hN)
+        self._kstate = None   # kernel path: dict(B, buf=[...], h=[[...], [...]])
+        self._last_path = None
+        self._pad_cache = {}
+        self.taps = None      # restatement: set to {} to receive the intermediate tensors of every forward
+
+    # ---- reference contract ------------------------------------------------------------------------------------------------
+    def reset(self):
+        self._tstate = None
+        self._kstate = None
+
+    def use_hip_kernels(self, flag=True):
+        """True (default): realtime_process of a GPU tensor with grad disabled runs on the kernels; False: always the restatement."""
+        self._hip = bool(flag)
+        return self
+
+    def compute_loss(self, source, pred_source, length):
+        """loss = 0.7 * stoi_loss + 0.3 * (-SI-SNR), NaN -> zeros (GeneralBeamformer.py:500-523); returns (loss, stoi, sisnr)."""
+        from .losses import compute_loss
+        return compute_loss(source, pred_source, length)
+
+    def forward(self, x):
+        """One segment [B, M, F, T, 2] -> [B, F, T, 2] on the torch restatement, carrying the encoder buffers and GRU states."""
+        y, self._tstate = self._segment(x, self._tstate)
+        return y
+
+    def realtime_process(self, mixture, flag=False):
+        flag = bool(flag.item() if torch.is_tensor(flag) else flag)
+        path = "kernel" if (self._hip and mixture.is_cuda and not torch.is_grad_enabled()) else "torch"
+        if flag and self._last_path not in (None, path):
+            raise RuntimeError("flag=True continues the state of the other path (kernels vs restatement): start with flag=False")
+        self._last_path = path
+        if path == "kernel":
+            return self._kernel_process(mixture, flag)
+        return self._torch_process(mixture, flag)
+
+    # ---- torch restatement ---------------------------------------------------------------------------------------------------
+    def _segment(self, x, st):
+        B, M, F, T, _ = x.shape
+        st = st or dict(buf=None, hS=None, hN=None)
+        taps = self.taps
+        noisy = x
+        re, im = x[..., 0], x[..., 1]
+        ang = torch.arctan(im / (re + EPS) + EPS)
+        h = torch.cat([torch.sqrt(re ** 2 + im ** 2 + 1e-10), ang[:, :1] - ang[:, 1:]], dim=1)
+        residuals, bufs = [h], []
+        for i, blk in enumerate(self.convlist):
+            P = blk.padding
+            buf = st["buf"][i] if st["buf"] is not None else h.new_zeros(B, h.shape[1], h.shape[2], P)
+            inp = torch.cat([buf, h], dim=-1)
+            bufs.append(inp[..., -P:].detach())
+            y = blk.dropout(Fn.conv2d(inp, blk.conv.weight, blk.conv.bias, stride=(2, 1), padding=(2, 0), dilation=blk.conv.dilation))
+            h = _gln(torch.relu(y), blk.norm)
+            residuals.append(h)
+        L = len(self.deconvlist)
+        for j, blk in enumerate(self.deconvlist):
+            y = Fn.conv_transpose2d(h, blk.conv.weight, blk.conv.bias, stride=(2, 1), padding=(2, 0), dilation=blk.conv.dilation)
+            y = _gln(torch.relu(blk.dropout(y)[..., -T:]), blk.norm)
+            if j < L - 1:
+                res = residuals[-2 - j]
+                if res.shape[2] > y.shape[2]:
+                    y = Fn.pad(y, (0, 0, 0, res.shape[2] - y.shape[2]))
+                elif res.shape[2] < y.shape[2]:
+                    y = y[:, :, :res.shape[2]]
+                m = torch.sigmoid(_gln(Fn.conv2d(res, blk.residualmask.weight, blk.residualmask.bias), blk.residualnorm))
+                y = m * torch.relu(Fn.conv2d(res, blk.residual.weight, blk.residual.bias)) + (1.0 - m) * y
+            h = y
+        if taps is not None:
+            taps["xl"] = h
+        phi = self._head_phi(h, noisy)
+        if taps is not None:
+            taps["phi_s"] = phi[0]
+        yS, hS = self._sequence(self.gru_S, phi[0].reshape(B * F, T, 9), st["hS"])
+        yN, hN = self._sequence(self.gru_N, phi[1].reshape(B * F, T, 9), st["hN"])
+        if taps is not None:
+            taps["seq_s"], taps["seq_n"] = yS.transpose(1, 2), yN.transpose(1, 2)   # the reference layout [B*F, 9, T]
+        w = self.linear((yS * yN).reshape(B, F, T, 9)).reshape(B, F, T, M, 2)  # .conj() of a real tensor: a no-op
+        if taps is not None:
+            taps["w"] = w
+        Y = self._beamform(w, noisy)
+        return Y, dict(buf=bufs, hS=hS.detach(), hN=hN.detach())
+
+    def _head_phi(self, xl, noisy):
+        """xl [B, 4M*9, F, T] -> (Phi_S, Phi_N) after ln_S / ln_N, [B, F*T, M, M] (GeneralBeamformer.py:336-357)."""
+        B, M, F, T, _ = noisy.shape
+        f5 = xl.reshape(B, 2, 2, M, 9, F * T)
+        u = Fn.unfold(noisy.reshape(B, M, F, T * 2), (3, 3), padding=1).reshape(B, M, 9, F * T, 2)
+        ur, ui = u[..., 0], u[..., 1]
+        out = []
+        for q, ln in ((0, self.ln_S), (1, self.ln_N)):
+            fr, fi = f5[:, q, 0], f5[:, q, 1]
+            sr = (fr * ur - fi * ui).sum(dim=2).transpose(1, 2)   # [B, F*T, M]
+            si = (fr * ui + fi * ur).sum(dim=2).transpose(1, 2)
+            phi = sr[..., :, None] * sr[..., None, :] + si[..., :, None] * si[..., None, :]
+            out.append(_gln(phi, ln))
+        return out
+
+    @staticmethod
+    def _beamform(w, noisy):
+        n = noisy.permute(0, 2, 3, 1, 4)  # [B, F, T, M, 2]
+        real = w[..., 0] * n[..., 0] - w[..., 1] * n[..., 1]
+        img = w[..., 0] * n[..., 1] + w[..., 1] * n[..., 0]
+        return torch.stack([real, img], dim=-1).sum(dim=-2)
+
+    @staticmethod
+    def _sequence(sm, x, h0):
+        """SequenceModel.forward on [B*F, T, 9] rows: GRU, fc, ReLU, gLN over T x 9 -> ([B*F, T, 9], hT)."""
+        o, hT = _gru(x, sm.sequence_model, h0)
+        o = torch.relu(sm.fc_output_layer(o))
+        return _gln(o.unsqueeze(1), sm.norm).squeeze(1), hT
+
+    def spectrum(self, seg):
+        """stft_trans of the segments [B, M, N, K] -> [B, M, N, F, T, 2] (torch.stft; speechbrain's STFT wrapper)."""
+        B, M, N, Ks = seg.shape
+        win = torch.hamming_window(self._win, device=seg.device)
+        X = torch.stft(seg.reshape(-1, Ks), self._cfg["n_fft"], self._hop, self._win, win, center=True, pad_mode="constant", normalized=False,
+                       onesided=True, return_complex=True)
+        return torch.view_as_real(X).reshape(B, M, N, *X.shape[-2:], 2)
+
+    def _torch_process(self, mixture, flag):
+        B, M, L = mixture.shape
+        Ks = self.segment_length
+        P = Ks // 2
+        if not flag:
+            mixture = Fn.pad(mixture, (P, 0))
+            self._tstate = None
+        Lp = mixture.shape[-1]
+        gap = Ks - (P + Lp % Ks) % Ks
+        xp = Fn.pad(mixture, (P, gap + P))
+        N = 2 * (Lp + gap + P) // Ks
+        idx = (torch.arange(N, device=mixture.device) * P)[:, None] + torch.arange(Ks, device=mixture.device)[None, :]
+        seg = xp[:, :, idx]  # [B, M, N, K]
+        win = torch.hamming_window(self._win, device=mixture.device)
+        n_fft = self._cfg["n_fft"]
+        X = self.spectrum(seg)
+        outs = []
+        for n in range(N):
+            outs.append(self.forward(X[:, :, n]))
+        Y = torch.view_as_complex(torch.stack(outs, dim=1).reshape(B * N, *outs[0].shape[1:]).contiguous())
+        y = torch.istft(Y, n_fft, self._hop, self._win, win, center=True, normalized=False, onesided=True).reshape(B, N, -1)
+        s1 = y[:, 0::2].reshape(B, -1)[:, P:]
+        s2 = y[:, 1::2].reshape(B, -1)[:, :-P]
+        out = (s1 + s2) / 2
+        if gap > 0:
+            out = out[:, :-gap]
+        return out if flag else out[:, P:]
+
+    # ---- kernel path ---------------------------------------------------------------------------------------------------------
+    def kernel_geometry_error(self):
+        """None when the kernel path supports this geometry, else the limit that fails (realtime_process raises it as ValueError)."""
+        c = self._cfg
+        M, k, H, ch = c["num_inputs"], c["kernel_size"], c["hidden"], [2 * c["num_inputs"] - 1] + c["num_channels"]
+        Lv = len(c["num_channels"])
+        T, F0 = 1 + self.segment_length // self._hop, c["n_fft"] // 2 + 1
+        if M != 3:
+            return f"num_inputs = {M}: the beamforming head's linear layers are 9 -> hidden -> 6, so 3 microphones only"
+        if k != 3:
+            return f"kernel_size = {k}: the convolution kernels are 5 x 3"
+        if F0 != self.num_freqs or T != self.num_time:
+            return f"STFT gives {F0} x {T} bins, the model is built for {self.num_freqs} x {self.num_time} (ln_S / ln_N weights)"
+        if T > 64:
+            return f"{T} frames per segment: the sequence head takes at most 64"
+        for what, co in [(f"convlist.{i}", ch[i + 1]) for i in range(Lv)] + [(f"deconvlist.{Lv - 1}", 4 * M * 9)]:
+            if (co + 31) // 32 * 32 not in (32, 64, 128):
+                return f"{what}: {co} output channels do not pad to 32, 64 or 128 (the conv kernels' GEMM rows)"
+        if not K._lib().se_train_gru_pseq_supported(1, H):
+            return f"hidden = {H}: no persistent GRU kernel (se_train_gru_pseq_supported)"
+        if (k - 1) * 2 ** (Lv - 1) >= T:
+            return f"encoder history (k - 1) * 2^(L - 1) = {(k - 1) * 2 ** (Lv - 1)} frames is not shorter than the {T}-frame segment"
+        Fq = [F0]
+        for _ in range(Lv):
+            Fq.append((Fq[-1] - 1) // 2 + 1)
+        for j in range(Lv - 1):
+            kk = Lv - 1 - j
+            if Fq[kk] < 2 * Fq[kk + 1] - 1:
+                return f"deconvlist.{j}: {2 * Fq[kk + 1] - 1} frequencies do not fit the {Fq[kk]}-bin skip tensor"
+        if 2 * Fq[1] - 1 != self.num_freqs:
+            return f"last decoder block gives {2 * Fq[1] - 1} frequencies, num_freqs = {self.num_freqs}"
+        return None
+
+    def _padded_w_ih(self, g):
+        """W_ih_l0 [3H][9] zero-padded to [3H][16] (the GEMM's K % 8), once per parameter version."""
+        w = g.weight_ih_l0
+        key = (id(g), w.data_ptr(), w._version)
+        if self._pad_cache.get(id(g), (None,))[0] != key:
+            wp = torch.zeros(w.shape[0], 16, device=w.device, dtype=torch.float32)
+            wp[:, :w.shape[1]].copy_(w.detach())
+            self._pad_cache[id(g)] = (key, wp)
+        return self._pad_cache[id(g)][1]
+
+    @torch.no_grad()
+    def _kernel_process(self, mixture, flag):
+        err = self.kernel_geometry_error()
+        if err:
+            raise ValueError(f"GeneralBeamformer kernel path: {err}")
+        if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist)):
+            raise ValueError("GeneralBeamformer kernel path: inference only (dropout is active in training mode; use the restatement)")
+        lib = K._lib()
+        K._need_gpu(mixture, self.ln_S.weight)
+        dev = mixture.device
+        mixture = mixture.contiguous().float()
+        B, M, L = mixture.shape
+        c = self._cfg
+        Ks, n_fft, H, NL = self.segment_length, c["n_fft"], c["hidden"], c["num_layers"]
+        P = Ks // 2
+        T, F0 = 1 + Ks // self._hop, n_fft // 2 + 1
+        sig = _sig(dev, n_fft, self._win, self._hop, Ks)
+        Lp = L if flag else L + P
+        off0 = -P if flag else -2 * P
+        skip = 0 if flag else P
+        gap = Ks - (P + Lp % Ks) % Ks
+        N = 2 * (Lp + gap + P) // Ks
+        st = K._st
+        Lv = len(self.convlist)
+        ch = [2 * M - 1] + c["num_channels"]
+        Fq = [F0]
+        for _ in range(Lv):
+            Fq.append((Fq[-1] - 1) // 2 + 1)
+        state = self._kstate if flag else None
+        if state is not None and state["B"] != B:
+            raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
+        BF = B * F0
+        if state is None:
+            state = dict(B=B, buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
+                         h=[[torch.zeros(BF, H, device=dev) for _ in range(NL)] for _ in range(2)])
+        models = (self.gru_S, self.gru_N)
+        w_ih0 = [self._padded_w_ih(m.sequence_model) for m in models]
+        yseg = _new(N, B, Ks, dev=dev)
+        tmo = []
+        step = max(1, int(self.max_segments))
+        for n0 in range(0, N, step):
+            Nc = min(step, N - n0)
+            S = Nc * B
+            spec = _new(Nc, B * M, T, F0, 2, dev=dev)
+            _run("k_stft", 0.0, lib.se_sig_stft, sig, _p(mixture), B, M, L, off0 + n0 * P, P, Nc, _p(spec), st())
+            # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input of block i (its time history)
+            xin = []
+            for i in range(Lv):
+                t_ = _new(Nc + 1, B, ch[i], T, Fq[i], dev=dev)
+                t_[0].copy_(state["buf"][i])
+                xin.append(t_)
+            _run("k_tfeat", 0.0, lib.se_train_feat, _p(spec), _p(xin[0], B * ch[0] * T * F0), S, M, T, F0, 0, st())
+            for i, blk in enumerate(self.convlist):
+                Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
+                y = _new(S, Co, T, Fo, dev=dev)
+                conv_w(0, _p(xin[i], B * Ci * T * Fi), _p(xin[i]), blk.conv.weight, Ci * 15, 15, blk.conv.bias, y, S, Ci, Co, T, Fi, Fo, d, 0)
+                if i < Lv - 1:
+                    out, off = xin[i + 1], B * Co * T * Fo
+                else:
+                    out, off = _new(S, Co, T, Fo, dev=dev), 0
+                gln_fwd(y, (Co * T * Fo, T * Fo, Fo), _p(out, off), (Co * T * Fo, T * Fo, Fo), blk.norm.weight, blk.norm.bias, S, Co, T, Fo, Fo, 0, 1, 0)
+                x_in = out
+            Ci, Fi = ch[Lv], Fq[Lv]
+            for j, blk in enumerate(self.deconvlist):
+                Co, d, Fy = blk.conv.weight.shape[1], 2 ** j, 2 * Fi - 1
+                yd = _new(S, Co, T, Fy, dev=dev)
+                for kind in (1, 2):
+                    conv_w(kind, _p(x_in), None, blk.conv.weight, 15, Co * 15, blk.conv.bias, yd, S, Ci, Co, T, Fi, Fy, d)
+                if j < Lv - 1:
+                    kk = Lv - 1 - j
+                    Cr, Fr = ch[kk], Fq[kk]
+                    z = _new(S, Co, T, Fr, dev=dev)
+                    gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(z), (Co * T * Fr, T * Fr, Fr), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fr, 0, 1, 0)
+                    uv = _new(S, 2 * Co, T, Fr, dev=dev)   # residual | residualmask, one 1x1 launch per half (2 Co may exceed 128 rows)
+                    res = _p(xin[kk], B * Cr * T * Fr)
+                    conv_w(3, res, None, blk.residual.weight, Cr, 1, blk.residual.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, 0)
+                    conv_w(3, res, None, blk.residualmask.weight, Cr, 1, blk.residualmask.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, Co)
+                    out = _new(S, Co, T, Fr, dev=dev)
+                    stt = _new(S, 2, dev=dev)
+                    _run("k_tskip_fwd", 0.0, lib.se_train_skip_fwd, _p(uv), _p(z), _p(blk.residualnorm.weight), _p(blk.residualnorm.bias), _p(out),
+                         _p(stt), S, Co, T, Fr, 1, 0, st())
+                    x_in, Ci, Fi = out, Co, Fr
+                else:
+                    xl = _new(S, Co, T, Fy, dev=dev)
+                    gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(xl), (Co * T * Fy, T * Fy, Fy), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fy, 0, 1, 0)
+            # head: PSD + ln -> GRU rows [B*F][Nc*T][16] (stream-major), two GRU models, sequence head, beamformer
+            R, TT = BF * Nc * T, Nc * T
+            rows = [_new(R, 16, dev=dev), _new(R, 16, dev=dev)]
+            _run("k_gbf_psd", 0.0, lib.se_gbf_psd_fwd, _p(xl), _p(spec), _p(self.ln_S.weight), _p(self.ln_S.bias), _p(self.ln_N.weight),
+                 _p(self.ln_N.bias), _p(rows[0]), _p(rows[1]), S, B, M, T, F0, st())
+            last = []
+            for q, m in enumerate(models):
+                g = m.sequence_model
+                x_l = rows[q]
+                for l in range(NL):
+                    gi = K._gemm(x_l, w_ih0[q] if l == 0 else getattr(g, f"weight_ih_l{l}"), getattr(g, f"bias_ih_l{l}"))
+                    out = _new(R, H, dev=dev)
+                    hT = _new(BF, H, dev=dev)
+                    sc = K._scratch(dev, BF, H, tag=("gbf", q, l))
+                    _run("k_gru_pseq_fwd", 2.0 * BF * 3 * H * H * TT, lib.se_train_gru_pseq_fwd, _p(gi), _p(state["h"][q][l]),
+                         _p(getattr(g, f"weight_hh_l{l}")), _p(getattr(g, f"bias_hh_l{l}")), _p(out), None, _p(hT), _p(sc), BF, TT, H, TT, 0, TT, st())
+                    tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
+                    del gi
+                    state["h"][q][l] = hT
+                    x_l = out
+                last.append(x_l)
+            del rows
+            phi = _new(S, F0, T, 9, dev=dev)
+            sS, sN = self.gru_S, self.gru_N
+            _run("k_gbf_seq", 0.0, lib.se_gbf_seq_fwd, _p(last[0]), _p(last[1]), _p(sS.fc_output_layer.weight), _p(sS.fc_output_layer.bias),
+                 _p(sS.norm.weight), _p(sS.norm.bias), _p(sN.fc_output_layer.weight), _p(sN.fc_output_layer.bias), _p(sN.norm.weight),
+                 _p(sN.norm.bias), _p(phi), None, None, S, B, F0, T, H, st())
+            del last
+            Y = _new(S, T, F0, 2, dev=dev)
+            lin = self.linear
+            _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
+                 _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
+            _run("k_istft", 0.0, lib.se_sig_istft, sig, _p(Y), S, _p(yseg, n0 * B * Ks), st())
+            state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
+        Lout = Lp - skip
+        pred = _new(B, Lout, dev=dev)
+        _run("k_tola", 0.0, lib.se_train_ola_fwd, sig, _p(yseg), _p(pred), B, Lout, skip, st())
+        self._kstate = state
+        if tmo and int(torch.cat(tmo).abs().sum()) != 0:
+            self._kstate = None
+            raise RuntimeError(f"persistent GRU kernel timed out waiting for its peer workgroups ({BF} streams, hidden {H}): output invalid")
+        return pred

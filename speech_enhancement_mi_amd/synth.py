@@ -152,6 +152,44 @@ def fsn_param_spec(num_freqs=201, num_mics=3, fb_hidden=512, sb_hidden=384, num_
     return spec
 
 
+def gbf_param_spec(num_channels, num_freqs, hidden, segment_length, num_layers=1, num_inputs=3, kernel_size=3):
+    """(key, shape) list of reference GeneralBeamformer.state_dict() (GeneralBeamformer.py:266-316; checked against the live module,
+    fixture gbf_keys.json).  The encoder / decoder blocks are the CRN's; the last decoder block outputs 4 M 9 channels."""
+    spec = []
+    L = len(num_channels)
+    c0 = 2 * num_inputs - 1
+    for i in range(L):
+        cin = c0 if i == 0 else num_channels[i - 1]
+        p = f"convlist.{i}."
+        spec += [(p + "conv.weight", (num_channels[i], cin, 5, kernel_size)), (p + "conv.bias", (num_channels[i],)),
+                 (p + "net.0.weight", (num_channels[i], cin, 5, kernel_size)), (p + "net.0.bias", (num_channels[i],)),
+                 (p + "norm.weight", (1, num_channels[i], 1, 1)), (p + "norm.bias", (1, num_channels[i], 1, 1))]
+    for j in range(L):
+        i = L - 1 - j
+        cin = num_channels[i]
+        cout = 4 * num_inputs * 9 if i == 0 else num_channels[i - 1]
+        p = f"deconvlist.{j}."
+        spec += [(p + "conv.weight", (cin, cout, 5, kernel_size)), (p + "conv.bias", (cout,)),
+                 (p + "net.0.weight", (cin, cout, 5, kernel_size)), (p + "net.0.bias", (cout,)),
+                 (p + "residualmask.weight", (cout, cout, 1, 1)), (p + "residualmask.bias", (cout,)),
+                 (p + "residualnorm.weight", (1, cout, 1, 1)), (p + "residualnorm.bias", (1, cout, 1, 1)),
+                 (p + "residual.weight", (cout, cout, 1, 1)), (p + "residual.bias", (cout,)),
+                 (p + "norm.weight", (1, cout, 1, 1)), (p + "norm.bias", (1, cout, 1, 1))]
+    FT = num_freqs * (segment_length // 160 + 1)
+    spec += [("ln_S.weight", (1, FT, 1, 1)), ("ln_S.bias", (1, FT, 1, 1)), ("ln_N.weight", (1, FT, 1, 1)), ("ln_N.bias", (1, FT, 1, 1))]
+    D = num_inputs * num_inputs
+    for name in ("gru_S", "gru_N"):
+        for l in range(num_layers):
+            ins = D if l == 0 else hidden
+            spec += [(f"{name}.sequence_model.weight_ih_l{l}", (3 * hidden, ins)), (f"{name}.sequence_model.weight_hh_l{l}", (3 * hidden, hidden)),
+                     (f"{name}.sequence_model.bias_ih_l{l}", (3 * hidden,)), (f"{name}.sequence_model.bias_hh_l{l}", (3 * hidden,))]
+        spec += [(f"{name}.fc_output_layer.weight", (D, hidden)), (f"{name}.fc_output_layer.bias", (D,)),
+                 (f"{name}.norm.weight", (1, 1, 1, D)), (f"{name}.norm.bias", (1, 1, 1, D))]
+    spec += [("linear.0.weight", (hidden, 9)), ("linear.0.bias", (hidden,)), ("linear.2.weight", (1, num_freqs, 1, 1)),
+             ("linear.2.bias", (1, num_freqs, 1, 1)), ("linear.3.weight", (6, hidden)), ("linear.3.bias", (6,))]
+    return spec
+
+
 def synth_utterances(batch: int, length: int, num_mics: int = 3, seed: int = 0,
                      sample_rate: int = 16000):
     """Synthetic noisy multi-mic speech-like audio: returns (mix [B,M,L], clean [B,L]).
