@@ -79,8 +79,12 @@ __device__ __forceinline__ void convp_stats_store(float *stats, int nslot, int s
 #define CPT(i)
 #endif
 
-template <int NTAP, int NT, int CO, int PL>
-__global__ __launch_bounds__(256, NT <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
+// NTAP2 > 0: the two output-frequency parities of a transposed convolution in ONE launch (a.ntap2 / rowgrp2 / coloff2 / wx2 /
+// oo2 / valid_m2 / stats_slot02 describe the second one).  Both parities read the same staged patch: every chunk is staged once
+// and feeds the NTAP-tap K loop into acc and the NTAP2-tap K loop into acc2; each parity then has its own R epilogue.  The
+// second accumulator set doubles the accumulator registers, so occupancy follows 2 NT.
+template <int NTAP, int NT, int CO, int PL, int NTAP2 = 0>
+__global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
 #ifdef SE_CP_TRACE
     unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast) :: "memory");
@@ -90,6 +94,7 @@ __global__ __launch_bounds__(256, NT <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
     // runs and staged at 9 GB/s per CU)
     extern __shared__ __align__(16) uint4 planes[];
     constexpr int NPAIR = (NTAP * CO + 1) / 2;
+    constexpr int NPAIR2 = NTAP2 ? (NTAP2 * CO + 1) / 2 : 1;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;  // provably wave-uniform (LDS-DMA destination, tile ownership)
     const int b = blockIdx.y;
@@ -127,11 +132,26 @@ __global__ __launch_bounds__(256, NT <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
         const int tp = en / CO, oc = en - tp * CO;
         toffL[pr] = (oc * Npos + a.rowgrp[tp] * (a.grouped ? RT : a.dil) * St + a.coloff[tp]) * 16;
     }
-    f32x16 acc[NT];
+    int toffL2[NPAIR2];  // second parity (NTAP2 > 0)
+    if constexpr (NTAP2 > 0) {
+#pragma unroll
+        for (int pr = 0; pr < NPAIR2; pr++) {
+            const int en = min(2 * pr + half, NTAP2 * CO - 1);
+            const int tp = en / CO, oc = en - tp * CO;
+            toffL2[pr] = (oc * Npos + a.rowgrp2[tp] * (a.grouped ? RT : a.dil) * St + a.coloff2[tp]) * 16;
+        }
+    }
+    f32x16 acc[NT], acc2[NT];  // (acc2 is dead without NTAP2)
 #pragma unroll
     for (int i = 0; i < NT; i++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[i][r] = 0.0f;
+    if constexpr (NTAP2 > 0) {
+#pragma unroll
+        for (int i = 0; i < NT; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc2[i][r] = 0.0f;
+    }
 
     // ---- LDS-DMA plan: item it = tid + 256 k = (plane, octet-in-chunk, patch position), LDS slot = it ----
     const int items = PL * CO * Npos;
@@ -190,14 +210,17 @@ __global__ __launch_bounds__(256, NT <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
 
     const uint4 *wxw = a.wx + (long)mt * 64 + l31 * 2 + half;  // + (((ch*NPAIR + pr)*PL + plane)*MT) * 64
     const long wx_plane = (long)MT * 64, wx_pair = PL * wx_plane, wx_chunk = NPAIR * wx_pair;
+    const uint4 *wxw2 = NTAP2 ? a.wx2 + (long)mt * 64 + l31 * 2 + half : nullptr;  // same layout with NPAIR2 pairs per chunk
+    const long wx_chunk2 = NPAIR2 * wx_pair;
 
     const char *ldsb = reinterpret_cast<const char *>(planes);
     const int plane_bytes = CO * Npos * 16;
     // One B fragment = the PL planes of 8 channels at one patch position.  The address is made opaque right before its reads:
     // otherwise the compiler hoists all NPAIR x NT x PL fragment addresses out of the chunk loop (hundreds of registers parked
     // in AGPRs and read back one by one) - one v_add per fragment is free next to six MFMAs.
-    auto read_b = [&](int i, int pr, uint4 (&bf)[PL]) {
-        int off = lane_base[i] + toffL[pr];
+    // (par = 1: the second tap list of a pair instance)
+    auto read_b = [&](int i, int par, int pr, uint4 (&bf)[PL]) {
+        int off = lane_base[i] + (par ? toffL2[pr] : toffL[pr]);
         asm volatile("" : "+v"(off));
 #pragma unroll
         for (int p = 0; p < PL; p++) bf[p] = *reinterpret_cast<const uint4 *>(ldsb + off + p * plane_bytes);
@@ -205,55 +228,69 @@ __global__ __launch_bounds__(256, NT <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
     CPT(0);  // prologue: tile geometry + LDS-DMA plan
     for (int ch = 0; ch < a.nchunk; ch++) {
         const uint4 *wc = wxw + ch * wx_chunk;
-        uint4 fa_n[PL];
+        uint4 fa_n[PL], fa_n2[PL];
 #pragma unroll
         for (int p = 0; p < PL; p++) fa_n[p] = wc[p * wx_plane];  // first weight fragments of the chunk: in flight during staging
+        if constexpr (NTAP2 > 0) {
+#pragma unroll
+            for (int p = 0; p < PL; p++) fa_n2[p] = wxw2[ch * wx_chunk2 + p * wx_plane];
+        }
         __syncthreads();  // previous chunk fully consumed
         CPT(1);
         stage(ch);
         CPT(2);
         __syncthreads();  // (the compiler drains vmcnt before the barrier: every wave's DMA pieces have landed)
         CPT(3);
-        uint4 bcur[PL], bnxt[PL];
-        read_b(0, 0, bcur);
 #pragma unroll
-        for (int pr = 0; pr < NPAIR; pr++) {
-            uint4 fa[PL];
+        for (int par = 0; par < (NTAP2 ? 2 : 1); par++) {  // NTAP2 > 0: the second tap list, same staged patch, into acc2
+            const int np = par ? NPAIR2 : NPAIR;
+            if (par) {
+                wc = wxw2 + ch * wx_chunk2;
 #pragma unroll
-            for (int p = 0; p < PL; p++) fa[p] = fa_n[p];
-            if (pr + 1 < NPAIR) {
-#pragma unroll
-                for (int p = 0; p < PL; p++) fa_n[p] = wc[(pr + 1) * wx_pair + p * wx_plane];
+                for (int p = 0; p < PL; p++) fa_n[p] = fa_n2[p];
             }
+            uint4 bcur[PL], bnxt[PL];
+            read_b(0, par, 0, bcur);
 #pragma unroll
-            for (int i = 0; i < NT; i++) {
-                // software pipeline, one fragment deep: the LDS reads of the NEXT (tile, K step) are issued before this
-                // fragment's MFMAs, whose 100-200 matrix-pipe cycles cover the LDS latency (one wave per SIMD: nothing else would)
-                if (i + 1 < NT) read_b(i + 1, pr, bnxt);
-                else if (pr + 1 < NPAIR) read_b(0, pr + 1, bnxt);
-                __builtin_amdgcn_sched_barrier(0);
-                f32x16 c = acc[i];
-                if (PL >= 2) {
-                    const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[0]), a1 = __builtin_bit_cast(bf16x8, fa[PL > 1 ? 1 : 0]),
-                                 a2 = __builtin_bit_cast(bf16x8, fa[PL > 2 ? 2 : 0]);
-                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, bcur[0]), b1 = __builtin_bit_cast(bf16x8, bcur[PL > 1 ? 1 : 0]);
-                    if (PL == 3) {
-                        const bf16x8 b2 = __builtin_bit_cast(bf16x8, bcur[PL > 2 ? 2 : 0]);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);  // mid*mid
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);  // hi*lo
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);  // lo*hi
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);  // hi*mid
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);  // mid*hi
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);  // hi*hi
-                } else {
-                    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[0]), __builtin_bit_cast(h8, bcur[0]), c, 0, 0, 0);
+            for (int pr = 0; pr < np; pr++) {
+                uint4 fa[PL];
+#pragma unroll
+                for (int p = 0; p < PL; p++) fa[p] = fa_n[p];
+                if (pr + 1 < np) {
+#pragma unroll
+                    for (int p = 0; p < PL; p++) fa_n[p] = wc[(pr + 1) * wx_pair + p * wx_plane];
                 }
-                acc[i] = c;
-                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int p = 0; p < PL; p++) bcur[p] = bnxt[p];
+                for (int i = 0; i < NT; i++) {
+                    // software pipeline, one fragment deep: the LDS reads of the NEXT (tile, K step) are issued before this
+                    // fragment's MFMAs, whose 100-200 matrix-pipe cycles cover the LDS latency (one wave per SIMD: nothing else would)
+                    if (i + 1 < NT) read_b(i + 1, par, pr, bnxt);
+                    else if (pr + 1 < np) read_b(0, par, pr + 1, bnxt);
+                    __builtin_amdgcn_sched_barrier(0);
+                    f32x16 c = par ? acc2[i] : acc[i];
+                    if (PL >= 2) {
+                        const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[0]), a1 = __builtin_bit_cast(bf16x8, fa[PL > 1 ? 1 : 0]),
+                                     a2 = __builtin_bit_cast(bf16x8, fa[PL > 2 ? 2 : 0]);
+                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, bcur[0]), b1 = __builtin_bit_cast(bf16x8, bcur[PL > 1 ? 1 : 0]);
+                        if (PL == 3) {
+                            const bf16x8 b2 = __builtin_bit_cast(bf16x8, bcur[PL > 2 ? 2 : 0]);
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);  // mid*mid
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);  // hi*lo
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);  // lo*hi
+                        }
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);  // hi*mid
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);  // mid*hi
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);  // hi*hi
+                    } else {
+                        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[0]), __builtin_bit_cast(h8, bcur[0]), c, 0, 0, 0);
+                    }
+                    if (par) acc2[i] = c;
+                    else acc[i] = c;
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int p = 0; p < PL; p++) bcur[p] = bnxt[p];
+                }
             }
         }
         CPT(4);  // MFMAs issued (the tail retires inside the next barrier segment)
@@ -406,30 +443,35 @@ __global__ __launch_bounds__(256, NT <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
     // R layout (or statistics only): register group q = r >> 2 holds rows 8 q + 4 half + {0..3} of M tile mt
     float *yb = a.y ? a.y + (long)b * a.y_stream : nullptr;
 #pragma unroll
-    for (int i = 0; i < NT; i++) {
-        const int p = p0 + (cg + i * NCG) * 32 + l31;
-        if (p >= p1) continue;
-        const int t = (int)(((float)p + 0.5f) * invFP), m = p - t * a.FP;
-        if (m >= a.valid_m) continue;
-        const long opos = (long)t * a.oT + a.oo + m;
+    for (int par = 0; par < (NTAP2 ? 2 : 1); par++) {  // NTAP2 > 0: the second parity from acc2
+        const int oo = par ? a.oo2 : a.oo, valid_m = par ? a.valid_m2 : a.valid_m;
+        if (par) { ssum = 0.0f; ssq = 0.0f; }
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int row0 = mt * 32 + 8 * q + 4 * half;
-            if (row0 >= a.Co) continue;
-            float v[4];
+        for (int i = 0; i < NT; i++) {
+            const int p = p0 + (cg + i * NCG) * 32 + l31;
+            if (p >= p1) continue;
+            const int t = (int)(((float)p + 0.5f) * invFP), m = p - t * a.FP;
+            if (m >= valid_m) continue;
+            const long opos = (long)t * a.oT + oo + m;
 #pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int row = row0 + e;
-                float x = acc[i][4 * q + e] + bv[4 * q + e];
-                if (row >= a.relu_lo && row < a.relu_hi) x = convp_act(x, a.act);
-                x = row < a.Co ? x : 0.0f;
-                v[e] = x;
-                if (row >= a.stats_lo && row < a.stats_hi && !(a.par_rows && (row & 1) && m >= a.FP - 1)) { ssum += x; ssq += x * x; }
+            for (int q = 0; q < 4; q++) {
+                const int row0 = mt * 32 + 8 * q + 4 * half;
+                if (row0 >= a.Co) continue;
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int row = row0 + e;
+                    float x = (par ? acc2[i][4 * q + e] : acc[i][4 * q + e]) + bv[4 * q + e];
+                    if (row >= a.relu_lo && row < a.relu_hi) x = convp_act(x, a.act);
+                    x = row < a.Co ? x : 0.0f;
+                    v[e] = x;
+                    if (row >= a.stats_lo && row < a.stats_hi && !(a.par_rows && (row & 1) && m >= a.FP - 1)) { ssum += x; ssq += x * x; }
+                }
+                if (yb) *reinterpret_cast<float4 *>(yb + ((long)(row0 >> 3) * a.y_npos + opos) * 8 + (row0 & 7)) = make_float4(v[0], v[1], v[2], v[3]);
             }
-            if (yb) *reinterpret_cast<float4 *>(yb + ((long)(row0 >> 3) * a.y_npos + opos) * 8 + (row0 & 7)) = make_float4(v[0], v[1], v[2], v[3]);
         }
+        if (a.stats) convp_stats_store(a.stats, a.stats_nslot, par ? a.stats_slot02 : a.stats_slot0, ssum, ssq, reinterpret_cast<float *>(planes), b);
     }
-    if (a.stats) convp_stats_store(a.stats, a.stats_nslot, a.stats_slot0, ssum, ssq, reinterpret_cast<float *>(planes), b);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

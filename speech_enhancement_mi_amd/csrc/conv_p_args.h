@@ -58,6 +58,13 @@ struct ConvPArgs {
     int bl_oT, bl_Fh, bl_Fo; // decoder output column f lives at t * bl_oT + (f & 1) * bl_Fh + (f >> 1); f >= bl_Fo -> zero pad
     const float *bl_nw, *bl_nb, *bl_mnw, *bl_mnb;
     SlabStats bl_sy, bl_su;
+    // ---- second output-frequency parity of a transposed convolution (k_conv_p<.., NTAP2 > 0>, kPOutR): same patch, chunks and
+    //      tiling as the first; its own taps, weights [nchunk][npair2][PL][MT][64], output column offset, valid positions and
+    //      statistics slots (first parity: slots [slot0, slot0 + grid), second: [stats_slot02, stats_slot02 + grid)) ----
+    int ntap2;
+    int rowgrp2[kMaxTaps], coloff2[kMaxTaps];
+    const uint4 *wx2;
+    int oo2, valid_m2, stats_slot02;
 };
 
 struct FeatPArgs {

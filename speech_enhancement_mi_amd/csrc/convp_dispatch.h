@@ -5,9 +5,9 @@
 
 namespace se {
 
-// k_conv_p<NTAP, NT, CO, PL>: 0 = launched, 1 = no such instance
-int conv_p_launch(int ntap, int NT, int CO, int PL, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a);
-bool conv_p_has_instance(int ntap, int NT, int CO);
+// k_conv_p<NTAP, NT, CO, PL[, NTAP2]> (ntap2 = 0: one tap list): 0 = launched, 1 = no such instance
+int conv_p_launch(int ntap, int ntap2, int NT, int CO, int PL, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a);
+bool conv_p_has_instance(int ntap, int NT, int CO, int ntap2 = 0);
 void conv_p_set_attributes();
 void launch_k_featurize_p(int PL, dim3 grid, hipStream_t st, const FeatPArgs &a);
 void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a);

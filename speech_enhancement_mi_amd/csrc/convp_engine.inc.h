@@ -5,7 +5,7 @@
 //
 //   k_featurize_p -> P            4 x ( k_conv_p -> R + statistics ; k_gln_p -> P )      [last level: -> fp32 GRU input]
 //   bottleneck (unchanged GEMM / GRU kernels) -> k_gln2_p -> P
-//   3 x ( k_conv_p even / odd -> R parity-planar ; k_conv_p 1x1 statistics pass ; k_conv_p 1x1 + fused skip gate -> P )
+//   3 x ( k_conv_p both parities -> R parity-planar ; k_skip_p, or k_conv_p 1x1 statistics pass + 1x1 with fused skip gate -> P )
 //   k_conv_p (both parities merged, 4 GEMM rows) -> R ; k_final_mask_p
 //
 // The ring slot r of encoder level i is xinP[i] + r * slot_elems (ONE allocation per level, so that the history slot is
@@ -20,9 +20,11 @@ struct ConvPPlan {
     bool active = false;
     DevBuf wx, bias;
     double flops = 0;
-    struct Geo { int NT = 0, tpw = 0, n_wg = 0, grouped = 0; size_t lds = 0; long items = 0; } geo[16];
-    int ngeo = 0;
-    int npair = 0, terms = 6;
+    struct Geo { int NT = 0, tpw = 0, n_wg = 0, grouped = 0; size_t lds = 0; long items = 0; } geo[16], gpair[16];
+    int ngeo = 0, ngpair = 0;  // gpair: tilings of the k_conv_p<.., NTAP2> instances (a.ntap2 > 0: a second tap list, the odd parity of a
+                               // transposed convolution, on the same patch)
+    int npair = 0, terms = 6, npair2 = 0;
+    double flops_pair = 0;
     std::string name;  // launch-site label ("enc3", "skip0", ...): SE_CONVP_NT_<name>=n forces a tiling for experiments
 };
 
@@ -40,6 +42,7 @@ struct PLevel {
     ConvPPlan gate[2];  // CRN_ELU / student: conv_trans * sigmoid(conv_gated) after the encoder convolution, <= 64 channels per launch
     SkipPPlan sk;
     bool dec_merged = false;
+    bool dec_pair_on = false;  // this batch: both parities in one launch of dec_even (a.ntap2 > 0), dec_odd not launched
 };
 
 // GEMM row -> logical row of the caller's weight selector, for the epilogue's register ownership (conv_p.hip.h)
@@ -89,10 +92,11 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
     if (ntap == 1) CO = C8 >= 4 ? 4 : (C8 >= 2 ? 2 : 1);
     if (C8 % CO) return fail(e, SE_ERR_ARG, "channel octets %d not a multiple of the chunk %d", C8, CO);
     const int nchunk = C8 / CO, npair = (ntap * CO + 1) / 2;
-    pl.ngeo = 0;
+    pl.ngeo = pl.ngpair = 0;
     static const int nts[] = {1, 2, 3, 4, 6, 8, 10, 12};
     for (int nt : nts) {
-        if (!conv_p_has_instance(ntap, nt, CO)) continue;
+        const bool single = conv_p_has_instance(ntap, nt, CO), pair = pl.a.ntap2 && conv_p_has_instance(ntap, nt, CO, pl.a.ntap2);
+        if (!single && !pair) continue;
         const int tpw_max = NCG * nt;
         const int n_wg = (tiles + tpw_max - 1) / tpw_max;
         const int tpw = (tiles + n_wg - 1) / n_wg;
@@ -106,8 +110,9 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
         // whole LDS-DMA instructions: the last one may write zero pieces past `items`, so the allocation covers NI * 256 pieces
         const size_t lds = (size_t)((items + 255) / 256) * 4096;
         if (lds > 160 * 1024) continue;
-        ConvPPlan::Geo &g = pl.geo[pl.ngeo++];
-        g.NT = nt; g.tpw = tpw; g.n_wg = n_wg; g.grouped = grouped; g.lds = lds; g.items = items;
+        const ConvPPlan::Geo g{nt, tpw, n_wg, grouped, lds, items};
+        if (single) pl.geo[pl.ngeo++] = g;
+        if (pair) pl.gpair[pl.ngpair++] = g;
     }
     if (!pl.ngeo) return fail(e, SE_ERR_ARG, "no conv_p tiling fits (taps %d, Ci %d, Co %d, FP %d, St %d)", ntap, Ci, Co, FP, St);
     ConvPArgs &a = pl.a;
@@ -123,6 +128,7 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
     a.nchunk = nchunk; a.St = St; a.act = act; a.relu_lo = relu_lo; a.relu_hi = relu_hi;
     a.out_mode = out_mode; a.row_perm = out_mode == kPOutP || out_mode == kPOutBlend || out_mode == kPOutGate;
     a.valid_m = FP; a.par_rows = 0; a.stats = nullptr;
+    pl.npair2 = a.ntap2 ? (a.ntap2 * CO + 1) / 2 : 0;
     pl.CO = CO; pl.npair = npair; pl.terms = PL == 3 ? 6 : (PL == 2 ? 3 : 1);
     // weights [chunk][pair][plane][mtile][row 32][k 16]: k = half*8 + c <-> entry 2*pair + half = (tap, octet) tap-major
     std::vector<uint16_t> wx((size_t)nchunk * npair * PL * MT * 32 * 16, 0);
@@ -160,34 +166,39 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
     return 0;
 }
 
-// Picks the tiling for the current batch: time ~ rounds x (workgroups per CU x MFMA cycles + staging + epilogue)
-void select_convp_geometry(se_engine *e, ConvPPlan &pl) {
-    if (!pl.active) return;
+// Picks the tiling for the current batch: time ~ rounds x (workgroups per CU x MFMA cycles + staging + epilogue).  pair: among the
+// tilings of the two-parity instances.  Returns the modelled cost.
+double select_convp_geometry(se_engine *e, ConvPPlan &pl, bool pair = false) {
+    if (!pl.active) return 0;
+    const ConvPPlan::Geo *geo = pair ? pl.gpair : pl.geo;
+    const int ngeo = pair ? pl.ngpair : pl.ngeo, npair2 = pair ? pl.npair2 : 0;
     double best = 0;
     int pick = -1;
     int force = getenv("SE_CONVP_NT") ? atoi(getenv("SE_CONVP_NT")) : 0;
     if (const char *s = getenv(("SE_CONVP_NT_" + pl.name).c_str())) force = atoi(s);
-    for (int k = 0; k < pl.ngeo; k++) {
-        const ConvPPlan::Geo &g = pl.geo[k];
-        const int wgpc = (g.NT <= 6 && g.lds <= 80 * 1024) ? 2 : 1;  // k_conv_p<.., NT <= 6> is built for two workgroups per CU
+    for (int k = 0; k < ngeo; k++) {
+        const ConvPPlan::Geo &g = geo[k];
+        const int nacc = npair2 ? 2 * g.NT : g.NT;  // accumulator sets x tiles
+        const int wgpc = (nacc <= 6 && g.lds <= 80 * 1024) ? 2 : 1;  // k_conv_p<.., NT <= 6> is built for two workgroups per CU
         const double rounds = std::ceil((double)g.n_wg * e->B / ((double)e->num_cu * wgpc));
-        const double mfma = (double)pl.a.nchunk * pl.npair * g.NT * pl.terms * 32.0;
+        const double mfma = (double)pl.a.nchunk * (pl.npair + npair2) * g.NT * pl.terms * 32.0;
         const double stage = (double)pl.a.nchunk * g.items * 1.0 + pl.a.nchunk * 2500.0;  // ~16 B/cycle/CU + DMA latency and barriers per chunk
-        const double epi = g.NT * 600.0 + 3000.0;
+        const double epi = nacc * 600.0 + (npair2 ? 2 : 1) * 3000.0;
         const double cost = rounds * (wgpc * mfma + stage + epi);
         if (pick < 0 || cost < best) { best = cost; pick = k; }
-        if (force && g.NT == force) { pick = k; break; }
+        if (force && g.NT == force) { pick = k; best = cost; break; }
     }
+    if (pick < 0 || (pair && force && geo[pick].NT != force)) return 1e300;  // (a pinned tiling the pair instances lack: two launches)
+    const ConvPPlan::Geo &g = geo[pick];
     if (getenv("SE_CONVP_VERBOSE")) {
-        const ConvPPlan::Geo &g = pl.geo[pick];
-        fprintf(stderr, "[conv_p] %-10s taps %2d Ci %3d rows %3d FP %3d: NT %2d tiles/wg %2d wgs/stream %2d lds %6zu items %5ld chunks %d pairs %d | candidates:", pl.name.c_str(),
-                pl.a.ntap, pl.a.Ci, pl.a.Co, pl.a.FP, g.NT, g.tpw, g.n_wg, g.lds, g.items, pl.a.nchunk, pl.npair);
-        for (int k = 0; k < pl.ngeo; k++) fprintf(stderr, " %d", pl.geo[k].NT);
+        fprintf(stderr, "[conv_p] %-10s taps %2d%s Ci %3d rows %3d FP %3d: NT %2d tiles/wg %2d wgs/stream %2d lds %6zu items %5ld chunks %d pairs %d cost %.0f | candidates:", pl.name.c_str(),
+                pl.a.ntap, pair ? "+6" : "", pl.a.Ci, pl.a.Co, pl.a.FP, g.NT, g.tpw, g.n_wg, g.lds, g.items, pl.a.nchunk, pl.npair + npair2, best);
+        for (int k = 0; k < ngeo; k++) fprintf(stderr, " %d", geo[k].NT);
         fprintf(stderr, "\n");
     }
-    const ConvPPlan::Geo &g = pl.geo[pick];
     pl.NT = g.NT; pl.grid_x = g.n_wg; pl.lds = g.lds;
     pl.a.tiles_per_wg = g.tpw; pl.a.grouped = g.grouped;
+    return best;
 }
 
 #ifdef SE_CP_TRACE
@@ -217,24 +228,39 @@ static CpTraceSites g_cp_trace_sites;
 
 int launch_conv_p(se_engine *e, const ConvPPlan &pl, const ConvPArgs &a_in, hipStream_t st, const char *label) {
     if (!pl.active) return 0;
-    ProfScope ps(e, "k_conv_p", label, pl.flops * e->B, st);
+    ProfScope ps(e, "k_conv_p", label, (a_in.ntap2 ? pl.flops_pair : pl.flops) * e->B, st);
     ConvPArgs a = a_in;
     a.trace = nullptr;
 #ifdef SE_CP_TRACE
     a.trace = g_cp_trace_sites.get(label, pl.NT, pl.grid_x);
 #endif
-    if (conv_p_launch(a.ntap, pl.NT, pl.CO, operand_planes(e->precision), dim3(pl.grid_x, e->Bact), pl.lds, st, a))
-        return fail(e, SE_ERR_ARG, "no conv_p kernel instance for %d taps x %d tiles x %d octets", a.ntap, pl.NT, pl.CO);
+    if (conv_p_launch(a.ntap, a.ntap2, pl.NT, pl.CO, operand_planes(e->precision), dim3(pl.grid_x, e->Bact), pl.lds, st, a))
+        return fail(e, SE_ERR_ARG, "no conv_p kernel instance for %d (+ %d) taps x %d tiles x %d octets", a.ntap, a.ntap2, pl.NT, pl.CO);
     HIPCHECK(e, hipGetLastError());
     return 0;
 }
 
+// statistics slots of a decoder level's odd parity: its own launch, the second half of a pair launch, or none (last level)
+int dec_odd_slots(const PLevel &pv) { return pv.dec_pair_on ? pv.dec_even.grid_x : (pv.dec_odd.active ? pv.dec_odd.grid_x : 0); }
+
 uint4 *decin_p(se_engine *e, int slot) { return reinterpret_cast<uint4 *>(e->cp->decinP[slot].p); }
 
 void select_all_p(se_engine *e) {
-    for (int i = 0; i < e->L; i++)
-        for (ConvPPlan *p : {&e->cp->pv[i].enc, &e->cp->pv[i].dec_even, &e->cp->pv[i].dec_odd, &e->cp->pv[i].skip, &e->cp->pv[i].skipm, &e->cp->pv[i].gate[0], &e->cp->pv[i].gate[1]})
-            select_convp_geometry(e, *p);
+    for (int i = 0; i < e->L; i++) {
+        PLevel &pv = e->cp->pv[i];
+        for (ConvPPlan *p : {&pv.enc, &pv.skip, &pv.skipm, &pv.gate[0], &pv.gate[1]}) select_convp_geometry(e, *p);
+        // a decoder level runs its two parities in one launch where the model prices that below the two launches of this batch
+        pv.dec_pair_on = false;
+        if (pv.dec_even.active && pv.dec_even.a.ntap2 && pv.dec_even.ngpair) {
+            const double two = select_convp_geometry(e, pv.dec_even) + select_convp_geometry(e, pv.dec_odd);
+            ConvPPlan::Geo keep{pv.dec_even.NT, pv.dec_even.a.tiles_per_wg, pv.dec_even.grid_x, pv.dec_even.a.grouped, pv.dec_even.lds, 0};
+            if (select_convp_geometry(e, pv.dec_even, true) < two) pv.dec_pair_on = true;
+            else { pv.dec_even.NT = keep.NT; pv.dec_even.a.tiles_per_wg = keep.tpw; pv.dec_even.grid_x = keep.n_wg; pv.dec_even.a.grouped = keep.grouped; pv.dec_even.lds = keep.lds; }
+        } else {
+            select_convp_geometry(e, pv.dec_even);
+            select_convp_geometry(e, pv.dec_odd);
+        }
+    }
     if (e->cp->pre_p)
         for (int i = 0; i < e->npre; i++) select_convp_geometry(e, e->cp->pre[i]);
 }
@@ -347,6 +373,7 @@ int prepare_weights_p(se_engine *e) {
         int rc;
         pv.dec_even.name = "dec" + std::to_string(j) + "_even"; pv.dec_odd.name = "dec" + std::to_string(j) + "_odd";
         pv.skip.name = "skip" + std::to_string(j); pv.skipm.name = "skipstat" + std::to_string(j);
+        pv.dec_even.a.ntap2 = 0;
         pv.dec_merged = lvl == 0;  // the last block (2 mask channels): both parities as 4 GEMM rows of ONE launch
         if (pv.dec_merged) {
             std::vector<std::array<int, 4>> tu;
@@ -369,6 +396,13 @@ int prepare_weights_p(se_engine *e) {
                 for (int kt = 0; kt < 3; kt++) te.push_back({kf, kt, 2 - kt, 2 - kf / 2});
             for (int kf = 1; kf < 5; kf += 2)
                 for (int kt = 0; kt < 3; kt++) to.push_back({kf, kt, 2 - kt, 1 + (3 - kf) / 2});
+            // e->dec_pair: ONE launch (k_conv_p<9, NT, 1, PL, 6>) can stage each chunk of the patch once for both parities; the odd
+            // parity then runs over the even one's Fi positions per row and drops m = Fi - 1 (valid_m2).  select_all_p decides per
+            // batch (PLevel::dec_pair_on); otherwise two launches.
+            // Not with one fp16 plane: there the single-parity kernels are small enough to share a CU with more workgroups than
+            // the model counts, and the pair launch measured 2 % slower (student, B = 1024, fp16).
+            const bool pair = e->dec_pair && operand_planes(e->precision) >= 2;
+            pv.dec_even.a.ntap2 = pair ? (int)to.size() : 0;  // before planning: plan_conv_p then also lists the pair tilings
             if ((rc = plan_conv_p(e, pv.dec_even, Ci, Co, Fi, Fi, 1, 1, 0, 3, d, Fi + 2, te, wsel, *b, 0, Co, e->act, kPOutR))) return rc;
             if ((rc = plan_conv_p(e, pv.dec_odd, Ci, Co, Fi - 1, Fi, 1, 1, 0, 3, d, Fi + 2, to, wsel, *b, 0, Co, e->act, kPOutR))) return rc;
             for (ConvPPlan *q : {&pv.dec_even, &pv.dec_odd}) {
@@ -378,6 +412,14 @@ int prepare_weights_p(se_engine *e) {
             }
             pv.dec_even.flops = 2.0 * Ci * Co * 9 * Fi * T;
             pv.dec_odd.flops = 2.0 * Ci * Co * 6 * Fi * T;
+            if (pair) {  // the odd parity's taps and weights (same chunks, CO = 1) ride along in the even plan
+                ConvPArgs &a = pv.dec_even.a;
+                const ConvPArgs &o = pv.dec_odd.a;
+                if (o.nchunk != a.nchunk || o.CoPad != a.CoPad) return fail(e, SE_ERR_ARG, "decoder parities of level %d do not share chunks", j);
+                for (int t = 0; t < o.ntap; t++) { a.rowgrp2[t] = o.rowgrp[t]; a.coloff2[t] = o.coloff[t]; }
+                a.wx2 = o.wx; a.oo2 = Fi; a.valid_m2 = Fi - 1;
+                pv.dec_even.flops_pair = pv.dec_even.flops + pv.dec_odd.flops;
+            }
         }
         if (lvl > 0) {  // skip path (CRN.py:387-396): statistics pass of residualmask + the gated 1x1 pair
             auto *mw = param(e, p + "residualmask.weight", (size_t)Co * Co);
@@ -493,7 +535,7 @@ int alloc_state_p(se_engine *e, hipStream_t st) {
     for (int i = 0; i < L; i++) {
         PLevel &pv = S.pv[i];
         if ((rc = dev_alloc(e, e->enc_stats[i], (size_t)B * 2 * (pv.enc.grid_x + (pv.gate[0].active ? pv.gate[0].grid_x : 0) + (pv.gate[1].active ? pv.gate[1].grid_x : 0) + 1)))) return rc;
-        if ((rc = dev_alloc(e, e->dec_stats[i], (size_t)B * 2 * (pv.dec_even.grid_x + (pv.dec_odd.active ? pv.dec_odd.grid_x : 0) + 1)))) return rc;
+        if ((rc = dev_alloc(e, e->dec_stats[i], (size_t)B * 2 * (pv.dec_even.grid_x + dec_odd_slots(pv) + 1)))) return rc;
         if ((rc = dev_alloc(e, e->skip_stats[i], (size_t)B * 2 * ((pv.skipm.active ? pv.skipm.grid_x : 0) + 1)))) return rc;
     }
     return 0;
@@ -618,14 +660,16 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
         const int lvl = L - 1 - j;
         const int Co = lvl == 0 ? 2 : e->Ch[lvl], Fi = e->F[lvl + 1], Fo = 2 * Fi - 1;
         PLevel &pv = S.pv[j];
-        const int ne = pv.dec_even.grid_x, no = pv.dec_odd.active ? pv.dec_odd.grid_x : 0;
+        const int ne = pv.dec_even.grid_x, no = dec_odd_slots(pv);
         for (ConvPPlan *q : {&pv.dec_even, &pv.dec_odd}) {
-            if (!q->active) continue;
+            if (!q->active || (q == &pv.dec_odd && pv.dec_pair_on)) continue;
             ConvPArgs a = q->a;
+            if (!pv.dec_pair_on) a.ntap2 = 0;
             a.xbase = xin; a.xbytes = (unsigned)xin_bytes; a.cur_off = 0; a.prev_off = -1;
             a.y = S.decR[j].p;
-            a.stats = e->dec_stats[j].p; a.stats_nslot = ne + no; a.stats_slot0 = q == &pv.dec_odd ? ne : 0;
-            if ((rc = launch_conv_p(e, *q, a, st, ("dec" + std::to_string(j) + (q == &pv.dec_odd ? "_odd" : "_even")).c_str()))) return rc;
+            a.stats = e->dec_stats[j].p; a.stats_nslot = ne + no; a.stats_slot0 = q == &pv.dec_odd ? ne : 0; a.stats_slot02 = ne;
+            const char *sfx = a.ntap2 ? "" : (q == &pv.dec_odd ? "_odd" : "_even");
+            if ((rc = launch_conv_p(e, *q, a, st, ("dec" + std::to_string(j) + sfx).c_str()))) return rc;
         }
         const SlabStats sy{e->dec_stats[j].p, ne + no, (long)Co * T * Fo, e->eps_mode};
         if (lvl > 0) {

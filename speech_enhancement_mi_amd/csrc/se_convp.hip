@@ -26,21 +26,46 @@ namespace se {
 #define SE_CP_ALL(X) SE_CP_NTS(X, 1)
 #endif
 
-int SE_FN(conv_p_launch_pl)(int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a) {
+// both parities of a transposed convolution in one launch (9 + 6 taps, decoder levels above the last): k_conv_p<9, NT, 1, PL, 6>.
+// Two accumulator sets: NT <= 3 keeps two workgroups per CU without scratch (NT = 4 / 6 spill at PL = 3).  Not built for one fp16
+// plane: the engine keeps two launches there (convp_engine.inc.h, prepare_weights_p).
+#if SE_CP_NTAP == 9 && SE_CP_PL >= 2
+#define SE_CP_PAIR(X) X(1, 1) X(2, 1) X(3, 1)
+#define SE_CP_NTAP2 6
+#else
+#define SE_CP_PAIR(X)
+#define SE_CP_NTAP2 0
+#endif
+
+int SE_FN(conv_p_launch_pl)(int ntap2, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a) {
 #define SE_CP_CASE(NT_, CO_) \
     case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL>), grid, dim3(256), lds, st, a); return 0;
+#define SE_CP_CASE2(NT_, CO_) \
+    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL, SE_CP_NTAP2>), grid, dim3(256), lds, st, a); return 0;
+    if (ntap2 == 0) {
+        switch (NT * 8 + CO) {
+            SE_CP_ALL(SE_CP_CASE)
+            default: return 1;
+        }
+    }
+    if (ntap2 != SE_CP_NTAP2) return 1;
     switch (NT * 8 + CO) {
-        SE_CP_ALL(SE_CP_CASE)
+        SE_CP_PAIR(SE_CP_CASE2)
         default: return 1;
     }
 #undef SE_CP_CASE
+#undef SE_CP_CASE2
 }
 
 void SE_FN(conv_p_set_attributes_pl)() {
 #define SE_CP_ATTR(NT_, CO_) \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SE_CP_ATTR2(NT_, CO_) \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL, SE_CP_NTAP2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     SE_CP_ALL(SE_CP_ATTR)
+    SE_CP_PAIR(SE_CP_ATTR2)
 #undef SE_CP_ATTR
+#undef SE_CP_ATTR2
 }
 
 #if SE_CP_PL == 3 && SE_CP_NTAP == 15

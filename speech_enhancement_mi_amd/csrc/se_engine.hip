@@ -138,6 +138,7 @@ struct se_engine {
     // 133 vs 228 us for the three GEMMs) and ties at 1280; the two-launch skip gate wins up to B = 64 (119 vs 147 us)
     int skinny_rows = 800;    // SE_GEMM_SKINNY_ROWS: bottleneck GEMMs with up to this many rows run on the skinny fp32 kernel
     int skip_min_batch = 96;  // SE_SKIP_MIN_BATCH: the streaming skip kernel needs at least this many streams
+    int dec_pair = 1;         // SE_DEC_PAIR=0: the transposed convolutions above the last level run one k_conv_p launch per parity
     int gemm_p_env = 1;
     DevBuf gruinP[kRing], seqP[4][kRing];  // [PL][B*T][D'] / [PL][B*T][H] bf16 planes
     DevBuf wih_xp;                          // W_ih0 planes with K in the engine's feature order (k_gemm_p)
@@ -1074,6 +1075,7 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (const char *s = getenv("SE_GEMM_P")) e->gemm_p_env = atoi(s);
     if (const char *s = getenv("SE_GEMM_SKINNY_ROWS")) e->skinny_rows = atoi(s);
     if (const char *s = getenv("SE_SKIP_MIN_BATCH")) e->skip_min_batch = atoi(s);
+    if (const char *s = getenv("SE_DEC_PAIR")) e->dec_pair = atoi(s) != 0 ? 1 : 0;
     e->cp = new se_convp_state();
     {
         int ncu = 0;
