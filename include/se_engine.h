@@ -140,7 +140,7 @@ int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap,
                     int64_t *launches, double *flops_per_launch);
 
 int se_abi_version(void);  /* 4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
-                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* */
+                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward) */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -377,6 +377,25 @@ int se_gbf_seq_fwd(const float *hS, const float *hN, const float *fcS_w, const f
                    const float *fcN_b, const float *nN_w, const float *nN_b, float *phi, float *yS, float *yN, int S, int B, int F, int T, int H, void *stream);
 int se_gbf_bf_fwd(const float *phi, const float *spec, const float *w0, const float *b0, const float *g, const float *beta, const float *w3,
                   const float *b3, float *Y, float *wout, int S, int M, int T, int F, int H, void *stream);
+/* Backward of the three head stages (training).  Forward statistics are recomputed from the same inputs.  Parameter gradients come out
+ * as slabs / planes to fold in a fixed order (se_train_colsum_tall, se_train_gemm_tn_det); no atomics.
+ * se_gbf_bf_bwd: dY [S][T][F][2] = raw se_sig_stft of the segment gradient (the irfft weights c_f / n_fft are applied here) ->
+ *   dphi [S][F][T][9]; planes over rows r = s*F*T + f*T + t: dpre [r][H] (linear.0 output gradient: linear.0.weight = dpre^T phi,
+ *   linear.0.bias = column sums), act [r][H] (linear.3 input), dw [r][8] (beamforming weight gradient, columns 6, 7 zero:
+ *   linear.3.weight = dw^T act); pg / pb [S][T][F]: sums over H for linear.2.weight / bias (column sums over S*T rows).
+ * se_gbf_seq_bwd: dphi -> dhS / dhN (last-layer GRU output gradients, rows [B][F][Nc][T] of H), dvS / dvN [rows][16] (fc_output_layer
+ *   output gradient, columns 9..15 zero: fc weight = dv^T h), part [S*F][54]: per model q at q*27 norm.weight (9), norm.bias (9),
+ *   fc_output_layer.bias (9).
+ * se_gbf_psd_bwd: drowsS / drowsN (gradients of the GRU input rows [B][F][Nc][T][16], columns 0..8 read) -> dxl [S][4M*9][T][F];
+ *   part [S][4][F*T]: ln_S weight, ln_S bias, ln_N weight, ln_N bias.  The noisy spectrum carries no gradient. */
+int se_gbf_psd_bwd(const float *xl, const float *spec, const float *wS, const float *bS, const float *wN, const float *bN, const float *drowsS,
+                   const float *drowsN, float *dxl, float *part, int S, int B, int M, int T, int F, void *stream);
+int se_gbf_seq_bwd(const float *dphi, const float *hS, const float *hN, const float *fcS_w, const float *fcS_b, const float *nS_w,
+                   const float *nS_b, const float *fcN_w, const float *fcN_b, const float *nN_w, const float *nN_b, float *dhS, float *dhN,
+                   float *dvS, float *dvN, float *part, int S, int B, int F, int T, int H, void *stream);
+int se_gbf_bf_bwd(const float *dY, const float *phi, const float *spec, const float *w0, const float *b0, const float *g, const float *beta,
+                  const float *w3, float *dphi, float *dpre, float *act, float *dw, float *pg, float *pb, int S, int M, int T, int F, int H,
+                  int n_fft, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

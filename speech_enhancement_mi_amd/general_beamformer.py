@@ -15,6 +15,8 @@ Two interchangeable paths:
   * the kernel path (`realtime_process` of a GPU tensor with grad disabled): every segment of a call at once, segment-major as in
     train_net.CRNFunction - U-Net on the se_train_* kernels, the two GRUs as persistent launches, the beamforming head on
     csrc/se_gbf.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
+  * HIP training (opt-in, use_hip_training(True)): `realtime_process` of a GPU tensor with grad enabled is ONE autograd node,
+    GBFFunction - the kernel path's forward keeping its activations, and a backward on the same kernels plus se_gbf_*_bwd.
 """
 from __future__ import annotations
 
@@ -23,10 +25,17 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .train_net import _new, _p, _run, _sig, conv_w, gln_fwd
+from .train_net import _new, _p, _run, _sig, colsum3, colsum_tall, conv_w, gemm_tn, gln_bwd, gln_fwd, transpose, wgrad
 
 EPS = 1e-8
 _DEFAULT_MAX_SEGMENTS = 8
+
+
+def _as_flag(flag):
+    """realtime_process's flag: a bool, or the trainer's per-utterance flag tensor (data['flag'], shape [B]; one value per batch)."""
+    if isinstance(flag, torch.Tensor):
+        return bool(flag.reshape(-1)[0].item())
+    return bool(flag)
 
 
 class _Norm(nn.Module):  # GlobalLayerNorm parameter holder, GeneralBeamformer.py:22-34
@@ -124,8 +133,10 @@ class GeneralBeamformer(nn.Module):
         self.gru_S = _SequenceModel(num_inputs * num_inputs, hidden, num_layers)
         self.gru_N = _SequenceModel(num_inputs * num_inputs, hidden, num_layers)
         self.linear = nn.Sequential(nn.Linear(9, hidden), nn.ReLU(), _Norm(num_freqs), nn.Linear(hidden, 6))
-        self.max_segments = _DEFAULT_MAX_SEGMENTS  # segments per kernel-path pass: bounds peak memory; the state carries across passes
+        self.max_segments = _DEFAULT_MAX_SEGMENTS  # segments per inference kernel pass: bounds peak memory; the state carries across
+        #                                            passes.  GBFFunction (training) runs every segment of a call in one pass.
         self._hip = True
+        self._hip_train = False
         self._tstate = None   # restatement: dict(buf=[...], hS, hN)
         self._kstate = None   # kernel path: dict(B, buf=[...], h=[[...], [...]])
         self._last_path = None
@@ -152,11 +163,32 @@ class GeneralBeamformer(nn.Module):
         y, self._tstate = self._segment(x, self._tstate)
         return y
 
+    def use_hip_training(self, flag=True):
+        """True: realtime_process of a GPU tensor with grad enabled runs forward AND backward on the kernels (GBFFunction), sharing the
+        carried state with the inference kernel path.  False (default): grad-enabled calls take the restatement.  Raises ValueError
+        at once for a geometry or a dropout setting the training kernels do not cover."""
+        if flag:
+            err = self.hip_training_error()
+            if err:
+                raise ValueError(f"GeneralBeamformer HIP training: {err}")
+        self._hip_train = bool(flag)
+        return self
+
     def realtime_process(self, mixture, flag=False):
-        flag = bool(flag.item() if torch.is_tensor(flag) else flag)
-        path = "kernel" if (self._hip and mixture.is_cuda and not torch.is_grad_enabled()) else "torch"
+        flag = _as_flag(flag)
+        grad = torch.is_grad_enabled()
+        train = self._hip_train and mixture.is_cuda and grad
+        path = "kernel" if train or (self._hip and mixture.is_cuda and not grad) else "torch"
         if flag and self._last_path not in (None, path):
             raise RuntimeError("flag=True continues the state of the other path (kernels vs restatement): start with flag=False")
+        if train:
+            err = self.hip_training_error()
+            if err:
+                raise ValueError(f"GeneralBeamformer HIP training: {err}")
+            params = [p for _, p in self.named_parameters()]
+            out = GBFFunction.apply(self, mixture, flag, *params)
+            self._last_path = path
+            return out
         self._last_path = path
         if path == "kernel":
             return self._kernel_process(mixture, flag)
@@ -240,7 +272,7 @@ class GeneralBeamformer(nn.Module):
     def spectrum(self, seg):
         """stft_trans of the segments [B, M, N, K] -> [B, M, N, F, T, 2] (torch.stft; speechbrain's STFT wrapper)."""
         B, M, N, Ks = seg.shape
-        win = torch.hamming_window(self._win, device=seg.device)
+        win = torch.hamming_window(self._win, device=seg.device, dtype=seg.dtype)
         X = torch.stft(seg.reshape(-1, Ks), self._cfg["n_fft"], self._hop, self._win, win, center=True, pad_mode="constant", normalized=False,
                        onesided=True, return_complex=True)
         return torch.view_as_real(X).reshape(B, M, N, *X.shape[-2:], 2)
@@ -258,7 +290,7 @@ class GeneralBeamformer(nn.Module):
         N = 2 * (Lp + gap + P) // Ks
         idx = (torch.arange(N, device=mixture.device) * P)[:, None] + torch.arange(Ks, device=mixture.device)[None, :]
         seg = xp[:, :, idx]  # [B, M, N, K]
-        win = torch.hamming_window(self._win, device=mixture.device)
+        win = torch.hamming_window(self._win, device=mixture.device, dtype=mixture.dtype)
         n_fft = self._cfg["n_fft"]
         X = self.spectrum(seg)
         outs = []
@@ -316,6 +348,149 @@ class GeneralBeamformer(nn.Module):
             self._pad_cache[id(g)] = (key, wp)
         return self._pad_cache[id(g)][1]
 
+    def hip_training_error(self):
+        """None when GBFFunction can train this model as it stands, else the limit that fails (geometry, or active dropout)."""
+        err = self.kernel_geometry_error()
+        if err:
+            return err
+        if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist)):
+            return "dropout is active in training mode: the training kernels have no dropout (use the restatement, or dropout = 0)"
+        return None
+
+    def _kernel_setup(self, mixture, flag):
+        """Geometry of one realtime_process call on the kernels and the state it starts from (the carried one for flag=True)."""
+        dev = mixture.device
+        B, M, L = mixture.shape
+        c = self._cfg
+        Ks, n_fft, H, NL = self.segment_length, c["n_fft"], c["hidden"], c["num_layers"]
+        P = Ks // 2
+        T, F0 = 1 + Ks // self._hop, n_fft // 2 + 1
+        Lp = L if flag else L + P
+        gap = Ks - (P + Lp % Ks) % Ks
+        Lv = len(self.convlist)
+        ch = [2 * M - 1] + c["num_channels"]
+        Fq = [F0]
+        for _ in range(Lv):
+            Fq.append((Fq[-1] - 1) // 2 + 1)
+        g = dict(B=B, M=M, L=L, Ks=Ks, n_fft=n_fft, H=H, NL=NL, P=P, T=T, F0=F0, Lp=Lp, off0=-P if flag else -2 * P, skip=0 if flag else P,
+                 N=2 * (Lp + gap + P) // Ks, Lv=Lv, ch=ch, Fq=Fq, BF=B * F0, sig=_sig(dev, n_fft, self._win, self._hop, Ks))
+        state = self._kstate if flag else None
+        if state is not None and state["B"] != B:
+            raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
+        if state is None:
+            state = dict(B=B, buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
+                         h=[[torch.zeros(B * F0, H, device=dev) for _ in range(NL)] for _ in range(2)])
+        return g, state
+
+    def _kernel_pass(self, mixture, g, state, n0, Nc, yseg, tmo, sv=None):
+        """Segments [n0, n0 + Nc) of the call: STFT, U-Net, head, GRUs, iSTFT into yseg; advances `state`.  sv (a dict): also keep
+        what GBFFunction.backward needs (GRU gates, layer outputs, the U-Net activations and gLN / skip statistics)."""
+        lib = K._lib()
+        dev = mixture.device
+        st = K._st
+        B, M, L, T, F0, H, NL, Lv, ch, Fq, BF, P = (g[k] for k in ("B", "M", "L", "T", "F0", "H", "NL", "Lv", "ch", "Fq", "BF", "P"))
+        S = Nc * B
+        keep = sv is not None
+        spec = _new(Nc, B * M, T, F0, 2, dev=dev)
+        _run("k_stft", 0.0, lib.se_sig_stft, g["sig"], _p(mixture), B, M, L, g["off0"] + n0 * P, P, Nc, _p(spec), st())
+        # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input of block i (its time history)
+        xin = []
+        for i in range(Lv):
+            t_ = _new(Nc + 1, B, ch[i], T, Fq[i], dev=dev)
+            t_[0].copy_(state["buf"][i])
+            xin.append(t_)
+        _run("k_tfeat", 0.0, lib.se_train_feat, _p(spec), _p(xin[0], B * ch[0] * T * F0), S, M, T, F0, 0, st())
+        ys, stats_e, dec = [], [], []
+        for i, blk in enumerate(self.convlist):
+            Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
+            y = _new(S, Co, T, Fo, dev=dev)
+            conv_w(0, _p(xin[i], B * Ci * T * Fi), _p(xin[i]), blk.conv.weight, Ci * 15, 15, blk.conv.bias, y, S, Ci, Co, T, Fi, Fo, d, 0)
+            if i < Lv - 1:
+                out, off = xin[i + 1], B * Co * T * Fo
+            else:
+                out, off = _new(S, Co, T, Fo, dev=dev), 0
+            stt = gln_fwd(y, (Co * T * Fo, T * Fo, Fo), _p(out, off), (Co * T * Fo, T * Fo, Fo), blk.norm.weight, blk.norm.bias, S, Co, T, Fo, Fo, 0, 1, 0)
+            if keep:
+                ys.append(y)
+                stats_e.append(stt)
+            x_in = out
+        Ci, Fi = ch[Lv], Fq[Lv]
+        for j, blk in enumerate(self.deconvlist):
+            Co, d, Fy = blk.conv.weight.shape[1], 2 ** j, 2 * Fi - 1
+            yd = _new(S, Co, T, Fy, dev=dev)
+            for kind in (1, 2):
+                conv_w(kind, _p(x_in), None, blk.conv.weight, 15, Co * 15, blk.conv.bias, yd, S, Ci, Co, T, Fi, Fy, d)
+            rec = dict(x_in=x_in, yd=yd, Ci=Ci, Co=Co, Fi=Fi, Fy=Fy, d=d)
+            if j < Lv - 1:
+                kk = Lv - 1 - j
+                Cr, Fr = ch[kk], Fq[kk]
+                z = _new(S, Co, T, Fr, dev=dev)
+                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(z), (Co * T * Fr, T * Fr, Fr), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fr, 0, 1, 0)
+                uv = _new(S, 2 * Co, T, Fr, dev=dev)   # residual | residualmask, one 1x1 launch per half (2 Co may exceed 128 rows)
+                res = _p(xin[kk], B * Cr * T * Fr)
+                conv_w(3, res, None, blk.residual.weight, Cr, 1, blk.residual.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, 0)
+                conv_w(3, res, None, blk.residualmask.weight, Cr, 1, blk.residualmask.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, Co)
+                out = _new(S, Co, T, Fr, dev=dev)
+                stt = _new(S, 2, dev=dev)
+                _run("k_tskip_fwd", 0.0, lib.se_train_skip_fwd, _p(uv), _p(z), _p(blk.residualnorm.weight), _p(blk.residualnorm.bias), _p(out),
+                     _p(stt), S, Co, T, Fr, 1, 0, st())
+                rec.update(z=z, uv=uv, st_uv=stt, k=kk, Cr=Cr, Fr=Fr)
+                x_in, Ci, Fi = out, Co, Fr
+            else:
+                xl = _new(S, Co, T, Fy, dev=dev)
+                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(xl), (Co * T * Fy, T * Fy, Fy), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fy, 0, 1, 0)
+            if keep:
+                dec.append(rec)
+        # head: PSD + ln -> GRU rows [B*F][Nc*T][16] (stream-major), two GRU models, sequence head, beamformer
+        R, TT = BF * Nc * T, Nc * T
+        rows = [_new(R, 16, dev=dev), _new(R, 16, dev=dev)]
+        _run("k_gbf_psd", 0.0, lib.se_gbf_psd_fwd, _p(xl), _p(spec), _p(self.ln_S.weight), _p(self.ln_S.bias), _p(self.ln_N.weight),
+             _p(self.ln_N.bias), _p(rows[0]), _p(rows[1]), S, B, M, T, F0, st())
+        models = (self.gru_S, self.gru_N)
+        last, outs, gates, h0s = [], [[], []], [[], []], [[], []]
+        for q, m in enumerate(models):
+            gm = m.sequence_model
+            x_l = rows[q]
+            for l in range(NL):
+                gi = K._gemm(x_l, self._padded_w_ih(gm) if l == 0 else getattr(gm, f"weight_ih_l{l}"), getattr(gm, f"bias_ih_l{l}"))
+                out = _new(R, H, dev=dev)
+                gt = _new(R, 4 * H, dev=dev) if keep else None
+                hT = _new(BF, H, dev=dev)
+                sc = K._scratch(dev, BF, H, tag=("gbf", q, l))
+                _run("k_gru_pseq_fwd", 2.0 * BF * 3 * H * H * TT, lib.se_train_gru_pseq_fwd, _p(gi), _p(state["h"][q][l]),
+                     _p(getattr(gm, f"weight_hh_l{l}")), _p(getattr(gm, f"bias_hh_l{l}")), _p(out), _p(gt), _p(hT), _p(sc), BF, TT, H, TT, 0, TT, st())
+                tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
+                del gi
+                if keep:
+                    outs[q].append(out)
+                    gates[q].append(gt)
+                    h0s[q].append(state["h"][q][l])
+                state["h"][q][l] = hT
+                x_l = out
+            last.append(x_l)
+        if not keep:
+            del rows
+        phi = _new(S, F0, T, 9, dev=dev)
+        sS, sN = self.gru_S, self.gru_N
+        _run("k_gbf_seq", 0.0, lib.se_gbf_seq_fwd, _p(last[0]), _p(last[1]), _p(sS.fc_output_layer.weight), _p(sS.fc_output_layer.bias),
+             _p(sS.norm.weight), _p(sS.norm.bias), _p(sN.fc_output_layer.weight), _p(sN.fc_output_layer.bias), _p(sN.norm.weight),
+             _p(sN.norm.bias), _p(phi), None, None, S, B, F0, T, H, st())
+        del last
+        Y = _new(S, T, F0, 2, dev=dev)
+        lin = self.linear
+        _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
+             _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
+        _run("k_istft", 0.0, lib.se_sig_istft, g["sig"], _p(Y), S, _p(yseg, n0 * B * g["Ks"]), st())
+        state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
+        if keep:
+            sv.update(spec=spec, xin=xin, ys=ys, stats_e=stats_e, dec=dec, xl=xl, rows=rows, outs=outs, gates=gates, h0s=h0s, phi=phi)
+
+    def _check_timeouts(self, tmo, g):
+        if tmo and int(torch.cat(tmo).abs().sum()) != 0:
+            self._kstate = None
+            raise RuntimeError(f"persistent GRU kernel timed out waiting for its peer workgroups ({g['BF']} streams, hidden {g['H']}): "
+                               "output invalid")
+
     @torch.no_grad()
     def _kernel_process(self, mixture, flag):
         err = self.kernel_geometry_error()
@@ -323,123 +498,193 @@ class GeneralBeamformer(nn.Module):
             raise ValueError(f"GeneralBeamformer kernel path: {err}")
         if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist)):
             raise ValueError("GeneralBeamformer kernel path: inference only (dropout is active in training mode; use the restatement)")
-        lib = K._lib()
         K._need_gpu(mixture, self.ln_S.weight)
-        dev = mixture.device
         mixture = mixture.contiguous().float()
-        B, M, L = mixture.shape
-        c = self._cfg
-        Ks, n_fft, H, NL = self.segment_length, c["n_fft"], c["hidden"], c["num_layers"]
-        P = Ks // 2
-        T, F0 = 1 + Ks // self._hop, n_fft // 2 + 1
-        sig = _sig(dev, n_fft, self._win, self._hop, Ks)
-        Lp = L if flag else L + P
-        off0 = -P if flag else -2 * P
-        skip = 0 if flag else P
-        gap = Ks - (P + Lp % Ks) % Ks
-        N = 2 * (Lp + gap + P) // Ks
-        st = K._st
-        Lv = len(self.convlist)
-        ch = [2 * M - 1] + c["num_channels"]
-        Fq = [F0]
-        for _ in range(Lv):
-            Fq.append((Fq[-1] - 1) // 2 + 1)
-        state = self._kstate if flag else None
-        if state is not None and state["B"] != B:
-            raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
-        BF = B * F0
-        if state is None:
-            state = dict(B=B, buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
-                         h=[[torch.zeros(BF, H, device=dev) for _ in range(NL)] for _ in range(2)])
-        models = (self.gru_S, self.gru_N)
-        w_ih0 = [self._padded_w_ih(m.sequence_model) for m in models]
-        yseg = _new(N, B, Ks, dev=dev)
+        g, state = self._kernel_setup(mixture, flag)
+        N, B = g["N"], g["B"]
+        yseg = _new(N, B, g["Ks"], dev=mixture.device)
         tmo = []
         step = max(1, int(self.max_segments))
         for n0 in range(0, N, step):
-            Nc = min(step, N - n0)
-            S = Nc * B
-            spec = _new(Nc, B * M, T, F0, 2, dev=dev)
-            _run("k_stft", 0.0, lib.se_sig_stft, sig, _p(mixture), B, M, L, off0 + n0 * P, P, Nc, _p(spec), st())
-            # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input of block i (its time history)
-            xin = []
-            for i in range(Lv):
-                t_ = _new(Nc + 1, B, ch[i], T, Fq[i], dev=dev)
-                t_[0].copy_(state["buf"][i])
-                xin.append(t_)
-            _run("k_tfeat", 0.0, lib.se_train_feat, _p(spec), _p(xin[0], B * ch[0] * T * F0), S, M, T, F0, 0, st())
-            for i, blk in enumerate(self.convlist):
-                Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
-                y = _new(S, Co, T, Fo, dev=dev)
-                conv_w(0, _p(xin[i], B * Ci * T * Fi), _p(xin[i]), blk.conv.weight, Ci * 15, 15, blk.conv.bias, y, S, Ci, Co, T, Fi, Fo, d, 0)
-                if i < Lv - 1:
-                    out, off = xin[i + 1], B * Co * T * Fo
-                else:
-                    out, off = _new(S, Co, T, Fo, dev=dev), 0
-                gln_fwd(y, (Co * T * Fo, T * Fo, Fo), _p(out, off), (Co * T * Fo, T * Fo, Fo), blk.norm.weight, blk.norm.bias, S, Co, T, Fo, Fo, 0, 1, 0)
-                x_in = out
-            Ci, Fi = ch[Lv], Fq[Lv]
-            for j, blk in enumerate(self.deconvlist):
-                Co, d, Fy = blk.conv.weight.shape[1], 2 ** j, 2 * Fi - 1
-                yd = _new(S, Co, T, Fy, dev=dev)
-                for kind in (1, 2):
-                    conv_w(kind, _p(x_in), None, blk.conv.weight, 15, Co * 15, blk.conv.bias, yd, S, Ci, Co, T, Fi, Fy, d)
-                if j < Lv - 1:
-                    kk = Lv - 1 - j
-                    Cr, Fr = ch[kk], Fq[kk]
-                    z = _new(S, Co, T, Fr, dev=dev)
-                    gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(z), (Co * T * Fr, T * Fr, Fr), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fr, 0, 1, 0)
-                    uv = _new(S, 2 * Co, T, Fr, dev=dev)   # residual | residualmask, one 1x1 launch per half (2 Co may exceed 128 rows)
-                    res = _p(xin[kk], B * Cr * T * Fr)
-                    conv_w(3, res, None, blk.residual.weight, Cr, 1, blk.residual.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, 0)
-                    conv_w(3, res, None, blk.residualmask.weight, Cr, 1, blk.residualmask.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, Co)
-                    out = _new(S, Co, T, Fr, dev=dev)
-                    stt = _new(S, 2, dev=dev)
-                    _run("k_tskip_fwd", 0.0, lib.se_train_skip_fwd, _p(uv), _p(z), _p(blk.residualnorm.weight), _p(blk.residualnorm.bias), _p(out),
-                         _p(stt), S, Co, T, Fr, 1, 0, st())
-                    x_in, Ci, Fi = out, Co, Fr
-                else:
-                    xl = _new(S, Co, T, Fy, dev=dev)
-                    gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(xl), (Co * T * Fy, T * Fy, Fy), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fy, 0, 1, 0)
-            # head: PSD + ln -> GRU rows [B*F][Nc*T][16] (stream-major), two GRU models, sequence head, beamformer
-            R, TT = BF * Nc * T, Nc * T
-            rows = [_new(R, 16, dev=dev), _new(R, 16, dev=dev)]
-            _run("k_gbf_psd", 0.0, lib.se_gbf_psd_fwd, _p(xl), _p(spec), _p(self.ln_S.weight), _p(self.ln_S.bias), _p(self.ln_N.weight),
-                 _p(self.ln_N.bias), _p(rows[0]), _p(rows[1]), S, B, M, T, F0, st())
-            last = []
-            for q, m in enumerate(models):
-                g = m.sequence_model
-                x_l = rows[q]
-                for l in range(NL):
-                    gi = K._gemm(x_l, w_ih0[q] if l == 0 else getattr(g, f"weight_ih_l{l}"), getattr(g, f"bias_ih_l{l}"))
-                    out = _new(R, H, dev=dev)
-                    hT = _new(BF, H, dev=dev)
-                    sc = K._scratch(dev, BF, H, tag=("gbf", q, l))
-                    _run("k_gru_pseq_fwd", 2.0 * BF * 3 * H * H * TT, lib.se_train_gru_pseq_fwd, _p(gi), _p(state["h"][q][l]),
-                         _p(getattr(g, f"weight_hh_l{l}")), _p(getattr(g, f"bias_hh_l{l}")), _p(out), None, _p(hT), _p(sc), BF, TT, H, TT, 0, TT, st())
-                    tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
-                    del gi
-                    state["h"][q][l] = hT
-                    x_l = out
-                last.append(x_l)
-            del rows
-            phi = _new(S, F0, T, 9, dev=dev)
-            sS, sN = self.gru_S, self.gru_N
-            _run("k_gbf_seq", 0.0, lib.se_gbf_seq_fwd, _p(last[0]), _p(last[1]), _p(sS.fc_output_layer.weight), _p(sS.fc_output_layer.bias),
-                 _p(sS.norm.weight), _p(sS.norm.bias), _p(sN.fc_output_layer.weight), _p(sN.fc_output_layer.bias), _p(sN.norm.weight),
-                 _p(sN.norm.bias), _p(phi), None, None, S, B, F0, T, H, st())
-            del last
-            Y = _new(S, T, F0, 2, dev=dev)
-            lin = self.linear
-            _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
-                 _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
-            _run("k_istft", 0.0, lib.se_sig_istft, sig, _p(Y), S, _p(yseg, n0 * B * Ks), st())
-            state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
-        Lout = Lp - skip
-        pred = _new(B, Lout, dev=dev)
-        _run("k_tola", 0.0, lib.se_train_ola_fwd, sig, _p(yseg), _p(pred), B, Lout, skip, st())
+            self._kernel_pass(mixture, g, state, n0, min(step, N - n0), yseg, tmo)
+        Lout = g["Lp"] - g["skip"]
+        pred = _new(B, Lout, dev=mixture.device)
+        _run("k_tola", 0.0, K._lib().se_train_ola_fwd, g["sig"], _p(yseg), _p(pred), B, Lout, g["skip"], K._st())
         self._kstate = state
-        if tmo and int(torch.cat(tmo).abs().sum()) != 0:
-            self._kstate = None
-            raise RuntimeError(f"persistent GRU kernel timed out waiting for its peer workgroups ({BF} streams, hidden {H}): output invalid")
+        self._check_timeouts(tmo, g)
         return pred
+
+
+class GBFFunction(torch.autograd.Function):
+    """pred = GeneralBeamformer.realtime_process(mixture, flag) on the kernels, forward AND backward, as one autograd node
+    (reference training step train.py:195-204).  forward(ctx, model, mixture, flag, *params), params in named_parameters() order.
+
+    Forward: the inference kernel path over all N segments of the call in one pass, keeping the GRU gates, layer outputs and U-Net
+    activations.  Backward: OLA / iSTFT adjoint, se_gbf_bf_bwd, se_gbf_seq_bwd, the GRU layers, se_gbf_psd_bwd, then the decoder and
+    encoder on the training kernels in train_net.CRNFunction's order.  The reference detaches h at every segment seam
+    (GeneralBeamformer.py:143), so each GRU layer's BPTT is ONE persistent launch over B*F*N independent streams of T steps.  No
+    float atomics: the gradients are bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, model, mixture, flag, *params):
+        K._need_gpu(mixture, model.ln_S.weight)
+        mixture = mixture.detach().contiguous().float()
+        g, state = model._kernel_setup(mixture, flag)
+        N, B = g["N"], g["B"]
+        yseg = _new(N, B, g["Ks"], dev=mixture.device)
+        tmo, sv = [], {}
+        model._kernel_pass(mixture, g, state, 0, N, yseg, tmo, sv)
+        Lout = g["Lp"] - g["skip"]
+        pred = _new(B, Lout, dev=mixture.device)
+        _run("k_tola", 0.0, K._lib().se_train_ola_fwd, g["sig"], _p(yseg), _p(pred), B, Lout, g["skip"], K._st())
+        model._kstate = state
+        g.update(S=N * B, Lout=Lout)
+        ctx.model, ctx.dims, ctx.sv, ctx.tmo = model, g, sv, tmo
+        return pred
+
+    @staticmethod
+    def backward(ctx, dpred):
+        lib = K._lib()
+        model, q, sv, tmo = ctx.model, ctx.dims, ctx.sv, list(ctx.tmo)
+        B, M, N, S, T, F0, Ks, H, NL, Lv, BF = (q[k] for k in ("B", "M", "N", "S", "T", "F0", "Ks", "H", "NL", "Lv", "BF"))
+        ch, Fq, sig = q["ch"], q["Fq"], q["sig"]
+        dev = dpred.device
+        st = K._st
+        dpred = dpred.contiguous().float()
+        grads = {}
+        zero_bias = torch.zeros(256, device=dev)
+
+        gseg = _new(S, Ks, dev=dev)
+        _run("k_tola", 0.0, lib.se_train_ola_bwd, sig, _p(dpred), _p(gseg), B, N, q["Lout"], q["skip"], st())
+        dY = _new(S, T, F0, 2, dev=dev)
+        _run("k_stft", 0.0, lib.se_sig_stft, sig, _p(gseg), S, 1, Ks, 0, 0, 1, _p(dY), st())
+        del gseg
+        # beamformer + linear head
+        FT = F0 * T
+        R1 = S * FT
+        lin = model.linear
+        dphi = _new(S, F0, T, 9, dev=dev)
+        dpre, act, dw = _new(R1, H, dev=dev), _new(R1, H, dev=dev), _new(R1, 8, dev=dev)
+        pg, pb = _new(S * T, F0, dev=dev), _new(S * T, F0, dev=dev)
+        _run("k_gbf_bf_bwd", 0.0, lib.se_gbf_bf_bwd, _p(dY), _p(sv["phi"]), _p(sv["spec"]), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight),
+             _p(lin[2].bias), _p(lin[3].weight), _p(dphi), _p(dpre), _p(act), _p(dw), _p(pg), _p(pb), S, M, T, F0, H, q["n_fft"], st())
+        grads["linear.0.weight"] = gemm_tn(dpre, sv["phi"].view(R1, 9))
+        grads["linear.0.bias"] = colsum_tall(dpre)
+        grads["linear.3.weight"] = gemm_tn(dw, act)[:6]
+        grads["linear.3.bias"] = colsum_tall(dw)[:6]
+        grads["linear.2.weight"], grads["linear.2.bias"] = colsum_tall(pg), colsum_tall(pb)
+        del dY, dpre, act, dw, pg, pb
+        # sequence heads: fc + ReLU + gLN of both models, and their product
+        R = BF * N * T
+        outs, gates, h0s, rows = sv["outs"], sv["gates"], sv["h0s"], sv["rows"]
+        models = (("gru_S", model.gru_S), ("gru_N", model.gru_N))
+        dh = [_new(R, H, dev=dev), _new(R, H, dev=dev)]
+        dv = [_new(R, 16, dev=dev), _new(R, 16, dev=dev)]
+        part = _new(S * F0, 54, dev=dev)
+        sS, sN = model.gru_S, model.gru_N
+        _run("k_gbf_seq_bwd", 0.0, lib.se_gbf_seq_bwd, _p(dphi), _p(outs[0][NL - 1]), _p(outs[1][NL - 1]), _p(sS.fc_output_layer.weight),
+             _p(sS.fc_output_layer.bias), _p(sS.norm.weight), _p(sS.norm.bias), _p(sN.fc_output_layer.weight), _p(sN.fc_output_layer.bias),
+             _p(sN.norm.weight), _p(sN.norm.bias), _p(dh[0]), _p(dh[1]), _p(dv[0]), _p(dv[1]), _p(part), S, B, F0, T, H, st())
+        del dphi
+        ps = colsum_tall(part)
+        for qi, (name, sm) in enumerate(models):
+            o = qi * 27
+            grads[name + ".norm.weight"], grads[name + ".norm.bias"] = ps[o:o + 9], ps[o + 9:o + 18]
+            grads[name + ".fc_output_layer.bias"] = ps[o + 18:o + 27]
+            grads[name + ".fc_output_layer.weight"] = gemm_tn(dv[qi], outs[qi][NL - 1])[:9]
+        del dv
+        # the GRU layers in reverse: the state is detached at every seam, so B*F*N independent streams of T steps per launch
+        drows = []
+        for qi, (name, sm) in enumerate(models):
+            gm = sm.sequence_model
+            dlayer = dh[qi]
+            for l in range(NL - 1, -1, -1):
+                out, gt = outs[qi][l], gates[qi][l]
+                hp = _new(R, H, dev=dev)
+                _run("k_gru_hprev", 0.0, lib.se_train_gru_hprev, _p(out), _p(h0s[qi][l]), _p(hp), BF, N * T, H, N * T, 0, N * T, st())
+                h0seg = hp.view(BF * N, T, H)[:, 0].contiguous()
+                dgi, dgh = _new(R, 3 * H, dev=dev), _new(R, 3 * H, dev=dev)
+                sc = K._scratch(dev, BF * N, H, tag=("gbf_bwd", qi, l))
+                _run("k_gru_pseq_bwd", 2.0 * BF * N * 3 * H * H * T, lib.se_train_gru_pseq_bwd, _p(dlayer), None, _p(gt), _p(out), _p(h0seg),
+                     _p(transpose(getattr(gm, f"weight_hh_l{l}"))), _p(dgi), _p(dgh), _p(sc), BF * N, T, H, T, 0, T, 0, st())
+                tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
+                pre = f"{name}.sequence_model."
+                x_l = rows[qi] if l == 0 else outs[qi][l - 1]
+                gw = gemm_tn(dgi, x_l)
+                grads[pre + f"weight_ih_l{l}"] = gw[:, :9].contiguous() if l == 0 else gw
+                grads[pre + f"weight_hh_l{l}"] = gemm_tn(dgh, hp)
+                grads[pre + f"bias_ih_l{l}"] = colsum_tall(dgi)
+                grads[pre + f"bias_hh_l{l}"] = colsum_tall(dgh)
+                w_ih = model._padded_w_ih(gm) if l == 0 else getattr(gm, f"weight_ih_l{l}")
+                dlayer = K._gemm(dgi, transpose(w_ih))   # l = 0: [R][16], the gradient of the GRU input rows
+                del dgi, dgh, hp
+            drows.append(dlayer)
+        del dh
+        # PSD + ln_S / ln_N
+        dxl = torch.empty_like(sv["xl"])
+        part = _new(S, 4 * FT, dev=dev)
+        _run("k_gbf_psd_bwd", 0.0, lib.se_gbf_psd_bwd, _p(sv["xl"]), _p(sv["spec"]), _p(model.ln_S.weight), _p(model.ln_S.bias),
+             _p(model.ln_N.weight), _p(model.ln_N.bias), _p(drows[0]), _p(drows[1]), _p(dxl), _p(part), S, B, M, T, F0, st())
+        del drows
+        pp = colsum_tall(part)
+        grads["ln_S.weight"], grads["ln_S.bias"] = pp[:FT], pp[FT:2 * FT]
+        grads["ln_N.weight"], grads["ln_N.bias"] = pp[2 * FT:3 * FT], pp[3 * FT:]
+        # decoder, last block first (train_net.CRNFunction.backward, ReLU + gLN variant)
+        dres = {}
+        dout = dxl
+        for j in range(Lv - 1, -1, -1):
+            blk, rec = model.deconvlist[j], sv["dec"][j]
+            Ci, Co, Fi, Fy, d = rec["Ci"], rec["Co"], rec["Fi"], rec["Fy"], rec["d"]
+            pre = f"deconvlist.{j}."
+            if j < Lv - 1:
+                Cr, Fr, k = rec["Cr"], rec["Fr"], rec["k"]
+                duv = _new(S, 2 * Co, T, Fr, dev=dev)
+                dz = _new(S, Co, T, Fr, dev=dev)
+                pw, pbn, pbias = _new(S, Co, dev=dev), _new(S, Co, dev=dev), _new(S, 2 * Co, dev=dev)
+                _run("k_tskip_bwd", 0.0, lib.se_train_skip_bwd, _p(dout), _p(rec["uv"]), _p(rec["z"]), _p(blk.residualnorm.weight),
+                     _p(blk.residualnorm.bias), _p(rec["st_uv"]), _p(duv), _p(dz), _p(pw), _p(pbn), _p(pbias), S, Co, T, Fr, 1, 0, st())
+                dnw, dnb, dbuv = colsum3(S, (pw, Co), (pbn, Co), (pbias, 2 * Co))
+                grads[pre + "residualnorm.weight"], grads[pre + "residualnorm.bias"] = dnw, dnb
+                grads[pre + "residual.bias"], grads[pre + "residualmask.bias"] = dbuv[:Co], dbuv[Co:]
+                res_off = B * Cr * T * Fr
+                dwuv = wgrad(duv, _p(sv["xin"][k], res_off), None, S, 2 * Co, Cr, T, Fr, Fr, 0, 1).view(2 * Co, Cr)
+                grads[pre + "residual.weight"], grads[pre + "residualmask.weight"] = dwuv[:Co], dwuv[Co:]
+                wuv = torch.cat([blk.residual.weight.detach().view(Co, Cr), blk.residualmask.weight.detach().view(Co, Cr)])
+                dr = _new(S, Cr, T, Fr, dev=dev)
+                conv_w(3, _p(duv), None, wuv, 1, Cr, zero_bias, dr, S, 2 * Co, Cr, T, Fr, Fr, 0)
+                dres[k] = dr
+                dy_ptr, ds = _p(dz), (Co * T * Fr, T * Fr, Fr)
+            else:
+                dy_ptr, ds = _p(dout), (Co * T * Fy, T * Fy, Fy)
+            dyd, dw_, db_, dpre_ = gln_bwd(dy_ptr, ds, rec["yd"], (Co * T * Fy, T * Fy, Fy), blk.norm.weight, rec["st"], S, Co, T, Fy, 0, 1, 0)
+            grads[pre + "norm.weight"], grads[pre + "norm.bias"], grads[pre + "conv.bias"] = dw_, db_, dpre_
+            grads[pre + "conv.weight"] = wgrad(rec["x_in"], dyd, None, S, Ci, Co, T, Fi, Fy, d, 15)
+            din = _new(S, Ci, T, Fi, dev=dev)
+            conv_w(0, _p(dyd), None, blk.conv.weight, Co * 15, 15, zero_bias, din, S, Co, Ci, T, Fy, Fi, d)
+            dout = din
+        # encoder, last block first; the time history (slab 0 of xin) is a constant but enters the weight gradient
+        Ce = ch[Lv]
+        dy_ptr, ds = _p(dout), (Ce * T * Fq[Lv], T * Fq[Lv], Fq[Lv])
+        for i in range(Lv - 1, -1, -1):
+            blk = model.convlist[i]
+            Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
+            pre = f"convlist.{i}."
+            dy, dw_, db_, dpre_ = gln_bwd(dy_ptr, ds, sv["ys"][i], (Co * T * Fo, T * Fo, Fo), blk.norm.weight, sv["stats_e"][i], S, Co, T, Fo, 0, 1, 0)
+            grads[pre + "norm.weight"], grads[pre + "norm.bias"], grads[pre + "conv.bias"] = dw_, db_, dpre_
+            slab = B * Ci * T * Fi
+            grads[pre + "conv.weight"] = wgrad(dy, _p(sv["xin"][i], slab), _p(sv["xin"][i]), S, Co, Ci, T, Fo, Fi, d, 15)
+            if i == 0:
+                break  # the features carry no gradient
+            dxi = _new(S, Ci, T, Fi, dev=dev)
+            for kind in (1, 2):
+                conv_w(kind, _p(dy), None, blk.conv.weight, 15, Ci * 15, zero_bias, dxi, S, Co, Ci, T, Fo, Fi, d)
+            if i in dres:
+                _run("k_tadd", 0.0, lib.se_train_add, _p(dxi), _p(dres[i]), dxi.numel(), st())
+            dy_ptr, ds = _p(dxi), (Ci * T * Fi, T * Fi, Fi)
+        ctx.sv = ctx.tmo = None
+        model._check_timeouts(tmo, q)
+        out = []
+        for name, p in model.named_parameters():
+            gr = grads.get(name.replace(".net.0.", ".conv."))
+            out.append(None if gr is None else gr.reshape(p.shape))
+        return (None, None, None, *out)
