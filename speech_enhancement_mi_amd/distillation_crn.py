@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .crn import TemporalCRN as _Base
+from .train_stages import _as_flag, segment_geometry
 
 
 class TemporalCRN(_Base):
@@ -59,10 +60,10 @@ class TemporalCRN(_Base):
             eng.reset(B)
         elif eng.batch != B:
             raise RuntimeError(f"flag=True with batch {B} but the carried state holds {eng.batch} streams")
-        Lp = x.shape[-1]
-        gap = K - (P + Lp % K) % K
+        c = self._cfg_args
+        g = segment_geometry(L, flag, K, int(round(c["sample_rate"] / 1000.0 * c["hop_length"])), c["n_fft"])
+        Lp, gap, N = g["Lp"], g["gap"], g["N"]
         xp = torch.nn.functional.pad(x, (P, gap + P))
-        N = 2 * (Lp + gap + P) // K
         segs, feats = [], None
         for n in range(N):
             segs.append(eng.step(xp[:, :, n * P:n * P + K].contiguous()))
@@ -83,12 +84,6 @@ class TemporalCRN(_Base):
 
 
 EPS = 1e-8  # distillation_crn.py:11
-
-
-def _as_flag(flag):
-    if isinstance(flag, torch.Tensor):
-        return bool(flag.reshape(-1)[0].item())
-    return bool(flag)
 
 
 def _flat_pair(t, s):

@@ -23,15 +23,10 @@ import torch.nn.functional as Fn
 
 from . import train_ops as K
 from .fullsubnet import FullSubNet
+from .train_stages import _as_flag, _sig, segment_geometry, stft, synthesis, synthesis_adjoint
 from .training import _TrainableMixin
 
 EPS = 1e-8  # fullsubnet.py:12
-
-
-def _as_flag(flag):
-    if isinstance(flag, torch.Tensor):
-        return bool(flag.reshape(-1)[0].item())
-    return bool(flag)
 
 
 class FSNFunction(torch.autograd.Function):
@@ -40,45 +35,33 @@ class FSNFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, mixture, flag, *params):
-        from . import train_net as N_
-        lib = K._lib()
         K._need_gpu(mixture, params[0])
         eng = model._engine_for(mixture)  # (re)loads the weights when an optimizer step changed them
         g = model._geometry(mixture)
-        B, M, L, N, T, F, P = g["B"], g["M"], g["L"], g["N"], g["T"], g["F"], g["P"]
+        B, M, L, N, T, F = g["B"], g["M"], g["L"], g["N"], g["T"], g["F"]
         dev = mixture.device
         mixture = mixture.contiguous().float()
         S = N * B
-        sig = N_._sig(dev, g["n_fft"], g["win"], g["hop"], g["Ks"])
-        spec = torch.empty(N, B * M, T, F, 2, device=dev)
-        K._chk(lib.se_sig_stft(sig, mixture.data_ptr(), B, M, L, g["off0"], P, N, spec.data_ptr(), K._st()))
+        spec = stft(g["sig"], mixture, B, M, L, g["off0"], g["P"], N, T, F)
         ws = torch.empty(eng.train_ws_bytes(B, N), dtype=torch.uint8, device=dev)
         crm = eng.train_fwd(spec, B, N, flag, ws)                                # [N, B, 2, F, T]
         xm = crm.permute(0, 1, 2, 4, 3).reshape(S, 2, T, F).contiguous()
         Y = torch.empty(S, T, F, 2, device=dev)
-        K._chk(lib.se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
-        yseg = torch.empty(S, g["Ks"], device=dev)
-        K._chk(lib.se_sig_istft(sig, Y.data_ptr(), S, yseg.data_ptr(), K._st()))
-        pred = torch.empty(B, L, device=dev)
-        K._chk(lib.se_train_ola_fwd(sig, yseg.data_ptr(), pred.data_ptr(), B, L, g["skip"], K._st()))
+        K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
+        pred = synthesis(g["sig"], Y, B, g["Ks"], L, g["skip"])
         model._hip_aux = (crm, spec)
-        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.sig, ctx.g = eng, ws, spec, xm, sig, g
+        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g = eng, ws, spec, xm, g
         ctx.shapes = [p.shape for p in params]
         return pred
 
     @staticmethod
     def backward(ctx, dpred):
-        lib = K._lib()
         g = ctx.g
         B, M, L, N, T, F = g["B"], g["M"], g["L"], g["N"], g["T"], g["F"]
-        S, Ks, dev = N * B, g["Ks"], dpred.device
-        dpred = dpred.contiguous().float()
-        gseg = torch.empty(S, Ks, device=dev)
-        K._chk(lib.se_train_ola_bwd(ctx.sig, dpred.data_ptr(), gseg.data_ptr(), B, N, L, g["skip"], K._st()))
-        dY = torch.empty(S, T, F, 2, device=dev)
-        K._chk(lib.se_sig_stft(ctx.sig, gseg.data_ptr(), S, 1, Ks, 0, 0, 1, dY.data_ptr(), K._st()))
+        S, dev = N * B, dpred.device
+        dY = synthesis_adjoint(g["sig"], dpred.contiguous().float(), B, N, L, g["skip"], g["Ks"], T, F)
         dx = torch.empty(S, 2, T, F, device=dev)
-        K._chk(lib.se_train_mask_bwd(dY.data_ptr(), ctx.xm.data_ptr(), ctx.spec.data_ptr(), dx.data_ptr(), S, M, T, F, g["n_fft"], K._st()))
+        K._chk(K._lib().se_train_mask_bwd(dY.data_ptr(), ctx.xm.data_ptr(), ctx.spec.data_ptr(), dx.data_ptr(), S, M, T, F, g["n_fft"], K._st()))
         dcrm = dx.view(N, B, 2, T, F).permute(0, 1, 2, 4, 3).contiguous()
         grads = [torch.empty(s, device=dev) for s in ctx.shapes]
         ctx.eng.train_bwd(dcrm, B, N, ctx.ws, grads)
@@ -107,16 +90,11 @@ class TrainableFullSubNet(FullSubNet):
         return self
 
     def _geometry(self, mixture, flag=None):
-        a = self._args
         B, M, L = mixture.shape
-        Ks = self.segment_length
-        P = Ks // 2
-        hop, win = self._hop, self._win
-        fl = self._cur_flag if flag is None else flag
-        Lp = L if fl else L + P
-        gap = Ks - (P + Lp % Ks) % Ks
-        return dict(B=B, M=M, L=L, Ks=Ks, P=P, hop=hop, win=win, n_fft=a["n_fft"], T=1 + Ks // hop, F=self.num_freqs,
-                    N=2 * (Lp + gap + P) // Ks, gap=gap, off0=-P if fl else -2 * P, skip=0 if fl else P)
+        n_fft, Ks = self._args["n_fft"], self.segment_length
+        g = segment_geometry(L, self._cur_flag if flag is None else flag, Ks, self._hop, n_fft)
+        g.update(B=B, M=M, n_fft=n_fft, F=self.num_freqs, sig=_sig(mixture.device, n_fft, self._win, self._hop, Ks))
+        return g
 
     def realtime_process(self, mixture, source=None, flag=False, train=False):
         if train:
@@ -146,13 +124,9 @@ class TrainableFullSubNet(FullSubNet):
         return pred, crm, x0
 
     def _mic0_spec(self, source, flag):
-        from . import train_net as N_
         src = source[:, :1].contiguous().float()
         g = self._geometry(src, flag)
-        N, B, T, F = g["N"], g["B"], g["T"], g["F"]
-        sig = N_._sig(src.device, g["n_fft"], g["win"], g["hop"], g["Ks"])
-        sspec = torch.empty(N, B, T, F, 2, device=src.device)
-        K._chk(K._lib().se_sig_stft(sig, src.data_ptr(), B, 1, g["L"], g["off0"], g["P"], N, sspec.data_ptr(), K._st()))
+        sspec = stft(g["sig"], src, g["B"], 1, g["L"], g["off0"], g["P"], g["N"], g["T"], g["F"])   # [N, B, T, F, 2]
         return sspec.permute(0, 1, 4, 3, 2).contiguous()
 
     # ---- torch restatement (the checker) ----

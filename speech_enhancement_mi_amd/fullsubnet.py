@@ -94,8 +94,8 @@ class FullSubNet(nn.Module):
 
     def _realtime_single_pass(self, mixture, source, flag):
         """train=True (fullsubnet.py:921-927): xf = all N windows' frames side by side [B, 2M, F, N*T] -> ONE forward."""
-        import ctypes as C
-        from . import train_net as N_, train_ops as K
+        from . import train_ops as K
+        from .train_stages import _sig, segment_geometry, stft, synthesis
         if flag:
             raise NotImplementedError("train=True continues a previous chunk only in the reference's autograd loop; the engine path takes flag=False")
         if source is None:
@@ -105,20 +105,14 @@ class FullSubNet(nn.Module):
         dev = mixture.device
         mixture, source = mixture.contiguous().float(), source.contiguous().float()
         B, M, L = mixture.shape
-        Ks, P = self.segment_length, self.segment_length // 2
         hop = int(round(a["sample_rate"] / 1000.0 * a["hop_length"]))
         win = int(round(a["sample_rate"] / 1000.0 * a["win_length"]))
-        T, F = 1 + Ks // hop, self.num_freqs
-        Lp = L + P
-        gap = Ks - (P + Lp % Ks) % Ks
-        N = 2 * (Lp + gap + P) // Ks
+        g = segment_geometry(L, False, self.segment_length, hop, a["n_fft"])
+        Ks, P, N, T, F = g["Ks"], g["P"], g["N"], g["T"], self.num_freqs
         S = N * B
-        lib = K._lib()
-        sig = N_._sig(dev, a["n_fft"], win, hop, Ks)
-        spec = torch.empty(N, B * M, T, F, 2, device=dev)
-        K._chk(lib.se_sig_stft(sig, mixture.data_ptr(), B, M, L, -2 * P, P, N, spec.data_ptr(), K._st()))
-        sspec = torch.empty(N, B * source.shape[1], T, F, 2, device=dev)
-        K._chk(lib.se_sig_stft(sig, source.data_ptr(), B, source.shape[1], L, -2 * P, P, N, sspec.data_ptr(), K._st()))
+        sig = _sig(dev, a["n_fft"], win, hop, Ks)
+        spec = stft(sig, mixture, B, M, L, g["off0"], P, N, T, F)
+        sspec = stft(sig, source, B, source.shape[1], L, g["off0"], P, N, T, F)
         xf = spec.view(N, B, M, T, F, 2).permute(1, 5, 2, 4, 0, 3).reshape(B, 2 * M, F, N * T).contiguous()
         long = self._long.get(N * T)
         if long is None:
@@ -133,11 +127,8 @@ class FullSubNet(nn.Module):
         pred_crm = crm_long.view(B, 2, F, N, T).permute(3, 0, 1, 2, 4).contiguous()  # [N, B, 2, F, T]
         xm = pred_crm.permute(0, 1, 2, 4, 3).reshape(S, 2, T, F).contiguous()
         Y = torch.empty(S, T, F, 2, device=dev)
-        K._chk(lib.se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
-        yseg = torch.empty(S, Ks, device=dev)
-        K._chk(lib.se_sig_istft(sig, Y.data_ptr(), S, yseg.data_ptr(), K._st()))
-        pred = torch.empty(B, L, device=dev)
-        K._chk(lib.se_train_ola_fwd(sig, yseg.data_ptr(), pred.data_ptr(), B, L, P, K._st()))
+        K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
+        pred = synthesis(sig, Y, B, Ks, L, g["skip"])
         x0 = spec.view(N, B, M, T, F, 2)[:, :, 0].permute(0, 1, 4, 3, 2).contiguous()    # [N, B, 2, F, T]
         s0 = sspec.view(N, B, -1, T, F, 2)[:, :, 0].permute(0, 1, 4, 3, 2).contiguous()
         return pred, pred_crm, s0, x0

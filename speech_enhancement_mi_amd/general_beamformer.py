@@ -13,8 +13,8 @@ Two interchangeable paths:
     torch ops, differentiable, so train.py can train the model through autograd.  The GRU cell is written out (no nn.GRU forward,
     no MIOpen RNN); the nn.GRU modules only own the parameters;
   * the kernel path (`realtime_process` of a GPU tensor with grad disabled): every segment of a call at once, segment-major as in
-    train_net.CRNFunction - U-Net on the se_train_* kernels, the two GRUs as persistent launches, the beamforming head on
-    csrc/se_gbf.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
+    train_net.CRNFunction - the U-Net and the signal chain are train_stages.py's (shared with CRNFunction), the two GRUs
+    persistent launches, the beamforming head on csrc/se_gbf.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
   * HIP training (opt-in, use_hip_training(True)): `realtime_process` of a GPU tensor with grad enabled is ONE autograd node,
     GBFFunction - the kernel path's forward keeping its activations, and a backward on the same kernels plus se_gbf_*_bwd.
 """
@@ -25,17 +25,12 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .train_net import _new, _p, _run, _sig, colsum3, colsum_tall, conv_w, gemm_tn, gln_bwd, gln_fwd, transpose, wgrad
+from .train_stages import (_as_flag, _cs, _new, _p, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd, encoder_block_fwd,
+                           gemm_tn, grads_in_parameter_order, gru_layer_bwd, input_features, istft, overlap_add, segment_geometry, stft,
+                           synthesis_adjoint)
 
 EPS = 1e-8
 _DEFAULT_MAX_SEGMENTS = 8
-
-
-def _as_flag(flag):
-    """realtime_process's flag: a bool, or the trainer's per-utterance flag tensor (data['flag'], shape [B]; one value per batch)."""
-    if isinstance(flag, torch.Tensor):
-        return bool(flag.reshape(-1)[0].item())
-    return bool(flag)
 
 
 class _Norm(nn.Module):  # GlobalLayerNorm parameter holder, GeneralBeamformer.py:22-34
@@ -284,10 +279,9 @@ class GeneralBeamformer(nn.Module):
         if not flag:
             mixture = Fn.pad(mixture, (P, 0))
             self._tstate = None
-        Lp = mixture.shape[-1]
-        gap = Ks - (P + Lp % Ks) % Ks
+        geo = segment_geometry(L, flag, Ks, self._hop, self._cfg["n_fft"])
+        gap, N = geo["gap"], geo["N"]
         xp = Fn.pad(mixture, (P, gap + P))
-        N = 2 * (Lp + gap + P) // Ks
         idx = (torch.arange(N, device=mixture.device) * P)[:, None] + torch.arange(Ks, device=mixture.device)[None, :]
         seg = xp[:, :, idx]  # [B, M, N, K]
         win = torch.hamming_window(self._win, device=mixture.device, dtype=mixture.dtype)
@@ -311,7 +305,8 @@ class GeneralBeamformer(nn.Module):
         c = self._cfg
         M, k, H, ch = c["num_inputs"], c["kernel_size"], c["hidden"], [2 * c["num_inputs"] - 1] + c["num_channels"]
         Lv = len(c["num_channels"])
-        T, F0 = 1 + self.segment_length // self._hop, c["n_fft"] // 2 + 1
+        geo = segment_geometry(0, False, self.segment_length, self._hop, c["n_fft"], ch)
+        T, F0, Fq = geo["T"], geo["F0"], geo["Fq"]
         if M != 3:
             return f"num_inputs = {M}: the beamforming head's linear layers are 9 -> hidden -> 6, so 3 microphones only"
         if k != 3:
@@ -327,9 +322,6 @@ class GeneralBeamformer(nn.Module):
             return f"hidden = {H}: no persistent GRU kernel (se_train_gru_pseq_supported)"
         if (k - 1) * 2 ** (Lv - 1) >= T:
             return f"encoder history (k - 1) * 2^(L - 1) = {(k - 1) * 2 ** (Lv - 1)} frames is not shorter than the {T}-frame segment"
-        Fq = [F0]
-        for _ in range(Lv):
-            Fq.append((Fq[-1] - 1) // 2 + 1)
         for j in range(Lv - 1):
             kk = Lv - 1 - j
             if Fq[kk] < 2 * Fq[kk + 1] - 1:
@@ -362,18 +354,10 @@ class GeneralBeamformer(nn.Module):
         dev = mixture.device
         B, M, L = mixture.shape
         c = self._cfg
-        Ks, n_fft, H, NL = self.segment_length, c["n_fft"], c["hidden"], c["num_layers"]
-        P = Ks // 2
-        T, F0 = 1 + Ks // self._hop, n_fft // 2 + 1
-        Lp = L if flag else L + P
-        gap = Ks - (P + Lp % Ks) % Ks
-        Lv = len(self.convlist)
-        ch = [2 * M - 1] + c["num_channels"]
-        Fq = [F0]
-        for _ in range(Lv):
-            Fq.append((Fq[-1] - 1) // 2 + 1)
-        g = dict(B=B, M=M, L=L, Ks=Ks, n_fft=n_fft, H=H, NL=NL, P=P, T=T, F0=F0, Lp=Lp, off0=-P if flag else -2 * P, skip=0 if flag else P,
-                 N=2 * (Lp + gap + P) // Ks, Lv=Lv, ch=ch, Fq=Fq, BF=B * F0, sig=_sig(dev, n_fft, self._win, self._hop, Ks))
+        H, NL, ch = c["hidden"], c["num_layers"], [2 * M - 1] + c["num_channels"]
+        g = segment_geometry(L, flag, self.segment_length, self._hop, c["n_fft"], ch)
+        T, F0, Fq, Lv = g["T"], g["F0"], g["Fq"], len(self.convlist)
+        g.update(B=B, M=M, n_fft=c["n_fft"], H=H, NL=NL, Lv=Lv, BF=B * F0, sig=_sig(dev, c["n_fft"], self._win, self._hop, self.segment_length))
         state = self._kstate if flag else None
         if state is not None and state["B"] != B:
             raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
@@ -391,56 +375,25 @@ class GeneralBeamformer(nn.Module):
         B, M, L, T, F0, H, NL, Lv, ch, Fq, BF, P = (g[k] for k in ("B", "M", "L", "T", "F0", "H", "NL", "Lv", "ch", "Fq", "BF", "P"))
         S = Nc * B
         keep = sv is not None
-        spec = _new(Nc, B * M, T, F0, 2, dev=dev)
-        _run("k_stft", 0.0, lib.se_sig_stft, g["sig"], _p(mixture), B, M, L, g["off0"] + n0 * P, P, Nc, _p(spec), st())
+        spec = stft(g["sig"], mixture, B, M, L, g["off0"] + n0 * P, P, Nc, T, F0)
         # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input of block i (its time history)
         xin = []
         for i in range(Lv):
             t_ = _new(Nc + 1, B, ch[i], T, Fq[i], dev=dev)
             t_[0].copy_(state["buf"][i])
             xin.append(t_)
-        _run("k_tfeat", 0.0, lib.se_train_feat, _p(spec), _p(xin[0], B * ch[0] * T * F0), S, M, T, F0, 0, st())
-        ys, stats_e, dec = [], [], []
+        input_features(spec, xin[0], S, B, M, ch[0], T, F0)
+        ys, stats_e = [], []
         for i, blk in enumerate(self.convlist):
-            Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
-            y = _new(S, Co, T, Fo, dev=dev)
-            conv_w(0, _p(xin[i], B * Ci * T * Fi), _p(xin[i]), blk.conv.weight, Ci * 15, 15, blk.conv.bias, y, S, Ci, Co, T, Fi, Fo, d, 0)
-            if i < Lv - 1:
-                out, off = xin[i + 1], B * Co * T * Fo
-            else:
-                out, off = _new(S, Co, T, Fo, dev=dev), 0
-            stt = gln_fwd(y, (Co * T * Fo, T * Fo, Fo), _p(out, off), (Co * T * Fo, T * Fo, Fo), blk.norm.weight, blk.norm.bias, S, Co, T, Fo, Fo, 0, 1, 0)
+            Co, Fo = ch[i + 1], Fq[i + 1]
+            if i == Lv - 1:
+                xin.append(_new(S, Co, T, Fo, dev=dev))   # the decoder's input: no history slab
+            y_st = encoder_block_fwd(blk, xin[i], _p(xin[i + 1], B * Co * T * Fo if i < Lv - 1 else 0), _cs(Co, T, Fo), S, B, ch[i], Co, T, Fq[i], Fo, 2 ** i)
             if keep:
-                ys.append(y)
-                stats_e.append(stt)
-            x_in = out
-        Ci, Fi = ch[Lv], Fq[Lv]
-        for j, blk in enumerate(self.deconvlist):
-            Co, d, Fy = blk.conv.weight.shape[1], 2 ** j, 2 * Fi - 1
-            yd = _new(S, Co, T, Fy, dev=dev)
-            for kind in (1, 2):
-                conv_w(kind, _p(x_in), None, blk.conv.weight, 15, Co * 15, blk.conv.bias, yd, S, Ci, Co, T, Fi, Fy, d)
-            rec = dict(x_in=x_in, yd=yd, Ci=Ci, Co=Co, Fi=Fi, Fy=Fy, d=d)
-            if j < Lv - 1:
-                kk = Lv - 1 - j
-                Cr, Fr = ch[kk], Fq[kk]
-                z = _new(S, Co, T, Fr, dev=dev)
-                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(z), (Co * T * Fr, T * Fr, Fr), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fr, 0, 1, 0)
-                uv = _new(S, 2 * Co, T, Fr, dev=dev)   # residual | residualmask, one 1x1 launch per half (2 Co may exceed 128 rows)
-                res = _p(xin[kk], B * Cr * T * Fr)
-                conv_w(3, res, None, blk.residual.weight, Cr, 1, blk.residual.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, 0)
-                conv_w(3, res, None, blk.residualmask.weight, Cr, 1, blk.residualmask.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, Co)
-                out = _new(S, Co, T, Fr, dev=dev)
-                stt = _new(S, 2, dev=dev)
-                _run("k_tskip_fwd", 0.0, lib.se_train_skip_fwd, _p(uv), _p(z), _p(blk.residualnorm.weight), _p(blk.residualnorm.bias), _p(out),
-                     _p(stt), S, Co, T, Fr, 1, 0, st())
-                rec.update(z=z, uv=uv, st_uv=stt, k=kk, Cr=Cr, Fr=Fr)
-                x_in, Ci, Fi = out, Co, Fr
-            else:
-                xl = _new(S, Co, T, Fy, dev=dev)
-                rec["st"] = gln_fwd(yd, (Co * T * Fy, T * Fy, Fy), _p(xl), (Co * T * Fy, T * Fy, Fy), blk.norm.weight, blk.norm.bias, S, Co, T, Fy, Fy, 0, 1, 0)
-            if keep:
-                dec.append(rec)
+                ys.append(y_st[0])
+                stats_e.append(y_st[1])
+        del y_st
+        xl, dec = decoder_fwd(self.deconvlist, xin, ch, Fq, S, B, T, 1, 0, keep=keep, stacked=False)
         # head: PSD + ln -> GRU rows [B*F][Nc*T][16] (stream-major), two GRU models, sequence head, beamformer
         R, TT = BF * Nc * T, Nc * T
         rows = [_new(R, 16, dev=dev), _new(R, 16, dev=dev)]
@@ -456,9 +409,8 @@ class GeneralBeamformer(nn.Module):
                 out = _new(R, H, dev=dev)
                 gt = _new(R, 4 * H, dev=dev) if keep else None
                 hT = _new(BF, H, dev=dev)
-                sc = K._scratch(dev, BF, H, tag=("gbf", q, l))
-                _run("k_gru_pseq_fwd", 2.0 * BF * 3 * H * H * TT, lib.se_train_gru_pseq_fwd, _p(gi), _p(state["h"][q][l]),
-                     _p(getattr(gm, f"weight_hh_l{l}")), _p(getattr(gm, f"bias_hh_l{l}")), _p(out), _p(gt), _p(hT), _p(sc), BF, TT, H, TT, 0, TT, st())
+                sc = K._gru_seq_fwd(gi, state["h"][q][l], getattr(gm, f"weight_hh_l{l}"), getattr(gm, f"bias_hh_l{l}"), out, gt, hT, BF, TT, H, TT, 0, TT,
+                                    tag=("gbf", q, l))
                 tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
                 del gi
                 if keep:
@@ -480,7 +432,7 @@ class GeneralBeamformer(nn.Module):
         lin = self.linear
         _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
              _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
-        _run("k_istft", 0.0, lib.se_sig_istft, g["sig"], _p(Y), S, _p(yseg, n0 * B * g["Ks"]), st())
+        istft(g["sig"], Y, yseg.view(-1, g["Ks"]), n0 * B)
         state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
         if keep:
             sv.update(spec=spec, xin=xin, ys=ys, stats_e=stats_e, dec=dec, xl=xl, rows=rows, outs=outs, gates=gates, h0s=h0s, phi=phi)
@@ -491,6 +443,19 @@ class GeneralBeamformer(nn.Module):
             raise RuntimeError(f"persistent GRU kernel timed out waiting for its peer workgroups ({g['BF']} streams, hidden {g['H']}): "
                                "output invalid")
 
+    def _kernel_run(self, mixture, flag, sv=None):
+        """Passes of max_segments segments; sv given (GBFFunction): ONE pass that keeps its activations.  -> (pred, geometry, time-outs)"""
+        g, state = self._kernel_setup(mixture, flag)
+        N, B = g["N"], g["B"]
+        yseg = _new(N, B, g["Ks"], dev=mixture.device)
+        tmo = []
+        step = N if sv is not None else max(1, int(self.max_segments))
+        for n0 in range(0, N, step):
+            self._kernel_pass(mixture, g, state, n0, min(step, N - n0), yseg, tmo, sv)
+        pred = overlap_add(g["sig"], yseg, B, g["L"], g["skip"])
+        self._kstate = state
+        return pred, g, tmo
+
     @torch.no_grad()
     def _kernel_process(self, mixture, flag):
         err = self.kernel_geometry_error()
@@ -499,18 +464,7 @@ class GeneralBeamformer(nn.Module):
         if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist)):
             raise ValueError("GeneralBeamformer kernel path: inference only (dropout is active in training mode; use the restatement)")
         K._need_gpu(mixture, self.ln_S.weight)
-        mixture = mixture.contiguous().float()
-        g, state = self._kernel_setup(mixture, flag)
-        N, B = g["N"], g["B"]
-        yseg = _new(N, B, g["Ks"], dev=mixture.device)
-        tmo = []
-        step = max(1, int(self.max_segments))
-        for n0 in range(0, N, step):
-            self._kernel_pass(mixture, g, state, n0, min(step, N - n0), yseg, tmo)
-        Lout = g["Lp"] - g["skip"]
-        pred = _new(B, Lout, dev=mixture.device)
-        _run("k_tola", 0.0, K._lib().se_train_ola_fwd, g["sig"], _p(yseg), _p(pred), B, Lout, g["skip"], K._st())
-        self._kstate = state
+        pred, g, tmo = self._kernel_run(mixture.contiguous().float(), flag)
         self._check_timeouts(tmo, g)
         return pred
 
@@ -520,25 +474,17 @@ class GBFFunction(torch.autograd.Function):
     (reference training step train.py:195-204).  forward(ctx, model, mixture, flag, *params), params in named_parameters() order.
 
     Forward: the inference kernel path over all N segments of the call in one pass, keeping the GRU gates, layer outputs and U-Net
-    activations.  Backward: OLA / iSTFT adjoint, se_gbf_bf_bwd, se_gbf_seq_bwd, the GRU layers, se_gbf_psd_bwd, then the decoder and
-    encoder on the training kernels in train_net.CRNFunction's order.  The reference detaches h at every segment seam
+    activations.  Backward: OLA / iSTFT adjoint, se_gbf_bf_bwd, se_gbf_seq_bwd, the GRU layers (train_stages.gru_layer_bwd),
+    se_gbf_psd_bwd, then train_stages.decoder_bwd and encoder_block_bwd, the passes CRNFunction runs.  The reference detaches h at every segment seam
     (GeneralBeamformer.py:143), so each GRU layer's BPTT is ONE persistent launch over B*F*N independent streams of T steps.  No
     float atomics: the gradients are bit-reproducible."""
 
     @staticmethod
     def forward(ctx, model, mixture, flag, *params):
         K._need_gpu(mixture, model.ln_S.weight)
-        mixture = mixture.detach().contiguous().float()
-        g, state = model._kernel_setup(mixture, flag)
-        N, B = g["N"], g["B"]
-        yseg = _new(N, B, g["Ks"], dev=mixture.device)
-        tmo, sv = [], {}
-        model._kernel_pass(mixture, g, state, 0, N, yseg, tmo, sv)
-        Lout = g["Lp"] - g["skip"]
-        pred = _new(B, Lout, dev=mixture.device)
-        _run("k_tola", 0.0, K._lib().se_train_ola_fwd, g["sig"], _p(yseg), _p(pred), B, Lout, g["skip"], K._st())
-        model._kstate = state
-        g.update(S=N * B, Lout=Lout)
+        sv = {}
+        pred, g, tmo = model._kernel_run(mixture.detach().contiguous().float(), flag, sv)
+        g["S"] = g["N"] * g["B"]
         ctx.model, ctx.dims, ctx.sv, ctx.tmo = model, g, sv, tmo
         return pred
 
@@ -554,11 +500,7 @@ class GBFFunction(torch.autograd.Function):
         grads = {}
         zero_bias = torch.zeros(256, device=dev)
 
-        gseg = _new(S, Ks, dev=dev)
-        _run("k_tola", 0.0, lib.se_train_ola_bwd, sig, _p(dpred), _p(gseg), B, N, q["Lout"], q["skip"], st())
-        dY = _new(S, T, F0, 2, dev=dev)
-        _run("k_stft", 0.0, lib.se_sig_stft, sig, _p(gseg), S, 1, Ks, 0, 0, 1, _p(dY), st())
-        del gseg
+        dY = synthesis_adjoint(sig, dpred, B, N, q["L"], q["skip"], Ks, T, F0)
         # beamformer + linear head
         FT = F0 * T
         R1 = S * FT
@@ -599,25 +541,12 @@ class GBFFunction(torch.autograd.Function):
             gm = sm.sequence_model
             dlayer = dh[qi]
             for l in range(NL - 1, -1, -1):
-                out, gt = outs[qi][l], gates[qi][l]
-                hp = _new(R, H, dev=dev)
-                _run("k_gru_hprev", 0.0, lib.se_train_gru_hprev, _p(out), _p(h0s[qi][l]), _p(hp), BF, N * T, H, N * T, 0, N * T, st())
-                h0seg = hp.view(BF * N, T, H)[:, 0].contiguous()
-                dgi, dgh = _new(R, 3 * H, dev=dev), _new(R, 3 * H, dev=dev)
-                sc = K._scratch(dev, BF * N, H, tag=("gbf_bwd", qi, l))
-                _run("k_gru_pseq_bwd", 2.0 * BF * N * 3 * H * H * T, lib.se_train_gru_pseq_bwd, _p(dlayer), None, _p(gt), _p(out), _p(h0seg),
-                     _p(transpose(getattr(gm, f"weight_hh_l{l}"))), _p(dgi), _p(dgh), _p(sc), BF * N, T, H, T, 0, T, 0, st())
-                tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
-                pre = f"{name}.sequence_model."
-                x_l = rows[qi] if l == 0 else outs[qi][l - 1]
-                gw = gemm_tn(dgi, x_l)
-                grads[pre + f"weight_ih_l{l}"] = gw[:, :9].contiguous() if l == 0 else gw
-                grads[pre + f"weight_hh_l{l}"] = gemm_tn(dgh, hp)
-                grads[pre + f"bias_ih_l{l}"] = colsum_tall(dgi)
-                grads[pre + f"bias_hh_l{l}"] = colsum_tall(dgh)
                 w_ih = model._padded_w_ih(gm) if l == 0 else getattr(gm, f"weight_ih_l{l}")
-                dlayer = K._gemm(dgi, transpose(w_ih))   # l = 0: [R][16], the gradient of the GRU input rows
-                del dgi, dgh, hp
+                x_l = rows[qi] if l == 0 else outs[qi][l - 1]
+                dlayer = gru_layer_bwd(dlayer, outs[qi][l], gates[qi][l], h0s[qi][l], x_l, w_ih, getattr(gm, f"weight_hh_l{l}"),
+                                       f"{name}.sequence_model.", l, grads, BF, N, T, H, N * T, 0, N * T, tag=("gbf_bwd", qi, l), tmo=tmo)
+                if l == 0:   # [3H][16] against the padded rows: the parameter is [3H][9]; dlayer [R][16] = the gradient of the GRU input rows
+                    grads[f"{name}.sequence_model.weight_ih_l0"] = grads[f"{name}.sequence_model.weight_ih_l0"][:, :9].contiguous()
             drows.append(dlayer)
         del dh
         # PSD + ln_S / ln_N
@@ -629,62 +558,15 @@ class GBFFunction(torch.autograd.Function):
         pp = colsum_tall(part)
         grads["ln_S.weight"], grads["ln_S.bias"] = pp[:FT], pp[FT:2 * FT]
         grads["ln_N.weight"], grads["ln_N.bias"] = pp[2 * FT:3 * FT], pp[3 * FT:]
-        # decoder, last block first (train_net.CRNFunction.backward, ReLU + gLN variant)
-        dres = {}
-        dout = dxl
-        for j in range(Lv - 1, -1, -1):
-            blk, rec = model.deconvlist[j], sv["dec"][j]
-            Ci, Co, Fi, Fy, d = rec["Ci"], rec["Co"], rec["Fi"], rec["Fy"], rec["d"]
-            pre = f"deconvlist.{j}."
-            if j < Lv - 1:
-                Cr, Fr, k = rec["Cr"], rec["Fr"], rec["k"]
-                duv = _new(S, 2 * Co, T, Fr, dev=dev)
-                dz = _new(S, Co, T, Fr, dev=dev)
-                pw, pbn, pbias = _new(S, Co, dev=dev), _new(S, Co, dev=dev), _new(S, 2 * Co, dev=dev)
-                _run("k_tskip_bwd", 0.0, lib.se_train_skip_bwd, _p(dout), _p(rec["uv"]), _p(rec["z"]), _p(blk.residualnorm.weight),
-                     _p(blk.residualnorm.bias), _p(rec["st_uv"]), _p(duv), _p(dz), _p(pw), _p(pbn), _p(pbias), S, Co, T, Fr, 1, 0, st())
-                dnw, dnb, dbuv = colsum3(S, (pw, Co), (pbn, Co), (pbias, 2 * Co))
-                grads[pre + "residualnorm.weight"], grads[pre + "residualnorm.bias"] = dnw, dnb
-                grads[pre + "residual.bias"], grads[pre + "residualmask.bias"] = dbuv[:Co], dbuv[Co:]
-                res_off = B * Cr * T * Fr
-                dwuv = wgrad(duv, _p(sv["xin"][k], res_off), None, S, 2 * Co, Cr, T, Fr, Fr, 0, 1).view(2 * Co, Cr)
-                grads[pre + "residual.weight"], grads[pre + "residualmask.weight"] = dwuv[:Co], dwuv[Co:]
-                wuv = torch.cat([blk.residual.weight.detach().view(Co, Cr), blk.residualmask.weight.detach().view(Co, Cr)])
-                dr = _new(S, Cr, T, Fr, dev=dev)
-                conv_w(3, _p(duv), None, wuv, 1, Cr, zero_bias, dr, S, 2 * Co, Cr, T, Fr, Fr, 0)
-                dres[k] = dr
-                dy_ptr, ds = _p(dz), (Co * T * Fr, T * Fr, Fr)
-            else:
-                dy_ptr, ds = _p(dout), (Co * T * Fy, T * Fy, Fy)
-            dyd, dw_, db_, dpre_ = gln_bwd(dy_ptr, ds, rec["yd"], (Co * T * Fy, T * Fy, Fy), blk.norm.weight, rec["st"], S, Co, T, Fy, 0, 1, 0)
-            grads[pre + "norm.weight"], grads[pre + "norm.bias"], grads[pre + "conv.bias"] = dw_, db_, dpre_
-            grads[pre + "conv.weight"] = wgrad(rec["x_in"], dyd, None, S, Ci, Co, T, Fi, Fy, d, 15)
-            din = _new(S, Ci, T, Fi, dev=dev)
-            conv_w(0, _p(dyd), None, blk.conv.weight, Co * 15, 15, zero_bias, din, S, Co, Ci, T, Fy, Fi, d)
-            dout = din
-        # encoder, last block first; the time history (slab 0 of xin) is a constant but enters the weight gradient
-        Ce = ch[Lv]
-        dy_ptr, ds = _p(dout), (Ce * T * Fq[Lv], T * Fq[Lv], Fq[Lv])
+        dout, dres = decoder_bwd(model.deconvlist, sv["dec"], sv["xin"], dxl, grads, zero_bias, S, B, T, 1, 0, stacked=False)
+        del dxl
+        # encoder, last block first
+        dy_ptr, ds = _p(dout), _cs(ch[Lv], T, Fq[Lv])
         for i in range(Lv - 1, -1, -1):
-            blk = model.convlist[i]
-            Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
-            pre = f"convlist.{i}."
-            dy, dw_, db_, dpre_ = gln_bwd(dy_ptr, ds, sv["ys"][i], (Co * T * Fo, T * Fo, Fo), blk.norm.weight, sv["stats_e"][i], S, Co, T, Fo, 0, 1, 0)
-            grads[pre + "norm.weight"], grads[pre + "norm.bias"], grads[pre + "conv.bias"] = dw_, db_, dpre_
-            slab = B * Ci * T * Fi
-            grads[pre + "conv.weight"] = wgrad(dy, _p(sv["xin"][i], slab), _p(sv["xin"][i]), S, Co, Ci, T, Fo, Fi, d, 15)
-            if i == 0:
-                break  # the features carry no gradient
-            dxi = _new(S, Ci, T, Fi, dev=dev)
-            for kind in (1, 2):
-                conv_w(kind, _p(dy), None, blk.conv.weight, 15, Ci * 15, zero_bias, dxi, S, Co, Ci, T, Fo, Fi, d)
-            if i in dres:
-                _run("k_tadd", 0.0, lib.se_train_add, _p(dxi), _p(dres[i]), dxi.numel(), st())
-            dy_ptr, ds = _p(dxi), (Ci * T * Fi, T * Fi, Fi)
+            dout = encoder_block_bwd(model.convlist[i], f"convlist.{i}.", grads, dy_ptr, ds, sv["ys"][i], sv["stats_e"][i], sv["xin"][i], dres.get(i),
+                                     zero_bias, S, B, ch[i], ch[i + 1], T, Fq[i], Fq[i + 1], 2 ** i, need_dx=i > 0)  # the features carry no gradient
+            if i:
+                dy_ptr, ds = _p(dout), _cs(ch[i], T, Fq[i])
         ctx.sv = ctx.tmo = None
         model._check_timeouts(tmo, q)
-        out = []
-        for name, p in model.named_parameters():
-            gr = grads.get(name.replace(".net.0.", ".conv."))
-            out.append(None if gr is None else gr.reshape(p.shape))
-        return (None, None, None, *out)
+        return (None, None, None, *grads_in_parameter_order(model, grads))
