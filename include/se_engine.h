@@ -285,6 +285,19 @@ int se_sig_istft(se_sig *g, const float *spec, int rows, float *wav, void *strea
  * when realtime_process padded the input (flag=False), else 0.  bwd: gseg [nseg][B][K] = adjoint(dout) / envelope. */
 int se_train_ola_fwd(se_sig *g, const float *yseg, float *out, int B, int64_t L, int64_t skip, void *stream);
 int se_train_ola_bwd(se_sig *g, const float *dout, float *gseg, int B, int nseg, int64_t L, int64_t skip, void *stream);
+/* The same three stages for a batch of chunk chains (data_c.py:60-84: every utterance has its own length and its own flag), additions
+ * at ABI 4.  off0 / len / skip: DEVICE int64 [B].  se_sig_stft_rows: wav [B][M][Lmax]; utterance b is wav[b][m][i] for 0 <= i < len[b] and
+ * ZERO elsewhere (enforced here, whatever the caller padded with); its segment y starts at off0[b] + y * seg_off; spec as se_sig_stft.
+ * se_train_ola_fwd_rows: out [B][Lmax], out[b][len[b]:] = 0; _bwd_rows never reads dout[b][len[b]:].  Row b equals the scalar call on
+ * that utterance alone bit for bit.  nseg must cover the longest utterance (train_stages.ragged_geometry). */
+int se_sig_stft_rows(se_sig *g, const float *wav, int B, int M, int64_t Lmax, const int64_t *off0, const int64_t *len, int64_t seg_off, int nseg, float *spec,
+                     void *stream);
+int se_train_ola_fwd_rows(se_sig *g, const float *yseg, float *out, int B, int64_t Lmax, const int64_t *skip, const int64_t *len, void *stream);
+int se_train_ola_bwd_rows(se_sig *g, const float *dout, float *gseg, int B, int nseg, int64_t Lmax, const int64_t *skip, const int64_t *len, void *stream);
+/* per-stream slab gather: dst[b][x] = src[idx[b] * sN + b * sB + x] for x < X, zeros where idx[b] < 0 (idx: device int64 [B]).  src
+ * [N + 1][B][X] (sN = B * X, sB = X): every utterance's carried state at its own last segment; src [1][B][X] with idx 0 / -1: the first
+ * slab of a mixed-flag batch (the carried row, or zeros after a reset). */
+int se_train_slab_gather(const float *src, const int64_t *idx, float *dst, int B, int64_t X, int64_t sN, int64_t sB, void *stream);
 /* features (CRN.py:463-467): spec [S][M][T][F][2] -> feat [S][2M-1][T][F] (no backward: the input carries no gradient) */
 int se_train_feat(const float *spec, float *feat, int S, int M, int T, int F, int atan2_phase, void *stream);
 /* decompress_cIRM + complex multiply with microphone 0 (utility.py:439-442, CRN.py:491-495): x [S][2][T][F] -> Y [S][T][F][2];

@@ -205,6 +205,41 @@ int se_train_ola_bwd(se_sig *g, const float *dout, float *gseg, int B, int nseg,
     return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "launch failed");
 }
 
+int se_sig_stft_rows(se_sig *g, const float *wav, int B, int M, int64_t Lmax, const int64_t *off0, const int64_t *len, int64_t seg_off, int nseg, float *spec,
+                     void *stream) {
+    if (!g || !wav || !off0 || !len || !spec || B <= 0 || M <= 0 || Lmax <= 0 || nseg <= 0) return train_fail(SE_ERR_ARG, "bad argument");
+    se::StftArgs a{};
+    a.src = wav; a.strideB = (long)M * Lmax; a.strideM = Lmax; a.M = M; a.L = Lmax;
+    a.offrow = reinterpret_cast<const long *>(off0); a.Lrow = reinterpret_cast<const long *>(len);
+    a.K = g->K; a.T = g->T; a.F = g->F; a.hop = g->hop;
+    a.spec = reinterpret_cast<cf2 *>(spec); a.sR = (long)g->T * g->F; a.sT = g->F; a.sF = 1;
+    a.window = g->window; a.tw = reinterpret_cast<const cf2 *>(g->tw); a.plan = g->plan;
+    a.seg_off = seg_off; a.seg_spec = (long)B * M * g->T * g->F;
+    se::launch_k_stft(dim3(B * M, nseg), se::stft_lds_bytes(g->K, g->N), static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "stft launch failed");
+}
+
+int se_train_ola_fwd_rows(se_sig *g, const float *yseg, float *out, int B, int64_t Lmax, const int64_t *skip, const int64_t *len, void *stream) {
+    if (!g || !yseg || !out || !skip || !len || B <= 0 || Lmax <= 0) return train_fail(SE_ERR_ARG, "bad argument");
+    hipLaunchKernelGGL(se::k_tola_fwd_rows, dim3((unsigned)((Lmax + 255) / 256), B), dim3(256), 0, static_cast<hipStream_t>(stream), yseg, out, B, g->K, (long)Lmax,
+                       reinterpret_cast<const long *>(skip), reinterpret_cast<const long *>(len));
+    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "launch failed");
+}
+
+int se_train_ola_bwd_rows(se_sig *g, const float *dout, float *gseg, int B, int nseg, int64_t Lmax, const int64_t *skip, const int64_t *len, void *stream) {
+    if (!g || !dout || !gseg || !skip || !len || B <= 0 || nseg <= 0 || Lmax <= 0) return train_fail(SE_ERR_ARG, "bad argument");
+    hipLaunchKernelGGL(se::k_tola_bwd_rows, dim3((g->K + 255) / 256, B, nseg), dim3(256), 0, static_cast<hipStream_t>(stream), dout, g->env, gseg, B, g->K, (long)Lmax,
+                       reinterpret_cast<const long *>(skip), reinterpret_cast<const long *>(len));
+    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "launch failed");
+}
+
+int se_train_slab_gather(const float *src, const int64_t *idx, float *dst, int B, int64_t X, int64_t sN, int64_t sB, void *stream) {
+    if (!src || !idx || !dst || B <= 0 || X <= 0) return train_fail(SE_ERR_ARG, "bad argument");
+    hipLaunchKernelGGL(se::k_slab_gather, dim3((unsigned)((X + 255) / 256), B), dim3(256), 0, static_cast<hipStream_t>(stream), src, reinterpret_cast<const long *>(idx), dst,
+                       (long)X, (long)sN, (long)sB);
+    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "launch failed");
+}
+
 int se_train_feat(const float *spec, float *feat, int S, int M, int T, int F, int atan2_phase, void *stream) {
     if (!spec || !feat || S <= 0) return train_fail(SE_ERR_ARG, "bad argument");
     hipLaunchKernelGGL(se::k_tfeat, dim3((T * F + 255) / 256, S), dim3(256), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const cf2 *>(spec), feat, M, T * F, atan2_phase);

@@ -55,6 +55,7 @@ struct StftArgs {
     FftPlan plan;
     long seg_off, seg_spec;  // blockIdx.y = segment of a batch of segments: off += y*seg_off, spec += y*seg_spec
     const long *Lrow;        // optional per-stream lengths [rows / M] (ragged batches): samples beyond a stream's own length read as zeros
+    const long *offrow;      // optional per-stream first-segment offsets [rows / M], in place of `off` (se_sig_stft_rows)
 };
 
 // LDS: sig[K+N] | win[N] | tw[N] (cf2) | bufA[kFftBatch*N/2] | bufB[kFftBatch*N/2]
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void k_stft(StftArgs a) {
     cf2 *bufB = bufA + kFftBatch * N2;
     const int row = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
     const float *src = a.src + (long)(row / a.M) * a.strideB + (long)(row % a.M) * a.strideM;
-    const long seg_first = a.off + (long)blockIdx.y * a.seg_off;
+    const long seg_first = (a.offrow ? a.offrow[row / a.M] : a.off) + (long)blockIdx.y * a.seg_off;
     cf2 *spec_out = a.spec + (long)blockIdx.y * a.seg_spec;
     const long Lr = a.Lrow ? min(a.Lrow[row / a.M], a.L) : a.L;
     for (int i = tid; i < K + N; i += nth) {

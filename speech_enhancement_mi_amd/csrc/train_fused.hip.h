@@ -374,6 +374,39 @@ __global__ __launch_bounds__(256) void k_tola_bwd(const float *dout, const float
     g[((long)n * B + b) * K + k] = v;
 }
 
+// ---- the same pair for a batch of chunk chains: utterance b has its own skip[b] (K/2 after a reset, else 0) and length len[b] ----
+// out [B][Lmax] with out[b][len[b]:] = 0; per sample the arithmetic of k_tola_fwd, so a row equals its own k_tola_fwd launch bit for bit
+__global__ __launch_bounds__(256) void k_tola_fwd_rows(const float *yseg, float *out, int B, int K, long Lmax, const long *skip, const long *len) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= Lmax) return;
+    if (i >= len[b]) { out[(long)b * Lmax + i] = 0.0f; return; }
+    const long P = K / 2, i2 = i + skip[b], i1 = i2 + P;
+    const float v1 = yseg[((2 * (i1 / K)) * (long)B + b) * K + i1 % K];
+    const float v2 = yseg[((2 * (i2 / K) + 1) * (long)B + b) * K + i2 % K];
+    out[(long)b * Lmax + i] = (v1 + v2) / 2;
+}
+// adjoint: dout[b][len[b]:] is never read, so segments past an utterance's end receive an exact zero gradient
+__global__ __launch_bounds__(256) void k_tola_bwd_rows(const float *dout, const float *env, float *g, int B, int K, long Lmax, const long *skip, const long *len) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y, n = blockIdx.z;
+    if (k >= K) return;
+    const long P = K / 2, sk = skip[b], Lb = min(len[b], Lmax);
+    const long pos = (long)(n >> 1) * K + k;
+    const long i = (n & 1) ? pos - sk : pos - sk - P;
+    const float v = (i >= 0 && i < Lb) ? 0.5f * dout[(long)b * Lmax + i] / env[k] : 0.0f;
+    g[((long)n * B + b) * K + k] = v;
+}
+// per-stream slab gather: dst[b][x] = src[idx[b] * sN + b * sB + x], zeros where idx[b] < 0.  With src [N + 1][B][X] it picks every
+// utterance's carried state at its own last segment; with src [1][B][X] and idx = 0 / -1 it is the masked first-slab fill.
+__global__ __launch_bounds__(256) void k_slab_gather(const float *src, const long *idx, float *dst, long X, long sN, long sB) {
+    const long x = (long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (x >= X) return;
+    const long n = idx[b];
+    dst[(long)b * X + x] = n < 0 ? 0.0f : src[n * sN + (long)b * sB + x];
+}
+
 // ---- CRN_ELU deltas (CRN_ELU.py:194-252, 335-340, 375-376) -----------------------------------------------------------------------
 // Gated 1x1 pair + norm: tg [S][2C][T][F] holds conv_trans(a) in channels [0, C) and conv_gated(a) in [C, 2C);
 // p = t * sigmoid(g); y = gLN(p) (CRN_ELU.py:240-241).  Backward: dp by the gLN formula, dt = dp * sigmoid(g), dg = dp * t * s (1 - s);

@@ -213,3 +213,33 @@ class ChunkChain:
 
     def __iter__(self):
         return self
+
+
+class ChunkChainBatch:
+    """B independent ChunkChains served together, one chunk of each per step - the batch the training kernels take with per-utterance
+    lengths and flags (realtime_process_train(mix, flag, lengths=length), train_step(..., length=, flag=)).  The reference runs one
+    chain at batch 1; here every chain keeps its own buffer, rng and refill rhythm, so chain b sees exactly the chunks, lengths and flags
+    it would see alone.  __next__ -> dict(mix [B, M, Lmax], source [B, ..., Lmax], noise likewise: zero beyond each chunk's length;
+    length [B] int64; flag [B] bool).  Pure torch / numpy."""
+
+    def __init__(self, chains):
+        self.chains = list(chains)
+        if not self.chains:
+            raise ValueError("ChunkChainBatch needs at least one ChunkChain")
+
+    def __next__(self):
+        items = [next(c) for c in self.chains]
+        Lmax = max(it["length"] for it in items)
+
+        def stack(key):
+            rows = [torch.as_tensor(it[key]) for it in items]
+            out = rows[0].new_zeros((len(rows),) + tuple(rows[0].shape[:-1]) + (Lmax,))
+            for b, r in enumerate(rows):
+                out[b, ..., :r.shape[-1]] = r
+            return out
+
+        return dict(mix=stack("mix"), source=stack("source"), noise=stack("noise"), length=torch.tensor([it["length"] for it in items], dtype=torch.int64),
+                    flag=torch.tensor([it["flag"] for it in items], dtype=torch.bool))
+
+    def __iter__(self):
+        return self

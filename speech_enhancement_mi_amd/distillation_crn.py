@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from .crn import TemporalCRN as _Base
-from .train_stages import _as_flag, segment_geometry
+from .train_stages import _as_flags, _as_lengths, segment_geometry
 
 
 class TemporalCRN(_Base):
@@ -253,16 +253,24 @@ class DistillationCRN(nn.Module):
         return DistillLossFunction.apply(bns, training, len(ss), *ss, *ts, *params)
 
     def forward(self, noisy, clean, length, flag):
-        flag = _as_flag(flag)
+        """flag and length per utterance: a batch of chunk chains (datagen.ChunkChainBatch) - teacher and student see utterance b up to
+        length[b] only and continue their own row b where flag[b] holds; a batch of full-length utterances with one flag is the plain call."""
+        B, Lmax = noisy.shape[0], noisy.shape[-1]
+        flags, lens = _as_flags(flag, B), _as_lengths(length, B, Lmax)
+        if len(set(flags)) == 1 and min(lens) == Lmax:
+            return self._forward(noisy, clean, length, flags[0], {})
+        return self._forward(noisy, clean, length, flags, dict(lengths=lens))
+
+    def _forward(self, noisy, clean, length, flag, kw):
         if self._hip:
             if any(p.requires_grad for p in self.teacher.parameters()):
                 raise RuntimeError("the HIP distillation path needs a frozen teacher (DistillationCRN(..., path=checkpoint)); "
                                    "a trainable teacher runs on the torch path only")
             with torch.no_grad():
-                _, ft = self.teacher.realtime_process_train(noisy, flag, features=True)
+                _, ft = self.teacher.realtime_process_train(noisy, flag, features=True, **kw)
         else:
-            _, ft = self.teacher.realtime_process_train(noisy, flag, features=True)
-        pred, fs = self.student.realtime_process_train(noisy, flag, features=True)
+            _, ft = self.teacher.realtime_process_train(noisy, flag, features=True, **kw)
+        pred, fs = self.student.realtime_process_train(noisy, flag, features=True, **kw)
         loss, stoi, sisnr = self.student.compute_loss(clean, pred, length)
         loss = loss + self.distillation_loss(ft, fs)
         return loss, stoi, sisnr

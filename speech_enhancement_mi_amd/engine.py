@@ -27,7 +27,7 @@ EXPORTS = [
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
     "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
     "se_train_add", "se_train_add3", "se_train_gate_fwd", "se_train_gate_bwd", "se_train_elu_bwd", "se_train_pre5", "se_train_gru_hprev", "se_train_conv_ws_floats", "se_train_conv_w", "se_train_conv_wgrad_det", "se_train_gemm_tn_det", "se_train_add_csum", "se_distill_ws_bytes",
-    "se_distill_fwd", "se_distill_bwd", "se_gbf_psd_fwd", "se_gbf_seq_fwd", "se_gbf_bf_fwd", "se_gbf_psd_bwd", "se_gbf_seq_bwd", "se_gbf_bf_bwd", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
+    "se_distill_fwd", "se_distill_bwd", "se_sig_stft_rows", "se_train_ola_fwd_rows", "se_train_ola_bwd_rows", "se_train_slab_gather", "se_gbf_psd_fwd", "se_gbf_seq_fwd", "se_gbf_bf_fwd", "se_gbf_psd_bwd", "se_gbf_seq_bwd", "se_gbf_bf_bwd", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
 ]
 
 
@@ -140,6 +140,10 @@ def load_library():
     L.se_sig_istft.argtypes = [vp, vp, i32, vp, vp]
     L.se_train_ola_fwd.argtypes = [vp, vp, vp, i32, i64, i64, vp]
     L.se_train_ola_bwd.argtypes = [vp, vp, vp, i32, i32, i64, i64, vp]
+    L.se_sig_stft_rows.argtypes = [vp, vp, i32, i32, i64, vp, vp, i64, i32, vp, vp]
+    L.se_train_ola_fwd_rows.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
+    L.se_train_ola_bwd_rows.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp]
+    L.se_train_slab_gather.argtypes = [vp, vp, vp, i32, i64, i64, i64, vp]
     L.se_train_feat.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     L.se_train_mask_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.se_train_mask_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]

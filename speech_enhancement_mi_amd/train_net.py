@@ -22,7 +22,8 @@ import torch
 from . import train_ops as K
 from .train_stages import (_cs, _new, _p, _run, _sig, colsum3, colsum_tall, conv_w, decoder_bwd, decoder_fwd,
                            encoder_block_bwd, encoder_block_fwd, encoder_conv_bwd, gemm_tn, gln_bwd, gln_fwd, grads_in_parameter_order,
-                           gru_layer_bwd, input_features, segment_geometry, stft, synthesis, synthesis_adjoint, transpose, wgrad)
+                           gru_layer_bwd, input_features, ragged_geometry, segment_geometry, slab_gather, stft, stft_rows, synthesis,
+                           synthesis_adjoint, synthesis_adjoint_rows, synthesis_rows, transpose, wgrad, _as_flags, _as_lengths, _rows)
 
 _side_streams = {}
 PIPELINE_LAYERS = True   # training forward: GRU layers as a wavefront over segments on one HIP stream per layer (False: layer after layer)
@@ -35,8 +36,14 @@ def _side_stream(dev, idx):
     return _side_streams[key]
 
 
-def _first_slab(t, state, key, idx):   # slab 0 = the carried state of a flag=True continuation, zeros after a reset
-    t[0].copy_(state[key][idx]) if state is not None and state.get(key) is not None else t[0].zero_()
+def _first_slab(t, state, key, idx, q):   # slab 0 = the carried state of a flag=True continuation, zeros after a reset
+    if state is None or state.get(key) is None:
+        t[0].zero_()
+    elif "rows" not in q:
+        t[0].copy_(state[key][idx])
+    else:   # chunk chains: row b of the carried batch where flags[b], zeros where utterance b starts afresh
+        X = t[0][0].numel()
+        slab_gather(state[key][idx], q["rows"]["carry"], q["B"], X, q["B"] * X, X, dst=t[0])
 
 
 def _inject(dpre, gf, S, Cc, X):   # dpre += d feature map; -> the bias gradient (per-channel sums of the result)
@@ -80,9 +87,20 @@ def gate_pair_bwd(dy_ptr, ds, a_t, tg, stt, blk, pre, grads, zero_bias, S, Co, T
 
 # ---- the stages of CRNFunction: q = the call's dimensions, sv = what the forward saves for the backward ---------------------------
 def _dims(model, mixture, flag):
+    """flag: a bool, or (flags, lengths) of a batch of chunk chains - B bools and B ints, host values"""
     B, M, L = mixture.shape
     n_fft = model._cfg_args["n_fft"]
-    q = segment_geometry(L, flag, model.segment_length, model._hop, n_fft, [2 * M - 1] + [blk.conv.weight.shape[0] for blk in model.convlist])
+    ch = [2 * M - 1] + [blk.conv.weight.shape[0] for blk in model.convlist]
+    if isinstance(flag, tuple):
+        q = ragged_geometry(flag[1], flag[0], model.segment_length, model._hop, n_fft, ch)
+        if len(q["flags"]) != B or q["L"] > L:
+            raise ValueError(f"flags / lengths {flag} do not describe a batch of {B} utterances of up to {L} samples")
+        q["L"] = L
+        dev = mixture.device   # everything the row kernels index by utterance, one small copy each, no host synchronisation
+        q["rows"] = dict(off0=_rows(q["off0"], dev), len=_rows(q["lengths"], dev), skip=_rows(q["skip"], dev), last=_rows(q["Nb"], dev),
+                         lastseg=_rows([n - 1 for n in q["Nb"]], dev), carry=_rows([0 if f else -1 for f in q["flags"]], dev))
+    else:
+        q = segment_geometry(L, flag, model.segment_length, model._hop, n_fft, ch)
     g = model.gru.sequence_model
     Lv = len(model.convlist)
     CL, FL = q["ch"][Lv], q["Fq"][Lv]
@@ -98,7 +116,7 @@ def _pre_fwd(model, q, sv, state):
     V, dev = sv["V"], sv["spec"].device
     cur = _new(N + 1, B, C0, T, F0, dev=dev)
     slab0 = B * C0 * T * F0
-    _first_slab(cur, state, "pbuf" if V else "buf", 0)
+    _first_slab(cur, state, "pbuf" if V else "buf", 0, q)
     input_features(sv["spec"], cur, S, B, M, C0, T, F0, 1 if V == 1 else 0)
     sv["pre"] = []
     if V:
@@ -109,7 +127,7 @@ def _pre_fwd(model, q, sv, state):
             out = _new(S, C0, T, F0, dev=dev)
             tg, stt = gate_pair(a_t, blk, _p(out), _cs(C0, T, F0), S, C0, T, F0, sv["em"])
             nxt = _new(N + 1, B, C0, T, F0, dev=dev)
-            _first_slab(nxt, state, "pbuf", k + 1) if k < 2 else _first_slab(nxt, state, "buf", 0)
+            _first_slab(nxt, state, "pbuf", k + 1, q) if k < 2 else _first_slab(nxt, state, "buf", 0, q)
             _run("k_tadd", 0.0, lib.se_train_add3, _p(nxt, slab0), _p(out), _p(cur, slab0), S * C0 * T * F0, K._st())
             sv["pre"].append(dict(cur=cur, a=a_t, tg=tg, st=stt))
             cur = nxt
@@ -146,7 +164,7 @@ def _encoder_fwd(model, q, sv, state, x_full, features):
         Ci, Co, Fi, Fo, d = ch[i], ch[i + 1], Fq[i], Fq[i + 1], 2 ** i
         if i < Lv - 1:
             nxt = _new(N + 1, B, Co, T, Fo, dev=dev)
-            _first_slab(nxt, state, "buf", i + 1)
+            _first_slab(nxt, state, "buf", i + 1, q)
             y_ptr, ysd = _p(nxt, B * Co * T * Fo), _cs(Co, T, Fo)
             xin.append(nxt)
         else:
@@ -203,7 +221,10 @@ def _gru_fwd(model, q, sv, state):
     outs, gates, h0s, hTs = [], [], [], []
     gi0 = K._gemm(seq, g.weight_ih_l0, g.bias_ih_l0)
     for l in range(NL):
-        h0s.append(state["h"][l] if state is not None and state["h"] is not None else torch.zeros(B, H, device=dev))
+        if state is None or state["h"] is None:
+            h0s.append(torch.zeros(B, H, device=dev))
+        else:
+            h0s.append(state["h"][l] if "rows" not in q else slab_gather(state["h"][l], q["rows"]["carry"], B, H, B * H, H))
         outs.append(_new(R, H, dev=dev)); gates.append(_new(R, 4 * H, dev=dev))
     if NL == 1 or N < 4 or not PIPELINE_LAYERS or not K._lib().se_train_gru_pseq_supported(B, H):
         layer_in = seq
@@ -286,10 +307,16 @@ class CRNFunction(torch.autograd.Function):
             raise ValueError("feature maps exist for the distillation_crn.py architecture (variant 2) only")
         q = _dims(model, mixture, flag)
         B, M, N, S, T, F0, Lv, CL, FL, D = (q[k] for k in ("B", "M", "N", "S", "T", "F0", "Lv", "CL", "FL", "D"))
-        state = model._state if flag else None
+        rows = q.get("rows")   # a batch of chunk chains: per-utterance offsets, lengths and flags on the device
+        state = model._state if (any(q["flags"]) if rows else flag) else None
+        if rows and state is not None and state["h"][0].shape[0] != B:
+            raise RuntimeError(f"flag=True continues row b of the carried state, which holds {state['h'][0].shape[0]} utterances, not {B}")
         act, em = 2 if V else 1, 1 if V == 2 else 0   # em = eps_mode of every gLN
         sv = dict(V=V, act=act, em=em)  # saved for backward
-        spec = sv["spec"] = stft(q["sig"], mixture, B, M, q["L"], q["off0"], q["P"], N, T, F0)
+        if rows:
+            spec = sv["spec"] = stft_rows(q["sig"], mixture, B, M, q["L"], rows["off0"], rows["len"], q["P"], N, T, F0)
+        else:
+            spec = sv["spec"] = stft(q["sig"], mixture, B, M, q["L"], q["off0"], q["P"], N, T, F0)
         f0 = _encoder_fwd(model, q, sv, state, _pre_fwd(model, q, sv, state), features)
         o_fc, hTs = _gru_fwd(model, q, sv, state)
         xd = _new(S, CL, T, FL, dev=spec.device)
@@ -300,9 +327,20 @@ class CRNFunction(torch.autograd.Function):
             raise RuntimeError("last decoder block must produce the 2-channel mask at full resolution")
         Y = _new(S, T, F0, 2, dev=spec.device)
         _run("k_tmask", 0.0, K._lib().se_train_mask_fwd, _p(xl), _p(spec), _p(Y), S, M, T, F0, K._st())
-        pred = synthesis(q["sig"], Y, B, q["Ks"], q["L"], q["skip"])
         # carried state for a flag=True continuation: the last segment's block inputs and the GRU state (detached by construction)
-        model._state = dict(buf=[sv["xin"][i][N] for i in range(Lv)], h=hTs, pbuf=[r["cur"][N] for r in sv["pre"]] if V else None)
+        if rows:   # ... of every utterance's OWN last segment: slab Nb[b], and the layer outputs' row of step Nb[b] * T - 1
+            pred = synthesis_rows(q["sig"], Y, B, q["Ks"], q["L"], rows["skip"], rows["len"])
+            H = q["H"]
+
+            def last(t):   # t [N + 1][B][...] -> [B][...]
+                X = t[0][0].numel()
+                return slab_gather(t, rows["last"], B, X, B * X, X).view(t.shape[1:])
+
+            model._state = dict(buf=[last(sv["xin"][i]) for i in range(Lv)], pbuf=[last(r["cur"]) for r in sv["pre"]] if V else None,
+                                h=[slab_gather(o, rows["lastseg"], B, H, B * T * H, T * H, (T - 1) * H) for o in sv["outs"]])
+        else:
+            pred = synthesis(q["sig"], Y, B, q["Ks"], q["L"], q["skip"])
+            model._state = dict(buf=[sv["xin"][i][N] for i in range(Lv)], h=hTs, pbuf=[r["cur"][N] for r in sv["pre"]] if V else None)
         ctx.model, ctx.dims, ctx.sv = model, q, sv
         if features:
             return (pred, f0, o_fc) + tuple(r["yd"] for r in dec[:Lv - 1])
@@ -324,7 +362,10 @@ class CRNFunction(torch.autograd.Function):
             if j < Lv - 1 and dfeats[2 + j] is not None:
                 return _inject(dyd, dfeats[2 + j], S, rec["Co"], T * rec["Fy"])
 
-        dY = synthesis_adjoint(q["sig"], dpred, B, N, q["L"], q["skip"], q["Ks"], T, F0)
+        if "rows" in q:
+            dY = synthesis_adjoint_rows(q["sig"], dpred, B, N, q["L"], q["rows"]["skip"], q["rows"]["len"], q["Ks"], T, F0)
+        else:
+            dY = synthesis_adjoint(q["sig"], dpred, B, N, q["L"], q["skip"], q["Ks"], T, F0)
         dx = _new(S, 2, T, F0, dev=dev)
         _run("k_tmask", 0.0, K._lib().se_train_mask_bwd, _p(dY), _p(sv["xl"]), _p(sv["spec"]), _p(dx), S, M, T, F0, q["n_fft"], K._st())
         dxd, dres = decoder_bwd(model.deconvlist, sv["dec"], sv["xin"], dx, grads, zero_bias, S, B, T, sv["act"], sv["em"], hook=feature_hook)
@@ -349,11 +390,23 @@ class CRNFeatFunction(torch.autograd.Function):
         return CRNFunction.backward(ctx, dpred, *dfeats)
 
 
-def realtime_process_fused(model, mixture, flag=False, features=False):
+def realtime_process_fused(model, mixture, flag=False, features=False, lengths=None):
+    """flag: a bool, or one value per utterance ([B] tensor / list); lengths: per-utterance lengths <= mixture.shape[-1] (None: all full).
+    With either given per utterance, the batch is B independent chunk chains (datagen.ChunkChainBatch): utterance b is zero beyond
+    lengths[b] (whatever the padding holds), starts from zero state where flag[b] is False and continues row b of model._state where it is
+    True; pred[b, lengths[b]:] = 0 and model._state afterwards holds, per utterance, what that utterance alone would carry.  The feature
+    maps of features=True cover all N = max N_b windows of every utterance.  A batch whose flags and lengths are all alike takes the
+    scalar kernels, as a bool flag does."""
     params = [p for _, p in model.named_parameters()]
+    if lengths is not None or isinstance(flag, (torch.Tensor, list, tuple)):
+        B, _, Lmax = mixture.shape
+        flags, lens = _as_flags(flag, B), _as_lengths(lengths, B, Lmax)
+        flag = flags[0] if len(set(flags)) == 1 and min(lens) == Lmax else (tuple(flags), tuple(lens))
+    else:
+        flag = bool(flag)
     if not features:
-        return CRNFunction.apply(model, mixture, bool(flag), *params)
-    pred, f0, f1, *fd = CRNFeatFunction.apply(model, mixture, bool(flag), *params)
+        return CRNFunction.apply(model, mixture, flag, *params)
+    pred, f0, f1, *fd = CRNFeatFunction.apply(model, mixture, flag, *params)
     S, C, T, F = f0.shape
     # the reference layout [N*B, C, F, T] as views: f1 is the fc output [S*T][D] reshaped (not permuted), like distillation_crn.py:368
     return pred, [f0.transpose(2, 3), f1.view(S, C, F, T)] + [f.transpose(2, 3) for f in fd]

@@ -21,6 +21,30 @@ def _as_flag(flag):
     return bool(flag.reshape(-1)[0].item()) if isinstance(flag, torch.Tensor) else bool(flag)
 
 
+def _as_flags(flag, B):
+    """Per-utterance flags of a batch of chunk chains: a bool or ONE value (every utterance; the reference trainer's flag tensor at
+    batch 1), or B values as a list or the trainer's flag tensor (read once, here).  -> a list of B bools; a mixed tensor stays mixed."""
+    if isinstance(flag, torch.Tensor):
+        flag = flag.reshape(-1).tolist()
+    if isinstance(flag, (list, tuple)):
+        if len(flag) == 1:
+            return [bool(flag[0])] * B
+        if len(flag) != B:
+            raise ValueError(f"{len(flag)} flags for a batch of {B} utterances")
+        return [bool(f) for f in flag]
+    return [bool(flag)] * B
+
+
+def _as_lengths(lengths, B, Lmax):
+    """Per-utterance lengths (a list or an integer tensor, read once, here; None: every utterance is Lmax long) -> a list of B ints"""
+    if lengths is None:
+        return [int(Lmax)] * B
+    lengths = [int(v) for v in (lengths.reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if len(lengths) != B or min(lengths) < 1 or max(lengths) > Lmax:
+        raise ValueError(f"lengths must be {B} values in [1, {Lmax}], got {lengths}")
+    return lengths
+
+
 def segment_geometry(L, flag, segment_length, hop, n_fft, ch=()):
     """One realtime_process call over L samples in half-overlapping segments (utility.segmentation); flag=False pads P = Ks / 2 samples
     on the left and strips them again.  ch = the U-Net levels' channels, input first; Fq[i] = level i's frequency size (stride 2)."""
@@ -33,6 +57,17 @@ def segment_geometry(L, flag, segment_length, hop, n_fft, ch=()):
         Fq.append((Fq[-1] - 1) // 2 + 1)
     return dict(L=L, Ks=Ks, P=P, Lp=Lp, gap=gap, N=2 * (Lp + gap + P) // Ks, off0=-P if flag else -2 * P, skip=0 if flag else P,
                 T=1 + Ks // hop, F0=Fq[0], ch=list(ch), Fq=Fq)
+
+
+def ragged_geometry(lengths, flags, segment_length, hop, n_fft, ch=()):
+    """A batch of chunk chains in one call: utterance b is lengths[b] samples long and continues its own state iff flags[b].  Segment
+    positions do not depend on the length, so every utterance keeps the geometry it would have alone: Lp, gap, Nb, off0, skip are lists,
+    entry b = segment_geometry(lengths[b], flags[b], ...); N = max Nb segments are run, L = max length is the width of the batch."""
+    per = [segment_geometry(int(L), bool(f), segment_length, hop, n_fft, ch) for L, f in zip(lengths, flags)]
+    q = dict(per[0])
+    q.update(L=max(p["L"] for p in per), N=max(p["N"] for p in per), lengths=[p["L"] for p in per], flags=[bool(f) for f in flags],
+             Nb=[p["N"] for p in per], **{k: [p[k] for p in per] for k in ("Lp", "gap", "off0", "skip")})
+    return q
 
 
 def grads_in_parameter_order(model, grads):
@@ -161,6 +196,27 @@ def stft(sig, x, B, M, L, off0, P, N, T, F0):
     return spec
 
 
+def _rows(values, dev):
+    """host ints -> a device int64 [B] (one asynchronous copy; the row kernels read it on the stream)"""
+    return torch.tensor(values, dtype=torch.int64).to(dev, non_blocking=True)
+
+
+def stft_rows(sig, x, B, M, Lmax, off0, lens, P, N, T, F0):
+    """stft for a batch of chunk chains: off0 / lens = device int64 [B]; utterance b is zero outside [0, lens[b]) whatever x holds there"""
+    spec = _new(N, B * M, T, F0, 2, dev=x.device)
+    _run("k_stft", 0.0, K._lib().se_sig_stft_rows, sig, _p(x), B, M, Lmax, C.c_void_p(off0.data_ptr()), C.c_void_p(lens.data_ptr()), P, N, _p(spec), K._st())
+    return spec
+
+
+def slab_gather(src, idx, B, X, sN, sB, off_floats=0, dst=None):
+    """dst [B][X] (new unless given): dst[b] = the X floats of src at off_floats + idx[b] * sN + b * sB, zeros where idx[b] < 0 (idx:
+    device int64 [B])"""
+    if dst is None:
+        dst = _new(B, X, dev=src.device)
+    _run("k_slab_gather", 0.0, K._lib().se_train_slab_gather, _p(src, off_floats), C.c_void_p(idx.data_ptr()), _p(dst), B, X, sN, sB, K._st())
+    return dst
+
+
 def input_features(spec, x_full, S, B, M, C0, T, F0, atan2=0):
     """spec -> magnitude + phase-difference features into slabs 1.. of x_full [N + 1][B][C0][T][F0]"""
     _run("k_tfeat", 0.0, K._lib().se_train_feat, _p(spec), _p(x_full, B * C0 * T * F0), S, M, T, F0, atan2, K._st())
@@ -189,6 +245,22 @@ def synthesis_adjoint(sig, dpred, B, N, Lout, skip, Ks, T, F0):
     """dpred [B][Lout] -> dY [S][T][F0][2]: the adjoint of overlap-add, then of the iSTFT (an STFT of every segment)"""
     gseg = _new(N * B, Ks, dev=dpred.device)
     _run("k_tola", 0.0, K._lib().se_train_ola_bwd, sig, _p(dpred), _p(gseg), B, N, Lout, skip, K._st())
+    return stft(sig, gseg, N * B, 1, Ks, 0, 0, 1, T, F0).view(N * B, T, F0, 2)
+
+
+def synthesis_rows(sig, Y, B, Ks, Lmax, skip, lens):
+    """synthesis for a batch of chunk chains: skip / lens = device int64 [B]; pred [B][Lmax] with pred[b][lens[b]:] = 0"""
+    yseg = _new(Y.shape[0], Ks, dev=Y.device)
+    istft(sig, Y, yseg)
+    pred = _new(B, Lmax, dev=Y.device)
+    _run("k_tola", 0.0, K._lib().se_train_ola_fwd_rows, sig, _p(yseg), _p(pred), B, Lmax, C.c_void_p(skip.data_ptr()), C.c_void_p(lens.data_ptr()), K._st())
+    return pred
+
+
+def synthesis_adjoint_rows(sig, dpred, B, N, Lmax, skip, lens, Ks, T, F0):
+    """synthesis_adjoint for a batch of chunk chains; dpred[b][lens[b]:] is ignored"""
+    gseg = _new(N * B, Ks, dev=dpred.device)
+    _run("k_tola", 0.0, K._lib().se_train_ola_bwd_rows, sig, _p(dpred), _p(gseg), B, N, Lmax, C.c_void_p(skip.data_ptr()), C.c_void_p(lens.data_ptr()), K._st())
     return stft(sig, gseg, N * B, 1, Ks, 0, 0, 1, T, F0).view(N * B, T, F0, 2)
 
 

@@ -22,6 +22,7 @@ from .crn import TemporalCRN
 from .crn_elu import TemporalCRN as TemporalCRNELU
 from .distillation_crn import TemporalCRN as TemporalStudentCRN
 from .losses import cal_si_snr
+from .train_stages import _as_flags, _as_lengths, ragged_geometry
 
 EPS = 1e-8
 
@@ -150,16 +151,72 @@ class _TrainableMixin:
         Y = torch.complex(m[:, 0] * re[:, 0] - m[:, 1] * im[:, 0], m[:, 1] * re[:, 0] + m[:, 0] * im[:, 0])
         return Y, dict(buf=new_buf, h=h.detach(), pbuf=new_pbuf if V else None)
 
-    def realtime_process_train(self, mixture, flag=False, features=False):
+    def _zero_state(self, B, M, like):
+        """The state of B utterances after a reset, spelled out (what `None` stands for in _forward_segment)"""
+        g = self.gru.sequence_model
+        ch = [2 * M - 1] + [blk.conv.weight.shape[0] for blk in self.convlist]
+        Fq = ragged_geometry([1], [True], self.segment_length, self._hop, self._nfft, ch)["Fq"]
+        return dict(buf=[like.new_zeros(B, ch[i], Fq[i], 2 * 2 ** i) for i in range(len(self.convlist))], h=like.new_zeros(g.num_layers, B, g.hidden_size),
+                    pbuf=[like.new_zeros(B, ch[0], Fq[0], 4) for _ in self.preconvlist] if self._VARIANT else None)
+
+    @staticmethod
+    def _merge_state(mask, a, b):
+        """per utterance: a where mask [B] holds, else b"""
+        pick = lambda x, y, bdim: torch.where(mask.view([-1 if d == bdim else 1 for d in range(x.dim())]), x, y)
+        return dict(buf=[pick(x, y, 0) for x, y in zip(a["buf"], b["buf"])], h=pick(a["h"], b["h"], 1),
+                    pbuf=None if a["pbuf"] is None else [pick(x, y, 0) for x, y in zip(a["pbuf"], b["pbuf"])])
+
+    def _realtime_process_chains(self, mixture, flags, lens, features):
+        """B independent chunk chains in one call: utterance b has its own length (zeros beyond it, enforced) and its own flag.  Every
+        statistic of the model is per utterance and segment positions do not depend on the length, so all utterances run the N = max N_b
+        segments of the longest; an utterance's carried state is taken after its OWN last segment, its output cut from its own samples."""
+        B, M, Lmax = mixture.shape
+        K = self.segment_length
+        P = K // 2
+        q = ragged_geometry(lens, flags, K, self._hop, self._nfft)
+        N, dev = q["N"], mixture.device
+        state = self._zero_state(B, M, mixture)
+        if any(flags):
+            if self._state is None or self._state.get("buf") is None or self._state["h"].shape[1] != B:
+                raise RuntimeError(f"flag=True continues row b of the carried state of {B} utterances: there is none")
+            state = self._merge_state(torch.tensor(flags, device=dev), self._state, state)
+        xp = torch.cat([Fn.pad(mixture[b:b + 1, :, :lens[b]], (-q["off0"][b], (N + 1) * P + q["off0"][b] - lens[b])) for b in range(B)])
+        idx = (torch.arange(N, device=dev) * P)[:, None] + torch.arange(K, device=dev)[None, :]
+        X = self._stft(xp[:, :, idx])  # [B, M, N, F, T]
+        Nb = torch.tensor(q["Nb"], device=dev)
+        final, outs, fts = state, [], []
+        for n in range(N):
+            f = [] if features else None
+            Y, state = self._forward_segment(X[:, :, n], state, f)
+            outs.append(self._istft(Y))
+            fts.append(f)
+            if n + 1 in q["Nb"]:
+                final = self._merge_state(Nb == n + 1, state, final)
+        self._state = final
+        y = torch.stack(outs, dim=1)  # [B, N, K]
+        full = (y[:, 0::2].reshape(B, -1)[:, P:] + y[:, 1::2].reshape(B, -1)[:, :-P]) / 2
+        out = torch.stack([Fn.pad(full[b, q["skip"][b]:q["skip"][b] + lens[b]], (0, Lmax - lens[b])) for b in range(B)])
+        if features:
+            return out, [torch.cat([f[k] for f in fts], dim=0) for k in range(len(fts[0]))]
+        return out
+
+    def realtime_process_train(self, mixture, flag=False, features=False, lengths=None):
         """Differentiable realtime_process (CRN.py:560-589): [B, M, L] -> [B, L].  features=True (variant 2): returns (pred, [ft0..ft4])
-        with the five distillation feature maps [N*B, C, F, T], window-major (distillation_crn.py:451-477)."""
+        with the five distillation feature maps [N*B, C, F, T], window-major (distillation_crn.py:451-477).
+        flag as one value per utterance ([B] tensor / list) and / or lengths ([B] ints <= L): the batch is B independent chunk chains
+        (train_net.realtime_process_fused states the contract; both paths honour it)."""
         if features and self._VARIANT != 2:
             raise ValueError("feature maps exist for the distillation_crn.py architecture (variant 2) only")
         if self._hip:  # every stage forward and backward on the hand-written kernels, one autograd node (train_net.py)
             from .train_net import realtime_process_fused
             if self._hip_state_from_torch:
                 raise RuntimeError("flag=True continuation across a use_hip_kernels() switch is not supported: start with flag=False")
-            return realtime_process_fused(self, mixture, flag, features=features)
+            return realtime_process_fused(self, mixture, flag, features=features, lengths=lengths)
+        if lengths is not None or isinstance(flag, (torch.Tensor, list, tuple)):
+            flags, lens = _as_flags(flag, mixture.shape[0]), _as_lengths(lengths, mixture.shape[0], mixture.shape[-1])
+            if len(set(flags)) > 1 or min(lens) < mixture.shape[-1]:
+                return self._realtime_process_chains(mixture, flags, lens, features)
+            flag = flags[0]
         K = self.segment_length
         P = K // 2
         if not flag:
@@ -240,7 +297,8 @@ class FlatBucket:
         return norm
 
 
-def train_step(model: TrainableCRN, bucket: FlatBucket, optimizer, mixture, source, length=None, accum: int = 1, loss: str = "sisnr", merge=None):
+def train_step(model: TrainableCRN, bucket: FlatBucket, optimizer, mixture, source, length=None, accum: int = 1, loss: str = "sisnr", merge=None,
+               flag=None):
     """One optimizer step of the reference trainer (train.py:195-204) under data parallelism: `accum` micro-batches of local
     utterances, one flat all-reduce, clip 5, Adam.  loss = "full": 0.7 * stoi_loss + 0.3 * (-SI-SNR) (compute_loss,
     CRN.py:609-611); "sisnr": the SI-SNR term alone.
@@ -249,7 +307,11 @@ def train_step(model: TrainableCRN, bucket: FlatBucket, optimizer, mixture, sour
     is per utterance, so the `accum` micro-batches can share ONE forward / backward sweep (half the dependent GRU steps) while
     the loss is still formed per micro-batch, sum_i loss(micro-batch i) / accum - the same function of the parameters, hence
     the same gradient up to fp32 summation order (tests/test_gpu_round3.py::test_merged_microbatches_give_the_accumulated_gradient).
-    merge=False runs the micro-batches one after the other like the reference loop."""
+    merge=False runs the micro-batches one after the other like the reference loop.
+
+    flag (a bool, or one value per utterance; default None = every call starts afresh and the forward sees the whole padded batch, as
+    before): the batch is one step of B chunk chains (datagen.ChunkChainBatch); flag and `length` reach the forward as its per-utterance
+    flags and lengths, and the model keeps every utterance's own state for the next step."""
     bucket.zero()
     total = 0.0
     if merge is None:
@@ -263,8 +325,14 @@ def train_step(model: TrainableCRN, bucket: FlatBucket, optimizer, mixture, sour
             return model.compute_loss(src, pred, ll)[0] / accum
         return si_snr_loss(pred, src, ln) / accum
 
+    B = mixture.shape[0]
+    chain = [{}] * accum   # the forward's flag / lengths per micro-batch
+    if flag is not None:
+        flags, lns = _as_flags(flag, B), _as_lengths(length, B, mixture.shape[-1])
+        per = -(-B // accum)   # torch.chunk's split
+        chain = [dict(flag=flags[i:i + per], lengths=lns[i:i + per]) for i in range(0, B, per)]
     if merge:
-        pred = model.realtime_process_train(mixture)
+        pred = model.realtime_process_train(mixture, **(dict(flag=flags, lengths=lns) if flag is not None else {}))
         val = None
         for slot, (p_i, src, ln) in enumerate(zip(pred.chunk(accum), srcs, lens)):
             v = loss_of(p_i, src, ln, slot)
@@ -272,8 +340,10 @@ def train_step(model: TrainableCRN, bucket: FlatBucket, optimizer, mixture, sour
         val.backward()
         total = float(val.detach())
     else:
-        for mix, src, ln in zip(mixture.chunk(accum), srcs, lens):
-            val = loss_of(model.realtime_process_train(mix), src, ln)
+        if flag is not None and any(flags) and accum > 1:
+            raise ValueError("one model carries one batch of states: chunk chains with flag=True need merge=True (or accum=1)")
+        for mix, src, ln, kw in zip(mixture.chunk(accum), srcs, lens, chain):
+            val = loss_of(model.realtime_process_train(mix, **kw), src, ln)
             val.backward()
             total += float(val.detach())
     if model._hip:
