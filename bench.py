@@ -13,9 +13,11 @@ collective, weak scaling); barrier + synchronize on both sides of the timed regi
     torch.cuda / HIP call, no exec), spawns the N ranks through torch.distributed.run as a child process and exits
     with the child's code.  Fewer than N visible devices -> non-zero exit with a message, never a silent fallback.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on the launch stream in an extra
-profiled step after the timed region) and `cpu_baseline` (the C oracle timed on the host cores, N=1 only) plus
-`cpu_baseline_torch` (the PyTorch-CPU restatement at B = 1 and 32, all cores, best of 3).
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline figure needs: set-up, warm-up, the timed
+steps, `--dump-outputs`, the line.  `--full` adds everything else the benchmark measures, in the same line: `roofline`
+(dominant kernel, HIP-event timed on the launch stream in an extra profiled step after the timed region), the `secondary`
+legs (other precisions, models and the training step, N=1 only), `cpu_baseline` (the C oracle timed on the host cores,
+N=1 only) and `cpu_baseline_torch` (the PyTorch-CPU restatement at B = 1 and 32, all cores, best of 3).
 """
 from __future__ import annotations
 
@@ -331,10 +333,11 @@ def timed_region(fn, steps, warmup, world, backend):
 # ---------------------------------------------------------------------------------------------------------------
 # workloads
 # ---------------------------------------------------------------------------------------------------------------
-def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_model=None, dump_dir=None):
+def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_model=None, dump_dir=None, profile=True):
     """BASELINE configs[3]: TemporalCRN data-parallel training, utterances sharded across ranks, ONE flat fp32 gradient
     all-reduce (24.5 MB) per optimizer step.  A step = forward + backward over `--utts` 3 s utterances per GPU (two
-    micro-batches, grad accumulation 2 like config.yaml:99), all-reduce, clip, Adam.  value = utterances/s over all ranks."""
+    micro-batches, grad accumulation 2 like config.yaml:99), all-reduce, clip, Adam.  value = utterances/s over all ranks.
+    profile=False leaves the extra profiled step out (roofline = None)."""
     import torch
     from speech_enhancement_mi_amd import synth
     train_model = train_model or args.train_model
@@ -406,7 +409,7 @@ def train_measure(args, rank, local_rank, world, backend, steps, warmup, train_m
                                 "params": torch.cat([p.detach().reshape(-1) for p in bucket.params]).cpu().numpy()})
     value = world * U * steps / dt
     roofline = None
-    if args.train_kernels == "hip":  # one extra profiled step: events around every hand-written launch on the launch stream
+    if profile and args.train_kernels == "hip":  # one extra profiled step: events around every hand-written launch on the launch stream
         from speech_enhancement_mi_amd import train_ops
         train_ops.PROF = {}
         torch.cuda.synchronize()
@@ -450,7 +453,7 @@ def train_line(args, rank, local_rank, train_model="crn"):
 
 def bench_train(args, rank, local_rank, world, backend):
     import torch.distributed as dist
-    result = train_measure(args, rank, local_rank, world, backend, args.steps, args.warmup, dump_dir=args.dump_outputs)
+    result = train_measure(args, rank, local_rank, world, backend, args.steps, args.warmup, dump_dir=args.dump_outputs, profile=args.full)
     if rank == 0:
         print(json.dumps(result))
     if world > 1:
@@ -511,10 +514,10 @@ def bench_fullsubnet(args, rank, local_rank, world, backend):
         dist.destroy_process_group()
 
 
-def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank, world, backend, label_progress="", keep_output=False):
-    """One CRN-family streaming workload: timed region + one extra profiled step (HIP events on the launch stream around every
-    launch).  Returns (value frames/s, ms_per_step, roofline dict, cfg, sd, variant, eng-derived info); keep_output: info["output"]
-    = the enhanced waveforms [B, L] of the last timed step, copied to the host before the profiled step."""
+def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank, world, backend, label_progress="", keep_output=False, profile=True):
+    """One CRN-family streaming workload: timed region + (profile=True) one extra profiled step, see crn_roofline.  Returns (value
+    frames/s, ms_per_step, roofline dict or None, info: cfg, sd, variant and eng-derived figures); keep_output: info["output"] = the
+    enhanced waveforms [B, L] of the last timed step, copied to the host before the profiled step."""
     import torch
     from speech_enhancement_mi_amd import engine, synth
     cfg = crn_cfg(nfft, model)
@@ -537,9 +540,18 @@ def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank,
     host_out = out.cpu().numpy() if keep_output else None
     frames = world * B * nseg * steps
     value = frames / dt
-    progress(f"{label_progress}{value:.0f} frames/s; profiled step")
+    progress(f"{label_progress}{value:.0f} frames/s")
+    roofline = crn_roofline(eng, mix, out, model, nfft, B, dtype, value, world) if profile else None
+    info = dict(cfg=cfg, sd=sd, variant=variant, label=label, nseg=nseg, mflop_per_frame=eng.flops_per_frame / 1e6, dt=dt, output=host_out)
+    eng.close()
+    del mix, out
+    torch.cuda.empty_cache()
+    return value, 1e3 * dt / steps, roofline, info
 
-    # ---- roofline leg: one extra profiled step, HIP events around every launch on the launch stream ----
+
+def crn_roofline(eng, mix, out, model, nfft, B, dtype, value, world):
+    """Roofline of one CRN-family workload from one extra profiled step: HIP events around every launch on the launch stream."""
+    import torch
     # On a stream of its own: timed events switch the stream's HSA queue to profiling mode for good, and everything launched on that
     # queue afterwards pays for it - the launch-dense secondary legs ran 14-16 % slower on the tainted default stream (FullSubNet 10.4 k
     # -> 9.0 k frames/s, training 335 -> 282 utt/s; profiles/leg_order_probe.py).  (Moving the LEGS to fresh streams instead costs the
@@ -571,25 +583,20 @@ def measure_crn(model, nfft, B, dtype, seconds, steps, warmup, rank, local_rank,
     workload_key = f"{model}/b{B}/nfft{nfft}/{dtype}"
     traffic, traffic_note = pmc_traffic(dom, workload_key)
     pipe_peak_equiv = BF16_DENSE_PEAK_TFLOPS / terms
-    roofline = dict(bound="mfma", kernel=dom, achieved=achieved, peak=peak, unit="TFLOP/s",
-                    frac=achieved / peak, frac_of_executed_pipe=terms * achieved / BF16_DENSE_PEAK_TFLOPS,
-                    executed_pipe="bf16 MFMA (v_mfma_f32_32x32x16_bf16)" if split else "fp16 MFMA",
-                    executed_pipe_peak=BF16_DENSE_PEAK_TFLOPS, terms_per_mac=terms, fp32_equivalent_roof=pipe_peak_equiv,
-                    traffic=traffic, traffic_note=traffic_note,
-                    executed_bf16_tflops=(terms * achieved if split else None), bf16_dense_peak=(BF16_DENSE_PEAK_TFLOPS if split else None),
-                    avg_launch_us=1e3 * d["ms"] / max(1, d["launches"]), launches_per_step=d["launches"],
-                    flops_per_launch=d["flops"] / max(1, d["launches"]),
-                    whole_path_tflops=value / world * eng.flops_per_frame / 1e12,
-                    kernels={k: dict(ms=round(v["ms"], 3), launches=v["launches"],
-                                     tflops=(v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0),
-                                     frac_of_executed_pipe=(terms * v["flops"] / (v["ms"] * 1e-3) / 1e12 / BF16_DENSE_PEAK_TFLOPS if v["ms"] > 0 else 0.0))
-                             for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1]["ms"])},
-                    labels={r["label"]: dict(ms=round(r["ms"], 3), launches=r["launches"]) for r in recs})
-    info = dict(cfg=cfg, sd=sd, variant=variant, label=label, nseg=nseg, mflop_per_frame=eng.flops_per_frame / 1e6, dt=dt, output=host_out)
-    eng.close()
-    del mix, out
-    torch.cuda.empty_cache()
-    return value, 1e3 * dt / steps, roofline, info
+    return dict(bound="mfma", kernel=dom, achieved=achieved, peak=peak, unit="TFLOP/s",
+                frac=achieved / peak, frac_of_executed_pipe=terms * achieved / BF16_DENSE_PEAK_TFLOPS,
+                executed_pipe="bf16 MFMA (v_mfma_f32_32x32x16_bf16)" if split else "fp16 MFMA",
+                executed_pipe_peak=BF16_DENSE_PEAK_TFLOPS, terms_per_mac=terms, fp32_equivalent_roof=pipe_peak_equiv,
+                traffic=traffic, traffic_note=traffic_note,
+                executed_bf16_tflops=(terms * achieved if split else None), bf16_dense_peak=(BF16_DENSE_PEAK_TFLOPS if split else None),
+                avg_launch_us=1e3 * d["ms"] / max(1, d["launches"]), launches_per_step=d["launches"],
+                flops_per_launch=d["flops"] / max(1, d["launches"]),
+                whole_path_tflops=value / world * eng.flops_per_frame / 1e12,
+                kernels={k: dict(ms=round(v["ms"], 3), launches=v["launches"],
+                                 tflops=(v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0),
+                                 frac_of_executed_pipe=(terms * v["flops"] / (v["ms"] * 1e-3) / 1e12 / BF16_DENSE_PEAK_TFLOPS if v["ms"] > 0 else 0.0))
+                         for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1]["ms"])},
+                labels={r["label"]: dict(ms=round(r["ms"], 3), launches=r["launches"]) for r in recs})
 
 
 TOL_NOTE = {"f32": "fp32-accurate (6-term split-bf16 MFMA), parity <= 1e-6 rel vs reference",
@@ -640,7 +647,7 @@ def bench_crn(args, rank, local_rank, world, backend):
     import torch.distributed as dist
     B = args.batch
     value, ms_per_step, roofline, info = measure_crn(args.model, args.nfft, B, args.dtype, args.seconds, args.steps, args.warmup, rank, local_rank, world, backend,
-                                                     keep_output=bool(args.dump_outputs))
+                                                     keep_output=bool(args.dump_outputs), profile=args.full)
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, {"enhanced": info.pop("output")})
     cfg, sd, variant, label, nseg = info["cfg"], info["sd"], info["variant"], info["label"], info["nseg"]
@@ -657,9 +664,9 @@ def bench_crn(args, rank, local_rank, world, backend):
                   roofline=roofline)
     if rank == 0:
         result["cpu_baseline"] = None
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             result["secondary"] = secondary_lines(args, rank, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             progress("cpu_baseline: C oracle")
             result["cpu_baseline"] = cpu_baseline(cfg, sd, variant)
             if variant == 0:
@@ -690,8 +697,11 @@ def parse_args(argv=None):
     ap.add_argument("--data", choices=["fixed", "gen"], default="fixed",
                     help="--mode train: fixed = one resident synthetic batch; gen = a fresh batch of simulated rooms per step from the GPU generator")
     ap.add_argument("--no-merge", action="store_true", help="--mode train: run the accumulation micro-batches one after the other (default: one shared sweep, same gradient)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline line only: skip the FullSubNet / student / CRN_ELU / training legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the roofline's extra profiled step, the secondary legs and the CPU "
+                         "baselines (default: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the FullSubNet / student / CRN_ELU / training legs")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "

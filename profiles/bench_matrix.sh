@@ -2,7 +2,7 @@
 # every bench line quoted in DESIGN.md, one JSON line per run under gpurun_out/matrix/ (run from the repo root on the GPU box)
 out=gpurun_out/matrix
 mkdir -p $out
-run() { name=$1; shift; timeout -k 10 600 python bench.py "$@" > $out/$name.json 2> $out/$name.err; echo "$name rc=$? $(tail -c 300 $out/$name.json | head -c 0)"; python - <<PY
+run() { name=$1; shift; timeout -k 10 600 python bench.py --full "$@" > $out/$name.json 2> $out/$name.err; echo "$name rc=$? $(tail -c 300 $out/$name.json | head -c 0)"; python - <<PY
 import json
 try:
     d=json.loads(open("$out/$name.json").read().strip().splitlines()[-1])
