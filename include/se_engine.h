@@ -139,7 +139,9 @@ int se_profile(se_engine *e, int enable);
 int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap, double *ms_total,
                     int64_t *launches, double *flops_per_launch);
 
-int se_abi_version(void);  /* 4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
+int se_abi_version(void);  /* 5: the first-generation training entry points are gone (se_train_conv_w, se_train_conv_wgrad_det and
+                              se_train_gemm_tn_det are the only convolution / weight-gradient forms);
+                              4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward) */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
@@ -214,35 +216,16 @@ int se_loss_sisnr_bwd(const float *separated, const float *source, const int64_t
                       const float *gscale, float *grad, void *stream);
 
 /* ---- training-step building blocks (reference train.py:195-204 = torch autograd over CRN.py:290-401, 196-287) --
- * fp32-exact MFMA kernels on device tensors; activations are [B][C][T][F] (F innermost).  The Python side
- * (speech_enhancement_mi_amd/train_ops.py) wires them into torch.autograd.Function objects; torch autograd is the checker.
+ * fp32-exact MFMA kernels on device tensors; activations are [B][C][T][F] (F innermost).  speech_enhancement_mi_amd/train_ops.py is
+ * the one launch layer over them (train_stages.py builds the models' passes on it); torch autograd is the checker.  The convolutions
+ * and the weight gradients are se_train_conv_w, se_train_conv_wgrad_det and se_train_gemm_tn_det further down: weight gradients are
+ * partial tiles per row split folded in a fixed order, the only form there is (no float atomics).
  * All calls enqueue on `stream` and return 0 or a negative se_status; se_train_last_error() gives the message. */
-typedef struct {
-    int32_t ntap, CC, nchunk, CoPad, FP;   /* weights are passed pre-arranged as [nchunk][ntap][CC][CoPad] fp32 (zero padded) */
-    int32_t tap_kf[15], tap_kt[15];        /* tap t of that arrangement = reference kernel element (kf, kt) */
-} se_train_conv_layout;
 const char *se_train_last_error(void);
-/* kind 0: TemporalConv2d (CRN.py:314: 5x3, stride (2,1), padding (2,0), dilation (1,d), causal with the history rows `xprev`);
- * kind 1 / 2: even / odd output-frequency parity of TemporalConvTranspose2d (CRN.py:369, keeping the last T columns).
- * The input gradient of kind 0 is kinds 1 + 2 applied to dy with the SAME weight tensor (and vice versa): same index algebra. */
-int se_train_conv_layout_query(int kind, int Ci, int Co, int T, int Fi, int Fy, int dil, se_train_conv_layout *out);
-int se_train_conv(int kind, const float *x, const float *xprev, const float *w_arranged, const float *bias, float *y, int B, int Ci, int Co,
-                  int T, int Fi, int Fy, int dil, int act, void *stream);
-/* C[a][b][5][3] = sum_{batch,t,m} G[a][t][m] * S[b][t-(2-kt)d][2m+kf-2]: weight gradient of kind 0 (G = dy, S = x, Sprev = history)
- * and of the transposed convolution (G = x, S = dy, Sprev = NULL) */
-int se_train_conv_wgrad(const float *G, const float *S, const float *Sprev, float *C, int B, int Ca, int Cb, int T, int Fm, int Fs, int dil,
-                        void *stream);
 /* C[M][N] = act(A[M][K] W[N][K]^T + bias[N])  (act: 0 none, 1 ReLU, 2 ELU); bias may be NULL; K % 8 == 0 */
 int se_train_gemm(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, int act, void *stream);
-/* C[Na][Nb] = sum_r A[r][i] B[r][j], both operands row-major [R][.]: dense / 1x1-convolution weight gradients over R rows */
-int se_train_gemm_tn(const float *A, const float *B, float *C, int64_t R, int Na, int Nb, void *stream);
-/* one GRU time step (CRN.py:269 nn.GRU cell), saving r, z, n, gh_n per row in `gates` for the backward pass */
-int se_train_gru_step(const float *gi, int64_t gi_ld, const float *hprev, const float *whh, const float *bhh, float *hout, float *seq,
-                      int64_t seq_ld, float *gates, int64_t gates_ld, int B, int H, void *stream);
-/* gate derivatives of one step: dh = d1 + d2 + d3 (NULL = absent) -> dgi, dgh (rows of 3H), dhz = z * dh */
-int se_train_gru_bwd_gates(const float *d1, int64_t d1_ld, const float *d2, const float *d3, const float *gates, int64_t gates_ld, const float *hprev,
-                           int64_t hprev_ld, float *dgi, float *dgh, int64_t dg_ld, float *dhz, int B, int H, void *stream);
-/* all T steps of one GRU layer in one call: forward (gate values saved) and the BPTT sweep with the gradient cut at segment
+/* all T steps of one GRU layer (CRN.py:269 nn.GRU) in one call, one launch per step: forward (r, z, n, gh_n saved per row in `gates`)
+ * and the BPTT sweep with the gradient cut at segment
  * boundaries ((t + 1) % seg_len == 0: the carried state is detached per segment, CRN.py:281).  gi [B][T][3H], out [B][T][H],
  * gates [B][T][4H], whh_t = W_hh^T [H][3H]; scratch: 2 B H floats (forward), 4 B H floats (backward); backward: B <= 16 */
 int se_train_gru_seq_fwd(const float *gi, const float *h0, const float *whh, const float *bhh, float *out, float *gates, float *hT, float *scratch,
@@ -340,13 +323,19 @@ int se_train_pre5(int mode, const float *x, const float *xprev, const float *w, 
                   int fd, int act, void *stream);
 /* h_{s-1} rows for the recurrent weight gradient (row addressing as se_train_gru_pseq_*) */
 int se_train_gru_hprev(const float *out, const float *h0, float *hp, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, void *stream);
-/* se_train_conv with the weights in their checkpoint layout (element (row, col, kf, kt) at w[row*sCo + col*sCi + kf*3 + kt]); kind 3 =
- * 1x1 convolution.  ws: se_train_conv_ws_floats() floats of scratch for the staged arrangement. */
+/* Convolutions with the weights in their checkpoint layout (element (row, col, kf, kt) at w[row*sCo + col*sCi + kf*3 + kt]).
+ * kind 0: TemporalConv2d (CRN.py:314: 5x3, stride (2,1), padding (2,0), dilation (1,d), causal with the history rows `xprev`);
+ * kind 1 / 2: even / odd output-frequency parity of TemporalConvTranspose2d (CRN.py:369, keeping the last T columns); kind 3: 1x1.
+ * The input gradient of kind 0 is kinds 1 + 2 applied to dy with the SAME weight tensor (and vice versa): same index algebra.
+ * ws: se_train_conv_ws_floats() floats of scratch for the arrangement the kernel stages (made on the device). */
 int se_train_conv_ws_floats(int kind, int Ci, int Co, int T, int Fi, int Fy, int dil);
 int se_train_conv_w(int kind, const float *x, const float *xprev, const float *w, int64_t sCo, int64_t sCi, const float *bias, float *y, float *ws,
                     int B, int Ci, int Co, int T, int Fi, int Fy, int dil, int act, int Cy, int cy0, void *stream);
                     /* Cy > 0: y has Cy channels per stream and this launch writes channels [cy0, cy0 + Co) */
-/* deterministic weight gradients: partial tiles per row split into ws[<= 64][...] (fold with se_train_colsum); ntap 15 or 1 */
+/* weight gradients as partial tiles per row split in ws[<= 64][...] (fold with se_train_colsum: fixed order, no atomics).
+ * _conv_wgrad_det: C[a][b][ntap] = sum_{batch,t,m} G[a][t][m] * S[b][t-(2-kt)d][2m+kf-2], ntap = 15 (5x3: kind 0 with G = dy, S = x, Sprev =
+ * history; the transposed convolution with G = x, S = dy, Sprev = NULL) or 1 (1x1).  _gemm_tn_det: C[Na][Nb] = sum_r A[r][i] B[r][j], both
+ * operands row-major [R][.]: dense-layer weight gradients over R rows. */
 int se_train_conv_wgrad_det(const float *G, const float *S, const float *Sprev, float *ws, int *nsplit_out, int B, int Ca, int Cb, int T, int Fm,
                             int Fs, int dil, int ntap, void *stream);
 int se_train_gemm_tn_det(const float *A, const float *B, float *ws, int *nsplit_out, int64_t R, int Na, int Nb, void *stream);

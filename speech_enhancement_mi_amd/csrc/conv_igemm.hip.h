@@ -186,7 +186,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(ConvArgs a) {
             const bool hist = ts < 0;
             const bool ok = fi >= 0 && fi < a.Fi && (hist ? (a.xprev != nullptr && ts + a.T >= 0) : ts < a.T);
             const int tsc = min(max(hist ? ts + a.T : ts, 0), a.T - 1), fic = min(max(fi, 0), a.Fi - 1);
-            goff[k] = c * (int)xs_c + tsc * a.Fi + fic;
+            // an odd Ci pads the chunk by one channel (CC = Ci + 1): its elements are zero at the LDS write, but their load
+            // must stay inside x too, so they read the last real channel
+            goff[k] = min(c, a.Ci - 1) * (int)xs_c + tsc * a.Fi + fic;
             okmask |= (ok ? 1u : 0u) << k;
             histmask |= (hist ? 1u : 0u) << k;
         }

@@ -496,7 +496,7 @@ struct GruStepArgs {
     long seq_ld;
     int B, H;
     float *gates;        // training only (nullptr in inference): r, z, n and gh_n of this step, rows of 4H with stride gates_ld,
-    long gates_ld;       // saved for the backward pass (train_ops.inc.h: k_gru_bwd_gates)
+    long gates_ld;       // saved for the backward pass (train_ops.inc.h: k_gru_bwd_step)
     __bf16 *seqp;        // optional: h_t also as split-bf16 planes [PL][rows][H] (the A operand of the next GEMM, k_gemm_p);
     long seqp_ld, seqp_plane;  // + t*H applied; row stride and plane stride in elements
     int seqp_pl;         // planes: 3, 2, or 1 (fp16)

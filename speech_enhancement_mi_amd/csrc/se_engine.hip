@@ -1021,7 +1021,7 @@ int tap_p_to_f32_dev(se_engine *e, const float *psrc, int C, int F, float *dst, 
 
 extern "C" {
 
-int se_abi_version(void) { return 4; }
+int se_abi_version(void) { return 5; }
 
 int se_config_size(void) { return (int)sizeof(se_config); }
 int fsn_config_size(void) { return (int)sizeof(fsn_config); }

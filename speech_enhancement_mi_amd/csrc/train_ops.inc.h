@@ -1,16 +1,21 @@
-// train_ops.inc.h - hand-written building blocks of the TRAINING step (reference train.py:195-204 runs
-// torch autograd over CRN.py:290-401 / 196-287); included at the end of se_engine.hip, exported through the se_train_* C ABI.
+// train_ops.inc.h - the fp32-exact MFMA building blocks of the TRAINING step (reference train.py:195-204 runs torch
+// autograd over CRN.py:290-401 / 196-287); included at the end of se_engine.hip, exported through the se_train_* C ABI and launched
+// from speech_enhancement_mi_amd/train_ops.py (the models' passes over them: train_stages.py).
 //
-// What runs where in `TrainableCRN` with use_hip_kernels(True) (speech_enhancement_mi_amd/train_ops.py):
-//   convolution forward            k_conv_igemm (fp32-exact MFMA implicit GEMM, conv_igemm.hip.h) on [B][C][T][F] activations
-//   conv / deconv input gradient   the SAME kernel with the roles swapped: d/dx of the strided causal convolution is the
-//                                  "keep the last T" transposed convolution of dy (and vice versa) - identical index algebra
-//   conv / deconv weight gradient  k_corr_wgrad below: C[a][b][kf][kt] = sum_{batch,t,m} G[a][t][m] * S[b][t-(2-kt)d][2m+kf-2]
-//   dense layers (gi, fc, dW, dx)  k_gemm_skinny below (fp32-exact MFMA GEMM, 32 x 32 tiles, K split over the four waves)
-//   GRU forward step               k_gru_step with the gate values saved for the backward pass
-//   GRU backward step (BPTT)       k_gru_bwd_gates (pointwise gate derivatives) + k_gemm_skinny (dh_{t-1} += dgh W_hh)
-// Everything is fp32 with exact MFMA accumulation order (v_mfma_f32_32x32x2_f32 / 16x16x4), so gradients agree with torch
-// autograd to rounding; the checker is tests/test_gpu_round2.py::test_hip_training_ops_vs_autograd.
+// What this file holds:
+//   se_train_conv_w                k_conv_igemm (fp32-exact MFMA implicit GEMM, conv_igemm.hip.h) on [B][C][T][F] activations, the weights
+//                                  read in checkpoint layout and staged on the device (k_arrange_w).  Kinds: strided causal 5x3 convolution,
+//                                  the two output parities of the transposed one, 1x1.  The input gradient of the strided convolution is
+//                                  the "keep the last T" transposed convolution of dy (and vice versa): identical index algebra, same kernel
+//   se_train_conv_wgrad_det        k_corr_wgrad below: C[a][b][kf][kt] = sum_{batch,t,m} G[a][t][m] * S[b][t-(2-kt)d][2m+kf-2]
+//   se_train_gemm                  k_gemm_skinny below (dense layers: gi, fc, dx; 32 x 32 tiles, K split over the four waves)
+//   se_train_gemm_tn_det           k_gemm_tn_acc below (dense / 1x1 weight gradients over row-major operands)
+//   se_train_gru_seq_fwd / _bwd    one launch per GRU step (k_gru_step / k_gru_step8 of gemm.hip.h, k_gru_bwd_step below): the route for
+//                                  hidden sizes the persistent kernels of gru_pseq.hip.h do not cover
+// Both weight-gradient kernels write one partial tile per row split and se_train_colsum (train_fused.hip.h) folds the splits in a fixed
+// order: no float atomic anywhere, gradients are bit-reproducible.  Everything is fp32 with exact MFMA accumulation order
+// (v_mfma_f32_32x32x2_f32 / 16x16x4), so results agree with torch autograd to rounding; the checkers are the *_vs_autograd tests of
+// tests/test_gpu_round2.py and tests/test_gpu_round3.py.
 
 namespace se {
 int train_fail(int code, const char *fmt, ...);  // se_train.hip (owns se_train_last_error)
@@ -105,18 +110,18 @@ void train_conv_attributes() {  // large dynamic LDS opt-in of every convolution
 
 namespace se {
 
-// C[a][b][kf][kt] += sum over (batch, t, m) of G[a][t][m] * S[b][t - (2 - kt) d][2 m + kf - 2]   (rows t' < 0 from Sprev, or zero)
+// C[a][b][kf][kt] = sum over (batch, t, m) of G[a][t][m] * S[b][t - (2 - kt) d][2 m + kf - 2]   (rows t' < 0 from Sprev, or zero)
 //   weight gradient of the strided convolution:   G = dy [B][Co][T][Fo], S = x [B][Ci][T][Fi] (+ history) -> dW [Co][Ci][5][3]
 //   weight gradient of the transposed convolution: G = x [B][Ci][T][Fi], S = dy [B][Co][T][2Fi-1]          -> dW [Ci][Co][5][3]
 // One workgroup = one 32 x 32 tile of C (rows a, columns n = b * 15 + tap) over a slice of the (batch, t) rows; its four waves
 // take rows round-robin, v_mfma_f32_32x32x2_f32 contracts two positions m per step, the waves' tiles are summed through LDS
-// and added to C with float atomics (the host zeroes C first).
+// and stored as the split's partial tile (se_train_colsum folds the splits in a fixed order: no atomics).
 struct WgradArgs {
     const float *G, *S, *Sprev;
     float *C;
     int B, Ca, Cb, T, Fm, Fs, dil, rows_per_split;
     int ntap, fs;  // 15 taps with frequency stride 2 (5x3 kernels), or ntap = 1, fs = 1 (1x1 convolutions)
-    long split_stride;  // > 0: split z writes its partial tile to C + z * split_stride (deterministic two-stage sum); 0: atomics into C
+    long split_stride;  // split z writes its partial tile to C + z * split_stride
 };
 
 __global__ __launch_bounds__(256) void k_corr_wgrad(WgradArgs a) {
@@ -198,8 +203,7 @@ __global__ __launch_bounds__(256) void k_corr_wgrad(WgradArgs a) {
             if (arow < a.Ca) {
                 const float v = acc[r] + red[0][r][lane] + red[1][r][lane] + red[2][r][lane];
                 float *dst = a.C + ((long)arow * a.Cb + bch) * a.ntap + tap;
-                if (a.split_stride) dst[(long)blockIdx.z * a.split_stride] = v;
-                else atomicAdd(dst, v);
+                dst[(long)blockIdx.z * a.split_stride] = v;
             }
         }
     }
@@ -276,7 +280,7 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(SkinnyArgs a) {
 // Gate derivatives of one GRU step (torch.nn.GRU cell; forward in gemm.hip.h: k_gru_step with `gates` saved):
 //   h = (1 - z) n + z hp ;  n = tanh(gi_n + r ghn) ;  r, z = sigmoid(gi + gh)
 // dh = d1 + d2 + d3 (any of them may be null): the loss gradient of this step's output plus what flows back from step t+1
-// (z_{t+1} dh_{t+1}, written here as `dhz`, and dgh_{t+1} W_hh from the GEMM that follows this kernel).
+// (z_{t+1} dh_{t+1}, written here as `dhz`, and dgh_{t+1} W_hh, `gout` of k_gru_bwd_step below).
 struct GruBwdArgs {
     const float *d1, *d2, *d3;  // [B][H] addends of dh_t (d1 with row stride d1_ld)
     long d1_ld;
@@ -290,36 +294,15 @@ struct GruBwdArgs {
     int B, H;
 };
 
-__global__ __launch_bounds__(256) void k_gru_bwd_gates(GruBwdArgs a) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)a.B * a.H) return;
-    const int b = (int)(i / a.H), j = (int)(i - (long)b * a.H);
-    float dh = 0.0f;
-    if (a.d1) dh += a.d1[(long)b * a.d1_ld + j];
-    if (a.d2) dh += a.d2[i];
-    if (a.d3) dh += a.d3[i];
-    const float *g = a.gates + (long)b * a.gates_ld;
-    const float r = g[j], z = g[a.H + j], n = g[2 * a.H + j], ghn = g[3 * a.H + j];
-    const float hp = a.hprev[(long)b * a.hprev_ld + j];
-    const float dn = dh * (1.0f - z), dz = dh * (hp - n);
-    const float da = dn * (1.0f - n * n);
-    const float dzp = dz * z * (1.0f - z);
-    const float drp = da * ghn * r * (1.0f - r);
-    float *gi = a.dgi + (long)b * a.dg_ld, *gh = a.dgh + (long)b * a.dg_ld;
-    gi[j] = drp; gi[a.H + j] = dzp; gi[2 * a.H + j] = da;
-    gh[j] = drp; gh[a.H + j] = dzp; gh[2 * a.H + j] = da * r;
-    a.dhz[i] = dh * z;
-}
-
 // C[Na][Nb] = sum_r A[r][i] B[r][j]: the weight gradient of a dense layer / 1x1 convolution, contracted over the R = streams x
 // positions rows of two ROW-major operands (no transposed copies of 20-MB activations; R up to 10^6, Na, Nb <= 128).  The rows
-// are split over blockIdx.z and the four waves; partial tiles are summed through LDS and added atomically into the zeroed C.
+// are split over blockIdx.z and the four waves; the waves' tiles are summed through LDS and stored as the split's partial tile.
 struct GemmTnArgs {
     const float *A, *B;
     float *C;
     long R, rows_per_split;
     int Na, Nb;
-    long split_stride;  // > 0: split z writes its partial tile to C + z * split_stride (no atomics); 0: atomicAdd into C
+    long split_stride;  // split z writes its partial tile to C + z * split_stride
 };
 
 __global__ __launch_bounds__(256) void k_gemm_tn_acc(GemmTnArgs a) {
@@ -359,8 +342,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn_acc(GemmTnArgs a) {
             if (i < a.Na) {
                 const float v = acc[r] + red[0][r][lane] + red[1][r][lane] + red[2][r][lane];
                 float *dst = a.C + (long)i * a.Nb + j0 + l31;
-                if (a.split_stride) dst[(long)blockIdx.z * a.split_stride] = v;
-                else atomicAdd(dst, v);
+                dst[(long)blockIdx.z * a.split_stride] = v;
             }
         }
     }
@@ -370,10 +352,10 @@ __global__ __launch_bounds__(256) void k_gemm_tn_acc(GemmTnArgs a) {
 //   g_t[b][k] = sum_j dgh_t[b][j] W_hh[j][k]      (w_hh_t = W_hh^T, [H][3H], K-contiguous like k_gemm_skinny's operands)
 // Every workgroup recomputes the (cheap, B x H element) gate derivatives into LDS, the owner of a 32-unit column block also
 // writes them out, then contracts its block of W_hh^T against the LDS copy (32x32x2 fp32 MFMA, K = 3H split over the four
-// waves, 12 eight-deep k blocks in flight per wave).  Replaces k_gru_bwd_gates + k_gemm_skinny (5 + 25 us, two dependent
-// launches per step) for micro-batches of up to 16 streams.
+// waves, 12 eight-deep k blocks in flight per wave): one launch per step where a pointwise gate kernel + k_gemm_skinny were two
+// dependent ones (5 + 25 us), for micro-batches of up to 16 streams.
 struct GruBwdStepArgs {
-    GruBwdArgs g;        // as k_gru_bwd_gates
+    GruBwdArgs g;        // the step's gate derivatives
     const float *whh_t;  // [H][3H]
     float *gout;         // [B][H] = dgh_t W_hh, or null for the first step of the sequence (nobody consumes it)
 };
@@ -475,48 +457,9 @@ __global__ __launch_bounds__(kGruBwdWaves * 64) void k_gru_bwd_step(GruBwdStepAr
 
 extern "C" {
 
-int se_train_conv_layout_query(int kind, int Ci, int Co, int T, int Fi, int Fy, int dil, se_train_conv_layout *out) {
-    if (!out) return tfail(SE_ERR_ARG, "null argument");
-    TrainConvGeo g;
-    int rc = train_conv_geometry(kind, Ci, Co, T, Fi, Fy, dil, g);
-    if (rc) return rc;
-    out->ntap = g.a.ntap; out->CC = g.a.CC; out->nchunk = g.a.nchunk; out->CoPad = g.a.CoPad; out->FP = g.a.FP;
-    for (int t = 0; t < 15; t++) { out->tap_kf[t] = t < g.a.ntap ? g.tap_kf[t] : 0; out->tap_kt[t] = t < g.a.ntap ? g.tap_kt[t] : 0; }
-    return SE_OK;
-}
-
-int se_train_conv(int kind, const float *x, const float *xprev, const float *w_arranged, const float *bias, float *y, int B, int Ci, int Co,
-                  int T, int Fi, int Fy, int dil, int act, void *stream) {
-    if (!x || !w_arranged || !bias || !y || B <= 0) return tfail(SE_ERR_ARG, "null argument");
-    TrainConvGeo g;
-    int rc = train_conv_geometry(kind, Ci, Co, T, Fi, Fy, dil, g);
-    if (rc) return rc;
-    ConvArgs a = g.a;
-    a.x = x; a.xprev = xprev; a.w = w_arranged; a.bias = bias; a.y = y;
-    a.act = act; a.relu_lo = 0; a.relu_hi = act ? Co : 0;
-    train_conv_attributes();
-    if (conv_igemm_launch(a.ntap, g.NT, a.CoPad, dim3(g.grid_x, B), g.lds, static_cast<hipStream_t>(stream), a))
-        return tfail(SE_ERR_ARG, "no conv kernel instance for %d taps x %d tiles", a.ntap, g.NT);
-    return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "conv launch failed");
-}
-
-int se_train_conv_wgrad(const float *G, const float *S, const float *Sprev, float *C, int B, int Ca, int Cb, int T, int Fm, int Fs, int dil,
-                        void *stream) {
-    if (!G || !S || !C || B <= 0) return tfail(SE_ERR_ARG, "null argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(C, 0, (size_t)Ca * Cb * 15 * sizeof(float), st) != hipSuccess) return tfail(SE_ERR_HIP, "memset failed");
-    const int nrows = B * T, tiles = ((Cb * 15 + 31) / 32) * ((Ca + 31) / 32);
-    int nsplit = std::max(1, std::min(nrows / 4, (4 * 256 + tiles - 1) / tiles));  // ~4 workgroups per CU over the whole grid
-    const int rows_per_split = (nrows + nsplit - 1) / nsplit;
-    nsplit = (nrows + rows_per_split - 1) / rows_per_split;
-    se::WgradArgs a{G, S, Sprev, C, B, Ca, Cb, T, Fm, Fs, dil, rows_per_split, 15, 2, 0};
-    hipLaunchKernelGGL(se::k_corr_wgrad, dim3((Cb * 15 + 31) / 32, (Ca + 31) / 32, nsplit), dim3(256), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "wgrad launch failed");
-}
-
 /* Deterministic weight gradient (no atomics): the (batch, t) rows are split over `nsplit` workgroup layers which write partial
  * tiles to ws[nsplit][Ca*Cb*ntap]; se_train_colsum folds them in a fixed order.  ntap = 15 (5x3 kernels, frequency stride 2) or
- * 1 (1x1 convolutions).  Returns the number of splits through *nsplit_out; ws needs se_train_wgrad_ws_floats() floats. */
+ * 1 (1x1 convolutions).  Returns the number of splits (<= 64) through *nsplit_out; ws needs 64 * Ca*Cb*ntap floats. */
 int se_train_conv_wgrad_det(const float *G, const float *S, const float *Sprev, float *ws, int *nsplit_out, int B, int Ca, int Cb, int T, int Fm,
                             int Fs, int dil, int ntap, void *stream) {
     if (!G || !S || !ws || !nsplit_out || B <= 0 || (ntap != 15 && ntap != 1)) return tfail(SE_ERR_ARG, "bad argument");
@@ -531,7 +474,7 @@ int se_train_conv_wgrad_det(const float *G, const float *S, const float *Sprev, 
     return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "wgrad launch failed");
 }
 
-/* se_train_conv with the weights in their checkpoint layout: element (co, ci, kf, kt) of the GEMM-row-major view at
+/* Convolution of kind 0..3 (train_conv_geometry) with the weights in their checkpoint layout: element (co, ci, kf, kt) of the GEMM-row-major view at
  * w[co * sCo + ci * sCi + kf * 3 + kt] (Conv2d: sCo = Ci*15, sCi = 15; ConvTranspose2d [Cin][Cout][5][3] read with rows = its Cout:
  * sCo = 15, sCi = Cout*15; 1x1: sCo = Ci, sCi = 1 or transposed).  The arrangement the kernel stages is made on the device into `ws`
  * (se_train_conv_ws_floats() floats) by one small launch ahead of the convolution: no host-side tensor shuffling per step. */
@@ -569,21 +512,8 @@ int se_train_gemm(const float *A, const float *W, const float *bias, float *C, i
     return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "gemm launch failed");
 }
 
-/* C[Na][Nb] = sum over the R rows of A[r][i] * B[r][j] (both row-major): weight gradients without transposed copies */
-int se_train_gemm_tn(const float *A, const float *B, float *C, int64_t R, int Na, int Nb, void *stream) {
-    if (!A || !B || !C || R <= 0 || Na <= 0 || Nb <= 0) return tfail(SE_ERR_ARG, "null argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(C, 0, (size_t)Na * Nb * sizeof(float), st) != hipSuccess) return tfail(SE_ERR_HIP, "memset failed");
-    const int tiles = ((Na + 31) / 32) * ((Nb + 31) / 32);
-    long nsplit = std::max<long>(1, std::min<long>((R + 255) / 256, (4 * 256 + tiles - 1) / tiles));  // ~4 workgroups per CU, >= 256 rows each
-    const long rows_per_split = ((R + nsplit - 1) / nsplit + 7) / 8 * 8;
-    nsplit = (R + rows_per_split - 1) / rows_per_split;
-    se::GemmTnArgs a{A, B, C, (long)R, rows_per_split, Na, Nb, 0};
-    hipLaunchKernelGGL(se::k_gemm_tn_acc, dim3((Nb + 31) / 32, (Na + 31) / 32, (unsigned)nsplit), dim3(256), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "gemm_tn launch failed");
-}
-
-/* deterministic form: partial tiles per row split to ws[nsplit][Na*Nb] (<= 64 splits), folded by se_train_colsum */
+/* C[Na][Nb] = sum over the R rows of A[r][i] * B[r][j] (both row-major): weight gradients without transposed copies, as partial tiles per
+ * row split in ws[nsplit][Na*Nb] (<= 64 splits), folded by se_train_colsum */
 int se_train_gemm_tn_det(const float *A, const float *B, float *ws, int *nsplit_out, int64_t R, int Na, int Nb, void *stream) {
     if (!A || !B || !ws || !nsplit_out || R <= 0 || Na <= 0 || Nb <= 0) return tfail(SE_ERR_ARG, "null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -595,22 +525,6 @@ int se_train_gemm_tn_det(const float *A, const float *B, float *ws, int *nsplit_
     hipLaunchKernelGGL(se::k_gemm_tn_acc, dim3((Nb + 31) / 32, (Na + 31) / 32, (unsigned)nsplit), dim3(256), 0, st, a);
     *nsplit_out = (int)nsplit;
     return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "gemm_tn launch failed");
-}
-
-int se_train_gru_step(const float *gi, int64_t gi_ld, const float *hprev, const float *whh, const float *bhh, float *hout, float *seq,
-                      int64_t seq_ld, float *gates, int64_t gates_ld, int B, int H, void *stream) {
-    if (!gi || !hprev || !whh || !bhh || !hout || !seq || B <= 0 || H <= 0 || H % 16) return tfail(SE_ERR_ARG, "bad argument (H must be a multiple of 16)");
-    se::GruStepArgs g{gi, (long)gi_ld, hprev, whh, bhh, hout, seq, (long)seq_ld, B, H, gates, (long)gates_ld};
-    hipLaunchKernelGGL(se::k_gru_step, dim3((H + 15) / 16, (B + 31) / 32), dim3(256), 0, static_cast<hipStream_t>(stream), g);
-    return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "gru step launch failed");
-}
-
-int se_train_gru_bwd_gates(const float *d1, int64_t d1_ld, const float *d2, const float *d3, const float *gates, int64_t gates_ld, const float *hprev,
-                           int64_t hprev_ld, float *dgi, float *dgh, int64_t dg_ld, float *dhz, int B, int H, void *stream) {
-    if (!gates || !hprev || !dgi || !dgh || !dhz || B <= 0 || H <= 0) return tfail(SE_ERR_ARG, "null argument");
-    se::GruBwdArgs a{d1, d2, d3, (long)d1_ld, gates, (long)gates_ld, hprev, (long)hprev_ld, dgi, dgh, (long)dg_ld, dhz, B, H};
-    hipLaunchKernelGGL(se::k_gru_bwd_gates, dim3((unsigned)(((long)B * H + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SE_OK : tfail(SE_ERR_HIP, "gru backward launch failed");
 }
 
 /* All T steps of one GRU layer from C (one Python call instead of T): forward with the gate values saved, and the BPTT
@@ -638,7 +552,7 @@ int se_train_gru_seq_bwd(const float *dout, const float *dhT, const float *gates
     if (!dout || !gates || !out || !h0 || !whh_t || !dgi || !dgh || !scratch || B <= 0 || T <= 0 || H <= 0 || H % 16) return tfail(SE_ERR_ARG, "bad argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *zb[2] = {scratch, scratch + (size_t)B * H}, *gb[2] = {scratch + (size_t)2 * B * H, scratch + (size_t)3 * B * H};
-    if (B > se::kGruBwdMaxB) return tfail(SE_ERR_ARG, "the fused BPTT step takes up to %d streams per call (got %d): use the per-step entry points", se::kGruBwdMaxB, B);
+    if (B > se::kGruBwdMaxB) return tfail(SE_ERR_ARG, "the fused BPTT step takes up to %d streams per call (got %d): call it per group of streams", se::kGruBwdMaxB, B);
     const size_t lds = (size_t)B * (3 * H + 4) * sizeof(float);
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(se::k_gru_bwd_step), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); attr = true; }

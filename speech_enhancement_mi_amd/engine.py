@@ -22,8 +22,7 @@ EXPORTS = [
     "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
     "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
-    "se_train_last_error", "se_train_conv_layout_query", "se_train_conv", "se_train_conv_wgrad", "se_train_gemm", "se_train_gemm_tn", "se_train_gru_step",
-    "se_train_gru_bwd_gates", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd",
+    "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd",
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
     "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
     "se_train_add", "se_train_add3", "se_train_gate_fwd", "se_train_gate_bwd", "se_train_elu_bwd", "se_train_pre5", "se_train_gru_hprev", "se_train_conv_ws_floats", "se_train_conv_w", "se_train_conv_wgrad_det", "se_train_gemm_tn_det", "se_train_add_csum", "se_distill_ws_bytes",
@@ -41,11 +40,6 @@ class SeConfig(C.Structure):
                 ("hidden", C.c_int32), ("num_layers", C.c_int32), ("num_inputs", C.c_int32),
                 ("kernel_size", C.c_int32), ("n_fft", C.c_int32), ("win", C.c_int32), ("hop", C.c_int32),
                 ("segment_length", C.c_int32), ("variant", C.c_int32), ("precision", C.c_int32)]
-
-
-class TrainConvLayout(C.Structure):  # se_train_conv_layout
-    _fields_ = [("ntap", C.c_int32), ("CC", C.c_int32), ("nchunk", C.c_int32), ("CoPad", C.c_int32), ("FP", C.c_int32),
-                ("tap_kf", C.c_int32 * 15), ("tap_kt", C.c_int32 * 15)]
 
 
 class FsnConfig(C.Structure):
@@ -120,13 +114,7 @@ def load_library():
     L.se_loss_sisnr_bwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
     i32, i64 = C.c_int, C.c_int64
     L.se_train_last_error.restype = C.c_char_p
-    L.se_train_conv_layout_query.argtypes = [i32] * 7 + [C.POINTER(TrainConvLayout)]
-    L.se_train_conv.argtypes = [i32, vp, vp, vp, vp, vp] + [i32] * 8 + [vp]
-    L.se_train_conv_wgrad.argtypes = [vp, vp, vp, vp] + [i32] * 7 + [vp]
     L.se_train_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.se_train_gemm_tn.argtypes = [vp, vp, vp, i64, i32, i32, vp]
-    L.se_train_gru_step.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, vp]
-    L.se_train_gru_bwd_gates.argtypes = [vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, vp]
     L.se_train_gru_seq_fwd.argtypes = [vp] * 8 + [i32, i32, i32, vp]
     L.se_train_gru_seq_bwd.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp]
     L.se_train_gru_pseq_supported.argtypes = [i32, i32]

@@ -1,7 +1,10 @@
-"""torch.autograd.Function wrappers over the hand-written training kernels (C ABI `se_train_*`, csrc/train_ops.inc.h).
+"""The single launch layer over the hand-written training kernels (C ABI `se_train_*`, csrc/train_ops.inc.h): pointer / stream /
+error plumbing, the optional per-kernel timing bench.py reads (PROF), and one launcher per kernel family - `conv_w` (weights in
+checkpoint layout, arranged on the device), `wgrad` and `gemm_tn` (partial tiles per split + a fixed-order `se_train_colsum` fold: no
+float atomics), `colsum3` / `colsum_tall`, `_gemm`, and the GRU sequence launches.  train_stages.py builds the models' passes on them.
 
-Replaces, in the timed region of the DP training step (reference train.py:195-204), torch's `conv2d` / `conv_transpose2d`
-/ `nn.GRU` / `nn.Linear` forward AND backward (MIOpen / rocBLAS) for the blocks of CRN.py:290-401 and 196-287:
+The four torch.autograd.Function wrappers at the end are the kernels' unit-test harness against torch autograd
+(tests/test_gpu_round2.py, test_gpu_round3.py), on exactly those launchers - the blocks of CRN.py:290-401 and 196-287:
 
   conv_block(x, xprev, W, b, d)      TemporalConv2d convolution (5x3, stride (2,1), causal dilation d, history rows `xprev`)
   deconv_block(x, W, b, d)           TemporalConvTranspose2d convolution, last T columns kept
@@ -9,7 +12,7 @@ Replaces, in the timed region of the DP training step (reference train.py:195-20
   gru_layer(x, h0, W_ih, W_hh, ...)  one GRU layer over T steps (BPTT in the backward)
 
 Activations are [B, C, T, F] (F innermost, the engine's layout).  Everything is fp32-exact MFMA arithmetic, so the gradients
-agree with torch autograd to rounding (tests/test_gpu_round2.py).  There is no CPU path: CPU tensors raise.
+agree with torch autograd to rounding.  There is no CPU path: CPU tensors raise.
 """
 from __future__ import annotations
 
@@ -24,8 +27,8 @@ def _lib():
     return _engine.load_library()
 
 
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+def _p(t, off_floats=0):
+    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr() + 4 * off_floats)
 
 
 def _st():
@@ -42,8 +45,6 @@ def _need_gpu(*ts):
         if t is not None and not t.is_cuda:
             raise RuntimeError("the hand-written training kernels run on the GPU only (no CPU fallback)")
 
-
-_layout_cache = {}
 
 # Optional per-kernel timing for bench.py's training roofline: PROF = {} switches it on; every launch is bracketed by two
 # torch.cuda events on the current stream (the stream the kernels are enqueued on).  profile_summary() folds them.
@@ -75,60 +76,104 @@ def profile_summary():
     return out
 
 
-def _layout(kind, Ci, Co, T, Fi, Fy, d):
-    key = (kind, Ci, Co, T, Fi, Fy, d)
-    if key not in _layout_cache:
-        lay = _engine.TrainConvLayout()
-        _chk(_lib().se_train_conv_layout_query(kind, Ci, Co, T, Fi, Fy, d, C.byref(lay)))
-        _layout_cache[key] = (lay.ntap, lay.CC, lay.nchunk, lay.CoPad, list(lay.tap_kf)[:lay.ntap], list(lay.tap_kt)[:lay.ntap])
-    return _layout_cache[key]
+def _new(*shape, dev):
+    return torch.empty(*shape, device=dev, dtype=torch.float32)
 
 
-def _arrange(w_co_ci, lay):
-    """w_co_ci [Co, Ci, 5, 3] (GEMM rows = first index) -> [nchunk][ntap][CC][CoPad] fp32, zero padded."""
-    ntap, CC, nchunk, CoPad, kf, kt = lay
-    Co, Ci = w_co_ci.shape[:2]
-    taps = w_co_ci[:, :, kf, kt]  # [Co, Ci, ntap]
-    out = w_co_ci.new_zeros(nchunk * CC, ntap, CoPad)
-    out[:Ci, :, :Co] = taps.permute(1, 2, 0)
-    return out.reshape(nchunk, CC, ntap, CoPad).permute(0, 2, 1, 3).contiguous()
+def _run(name, flops, fn, *args):
+    with _Timed(name, flops):
+        _chk(fn(*args))
 
 
-def _conv_launch(kind, x, xprev, w_co_ci, bias, y, d, act=0):
-    B, Ci, T, Fi = x.shape
-    Co, Fy = y.shape[1], y.shape[3]
-    lay = _layout(kind, Ci, Co, T, Fi, Fy, d)
-    wa = _arrange(w_co_ci, lay)
-    FP = Fy if kind == 0 else ((Fy + 1) // 2 if kind == 1 else Fy // 2)
-    with _Timed("k_conv_igemm", 2.0 * B * Co * Ci * lay[0] * T * FP):
-        _chk(_lib().se_train_conv(kind, _p(x), _p(xprev), _p(wa), _p(bias), _p(y), B, Ci, Co, T, Fi, Fy, d, act, _st()))
+# ---- thin launch helpers ---------------------------------------------------------------------------------------------------------
+def conv_w(kind, x_ptr, xprev_ptr, w, sCo, sCi, bias, y, S, Ci, Co, T, Fi, Fy, d, act=0, Cy=0, cy0=0):
+    """kind 0: strided causal 5x3 convolution, 1 / 2: even / odd output-frequency parity of the transposed one, 3: 1x1.  Element
+    (row, col, kf, kt) of the weights' GEMM-row-major view is read at w[row * sCo + col * sCi + kf * 3 + kt]."""
+    lib = _lib()
+    n = lib.se_train_conv_ws_floats(kind, Ci, Co, T, Fi, Fy, d)
+    if n < 0:
+        _chk(n)
+    ws = _new(n, dev=y.device)
+    FP = Fy if kind in (0, 3) else ((Fy + 1) // 2 if kind == 1 else Fy // 2)
+    ntap = {0: 15, 1: 9, 2: 6, 3: 1}[kind]
+    _run("k_conv_igemm", 2.0 * S * Co * Ci * ntap * T * FP, lib.se_train_conv_w, kind, x_ptr, xprev_ptr, _p(w), sCo, sCi, _p(bias), _p(y), _p(ws),
+         S, Ci, Co, T, Fi, Fy, d, act, Cy, cy0, _st())
 
 
-def _strided_conv(x, xprev, w, bias, d):  # w [Co, Ci, 5, 3]
+def wgrad(G, Sx, Sprev_ptr, S, Ca, Cb, T, Fm, Fs, d, ntap):
+    """Deterministic weight gradient [Ca][Cb][ntap]: partial tiles per row split + a fixed-order fold."""
+    lib = _lib()
+    n = Ca * Cb * ntap
+    ws = _new(64 * n, dev=G.device)
+    ns = C.c_int(0)
+    _run("k_corr_wgrad", 2.0 * S * Ca * Cb * ntap * T * Fm, lib.se_train_conv_wgrad_det, _p(G), _p(Sx) if isinstance(Sx, torch.Tensor) else Sx, Sprev_ptr,
+         _p(ws), C.byref(ns), S, Ca, Cb, T, Fm, Fs, d, ntap, _st())
+    out = _new(n, dev=G.device)
+    _run("k_colsum", 0.0, lib.se_train_colsum, _p(ws), _p(out), n, None, None, 0, None, None, 0, ns.value, 0, _st())
+    return out
+
+
+def gemm_tn(A, Bm):
+    """sum_r A[r, :]^T B[r, :] -> [Na, Nb], deterministic."""
+    lib = _lib()
+    R, Na = A.shape
+    Nb = Bm.shape[1]
+    ws = _new(64 * Na * Nb, dev=A.device)
+    ns = C.c_int(0)
+    _run("k_gemm_tn_acc", 2.0 * R * Na * Nb, lib.se_train_gemm_tn_det, _p(A), _p(Bm), _p(ws), C.byref(ns), R, Na, Nb, _st())
+    out = _new(Na, Nb, dev=A.device)
+    _run("k_colsum", 0.0, lib.se_train_colsum, _p(ws), _p(out), Na * Nb, None, None, 0, None, None, 0, ns.value, 0, _st())
+    return out
+
+
+def colsum3(R, *pairs):
+    """pairs = (part [R, n], n) ...: returns the column sums (fixed order)."""
+    lib = _lib()
+    outs = [_new(n, dev=p.device) for p, n in pairs]
+    a = []
+    for k in range(3):
+        if k < len(pairs):
+            a += [_p(pairs[k][0]), _p(outs[k]), pairs[k][1]]
+        else:
+            a += [None, None, 0]
+    _run("k_colsum", 0.0, lib.se_train_colsum, *a, R, 0, _st())
+    return outs
+
+
+def colsum_tall(x):
+    lib = _lib()
+    R, n = x.shape
+    ws = _new((R + 63) // 64, n, dev=x.device)
+    out = _new(n, dev=x.device)
+    _run("k_colsum", 0.0, lib.se_train_colsum_tall, _p(x), R, n, _p(ws), _p(out), 0, _st())
+    return out
+
+
+# ---- per-op autograd functions: the unit-test harness of the launchers above ----------------------------------------------------
+def _conv(x, xprev, w, bias, d):
+    """Strided convolution; w [Co, Ci, 5, 3] contiguous (a ConvTranspose2d weight [Cin, Cout, 5, 3] gives the deconv's input gradient)"""
     B, Ci, T, Fi = x.shape
     Co, Fo = w.shape[0], (Fi - 1) // 2 + 1
-    y = torch.empty(B, Co, T, Fo, device=x.device, dtype=torch.float32)
-    _conv_launch(0, x, xprev, w, bias, y, d)
+    y = _new(B, Co, T, Fo, dev=x.device)
+    conv_w(0, _p(x), _p(xprev), w, Ci * 15, 15, bias, y, B, Ci, Co, T, Fi, Fo, d)
     return y
 
 
-def _transposed_conv(x, w_ci_co, bias, d, Fy):  # w [Ci, Co, 5, 3] (torch ConvTranspose2d layout)
+def _deconv(x, w, bias, d, Fy):
+    """Transposed convolution, both parities; w [Ci, Co, 5, 3] contiguous, read with GEMM rows = its Co (a Conv2d weight [Cout, Cin, 5, 3]
+    gives the conv's input gradient)"""
     B, Ci, T, Fi = x.shape
-    Co = w_ci_co.shape[1]
-    y = torch.empty(B, Co, T, Fy, device=x.device, dtype=torch.float32)
-    wt = w_ci_co.permute(1, 0, 2, 3)  # GEMM rows = output channels
-    _conv_launch(1, x, None, wt, bias, y, d)
-    _conv_launch(2, x, None, wt, bias, y, d)
+    Co = w.shape[1]
+    y = _new(B, Co, T, Fy, dev=x.device)
+    for kind in (1, 2):
+        conv_w(kind, _p(x), None, w, 15, Co * 15, bias, y, B, Ci, Co, T, Fi, Fy, d)
     return y
 
 
-def _wgrad(G, S, Sprev, d):
+def _conv_wgrad(G, Sx, Sprev, d):
     B, Ca, T, Fm = G.shape
-    Cb, Fs = S.shape[1], S.shape[3]
-    out = torch.empty(Ca, Cb, 5, 3, device=G.device, dtype=torch.float32)
-    with _Timed("k_corr_wgrad", 2.0 * B * Ca * Cb * 15 * T * Fm):
-        _chk(_lib().se_train_conv_wgrad(_p(G), _p(S), _p(Sprev), _p(out), B, Ca, Cb, T, Fm, Fs, d, _st()))
-    return out
+    Cb, Fs = Sx.shape[1], Sx.shape[3]
+    return wgrad(G, Sx, _p(Sprev), B, Ca, Cb, T, Fm, Fs, d, 15).view(Ca, Cb, 5, 3)
 
 
 class _ConvFn(torch.autograd.Function):
@@ -137,7 +182,7 @@ class _ConvFn(torch.autograd.Function):
         _need_gpu(x, w)
         x = x.contiguous()
         xprev = None if xprev is None else xprev.contiguous()
-        y = _strided_conv(x, xprev, w.contiguous(), b.contiguous(), d)
+        y = _conv(x, xprev, w.contiguous(), b.contiguous(), d)
         ctx.save_for_backward(x, xprev if xprev is not None else x.new_empty(0), w)
         ctx.d, ctx.has_prev = d, xprev is not None
         return y
@@ -149,8 +194,8 @@ class _ConvFn(torch.autograd.Function):
         d = ctx.d
         zero_b = dy.new_zeros(w.shape[1])
         # d/dx: transposed convolution of dy with the same weight tensor read as [Cin' = Co][Cout' = Ci]
-        dx = _transposed_conv(dy, w, zero_b, d, x.shape[3]) if ctx.needs_input_grad[0] else None
-        dw = _wgrad(dy, x, xprev if ctx.has_prev else None, d) if ctx.needs_input_grad[2] else None
+        dx = _deconv(dy, w.contiguous(), zero_b, d, x.shape[3]) if ctx.needs_input_grad[0] else None
+        dw = _conv_wgrad(dy, x, xprev if ctx.has_prev else None, d) if ctx.needs_input_grad[2] else None
         db = dy.sum((0, 2, 3)) if ctx.needs_input_grad[3] else None
         return dx, None, dw, db, None
 
@@ -160,7 +205,7 @@ class _DeconvFn(torch.autograd.Function):
     def forward(ctx, x, w, b, d):
         _need_gpu(x, w)
         x = x.contiguous()
-        y = _transposed_conv(x, w.contiguous(), b.contiguous(), d, 2 * x.shape[3] - 1)
+        y = _deconv(x, w.contiguous(), b.contiguous(), d, 2 * x.shape[3] - 1)
         ctx.save_for_backward(x, w)
         ctx.d = d
         return y
@@ -172,8 +217,8 @@ class _DeconvFn(torch.autograd.Function):
         d = ctx.d
         dx = None
         if ctx.needs_input_grad[0]:  # strided causal convolution of dy (no history) with the weights read as [Cout' = Ci][Cin' = Co]
-            dx = _strided_conv(dy, None, w, dy.new_zeros(w.shape[0]), d)
-        dw = _wgrad(x, dy, None, d) if ctx.needs_input_grad[1] else None
+            dx = _conv(dy, None, w.contiguous(), dy.new_zeros(w.shape[0]), d)
+        dw = _conv_wgrad(x, dy, None, d) if ctx.needs_input_grad[1] else None
         db = dy.sum((0, 2, 3)) if ctx.needs_input_grad[2] else None
         return dx, dw, db, None
 
@@ -194,17 +239,6 @@ def _gemm(A, W, bias=None, act=0):
     return out
 
 
-def _gemm_tn(A, B):
-    """sum_r A[r, :]^T B[r, :] -> [Na, Nb] (row-major operands; the contraction runs over the rows)"""
-    A, B = A.contiguous(), B.contiguous()
-    R, Na = A.shape
-    Nb = B.shape[1]
-    out = torch.empty(Na, Nb, device=A.device, dtype=torch.float32)
-    with _Timed("k_gemm_tn_acc", 2.0 * R * Na * Nb):
-        _chk(_lib().se_train_gemm_tn(_p(A), _p(B), _p(out), R, Na, Nb, _st()))
-    return out
-
-
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
@@ -219,7 +253,7 @@ class _LinearFn(torch.autograd.Function):
         x2, w = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         dx = _gemm(dy2, w.t().contiguous()).reshape(ctx.shape) if ctx.needs_input_grad[0] else None
-        dw = _gemm_tn(dy2, x2) if ctx.needs_input_grad[1] else None
+        dw = gemm_tn(dy2, x2) if ctx.needs_input_grad[1] else None
         db = dy2.sum(0) if ctx.needs_input_grad[2] else None
         return dx, dw, db
 
@@ -321,8 +355,8 @@ class _GruLayerFn(torch.autograd.Function):
         dgi2, dgh2 = dgi.reshape(B * T, 3 * H), dgh.reshape(B * T, 3 * H)
         hprev_all = torch.cat([h0[:, None], out[:, :-1]], dim=1).reshape(B * T, H)
         dx = _gemm(dgi2, w_ih.t().contiguous()).reshape(B, T, In) if ctx.needs_input_grad[0] else None
-        dw_ih = _gemm_tn(dgi2, x2)
-        dw_hh = _gemm_tn(dgh2, hprev_all)
+        dw_ih = gemm_tn(dgi2, x2)
+        dw_hh = gemm_tn(dgh2, hprev_all)
         return dx, None, dw_ih, dw_hh, dgi2.sum(0), dgh2.sum(0), None
 
 

@@ -1,5 +1,6 @@
-"""The passes that every model's kernel path shares, one definition each: the launch helpers over the `se_train_*` / `se_sig_*`
-C ABI, the call geometry, the signal chain (STFT in, iSTFT + overlap-add out, and its adjoint), the plain U-Net encoder block, the
+"""The passes that every model's kernel path shares, one definition each, on the launch layer of train_ops.py (`conv_w`, `wgrad`,
+`gemm_tn`, `colsum3`, `colsum_tall`, `_new`, `_p`, `_run`: re-exported here): the call geometry, the signal chain (STFT in,
+iSTFT + overlap-add out, and its adjoint), the plain U-Net encoder block, the
 U-Net decoder and one GRU layer of the backward sweep.  train_net.CRNFunction, general_beamformer (inference and GBFFunction) and
 fsn_training.FSNFunction are orchestration over these.  Layout: S = N segments x B utterances, SEGMENT-major, activations
 [S][C][T][F]; an encoder block's input is [N + 1][B][C][T][F] with the carried time history in slab 0 (`xprev = x - one slab`).
@@ -12,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import train_ops as K
+from .train_ops import _new, _p, _run, colsum3, colsum_tall, conv_w, gemm_tn, wgrad  # noqa: F401  (re-exported)
 
 _sig_cache = {}
 
@@ -83,81 +85,6 @@ def _sig(dev, n_fft, win, hop, seg):
         K._chk(K._lib().se_sig_create(n_fft, win, hop, seg, dev.index or 0, C.byref(h)))
         _sig_cache[key] = h
     return _sig_cache[key]
-
-
-def _p(t, off_floats=0):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr() + 4 * off_floats)
-
-
-def _new(*shape, dev):
-    return torch.empty(*shape, device=dev, dtype=torch.float32)
-
-
-def _run(name, flops, fn, *args):
-    with K._Timed(name, flops):
-        K._chk(fn(*args))
-
-
-# ---- thin launch helpers ---------------------------------------------------------------------------------------------------------
-def conv_w(kind, x_ptr, xprev_ptr, w, sCo, sCi, bias, y, S, Ci, Co, T, Fi, Fy, d, act=0, Cy=0, cy0=0):
-    lib = K._lib()
-    n = lib.se_train_conv_ws_floats(kind, Ci, Co, T, Fi, Fy, d)
-    if n < 0:
-        K._chk(n)
-    ws = _new(n, dev=y.device)
-    FP = Fy if kind in (0, 3) else ((Fy + 1) // 2 if kind == 1 else Fy // 2)
-    ntap = {0: 15, 1: 9, 2: 6, 3: 1}[kind]
-    _run("k_conv_igemm", 2.0 * S * Co * Ci * ntap * T * FP, lib.se_train_conv_w, kind, x_ptr, xprev_ptr, _p(w), sCo, sCi, _p(bias), _p(y), _p(ws),
-         S, Ci, Co, T, Fi, Fy, d, act, Cy, cy0, K._st())
-
-
-def wgrad(G, Sx, Sprev_ptr, S, Ca, Cb, T, Fm, Fs, d, ntap):
-    """Deterministic weight gradient [Ca][Cb][ntap]: partial tiles per row split + a fixed-order fold."""
-    lib = K._lib()
-    n = Ca * Cb * ntap
-    ws = _new(64 * n, dev=G.device)
-    ns = C.c_int(0)
-    _run("k_corr_wgrad", 2.0 * S * Ca * Cb * ntap * T * Fm, lib.se_train_conv_wgrad_det, _p(G), _p(Sx) if isinstance(Sx, torch.Tensor) else Sx, Sprev_ptr,
-         _p(ws), C.byref(ns), S, Ca, Cb, T, Fm, Fs, d, ntap, K._st())
-    out = _new(n, dev=G.device)
-    _run("k_colsum", 0.0, lib.se_train_colsum, _p(ws), _p(out), n, None, None, 0, None, None, 0, ns.value, 0, K._st())
-    return out
-
-
-def gemm_tn(A, Bm):
-    """sum_r A[r, :]^T B[r, :] -> [Na, Nb], deterministic."""
-    lib = K._lib()
-    R, Na = A.shape
-    Nb = Bm.shape[1]
-    ws = _new(64 * Na * Nb, dev=A.device)
-    ns = C.c_int(0)
-    _run("k_gemm_tn_acc", 2.0 * R * Na * Nb, lib.se_train_gemm_tn_det, _p(A), _p(Bm), _p(ws), C.byref(ns), R, Na, Nb, K._st())
-    out = _new(Na, Nb, dev=A.device)
-    _run("k_colsum", 0.0, lib.se_train_colsum, _p(ws), _p(out), Na * Nb, None, None, 0, None, None, 0, ns.value, 0, K._st())
-    return out
-
-
-def colsum3(R, *pairs):
-    """pairs = (part [R, n], n) ...: returns the column sums (fixed order)."""
-    lib = K._lib()
-    outs = [_new(n, dev=p.device) for p, n in pairs]
-    a = []
-    for k in range(3):
-        if k < len(pairs):
-            a += [_p(pairs[k][0]), _p(outs[k]), pairs[k][1]]
-        else:
-            a += [None, None, 0]
-    _run("k_colsum", 0.0, lib.se_train_colsum, *a, R, 0, K._st())
-    return outs
-
-
-def colsum_tall(x):
-    lib = K._lib()
-    R, n = x.shape
-    ws = _new((R + 63) // 64, n, dev=x.device)
-    out = _new(n, dev=x.device)
-    _run("k_colsum", 0.0, lib.se_train_colsum_tall, _p(x), R, n, _p(ws), _p(out), 0, K._st())
-    return out
 
 
 def gln_fwd(x, xs, y_ptr, ys, w, b, S, Cc, T, Fi, Fo, mode, act, eps_mode=0):
