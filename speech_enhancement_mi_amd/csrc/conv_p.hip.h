@@ -562,11 +562,40 @@ __global__ __launch_bounds__(256) void k_gln_p(GlnPArgs a) {
     }
 }
 
-// exact two-pass gLN(last=True) of the fc output (CRN.py:127-129, 279): x [b][T][D] fp32, d = c * F + f (the reference's
-// feature order) -> decoder input in the P layout
+// gLN(last=True) of the fc output (CRN.py:127-129, 279) from the FC GEMM's per-row partial statistics -> decoder input in the P layout.
+// The FC weight rows are permuted at load time so that output column (o * F + f) * 8 + c holds reference feature (8 o + c) * F + f:
+// x [b*T + t][o][f][8] is the R-layout shape and a thread's 8 channels are 32 contiguous bytes.  The affine is per ELEMENT
+// (w, b in the same column order), which is the one difference from k_gln_p.
 
 template <int PL>
-__global__ __launch_bounds__(1024) void k_gln2_p(Gln2PArgs a) {
+__global__ __launch_bounds__(256) void k_gln2_p(Gln2PArgs a) {
+    __shared__ float sm[2];
+    const int b = blockIdx.z, o = blockIdx.y;
+    float mean, inv;
+    slab_mean_inv(a.st, b, sm, mean, inv);
+    const int TF = a.T * a.F, OF = a.C8 * a.F;
+    const float invF = 1.0f / (float)a.F;
+    const float *xb = a.x + ((long)b * a.T * OF + (long)o * a.F) * 8;
+    const float *wb = a.w + (long)o * a.F * 8, *bb = a.b + (long)o * a.F * 8;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < TF; i += gridDim.x * 256) {
+        const int t = (int)(((float)i + 0.5f) * invF), f = i - t * a.F;
+        const float4 *src = reinterpret_cast<const float4 *>(xb + ((long)t * OF + f) * 8);
+        const float4 *wp = reinterpret_cast<const float4 *>(wb + f * 8), *bp = reinterpret_cast<const float4 *>(bb + f * 8);
+        const float4 u0 = src[0], u1 = src[1], w0 = wp[0], w1 = wp[1], b0 = bp[0], b1 = bp[1];
+        float v[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
+        const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+        const float bs[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+        for (int c = 0; c < 8; c++) v[c] = (v[c] - mean) * inv * w[c] + bs[c];  // padded channels: zero column, zero affine
+        split_store8<PL>(v, a.y + (long)b * a.y_stream + (long)o * PL * TF + i, TF);
+    }
+}
+
+// The same norm on the fp32 GEMM route (few GEMM rows: skinny / k_gemm_x kernels, no epilogue statistics): exact two-pass
+// statistics in the kernel, one workgroup per stream.  x [b][T][D] fp32, d = c * F + f (the reference's feature order)
+
+template <int PL>
+__global__ __launch_bounds__(1024) void k_gln2_stream_p(Gln2PArgs a) {
     __shared__ double red[16];
     const int b = blockIdx.x;
     const int D = a.C * a.F;

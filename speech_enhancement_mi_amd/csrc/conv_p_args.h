@@ -98,11 +98,13 @@ struct GlnPArgs {
 };
 
 struct Gln2PArgs {
-    const float *x;
-    const float *w, *b;  // [D]
+    const float *x;      // k_gln2_p: fc output with octet-interleaved columns [b*T + t][o][f][8] (k_gemm_p with permuted weight rows)
+                         // k_gln2_stream_p: [b][T][D], d = c * F + f (the reference's feature order; fp32 GEMM route)
+    const float *w, *b;  // per-element affine in the column order of x
     uint4 *y;            // P[b][o][pl][t][f]
     long y_stream;
     int T, F, C, C8, eps_mode;
+    SlabStats st;        // k_gln2_p: per-row partials from the k_gemm_p epilogue
 };
 
 struct MaskPArgs {

@@ -289,6 +289,8 @@ struct GemmPArgs {
     int gx, gy;        // XCD grid (gx * gy = 8, nrt % gx == 0, nct % gy == 0); gx = 0: plain row-major tile order; gx = -1: banded -
                        // XCD x (= block id mod 8) owns the gy consecutive tiles [x * gy, (x + 1) * gy) of the row-major order (a band
                        // of rows: A is fetched by one L2 apart from the band seams), for tile grids no equal 8-block split divides
+    float *stats;      // optional: (sum, sum of squares) of the stored values of row m over the 128 columns of column tile ct at
+                       // stats[(m * nct + ct) * 2]; rows of a stream are contiguous, so this is a SlabStats slab [b][T * nct][2]
 };
 
 constexpr int kGemmPBM = 256, kGemmPBN = 128;
@@ -298,6 +300,24 @@ constexpr int kGemmPBM = 256, kGemmPBN = 128;
 #else
 #define SE_DS_READ128(dst, addr, OFF) (void)(addr)
 #endif
+
+// Sums 16 values per lane over the 32 lanes of a lane half.  Reduce-scatter: at distance n = 8, 4, 2, 1 a lane keeps the half of its
+// values whose index has the lane's bit n and hands the other half to its partner; one last add joins lanes l and l ^ 16
+// (16 shuffles instead of 80).  Afterwards v[0] of lane l31 is the total of index l31 & 15.  The order of the additions is fixed.
+__device__ __forceinline__ void gemm_p_rowsum16(float (&v)[16], int l31) {
+#pragma unroll
+    for (int n = 8; n >= 1; n >>= 1) {
+        // (bit selects, not `hi ? v[j + n] : v[j]`: the compiler turns that into a per-lane index into v, a 16-way compare chain)
+        const unsigned hi = (l31 & n) ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+        for (int j = 0; j < n; j++) {
+            const unsigned lo_b = __float_as_uint(v[j]), hi_b = __float_as_uint(v[j + n]);
+            const float keep = __uint_as_float((lo_b & ~hi) | (hi_b & hi)), send = __uint_as_float((hi_b & ~hi) | (lo_b & hi));
+            v[j] = keep + __shfl_xor(send, n, 64);
+        }
+    }
+    v[0] += __shfl_xor(v[0], 16, 64);
+}
 
 template <int PL>
 __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
@@ -461,18 +481,46 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
     float bsj[2];
 #pragma unroll
     for (int jj = 0; jj < 2; jj++) bsj[jj] = a.bias ? a.bias[min(n0 + wn + jj * 32 + l31, a.N - 1)] : 0.0f;
+    // Optional partial statistics of the norm that follows (a.stats, uniform): per row, (sum, sum of squares) of the stored values
+    // over the real columns of this tile.  The ring is free after the barrier: every wave is past its last fragment read and
+    // its last DMA has landed.  The values are summed where they are stored, so the epilogue evaluates every element once.
+    float *red = reinterpret_cast<float *>(gl);
+    if (a.stats) __syncthreads();
+    float tot[4];
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+    for (int g = 0; g < 4; g++) {  // group g: rows r = 8 (g & 1) + {0..7} of M tile i = g >> 1
+        const int i = g >> 1;
+        float v[16];  // [0, 8): sums of the 8 rows over this lane's two columns, [8, 16): sums of squares
 #pragma unroll
-        for (int jj = 0; jj < 2; jj++) {
-            const int n = n0 + wn + jj * 32 + l31;
-            if (n >= a.N) continue;
+        for (int k = 0; k < 8; k++) {
+            const int r = 8 * (g & 1) + k, m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            float ss = 0.0f, qq = 0.0f;
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (m < a.M) a.C[(long)m * a.ldc + n] = conv_act(acc[i][jj][r] + bsj[jj], a.relu);
+            for (int jj = 0; jj < 2; jj++) {
+                const int n = n0 + wn + jj * 32 + l31;
+                if (n >= a.N) continue;
+                const float x = conv_act(acc[i][jj][r] + bsj[jj], a.relu);
+                if (m < a.M) a.C[(long)m * a.ldc + n] = x;
+                ss += x; qq += x * x;
+            }
+            v[k] = ss; v[8 + k] = qq;
+        }
+        if (a.stats) {
+            gemm_p_rowsum16(v, l31);  // lane l31: k = l31 & 7 is the row of the group, bit 3 selects sum / sum of squares
+            tot[g] = v[0];
+            if (wave >= 4) red[((wave & 3) * 4 + g) * 64 + lane] = v[0];
+        }
+    }
+    if (a.stats) {
+        __syncthreads();  // the two N-waves of a row meet through LDS
+        if (wave < 4 && l31 < 16) {
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int r = 8 * (g & 1) + (l31 & 7), m = m0 + wm + (g >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (m < a.M) a.stats[((long)m * a.nct + ct) * 2 + ((l31 >> 3) & 1)] = tot[g] + red[(wave * 4 + g) * 64 + lane];
             }
         }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -85,9 +85,14 @@ void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a) {
     else hipLaunchKernelGGL(k_gln_p<3>, grid, dim3(256), 0, st, a);
 }
 void launch_k_gln2_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a) {
-    if (PL == 1) hipLaunchKernelGGL(k_gln2_p<1>, grid, dim3(1024), 0, st, a);
-    else if (PL == 2) hipLaunchKernelGGL(k_gln2_p<2>, grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL(k_gln2_p<3>, grid, dim3(1024), 0, st, a);
+    if (PL == 1) hipLaunchKernelGGL(k_gln2_p<1>, grid, dim3(256), 0, st, a);
+    else if (PL == 2) hipLaunchKernelGGL(k_gln2_p<2>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_gln2_p<3>, grid, dim3(256), 0, st, a);
+}
+void launch_k_gln2_stream_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a) {
+    if (PL == 1) hipLaunchKernelGGL(k_gln2_stream_p<1>, grid, dim3(1024), 0, st, a);
+    else if (PL == 2) hipLaunchKernelGGL(k_gln2_stream_p<2>, grid, dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL(k_gln2_stream_p<3>, grid, dim3(1024), 0, st, a);
 }
 void launch_k_final_mask_p(dim3 grid, hipStream_t st, const MaskPArgs &a) { hipLaunchKernelGGL(k_final_mask_p<0>, grid, dim3(256), 0, st, a); }
 #endif

@@ -142,6 +142,10 @@ struct se_engine {
     int gemm_p_env = 1;
     DevBuf gruinP[kRing], seqP[4][kRing];  // [PL][B*T][D'] / [PL][B*T][H] bf16 planes
     DevBuf wih_xp;                          // W_ih0 planes with K in the engine's feature order (k_gemm_p)
+    // fc_output_layer + gLN(last) on the plane GEMM route: weight rows, bias and the norm's per-element affine permuted like W_ih0's
+    // K axis, so that fc_out column (o * F + f) * 8 + c holds reference feature (8 o + c) * F + f (channels padded to whole octets
+    // with zero rows); fc_stats [B][T * column tiles][2] = per-row (sum, sum of squares) partials from the GEMM's epilogue
+    DevBuf fcw_xp, fcb_p, gnw_p, gnb_p, fc_stats;
     int dbg_skip = 0;         // SE_DBG_SKIP bit mask, TIMING EXPERIMENTS ONLY (results are wrong): 1 = no GRU step launches, 2 = no bottleneck
                               // GEMMs, 4 = no encoder convolutions, 8 = no decoder
 
@@ -664,7 +668,7 @@ int launch_gemm(se_engine *e, const float *A, long lda, const float *W, long ldw
 
 // C = act(A W^T + bias) with both operands as split-bf16 planes ([PL][rows][K] bf16, K % 32 == 0): k_gemm_p
 int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *bias, float *C, long ldc, int Mr, int Nc, int Kd, int relu,
-                  hipStream_t st, const char *label) {
+                  hipStream_t st, const char *label, float *stats = nullptr) {
     const int PL = operand_planes(e->precision);
     ProfScope ps(e, "k_gemm_p", label, 2.0 * Mr * Nc * Kd, st);
     const int nrt = (Mr + kGemmPBM - 1) / kGemmPBM, nct = (Nc + kGemmPBN - 1) / kGemmPBN;
@@ -688,7 +692,7 @@ int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *b
     // the A planes are laid out for the ALLOCATION batch ([PL][B * T][K]); a ragged call multiplies a prefix of the rows only (Mr = Bact * T)
     const long Ma = std::max<long>(Mr, (long)e->B * e->T);
     GemmPArgs g{reinterpret_cast<const uint4 *>(Ap), reinterpret_cast<const uint4 *>(Wp), Ma * Kd / 8, (long)Nc * Kd / 8, bias, C, Mr, Nc, Kd, ldc, relu,
-                (unsigned)((size_t)PL * Ma * Kd * 2), (unsigned)((size_t)PL * Nc * Kd * 2), nrt, nct, gx, gy};
+                (unsigned)((size_t)PL * Ma * Kd * 2), (unsigned)((size_t)PL * Nc * Kd * 2), nrt, nct, gx, gy, stats};
     const dim3 grid(nblocks);
     const size_t lds = (size_t)2 * 1536 * PL * 16;
     if (PL == 1) hipLaunchKernelGGL(k_gemm_p<1>, grid, dim3(512), lds, st, g);
@@ -855,14 +859,23 @@ int stage_gru_out(se_engine *e, int cur, hipStream_t st) {
     const int Ba = e->Bact;
     (void)B;
     int rc;
-    if (e->dbg_skip & 2) {}
-    else if (e->gemm_p) { if ((rc = launch_gemm_p(e, e->seqP[e->NL - 1][cur].p, e->fcw_x.p, e->fcb.p, e->fc_out.p, D, Ba * T, D, H, e->act, st, "gru_fc"))) return rc; }
-    else if ((rc = launch_gemm(e, e->seqr[e->NL - 1][cur].p, H, e->fcw.p, H, e->fcb.p, e->fc_out.p, D, Ba * T, D, H, e->act, st, "gru_fc", e->fcw_x.p))) return rc;
     // decoder input in the plane layout
-    const int PL = operand_planes(e->precision), C = e->Ch[L], C8 = (C + 7) / 8;
-    ProfScope ps(e, "k_gln2_p", "gln", 0, st);
-    Gln2PArgs g{e->fc_out.p, e->gnw.p, e->gnb.p, decin_p(e, cur), (long)C8 * PL * T * e->F[L], T, e->F[L], C, C8, e->eps_mode};
-    launch_k_gln2_p(PL, dim3(Ba), st, g);
+    const int PL = operand_planes(e->precision), C = e->Ch[L], C8 = (C + 7) / 8, Fl = e->F[L];
+    Gln2PArgs g{e->fc_out.p, e->gnw.p, e->gnb.p, decin_p(e, cur), (long)C8 * PL * T * Fl, T, Fl, C, C8, e->eps_mode, SlabStats{}};
+    if (e->gemm_p) {  // octet-interleaved columns, statistics from the GEMM's epilogue, full-chip one-pass norm
+        const int ND = C8 * Fl * 8, nct = (ND + kGemmPBN - 1) / kGemmPBN;
+        if (!(e->dbg_skip & 2) && (rc = launch_gemm_p(e, e->seqP[e->NL - 1][cur].p, e->fcw_xp.p, e->fcb_p.p, e->fc_out.p, ND, Ba * T, ND, H, e->act, st, "gru_fc", e->fc_stats.p))) return rc;
+        ProfScope ps(e, "k_gln2_p", "gln_fc", 0, st);  // (records are keyed by label: its own, not the conv norms' "gln")
+        g.w = e->gnw_p.p; g.b = e->gnb_p.p;
+        g.st = SlabStats{e->fc_stats.p, T * nct, (long)T * C * Fl, e->eps_mode};
+        launch_k_gln2_p(PL, dim3((T * Fl + 1023) / 1024, C8, Ba), st, g);
+        HIPCHECK(e, hipGetLastError());
+        return 0;
+    }
+    // fp32 GEMM route (few rows): the reference's column order, two-pass statistics in the norm kernel
+    if (!(e->dbg_skip & 2) && (rc = launch_gemm(e, e->seqr[e->NL - 1][cur].p, H, e->fcw.p, H, e->fcb.p, e->fc_out.p, D, Ba * T, D, H, e->act, st, "gru_fc", e->fcw_x.p))) return rc;
+    ProfScope ps(e, "k_gln2_stream_p", "gln_fc_stream", 0, st);
+    launch_k_gln2_stream_p(PL, dim3(Ba), st, g);
     HIPCHECK(e, hipGetLastError());
     return 0;
 }
@@ -955,6 +968,22 @@ int ensure_ready(se_engine *e) {
                     wp[(size_t)r * D + ((size_t)(cabs >> 3) * Fl + f) * 8 + (cabs & 7)] = w[(size_t)r * D + d];
                 }
             if ((rc = upload_split3(e, e->wih_xp, wp))) return rc;
+            // fc_output_layer rows, its bias and the affine of the norm behind it in the same order (each dot product is unchanged;
+            // only where it lands changes), channels padded to whole octets with zero rows.  (gemm_p_cap above asks for whole
+            // octets, so today ND == D and no padding row exists; the padding is what a relaxed cap would need, and is untested)
+            const int Cl = e->Ch[e->L], ND = (Cl + 7) / 8 * Fl * 8;
+            const std::vector<float> &fw = e->params["gru.fc_output_layer.weight"], &fb = e->params["gru.fc_output_layer.bias"];
+            const std::vector<float> &nw = e->params["gru.norm.weight"], &nb = e->params["gru.norm.bias"];
+            std::vector<float> fwp((size_t)ND * H, 0.0f), fbp(ND, 0.0f), nwp(ND, 0.0f), nbp(ND, 0.0f);
+            for (int d = 0; d < D; d++) {
+                const int cabs = d / Fl, f = d - cabs * Fl;
+                const size_t dp = ((size_t)(cabs >> 3) * Fl + f) * 8 + (cabs & 7);
+                std::copy(fw.begin() + (size_t)d * H, fw.begin() + (size_t)(d + 1) * H, fwp.begin() + dp * H);
+                fbp[dp] = fb[d]; nwp[dp] = nw[d]; nbp[dp] = nb[d];
+            }
+            if ((rc = upload_split3(e, e->fcw_xp, fwp)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
+                (rc = dev_upload(e, e->gnb_p, nbp)))
+                return rc;
         }
         if (e->B > 0) select_all_p(e);
     }
@@ -1120,7 +1149,7 @@ void se_destroy(se_engine *e) {
     g_cp_trace_sites.dump();
 #endif
     DevBuf *singles[] = {&e->window, &e->env, &e->tw, &e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
-                         &e->fcw_x, &e->wih_xp, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
+                         &e->fcw_x, &e->wih_xp, &e->fcw_xp, &e->fcb_p, &e->gnw_p, &e->gnb_p, &e->fc_stats, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
     for (DevBuf *b : singles) dev_free(*b);
     for (int r = 0; r < kRing; r++) {
         dev_free(e->spec[r]); dev_free(e->gru_in[r]); dev_free(e->dec_in[r]); dev_free(e->gi0[r]); dev_free(e->gruinP[r]);
@@ -1220,7 +1249,9 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
         if ((rc = dev_alloc(e, e->pre_stats[i], (size_t)B * 2 * (e->lv[i].pre.grid_x + 1)))) return rc;
         if ((rc = dev_alloc(e, e->pre_g, nf))) return rc;
     }
-    if ((rc = dev_alloc(e, e->fc_out, (size_t)B * T * D))) return rc;
+    const size_t fcND = (size_t)(e->Ch[L] + 7) / 8 * e->F[L] * 8;  // fc output columns on the plane GEMM route (channels in whole octets)
+    if ((rc = dev_alloc(e, e->fc_out, (size_t)B * T * std::max<size_t>(D, fcND)))) return rc;
+    if (e->gemm_p && (rc = dev_alloc(e, e->fc_stats, (size_t)B * T * ((fcND + kGemmPBN - 1) / kGemmPBN) * 2))) return rc;
     for (int r = 0; r < kRing; r++) {
         if ((rc = dev_alloc(e, e->gi0[r], (size_t)B * T * 3 * H))) return rc;
         for (int l = 0; l < e->NL; l++)
