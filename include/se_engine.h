@@ -98,9 +98,29 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
  * of streams that still take part in it only - every layout is stream-major, so nothing moves; grids, GEMM rows and recurrence rows
  * shrink (plane path, CRN.py variant, batches on the plane-GEMM route; SE_RAGGED_COMPACT=0 turns it off).  With unsorted lengths every
  * stream runs every segment.  Either way the carried state of a stream that ended early is not a continuation state: follow with
- * flag = 0, or se_reset_stream, for those streams. */
+ * flag = 0, or se_reset_stream, for those streams - or use se_realtime_process_chains below, which leaves every stream its own state. */
 int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, int flag, float *out,
                                void *stream);
+
+/* A batch of chunk CHAINS (the reference continues every stream of its chunk chain, CRN.py:568-575, data_c.py:60-84, 155-173): B callers,
+ * each with its own chunk length and its own flag, in one call.  lengths and flags are HOST arrays of `batch` entries.
+ *  - stream b is mixture[b, :, :lengths[b]] and ZERO beyond, whatever the padding holds; 0 < lengths[b] <= max_length.
+ *  - flags[b] == 0: stream b starts from zero state, gets the K/2 left pad and has it stripped again (first segment at -K);
+ *    flags[b] != 0: it continues row b of the carried state, no pad (first segment at -K/2).
+ *  - a call with any flag set needs a carried batch of the same size (SE_ERR_STATE otherwise); with all flags zero the batch size may
+ *    change, like flag = 0 of se_realtime_process.
+ *  - out[b, lengths[b]:] = 0.
+ *  - afterwards the state of EVERY stream (conv time buffers of every encoder level, the preconv buffers of variants 1 / 2, GRU h of
+ *    every layer) is what that stream alone would carry after its own last segment: the state se_export_state, se_step,
+ *    se_reset_stream and a following se_realtime_process* call see.  A chains call with a new caller's flag at 0 therefore replaces
+ *    se_reset_stream + se_realtime_process_ragged, and no stream has to wait for the longest one.
+ * Every stream keeps the segment geometry it has alone (utility.py:327-329, 360-368 with lead = flags[b] ? 0 : K/2); the call runs
+ * max_b N_b segments.  The state of a stream is saved when its last segment has passed a stage (encoder rows on the encoder's stream,
+ * layer l's h after layer l) and written back when the call ends; a reset among continuing streams zeroes that stream's rows at
+ * entry.  Prefix compaction as in se_realtime_process_ragged, when the segment counts N_b are non-increasing.  A uniform batch (equal
+ * flags, every length == max_length) is exactly se_realtime_process: no save, no restore, no extra launch. */
+int se_realtime_process_chains(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host,
+                               const uint8_t *flags_host, float *out, void *stream);
 
 /* Per-stage entry points (parity tests; same arithmetic as inside se_step).
  * se_stft:    stft_trans  (CRN.py:505-512): seg [n, K] -> spec [n, F, T, 2]   (n = B*M rows)
@@ -142,7 +162,8 @@ int se_profile_read(se_engine *e, int index, char *kernel, char *label, int cap,
 int se_abi_version(void);  /* 5: the first-generation training entry points are gone (se_train_conv_w, se_train_conv_wgrad_det and
                               se_train_gemm_tn_det are the only convolution / weight-gradient forms);
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
-                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward) */
+                              additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
+                              addition at 5: se_realtime_process_chains */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);

@@ -151,9 +151,14 @@ class TemporalCRN(nn.Module):
 
     def realtime_process(self, mixture, flag=False, lengths=None):
         """lengths: extension over the reference - a ragged batch (zero-padded to the longest utterance): every stream is processed as if
-        alone with its own length (own padding; zeros beyond its length in the output)."""
+        alone with its own length (own padding; zeros beyond its length in the output).
+        flag: a bool or a one-element tensor (the reference trainer's flag) for the whole batch; a sequence or tensor with one value per
+        stream makes the call a batch of chunk chains (Engine.realtime_process_chains): stream b continues its own state where flag[b] is
+        set, starts afresh where it is not, and every stream leaves the state it would carry alone."""
         eng = self._engine_for(mixture)
-        return eng.realtime_process(mixture.contiguous().float(), flag=bool(flag), lengths=lengths)
+        if not isinstance(flag, (torch.Tensor, list, tuple)):
+            flag = bool(flag)
+        return eng.realtime_process(mixture.contiguous().float(), flag=flag, lengths=lengths)
 
     def compute_loss(self, source, pred_source, length):
         """loss = 0.7 * stoi_loss + 0.3 * (-SI-SNR), NaN -> zeros  (CRN.py:593-617); returns (loss, stoi, sisnr) on the

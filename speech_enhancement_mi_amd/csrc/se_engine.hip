@@ -32,6 +32,7 @@
 #include "gemm.hip.h"
 #include "norm.hip.h"
 #include "stft.hip.h"
+#include "state_rows.hip.h"
 
 using namespace se;
 
@@ -121,7 +122,18 @@ struct se_engine {
     DevBuf pin[3][2], pre_g, pre_stats[3];  // CRN_ELU preconv chain (inputs ping-ponged: they carry 4 history columns)
     DevBuf yseg;
     DevBuf ragged_len;       // se_realtime_process_ragged: per-stream lengths (int64) on the device
-    bool ragged_on = false;
+    // per-stream geometry of the running call (device int64 [B]; null outside a ragged / chains call): valid samples, first-segment
+    // offset, strip of the overlap-average
+    const long *row_len = nullptr, *row_off = nullptr, *row_skip = nullptr;
+    // se_realtime_process_chains (state_rows.hip.h).  chain_dev: int64 len[B] | off0[B] | skip[B], then int: the streams by ascending
+    // segment count [B] | the streams with flag 0 [B].  carry_*: one row per stream in the live tensors' row layout, filled when a
+    // stream's last segment has passed the stage that owns the tensor, written back at call exit.
+    DevBuf chain_dev, carry_x[SE_MAX_LEVELS], carry_p[3], carry_h[4];
+    bool chain_on = false;         // some stream ends before the longest one: save / restore is live
+    int chain_nseg = 0;            // N = segments of the longest stream
+    const int *chain_sorted = nullptr;  // device: streams by ascending segment count
+    std::vector<int> chain_le;     // chain_le[k] = streams with at most k segments, k = 0 .. N: those whose last segment is n are
+                                   // positions [chain_le[n], chain_le[n + 1]) of chain_sorted
     // Prefix compaction of a ragged batch: every layout is stream-major, so when the lengths are non-increasing the streams that still take
     // part in segment n are a PREFIX of the batch and every launch of that segment simply covers Bact < B streams (grids, GEMM rows, GRU
     // rows); strides and plane sizes stay those of the allocation batch B.  Bact is set per stage call by se_realtime_process.
@@ -923,7 +935,7 @@ int launch_stft(se_engine *e, const float *src, long strideB, long strideM, int 
     a.K = e->K; a.T = e->T; a.F = e->F[0]; a.hop = e->c.hop;
     a.spec = spec; a.sR = sR; a.sT = sT; a.sF = sF;
     a.window = e->window.p; a.tw = reinterpret_cast<const cf2 *>(e->tw.p); a.plan = e->plan;
-    a.Lrow = e->ragged_on ? reinterpret_cast<const long *>(e->ragged_len.p) : nullptr;
+    a.Lrow = e->row_len; a.offrow = e->row_off;  // chains: `off` then counts from every stream's own first segment
     ProfScope ps(e, "k_stft", "stft", 0, st);
     launch_k_stft(dim3(rows, nseg), stft_lds_bytes(e->K, e->N), st, a);
     HIPCHECK(e, hipGetLastError());
@@ -1151,6 +1163,10 @@ void se_destroy(se_engine *e) {
     DevBuf *singles[] = {&e->window, &e->env, &e->tw, &e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
                          &e->fcw_x, &e->wih_xp, &e->fcw_xp, &e->fcb_p, &e->gnw_p, &e->gnb_p, &e->fc_stats, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
     for (DevBuf *b : singles) dev_free(*b);
+    dev_free(e->ragged_len); dev_free(e->chain_dev);
+    for (DevBuf &b : e->carry_x) dev_free(b);
+    for (DevBuf &b : e->carry_p) dev_free(b);
+    for (DevBuf &b : e->carry_h) dev_free(b);
     for (int r = 0; r < kRing; r++) {
         dev_free(e->spec[r]); dev_free(e->gru_in[r]); dev_free(e->dec_in[r]); dev_free(e->gi0[r]); dev_free(e->gruinP[r]);
         for (int l = 0; l < 4; l++) dev_free(e->seqP[l][r]);
@@ -1373,6 +1389,67 @@ int se_step(se_engine *e, const float *wav_in, float *wav_out, void *stream) {
     return step_dev(e, wav_in, (long)e->M * e->K, e->K, 0, e->K, wav_out, e->K, static_cast<hipStream_t>(stream));
 }
 
+// ---- per-stream state rows (state_rows.hip.h): the live tensors a stream's carried state lives in, as table entries ----
+// which: bit 0 = encoder rows (conv history of every level + preconv history) in ring slot e->slot / parity e->parity, bit (1 + l) = h of
+// GRU layer l in its current half.  dir 0: live -> carry (save), 1: carry -> live (restore), 2: zeros -> live.
+static int chain_rows(se_engine *e, unsigned which, int dir, const int *streams, int nstreams, hipStream_t st) {
+    if (nstreams <= 0) return 0;
+    StateRowTable t{};
+    int n = 0;
+    long wmax = 0;
+    auto add = [&](float *live, float *carry, long words) {
+        StateRow &r = t.r[n++];
+        r.src = reinterpret_cast<const uint32_t *>(dir == 0 ? live : dir == 1 ? carry : nullptr);
+        r.dst = reinterpret_cast<uint32_t *>(dir == 0 ? carry : live);
+        r.words = words;
+        wmax = std::max(wmax, words);
+    };
+    static_assert(SE_MAX_LEVELS + 3 + 4 <= kStateRowsMax, "state row table too small");
+    if (which & 1u) {
+        for (int i = 0; i < e->L; i++) {  // [slot][b][C8][PL][T][F] pieces of 16 bytes
+            const long per16 = e->cp->slot_elems[i] / e->B;
+            add(e->cp->xinP[i].p + (size_t)e->slot * e->cp->slot_elems[i] * 4, e->carry_x[i].p, per16 * 4);
+        }
+        for (int i = 0; i < e->npre; i++) {
+            if (e->cp->pre_p) {
+                const long per16 = e->cp->pslot_elems / e->B;
+                add(e->cp->pinP[i].p + (size_t)e->slot * e->cp->pslot_elems * 4, e->carry_p[i].p, per16 * 4);
+            } else {
+                add(e->pin[i][e->parity].p, e->carry_p[i].p, (long)e->Ch[0] * e->T * e->F[0]);
+            }
+        }
+    }
+    for (int l = 0; l < e->NL; l++)
+        if (which & (2u << l)) add(e->hbuf[l][e->hcur[l]].p, e->carry_h[l].p, e->H);
+    ProfScope ps(e, "k_state_rows", dir == 0 ? "state_save" : dir == 1 ? "state_restore" : "state_zero", 0, st);
+    launch_k_state_rows(st, t, n, streams, nstreams, wmax);
+    HIPCHECK(e, hipGetLastError());
+    return 0;
+}
+
+// the streams whose LAST segment is n keep what the stage(s) in `which` have just left behind (nothing when no stream ends there, or
+// when n is the last segment of the call: those streams' state is already where it belongs)
+static int chain_save(se_engine *e, long n, unsigned which, hipStream_t st) {
+    if (!e->chain_on || n + 1 >= e->chain_nseg) return 0;
+    const int lo = e->chain_le[n], hi = e->chain_le[n + 1];
+    return chain_rows(e, which, 0, e->chain_sorted + lo, hi - lo, st);
+}
+
+static int alloc_carry(se_engine *e) {
+    int rc;
+    for (int i = 0; i < e->L; i++)
+        if ((rc = dev_alloc(e, e->carry_x[i], (size_t)e->cp->slot_elems[i] * 4))) return rc;
+    for (int i = 0; i < e->npre; i++)
+        if ((rc = dev_alloc(e, e->carry_p[i], e->cp->pre_p ? (size_t)e->cp->pslot_elems * 4 : (size_t)e->B * e->Ch[0] * e->T * e->F[0]))) return rc;
+    for (int l = 0; l < e->NL; l++)
+        if ((rc = dev_alloc(e, e->carry_h[l], (size_t)e->B * e->H))) return rc;
+    return 0;
+}
+
+// The segments of one realtime_process call on state that is ready: Nseg half-overlapping windows, window n of a stream starting at
+// off_first + n * K/2 (+ the stream's own e->row_off), overlap-average with `skip` (or e->row_skip) stripped -> out [batch, length].
+static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st);
+
 int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
     if (!e || !mixture || !out || batch <= 0 || length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     int rc;
@@ -1382,12 +1459,18 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
         if (e->B != batch) return fail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
         if ((rc = ensure_ready(e))) return rc;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const long K = e->K, P = K / 2;
     const long lead = flag ? 0 : P;                      // CRN.py:568-570
     const long Lp = length + lead;
     const long gap = K - (P + Lp % K) % K;               // utility.py:327-329
     const long Nseg = 2 * (Lp + gap + P) / K;            // utility.py:360-368
+    // segment n covers padded[n*P, n*P+K) with padded = [0]*P | [0]*lead | x | zeros; the strip is the lead (CRN.py:587-588)
+    return run_segments(e, mixture, batch, length, Nseg, -P - lead, lead, out, static_cast<hipStream_t>(stream));
+}
+
+static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st) {
+    int rc;
+    const long K = e->K, P = K / 2;
     if ((rc = dev_alloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
     bool piped = e->pipeline && !e->prof_on && Nseg > 1;
     if (piped && ensure_stage_streams(e)) {  // no extra streams / events available: fall back to the caller's stream for good
@@ -1406,11 +1489,11 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
     struct RestoreBact { se_engine *e; ~RestoreBact() { e->Bact = e->B; for (int &v : e->bact_slot) v = e->B; } } restore_bact{e};
     if (!piped) {
         for (long n = 0; n < Nseg; n++) {
-            // segment n covers padded[n*P, n*P+K) with padded = [0]*P | [0]*lead | x | zeros
-            const long off = n * P - P - lead;
+            const long off = off_first + n * P;
             e->Bact = bact_of(n);
             // yseg is [B][Nseg][K]: the iSTFT writes segment n of every stream with row stride Nseg*K
             if ((rc = step_dev(e, mixture, (long)e->M * length, length, off, length, e->yseg.p + n * K, Nseg * K, st))) return rc;
+            if ((rc = chain_save(e, n, ~0u, st))) return rc;
         }
     } else {
         // Segments are sequentially dependent only WITHIN a stage (conv history, GRU state), so the three stages run as a
@@ -1441,12 +1524,13 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
                     const cf2 *spec = reinterpret_cast<const cf2 *>(e->spec_all.p + spec_n * i);
                     if (i % kFftSub == 0) {
                         const long ns = std::min<long>(kFftSub, cn - i);
-                        if ((rc = launch_stft(e, mixture, (long)e->M * length, length, (int)M, (c0 + i) * P - P - lead, length, e->Bact * (int)M,
+                        if ((rc = launch_stft(e, mixture, (long)e->M * length, length, (int)M, off_first + (c0 + i) * P, length, e->Bact * (int)M,
                                               reinterpret_cast<cf2 *>(e->spec_all.p + spec_n * i), T * F, F, 1, sE, (int)ns, P, (long)(spec_n / 2)))) return rc;
                     }
                     if (i >= kRing) HIPCHECK(e, hipStreamWaitEvent(sE, e->ev_dec[cur], 0));  // slot cur was last read by the decoder of segment i - kRing
                     if ((rc = run_encoder(e, cur, prev, spec, M * T * F, T * F, F, 1, sE))) return rc;
                     if ((rc = stage_gru_proj0(e, cur, sE))) return rc;
+                    if ((rc = chain_save(e, c0 + i, 1u, sE))) return rc;  // before the encoder stream reuses the slot, kRing segments on
                     HIPCHECK(e, hipEventRecord(e->ev_enc[cur], sE));
                     HIPCHECK(e, hipStreamWaitEvent(sG, e->ev_enc[cur], 0));
                 }
@@ -1457,11 +1541,14 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
                     for (int l = 0; l < NL; l++)
                         if (i - l >= 0 && i - l < cn) slots[l] = slot_of(i - l);
                     if ((rc = stage_gru_round(e, slots, sG))) return rc;
+                    for (int l = 0; l < NL; l++)  // layer l has just finished segment i - l
+                        if (slots[l] >= 0 && (rc = chain_save(e, c0 + i - l, 2u << l, sG))) return rc;
                     done = i - (NL - 1);
                 } else {
                     e->Bact = e->bact_slot[slot_of(i)];
                     for (int l = 0; l < NL; l++)
                         if ((rc = stage_gru_layer(e, l, slot_of(i), sG, /*overlapped=*/true))) return rc;
+                    if ((rc = chain_save(e, c0 + i, ~1u, sG))) return rc;
                     done = i;
                 }
                 if (done < 0 || done >= cn) continue;
@@ -1487,9 +1574,9 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
             }
         }
     }
-    const long skip = lead;  // CRN.py:587-588
-    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip,
-                         e->ragged_on ? reinterpret_cast<const long *>(e->ragged_len.p) : nullptr);
+    // the streams that ended before the longest one get their own state back (the stage streams have joined `st`)
+    if (e->chain_on && (rc = chain_rows(e, ~0u, 1, e->chain_sorted, e->chain_le[Nseg - 1], st))) return rc;
+    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, e->row_len, e->row_skip);
     HIPCHECK(e, hipGetLastError());
     return SE_OK;
 }
@@ -1516,11 +1603,75 @@ int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, in
             e->ragged_nseg.push_back((int)(2 * (Lp + gap + P) / K));
         }
     }
-    e->ragged_on = true;
+    e->row_len = reinterpret_cast<const long *>(e->ragged_len.p);
     rc = se_realtime_process(e, mixture, batch, max_length, flag, out, stream);
-    e->ragged_on = false;
+    e->row_len = nullptr;
     e->ragged_nseg.clear();
     return rc;
+}
+
+int se_realtime_process_chains(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host,
+                               const uint8_t *flags_host, float *out, void *stream) {
+    if (!e || !mixture || !out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
+    bool any = false, all = true, full = true;
+    for (int b = 0; b < batch; b++) {
+        if (lengths_host[b] <= 0 || lengths_host[b] > max_length) return fail(e, SE_ERR_ARG, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths_host[b], (long long)max_length);
+        any = any || flags_host[b];
+        all = all && flags_host[b];
+        full = full && lengths_host[b] == max_length;
+    }
+    if (any && e->B <= 0) return fail(e, SE_ERR_STATE, "a stream continues (flag set) but the engine carries no state");
+    if (any && e->B != batch) return fail(e, SE_ERR_STATE, "a stream continues (flag set) in a batch of %d but the carried state holds %d streams", batch, e->B);
+    if (full && (all || !any)) return se_realtime_process(e, mixture, batch, max_length, all ? 1 : 0, out, stream);  // a uniform batch
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    if (!any) rc = reset_on_stream(e, batch, st);
+    else rc = ensure_ready(e);
+    if (rc) return rc;
+    // every stream keeps the geometry it has alone (utility.py:327-329, 360-368 with its own lead)
+    const long K = e->K, P = K / 2;
+    const int B = batch;
+    std::vector<int64_t> geo((size_t)4 * B);  // len | off0 | skip | (int) sorted streams, flag-0 streams: one upload
+    std::vector<int> nb(B), idx((size_t)2 * B, 0);
+    int N = 0, nzero = 0;
+    for (int b = 0; b < B; b++) {
+        const long lead = flags_host[b] ? 0 : P, Lp = lengths_host[b] + lead, gap = K - (P + Lp % K) % K;
+        nb[b] = (int)(2 * (Lp + gap + P) / K);
+        N = std::max(N, nb[b]);
+        geo[b] = lengths_host[b];
+        geo[(size_t)B + b] = -P - lead;
+        geo[2 * (size_t)B + b] = lead;
+        idx[b] = b;
+        if (!flags_host[b]) idx[B + nzero++] = b;
+    }
+    std::stable_sort(idx.begin(), idx.begin() + B, [&](int a, int b) { return nb[a] < nb[b]; });
+    memcpy(geo.data() + 3 * (size_t)B, idx.data(), (size_t)2 * B * sizeof(int));
+    e->chain_le.assign((size_t)N + 1, 0);
+    for (int b = 0; b < B; b++) e->chain_le[nb[b]]++;
+    for (int k = 1; k <= N; k++) e->chain_le[k] += e->chain_le[k - 1];
+    if ((rc = dev_alloc(e, e->chain_dev, (size_t)8 * B)) || (rc = alloc_carry(e))) return rc;
+    static_assert(sizeof(long) == sizeof(int64_t), "per-stream geometry is passed to the kernels as long");
+    HIPCHECK(e, hipMemcpyAsync(e->chain_dev.p, geo.data(), (size_t)4 * B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(e, hipStreamSynchronize(st));  // the staging vector and the host arrays live for the call only
+    const long *dev64 = reinterpret_cast<const long *>(e->chain_dev.p);
+    const int *dev32 = reinterpret_cast<const int *>(dev64 + 3 * (size_t)B);
+    // a reset among continuing streams: zero those streams' rows (se_reset_stream for any number of streams in one launch)
+    if (any && (rc = chain_rows(e, ~0u, 2, dev32 + B, nzero, st))) return rc;
+    struct Scope {
+        se_engine *e;
+        ~Scope() { e->row_len = e->row_off = e->row_skip = nullptr; e->chain_on = false; e->chain_sorted = nullptr; e->ragged_nseg.clear(); }
+    } scope{e};
+    e->row_len = dev64; e->row_off = dev64 + B; e->row_skip = dev64 + 2 * (size_t)B;
+    e->chain_sorted = dev32;
+    e->chain_nseg = N;
+    e->chain_on = e->chain_le[N - 1] > 0;
+    // prefix compaction: the streams still running in segment n are a prefix of the batch when the SEGMENT COUNTS are non-increasing (a
+    // reset stream has one lead more than a continuing one); the streams beyond the prefix are exactly those whose rows were saved
+    bool sorted = true;
+    for (int b = 1; b < B; b++) sorted = sorted && nb[b] <= nb[b - 1];
+    e->ragged_nseg.clear();
+    if (sorted) e->ragged_nseg = nb;
+    return run_segments(e, mixture, batch, max_length, N, 0, 0, out, st);
 }
 
 static int copy_out(se_engine *e, const float *dev, size_t n, float *host, int64_t cap, int64_t *count, hipStream_t st) {

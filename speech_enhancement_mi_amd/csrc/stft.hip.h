@@ -55,7 +55,8 @@ struct StftArgs {
     FftPlan plan;
     long seg_off, seg_spec;  // blockIdx.y = segment of a batch of segments: off += y*seg_off, spec += y*seg_spec
     const long *Lrow;        // optional per-stream lengths [rows / M] (ragged batches): samples beyond a stream's own length read as zeros
-    const long *offrow;      // optional per-stream first-segment offsets [rows / M], in place of `off` (se_sig_stft_rows)
+    const long *offrow;      // optional per-stream first-segment offsets [rows / M], added to `off` (se_sig_stft_rows: off = 0;
+                             // se_realtime_process_chains: off = the segment's distance from every stream's own first segment)
 };
 
 // LDS: sig[K+N] | win[N] | tw[N] (cf2) | bufA[kFftBatch*N/2] | bufB[kFftBatch*N/2]
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void k_stft(StftArgs a) {
     cf2 *bufB = bufA + kFftBatch * N2;
     const int row = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
     const float *src = a.src + (long)(row / a.M) * a.strideB + (long)(row % a.M) * a.strideM;
-    const long seg_first = (a.offrow ? a.offrow[row / a.M] : a.off) + (long)blockIdx.y * a.seg_off;
+    const long seg_first = (a.offrow ? a.offrow[row / a.M] + a.off : a.off) + (long)blockIdx.y * a.seg_off;
     cf2 *spec_out = a.spec + (long)blockIdx.y * a.seg_spec;
     const long Lr = a.Lrow ? min(a.Lrow[row / a.M], a.L) : a.L;
     for (int i = tid; i < K + N; i += nth) {
@@ -167,14 +168,15 @@ __global__ __launch_bounds__(256) void k_istft(IstftArgs a) {
 }
 
 // utility.over_add on the engine's segment outputs (utility.py:373-403) + the K/2 strip of
-// realtime_process (CRN.py:587-588).  yseg [B, Nseg, K] -> out [B, L].
-__global__ void k_overlap_avg(const float *yseg, float *out, int Nseg, int K, long L, long skip, const long *Lrow) {
+// realtime_process (CRN.py:587-588).  yseg [B, Nseg, K] -> out [B, L].  skiprow (optional, [B]): per-stream strip in place of `skip`
+// (a batch of chunk chains: K/2 for a stream that was reset, 0 for one that continues); stream b then reads its own segments only.
+__global__ void k_overlap_avg(const float *yseg, float *out, int Nseg, int K, long L, long skip, const long *Lrow, const long *skiprow) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (i >= L) return;
     if (Lrow && i >= Lrow[b]) { out[(long)b * L + i] = 0.0f; return; }  // ragged batch: nothing beyond the stream's own length
     const long P = K / 2;
-    const long i2 = i + skip, i1 = i2 + P;
+    const long i2 = i + (skiprow ? skiprow[b] : skip), i1 = i2 + P;
     const float *y = yseg + (long)b * Nseg * K;
     const float v1 = y[(2 * (i1 / K)) * K + i1 % K];
     const float v2 = y[(2 * (i2 / K) + 1) * K + i2 % K];
@@ -186,7 +188,8 @@ __global__ void k_overlap_avg(const float *yseg, float *out, int Nseg, int K, lo
 // host-side launchers, defined in se_aux.hip
 void launch_k_stft(dim3 grid, size_t lds, hipStream_t st, const StftArgs &a);
 void launch_k_istft(dim3 grid, size_t lds, hipStream_t st, const IstftArgs &a);
-void launch_k_overlap_avg(dim3 grid, hipStream_t st, const float *yseg, float *out, int Nseg, int K, long L, long skip, const long *Lrow = nullptr);
+void launch_k_overlap_avg(dim3 grid, hipStream_t st, const float *yseg, float *out, int Nseg, int K, long L, long skip, const long *Lrow = nullptr,
+                          const long *skiprow = nullptr);
 void aux_set_fft_lds(int stft_bytes, int istft_bytes);
 
 }  // namespace se

@@ -18,7 +18,7 @@ SE_MAX_LEVELS = 8
 
 EXPORTS = [
     "se_abi_version", "se_config_size", "fsn_config_size", "se_create", "se_destroy", "se_last_error", "se_load_param", "se_reset", "se_reset_stream", "se_step",
-    "se_realtime_process", "se_realtime_process_ragged", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
+    "se_realtime_process", "se_realtime_process_ragged", "se_realtime_process_chains", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
     "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
     "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
@@ -79,6 +79,7 @@ def load_library():
     L.se_step.argtypes = [vp, fp, fp, vp]
     L.se_realtime_process.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, fp, vp]
     L.se_realtime_process_ragged.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.c_int, fp, vp]
+    L.se_realtime_process_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), fp, vp]
     L.se_stft.argtypes = [vp, fp, C.c_int, fp, vp]
     L.se_istft.argtypes = [vp, fp, C.c_int, fp, vp]
     L.se_forward.argtypes = [vp, fp, fp, vp]
@@ -192,8 +193,45 @@ def make_config(num_channels, num_freqs, hidden, segment_length, num_layers=1, n
     return cfg
 
 
+def chain_geometry(lengths, flags, segment_length):
+    """Per-stream segment geometry of one se_realtime_process_chains call (utility.py:327-329, 360-368 per stream, with
+    lead = 0 for a stream that continues and K/2 for one that is reset): Nb[b] segments, the first one starting at sample off0[b] of the
+    stream, skip[b] samples stripped from its overlap-average; the call runs N = max Nb segments.  Pure Python: what the engine computes
+    on the host, and what train_stages.ragged_geometry gives for the training side."""
+    K = int(segment_length)
+    P = K // 2
+    Nb, off0, skip = [], [], []
+    for L, f in zip(lengths, flags):
+        lead = 0 if f else P
+        Lp = int(L) + lead
+        gap = K - (P + Lp % K) % K
+        Nb.append(2 * (Lp + gap + P) // K)
+        off0.append(-P - lead)
+        skip.append(lead)
+    return dict(Nb=Nb, off0=off0, skip=skip, N=max(Nb) if Nb else 0)
+
+
+def _flags_of(flag, B):
+    """The flag argument of realtime_process: a bool or ONE value (the reference trainer's flag tensor) -> a bool; a sequence or tensor
+    with one value per stream -> a list of B bools (the convention of train_stages._as_flags)."""
+    if hasattr(flag, "reshape") and hasattr(flag, "tolist"):
+        flag = flag.reshape(-1).tolist()
+    if isinstance(flag, (list, tuple)):
+        if len(flag) == 1:
+            return bool(flag[0])
+        if len(flag) != B:
+            raise RuntimeError(f"{len(flag)} flags for a batch of {B}")
+        return [bool(f) for f in flag]
+    return bool(flag)
+
+
 class Engine:
-    """Thin RAII wrapper over one se_engine handle.  All tensor arguments are CUDA(HIP) torch tensors."""
+    """Thin RAII wrapper over one se_engine handle.  All tensor arguments are CUDA(HIP) torch tensors.
+
+    Slot map: realtime_process_chains sorts a FRESH batch (all flags 0) by segment count, so that the engine can launch every segment
+    for the prefix of streams still running only.  The permutation stays with the engine (self._order[slot] = caller row) for as long as
+    that batch is carried: later chains calls, a scalar flag=True call, reset_stream and export_state / import_state all address the
+    caller's row b, which is always the same stream.  reset() and every call that starts a fresh batch drop or replace the map."""
 
     def __init__(self, cfg: SeConfig, device: int = 0):
         self.lib = load_library()
@@ -207,6 +245,8 @@ class Engine:
         self.T = self.lib.se_frames_per_segment(h)
         self.F, self.M, self.K = cfg.num_freqs, cfg.num_inputs, cfg.segment_length
         self.batch = 0
+        self._order = None      # slot map of the carried batch: _order[slot] = caller row (None: caller row b is engine row b)
+        self._order_idx = None  # the same as an int64 device tensor
 
     def close(self):
         if getattr(self, "_h", None):
@@ -246,9 +286,12 @@ class Engine:
     def reset(self, batch: int):
         self._check(self.lib.se_reset(self._h, int(batch)))
         self.batch = int(batch)
+        self._order = self._order_idx = None
 
     def reset_stream(self, index: int):
         """Zero the state of ONE stream of the batch (a new caller takes the slot); the others keep streaming."""
+        if self._order is not None and 0 <= int(index) < len(self._order):
+            index = self._order.index(int(index))
         self._check(self.lib.se_reset_stream(self._h, int(index), self._stream()))
 
     def step(self, wav_in, wav_out=None):
@@ -260,13 +303,22 @@ class Engine:
         return wav_out
 
     def realtime_process(self, mixture, flag=False, out=None, lengths=None):
-        """lengths (optional, [B] ints <= L): ragged batch - every stream is processed as if alone with its own length."""
+        """lengths (optional, [B] ints <= L): ragged batch - every stream is processed as if alone with its own length.
+        flag: a bool (or one value) for the whole batch, or one value per stream: a batch of chunk chains (realtime_process_chains)."""
         import torch
         B, M, L = mixture.shape
         if M != self.M:
             raise RuntimeError(f"expected {self.M} microphones, got {M}")
+        flag = _flags_of(flag, B)
+        if isinstance(flag, list):
+            return self.realtime_process_chains(mixture, flag, lengths, out=out)
+        if flag and self._order is not None and len(self._order) == B:
+            # the carried batch was permuted by a chains call: keep the caller's row b on its stream
+            return self.realtime_process_chains(mixture, [True] * B, lengths, out=out)
         if out is None:
             out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
+        if not flag:
+            self._order = self._order_idx = None
         if lengths is not None:
             ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
             if len(ln) != B:
@@ -291,6 +343,60 @@ class Engine:
         self._check(self.lib.se_realtime_process(self._h, self._dev(mixture), B, L, int(bool(flag)), self._dev(out, (B, L)), self._stream()))
         self.batch = B
         return out
+
+    def realtime_process_chains(self, mixture, flags, lengths=None, out=None):
+        """A batch of chunk chains (se_realtime_process_chains): mixture [B, M, L]; stream b is mixture[b, :, :lengths[b]], continues its
+        carried state where flags[b] is set and starts from zero state (K/2 left pad, stripped again) where it is not; every stream leaves
+        the state it would carry alone.  out[b, lengths[b]:] = 0.  Rows are the caller's: see the slot map in the class docstring."""
+        import torch
+        B, M, L = mixture.shape
+        if M != self.M:
+            raise RuntimeError(f"expected {self.M} microphones, got {M}")
+        fl = _flags_of(flags, B)
+        if not isinstance(fl, list):
+            fl = [fl] * B
+        ln = [L] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
+        if len(ln) != B:
+            raise RuntimeError(f"{len(ln)} lengths for a batch of {B}")
+        if out is None:
+            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
+        if any(fl):  # a carried batch keeps its slots
+            order = self._order if self._order is not None and len(self._order) == B else None
+        else:        # a fresh batch: most segments first (stable), for the engine's prefix compaction
+            nb = chain_geometry(ln, fl, self.K)["Nb"]
+            order = sorted(range(B), key=lambda i: -nb[i])
+            if order == list(range(B)):
+                order = None
+        if order is None:
+            src, dst, idx = mixture, out, None
+        else:
+            idx = self._order_idx if order is self._order and self._order_idx is not None and self._order_idx.device == mixture.device else None
+            if idx is None:
+                idx = torch.tensor(order, dtype=torch.int64, device=mixture.device)
+            src, dst = mixture.index_select(0, idx).contiguous(), torch.empty_like(out)
+            ln, fl = [ln[i] for i in order], [fl[i] for i in order]
+        self._check(self.lib.se_realtime_process_chains(self._h, self._dev(src), B, L, (C.c_int64 * B)(*ln), (C.c_uint8 * B)(*[int(f) for f in fl]),
+                                                        self._dev(dst, (B, L)), self._stream()))
+        self._order, self._order_idx = order, idx
+        if idx is not None:
+            out.index_copy_(0, idx, dst)
+        self.batch = B
+        return out
+
+    def _state_rows(self, name, arr, to_engine):
+        """export_state / import_state speak the caller's rows: [layers, B, H] for "h", [B, ...] for the buffers"""
+        if self._order is None:
+            return arr
+        B = len(self._order)
+        a = arr.reshape((self.cfg.num_layers, B, -1) if name == "h" else (B, -1))
+        o = np.empty_like(a)
+        if to_engine:   # engine row s = caller row order[s]
+            o[...] = np.take(a, self._order, axis=1 if name == "h" else 0)
+        elif name == "h":
+            o[:, self._order] = a
+        else:
+            o[self._order] = a
+        return o.reshape(-1)
 
     def stft(self, seg):
         import torch
@@ -337,10 +443,10 @@ class Engine:
         return out
 
     def export_state(self, name: str) -> np.ndarray:
-        return self._host_read(self.lib.se_export_state, name)
+        return self._state_rows(name, self._host_read(self.lib.se_export_state, name), to_engine=False)
 
     def import_state(self, name: str, arr: np.ndarray):
-        a = np.ascontiguousarray(arr, dtype=np.float32)
+        a = np.ascontiguousarray(self._state_rows(name, np.ascontiguousarray(arr, dtype=np.float32).reshape(-1), to_engine=True))
         self._check(self.lib.se_import_state(self._h, name.encode(), C.c_void_p(a.ctypes.data), a.size, self._stream()))
 
     def profile(self, enable: bool):
