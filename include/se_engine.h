@@ -163,7 +163,8 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               se_train_gemm_tn_det are the only convolution / weight-gradient forms);
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
-                              addition at 5: se_realtime_process_chains */
+                              additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
+                              fsn_import_state */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -195,6 +196,33 @@ int fsn_reset(fsn_engine *e, int batch);
 int fsn_forward(fsn_engine *e, const float *x, float *crm, void *stream);
 /* FullSubNet.realtime_process(mixture, source, flag, train=False)[0] (fullsubnet.py:903-961): [B, M, L] -> [B, L] */
 int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream);
+/* A batch of chunk CHAINS, the contract of se_realtime_process_chains word for word, applied to realtime_process(train=False): B callers,
+ * each with its own chunk length and its own flag, in one call.  lengths and flags are HOST arrays of `batch` entries.
+ *  - stream b is mixture[b, :, :lengths[b]] and ZERO beyond, whatever the padding holds; 0 < lengths[b] <= max_length.
+ *  - flags[b] == 0: stream b starts from zero LSTM state and reset norms, gets the K/2 left pad and has it stripped again;
+ *    flags[b] != 0: it continues row b of the carried state, no pad.
+ *  - a call with any flag set needs a carried batch of the same size (SE_ERR_STATE otherwise); with all flags zero the batch size may
+ *    change.  A failing call leaves the engine usable.
+ *  - out[b, lengths[b]:] = 0.
+ *  - afterwards the state of EVERY stream (full-band h, c of every layer; sub-band h, c of every layer, the stream's F rows; both
+ *    CumLayerNorm running means and both step counters, which are per stream) is what that stream alone carries after its own last
+ *    window: the state a following fsn_realtime_process*, fsn_forward, fsn_reset_stream and fsn_export_state see.
+ * Every stream keeps the window geometry it has alone (lead = flags[b] ? 0 : K/2); the call runs max_b N_b windows.  A stream's
+ * full-band rows, mean and counter are saved right after the full-band stage of its last window (on the engine's side stream, which
+ * runs one window ahead), its sub-band rows after the sub-band stage, and written back when the call ends; a reset among continuing
+ * streams zeroes that stream's rows and counters at entry.  Prefix compaction when the window counts N_b are NON-INCREASING (sort a
+ * fresh batch; the Python shim does): every window is launched for the streams still running only.  With unsorted counts every stream
+ * runs every window.  A uniform batch (equal flags, every length == max_length) is exactly fsn_realtime_process: same launches, no
+ * save, no restore. */
+int fsn_realtime_process_chains(fsn_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host,
+                                const uint8_t *flags_host, float *out, void *stream);
+/* reset_state + both CumLayerNorm.reset() (fullsubnet.py:826-832, 203-205) for ONE stream of the carried batch; the others keep streaming */
+int fsn_reset_stream(fsn_engine *e, int stream_index, void *stream);
+/* Streaming state hand-over in the reference's layouts, HOST pointers; synchronises.  Names: "fh", "fc" [layers, B, H_fb]; "sh", "sc"
+ * [layers, B*F, H_sb], row b*F + f (fullsubnet.py:810-811, 829); "mean_fb", "mean_sb" [B]; "step_fb", "step_sb" [B]: the CumLayerNorm
+ * step counters, small integers (0 .. 80) held exactly as floats, 0 = no mean yet.  Unknown name: SE_ERR_KEY; wrong count: SE_ERR_SHAPE. */
+int fsn_export_state(fsn_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream);
+int fsn_import_state(fsn_engine *e, const char *name, const float *host_in, int64_t count, void *stream);
 /* host copies of "fb_out" [B*T, F], "mean_fb" [B], "mean_sb" [B] after the last forward */
 int fsn_read_tap(fsn_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream);
 double fsn_flops_per_frame(const fsn_engine *e);

@@ -45,16 +45,21 @@ __global__ __launch_bounds__(256) void k_fsn_mag(FsnMagArgs a) {
     if (threadIdx.x == 0) a.partial[(long)b * gridDim.x + blockIdx.x] = (float)s;
 }
 
-// run_mean[b] <- first call ? mean : alpha*run_mean + (1-alpha)*mean ; scale[b] = run_mean + eps
-__global__ void k_fsn_runmean(const float *partial, int nslot, double count, float *run_mean, float *denom, int B, int first, float alpha) {
+// run_mean[b] <- no mean yet ? mean : alpha*run_mean + (1-alpha)*mean, alpha = step / (step + 1) ; scale[b] = run_mean + eps
+// step[b] (device, one counter per stream and norm) = the CumLayerNorm updates stream b has seen, capped at 80 (fullsubnet.py:192-198);
+// 0 = "no mean yet": the first update is a branch of its own, not alpha = 0 (0 * a stale mean may be NaN)
+__global__ void k_fsn_runmean(const float *partial, int nslot, double count, float *run_mean, float *denom, int B, int *step) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double s = 0;
     for (int i = 0; i < nslot; i++) s += (double)partial[(long)b * nslot + i];
     const float mean = (float)(s / count);
-    const float rm = first ? mean : alpha * run_mean[b] + (1.0f - alpha) * mean;
+    const int n = step[b];
+    const float alpha = (float)n / (float)(n + 1);
+    const float rm = n == 0 ? mean : alpha * run_mean[b] + (1.0f - alpha) * mean;
     run_mean[b] = rm;
     denom[b] = rm + kEps;
+    step[b] = min(n + 1, 80);
 }
 
 __global__ void k_fsn_scale(float *x, long per_stream, const float *denom) {
@@ -98,12 +103,14 @@ __global__ __launch_bounds__(256) void k_fsn_unfold(FsnUnfoldArgs a) {
 }
 
 // sbin is time-major, so the per-stream scale cannot use k_fsn_scale's contiguous layout
-__global__ void k_fsn_scale_sb(float *sbin, int B, int T, int F, int SI, const float *denom) {
-    const long per_t = (long)B * F * SI, total = per_t * T;
+// (Bact <= B: the streams a window runs for, a prefix of the batch; B stays the time stride)
+__global__ void k_fsn_scale_sb(float *sbin, int B, int T, int F, int SI, const float *denom, int Bact) {
+    const long per_t = (long)B * F * SI, act_t = (long)Bact * F * SI, total = act_t * T;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long r = i % per_t;
+        const long t = i / act_t, r = i - t * act_t;
         const int b = (int)(r / ((long)F * SI));
-        sbin[i] = sbin[i] / denom[b];
+        float *p = sbin + t * per_t + r;
+        *p = *p / denom[b];
     }
 }
 

@@ -20,7 +20,14 @@ struct fsn_engine {
     } fb, sb;
     int B = 0;
     DevBuf spec, maskspec, mag, fb_seq, fb_out, sbin, mask, part_fb, part_sb, mean_fb, mean_sb, denom_fb, denom_sb, yseg;
-    int step_fb = 0, step_sb = 0, have_fb = 0, have_sb = 0, nslot_fb = 0, nslot_sb = 0;
+    int nslot_fb = 0, nslot_sb = 0;
+    // CumLayerNorm step counters (fullsubnet.py:192-198): one int per stream and norm, on the device (k_fsn_runmean); 0 = no mean yet
+    DevBuf step_fb, step_sb;
+    // fsn_realtime_process_chains.  Bact > 0: the stages run for the prefix of Bact streams (grids, LSTM / GEMM / STFT rows); B stays every
+    // allocation and time stride.  chain_dev: int64 len[B] | off0[B] | skip[B], then int: the streams by ascending window count [B], the
+    // streams to zero at entry [B].  carry_*: the rows of the streams that ended before the longest one (state_rows.hip.h).
+    int Bact = 0;
+    DevBuf chain_dev, carry_h[2][4], carry_c[2][4], carry_mean[2], carry_step[2];
     // realtime_process: the full-band model of window n + 1 runs on `side` while the sub-band model of window n runs on the caller's stream
     // (the full-band recurrence is 42 launches of 32 workgroups per window, 11 % of the serial time, latency-bound: profiles/r03_fsn_*)
     hipStream_t side = nullptr;
@@ -198,7 +205,9 @@ int fsn_lstm_step(fsn_engine *e, fsn_engine::Model &m, int l, const float *x, lo
     }
 #endif
     // big tile (256 rows x 64 units) where it fills the chip: the sub-band model at B >= 32 streams
-    if (e->lstm_big == 1 && m.H % kLbU == 0 && R >= 32 * kLbM) {
+    // (the carried batch picks the route, not the active prefix of a chains call: one kernel for a stream from its first window to its last)
+    const long Rroute = (long)e->B * (&m == &e->sb ? e->F : 1);
+    if (e->lstm_big == 1 && m.H % kLbU == 0 && Rroute >= 32 * kLbM) {
         static bool attr = false;
         if (!attr) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lstm_step_big<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -223,15 +232,12 @@ int fsn_lstm_step(fsn_engine *e, fsn_engine::Model &m, int l, const float *x, lo
 // forward on device.  Spectrum given by (re, im) pointers + strides in float units for (b, m, t, f).
 // Stage A of a window: |X|, its CumLayerNorm, the full-band LSTM and its output layer -> e->mag, e->fb_out (read by stage B's unfold only)
 int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long sM, long sT, long sF, hipStream_t st) {
-    const int B = e->B, T = e->T, F = e->F, M = e->M, Kp = e->Kp;
+    const int B = e->Bact > 0 ? e->Bact : e->B, T = e->T, F = e->F, M = e->M, Kp = e->Kp;
     {  // |X| + CumLayerNorm of the full-band input (fullsubnet.py:782-788)
         FsnMagArgs a{re, im, sB, sM, sT, sF, e->mag.p, e->part_fb.p, M, T, F, Kp};
         hipLaunchKernelGGL(k_fsn_mag, dim3(e->nslot_fb, B), dim3(256), 0, st, a);
-        const float alpha = (float)e->step_fb / (float)(e->step_fb + 1);
         hipLaunchKernelGGL(k_fsn_runmean, dim3((B + 255) / 256), dim3(256), 0, st, e->part_fb.p, e->nslot_fb, (double)M * T * F, e->mean_fb.p,
-                           e->denom_fb.p, B, e->have_fb ? 0 : 1, alpha);
-        e->have_fb = 1;
-        e->step_fb = std::min(e->step_fb + 1, 80);
+                           e->denom_fb.p, B, reinterpret_cast<int *>(e->step_fb.p));
         hipLaunchKernelGGL(k_fsn_scale, dim3(16, B), dim3(256), 0, st, e->mag.p, (long)T * Kp, e->denom_fb.p);
         FHIP(e, hipGetLastError());
     }
@@ -266,23 +272,21 @@ int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long 
 // have been read, i.e. when the next window's stage A may overwrite them.
 int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long sT, long sF, float *crm_out, cf2 *spec_out,
                  long oB, long oT, long oF, hipStream_t st, hipEvent_t consumed) {
-    const int B = e->B, T = e->T, F = e->F, Kp = e->Kp, SI = e->SI;
+    const int B = e->Bact > 0 ? e->Bact : e->B, T = e->T, F = e->F, Kp = e->Kp, SI = e->SI;
     const int R = B * F;
+    const long Rall = (long)e->B * F;  // sbin's time stride: the carried batch, whatever prefix of it this window runs for
     {  // sub-band input + its CumLayerNorm (fullsubnet.py:796-802)
-        FsnUnfoldArgs a{e->mag.p, e->fb_out.p, e->sbin.p, e->part_sb.p, B, T, F, Kp, e->c.sb_neighbors, SI};
+        FsnUnfoldArgs a{e->mag.p, e->fb_out.p, e->sbin.p, e->part_sb.p, e->B, T, F, Kp, e->c.sb_neighbors, SI};
         hipLaunchKernelGGL(k_fsn_unfold, dim3(e->nslot_sb, B), dim3(256), 0, st, a);
         if (consumed) FHIP(e, hipEventRecord(consumed, st));
-        const float alpha = (float)e->step_sb / (float)(e->step_sb + 1);
         hipLaunchKernelGGL(k_fsn_runmean, dim3((B + 255) / 256), dim3(256), 0, st, e->part_sb.p, e->nslot_sb, (double)F * SI * T, e->mean_sb.p,
-                           e->denom_sb.p, B, e->have_sb ? 0 : 1, alpha);
-        e->have_sb = 1;
-        e->step_sb = std::min(e->step_sb + 1, 80);
-        hipLaunchKernelGGL(k_fsn_scale_sb, dim3(2048), dim3(256), 0, st, e->sbin.p, B, T, F, SI, e->denom_sb.p);
+                           e->denom_sb.p, B, reinterpret_cast<int *>(e->step_sb.p));
+        hipLaunchKernelGGL(k_fsn_scale_sb, dim3(2048), dim3(256), 0, st, e->sbin.p, e->B, T, F, SI, e->denom_sb.p, B);
         FHIP(e, hipGetLastError());
     }
     if (e->tr) {  // training forward: the normalised sub-band input, this window's denominators, the state entering the window
         FHIP(e, hipMemcpyAsync(e->tr_ws + e->tr->denom + (long)e->tr_n * B, e->denom_sb.p, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
-        int rc = fsn_train_save_window(e, 1, e->sbin.p, SI, (long)R * SI, SI, R, st);
+        int rc = fsn_train_save_window(e, 1, e->sbin.p, SI, Rall * SI, SI, R, st);
         if (rc) return rc;
     }
     // two layers (the reference configuration) on two streams: layer 0 of step t + 1 next to layer 1 of step t.  h of layer 0 ping-pongs
@@ -293,7 +297,7 @@ int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long 
             hipStream_t sl = wave && l == 1 ? e->side2 : st;
             if (wave && l == 0 && t >= 2) FHIP(e, hipStreamWaitEvent(st, e->ev_l1[t - 2], 0));
             if (wave && l == 1) FHIP(e, hipStreamWaitEvent(sl, e->ev_l0[t], 0));
-            if (l == 0) fsn_lstm_step(e, e->sb, 0, e->sbin.p + (long)t * R * SI, SI, SI, (SI + 31) & ~31, R, nullptr, 0, sl, t);
+            if (l == 0) fsn_lstm_step(e, e->sb, 0, e->sbin.p + (long)t * Rall * SI, SI, SI, (SI + 31) & ~31, R, nullptr, 0, sl, t);
             else fsn_lstm_step(e, e->sb, l, e->sb.h[l - 1][e->sb.hcur[l - 1]].p, e->sb.H, e->sb.H, (e->sb.H + 31) & ~31, R, nullptr, 0, sl, t);
             if (wave && l == 0) FHIP(e, hipEventRecord(e->ev_l0[t], st));
         }
@@ -334,7 +338,7 @@ int fsn_reset_on(fsn_engine *e, int batch, hipStream_t st) {
         (rc = falloc(e, e->fb_out, (size_t)B * T * F)) || (rc = falloc(e, e->sbin, (size_t)T * R * e->SI)) ||
         (rc = falloc(e, e->mask, (size_t)R * 2 * T)) || (rc = falloc(e, e->part_fb, (size_t)B * e->nslot_fb)) ||
         (rc = falloc(e, e->part_sb, (size_t)B * e->nslot_sb)) || (rc = falloc(e, e->mean_fb, B)) || (rc = falloc(e, e->mean_sb, B)) ||
-        (rc = falloc(e, e->denom_fb, B)) || (rc = falloc(e, e->denom_sb, B)))
+        (rc = falloc(e, e->denom_fb, B)) || (rc = falloc(e, e->denom_sb, B)) || (rc = falloc(e, e->step_fb, B)) || (rc = falloc(e, e->step_sb, B)))
         return rc;
     FHIP(e, hipMemsetAsync(e->mag.p, 0, (size_t)B * T * e->Kp * sizeof(float), st));  // padding columns must be zero
     for (int l = 0; l < e->NL; l++) {
@@ -348,7 +352,9 @@ int fsn_reset_on(fsn_engine *e, int batch, hipStream_t st) {
         FHIP(e, hipMemsetAsync(e->sb.c[l].p, 0, (size_t)R * e->sb.H * sizeof(float), st));
         e->fb.hcur[l] = e->sb.hcur[l] = 0;
     }
-    e->step_fb = e->step_sb = e->have_fb = e->have_sb = 0;
+    FHIP(e, hipMemsetAsync(e->step_fb.p, 0, (size_t)B * sizeof(int), st));  // both norms: no mean yet (CumLayerNorm.reset)
+    FHIP(e, hipMemsetAsync(e->step_sb.p, 0, (size_t)B * sizeof(int), st));
+    e->Bact = 0;
     e->sig->B = B;  // the shared STFT/iSTFT launchers size their grids from B
     return 0;
 }
@@ -414,8 +420,11 @@ void fsn_destroy(fsn_engine *e) {
         dev_free(m->fcw); dev_free(m->fcw_x); dev_free(m->fcb); dev_free(m->wcol); dev_free(m->fcw_t);
     }
     for (DevBuf *b : {&e->spec, &e->maskspec, &e->mag, &e->fb_seq, &e->fb_out, &e->sbin, &e->mask, &e->part_fb, &e->part_sb, &e->mean_fb,
-                      &e->mean_sb, &e->denom_fb, &e->denom_sb, &e->yseg})
+                      &e->mean_sb, &e->denom_fb, &e->denom_sb, &e->yseg, &e->step_fb, &e->step_sb, &e->chain_dev, &e->carry_mean[0], &e->carry_mean[1],
+                      &e->carry_step[0], &e->carry_step[1]})
         dev_free(*b);
+    for (int mi = 0; mi < 2; mi++)
+        for (int l = 0; l < 4; l++) { dev_free(e->carry_h[mi][l]); dev_free(e->carry_c[mi][l]); }
     if (e->side) (void)hipStreamDestroy(e->side);
     if (e->side2) (void)hipStreamDestroy(e->side2);
     for (hipEvent_t ev : e->ev_l0) if (ev) (void)hipEventDestroy(ev);
@@ -467,6 +476,114 @@ int fsn_forward(fsn_engine *e, const float *x, float *crm, void *stream) {
     return fsn_forward_dev(e, x, x + M * F * T, 2 * M * F * T, F * T, 1, T, crm, nullptr, 0, 0, 0, static_cast<hipStream_t>(stream));
 }
 
+// ---- per-stream state rows (state_rows.hip.h): which bit 0 = the full-band set (h, c of every layer, mean_fb, step_fb), bit 1 = the
+// sub-band set (the same of the sub-band model; its rows are the stream's F sub-band rows).  h lives in the half hcur[l] points at NOW.
+// dir 0: live -> carry (save), 1: carry -> live (restore), 2: zeros -> live.  One launch per set.
+static int fsn_chain_rows(fsn_engine *e, unsigned which, int dir, const int *streams, int nstreams, hipStream_t st) {
+    if (nstreams <= 0) return 0;
+    static_assert(2 * 4 + 2 <= kStateRowsMax, "state row table too small");
+    for (int mi = 0; mi < 2; mi++) {
+        if (!(which & (1u << mi))) continue;
+        fsn_engine::Model &m = mi ? e->sb : e->fb;
+        StateRowTable t{};
+        int n = 0;
+        long wmax = 0;
+        auto add = [&](float *live, float *carry, long words) {
+            StateRow &r = t.r[n++];
+            r.src = reinterpret_cast<const uint32_t *>(dir == 0 ? live : dir == 1 ? carry : nullptr);
+            r.dst = reinterpret_cast<uint32_t *>(dir == 0 ? carry : live);
+            r.words = words;
+            wmax = std::max(wmax, words);
+        };
+        const long per = (long)(mi ? e->F : 1) * m.H;
+        for (int l = 0; l < e->NL; l++) {
+            add(m.h[l][m.hcur[l]].p, e->carry_h[mi][l].p, per);
+            add(m.c[l].p, e->carry_c[mi][l].p, per);
+        }
+        add(mi ? e->mean_sb.p : e->mean_fb.p, e->carry_mean[mi].p, 1);
+        add(mi ? e->step_sb.p : e->step_fb.p, e->carry_step[mi].p, 1);
+        launch_k_state_rows(st, t, n, streams, nstreams, wmax);
+        FHIP(e, hipGetLastError());
+    }
+    return 0;
+}
+
+static int fsn_alloc_carry(fsn_engine *e) {
+    int rc;
+    for (int mi = 0; mi < 2; mi++) {
+        const fsn_engine::Model &m = mi ? e->sb : e->fb;
+        const size_t per = (size_t)(mi ? e->F : 1) * m.H;
+        for (int l = 0; l < e->NL; l++)
+            if ((rc = falloc(e, e->carry_h[mi][l], (size_t)e->B * per)) || (rc = falloc(e, e->carry_c[mi][l], (size_t)e->B * per))) return rc;
+        if ((rc = falloc(e, e->carry_mean[mi], e->B)) || (rc = falloc(e, e->carry_step[mi], e->B))) return rc;
+    }
+    return 0;
+}
+
+// what a chains call adds to the window loop (null: the uniform call)
+struct FsnChain {
+    const long *len, *off0, *skip;  // device [B]: own length, first window's offset (-K/2 - lead), strip (lead)
+    const int *sorted;              // device [B]: streams by ascending window count
+    std::vector<int> le;            // le[k] = streams with at most k windows, k = 0 .. N: those whose LAST window is n are positions
+                                    // [le[n], le[n + 1]) of `sorted`
+    bool compact = false;           // window counts non-increasing: window n runs for the prefix of B - le[n] streams
+};
+
+// The windows of one realtime_process call on state that is ready: Nseg half-overlapping windows, window n of a stream starting at
+// n*K/2 - K/2 - lead (uniform) or n*K/2 + off0[b] (chains), STFT -> stage A -> stage B -> iSTFT, then the overlap average.
+static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long length, long Nseg, long lead, float *out, hipStream_t st, const FsnChain *ch) {
+    int rc;
+    const long K = e->K, P = K / 2;
+    if ((rc = falloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
+    const long F = e->F, T = e->T, M = e->M;
+    cf2 *spec = reinterpret_cast<cf2 *>(e->spec.p);
+    cf2 *ms = reinterpret_cast<cf2 *>(e->maskspec.p);
+    const size_t spec_floats = (size_t)batch * M * T * F * 2;
+    const bool piped = e->pipeline && e->side && Nseg > 1;
+    hipStream_t sa = piped ? e->side : st;
+    if (piped) {  // the side stream starts after whatever the caller's stream holds (reset, the previous call's tail)
+        FHIP(e, hipEventRecord(e->ev_fork, st));
+        FHIP(e, hipStreamWaitEvent(sa, e->ev_fork, 0));
+    }
+    struct Scope {  // a failing call leaves the engine usable: nothing of the chain outlives the call
+        fsn_engine *e;
+        ~Scope() { e->Bact = 0; e->sig->row_len = e->sig->row_off = nullptr; }
+    } scope{e};
+    const bool saving = ch && ch->le[Nseg - 1] > 0;  // some stream ends before the longest one: save / restore is live
+    if (ch) { e->sig->row_len = ch->len; e->sig->row_off = ch->off0; }
+    for (long n = 0; n < Nseg; n++) {
+        const long off = ch ? n * P : n * P - P - lead;
+        const int slot = piped ? (int)(n & 1) : 0;
+        const float *sp = e->spec.p + slot * spec_floats;
+        const int bact = ch && ch->compact ? batch - ch->le[n] : batch;
+        const int nlast = saving && n + 1 < Nseg ? ch->le[n + 1] - ch->le[n] : 0;  // streams whose last window this is (the call's last window saves nothing)
+        if (ch) e->Bact = bact;
+        if (piped) {
+            if (n >= 2) FHIP(e, hipStreamWaitEvent(sa, e->ev_done[slot], 0));          // window n - 2 has masked spectrum[slot]
+            if (n >= 1) FHIP(e, hipStreamWaitEvent(sa, e->ev_consumed[slot ^ 1], 0));  // window n - 1 has unfolded mag / fb_out
+        }
+        if (launch_stft(e->sig, mixture, (long)M * length, length, (int)M, off, length, bact * (int)M, spec + slot * (spec_floats / 2), T * F, F, 1, sa))
+            return ffail(e, SE_ERR_HIP, "stft: %s", se_last_error(e->sig));
+        if ((rc = fsn_stage_fb(e, sp, sp + 1, 2 * M * T * F, 2 * T * F, 2 * F, 2, sa))) return rc;
+        // the full-band stage of window n + 1 runs ahead on `side`: the full-band rows of the streams that end here are kept now, on `side`
+        if (nlast && (rc = fsn_chain_rows(e, 1u, 0, ch->sorted + ch->le[n], nlast, sa))) return rc;
+        if (piped) {
+            FHIP(e, hipEventRecord(e->ev_ready[slot], sa));
+            FHIP(e, hipStreamWaitEvent(st, e->ev_ready[slot], 0));
+        }
+        if ((rc = fsn_stage_sb(e, sp, sp + 1, 2 * M * T * F, 2 * F, 2, nullptr, ms, T * F, F, 1, st, piped ? e->ev_consumed[slot] : nullptr))) return rc;
+        if (nlast && (rc = fsn_chain_rows(e, 2u, 0, ch->sorted + ch->le[n], nlast, st))) return rc;  // stage B has joined `side2`
+        if (launch_istft(e->sig, ms, T * F, F, 1, bact, e->yseg.p + n * K, Nseg * K, st)) return ffail(e, SE_ERR_HIP, "istft: %s", se_last_error(e->sig));
+        if (piped) FHIP(e, hipEventRecord(e->ev_done[slot], st));
+    }
+    // the streams that ended before the longest one get their own state back (the last stage B waited for everything on `side`)
+    if (saving && (rc = fsn_chain_rows(e, 3u, 1, ch->sorted, ch->le[Nseg - 1], st))) return rc;
+    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, lead, ch ? ch->len : nullptr,
+                         ch ? ch->skip : nullptr);
+    FHIP(e, hipGetLastError());
+    return SE_OK;
+}
+
 // FullSubNet.realtime_process(mixture, source, flag, train=False)[0]: mixture [B, M, L] -> [B, L]
 int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
     if (!e || !mixture || !out || batch <= 0 || length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
@@ -480,38 +597,153 @@ int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t
     }
     const long K = e->K, P = K / 2, lead = flag ? 0 : P, Lp = length + lead;
     const long gap = K - (P + Lp % K) % K, Nseg = 2 * (Lp + gap + P) / K;
-    if ((rc = falloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
-    const long F = e->F, T = e->T, M = e->M;
-    cf2 *spec = reinterpret_cast<cf2 *>(e->spec.p);
-    cf2 *ms = reinterpret_cast<cf2 *>(e->maskspec.p);
-    const size_t spec_floats = (size_t)batch * M * T * F * 2;
-    const bool piped = e->pipeline && e->side && Nseg > 1;
-    hipStream_t sa = piped ? e->side : st;
-    if (piped) {  // the side stream starts after whatever the caller's stream holds (reset, the previous call's tail)
-        FHIP(e, hipEventRecord(e->ev_fork, st));
-        FHIP(e, hipStreamWaitEvent(sa, e->ev_fork, 0));
+    return fsn_run_windows(e, mixture, batch, length, Nseg, lead, out, st, nullptr);
+}
+
+// A batch of chunk chains: one flag and one length per stream, every stream leaves the state it would carry alone (include/se_engine.h)
+int fsn_realtime_process_chains(fsn_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host,
+                                float *out, void *stream) {
+    if (!e || !mixture || !out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    bool any = false, all = true, full = true;
+    for (int b = 0; b < batch; b++) {
+        if (lengths_host[b] <= 0 || lengths_host[b] > max_length)
+            return ffail(e, SE_ERR_ARG, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths_host[b], (long long)max_length);
+        any = any || flags_host[b];
+        all = all && flags_host[b];
+        full = full && lengths_host[b] == max_length;
     }
-    for (long n = 0; n < Nseg; n++) {
-        const long off = n * P - P - lead;
-        const int slot = piped ? (int)(n & 1) : 0;
-        const float *sp = e->spec.p + slot * spec_floats;
-        if (piped) {
-            if (n >= 2) FHIP(e, hipStreamWaitEvent(sa, e->ev_done[slot], 0));          // window n - 2 has masked spectrum[slot]
-            if (n >= 1) FHIP(e, hipStreamWaitEvent(sa, e->ev_consumed[slot ^ 1], 0));  // window n - 1 has unfolded mag / fb_out
-        }
-        if (launch_stft(e->sig, mixture, (long)M * length, length, (int)M, off, length, batch * (int)M, spec + slot * (spec_floats / 2), T * F, F, 1, sa))
-            return ffail(e, SE_ERR_HIP, "stft: %s", se_last_error(e->sig));
-        if ((rc = fsn_stage_fb(e, sp, sp + 1, 2 * M * T * F, 2 * T * F, 2 * F, 2, sa))) return rc;
-        if (piped) {
-            FHIP(e, hipEventRecord(e->ev_ready[slot], sa));
-            FHIP(e, hipStreamWaitEvent(st, e->ev_ready[slot], 0));
-        }
-        if ((rc = fsn_stage_sb(e, sp, sp + 1, 2 * M * T * F, 2 * F, 2, nullptr, ms, T * F, F, 1, st, piped ? e->ev_consumed[slot] : nullptr))) return rc;
-        if (launch_istft(e->sig, ms, T * F, F, 1, batch, e->yseg.p + n * K, Nseg * K, st)) return ffail(e, SE_ERR_HIP, "istft: %s", se_last_error(e->sig));
-        if (piped) FHIP(e, hipEventRecord(e->ev_done[slot], st));
+    if (any && e->B <= 0) return ffail(e, SE_ERR_STATE, "a stream continues (flag set) but the engine carries no state");
+    if (any && e->B != batch) return ffail(e, SE_ERR_STATE, "a stream continues (flag set) in a batch of %d but the carried state holds %d streams", batch, e->B);
+    if (full && (all || !any)) return fsn_realtime_process(e, mixture, batch, max_length, all ? 1 : 0, out, stream);  // a uniform batch
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    if (!any) rc = fsn_reset_on(e, batch, st);
+    else {
+        FHIP(e, hipSetDevice(e->device));
+        rc = fsn_prepare(e);
     }
-    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, lead);
-    FHIP(e, hipGetLastError());
+    if (rc) return rc;
+    // every stream keeps the geometry it has alone (the lead / gap / Nseg arithmetic of fsn_realtime_process with its own lead)
+    const long K = e->K, P = K / 2;
+    const int B = batch;
+    std::vector<int64_t> geo((size_t)4 * B);  // len | off0 | skip | (int) sorted streams, flag-0 streams: one upload
+    std::vector<int> nb(B), idx((size_t)2 * B, 0);
+    int N = 0, nzero = 0;
+    for (int b = 0; b < B; b++) {
+        const long lead = flags_host[b] ? 0 : P, Lp = lengths_host[b] + lead, gap = K - (P + Lp % K) % K;
+        nb[b] = (int)(2 * (Lp + gap + P) / K);
+        N = std::max(N, nb[b]);
+        geo[b] = lengths_host[b];
+        geo[(size_t)B + b] = -P - lead;
+        geo[2 * (size_t)B + b] = lead;
+        idx[b] = b;
+        if (!flags_host[b]) idx[B + nzero++] = b;
+    }
+    std::stable_sort(idx.begin(), idx.begin() + B, [&](int a, int b) { return nb[a] < nb[b]; });
+    memcpy(geo.data() + 3 * (size_t)B, idx.data(), (size_t)2 * B * sizeof(int));
+    FsnChain ch;
+    ch.le.assign((size_t)N + 1, 0);
+    for (int b = 0; b < B; b++) ch.le[nb[b]]++;
+    for (int k = 1; k <= N; k++) ch.le[k] += ch.le[k - 1];
+    if ((rc = falloc(e, e->chain_dev, (size_t)8 * B)) || (rc = fsn_alloc_carry(e))) return rc;
+    static_assert(sizeof(long) == sizeof(int64_t), "per-stream geometry is passed to the kernels as long");
+    FHIP(e, hipMemcpyAsync(e->chain_dev.p, geo.data(), (size_t)4 * B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    FHIP(e, hipStreamSynchronize(st));  // the staging vector and the host arrays live for the call only
+    const long *dev64 = reinterpret_cast<const long *>(e->chain_dev.p);
+    const int *dev32 = reinterpret_cast<const int *>(dev64 + 3 * (size_t)B);
+    ch.len = dev64; ch.off0 = dev64 + B; ch.skip = dev64 + 2 * (size_t)B;
+    ch.sorted = dev32;
+    // a reset among continuing streams: zero those streams' rows and counters (fsn_reset_stream for any number of streams in two launches)
+    if (any && (rc = fsn_chain_rows(e, 3u, 2, dev32 + B, nzero, st))) return rc;
+    // prefix compaction: the streams still running in window n are a prefix of the batch when the WINDOW COUNTS are non-increasing (a
+    // reset stream has one lead more than a continuing one); the streams beyond the prefix are exactly those whose rows were saved
+    ch.compact = true;
+    for (int b = 1; b < B; b++) ch.compact = ch.compact && nb[b] <= nb[b - 1];
+    return fsn_run_windows(e, mixture, batch, max_length, N, 0, out, st, &ch);
+}
+
+// reset_state + both CumLayerNorm.reset() (fullsubnet.py:826-832, 203-205) for ONE stream of the carried batch
+int fsn_reset_stream(fsn_engine *e, int stream_index, void *stream) {
+    if (!e) return SE_ERR_ARG;
+    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "fsn_reset_stream before fsn_reset");
+    if (stream_index < 0 || stream_index >= e->B) return ffail(e, SE_ERR_ARG, "stream index %d outside the batch of %d", stream_index, e->B);
+    FHIP(e, hipSetDevice(e->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t b = (size_t)stream_index;
+    for (int mi = 0; mi < 2; mi++) {
+        fsn_engine::Model &m = mi ? e->sb : e->fb;
+        const size_t per = (size_t)(mi ? e->F : 1) * m.H;
+        for (int l = 0; l < e->NL; l++) {
+            FHIP(e, hipMemsetAsync(m.h[l][m.hcur[l]].p + per * b, 0, per * sizeof(float), st));
+            FHIP(e, hipMemsetAsync(m.c[l].p + per * b, 0, per * sizeof(float), st));
+        }
+    }
+    for (DevBuf *w : {&e->mean_fb, &e->mean_sb, &e->step_fb, &e->step_sb}) FHIP(e, hipMemsetAsync(w->p + b, 0, sizeof(float), st));
+    return SE_OK;
+}
+
+// the tensor behind a state name: fh / fc / sh / sc -> per layer (l < NL) a device pointer and its length; mean_* / step_* -> one vector
+static int fsn_state_of(fsn_engine *e, const char *name, float *ptr[4], size_t *per_layer, int *layers, bool *is_step) {
+    const size_t B = (size_t)e->B;
+    *is_step = false;
+    if (!strcmp(name, "fh") || !strcmp(name, "fc") || !strcmp(name, "sh") || !strcmp(name, "sc")) {
+        fsn_engine::Model &m = name[0] == 's' ? e->sb : e->fb;
+        for (int l = 0; l < e->NL; l++) ptr[l] = name[1] == 'h' ? m.h[l][m.hcur[l]].p : m.c[l].p;
+        *per_layer = B * (name[0] == 's' ? e->F : 1) * m.H;  // sub band: row b*F + f, the reference's [num_freqs * batch] order (fullsubnet.py:810-811, 829)
+        *layers = e->NL;
+        return 0;
+    }
+    *layers = 1;
+    *per_layer = B;
+    if (!strcmp(name, "mean_fb")) ptr[0] = e->mean_fb.p;
+    else if (!strcmp(name, "mean_sb")) ptr[0] = e->mean_sb.p;
+    else if (!strcmp(name, "step_fb")) { ptr[0] = e->step_fb.p; *is_step = true; }
+    else if (!strcmp(name, "step_sb")) { ptr[0] = e->step_sb.p; *is_step = true; }
+    else return ffail(e, SE_ERR_KEY, "unknown state %s", name);
+    return 0;
+}
+
+int fsn_export_state(fsn_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream) {
+    if (!e || !name || !host_out) return ffail(e, SE_ERR_ARG, "null argument");
+    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "no state: call fsn_reset first");
+    float *ptr[4];
+    size_t per = 0;
+    int layers = 0, rc;
+    bool is_step = false;
+    if ((rc = fsn_state_of(e, name, ptr, &per, &layers, &is_step))) return rc;
+    const size_t n = per * layers;
+    if (count) *count = (int64_t)n;
+    if ((int64_t)n > capacity) return ffail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
+    FHIP(e, hipSetDevice(e->device));
+    FHIP(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    for (int l = 0; l < layers; l++) FHIP(e, hipMemcpy(host_out + (size_t)l * per, ptr[l], per * sizeof(float), hipMemcpyDeviceToHost));
+    if (is_step)  // the counters are ints on the device, small integers held exactly as floats outside
+        for (size_t i = 0; i < n; i++) { int v; memcpy(&v, host_out + i, sizeof v); host_out[i] = (float)v; }
+    return SE_OK;
+}
+
+int fsn_import_state(fsn_engine *e, const char *name, const float *host_in, int64_t count, void *stream) {
+    if (!e || !name || !host_in) return ffail(e, SE_ERR_ARG, "null argument");
+    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "no state: call fsn_reset first");
+    float *ptr[4];
+    size_t per = 0;
+    int layers = 0, rc;
+    bool is_step = false;
+    if ((rc = fsn_state_of(e, name, ptr, &per, &layers, &is_step))) return rc;
+    if (count != (int64_t)(per * layers)) return ffail(e, SE_ERR_SHAPE, "state %s needs %zu floats", name, per * layers);
+    FHIP(e, hipSetDevice(e->device));
+    FHIP(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    if (is_step) {
+        std::vector<int> v(per);
+        for (size_t i = 0; i < per; i++) {
+            if (!(host_in[i] >= 0.0f && host_in[i] <= 80.0f) || host_in[i] != (float)(int)host_in[i])
+                return ffail(e, SE_ERR_ARG, "state %s: %g is not a step count in 0 .. 80", name, (double)host_in[i]);
+            v[i] = (int)host_in[i];
+        }
+        FHIP(e, hipMemcpy(ptr[0], v.data(), per * sizeof(int), hipMemcpyHostToDevice));
+        return SE_OK;
+    }
+    for (int l = 0; l < layers; l++) FHIP(e, hipMemcpy(ptr[l], host_in + (size_t)l * per, per * sizeof(float), hipMemcpyHostToDevice));
     return SE_OK;
 }
 

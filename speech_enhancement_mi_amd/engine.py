@@ -21,6 +21,7 @@ EXPORTS = [
     "se_realtime_process", "se_realtime_process_ragged", "se_realtime_process_chains", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
     "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
+    "fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state",
     "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
     "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd",
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
@@ -99,6 +100,10 @@ def load_library():
     L.fsn_reset.argtypes = [vp, C.c_int]
     L.fsn_forward.argtypes = [vp, fp, fp, vp]
     L.fsn_realtime_process.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, fp, vp]
+    L.fsn_realtime_process_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), fp, vp]
+    L.fsn_reset_stream.argtypes = [vp, C.c_int, vp]
+    L.fsn_export_state.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
+    L.fsn_import_state.argtypes = [vp, C.c_char_p, fp, C.c_int64, vp]
     L.fsn_read_tap.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
     L.fsn_flops_per_frame.argtypes = [vp]
     L.fsn_flops_per_frame.restype = C.c_double
@@ -473,7 +478,13 @@ class Engine:
 
 
 class FsnEngine:
-    """RAII wrapper over one fsn_engine handle (FullSubNet, fullsubnet.py:685-961)."""
+    """RAII wrapper over one fsn_engine handle (FullSubNet, fullsubnet.py:685-961).
+
+    Slot map: exactly Engine's.  realtime_process_chains sorts a FRESH batch (all flags 0) by window count for the engine's prefix
+    compaction; the permutation (self._order[slot] = caller row) stays with the engine while that batch is carried, so the caller's row b
+    is always the same stream for inputs, outputs, reset_stream, export_state and import_state."""
+
+    STATE_NAMES = ("fh", "fc", "sh", "sc", "mean_fb", "mean_sb", "step_fb", "step_sb")
 
     def __init__(self, num_freqs, num_mics, fb_hidden, sb_hidden, num_layers=2, sb_neighbors=15, fb_neighbors=0, look_ahead=0,
                  sample_rate=16000, segment_length=3200, win_length=25, hop_length=10, n_fft=400, device=0, precision=0):
@@ -489,6 +500,8 @@ class FsnEngine:
         self._h = h
         self.F, self.M, self.K, self.T = cfg.num_freqs, cfg.num_mics, cfg.segment_length, 1 + cfg.segment_length // cfg.hop
         self.batch = 0
+        self._order = None      # slot map of the carried batch: _order[slot] = caller row (None: caller row b is engine row b)
+        self._order_idx = None  # the same as an int64 device tensor
 
     def close(self):
         if getattr(self, "_h", None):
@@ -514,6 +527,13 @@ class FsnEngine:
     def reset(self, batch):
         self._check(self.lib.fsn_reset(self._h, int(batch)))
         self.batch = int(batch)
+        self._order = self._order_idx = None
+
+    def reset_stream(self, index):
+        """Zero the LSTM state and reset both norms of ONE stream of the batch (a new caller takes the slot); the others keep streaming."""
+        if self._order is not None and 0 <= int(index) < len(self._order):
+            index = self._order.index(int(index))
+        self._check(self.lib.fsn_reset_stream(self._h, int(index), Engine._stream()))
 
     def forward(self, x):
         import torch
@@ -522,26 +542,103 @@ class FsnEngine:
         self._check(self.lib.fsn_forward(self._h, Engine._dev(x, (B, 2 * self.M, self.F, self.T)), Engine._dev(crm), Engine._stream()))
         return crm
 
-    def realtime_process(self, mixture, flag=False, out=None):
+    def realtime_process(self, mixture, flag=False, lengths=None, out=None):
+        """flag: a bool (or one value) for the whole batch, or one value per stream: a batch of chunk chains (realtime_process_chains).
+        lengths (optional, [B] ints <= L): every stream is processed as if alone with its own length."""
         import torch
         B, M, L = mixture.shape
         if M != self.M:
             raise RuntimeError(f"expected {self.M} microphones, got {M}")
+        flag = _flags_of(flag, B)
+        if isinstance(flag, list) or lengths is not None:
+            return self.realtime_process_chains(mixture, flag if isinstance(flag, list) else [flag] * B, lengths, out=out)
+        if flag and self._order is not None and len(self._order) == B:
+            # the carried batch was permuted by a chains call: keep the caller's row b on its stream
+            return self.realtime_process_chains(mixture, [True] * B, None, out=out)
         if out is None:
             out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
+        if not flag:
+            self._order = self._order_idx = None
         self._check(self.lib.fsn_realtime_process(self._h, Engine._dev(mixture), B, L, int(bool(flag)), Engine._dev(out, (B, L)), Engine._stream()))
         self.batch = B
         return out
 
-    def read_tap(self, name):
+    def realtime_process_chains(self, mixture, flags, lengths=None, out=None):
+        """A batch of chunk chains (fsn_realtime_process_chains): mixture [B, M, L]; stream b is mixture[b, :, :lengths[b]], continues its
+        carried state where flags[b] is set and starts from zero state and reset norms (K/2 left pad, stripped again) where it is not;
+        every stream leaves the state it would carry alone.  out[b, lengths[b]:] = 0.  Rows are the caller's: see the class docstring."""
+        import torch
+        B, M, L = mixture.shape
+        if M != self.M:
+            raise RuntimeError(f"expected {self.M} microphones, got {M}")
+        fl = _flags_of(flags, B)
+        if not isinstance(fl, list):
+            fl = [fl] * B
+        ln = [L] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
+        if len(ln) != B:
+            raise RuntimeError(f"{len(ln)} lengths for a batch of {B}")
+        if out is None:
+            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
+        if any(fl):  # a carried batch keeps its slots
+            order = self._order if self._order is not None and len(self._order) == B else None
+        else:        # a fresh batch: most windows first (stable), for the engine's prefix compaction
+            nb = chain_geometry(ln, fl, self.K)["Nb"]
+            order = sorted(range(B), key=lambda i: -nb[i])
+            if order == list(range(B)):
+                order = None
+        if order is None:
+            src, dst, idx = mixture, out, None
+        else:
+            idx = self._order_idx if order is self._order and self._order_idx is not None and self._order_idx.device == mixture.device else None
+            if idx is None:
+                idx = torch.tensor(order, dtype=torch.int64, device=mixture.device)
+            src, dst = mixture.index_select(0, idx).contiguous(), torch.empty_like(out)
+            ln, fl = [ln[i] for i in order], [fl[i] for i in order]
+        self._check(self.lib.fsn_realtime_process_chains(self._h, Engine._dev(src), B, L, (C.c_int64 * B)(*ln), (C.c_uint8 * B)(*[int(f) for f in fl]),
+                                                         Engine._dev(dst, (B, L)), Engine._stream()))
+        self._order, self._order_idx = order, idx
+        if idx is not None:
+            out.index_copy_(0, idx, dst)
+        self.batch = B
+        return out
+
+    def _state_rows(self, name, arr, to_engine):
+        """export_state / import_state speak the caller's rows: [layers, B, ...] for the LSTM states, [B] for means and counters"""
+        if self._order is None:
+            return arr
+        B = len(self._order)
+        layered = name in ("fh", "fc", "sh", "sc")
+        a = arr.reshape((self.cfg.num_layers, B, -1) if layered else (B, -1))
+        o = np.empty_like(a)
+        if to_engine:   # engine row s = caller row order[s]
+            o[...] = np.take(a, self._order, axis=1 if layered else 0)
+        elif layered:
+            o[:, self._order] = a
+        else:
+            o[self._order] = a
+        return o.reshape(-1)
+
+    def _host_read(self, fn, name):
         n = C.c_int64(0)
         probe = np.empty(1, np.float32)
-        self.lib.fsn_read_tap(self._h, name.encode(), C.c_void_p(probe.ctypes.data), 0, C.byref(n), Engine._stream())
+        rc = fn(self._h, name.encode(), C.c_void_p(probe.ctypes.data), 0, C.byref(n), Engine._stream())
         if n.value <= 0:
-            self._check(-1)
+            self._check(rc if rc != 0 else -1)
         out = np.empty(n.value, np.float32)
-        self._check(self.lib.fsn_read_tap(self._h, name.encode(), C.c_void_p(out.ctypes.data), n.value, C.byref(n), Engine._stream()))
+        self._check(fn(self._h, name.encode(), C.c_void_p(out.ctypes.data), n.value, C.byref(n), Engine._stream()))
         return out
+
+    def export_state(self, name):
+        """One of STATE_NAMES as a flat host array in the reference's layout ("fh", "fc" [layers, B, H_fb]; "sh", "sc" [layers, B*F, H_sb];
+        means and step counters [B]), rows in the caller's order."""
+        return self._state_rows(name, self._host_read(self.lib.fsn_export_state, name), to_engine=False)
+
+    def import_state(self, name, arr):
+        a = np.ascontiguousarray(self._state_rows(name, np.ascontiguousarray(arr, dtype=np.float32).reshape(-1), to_engine=True))
+        self._check(self.lib.fsn_import_state(self._h, name.encode(), C.c_void_p(a.ctypes.data), a.size, Engine._stream()))
+
+    def read_tap(self, name):
+        return self._host_read(self.lib.fsn_read_tap, name)
 
     @property
     def flops_per_frame(self):
@@ -560,6 +657,8 @@ class FsnEngine:
         self._check(self.lib.fsn_train_fwd(self._h, Engine._dev(spec, (nseg, batch * self.M, self.T, self.F, 2)), int(batch), int(nseg), int(bool(flag)),
                                            C.c_void_p(ws.data_ptr()), Engine._dev(crm), Engine._stream()))
         self.batch = int(batch)
+        if not flag:
+            self._order = self._order_idx = None
         return crm
 
     def train_bwd(self, dcrm, batch, nseg, ws, grads):

@@ -85,11 +85,17 @@ class FullSubNet(nn.Module):
             eng.reset(noisy_complex.shape[0])
         return eng.forward(noisy_complex.contiguous().float())
 
-    def realtime_process(self, mixture, source=None, flag=False, train=True):
+    def realtime_process(self, mixture, source=None, flag=False, train=True, lengths=None):
+        """flag: a bool or ONE value for the whole batch (the reference), or one value per utterance (a tensor or list of B): a batch of
+        chunk chains, every utterance continuing (flag set) or starting (flag clear) on its own.  lengths (optional, [B] ints <= L):
+        utterance b is mixture[b, :, :lengths[b]]; pred[b, lengths[b]:] = 0.  Both are extensions over the reference (train=False only)."""
+        flag = _engine._flags_of(flag, mixture.shape[0])
         if train:
-            return self._realtime_single_pass(mixture, source, flag)
+            if lengths is not None:
+                raise NotImplementedError("train=True takes one length for the whole batch")
+            return self._realtime_single_pass(mixture, source, any(flag) if isinstance(flag, list) else flag)
         eng = self._engine_for(mixture)
-        pred = eng.realtime_process(mixture.contiguous().float(), flag=bool(flag))
+        pred = eng.realtime_process(mixture.contiguous().float(), flag=flag, lengths=lengths)
         return pred if source is None else (pred, None, None, None)
 
     def _realtime_single_pass(self, mixture, source, flag):

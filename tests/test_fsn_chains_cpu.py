@@ -1,0 +1,84 @@
+"""CPU-side checks of fsn_realtime_process_chains and the FullSubNet state hand-over: the new entry points are part of the built library
+and the header, the ABI version stays 5, the shim's per-stream geometry is the engine's window arithmetic, and the flag conventions of
+FullSubNet.realtime_process hold before any GPU work starts."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import FSN_TINY, ROOT
+from speech_enhancement_mi_amd import engine
+
+NEW = ("fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state")
+CALLS = (((False, False, False), (8000, 5200, 3400)), ((True, False, True), (4800, 7000, 3300)))  # make_golden_fsn_chain.py
+
+
+def test_new_symbols_resolve_and_abi_stays_5():
+    lib = engine.load_library()
+    for name in NEW:
+        assert name in engine.EXPORTS, name
+        assert hasattr(lib, name), name
+    assert lib.se_abi_version() == 5
+    with open(os.path.join(ROOT, "include", "se_engine.h")) as f:
+        code = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    for name in NEW:
+        assert re.search(r"\bint\s+" + name + r"\s*\(", code), f"{name} is not declared in se_engine.h outside comments"
+    m = re.search(r"\bint\s+fsn_realtime_process_chains\s*\(([^)]*)\)\s*;", code)
+    assert [a.strip().split()[-1].lstrip("*") for a in m.group(1).split(",")] == \
+        ["e", "mixture", "batch", "max_length", "lengths_host", "flags_host", "out", "stream"]
+
+
+def _windows_of_fsn_realtime_process(length, flag, K):
+    """the lead / gap / Nseg arithmetic of fsn_realtime_process (csrc/fsn_engine.inc.h), restated: window count, offset of the first
+    window in the stream, samples stripped from the overlap average"""
+    P = K // 2
+    lead = 0 if flag else P
+    Lp = length + lead
+    gap = K - (P + Lp % K) % K
+    return 2 * (Lp + gap + P) // K, 0 * P - P - lead, lead
+
+
+@pytest.mark.parametrize("K", [3200, 400])
+def test_chain_geometry_is_the_engines_window_arithmetic(K):
+    for flags, lens in CALLS + (((True, True, False, False), (1, K, K // 2, K + 1)), ((False, True), (70000, 70000))):
+        g = engine.chain_geometry(lens, flags, K)
+        want = [_windows_of_fsn_realtime_process(l, f, K) for l, f in zip(lens, flags)]
+        assert g["Nb"] == [w[0] for w in want]
+        assert g["off0"] == [w[1] for w in want]
+        assert g["skip"] == [w[2] for w in want]
+        assert g["N"] == max(g["Nb"])
+    if K == 3200:
+        assert engine.chain_geometry(CALLS[0][1], CALLS[0][0], K)["Nb"] == [8, 6, 6]
+
+
+def test_fixture_is_committed_and_small():
+    g = np.load(os.path.join(ROOT, "tests", "golden", "fsn_chain_golden.npz"))
+    assert sorted(g.files) == sorted(f"call{c}_utt{b}" for c in (1, 2) for b in range(3))
+    for c, (_, lens) in enumerate(CALLS):
+        for b, l in enumerate(lens):
+            a = g[f"call{c + 1}_utt{b}"]
+            assert a.shape == (l,) and a.dtype == np.float32 and np.all(np.isfinite(a)) and np.any(a)
+
+
+def test_flag_conventions_of_fullsubnet_realtime_process():
+    """flag: a bool, ONE value, or one value per utterance (list or tensor of B).  The flags are parsed before the engine is looked up,
+    so on a CPU tensor a well-formed flag argument gets as far as the engine's "no CPU fallback" and a malformed one does not."""
+    from speech_enhancement_mi_amd.fullsubnet import FullSubNet
+    m = FullSubNet(**FSN_TINY)
+    x = torch.zeros(3, 3, 4000)
+    for flag in (False, True, torch.tensor([1]), [0], [True, False, True], torch.tensor([1, 0, 1]), torch.tensor([[1], [0], [0]])):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            m.realtime_process(x, flag=flag, train=False)
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            m.realtime_process(x, flag=flag, train=False, lengths=[4000, 3000, 100])
+    for flag in ([True, False], torch.tensor([1, 0, 1, 1])):
+        with pytest.raises(RuntimeError, match="flags for a batch of 3"):
+            m.realtime_process(x, flag=flag, train=False)
+    # train=True keeps refusing a continuation, per utterance too
+    for flag in (True, [False, True, False], torch.tensor([1])):
+        with pytest.raises(NotImplementedError):
+            m.realtime_process(x, x, flag=flag, train=True)
+    assert engine._flags_of(torch.tensor([1, 0, 1]), 3) == [True, False, True]
+    assert engine._flags_of([1], 3) is True and engine._flags_of(False, 3) is False
