@@ -122,6 +122,13 @@ int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, in
 int se_realtime_process_chains(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host,
                                const uint8_t *flags_host, float *out, void *stream);
 
+/* The segment geometry both engines give a stream of `length` samples cut into half-overlapping segments of segment_length: *nseg
+ * segments, the first starting at sample *off0 of the stream (-K/2 when it continues, -K after a reset, whose K/2 lead of zeros the
+ * overlap average strips again: *skip).  Host arithmetic only, no device, no engine: what every *_realtime_process* call computes per
+ * stream, exported so that a binding's own copy (engine.chain_geometry) can be checked against it.  SE_ERR_ARG on a non-positive
+ * size or a null pointer. */
+int se_chunk_geometry(int segment_length, int64_t length, int continues, int64_t *nseg, int64_t *off0, int64_t *skip);
+
 /* Per-stage entry points (parity tests; same arithmetic as inside se_step).
  * se_stft:    stft_trans  (CRN.py:505-512): seg [n, K] -> spec [n, F, T, 2]   (n = B*M rows)
  * se_istft:   istft_trans (CRN.py:514-520): spec [n, F, T, 2] -> wav [n, K]
@@ -164,7 +171,7 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
                               additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
-                              fsn_import_state */
+                              fsn_import_state; se_chunk_geometry */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);

@@ -24,10 +24,10 @@ struct fsn_engine {
     // CumLayerNorm step counters (fullsubnet.py:192-198): one int per stream and norm, on the device (k_fsn_runmean); 0 = no mean yet
     DevBuf step_fb, step_sb;
     // fsn_realtime_process_chains.  Bact > 0: the stages run for the prefix of Bact streams (grids, LSTM / GEMM / STFT rows); B stays every
-    // allocation and time stride.  chain_dev: int64 len[B] | off0[B] | skip[B], then int: the streams by ascending window count [B], the
-    // streams to zero at entry [B].  carry_*: the rows of the streams that ended before the longest one (state_rows.hip.h).
+    // allocation and time stride.  plan_dev: the device copy of the call's ChainPlan vectors (chain_plan.h).  carry_*: the rows of the
+    // streams that ended before the longest one (state_rows.hip.h, fsn_state_rows_of).
     int Bact = 0;
-    DevBuf chain_dev, carry_h[2][4], carry_c[2][4], carry_mean[2], carry_step[2];
+    DevBuf plan_dev, carry_h[2][4], carry_c[2][4], carry_mean[2], carry_step[2];
     // realtime_process: the full-band model of window n + 1 runs on `side` while the sub-band model of window n runs on the caller's stream
     // (the full-band recurrence is 42 launches of 32 workgroups per window, 11 % of the serial time, latency-bound: profiles/r03_fsn_*)
     hipStream_t side = nullptr;
@@ -361,6 +361,21 @@ int fsn_reset_on(fsn_engine *e, int batch, hipStream_t st) {
 
 }  // namespace
 
+// ---- WHERE a stream's carried state lives: f(live tensor, carry buffer, words per stream row) for every state tensor of model mi ----
+// mi 0 = the full-band set (h, c of every layer, mean_fb, step_fb), 1 = the sub-band set (the same of the sub-band model; its rows are
+// the stream's F sub-band rows).  h lives in the half hcur[l] points at NOW.  Stops at the first f that returns non-zero.
+template <class Fn>
+static int fsn_state_rows_of(fsn_engine *e, int mi, Fn &&f) {
+    static_assert(2 * 4 + 2 <= kStateRowsMax, "state row table too small");
+    fsn_engine::Model &m = mi ? e->sb : e->fb;
+    const long per = (long)(mi ? e->F : 1) * m.H;
+    int rc;
+    for (int l = 0; l < e->NL; l++)
+        if ((rc = f(m.h[l][m.hcur[l]].p, e->carry_h[mi][l], per)) || (rc = f(m.c[l].p, e->carry_c[mi][l], per))) return rc;
+    if ((rc = f(mi ? e->mean_sb.p : e->mean_fb.p, e->carry_mean[mi], 1L))) return rc;
+    return f(mi ? e->step_sb.p : e->step_fb.p, e->carry_step[mi], 1L);
+}
+
 extern "C" {
 
 const char *fsn_last_error(const fsn_engine *e) { return e ? e->err.c_str() : g_fsn_create_error.c_str(); }
@@ -420,7 +435,7 @@ void fsn_destroy(fsn_engine *e) {
         dev_free(m->fcw); dev_free(m->fcw_x); dev_free(m->fcb); dev_free(m->wcol); dev_free(m->fcw_t);
     }
     for (DevBuf *b : {&e->spec, &e->maskspec, &e->mag, &e->fb_seq, &e->fb_out, &e->sbin, &e->mask, &e->part_fb, &e->part_sb, &e->mean_fb,
-                      &e->mean_sb, &e->denom_fb, &e->denom_sb, &e->yseg, &e->step_fb, &e->step_sb, &e->chain_dev, &e->carry_mean[0], &e->carry_mean[1],
+                      &e->mean_sb, &e->denom_fb, &e->denom_sb, &e->yseg, &e->step_fb, &e->step_sb, &e->plan_dev, &e->carry_mean[0], &e->carry_mean[1],
                       &e->carry_step[0], &e->carry_step[1]})
         dev_free(*b);
     for (int mi = 0; mi < 2; mi++)
@@ -476,62 +491,31 @@ int fsn_forward(fsn_engine *e, const float *x, float *crm, void *stream) {
     return fsn_forward_dev(e, x, x + M * F * T, 2 * M * F * T, F * T, 1, T, crm, nullptr, 0, 0, 0, static_cast<hipStream_t>(stream));
 }
 
-// ---- per-stream state rows (state_rows.hip.h): which bit 0 = the full-band set (h, c of every layer, mean_fb, step_fb), bit 1 = the
-// sub-band set (the same of the sub-band model; its rows are the stream's F sub-band rows).  h lives in the half hcur[l] points at NOW.
-// dir 0: live -> carry (save), 1: carry -> live (restore), 2: zeros -> live.  One launch per set.
-static int fsn_chain_rows(fsn_engine *e, unsigned which, int dir, const int *streams, int nstreams, hipStream_t st) {
-    if (nstreams <= 0) return 0;
-    static_assert(2 * 4 + 2 <= kStateRowsMax, "state row table too small");
+// the rows of the streams a ChainPlan names: which bit mi = model mi, dir 0 save, 1 restore, 2 zero.  One launch per model.
+static int fsn_chain_rows(fsn_engine *e, unsigned which, int dir, StreamRange r, hipStream_t st) {
+    if (r.count <= 0) return 0;
     for (int mi = 0; mi < 2; mi++) {
         if (!(which & (1u << mi))) continue;
-        fsn_engine::Model &m = mi ? e->sb : e->fb;
-        StateRowTable t{};
-        int n = 0;
-        long wmax = 0;
-        auto add = [&](float *live, float *carry, long words) {
-            StateRow &r = t.r[n++];
-            r.src = reinterpret_cast<const uint32_t *>(dir == 0 ? live : dir == 1 ? carry : nullptr);
-            r.dst = reinterpret_cast<uint32_t *>(dir == 0 ? carry : live);
-            r.words = words;
-            wmax = std::max(wmax, words);
-        };
-        const long per = (long)(mi ? e->F : 1) * m.H;
-        for (int l = 0; l < e->NL; l++) {
-            add(m.h[l][m.hcur[l]].p, e->carry_h[mi][l].p, per);
-            add(m.c[l].p, e->carry_c[mi][l].p, per);
-        }
-        add(mi ? e->mean_sb.p : e->mean_fb.p, e->carry_mean[mi].p, 1);
-        add(mi ? e->step_sb.p : e->step_fb.p, e->carry_step[mi].p, 1);
-        launch_k_state_rows(st, t, n, streams, nstreams, wmax);
+        StateRowList rows;
+        fsn_state_rows_of(e, mi, [&](float *live, DevBuf &carry, long words) { rows.add(live, carry.p, words); return 0; });
+        rows.launch(st, dir, r.streams, r.count);
         FHIP(e, hipGetLastError());
     }
     return 0;
 }
 
 static int fsn_alloc_carry(fsn_engine *e) {
-    int rc;
-    for (int mi = 0; mi < 2; mi++) {
-        const fsn_engine::Model &m = mi ? e->sb : e->fb;
-        const size_t per = (size_t)(mi ? e->F : 1) * m.H;
-        for (int l = 0; l < e->NL; l++)
-            if ((rc = falloc(e, e->carry_h[mi][l], (size_t)e->B * per)) || (rc = falloc(e, e->carry_c[mi][l], (size_t)e->B * per))) return rc;
-        if ((rc = falloc(e, e->carry_mean[mi], e->B)) || (rc = falloc(e, e->carry_step[mi], e->B))) return rc;
-    }
-    return 0;
+    int rc = 0;
+    for (int mi = 0; mi < 2 && !rc; mi++)
+        rc = fsn_state_rows_of(e, mi, [&](float *, DevBuf &carry, long words) { return falloc(e, carry, (size_t)e->B * words); });
+    return rc;
 }
 
-// what a chains call adds to the window loop (null: the uniform call)
-struct FsnChain {
-    const long *len, *off0, *skip;  // device [B]: own length, first window's offset (-K/2 - lead), strip (lead)
-    const int *sorted;              // device [B]: streams by ascending window count
-    std::vector<int> le;            // le[k] = streams with at most k windows, k = 0 .. N: those whose LAST window is n are positions
-                                    // [le[n], le[n + 1]) of `sorted`
-    bool compact = false;           // window counts non-increasing: window n runs for the prefix of B - le[n] streams
-};
-
 // The windows of one realtime_process call on state that is ready: Nseg half-overlapping windows, window n of a stream starting at
-// n*K/2 - K/2 - lead (uniform) or n*K/2 + off0[b] (chains), STFT -> stage A -> stage B -> iSTFT, then the overlap average.
-static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long length, long Nseg, long lead, float *out, hipStream_t st, const FsnChain *ch) {
+// n*K/2 + off0 (uniform) or n*K/2 + ch->off0[b] (chains), STFT -> stage A -> stage B -> iSTFT, then the overlap average with `skip` (or
+// ch->skip[b]) stripped.  ch: the chains call's ChainPlan (chain_plan.h), null for the uniform call.
+static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long length, long Nseg, long off0, long skip, float *out, hipStream_t st,
+                           const ChainPlan *ch) {
     int rc;
     const long K = e->K, P = K / 2;
     if ((rc = falloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
@@ -545,18 +529,17 @@ static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long 
         FHIP(e, hipEventRecord(e->ev_fork, st));
         FHIP(e, hipStreamWaitEvent(sa, e->ev_fork, 0));
     }
-    struct Scope {  // a failing call leaves the engine usable: nothing of the chain outlives the call
+    struct Scope {  // a failing call leaves the engine usable: nothing of the plan outlives the call
         fsn_engine *e;
         ~Scope() { e->Bact = 0; e->sig->row_len = e->sig->row_off = nullptr; }
     } scope{e};
-    const bool saving = ch && ch->le[Nseg - 1] > 0;  // some stream ends before the longest one: save / restore is live
     if (ch) { e->sig->row_len = ch->len; e->sig->row_off = ch->off0; }
     for (long n = 0; n < Nseg; n++) {
-        const long off = ch ? n * P : n * P - P - lead;
+        const long off = n * P + (ch ? 0 : off0);
         const int slot = piped ? (int)(n & 1) : 0;
         const float *sp = e->spec.p + slot * spec_floats;
-        const int bact = ch && ch->compact ? batch - ch->le[n] : batch;
-        const int nlast = saving && n + 1 < Nseg ? ch->le[n + 1] - ch->le[n] : 0;  // streams whose last window this is (the call's last window saves nothing)
+        const int bact = ch ? ch->bact(n) : batch;
+        const StreamRange last = ch ? ch->ending(n) : StreamRange{nullptr, 0};  // the streams whose last window this is
         if (ch) e->Bact = bact;
         if (piped) {
             if (n >= 2) FHIP(e, hipStreamWaitEvent(sa, e->ev_done[slot], 0));          // window n - 2 has masked spectrum[slot]
@@ -566,19 +549,19 @@ static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long 
             return ffail(e, SE_ERR_HIP, "stft: %s", se_last_error(e->sig));
         if ((rc = fsn_stage_fb(e, sp, sp + 1, 2 * M * T * F, 2 * T * F, 2 * F, 2, sa))) return rc;
         // the full-band stage of window n + 1 runs ahead on `side`: the full-band rows of the streams that end here are kept now, on `side`
-        if (nlast && (rc = fsn_chain_rows(e, 1u, 0, ch->sorted + ch->le[n], nlast, sa))) return rc;
+        if ((rc = fsn_chain_rows(e, 1u, 0, last, sa))) return rc;
         if (piped) {
             FHIP(e, hipEventRecord(e->ev_ready[slot], sa));
             FHIP(e, hipStreamWaitEvent(st, e->ev_ready[slot], 0));
         }
         if ((rc = fsn_stage_sb(e, sp, sp + 1, 2 * M * T * F, 2 * F, 2, nullptr, ms, T * F, F, 1, st, piped ? e->ev_consumed[slot] : nullptr))) return rc;
-        if (nlast && (rc = fsn_chain_rows(e, 2u, 0, ch->sorted + ch->le[n], nlast, st))) return rc;  // stage B has joined `side2`
+        if ((rc = fsn_chain_rows(e, 2u, 0, last, st))) return rc;  // stage B has joined `side2`
         if (launch_istft(e->sig, ms, T * F, F, 1, bact, e->yseg.p + n * K, Nseg * K, st)) return ffail(e, SE_ERR_HIP, "istft: %s", se_last_error(e->sig));
         if (piped) FHIP(e, hipEventRecord(e->ev_done[slot], st));
     }
     // the streams that ended before the longest one get their own state back (the last stage B waited for everything on `side`)
-    if (saving && (rc = fsn_chain_rows(e, 3u, 1, ch->sorted, ch->le[Nseg - 1], st))) return rc;
-    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, lead, ch ? ch->len : nullptr,
+    if (ch && (rc = fsn_chain_rows(e, 3u, 1, ch->ended_early(), st))) return rc;
+    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, ch ? ch->len : nullptr,
                          ch ? ch->skip : nullptr);
     FHIP(e, hipGetLastError());
     return SE_OK;
@@ -595,71 +578,34 @@ int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t
         FHIP(e, hipSetDevice(e->device));
         if ((rc = fsn_prepare(e))) return rc;
     }
-    const long K = e->K, P = K / 2, lead = flag ? 0 : P, Lp = length + lead;
-    const long gap = K - (P + Lp % K) % K, Nseg = 2 * (Lp + gap + P) / K;
-    return fsn_run_windows(e, mixture, batch, length, Nseg, lead, out, st, nullptr);
+    const ChunkGeometry g = chunk_geometry(e->K, length, flag);
+    return fsn_run_windows(e, mixture, batch, length, g.nseg, g.off0, g.skip, out, st, nullptr);
 }
 
-// A batch of chunk chains: one flag and one length per stream, every stream leaves the state it would carry alone (include/se_engine.h)
+// A batch of chunk chains (include/se_engine.h): reset or prepare, plan (chain_plan.h), upload, zero the flag-0 rows and counters, run
 int fsn_realtime_process_chains(fsn_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host,
                                 float *out, void *stream) {
     if (!e || !mixture || !out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
-    bool any = false, all = true, full = true;
-    for (int b = 0; b < batch; b++) {
-        if (lengths_host[b] <= 0 || lengths_host[b] > max_length)
-            return ffail(e, SE_ERR_ARG, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths_host[b], (long long)max_length);
-        any = any || flags_host[b];
-        all = all && flags_host[b];
-        full = full && lengths_host[b] == max_length;
-    }
-    if (any && e->B <= 0) return ffail(e, SE_ERR_STATE, "a stream continues (flag set) but the engine carries no state");
-    if (any && e->B != batch) return ffail(e, SE_ERR_STATE, "a stream continues (flag set) in a batch of %d but the carried state holds %d streams", batch, e->B);
-    if (full && (all || !any)) return fsn_realtime_process(e, mixture, batch, max_length, all ? 1 : 0, out, stream);  // a uniform batch
+    ChainPlan plan;
+    std::string err;
+    int uniform_flag = 0;
+    int rc = plan_chains(plan, e->K, batch, max_length, lengths_host, flags_host, e->B, &uniform_flag, err);
+    if (rc == kPlanUniform) return fsn_realtime_process(e, mixture, batch, max_length, uniform_flag, out, stream);
+    if (rc) return ffail(e, rc, "%s", err.c_str());
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    if (!any) rc = fsn_reset_on(e, batch, st);
+    if (!plan.continues()) rc = fsn_reset_on(e, batch, st);
     else {
         FHIP(e, hipSetDevice(e->device));
         rc = fsn_prepare(e);
     }
     if (rc) return rc;
-    // every stream keeps the geometry it has alone (the lead / gap / Nseg arithmetic of fsn_realtime_process with its own lead)
-    const long K = e->K, P = K / 2;
-    const int B = batch;
-    std::vector<int64_t> geo((size_t)4 * B);  // len | off0 | skip | (int) sorted streams, flag-0 streams: one upload
-    std::vector<int> nb(B), idx((size_t)2 * B, 0);
-    int N = 0, nzero = 0;
-    for (int b = 0; b < B; b++) {
-        const long lead = flags_host[b] ? 0 : P, Lp = lengths_host[b] + lead, gap = K - (P + Lp % K) % K;
-        nb[b] = (int)(2 * (Lp + gap + P) / K);
-        N = std::max(N, nb[b]);
-        geo[b] = lengths_host[b];
-        geo[(size_t)B + b] = -P - lead;
-        geo[2 * (size_t)B + b] = lead;
-        idx[b] = b;
-        if (!flags_host[b]) idx[B + nzero++] = b;
-    }
-    std::stable_sort(idx.begin(), idx.begin() + B, [&](int a, int b) { return nb[a] < nb[b]; });
-    memcpy(geo.data() + 3 * (size_t)B, idx.data(), (size_t)2 * B * sizeof(int));
-    FsnChain ch;
-    ch.le.assign((size_t)N + 1, 0);
-    for (int b = 0; b < B; b++) ch.le[nb[b]]++;
-    for (int k = 1; k <= N; k++) ch.le[k] += ch.le[k - 1];
-    if ((rc = falloc(e, e->chain_dev, (size_t)8 * B)) || (rc = fsn_alloc_carry(e))) return rc;
-    static_assert(sizeof(long) == sizeof(int64_t), "per-stream geometry is passed to the kernels as long");
-    FHIP(e, hipMemcpyAsync(e->chain_dev.p, geo.data(), (size_t)4 * B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if ((rc = falloc(e, e->plan_dev, plan.staging_floats())) || (rc = fsn_alloc_carry(e))) return rc;
+    FHIP(e, hipMemcpyAsync(e->plan_dev.p, plan.staging.data(), plan.staging.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     FHIP(e, hipStreamSynchronize(st));  // the staging vector and the host arrays live for the call only
-    const long *dev64 = reinterpret_cast<const long *>(e->chain_dev.p);
-    const int *dev32 = reinterpret_cast<const int *>(dev64 + 3 * (size_t)B);
-    ch.len = dev64; ch.off0 = dev64 + B; ch.skip = dev64 + 2 * (size_t)B;
-    ch.sorted = dev32;
+    plan.carve(e->plan_dev.p);
     // a reset among continuing streams: zero those streams' rows and counters (fsn_reset_stream for any number of streams in two launches)
-    if (any && (rc = fsn_chain_rows(e, 3u, 2, dev32 + B, nzero, st))) return rc;
-    // prefix compaction: the streams still running in window n are a prefix of the batch when the WINDOW COUNTS are non-increasing (a
-    // reset stream has one lead more than a continuing one); the streams beyond the prefix are exactly those whose rows were saved
-    ch.compact = true;
-    for (int b = 1; b < B; b++) ch.compact = ch.compact && nb[b] <= nb[b - 1];
-    return fsn_run_windows(e, mixture, batch, max_length, N, 0, out, st, &ch);
+    if (plan.continues() && (rc = fsn_chain_rows(e, 3u, 2, plan.reset_streams(), st))) return rc;
+    return fsn_run_windows(e, mixture, batch, max_length, plan.N, 0, 0, out, st, &plan);
 }
 
 // reset_state + both CumLayerNorm.reset() (fullsubnet.py:826-832, 203-205) for ONE stream of the carried batch
@@ -669,17 +615,13 @@ int fsn_reset_stream(fsn_engine *e, int stream_index, void *stream) {
     if (stream_index < 0 || stream_index >= e->B) return ffail(e, SE_ERR_ARG, "stream index %d outside the batch of %d", stream_index, e->B);
     FHIP(e, hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t b = (size_t)stream_index;
-    for (int mi = 0; mi < 2; mi++) {
-        fsn_engine::Model &m = mi ? e->sb : e->fb;
-        const size_t per = (size_t)(mi ? e->F : 1) * m.H;
-        for (int l = 0; l < e->NL; l++) {
-            FHIP(e, hipMemsetAsync(m.h[l][m.hcur[l]].p + per * b, 0, per * sizeof(float), st));
-            FHIP(e, hipMemsetAsync(m.c[l].p + per * b, 0, per * sizeof(float), st));
-        }
-    }
-    for (DevBuf *w : {&e->mean_fb, &e->mean_sb, &e->step_fb, &e->step_sb}) FHIP(e, hipMemsetAsync(w->p + b, 0, sizeof(float), st));
-    return SE_OK;
+    int rc = 0;
+    for (int mi = 0; mi < 2 && !rc; mi++)
+        rc = fsn_state_rows_of(e, mi, [&](float *live, DevBuf &, long words) {
+            FHIP(e, hipMemsetAsync(live + words * stream_index, 0, (size_t)words * sizeof(float), st));
+            return 0;
+        });
+    return rc;
 }
 
 // the tensor behind a state name: fh / fc / sh / sc -> per layer (l < NL) a device pointer and its length; mean_* / step_* -> one vector

@@ -33,6 +33,7 @@
 #include "norm.hip.h"
 #include "stft.hip.h"
 #include "state_rows.hip.h"
+#include "chain_plan.h"
 
 using namespace se;
 
@@ -121,25 +122,18 @@ struct se_engine {
     DevBuf enc_stats[SE_MAX_LEVELS], dec_stats[SE_MAX_LEVELS], skip_stats[SE_MAX_LEVELS];  // [B][slots][2] norm partials
     DevBuf pin[3][2], pre_g, pre_stats[3];  // CRN_ELU preconv chain (inputs ping-ponged: they carry 4 history columns)
     DevBuf yseg;
-    DevBuf ragged_len;       // se_realtime_process_ragged: per-stream lengths (int64) on the device
-    // per-stream geometry of the running call (device int64 [B]; null outside a ragged / chains call): valid samples, first-segment
-    // offset, strip of the overlap-average
-    const long *row_len = nullptr, *row_off = nullptr, *row_skip = nullptr;
-    // se_realtime_process_chains (state_rows.hip.h).  chain_dev: int64 len[B] | off0[B] | skip[B], then int: the streams by ascending
-    // segment count [B] | the streams with flag 0 [B].  carry_*: one row per stream in the live tensors' row layout, filled when a
-    // stream's last segment has passed the stage that owns the tensor, written back at call exit.
-    DevBuf chain_dev, carry_x[SE_MAX_LEVELS], carry_p[3], carry_h[4];
-    bool chain_on = false;         // some stream ends before the longest one: save / restore is live
-    int chain_nseg = 0;            // N = segments of the longest stream
-    const int *chain_sorted = nullptr;  // device: streams by ascending segment count
-    std::vector<int> chain_le;     // chain_le[k] = streams with at most k segments, k = 0 .. N: those whose last segment is n are
-                                   // positions [chain_le[n], chain_le[n + 1]) of chain_sorted
-    // Prefix compaction of a ragged batch: every layout is stream-major, so when the lengths are non-increasing the streams that still take
-    // part in segment n are a PREFIX of the batch and every launch of that segment simply covers Bact < B streams (grids, GEMM rows, GRU
-    // rows); strides and plane sizes stay those of the allocation batch B.  Bact is set per stage call by se_realtime_process.
+    // A ragged / chains call is described by its ChainPlan (chain_plan.h), which run_segments gets as an argument.  What the engine keeps:
+    // plan_dev, the device copy of the plan's per-stream vectors (8 * B floats); row_len / row_off, the plan's lengths and first-segment
+    // offsets for launch_stft (device int64 [B]; set and cleared by run_segments, the FullSubNet engine sets them on its `sig`); carry_*,
+    // one row per stream in the live tensors' row layout (state_rows_of), filled when a stream's last segment has passed the stage that
+    // owns the tensor, written back at call exit.
+    const long *row_len = nullptr, *row_off = nullptr;
+    DevBuf plan_dev, carry_x[SE_MAX_LEVELS], carry_p[3], carry_h[4];
+    // Prefix compaction: every layout is stream-major, so when the plan is `compact` the streams that still take part in segment n are a
+    // PREFIX of the batch and every launch of that segment simply covers Bact = plan->bact(n) < B streams (grids, GEMM rows, GRU rows);
+    // strides and plane sizes stay those of the allocation batch B.  Bact is set per stage call by run_segments.
     int Bact = 0;
     int bact_slot[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // launch batch of the segment living in each ring slot (the lagged GRU rounds mix segments)
-    std::vector<int> ragged_nseg;  // per stream: segments it takes part in (empty: all)
     // plane-layout convolution path (conv_p.hip.h, convp_engine.inc.h): activations as split-bf16 planes
     struct se_convp_state *cp = nullptr;
     // plane-layout bottleneck GEMMs (k_gemm_p): A operands arrive as split-bf16 planes from their producers
@@ -1060,6 +1054,27 @@ int tap_p_to_f32_dev(se_engine *e, const float *psrc, int C, int F, float *dst, 
 }
 }  // namespace
 
+// ---- WHERE a stream's carried state lives: f(live tensor, carry buffer, words per stream row) for every state tensor in `which` ----
+// which: bit 0 = encoder rows (conv history of every level + preconv history) in ring slot e->slot / parity e->parity, bit (1 + l) = h of
+// GRU layer l in its current half.  Stream b's row starts at live + b * words.  Stops at the first f that returns non-zero.
+template <class F>
+static int state_rows_of(se_engine *e, unsigned which, F &&f) {
+    static_assert(SE_MAX_LEVELS + 3 + 4 <= kStateRowsMax, "state row table too small");
+    int rc;
+    if (which & 1u) {
+        for (int i = 0; i < e->L; i++)  // [slot][b][C8][PL][T][F] pieces of 16 bytes
+            if ((rc = f(e->cp->xinP[i].p + (size_t)e->slot * e->cp->slot_elems[i] * 4, e->carry_x[i], (long)(e->cp->slot_elems[i] / e->B) * 4))) return rc;
+        for (int i = 0; i < e->npre; i++) {
+            if (e->cp->pre_p) rc = f(e->cp->pinP[i].p + (size_t)e->slot * e->cp->pslot_elems * 4, e->carry_p[i], (long)(e->cp->pslot_elems / e->B) * 4);
+            else rc = f(e->pin[i][e->parity].p, e->carry_p[i], (long)e->Ch[0] * e->T * e->F[0]);
+            if (rc) return rc;
+        }
+    }
+    for (int l = 0; l < e->NL; l++)
+        if ((which & (2u << l)) && (rc = f(e->hbuf[l][e->hcur[l]].p, e->carry_h[l], (long)e->H))) return rc;
+    return 0;
+}
+
 extern "C" {
 
 int se_abi_version(void) { return 5; }
@@ -1163,7 +1178,7 @@ void se_destroy(se_engine *e) {
     DevBuf *singles[] = {&e->window, &e->env, &e->tw, &e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
                          &e->fcw_x, &e->wih_xp, &e->fcw_xp, &e->fcb_p, &e->gnw_p, &e->gnb_p, &e->fc_stats, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
     for (DevBuf *b : singles) dev_free(*b);
-    dev_free(e->ragged_len); dev_free(e->chain_dev);
+    dev_free(e->plan_dev);
     for (DevBuf &b : e->carry_x) dev_free(b);
     for (DevBuf &b : e->carry_p) dev_free(b);
     for (DevBuf &b : e->carry_h) dev_free(b);
@@ -1309,24 +1324,11 @@ int se_reset_stream(se_engine *e, int stream_index, void *stream) {
     if (stream_index < 0 || stream_index >= e->B) return fail(e, SE_ERR_ARG, "stream index %d outside the batch of %d", stream_index, e->B);
     HIPCHECK(e, hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int T = e->T, H = e->H, b = stream_index;
     // conv time buffers = the tail of the current ring slot (the next window reads it as history)
-    for (int i = 0; i < e->L; i++) {  // [slot][b][C8][PL][T][F] pieces of 16 bytes
-        const size_t per16 = (size_t)(e->cp->slot_elems[i] / e->B);
-        HIPCHECK(e, hipMemsetAsync(e->cp->xinP[i].p + ((size_t)e->slot * e->cp->slot_elems[i] + per16 * b) * 4, 0, per16 * 16, st));
-    }
-    for (int i = 0; i < e->npre; i++) {
-        if (e->cp->pre_p) {
-            const size_t per16 = (size_t)(e->cp->pslot_elems / e->B);
-            HIPCHECK(e, hipMemsetAsync(e->cp->pinP[i].p + ((size_t)e->slot * e->cp->pslot_elems + per16 * b) * 4, 0, per16 * 16, st));
-            continue;
-        }
-        const size_t per = (size_t)e->Ch[0] * T * e->F[0];
-        HIPCHECK(e, hipMemsetAsync(e->pin[i][e->parity].p + per * b, 0, per * sizeof(float), st));
-    }
-    for (int l = 0; l < e->NL; l++)
-        HIPCHECK(e, hipMemsetAsync(e->hbuf[l][e->hcur[l]].p + (size_t)H * b, 0, (size_t)H * sizeof(float), st));
-    return SE_OK;
+    return state_rows_of(e, ~0u, [&](float *live, DevBuf &, long words) {
+        HIPCHECK(e, hipMemsetAsync(live + words * stream_index, 0, (size_t)words * sizeof(float), st));
+        return 0;
+    });
 }
 
 int se_forward(se_engine *e, const float *x, float *y, void *stream) {
@@ -1389,68 +1391,34 @@ int se_step(se_engine *e, const float *wav_in, float *wav_out, void *stream) {
     return step_dev(e, wav_in, (long)e->M * e->K, e->K, 0, e->K, wav_out, e->K, static_cast<hipStream_t>(stream));
 }
 
-// ---- per-stream state rows (state_rows.hip.h): the live tensors a stream's carried state lives in, as table entries ----
-// which: bit 0 = encoder rows (conv history of every level + preconv history) in ring slot e->slot / parity e->parity, bit (1 + l) = h of
-// GRU layer l in its current half.  dir 0: live -> carry (save), 1: carry -> live (restore), 2: zeros -> live.
-static int chain_rows(se_engine *e, unsigned which, int dir, const int *streams, int nstreams, hipStream_t st) {
-    if (nstreams <= 0) return 0;
-    StateRowTable t{};
-    int n = 0;
-    long wmax = 0;
-    auto add = [&](float *live, float *carry, long words) {
-        StateRow &r = t.r[n++];
-        r.src = reinterpret_cast<const uint32_t *>(dir == 0 ? live : dir == 1 ? carry : nullptr);
-        r.dst = reinterpret_cast<uint32_t *>(dir == 0 ? carry : live);
-        r.words = words;
-        wmax = std::max(wmax, words);
-    };
-    static_assert(SE_MAX_LEVELS + 3 + 4 <= kStateRowsMax, "state row table too small");
-    if (which & 1u) {
-        for (int i = 0; i < e->L; i++) {  // [slot][b][C8][PL][T][F] pieces of 16 bytes
-            const long per16 = e->cp->slot_elems[i] / e->B;
-            add(e->cp->xinP[i].p + (size_t)e->slot * e->cp->slot_elems[i] * 4, e->carry_x[i].p, per16 * 4);
-        }
-        for (int i = 0; i < e->npre; i++) {
-            if (e->cp->pre_p) {
-                const long per16 = e->cp->pslot_elems / e->B;
-                add(e->cp->pinP[i].p + (size_t)e->slot * e->cp->pslot_elems * 4, e->carry_p[i].p, per16 * 4);
-            } else {
-                add(e->pin[i][e->parity].p, e->carry_p[i].p, (long)e->Ch[0] * e->T * e->F[0]);
-            }
-        }
-    }
-    for (int l = 0; l < e->NL; l++)
-        if (which & (2u << l)) add(e->hbuf[l][e->hcur[l]].p, e->carry_h[l].p, e->H);
+// ---- per-stream state rows (state_rows.hip.h) of the streams a ChainPlan names: dir 0 save, 1 restore, 2 zero ----
+static int chain_rows(se_engine *e, unsigned which, int dir, StreamRange r, hipStream_t st) {
+    if (r.count <= 0) return 0;
+    StateRowList rows;
+    state_rows_of(e, which, [&](float *live, DevBuf &carry, long words) { rows.add(live, carry.p, words); return 0; });
     ProfScope ps(e, "k_state_rows", dir == 0 ? "state_save" : dir == 1 ? "state_restore" : "state_zero", 0, st);
-    launch_k_state_rows(st, t, n, streams, nstreams, wmax);
+    rows.launch(st, dir, r.streams, r.count);
     HIPCHECK(e, hipGetLastError());
     return 0;
 }
 
-// the streams whose LAST segment is n keep what the stage(s) in `which` have just left behind (nothing when no stream ends there, or
-// when n is the last segment of the call: those streams' state is already where it belongs)
-static int chain_save(se_engine *e, long n, unsigned which, hipStream_t st) {
-    if (!e->chain_on || n + 1 >= e->chain_nseg) return 0;
-    const int lo = e->chain_le[n], hi = e->chain_le[n + 1];
-    return chain_rows(e, which, 0, e->chain_sorted + lo, hi - lo, st);
+// the streams whose LAST segment is n keep what the stage(s) in `which` have just left behind
+static int chain_save(se_engine *e, const ChainPlan *plan, long n, unsigned which, hipStream_t st) {
+    return plan ? chain_rows(e, which, 0, plan->ending(n), st) : 0;
 }
 
 static int alloc_carry(se_engine *e) {
-    int rc;
-    for (int i = 0; i < e->L; i++)
-        if ((rc = dev_alloc(e, e->carry_x[i], (size_t)e->cp->slot_elems[i] * 4))) return rc;
-    for (int i = 0; i < e->npre; i++)
-        if ((rc = dev_alloc(e, e->carry_p[i], e->cp->pre_p ? (size_t)e->cp->pslot_elems * 4 : (size_t)e->B * e->Ch[0] * e->T * e->F[0]))) return rc;
-    for (int l = 0; l < e->NL; l++)
-        if ((rc = dev_alloc(e, e->carry_h[l], (size_t)e->B * e->H))) return rc;
-    return 0;
+    return state_rows_of(e, ~0u, [&](float *, DevBuf &carry, long words) { return dev_alloc(e, carry, (size_t)e->B * words); });
 }
 
 // The segments of one realtime_process call on state that is ready: Nseg half-overlapping windows, window n of a stream starting at
-// off_first + n * K/2 (+ the stream's own e->row_off), overlap-average with `skip` (or e->row_skip) stripped -> out [batch, length].
-static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st);
+// off_first + n * K/2 (+ the stream's own plan->off0), overlap-average with `skip` (or plan->skip) stripped -> out [batch, length].
+// plan: the ragged / chains call's ChainPlan (chain_plan.h), null for a uniform call.
+static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st,
+                        const ChainPlan *plan);
 
-int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
+// se_realtime_process, and se_realtime_process_ragged with its plan
+static int process_uniform(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream, const ChainPlan *plan) {
     if (!e || !mixture || !out || batch <= 0 || length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     int rc;
     if (!flag) {
@@ -1459,16 +1427,23 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
         if (e->B != batch) return fail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
         if ((rc = ensure_ready(e))) return rc;
     }
-    const long K = e->K, P = K / 2;
-    const long lead = flag ? 0 : P;                      // CRN.py:568-570
-    const long Lp = length + lead;
-    const long gap = K - (P + Lp % K) % K;               // utility.py:327-329
-    const long Nseg = 2 * (Lp + gap + P) / K;            // utility.py:360-368
-    // segment n covers padded[n*P, n*P+K) with padded = [0]*P | [0]*lead | x | zeros; the strip is the lead (CRN.py:587-588)
-    return run_segments(e, mixture, batch, length, Nseg, -P - lead, lead, out, static_cast<hipStream_t>(stream));
+    const ChunkGeometry g = chunk_geometry(e->K, length, flag);
+    return run_segments(e, mixture, batch, length, g.nseg, g.off0, g.skip, out, static_cast<hipStream_t>(stream), plan);
 }
 
-static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st) {
+int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
+    return process_uniform(e, mixture, batch, length, flag, out, stream, nullptr);
+}
+
+int se_chunk_geometry(int segment_length, int64_t length, int continues, int64_t *nseg, int64_t *off0, int64_t *skip) {
+    if (segment_length <= 0 || length <= 0 || !nseg || !off0 || !skip) return SE_ERR_ARG;
+    const ChunkGeometry g = chunk_geometry(segment_length, length, continues != 0);
+    *nseg = g.nseg; *off0 = g.off0; *skip = g.skip;
+    return SE_OK;
+}
+
+static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st,
+                        const ChainPlan *plan) {
     int rc;
     const long K = e->K, P = K / 2;
     if ((rc = dev_alloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
@@ -1477,23 +1452,22 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
         e->pipeline = 0;
         piped = false;
     }
-    // launch batch of segment n: with non-increasing lengths the streams still running are a prefix of the batch (see se_engine::Bact)
+    // launch batch of segment n: the prefix of streams still running when the plan is compact (see se_engine::Bact)
     static const bool compact_env = [] { const char *v = getenv("SE_RAGGED_COMPACT"); return !(v && v[0] == '0'); }();
-    const bool compact = compact_env && !e->ragged_nseg.empty() && e->gemm_p && e->variant == 0;
-    auto bact_of = [&](long n) {
-        if (!compact) return e->B;
-        int c = 0;
-        while (c < e->B && e->ragged_nseg[c] > n) c++;
-        return std::max(c, 1);
-    };
-    struct RestoreBact { se_engine *e; ~RestoreBact() { e->Bact = e->B; for (int &v : e->bact_slot) v = e->B; } } restore_bact{e};
+    const bool compact = compact_env && plan && e->gemm_p && e->variant == 0;
+    auto bact_of = [&](long n) { return compact ? plan->bact(n) : e->B; };
+    struct RestoreBact {  // a failing call leaves the engine usable: nothing of the plan outlives the call
+        se_engine *e;
+        ~RestoreBact() { e->Bact = e->B; for (int &v : e->bact_slot) v = e->B; e->row_len = e->row_off = nullptr; }
+    } restore_bact{e};
+    if (plan) { e->row_len = plan->len; e->row_off = plan->off0; }
     if (!piped) {
         for (long n = 0; n < Nseg; n++) {
             const long off = off_first + n * P;
             e->Bact = bact_of(n);
             // yseg is [B][Nseg][K]: the iSTFT writes segment n of every stream with row stride Nseg*K
             if ((rc = step_dev(e, mixture, (long)e->M * length, length, off, length, e->yseg.p + n * K, Nseg * K, st))) return rc;
-            if ((rc = chain_save(e, n, ~0u, st))) return rc;
+            if ((rc = chain_save(e, plan, n, ~0u, st))) return rc;
         }
     } else {
         // Segments are sequentially dependent only WITHIN a stage (conv history, GRU state), so the three stages run as a
@@ -1530,7 +1504,7 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
                     if (i >= kRing) HIPCHECK(e, hipStreamWaitEvent(sE, e->ev_dec[cur], 0));  // slot cur was last read by the decoder of segment i - kRing
                     if ((rc = run_encoder(e, cur, prev, spec, M * T * F, T * F, F, 1, sE))) return rc;
                     if ((rc = stage_gru_proj0(e, cur, sE))) return rc;
-                    if ((rc = chain_save(e, c0 + i, 1u, sE))) return rc;  // before the encoder stream reuses the slot, kRing segments on
+                    if ((rc = chain_save(e, plan, c0 + i, 1u, sE))) return rc;  // before the encoder stream reuses the slot, kRing segments on
                     HIPCHECK(e, hipEventRecord(e->ev_enc[cur], sE));
                     HIPCHECK(e, hipStreamWaitEvent(sG, e->ev_enc[cur], 0));
                 }
@@ -1542,13 +1516,13 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
                         if (i - l >= 0 && i - l < cn) slots[l] = slot_of(i - l);
                     if ((rc = stage_gru_round(e, slots, sG))) return rc;
                     for (int l = 0; l < NL; l++)  // layer l has just finished segment i - l
-                        if (slots[l] >= 0 && (rc = chain_save(e, c0 + i - l, 2u << l, sG))) return rc;
+                        if (slots[l] >= 0 && (rc = chain_save(e, plan, c0 + i - l, 2u << l, sG))) return rc;
                     done = i - (NL - 1);
                 } else {
                     e->Bact = e->bact_slot[slot_of(i)];
                     for (int l = 0; l < NL; l++)
                         if ((rc = stage_gru_layer(e, l, slot_of(i), sG, /*overlapped=*/true))) return rc;
-                    if ((rc = chain_save(e, c0 + i, ~1u, sG))) return rc;
+                    if ((rc = chain_save(e, plan, c0 + i, ~1u, sG))) return rc;
                     done = i;
                 }
                 if (done < 0 || done >= cn) continue;
@@ -1575,8 +1549,9 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
         }
     }
     // the streams that ended before the longest one get their own state back (the stage streams have joined `st`)
-    if (e->chain_on && (rc = chain_rows(e, ~0u, 1, e->chain_sorted, e->chain_le[Nseg - 1], st))) return rc;
-    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, e->row_len, e->row_skip);
+    if (plan && (rc = chain_rows(e, ~0u, 1, plan->ended_early(), st))) return rc;
+    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, plan ? plan->len : nullptr,
+                         plan ? plan->skip : nullptr);
     HIPCHECK(e, hipGetLastError());
     return SE_OK;
 }
@@ -1584,94 +1559,38 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
 int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, int flag, float *out,
                                void *stream) {
     if (!e || !lengths_host || batch <= 0) return fail(e, SE_ERR_ARG, "bad argument");
-    for (int b = 0; b < batch; b++)
-        if (lengths_host[b] <= 0 || lengths_host[b] > max_length) return fail(e, SE_ERR_ARG, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths_host[b], (long long)max_length);
-    int rc = dev_alloc(e, e->ragged_len, (size_t)batch * 2);
-    if (rc) return rc;
-    static_assert(sizeof(long) == sizeof(int64_t), "per-stream lengths are passed to the kernels as long");
-    HIPCHECK(e, hipMemcpyAsync(e->ragged_len.p, lengths_host, (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+    // segments stream b takes part in (the count it would have alone), for the prefix compaction; only when the lengths are non-increasing
+    // (the Python shim sorts the batch), otherwise every stream runs every segment
+    ChainPlan plan;
+    std::string err;
+    int rc = plan_ragged(plan, e->K, batch, max_length, lengths_host, flag, err);
+    if (rc) return fail(e, rc, "%s", err.c_str());
+    if ((rc = dev_alloc(e, e->plan_dev, (size_t)batch * 2))) return rc;
+    HIPCHECK(e, hipMemcpyAsync(e->plan_dev.p, lengths_host, (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
     HIPCHECK(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));  // the host array is borrowed for the call only
-    // segments stream b takes part in (the count it would have alone: utility.py:327-329, 360-368), for the prefix compaction; only when the
-    // lengths are non-increasing (the Python shim sorts the batch), otherwise every stream runs every segment as before
-    e->ragged_nseg.clear();
-    bool sorted = true;
-    for (int b = 1; b < batch; b++) sorted = sorted && lengths_host[b] <= lengths_host[b - 1];
-    if (sorted) {
-        const long K = e->K, P = K / 2, lead = flag ? 0 : P;
-        for (int b = 0; b < batch; b++) {
-            const long Lp = lengths_host[b] + lead, gap = K - (P + Lp % K) % K;
-            e->ragged_nseg.push_back((int)(2 * (Lp + gap + P) / K));
-        }
-    }
-    e->row_len = reinterpret_cast<const long *>(e->ragged_len.p);
-    rc = se_realtime_process(e, mixture, batch, max_length, flag, out, stream);
-    e->row_len = nullptr;
-    e->ragged_nseg.clear();
-    return rc;
+    plan.len = reinterpret_cast<const long *>(e->plan_dev.p);
+    return process_uniform(e, mixture, batch, max_length, flag, out, stream, &plan);
 }
 
+// A batch of chunk chains (include/se_engine.h): reset or make ready, plan (chain_plan.h), upload, zero the flag-0 rows, run
 int se_realtime_process_chains(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host,
                                const uint8_t *flags_host, float *out, void *stream) {
     if (!e || !mixture || !out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
-    bool any = false, all = true, full = true;
-    for (int b = 0; b < batch; b++) {
-        if (lengths_host[b] <= 0 || lengths_host[b] > max_length) return fail(e, SE_ERR_ARG, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths_host[b], (long long)max_length);
-        any = any || flags_host[b];
-        all = all && flags_host[b];
-        full = full && lengths_host[b] == max_length;
-    }
-    if (any && e->B <= 0) return fail(e, SE_ERR_STATE, "a stream continues (flag set) but the engine carries no state");
-    if (any && e->B != batch) return fail(e, SE_ERR_STATE, "a stream continues (flag set) in a batch of %d but the carried state holds %d streams", batch, e->B);
-    if (full && (all || !any)) return se_realtime_process(e, mixture, batch, max_length, all ? 1 : 0, out, stream);  // a uniform batch
+    ChainPlan plan;
+    std::string err;
+    int uniform_flag = 0;
+    int rc = plan_chains(plan, e->K, batch, max_length, lengths_host, flags_host, e->B, &uniform_flag, err);
+    if (rc == kPlanUniform) return se_realtime_process(e, mixture, batch, max_length, uniform_flag, out, stream);
+    if (rc) return fail(e, rc, "%s", err.c_str());
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    if (!any) rc = reset_on_stream(e, batch, st);
-    else rc = ensure_ready(e);
-    if (rc) return rc;
-    // every stream keeps the geometry it has alone (utility.py:327-329, 360-368 with its own lead)
-    const long K = e->K, P = K / 2;
-    const int B = batch;
-    std::vector<int64_t> geo((size_t)4 * B);  // len | off0 | skip | (int) sorted streams, flag-0 streams: one upload
-    std::vector<int> nb(B), idx((size_t)2 * B, 0);
-    int N = 0, nzero = 0;
-    for (int b = 0; b < B; b++) {
-        const long lead = flags_host[b] ? 0 : P, Lp = lengths_host[b] + lead, gap = K - (P + Lp % K) % K;
-        nb[b] = (int)(2 * (Lp + gap + P) / K);
-        N = std::max(N, nb[b]);
-        geo[b] = lengths_host[b];
-        geo[(size_t)B + b] = -P - lead;
-        geo[2 * (size_t)B + b] = lead;
-        idx[b] = b;
-        if (!flags_host[b]) idx[B + nzero++] = b;
-    }
-    std::stable_sort(idx.begin(), idx.begin() + B, [&](int a, int b) { return nb[a] < nb[b]; });
-    memcpy(geo.data() + 3 * (size_t)B, idx.data(), (size_t)2 * B * sizeof(int));
-    e->chain_le.assign((size_t)N + 1, 0);
-    for (int b = 0; b < B; b++) e->chain_le[nb[b]]++;
-    for (int k = 1; k <= N; k++) e->chain_le[k] += e->chain_le[k - 1];
-    if ((rc = dev_alloc(e, e->chain_dev, (size_t)8 * B)) || (rc = alloc_carry(e))) return rc;
-    static_assert(sizeof(long) == sizeof(int64_t), "per-stream geometry is passed to the kernels as long");
-    HIPCHECK(e, hipMemcpyAsync(e->chain_dev.p, geo.data(), (size_t)4 * B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if ((rc = plan.continues() ? ensure_ready(e) : reset_on_stream(e, batch, st))) return rc;
+    if ((rc = dev_alloc(e, e->plan_dev, plan.staging_floats())) || (rc = alloc_carry(e))) return rc;
+    HIPCHECK(e, hipMemcpyAsync(e->plan_dev.p, plan.staging.data(), plan.staging.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHECK(e, hipStreamSynchronize(st));  // the staging vector and the host arrays live for the call only
-    const long *dev64 = reinterpret_cast<const long *>(e->chain_dev.p);
-    const int *dev32 = reinterpret_cast<const int *>(dev64 + 3 * (size_t)B);
+    plan.carve(e->plan_dev.p);
     // a reset among continuing streams: zero those streams' rows (se_reset_stream for any number of streams in one launch)
-    if (any && (rc = chain_rows(e, ~0u, 2, dev32 + B, nzero, st))) return rc;
-    struct Scope {
-        se_engine *e;
-        ~Scope() { e->row_len = e->row_off = e->row_skip = nullptr; e->chain_on = false; e->chain_sorted = nullptr; e->ragged_nseg.clear(); }
-    } scope{e};
-    e->row_len = dev64; e->row_off = dev64 + B; e->row_skip = dev64 + 2 * (size_t)B;
-    e->chain_sorted = dev32;
-    e->chain_nseg = N;
-    e->chain_on = e->chain_le[N - 1] > 0;
-    // prefix compaction: the streams still running in segment n are a prefix of the batch when the SEGMENT COUNTS are non-increasing (a
-    // reset stream has one lead more than a continuing one); the streams beyond the prefix are exactly those whose rows were saved
-    bool sorted = true;
-    for (int b = 1; b < B; b++) sorted = sorted && nb[b] <= nb[b - 1];
-    e->ragged_nseg.clear();
-    if (sorted) e->ragged_nseg = nb;
-    return run_segments(e, mixture, batch, max_length, N, 0, 0, out, st);
+    if (plan.continues() && (rc = chain_rows(e, ~0u, 2, plan.reset_streams(), st))) return rc;
+    return run_segments(e, mixture, batch, max_length, plan.N, 0, 0, out, st, &plan);
 }
 
 static int copy_out(se_engine *e, const float *dev, size_t n, float *host, int64_t cap, int64_t *count, hipStream_t st) {

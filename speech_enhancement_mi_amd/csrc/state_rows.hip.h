@@ -11,6 +11,11 @@
 // list, blockIdx.x strides over the row.  Pure bandwidth: 16-byte loads and plain 16-byte vector stores when the row is a whole number
 // of 16-byte pieces (always for the plane tensors; fp32 rows of odd sizes move word by word), no atomics, no reductions; a row's bytes
 // depend on nothing but that row, so results do not depend on the batch or on launch order.
+//
+// WHERE stream b's state lives is written once per engine: an enumerator of (live tensor, carry buffer, words per stream row) - state_rows_of
+// in se_engine.hip, fsn_state_rows_of in fsn_engine.inc.h.  The chain save / restore / zero (through a StateRowList below), the carry
+// allocation and *_reset_stream all walk it, so a new state tensor is added in that one place.  WHICH streams move and when is the
+// call's ChainPlan (chain_plan.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,5 +58,24 @@ inline void launch_k_state_rows(hipStream_t st, const StateRowTable &t, int nrow
     const unsigned gx = (unsigned)std::min<long>(std::max<long>((units + 255) / 256, 1), 32);  // <= 32 workgroups per row, the rest by stride
     hipLaunchKernelGGL(k_state_rows, dim3(gx, (unsigned)nstreams, (unsigned)nrows), dim3(256), 0, st, t, streams);
 }
+
+// The rows of one launch: add() every tensor, then launch() in one direction for a device list of streams.
+struct StateRowList {
+    struct Row { float *live, *carry; long words; } row[kStateRowsMax];
+    int n = 0;
+    void add(float *live, float *carry, long words) { row[n++] = Row{live, carry, words}; }
+    // dir 0: live -> carry (save), 1: carry -> live (restore), 2: zeros -> live
+    void launch(hipStream_t st, int dir, const int *streams, int nstreams) const {
+        StateRowTable t{};
+        long wmax = 0;
+        for (int i = 0; i < n; i++) {
+            t.r[i].src = reinterpret_cast<const uint32_t *>(dir == 0 ? row[i].live : dir == 1 ? row[i].carry : nullptr);
+            t.r[i].dst = reinterpret_cast<uint32_t *>(dir == 0 ? row[i].carry : row[i].live);
+            t.r[i].words = row[i].words;
+            wmax = std::max(wmax, row[i].words);
+        }
+        launch_k_state_rows(st, t, n, streams, nstreams, wmax);
+    }
+};
 
 }  // namespace se

@@ -18,7 +18,7 @@ SE_MAX_LEVELS = 8
 
 EXPORTS = [
     "se_abi_version", "se_config_size", "fsn_config_size", "se_create", "se_destroy", "se_last_error", "se_load_param", "se_reset", "se_reset_stream", "se_step",
-    "se_realtime_process", "se_realtime_process_ragged", "se_realtime_process_chains", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
+    "se_realtime_process", "se_realtime_process_ragged", "se_realtime_process_chains", "se_chunk_geometry", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
     "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
     "fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state",
@@ -81,6 +81,7 @@ def load_library():
     L.se_realtime_process.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, fp, vp]
     L.se_realtime_process_ragged.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.c_int, fp, vp]
     L.se_realtime_process_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), fp, vp]
+    L.se_chunk_geometry.argtypes = [C.c_int, C.c_int64, C.c_int, i64p, i64p, i64p]
     L.se_stft.argtypes = [vp, fp, C.c_int, fp, vp]
     L.se_istft.argtypes = [vp, fp, C.c_int, fp, vp]
     L.se_forward.argtypes = [vp, fp, fp, vp]
@@ -201,8 +202,9 @@ def make_config(num_channels, num_freqs, hidden, segment_length, num_layers=1, n
 def chain_geometry(lengths, flags, segment_length):
     """Per-stream segment geometry of one se_realtime_process_chains call (utility.py:327-329, 360-368 per stream, with
     lead = 0 for a stream that continues and K/2 for one that is reset): Nb[b] segments, the first one starting at sample off0[b] of the
-    stream, skip[b] samples stripped from its overlap-average; the call runs N = max Nb segments.  Pure Python: what the engine computes
-    on the host, and what train_stages.ragged_geometry gives for the training side."""
+    stream, skip[b] samples stripped from its overlap-average; the call runs N = max Nb segments.  Pure Python (profiles and CPU tests use
+    it without a library): the engines' chunk_geometry (csrc/chain_plan.h), which se_chunk_geometry exports and tests/test_chain_plan_cpu.py
+    compares with this, and what train_stages.ragged_geometry gives for the training side."""
     K = int(segment_length)
     P = K // 2
     Nb, off0, skip = [], [], []
@@ -230,32 +232,76 @@ def _flags_of(flag, B):
     return bool(flag)
 
 
-class Engine:
-    """Thin RAII wrapper over one se_engine handle.  All tensor arguments are CUDA(HIP) torch tensors.
+class SlotMap:
+    """Which engine row (slot) holds which caller row while a batch is carried: order[slot] = caller row, None = the identity.
 
-    Slot map: realtime_process_chains sorts a FRESH batch (all flags 0) by segment count, so that the engine can launch every segment
-    for the prefix of streams still running only.  The permutation stays with the engine (self._order[slot] = caller row) for as long as
-    that batch is carried: later chains calls, a scalar flag=True call, reset_stream and export_state / import_state all address the
-    caller's row b, which is always the same stream.  reset() and every call that starts a fresh batch drop or replace the map."""
+    realtime_process_chains sorts a FRESH batch (all flags 0) by segment count, most first, so that the engine can launch every segment
+    for the prefix of streams still running only.  The permutation stays (choose() hands back the stored object) for as long as that
+    batch is carried: later chains calls, a scalar flag=True call, reset_stream and export_state / import_state all address the caller's
+    row b, which is always the same stream.  reset() and every call that starts a fresh batch drop or replace the map.  Plain Python."""
 
-    def __init__(self, cfg: SeConfig, device: int = 0):
-        self.lib = load_library()
-        self.cfg = cfg
-        self.device = int(device)
-        h = C.c_void_p()
-        rc = self.lib.se_create(C.byref(cfg), self.device, C.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"se_create failed ({rc}): {self.lib.se_last_error(None).decode()}")
+    def __init__(self):
+        self.order = None
+
+    def choose(self, flags, counts):
+        """The order of the call with these per-stream flags; counts (per-stream segment counts) are read for a fresh batch only.  The
+        caller stores the result in .order once the call has succeeded."""
+        B = len(flags)
+        if any(flags):  # a carried batch keeps its slots
+            return self.order if self.order is not None and len(self.order) == B else None
+        order = sorted(range(B), key=lambda i: -counts[i])  # stable
+        return None if order == list(range(B)) else order
+
+    def engine_index(self, caller_row):
+        row = int(caller_row)
+        return self.order.index(row) if self.order is not None and 0 <= row < len(self.order) else row
+
+    def _rows(self, arr, layered, layers):
+        B = len(self.order)
+        return arr.reshape((layers, B, -1) if layered else (B, -1)), (1 if layered else 0)
+
+    def to_engine(self, arr, layered=False, layers=1):
+        """caller rows -> engine rows of a flat state array ([layers, B, ...] when layered, else [B, ...]): engine row s = caller row order[s]"""
+        if self.order is None:
+            return arr
+        a, axis = self._rows(arr, layered, layers)
+        return np.take(a, self.order, axis=axis).reshape(-1)
+
+    def to_caller(self, arr, layered=False, layers=1):
+        if self.order is None:
+            return arr
+        a, axis = self._rows(arr, layered, layers)
+        o = np.empty_like(a)
+        o[(slice(None),) * axis + (self.order,)] = a
+        return o.reshape(-1)
+
+
+class _EngineBase:
+    """What Engine and FsnEngine share: the handle, error checks, parameters, the slot map (SlotMap) and every call that speaks the
+    caller's rows.  PREFIX selects the C symbols (se_* / fsn_*), LAYERED names the states laid out [layers, B, ...]."""
+
+    PREFIX = ""
+    LAYERED = ()
+
+    def _init_handle(self, h):
         self._h = h
-        self.T = self.lib.se_frames_per_segment(h)
-        self.F, self.M, self.K = cfg.num_freqs, cfg.num_inputs, cfg.segment_length
         self.batch = 0
-        self._order = None      # slot map of the carried batch: _order[slot] = caller row (None: caller row b is engine row b)
-        self._order_idx = None  # the same as an int64 device tensor
+        self._slots = SlotMap()
+        self._order_idx = None  # the slot map as an int64 device tensor
+
+    def _fn(self, name):
+        return getattr(self.lib, f"{self.PREFIX}_{name}")
+
+    @property
+    def _order(self):
+        return self._slots.order
+
+    def _set_slots(self, order=None, idx=None):
+        self._slots.order, self._order_idx = order, idx
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.se_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -266,7 +312,7 @@ class Engine:
 
     def _check(self, rc):
         if rc != 0:
-            raise RuntimeError(f"se_engine error {rc}: {self.lib.se_last_error(self._h).decode()}")
+            raise RuntimeError(f"{self.PREFIX}_engine error {rc}: {self._fn('last_error')(self._h).decode()}")
 
     @staticmethod
     def _stream():
@@ -286,18 +332,91 @@ class Engine:
         for k, v in sd.items():
             a = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
             shp = (C.c_int64 * max(1, a.ndim))(*a.shape)
-            self._check(self.lib.se_load_param(self._h, k.encode(), C.c_void_p(a.ctypes.data), shp, a.ndim))
+            self._check(self._fn("load_param")(self._h, k.encode(), C.c_void_p(a.ctypes.data), shp, a.ndim))
 
     def reset(self, batch: int):
-        self._check(self.lib.se_reset(self._h, int(batch)))
+        self._check(self._fn("reset")(self._h, int(batch)))
         self.batch = int(batch)
-        self._order = self._order_idx = None
+        self._set_slots()
 
     def reset_stream(self, index: int):
-        """Zero the state of ONE stream of the batch (a new caller takes the slot); the others keep streaming."""
-        if self._order is not None and 0 <= int(index) < len(self._order):
-            index = self._order.index(int(index))
-        self._check(self.lib.se_reset_stream(self._h, int(index), self._stream()))
+        """Zero the state of ONE stream of the batch (FullSubNet: and reset both norms; a new caller takes the slot); the others keep
+        streaming."""
+        self._check(self._fn("reset_stream")(self._h, self._slots.engine_index(index), self._stream()))
+
+    def realtime_process_chains(self, mixture, flags, lengths=None, out=None):
+        """A batch of chunk chains (se_ / fsn_realtime_process_chains): mixture [B, M, L]; stream b is mixture[b, :, :lengths[b]], continues
+        its carried state where flags[b] is set and starts from zero state (FullSubNet: and reset norms; K/2 left pad, stripped again) where
+        it is not; every stream leaves the state it would carry alone.  out[b, lengths[b]:] = 0.  Rows are the caller's: see SlotMap."""
+        import torch
+        B, M, L = mixture.shape
+        if M != self.M:
+            raise RuntimeError(f"expected {self.M} microphones, got {M}")
+        fl = _flags_of(flags, B)
+        if not isinstance(fl, list):
+            fl = [fl] * B
+        ln = [L] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
+        if len(ln) != B:
+            raise RuntimeError(f"{len(ln)} lengths for a batch of {B}")
+        if out is None:
+            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
+        order = self._slots.choose(fl, None if any(fl) else chain_geometry(ln, fl, self.K)["Nb"])
+        if order is None:
+            src, dst, idx = mixture, out, None
+        else:
+            idx = self._order_idx if order is self._order and self._order_idx is not None and self._order_idx.device == mixture.device else None
+            if idx is None:
+                idx = torch.tensor(order, dtype=torch.int64, device=mixture.device)
+            src, dst = mixture.index_select(0, idx).contiguous(), torch.empty_like(out)
+            ln, fl = [ln[i] for i in order], [fl[i] for i in order]
+        self._check(self._fn("realtime_process_chains")(self._h, self._dev(src), B, L, (C.c_int64 * B)(*ln), (C.c_uint8 * B)(*[int(f) for f in fl]),
+                                                        self._dev(dst, (B, L)), self._stream()))
+        self._set_slots(order, idx)
+        if idx is not None:
+            out.index_copy_(0, idx, dst)
+        self.batch = B
+        return out
+
+    def _host_read(self, fn, name: str) -> np.ndarray:
+        n = C.c_int64(0)
+        probe = np.empty(1, np.float32)
+        rc = fn(self._h, name.encode(), C.c_void_p(probe.ctypes.data), 0, C.byref(n), self._stream())
+        if n.value <= 0:
+            self._check(rc if rc != 0 else -1)
+        out = np.empty(n.value, np.float32)
+        self._check(fn(self._h, name.encode(), C.c_void_p(out.ctypes.data), n.value, C.byref(n), self._stream()))
+        return out
+
+    def read_tap(self, name: str) -> np.ndarray:
+        return self._host_read(self._fn("read_tap"), name)
+
+    def export_state(self, name: str) -> np.ndarray:
+        """A state tensor as a flat host array in the reference's layout ([layers, B, ...] for the names in LAYERED, else [B, ...]), rows in
+        the caller's order."""
+        return self._slots.to_caller(self._host_read(self._fn("export_state"), name), name in self.LAYERED, self.cfg.num_layers)
+
+    def import_state(self, name: str, arr: np.ndarray):
+        a = np.ascontiguousarray(self._slots.to_engine(np.ascontiguousarray(arr, dtype=np.float32).reshape(-1), name in self.LAYERED, self.cfg.num_layers))
+        self._check(self._fn("import_state")(self._h, name.encode(), C.c_void_p(a.ctypes.data), a.size, self._stream()))
+
+
+class Engine(_EngineBase):
+    """Thin RAII wrapper over one se_engine handle.  All tensor arguments are CUDA(HIP) torch tensors.  Rows are the caller's (SlotMap)."""
+
+    PREFIX = "se"
+    LAYERED = ("h",)
+
+    def __init__(self, cfg: SeConfig, device: int = 0):
+        self.lib = load_library()
+        self.cfg = cfg
+        self.device = int(device)
+        h = C.c_void_p()
+        rc = self.lib.se_create(C.byref(cfg), self.device, C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"se_create failed ({rc}): {self.lib.se_last_error(None).decode()}")
+        self._init_handle(h)
+        self.T = self.lib.se_frames_per_segment(h)
+        self.F, self.M, self.K = cfg.num_freqs, cfg.num_inputs, cfg.segment_length
 
     def step(self, wav_in, wav_out=None):
         import torch
@@ -323,7 +442,7 @@ class Engine:
         if out is None:
             out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
         if not flag:
-            self._order = self._order_idx = None
+            self._set_slots()
         if lengths is not None:
             ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
             if len(ln) != B:
@@ -349,60 +468,6 @@ class Engine:
         self.batch = B
         return out
 
-    def realtime_process_chains(self, mixture, flags, lengths=None, out=None):
-        """A batch of chunk chains (se_realtime_process_chains): mixture [B, M, L]; stream b is mixture[b, :, :lengths[b]], continues its
-        carried state where flags[b] is set and starts from zero state (K/2 left pad, stripped again) where it is not; every stream leaves
-        the state it would carry alone.  out[b, lengths[b]:] = 0.  Rows are the caller's: see the slot map in the class docstring."""
-        import torch
-        B, M, L = mixture.shape
-        if M != self.M:
-            raise RuntimeError(f"expected {self.M} microphones, got {M}")
-        fl = _flags_of(flags, B)
-        if not isinstance(fl, list):
-            fl = [fl] * B
-        ln = [L] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
-        if len(ln) != B:
-            raise RuntimeError(f"{len(ln)} lengths for a batch of {B}")
-        if out is None:
-            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
-        if any(fl):  # a carried batch keeps its slots
-            order = self._order if self._order is not None and len(self._order) == B else None
-        else:        # a fresh batch: most segments first (stable), for the engine's prefix compaction
-            nb = chain_geometry(ln, fl, self.K)["Nb"]
-            order = sorted(range(B), key=lambda i: -nb[i])
-            if order == list(range(B)):
-                order = None
-        if order is None:
-            src, dst, idx = mixture, out, None
-        else:
-            idx = self._order_idx if order is self._order and self._order_idx is not None and self._order_idx.device == mixture.device else None
-            if idx is None:
-                idx = torch.tensor(order, dtype=torch.int64, device=mixture.device)
-            src, dst = mixture.index_select(0, idx).contiguous(), torch.empty_like(out)
-            ln, fl = [ln[i] for i in order], [fl[i] for i in order]
-        self._check(self.lib.se_realtime_process_chains(self._h, self._dev(src), B, L, (C.c_int64 * B)(*ln), (C.c_uint8 * B)(*[int(f) for f in fl]),
-                                                        self._dev(dst, (B, L)), self._stream()))
-        self._order, self._order_idx = order, idx
-        if idx is not None:
-            out.index_copy_(0, idx, dst)
-        self.batch = B
-        return out
-
-    def _state_rows(self, name, arr, to_engine):
-        """export_state / import_state speak the caller's rows: [layers, B, H] for "h", [B, ...] for the buffers"""
-        if self._order is None:
-            return arr
-        B = len(self._order)
-        a = arr.reshape((self.cfg.num_layers, B, -1) if name == "h" else (B, -1))
-        o = np.empty_like(a)
-        if to_engine:   # engine row s = caller row order[s]
-            o[...] = np.take(a, self._order, axis=1 if name == "h" else 0)
-        elif name == "h":
-            o[:, self._order] = a
-        else:
-            o[self._order] = a
-        return o.reshape(-1)
-
     def stft(self, seg):
         import torch
         n = seg.shape[0]
@@ -424,19 +489,6 @@ class Engine:
         self._check(self.lib.se_forward(self._h, self._dev(x, (B, self.M, self.F, self.T, 2)), self._dev(y), self._stream()))
         return y
 
-    def _host_read(self, fn, name: str) -> np.ndarray:
-        n = C.c_int64(0)
-        probe = np.empty(1, np.float32)
-        fn(self._h, name.encode(), C.c_void_p(probe.ctypes.data), 0, C.byref(n), self._stream())
-        if n.value <= 0:
-            self._check(-1)
-        out = np.empty(n.value, np.float32)
-        self._check(fn(self._h, name.encode(), C.c_void_p(out.ctypes.data), n.value, C.byref(n), self._stream()))
-        return out
-
-    def read_tap(self, name: str) -> np.ndarray:
-        return self._host_read(self.lib.se_read_tap, name)
-
     def read_tap_dev(self, name: str, numel: int):
         """A distillation feature tap ("ft0".."ft<L>") as a flat fp32 DEVICE tensor of `numel` elements ([B, C, F, T] memory): no host copy."""
         import torch
@@ -446,13 +498,6 @@ class Engine:
         if n.value != numel:
             raise RuntimeError(f"tap {name}: engine wrote {n.value} elements, caller expected {numel}")
         return out
-
-    def export_state(self, name: str) -> np.ndarray:
-        return self._state_rows(name, self._host_read(self.lib.se_export_state, name), to_engine=False)
-
-    def import_state(self, name: str, arr: np.ndarray):
-        a = np.ascontiguousarray(self._state_rows(name, np.ascontiguousarray(arr, dtype=np.float32).reshape(-1), to_engine=True))
-        self._check(self.lib.se_import_state(self._h, name.encode(), C.c_void_p(a.ctypes.data), a.size, self._stream()))
 
     def profile(self, enable: bool):
         self._check(self.lib.se_profile(self._h, int(bool(enable))))
@@ -477,14 +522,14 @@ class Engine:
         return float(self.lib.se_flops_per_frame(self._h))
 
 
-class FsnEngine:
-    """RAII wrapper over one fsn_engine handle (FullSubNet, fullsubnet.py:685-961).
+class FsnEngine(_EngineBase):
+    """RAII wrapper over one fsn_engine handle (FullSubNet, fullsubnet.py:685-961).  Rows are the caller's (SlotMap).
 
-    Slot map: exactly Engine's.  realtime_process_chains sorts a FRESH batch (all flags 0) by window count for the engine's prefix
-    compaction; the permutation (self._order[slot] = caller row) stays with the engine while that batch is carried, so the caller's row b
-    is always the same stream for inputs, outputs, reset_stream, export_state and import_state."""
+    State names: "fh", "fc" [layers, B, H_fb]; "sh", "sc" [layers, B*F, H_sb]; the norms' means and step counters [B]."""
 
-    STATE_NAMES = ("fh", "fc", "sh", "sc", "mean_fb", "mean_sb", "step_fb", "step_sb")
+    PREFIX = "fsn"
+    LAYERED = ("fh", "fc", "sh", "sc")
+    STATE_NAMES = LAYERED + ("mean_fb", "mean_sb", "step_fb", "step_sb")
 
     def __init__(self, num_freqs, num_mics, fb_hidden, sb_hidden, num_layers=2, sb_neighbors=15, fb_neighbors=0, look_ahead=0,
                  sample_rate=16000, segment_length=3200, win_length=25, hop_length=10, n_fft=400, device=0, precision=0):
@@ -497,49 +542,14 @@ class FsnEngine:
         rc = self.lib.fsn_create(C.byref(cfg), int(device), C.byref(h))
         if rc != 0:
             raise RuntimeError(f"fsn_create failed ({rc}): {self.lib.fsn_last_error(None).decode()}")
-        self._h = h
+        self._init_handle(h)
         self.F, self.M, self.K, self.T = cfg.num_freqs, cfg.num_mics, cfg.segment_length, 1 + cfg.segment_length // cfg.hop
-        self.batch = 0
-        self._order = None      # slot map of the carried batch: _order[slot] = caller row (None: caller row b is engine row b)
-        self._order_idx = None  # the same as an int64 device tensor
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.fsn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(f"fsn_engine error {rc}: {self.lib.fsn_last_error(self._h).decode()}")
-
-    def load_state_dict(self, sd):
-        for k, v in sd.items():
-            a = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
-            shp = (C.c_int64 * max(1, a.ndim))(*a.shape)
-            self._check(self.lib.fsn_load_param(self._h, k.encode(), C.c_void_p(a.ctypes.data), shp, a.ndim))
-
-    def reset(self, batch):
-        self._check(self.lib.fsn_reset(self._h, int(batch)))
-        self.batch = int(batch)
-        self._order = self._order_idx = None
-
-    def reset_stream(self, index):
-        """Zero the LSTM state and reset both norms of ONE stream of the batch (a new caller takes the slot); the others keep streaming."""
-        if self._order is not None and 0 <= int(index) < len(self._order):
-            index = self._order.index(int(index))
-        self._check(self.lib.fsn_reset_stream(self._h, int(index), Engine._stream()))
 
     def forward(self, x):
         import torch
         B = self.batch
         crm = torch.empty((B, 2, self.F, self.T), dtype=torch.float32, device=x.device)
-        self._check(self.lib.fsn_forward(self._h, Engine._dev(x, (B, 2 * self.M, self.F, self.T)), Engine._dev(crm), Engine._stream()))
+        self._check(self.lib.fsn_forward(self._h, self._dev(x, (B, 2 * self.M, self.F, self.T)), self._dev(crm), self._stream()))
         return crm
 
     def realtime_process(self, mixture, flag=False, lengths=None, out=None):
@@ -558,87 +568,10 @@ class FsnEngine:
         if out is None:
             out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
         if not flag:
-            self._order = self._order_idx = None
-        self._check(self.lib.fsn_realtime_process(self._h, Engine._dev(mixture), B, L, int(bool(flag)), Engine._dev(out, (B, L)), Engine._stream()))
+            self._set_slots()
+        self._check(self.lib.fsn_realtime_process(self._h, self._dev(mixture), B, L, int(bool(flag)), self._dev(out, (B, L)), self._stream()))
         self.batch = B
         return out
-
-    def realtime_process_chains(self, mixture, flags, lengths=None, out=None):
-        """A batch of chunk chains (fsn_realtime_process_chains): mixture [B, M, L]; stream b is mixture[b, :, :lengths[b]], continues its
-        carried state where flags[b] is set and starts from zero state and reset norms (K/2 left pad, stripped again) where it is not;
-        every stream leaves the state it would carry alone.  out[b, lengths[b]:] = 0.  Rows are the caller's: see the class docstring."""
-        import torch
-        B, M, L = mixture.shape
-        if M != self.M:
-            raise RuntimeError(f"expected {self.M} microphones, got {M}")
-        fl = _flags_of(flags, B)
-        if not isinstance(fl, list):
-            fl = [fl] * B
-        ln = [L] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if hasattr(lengths, "reshape") else lengths)]
-        if len(ln) != B:
-            raise RuntimeError(f"{len(ln)} lengths for a batch of {B}")
-        if out is None:
-            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
-        if any(fl):  # a carried batch keeps its slots
-            order = self._order if self._order is not None and len(self._order) == B else None
-        else:        # a fresh batch: most windows first (stable), for the engine's prefix compaction
-            nb = chain_geometry(ln, fl, self.K)["Nb"]
-            order = sorted(range(B), key=lambda i: -nb[i])
-            if order == list(range(B)):
-                order = None
-        if order is None:
-            src, dst, idx = mixture, out, None
-        else:
-            idx = self._order_idx if order is self._order and self._order_idx is not None and self._order_idx.device == mixture.device else None
-            if idx is None:
-                idx = torch.tensor(order, dtype=torch.int64, device=mixture.device)
-            src, dst = mixture.index_select(0, idx).contiguous(), torch.empty_like(out)
-            ln, fl = [ln[i] for i in order], [fl[i] for i in order]
-        self._check(self.lib.fsn_realtime_process_chains(self._h, Engine._dev(src), B, L, (C.c_int64 * B)(*ln), (C.c_uint8 * B)(*[int(f) for f in fl]),
-                                                         Engine._dev(dst, (B, L)), Engine._stream()))
-        self._order, self._order_idx = order, idx
-        if idx is not None:
-            out.index_copy_(0, idx, dst)
-        self.batch = B
-        return out
-
-    def _state_rows(self, name, arr, to_engine):
-        """export_state / import_state speak the caller's rows: [layers, B, ...] for the LSTM states, [B] for means and counters"""
-        if self._order is None:
-            return arr
-        B = len(self._order)
-        layered = name in ("fh", "fc", "sh", "sc")
-        a = arr.reshape((self.cfg.num_layers, B, -1) if layered else (B, -1))
-        o = np.empty_like(a)
-        if to_engine:   # engine row s = caller row order[s]
-            o[...] = np.take(a, self._order, axis=1 if layered else 0)
-        elif layered:
-            o[:, self._order] = a
-        else:
-            o[self._order] = a
-        return o.reshape(-1)
-
-    def _host_read(self, fn, name):
-        n = C.c_int64(0)
-        probe = np.empty(1, np.float32)
-        rc = fn(self._h, name.encode(), C.c_void_p(probe.ctypes.data), 0, C.byref(n), Engine._stream())
-        if n.value <= 0:
-            self._check(rc if rc != 0 else -1)
-        out = np.empty(n.value, np.float32)
-        self._check(fn(self._h, name.encode(), C.c_void_p(out.ctypes.data), n.value, C.byref(n), Engine._stream()))
-        return out
-
-    def export_state(self, name):
-        """One of STATE_NAMES as a flat host array in the reference's layout ("fh", "fc" [layers, B, H_fb]; "sh", "sc" [layers, B*F, H_sb];
-        means and step counters [B]), rows in the caller's order."""
-        return self._state_rows(name, self._host_read(self.lib.fsn_export_state, name), to_engine=False)
-
-    def import_state(self, name, arr):
-        a = np.ascontiguousarray(self._state_rows(name, np.ascontiguousarray(arr, dtype=np.float32).reshape(-1), to_engine=True))
-        self._check(self.lib.fsn_import_state(self._h, name.encode(), C.c_void_p(a.ctypes.data), a.size, Engine._stream()))
-
-    def read_tap(self, name):
-        return self._host_read(self.lib.fsn_read_tap, name)
 
     @property
     def flops_per_frame(self):
@@ -654,15 +587,15 @@ class FsnEngine:
         """spec [nseg, batch*M, T, F, 2] (se_sig_stft) -> crm [nseg, batch, 2, F, T]; activations saved into ws (uint8 device tensor)."""
         import torch
         crm = torch.empty((nseg, batch, 2, self.F, self.T), dtype=torch.float32, device=spec.device)
-        self._check(self.lib.fsn_train_fwd(self._h, Engine._dev(spec, (nseg, batch * self.M, self.T, self.F, 2)), int(batch), int(nseg), int(bool(flag)),
-                                           C.c_void_p(ws.data_ptr()), Engine._dev(crm), Engine._stream()))
+        self._check(self.lib.fsn_train_fwd(self._h, self._dev(spec, (nseg, batch * self.M, self.T, self.F, 2)), int(batch), int(nseg), int(bool(flag)),
+                                           C.c_void_p(ws.data_ptr()), self._dev(crm), self._stream()))
         self.batch = int(batch)
         if not flag:
-            self._order = self._order_idx = None
+            self._set_slots()
         return crm
 
     def train_bwd(self, dcrm, batch, nseg, ws, grads):
         """dcrm [nseg, batch, 2, F, T] -> writes every parameter gradient into `grads` (device tensors, state_dict order)."""
         ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-        self._check(self.lib.fsn_train_bwd(self._h, Engine._dev(dcrm, (nseg, batch, 2, self.F, self.T)), int(batch), int(nseg), C.c_void_p(ws.data_ptr()),
-                                           ptrs, len(grads), Engine._stream()))
+        self._check(self.lib.fsn_train_bwd(self._h, self._dev(dcrm, (nseg, batch, 2, self.F, self.T)), int(batch), int(nseg), C.c_void_p(ws.data_ptr()),
+                                           ptrs, len(grads), self._stream()))

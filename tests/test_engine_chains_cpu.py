@@ -44,7 +44,9 @@ def test_chains_entry_point_declared_exported_and_listed():
     assert m, "se_realtime_process_chains is not declared in se_engine.h outside comments"
     args = m.group(1)
     assert "const int64_t *lengths_host" in args and "const uint8_t *flags_host" in args and "int64_t max_length" in args
-    assert "se_realtime_process_chains" in engine.EXPORTS
+    assert re.search(r"\bint\s+se_chunk_geometry\s*\(", code), "se_chunk_geometry is not declared in se_engine.h outside comments"
     lib = ctypes.CDLL(engine.LIB_PATH)
-    assert hasattr(lib, "se_realtime_process_chains")
+    for name in ("se_realtime_process_chains", "se_chunk_geometry"):
+        assert name in engine.EXPORTS, name
+        assert hasattr(lib, name), name
     assert lib.se_abi_version() == 5

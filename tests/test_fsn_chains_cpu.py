@@ -11,7 +11,7 @@ import torch
 from conftest import FSN_TINY, ROOT
 from speech_enhancement_mi_amd import engine
 
-NEW = ("fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state")
+NEW = ("fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state", "se_chunk_geometry")
 CALLS = (((False, False, False), (8000, 5200, 3400)), ((True, False, True), (4800, 7000, 3300)))  # make_golden_fsn_chain.py
 
 
