@@ -171,7 +171,7 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
                               additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
-                              fsn_import_state; se_chunk_geometry */
+                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -248,6 +248,26 @@ double fsn_flops_per_frame(const fsn_engine *e);
 int64_t fsn_train_ws_bytes(fsn_engine *e, int batch, int nseg);
 int fsn_train_fwd(fsn_engine *e, const float *spec, int batch, int nseg, int flag, void *ws, float *crm_out, void *stream);
 int fsn_train_bwd(fsn_engine *e, const float *dcrm, int batch, int nseg, void *ws, float *const *grads, int ngrads, void *stream);
+/* Training over a batch of chunk CHAINS: the contract of fsn_realtime_process_chains (per-stream lengths and flags, HOST arrays of
+ * `batch` entries; the same validation, error codes and texts; every stream leaves the state it alone would carry), applied to the
+ * training forward and backward.  All three calls take the same (batch, max_length, lengths, flags) and derive the same plan from
+ * them; the backward rebuilds it from these host arguments, and finds the device row table where the forward left it, in a header
+ * region of ws.  nseg = N = max_b N_b windows (se_chunk_geometry per stream).
+ *  - spec = se_sig_stft_rows of the chunk [N][batch * M][T][F][2] (per-row offset and length; a stream's windows past its own last
+ *    one are all-zero spectra); crm_out and dcrm are dense [N][batch][2][F][T]; windows n >= N_b of stream b hold exact zeros in crm_out.
+ *  - PACKED workspace when the window counts N_b are non-increasing (sort a fresh batch; the Python shim does): window n runs for the
+ *    bact(n) streams still running and its activations go to packed rows base[n] = sum_{m<n} bact(m), so the workspace, the LSTM steps,
+ *    the BPTT and the weight-gradient rows cover sum_b N_b windows, not N * batch.  The window seams are detached (fullsubnet.py:819-820,
+ *    200), which is what makes the windows independent rows of the backward.  Otherwise (a carried batch keeps its slots) the dense
+ *    layout of fsn_train_fwd: every stream runs every window, dead windows read zeros and their rows are restored afterwards.
+ *  - a uniform batch (equal flags, every length == max_length) IS fsn_train_ws_bytes / fsn_train_fwd / fsn_train_bwd: same launches.
+ *  - fsn_train_fwd_chains synchronises `stream` once, after uploading the plan (the host arrays live for the call only).
+ * Deterministic like fsn_train_bwd.  fsn_train_ws_bytes_chains returns a negative SE_ERR_* code on a refused plan. */
+int64_t fsn_train_ws_bytes_chains(fsn_engine *e, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host);
+int fsn_train_fwd_chains(fsn_engine *e, const float *spec, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host,
+                         void *ws, float *crm_out, void *stream);
+int fsn_train_bwd_chains(fsn_engine *e, const float *dcrm, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host,
+                         void *ws, float *const *grads, int ngrads, void *stream);
 
 /* ---- training loss (reference CRN.py:593-617 compute_loss) ------------------------------------------------
  * SI-SNR term, utility.cal_si_snr (utility.py:207-223), device-resident: separated / source [B, L] fp32 device tensors,

@@ -45,12 +45,15 @@ struct fsn_engine {
     int lstm_big = 1;     // SE_FSN_BIG=0: keep the 128 x 128 step tiles where the 256-row x 64-unit tile would be picked (read at fsn_create)
 };
 
-// Float offsets into the workspace of fsn_train_fwd / fsn_train_bwd (include/se_engine.h).  Model index 0 = full band (S = N*B rows per
-// step), 1 = sub band (S = N*B*F rows).  Every saved tensor is [T][S][.]: step t of ALL N windows is one contiguous slab, window n's
-// rows at n*B (*F) inside it, so one backward launch per step covers every window (the state is detached at each seam).
+// Float offsets into the workspace of fsn_train_fwd / fsn_train_bwd (include/se_engine.h).  Model index 0 = full band (S = base[N]
+// rows per step: N*B, or the packed sum of bact(n) of a chains call), 1 = sub band (S * F rows).  Every saved tensor is [T][S][.]: step t
+// of ALL N windows is one contiguous slab, window n's rows at base[n] (*F) inside it, so one backward launch per step covers every
+// window (the state is detached at each seam).
 struct FsnTrainLayout {
     int B = 0, N = 0;
     long S[2]{};
+    std::vector<long> base;                        // full-band row of window n's first stream, n = 0 .. N (base[N] = S[0])
+    size_t hdr = 0;                                // chains: the plan's staging vector (8 B floats), then the packed row table (S[0] ints)
     size_t gates[2][4]{}, cs[2][4]{}, hs[2][4]{};  // gates i, f, g, o [T][S][4H]; c, h [T + 1][S][H], slot 0 = the state entering the window
     size_t xs[2]{};                                // layer-0 inputs: full band [T][S][Kp] (normalised |X|), sub band [T][S][SI]
     size_t fbo = 0;                                // full-band output after the ReLU [T][S][F]
@@ -158,7 +161,7 @@ int fsn_prepare(fsn_engine *e) {
 int fsn_train_save_window(fsn_engine *e, int mi, const float *x, long sR, long sT, int W, int R, hipStream_t st) {
     const FsnTrainLayout &L = *e->tr;
     fsn_engine::Model &m = mi ? e->sb : e->fb;
-    const long S = L.S[mi], r0 = (long)e->tr_n * R;
+    const long S = L.S[mi], r0 = L.base[e->tr_n] * (mi ? e->F : 1);
     hipLaunchKernelGGL(k_fsn_save_rows, dim3(2048), dim3(256), 0, st, x, sR, sT, W, R, e->T, e->tr_ws + L.xs[mi] + r0 * W, S * W);
     FHIP(e, hipGetLastError());
     for (int l = 0; l < e->NL; l++) {
@@ -177,7 +180,7 @@ int fsn_lstm_step(fsn_engine *e, fsn_engine::Model &m, int l, const float *x, lo
     if (e->tr && t >= 0) {  // all training steps take the 128 x 128 tile (at R = B*F = 1 608 per window the step is latency-bound anyway)
         const FsnTrainLayout &L = *e->tr;
         const int mi = &m == &e->sb ? 1 : 0;
-        const long S = L.S[mi], r0 = (long)e->tr_n * R, H = m.H;
+        const long S = L.S[mi], r0 = L.base[e->tr_n] * (mi ? e->F : 1), H = m.H;
         a.gsave = e->tr_ws + L.gates[mi][l] + ((long)t * S + r0) * 4 * H;
         a.csave = e->tr_ws + L.cs[mi][l] + ((long)(t + 1) * S + r0) * H;
         a.hsave = e->tr_ws + L.hs[mi][l] + ((long)(t + 1) * S + r0) * H;
@@ -262,7 +265,7 @@ int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long 
     if (e->tr) {  // fb_out [B*T][F] -> [T][S][F] (its sign is the ReLU's derivative)
         const FsnTrainLayout &L = *e->tr;
         hipLaunchKernelGGL(k_fsn_save_rows, dim3(1024), dim3(256), 0, st, e->fb_out.p, (long)T * F, (long)F, F, B, T,
-                           e->tr_ws + L.fbo + (long)e->tr_n * B * F, L.S[0] * F);
+                           e->tr_ws + L.fbo + L.base[e->tr_n] * F, L.S[0] * F);
         FHIP(e, hipGetLastError());
     }
     return 0;
@@ -285,7 +288,7 @@ int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long 
         FHIP(e, hipGetLastError());
     }
     if (e->tr) {  // training forward: the normalised sub-band input, this window's denominators, the state entering the window
-        FHIP(e, hipMemcpyAsync(e->tr_ws + e->tr->denom + (long)e->tr_n * B, e->denom_sb.p, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+        FHIP(e, hipMemcpyAsync(e->tr_ws + e->tr->denom + e->tr->base[e->tr_n], e->denom_sb.p, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
         int rc = fsn_train_save_window(e, 1, e->sbin.p, SI, Rall * SI, SI, R, st);
         if (rc) return rc;
     }

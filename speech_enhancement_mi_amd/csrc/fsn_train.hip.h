@@ -4,7 +4,8 @@
 //   k_fsn_save_rows   training forward: a per-window tensor (element (r, t, k) at src[r*sR + t*sT + k]) into the [T][S][W] layout
 //   k_lstm_bwd_step   one BPTT step of one LSTM layer for ALL windows' sequences: dh_rec = dG_{t+1} W_hh as an fp32-exact MFMA GEMM
 //                     (M = S rows, N = H units, K = 4H), the LSTM cell backward in the epilogue
-//   k_fsn_gather_dm   d crm [N][B][2][F][T] -> d mask [T][S][2] (the sub-band output layer's gradient, rows of the backward layout)
+//   k_fsn_gather_dm   d crm [N][B][2][F][T] -> d mask [T][S][2] (the sub-band output layer's gradient, rows of the backward layout:
+//                     dense, or packed through a row table)
 //   k_fsn_dfb         d fb_out: column SI - 1 of the sub-band input gradient (dG_0 . W_ih_l0[:, SI - 1]) / that window's CumLayerNorm
 //                     denominator (the running mean is detached, fullsubnet.py:200), through the full-band ReLU
 // Every sum has a fixed order (no float atomics): the gradients are bit-reproducible.
@@ -151,27 +152,30 @@ __global__ __launch_bounds__(256) void k_lstm_bwd_step(LstmBwdArgs a) {
     }
 }
 
-// dm[t][s][c] = dcrm[n][b][c][f][t], s = n*B*F + b*F + f
-__global__ void k_fsn_gather_dm(const float *dcrm, float *dm, int N, int B, int F, int T) {
-    const long S = (long)N * B * F, total = (long)T * S * 2;
+// dm[t][s][c] = dcrm[n][b][c][f][t], s = p*F + f over the S0 rows p of the backward layout: p = n*B + b (rowmap null, the dense
+// layout) or rowmap[p] = n*B + b (the packed layout of a chains call, which leaves the dead windows out)
+__global__ void k_fsn_gather_dm(const float *dcrm, float *dm, const int *rowmap, long S0, int F, int T) {
+    const long S = S0 * F, total = (long)T * S * 2;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i & 1);
         const long q = i >> 1;
         const int t = (int)(q / S);
         const long s = q - (long)t * S;
-        const long nb = s / F;
-        const int f = (int)(s - nb * F);
+        const long p = s / F;
+        const int f = (int)(s - p * F);
+        const long nb = rowmap ? rowmap[p] : p;
         dm[i] = dcrm[((nb * 2 + c) * F + f) * T + t];
     }
 }
 
-// dpre[t][n*B + b][f] (row stride Fp, columns >= F untouched) = relu'(fb_out) * (sum_g dG0[t][n*B*F + b*F + f][g] * wcol[g]) / denom[n][b]
-// one wave per (t, n, b, f); lanes across g, a fixed shuffle tree
+// dpre[t][p][f] (row stride Fp, columns >= F untouched) = relu'(fb_out) * (sum_g dG0[t][p*F + f][g] * wcol[g]) / denom[p], p = the
+// S0 rows of the backward layout (dense n*B + b, or packed): denom, fbo and dpre are all indexed by p
+// one wave per (t, p, f); lanes across g, a fixed shuffle tree
 __global__ __launch_bounds__(256) void k_fsn_dfb(const float *dg0, const float *wcol, const float *denom, const float *fbo, float *dpre,
-                                                 int N, int B, int F, int T, int H4, int Fp) {
+                                                 long S0, int F, int T, int H4, int Fp) {
     const int lane = threadIdx.x & 63;
     const long wid = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((long)gridDim.x * blockDim.x) >> 6;
-    const long Ssb = (long)N * B * F, total = (long)T * Ssb;
+    const long Ssb = S0 * F, total = (long)T * Ssb;
     for (long row = wid; row < total; row += nw) {
         const float *g = dg0 + row * H4;
         float s = 0.0f;
@@ -180,10 +184,10 @@ __global__ __launch_bounds__(256) void k_fsn_dfb(const float *dg0, const float *
         for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
         if (lane == 0) {
             const int t = (int)(row / Ssb);
-            const long q = row - (long)t * Ssb, nb = q / F;
-            const int f = (int)(q - nb * F);
-            const long r = (long)t * N * B + nb;  // row of the full-band layout [T][N*B]
-            dpre[r * Fp + f] = fbo[r * F + f] > 0.0f ? s / denom[nb] : 0.0f;
+            const long q = row - (long)t * Ssb, p = q / F;
+            const int f = (int)(q - p * F);
+            const long r = (long)t * S0 + p;  // row of the full-band layout [T][S0]
+            dpre[r * Fp + f] = fbo[r * F + f] > 0.0f ? s / denom[p] : 0.0f;
         }
     }
 }

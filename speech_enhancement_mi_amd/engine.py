@@ -22,7 +22,7 @@ EXPORTS = [
     "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
     "fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state",
-    "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
+    "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "fsn_train_ws_bytes_chains", "fsn_train_fwd_chains", "fsn_train_bwd_chains", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
     "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd",
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
     "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
@@ -112,6 +112,10 @@ def load_library():
     L.fsn_train_ws_bytes.restype = C.c_int64
     L.fsn_train_fwd.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, vp, fp, vp]
     L.fsn_train_bwd.argtypes = [vp, fp, C.c_int, C.c_int, vp, C.POINTER(vp), C.c_int, vp]
+    L.fsn_train_ws_bytes_chains.argtypes = [vp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8)]
+    L.fsn_train_ws_bytes_chains.restype = C.c_int64
+    L.fsn_train_fwd_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), vp, fp, vp]
+    L.fsn_train_bwd_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), vp, C.POINTER(vp), C.c_int, vp]
     L.se_loss_sisnr_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp]
     L.se_loss_stoi_ws_floats.argtypes = [C.c_int, C.c_int64]
     L.se_loss_stoi_ws_floats.restype = C.c_int64
@@ -599,3 +603,50 @@ class FsnEngine(_EngineBase):
         ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         self._check(self.lib.fsn_train_bwd(self._h, self._dev(dcrm, (nseg, batch, 2, self.F, self.T)), int(batch), int(nseg), C.c_void_p(ws.data_ptr()),
                                            ptrs, len(grads), self._stream()))
+
+    # ---- training over a batch of chunk chains (fsn_train_*_chains).  lengths / flags are host values in ENGINE order: the caller
+    # (fsn_training.FSNFunction) asks train_chain_order() first and permutes its rows, as realtime_process_chains does for inference ----
+    def train_chain_order(self, flags, lengths, device):
+        """(order, idx) of a training chains call: order[slot] = caller row (None: the identity), idx = order as an int64 device tensor.
+        A fresh batch (all flags False) is sorted stably by descending window count (SlotMap.choose), which makes the plan compact and
+        the workspace packed; a carried batch keeps its map.  Stored by train_fwd_chains once the forward has succeeded."""
+        import torch
+        order = self._slots.choose(flags, None if any(flags) else chain_geometry(lengths, flags, self.K)["Nb"])
+        if order is None:
+            return None, None
+        idx = self._order_idx if order is self._order and self._order_idx is not None and self._order_idx.device == device else None
+        if idx is None:
+            idx = torch.tensor(order, dtype=torch.int64, device=device)
+        return order, idx
+
+    @staticmethod
+    def _chain_args(batch, lengths, flags):
+        if len(lengths) != batch or len(flags) != batch:
+            raise RuntimeError(f"{len(lengths)} lengths and {len(flags)} flags for a batch of {batch}")
+        return (C.c_int64 * batch)(*[int(v) for v in lengths]), (C.c_uint8 * batch)(*[int(bool(f)) for f in flags])
+
+    def train_ws_bytes_chains(self, batch, max_length, lengths, flags):
+        ln, fl = self._chain_args(batch, lengths, flags)
+        n = int(self.lib.fsn_train_ws_bytes_chains(self._h, int(batch), int(max_length), ln, fl))
+        self._check(0 if n > 0 else n)
+        return n
+
+    def train_fwd_chains(self, spec, batch, max_length, lengths, flags, ws, nseg, order=None, idx=None):
+        """spec [nseg, batch*M, T, F, 2] (se_sig_stft_rows) -> crm [nseg, batch, 2, F, T], exact zeros in the windows past a stream's own
+        last one; activations saved into ws (train_ws_bytes_chains of the same arguments).  (order, idx): train_chain_order's."""
+        import torch
+        ln, fl = self._chain_args(batch, lengths, flags)
+        crm = torch.empty((nseg, batch, 2, self.F, self.T), dtype=torch.float32, device=spec.device)
+        self._check(self.lib.fsn_train_fwd_chains(self._h, self._dev(spec, (nseg, batch * self.M, self.T, self.F, 2)), int(batch), int(max_length), ln, fl,
+                                                  C.c_void_p(ws.data_ptr()), self._dev(crm), self._stream()))
+        self.batch = int(batch)
+        self._set_slots(order, idx)
+        return crm
+
+    def train_bwd_chains(self, dcrm, batch, max_length, lengths, flags, ws, grads):
+        """dcrm [nseg, batch, 2, F, T] (dense) and the forward's own (batch, max_length, lengths, flags, ws) -> every parameter gradient"""
+        ln, fl = self._chain_args(batch, lengths, flags)
+        ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        nseg = dcrm.shape[0]
+        self._check(self.lib.fsn_train_bwd_chains(self._h, self._dev(dcrm, (nseg, batch, 2, self.F, self.T)), int(batch), int(max_length), ln, fl,
+                                                  C.c_void_p(ws.data_ptr()), ptrs, len(grads), self._stream()))

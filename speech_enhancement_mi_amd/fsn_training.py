@@ -15,6 +15,14 @@ What the reference detaches, both paths detach: the LSTM states after every wind
 window seam) and both CumLayerNorm running means (fullsubnet.py:200: the norm's gradient is 1 / (mean + EPS) of the window).
 Under torch.no_grad() on the GPU, realtime_process takes FullSubNet's inference engine.  train=True keeps FullSubNet's forward-only
 single pass.
+
+Batched chunk chains (datagen.ChunkChainBatch): `flag` with one value per utterance and / or `lengths` make the batch B independent
+chains, the contract of fsn_realtime_process_chains and of CRN chain training: utterance b is mixture[b, :, :lengths[b]] (zero beyond,
+whatever the padding holds), starts from zero state, reset norms and the K/2 lead where flag[b] is False, continues row b of the
+carried state where it is True; pred[b, lengths[b]:] = 0; crm / x / s cover all N = max N_b windows, crm with exact zeros in the
+windows past an utterance's own last one; afterwards every utterance holds the state it alone would carry.  Both forwards honour it
+(fsn_train_*_chains on the kernels: a fresh batch is sorted by window count and its workspace packed).  A batch whose
+flags are all alike and whose lengths are all Lmax takes the scalar path, as a bool flag does.
 """
 from __future__ import annotations
 
@@ -23,24 +31,37 @@ import torch.nn.functional as Fn
 
 from . import train_ops as K
 from .fullsubnet import FullSubNet
-from .train_stages import _as_flag, _sig, segment_geometry, stft, synthesis, synthesis_adjoint
+from .train_stages import (_as_flag, _as_flags, _as_lengths, _rows, _sig, ragged_geometry, segment_geometry, stft, stft_rows, synthesis,
+                           synthesis_adjoint, synthesis_adjoint_rows, synthesis_rows)
 from .training import _TrainableMixin
 
 EPS = 1e-8  # fullsubnet.py:12
 
 
+def _x0(spec, N, B, M, T, F):
+    """mic 0 of spec [N][B*M][T][F][2] in the reference's layout [N, B, 2, F, T]"""
+    return spec.view(N, B, M, T, F, 2)[:, :, 0].permute(0, 1, 4, 3, 2).contiguous()
+
+
 class FSNFunction(torch.autograd.Function):
     """pred = realtime_process(mixture, flag, train=False)[0] on the kernels.  forward(ctx, model, mixture, flag, *params) with params
-    in state_dict order (what fsn_train_bwd writes)."""
+    in state_dict order (what fsn_train_bwd writes).  flag: a bool, or (flags, lengths) - B bools and B ints, host values - of a batch
+    of chunk chains (fsn_train_*_chains)."""
 
     @staticmethod
     def forward(ctx, model, mixture, flag, *params):
         K._need_gpu(mixture, params[0])
         eng = model._engine_for(mixture)  # (re)loads the weights when an optimizer step changed them
-        g = model._geometry(mixture)
-        B, M, L, N, T, F = g["B"], g["M"], g["L"], g["N"], g["T"], g["F"]
-        dev = mixture.device
         mixture = mixture.contiguous().float()
+        B, M, L = mixture.shape
+        if not isinstance(flag, tuple) and flag and eng._order is not None and len(eng._order) == B:
+            flag = ((True,) * B, (L,) * B)  # the carried batch was permuted by a chains call: keep the caller's row b on its utterance
+        ctx.shapes = [p.shape for p in params]
+        if isinstance(flag, tuple):
+            return FSNFunction._forward_chains(ctx, model, eng, mixture, list(flag[0]), list(flag[1]))
+        g = model._geometry(mixture, flag)
+        N, T, F = g["N"], g["T"], g["F"]
+        dev = mixture.device
         S = N * B
         spec = stft(g["sig"], mixture, B, M, L, g["off0"], g["P"], N, T, F)
         ws = torch.empty(eng.train_ws_bytes(B, N), dtype=torch.uint8, device=dev)
@@ -49,9 +70,37 @@ class FSNFunction(torch.autograd.Function):
         Y = torch.empty(S, T, F, 2, device=dev)
         K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
         pred = synthesis(g["sig"], Y, B, g["Ks"], L, g["skip"])
-        model._hip_aux = (crm, spec)
-        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g = eng, ws, spec, xm, g
-        ctx.shapes = [p.shape for p in params]
+        model._hip_aux = (crm, _x0(spec, N, B, M, T, F))
+        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g, ctx.chain = eng, ws, spec, xm, g, None
+        return pred
+
+    @staticmethod
+    def _forward_chains(ctx, model, eng, mixture, flags, lens):
+        """Rows are the caller's outside, the engine's inside: a fresh batch is sorted by window count (FsnEngine.train_chain_order), a
+        carried one keeps its slots; mixture is permuted on the way in, pred / crm / x on the way out."""
+        B, M, L = mixture.shape
+        dev = mixture.device
+        order, idx = eng.train_chain_order(flags, lens, dev)
+        if order is not None:
+            mixture = mixture.index_select(0, idx)
+            flags, lens = [flags[i] for i in order], [lens[i] for i in order]
+        g = model._chain_geometry(mixture, flags, lens)
+        N, T, F, rows = g["N"], g["T"], g["F"], g["rows"]
+        S = N * B
+        spec = stft_rows(g["sig"], mixture, B, M, L, rows["off0"], rows["len"], g["P"], N, T, F)
+        ws = torch.empty(eng.train_ws_bytes_chains(B, L, lens, flags), dtype=torch.uint8, device=dev)
+        crm = eng.train_fwd_chains(spec, B, L, lens, flags, ws, N, order, idx)    # [N, B, 2, F, T], zeros in the dead windows
+        # the mask runs over all N * B segments: a dead segment has a zero spectrum (and, in the backward, a zero gradient)
+        xm = crm.permute(0, 1, 2, 4, 3).reshape(S, 2, T, F).contiguous()
+        Y = torch.empty(S, T, F, 2, device=dev)
+        K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
+        pred = synthesis_rows(g["sig"], Y, B, g["Ks"], L, rows["skip"], rows["len"])
+        x0 = _x0(spec, N, B, M, T, F)
+        if idx is not None:
+            pred = torch.empty_like(pred).index_copy_(0, idx, pred)
+            crm, x0 = torch.empty_like(crm).index_copy_(1, idx, crm), torch.empty_like(x0).index_copy_(1, idx, x0)
+        model._hip_aux = (crm, x0)
+        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g, ctx.chain = eng, ws, spec, xm, g, (flags, lens, idx)
         return pred
 
     @staticmethod
@@ -59,12 +108,22 @@ class FSNFunction(torch.autograd.Function):
         g = ctx.g
         B, M, L, N, T, F = g["B"], g["M"], g["L"], g["N"], g["T"], g["F"]
         S, dev = N * B, dpred.device
-        dY = synthesis_adjoint(g["sig"], dpred.contiguous().float(), B, N, L, g["skip"], g["Ks"], T, F)
+        dpred = dpred.contiguous().float()
+        if ctx.chain is None:
+            dY = synthesis_adjoint(g["sig"], dpred, B, N, L, g["skip"], g["Ks"], T, F)
+        else:
+            flags, lens, idx = ctx.chain
+            if idx is not None:
+                dpred = dpred.index_select(0, idx)
+            dY = synthesis_adjoint_rows(g["sig"], dpred, B, N, L, g["rows"]["skip"], g["rows"]["len"], g["Ks"], T, F)
         dx = torch.empty(S, 2, T, F, device=dev)
         K._chk(K._lib().se_train_mask_bwd(dY.data_ptr(), ctx.xm.data_ptr(), ctx.spec.data_ptr(), dx.data_ptr(), S, M, T, F, g["n_fft"], K._st()))
         dcrm = dx.view(N, B, 2, T, F).permute(0, 1, 2, 4, 3).contiguous()
         grads = [torch.empty(s, device=dev) for s in ctx.shapes]
-        ctx.eng.train_bwd(dcrm, B, N, ctx.ws, grads)
+        if ctx.chain is None:
+            ctx.eng.train_bwd(dcrm, B, N, ctx.ws, grads)
+        else:
+            ctx.eng.train_bwd_chains(dcrm, B, L, lens, flags, ctx.ws, grads)
         ctx.ws = ctx.spec = ctx.xm = None
         return (None, None, None, *grads)
 
@@ -96,18 +155,45 @@ class TrainableFullSubNet(FullSubNet):
         g.update(B=B, M=M, n_fft=n_fft, F=self.num_freqs, sig=_sig(mixture.device, n_fft, self._win, self._hop, Ks))
         return g
 
-    def realtime_process(self, mixture, source=None, flag=False, train=False):
+    def _chain_geometry(self, mixture, flags, lens):
+        """_geometry of a batch of chunk chains: per-utterance Nb / off0 / skip as host lists, and as device int64 rows for the row kernels"""
+        B, M, L = mixture.shape
+        n_fft, Ks = self._args["n_fft"], self.segment_length
+        g = ragged_geometry(lens, flags, Ks, self._hop, n_fft)
+        dev = mixture.device
+        g.update(B=B, M=M, L=L, n_fft=n_fft, F=self.num_freqs, sig=_sig(dev, n_fft, self._win, self._hop, Ks),
+                 rows=dict(off0=_rows(g["off0"], dev), len=_rows(g["lengths"], dev), skip=_rows(g["skip"], dev)))
+        return g
+
+    def realtime_process(self, mixture, source=None, flag=False, train=False, lengths=None):
+        """flag: a bool or ONE value for the batch, or one value per utterance; lengths (optional): B ints <= Lmax, host values or a
+        tensor read once, here - nothing later in the call synchronises for them.  See the module docstring for the chains contract."""
         if train:
+            if lengths is not None:
+                raise NotImplementedError("train=True takes one flag and one length for the whole batch")
             return super().realtime_process(mixture, source, flag, True)
-        flag = _as_flag(flag)
+        B, _, Lmax = mixture.shape
+        chain = None
+        if lengths is not None or (isinstance(flag, (list, tuple)) and len(flag) > 1) or (isinstance(flag, torch.Tensor) and flag.numel() > 1):
+            flags, lens = _as_flags(flag, B), _as_lengths(lengths, B, Lmax)
+            if len(set(flags)) == 1 and min(lens) == Lmax:
+                flag = flags[0]   # a uniform batch IS the scalar call
+            else:
+                chain = (tuple(flags), tuple(lens))
+        else:
+            flag = _as_flag(flag[0] if isinstance(flag, (list, tuple)) else flag)
         if not torch.is_grad_enabled() and mixture.is_cuda:
-            return super().realtime_process(mixture, source, flag, False)
+            if chain is None:
+                return super().realtime_process(mixture, source, flag, False)
+            return super().realtime_process(mixture, source, list(chain[0]), False, lengths=list(chain[1]))
         self._cur_flag = flag
         if self._hip:
-            pred, crm, x = self._hip_forward(mixture, flag)
-            s = None if source is None else self._mic0_spec(source, flag)
-        else:
+            pred, crm, x = self._hip_forward(mixture, flag if chain is None else chain)
+            s = None if source is None else self._mic0_spec(source, flag if chain is None else chain)
+        elif chain is None:
             pred, crm, x, s = self._torch_forward(mixture, source, flag)
+        else:
+            pred, crm, x, s = self._torch_forward_chains(mixture, source, list(chain[0]), list(chain[1]))
         if source is None:
             return pred
         return pred, crm.detach(), s.detach(), x.detach()
@@ -116,17 +202,19 @@ class TrainableFullSubNet(FullSubNet):
     def _hip_forward(self, mixture, flag):
         params = list(self.parameters())
         pred = FSNFunction.apply(self, mixture, flag, *params)
-        crm, spec = self._hip_aux
+        crm, x0 = self._hip_aux
         self._hip_aux = None
-        g = self._geometry(mixture, flag)
-        N, B, M, T, F = g["N"], g["B"], g["M"], g["T"], g["F"]
-        x0 = spec.view(N, B, M, T, F, 2)[:, :, 0].permute(0, 1, 4, 3, 2).contiguous()  # [N, B, 2, F, T]
         return pred, crm, x0
 
     def _mic0_spec(self, source, flag):
+        """mic 0 of the source's windows [N, B, 2, F, T]; flag: a bool, or (flags, lengths): per-row offsets, zero beyond each length"""
         src = source[:, :1].contiguous().float()
-        g = self._geometry(src, flag)
-        sspec = stft(g["sig"], src, g["B"], 1, g["L"], g["off0"], g["P"], g["N"], g["T"], g["F"])   # [N, B, T, F, 2]
+        if isinstance(flag, tuple):
+            g = self._chain_geometry(src, list(flag[0]), list(flag[1]))
+            sspec = stft_rows(g["sig"], src, g["B"], 1, g["L"], g["rows"]["off0"], g["rows"]["len"], g["P"], g["N"], g["T"], g["F"])
+        else:
+            g = self._geometry(src, flag)
+            sspec = stft(g["sig"], src, g["B"], 1, g["L"], g["off0"], g["P"], g["N"], g["T"], g["F"])   # [N, B, T, F, 2]
         return sspec.permute(0, 1, 4, 3, 2).contiguous()
 
     # ---- torch restatement (the checker) ----
@@ -164,7 +252,8 @@ class TrainableFullSubNet(FullSubNet):
         mean = x.detach().mean(dim=(1, 2, 3), keepdim=True)
         rm, step = st.get(key), st.get(key + "_step", 0)
         rm = mean if rm is None else (step / (step + 1)) * rm + (1.0 - step / (step + 1)) * mean
-        st[key], st[key + "_step"] = rm, min(step + 1, 80)
+        # the counter is one int for the batch, or - once a chains call has run - one value per utterance [B, 1, 1, 1]
+        st[key], st[key + "_step"] = rm, torch.clamp(step + 1, max=80) if isinstance(step, torch.Tensor) else min(step + 1, 80)
         return x / (rm + EPS)
 
     def _layers(self, seq):
@@ -224,5 +313,85 @@ class TrainableFullSubNet(FullSubNet):
         if source is not None:
             src = source if flag else Fn.pad(source, (P, 0))
             S0 = self._stft(self._segment(src[:, :1])[0])[:, 0].transpose(0, 1)
+            s0 = torch.stack([S0.real, S0.imag], dim=2)
+        return pred, crm, x0, s0
+
+    # ---- torch restatement of a batch of chunk chains ----
+    _STATE_KEYS = ("mean_fb", "mean_fb_step", "mean_sb", "mean_sb_step", "fh", "sh")
+
+    def _chain_state(self, B, like):
+        """The state of B utterances as a chains call keeps it - every entry a tensor with one row (F rows for the sub band) per utterance:
+        the carried state brought to that form, or (nothing carried) the state after a reset, spelled out."""
+        st, F, NL = self._tstate or {}, self.num_freqs, self._args["num_layers"]
+        out = {}
+        for key in ("mean_fb", "mean_sb"):
+            rm, step = st.get(key), st.get(key + "_step", 0)
+            out[key] = like.new_zeros(B, 1, 1, 1) if rm is None else rm
+            out[key + "_step"] = step if isinstance(step, torch.Tensor) else like.new_full((B, 1, 1, 1), float(step))
+        for key, rows, H in (("fh", B, self._args["fb_hidden"]), ("sh", B * F, self._args["sb_hidden"])):
+            out[key] = st.get(key) or [(like.new_zeros(rows, H), like.new_zeros(rows, H)) for _ in range(NL)]
+        return out
+
+    def _merge_state(self, mask, a, b):
+        """per utterance: a where mask [B] holds, else b"""
+        F = self.num_freqs
+        out = {}
+        for key in self._STATE_KEYS:
+            if key in ("fh", "sh"):
+                m = (mask if key == "fh" else mask.repeat_interleave(F))[:, None]   # sub band: row b * F + f
+                out[key] = [(torch.where(m, ha, hb), torch.where(m, ca, cb)) for (ha, ca), (hb, cb) in zip(a[key], b[key])]
+            else:
+                out[key] = torch.where(mask.view(-1, 1, 1, 1), a[key], b[key])
+        return out
+
+    def _torch_forward_chains(self, mixture, source, flags, lens):
+        """B independent chunk chains in one call.  Every statistic of the model is per utterance and window positions do not depend on
+        the length, so all utterances run the N = max N_b windows of the longest; state, means and counters are kept per utterance and
+        an utterance's carried state is taken after its OWN last window, its output cut from its own samples."""
+        B, M, Lmax = mixture.shape
+        K_ = self.segment_length
+        P = K_ // 2
+        q = ragged_geometry(lens, flags, K_, self._hop, self._nfft)
+        N, dev = q["N"], mixture.device
+        carried = None
+        if any(flags):
+            if self._tstate is None or "fh" not in self._tstate:
+                raise RuntimeError("flag=True continues a previous chunk of this path: start with flag=False")
+            if self._tstate["fh"][0][0].shape[0] != B:
+                raise RuntimeError(f"flag=True continues row b of the carried state, which holds {self._tstate['fh'][0][0].shape[0]} utterances, not {B}")
+            carried = self._chain_state(B, mixture)
+        self._tstate = None
+        state = self._chain_state(B, mixture)   # after a reset
+        if carried is not None:
+            state = self._merge_state(torch.tensor(flags, device=dev), carried, state)
+
+        def windows(x):   # [B, C, Lmax] -> the N windows of every utterance's own samples [B, C, N, F, T]
+            xp = torch.cat([Fn.pad(x[b:b + 1, :, :lens[b]], (-q["off0"][b], (N + 1) * P + q["off0"][b] - lens[b])) for b in range(B)])
+            idx = (torch.arange(N, device=dev) * P)[:, None] + torch.arange(K_, device=dev)[None, :]
+            return self._stft(xp[:, :, idx])
+
+        X = windows(mixture)
+        Nb = torch.tensor(q["Nb"], device=dev)
+        final, crms = state, []
+        for n in range(N):
+            state = dict(state)
+            crms.append(self._torch_window(X[:, :, n], state))
+            if n + 1 in q["Nb"]:
+                final = self._merge_state(Nb == n + 1, state, final)
+        self._tstate = final
+        live = (torch.arange(N, device=dev)[:, None] < Nb[None, :]).to(mixture.dtype).view(N, B, 1, 1, 1)
+        crm = torch.stack(crms, dim=0) * live   # [N, B, 2, F, T]: exact zeros past every utterance's own last window
+        m = 9.9 * (crm >= 9.9) - 9.9 * (crm <= -9.9) + crm * (crm.abs() < 9.9)  # decompress_cIRM, utility.py:439-442
+        m = -10.0 * torch.log((10.0 - m) / (10.0 + m))
+        X0 = X[:, 0].transpose(0, 1)        # [N, B, F, T]
+        re, im = X0.real, X0.imag
+        Y = torch.complex(m[:, :, 0] * re - m[:, :, 1] * im, m[:, :, 1] * re + m[:, :, 0] * im)
+        y = self._istft(Y).transpose(0, 1)  # [B, N, K]
+        full = (y[:, 0::2].reshape(B, -1)[:, P:] + y[:, 1::2].reshape(B, -1)[:, :-P]) / 2
+        pred = torch.stack([Fn.pad(full[b, q["skip"][b]:q["skip"][b] + lens[b]], (0, Lmax - lens[b])) for b in range(B)])
+        x0 = torch.stack([re, im], dim=2)
+        s0 = None
+        if source is not None:
+            S0 = windows(source[:, :1])[:, 0].transpose(0, 1)
             s0 = torch.stack([S0.real, S0.imag], dim=2)
         return pred, crm, x0, s0
