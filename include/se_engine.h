@@ -325,6 +325,16 @@ int se_train_gru_pseq_fwd(const float *gi, const float *h0, const float *whh, co
 int se_train_gru_pseq_bwd(const float *dout, const float *dhT, const float *gates, const float *out, const float *h0, const float *whh_t,
                           float *dgi, float *dgh, float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, int seg_len,
                           void *stream);
+/* The same two launches with a step count per stream (chunk chains: utterances of different lengths in one call).  steps: DEVICE int32
+ * [B], 0 <= steps[b] <= T (clamped).  A group of streams runs max steps[b] dependent steps instead of T.  Stream b computes, bit for
+ * bit, what the plain call gives for it alone with T = steps[b]: out / gates (dgi / dgh) rows s < steps[b], hT[b] after its own last
+ * step (h0[b] where steps[b] = 0), dhT[b] entering at step steps[b] - 1.  Rows s >= steps[b] of out / gates / dgi / dgh are written as
+ * zeros by the kernel; dout / gates / out are not read there. */
+int se_train_gru_pseq_fwd_rows(const float *gi, const float *h0, const float *whh, const float *bhh, float *out, float *gates, float *hT,
+                               float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, const int32_t *steps, void *stream);
+int se_train_gru_pseq_bwd_rows(const float *dout, const float *dhT, const float *gates, const float *out, const float *h0, const float *whh_t,
+                               float *dgi, float *dgh, float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, int seg_len,
+                               const int32_t *steps, void *stream);
 
 /* ---- round 3: the norm / pointwise / signal stages of the training step, forward and backward (csrc/train_fused.hip.h) ----
  * Layout: activations [S][C][T][F] fp32, S = N segments x B utterances, SEGMENT-major (stream n * B + b), so the time history of

@@ -14,11 +14,25 @@
 // cdna_hip_programming.md Guideline 16 R1 in its counter form).  Nothing depends on dispatch order or XCD placement; the spin
 // is bounded (wall clock) and a timeout makes every workgroup leave the loop, so the grid always drains.
 //
+// Per-stream step counts (the ROWS = true instantiations of the two kernels; chunk chains: every
+// stream has its own length).  steps[b] in [0, T] (clamped here) is the number of steps stream b runs.  A group runs Tg = max steps[b]
+// over ALL its streams - every thread of every workgroup of the group folds the same Bg values, so the workgroups agree on the trip
+// count and on the arrival targets NWG (s + 1), which are unchanged.  A stream's arithmetic for s < steps[b] is the plain kernel's
+// (MFMA rows are independent); it stores out / gates (backward: dgi / dgh) only for s < steps[b], hT at its own last step (h0 where
+// steps[b] = 0), and the KERNEL zero-fills its rows s >= steps[b] after the step loop (no memset in the entry point, so no assumption
+// about the row layout).  Backward: dout / gates / out are not read at rows s >= steps[b]; dhT[b] enters at step steps[b] - 1.
+// The rows launches use 16-stream groups for any B (MT = 1 only; se_train.hip pseq_groups): a stream then runs in the instantiation it
+// would run in alone, which is what makes its result independent of the batch.  (The plain entry points put 17 .. 32 streams into ONE
+// two-tile group, and hipcc contracts (1 - z) n + z h differently there than in the one-tile kernels at H <= 256: those launches are
+// not bit-equal to a stream alone, so for 17 .. 32 streams rows-with-full-steps and the plain launch differ in the last bit.)
+//
 // MFMA: v_mfma_f32_16x16x4_f32 (exact fp32).  Lane l supplies A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15]; within
 // a wave's K share lane group q = l >> 4 contracts k = kbase + q * KJ + j at MFMA j (any order is fine as long as A and B agree),
 // so a lane's KJ operands are contiguous in memory (16-byte loads).  D: lane l holds rows 4 (l >> 4) + r, column l & 15.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace se {
 
@@ -57,10 +71,18 @@ struct GruPseqBwdArgs {
     int Bg;              // streams per group (see GruPseqFwdArgs)
 };
 
+// the ROWS instantiations take the plain arguments plus steps [B] (own structs: the plain kernels keep their kernarg layout)
+struct GruPseqFwdRowsArgs : GruPseqFwdArgs { const int *steps; };
+struct GruPseqBwdRowsArgs : GruPseqBwdArgs { const int *steps; };
+template <bool ROWS> using GruPseqFwdArgsT = std::conditional_t<ROWS, GruPseqFwdRowsArgs, GruPseqFwdArgs>;
+template <bool ROWS> using GruPseqBwdArgsT = std::conditional_t<ROWS, GruPseqBwdRowsArgs, GruPseqBwdArgs>;
+
 __device__ __forceinline__ long pseq_row(int b, int s, int Tseg, long ldN, long ldB) {
     const int n = s / Tseg;
     return (long)n * ldN + (long)b * ldB + (s - n * Tseg);
 }
+
+__device__ __forceinline__ int pseq_steps(const int *steps, int b, int T) { return min(max(steps[b], 0), T); }
 
 // one lane: arrive / wait until `target` arrivals are visible (bounded; returns false on timeout)
 __device__ __forceinline__ void pseq_arrive(unsigned *sync) { __hip_atomic_fetch_add((pgu32 *)sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -81,8 +103,8 @@ __device__ __forceinline__ bool pseq_wait(unsigned *sync, unsigned *tmo_word, un
     return true;
 }
 
-template <int KJ, int MT>
-__global__ __launch_bounds__(512) void k_gru_pseq_fwd(GruPseqFwdArgs a) {
+template <int KJ, int MT, bool ROWS>
+__global__ __launch_bounds__(512) void k_gru_pseq_fwd(GruPseqFwdArgsT<ROWS> a) {
     __shared__ float red[8][MT][3][4][64];
     __shared__ int s_fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -122,6 +144,23 @@ __global__ __launch_bounds__(512) void k_gru_pseq_fwd(GruPseqFwdArgs a) {
                 hown[mt][r] = row < B ? a.h0[(long)row * H + u0 + l15] : 0.0f;
             }
     }
+    // ROWS: Tg = the group's trip count, from ALL its streams in every thread; st = the step counts of this lane's rows
+    int Tg = a.T;
+    [[maybe_unused]] int st[MT][4];
+    [[maybe_unused]] const int *steps = nullptr;
+    if constexpr (ROWS) {
+        steps = a.steps + b0;
+        Tg = 0;
+        for (int i = 0; i < B; i++) Tg = max(Tg, pseq_steps(steps, i, a.T));
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int row = mt * 16 + kq * 4 + r;
+                st[mt][r] = row < B ? pseq_steps(steps, row, a.T) : 0;
+                if (wave == 0 && row < B && st[mt][r] == 0) a.hT[(long)row * H + u0 + l15] = hown[mt][r];   // hT = h0
+            }
+    }
     // gate pre-activations: independent of the recurrence, fetched ONE STEP AHEAD (every step touches new rows: an HBM round trip that
     // would otherwise sit on the step's critical path)
     float gir[MT][4], giz[MT][4], gin[MT][4], nir[MT][4], niz[MT][4], nin[MT][4];
@@ -135,15 +174,15 @@ __global__ __launch_bounds__(512) void k_gru_pseq_fwd(GruPseqFwdArgs a) {
                 xr[mt][r] = g[0]; xz[mt][r] = g[H]; xn[mt][r] = g[2 * H];
             }
     };
-    if (wave == 0) fetch_gi(0, nir, niz, nin);
+    if (wave == 0 && (!ROWS || Tg > 0)) fetch_gi(0, nir, niz, nin);
     __syncthreads();
-    for (int s = 0; s < a.T; s++) {
+    for (int s = 0; s < Tg; s++) {
         if (wave == 0) {
 #pragma unroll
             for (int mt = 0; mt < MT; mt++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) { gir[mt][r] = nir[mt][r]; giz[mt][r] = niz[mt][r]; gin[mt][r] = nin[mt][r]; }
-            if (s + 1 < a.T) fetch_gi(s + 1, nir, niz, nin);
+            if (s + 1 < Tg) fetch_gi(s + 1, nir, niz, nin);
         }
         pf32x4 acc[MT][3];
 #pragma unroll
@@ -203,10 +242,10 @@ __global__ __launch_bounds__(512) void k_gru_pseq_fwd(GruPseqFwdArgs a) {
                     const float hn = (1.0f - zg) * ng + zg * hown[mt][r];
                     hown[mt][r] = hn;
                     vr[mt][r] = rg; vz[mt][r] = zg; vn[mt][r] = ng; vg[mt][r] = gh_n;
-                    if (row < B && s + 1 < a.T)
+                    if (row < B && s + 1 < Tg)
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hn), rs, (((s & 1) * B + row) * H + u0 + l15) * 4, 0, 16);  // sc1
                 }
-            if (s + 1 < a.T) {
+            if (s + 1 < Tg) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the only storing wave drains its write-through stores before it signals
                 if (lane == 0) pseq_arrive(a.sync);
             }
@@ -217,24 +256,40 @@ __global__ __launch_bounds__(512) void k_gru_pseq_fwd(GruPseqFwdArgs a) {
                 for (int r = 0; r < 4; r++) {
                     const int row = mt * 16 + kq * 4 + r;
                     if (row >= B) continue;
+                    if constexpr (ROWS) if (s >= st[mt][r]) continue;
                     const long ro = pseq_row(row, s, a.Tseg, a.ldN, a.ldB);
                     a.out[ro * H + u0 + l15] = hown[mt][r];
                     if (a.gates) {
                         float *gs = a.gates + ro * 4 * H + u0 + l15;
                         gs[0] = vr[mt][r]; gs[H] = vz[mt][r]; gs[2 * H] = vn[mt][r]; gs[3 * H] = vg[mt][r];
                     }
-                    if (s + 1 == a.T) a.hT[(long)row * H + u0 + l15] = hown[mt][r];
+                    if (s + 1 == (ROWS ? st[mt][r] : Tg)) a.hT[(long)row * H + u0 + l15] = hown[mt][r];
                 }
-            if (s + 1 < a.T && lane == 0 && !pseq_wait(a.sync, tmo, NWG * (unsigned)(s + 1))) s_fail = 1;
+            if (s + 1 < Tg && lane == 0 && !pseq_wait(a.sync, tmo, NWG * (unsigned)(s + 1))) s_fail = 1;
         }
         __syncthreads();
         if (s_fail) break;  // uniform
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the sc1 loads below the poll
     }
+    if constexpr (ROWS) {  // rows s >= steps[b] of this workgroup's 16 units: zeros (all threads; 16 lanes per row)
+        for (int row = 0; row < B; row++) {
+            const int s0 = pseq_steps(steps, row, a.T);
+            for (int i = tid; i < (a.T - s0) * 16; i += blockDim.x) {
+                const long ro = pseq_row(row, s0 + (i >> 4), a.Tseg, a.ldN, a.ldB);
+                const int u = u0 + (i & 15);
+                a.out[ro * H + u] = 0.0f;
+                if (a.gates) {
+                    float *gs = a.gates + ro * 4 * H + u;
+                    gs[0] = 0.0f; gs[H] = 0.0f; gs[2 * H] = 0.0f; gs[3 * H] = 0.0f;
+                }
+            }
+        }
+    }
 }
 
-template <int KJ, int MT>
-__global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
+
+template <int KJ, int MT, bool ROWS>
+__global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgsT<ROWS> a) {
     __shared__ float red[8][MT][4][64];
     __shared__ int s_fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -262,6 +317,22 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
         }
     }
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.gx, 0, (int)(2L * B * K3 * 4), 0x00020000);
+    // ROWS: Tg = the group's trip count, from ALL its streams in every thread; st = the step counts of this lane's rows
+    int Tg = a.T;
+    [[maybe_unused]] int st[MT][4];
+    [[maybe_unused]] const int *steps = nullptr;
+    if constexpr (ROWS) {
+        steps = a.steps + b0;
+        Tg = 0;
+        for (int i = 0; i < B; i++) Tg = max(Tg, pseq_steps(steps, i, a.T));
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int row = mt * 16 + kq * 4 + r;
+                st[mt][r] = row < B ? pseq_steps(steps, row, a.T) : 0;
+            }
+    }
     float dhz[MT][4], gown[MT][4];  // wave 0: z_{s+1} dh_{s+1} and (dgh_{s+1} W_hh) of its (row, unit) pairs
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
@@ -280,6 +351,12 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int row = min(mt * 16 + kq * 4 + r, B - 1);
+                if constexpr (ROWS)
+                    if (s >= st[mt][r]) {   // a dead row: nothing is read (the step skips it)
+#pragma unroll
+                        for (int k = 0; k < 6; k++) x[mt][r][k] = 0.0f;
+                        continue;
+                    }
                 const long ro = pseq_row(row, s, a.Tseg, a.ldN, a.ldB);
                 const int u = u0 + l15;
                 const float *g = a.gates + ro * 4 * H + u;
@@ -288,11 +365,11 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
                 x[mt][r][5] = s == 0 ? a.h0[(long)row * H + u] : a.out[pseq_row(row, s - 1, a.Tseg, a.ldN, a.ldB) * H + u];
             }
     };
-    if (wave == 0) fetch_in(a.T - 1, nin6);
+    if (wave == 0 && (!ROWS || Tg > 0)) fetch_in(Tg - 1, nin6);
     __syncthreads();
-    for (int s = a.T - 1; s >= 0; s--) {
-        const int it = a.T - 1 - s;
-        const bool cut = s + 1 < a.T && a.seg_len > 0 && (s + 1) % a.seg_len == 0;  // uniform: nothing flows back across a seam
+    for (int s = Tg - 1; s >= 0; s--) {
+        const int it = Tg - 1 - s;
+        const bool cut = s + 1 < Tg && a.seg_len > 0 && (s + 1) % a.seg_len == 0;  // uniform: nothing flows back across a seam
         if (wave == 0) {
 #pragma unroll
             for (int mt = 0; mt < MT; mt++)
@@ -307,9 +384,14 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
                 for (int r = 0; r < 4; r++) {
                     const int row = mt * 16 + kq * 4 + r;
                     if (row >= B) continue;
+                    if constexpr (ROWS) if (s >= st[mt][r]) continue;   // dead: dhz keeps dhT, which enters at step st - 1
                     const int u = u0 + l15;
                     float dh = pin[mt][r][0];
-                    if (!cut) dh += dhz[mt][r] + gown[mt][r];
+                    if constexpr (ROWS) {
+                        if (!(cut && s + 1 < st[mt][r])) dh += dhz[mt][r] + gown[mt][r];   // a stream's own last step is no seam
+                    } else {
+                        if (!cut) dh += dhz[mt][r] + gown[mt][r];
+                    }
                     const float rg = pin[mt][r][1], zg = pin[mt][r][2], ng = pin[mt][r][3], ghn = pin[mt][r][4];
                     const float hp = pin[mt][r][5];
                     const float dn = dh * (1.0f - zg), dz = dh * (hp - ng);
@@ -335,6 +417,7 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
                 for (int r = 0; r < 4; r++) {
                     const int row = mt * 16 + kq * 4 + r;
                     if (row >= B) continue;
+                    if constexpr (ROWS) if (s >= st[mt][r]) continue;
                     const long ro = pseq_row(row, s, a.Tseg, a.ldN, a.ldB);
                     float *gi = a.dgi + ro * K3 + u0 + l15, *gh = a.dgh + ro * K3 + u0 + l15;
                     gi[0] = vo[mt][r][0]; gi[H] = vo[mt][r][1]; gi[2 * H] = vo[mt][r][2];
@@ -381,10 +464,22 @@ __global__ __launch_bounds__(512) void k_gru_pseq_bwd(GruPseqBwdArgs a) {
                     float p = acc[mt][r];
                     for (int wv = 1; wv < nw; wv++) p += red[wv][mt][r][lane];
                     gown[mt][r] = p;
+                    if constexpr (ROWS) if (s >= st[mt][r]) gown[mt][r] = 0.0f;   // step s of a dead row published nothing
                 }
         }
         // the other waves may not overwrite `red` before wave 0 has read it: they next write it after the NEXT step's first
         // barrier, which wave 0 only reaches after these reads
+    }
+    if constexpr (ROWS) {  // rows s >= steps[b] of this workgroup's 16 units: zeros (all threads; 16 lanes per row)
+        for (int row = 0; row < B; row++) {
+            const int s0 = pseq_steps(steps, row, a.T);
+            for (int i = tid; i < (a.T - s0) * 16; i += blockDim.x) {
+                const long ro = pseq_row(row, s0 + (i >> 4), a.Tseg, a.ldN, a.ldB);
+                float *gi = a.dgi + ro * K3 + u0 + (i & 15), *gh = a.dgh + ro * K3 + u0 + (i & 15);
+                gi[0] = 0.0f; gi[H] = 0.0f; gi[2 * H] = 0.0f;
+                gh[0] = 0.0f; gh[H] = 0.0f; gh[2 * H] = 0.0f;
+            }
+        }
     }
 }
 

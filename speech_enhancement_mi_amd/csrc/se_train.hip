@@ -67,65 +67,103 @@ int se_train_gru_pseq_supported(int B, int H) { return B >= 1 && H > 0 && H % 16
 // One launch for ANY number of independent streams: groups of Bg <= 32 streams (blockIdx.y), each group = H/16 resident workgroups with
 // their own arrival counter and exchange slab.  Blocks are dispatched group-major, so a group's workgroups become resident together and a
 // group that does not fit yet simply waits in the dispatcher until an earlier group drains - groups never wait on each other.
-#define SE_PSEQ_LAUNCH(KERNEL, ARGS)                                                                         \
+#define SE_PSEQ_LAUNCH(KERNEL, ROWS, ARGS)                                                                        \
     do {                                                                                                     \
         const dim3 grid(H / 16, groups), block(64 * (H / (4 * kj)));                                         \
         if (MT == 1) {                                                                                       \
-            if (kj == 4) hipLaunchKernelGGL((se::KERNEL<4, 1>), grid, block, 0, st, ARGS);                   \
-            else if (kj == 8) hipLaunchKernelGGL((se::KERNEL<8, 1>), grid, block, 0, st, ARGS);              \
-            else if (kj == 16) hipLaunchKernelGGL((se::KERNEL<16, 1>), grid, block, 0, st, ARGS);            \
-            else hipLaunchKernelGGL((se::KERNEL<32, 1>), grid, block, 0, st, ARGS);                          \
+            if (kj == 4) hipLaunchKernelGGL((se::KERNEL<4, 1, ROWS>), grid, block, 0, st, ARGS);                   \
+            else if (kj == 8) hipLaunchKernelGGL((se::KERNEL<8, 1, ROWS>), grid, block, 0, st, ARGS);              \
+            else if (kj == 16) hipLaunchKernelGGL((se::KERNEL<16, 1, ROWS>), grid, block, 0, st, ARGS);            \
+            else hipLaunchKernelGGL((se::KERNEL<32, 1, ROWS>), grid, block, 0, st, ARGS);                          \
         } else {                                                                                             \
-            if (kj == 4) hipLaunchKernelGGL((se::KERNEL<4, 2>), grid, block, 0, st, ARGS);                   \
-            else if (kj == 8) hipLaunchKernelGGL((se::KERNEL<8, 2>), grid, block, 0, st, ARGS);              \
-            else if (kj == 16) hipLaunchKernelGGL((se::KERNEL<16, 2>), grid, block, 0, st, ARGS);            \
-            else hipLaunchKernelGGL((se::KERNEL<32, 2>), grid, block, 0, st, ARGS);                          \
+            constexpr int MT2 = ROWS ? 1 : 2; /* the rows launches never form a two-tile group (pseq_groups) */    \
+            if (kj == 4) hipLaunchKernelGGL((se::KERNEL<4, MT2, ROWS>), grid, block, 0, st, ARGS);                 \
+            else if (kj == 8) hipLaunchKernelGGL((se::KERNEL<8, MT2, ROWS>), grid, block, 0, st, ARGS);            \
+            else if (kj == 16) hipLaunchKernelGGL((se::KERNEL<16, MT2, ROWS>), grid, block, 0, st, ARGS);          \
+            else hipLaunchKernelGGL((se::KERNEL<32, MT2, ROWS>), grid, block, 0, st, ARGS);                        \
         }                                                                                                    \
     } while (0)
 
-static void pseq_groups(int B, int &Bg, int &groups, int &MT) {
+// rows (the _rows entry points): 16-stream groups for ANY B, so a stream always runs in the one-tile kernel it would run in alone -
+// the two-tile instantiations round the state update differently (the compiler contracts (1 - z) n + z h the other way round), which
+// a result that must not depend on the batch cannot have
+static void pseq_groups(int B, int &Bg, int &groups, int &MT, bool rows = false) {
     // 16-stream groups (one MFMA row tile) once there are more streams than two groups' worth: more groups in flight, shorter steps
     Bg = B <= 32 ? B : 16;
-    if (B <= 32 && B > 16) Bg = B;
+    if (rows && B > 16) Bg = 16;
     groups = (B + Bg - 1) / Bg;
     MT = Bg > 16 ? 2 : 1;
 }
 
 int se_train_gru_pseq_scratch_floats(int B, int H) {
     int Bg, groups, MT;
-    pseq_groups(B, Bg, groups, MT);
+    pseq_groups(B, Bg, groups, MT, true);   // covers the plain launches too: 17 .. 32 streams are one group there, two here
     return 16 * groups + groups * 2 * Bg * 3 * H;
 }
 
-int se_train_gru_pseq_fwd(const float *gi, const float *h0, const float *whh, const float *bhh, float *out, float *gates, float *hT,
-                          float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, void *stream) {
+// steps: null = the plain kernels (every stream runs T steps), else the per-stream step counts of the _rows entry points
+static int pseq_fwd(const float *gi, const float *h0, const float *whh, const float *bhh, float *out, float *gates, float *hT, float *scratch, int B, int T,
+                    int H, int Tseg, int64_t ldN, int64_t ldB, const int32_t *steps, void *stream) {
     if (!gi || !h0 || !whh || !bhh || !out || !hT || !scratch || T <= 0 || Tseg <= 0) return train_fail(SE_ERR_ARG, "null / bad argument");
     if (!se_train_gru_pseq_supported(B, H)) return train_fail(SE_ERR_ARG, "persistent GRU: B = %d, H = %d unsupported", B, H);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int Bg, groups, MT;
-    pseq_groups(B, Bg, groups, MT);
-    if (groups > 1 && ldN != 0) return train_fail(SE_ERR_ARG, "more than 32 streams need rows [B][T] (ldN = 0)");
+    pseq_groups(B, Bg, groups, MT, steps != nullptr);
+    if (groups > 1 && ldN != 0) return train_fail(SE_ERR_ARG, "more than %d streams need rows [B][T] (ldN = 0)", steps ? 16 : 32);
     const int kj = se::pseq_kj(H);
     if (hipMemsetAsync(scratch, 0, (size_t)64 * groups, st) != hipSuccess) return train_fail(SE_ERR_HIP, "memset failed");  // arrival counters + timeout word
     se::GruPseqFwdArgs a{gi, h0, whh, bhh, out, gates, hT, scratch + 16 * groups, reinterpret_cast<unsigned *>(scratch), B, T, H, Tseg, (long)ldN, (long)ldB, Bg};
-    SE_PSEQ_LAUNCH(k_gru_pseq_fwd, a);
+    if (steps) {
+        const se::GruPseqFwdRowsArgs r{a, steps};
+        SE_PSEQ_LAUNCH(k_gru_pseq_fwd, true, r);
+    } else {
+        SE_PSEQ_LAUNCH(k_gru_pseq_fwd, false, a);
+    }
     return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "persistent GRU forward launch failed");
+}
+
+int se_train_gru_pseq_fwd(const float *gi, const float *h0, const float *whh, const float *bhh, float *out, float *gates, float *hT,
+                          float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, void *stream) {
+    return pseq_fwd(gi, h0, whh, bhh, out, gates, hT, scratch, B, T, H, Tseg, ldN, ldB, nullptr, stream);
+}
+
+int se_train_gru_pseq_fwd_rows(const float *gi, const float *h0, const float *whh, const float *bhh, float *out, float *gates, float *hT,
+                               float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, const int32_t *steps, void *stream) {
+    if (!steps) return train_fail(SE_ERR_ARG, "null / bad argument");
+    return pseq_fwd(gi, h0, whh, bhh, out, gates, hT, scratch, B, T, H, Tseg, ldN, ldB, steps, stream);
+}
+
+static int pseq_bwd(const float *dout, const float *dhT, const float *gates, const float *out, const float *h0, const float *whh_t, float *dgi, float *dgh,
+                    float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, int seg_len, const int32_t *steps, void *stream) {
+    if (!dout || !gates || !out || !h0 || !whh_t || !dgi || !dgh || !scratch || T <= 0 || Tseg <= 0) return train_fail(SE_ERR_ARG, "null / bad argument");
+    if (!se_train_gru_pseq_supported(B, H)) return train_fail(SE_ERR_ARG, "persistent GRU: B = %d, H = %d unsupported", B, H);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int Bg, groups, MT;
+    pseq_groups(B, Bg, groups, MT, steps != nullptr);
+    if (groups > 1 && ldN != 0) return train_fail(SE_ERR_ARG, "more than %d streams need rows [B][T] (ldN = 0)", steps ? 16 : 32);
+    const int kj = se::pseq_kj(H);
+    if (hipMemsetAsync(scratch, 0, (size_t)64 * groups, st) != hipSuccess) return train_fail(SE_ERR_HIP, "memset failed");
+    se::GruPseqBwdArgs a{dout, dhT, gates, out, h0, whh_t, dgi, dgh, scratch + 16 * groups, reinterpret_cast<unsigned *>(scratch), B, T, H, Tseg, seg_len, (long)ldN, (long)ldB, Bg};
+    if (steps) {
+        const se::GruPseqBwdRowsArgs r{a, steps};
+        SE_PSEQ_LAUNCH(k_gru_pseq_bwd, true, r);
+    } else {
+        SE_PSEQ_LAUNCH(k_gru_pseq_bwd, false, a);
+    }
+    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "persistent GRU backward launch failed");
 }
 
 int se_train_gru_pseq_bwd(const float *dout, const float *dhT, const float *gates, const float *out, const float *h0, const float *whh_t,
                           float *dgi, float *dgh, float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, int seg_len,
                           void *stream) {
-    if (!dout || !gates || !out || !h0 || !whh_t || !dgi || !dgh || !scratch || T <= 0 || Tseg <= 0) return train_fail(SE_ERR_ARG, "null / bad argument");
-    if (!se_train_gru_pseq_supported(B, H)) return train_fail(SE_ERR_ARG, "persistent GRU: B = %d, H = %d unsupported", B, H);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int Bg, groups, MT;
-    pseq_groups(B, Bg, groups, MT);
-    if (groups > 1 && ldN != 0) return train_fail(SE_ERR_ARG, "more than 32 streams need rows [B][T] (ldN = 0)");
-    const int kj = se::pseq_kj(H);
-    if (hipMemsetAsync(scratch, 0, (size_t)64 * groups, st) != hipSuccess) return train_fail(SE_ERR_HIP, "memset failed");
-    se::GruPseqBwdArgs a{dout, dhT, gates, out, h0, whh_t, dgi, dgh, scratch + 16 * groups, reinterpret_cast<unsigned *>(scratch), B, T, H, Tseg, seg_len, (long)ldN, (long)ldB, Bg};
-    SE_PSEQ_LAUNCH(k_gru_pseq_bwd, a);
-    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "persistent GRU backward launch failed");
+    return pseq_bwd(dout, dhT, gates, out, h0, whh_t, dgi, dgh, scratch, B, T, H, Tseg, ldN, ldB, seg_len, nullptr, stream);
+}
+
+int se_train_gru_pseq_bwd_rows(const float *dout, const float *dhT, const float *gates, const float *out, const float *h0, const float *whh_t,
+                               float *dgi, float *dgh, float *scratch, int B, int T, int H, int Tseg, int64_t ldN, int64_t ldB, int seg_len,
+                               const int32_t *steps, void *stream) {
+    if (!steps) return train_fail(SE_ERR_ARG, "null / bad argument");
+    return pseq_bwd(dout, dhT, gates, out, h0, whh_t, dgi, dgh, scratch, B, T, H, Tseg, ldN, ldB, seg_len, steps, stream);
 }
 
 #define TCHECK(call)                                                                                             \

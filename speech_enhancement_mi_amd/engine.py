@@ -23,7 +23,7 @@ EXPORTS = [
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
     "fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state",
     "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "fsn_train_ws_bytes_chains", "fsn_train_fwd_chains", "fsn_train_bwd_chains", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
-    "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd",
+    "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd", "se_train_gru_pseq_fwd_rows", "se_train_gru_pseq_bwd_rows",
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
     "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
     "se_train_add", "se_train_add3", "se_train_gate_fwd", "se_train_gate_bwd", "se_train_elu_bwd", "se_train_pre5", "se_train_gru_hprev", "se_train_conv_ws_floats", "se_train_conv_w", "se_train_conv_wgrad_det", "se_train_gemm_tn_det", "se_train_add_csum", "se_distill_ws_bytes",
@@ -132,6 +132,8 @@ def load_library():
     L.se_train_gru_pseq_scratch_floats.argtypes = [i32, i32]
     L.se_train_gru_pseq_fwd.argtypes = [vp] * 8 + [i32, i32, i32, i32, i64, i64, vp]
     L.se_train_gru_pseq_bwd.argtypes = [vp] * 9 + [i32, i32, i32, i32, i64, i64, i32, vp]
+    L.se_train_gru_pseq_fwd_rows.argtypes = [vp] * 8 + [i32, i32, i32, i32, i64, i64, vp, vp]
+    L.se_train_gru_pseq_bwd_rows.argtypes = [vp] * 9 + [i32, i32, i32, i32, i64, i64, i32, vp, vp]
     L.se_sig_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.se_sig_destroy.argtypes = [vp]
     L.se_sig_destroy.restype = None

@@ -5,7 +5,8 @@ Same constructor, state_dict keys and shapes (the `convlist.i.conv.*` / `net.0.*
 last decoder block included), same entry points:
 
     forward(x[B, M, F, T, 2]) -> [B, F, T, 2]          one segment, stateful (GeneralBeamformer.py:318-373)
-    realtime_process(mixture[B, M, L], flag) -> [B, L]  GeneralBeamformer.py:449-496
+    realtime_process(mixture[B, M, L], flag, lengths=None) -> [B, L]  GeneralBeamformer.py:449-496; with per-utterance flags /
+                                                        lengths the batch is B independent chunk chains (all three paths)
     reset(), compute_loss(source, pred_source, length)
 
 Two interchangeable paths:
@@ -20,14 +21,16 @@ Two interchangeable paths:
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .train_stages import (_as_flag, _cs, _new, _p, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd, encoder_block_fwd,
-                           gemm_tn, grads_in_parameter_order, gru_layer_bwd, input_features, istft, overlap_add, segment_geometry, stft,
-                           synthesis_adjoint)
+from .train_stages import (_as_flags, _as_lengths, _cs, _new, _p, _rows, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd,
+                           encoder_block_fwd, gemm_tn, grads_in_parameter_order, gru_layer_bwd, input_features, istft, overlap_add,
+                           ragged_geometry, segment_geometry, slab_gather, stft, stft_rows, synthesis_adjoint, synthesis_adjoint_rows)
 
 EPS = 1e-8
 _DEFAULT_MAX_SEGMENTS = 8
@@ -169,8 +172,23 @@ class GeneralBeamformer(nn.Module):
         self._hip_train = bool(flag)
         return self
 
-    def realtime_process(self, mixture, flag=False):
-        flag = _as_flag(flag)
+    def realtime_process(self, mixture, flag=False, lengths=None):
+        """flag: a bool, one value, or one per utterance ([B] tensor / list); lengths: per-utterance lengths <= mixture.shape[-1] (None:
+        all full).  With either given per utterance the batch is B independent chunk chains (datagen.ChunkChainBatch), the semantics of
+        train_net.realtime_process_fused: utterance b is zero beyond lengths[b] (whatever the padding holds), starts from zero state where
+        flag[b] is False and continues row b of the carried state where it is True; pred[b, lengths[b]:] = 0, and the carried state
+        afterwards holds, per utterance, what that utterance alone would carry.  A batch whose flags and lengths are all alike takes the
+        uniform code path, as a bool flag does."""
+        B, _, Lmax = mixture.shape
+        chains = None
+        if lengths is not None or isinstance(flag, (torch.Tensor, list, tuple)):
+            flags, lens = _as_flags(flag, B), _as_lengths(lengths, B, Lmax)
+            if len(set(flags)) == 1 and min(lens) == Lmax:
+                flag = flags[0]
+            else:
+                chains, flag = (tuple(flags), tuple(lens)), any(flags)
+        else:
+            flag = bool(flag)
         grad = torch.is_grad_enabled()
         train = self._hip_train and mixture.is_cuda and grad
         path = "kernel" if train or (self._hip and mixture.is_cuda and not grad) else "torch"
@@ -181,13 +199,13 @@ class GeneralBeamformer(nn.Module):
             if err:
                 raise ValueError(f"GeneralBeamformer HIP training: {err}")
             params = [p for _, p in self.named_parameters()]
-            out = GBFFunction.apply(self, mixture, flag, *params)
+            out = GBFFunction.apply(self, mixture, chains or flag, *params)
             self._last_path = path
             return out
         self._last_path = path
         if path == "kernel":
-            return self._kernel_process(mixture, flag)
-        return self._torch_process(mixture, flag)
+            return self._kernel_process(mixture, chains or flag)
+        return self._torch_chains(mixture, *chains) if chains else self._torch_process(mixture, flag)
 
     # ---- torch restatement ---------------------------------------------------------------------------------------------------
     def _segment(self, x, st):
@@ -299,6 +317,24 @@ class GeneralBeamformer(nn.Module):
             out = out[:, :-gap]
         return out if flag else out[:, P:]
 
+    def _torch_chains(self, mixture, flags, lens):
+        """A batch of chunk chains on the restatement (the oracle of the kernel paths): every utterance alone on its own rows of the
+        carried state, the results merged."""
+        B = mixture.shape[0]
+        st = self._tstate
+        if any(flags) and (st is None or st["buf"][0].shape[0] != B):
+            raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is "
+                             f"{'none' if st is None else 'one of ' + str(st['buf'][0].shape[0])}")
+        F = self.num_freqs
+        preds, states = [], []
+        for b, (f, L) in enumerate(zip(flags, lens)):
+            self._tstate = dict(buf=[t[b:b + 1] for t in st["buf"]], hS=st["hS"][:, b * F:(b + 1) * F], hN=st["hN"][:, b * F:(b + 1) * F]) if f else None
+            preds.append(Fn.pad(self._torch_process(mixture[b:b + 1, :, :L], f), (0, mixture.shape[-1] - L)))
+            states.append(self._tstate)
+        self._tstate = dict(buf=[torch.cat([s_["buf"][i] for s_ in states]) for i in range(len(self.convlist))],
+                            hS=torch.cat([s_["hS"] for s_ in states], dim=1), hN=torch.cat([s_["hN"] for s_ in states], dim=1))
+        return torch.cat(preds)
+
     # ---- kernel path ---------------------------------------------------------------------------------------------------------
     def kernel_geometry_error(self):
         """None when the kernel path supports this geometry, else the limit that fails (realtime_process raises it as ValueError)."""
@@ -350,17 +386,35 @@ class GeneralBeamformer(nn.Module):
         return None
 
     def _kernel_setup(self, mixture, flag):
-        """Geometry of one realtime_process call on the kernels and the state it starts from (the carried one for flag=True)."""
+        """Geometry of one realtime_process call on the kernels and the state it starts from (the carried one for flag=True).  flag: a
+        bool, or (flags, lengths) of a batch of chunk chains - then every utterance keeps the geometry it would have alone
+        (train_stages.ragged_geometry), g["rows"] holds what the row kernels index by utterance, and the start state is row b of the
+        carried one where flags[b], zeros elsewhere."""
         dev = mixture.device
         B, M, L = mixture.shape
         c = self._cfg
         H, NL, ch = c["hidden"], c["num_layers"], [2 * M - 1] + c["num_channels"]
-        g = segment_geometry(L, flag, self.segment_length, self._hop, c["n_fft"], ch)
+        chains = flag if isinstance(flag, tuple) else None
+        if chains:
+            g = ragged_geometry(chains[1], chains[0], self.segment_length, self._hop, c["n_fft"], ch)
+            g["L"], flag = L, any(chains[0])
+            g["rows"] = dict(len=_rows(g["lengths"], dev), skip=_rows(g["skip"], dev))
+        else:
+            g = segment_geometry(L, flag, self.segment_length, self._hop, c["n_fft"], ch)
         T, F0, Fq, Lv = g["T"], g["F0"], g["Fq"], len(self.convlist)
         g.update(B=B, M=M, n_fft=c["n_fft"], H=H, NL=NL, Lv=Lv, BF=B * F0, sig=_sig(dev, c["n_fft"], self._win, self._hop, self.segment_length))
         state = self._kstate if flag else None
+        if chains and flag and state is None:
+            raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is none")
         if state is not None and state["B"] != B:
             raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
+        if chains and state is not None:   # mixed flags: the carried row where flags[b], zeros where utterance b starts afresh
+            carry = _rows([0 if f else -1 for f in chains[0]], dev)
+
+            def start(t, X):
+                return slab_gather(t, carry, B, X, B * X, X).view(t.shape)
+
+            state = dict(B=B, buf=[start(t, t[0].numel()) for t in state["buf"]], h=[[start(t, F0 * H) for t in hq] for hq in state["h"]])
         if state is None:
             state = dict(B=B, buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
                          h=[[torch.zeros(B * F0, H, device=dev) for _ in range(NL)] for _ in range(2)])
@@ -375,7 +429,14 @@ class GeneralBeamformer(nn.Module):
         B, M, L, T, F0, H, NL, Lv, ch, Fq, BF, P = (g[k] for k in ("B", "M", "L", "T", "F0", "H", "NL", "Lv", "ch", "Fq", "BF", "P"))
         S = Nc * B
         keep = sv is not None
-        spec = stft(g["sig"], mixture, B, M, L, g["off0"] + n0 * P, P, Nc, T, F0)
+        chain = g.get("rows")
+        if chain:   # chunk chains: utterance b has live[b] of this pass's Nc segments; its GRU streams run live[b] * T steps
+            live = [min(max(nb - n0, 0), Nc) for nb in g["Nb"]]
+            steps = torch.tensor(live, dtype=torch.int32).mul_(T).repeat_interleave(F0).to(dev, non_blocking=True)
+            spec = stft_rows(g["sig"], mixture, B, M, L, _rows([o + n0 * P for o in g["off0"]], dev), chain["len"], P, Nc, T, F0)
+        else:
+            steps = None
+            spec = stft(g["sig"], mixture, B, M, L, g["off0"] + n0 * P, P, Nc, T, F0)
         # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input of block i (its time history)
         xin = []
         for i in range(Lv):
@@ -410,7 +471,7 @@ class GeneralBeamformer(nn.Module):
                 gt = _new(R, 4 * H, dev=dev) if keep else None
                 hT = _new(BF, H, dev=dev)
                 sc = K._gru_seq_fwd(gi, state["h"][q][l], getattr(gm, f"weight_hh_l{l}"), getattr(gm, f"bias_hh_l{l}"), out, gt, hT, BF, TT, H, TT, 0, TT,
-                                    tag=("gbf", q, l))
+                                    tag=("gbf", q, l), steps=steps)
                 tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
                 del gi
                 if keep:
@@ -433,7 +494,12 @@ class GeneralBeamformer(nn.Module):
         _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
              _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
         istft(g["sig"], Y, yseg.view(-1, g["Ks"]), n0 * B)
-        state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
+        if chain:   # every utterance's own last live segment of the pass; slab 0 (its previous rows) where it has none
+            last = _rows(live, dev)
+            state["buf"] = [slab_gather(xin[i], last, B, xin[i][0][0].numel(), xin[i][0].numel(), xin[i][0][0].numel()).view(xin[i].shape[1:])
+                            for i in range(Lv)]
+        else:
+            state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
         if keep:
             sv.update(spec=spec, xin=xin, ys=ys, stats_e=stats_e, dec=dec, xl=xl, rows=rows, outs=outs, gates=gates, h0s=h0s, phi=phi)
 
@@ -452,7 +518,12 @@ class GeneralBeamformer(nn.Module):
         step = N if sv is not None else max(1, int(self.max_segments))
         for n0 in range(0, N, step):
             self._kernel_pass(mixture, g, state, n0, min(step, N - n0), yseg, tmo, sv)
-        pred = overlap_add(g["sig"], yseg, B, g["L"], g["skip"])
+        if "rows" in g:
+            pred = _new(B, g["L"], dev=mixture.device)
+            _run("k_tola", 0.0, K._lib().se_train_ola_fwd_rows, g["sig"], _p(yseg), _p(pred), B, g["L"], C.c_void_p(g["rows"]["skip"].data_ptr()),
+                 C.c_void_p(g["rows"]["len"].data_ptr()), K._st())
+        else:
+            pred = overlap_add(g["sig"], yseg, B, g["L"], g["skip"])
         self._kstate = state
         return pred, g, tmo
 
@@ -471,7 +542,8 @@ class GeneralBeamformer(nn.Module):
 
 class GBFFunction(torch.autograd.Function):
     """pred = GeneralBeamformer.realtime_process(mixture, flag) on the kernels, forward AND backward, as one autograd node
-    (reference training step train.py:195-204).  forward(ctx, model, mixture, flag, *params), params in named_parameters() order.
+    (reference training step train.py:195-204).  forward(ctx, model, mixture, flag, *params), params in named_parameters() order;
+    flag: a bool, or (flags, lengths) of a batch of chunk chains (_kernel_setup).
 
     Forward: the inference kernel path over all N segments of the call in one pass, keeping the GRU gates, layer outputs and U-Net
     activations.  Backward: OLA / iSTFT adjoint, se_gbf_bf_bwd, se_gbf_seq_bwd, the GRU layers (train_stages.gru_layer_bwd),
@@ -500,7 +572,14 @@ class GBFFunction(torch.autograd.Function):
         grads = {}
         zero_bias = torch.zeros(256, device=dev)
 
-        dY = synthesis_adjoint(sig, dpred, B, N, q["L"], q["skip"], Ks, T, F0)
+        chain = q.get("rows")
+        if chain:   # chunk chains: dpred[b, lengths[b]:] is never read; a sequence of the GRU sweep is one (stream, segment) pair
+            dY = synthesis_adjoint_rows(sig, dpred, B, N, q["L"], chain["skip"], chain["len"], Ks, T, F0)
+            steps = (torch.arange(N)[None, :] < torch.tensor(q["Nb"])[:, None]).to(torch.int32).mul_(T).repeat_interleave(F0, dim=0)
+            steps = steps.reshape(-1).to(dev, non_blocking=True)
+        else:
+            dY = synthesis_adjoint(sig, dpred, B, N, q["L"], q["skip"], Ks, T, F0)
+            steps = None
         # beamformer + linear head
         FT = F0 * T
         R1 = S * FT
@@ -544,7 +623,7 @@ class GBFFunction(torch.autograd.Function):
                 w_ih = model._padded_w_ih(gm) if l == 0 else getattr(gm, f"weight_ih_l{l}")
                 x_l = rows[qi] if l == 0 else outs[qi][l - 1]
                 dlayer = gru_layer_bwd(dlayer, outs[qi][l], gates[qi][l], h0s[qi][l], x_l, w_ih, getattr(gm, f"weight_hh_l{l}"),
-                                       f"{name}.sequence_model.", l, grads, BF, N, T, H, N * T, 0, N * T, tag=("gbf_bwd", qi, l), tmo=tmo)
+                                       f"{name}.sequence_model.", l, grads, BF, N, T, H, N * T, 0, N * T, tag=("gbf_bwd", qi, l), tmo=tmo, steps=steps)
                 if l == 0:   # [3H][16] against the padded rows: the parameter is [3H][9]; dlayer [R][16] = the gradient of the GRU input rows
                     grads[f"{name}.sequence_model.weight_ih_l0"] = grads[f"{name}.sequence_model.weight_ih_l0"][:, :9].contiguous()
             drows.append(dlayer)

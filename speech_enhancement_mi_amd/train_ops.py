@@ -280,14 +280,27 @@ def pseq_check():
             raise RuntimeError(f"persistent GRU kernel timed out waiting for its peer workgroups (device {key[0]}, B = {key[1]}, H = {key[2]})")
 
 
-def _gru_seq_fwd(gi, h0, w_hh, b_hh, out, gates, hT, B, T, H, Tseg, ldN, ldB, tag=0):
-    """All T steps of one layer.  gi / out / gates rows are addressed as row(b, s) = (s // Tseg) * ldN + b * ldB + s % Tseg.  -> scratch"""
+def _steps_ptr(steps, B):
+    if steps.dtype != torch.int32 or not steps.is_cuda or not steps.is_contiguous() or steps.numel() != B:
+        raise ValueError(f"steps must be a contiguous device int32 tensor of {B} entries")
+    return C.c_void_p(steps.data_ptr())
+
+
+def _gru_seq_fwd(gi, h0, w_hh, b_hh, out, gates, hT, B, T, H, Tseg, ldN, ldB, tag=0, steps=None):
+    """All T steps of one layer.  gi / out / gates rows are addressed as row(b, s) = (s // Tseg) * ldN + b * ldB + s % Tseg.  steps (a
+    device int32 [B], persistent kernel only): stream b runs steps[b] <= T steps, its later rows of out / gates are zeros.  -> scratch"""
     lib = _lib()
     if lib.se_train_gru_pseq_supported(B, H) and (B <= 32 or ldN == 0):  # ONE persistent launch (groups of <= 32 streams inside it)
         sc = _scratch(gi.device, B, H, tag)
         with _Timed("k_gru_pseq_fwd", 2.0 * B * 3 * H * H * T):
-            _chk(lib.se_train_gru_pseq_fwd(_p(gi), _p(h0), _p(w_hh), _p(b_hh), _p(out), _p(gates), _p(hT), _p(sc), B, T, H, Tseg, ldN, ldB, _st()))
+            if steps is None:
+                _chk(lib.se_train_gru_pseq_fwd(_p(gi), _p(h0), _p(w_hh), _p(b_hh), _p(out), _p(gates), _p(hT), _p(sc), B, T, H, Tseg, ldN, ldB, _st()))
+            else:
+                _chk(lib.se_train_gru_pseq_fwd_rows(_p(gi), _p(h0), _p(w_hh), _p(b_hh), _p(out), _p(gates), _p(hT), _p(sc), B, T, H, Tseg, ldN, ldB,
+                                                    _steps_ptr(steps, B), _st()))
         return sc
+    if steps is not None:
+        raise RuntimeError(f"hidden size {H}: per-stream step counts need the persistent GRU kernel")
     if Tseg != T or ldB != T:
         raise RuntimeError(f"hidden size {H}: no persistent GRU kernel, and the step-launch kernels take [B][T] rows only")
     for b0 in range(0, B, 16):  # step-launch kernels (round 2): groups of <= 16 streams
@@ -299,14 +312,21 @@ def _gru_seq_fwd(gi, h0, w_hh, b_hh, out, gates, hT, B, T, H, Tseg, ldN, ldB, ta
                                           C.c_void_p(hT.data_ptr() + 4 * b0 * H), _p(scratch), nb, T, H, _st()))
 
 
-def _gru_seq_bwd(dout, dhT, gates, out, h0, w_hh_t, dgi, dgh, B, T, H, Tseg, ldN, ldB, seg_len, tag=0):
+def _gru_seq_bwd(dout, dhT, gates, out, h0, w_hh_t, dgi, dgh, B, T, H, Tseg, ldN, ldB, seg_len, tag=0, steps=None):
+    """The BPTT sweep of _gru_seq_fwd; steps as there: rows s >= steps[b] of dgi / dgh are zeros and dout is not read there"""
     lib = _lib()
     if lib.se_train_gru_pseq_supported(B, H) and (B <= 32 or ldN == 0):
         sc = _scratch(dout.device, B, H, tag)
         with _Timed("k_gru_pseq_bwd", 2.0 * B * 3 * H * H * T):
-            _chk(lib.se_train_gru_pseq_bwd(_p(dout), _p(dhT), _p(gates), _p(out), _p(h0), _p(w_hh_t), _p(dgi), _p(dgh), _p(sc), B, T, H, Tseg, ldN, ldB,
-                                           seg_len, _st()))
+            if steps is None:
+                _chk(lib.se_train_gru_pseq_bwd(_p(dout), _p(dhT), _p(gates), _p(out), _p(h0), _p(w_hh_t), _p(dgi), _p(dgh), _p(sc), B, T, H, Tseg, ldN, ldB,
+                                               seg_len, _st()))
+            else:
+                _chk(lib.se_train_gru_pseq_bwd_rows(_p(dout), _p(dhT), _p(gates), _p(out), _p(h0), _p(w_hh_t), _p(dgi), _p(dgh), _p(sc), B, T, H, Tseg, ldN,
+                                                    ldB, seg_len, _steps_ptr(steps, B), _st()))
         return sc
+    if steps is not None:
+        raise RuntimeError(f"hidden size {H}: per-stream step counts need the persistent GRU kernel")
     if Tseg != T or ldB != T:
         raise RuntimeError(f"hidden size {H}: no persistent GRU kernel, and the step-launch kernels take [B][T] rows only")
     for b0 in range(0, B, 16):

@@ -311,20 +311,22 @@ def decoder_bwd(deconvlist, dec, xin, dout, grads, zero_bias, S, B, T, act, eps_
 
 
 # ---- GRU layer, backward ---------------------------------------------------------------------------------------------------------
-def gru_layer_bwd(dlayer, out, gates, h0, x_l, w_ih, w_hh, pre, l, grads, streams, nseg, T, H, Tseg, ldN, ldB, tag=0, tmo=None):
+def gru_layer_bwd(dlayer, out, gates, h0, x_l, w_ih, w_hh, pre, l, grads, streams, nseg, T, H, Tseg, ldN, ldB, tag=0, tmo=None, steps=None):
     """One GRU layer of the backward sweep.  out / gates / dlayer hold `streams` sequences of nseg * T steps, rows addressed like
     train_ops._gru_seq_fwd's (Tseg, ldN, ldB); h0 [streams][H] is the state the call started from.  The carried state is detached at
     every segment seam (CRN.py:281), so NOTHING flows back across a seam: the rows are already [streams * nseg][T], and the BPTT is
     ONE persistent launch over streams * nseg independent sequences of T steps, each entering at row 0 of its h_{t-1} block.
     w_ih: the weight the forward's input GEMM used (zero-padded columns included).  Gradients go to grads[pre + "weight_ih_l{l}"] ...
-    tag: the scratch buffer's (train_ops._scratch); tmo: a list that receives the launch's time-out word.  -> d x_l"""
+    tag: the scratch buffer's (train_ops._scratch); tmo: a list that receives the launch's time-out word.  steps (device int32
+    [streams * nseg], T or 0 per sequence; rows [streams][nseg * T] only): the dead sequences are skipped - dlayer is not read there and
+    their dgi / dgh rows are zeros, which is what the weight-gradient GEMMs and column sums over all rows need.  -> d x_l"""
     dev = out.device
     R, n = streams * nseg * T, streams * nseg
     hp = _new(R, H, dev=dev)
     _run("k_gru_hprev", 0.0, K._lib().se_train_gru_hprev, _p(out), _p(h0), _p(hp), streams, nseg * T, H, Tseg, ldN, ldB, K._st())
     h0seg = hp.view(n, T, H)[:, 0].contiguous()
     dgi, dgh = _new(R, 3 * H, dev=dev), _new(R, 3 * H, dev=dev)
-    sc = K._gru_seq_bwd(dlayer, None, gates, out, h0seg, transpose(w_hh), dgi, dgh, n, T, H, T, 0, T, 0, tag)
+    sc = K._gru_seq_bwd(dlayer, None, gates, out, h0seg, transpose(w_hh), dgi, dgh, n, T, H, T, 0, T, 0, tag, steps=steps)
     if tmo is not None:
         tmo.append(sc[:2].view(torch.int32)[1:2].clone())   # this launch's timeout word, before the next launch's memset
     grads[pre + f"weight_ih_l{l}"] = gemm_tn(dgi, x_l)
