@@ -156,8 +156,6 @@ class TemporalCRN(nn.Module):
         stream makes the call a batch of chunk chains (Engine.realtime_process_chains): stream b continues its own state where flag[b] is
         set, starts afresh where it is not, and every stream leaves the state it would carry alone."""
         eng = self._engine_for(mixture)
-        if not isinstance(flag, (torch.Tensor, list, tuple)):
-            flag = bool(flag)
         return eng.realtime_process(mixture.contiguous().float(), flag=flag, lengths=lengths)
 
     def compute_loss(self, source, pred_source, length):

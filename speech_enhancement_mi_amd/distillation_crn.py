@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from .crn import TemporalCRN as _Base
-from .train_stages import _as_flags, _as_lengths, segment_geometry
+from .call_plan import call_plan, segment_geometry
 
 
 class TemporalCRN(_Base):
@@ -256,10 +256,11 @@ class DistillationCRN(nn.Module):
         """flag and length per utterance: a batch of chunk chains (datagen.ChunkChainBatch) - teacher and student see utterance b up to
         length[b] only and continue their own row b where flag[b] holds; a batch of full-length utterances with one flag is the plain call."""
         B, Lmax = noisy.shape[0], noisy.shape[-1]
-        flags, lens = _as_flags(flag, B), _as_lengths(length, B, Lmax)
-        if len(set(flags)) == 1 and min(lens) == Lmax:
-            return self._forward(noisy, clean, length, flags[0], {})
-        return self._forward(noisy, clean, length, flags, dict(lengths=lens))
+        st = self.student
+        plan = call_plan(flag, length, B, Lmax, st.segment_length, st._hop, st._nfft)
+        if plan.uniform:
+            return self._forward(noisy, clean, length, plan.flag, {})
+        return self._forward(noisy, clean, length, plan.flags, dict(lengths=plan.lengths))
 
     def _forward(self, noisy, clean, length, flag, kw):
         if self._hip:

@@ -12,6 +12,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from .call_plan import chain_geometry, flags_of as _flags_of  # noqa: F401  (the geometry and the flag parser live there; these names stay)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libse_engine.so")
 SE_MAX_LEVELS = 8
@@ -203,39 +205,6 @@ def make_config(num_channels, num_freqs, hidden, segment_length, num_layers=1, n
     cfg.variant = int(variant)
     cfg.precision = int(precision)  # 0 = fp32-accurate (bf16x6), 1 = fp16 MFMA operands (model.half()), 2 = bf16x3 (set_precision)
     return cfg
-
-
-def chain_geometry(lengths, flags, segment_length):
-    """Per-stream segment geometry of one se_realtime_process_chains call (utility.py:327-329, 360-368 per stream, with
-    lead = 0 for a stream that continues and K/2 for one that is reset): Nb[b] segments, the first one starting at sample off0[b] of the
-    stream, skip[b] samples stripped from its overlap-average; the call runs N = max Nb segments.  Pure Python (profiles and CPU tests use
-    it without a library): the engines' chunk_geometry (csrc/chain_plan.h), which se_chunk_geometry exports and tests/test_chain_plan_cpu.py
-    compares with this, and what train_stages.ragged_geometry gives for the training side."""
-    K = int(segment_length)
-    P = K // 2
-    Nb, off0, skip = [], [], []
-    for L, f in zip(lengths, flags):
-        lead = 0 if f else P
-        Lp = int(L) + lead
-        gap = K - (P + Lp % K) % K
-        Nb.append(2 * (Lp + gap + P) // K)
-        off0.append(-P - lead)
-        skip.append(lead)
-    return dict(Nb=Nb, off0=off0, skip=skip, N=max(Nb) if Nb else 0)
-
-
-def _flags_of(flag, B):
-    """The flag argument of realtime_process: a bool or ONE value (the reference trainer's flag tensor) -> a bool; a sequence or tensor
-    with one value per stream -> a list of B bools (the convention of train_stages._as_flags)."""
-    if hasattr(flag, "reshape") and hasattr(flag, "tolist"):
-        flag = flag.reshape(-1).tolist()
-    if isinstance(flag, (list, tuple)):
-        if len(flag) == 1:
-            return bool(flag[0])
-        if len(flag) != B:
-            raise RuntimeError(f"{len(flag)} flags for a batch of {B}")
-        return [bool(f) for f in flag]
-    return bool(flag)
 
 
 class SlotMap:

@@ -31,8 +31,8 @@ import torch.nn.functional as Fn
 
 from . import train_ops as K
 from .fullsubnet import FullSubNet
-from .train_stages import (_as_flag, _as_flags, _as_lengths, _rows, _sig, ragged_geometry, segment_geometry, stft, stft_rows, synthesis,
-                           synthesis_adjoint, synthesis_adjoint_rows, synthesis_rows)
+from .call_plan import call_plan, overlap_add_cut, windows
+from .train_stages import _sig, stft, synthesis, synthesis_adjoint
 from .training import _TrainableMixin
 
 EPS = 1e-8  # fullsubnet.py:12
@@ -44,86 +44,69 @@ def _x0(spec, N, B, M, T, F):
 
 
 class FSNFunction(torch.autograd.Function):
-    """pred = realtime_process(mixture, flag, train=False)[0] on the kernels.  forward(ctx, model, mixture, flag, *params) with params
-    in state_dict order (what fsn_train_bwd writes).  flag: a bool, or (flags, lengths) - B bools and B ints, host values - of a batch
-    of chunk chains (fsn_train_*_chains)."""
+    """pred = realtime_process(mixture, flag, train=False)[0] on the kernels.  forward(ctx, model, mixture, plan, *params) with params
+    in state_dict order (what fsn_train_bwd writes); plan: the call's CallPlan - uniform: fsn_train_*, chains: fsn_train_*_chains."""
 
     @staticmethod
-    def forward(ctx, model, mixture, flag, *params):
+    def forward(ctx, model, mixture, plan, *params):
+        """Chains: rows are the caller's outside, the engine's inside - a fresh batch is sorted by window count
+        (FsnEngine.train_chain_order), a carried one keeps its slots; mixture is permuted on the way in, pred / crm / x on the way out."""
         K._need_gpu(mixture, params[0])
         eng = model._engine_for(mixture)  # (re)loads the weights when an optimizer step changed them
         mixture = mixture.contiguous().float()
         B, M, L = mixture.shape
-        if not isinstance(flag, tuple) and flag and eng._order is not None and len(eng._order) == B:
-            flag = ((True,) * B, (L,) * B)  # the carried batch was permuted by a chains call: keep the caller's row b on its utterance
+        dev = mixture.device
+        if plan.uniform and plan.flag and eng._order is not None and len(eng._order) == B:
+            plan = model._plan(mixture, [True] * B, uniform=False)  # the carried batch was permuted by a chains call: keep the caller's row b on its utterance
         ctx.shapes = [p.shape for p in params]
-        if isinstance(flag, tuple):
-            return FSNFunction._forward_chains(ctx, model, eng, mixture, list(flag[0]), list(flag[1]))
-        g = model._geometry(mixture, flag)
+        order = idx = None
+        if not plan.uniform:
+            order, idx = eng.train_chain_order(plan.flags, plan.lengths, dev)
+            if order is not None:
+                mixture = mixture.index_select(0, idx)
+                plan = model._plan(mixture, [plan.flags[i] for i in order], [plan.lengths[i] for i in order], uniform=False)
+        flags, lens = plan.flags, plan.lengths
+        g = model._geometry(mixture, plan)
         N, T, F = g["N"], g["T"], g["F"]
-        dev = mixture.device
         S = N * B
-        spec = stft(g["sig"], mixture, B, M, L, g["off0"], g["P"], N, T, F)
-        ws = torch.empty(eng.train_ws_bytes(B, N), dtype=torch.uint8, device=dev)
-        crm = eng.train_fwd(spec, B, N, flag, ws)                                # [N, B, 2, F, T]
-        xm = crm.permute(0, 1, 2, 4, 3).reshape(S, 2, T, F).contiguous()
-        Y = torch.empty(S, T, F, 2, device=dev)
-        K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
-        pred = synthesis(g["sig"], Y, B, g["Ks"], L, g["skip"])
-        model._hip_aux = (crm, _x0(spec, N, B, M, T, F))
-        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g, ctx.chain = eng, ws, spec, xm, g, None
-        return pred
-
-    @staticmethod
-    def _forward_chains(ctx, model, eng, mixture, flags, lens):
-        """Rows are the caller's outside, the engine's inside: a fresh batch is sorted by window count (FsnEngine.train_chain_order), a
-        carried one keeps its slots; mixture is permuted on the way in, pred / crm / x on the way out."""
-        B, M, L = mixture.shape
-        dev = mixture.device
-        order, idx = eng.train_chain_order(flags, lens, dev)
-        if order is not None:
-            mixture = mixture.index_select(0, idx)
-            flags, lens = [flags[i] for i in order], [lens[i] for i in order]
-        g = model._chain_geometry(mixture, flags, lens)
-        N, T, F, rows = g["N"], g["T"], g["F"], g["rows"]
-        S = N * B
-        spec = stft_rows(g["sig"], mixture, B, M, L, rows["off0"], rows["len"], g["P"], N, T, F)
-        ws = torch.empty(eng.train_ws_bytes_chains(B, L, lens, flags), dtype=torch.uint8, device=dev)
-        crm = eng.train_fwd_chains(spec, B, L, lens, flags, ws, N, order, idx)    # [N, B, 2, F, T], zeros in the dead windows
+        spec = stft(plan, g["sig"], mixture, M)
+        if plan.uniform:
+            ws = torch.empty(eng.train_ws_bytes(B, N), dtype=torch.uint8, device=dev)
+            crm = eng.train_fwd(spec, B, N, plan.flag, ws)                                # [N, B, 2, F, T]
+        else:
+            ws = torch.empty(eng.train_ws_bytes_chains(B, L, lens, flags), dtype=torch.uint8, device=dev)
+            crm = eng.train_fwd_chains(spec, B, L, lens, flags, ws, N, order, idx)    # [N, B, 2, F, T], zeros in the dead windows
         # the mask runs over all N * B segments: a dead segment has a zero spectrum (and, in the backward, a zero gradient)
         xm = crm.permute(0, 1, 2, 4, 3).reshape(S, 2, T, F).contiguous()
         Y = torch.empty(S, T, F, 2, device=dev)
         K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
-        pred = synthesis_rows(g["sig"], Y, B, g["Ks"], L, rows["skip"], rows["len"])
+        pred = synthesis(plan, g["sig"], Y)
         x0 = _x0(spec, N, B, M, T, F)
         if idx is not None:
             pred = torch.empty_like(pred).index_copy_(0, idx, pred)
             crm, x0 = torch.empty_like(crm).index_copy_(1, idx, crm), torch.empty_like(x0).index_copy_(1, idx, x0)
         model._hip_aux = (crm, x0)
-        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g, ctx.chain = eng, ws, spec, xm, g, (flags, lens, idx)
+        ctx.eng, ctx.ws, ctx.spec, ctx.xm, ctx.g, ctx.idx = eng, ws, spec, xm, g, idx
         return pred
 
     @staticmethod
     def backward(ctx, dpred):
         g = ctx.g
+        plan = g["plan"]
         B, M, L, N, T, F = g["B"], g["M"], g["L"], g["N"], g["T"], g["F"]
         S, dev = N * B, dpred.device
         dpred = dpred.contiguous().float()
-        if ctx.chain is None:
-            dY = synthesis_adjoint(g["sig"], dpred, B, N, L, g["skip"], g["Ks"], T, F)
-        else:
-            flags, lens, idx = ctx.chain
-            if idx is not None:
-                dpred = dpred.index_select(0, idx)
-            dY = synthesis_adjoint_rows(g["sig"], dpred, B, N, L, g["rows"]["skip"], g["rows"]["len"], g["Ks"], T, F)
+        if ctx.idx is not None:
+            dpred = dpred.index_select(0, ctx.idx)
+        dY = synthesis_adjoint(plan, g["sig"], dpred)
         dx = torch.empty(S, 2, T, F, device=dev)
         K._chk(K._lib().se_train_mask_bwd(dY.data_ptr(), ctx.xm.data_ptr(), ctx.spec.data_ptr(), dx.data_ptr(), S, M, T, F, g["n_fft"], K._st()))
         dcrm = dx.view(N, B, 2, T, F).permute(0, 1, 2, 4, 3).contiguous()
         grads = [torch.empty(s, device=dev) for s in ctx.shapes]
-        if ctx.chain is None:
+        if plan.uniform:
             ctx.eng.train_bwd(dcrm, B, N, ctx.ws, grads)
         else:
-            ctx.eng.train_bwd_chains(dcrm, B, L, lens, flags, ctx.ws, grads)
+            ctx.eng.train_bwd_chains(dcrm, B, L, plan.lengths, plan.flags, ctx.ws, grads)
         ctx.ws = ctx.spec = ctx.xm = None
         return (None, None, None, *grads)
 
@@ -148,22 +131,15 @@ class TrainableFullSubNet(FullSubNet):
         self._tstate = None
         return self
 
-    def _geometry(self, mixture, flag=None):
-        B, M, L = mixture.shape
-        n_fft, Ks = self._args["n_fft"], self.segment_length
-        g = segment_geometry(L, self._cur_flag if flag is None else flag, Ks, self._hop, n_fft)
-        g.update(B=B, M=M, n_fft=n_fft, F=self.num_freqs, sig=_sig(mixture.device, n_fft, self._win, self._hop, Ks))
-        return g
+    def _plan(self, x, flag=False, lengths=None, uniform=None):
+        """the CallPlan of realtime_process(x [B, C, L], flag, lengths); uniform=False: the chains form whatever the triage says"""
+        return call_plan(flag, lengths, x.shape[0], x.shape[-1], self.segment_length, self._hop, self._nfft, uniform=uniform)
 
-    def _chain_geometry(self, mixture, flags, lens):
-        """_geometry of a batch of chunk chains: per-utterance Nb / off0 / skip as host lists, and as device int64 rows for the row kernels"""
+    def _geometry(self, mixture, plan):
+        """the plan's geometry and the model's own sizes"""
         B, M, L = mixture.shape
-        n_fft, Ks = self._args["n_fft"], self.segment_length
-        g = ragged_geometry(lens, flags, Ks, self._hop, n_fft)
-        dev = mixture.device
-        g.update(B=B, M=M, L=L, n_fft=n_fft, F=self.num_freqs, sig=_sig(dev, n_fft, self._win, self._hop, Ks),
-                 rows=dict(off0=_rows(g["off0"], dev), len=_rows(g["lengths"], dev), skip=_rows(g["skip"], dev)))
-        return g
+        return dict(plan.geo, plan=plan, B=B, M=M, L=L, n_fft=self._nfft, F=self.num_freqs,
+                    sig=_sig(mixture.device, self._nfft, self._win, self._hop, self.segment_length))
 
     def realtime_process(self, mixture, source=None, flag=False, train=False, lengths=None):
         """flag: a bool or ONE value for the batch, or one value per utterance; lengths (optional): B ints <= Lmax, host values or a
@@ -172,53 +148,37 @@ class TrainableFullSubNet(FullSubNet):
             if lengths is not None:
                 raise NotImplementedError("train=True takes one flag and one length for the whole batch")
             return super().realtime_process(mixture, source, flag, True)
-        B, _, Lmax = mixture.shape
-        chain = None
-        if lengths is not None or (isinstance(flag, (list, tuple)) and len(flag) > 1) or (isinstance(flag, torch.Tensor) and flag.numel() > 1):
-            flags, lens = _as_flags(flag, B), _as_lengths(lengths, B, Lmax)
-            if len(set(flags)) == 1 and min(lens) == Lmax:
-                flag = flags[0]   # a uniform batch IS the scalar call
-            else:
-                chain = (tuple(flags), tuple(lens))
-        else:
-            flag = _as_flag(flag[0] if isinstance(flag, (list, tuple)) else flag)
+        plan = self._plan(mixture, flag, lengths)
         if not torch.is_grad_enabled() and mixture.is_cuda:
-            if chain is None:
-                return super().realtime_process(mixture, source, flag, False)
-            return super().realtime_process(mixture, source, list(chain[0]), False, lengths=list(chain[1]))
-        self._cur_flag = flag
+            if plan.uniform:
+                return super().realtime_process(mixture, source, plan.flag, False)
+            return super().realtime_process(mixture, source, plan.flags, False, lengths=plan.lengths)
         if self._hip:
-            pred, crm, x = self._hip_forward(mixture, flag if chain is None else chain)
-            s = None if source is None else self._mic0_spec(source, flag if chain is None else chain)
-        elif chain is None:
-            pred, crm, x, s = self._torch_forward(mixture, source, flag)
+            pred, crm, x = self._hip_forward(mixture, plan)
+            s = None if source is None else self._mic0_spec(source, plan)
+        elif plan.uniform:
+            pred, crm, x, s = self._torch_forward(mixture, source, plan)
         else:
-            pred, crm, x, s = self._torch_forward_chains(mixture, source, list(chain[0]), list(chain[1]))
+            pred, crm, x, s = self._torch_forward_chains(mixture, source, plan)
         if source is None:
             return pred
         return pred, crm.detach(), s.detach(), x.detach()
 
     # ---- kernels ----
-    def _hip_forward(self, mixture, flag):
+    def _hip_forward(self, mixture, plan):
         params = list(self.parameters())
-        pred = FSNFunction.apply(self, mixture, flag, *params)
+        pred = FSNFunction.apply(self, mixture, plan, *params)
         crm, x0 = self._hip_aux
         self._hip_aux = None
         return pred, crm, x0
 
-    def _mic0_spec(self, source, flag):
-        """mic 0 of the source's windows [N, B, 2, F, T]; flag: a bool, or (flags, lengths): per-row offsets, zero beyond each length"""
+    def _mic0_spec(self, source, plan):
+        """mic 0 of the source's windows [N, B, 2, F, T], by the mixture's plan: per-row offsets, zero beyond each length"""
         src = source[:, :1].contiguous().float()
-        if isinstance(flag, tuple):
-            g = self._chain_geometry(src, list(flag[0]), list(flag[1]))
-            sspec = stft_rows(g["sig"], src, g["B"], 1, g["L"], g["rows"]["off0"], g["rows"]["len"], g["P"], g["N"], g["T"], g["F"])
-        else:
-            g = self._geometry(src, flag)
-            sspec = stft(g["sig"], src, g["B"], 1, g["L"], g["off0"], g["P"], g["N"], g["T"], g["F"])   # [N, B, T, F, 2]
+        sspec = stft(plan, _sig(src.device, self._nfft, self._win, self._hop, self.segment_length), src, 1)   # [N, B, T, F, 2]
         return sspec.permute(0, 1, 4, 3, 2).contiguous()
 
     # ---- torch restatement (the checker) ----
-    _segment = _TrainableMixin._segment
     _stft = _TrainableMixin._stft
     _istft = _TrainableMixin._istft
 
@@ -281,40 +241,32 @@ class TrainableFullSubNet(FullSubNet):
         m = Fn.linear(sb_h, self.sb_model.fc_output_layer.weight, self.sb_model.fc_output_layer.bias)  # [B*F, T, 2]
         return m.reshape(B, F, T, 2).permute(0, 3, 1, 2)
 
-    def _torch_forward(self, mixture, source, flag):
-        K_ = self.segment_length
-        P = K_ // 2
-        M = mixture.shape[1]
-        if not flag:
-            mixture = Fn.pad(mixture, (P, 0))
-            self._tstate = {}
-        elif self._tstate is None:
-            raise RuntimeError("flag=True continues a previous chunk of this path: start with flag=False")
-        seg, gap = self._segment(mixture)   # [B, M, N, K]
-        X = self._stft(seg)                 # [B, M, N, F, T]
-        st = self._tstate
-        crms = [self._torch_window(X[:, :, n], st) for n in range(X.shape[2])]
-        crm = torch.stack(crms, dim=0)      # [N, B, 2, F, T]
-        m = 9.9 * (crm >= 9.9) - 9.9 * (crm <= -9.9) + crm * (crm.abs() < 9.9)  # decompress_cIRM, utility.py:439-442
+    def _torch_outputs(self, plan, X, crm, source):
+        """What both restatement loops end with: crm [N, B, 2, F, T] over the windows' spectra X [B, M, N, F, T] -> decompress_cIRM
+        (utility.py:439-442), complex multiply with mic 0, iSTFT, overlap-add.  -> (pred, crm, x0, s0: mic 0 of mixture / source)"""
+        m = 9.9 * (crm >= 9.9) - 9.9 * (crm <= -9.9) + crm * (crm.abs() < 9.9)
         m = -10.0 * torch.log((10.0 - m) / (10.0 + m))
         X0 = X[:, 0].transpose(0, 1)        # [N, B, F, T]
         re, im = X0.real, X0.imag
         Y = torch.complex(m[:, :, 0] * re - m[:, :, 1] * im, m[:, :, 1] * re + m[:, :, 0] * im)
-        y = self._istft(Y).transpose(0, 1)  # [B, N, K]
-        B = y.shape[0]
-        s1 = y[:, 0::2].reshape(B, -1)[:, P:]
-        s2 = y[:, 1::2].reshape(B, -1)[:, :-P]
-        out = (s1 + s2) / 2
-        if gap > 0:
-            out = out[:, :-gap]
-        pred = out if flag else out[:, P:]
-        x0 = torch.stack([re, im], dim=2)
+        pred = overlap_add_cut(plan, self._istft(Y).transpose(0, 1))  # [B, N, K] -> [B, L]
         s0 = None
         if source is not None:
-            src = source if flag else Fn.pad(source, (P, 0))
-            S0 = self._stft(self._segment(src[:, :1])[0])[:, 0].transpose(0, 1)
+            S0 = self._stft(windows(plan, source[:, :1]))[:, 0].transpose(0, 1)
             s0 = torch.stack([S0.real, S0.imag], dim=2)
-        return pred, crm, x0, s0
+        return pred, crm, torch.stack([re, im], dim=2), s0
+
+    def _torch_forward(self, mixture, source, plan):
+        """The uniform call: one state for the batch, the CumLayerNorm step counters Python ints (_torch_forward_chains keeps them as
+        float32 tensors per utterance, which rounds the running-mean ratio differently: the two loops stay apart)."""
+        if not plan.flag:
+            self._tstate = {}
+        elif self._tstate is None:
+            raise RuntimeError("flag=True continues a previous chunk of this path: start with flag=False")
+        X = self._stft(windows(plan, mixture))   # [B, M, N, F, T]
+        st = self._tstate
+        crm = torch.stack([self._torch_window(X[:, :, n], st) for n in range(plan.N)], dim=0)   # [N, B, 2, F, T]
+        return self._torch_outputs(plan, X, crm, source)
 
     # ---- torch restatement of a batch of chunk chains ----
     _STATE_KEYS = ("mean_fb", "mean_fb_step", "mean_sb", "mean_sb_step", "fh", "sh")
@@ -344,17 +296,13 @@ class TrainableFullSubNet(FullSubNet):
                 out[key] = torch.where(mask.view(-1, 1, 1, 1), a[key], b[key])
         return out
 
-    def _torch_forward_chains(self, mixture, source, flags, lens):
+    def _torch_forward_chains(self, mixture, source, plan):
         """B independent chunk chains in one call.  Every statistic of the model is per utterance and window positions do not depend on
         the length, so all utterances run the N = max N_b windows of the longest; state, means and counters are kept per utterance and
         an utterance's carried state is taken after its OWN last window, its output cut from its own samples."""
-        B, M, Lmax = mixture.shape
-        K_ = self.segment_length
-        P = K_ // 2
-        q = ragged_geometry(lens, flags, K_, self._hop, self._nfft)
-        N, dev = q["N"], mixture.device
+        B, N, dev = plan.B, plan.N, mixture.device
         carried = None
-        if any(flags):
+        if plan.any_flag:
             if self._tstate is None or "fh" not in self._tstate:
                 raise RuntimeError("flag=True continues a previous chunk of this path: start with flag=False")
             if self._tstate["fh"][0][0].shape[0] != B:
@@ -363,35 +311,16 @@ class TrainableFullSubNet(FullSubNet):
         self._tstate = None
         state = self._chain_state(B, mixture)   # after a reset
         if carried is not None:
-            state = self._merge_state(torch.tensor(flags, device=dev), carried, state)
-
-        def windows(x):   # [B, C, Lmax] -> the N windows of every utterance's own samples [B, C, N, F, T]
-            xp = torch.cat([Fn.pad(x[b:b + 1, :, :lens[b]], (-q["off0"][b], (N + 1) * P + q["off0"][b] - lens[b])) for b in range(B)])
-            idx = (torch.arange(N, device=dev) * P)[:, None] + torch.arange(K_, device=dev)[None, :]
-            return self._stft(xp[:, :, idx])
-
-        X = windows(mixture)
-        Nb = torch.tensor(q["Nb"], device=dev)
+            state = self._merge_state(torch.tensor(plan.flags, device=dev), carried, state)
+        X = self._stft(windows(plan, mixture))   # the N windows of every utterance's own samples [B, M, N, F, T]
+        Nb = torch.tensor(plan.Nb, device=dev)
         final, crms = state, []
         for n in range(N):
             state = dict(state)
             crms.append(self._torch_window(X[:, :, n], state))
-            if n + 1 in q["Nb"]:
+            if n + 1 in plan.Nb:
                 final = self._merge_state(Nb == n + 1, state, final)
         self._tstate = final
         live = (torch.arange(N, device=dev)[:, None] < Nb[None, :]).to(mixture.dtype).view(N, B, 1, 1, 1)
         crm = torch.stack(crms, dim=0) * live   # [N, B, 2, F, T]: exact zeros past every utterance's own last window
-        m = 9.9 * (crm >= 9.9) - 9.9 * (crm <= -9.9) + crm * (crm.abs() < 9.9)  # decompress_cIRM, utility.py:439-442
-        m = -10.0 * torch.log((10.0 - m) / (10.0 + m))
-        X0 = X[:, 0].transpose(0, 1)        # [N, B, F, T]
-        re, im = X0.real, X0.imag
-        Y = torch.complex(m[:, :, 0] * re - m[:, :, 1] * im, m[:, :, 1] * re + m[:, :, 0] * im)
-        y = self._istft(Y).transpose(0, 1)  # [B, N, K]
-        full = (y[:, 0::2].reshape(B, -1)[:, P:] + y[:, 1::2].reshape(B, -1)[:, :-P]) / 2
-        pred = torch.stack([Fn.pad(full[b, q["skip"][b]:q["skip"][b] + lens[b]], (0, Lmax - lens[b])) for b in range(B)])
-        x0 = torch.stack([re, im], dim=2)
-        s0 = None
-        if source is not None:
-            S0 = windows(source[:, :1])[:, 0].transpose(0, 1)
-            s0 = torch.stack([S0.real, S0.imag], dim=2)
-        return pred, crm, x0, s0
+        return self._torch_outputs(plan, X, crm, source)

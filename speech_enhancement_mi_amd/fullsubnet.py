@@ -101,7 +101,8 @@ class FullSubNet(nn.Module):
     def _realtime_single_pass(self, mixture, source, flag):
         """train=True (fullsubnet.py:921-927): xf = all N windows' frames side by side [B, 2M, F, N*T] -> ONE forward."""
         from . import train_ops as K
-        from .train_stages import _sig, segment_geometry, stft, synthesis
+        from .call_plan import call_plan
+        from .train_stages import _sig, stft, synthesis
         if flag:
             raise NotImplementedError("train=True continues a previous chunk only in the reference's autograd loop; the engine path takes flag=False")
         if source is None:
@@ -113,12 +114,12 @@ class FullSubNet(nn.Module):
         B, M, L = mixture.shape
         hop = int(round(a["sample_rate"] / 1000.0 * a["hop_length"]))
         win = int(round(a["sample_rate"] / 1000.0 * a["win_length"]))
-        g = segment_geometry(L, False, self.segment_length, hop, a["n_fft"])
-        Ks, P, N, T, F = g["Ks"], g["P"], g["N"], g["T"], self.num_freqs
+        g = call_plan(False, None, B, L, self.segment_length, hop, a["n_fft"])
+        Ks, N, T, F = g.Ks, g.N, g.T, self.num_freqs
         S = N * B
         sig = _sig(dev, a["n_fft"], win, hop, Ks)
-        spec = stft(sig, mixture, B, M, L, g["off0"], P, N, T, F)
-        sspec = stft(sig, source, B, source.shape[1], L, g["off0"], P, N, T, F)
+        spec = stft(g, sig, mixture, M)
+        sspec = stft(g, sig, source, source.shape[1])
         xf = spec.view(N, B, M, T, F, 2).permute(1, 5, 2, 4, 0, 3).reshape(B, 2 * M, F, N * T).contiguous()
         long = self._long.get(N * T)
         if long is None:
@@ -134,7 +135,7 @@ class FullSubNet(nn.Module):
         xm = pred_crm.permute(0, 1, 2, 4, 3).reshape(S, 2, T, F).contiguous()
         Y = torch.empty(S, T, F, 2, device=dev)
         K._chk(K._lib().se_train_mask_fwd(xm.data_ptr(), spec.data_ptr(), Y.data_ptr(), S, M, T, F, K._st()))
-        pred = synthesis(sig, Y, B, Ks, L, g["skip"])
+        pred = synthesis(g, sig, Y)
         x0 = spec.view(N, B, M, T, F, 2)[:, :, 0].permute(0, 1, 4, 3, 2).contiguous()    # [N, B, 2, F, T]
         s0 = sspec.view(N, B, -1, T, F, 2)[:, :, 0].permute(0, 1, 4, 3, 2).contiguous()
         return pred, pred_crm, s0, x0

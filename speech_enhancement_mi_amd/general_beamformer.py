@@ -21,16 +21,15 @@ Two interchangeable paths:
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .train_stages import (_as_flags, _as_lengths, _cs, _new, _p, _rows, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd,
-                           encoder_block_fwd, gemm_tn, grads_in_parameter_order, gru_layer_bwd, input_features, istft, overlap_add,
-                           ragged_geometry, segment_geometry, slab_gather, stft, stft_rows, synthesis_adjoint, synthesis_adjoint_rows)
+from .call_plan import call_plan, overlap_add_cut, segment_geometry, windows
+from .train_stages import (_cs, _new, _p, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd, encoder_block_fwd, gemm_tn,
+                           grads_in_parameter_order, gru_layer_bwd, gru_steps, gru_steps_bwd, input_features, istft, overlap_add, own_last_slab,
+                           start_rows, stft, synthesis_adjoint)
 
 EPS = 1e-8
 _DEFAULT_MAX_SEGMENTS = 8
@@ -179,33 +178,26 @@ class GeneralBeamformer(nn.Module):
         flag[b] is False and continues row b of the carried state where it is True; pred[b, lengths[b]:] = 0, and the carried state
         afterwards holds, per utterance, what that utterance alone would carry.  A batch whose flags and lengths are all alike takes the
         uniform code path, as a bool flag does."""
-        B, _, Lmax = mixture.shape
-        chains = None
-        if lengths is not None or isinstance(flag, (torch.Tensor, list, tuple)):
-            flags, lens = _as_flags(flag, B), _as_lengths(lengths, B, Lmax)
-            if len(set(flags)) == 1 and min(lens) == Lmax:
-                flag = flags[0]
-            else:
-                chains, flag = (tuple(flags), tuple(lens)), any(flags)
-        else:
-            flag = bool(flag)
+        B, M, Lmax = mixture.shape
+        c = self._cfg
+        plan = call_plan(flag, lengths, B, Lmax, self.segment_length, self._hop, c["n_fft"], [2 * M - 1] + c["num_channels"])
         grad = torch.is_grad_enabled()
         train = self._hip_train and mixture.is_cuda and grad
         path = "kernel" if train or (self._hip and mixture.is_cuda and not grad) else "torch"
-        if flag and self._last_path not in (None, path):
+        if plan.any_flag and self._last_path not in (None, path):
             raise RuntimeError("flag=True continues the state of the other path (kernels vs restatement): start with flag=False")
         if train:
             err = self.hip_training_error()
             if err:
                 raise ValueError(f"GeneralBeamformer HIP training: {err}")
             params = [p for _, p in self.named_parameters()]
-            out = GBFFunction.apply(self, mixture, chains or flag, *params)
+            out = GBFFunction.apply(self, mixture, plan, *params)
             self._last_path = path
             return out
         self._last_path = path
         if path == "kernel":
-            return self._kernel_process(mixture, chains or flag)
-        return self._torch_chains(mixture, *chains) if chains else self._torch_process(mixture, flag)
+            return self._kernel_process(mixture, plan)
+        return self._torch_process(mixture, plan.flag) if plan.uniform else self._torch_chains(mixture, plan.flags, plan.lengths)
 
     # ---- torch restatement ---------------------------------------------------------------------------------------------------
     def _segment(self, x, st):
@@ -292,30 +284,16 @@ class GeneralBeamformer(nn.Module):
 
     def _torch_process(self, mixture, flag):
         B, M, L = mixture.shape
-        Ks = self.segment_length
-        P = Ks // 2
         if not flag:
-            mixture = Fn.pad(mixture, (P, 0))
             self._tstate = None
-        geo = segment_geometry(L, flag, Ks, self._hop, self._cfg["n_fft"])
-        gap, N = geo["gap"], geo["N"]
-        xp = Fn.pad(mixture, (P, gap + P))
-        idx = (torch.arange(N, device=mixture.device) * P)[:, None] + torch.arange(Ks, device=mixture.device)[None, :]
-        seg = xp[:, :, idx]  # [B, M, N, K]
-        win = torch.hamming_window(self._win, device=mixture.device, dtype=mixture.dtype)
         n_fft = self._cfg["n_fft"]
-        X = self.spectrum(seg)
-        outs = []
-        for n in range(N):
-            outs.append(self.forward(X[:, :, n]))
-        Y = torch.view_as_complex(torch.stack(outs, dim=1).reshape(B * N, *outs[0].shape[1:]).contiguous())
-        y = torch.istft(Y, n_fft, self._hop, self._win, win, center=True, normalized=False, onesided=True).reshape(B, N, -1)
-        s1 = y[:, 0::2].reshape(B, -1)[:, P:]
-        s2 = y[:, 1::2].reshape(B, -1)[:, :-P]
-        out = (s1 + s2) / 2
-        if gap > 0:
-            out = out[:, :-gap]
-        return out if flag else out[:, P:]
+        plan = call_plan(flag, None, B, L, self.segment_length, self._hop, n_fft)
+        X = self.spectrum(windows(plan, mixture))
+        outs = [self.forward(X[:, :, n]) for n in range(plan.N)]
+        win = torch.hamming_window(self._win, device=mixture.device, dtype=mixture.dtype)
+        Y = torch.view_as_complex(torch.stack(outs, dim=1).reshape(B * plan.N, *outs[0].shape[1:]).contiguous())
+        y = torch.istft(Y, n_fft, self._hop, self._win, win, center=True, normalized=False, onesided=True).reshape(B, plan.N, -1)
+        return overlap_add_cut(plan, y)
 
     def _torch_chains(self, mixture, flags, lens):
         """A batch of chunk chains on the restatement (the oracle of the kernel paths): every utterance alone on its own rows of the
@@ -385,37 +363,24 @@ class GeneralBeamformer(nn.Module):
             return "dropout is active in training mode: the training kernels have no dropout (use the restatement, or dropout = 0)"
         return None
 
-    def _kernel_setup(self, mixture, flag):
-        """Geometry of one realtime_process call on the kernels and the state it starts from (the carried one for flag=True).  flag: a
-        bool, or (flags, lengths) of a batch of chunk chains - then every utterance keeps the geometry it would have alone
-        (train_stages.ragged_geometry), g["rows"] holds what the row kernels index by utterance, and the start state is row b of the
-        carried one where flags[b], zeros elsewhere."""
+    def _kernel_setup(self, mixture, plan):
+        """The sizes of one realtime_process call on the kernels (the plan's geometry and the model's own) and the state it starts from:
+        zeros, or the carried one - row b of it where flags[b], zeros elsewhere, for a batch of chunk chains."""
         dev = mixture.device
         B, M, L = mixture.shape
         c = self._cfg
-        H, NL, ch = c["hidden"], c["num_layers"], [2 * M - 1] + c["num_channels"]
-        chains = flag if isinstance(flag, tuple) else None
-        if chains:
-            g = ragged_geometry(chains[1], chains[0], self.segment_length, self._hop, c["n_fft"], ch)
-            g["L"], flag = L, any(chains[0])
-            g["rows"] = dict(len=_rows(g["lengths"], dev), skip=_rows(g["skip"], dev))
-        else:
-            g = segment_geometry(L, flag, self.segment_length, self._hop, c["n_fft"], ch)
-        T, F0, Fq, Lv = g["T"], g["F0"], g["Fq"], len(self.convlist)
-        g.update(B=B, M=M, n_fft=c["n_fft"], H=H, NL=NL, Lv=Lv, BF=B * F0, sig=_sig(dev, c["n_fft"], self._win, self._hop, self.segment_length))
-        state = self._kstate if flag else None
-        if chains and flag and state is None:
+        H, NL = c["hidden"], c["num_layers"]
+        T, F0, ch, Fq, Lv = plan.T, plan.F0, plan.ch, plan.Fq, len(self.convlist)
+        g = dict(plan.geo, plan=plan, L=L, B=B, M=M, n_fft=c["n_fft"], H=H, NL=NL, Lv=Lv, BF=B * F0,
+                 sig=_sig(dev, c["n_fft"], self._win, self._hop, self.segment_length))
+        state = self._kstate if plan.any_flag else None
+        if not plan.uniform and plan.any_flag and state is None:
             raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is none")
         if state is not None and state["B"] != B:
             raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
-        if chains and state is not None:   # mixed flags: the carried row where flags[b], zeros where utterance b starts afresh
-            carry = _rows([0 if f else -1 for f in chains[0]], dev)
-
-            def start(t, X):
-                return slab_gather(t, carry, B, X, B * X, X).view(t.shape)
-
-            state = dict(B=B, buf=[start(t, t[0].numel()) for t in state["buf"]], h=[[start(t, F0 * H) for t in hq] for hq in state["h"]])
-        if state is None:
+        if state is not None:
+            state = dict(B=B, buf=[start_rows(plan, t) for t in state["buf"]], h=[[start_rows(plan, t) for t in hq] for hq in state["h"]])
+        else:
             state = dict(B=B, buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
                          h=[[torch.zeros(B * F0, H, device=dev) for _ in range(NL)] for _ in range(2)])
         return g, state
@@ -429,14 +394,10 @@ class GeneralBeamformer(nn.Module):
         B, M, L, T, F0, H, NL, Lv, ch, Fq, BF, P = (g[k] for k in ("B", "M", "L", "T", "F0", "H", "NL", "Lv", "ch", "Fq", "BF", "P"))
         S = Nc * B
         keep = sv is not None
-        chain = g.get("rows")
-        if chain:   # chunk chains: utterance b has live[b] of this pass's Nc segments; its GRU streams run live[b] * T steps
-            live = [min(max(nb - n0, 0), Nc) for nb in g["Nb"]]
-            steps = torch.tensor(live, dtype=torch.int32).mul_(T).repeat_interleave(F0).to(dev, non_blocking=True)
-            spec = stft_rows(g["sig"], mixture, B, M, L, _rows([o + n0 * P for o in g["off0"]], dev), chain["len"], P, Nc, T, F0)
-        else:
-            steps = None
-            spec = stft(g["sig"], mixture, B, M, L, g["off0"] + n0 * P, P, Nc, T, F0)
+        plan = g["plan"]
+        # chunk chains: utterance b has live[b] of this pass's Nc segments; its GRU streams run live[b] * T steps
+        steps, live = gru_steps(plan, dev, T, F0, n0, Nc)
+        spec = stft(plan, g["sig"], mixture, M, n0, Nc)
         # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input of block i (its time history)
         xin = []
         for i in range(Lv):
@@ -494,12 +455,8 @@ class GeneralBeamformer(nn.Module):
         _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
              _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
         istft(g["sig"], Y, yseg.view(-1, g["Ks"]), n0 * B)
-        if chain:   # every utterance's own last live segment of the pass; slab 0 (its previous rows) where it has none
-            last = _rows(live, dev)
-            state["buf"] = [slab_gather(xin[i], last, B, xin[i][0][0].numel(), xin[i][0].numel(), xin[i][0][0].numel()).view(xin[i].shape[1:])
-                            for i in range(Lv)]
-        else:
-            state["buf"] = [xin[i][Nc].clone() for i in range(Lv)]
+        # every utterance's own last live segment of the pass; slab 0 (its previous rows) where it has none
+        state["buf"] = [own_last_slab(plan, xin[i], live, copy=True) for i in range(Lv)]
         if keep:
             sv.update(spec=spec, xin=xin, ys=ys, stats_e=stats_e, dec=dec, xl=xl, rows=rows, outs=outs, gates=gates, h0s=h0s, phi=phi)
 
@@ -509,41 +466,36 @@ class GeneralBeamformer(nn.Module):
             raise RuntimeError(f"persistent GRU kernel timed out waiting for its peer workgroups ({g['BF']} streams, hidden {g['H']}): "
                                "output invalid")
 
-    def _kernel_run(self, mixture, flag, sv=None):
+    def _kernel_run(self, mixture, plan, sv=None):
         """Passes of max_segments segments; sv given (GBFFunction): ONE pass that keeps its activations.  -> (pred, geometry, time-outs)"""
-        g, state = self._kernel_setup(mixture, flag)
+        g, state = self._kernel_setup(mixture, plan)
         N, B = g["N"], g["B"]
         yseg = _new(N, B, g["Ks"], dev=mixture.device)
         tmo = []
         step = N if sv is not None else max(1, int(self.max_segments))
         for n0 in range(0, N, step):
             self._kernel_pass(mixture, g, state, n0, min(step, N - n0), yseg, tmo, sv)
-        if "rows" in g:
-            pred = _new(B, g["L"], dev=mixture.device)
-            _run("k_tola", 0.0, K._lib().se_train_ola_fwd_rows, g["sig"], _p(yseg), _p(pred), B, g["L"], C.c_void_p(g["rows"]["skip"].data_ptr()),
-                 C.c_void_p(g["rows"]["len"].data_ptr()), K._st())
-        else:
-            pred = overlap_add(g["sig"], yseg, B, g["L"], g["skip"])
+        pred = overlap_add(plan, g["sig"], yseg)
         self._kstate = state
         return pred, g, tmo
 
     @torch.no_grad()
-    def _kernel_process(self, mixture, flag):
+    def _kernel_process(self, mixture, plan):
         err = self.kernel_geometry_error()
         if err:
             raise ValueError(f"GeneralBeamformer kernel path: {err}")
         if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist)):
             raise ValueError("GeneralBeamformer kernel path: inference only (dropout is active in training mode; use the restatement)")
         K._need_gpu(mixture, self.ln_S.weight)
-        pred, g, tmo = self._kernel_run(mixture.contiguous().float(), flag)
+        pred, g, tmo = self._kernel_run(mixture.contiguous().float(), plan)
         self._check_timeouts(tmo, g)
         return pred
 
 
 class GBFFunction(torch.autograd.Function):
     """pred = GeneralBeamformer.realtime_process(mixture, flag) on the kernels, forward AND backward, as one autograd node
-    (reference training step train.py:195-204).  forward(ctx, model, mixture, flag, *params), params in named_parameters() order;
-    flag: a bool, or (flags, lengths) of a batch of chunk chains (_kernel_setup).
+    (reference training step train.py:195-204).  forward(ctx, model, mixture, plan, *params), params in named_parameters() order;
+    plan: the call's CallPlan (realtime_process builds it).
 
     Forward: the inference kernel path over all N segments of the call in one pass, keeping the GRU gates, layer outputs and U-Net
     activations.  Backward: OLA / iSTFT adjoint, se_gbf_bf_bwd, se_gbf_seq_bwd, the GRU layers (train_stages.gru_layer_bwd),
@@ -552,10 +504,10 @@ class GBFFunction(torch.autograd.Function):
     float atomics: the gradients are bit-reproducible."""
 
     @staticmethod
-    def forward(ctx, model, mixture, flag, *params):
+    def forward(ctx, model, mixture, plan, *params):
         K._need_gpu(mixture, model.ln_S.weight)
         sv = {}
-        pred, g, tmo = model._kernel_run(mixture.detach().contiguous().float(), flag, sv)
+        pred, g, tmo = model._kernel_run(mixture.detach().contiguous().float(), plan, sv)
         g["S"] = g["N"] * g["B"]
         ctx.model, ctx.dims, ctx.sv, ctx.tmo = model, g, sv, tmo
         return pred
@@ -572,14 +524,8 @@ class GBFFunction(torch.autograd.Function):
         grads = {}
         zero_bias = torch.zeros(256, device=dev)
 
-        chain = q.get("rows")
-        if chain:   # chunk chains: dpred[b, lengths[b]:] is never read; a sequence of the GRU sweep is one (stream, segment) pair
-            dY = synthesis_adjoint_rows(sig, dpred, B, N, q["L"], chain["skip"], chain["len"], Ks, T, F0)
-            steps = (torch.arange(N)[None, :] < torch.tensor(q["Nb"])[:, None]).to(torch.int32).mul_(T).repeat_interleave(F0, dim=0)
-            steps = steps.reshape(-1).to(dev, non_blocking=True)
-        else:
-            dY = synthesis_adjoint(sig, dpred, B, N, q["L"], q["skip"], Ks, T, F0)
-            steps = None
+        dY = synthesis_adjoint(q["plan"], sig, dpred)
+        steps = gru_steps_bwd(q["plan"], dev, T, F0)   # chunk chains: a sequence of the GRU sweep is one (stream, segment) pair
         # beamformer + linear head
         FT = F0 * T
         R1 = S * FT

@@ -22,8 +22,8 @@ import torch
 from . import train_ops as K
 from .train_stages import (_cs, _new, _p, _run, _sig, colsum3, colsum_tall, conv_w, decoder_bwd, decoder_fwd,
                            encoder_block_bwd, encoder_block_fwd, encoder_conv_bwd, gemm_tn, gln_bwd, gln_fwd, grads_in_parameter_order,
-                           gru_layer_bwd, input_features, ragged_geometry, segment_geometry, slab_gather, stft, stft_rows, synthesis,
-                           synthesis_adjoint, synthesis_adjoint_rows, synthesis_rows, transpose, wgrad, _as_flags, _as_lengths, _rows)
+                           gru_layer_bwd, input_features, own_last_slab, row_table, slab_gather, start_rows, stft, synthesis, synthesis_adjoint,
+                           transpose, wgrad, call_plan)
 
 _side_streams = {}
 PIPELINE_LAYERS = True   # training forward: GRU layers as a wavefront over segments on one HIP stream per layer (False: layer after layer)
@@ -39,11 +39,8 @@ def _side_stream(dev, idx):
 def _first_slab(t, state, key, idx, q):   # slab 0 = the carried state of a flag=True continuation, zeros after a reset
     if state is None or state.get(key) is None:
         t[0].zero_()
-    elif "rows" not in q:
-        t[0].copy_(state[key][idx])
-    else:   # chunk chains: row b of the carried batch where flags[b], zeros where utterance b starts afresh
-        X = t[0][0].numel()
-        slab_gather(state[key][idx], q["rows"]["carry"], q["B"], X, q["B"] * X, X, dst=t[0])
+    else:   # ... chunk chains: per utterance
+        start_rows(q["plan"], state[key][idx], dst=t[0])
 
 
 def _inject(dpre, gf, S, Cc, X):   # dpre += d feature map; -> the bias gradient (per-channel sums of the result)
@@ -86,25 +83,24 @@ def gate_pair_bwd(dy_ptr, ds, a_t, tg, stt, blk, pre, grads, zero_bias, S, Co, T
 
 
 # ---- the stages of CRNFunction: q = the call's dimensions, sv = what the forward saves for the backward ---------------------------
-def _dims(model, mixture, flag):
-    """flag: a bool, or (flags, lengths) of a batch of chunk chains - B bools and B ints, host values"""
+def _plan(model, mixture, flag=False, lengths=None, uniform=None):
+    """the CallPlan of realtime_process(mixture, flag, lengths) on this model: the U-Net level sizes come with it.  uniform=False: the
+    chains form (the `_rows` kernels) whatever the triage says"""
     B, M, L = mixture.shape
-    n_fft = model._cfg_args["n_fft"]
     ch = [2 * M - 1] + [blk.conv.weight.shape[0] for blk in model.convlist]
-    if isinstance(flag, tuple):
-        q = ragged_geometry(flag[1], flag[0], model.segment_length, model._hop, n_fft, ch)
-        if len(q["flags"]) != B or q["L"] > L:
-            raise ValueError(f"flags / lengths {flag} do not describe a batch of {B} utterances of up to {L} samples")
-        q["L"] = L
-        dev = mixture.device   # everything the row kernels index by utterance, one small copy each, no host synchronisation
-        q["rows"] = dict(off0=_rows(q["off0"], dev), len=_rows(q["lengths"], dev), skip=_rows(q["skip"], dev), last=_rows(q["Nb"], dev),
-                         lastseg=_rows([n - 1 for n in q["Nb"]], dev), carry=_rows([0 if f else -1 for f in q["flags"]], dev))
-    else:
-        q = segment_geometry(L, flag, model.segment_length, model._hop, n_fft, ch)
+    return call_plan(flag, lengths, B, L, model.segment_length, model._hop, model._cfg_args["n_fft"], ch, uniform)
+
+
+def _dims(model, mixture, plan):
+    """q = the plan's geometry and the model's own sizes"""
+    B, M, L = mixture.shape
+    if plan.B != B or plan.L != L:
+        raise ValueError(f"the call plan describes a batch of {plan.B} utterances of up to {plan.L} samples, not {B} of {L}")
     g = model.gru.sequence_model
     Lv = len(model.convlist)
-    CL, FL = q["ch"][Lv], q["Fq"][Lv]
-    q.update(B=B, M=M, S=q["N"] * B, Lv=Lv, H=g.hidden_size, NL=g.num_layers, CL=CL, FL=FL, D=CL * FL, n_fft=n_fft,
+    CL, FL = plan.ch[Lv], plan.Fq[Lv]
+    n_fft = model._cfg_args["n_fft"]
+    q = dict(plan.geo, plan=plan, L=L, B=B, M=M, S=plan.N * B, Lv=Lv, H=g.hidden_size, NL=g.num_layers, CL=CL, FL=FL, D=CL * FL, n_fft=n_fft,
              sig=_sig(mixture.device, n_fft, model._win, model._hop, model.segment_length))
     return q
 
@@ -224,7 +220,7 @@ def _gru_fwd(model, q, sv, state):
         if state is None or state["h"] is None:
             h0s.append(torch.zeros(B, H, device=dev))
         else:
-            h0s.append(state["h"][l] if "rows" not in q else slab_gather(state["h"][l], q["rows"]["carry"], B, H, B * H, H))
+            h0s.append(start_rows(q["plan"], state["h"][l]))
         outs.append(_new(R, H, dev=dev)); gates.append(_new(R, 4 * H, dev=dev))
     if NL == 1 or N < 4 or not PIPELINE_LAYERS or not K._lib().se_train_gru_pseq_supported(B, H):
         layer_in = seq
@@ -291,13 +287,14 @@ def _gru_bwd(model, q, sv, dxd, df1, grads):
 
 class CRNFunction(torch.autograd.Function):
     """pred = realtime_process(mixture) for the CRN.py (variant 0), CRN_ELU.py (variant 1, the model train.py:16 trains) and
-    distillation_crn.py (variant 2) networks.  forward(ctx, model, mixture, flag, *params).  features=True (CRNFeatFunction, variant 2):
+    distillation_crn.py (variant 2) networks.  forward(ctx, model, mixture, plan, *params), plan = _plan(model, mixture, flag, lengths).
+    features=True (CRNFeatFunction, variant 2):
     the five distillation feature maps are extra outputs in the training layout - f0, f2..f4 [S][C][T][F] before activation, f1 the
     fc output [S*T][D] - and the backward adds their gradients (None: skipped) into the pre-activation gradients, bias gradients
     included."""
 
     @staticmethod
-    def forward(ctx, model, mixture, flag, *params, features=False):
+    def forward(ctx, model, mixture, plan, *params, features=False):
         K._need_gpu(mixture, params[0])
         mixture = mixture.contiguous()
         V = model._VARIANT            # 0 = CRN.py (ReLU); 1 = CRN_ELU.py (ELU, gated 1x1 pair per block, three 5x5 pre-conv blocks, atan2 phase)
@@ -305,18 +302,14 @@ class CRNFunction(torch.autograd.Function):
             raise NotImplementedError(f"no training kernels for variant {V}")
         if features and V != 2:
             raise ValueError("feature maps exist for the distillation_crn.py architecture (variant 2) only")
-        q = _dims(model, mixture, flag)
+        q = _dims(model, mixture, plan)
         B, M, N, S, T, F0, Lv, CL, FL, D = (q[k] for k in ("B", "M", "N", "S", "T", "F0", "Lv", "CL", "FL", "D"))
-        rows = q.get("rows")   # a batch of chunk chains: per-utterance offsets, lengths and flags on the device
-        state = model._state if (any(q["flags"]) if rows else flag) else None
-        if rows and state is not None and state["h"][0].shape[0] != B:
+        state = model._state if plan.any_flag else None
+        if not plan.uniform and state is not None and state["h"][0].shape[0] != B:
             raise RuntimeError(f"flag=True continues row b of the carried state, which holds {state['h'][0].shape[0]} utterances, not {B}")
         act, em = 2 if V else 1, 1 if V == 2 else 0   # em = eps_mode of every gLN
         sv = dict(V=V, act=act, em=em)  # saved for backward
-        if rows:
-            spec = sv["spec"] = stft_rows(q["sig"], mixture, B, M, q["L"], rows["off0"], rows["len"], q["P"], N, T, F0)
-        else:
-            spec = sv["spec"] = stft(q["sig"], mixture, B, M, q["L"], q["off0"], q["P"], N, T, F0)
+        spec = sv["spec"] = stft(plan, q["sig"], mixture, M)
         f0 = _encoder_fwd(model, q, sv, state, _pre_fwd(model, q, sv, state), features)
         o_fc, hTs = _gru_fwd(model, q, sv, state)
         xd = _new(S, CL, T, FL, dev=spec.device)
@@ -327,20 +320,12 @@ class CRNFunction(torch.autograd.Function):
             raise RuntimeError("last decoder block must produce the 2-channel mask at full resolution")
         Y = _new(S, T, F0, 2, dev=spec.device)
         _run("k_tmask", 0.0, K._lib().se_train_mask_fwd, _p(xl), _p(spec), _p(Y), S, M, T, F0, K._st())
-        # carried state for a flag=True continuation: the last segment's block inputs and the GRU state (detached by construction)
-        if rows:   # ... of every utterance's OWN last segment: slab Nb[b], and the layer outputs' row of step Nb[b] * T - 1
-            pred = synthesis_rows(q["sig"], Y, B, q["Ks"], q["L"], rows["skip"], rows["len"])
-            H = q["H"]
-
-            def last(t):   # t [N + 1][B][...] -> [B][...]
-                X = t[0][0].numel()
-                return slab_gather(t, rows["last"], B, X, B * X, X).view(t.shape[1:])
-
-            model._state = dict(buf=[last(sv["xin"][i]) for i in range(Lv)], pbuf=[last(r["cur"]) for r in sv["pre"]] if V else None,
-                                h=[slab_gather(o, rows["lastseg"], B, H, B * T * H, T * H, (T - 1) * H) for o in sv["outs"]])
-        else:
-            pred = synthesis(q["sig"], Y, B, q["Ks"], q["L"], q["skip"])
-            model._state = dict(buf=[sv["xin"][i][N] for i in range(Lv)], h=hTs, pbuf=[r["cur"][N] for r in sv["pre"]] if V else None)
+        pred = synthesis(plan, q["sig"], Y)
+        # carried state for a flag=True continuation (detached by construction): the block inputs after every utterance's OWN last
+        # segment (slab Nb[b]) and the GRU state there - chains: the layer outputs' row of step Nb[b] * T - 1
+        H, dev = q["H"], spec.device
+        model._state = dict(buf=[own_last_slab(plan, sv["xin"][i]) for i in range(Lv)], pbuf=[own_last_slab(plan, r["cur"]) for r in sv["pre"]] if V else None,
+                            h=hTs if plan.uniform else [slab_gather(o, row_table(plan, dev, "lastseg"), B, H, B * T * H, T * H, (T - 1) * H) for o in sv["outs"]])
         ctx.model, ctx.dims, ctx.sv = model, q, sv
         if features:
             return (pred, f0, o_fc) + tuple(r["yd"] for r in dec[:Lv - 1])
@@ -362,10 +347,7 @@ class CRNFunction(torch.autograd.Function):
             if j < Lv - 1 and dfeats[2 + j] is not None:
                 return _inject(dyd, dfeats[2 + j], S, rec["Co"], T * rec["Fy"])
 
-        if "rows" in q:
-            dY = synthesis_adjoint_rows(q["sig"], dpred, B, N, q["L"], q["rows"]["skip"], q["rows"]["len"], q["Ks"], T, F0)
-        else:
-            dY = synthesis_adjoint(q["sig"], dpred, B, N, q["L"], q["skip"], q["Ks"], T, F0)
+        dY = synthesis_adjoint(q["plan"], q["sig"], dpred)
         dx = _new(S, 2, T, F0, dev=dev)
         _run("k_tmask", 0.0, K._lib().se_train_mask_bwd, _p(dY), _p(sv["xl"]), _p(sv["spec"]), _p(dx), S, M, T, F0, q["n_fft"], K._st())
         dxd, dres = decoder_bwd(model.deconvlist, sv["dec"], sv["xin"], dx, grads, zero_bias, S, B, T, sv["act"], sv["em"], hook=feature_hook)
@@ -381,9 +363,9 @@ class CRNFeatFunction(torch.autograd.Function):
     """CRNFunction with features=True: (pred, f0, f1, f2, ...)."""
 
     @staticmethod
-    def forward(ctx, model, mixture, flag, *params):
+    def forward(ctx, model, mixture, plan, *params):
         ctx.set_materialize_grads(False)
-        return CRNFunction.forward(ctx, model, mixture, flag, *params, features=True)
+        return CRNFunction.forward(ctx, model, mixture, plan, *params, features=True)
 
     @staticmethod
     def backward(ctx, dpred, *dfeats):
@@ -398,15 +380,10 @@ def realtime_process_fused(model, mixture, flag=False, features=False, lengths=N
     maps of features=True cover all N = max N_b windows of every utterance.  A batch whose flags and lengths are all alike takes the
     scalar kernels, as a bool flag does."""
     params = [p for _, p in model.named_parameters()]
-    if lengths is not None or isinstance(flag, (torch.Tensor, list, tuple)):
-        B, _, Lmax = mixture.shape
-        flags, lens = _as_flags(flag, B), _as_lengths(lengths, B, Lmax)
-        flag = flags[0] if len(set(flags)) == 1 and min(lens) == Lmax else (tuple(flags), tuple(lens))
-    else:
-        flag = bool(flag)
+    plan = _plan(model, mixture, flag, lengths)
     if not features:
-        return CRNFunction.apply(model, mixture, flag, *params)
-    pred, f0, f1, *fd = CRNFeatFunction.apply(model, mixture, flag, *params)
+        return CRNFunction.apply(model, mixture, plan, *params)
+    pred, f0, f1, *fd = CRNFeatFunction.apply(model, mixture, plan, *params)
     S, C, T, F = f0.shape
     # the reference layout [N*B, C, F, T] as views: f1 is the fc output [S*T][D] reshaped (not permuted), like distillation_crn.py:368
     return pred, [f0.transpose(2, 3), f1.view(S, C, F, T)] + [f.transpose(2, 3) for f in fd]

@@ -1,6 +1,7 @@
 """The passes that every model's kernel path shares, one definition each, on the launch layer of train_ops.py (`conv_w`, `wgrad`,
-`gemm_tn`, `colsum3`, `colsum_tall`, `_new`, `_p`, `_run`: re-exported here): the call geometry, the signal chain (STFT in,
-iSTFT + overlap-add out, and its adjoint), the plain U-Net encoder block, the
+`gemm_tn`, `colsum3`, `colsum_tall`, `_new`, `_p`, `_run`: re-exported here): the signal chain (STFT in, iSTFT + overlap-add out, and its
+adjoint) and the carried-state gathers, which take the call's CallPlan (call_plan.py: the call geometry and the flag / lengths parser,
+re-exported here under the names they had) and pick the scalar kernel or its `_rows` twin, the plain U-Net encoder block, the
 U-Net decoder and one GRU layer of the backward sweep.  train_net.CRNFunction, general_beamformer (inference and GBFFunction) and
 fsn_training.FSNFunction are orchestration over these.  Layout: S = N segments x B utterances, SEGMENT-major, activations
 [S][C][T][F]; an encoder block's input is [N + 1][B][C][T][F] with the carried time history in slab 0 (`xprev = x - one slab`).
@@ -13,63 +14,11 @@ import ctypes as C
 import torch
 
 from . import train_ops as K
+from .call_plan import CallPlan, call_plan, ragged_geometry, segment_geometry  # noqa: F401  (re-exported)
+from .call_plan import as_flag as _as_flag, as_flags as _as_flags, as_lengths as _as_lengths  # noqa: F401  (the names callers know)
 from .train_ops import _new, _p, _run, colsum3, colsum_tall, conv_w, gemm_tn, wgrad  # noqa: F401  (re-exported)
 
 _sig_cache = {}
-
-
-def _as_flag(flag):
-    """realtime_process's flag: a bool, or the trainer's per-utterance flag tensor (data['flag'], shape [B]; one value per batch)."""
-    return bool(flag.reshape(-1)[0].item()) if isinstance(flag, torch.Tensor) else bool(flag)
-
-
-def _as_flags(flag, B):
-    """Per-utterance flags of a batch of chunk chains: a bool or ONE value (every utterance; the reference trainer's flag tensor at
-    batch 1), or B values as a list or the trainer's flag tensor (read once, here).  -> a list of B bools; a mixed tensor stays mixed."""
-    if isinstance(flag, torch.Tensor):
-        flag = flag.reshape(-1).tolist()
-    if isinstance(flag, (list, tuple)):
-        if len(flag) == 1:
-            return [bool(flag[0])] * B
-        if len(flag) != B:
-            raise ValueError(f"{len(flag)} flags for a batch of {B} utterances")
-        return [bool(f) for f in flag]
-    return [bool(flag)] * B
-
-
-def _as_lengths(lengths, B, Lmax):
-    """Per-utterance lengths (a list or an integer tensor, read once, here; None: every utterance is Lmax long) -> a list of B ints"""
-    if lengths is None:
-        return [int(Lmax)] * B
-    lengths = [int(v) for v in (lengths.reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-    if len(lengths) != B or min(lengths) < 1 or max(lengths) > Lmax:
-        raise ValueError(f"lengths must be {B} values in [1, {Lmax}], got {lengths}")
-    return lengths
-
-
-def segment_geometry(L, flag, segment_length, hop, n_fft, ch=()):
-    """One realtime_process call over L samples in half-overlapping segments (utility.segmentation); flag=False pads P = Ks / 2 samples
-    on the left and strips them again.  ch = the U-Net levels' channels, input first; Fq[i] = level i's frequency size (stride 2)."""
-    Ks = segment_length
-    P = Ks // 2
-    Lp = L if flag else L + P
-    gap = Ks - (P + Lp % Ks) % Ks
-    Fq = [n_fft // 2 + 1]
-    for _ in ch[1:]:
-        Fq.append((Fq[-1] - 1) // 2 + 1)
-    return dict(L=L, Ks=Ks, P=P, Lp=Lp, gap=gap, N=2 * (Lp + gap + P) // Ks, off0=-P if flag else -2 * P, skip=0 if flag else P,
-                T=1 + Ks // hop, F0=Fq[0], ch=list(ch), Fq=Fq)
-
-
-def ragged_geometry(lengths, flags, segment_length, hop, n_fft, ch=()):
-    """A batch of chunk chains in one call: utterance b is lengths[b] samples long and continues its own state iff flags[b].  Segment
-    positions do not depend on the length, so every utterance keeps the geometry it would have alone: Lp, gap, Nb, off0, skip are lists,
-    entry b = segment_geometry(lengths[b], flags[b], ...); N = max Nb segments are run, L = max length is the width of the batch."""
-    per = [segment_geometry(int(L), bool(f), segment_length, hop, n_fft, ch) for L, f in zip(lengths, flags)]
-    q = dict(per[0])
-    q.update(L=max(p["L"] for p in per), N=max(p["N"] for p in per), lengths=[p["L"] for p in per], flags=[bool(f) for f in flags],
-             Nb=[p["N"] for p in per], **{k: [p[k] for p in per] for k in ("Lp", "gap", "off0", "skip")})
-    return q
 
 
 def grads_in_parameter_order(model, grads):
@@ -115,23 +64,39 @@ def _cs(Cc, T, Fq):
     return (Cc * T * Fq, T * Fq, Fq)
 
 
-# ---- signal chain ----------------------------------------------------------------------------------------------------------------
-def stft(sig, x, B, M, L, off0, P, N, T, F0):
-    """x [B][M][L] -> spec [N][B*M][T][F0][2]: segment n of every row starts at sample off0 + n * P (zeros outside [0, L))."""
-    spec = _new(N, B * M, T, F0, 2, dev=x.device)
-    _run("k_stft", 0.0, K._lib().se_sig_stft, sig, _p(x), B, M, L, off0, P, N, _p(spec), K._st())
-    return spec
-
-
+# ---- signal chain: every helper takes the call's CallPlan and launches the scalar kernel (uniform) or its `_rows` twin (chains) -----
 def _rows(values, dev):
     """host ints -> a device int64 [B] (one asynchronous copy; the row kernels read it on the stream)"""
     return torch.tensor(values, dtype=torch.int64).to(dev, non_blocking=True)
 
 
-def stft_rows(sig, x, B, M, Lmax, off0, lens, P, N, T, F0):
-    """stft for a batch of chunk chains: off0 / lens = device int64 [B]; utterance b is zero outside [0, lens[b]) whatever x holds there"""
-    spec = _new(N, B * M, T, F0, 2, dev=x.device)
-    _run("k_stft", 0.0, K._lib().se_sig_stft_rows, sig, _p(x), B, M, Lmax, C.c_void_p(off0.data_ptr()), C.c_void_p(lens.data_ptr()), P, N, _p(spec), K._st())
+def row_table(plan, dev, key):
+    """plan.table(key) as a device int64 [B]: copied once per plan and device, kept on the plan"""
+    if (dev, key) not in plan.dev:
+        plan.dev[dev, key] = _rows(plan.table(key), dev)
+    return plan.dev[dev, key]
+
+
+def _ip(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _stft(sig, x, rows_, M, L, off0, P, N, T, F0):
+    """x [rows_][M][L] -> spec [N][rows_*M][T][F0][2]: segment n of every row starts at sample off0 + n * P (zeros outside [0, L))."""
+    spec = _new(N, rows_ * M, T, F0, 2, dev=x.device)
+    _run("k_stft", 0.0, K._lib().se_sig_stft, sig, _p(x), rows_, M, L, off0, P, N, _p(spec), K._st())
+    return spec
+
+
+def stft(plan, sig, x, M, n0=0, Nc=None):
+    """x [B][M][L] -> spec [Nc][B*M][T][F0][2], segments [n0, n0 + Nc) of the call (default: all N): segment n of utterance b starts at
+    sample off0[b] + n * P; zeros outside [0, lengths[b]) whatever x holds there."""
+    N = plan.N - n0 if Nc is None else Nc
+    if plan.uniform:
+        return _stft(sig, x, plan.B, M, plan.L, plan.off0 + n0 * plan.P, plan.P, N, plan.T, plan.F0)
+    off0 = row_table(plan, x.device, "off0") if n0 == 0 else _rows([o + n0 * plan.P for o in plan.off0], x.device)
+    spec = _new(N, plan.B * M, plan.T, plan.F0, 2, dev=x.device)
+    _run("k_stft", 0.0, K._lib().se_sig_stft_rows, sig, _p(x), plan.B, M, plan.L, _ip(off0), _ip(row_table(plan, x.device, "len")), plan.P, N, _p(spec), K._st())
     return spec
 
 
@@ -140,8 +105,26 @@ def slab_gather(src, idx, B, X, sN, sB, off_floats=0, dst=None):
     device int64 [B])"""
     if dst is None:
         dst = _new(B, X, dev=src.device)
-    _run("k_slab_gather", 0.0, K._lib().se_train_slab_gather, _p(src, off_floats), C.c_void_p(idx.data_ptr()), _p(dst), B, X, sN, sB, K._st())
+    _run("k_slab_gather", 0.0, K._lib().se_train_slab_gather, _p(src, off_floats), _ip(idx), _p(dst), B, X, sN, sB, K._st())
     return dst
+
+
+def start_rows(plan, t, dst=None):
+    """The rows of the carried tensor t [B][...] a call starts from: t itself when uniform (the caller decides between it and zeros by
+    plan.flag), else row b where flags[b] and zeros where utterance b starts afresh (a new tensor, or into dst)."""
+    if plan.uniform:
+        return t if dst is None else dst.copy_(t)
+    X = t.numel() // plan.B
+    return slab_gather(t, row_table(plan, t.device, "carry"), plan.B, X, plan.B * X, X, dst=dst).view(t.shape)
+
+
+def own_last_slab(plan, t, counts=None, copy=False):
+    """t [n + 1][B][...] -> [B][...]: the slab after utterance b's own last segment - slab n for all when uniform (a view of t unless
+    copy), else slab Nb[b], or counts[b] (a device int64 [B]) where t holds a part of the call only."""
+    if plan.uniform:
+        return t[-1].clone() if copy else t[-1]
+    X = t[0][0].numel()
+    return slab_gather(t, row_table(plan, t.device, "last") if counts is None else counts, plan.B, X, plan.B * X, X).view(t.shape[1:])
 
 
 def input_features(spec, x_full, S, B, M, C0, T, F0, atan2=0):
@@ -154,41 +137,52 @@ def istft(sig, Y, yseg, row0=0):
     _run("k_istft", 0.0, K._lib().se_sig_istft, sig, _p(Y), Y.shape[0], _p(yseg, row0 * yseg.shape[-1]), K._st())
 
 
-def overlap_add(sig, yseg, B, Lout, skip):
-    """utility.over_add of the segment-major yseg [N*B][Ks] -> pred [B][Lout], the first `skip` samples dropped"""
-    pred = _new(B, Lout, dev=yseg.device)
-    _run("k_tola", 0.0, K._lib().se_train_ola_fwd, sig, _p(yseg), _p(pred), B, Lout, skip, K._st())
+def overlap_add(plan, sig, yseg):
+    """utility.over_add of the segment-major yseg [N*B][Ks] -> pred [B][L]: the first skip[b] samples dropped, pred[b][lengths[b]:] = 0"""
+    dev = yseg.device
+    pred = _new(plan.B, plan.L, dev=dev)
+    if plan.uniform:
+        _run("k_tola", 0.0, K._lib().se_train_ola_fwd, sig, _p(yseg), _p(pred), plan.B, plan.L, plan.skip, K._st())
+    else:
+        _run("k_tola", 0.0, K._lib().se_train_ola_fwd_rows, sig, _p(yseg), _p(pred), plan.B, plan.L, _ip(row_table(plan, dev, "skip")), _ip(row_table(plan, dev, "len")), K._st())
     return pred
 
 
-def synthesis(sig, Y, B, Ks, Lout, skip):
-    """Y [S][T][F0][2] -> pred [B][Lout]: iSTFT of every segment, then overlap-add"""
-    yseg = _new(Y.shape[0], Ks, dev=Y.device)
+def synthesis(plan, sig, Y):
+    """Y [S][T][F0][2] -> pred [B][L]: iSTFT of every segment, then overlap-add"""
+    yseg = _new(Y.shape[0], plan.Ks, dev=Y.device)
     istft(sig, Y, yseg)
-    return overlap_add(sig, yseg, B, Lout, skip)
+    return overlap_add(plan, sig, yseg)
 
 
-def synthesis_adjoint(sig, dpred, B, N, Lout, skip, Ks, T, F0):
-    """dpred [B][Lout] -> dY [S][T][F0][2]: the adjoint of overlap-add, then of the iSTFT (an STFT of every segment)"""
-    gseg = _new(N * B, Ks, dev=dpred.device)
-    _run("k_tola", 0.0, K._lib().se_train_ola_bwd, sig, _p(dpred), _p(gseg), B, N, Lout, skip, K._st())
-    return stft(sig, gseg, N * B, 1, Ks, 0, 0, 1, T, F0).view(N * B, T, F0, 2)
+def synthesis_adjoint(plan, sig, dpred):
+    """dpred [B][L] -> dY [S][T][F0][2]: the adjoint of overlap-add (dpred[b][lengths[b]:] is never read), then of the iSTFT (an STFT
+    of every segment)"""
+    B, N, dev = plan.B, plan.N, dpred.device
+    gseg = _new(N * B, plan.Ks, dev=dev)
+    if plan.uniform:
+        _run("k_tola", 0.0, K._lib().se_train_ola_bwd, sig, _p(dpred), _p(gseg), B, N, plan.L, plan.skip, K._st())
+    else:
+        _run("k_tola", 0.0, K._lib().se_train_ola_bwd_rows, sig, _p(dpred), _p(gseg), B, N, plan.L, _ip(row_table(plan, dev, "skip")), _ip(row_table(plan, dev, "len")), K._st())
+    return _stft(sig, gseg, N * B, 1, plan.Ks, 0, 0, 1, plan.T, plan.F0).view(N * B, plan.T, plan.F0, 2)
 
 
-def synthesis_rows(sig, Y, B, Ks, Lmax, skip, lens):
-    """synthesis for a batch of chunk chains: skip / lens = device int64 [B]; pred [B][Lmax] with pred[b][lens[b]:] = 0"""
-    yseg = _new(Y.shape[0], Ks, dev=Y.device)
-    istft(sig, Y, yseg)
-    pred = _new(B, Lmax, dev=Y.device)
-    _run("k_tola", 0.0, K._lib().se_train_ola_fwd_rows, sig, _p(yseg), _p(pred), B, Lmax, C.c_void_p(skip.data_ptr()), C.c_void_p(lens.data_ptr()), K._st())
-    return pred
+def gru_steps(plan, dev, T, per, n0=0, Nc=None):
+    """Step counts of a GRU launch over segments [n0, n0 + Nc) with `per` streams per utterance, stream-major: live segments x T, a
+    device int32 [B * per] - and the live counts, a device int64 [B] for own_last_slab.  Uniform: (None, None), every stream runs all."""
+    if plan.uniform:
+        return None, None
+    live = plan.live(n0, Nc)
+    return torch.tensor(live, dtype=torch.int32).mul_(T).repeat_interleave(per).to(dev, non_blocking=True), _rows(live, dev)
 
 
-def synthesis_adjoint_rows(sig, dpred, B, N, Lmax, skip, lens, Ks, T, F0):
-    """synthesis_adjoint for a batch of chunk chains; dpred[b][lens[b]:] is ignored"""
-    gseg = _new(N * B, Ks, dev=dpred.device)
-    _run("k_tola", 0.0, K._lib().se_train_ola_bwd_rows, sig, _p(dpred), _p(gseg), B, N, Lmax, C.c_void_p(skip.data_ptr()), C.c_void_p(lens.data_ptr()), K._st())
-    return stft(sig, gseg, N * B, 1, Ks, 0, 0, 1, T, F0).view(N * B, T, F0, 2)
+def gru_steps_bwd(plan, dev, T, per):
+    """Step counts of the backward sweep, one sequence per (stream, segment): T where the segment is the utterance's own, else 0 - a
+    device int32 [B * per * N]; None when uniform."""
+    if plan.uniform:
+        return None
+    steps = (torch.arange(plan.N)[None, :] < torch.tensor(plan.Nb)[:, None]).to(torch.int32).mul_(T).repeat_interleave(per, dim=0)
+    return steps.reshape(-1).to(dev, non_blocking=True)
 
 
 # ---- U-Net encoder block, plain variant: conv + gLN + ReLU ------------------------------------------------------------------------

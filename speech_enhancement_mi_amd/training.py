@@ -22,7 +22,7 @@ from .crn import TemporalCRN
 from .crn_elu import TemporalCRN as TemporalCRNELU
 from .distillation_crn import TemporalCRN as TemporalStudentCRN
 from .losses import cal_si_snr
-from .train_stages import _as_flags, _as_lengths, ragged_geometry
+from .call_plan import as_flags, as_lengths, call_plan, overlap_add_cut, segment_geometry, windows
 
 EPS = 1e-8
 
@@ -63,14 +63,9 @@ class _TrainableMixin:
 
     # ---- signal glue (utility.py:312-403, CRN.py:505-520) ----
     def _segment(self, x):
-        B, M, L = x.shape
-        K = self.segment_length
-        P = K // 2
-        gap = K - (P + L % K) % K
-        xp = Fn.pad(x, (P, gap + P))
-        n = 2 * (L + gap + P) // K
-        idx = (torch.arange(n, device=x.device) * P)[:, None] + torch.arange(K, device=x.device)[None, :]
-        return xp[:, :, idx], gap  # [B, M, N, K]
+        """utility.segmentation of x [B, M, L] as it stands (no lead): call_plan.windows of a continuing call -> ([B, M, N, K], gap)"""
+        plan = call_plan(True, None, x.shape[0], x.shape[-1], self.segment_length, self.segment_length, 0)   # the STFT sizes do not enter
+        return windows(plan, x), plan.gap
 
     def _stft(self, seg):  # [..., K] -> [..., F, T] complex
         shp = seg.shape[:-1]
@@ -155,7 +150,7 @@ class _TrainableMixin:
         """The state of B utterances after a reset, spelled out (what `None` stands for in _forward_segment)"""
         g = self.gru.sequence_model
         ch = [2 * M - 1] + [blk.conv.weight.shape[0] for blk in self.convlist]
-        Fq = ragged_geometry([1], [True], self.segment_length, self._hop, self._nfft, ch)["Fq"]
+        Fq = segment_geometry(1, True, self.segment_length, self._hop, self._nfft, ch)["Fq"]
         return dict(buf=[like.new_zeros(B, ch[i], Fq[i], 2 * 2 ** i) for i in range(len(self.convlist))], h=like.new_zeros(g.num_layers, B, g.hidden_size),
                     pbuf=[like.new_zeros(B, ch[0], Fq[0], 4) for _ in self.preconvlist] if self._VARIANT else None)
 
@@ -166,45 +161,14 @@ class _TrainableMixin:
         return dict(buf=[pick(x, y, 0) for x, y in zip(a["buf"], b["buf"])], h=pick(a["h"], b["h"], 1),
                     pbuf=None if a["pbuf"] is None else [pick(x, y, 0) for x, y in zip(a["pbuf"], b["pbuf"])])
 
-    def _realtime_process_chains(self, mixture, flags, lens, features):
-        """B independent chunk chains in one call: utterance b has its own length (zeros beyond it, enforced) and its own flag.  Every
-        statistic of the model is per utterance and segment positions do not depend on the length, so all utterances run the N = max N_b
-        segments of the longest; an utterance's carried state is taken after its OWN last segment, its output cut from its own samples."""
-        B, M, Lmax = mixture.shape
-        K = self.segment_length
-        P = K // 2
-        q = ragged_geometry(lens, flags, K, self._hop, self._nfft)
-        N, dev = q["N"], mixture.device
-        state = self._zero_state(B, M, mixture)
-        if any(flags):
-            if self._state is None or self._state.get("buf") is None or self._state["h"].shape[1] != B:
-                raise RuntimeError(f"flag=True continues row b of the carried state of {B} utterances: there is none")
-            state = self._merge_state(torch.tensor(flags, device=dev), self._state, state)
-        xp = torch.cat([Fn.pad(mixture[b:b + 1, :, :lens[b]], (-q["off0"][b], (N + 1) * P + q["off0"][b] - lens[b])) for b in range(B)])
-        idx = (torch.arange(N, device=dev) * P)[:, None] + torch.arange(K, device=dev)[None, :]
-        X = self._stft(xp[:, :, idx])  # [B, M, N, F, T]
-        Nb = torch.tensor(q["Nb"], device=dev)
-        final, outs, fts = state, [], []
-        for n in range(N):
-            f = [] if features else None
-            Y, state = self._forward_segment(X[:, :, n], state, f)
-            outs.append(self._istft(Y))
-            fts.append(f)
-            if n + 1 in q["Nb"]:
-                final = self._merge_state(Nb == n + 1, state, final)
-        self._state = final
-        y = torch.stack(outs, dim=1)  # [B, N, K]
-        full = (y[:, 0::2].reshape(B, -1)[:, P:] + y[:, 1::2].reshape(B, -1)[:, :-P]) / 2
-        out = torch.stack([Fn.pad(full[b, q["skip"][b]:q["skip"][b] + lens[b]], (0, Lmax - lens[b])) for b in range(B)])
-        if features:
-            return out, [torch.cat([f[k] for f in fts], dim=0) for k in range(len(fts[0]))]
-        return out
-
     def realtime_process_train(self, mixture, flag=False, features=False, lengths=None):
         """Differentiable realtime_process (CRN.py:560-589): [B, M, L] -> [B, L].  features=True (variant 2): returns (pred, [ft0..ft4])
         with the five distillation feature maps [N*B, C, F, T], window-major (distillation_crn.py:451-477).
         flag as one value per utterance ([B] tensor / list) and / or lengths ([B] ints <= L): the batch is B independent chunk chains
-        (train_net.realtime_process_fused states the contract; both paths honour it)."""
+        (train_net.realtime_process_fused states the contract; both paths honour it).  Here: every statistic of the model is per utterance
+        and segment positions do not depend on the length, so all utterances run the N = max N_b segments of the longest; an utterance's
+        carried state is taken after its OWN last segment, its output cut from its own samples.  The uniform call is that loop with one
+        flag and N_b = N for all (bit for bit what a loop without the per-utterance merges gives)."""
         if features and self._VARIANT != 2:
             raise ValueError("feature maps exist for the distillation_crn.py architecture (variant 2) only")
         if self._hip:  # every stage forward and backward on the hand-written kernels, one autograd node (train_net.py)
@@ -212,36 +176,29 @@ class _TrainableMixin:
             if self._hip_state_from_torch:
                 raise RuntimeError("flag=True continuation across a use_hip_kernels() switch is not supported: start with flag=False")
             return realtime_process_fused(self, mixture, flag, features=features, lengths=lengths)
-        if lengths is not None or isinstance(flag, (torch.Tensor, list, tuple)):
-            flags, lens = _as_flags(flag, mixture.shape[0]), _as_lengths(lengths, mixture.shape[0], mixture.shape[-1])
-            if len(set(flags)) > 1 or min(lens) < mixture.shape[-1]:
-                return self._realtime_process_chains(mixture, flags, lens, features)
-            flag = flags[0]
-        K = self.segment_length
-        P = K // 2
-        if not flag:
-            mixture = Fn.pad(mixture, (P, 0))
-            self._state = dict(buf=None, h=None, pbuf=None)
-        seg, gap = self._segment(mixture)  # [B, M, N, K]
-        X = self._stft(seg)  # [B, M, N, F, T]
-        state = self._state
-        outs = []
-        fts = [] if features else None
-        for n in range(X.shape[2]):
+        B, M, Lmax = mixture.shape
+        plan = call_plan(flag, lengths, B, Lmax, self.segment_length, self._hop, self._nfft)
+        dev = mixture.device
+        if plan.uniform:   # one flag: the carried state as it stands, or None entries = zeros (_forward_segment)
+            state = self._state if plan.flag else dict(buf=None, h=None, pbuf=None)
+        else:
+            state = self._zero_state(B, M, mixture)
+            if plan.any_flag:
+                if self._state is None or self._state.get("buf") is None or self._state["h"].shape[1] != B:
+                    raise RuntimeError(f"flag=True continues row b of the carried state of {B} utterances: there is none")
+                state = self._merge_state(torch.tensor(plan.flags, device=dev), self._state, state)
+        X = self._stft(windows(plan, mixture))  # [B, M, N, F, T]
+        Nb = torch.tensor(plan.Nb, device=dev)
+        final, outs, fts = state, [], []
+        for n in range(plan.N):
             f = [] if features else None
             Y, state = self._forward_segment(X[:, :, n], state, f)
             outs.append(self._istft(Y))
-            if features:
-                fts.append(f)
-        y = torch.stack(outs, dim=1)  # [B, N, K]
-        self._state = state
-        B, N, _ = y.shape
-        s1 = y[:, 0::2].reshape(B, -1)[:, P:]
-        s2 = y[:, 1::2].reshape(B, -1)[:, :-P]
-        out = (s1 + s2) / 2
-        if gap > 0:
-            out = out[:, :-gap]
-        out = out if flag else out[:, P:]
+            fts.append(f)
+            if not plan.uniform and n + 1 in plan.Nb:
+                final = self._merge_state(Nb == n + 1, state, final)
+        self._state = state if plan.uniform else final
+        out = overlap_add_cut(plan, torch.stack(outs, dim=1))  # [B, N, K] -> [B, L]
         if features:
             return out, [torch.cat([f[k] for f in fts], dim=0) for k in range(len(fts[0]))]
         return out
@@ -328,7 +285,7 @@ def train_step(model: TrainableCRN, bucket: FlatBucket, optimizer, mixture, sour
     B = mixture.shape[0]
     chain = [{}] * accum   # the forward's flag / lengths per micro-batch
     if flag is not None:
-        flags, lns = _as_flags(flag, B), _as_lengths(length, B, mixture.shape[-1])
+        flags, lns = as_flags(flag, B), as_lengths(length, B, mixture.shape[-1])
         per = -(-B // accum)   # torch.chunk's split
         chain = [dict(flag=flags[i:i + per], lengths=lns[i:i + per]) for i in range(0, B, per)]
     if merge:

@@ -133,7 +133,7 @@ def _flat_grad(m):
 def test_uniform_batch_is_unchanged():
     """flag as a uniform tensor + lengths = [L] * B is the bool call, bit for bit - through the dispatch (scalar kernels) and when the
     row kernels themselves are given the uniform batch; a reset call and a continuation, pred and every gradient."""
-    from speech_enhancement_mi_amd.train_net import CRNFunction
+    from speech_enhancement_mi_amd.train_net import CRNFunction, _plan
     B, L = 4, 6400
     mix, _ = synth.synth_utterances(B, 2 * L, 3, seed=31)
     x = torch.from_numpy(mix).cuda()
@@ -149,7 +149,7 @@ def test_uniform_batch_is_unchanged():
             elif how == "uniform":
                 pred = m.realtime_process_train(xc, torch.tensor([flag] * B), lengths=[L] * B)
             else:
-                pred = CRNFunction.apply(m, xc, ((flag,) * B, (L,) * B), *[p for _, p in m.named_parameters()])
+                pred = CRNFunction.apply(m, xc, _plan(m, xc, flag, uniform=False), *[p for _, p in m.named_parameters()])
             m.zero_grad()
             (pred * w).sum().backward()
             out += [pred.detach().clone(), _flat_grad(m).clone()]
