@@ -171,7 +171,7 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
                               additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
-                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains */
+                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference) */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -484,6 +484,45 @@ int se_gbf_seq_bwd(const float *dphi, const float *hS, const float *hN, const fl
 int se_gbf_bf_bwd(const float *dY, const float *phi, const float *spec, const float *w0, const float *b0, const float *g, const float *beta,
                   const float *w3, float *dphi, float *dpre, float *act, float *dw, float *pg, float *pb, int S, int M, int T, int F, int H,
                   int n_fft, void *stream);
+
+/* ---- GTSA inference (reference GTSA.py:139-307; csrc/se_gtsa.hip; additions at ABI 5) ------------------------------------------------
+ * Window-major streams S = Nc x B (s = n B + b).  ONE activation layout x [S][5][T][Fs]: 5 = 2M - 1 features of M = 3 microphones, Fs >= F
+ * the row stride (F padded to the GEMM's K % 8; every kernel that writes x writes zeros into the pad).  Even transformer layers take rows
+ * (s, c, t) of F; odd layers rows (s, f, t) of 5 at stride T Fs.  T <= 32 frames per window; se_gtsa_limits reports the limits.
+ * The rolling key / value buffer of a layer is a tape per (sequence, head): rows [0, maxlen) the carried part
+ * kc / vc [(b U + u) Hh + h][maxlen][D], then row maxlen + n T + t = row ((n B + b) U + u) T + t of kn / vn (stride ldk, head h at
+ * column h D).  U sequences per utterance (5 on even layers, F on odd), Hh heads of D (3 x 67 / 1 x 5).
+ * se_gtsa_feat: spec [S][M][T][F][2] -> x: sqrt(re^2 + im^2 + 1e-10) of every microphone, atan2 phase differences angle_0 - angle_m;
+ *   a bin that is exactly zero has phase 0 whatever the signs of its zeros.
+ * se_gtsa_attn: out[row ((s U + u) T + t), stride ldo, column h D ..] = softmax_j(|q . k_j G[i][j] / sqrt(model_dim)|) v_j over the
+ *   maxlen tape rows [(n + 1) T, (n + 1) T + maxlen) of window n, i = maxlen - T + t, G = exp(-(i - j)^2 / (delta^2 + 1e-8));
+ *   q rows like out at stride ldq.  T <= maxlen <= 4096.  Scores and probabilities stay on chip.
+ * se_gtsa_tape: ko / vo (same layout as kc / vc, other memory) = the last maxlen tape rows after Nc windows.
+ * se_gtsa_addnorm: y = gLN(a + x) for nseq sequences of T rows (a at stride lda, x / y at stride Fs; y may be x): statistics over
+ *   T x F, (v - mean) / (sqrt(var + 1e-10) + 1e-8) * w[f] + b[f]; T F <= 8192.
+ * se_gtsa_qkv5: the 5 x 5 q / k / v projections of an odd layer -> qkv [S][F][T][16] (q 0..4, k 5..9, v 10..14, 15 zero).
+ * se_gtsa_tail5: an odd layer after attention, in place if y = x: att rows [S][F][T] (stride lda) -> linear (5 x 5) + x, gLN (naw, nab),
+ *   linear_in [fn][5] + ReLU + linear_out [5][fn] + residual, gLN (niw, nib).  The hidden activation is never stored.
+ * se_gtsa_gather3: A [S T][3 * 5][Fs] = frames t - 2, t - 1, t of x; frames before window 0 come from buf [B][5][2][Fs].
+ * se_gtsa_out: g rows [S T] (stride ldg: conv_trans at column o, conv_gated at 2F + o) -> gLN over 2F x T of trans * sigmoid(gated)
+ *   with affine [2F], decompress_cIRM, times microphone 0 of spec -> Y [S][T][F][2]; tap (may be NULL) [S][2F][T] the mask before
+ *   decompress_cIRM.
+ * No atomics; reductions in a fixed order independent of S. */
+int se_gtsa_limits(int *max_frames, int *max_maxlen, int *max_norm_values);
+int se_gtsa_feat(const float *spec, float *x, int S, int M, int T, int F, int Fs, void *stream);
+int se_gtsa_attn(const float *q, const float *kn, const float *vn, const float *kc, const float *vc, float *out, const float *delta, int ldq,
+                 int ldk, int ldo, int S, int B, int U, int Hh, int D, int T, int maxlen, int model_dim, void *stream);
+int se_gtsa_tape(const float *kn, const float *vn, const float *kc, const float *vc, float *ko, float *vo, int ldk, int Nc, int B, int U, int Hh,
+                 int D, int T, int maxlen, void *stream);
+int se_gtsa_addnorm(const float *a, int lda, const float *x, float *y, const float *w, const float *b, int nseq, int T, int F, int Fs, void *stream);
+int se_gtsa_qkv5(const float *x, const float *wq, const float *bq, const float *wk, const float *bk, const float *wv, const float *bv, float *qkv,
+                 int S, int T, int F, int Fs, void *stream);
+int se_gtsa_tail5(const float *att, int lda, const float *x, float *y, const float *wo, const float *bo, const float *naw, const float *nab,
+                  const float *win, const float *bin, const float *wout, const float *bout, const float *niw, const float *nib, int S, int T, int F,
+                  int Fs, int fn, void *stream);
+int se_gtsa_gather3(const float *x, const float *buf, float *A, int S, int B, int T, int Fs, void *stream);
+int se_gtsa_out(const float *g, int ldg, const float *nw, const float *nb, const float *spec, float *Y, float *tap, int S, int M, int T, int F,
+                void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -190,6 +190,43 @@ def gbf_param_spec(num_channels, num_freqs, hidden, segment_length, num_layers=1
     return spec
 
 
+def gtsa_param_spec(num_mics, num_freqs, num_layers, fn_dim, maxlen=500):
+    """(key, shape) list of reference GTSA.state_dict() of a freshly built model (GTSA.py:256-274; checked against the live module,
+    fixture gtsa_keys.json): `last_conv` first, then the layers - even ones over num_freqs, odd ones over 2 * num_mics - 1."""
+    C0, F = 2 * num_mics - 1, num_freqs
+    p = "last_conv."
+    spec = [(p + "conv.weight", (2 * F, C0 * F, 3)), (p + "conv.bias", (2 * F,)), (p + "conv_trans.weight", (2 * F, 2 * F, 1)),
+            (p + "conv_trans.bias", (2 * F,)), (p + "conv_gated.weight", (2 * F, 2 * F, 1)), (p + "conv_gated.bias", (2 * F,)),
+            (p + "net.0.weight", (2 * F, C0 * F, 3)), (p + "net.0.bias", (2 * F,)), (p + "norm.weight", (1, 2 * F, 1)), (p + "norm.bias", (1, 2 * F, 1))]
+    for i in range(num_layers):
+        d = F if i % 2 == 0 else C0
+        p = f"layers.{i}."
+        spec += [(p + "attention.delta", (1,)), (p + "attention.ind", (maxlen, maxlen))]
+        for name in ("ql", "kl", "vl", "linear"):
+            spec += [(p + f"attention.{name}.weight", (d, d)), (p + f"attention.{name}.bias", (d,))]
+        spec += [(p + "norm_a.weight", (1, 1, d)), (p + "norm_a.bias", (1, 1, d)), (p + "linear_in.weight", (fn_dim, d)), (p + "linear_in.bias", (fn_dim,)),
+                 (p + "linear_out.weight", (d, fn_dim)), (p + "linear_out.bias", (d,)), (p + "norm_i.weight", (1, 1, d)), (p + "norm_i.bias", (1, 1, d))]
+    return spec
+
+
+def gtsa_state_dict(spec, seed: int = 0) -> Dict[str, np.ndarray]:
+    """make_state_dict for a GTSA spec, then: every `ind` the true table -(i - j)^2 (int64), every `delta` in [3, 12] (at the initial 1
+    the Gaussian is almost diagonal and a wrong window offset would go unnoticed), `norm_a` / `norm_i` the perturbed (1, 0) affine of
+    the other norms.  The q / k projections keep make_state_dict's scale: tests/golden/make_golden_gtsa.py checks that float32 holds
+    the fixture at that scale."""
+    out = make_state_dict(spec, seed)
+    for name, shape in spec:
+        u = hash_tensor(name, tuple(shape), seed)
+        if name.endswith("attention.ind"):
+            i = np.arange(1, shape[0] + 1, dtype=np.int64)
+            out[name] = -(i[:, None] - i[None, :]) ** 2
+        elif name.endswith("attention.delta"):
+            out[name] = (7.5 + 4.5 * u).astype(np.float32)
+        elif ".norm_a." in name or ".norm_i." in name:
+            out[name] = (1.0 + 0.25 * u if name.endswith("weight") else 0.25 * u).astype(np.float32)
+    return out
+
+
 def synth_utterances(batch: int, length: int, num_mics: int = 3, seed: int = 0,
                      sample_rate: int = 16000):
     """Synthetic noisy multi-mic speech-like audio: returns (mix [B,M,L], clean [B,L]).
