@@ -94,11 +94,11 @@ int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t l
 /* Ragged batch (the reference's utterances are 1 .. 3.75 s long, data_c.py:155-173): stream b holds lengths[b] <= max_length valid
  * samples of mixture [B, M, max_length]; every stream gets exactly the output it would get alone - its own zero padding (samples past
  * its length read as zeros) and out[b, lengths[b]:] = 0.  lengths is a HOST array.
- * Prefix compaction: when the lengths are NON-INCREASING (sort the batch; the Python shim does) every segment is launched for the prefix
- * of streams that still take part in it only - every layout is stream-major, so nothing moves; grids, GEMM rows and recurrence rows
- * shrink (plane path, CRN.py variant, batches on the plane-GEMM route; SE_RAGGED_COMPACT=0 turns it off).  With unsorted lengths every
- * stream runs every segment.  Either way the carried state of a stream that ended early is not a continuation state: follow with
- * flag = 0, or se_reset_stream, for those streams - or use se_realtime_process_chains below, which leaves every stream its own state. */
+ * This is se_realtime_process_chains (below) with the one flag for every stream, and everything said there holds: a stream that ends
+ * before the longest one keeps its own continuation state, and when the segment counts are NON-INCREASING (sort the batch; the Python
+ * shim does) every segment is launched for the prefix of streams that still take part in it only - every layout is stream-major, so
+ * nothing moves; grids, GEMM rows and recurrence rows shrink (plane path, CRN.py variant, batches on the plane-GEMM route;
+ * SE_RAGGED_COMPACT=0 turns it off).  With unsorted counts every stream runs every segment. */
 int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, int flag, float *out,
                                void *stream);
 
@@ -117,7 +117,7 @@ int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, in
  * Every stream keeps the segment geometry it has alone (utility.py:327-329, 360-368 with lead = flags[b] ? 0 : K/2); the call runs
  * max_b N_b segments.  The state of a stream is saved when its last segment has passed a stage (encoder rows on the encoder's stream,
  * layer l's h after layer l) and written back when the call ends; a reset among continuing streams zeroes that stream's rows at
- * entry.  Prefix compaction as in se_realtime_process_ragged, when the segment counts N_b are non-increasing.  A uniform batch (equal
+ * entry.  Prefix compaction (see se_realtime_process_ragged) when the segment counts N_b are non-increasing.  A uniform batch (equal
  * flags, every length == max_length) is exactly se_realtime_process: no save, no restore, no extra launch. */
 int se_realtime_process_chains(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host,
                                const uint8_t *flags_host, float *out, void *stream);

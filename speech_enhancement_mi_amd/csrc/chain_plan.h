@@ -6,7 +6,7 @@
 // engine.chain_geometry restates it in Python and tests/test_chain_plan_cpu.py holds the two together through se_chunk_geometry.
 //
 // A ChainPlan is everything a call needs beyond the uniform case:
-//   nseg[b]      segments stream b takes part in (the count it has alone); N = the most any stream has (ragged: of max_length)
+//   nseg[b]      segments stream b takes part in (the count it has alone); N = the most any stream has
 //   le[k]        streams with at most k segments, k = 0 .. N
 //   sorted       device: the streams by ascending segment count (stable), so the streams whose LAST segment is n are positions
 //                [le[n], le[n + 1]) of it: ending(n).  Their state rows are saved there and restored at call exit (ended_early())
@@ -15,8 +15,8 @@
 //   compact      the streams still running in segment n are a PREFIX of the batch (counts non-increasing): launches cover bact(n) streams
 //   saving       some stream ends before the longest one: save / restore is live
 // plan_chains() validates, sorts and fills `staging` = len | off0 | skip | (int) sorted | zeroed; the engine uploads it with one copy
-// into 8 * B floats of its own and calls carve().  plan_ragged() is the plan of se_realtime_process_ragged: a common flag, lengths only,
-// nothing saved.  Plain host C++: no HIP types, no engine types.
+// into 8 * B floats of its own and calls carve() (engine_host.h: upload_plan).  A ragged call (se_realtime_process_ragged: a common flag,
+// lengths only) is a chains call whose flags are all equal.  Plain host C++: no HIP types, no engine types.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -65,27 +65,6 @@ struct ChainPlan {
     }
 };
 
-namespace plan_detail {
-
-inline int check_lengths(int batch, int64_t max_length, const int64_t *lengths, std::string &err) {
-    for (int b = 0; b < batch; b++)
-        if (lengths[b] <= 0 || lengths[b] > max_length) {
-            char buf[128];
-            snprintf(buf, sizeof buf, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths[b], (long long)max_length);
-            err = buf;
-            return SE_ERR_ARG;
-        }
-    return 0;
-}
-
-inline void count_le(ChainPlan &p) {
-    p.le.assign((size_t)p.N + 1, 0);
-    for (int b = 0; b < p.B; b++) p.le[p.nseg[b]]++;
-    for (int k = 1; k <= p.N; k++) p.le[k] += p.le[k - 1];
-}
-
-}  // namespace plan_detail
-
 enum { kPlanFilled = 0, kPlanUniform = 1 };
 
 // One flag and one length per stream; `carried` = the streams whose state the engine holds (<= 0: none).  Returns kPlanFilled with p
@@ -93,7 +72,13 @@ enum { kPlanFilled = 0, kPlanUniform = 1 };
 // it), or an SE_ERR_* code with its text in err.
 inline int plan_chains(ChainPlan &p, long K, int batch, int64_t max_length, const int64_t *lengths, const uint8_t *flags, int carried,
                        int *uniform_flag, std::string &err) {
-    if (int rc = plan_detail::check_lengths(batch, max_length, lengths, err)) return rc;
+    for (int b = 0; b < batch; b++)
+        if (lengths[b] <= 0 || lengths[b] > max_length) {
+            char buf[128];
+            snprintf(buf, sizeof buf, "length of stream %d (%lld) outside (0, %lld]", b, (long long)lengths[b], (long long)max_length);
+            err = buf;
+            return SE_ERR_ARG;
+        }
     bool any = false, all = true, full = true;
     for (int b = 0; b < batch; b++) {
         any = any || flags[b];
@@ -125,30 +110,14 @@ inline int plan_chains(ChainPlan &p, long K, int batch, int64_t max_length, cons
     }
     std::stable_sort(idx.begin(), idx.begin() + B, [&](int a, int b) { return p.nseg[a] < p.nseg[b]; });
     memcpy(p.staging.data() + 3 * B, idx.data(), 2 * B * sizeof(int));
-    plan_detail::count_le(p);
+    p.le.assign((size_t)p.N + 1, 0);
+    for (int b = 0; b < batch; b++) p.le[p.nseg[b]]++;
+    for (int k = 1; k <= p.N; k++) p.le[k] += p.le[k - 1];
     p.saving = p.le[p.N - 1] > 0;
     // prefix compaction: the streams still running in segment n are a prefix of the batch when the SEGMENT COUNTS are non-increasing (a
     // reset stream has one lead more than a continuing one); the streams beyond the prefix are exactly those whose rows were saved
     p.compact = true;
     for (int b = 1; b < batch; b++) p.compact = p.compact && p.nseg[b] <= p.nseg[b - 1];
-    return kPlanFilled;
-}
-
-// One flag for the batch, one length per stream, every stream cut like the longest (common offset and strip), nothing saved: streams past
-// their end stop taking part only when the LENGTHS are non-increasing (the Python shim sorts a fresh batch).  The engine uploads the
-// lengths and sets len.
-inline int plan_ragged(ChainPlan &p, long K, int batch, int64_t max_length, const int64_t *lengths, int flag, std::string &err) {
-    if (int rc = plan_detail::check_lengths(batch, max_length, lengths, err)) return rc;
-    p = ChainPlan{};
-    p.B = batch;
-    p.N = (int)chunk_geometry(K, max_length, flag).nseg;
-    p.nseg.resize((size_t)batch);
-    p.compact = true;
-    for (int b = 0; b < batch; b++) {
-        p.nseg[b] = (int)chunk_geometry(K, lengths[b], flag).nseg;
-        p.compact = p.compact && (b == 0 || lengths[b] <= lengths[b - 1]);
-    }
-    plan_detail::count_le(p);
     return kPlanFilled;
 }
 

@@ -2,13 +2,11 @@
 // (one translation unit, so the kernels in the shared headers are defined once).
 // Reference: FullSubNet.forward / realtime_process(train=False), fullsubnet.py:769-824, 903-961.
 
-struct fsn_engine {
+struct fsn_engine : EngineHost {
     fsn_config c{};
-    int device = 0, T = 0, F = 0, M = 0, K = 0, N = 0, Kp = 0, SI = 0, NL = 0;
-    std::string err;
-    std::map<std::string, std::vector<float>> params;
+    int T = 0, F = 0, M = 0, K = 0, N = 0, Kp = 0, SI = 0, NL = 0;
     bool weights_ready = false;
-    se_engine *sig = nullptr;  // STFT/iSTFT tables and launches are shared with the CRN engine object
+    SigChain sig;  // STFT / iSTFT tables and plan (sig_chain.h)
     struct Model {
         int in = 0, inp = 0, H = 0, out = 0;
         DevBuf Wp[4], bias[4];      // per layer: bf16x3 planes of [W_ih | W_hh] (K padded to 32s), b_ih + b_hh
@@ -64,64 +62,6 @@ struct FsnTrainLayout {
 
 namespace {
 
-thread_local std::string g_fsn_create_error;
-
-int ffail(fsn_engine *e, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (e) e->err = buf;
-    else g_fsn_create_error = buf;
-    return code;
-}
-
-#define FHIP(e, call)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t _st = (call);                                                                                       \
-        if (_st != hipSuccess) return ffail(e, SE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_st), __FILE__, __LINE__); \
-    } while (0)
-
-int falloc(fsn_engine *e, DevBuf &b, size_t n) {
-    if (b.p && b.n >= n) return 0;
-    if (b.p) FHIP(e, hipFree(b.p));
-    b.p = nullptr; b.n = 0;
-    FHIP(e, hipMalloc(reinterpret_cast<void **>(&b.p), (n ? n : 1) * sizeof(float)));
-    b.n = n;
-    return 0;
-}
-
-int fupload(fsn_engine *e, DevBuf &b, const std::vector<float> &h) {
-    int rc = falloc(e, b, h.size());
-    if (rc) return rc;
-    FHIP(e, hipMemcpy(b.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-
-int fupload_planes(fsn_engine *e, DevBuf &b, const std::vector<float> &w) {  // three bf16 planes of w
-    const size_t n = w.size();
-    std::vector<uint16_t> planes(3 * n);
-    for (size_t i = 0; i < n; i++) {
-        const float x = w[i];
-        const uint16_t h = bf16_rne(x);
-        const float r1 = x - bf16_to_f32(h);
-        const uint16_t m = bf16_rne(r1);
-        planes[i] = h; planes[n + i] = m; planes[2 * n + i] = bf16_rne(r1 - bf16_to_f32(m));
-    }
-    int rc = falloc(e, b, (3 * n + 1) / 2);
-    if (rc) return rc;
-    FHIP(e, hipMemcpy(b.p, planes.data(), planes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    return 0;
-}
-
-const std::vector<float> *fparam(fsn_engine *e, const std::string &key, size_t expect) {
-    auto it = e->params.find(key);
-    if (it == e->params.end()) { ffail(e, SE_ERR_PARAM_MISSING, "parameter %s was never loaded", key.c_str()); return nullptr; }
-    if (it->second.size() != expect) { ffail(e, SE_ERR_SHAPE, "parameter %s has %zu elements, expected %zu", key.c_str(), it->second.size(), expect); return nullptr; }
-    return &it->second;
-}
-
 int fsn_prepare(fsn_engine *e) {
     if (e->weights_ready) return 0;
     struct { fsn_engine::Model *m; const char *name; } models[2] = {{&e->fb, "fb_model"}, {&e->sb, "sb_model"}};
@@ -131,10 +71,10 @@ int fsn_prepare(fsn_engine *e) {
         for (int l = 0; l < e->NL; l++) {
             const std::string p = std::string(mm.name) + ".sequence_model.", s = std::to_string(l);
             const int in = l == 0 ? m.in : H, inp = l == 0 ? m.inp : Hp;
-            auto *wih = fparam(e, p + "weight_ih_l" + s, 4 * (size_t)H * in);
-            auto *whh = fparam(e, p + "weight_hh_l" + s, 4 * (size_t)H * H);
-            auto *bih = fparam(e, p + "bias_ih_l" + s, 4 * (size_t)H);
-            auto *bhh = fparam(e, p + "bias_hh_l" + s, 4 * (size_t)H);
+            auto *wih = param(e, p + "weight_ih_l" + s, 4 * (size_t)H * in);
+            auto *whh = param(e, p + "weight_hh_l" + s, 4 * (size_t)H * H);
+            auto *bih = param(e, p + "bias_ih_l" + s, 4 * (size_t)H);
+            auto *bhh = param(e, p + "bias_hh_l" + s, 4 * (size_t)H);
             if (!wih || !whh || !bih || !bhh) return SE_ERR_PARAM_MISSING;
             const int Kt = inp + Hp;
             std::vector<float> cat((size_t)4 * H * Kt, 0.0f), bias(4 * (size_t)H);
@@ -144,13 +84,13 @@ int fsn_prepare(fsn_engine *e) {
                 bias[r] = (*bih)[r] + (*bhh)[r];
             }
             int rc;
-            if ((rc = fupload_planes(e, m.Wp[l], cat)) || (rc = fupload(e, m.bias[l], bias))) return rc;
+            if ((rc = upload_planes(e, m.Wp[l], cat, 0)) || (rc = dev_upload(e, m.bias[l], bias))) return rc;
         }
-        auto *fw = fparam(e, std::string(mm.name) + ".fc_output_layer.weight", (size_t)m.out * H);
-        auto *fbv = fparam(e, std::string(mm.name) + ".fc_output_layer.bias", m.out);
+        auto *fw = param(e, std::string(mm.name) + ".fc_output_layer.weight", (size_t)m.out * H);
+        auto *fbv = param(e, std::string(mm.name) + ".fc_output_layer.bias", m.out);
         if (!fw || !fbv) return SE_ERR_PARAM_MISSING;
         int rc;
-        if ((rc = fupload(e, m.fcw, *fw)) || (rc = fupload_planes(e, m.fcw_x, *fw)) || (rc = fupload(e, m.fcb, *fbv))) return rc;
+        if ((rc = dev_upload(e, m.fcw, *fw)) || (rc = upload_planes(e, m.fcw_x, *fw, 0)) || (rc = dev_upload(e, m.fcb, *fbv))) return rc;
     }
     e->weights_ready = true;
     return 0;
@@ -163,11 +103,11 @@ int fsn_train_save_window(fsn_engine *e, int mi, const float *x, long sR, long s
     fsn_engine::Model &m = mi ? e->sb : e->fb;
     const long S = L.S[mi], r0 = L.base[e->tr_n] * (mi ? e->F : 1);
     hipLaunchKernelGGL(k_fsn_save_rows, dim3(2048), dim3(256), 0, st, x, sR, sT, W, R, e->T, e->tr_ws + L.xs[mi] + r0 * W, S * W);
-    FHIP(e, hipGetLastError());
+    HIPCHECK(e, hipGetLastError());
     for (int l = 0; l < e->NL; l++) {
         const size_t n = (size_t)R * m.H;
-        FHIP(e, hipMemcpyAsync(e->tr_ws + L.hs[mi][l] + r0 * m.H, m.h[l][m.hcur[l]].p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-        FHIP(e, hipMemcpyAsync(e->tr_ws + L.cs[mi][l] + r0 * m.H, m.c[l].p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHECK(e, hipMemcpyAsync(e->tr_ws + L.hs[mi][l] + r0 * m.H, m.h[l][m.hcur[l]].p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHECK(e, hipMemcpyAsync(e->tr_ws + L.cs[mi][l] + r0 * m.H, m.c[l].p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return 0;
 }
@@ -242,7 +182,7 @@ int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long 
         hipLaunchKernelGGL(k_fsn_runmean, dim3((B + 255) / 256), dim3(256), 0, st, e->part_fb.p, e->nslot_fb, (double)M * T * F, e->mean_fb.p,
                            e->denom_fb.p, B, reinterpret_cast<int *>(e->step_fb.p));
         hipLaunchKernelGGL(k_fsn_scale, dim3(16, B), dim3(256), 0, st, e->mag.p, (long)T * Kp, e->denom_fb.p);
-        FHIP(e, hipGetLastError());
+        HIPCHECK(e, hipGetLastError());
     }
     if (e->tr) {  // training forward: the layer-0 input and the state entering the window
         int rc = fsn_train_save_window(e, 0, e->mag.p, (long)T * Kp, Kp, Kp, B, st);
@@ -256,17 +196,17 @@ int fsn_stage_fb(fsn_engine *e, const float *re, const float *im, long sB, long 
                                last ? e->fb_seq.p + (long)t * e->fb.H : nullptr, (long)T * e->fb.H, st, t);
         }
     }
-    FHIP(e, hipGetLastError());
+    HIPCHECK(e, hipGetLastError());
     {  // fc_output_layer + ReLU (fullsubnet.py:288-290): [B*T, H] -> [B*T, F]
         GemmX6Args g{e->fb_seq.p, reinterpret_cast<const __bf16 *>(e->fb.fcw_x.p), e->fb.fcb.p, e->fb_out.p, B * T, F, e->fb.H, (long)e->fb.H, (long)F, 1};
         hipLaunchKernelGGL(k_gemm_x<3>, dim3((F + kGemmBN - 1) / kGemmBN, (B * T + kGemmBM - 1) / kGemmBM), dim3(256), 0, st, g);
     }
-    FHIP(e, hipGetLastError());
+    HIPCHECK(e, hipGetLastError());
     if (e->tr) {  // fb_out [B*T][F] -> [T][S][F] (its sign is the ReLU's derivative)
         const FsnTrainLayout &L = *e->tr;
         hipLaunchKernelGGL(k_fsn_save_rows, dim3(1024), dim3(256), 0, st, e->fb_out.p, (long)T * F, (long)F, F, B, T,
                            e->tr_ws + L.fbo + L.base[e->tr_n] * F, L.S[0] * F);
-        FHIP(e, hipGetLastError());
+        HIPCHECK(e, hipGetLastError());
     }
     return 0;
 }
@@ -281,14 +221,14 @@ int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long 
     {  // sub-band input + its CumLayerNorm (fullsubnet.py:796-802)
         FsnUnfoldArgs a{e->mag.p, e->fb_out.p, e->sbin.p, e->part_sb.p, e->B, T, F, Kp, e->c.sb_neighbors, SI};
         hipLaunchKernelGGL(k_fsn_unfold, dim3(e->nslot_sb, B), dim3(256), 0, st, a);
-        if (consumed) FHIP(e, hipEventRecord(consumed, st));
+        if (consumed) HIPCHECK(e, hipEventRecord(consumed, st));
         hipLaunchKernelGGL(k_fsn_runmean, dim3((B + 255) / 256), dim3(256), 0, st, e->part_sb.p, e->nslot_sb, (double)F * SI * T, e->mean_sb.p,
                            e->denom_sb.p, B, reinterpret_cast<int *>(e->step_sb.p));
         hipLaunchKernelGGL(k_fsn_scale_sb, dim3(2048), dim3(256), 0, st, e->sbin.p, e->B, T, F, SI, e->denom_sb.p, B);
-        FHIP(e, hipGetLastError());
+        HIPCHECK(e, hipGetLastError());
     }
     if (e->tr) {  // training forward: the normalised sub-band input, this window's denominators, the state entering the window
-        FHIP(e, hipMemcpyAsync(e->tr_ws + e->tr->denom + e->tr->base[e->tr_n], e->denom_sb.p, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHECK(e, hipMemcpyAsync(e->tr_ws + e->tr->denom + e->tr->base[e->tr_n], e->denom_sb.p, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
         int rc = fsn_train_save_window(e, 1, e->sbin.p, SI, Rall * SI, SI, R, st);
         if (rc) return rc;
     }
@@ -298,23 +238,23 @@ int fsn_stage_sb(fsn_engine *e, const float *re, const float *im, long sB, long 
     for (int t = 0; t < T; t++) {  // sub-band LSTM over B*F rows + Linear(H -> 2)  (fullsubnet.py:812-814)
         for (int l = 0; l < e->NL; l++) {
             hipStream_t sl = wave && l == 1 ? e->side2 : st;
-            if (wave && l == 0 && t >= 2) FHIP(e, hipStreamWaitEvent(st, e->ev_l1[t - 2], 0));
-            if (wave && l == 1) FHIP(e, hipStreamWaitEvent(sl, e->ev_l0[t], 0));
+            if (wave && l == 0 && t >= 2) HIPCHECK(e, hipStreamWaitEvent(st, e->ev_l1[t - 2], 0));
+            if (wave && l == 1) HIPCHECK(e, hipStreamWaitEvent(sl, e->ev_l0[t], 0));
             if (l == 0) fsn_lstm_step(e, e->sb, 0, e->sbin.p + (long)t * Rall * SI, SI, SI, (SI + 31) & ~31, R, nullptr, 0, sl, t);
             else fsn_lstm_step(e, e->sb, l, e->sb.h[l - 1][e->sb.hcur[l - 1]].p, e->sb.H, e->sb.H, (e->sb.H + 31) & ~31, R, nullptr, 0, sl, t);
-            if (wave && l == 0) FHIP(e, hipEventRecord(e->ev_l0[t], st));
+            if (wave && l == 0) HIPCHECK(e, hipEventRecord(e->ev_l0[t], st));
         }
         const int ll = e->NL - 1;
         hipStream_t so = wave ? e->side2 : st;
         hipLaunchKernelGGL(k_fsn_sbfc, dim3(2048), dim3(256), 0, so, e->sb.h[ll][e->sb.hcur[ll]].p, e->sb.fcw.p, e->sb.fcb.p, e->mask.p, R, e->sb.H, T, t);
-        if (wave) FHIP(e, hipEventRecord(e->ev_l1[t], so));
+        if (wave) HIPCHECK(e, hipEventRecord(e->ev_l1[t], so));
     }
-    if (wave) FHIP(e, hipStreamWaitEvent(st, e->ev_l1[T - 1], 0));  // join: the mask needs every step's output
-    FHIP(e, hipGetLastError());
+    if (wave) HIPCHECK(e, hipStreamWaitEvent(st, e->ev_l1[T - 1], 0));  // join: the mask needs every step's output
+    HIPCHECK(e, hipGetLastError());
     {
         FsnMaskArgs a{e->mask.p, spec_out ? re : nullptr, spec_out ? im : nullptr, sB, sT, sF, spec_out, oB, oT, oF, crm_out, T, F};
         launch_k_fsn_mask(dim3((T * F + 255) / 256, B), st, a);
-        FHIP(e, hipGetLastError());
+        HIPCHECK(e, hipGetLastError());
     }
     return 0;
 }
@@ -327,8 +267,8 @@ int fsn_forward_dev(fsn_engine *e, const float *re, const float *im, long sB, lo
 }
 
 int fsn_reset_on(fsn_engine *e, int batch, hipStream_t st) {
-    if (!e || batch <= 0) return ffail(e, SE_ERR_ARG, "batch must be positive");
-    FHIP(e, hipSetDevice(e->device));
+    if (!e || batch <= 0) return fail(e, SE_ERR_ARG, "batch must be positive");
+    HIPCHECK(e, hipSetDevice(e->device));
     int rc = fsn_prepare(e);
     if (rc) return rc;
     const int B = batch, T = e->T, F = e->F, M = e->M, R = B * F;
@@ -336,29 +276,28 @@ int fsn_reset_on(fsn_engine *e, int batch, hipStream_t st) {
     e->nslot_fb = 8;
     e->nslot_sb = 32;
     // spec holds two windows: stage A of window n + 1 transforms while stage B of window n still masks its spectrum
-    if ((rc = falloc(e, e->spec, (size_t)2 * B * M * T * F * 2)) || (rc = falloc(e, e->maskspec, (size_t)B * T * F * 2)) ||
-        (rc = falloc(e, e->mag, (size_t)B * T * e->Kp)) || (rc = falloc(e, e->fb_seq, (size_t)B * T * e->fb.H)) ||
-        (rc = falloc(e, e->fb_out, (size_t)B * T * F)) || (rc = falloc(e, e->sbin, (size_t)T * R * e->SI)) ||
-        (rc = falloc(e, e->mask, (size_t)R * 2 * T)) || (rc = falloc(e, e->part_fb, (size_t)B * e->nslot_fb)) ||
-        (rc = falloc(e, e->part_sb, (size_t)B * e->nslot_sb)) || (rc = falloc(e, e->mean_fb, B)) || (rc = falloc(e, e->mean_sb, B)) ||
-        (rc = falloc(e, e->denom_fb, B)) || (rc = falloc(e, e->denom_sb, B)) || (rc = falloc(e, e->step_fb, B)) || (rc = falloc(e, e->step_sb, B)))
+    if ((rc = dev_alloc(e, e->spec, (size_t)2 * B * M * T * F * 2)) || (rc = dev_alloc(e, e->maskspec, (size_t)B * T * F * 2)) ||
+        (rc = dev_alloc(e, e->mag, (size_t)B * T * e->Kp)) || (rc = dev_alloc(e, e->fb_seq, (size_t)B * T * e->fb.H)) ||
+        (rc = dev_alloc(e, e->fb_out, (size_t)B * T * F)) || (rc = dev_alloc(e, e->sbin, (size_t)T * R * e->SI)) ||
+        (rc = dev_alloc(e, e->mask, (size_t)R * 2 * T)) || (rc = dev_alloc(e, e->part_fb, (size_t)B * e->nslot_fb)) ||
+        (rc = dev_alloc(e, e->part_sb, (size_t)B * e->nslot_sb)) || (rc = dev_alloc(e, e->mean_fb, B)) || (rc = dev_alloc(e, e->mean_sb, B)) ||
+        (rc = dev_alloc(e, e->denom_fb, B)) || (rc = dev_alloc(e, e->denom_sb, B)) || (rc = dev_alloc(e, e->step_fb, B)) || (rc = dev_alloc(e, e->step_sb, B)))
         return rc;
-    FHIP(e, hipMemsetAsync(e->mag.p, 0, (size_t)B * T * e->Kp * sizeof(float), st));  // padding columns must be zero
+    HIPCHECK(e, hipMemsetAsync(e->mag.p, 0, (size_t)B * T * e->Kp * sizeof(float), st));  // padding columns must be zero
     for (int l = 0; l < e->NL; l++) {
         for (int p = 0; p < 2; p++) {
-            if ((rc = falloc(e, e->fb.h[l][p], (size_t)B * e->fb.H)) || (rc = falloc(e, e->sb.h[l][p], (size_t)R * e->sb.H))) return rc;
-            FHIP(e, hipMemsetAsync(e->fb.h[l][p].p, 0, (size_t)B * e->fb.H * sizeof(float), st));
-            FHIP(e, hipMemsetAsync(e->sb.h[l][p].p, 0, (size_t)R * e->sb.H * sizeof(float), st));
+            if ((rc = dev_alloc(e, e->fb.h[l][p], (size_t)B * e->fb.H)) || (rc = dev_alloc(e, e->sb.h[l][p], (size_t)R * e->sb.H))) return rc;
+            HIPCHECK(e, hipMemsetAsync(e->fb.h[l][p].p, 0, (size_t)B * e->fb.H * sizeof(float), st));
+            HIPCHECK(e, hipMemsetAsync(e->sb.h[l][p].p, 0, (size_t)R * e->sb.H * sizeof(float), st));
         }
-        if ((rc = falloc(e, e->fb.c[l], (size_t)B * e->fb.H)) || (rc = falloc(e, e->sb.c[l], (size_t)R * e->sb.H))) return rc;
-        FHIP(e, hipMemsetAsync(e->fb.c[l].p, 0, (size_t)B * e->fb.H * sizeof(float), st));
-        FHIP(e, hipMemsetAsync(e->sb.c[l].p, 0, (size_t)R * e->sb.H * sizeof(float), st));
+        if ((rc = dev_alloc(e, e->fb.c[l], (size_t)B * e->fb.H)) || (rc = dev_alloc(e, e->sb.c[l], (size_t)R * e->sb.H))) return rc;
+        HIPCHECK(e, hipMemsetAsync(e->fb.c[l].p, 0, (size_t)B * e->fb.H * sizeof(float), st));
+        HIPCHECK(e, hipMemsetAsync(e->sb.c[l].p, 0, (size_t)R * e->sb.H * sizeof(float), st));
         e->fb.hcur[l] = e->sb.hcur[l] = 0;
     }
-    FHIP(e, hipMemsetAsync(e->step_fb.p, 0, (size_t)B * sizeof(int), st));  // both norms: no mean yet (CumLayerNorm.reset)
-    FHIP(e, hipMemsetAsync(e->step_sb.p, 0, (size_t)B * sizeof(int), st));
+    HIPCHECK(e, hipMemsetAsync(e->step_fb.p, 0, (size_t)B * sizeof(int), st));  // both norms: no mean yet (CumLayerNorm.reset)
+    HIPCHECK(e, hipMemsetAsync(e->step_sb.p, 0, (size_t)B * sizeof(int), st));
     e->Bact = 0;
-    e->sig->B = B;  // the shared STFT/iSTFT launchers size their grids from B
     return 0;
 }
 
@@ -381,27 +320,32 @@ static int fsn_state_rows_of(fsn_engine *e, int mi, Fn &&f) {
 
 extern "C" {
 
-const char *fsn_last_error(const fsn_engine *e) { return e ? e->err.c_str() : g_fsn_create_error.c_str(); }
+const char *fsn_last_error(const fsn_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
 int fsn_create(const fsn_config *cfg, int device, fsn_engine **out) {
-    if (!cfg || !out) return ffail(nullptr, SE_ERR_ARG, "null argument");
+    if (!cfg || !out) return fail(nullptr, SE_ERR_ARG, "null argument");
     *out = nullptr;
-    if (cfg->fb_neighbors != 0 || cfg->look_ahead != 0) return ffail(nullptr, SE_ERR_ARG, "only fb_num_neighbors = 0, look_ahead = 0 (config.yaml:154-157) are supported");
-    if (cfg->num_layers < 1 || cfg->num_layers > 4) return ffail(nullptr, SE_ERR_ARG, "num_layers %d out of range", cfg->num_layers);
-    if (cfg->fb_hidden % 8 || cfg->sb_hidden % 8 || cfg->fb_hidden <= 0 || cfg->sb_hidden <= 0) return ffail(nullptr, SE_ERR_ARG, "hidden sizes must be positive multiples of 8");
-    if ((2 * cfg->sb_neighbors + 2) % 4) return ffail(nullptr, SE_ERR_ARG, "sub-band input width 2*sb_num_neighbors+2 must be a multiple of 4");
-    if (cfg->precision != 0 && cfg->precision != 2) return ffail(nullptr, SE_ERR_ARG, "fsn precision %d unknown (0 fp32-accurate, 2 bf16x3)", cfg->precision);
-    // STFT tables / launchers: borrow a CRN engine object configured with the same STFT geometry
-    se_config sc{};
-    sc.num_levels = 4; for (int i = 0; i < 4; i++) sc.channels[i] = 8;
-    sc.num_freqs = cfg->num_freqs; sc.hidden = 16; sc.num_layers = 1; sc.num_inputs = cfg->num_mics; sc.kernel_size = 3;
-    sc.n_fft = cfg->n_fft; sc.win = cfg->win; sc.hop = cfg->hop; sc.segment_length = cfg->segment_length; sc.variant = 0;
-    se_engine *sig = nullptr;
-    int rc = se_create(&sc, device, &sig);
-    if (rc) { g_fsn_create_error = std::string("STFT setup: ") + se_last_error(nullptr); return rc; }
+    if (cfg->fb_neighbors != 0 || cfg->look_ahead != 0) return fail(nullptr, SE_ERR_ARG, "only fb_num_neighbors = 0, look_ahead = 0 (config.yaml:154-157) are supported");
+    if (cfg->num_layers < 1 || cfg->num_layers > 4) return fail(nullptr, SE_ERR_ARG, "num_layers %d out of range", cfg->num_layers);
+    if (cfg->fb_hidden % 8 || cfg->sb_hidden % 8 || cfg->fb_hidden <= 0 || cfg->sb_hidden <= 0) return fail(nullptr, SE_ERR_ARG, "hidden sizes must be positive multiples of 8");
+    if ((2 * cfg->sb_neighbors + 2) % 4) return fail(nullptr, SE_ERR_ARG, "sub-band input width 2*sb_num_neighbors+2 must be a multiple of 4");
+    if (cfg->precision != 0 && cfg->precision != 2) return fail(nullptr, SE_ERR_ARG, "fsn precision %d unknown (0 fp32-accurate, 2 bf16x3)", cfg->precision);
+    if (cfg->n_fft % 2 || cfg->num_freqs != cfg->n_fft / 2 + 1) return fail(nullptr, SE_ERR_ARG, "num_freqs must be n_fft/2+1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, SE_ERR_HIP, "no HIP device available: the engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(nullptr, SE_ERR_ARG, "device %d out of range (%d visible)", device, ndev);
     fsn_engine *e = new fsn_engine();
-    e->c = *cfg; e->device = device; e->sig = sig;
-    e->T = sig->T; e->F = cfg->num_freqs; e->M = cfg->num_mics; e->K = cfg->segment_length; e->N = cfg->n_fft; e->NL = cfg->num_layers;
+    std::string why;
+    if (int rc = sig_chain_create(e->sig, cfg->n_fft, cfg->win, cfg->hop, cfg->segment_length, device, why)) { delete e; return fail(nullptr, rc, "%s", why.c_str()); }
+    // the floor the engine has always had: inherited from the CRN geometry it used to be checked against, not FullSubNet's own
+    if (e->sig.T <= 16) {
+        sig_chain_destroy(e->sig);
+        delete e;
+        return fail(nullptr, SE_ERR_ARG, "segment_length %d at hop %d gives %d frames per segment: more than 16 frames are required", cfg->segment_length, cfg->hop,
+                    1 + cfg->segment_length / cfg->hop);
+    }
+    e->c = *cfg; e->device = device;
+    e->T = e->sig.T; e->F = cfg->num_freqs; e->M = cfg->num_mics; e->K = cfg->segment_length; e->N = cfg->n_fft; e->NL = cfg->num_layers;
     e->Kp = (cfg->num_freqs * cfg->num_mics + 31) & ~31;
     e->SI = 2 * cfg->sb_neighbors + 2;
     e->fb.in = cfg->num_freqs * cfg->num_mics; e->fb.inp = e->Kp; e->fb.H = cfg->fb_hidden; e->fb.out = cfg->num_freqs;
@@ -420,7 +364,7 @@ int fsn_create(const fsn_config *cfg, int device, fsn_engine **out) {
         e->ev_l0.assign(e->T, nullptr); e->ev_l1.assign(e->T, nullptr);
         for (int t = 0; t < e->T && ok; t++)
             ok = hipEventCreateWithFlags(&e->ev_l0[t], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&e->ev_l1[t], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { fsn_destroy(e); return ffail(nullptr, SE_ERR_HIP, "fsn_create: side stream / events: %s", hipGetErrorString(hipGetLastError())); }
+        if (!ok) { fsn_destroy(e); return fail(nullptr, SE_ERR_HIP, "fsn_create: side stream / events: %s", hipGetErrorString(hipGetLastError())); }
     }
     *out = e;
     return SE_OK;
@@ -449,12 +393,12 @@ void fsn_destroy(fsn_engine *e) {
     for (hipEvent_t ev : e->ev_l1) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {e->ev_fork, e->ev_ready[0], e->ev_ready[1], e->ev_consumed[0], e->ev_consumed[1], e->ev_done[0], e->ev_done[1]})
         if (ev) (void)hipEventDestroy(ev);
-    se_destroy(e->sig);
+    sig_chain_destroy(e->sig);
     delete e;
 }
 
 int fsn_load_param(fsn_engine *e, const char *key, const float *host_data, const int64_t *shape, int ndim) {
-    if (!e || !key || !host_data) return ffail(e, SE_ERR_ARG, "null argument");
+    if (!e || !key || !host_data) return fail(e, SE_ERR_ARG, "null argument");
     const std::string k(key);
     bool ok = false;
     for (const char *mname : {"fb_model.", "sb_model."}) {
@@ -467,27 +411,24 @@ int fsn_load_param(fsn_engine *e, const char *key, const float *host_data, const
                  (!strcmp(what, "weight_ih_l") || !strcmp(what, "weight_hh_l") || !strcmp(what, "bias_ih_l") || !strcmp(what, "bias_hh_l"));
         else ok = rest == "fc_output_layer.weight" || rest == "fc_output_layer.bias";
     }
-    if (!ok) return ffail(e, SE_ERR_KEY, "unknown parameter key %s", key);
-    size_t cnt = 1;
-    for (int i = 0; i < ndim; i++) cnt *= (size_t)shape[i];
-    e->params[k].assign(host_data, host_data + cnt);
+    if (!ok) return fail(e, SE_ERR_KEY, "unknown parameter key %s", key);
     e->weights_ready = false;
     e->train_ready = false;
-    return SE_OK;
+    return store_param(e, k, host_data, shape, ndim);
 }
 
 int fsn_reset(fsn_engine *e, int batch) {
     int rc = fsn_reset_on(e, batch, nullptr);
     if (rc) return rc;
-    FHIP(e, hipDeviceSynchronize());
+    HIPCHECK(e, hipDeviceSynchronize());
     return SE_OK;
 }
 
 // FullSubNet.forward: x [B, 2M, F, T] (re x M then im x M) -> crm [B, 2, F, T]
 int fsn_forward(fsn_engine *e, const float *x, float *crm, void *stream) {
-    if (!e || !x || !crm) return ffail(e, SE_ERR_ARG, "null argument");
-    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "fsn_forward before fsn_reset");
-    FHIP(e, hipSetDevice(e->device));
+    if (!e || !x || !crm) return fail(e, SE_ERR_ARG, "null argument");
+    if (e->B <= 0) return fail(e, SE_ERR_STATE, "fsn_forward before fsn_reset");
+    HIPCHECK(e, hipSetDevice(e->device));
     int rc = fsn_prepare(e);
     if (rc) return rc;
     const long F = e->F, T = e->T, M = e->M;
@@ -502,7 +443,7 @@ static int fsn_chain_rows(fsn_engine *e, unsigned which, int dir, StreamRange r,
         StateRowList rows;
         fsn_state_rows_of(e, mi, [&](float *live, DevBuf &carry, long words) { rows.add(live, carry.p, words); return 0; });
         rows.launch(st, dir, r.streams, r.count);
-        FHIP(e, hipGetLastError());
+        HIPCHECK(e, hipGetLastError());
     }
     return 0;
 }
@@ -510,7 +451,7 @@ static int fsn_chain_rows(fsn_engine *e, unsigned which, int dir, StreamRange r,
 static int fsn_alloc_carry(fsn_engine *e) {
     int rc = 0;
     for (int mi = 0; mi < 2 && !rc; mi++)
-        rc = fsn_state_rows_of(e, mi, [&](float *, DevBuf &carry, long words) { return falloc(e, carry, (size_t)e->B * words); });
+        rc = fsn_state_rows_of(e, mi, [&](float *, DevBuf &carry, long words) { return dev_alloc(e, carry, (size_t)e->B * words); });
     return rc;
 }
 
@@ -521,7 +462,7 @@ static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long 
                            const ChainPlan *ch) {
     int rc;
     const long K = e->K, P = K / 2;
-    if ((rc = falloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
+    if ((rc = dev_alloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
     const long F = e->F, T = e->T, M = e->M;
     cf2 *spec = reinterpret_cast<cf2 *>(e->spec.p);
     cf2 *ms = reinterpret_cast<cf2 *>(e->maskspec.p);
@@ -529,14 +470,14 @@ static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long 
     const bool piped = e->pipeline && e->side && Nseg > 1;
     hipStream_t sa = piped ? e->side : st;
     if (piped) {  // the side stream starts after whatever the caller's stream holds (reset, the previous call's tail)
-        FHIP(e, hipEventRecord(e->ev_fork, st));
-        FHIP(e, hipStreamWaitEvent(sa, e->ev_fork, 0));
+        HIPCHECK(e, hipEventRecord(e->ev_fork, st));
+        HIPCHECK(e, hipStreamWaitEvent(sa, e->ev_fork, 0));
     }
     struct Scope {  // a failing call leaves the engine usable: nothing of the plan outlives the call
         fsn_engine *e;
-        ~Scope() { e->Bact = 0; e->sig->row_len = e->sig->row_off = nullptr; }
+        ~Scope() { e->Bact = 0; }
     } scope{e};
-    if (ch) { e->sig->row_len = ch->len; e->sig->row_off = ch->off0; }
+    const SigRows rows = ch ? SigRows{ch->len, ch->off0} : SigRows{};
     for (long n = 0; n < Nseg; n++) {
         const long off = n * P + (ch ? 0 : off0);
         const int slot = piped ? (int)(n & 1) : 0;
@@ -545,40 +486,39 @@ static int fsn_run_windows(fsn_engine *e, const float *mixture, int batch, long 
         const StreamRange last = ch ? ch->ending(n) : StreamRange{nullptr, 0};  // the streams whose last window this is
         if (ch) e->Bact = bact;
         if (piped) {
-            if (n >= 2) FHIP(e, hipStreamWaitEvent(sa, e->ev_done[slot], 0));          // window n - 2 has masked spectrum[slot]
-            if (n >= 1) FHIP(e, hipStreamWaitEvent(sa, e->ev_consumed[slot ^ 1], 0));  // window n - 1 has unfolded mag / fb_out
+            if (n >= 2) HIPCHECK(e, hipStreamWaitEvent(sa, e->ev_done[slot], 0));          // window n - 2 has masked spectrum[slot]
+            if (n >= 1) HIPCHECK(e, hipStreamWaitEvent(sa, e->ev_consumed[slot ^ 1], 0));  // window n - 1 has unfolded mag / fb_out
         }
-        if (launch_stft(e->sig, mixture, (long)M * length, length, (int)M, off, length, bact * (int)M, spec + slot * (spec_floats / 2), T * F, F, 1, sa))
-            return ffail(e, SE_ERR_HIP, "stft: %s", se_last_error(e->sig));
+        HIPCHECK(e, sig_stft(e->sig, mixture, (long)M * length, length, (int)M, off, length, rows, bact * (int)M, spec + slot * (spec_floats / 2), T * F, F, 1, sa));
         if ((rc = fsn_stage_fb(e, sp, sp + 1, 2 * M * T * F, 2 * T * F, 2 * F, 2, sa))) return rc;
         // the full-band stage of window n + 1 runs ahead on `side`: the full-band rows of the streams that end here are kept now, on `side`
         if ((rc = fsn_chain_rows(e, 1u, 0, last, sa))) return rc;
         if (piped) {
-            FHIP(e, hipEventRecord(e->ev_ready[slot], sa));
-            FHIP(e, hipStreamWaitEvent(st, e->ev_ready[slot], 0));
+            HIPCHECK(e, hipEventRecord(e->ev_ready[slot], sa));
+            HIPCHECK(e, hipStreamWaitEvent(st, e->ev_ready[slot], 0));
         }
         if ((rc = fsn_stage_sb(e, sp, sp + 1, 2 * M * T * F, 2 * F, 2, nullptr, ms, T * F, F, 1, st, piped ? e->ev_consumed[slot] : nullptr))) return rc;
         if ((rc = fsn_chain_rows(e, 2u, 0, last, st))) return rc;  // stage B has joined `side2`
-        if (launch_istft(e->sig, ms, T * F, F, 1, bact, e->yseg.p + n * K, Nseg * K, st)) return ffail(e, SE_ERR_HIP, "istft: %s", se_last_error(e->sig));
-        if (piped) FHIP(e, hipEventRecord(e->ev_done[slot], st));
+        HIPCHECK(e, sig_istft(e->sig, ms, T * F, F, 1, bact, e->yseg.p + n * K, Nseg * K, st));
+        if (piped) HIPCHECK(e, hipEventRecord(e->ev_done[slot], st));
     }
     // the streams that ended before the longest one get their own state back (the last stage B waited for everything on `side`)
     if (ch && (rc = fsn_chain_rows(e, 3u, 1, ch->ended_early(), st))) return rc;
-    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, ch ? ch->len : nullptr,
+    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, rows.len,
                          ch ? ch->skip : nullptr);
-    FHIP(e, hipGetLastError());
+    HIPCHECK(e, hipGetLastError());
     return SE_OK;
 }
 
 // FullSubNet.realtime_process(mixture, source, flag, train=False)[0]: mixture [B, M, L] -> [B, L]
 int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
-    if (!e || !mixture || !out || batch <= 0 || length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !mixture || !out || batch <= 0 || length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
     if (!flag) { if ((rc = fsn_reset_on(e, batch, st))) return rc; }
     else {
-        if (e->B != batch) return ffail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
-        FHIP(e, hipSetDevice(e->device));
+        if (e->B != batch) return fail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
+        HIPCHECK(e, hipSetDevice(e->device));
         if ((rc = fsn_prepare(e))) return rc;
     }
     const ChunkGeometry g = chunk_geometry(e->K, length, flag);
@@ -588,24 +528,21 @@ int fsn_realtime_process(fsn_engine *e, const float *mixture, int batch, int64_t
 // A batch of chunk chains (include/se_engine.h): reset or prepare, plan (chain_plan.h), upload, zero the flag-0 rows and counters, run
 int fsn_realtime_process_chains(fsn_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host,
                                 float *out, void *stream) {
-    if (!e || !mixture || !out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !mixture || !out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     ChainPlan plan;
     std::string err;
     int uniform_flag = 0;
     int rc = plan_chains(plan, e->K, batch, max_length, lengths_host, flags_host, e->B, &uniform_flag, err);
     if (rc == kPlanUniform) return fsn_realtime_process(e, mixture, batch, max_length, uniform_flag, out, stream);
-    if (rc) return ffail(e, rc, "%s", err.c_str());
+    if (rc) return fail(e, rc, "%s", err.c_str());
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!plan.continues()) rc = fsn_reset_on(e, batch, st);
     else {
-        FHIP(e, hipSetDevice(e->device));
+        HIPCHECK(e, hipSetDevice(e->device));
         rc = fsn_prepare(e);
     }
     if (rc) return rc;
-    if ((rc = falloc(e, e->plan_dev, plan.staging_floats())) || (rc = fsn_alloc_carry(e))) return rc;
-    FHIP(e, hipMemcpyAsync(e->plan_dev.p, plan.staging.data(), plan.staging.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    FHIP(e, hipStreamSynchronize(st));  // the staging vector and the host arrays live for the call only
-    plan.carve(e->plan_dev.p);
+    if ((rc = fsn_alloc_carry(e)) || (rc = upload_plan(e, e->plan_dev, plan, st))) return rc;
     // a reset among continuing streams: zero those streams' rows and counters (fsn_reset_stream for any number of streams in two launches)
     if (plan.continues() && (rc = fsn_chain_rows(e, 3u, 2, plan.reset_streams(), st))) return rc;
     return fsn_run_windows(e, mixture, batch, max_length, plan.N, 0, 0, out, st, &plan);
@@ -614,14 +551,14 @@ int fsn_realtime_process_chains(fsn_engine *e, const float *mixture, int batch, 
 // reset_state + both CumLayerNorm.reset() (fullsubnet.py:826-832, 203-205) for ONE stream of the carried batch
 int fsn_reset_stream(fsn_engine *e, int stream_index, void *stream) {
     if (!e) return SE_ERR_ARG;
-    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "fsn_reset_stream before fsn_reset");
-    if (stream_index < 0 || stream_index >= e->B) return ffail(e, SE_ERR_ARG, "stream index %d outside the batch of %d", stream_index, e->B);
-    FHIP(e, hipSetDevice(e->device));
+    if (e->B <= 0) return fail(e, SE_ERR_STATE, "fsn_reset_stream before fsn_reset");
+    if (stream_index < 0 || stream_index >= e->B) return fail(e, SE_ERR_ARG, "stream index %d outside the batch of %d", stream_index, e->B);
+    HIPCHECK(e, hipSetDevice(e->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = 0;
     for (int mi = 0; mi < 2 && !rc; mi++)
         rc = fsn_state_rows_of(e, mi, [&](float *live, DevBuf &, long words) {
-            FHIP(e, hipMemsetAsync(live + words * stream_index, 0, (size_t)words * sizeof(float), st));
+            HIPCHECK(e, hipMemsetAsync(live + words * stream_index, 0, (size_t)words * sizeof(float), st));
             return 0;
         });
     return rc;
@@ -644,13 +581,13 @@ static int fsn_state_of(fsn_engine *e, const char *name, float *ptr[4], size_t *
     else if (!strcmp(name, "mean_sb")) ptr[0] = e->mean_sb.p;
     else if (!strcmp(name, "step_fb")) { ptr[0] = e->step_fb.p; *is_step = true; }
     else if (!strcmp(name, "step_sb")) { ptr[0] = e->step_sb.p; *is_step = true; }
-    else return ffail(e, SE_ERR_KEY, "unknown state %s", name);
+    else return fail(e, SE_ERR_KEY, "unknown state %s", name);
     return 0;
 }
 
 int fsn_export_state(fsn_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream) {
-    if (!e || !name || !host_out) return ffail(e, SE_ERR_ARG, "null argument");
-    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "no state: call fsn_reset first");
+    if (!e || !name || !host_out) return fail(e, SE_ERR_ARG, "null argument");
+    if (e->B <= 0) return fail(e, SE_ERR_STATE, "no state: call fsn_reset first");
     float *ptr[4];
     size_t per = 0;
     int layers = 0, rc;
@@ -658,53 +595,53 @@ int fsn_export_state(fsn_engine *e, const char *name, float *host_out, int64_t c
     if ((rc = fsn_state_of(e, name, ptr, &per, &layers, &is_step))) return rc;
     const size_t n = per * layers;
     if (count) *count = (int64_t)n;
-    if ((int64_t)n > capacity) return ffail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
-    FHIP(e, hipSetDevice(e->device));
-    FHIP(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    for (int l = 0; l < layers; l++) FHIP(e, hipMemcpy(host_out + (size_t)l * per, ptr[l], per * sizeof(float), hipMemcpyDeviceToHost));
+    if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
+    HIPCHECK(e, hipSetDevice(e->device));
+    HIPCHECK(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    for (int l = 0; l < layers; l++) HIPCHECK(e, hipMemcpy(host_out + (size_t)l * per, ptr[l], per * sizeof(float), hipMemcpyDeviceToHost));
     if (is_step)  // the counters are ints on the device, small integers held exactly as floats outside
         for (size_t i = 0; i < n; i++) { int v; memcpy(&v, host_out + i, sizeof v); host_out[i] = (float)v; }
     return SE_OK;
 }
 
 int fsn_import_state(fsn_engine *e, const char *name, const float *host_in, int64_t count, void *stream) {
-    if (!e || !name || !host_in) return ffail(e, SE_ERR_ARG, "null argument");
-    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "no state: call fsn_reset first");
+    if (!e || !name || !host_in) return fail(e, SE_ERR_ARG, "null argument");
+    if (e->B <= 0) return fail(e, SE_ERR_STATE, "no state: call fsn_reset first");
     float *ptr[4];
     size_t per = 0;
     int layers = 0, rc;
     bool is_step = false;
     if ((rc = fsn_state_of(e, name, ptr, &per, &layers, &is_step))) return rc;
-    if (count != (int64_t)(per * layers)) return ffail(e, SE_ERR_SHAPE, "state %s needs %zu floats", name, per * layers);
-    FHIP(e, hipSetDevice(e->device));
-    FHIP(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    if (count != (int64_t)(per * layers)) return fail(e, SE_ERR_SHAPE, "state %s needs %zu floats", name, per * layers);
+    HIPCHECK(e, hipSetDevice(e->device));
+    HIPCHECK(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     if (is_step) {
         std::vector<int> v(per);
         for (size_t i = 0; i < per; i++) {
             if (!(host_in[i] >= 0.0f && host_in[i] <= 80.0f) || host_in[i] != (float)(int)host_in[i])
-                return ffail(e, SE_ERR_ARG, "state %s: %g is not a step count in 0 .. 80", name, (double)host_in[i]);
+                return fail(e, SE_ERR_ARG, "state %s: %g is not a step count in 0 .. 80", name, (double)host_in[i]);
             v[i] = (int)host_in[i];
         }
-        FHIP(e, hipMemcpy(ptr[0], v.data(), per * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHECK(e, hipMemcpy(ptr[0], v.data(), per * sizeof(int), hipMemcpyHostToDevice));
         return SE_OK;
     }
-    for (int l = 0; l < layers; l++) FHIP(e, hipMemcpy(ptr[l], host_in + (size_t)l * per, per * sizeof(float), hipMemcpyHostToDevice));
+    for (int l = 0; l < layers; l++) HIPCHECK(e, hipMemcpy(ptr[l], host_in + (size_t)l * per, per * sizeof(float), hipMemcpyHostToDevice));
     return SE_OK;
 }
 
 int fsn_read_tap(fsn_engine *e, const char *name, float *host_out, int64_t capacity, int64_t *count, void *stream) {
-    if (!e || !name || !host_out) return ffail(e, SE_ERR_ARG, "null argument");
-    if (e->B <= 0) return ffail(e, SE_ERR_STATE, "no forward has run");
+    if (!e || !name || !host_out) return fail(e, SE_ERR_ARG, "null argument");
+    if (e->B <= 0) return fail(e, SE_ERR_STATE, "no forward has run");
     const float *src = nullptr;
     size_t n = 0;
     if (!strcmp(name, "fb_out")) { src = e->fb_out.p; n = (size_t)e->B * e->T * e->F; }          // [B*T][F]
     else if (!strcmp(name, "mean_fb")) { src = e->mean_fb.p; n = e->B; }
     else if (!strcmp(name, "mean_sb")) { src = e->mean_sb.p; n = e->B; }
-    else return ffail(e, SE_ERR_KEY, "unknown tap %s", name);
+    else return fail(e, SE_ERR_KEY, "unknown tap %s", name);
     if (count) *count = (int64_t)n;
-    if ((int64_t)n > capacity) return ffail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
-    FHIP(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    FHIP(e, hipMemcpy(host_out, src, n * sizeof(float), hipMemcpyDeviceToHost));
+    if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
+    HIPCHECK(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    HIPCHECK(e, hipMemcpy(host_out, src, n * sizeof(float), hipMemcpyDeviceToHost));
     return SE_OK;
 }
 

@@ -75,7 +75,7 @@ int fsn_train_plan_chains(fsn_engine *e, int carried, int batch, int64_t max_len
     std::string err;
     const int rc = plan_chains(c.plan, e->K, batch, max_length, lengths, flags, carried, uniform_flag, err);
     if (rc == kPlanUniform) { *nseg = (int)chunk_geometry(e->K, max_length, *uniform_flag).nseg; return rc; }
-    if (rc) return ffail(e, rc, "%s", err.c_str());
+    if (rc) return fail(e, rc, "%s", err.c_str());
     const ChainPlan &p = c.plan;
     std::vector<long> base((size_t)p.N + 1, 0);
     for (int n = 0; n < p.N; n++) base[n + 1] = base[n] + p.bact(n);
@@ -101,31 +101,31 @@ int fsn_prepare_train(fsn_engine *e) {
         for (int l = 0; l < e->NL; l++) {
             const std::string p = std::string(mm.name) + ".sequence_model.", s = std::to_string(l);
             const int in = l == 0 ? m.in : H;
-            auto *wih = fparam(e, p + "weight_ih_l" + s, 4 * (size_t)H * in);
-            auto *whh = fparam(e, p + "weight_hh_l" + s, 4 * (size_t)H * H);
+            auto *wih = param(e, p + "weight_ih_l" + s, 4 * (size_t)H * in);
+            auto *whh = param(e, p + "weight_hh_l" + s, 4 * (size_t)H * H);
             if (!wih || !whh) return SE_ERR_PARAM_MISSING;
             std::vector<float> t((size_t)H * 4 * H);
             for (int r = 0; r < 4 * H; r++)
                 for (int k = 0; k < H; k++) t[(size_t)k * 4 * H + r] = (*whh)[(size_t)r * H + k];
-            if ((rc = fupload(e, m.whh_t[l], t))) return rc;
+            if ((rc = dev_upload(e, m.whh_t[l], t))) return rc;
             if (l > 0) {
                 for (int r = 0; r < 4 * H; r++)
                     for (int k = 0; k < H; k++) t[(size_t)k * 4 * H + r] = (*wih)[(size_t)r * H + k];
-                if ((rc = fupload(e, m.wih_t[l], t))) return rc;
+                if ((rc = dev_upload(e, m.wih_t[l], t))) return rc;
             } else if (&m == &e->sb) {  // the sub-band input's last column is fb_out (fb_num_neighbors = 0): the only one with a gradient
                 std::vector<float> col(4 * (size_t)H);
                 for (int r = 0; r < 4 * H; r++) col[r] = (*wih)[(size_t)r * in + in - 1];
-                if ((rc = fupload(e, m.wcol, col))) return rc;
+                if ((rc = dev_upload(e, m.wcol, col))) return rc;
             }
         }
     }
     const int F = e->F, Fp = (F + 7) & ~7, Hf = e->fb.H;
-    auto *fw = fparam(e, "fb_model.fc_output_layer.weight", (size_t)F * Hf);
+    auto *fw = param(e, "fb_model.fc_output_layer.weight", (size_t)F * Hf);
     if (!fw) return SE_ERR_PARAM_MISSING;
     std::vector<float> t((size_t)Hf * Fp, 0.0f);
     for (int f = 0; f < F; f++)
         for (int k = 0; k < Hf; k++) t[(size_t)k * Fp + f] = (*fw)[(size_t)f * Hf + k];
-    if ((rc = fupload(e, e->fb.fcw_t, t))) return rc;
+    if ((rc = dev_upload(e, e->fb.fcw_t, t))) return rc;
     e->train_ready = true;
     return 0;
 }
@@ -158,13 +158,13 @@ int fsn_train_windows(fsn_engine *e, const float *spec, int batch, const FsnTrai
         // mean(sqrt(EPS)) + EPS > 0, so nothing non-finite can arise from them.
         if (!ch->compact)
             for (int b = 0; b < batch; b++)
-                if (ch->nseg[b] <= n) FHIP(e, hipMemsetAsync(crm + (size_t)b * 2 * F * T, 0, (size_t)2 * F * T * sizeof(float), st));
+                if (ch->nseg[b] <= n) HIPCHECK(e, hipMemsetAsync(crm + (size_t)b * 2 * F * T, 0, (size_t)2 * F * T * sizeof(float), st));
     }
     if (ch && (rc = fsn_chain_rows(e, 3u, 1, ch->ended_early(), st))) return rc;
     return 0;
 }
 
-int tchk(fsn_engine *e, int rc) { return rc ? ffail(e, rc, "%s", se_train_last_error()) : 0; }
+int tchk(fsn_engine *e, int rc) { return rc ? fail(e, rc, "%s", se_train_last_error()) : 0; }
 
 // all T steps of layer l of model mi, last step first; dG of every step stays in L.dg for the weight gradients
 int fsn_bptt(fsn_engine *e, const FsnTrainLayout &L, float *ws, int mi, int l, const float *dout, const float *dm, const float *wfc, hipStream_t st) {
@@ -186,7 +186,7 @@ int fsn_bptt(fsn_engine *e, const FsnTrainLayout &L, float *ws, int mi, int l, c
         a.S = (int)S; a.H = (int)H;
         hipLaunchKernelGGL(k_lstm_bwd_step, grid, dim3(256), 0, st, a);
     }
-    FHIP(e, hipGetLastError());
+    HIPCHECK(e, hipGetLastError());
     return 0;
 }
 
@@ -196,7 +196,7 @@ int fsn_wgrad(fsn_engine *e, const FsnTrainLayout &L, float *ws, const float *A,
     int ns = 0, rc;
     if ((rc = tchk(e, se_train_gemm_tn_det(A, X, ws + L.wsum, &ns, R, Na, Nb, st)))) return rc;
     if ((rc = tchk(e, se_train_colsum(ws + L.wsum, ws + L.tmp, Na * Nb, nullptr, nullptr, 0, nullptr, nullptr, 0, ns, 0, st)))) return rc;
-    FHIP(e, hipMemcpy2DAsync(out, (size_t)cols * sizeof(float), ws + L.tmp, (size_t)Nb * sizeof(float), (size_t)cols * sizeof(float), rows,
+    HIPCHECK(e, hipMemcpy2DAsync(out, (size_t)cols * sizeof(float), ws + L.tmp, (size_t)Nb * sizeof(float), (size_t)cols * sizeof(float), rows,
                              hipMemcpyDeviceToDevice, st));
     return 0;
 }
@@ -206,7 +206,7 @@ int fsn_bgrad(fsn_engine *e, const FsnTrainLayout &L, float *ws, const float *x,
     int rc;
     if ((rc = tchk(e, se_train_colsum_tall(x, R, ld, ws + L.csum, ws + L.tmp, 0, st)))) return rc;
     for (float *o : {out1, out2})
-        if (o) FHIP(e, hipMemcpyAsync(o, ws + L.tmp, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (o) HIPCHECK(e, hipMemcpyAsync(o, ws + L.tmp, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
@@ -217,19 +217,19 @@ int fsn_train_bwd_rows(fsn_engine *e, const float *dcrm, const FsnTrainLayout &L
 extern "C" {
 
 int64_t fsn_train_ws_bytes(fsn_engine *e, int batch, int nseg) {
-    if (!e || batch <= 0 || nseg <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || batch <= 0 || nseg <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     FsnTrainLayout L;
     fsn_train_plan(e, batch, nseg, L);
     return (int64_t)(L.total * sizeof(float));
 }
 
 int fsn_train_fwd(fsn_engine *e, const float *spec, int batch, int nseg, int flag, void *ws, float *crm_out, void *stream) {
-    if (!e || !spec || !ws || !crm_out || batch <= 0 || nseg <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !spec || !ws || !crm_out || batch <= 0 || nseg <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    FHIP(e, hipSetDevice(e->device));
+    HIPCHECK(e, hipSetDevice(e->device));
     int rc;
     if (!flag) { if ((rc = fsn_reset_on(e, batch, st))) return rc; }
-    else if (e->B != batch) return ffail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
+    else if (e->B != batch) return fail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
     if ((rc = fsn_prepare(e))) return rc;
     FsnTrainLayout L;
     fsn_train_plan(e, batch, nseg, L);
@@ -237,7 +237,7 @@ int fsn_train_fwd(fsn_engine *e, const float *spec, int batch, int nseg, int fla
 }
 
 int64_t fsn_train_ws_bytes_chains(fsn_engine *e, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host) {
-    if (!e || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     FsnTrainChains c;
     int nseg = 0, uflag = 0;
     const int rc = fsn_train_plan_chains(e, e->B, batch, max_length, lengths_host, flags_host, c, &nseg, &uflag);
@@ -249,7 +249,7 @@ int64_t fsn_train_ws_bytes_chains(fsn_engine *e, int batch, int64_t max_length, 
 // reset or prepare, plan, upload the header, zero the flag-0 rows and counters among continuing streams, run the windows
 int fsn_train_fwd_chains(fsn_engine *e, const float *spec, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host, void *ws,
                          float *crm_out, void *stream) {
-    if (!e || !spec || !ws || !crm_out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !spec || !ws || !crm_out || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     FsnTrainChains c;
     int nseg = 0, uflag = 0;
     int rc = fsn_train_plan_chains(e, e->B, batch, max_length, lengths_host, flags_host, c, &nseg, &uflag);
@@ -259,7 +259,7 @@ int fsn_train_fwd_chains(fsn_engine *e, const float *spec, int batch, int64_t ma
     ChainPlan &plan = c.plan;
     if (!plan.continues()) rc = fsn_reset_on(e, batch, st);
     else {
-        FHIP(e, hipSetDevice(e->device));
+        HIPCHECK(e, hipSetDevice(e->device));
         rc = fsn_prepare(e);
     }
     if (rc || (rc = fsn_alloc_carry(e))) return rc;
@@ -267,17 +267,17 @@ int fsn_train_fwd_chains(fsn_engine *e, const float *spec, int batch, int64_t ma
     std::vector<int32_t> hdr(plan.staging_floats() + c.rowmap.size());
     memcpy(hdr.data(), plan.staging.data(), plan.staging.size() * sizeof(int64_t));
     if (c.packed()) memcpy(hdr.data() + plan.staging_floats(), c.rowmap.data(), c.rowmap.size() * sizeof(int));
-    FHIP(e, hipMemcpyAsync(wsf + c.L.hdr, hdr.data(), hdr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    FHIP(e, hipStreamSynchronize(st));  // the header and the host arrays live for the call only
+    HIPCHECK(e, hipMemcpyAsync(wsf + c.L.hdr, hdr.data(), hdr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(e, hipStreamSynchronize(st));  // the header and the host arrays live for the call only
     plan.carve(wsf + c.L.hdr);
     if (plan.continues() && (rc = fsn_chain_rows(e, 3u, 2, plan.reset_streams(), st))) return rc;
     // dead windows (n >= the stream's own count) hold exact zeros: the packed route never writes them, the dense route clears them
-    FHIP(e, hipMemsetAsync(crm_out, 0, (size_t)plan.N * batch * 2 * e->F * e->T * sizeof(float), st));
+    HIPCHECK(e, hipMemsetAsync(crm_out, 0, (size_t)plan.N * batch * 2 * e->F * e->T * sizeof(float), st));
     return fsn_train_windows(e, spec, batch, c.L, wsf, crm_out, st, &plan);
 }
 
 int fsn_train_bwd(fsn_engine *e, const float *dcrm, int batch, int nseg, void *wsp, float *const *grads, int ngrads, void *stream) {
-    if (!e || !dcrm || !wsp || !grads || batch <= 0 || nseg <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !dcrm || !wsp || !grads || batch <= 0 || nseg <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     FsnTrainLayout L;
     fsn_train_plan(e, batch, nseg, L);
     return fsn_train_bwd_rows(e, dcrm, L, nullptr, wsp, grads, ngrads, stream);
@@ -285,7 +285,7 @@ int fsn_train_bwd(fsn_engine *e, const float *dcrm, int batch, int nseg, void *w
 
 int fsn_train_bwd_chains(fsn_engine *e, const float *dcrm, int batch, int64_t max_length, const int64_t *lengths_host, const uint8_t *flags_host, void *wsp,
                          float *const *grads, int ngrads, void *stream) {
-    if (!e || !dcrm || !wsp || !grads || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return ffail(e, SE_ERR_ARG, "bad argument");
+    if (!e || !dcrm || !wsp || !grads || !lengths_host || !flags_host || batch <= 0 || max_length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     FsnTrainChains c;
     int nseg = 0, uflag = 0;
     const int rc = fsn_train_plan_chains(e, batch, batch, max_length, lengths_host, flags_host, c, &nseg, &uflag);
@@ -303,11 +303,11 @@ namespace {
 // the backward over the L.S[0] rows of the layout (dense or packed: the kernels see a flat S); rowmap: device, packed row -> n*B + b
 int fsn_train_bwd_rows(fsn_engine *e, const float *dcrm, const FsnTrainLayout &L, const int *rowmap, void *wsp, float *const *grads, int ngrads, void *stream) {
     const int NL = e->NL;
-    if (ngrads != 2 * (4 * NL + 2)) return ffail(e, SE_ERR_ARG, "expected %d gradient pointers, got %d", 2 * (4 * NL + 2), ngrads);
+    if (ngrads != 2 * (4 * NL + 2)) return fail(e, SE_ERR_ARG, "expected %d gradient pointers, got %d", 2 * (4 * NL + 2), ngrads);
     for (int i = 0; i < ngrads; i++)
-        if (!grads[i]) return ffail(e, SE_ERR_ARG, "gradient pointer %d is null", i);
+        if (!grads[i]) return fail(e, SE_ERR_ARG, "gradient pointer %d is null", i);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    FHIP(e, hipSetDevice(e->device));
+    HIPCHECK(e, hipSetDevice(e->device));
     int rc;
     if ((rc = fsn_prepare_train(e))) return rc;
     float *ws = static_cast<float *>(wsp);
@@ -317,7 +317,7 @@ int fsn_train_bwd_rows(fsn_engine *e, const float *dcrm, const FsnTrainLayout &L
 
     // sub band: Linear(H -> 2) (no activation) over the last layer, then the layers top down
     hipLaunchKernelGGL(k_fsn_gather_dm, dim3(2048), dim3(256), 0, st, dcrm, ws + L.dm, rowmap, S0, F, T);
-    FHIP(e, hipGetLastError());
+    HIPCHECK(e, hipGetLastError());
     if ((rc = fsn_wgrad(e, L, ws, ws + L.dm, ws + L.hs[1][NL - 1] + S1 * Hs, R1, 2, Hs, gsb[4 * NL], 2, Hs, st))) return rc;
     if ((rc = fsn_bgrad(e, L, ws, ws + L.dm, R1, 2, 2, gsb[4 * NL + 1], nullptr, st))) return rc;
     for (int l = NL - 1; l >= 0; l--) {
@@ -332,9 +332,9 @@ int fsn_train_bwd_rows(fsn_engine *e, const float *dcrm, const FsnTrainLayout &L
         if (l > 0) {
             if ((rc = tchk(e, se_train_gemm(dg, e->sb.wih_t[l].p, nullptr, ws + L.dx, (int)R1, Hs, 4 * Hs, 0, st)))) return rc;
         } else {  // d fb_out through the sub-band CumLayerNorm and the full-band ReLU
-            FHIP(e, hipMemsetAsync(ws + L.dpre, 0, (size_t)R0 * Fp * sizeof(float), st));
+            HIPCHECK(e, hipMemsetAsync(ws + L.dpre, 0, (size_t)R0 * Fp * sizeof(float), st));
             hipLaunchKernelGGL(k_fsn_dfb, dim3(4096), dim3(256), 0, st, dg, e->sb.wcol.p, ws + L.denom, ws + L.fbo, ws + L.dpre, S0, F, T, 4 * Hs, Fp);
-            FHIP(e, hipGetLastError());
+            HIPCHECK(e, hipGetLastError());
         }
     }
     // full band: Linear(H -> F) + ReLU over the last layer, then the layers top down (the input |X| carries no gradient)

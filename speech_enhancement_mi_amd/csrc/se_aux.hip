@@ -10,11 +10,17 @@
 // no packed-FP32 instruction, cost the same time (STFT 56 vs 57 us) and are exact under co-execution (0 of 800 launches
 // differed; tests/test_gpu_parity.py::test_fft_kernels_exact_under_coexecution and tests/test_isa_inventory.py keep it so).
 #include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
 #define SE_AUX_KERNELS 1
+#include "../../include/se_engine.h"
 #include "fft_lds.h"
 #include "norm.hip.h"
 #include "stft.hip.h"
 #include "fsn_mask.hip.h"
+#include "sig_chain.h"
 
 namespace se {
 
@@ -40,6 +46,68 @@ void aux_set_fft_lds(int stft_bytes, int istft_bytes) {
     stft_bytes = cur_stft; istft_bytes = cur_istft;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft), hipFuncAttributeMaxDynamicSharedMemorySize, stft_bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_istft), hipFuncAttributeMaxDynamicSharedMemorySize, istft_bytes);
+}
+
+// ---- the signal chain (sig_chain.h) ----
+int sig_chain_create(SigChain &s, int n_fft, int win, int hop, int K, int device, std::string &err) {
+    s = SigChain{};
+    if (n_fft <= 0 || n_fft % 2 || win <= 0 || win > n_fft || hop <= 0 || K <= 0 || K % hop) { err = "bad STFT geometry"; return SE_ERR_ARG; }
+    s.device = device; s.N = n_fft; s.win = win; s.hop = hop; s.K = K; s.T = 1 + K / hop; s.F = n_fft / 2 + 1;
+    s.plan.N = n_fft;
+    s.plan.npass = fft_plan(n_fft / 2, s.plan.radices);
+    if (!s.plan.npass || s.plan.npass > kMaxRadices) { err = "n_fft must factor into 2s and 5s"; return SE_ERR_ARG; }
+    if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return SE_ERR_HIP; }
+    // tables: hamming(win) centred in n_fft (torch.stft), twiddles, overlap-add envelope
+    const int N = n_fft, T = s.T;
+    std::vector<float> w(N, 0.0f), tw(2 * (size_t)N), env(K, 0.0f);
+    const int left = (N - win) / 2;
+    for (int i = 0; i < win; i++) w[left + i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / win));
+    for (int i = 0; i < N; i++) { tw[2 * i] = (float)cos(2.0 * M_PI * i / N); tw[2 * i + 1] = (float)-sin(2.0 * M_PI * i / N); }
+    for (int i = 0; i < K; i++) {
+        const int pos = N / 2 + i;
+        float sum = 0;
+        for (int t = 0; t < T; t++) { const int n = pos - t * hop; if (n >= 0 && n < N) sum += w[n] * w[n]; }
+        env[i] = sum;
+    }
+    auto up = [](float *&d, const std::vector<float> &h) {
+        return hipMalloc(reinterpret_cast<void **>(&d), h.size() * sizeof(float)) == hipSuccess &&
+               hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!up(s.window, w) || !up(s.tw, tw) || !up(s.env, env)) { sig_chain_destroy(s); err = "STFT table upload failed"; return SE_ERR_HIP; }
+    aux_set_fft_lds((int)stft_lds_bytes(K, N), (int)istft_lds_bytes(T, N));
+    return SE_OK;
+}
+
+void sig_chain_destroy(SigChain &s) {
+    if (!s.window && !s.tw && !s.env) return;
+    (void)hipSetDevice(s.device);
+    for (float **p : {&s.window, &s.tw, &s.env}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+}
+
+hipError_t sig_stft(const SigChain &s, const float *src, long strideB, long strideM, int M, long off, long Lsrc, SigRows rows, int nrows, cf2 *spec,
+                    long sR, long sT, long sF, hipStream_t st, int nseg, long seg_off, long seg_spec) {
+    StftArgs a{};
+    a.src = src; a.strideB = strideB; a.strideM = strideM; a.M = M; a.off = off; a.L = Lsrc;
+    a.K = s.K; a.T = s.T; a.F = s.F; a.hop = s.hop;
+    a.spec = spec; a.sR = sR; a.sT = sT; a.sF = sF;
+    a.window = s.window; a.tw = reinterpret_cast<const cf2 *>(s.tw); a.plan = s.plan;
+    a.seg_off = seg_off; a.seg_spec = seg_spec;
+    a.Lrow = rows.len; a.offrow = rows.off0;
+    launch_k_stft(dim3(nrows, nseg), stft_lds_bytes(s.K, s.N), st, a);
+    return hipGetLastError();
+}
+
+hipError_t sig_istft(const SigChain &s, const cf2 *spec, long sR, long sT, long sF, int nrows, float *wav, long wav_ld, hipStream_t st, int nseg,
+                     long seg_spec, long seg_wav) {
+    IstftArgs a{};
+    a.spec = spec; a.sR = sR; a.sT = sT; a.sF = sF; a.K = s.K; a.T = s.T; a.F = s.F; a.hop = s.hop;
+    a.wav = wav; a.wav_ld = wav_ld; a.window = s.window; a.env = s.env; a.tw = reinterpret_cast<const cf2 *>(s.tw); a.plan = s.plan;
+    a.seg_spec = seg_spec; a.seg_wav = seg_wav;
+    launch_k_istft(dim3(nrows, nseg), istft_lds_bytes(s.T, s.N), st, a);
+    return hipGetLastError();
 }
 
 }  // namespace se

@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,17 +33,12 @@
 #include "stft.hip.h"
 #include "state_rows.hip.h"
 #include "chain_plan.h"
+#include "engine_host.h"
+#include "sig_chain.h"
 
 using namespace se;
 
 namespace {
-
-thread_local std::string g_create_error;
-
-struct DevBuf {
-    float *p = nullptr;
-    size_t n = 0;
-};
 
 constexpr int kFftSub = 8;      // segments per STFT / iSTFT launch inside the pipelined path
 constexpr int kPipeChunk = 64;  // segments per pipelined chunk (bounds spec_all / mask_all)
@@ -75,22 +69,16 @@ struct Level {  // one encoder/decoder level
 
 }  // namespace
 
-struct se_engine {
+struct se_engine : EngineHost {
     se_config c{};
-    int device = 0;
     int L = 0, T = 0, D = 0, M = 0, K = 0, N = 0, H = 0, NL = 0;
     int F[SE_MAX_LEVELS + 1]{};
     int Ch[SE_MAX_LEVELS + 1]{};  // Ch[0] = 2M-1, Ch[i+1] = channels[i]
-    std::string err;
-    std::map<std::string, std::vector<float>> params;  // host copies by canonical key
-    std::map<std::string, std::vector<int64_t>> shapes;
     bool weights_ready = false;
     int gru_direct = -1;      // SE_GRU_DIRECT: 1 = always k_gru_step (W_hh streamed from L2), 0 = always k_gru_step2 (LDS slice),
                               // default -1 = k_gru_step in the overlapped (pipelined) bottleneck stage, k_gru_step2 otherwise
 
-    // constant tables
-    DevBuf window, env, tw;
-    FftPlan plan{};
+    SigChain sig;  // STFT / iSTFT tables and plan (sig_chain.h)
 
     // weights
     Level lv[SE_MAX_LEVELS];  // enc i at lv[i]; decoder j at lv[j] (dec_* members)
@@ -123,11 +111,8 @@ struct se_engine {
     DevBuf pin[3][2], pre_g, pre_stats[3];  // CRN_ELU preconv chain (inputs ping-ponged: they carry 4 history columns)
     DevBuf yseg;
     // A ragged / chains call is described by its ChainPlan (chain_plan.h), which run_segments gets as an argument.  What the engine keeps:
-    // plan_dev, the device copy of the plan's per-stream vectors (8 * B floats); row_len / row_off, the plan's lengths and first-segment
-    // offsets for launch_stft (device int64 [B]; set and cleared by run_segments, the FullSubNet engine sets them on its `sig`); carry_*,
-    // one row per stream in the live tensors' row layout (state_rows_of), filled when a stream's last segment has passed the stage that
-    // owns the tensor, written back at call exit.
-    const long *row_len = nullptr, *row_off = nullptr;
+    // plan_dev, the device copy of the plan's per-stream vectors (8 * B floats); carry_*, one row per stream in the live tensors' row
+    // layout (state_rows_of), filled when a stream's last segment has passed the stage that owns the tensor, written back at call exit.
     DevBuf plan_dev, carry_x[SE_MAX_LEVELS], carry_p[3], carry_h[4];
     // Prefix compaction: every layout is stream-major, so when the plan is `compact` the streams that still take part in segment n are a
     // PREFIX of the batch and every launch of that segment simply covers Bact = plan->bact(n) < B streams (grids, GEMM rows, GRU rows);
@@ -166,48 +151,6 @@ struct se_engine {
 
 namespace {
 
-int fail(se_engine *e, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (e) e->err = buf;
-    else g_create_error = buf;
-    return code;
-}
-
-#define HIPCHECK(e, call)                                                                      \
-    do {                                                                                       \
-        hipError_t _st = (call);                                                               \
-        if (_st != hipSuccess)                                                                 \
-            return fail(e, SE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_st), \
-                        __FILE__, __LINE__);                                                   \
-    } while (0)
-
-int dev_alloc(se_engine *e, DevBuf &b, size_t n) {
-    if (b.p && b.n >= n) return 0;
-    if (b.p) HIPCHECK(e, hipFree(b.p));
-    b.p = nullptr;
-    b.n = 0;
-    HIPCHECK(e, hipMalloc(reinterpret_cast<void **>(&b.p), (n ? n : 1) * sizeof(float)));
-    b.n = n;
-    return 0;
-}
-
-int dev_upload(se_engine *e, DevBuf &b, const std::vector<float> &h) {
-    int rc = dev_alloc(e, b, h.size());
-    if (rc) return rc;
-    HIPCHECK(e, hipMemcpy(b.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-
-void dev_free(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
-}
-
 int prof_label(se_engine *e, const char *kernel, const std::string &label, double flops) {
     for (size_t i = 0; i < e->prof_labels.size(); i++)
         if (e->prof_labels[i].label == label) { e->prof_labels[i].flops = flops; return (int)i; }
@@ -235,74 +178,11 @@ struct ProfScope {  // brackets one launch with two events when profiling is on
     }
 };
 
-uint16_t f16_rne(float x) {  // IEEE half, round to nearest even (the host compiler's _Float16 conversion)
-    const _Float16 h = (_Float16)x;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-uint16_t bf16_rne(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-float bf16_to_f32(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-// operand planes per precision mode: 0 -> 3 bf16 planes (hi, mid, lo; six products), 1 -> 1 fp16 plane, 2 -> 2 bf16 planes
-// (hi, mid; three products hi*hi + hi*mid + mid*hi)
-inline int operand_planes(int precision) { return precision == 1 ? 1 : (precision == 2 ? 2 : 3); }
-
-// bf16 planes (hi, mid, lo) of a [rows][cols] fp32 matrix -> device buffer of PL*rows*cols uint16
-int upload_split3(se_engine *e, DevBuf &b, const std::vector<float> &w) {
-    const size_t n = w.size();
-    if (e->precision == 1) {  // one fp16 plane
-        std::vector<uint16_t> plane(n);
-        for (size_t i = 0; i < n; i++) plane[i] = f16_rne(w[i]);
-        int rc = dev_alloc(e, b, (n + 1) / 2);
-        if (rc) return rc;
-        HIPCHECK(e, hipMemcpy(b.p, plane.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
-        return 0;
-    }
-    const int PL = operand_planes(e->precision);
-    std::vector<uint16_t> planes(PL * n);
-    for (size_t i = 0; i < n; i++) {
-        const float x = w[i];
-        const uint16_t h = bf16_rne(x);
-        const float r1 = x - bf16_to_f32(h);
-        const uint16_t m = bf16_rne(r1);
-        const float r2 = r1 - bf16_to_f32(m);
-        planes[i] = h; planes[n + i] = m;
-        if (PL > 2) planes[2 * n + i] = bf16_rne(r2);
-    }
-    int rc = dev_alloc(e, b, (PL * n + 1) / 2);
-    if (rc) return rc;
-    HIPCHECK(e, hipMemcpy(b.p, planes.data(), planes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    return 0;
-}
-
 std::string canon(const char *key) {
     std::string k(key);
     size_t pos = k.find(".net.0.");
     if (pos != std::string::npos) k.replace(pos, 7, ".conv.");  // CRN.py:314-316 alias
     return k;
-}
-
-const std::vector<float> *param(se_engine *e, const std::string &key, size_t expect) {
-    auto it = e->params.find(key);
-    if (it == e->params.end()) {
-        fail(e, SE_ERR_PARAM_MISSING, "parameter %s was never loaded", key.c_str());
-        return nullptr;
-    }
-    if (it->second.size() != expect) {
-        fail(e, SE_ERR_SHAPE, "parameter %s has %zu elements, expected %zu", key.c_str(), it->second.size(), expect);
-        return nullptr;
-    }
-    return &it->second;
 }
 
 // ---- conv planning --------------------------------------------------------------------------------
@@ -582,7 +462,7 @@ int prepare_weights(se_engine *e) {
         auto *d = param(e, "gru.sequence_model.bias_hh_l" + s, 3 * (size_t)H);
         if (!a || !b || !c || !d) return SE_ERR_PARAM_MISSING;
         int rc;
-        if ((rc = upload_split3(e, e->wih_x[l], *a))) return rc;
+        if ((rc = upload_planes(e, e->wih_x[l], *a, e->precision))) return rc;
         if ((rc = dev_upload(e, e->wih[l], *a)) || (rc = dev_upload(e, e->whh[l], *b)) ||
             (rc = dev_upload(e, e->bih[l], *c)) || (rc = dev_upload(e, e->bhh[l], *d)))
             return rc;
@@ -594,7 +474,7 @@ int prepare_weights(se_engine *e) {
         auto *d = param(e, "gru.norm.bias", D);
         if (!a || !b || !c || !d) return SE_ERR_PARAM_MISSING;
         int rc;
-        if ((rc = upload_split3(e, e->fcw_x, *a))) return rc;
+        if ((rc = upload_planes(e, e->fcw_x, *a, e->precision))) return rc;
         if ((rc = dev_upload(e, e->fcw, *a)) || (rc = dev_upload(e, e->fcb, *b)) || (rc = dev_upload(e, e->gnw, *c)) ||
             (rc = dev_upload(e, e->gnb, *d)))
             return rc;
@@ -920,31 +800,19 @@ int forward_dev(se_engine *e, const cf2 *spec, long sB, long sM, long sT, long s
     return run_decoder(e, cur, spec, sB, sT, sF, out, oB, oT, oF, st);
 }
 
-// nseg > 1: one launch for nseg consecutive segments (segment y reads off + y*seg_off, writes spec + y*seg_spec)
-int launch_stft(se_engine *e, const float *src, long strideB, long strideM, int M, long off, long Lsrc, int rows,
+// k_stft / k_istft on the engine's signal chain (sig_chain.h), timed and with the engine's error text.  rows: the per-stream lengths and
+// offsets of a chains call.  nseg > 1: one launch for nseg consecutive segments (segment y reads off + y*seg_off, writes spec + y*seg_spec)
+int launch_stft(se_engine *e, const float *src, long strideB, long strideM, int M, long off, long Lsrc, SigRows rows, int nrows,
                 cf2 *spec, long sR, long sT, long sF, hipStream_t st, int nseg = 1, long seg_off = 0, long seg_spec = 0) {
-    StftArgs a{};
-    a.seg_off = seg_off; a.seg_spec = seg_spec;
-    a.src = src; a.strideB = strideB; a.strideM = strideM; a.M = M; a.off = off; a.L = Lsrc;
-    a.K = e->K; a.T = e->T; a.F = e->F[0]; a.hop = e->c.hop;
-    a.spec = spec; a.sR = sR; a.sT = sT; a.sF = sF;
-    a.window = e->window.p; a.tw = reinterpret_cast<const cf2 *>(e->tw.p); a.plan = e->plan;
-    a.Lrow = e->row_len; a.offrow = e->row_off;  // chains: `off` then counts from every stream's own first segment
     ProfScope ps(e, "k_stft", "stft", 0, st);
-    launch_k_stft(dim3(rows, nseg), stft_lds_bytes(e->K, e->N), st, a);
-    HIPCHECK(e, hipGetLastError());
+    HIPCHECK(e, sig_stft(e->sig, src, strideB, strideM, M, off, Lsrc, rows, nrows, spec, sR, sT, sF, st, nseg, seg_off, seg_spec));
     return 0;
 }
 
-int launch_istft(se_engine *e, const cf2 *spec, long sR, long sT, long sF, int rows, float *wav, long wav_ld, hipStream_t st,
+int launch_istft(se_engine *e, const cf2 *spec, long sR, long sT, long sF, int nrows, float *wav, long wav_ld, hipStream_t st,
                  int nseg = 1, long seg_spec = 0, long seg_wav = 0) {
-    IstftArgs a{};
-    a.seg_spec = seg_spec; a.seg_wav = seg_wav;
-    a.spec = spec; a.sR = sR; a.sT = sT; a.sF = sF; a.K = e->K; a.T = e->T; a.F = e->F[0]; a.hop = e->c.hop;
-    a.wav = wav; a.wav_ld = wav_ld; a.window = e->window.p; a.env = e->env.p; a.tw = reinterpret_cast<const cf2 *>(e->tw.p); a.plan = e->plan;
     ProfScope ps(e, "k_istft", "istft", 0, st);
-    launch_k_istft(dim3(rows, nseg), istft_lds_bytes(e->T, e->N), st, a);
-    HIPCHECK(e, hipGetLastError());
+    HIPCHECK(e, sig_istft(e->sig, spec, sR, sT, sF, nrows, wav, wav_ld, st, nseg, seg_spec, seg_wav));
     return 0;
 }
 
@@ -973,7 +841,7 @@ int ensure_ready(se_engine *e) {
                     const int cabs = d / Fl, f = d - cabs * Fl;
                     wp[(size_t)r * D + ((size_t)(cabs >> 3) * Fl + f) * 8 + (cabs & 7)] = w[(size_t)r * D + d];
                 }
-            if ((rc = upload_split3(e, e->wih_xp, wp))) return rc;
+            if ((rc = upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
             // fc_output_layer rows, its bias and the affine of the norm behind it in the same order (each dot product is unchanged;
             // only where it lands changes), channels padded to whole octets with zero rows.  (gemm_p_cap above asks for whole
             // octets, so today ND == D and no padding row exists; the padding is what a relaxed cap would need, and is untested)
@@ -987,7 +855,7 @@ int ensure_ready(se_engine *e) {
                 std::copy(fw.begin() + (size_t)d * H, fw.begin() + (size_t)(d + 1) * H, fwp.begin() + dp * H);
                 fbp[dp] = fb[d]; nwp[dp] = nw[d]; nbp[dp] = nb[d];
             }
-            if ((rc = upload_split3(e, e->fcw_xp, fwp)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
+            if ((rc = upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
                 (rc = dev_upload(e, e->gnb_p, nbp)))
                 return rc;
         }
@@ -1093,7 +961,6 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (cfg->num_layers < 1 || cfg->num_layers > 4) return fail(nullptr, SE_ERR_ARG, "num_layers %d out of range", cfg->num_layers);
     if (cfg->hidden <= 0 || cfg->hidden % 16) return fail(nullptr, SE_ERR_ARG, "hidden must be a positive multiple of 16 (k_gru_step walks 16-deep k blocks)");
     if (cfg->n_fft % 2 || cfg->num_freqs != cfg->n_fft / 2 + 1) return fail(nullptr, SE_ERR_ARG, "num_freqs must be n_fft/2+1 (CRN.py:511)");
-    if (cfg->win > cfg->n_fft || cfg->hop <= 0 || cfg->segment_length % cfg->hop) return fail(nullptr, SE_ERR_ARG, "bad STFT geometry");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, SE_ERR_HIP, "no HIP device available: the engine has no CPU fallback");
@@ -1110,17 +977,18 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     e->npre = cfg->variant ? 3 : 0;
     e->atan2_phase = cfg->variant == 1;
     e->eps_mode = cfg->variant == 2;
-    e->T = 1 + cfg->segment_length / cfg->hop;
+    auto bail = [&](int code, const char *msg) { g_create_error = msg; sig_chain_destroy(e->sig); delete e; return code; };
+    {  // STFT geometry, tables and the FFT kernels' LDS opt-in
+        std::string why;
+        if (int rc = sig_chain_create(e->sig, cfg->n_fft, cfg->win, cfg->hop, cfg->segment_length, device, why)) return bail(rc, why.c_str());
+    }
+    e->T = e->sig.T;
     e->F[0] = cfg->num_freqs;
     e->Ch[0] = 2 * cfg->num_inputs - 1;
     for (int i = 0; i < L; i++) { e->F[i + 1] = (e->F[i] - 1) / 2 + 1; e->Ch[i + 1] = cfg->channels[i]; }
     e->D = (cfg->num_freqs / 16 + 1) * cfg->channels[L - 1];
-    auto bail = [&](int code, const char *msg) { g_create_error = msg; delete e; return code; };
     if (e->D != e->F[L] * cfg->channels[L - 1]) return bail(SE_ERR_ARG, "num_freqs/num_levels combination breaks the reference reshape (CRN.py:450,478)");
     if (e->T <= 2 * (1 << (L - 1))) return bail(SE_ERR_ARG, "segment shorter than the largest dilation history (CRN.py:333)");
-    e->plan.N = cfg->n_fft;
-    e->plan.npass = fft_plan(cfg->n_fft / 2, e->plan.radices);
-    if (!e->plan.npass || e->plan.npass > kMaxRadices) return bail(SE_ERR_ARG, "n_fft must factor into 2s and 5s");
     if (const char *s = getenv("SE_GRU_DIRECT")) e->gru_direct = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
@@ -1137,25 +1005,6 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) e->num_cu = ncu;
     }
-    if (hipSetDevice(device) != hipSuccess) return bail(SE_ERR_HIP, "hipSetDevice failed");
-    // tables: hamming(win) centred in n_fft (torch.stft), twiddles, overlap-add envelope
-    const int N = e->N, T = e->T, hop = cfg->hop, K = e->K;
-    std::vector<float> win(N, 0.0f), tw(2 * (size_t)N), env(K, 0.0f);
-    const int left = (N - cfg->win) / 2;
-    for (int i = 0; i < cfg->win; i++) win[left + i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / cfg->win));
-    for (int i = 0; i < N; i++) { tw[2 * i] = (float)cos(2.0 * M_PI * i / N); tw[2 * i + 1] = (float)-sin(2.0 * M_PI * i / N); }
-    for (int i = 0; i < K; i++) {
-        const int pos = N / 2 + i;
-        float s = 0;
-        for (int t = 0; t < T; t++) { const int n = pos - t * hop; if (n >= 0 && n < N) s += win[n] * win[n]; }
-        env[i] = s;
-    }
-    int rc;
-    if ((rc = dev_upload(e, e->window, win)) || (rc = dev_upload(e, e->tw, tw)) || (rc = dev_upload(e, e->env, env))) {
-        g_create_error = e->err; delete e; return rc;
-    }
-    // opt in to large dynamic LDS for the FFT kernels
-    aux_set_fft_lds((int)stft_lds_bytes(K, N), (int)istft_lds_bytes(T, N));
     conv_set_attributes();
     conv_p_set_attributes();
     skip_p_set_attributes();
@@ -1175,7 +1024,7 @@ void se_destroy(se_engine *e) {
 #ifdef SE_CP_TRACE
     g_cp_trace_sites.dump();
 #endif
-    DevBuf *singles[] = {&e->window, &e->env, &e->tw, &e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
+    DevBuf *singles[] = {&e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
                          &e->fcw_x, &e->wih_xp, &e->fcw_xp, &e->fcb_p, &e->gnw_p, &e->gnb_p, &e->fc_stats, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
     for (DevBuf *b : singles) dev_free(*b);
     dev_free(e->plan_dev);
@@ -1207,6 +1056,7 @@ void se_destroy(se_engine *e) {
         if (i < 3) { dev_free(e->pin[i][0]); dev_free(e->pin[i][1]); dev_free(e->pre_stats[i]); }
     }
     free_state_p(e);
+    sig_chain_destroy(e->sig);
     delete e;
 }
 
@@ -1235,13 +1085,8 @@ int se_load_param(se_engine *e, const char *key, const float *host_data, const i
     else
         ok = k == "gru.fc_output_layer.weight" || k == "gru.fc_output_layer.bias" || k == "gru.norm.weight" || k == "gru.norm.bias";
     if (!ok) return fail(e, SE_ERR_KEY, "unknown parameter key %s", key);
-    size_t cnt = 1;
-    std::vector<int64_t> shp;
-    for (int i = 0; i < ndim; i++) { if (shape[i] < 0) return fail(e, SE_ERR_SHAPE, "negative dimension in %s", key); cnt *= (size_t)shape[i]; shp.push_back(shape[i]); }
-    e->params[k].assign(host_data, host_data + cnt);
-    e->shapes[k] = shp;
     e->weights_ready = false;
-    return SE_OK;
+    return store_param(e, k, host_data, shape, ndim);
 }
 
 // (Re)allocates state for `batch` streams if needed and zeroes it asynchronously on `st`.
@@ -1346,7 +1191,7 @@ int se_stft(se_engine *e, const float *seg, int n, float *spec, void *stream) {
     if (!e || !seg || !spec || n <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     HIPCHECK(e, hipSetDevice(e->device));
     const long F = e->F[0], T = e->T;
-    return launch_stft(e, seg, e->K, 0, 1, 0, e->K, n, reinterpret_cast<cf2 *>(spec), F * T, 1, T, static_cast<hipStream_t>(stream));
+    return launch_stft(e, seg, e->K, 0, 1, 0, e->K, SigRows{}, n, reinterpret_cast<cf2 *>(spec), F * T, 1, T, static_cast<hipStream_t>(stream));
 }
 
 int se_istft(se_engine *e, const float *spec, int n, float *wav, void *stream) {
@@ -1373,12 +1218,12 @@ static int ensure_stage_streams(se_engine *e) {
     return 0;
 }
 
-static int step_dev(se_engine *e, const float *src, long strideB, long strideM, long off, long Lsrc, float *wav_out, long wav_ld, hipStream_t st) {
+static int step_dev(se_engine *e, const float *src, long strideB, long strideM, long off, long Lsrc, SigRows rows, float *wav_out, long wav_ld, hipStream_t st) {
     const long F = e->F[0], T = e->T, M = e->M;
     int rc;
     cf2 *spec = reinterpret_cast<cf2 *>(e->spec[(e->slot + 1) % kRing].p);
     cf2 *ms = reinterpret_cast<cf2 *>(e->maskspec.p);
-    if ((rc = launch_stft(e, src, strideB, strideM, (int)M, off, Lsrc, e->Bact * (int)M, spec, T * F, F, 1, st))) return rc;
+    if ((rc = launch_stft(e, src, strideB, strideM, (int)M, off, Lsrc, rows, e->Bact * (int)M, spec, T * F, F, 1, st))) return rc;
     if ((rc = forward_dev(e, spec, M * T * F, T * F, F, 1, ms, T * F, F, 1, st))) return rc;
     return launch_istft(e, ms, T * F, F, 1, e->Bact, wav_out, wav_ld, st);
 }
@@ -1388,7 +1233,7 @@ int se_step(se_engine *e, const float *wav_in, float *wav_out, void *stream) {
     if (e->B <= 0) return fail(e, SE_ERR_STATE, "se_step before se_reset");
     int rc = ensure_ready(e);
     if (rc) return rc;
-    return step_dev(e, wav_in, (long)e->M * e->K, e->K, 0, e->K, wav_out, e->K, static_cast<hipStream_t>(stream));
+    return step_dev(e, wav_in, (long)e->M * e->K, e->K, 0, e->K, SigRows{}, wav_out, e->K, static_cast<hipStream_t>(stream));
 }
 
 // ---- per-stream state rows (state_rows.hip.h) of the streams a ChainPlan names: dir 0 save, 1 restore, 2 zero ----
@@ -1411,14 +1256,20 @@ static int alloc_carry(se_engine *e) {
     return state_rows_of(e, ~0u, [&](float *, DevBuf &carry, long words) { return dev_alloc(e, carry, (size_t)e->B * words); });
 }
 
-// The segments of one realtime_process call on state that is ready: Nseg half-overlapping windows, window n of a stream starting at
-// off_first + n * K/2 (+ the stream's own plan->off0), overlap-average with `skip` (or plan->skip) stripped -> out [batch, length].
-// plan: the ragged / chains call's ChainPlan (chain_plan.h), null for a uniform call.
-static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st,
-                        const ChainPlan *plan);
+// What run_segments walks: a uniform call's geometry (every stream: N segments from off_first, `skip` stripped), or a chains call's plan
+// (chain_plan.h), which carries every stream's own length, first-segment offset and strip.
+struct SegmentWalk {
+    long N, off_first, skip;
+    const ChainPlan *plan;
+    SegmentWalk(const ChunkGeometry &g) : N(g.nseg), off_first(g.off0), skip(g.skip), plan(nullptr) {}
+    SegmentWalk(const ChainPlan &p) : N(p.N), off_first(0), skip(0), plan(&p) {}
+};
 
-// se_realtime_process, and se_realtime_process_ragged with its plan
-static int process_uniform(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream, const ChainPlan *plan) {
+// The segments of one realtime_process call on state that is ready: w.N half-overlapping windows, window n of a stream starting at
+// w.off_first + n * K/2 (+ the stream's own plan->off0), overlap-average with the strip taken off -> out [batch, length].
+static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, const SegmentWalk &w, float *out, hipStream_t st);
+
+int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
     if (!e || !mixture || !out || batch <= 0 || length <= 0) return fail(e, SE_ERR_ARG, "bad argument");
     int rc;
     if (!flag) {
@@ -1427,12 +1278,7 @@ static int process_uniform(se_engine *e, const float *mixture, int batch, int64_
         if (e->B != batch) return fail(e, SE_ERR_STATE, "flag=True with batch %d but the carried state holds %d streams", batch, e->B);
         if ((rc = ensure_ready(e))) return rc;
     }
-    const ChunkGeometry g = chunk_geometry(e->K, length, flag);
-    return run_segments(e, mixture, batch, length, g.nseg, g.off0, g.skip, out, static_cast<hipStream_t>(stream), plan);
-}
-
-int se_realtime_process(se_engine *e, const float *mixture, int batch, int64_t length, int flag, float *out, void *stream) {
-    return process_uniform(e, mixture, batch, length, flag, out, stream, nullptr);
+    return run_segments(e, mixture, batch, length, chunk_geometry(e->K, length, flag), out, static_cast<hipStream_t>(stream));
 }
 
 int se_chunk_geometry(int segment_length, int64_t length, int continues, int64_t *nseg, int64_t *off0, int64_t *skip) {
@@ -1442,10 +1288,11 @@ int se_chunk_geometry(int segment_length, int64_t length, int continues, int64_t
     return SE_OK;
 }
 
-static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, long Nseg, long off_first, long skip, float *out, hipStream_t st,
-                        const ChainPlan *plan) {
+static int run_segments(se_engine *e, const float *mixture, int batch, int64_t length, const SegmentWalk &w, float *out, hipStream_t st) {
     int rc;
-    const long K = e->K, P = K / 2;
+    const long K = e->K, P = K / 2, Nseg = w.N, off_first = w.off_first;
+    const ChainPlan *plan = w.plan;
+    const SigRows rows = plan ? SigRows{plan->len, plan->off0} : SigRows{};
     if ((rc = dev_alloc(e, e->yseg, (size_t)batch * Nseg * K))) return rc;
     bool piped = e->pipeline && !e->prof_on && Nseg > 1;
     if (piped && ensure_stage_streams(e)) {  // no extra streams / events available: fall back to the caller's stream for good
@@ -1458,15 +1305,14 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
     auto bact_of = [&](long n) { return compact ? plan->bact(n) : e->B; };
     struct RestoreBact {  // a failing call leaves the engine usable: nothing of the plan outlives the call
         se_engine *e;
-        ~RestoreBact() { e->Bact = e->B; for (int &v : e->bact_slot) v = e->B; e->row_len = e->row_off = nullptr; }
+        ~RestoreBact() { e->Bact = e->B; for (int &v : e->bact_slot) v = e->B; }
     } restore_bact{e};
-    if (plan) { e->row_len = plan->len; e->row_off = plan->off0; }
     if (!piped) {
         for (long n = 0; n < Nseg; n++) {
             const long off = off_first + n * P;
             e->Bact = bact_of(n);
             // yseg is [B][Nseg][K]: the iSTFT writes segment n of every stream with row stride Nseg*K
-            if ((rc = step_dev(e, mixture, (long)e->M * length, length, off, length, e->yseg.p + n * K, Nseg * K, st))) return rc;
+            if ((rc = step_dev(e, mixture, (long)e->M * length, length, off, length, rows, e->yseg.p + n * K, Nseg * K, st))) return rc;
             if ((rc = chain_save(e, plan, n, ~0u, st))) return rc;
         }
     } else {
@@ -1498,7 +1344,7 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
                     const cf2 *spec = reinterpret_cast<const cf2 *>(e->spec_all.p + spec_n * i);
                     if (i % kFftSub == 0) {
                         const long ns = std::min<long>(kFftSub, cn - i);
-                        if ((rc = launch_stft(e, mixture, (long)e->M * length, length, (int)M, off_first + (c0 + i) * P, length, e->Bact * (int)M,
+                        if ((rc = launch_stft(e, mixture, (long)e->M * length, length, (int)M, off_first + (c0 + i) * P, length, rows, e->Bact * (int)M,
                                               reinterpret_cast<cf2 *>(e->spec_all.p + spec_n * i), T * F, F, 1, sE, (int)ns, P, (long)(spec_n / 2)))) return rc;
                     }
                     if (i >= kRing) HIPCHECK(e, hipStreamWaitEvent(sE, e->ev_dec[cur], 0));  // slot cur was last read by the decoder of segment i - kRing
@@ -1550,26 +1396,10 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
     }
     // the streams that ended before the longest one get their own state back (the stage streams have joined `st`)
     if (plan && (rc = chain_rows(e, ~0u, 1, plan->ended_early(), st))) return rc;
-    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, skip, plan ? plan->len : nullptr,
+    launch_k_overlap_avg(dim3((unsigned)((length + 255) / 256), batch), st, e->yseg.p, out, (int)Nseg, (int)K, (long)length, w.skip, rows.len,
                          plan ? plan->skip : nullptr);
     HIPCHECK(e, hipGetLastError());
     return SE_OK;
-}
-
-int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, int flag, float *out,
-                               void *stream) {
-    if (!e || !lengths_host || batch <= 0) return fail(e, SE_ERR_ARG, "bad argument");
-    // segments stream b takes part in (the count it would have alone), for the prefix compaction; only when the lengths are non-increasing
-    // (the Python shim sorts the batch), otherwise every stream runs every segment
-    ChainPlan plan;
-    std::string err;
-    int rc = plan_ragged(plan, e->K, batch, max_length, lengths_host, flag, err);
-    if (rc) return fail(e, rc, "%s", err.c_str());
-    if ((rc = dev_alloc(e, e->plan_dev, (size_t)batch * 2))) return rc;
-    HIPCHECK(e, hipMemcpyAsync(e->plan_dev.p, lengths_host, (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
-    HIPCHECK(e, hipStreamSynchronize(static_cast<hipStream_t>(stream)));  // the host array is borrowed for the call only
-    plan.len = reinterpret_cast<const long *>(e->plan_dev.p);
-    return process_uniform(e, mixture, batch, max_length, flag, out, stream, &plan);
 }
 
 // A batch of chunk chains (include/se_engine.h): reset or make ready, plan (chain_plan.h), upload, zero the flag-0 rows, run
@@ -1584,13 +1414,18 @@ int se_realtime_process_chains(se_engine *e, const float *mixture, int batch, in
     if (rc) return fail(e, rc, "%s", err.c_str());
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = plan.continues() ? ensure_ready(e) : reset_on_stream(e, batch, st))) return rc;
-    if ((rc = dev_alloc(e, e->plan_dev, plan.staging_floats())) || (rc = alloc_carry(e))) return rc;
-    HIPCHECK(e, hipMemcpyAsync(e->plan_dev.p, plan.staging.data(), plan.staging.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(e, hipStreamSynchronize(st));  // the staging vector and the host arrays live for the call only
-    plan.carve(e->plan_dev.p);
+    if ((rc = alloc_carry(e)) || (rc = upload_plan(e, e->plan_dev, plan, st))) return rc;
     // a reset among continuing streams: zero those streams' rows (se_reset_stream for any number of streams in one launch)
     if (plan.continues() && (rc = chain_rows(e, ~0u, 2, plan.reset_streams(), st))) return rc;
-    return run_segments(e, mixture, batch, max_length, plan.N, 0, 0, out, st, &plan);
+    return run_segments(e, mixture, batch, max_length, plan, out, st);
+}
+
+// a chains call in which every stream has the one flag
+int se_realtime_process_ragged(se_engine *e, const float *mixture, int batch, int64_t max_length, const int64_t *lengths_host, int flag, float *out,
+                               void *stream) {
+    if (batch <= 0) return fail(e, SE_ERR_ARG, "bad argument");
+    const std::vector<uint8_t> flags((size_t)batch, flag ? 1 : 0);
+    return se_realtime_process_chains(e, mixture, batch, max_length, lengths_host, flags.data(), out, stream);
 }
 
 static int copy_out(se_engine *e, const float *dev, size_t n, float *host, int64_t cap, int64_t *count, hipStream_t st) {

@@ -14,6 +14,7 @@
 
 #include "../../include/se_engine.h"
 #include "gru_pseq.hip.h"
+#include "sig_chain.h"
 #include "stft.hip.h"
 #include "train_fused.hip.h"
 
@@ -51,12 +52,8 @@ void launch_arrange_w(const float *w, float *out, long sCo, long sCi, int Co, in
 
 using se::train_fail;
 
-// STFT geometry + tables of the training step's signal stages (the engine's k_stft / k_istft kernels without an engine handle)
-struct se_sig {
-    int device = 0, N = 0, win = 0, hop = 0, K = 0, T = 0, F = 0;
-    float *window = nullptr, *env = nullptr, *tw = nullptr;
-    se::FftPlan plan{};
-};
+// the training step's signal stages: the engine's signal chain (sig_chain.h) without an engine handle
+struct se_sig : se::SigChain {};
 
 extern "C" {
 
@@ -166,69 +163,44 @@ int se_train_gru_pseq_bwd_rows(const float *dout, const float *dhT, const float 
     return pseq_bwd(dout, dhT, gates, out, h0, whh_t, dgi, dgh, scratch, B, T, H, Tseg, ldN, ldB, seg_len, steps, stream);
 }
 
-#define TCHECK(call)                                                                                             \
-    do {                                                                                                         \
-        if ((call) != hipSuccess) return train_fail(SE_ERR_HIP, "%s failed (%s:%d)", #call, __FILE__, __LINE__); \
-    } while (0)
-
 int se_sig_create(int n_fft, int win, int hop, int K, int device, se_sig **out) {
-    if (!out || n_fft <= 0 || n_fft % 2 || win <= 0 || win > n_fft || hop <= 0 || K <= 0 || K % hop) return train_fail(SE_ERR_ARG, "bad STFT geometry");
+    if (!out) return train_fail(SE_ERR_ARG, "null argument");
     se_sig *g = new se_sig();
-    g->device = device; g->N = n_fft; g->win = win; g->hop = hop; g->K = K; g->T = 1 + K / hop; g->F = n_fft / 2 + 1;
-    g->plan.N = n_fft;
-    g->plan.npass = fft_plan(n_fft / 2, g->plan.radices);
-    if (!g->plan.npass || g->plan.npass > se::kMaxRadices) { delete g; return train_fail(SE_ERR_ARG, "n_fft must factor into 2s and 5s"); }
-    if (hipSetDevice(device) != hipSuccess) { delete g; return train_fail(SE_ERR_HIP, "hipSetDevice failed"); }
-    const int N = n_fft, T = g->T;
-    std::vector<float> w(N, 0.0f), tw(2 * (size_t)N), env(K, 0.0f);
-    const int left = (N - win) / 2;
-    for (int i = 0; i < win; i++) w[left + i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / win));
-    for (int i = 0; i < N; i++) { tw[2 * i] = (float)cos(2.0 * M_PI * i / N); tw[2 * i + 1] = (float)-sin(2.0 * M_PI * i / N); }
-    for (int i = 0; i < K; i++) {
-        const int pos = N / 2 + i;
-        float sum = 0;
-        for (int t = 0; t < T; t++) { const int n = pos - t * hop; if (n >= 0 && n < N) sum += w[n] * w[n]; }
-        env[i] = sum;
-    }
-    auto up = [&](float *&d, const std::vector<float> &h) {
-        return hipMalloc(reinterpret_cast<void **>(&d), h.size() * sizeof(float)) == hipSuccess &&
-               hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(g->window, w) || !up(g->tw, tw) || !up(g->env, env)) { se_sig_destroy(g); return train_fail(SE_ERR_HIP, "table upload failed"); }
-    se::aux_set_fft_lds((int)se::stft_lds_bytes(K, N), (int)se::istft_lds_bytes(T, N));
+    std::string err;
+    const int rc = se::sig_chain_create(*g, n_fft, win, hop, K, device, err);
+    if (rc) { delete g; return train_fail(rc, "%s", err.c_str()); }
     *out = g;
     return SE_OK;
 }
 
 void se_sig_destroy(se_sig *g) {
     if (!g) return;
-    (void)hipSetDevice(g->device);
-    if (g->window) (void)hipFree(g->window);
-    if (g->tw) (void)hipFree(g->tw);
-    if (g->env) (void)hipFree(g->env);
+    se::sig_chain_destroy(*g);
     delete g;
 }
 
-int se_sig_stft(se_sig *g, const float *wav, int B, int M, int64_t L, int64_t off0, int64_t seg_off, int nseg, float *spec, void *stream) {
+// B x M rows of L samples, nseg segments seg_off apart from off0 (+ the stream's own rows.off0) -> spec [nseg][B * M][T][F]
+static int sig_stft_rows(se_sig *g, const float *wav, int B, int M, int64_t L, int64_t off0, se::SigRows rows, int64_t seg_off, int nseg, float *spec, void *stream) {
     if (!g || !wav || !spec || B <= 0 || M <= 0 || nseg <= 0) return train_fail(SE_ERR_ARG, "bad argument");
-    se::StftArgs a{};
-    a.src = wav; a.strideB = (long)M * L; a.strideM = L; a.M = M; a.off = off0; a.L = L;
-    a.K = g->K; a.T = g->T; a.F = g->F; a.hop = g->hop;
-    a.spec = reinterpret_cast<cf2 *>(spec); a.sR = (long)g->T * g->F; a.sT = g->F; a.sF = 1;
-    a.window = g->window; a.tw = reinterpret_cast<const cf2 *>(g->tw); a.plan = g->plan;
-    a.seg_off = seg_off; a.seg_spec = (long)B * M * g->T * g->F;
-    se::launch_k_stft(dim3(B * M, nseg), se::stft_lds_bytes(g->K, g->N), static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "stft launch failed");
+    const long TF = (long)g->T * g->F;
+    return se::sig_stft(*g, wav, (long)M * L, L, M, off0, L, rows, B * M, reinterpret_cast<cf2 *>(spec), TF, g->F, 1, static_cast<hipStream_t>(stream), nseg,
+                        seg_off, (long)B * M * TF) == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "stft launch failed");
+}
+
+int se_sig_stft(se_sig *g, const float *wav, int B, int M, int64_t L, int64_t off0, int64_t seg_off, int nseg, float *spec, void *stream) {
+    return sig_stft_rows(g, wav, B, M, L, off0, se::SigRows{}, seg_off, nseg, spec, stream);
+}
+
+int se_sig_stft_rows(se_sig *g, const float *wav, int B, int M, int64_t Lmax, const int64_t *off0, const int64_t *len, int64_t seg_off, int nseg, float *spec,
+                     void *stream) {
+    if (!off0 || !len || Lmax <= 0) return train_fail(SE_ERR_ARG, "bad argument");
+    return sig_stft_rows(g, wav, B, M, Lmax, 0, se::SigRows{reinterpret_cast<const long *>(len), reinterpret_cast<const long *>(off0)}, seg_off, nseg, spec, stream);
 }
 
 int se_sig_istft(se_sig *g, const float *spec, int rows, float *wav, void *stream) {
     if (!g || !spec || !wav || rows <= 0) return train_fail(SE_ERR_ARG, "bad argument");
-    se::IstftArgs a{};
-    a.spec = reinterpret_cast<const cf2 *>(spec); a.sR = (long)g->T * g->F; a.sT = g->F; a.sF = 1;
-    a.K = g->K; a.T = g->T; a.F = g->F; a.hop = g->hop;
-    a.wav = wav; a.wav_ld = g->K; a.window = g->window; a.env = g->env; a.tw = reinterpret_cast<const cf2 *>(g->tw); a.plan = g->plan;
-    se::launch_k_istft(dim3(rows, 1), se::istft_lds_bytes(g->T, g->N), static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "istft launch failed");
+    return se::sig_istft(*g, reinterpret_cast<const cf2 *>(spec), (long)g->T * g->F, g->F, 1, rows, wav, g->K, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? SE_OK : train_fail(SE_ERR_HIP, "istft launch failed");
 }
 
 int se_train_ola_fwd(se_sig *g, const float *yseg, float *out, int B, int64_t L, int64_t skip, void *stream) {
@@ -241,20 +213,6 @@ int se_train_ola_bwd(se_sig *g, const float *dout, float *gseg, int B, int nseg,
     if (!g || !dout || !gseg || B <= 0 || nseg <= 0) return train_fail(SE_ERR_ARG, "bad argument");
     hipLaunchKernelGGL(se::k_tola_bwd, dim3((g->K + 255) / 256, B, nseg), dim3(256), 0, static_cast<hipStream_t>(stream), dout, g->env, gseg, B, g->K, (long)L, (long)skip);
     return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "launch failed");
-}
-
-int se_sig_stft_rows(se_sig *g, const float *wav, int B, int M, int64_t Lmax, const int64_t *off0, const int64_t *len, int64_t seg_off, int nseg, float *spec,
-                     void *stream) {
-    if (!g || !wav || !off0 || !len || !spec || B <= 0 || M <= 0 || Lmax <= 0 || nseg <= 0) return train_fail(SE_ERR_ARG, "bad argument");
-    se::StftArgs a{};
-    a.src = wav; a.strideB = (long)M * Lmax; a.strideM = Lmax; a.M = M; a.L = Lmax;
-    a.offrow = reinterpret_cast<const long *>(off0); a.Lrow = reinterpret_cast<const long *>(len);
-    a.K = g->K; a.T = g->T; a.F = g->F; a.hop = g->hop;
-    a.spec = reinterpret_cast<cf2 *>(spec); a.sR = (long)g->T * g->F; a.sT = g->F; a.sF = 1;
-    a.window = g->window; a.tw = reinterpret_cast<const cf2 *>(g->tw); a.plan = g->plan;
-    a.seg_off = seg_off; a.seg_spec = (long)B * M * g->T * g->F;
-    se::launch_k_stft(dim3(B * M, nseg), se::stft_lds_bytes(g->K, g->N), static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SE_OK : train_fail(SE_ERR_HIP, "stft launch failed");
 }
 
 int se_train_ola_fwd_rows(se_sig *g, const float *yseg, float *out, int B, int64_t Lmax, const int64_t *skip, const int64_t *len, void *stream) {

@@ -362,6 +362,28 @@ class _EngineBase:
         self.batch = B
         return out
 
+    def realtime_process(self, mixture, flag=False, lengths=None, out=None):
+        """flag: a bool (or one value) for the whole batch, or one value per stream: a batch of chunk chains (realtime_process_chains).
+        lengths (optional, [B] ints <= L): every stream is processed as if alone with its own length - a chains call in which every
+        stream has the one flag, so a fresh batch is sorted by segment count (SlotMap) and every stream leaves its own state."""
+        import torch
+        B, M, L = mixture.shape
+        if M != self.M:
+            raise RuntimeError(f"expected {self.M} microphones, got {M}")
+        flag = _flags_of(flag, B)
+        if isinstance(flag, list) or lengths is not None:
+            return self.realtime_process_chains(mixture, flag if isinstance(flag, list) else [flag] * B, lengths, out=out)
+        if flag and self._order is not None and len(self._order) == B:
+            # the carried batch was permuted by a chains call: keep the caller's row b on its stream
+            return self.realtime_process_chains(mixture, [True] * B, None, out=out)
+        if out is None:
+            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
+        if not flag:
+            self._set_slots()
+        self._check(self._fn("realtime_process")(self._h, self._dev(mixture), B, L, int(bool(flag)), self._dev(out, (B, L)), self._stream()))
+        self.batch = B
+        return out
+
     def _host_read(self, fn, name: str) -> np.ndarray:
         n = C.c_int64(0)
         probe = np.empty(1, np.float32)
@@ -410,48 +432,6 @@ class Engine(_EngineBase):
             wav_out = torch.empty((B, self.K), dtype=torch.float32, device=wav_in.device)
         self._check(self.lib.se_step(self._h, self._dev(wav_in, (B, self.M, self.K)), self._dev(wav_out, (B, self.K)), self._stream()))
         return wav_out
-
-    def realtime_process(self, mixture, flag=False, out=None, lengths=None):
-        """lengths (optional, [B] ints <= L): ragged batch - every stream is processed as if alone with its own length.
-        flag: a bool (or one value) for the whole batch, or one value per stream: a batch of chunk chains (realtime_process_chains)."""
-        import torch
-        B, M, L = mixture.shape
-        if M != self.M:
-            raise RuntimeError(f"expected {self.M} microphones, got {M}")
-        flag = _flags_of(flag, B)
-        if isinstance(flag, list):
-            return self.realtime_process_chains(mixture, flag, lengths, out=out)
-        if flag and self._order is not None and len(self._order) == B:
-            # the carried batch was permuted by a chains call: keep the caller's row b on its stream
-            return self.realtime_process_chains(mixture, [True] * B, lengths, out=out)
-        if out is None:
-            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
-        if not flag:
-            self._set_slots()
-        if lengths is not None:
-            ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(ln) != B:
-                raise RuntimeError(f"{len(ln)} lengths for a batch of {B}")
-            # Prefix compaction (DESIGN.md 7): with non-increasing lengths the engine launches every segment for the streams still running
-            # only.  A fresh batch (flag=False) is therefore sorted by length here and un-sorted on the way out; a continuation keeps its
-            # slots (the carried state lives in them) and is compacted only if it happens to be sorted.
-            order = sorted(range(B), key=lambda i: -ln[i])
-            permute = not flag and order != list(range(B))
-            if permute:
-                idx = torch.tensor(order, dtype=torch.int64, device=mixture.device)
-                src, dst = mixture.index_select(0, idx).contiguous(), torch.empty_like(out)
-                ln_call = [ln[i] for i in order]
-            else:
-                src, dst, ln_call = mixture, out, ln
-            arr = (C.c_int64 * B)(*ln_call)
-            self._check(self.lib.se_realtime_process_ragged(self._h, self._dev(src), B, L, arr, int(bool(flag)), self._dev(dst, (B, L)), self._stream()))
-            if permute:
-                out.index_copy_(0, idx, dst)
-            self.batch = B
-            return out
-        self._check(self.lib.se_realtime_process(self._h, self._dev(mixture), B, L, int(bool(flag)), self._dev(out, (B, L)), self._stream()))
-        self.batch = B
-        return out
 
     def stft(self, seg):
         import torch
@@ -536,27 +516,6 @@ class FsnEngine(_EngineBase):
         crm = torch.empty((B, 2, self.F, self.T), dtype=torch.float32, device=x.device)
         self._check(self.lib.fsn_forward(self._h, self._dev(x, (B, 2 * self.M, self.F, self.T)), self._dev(crm), self._stream()))
         return crm
-
-    def realtime_process(self, mixture, flag=False, lengths=None, out=None):
-        """flag: a bool (or one value) for the whole batch, or one value per stream: a batch of chunk chains (realtime_process_chains).
-        lengths (optional, [B] ints <= L): every stream is processed as if alone with its own length."""
-        import torch
-        B, M, L = mixture.shape
-        if M != self.M:
-            raise RuntimeError(f"expected {self.M} microphones, got {M}")
-        flag = _flags_of(flag, B)
-        if isinstance(flag, list) or lengths is not None:
-            return self.realtime_process_chains(mixture, flag if isinstance(flag, list) else [flag] * B, lengths, out=out)
-        if flag and self._order is not None and len(self._order) == B:
-            # the carried batch was permuted by a chains call: keep the caller's row b on its stream
-            return self.realtime_process_chains(mixture, [True] * B, None, out=out)
-        if out is None:
-            out = torch.empty((B, L), dtype=torch.float32, device=mixture.device)
-        if not flag:
-            self._set_slots()
-        self._check(self.lib.fsn_realtime_process(self._h, self._dev(mixture), B, L, int(bool(flag)), self._dev(out, (B, L)), self._stream()))
-        self.batch = B
-        return out
 
     @property
     def flops_per_frame(self):

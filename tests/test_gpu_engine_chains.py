@@ -233,3 +233,74 @@ def test_chain_errors_leave_the_engine_usable():
     for b, l in enumerate(lens2):
         assert rel_rms(y2[b, :l], g[f"crn_call2_utt{b}"]) < 1e-4, b
     assert torch.equal(e.realtime_process(x, flag=[False] * 3, lengths=lens), ref)
+
+
+# ---- 7. a ragged call is a chains call; one signal chain; FullSubNet's frame floor ----------------------------------------------------
+def test_ragged_call_is_a_chains_call_state_included():
+    """se_realtime_process_ragged, called directly, against realtime_process(flag=[False] * 3, lengths=...) on a second engine with the
+    same weights (TINY, the fresh batch of chain_cases.CALLS[0]): the same outputs and the same exported h / conv buffers, bit for bit -
+    the streams that ended early keep their own state.  Then a flag=True call with the CALLS[1] lengths on the first engine: every
+    stream within BAR_ALONE of its own two-chunk chain run alone."""
+    import ctypes as C
+    ea, eb, e1 = _engine(TINY, seed=0), _engine(TINY, seed=0), _engine(TINY, seed=0)
+    lens0, lens1 = list(cc.CALLS[0][1]), list(cc.CALLS[1][1])
+    x0, x1 = cc.chain_batch(0).cuda(), cc.chain_batch(1).cuda()
+    B, L0 = x0.shape[0], x0.shape[2]
+    ya = torch.empty((B, L0), dtype=torch.float32, device="cuda")
+    ea._check(ea.lib.se_realtime_process_ragged(ea._h, ea._dev(x0), B, L0, (C.c_int64 * B)(*lens0), 0, ea._dev(ya, (B, L0)), ea._stream()))
+    ea.batch = B
+    yb = eb.realtime_process(x0, flag=[False] * B, lengths=lens0)
+    assert np.array_equal(ya.cpu().numpy(), yb.cpu().numpy())
+    for name in _state_names(TINY):
+        assert np.array_equal(ea.export_state(name), eb.export_state(name)), name
+    y2 = ea.realtime_process(x1, flag=True, lengths=lens1).cpu().numpy()
+    for b in range(B):
+        e1.realtime_process(x0[b:b + 1, :, :lens0[b]].contiguous(), flag=False)
+        alone = e1.realtime_process(x1[b:b + 1, :, :lens1[b]].contiguous(), flag=True).cpu().numpy()[0]
+        err = rel_rms(y2[b, :lens1[b]], alone)
+        print(f"ragged continuation stream {b} (length {lens1[b]}): rel rms {err:.3e}")
+        assert err < BAR_ALONE, (b, err)
+        assert np.all(y2[b, lens1[b]:] == 0.0), b
+
+
+@pytest.mark.parametrize("n_fft", [400, 512])
+def test_engine_and_training_handle_share_one_signal_chain(n_fft):
+    """Engine.stft / istft (se_stft, se_istft) and the training signal handle (train_stages._sig + se_sig_stft / se_sig_istft) on the same
+    6 rows of 3200 samples: one table builder and one launcher behind both, so after the layout transpose the results are bit-equal."""
+    from speech_enhancement_mi_amd import engine, train_stages as ts
+    from speech_enhancement_mi_amd import train_ops as K
+    cfg = dict(TINY, n_fft=n_fft, num_freqs=n_fft // 2 + 1)
+    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"], cfg["num_inputs"],
+                           cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
+    e = engine.Engine(c, 0)
+    n, Ks = 6, cfg["segment_length"]
+    seg = torch.from_numpy(np.random.default_rng(9).standard_normal((n, Ks)).astype(np.float32)).cuda()
+    sig = ts._sig(seg.device, n_fft, c.win, c.hop, Ks)
+    spec_e = e.stft(seg)                                                        # [n, F, T, 2]
+    spec_s = ts._stft(sig, seg.reshape(n, 1, Ks), n, 1, Ks, 0, Ks // 2, 1, e.T, e.F)[0]   # [n, T, F, 2]
+    assert np.array_equal(spec_e.permute(0, 2, 1, 3).cpu().numpy(), spec_s.cpu().numpy())
+    assert float(spec_s.abs().max()) > 1.0
+    wav_e = e.istft(spec_e)
+    wav_s = torch.empty((n, Ks), dtype=torch.float32, device="cuda")
+    K._chk(K._lib().se_sig_istft(sig, ts._p(spec_s.contiguous()), n, ts._p(wav_s), K._st()))
+    assert np.array_equal(wav_e.cpu().numpy(), wav_s.cpu().numpy())
+    assert rel_rms(wav_s.cpu().numpy(), seg.cpu().numpy()) < 1e-4   # sanity only: the pair inverts, so neither side compared empty buffers
+
+
+@pytest.mark.parametrize("frames", [16, 2])
+def test_fsn_engine_refuses_segments_of_at_most_16_frames(frames):
+    """FsnEngine with a segment of at most 16 frames (segment_length <= 15 hops; 16 hops = 17 frames is the first accepted, before and
+    after the engine got its own signal chain) raises at creation and names the frame floor.  The floor is inherited from the CRN geometry the engine's STFT used to be checked against, not FullSubNet's own
+    (DESIGN.md 7): this test pins the UNCHANGED acceptance, so that lifting the floor is a decision with a test of its own."""
+    from conftest import FSN_TINY
+    from speech_enhancement_mi_amd.engine import FsnEngine
+    cfg = FSN_TINY
+    hop = cfg["sample_rate"] // 1000 * cfg["hop_length"]
+
+    def make(seg):
+        return FsnEngine(cfg["num_freqs"], cfg["num_mics"], cfg["fb_model_hidden_size"], cfg["sb_model_hidden_size"], cfg["num_layers"],
+                         cfg["sb_num_neighbors"], cfg["fb_num_neighbors"], cfg["look_ahead"], cfg["sample_rate"], seg,
+                         cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
+    with pytest.raises(RuntimeError, match=f"{frames} frames per segment: more than 16 frames"):
+        make(hop * (frames - 1))
+    make(hop * 16).close()   # 17 frames: accepted
