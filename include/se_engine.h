@@ -507,6 +507,10 @@ int se_gbf_bf_bwd(const float *dY, const float *phi, const float *spec, const fl
  * se_gtsa_out: g rows [S T] (stride ldg: conv_trans at column o, conv_gated at 2F + o) -> gLN over 2F x T of trans * sigmoid(gated)
  *   with affine [2F], decompress_cIRM, times microphone 0 of spec -> Y [S][T][F][2]; tap (may be NULL) [S][2F][T] the mask before
  *   decompress_cIRM.
+ * Chunk chains (stream b has cnt[b] <= Nc windows of its own in the pass; cnt a device int64 [B], values outside [0, Nc] clamped):
+ * se_gtsa_tape_rows: se_gtsa_tape with every stream's tape ending after its own windows: ko / vo of stream b = tape rows
+ *   [cnt[b] T, cnt[b] T + maxlen) - the carried part itself where cnt[b] = 0; cnt[b] = Nc for all b is se_gtsa_tape bit for bit.
+ * se_gtsa_lastframes_rows: buf_out [B][5][2][Fs] = frames T - 2, T - 1 of x [(cnt[b] - 1) B + b], buf_in[b] where cnt[b] = 0 (T >= 2).
  * No atomics; reductions in a fixed order independent of S. */
 int se_gtsa_limits(int *max_frames, int *max_maxlen, int *max_norm_values);
 int se_gtsa_feat(const float *spec, float *x, int S, int M, int T, int F, int Fs, void *stream);
@@ -514,6 +518,9 @@ int se_gtsa_attn(const float *q, const float *kn, const float *vn, const float *
                  int ldk, int ldo, int S, int B, int U, int Hh, int D, int T, int maxlen, int model_dim, void *stream);
 int se_gtsa_tape(const float *kn, const float *vn, const float *kc, const float *vc, float *ko, float *vo, int ldk, int Nc, int B, int U, int Hh,
                  int D, int T, int maxlen, void *stream);
+int se_gtsa_tape_rows(const float *kn, const float *vn, const float *kc, const float *vc, float *ko, float *vo, const int64_t *cnt, int ldk, int Nc,
+                      int B, int U, int Hh, int D, int T, int maxlen, void *stream);
+int se_gtsa_lastframes_rows(const float *x, const float *buf_in, float *buf_out, const int64_t *cnt, int Nc, int B, int T, int Fs, void *stream);
 int se_gtsa_addnorm(const float *a, int lda, const float *x, float *y, const float *w, const float *b, int nseq, int T, int F, int Fs, void *stream);
 int se_gtsa_qkv5(const float *x, const float *wq, const float *bq, const float *wk, const float *bk, const float *wv, const float *bv, float *qkv,
                  int S, int T, int F, int Fs, void *stream);

@@ -13,12 +13,13 @@
 //   k_gtsa_feat     |X| of every microphone and atan2 phase differences (GTSA.py:279-284)
 //   k_gtsa_attn<D>  one workgroup per (stream, sequence, head): softmax(|Q K^T G / sqrt(model_dim)|) V over the window, keys walked in
 //                   tiles of 64 with a running maximum and sum; G from delta in the kernel; scores never leave the chip
-//   k_gtsa_tape     the carried K / V a call leaves behind
+//   k_gtsa_tape     the carried K / V a call leaves behind (k_gtsa_tape_rows: every stream's tape ends at its own window count)
 //   k_gtsa_addnorm  y = gLN(a + x) per (s, c) sequence over T x F, affine per f (even layers: after attention and after the FFN)
 //   k_gtsa_qkv5     the 5 x 5 q / k / v projections of an odd layer, written as rows [S][F][T][16] (q 0..4, k 5..9, v 10..14)
 //   k_gtsa_tail5    an odd layer after attention in one launch: output projection, residual, gLN, FFN 5 -> fn -> 5 (fn walked with
 //                   the 5-wide accumulator in registers, the hidden activation never stored), residual, gLN
 //   k_gtsa_gather3  the k = 3 convolution's GEMM rows: three frames (t - 2, t - 1, t) of all 5 F inputs per output frame
+//   k_gtsa_lastframes_rows  the two input frames last_conv carries on: the end of every stream's own last window of the pass
 //   k_gtsa_out      conv_trans * sigmoid(conv_gated), gLN over 2F x T, decompress_cIRM, complex product with microphone 0
 //
 // fp32 arithmetic, statistics combined in double, no atomics, every reduction in a fixed order that does not depend on S: results are
@@ -229,6 +230,37 @@ __global__ __launch_bounds__(kThreads) void k_gtsa_tape(TapeArgs a) {
     }
 }
 
+// chunk chains: stream b has cnt[b] <= Nc windows of its own in this pass, so its tape ends after cnt[b] windows.  Per element the copy
+// of k_gtsa_tape with Nc replaced by the stream's own count; cnt[b] = 0 copies the carried part.
+struct TapeRowsArgs {
+    TapeArgs t;
+    const long *cnt;  // [B], clamped to [0, Nc] here
+};
+
+__global__ __launch_bounds__(kThreads) void k_gtsa_tape_rows(TapeRowsArgs ar) {
+    const TapeArgs &a = ar.t;
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= a.total) return;
+    const int d = (int)(i % a.D);
+    const long row = i / a.D;
+    const int r = (int)(row % a.maxlen);
+    const long buh = row / a.maxlen;
+    const int h = (int)(buh % a.Hh);
+    const long bu = buh / a.Hh;  // b U + u
+    const long b = bu / a.U, u = bu - b * a.U;
+    const long c = ar.cnt[b];
+    const int own = c < 0 ? 0 : (c > a.Nc ? a.Nc : (int)c);
+    const int tr = own * a.T + r;  // tape row
+    if (tr < a.maxlen) {
+        const long off = (buh * a.maxlen + tr) * a.D + d;
+        a.ko[i] = a.kc[off]; a.vo[i] = a.vc[off];
+    } else {
+        const int rr = tr - a.maxlen, nn = rr / a.T, tt = rr - nn * a.T;  // nn < own
+        const long off = ((((long)nn * a.B + b) * a.U + u) * a.T + tt) * a.ldk + h * a.D + d;
+        a.ko[i] = a.kn[off]; a.vo[i] = a.vn[off];
+    }
+}
+
 // ---- even layers: residual + gLN per (s, c) sequence ---------------------------------------------------------------------------------
 struct NormArgs {
     const float *a;  // rows [nseq T] at stride lda
@@ -415,6 +447,24 @@ __global__ __launch_bounds__(kThreads) void k_gtsa_gather3(GatherArgs a) {
     for (int f = threadIdx.x; f < a.Fs; f += kThreads) dst[f] = src[f];
 }
 
+// chunk chains: the two-frame buffer a pass leaves behind is the last two frames of every stream's OWN last window of the pass
+struct LastFramesArgs {
+    const float *x;       // [Nc B][5][T][Fs]
+    const float *buf_in;  // [B][5][2][Fs]
+    float *buf_out;       // [B][5][2][Fs], not buf_in
+    const long *cnt;      // [B], clamped to [0, Nc] here
+    int Nc, B, T, Fs;
+};
+
+__global__ __launch_bounds__(kThreads) void k_gtsa_lastframes_rows(LastFramesArgs a) {
+    const int b = blockIdx.x, cj = blockIdx.y, c = cj >> 1, j = cj & 1;
+    const long n = a.cnt[b];
+    const int own = n < 0 ? 0 : (n > a.Nc ? a.Nc : (int)n);
+    const long o = (((long)b * kC + c) * 2 + j) * a.Fs;
+    const float *src = own == 0 ? a.buf_in + o : a.x + ((((long)(own - 1) * a.B + b) * kC + c) * a.T + a.T - 2 + j) * a.Fs;
+    for (int f = threadIdx.x; f < a.Fs; f += kThreads) a.buf_out[o + f] = src[f];
+}
+
 struct OutArgs {
     const float *g;      // rows [S T] at stride ldg: conv_trans output at column o, conv_gated at Co + o, Co = 2 F
     const float *nw, *nb;  // [Co]
@@ -521,6 +571,16 @@ int se_gtsa_tape(const float *kn, const float *vn, const float *kc, const float 
     return launched("se_gtsa_tape");
 }
 
+int se_gtsa_tape_rows(const float *kn, const float *vn, const float *kc, const float *vc, float *ko, float *vo, const int64_t *cnt, int ldk, int Nc,
+                      int B, int U, int Hh, int D, int T, int maxlen, void *stream) {
+    if (!kn || !vn || !kc || !vc || !ko || !vo || !cnt || ko == kc || vo == vc || Nc <= 0 || B <= 0 || U <= 0 || Hh <= 0 || D <= 0 || T <= 0 ||
+        maxlen <= 0 || ldk < Hh * D)
+        return se::train_fail(SE_ERR_ARG, "se_gtsa_tape_rows: null / bad argument (the new carried part is written out of place)");
+    TapeRowsArgs a{{kn, vn, kc, vc, ko, vo, ldk, Nc, B, U, Hh, D, T, maxlen, (long)B * U * Hh * maxlen * D}, reinterpret_cast<const long *>(cnt)};
+    hipLaunchKernelGGL(k_gtsa_tape_rows, dim3((unsigned)((a.t.total + kThreads - 1) / kThreads)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    return launched("se_gtsa_tape_rows");
+}
+
 int se_gtsa_addnorm(const float *a_, int lda, const float *x, float *y, const float *w, const float *b, int nseq, int T, int F, int Fs, void *stream) {
     if (!a_ || !x || !y || !w || !b || nseq <= 0 || T <= 0 || F <= 0 || Fs < F || lda < F) return se::train_fail(SE_ERR_ARG, "se_gtsa_addnorm: null / bad argument");
     if ((long)T * F > kNormMax) return se::train_fail(SE_ERR_ARG, "se_gtsa_addnorm: %d x %d values per sequence (at most %d)", T, F, kNormMax);
@@ -555,6 +615,14 @@ int se_gtsa_gather3(const float *x, const float *buf, float *A, int S, int B, in
     GatherArgs a{x, buf, A, B, T, Fs};
     hipLaunchKernelGGL(k_gtsa_gather3, dim3(S * T, 3 * kC), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     return launched("se_gtsa_gather3");
+}
+
+int se_gtsa_lastframes_rows(const float *x, const float *buf_in, float *buf_out, const int64_t *cnt, int Nc, int B, int T, int Fs, void *stream) {
+    if (!x || !buf_in || !buf_out || !cnt || buf_out == buf_in || Nc <= 0 || B <= 0 || B > 0x7fffffff / Nc || T < 2 || Fs <= 0)
+        return se::train_fail(SE_ERR_ARG, "se_gtsa_lastframes_rows: null / bad argument (out of place, at least 2 frames)");
+    LastFramesArgs a{x, buf_in, buf_out, reinterpret_cast<const long *>(cnt), Nc, B, T, Fs};
+    hipLaunchKernelGGL(k_gtsa_lastframes_rows, dim3(B, 2 * kC), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    return launched("se_gtsa_lastframes_rows");
 }
 
 int se_gtsa_out(const float *g, int ldg, const float *nw, const float *nb, const float *spec, float *Y, float *tap, int S, int M, int T, int F,

@@ -30,7 +30,7 @@ EXPORTS = [
     "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
     "se_train_add", "se_train_add3", "se_train_gate_fwd", "se_train_gate_bwd", "se_train_elu_bwd", "se_train_pre5", "se_train_gru_hprev", "se_train_conv_ws_floats", "se_train_conv_w", "se_train_conv_wgrad_det", "se_train_gemm_tn_det", "se_train_add_csum", "se_distill_ws_bytes",
     "se_distill_fwd", "se_distill_bwd", "se_sig_stft_rows", "se_train_ola_fwd_rows", "se_train_ola_bwd_rows", "se_train_slab_gather", "se_gbf_psd_fwd", "se_gbf_seq_fwd", "se_gbf_bf_fwd", "se_gbf_psd_bwd", "se_gbf_seq_bwd", "se_gbf_bf_bwd", "se_gtsa_limits", "se_gtsa_feat", "se_gtsa_attn", "se_gtsa_tape", "se_gtsa_addnorm", "se_gtsa_qkv5", "se_gtsa_tail5",
-    "se_gtsa_gather3", "se_gtsa_out", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
+    "se_gtsa_gather3", "se_gtsa_out", "se_gtsa_tape_rows", "se_gtsa_lastframes_rows", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
 ]
 
 
@@ -183,7 +183,9 @@ def load_library():
     L.se_gtsa_feat.argtypes = [vp] * 2 + [i32] * 5 + [vp]
     L.se_gtsa_attn.argtypes = [vp] * 7 + [i32] * 11 + [vp]
     L.se_gtsa_tape.argtypes = [vp] * 6 + [i32] * 8 + [vp]
-    L.se_gtsa_addnorm.argtypes = [vp, i32] + [vp] * 4 + [i32] * 4 + [vp]
+    L.se_gtsa_tape_rows.argtypes = [vp] * 7 + [i32] * 8 + [vp]
+    L.se_gtsa_lastframes_rows.argtypes = [vp] * 4 + [i32] * 4 + [vp]
+    L.se_gtsa_addnorm.argtypes =[vp, i32] + [vp] * 4 + [i32] * 4 + [vp]
     L.se_gtsa_qkv5.argtypes = [vp] * 8 + [i32] * 4 + [vp]
     L.se_gtsa_tail5.argtypes = [vp, i32] + [vp] * 12 + [i32] * 5 + [vp]
     L.se_gtsa_gather3.argtypes = [vp] * 3 + [i32] * 4 + [vp]

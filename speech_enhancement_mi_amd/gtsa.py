@@ -7,8 +7,8 @@ Same constructor (the ignored `num_heads` / `model_dim` included), state_dict ke
 `last_conv.net.0.*` aliases), same entry points:
 
     forward(x[B, M, F, T, 2]) -> [B, F, T, 2]          one window, stateful (GTSA.py:277-307)
-    realtime_process(mixture[B, M, L], flag=False) -> [B, L]   GTSA.py:370-407
-    reset(), use_hip_kernels(flag), kernel_geometry_error(), max_segments, _last_path
+    realtime_process(mixture[B, M, L], flag=False, lengths=None) -> [B, L]   GTSA.py:370-407; per-utterance flags / lengths: chunk chains
+    reset(), use_hip_kernels(flag), kernel_geometry_error(), max_segments, _last_path, _last_passes
 
 Within one layer, attention at window n reads keys and values of windows <= n of that layer's INPUT, never an attention output of the
 same layer: a layer has no sequential dependence across windows, so a call runs layer by layer with every window at once.  The rolling
@@ -22,6 +22,12 @@ Two paths:
   * the kernel path (`realtime_process` of a GPU tensor, grad disabled, eval mode): STFT / iSTFT / overlap-add of train_stages.py, the
     nn.Linear layers of the even layers and the three convolutions of `last_conv` on se_train_gemm, everything else on
     csrc/se_gtsa.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
+
+A call with per-utterance flags or lengths is a batch of B independent CHUNK CHAINS (call_plan.py): utterance b runs its own Nb[b] windows
+and leaves the state it would carry alone.  The restatement runs every utterance literally alone (`_torch_chains`); the kernel path sorts
+the streams by window count, so the streams still running at window n0 are a prefix, and every pass runs on that prefix only
+(`chain_passes`), the tape tail and the last_conv buffer stopping at each stream's own last window (se_gtsa_tape_rows,
+se_gtsa_lastframes_rows).
 """
 from __future__ import annotations
 
@@ -33,11 +39,18 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .call_plan import call_plan, overlap_add_cut, windows
-from .train_stages import _new, _p, _run, _sig, istft, overlap_add, stft
+from .call_plan import CallPlan, call_plan, overlap_add_cut, windows
+from .train_stages import _ip, _new, _p, _rows, _run, _sig, istft, overlap_add, slab_gather, stft
 
 EPS = 1e-8
 _DEFAULT_MAX_SEGMENTS = 8
+
+
+def chain_passes(Nb_sorted, step):
+    """The passes of a chunk-chain call whose streams are sorted by window count, descending: [(n0, Nc, Bp), ...] - windows
+    [n0, n0 + Nc) of the call, run on the Bp leading streams, the ones with a window of their own at n0 or later."""
+    N, step = max(Nb_sorted, default=0), max(1, int(step))
+    return [(n0, min(step, N - n0), sum(nb > n0 for nb in Nb_sorted)) for n0 in range(0, N, step)]
 
 
 class _Norm(nn.Module):  # GlobalLayerNorm(time=False), GTSA.py:74-129: denominator sqrt(var + 1e-10) + 1e-8
@@ -158,6 +171,7 @@ class GTSA(nn.Module):
         self._tstate = None   # restatement: dict(bk=[...], bv=[...] per layer [heads * Bs, maxlen, D], buf [B, C F, 2])
         self._kstate = None   # kernel path: dict(B, k=[...], v=[...] per layer [(b U + u) Hh + h][maxlen][D], buf [B][C][2][Fs])
         self._last_path = None
+        self._last_passes = None   # kernel path: the passes of the last call, [(first window, windows, streams), ...]
         self._wcache = {}
         self.taps = None      # restatement forward(): set to {} to receive feat / att0 / layer1 / last
 
@@ -287,18 +301,52 @@ class GTSA(nn.Module):
         y = torch.istft(Yc, self._cfg["n_fft"], self._hop, self._win, win, center=True, normalized=False, onesided=True).reshape(B, plan.N, -1)
         return overlap_add_cut(plan, y)
 
-    def realtime_process(self, mixture, flag=False):
+    def _torch_chains(self, mixture, plan):
+        """A batch of chunk chains on the restatement (the oracle of the kernel path): every utterance literally alone - B = 1, its own
+        length and flag, its own rows of the carried state - the outputs padded to the batch width, the states merged row by row.
+        bk / bv are head-major, [heads * B * U, maxlen, D] with row h (B U) + b U + u, so utterance b is [:, b] of [heads, B, U, ..]."""
+        B, Lmax = mixture.shape[0], mixture.shape[-1]
+        st = self._tstate
+        heads = [l.attention.num_heads for l in self.layers]
+        preds, states = [], []
+        try:
+            for b, (f, L) in enumerate(zip(plan.flags, plan.lengths)):
+                self._tstate = dict(buf=st["buf"][b:b + 1], **{k: [t.reshape(h, B, -1, *t.shape[1:])[:, b].reshape(-1, *t.shape[1:])
+                                                                   for t, h in zip(st[k], heads)] for k in ("bk", "bv")}) if f else None
+                own = call_plan(f, None, 1, L, self.segment_length, self._hop, self._cfg["n_fft"])
+                preds.append(Fn.pad(self._torch_process(mixture[b:b + 1, :, :L], own), (0, Lmax - L)))
+                states.append(self._tstate)
+        except BaseException:
+            self._tstate = st   # a call that fails leaves the previous state intact
+            raise
+        self._tstate = dict(buf=torch.cat([s["buf"] for s in states]),
+                            **{k: [torch.cat([s[k][i].reshape(h, 1, -1, *s[k][i].shape[1:]) for s in states], dim=1).flatten(0, 2)
+                                   for i, h in enumerate(heads)] for k in ("bk", "bv")})
+        return torch.cat(preds)
+
+    def realtime_process(self, mixture, flag=False, lengths=None):
+        """flag: a bool, one value, or one per utterance ([B] tensor / list); lengths: per-utterance lengths <= mixture.shape[-1] (None:
+        all full).  With either given per utterance the batch is B independent chunk chains (datagen.ChunkChainBatch), the semantics of
+        GeneralBeamformer.realtime_process: utterance b is mixture[b, :, :lengths[b]] (whatever the padding holds), starts from zero state
+        where flag[b] is False and continues row b of the carried state where it is True; pred[b, lengths[b]:] = 0, and the carried state
+        afterwards holds, per utterance, what that utterance alone would carry: rolling K / V buffers advanced by its own Nb[b] windows,
+        the last_conv buffer the last two frames of its own last window.  A batch whose flags and lengths are all alike takes the uniform
+        code path, as a bool flag does."""
         B, M, L = mixture.shape
-        plan = call_plan(flag, None, B, L, self.segment_length, self._hop, self._cfg["n_fft"])
-        if not plan.uniform:
-            raise ValueError("GTSA takes one flag for the whole batch (per-stream flags and lengths are not built for it yet)")
+        plan = call_plan(flag, lengths, B, L, self.segment_length, self._hop, self._cfg["n_fft"])
         path = "kernel" if self._hip and mixture.is_cuda and not torch.is_grad_enabled() and not self.training else "torch"
         if plan.any_flag and self._last_path not in (None, path):
             raise RuntimeError("flag=True continues the state of the other path (kernels vs restatement): start with flag=False")
+        if not plan.uniform and plan.any_flag:   # before any state is touched
+            st = self._kstate if path == "kernel" else self._tstate
+            have = None if st is None else st["buf"].shape[0]
+            if have != B:
+                raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is "
+                                 f"{'none' if have is None else 'one of ' + str(have)}")
         self._last_path = path
         if path == "kernel":
-            return self._kernel_process(mixture, plan)
-        return self._torch_process(mixture, plan)
+            return self._kernel_process(mixture, plan) if plan.uniform else self._kernel_chains(mixture, plan)
+        return self._torch_process(mixture, plan) if plan.uniform else self._torch_chains(mixture, plan)
 
     # ---- kernel path ---------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -367,12 +415,21 @@ class GTSA(nn.Module):
         return (5, 3, self.num_freqs // 3) if i % 2 == 0 else (self.num_freqs, 1, 5)
 
     def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, yseg, Fs, taps=None):
-        """Windows [n0, n0 + Nc) of the call: STFT, features, the layers, the output stage, iSTFT into yseg; advances `state`."""
+        """Windows [n0, n0 + Nc) of the call: STFT, features, the layers, the output stage, iSTFT into yseg; advances `state`.
+        Chunk chains: `plan` holds the streams of this pass (the leading plan.B rows of mixture and of every state tensor; yseg may be
+        wider), and the state stops at every stream's own last window of the pass."""
         lib, st, dev = K._lib(), K._st, mixture.device
         B, M, T, F, maxlen, fn = plan.B, mixture.shape[1], plan.T, plan.F0, self._cfg["maxlen"], self._cfg["fn_dim"]
         S = Nc * B
         rows = S * 5 * T
         even_w, conv_w = self._weights(Fs)
+        cnt = None if plan.uniform else _rows(plan.live(n0, Nc), dev)   # per stream: its own windows among the Nc of this pass
+
+        def tape(kn, vn, kc, vc, ko, vo, ldk, U, Hh, D):
+            if cnt is None:
+                _run("k_gtsa_tape", 0.0, lib.se_gtsa_tape, kn, vn, _p(kc), _p(vc), _p(ko), _p(vo), ldk, Nc, B, U, Hh, D, T, maxlen, st())
+            else:
+                _run("k_gtsa_tape", 0.0, lib.se_gtsa_tape_rows, kn, vn, _p(kc), _p(vc), _p(ko), _p(vo), _ip(cnt), ldk, Nc, B, U, Hh, D, T, maxlen, st())
         spec = stft(plan, sig, mixture, M, n0, Nc)
         x = _new(S, 5, T, Fs, dev=dev)
         _run("k_gtsa_feat", 0.0, lib.se_gtsa_feat, _p(spec), _p(x), S, M, T, F, Fs, st())
@@ -389,7 +446,7 @@ class GTSA(nn.Module):
                 qkv = K._gemm(x.view(rows, Fs), w["wqkv"], w["bqkv"])     # [rows][3F]
                 kn, vn, ldk = _p(qkv, F), _p(qkv, 2 * F), 3 * F
                 _run("k_gtsa_attn", 0.0, lib.se_gtsa_attn, _p(qkv), kn, vn, _p(kc), _p(vc), _p(att), _p(a.delta), ldk, ldk, Fs, S, B, U, Hh, D, T, maxlen, F, st())
-                _run("k_gtsa_tape", 0.0, lib.se_gtsa_tape, kn, vn, _p(kc), _p(vc), _p(ko), _p(vo), ldk, Nc, B, U, Hh, D, T, maxlen, st())
+                tape(kn, vn, kc, vc, ko, vo, ldk, U, Hh, D)
                 del qkv
                 o = K._gemm(att, w["wo"], a.linear.bias)                  # [rows][F]
                 if taps is not None and i == 0:
@@ -407,7 +464,7 @@ class GTSA(nn.Module):
                 kn, vn = _p(qkv, 5), _p(qkv, 10)
                 at5 = _new(S, F, T, 8, dev=dev)
                 _run("k_gtsa_attn", 0.0, lib.se_gtsa_attn, _p(qkv), kn, vn, _p(kc), _p(vc), _p(at5), _p(a.delta), 16, 16, 8, S, B, U, Hh, D, T, maxlen, 5, st())
-                _run("k_gtsa_tape", 0.0, lib.se_gtsa_tape, kn, vn, _p(kc), _p(vc), _p(ko), _p(vo), 16, Nc, B, U, Hh, D, T, maxlen, st())
+                tape(kn, vn, kc, vc, ko, vo, 16, U, Hh, D)
                 del qkv
                 _run("k_gtsa_tail5", 0.0, lib.se_gtsa_tail5, _p(at5), 8, _p(x), _p(x), _p(a.linear.weight), _p(a.linear.bias), _p(layer.norm_a.weight),
                      _p(layer.norm_a.bias), _p(layer.linear_in.weight), _p(layer.linear_in.bias), _p(layer.linear_out.weight), _p(layer.linear_out.bias),
@@ -418,7 +475,12 @@ class GTSA(nn.Module):
                 taps["layer1"] = x.clone()
         A = _new(S * T, 15 * Fs, dev=dev)
         _run("k_gtsa_gather3", 0.0, lib.se_gtsa_gather3, _p(x), _p(state["buf"]), _p(A), S, B, T, Fs, st())
-        state["buf"] = x[S - B:, :, T - 2:, :].contiguous()
+        if cnt is None:
+            state["buf"] = x[S - B:, :, T - 2:, :].contiguous()
+        else:
+            buf = torch.empty_like(state["buf"])
+            _run("k_gtsa_lastframes", 0.0, lib.se_gtsa_lastframes_rows, _p(x), _p(state["buf"]), _p(buf), _ip(cnt), Nc, B, T, Fs, st())
+            state["buf"] = buf
         g1 = K._gemm(A, conv_w["w1"], conv_w["b1"])
         del A
         g2 = K._gemm(g1, conv_w["w2"], conv_w["b2"])                     # [S T][2 * 2F]: conv_trans | conv_gated
@@ -428,7 +490,12 @@ class GTSA(nn.Module):
         _run("k_gtsa_out", 0.0, lib.se_gtsa_out, _p(g2), 4 * F, _p(lc.norm.weight), _p(lc.norm.bias), _p(spec), _p(Y), _p(tap), S, M, T, F, st())
         if taps is not None:
             taps["last"] = tap
-        istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
+        if yseg.shape[1] == B:
+            istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
+        else:   # a prefix pass: yseg is window-major at the whole batch's stride, so its rows go in window by window
+            part = _new(Nc, B, plan.Ks, dev=dev)
+            istft(sig, Y, part.view(-1, plan.Ks))
+            yseg[n0:n0 + Nc, :B].copy_(part)
 
     @torch.no_grad()
     def _kernel_process(self, mixture, plan, taps=None):
@@ -460,4 +527,61 @@ class GTSA(nn.Module):
             self._kernel_pass(mixture, plan, sig, state, n0, min(step, plan.N - n0), yseg, Fs, taps)
         pred = overlap_add(plan, sig, yseg)
         self._kstate = state
+        self._last_passes = [(n0, min(step, plan.N - n0), B) for n0 in range(0, plan.N, step)]
+        return pred
+
+    @torch.no_grad()
+    def _kernel_chains(self, mixture, plan):
+        """A batch of chunk chains on the kernels.  The streams are sorted by window count (descending, stable), so the streams with a
+        window at n0 or later are a prefix: pass (n0, Nc, Bp) of chain_passes runs on the leading Bp rows of the sorted mixture, tables
+        and state - every layout is stream-major.  A stream leaves the working state for its row of the new carried state when the
+        prefix drops it; the streams still in the prefix at the end follow.  pred is un-sorted by the same index."""
+        err = self.kernel_geometry_error()
+        if err:
+            raise ValueError(f"GTSA kernel path: {err}")
+        K._need_gpu(mixture, self.last_conv.conv.weight)
+        dev = mixture.device
+        B, M, L = mixture.shape
+        if M != self._cfg["num_mics"]:
+            raise ValueError(f"GTSA kernel path: {M} microphones, the model is built for {self._cfg['num_mics']}")
+        F, maxlen, n_fft = self.num_freqs, self._cfg["maxlen"], self._cfg["n_fft"]
+        Fs = (F + 7) // 8 * 8
+        order = sorted(range(B), key=lambda b: -plan.Nb[b])
+        order_dev = _rows(order, dev)
+        sub = {B: CallPlan([plan.flags[b] for b in order], [plan.lengths[b] for b in order], L, self.segment_length, self._hop, n_fft, uniform=False)}
+        sp = sub[B]
+        mix = mixture.float().index_select(0, order_dev)
+        shapes = [self._seq_shape(i) for i in range(len(self.layers))]
+        if plan.any_flag:   # the carried row where the flag is set, zeros elsewhere - start_rows' gather, reading the rows in sorted order
+            carry = _rows([b if plan.flags[b] else -1 for b in order], dev)
+            start = lambda t: slab_gather(t, carry, B, t.numel() // B, t.numel() // B, 0).view(t.shape)   # noqa: E731
+            state = dict(k=[start(t) for t in self._kstate["k"]], v=[start(t) for t in self._kstate["v"]], buf=start(self._kstate["buf"]))
+        else:
+            state = dict(k=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes],
+                         v=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes], buf=torch.zeros(B, 5, 2, Fs, device=dev))
+        new = dict(B=B, k=[torch.empty_like(t) for t in state["k"]], v=[torch.empty_like(t) for t in state["v"]], buf=torch.empty_like(state["buf"]))
+
+        def retire(lo, hi, cur):
+            """rows [lo, hi) of the working state (cur streams, sorted) -> their own rows of the new carried state; rows [0, lo) stay"""
+            def move(t, o):
+                o.view(B, -1).index_copy_(0, order_dev[lo:hi], t.view(cur, -1)[lo:hi])
+                return t[:t.shape[0] // cur * lo]
+            state["k"] = [move(t, o) for t, o in zip(state["k"], new["k"])]
+            state["v"] = [move(t, o) for t, o in zip(state["v"], new["v"])]
+            state["buf"] = move(state["buf"], new["buf"])
+
+        sig = _sig(dev, n_fft, self._win, self._hop, self.segment_length)
+        yseg = torch.zeros(sp.N, B, sp.Ks, device=dev)   # windows a prefix pass never writes stay zero
+        passes = chain_passes(sp.Nb, self.max_segments)
+        cur = B
+        for n0, Nc, Bp in passes:
+            if Bp < cur:
+                retire(Bp, cur, cur)
+                cur = Bp
+                sub[Bp] = CallPlan(sp.flags[:Bp], sp.lengths[:Bp], L, self.segment_length, self._hop, n_fft, uniform=False)
+            self._kernel_pass(mix[:Bp], sub[Bp], sig, state, n0, Nc, yseg, Fs)
+        retire(0, cur, cur)
+        pred = torch.empty(B, L, device=dev).index_copy_(0, order_dev, overlap_add(sp, sig, yseg))
+        self._kstate = new
+        self._last_passes = passes
         return pred
