@@ -5,7 +5,7 @@ optional per-utterance `lengths`.  `call_plan` reads them (a tensor once, here: 
 triages: one flag for all and every utterance Lmax long is a UNIFORM call, carrying `segment_geometry`'s values and taking the scalar
 kernels; anything else is a batch of B independent CHUNK CHAINS (datagen.ChunkChainBatch), carrying `ragged_geometry`'s and taking the
 `_rows` kernels.  The result is a `CallPlan`; train_stages.py's signal-chain helpers, the three autograd Functions and the torch
-restatements (`windows`, `overlap_add_cut` below) take it and never look at `flag` again.
+restatements (`windows`, `stft_windows`, `istft_windows`, `overlap_add_cut` below) take it and never look at `flag` again.
 
 Pure Python and torch-free at import (tensors are handled by duck typing), so engine.py and train_stages.py both import it: the
 geometry arithmetic (`_chunk`) and the flag parser (`flags_of`) exist once.  tests/test_chain_plan_cpu.py holds the arithmetic equal
@@ -155,3 +155,25 @@ def overlap_add_cut(plan, y):
     if plan.uniform:
         return full[:, plan.skip:plan.skip + plan.L]
     return torch.stack([Fn.pad(full[b, s:s + L], (0, plan.L - L)) for b, (L, s) in enumerate(zip(plan.lengths, plan.skip))])
+
+
+def _hamming(win, like, dtype):
+    import torch
+    return torch.hamming_window(win, device=like.device, dtype=dtype)
+
+
+def stft_windows(seg, n_fft, hop, win, window_dtype):
+    """stft_trans of windows [..., Ks] -> complex [..., F, T] (torch.stft as speechbrain's STFT wrapper calls it).  window_dtype: the
+    Hamming window's - the drop-in models take the input's, the training restatements float32 whatever the input is."""
+    import torch
+    X = torch.stft(seg.reshape(-1, seg.shape[-1]), n_fft, hop, win, _hamming(win, seg, window_dtype), center=True, pad_mode="constant",
+                   normalized=False, onesided=True, return_complex=True)
+    return X.reshape(*seg.shape[:-1], *X.shape[-2:])
+
+
+def istft_windows(spec, n_fft, hop, win, window_dtype):
+    """complex [..., F, T] -> windows [..., Ks], the inverse of stft_windows"""
+    import torch
+    y = torch.istft(spec.reshape(-1, *spec.shape[-2:]), n_fft, hop, win, _hamming(win, spec, window_dtype), center=True, normalized=False,
+                    onesided=True)
+    return y.reshape(*spec.shape[:-2], y.shape[-1])

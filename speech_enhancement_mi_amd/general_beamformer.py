@@ -9,6 +9,7 @@ last decoder block included), same entry points:
                                                         lengths the batch is B independent chunk chains (all three paths)
     reset(), compute_loss(source, pred_source, length)
 
+The call's contract, the choice of path, the refusals and the carried state are streaming.StreamingMixin's, shared with gtsa.GTSA.
 Two interchangeable paths:
   * the torch restatement (`forward`, and `realtime_process` on the CPU, with grad enabled, or after use_hip_kernels(False)): plain
     torch ops, differentiable, so train.py can train the model through autograd.  The GRU cell is written out (no nn.GRU forward,
@@ -26,22 +27,17 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .call_plan import call_plan, overlap_add_cut, segment_geometry, windows
+from .call_plan import segment_geometry
+from .crn import _Deconv, _Norm as _NormParams, _Seq
+from .streaming import StreamingMixin
 from .train_stages import (_cs, _new, _p, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd, encoder_block_fwd, gemm_tn,
                            grads_in_parameter_order, gru_layer_bwd, gru_steps, gru_steps_bwd, input_features, istft, overlap_add, own_last_slab,
                            start_rows, stft, synthesis_adjoint)
 
 EPS = 1e-8
-_DEFAULT_MAX_SEGMENTS = 8
 
 
-class _Norm(nn.Module):  # GlobalLayerNorm parameter holder, GeneralBeamformer.py:22-34
-    def __init__(self, dim, last=False):
-        super().__init__()
-        shape = (1, 1, 1, dim) if last else (1, dim, 1, 1)
-        self.weight = nn.Parameter(torch.ones(shape))
-        self.bias = nn.Parameter(torch.zeros(shape))
-
+class _Norm(_NormParams):  # crn.py's GlobalLayerNorm parameter holder, callable: `linear` is an nn.Sequential that runs through its norm
     def forward(self, x):
         return _gln(x, self)
 
@@ -54,7 +50,7 @@ def _gln(x, norm):
     return (x - mean) / (torch.sqrt(var + EPS) + EPS) * norm.weight + norm.bias
 
 
-class _Conv(nn.Module):  # TemporalConv2d, GeneralBeamformer.py:155-205
+class _Conv(nn.Module):  # TemporalConv2d, GeneralBeamformer.py:155-205; crn.py's holder has no `padding`, the restatement's time history
     def __init__(self, cin, cout, k, dil, dropout):
         super().__init__()
         self.padding = (k - 1) * dil
@@ -62,26 +58,6 @@ class _Conv(nn.Module):  # TemporalConv2d, GeneralBeamformer.py:155-205
         self.dropout = nn.Dropout(dropout)
         self.net = nn.Sequential(self.conv, self.dropout)
         self.norm = _Norm(cout)
-
-
-class _Deconv(nn.Module):  # TemporalConvTranspose2d, GeneralBeamformer.py:208-263
-    def __init__(self, cin, cout, k, dil, dropout):
-        super().__init__()
-        self.conv = nn.ConvTranspose2d(cin, cout, (5, k), stride=(2, 1), padding=(2, 0), dilation=(1, dil))
-        self.dropout = nn.Dropout(dropout)
-        self.net = nn.Sequential(self.conv, self.dropout)
-        self.residualmask = nn.Conv2d(cout, cout, (1, 1))
-        self.residualnorm = _Norm(cout)
-        self.residual = nn.Conv2d(cout, cout, (1, 1))
-        self.norm = _Norm(cout)
-
-
-class _SequenceModel(nn.Module):  # SequenceModel(9, hidden, num_layers, GRU, ReLU), GeneralBeamformer.py:64-152
-    def __init__(self, size, hidden, num_layers):
-        super().__init__()
-        self.sequence_model = nn.GRU(size, hidden, num_layers, batch_first=True)
-        self.fc_output_layer = nn.Linear(hidden, size)
-        self.norm = _Norm(size, last=True)
 
 
 def _gru(x, g, h0):
@@ -105,7 +81,7 @@ def _gru(x, g, h0):
     return x, torch.stack(hs)
 
 
-class GeneralBeamformer(nn.Module):
+class GeneralBeamformer(StreamingMixin, nn.Module):
     def __init__(self, num_channels, num_freqs, hidden, segment_length, num_layers=1, num_inputs=3, kernel_size=3, dropout=0.0,
                  sample_rate=16000, win_length=25, hop_length=10, n_fft=400):
         super().__init__()
@@ -114,8 +90,10 @@ class GeneralBeamformer(nn.Module):
         self.num_time = segment_length // 160 + 1
         self._cfg = dict(num_channels=list(num_channels), hidden=hidden, num_layers=num_layers, num_inputs=num_inputs,
                          kernel_size=kernel_size, sample_rate=sample_rate, win_length=win_length, hop_length=hop_length, n_fft=n_fft)
-        self._win = int(round(sample_rate / 1000.0 * win_length))
-        self._hop = int(round(sample_rate / 1000.0 * hop_length))
+        # _tstate: dict(buf=[...], hS, hN); _kstate: dict(B, buf=[...], h=[[...], [...]]); taps: xl / phi_s / seq_s / seq_n / w of every
+        # forward; max_segments bounds the inference passes only, GBFFunction (training) runs every segment of a call in one pass
+        self._init_streaming(num_inputs, sample_rate, win_length, hop_length)
+        self._hip_train = False
         L = len(num_channels)
         convs, deconvs = [], []
         for i in range(L):
@@ -127,29 +105,11 @@ class GeneralBeamformer(nn.Module):
         self.deconvlist = nn.ModuleList(deconvs)
         self.ln_S = _Norm(num_freqs * self.num_time)
         self.ln_N = _Norm(num_freqs * self.num_time)
-        self.gru_S = _SequenceModel(num_inputs * num_inputs, hidden, num_layers)
-        self.gru_N = _SequenceModel(num_inputs * num_inputs, hidden, num_layers)
+        self.gru_S = _Seq(num_inputs * num_inputs, hidden, num_layers)
+        self.gru_N = _Seq(num_inputs * num_inputs, hidden, num_layers)
         self.linear = nn.Sequential(nn.Linear(9, hidden), nn.ReLU(), _Norm(num_freqs), nn.Linear(hidden, 6))
-        self.max_segments = _DEFAULT_MAX_SEGMENTS  # segments per inference kernel pass: bounds peak memory; the state carries across
-        #                                            passes.  GBFFunction (training) runs every segment of a call in one pass.
-        self._hip = True
-        self._hip_train = False
-        self._tstate = None   # restatement: dict(buf=[...], hS, hN)
-        self._kstate = None   # kernel path: dict(B, buf=[...], h=[[...], [...]])
-        self._last_path = None
-        self._pad_cache = {}
-        self.taps = None      # restatement: set to {} to receive the intermediate tensors of every forward
 
     # ---- reference contract ------------------------------------------------------------------------------------------------
-    def reset(self):
-        self._tstate = None
-        self._kstate = None
-
-    def use_hip_kernels(self, flag=True):
-        """True (default): realtime_process of a GPU tensor with grad disabled runs on the kernels; False: always the restatement."""
-        self._hip = bool(flag)
-        return self
-
     def compute_loss(self, source, pred_source, length):
         """loss = 0.7 * stoi_loss + 0.3 * (-SI-SNR), NaN -> zeros (GeneralBeamformer.py:500-523); returns (loss, stoi, sisnr)."""
         from .losses import compute_loss
@@ -171,33 +131,24 @@ class GeneralBeamformer(nn.Module):
         self._hip_train = bool(flag)
         return self
 
-    def realtime_process(self, mixture, flag=False, lengths=None):
-        """flag: a bool, one value, or one per utterance ([B] tensor / list); lengths: per-utterance lengths <= mixture.shape[-1] (None:
-        all full).  With either given per utterance the batch is B independent chunk chains (datagen.ChunkChainBatch), the semantics of
-        train_net.realtime_process_fused: utterance b is zero beyond lengths[b] (whatever the padding holds), starts from zero state where
-        flag[b] is False and continues row b of the carried state where it is True; pred[b, lengths[b]:] = 0, and the carried state
-        afterwards holds, per utterance, what that utterance alone would carry.  A batch whose flags and lengths are all alike takes the
-        uniform code path, as a bool flag does."""
-        B, M, Lmax = mixture.shape
-        c = self._cfg
-        plan = call_plan(flag, lengths, B, Lmax, self.segment_length, self._hop, c["n_fft"], [2 * M - 1] + c["num_channels"])
+    def _plan_channels(self, M):
+        return [2 * M - 1] + self._cfg["num_channels"]
+
+    def _choose_path(self, mixture):
         grad = torch.is_grad_enabled()
-        train = self._hip_train and mixture.is_cuda and grad
-        path = "kernel" if train or (self._hip and mixture.is_cuda and not grad) else "torch"
-        if plan.any_flag and self._last_path not in (None, path):
-            raise RuntimeError("flag=True continues the state of the other path (kernels vs restatement): start with flag=False")
-        if train:
-            err = self.hip_training_error()
-            if err:
-                raise ValueError(f"GeneralBeamformer HIP training: {err}")
-            params = [p for _, p in self.named_parameters()]
-            out = GBFFunction.apply(self, mixture, plan, *params)
-            self._last_path = path
-            return out
-        self._last_path = path
-        if path == "kernel":
-            return self._kernel_process(mixture, plan)
-        return self._torch_process(mixture, plan.flag) if plan.uniform else self._torch_chains(mixture, plan.flags, plan.lengths)
+        if self._hip_train and mixture.is_cuda and grad:
+            return "train"
+        return "kernel" if self._hip and mixture.is_cuda and not grad else "torch"
+
+    def _train_call(self, mixture, plan):
+        err = self.hip_training_error()
+        if err:
+            raise ValueError(f"GeneralBeamformer HIP training: {err}")
+        return GBFFunction.apply(self, mixture, plan, *[p for _, p in self.named_parameters()])
+
+    @staticmethod
+    def _batch_of(state):
+        return state["buf"][0].shape[0]
 
     # ---- torch restatement ---------------------------------------------------------------------------------------------------
     def _segment(self, x, st):
@@ -274,44 +225,20 @@ class GeneralBeamformer(nn.Module):
         o = torch.relu(sm.fc_output_layer(o))
         return _gln(o.unsqueeze(1), sm.norm).squeeze(1), hT
 
-    def spectrum(self, seg):
-        """stft_trans of the segments [B, M, N, K] -> [B, M, N, F, T, 2] (torch.stft; speechbrain's STFT wrapper)."""
-        B, M, N, Ks = seg.shape
-        win = torch.hamming_window(self._win, device=seg.device, dtype=seg.dtype)
-        X = torch.stft(seg.reshape(-1, Ks), self._cfg["n_fft"], self._hop, self._win, win, center=True, pad_mode="constant", normalized=False,
-                       onesided=True, return_complex=True)
-        return torch.view_as_real(X).reshape(B, M, N, *X.shape[-2:], 2)
+    def _torch_windows(self, X, st):
+        outs = []
+        for n in range(X.shape[2]):
+            y, st = self._segment(X[:, :, n], st)
+            outs.append(y)
+        return torch.stack(outs, dim=1), st
 
-    def _torch_process(self, mixture, flag):
-        B, M, L = mixture.shape
-        if not flag:
-            self._tstate = None
-        n_fft = self._cfg["n_fft"]
-        plan = call_plan(flag, None, B, L, self.segment_length, self._hop, n_fft)
-        X = self.spectrum(windows(plan, mixture))
-        outs = [self.forward(X[:, :, n]) for n in range(plan.N)]
-        win = torch.hamming_window(self._win, device=mixture.device, dtype=mixture.dtype)
-        Y = torch.view_as_complex(torch.stack(outs, dim=1).reshape(B * plan.N, *outs[0].shape[1:]).contiguous())
-        y = torch.istft(Y, n_fft, self._hop, self._win, win, center=True, normalized=False, onesided=True).reshape(B, plan.N, -1)
-        return overlap_add_cut(plan, y)
+    def _state_row(self, st, b, B):
+        F = self.num_freqs   # hS / hN: [layers, B * F, H]
+        return dict(buf=[t[b:b + 1] for t in st["buf"]], hS=st["hS"][:, b * F:(b + 1) * F], hN=st["hN"][:, b * F:(b + 1) * F])
 
-    def _torch_chains(self, mixture, flags, lens):
-        """A batch of chunk chains on the restatement (the oracle of the kernel paths): every utterance alone on its own rows of the
-        carried state, the results merged."""
-        B = mixture.shape[0]
-        st = self._tstate
-        if any(flags) and (st is None or st["buf"][0].shape[0] != B):
-            raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is "
-                             f"{'none' if st is None else 'one of ' + str(st['buf'][0].shape[0])}")
-        F = self.num_freqs
-        preds, states = [], []
-        for b, (f, L) in enumerate(zip(flags, lens)):
-            self._tstate = dict(buf=[t[b:b + 1] for t in st["buf"]], hS=st["hS"][:, b * F:(b + 1) * F], hN=st["hN"][:, b * F:(b + 1) * F]) if f else None
-            preds.append(Fn.pad(self._torch_process(mixture[b:b + 1, :, :L], f), (0, mixture.shape[-1] - L)))
-            states.append(self._tstate)
-        self._tstate = dict(buf=[torch.cat([s_["buf"][i] for s_ in states]) for i in range(len(self.convlist))],
-                            hS=torch.cat([s_["hS"] for s_ in states], dim=1), hN=torch.cat([s_["hN"] for s_ in states], dim=1))
-        return torch.cat(preds)
+    def _state_merge(self, rows):
+        return dict(buf=[torch.cat([r["buf"][i] for r in rows]) for i in range(len(self.convlist))],
+                    hS=torch.cat([r["hS"] for r in rows], dim=1), hN=torch.cat([r["hN"] for r in rows], dim=1))
 
     # ---- kernel path ---------------------------------------------------------------------------------------------------------
     def kernel_geometry_error(self):
@@ -347,12 +274,7 @@ class GeneralBeamformer(nn.Module):
     def _padded_w_ih(self, g):
         """W_ih_l0 [3H][9] zero-padded to [3H][16] (the GEMM's K % 8), once per parameter version."""
         w = g.weight_ih_l0
-        key = (id(g), w.data_ptr(), w._version)
-        if self._pad_cache.get(id(g), (None,))[0] != key:
-            wp = torch.zeros(w.shape[0], 16, device=w.device, dtype=torch.float32)
-            wp[:, :w.shape[1]].copy_(w.detach())
-            self._pad_cache[id(g)] = (key, wp)
-        return self._pad_cache[id(g)][1]
+        return self._cached(("w_ih", id(g)), [w], lambda: Fn.pad(w.float(), (0, 16 - w.shape[1])))
 
     def hip_training_error(self):
         """None when GBFFunction can train this model as it stands, else the limit that fails (geometry, or active dropout)."""
@@ -373,11 +295,7 @@ class GeneralBeamformer(nn.Module):
         T, F0, ch, Fq, Lv = plan.T, plan.F0, plan.ch, plan.Fq, len(self.convlist)
         g = dict(plan.geo, plan=plan, L=L, B=B, M=M, n_fft=c["n_fft"], H=H, NL=NL, Lv=Lv, BF=B * F0,
                  sig=_sig(dev, c["n_fft"], self._win, self._hop, self.segment_length))
-        state = self._kstate if plan.any_flag else None
-        if not plan.uniform and plan.any_flag and state is None:
-            raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is none")
-        if state is not None and state["B"] != B:
-            raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
+        state = self._kstate if plan.any_flag else None   # realtime_process has refused a state of another batch size
         if state is not None:
             state = dict(B=B, buf=[start_rows(plan, t) for t in state["buf"]], h=[[start_rows(plan, t) for t in hq] for hq in state["h"]])
         else:
@@ -481,13 +399,9 @@ class GeneralBeamformer(nn.Module):
 
     @torch.no_grad()
     def _kernel_process(self, mixture, plan):
-        err = self.kernel_geometry_error()
-        if err:
-            raise ValueError(f"GeneralBeamformer kernel path: {err}")
         if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist)):
             raise ValueError("GeneralBeamformer kernel path: inference only (dropout is active in training mode; use the restatement)")
-        K._need_gpu(mixture, self.ln_S.weight)
-        pred, g, tmo = self._kernel_run(mixture.contiguous().float(), plan)
+        pred, g, tmo = self._kernel_run(mixture, plan)
         self._check_timeouts(tmo, g)
         return pred
 

@@ -16,7 +16,8 @@ buffer is a TAPE per (sequence, head): the carried buffer in rows [0, maxlen), t
 it; window n attends to rows [(n + 1) T, (n + 1) T + maxlen) - the reference's cat([bk[:, T:], k]) applied n + 1 times - and the call
 leaves the last maxlen rows behind.  The two-frame input buffer of `last_conv` is the previous window's last two input frames.
 
-Two paths:
+Two paths (the call's contract, the choice between them, the refusals and the carried state: streaming.StreamingMixin, shared with
+general_beamformer.GeneralBeamformer):
   * the torch restatement (CPU, grad enabled, training mode, or after use_hip_kernels(False)): plain torch ops, differentiable.
     `realtime_process` uses the tape, `forward` the reference's window-by-window form, both on the same state.
   * the kernel path (`realtime_process` of a GPU tensor, grad disabled, eval mode): STFT / iSTFT / overlap-add of train_stages.py, the
@@ -24,7 +25,7 @@ Two paths:
     csrc/se_gtsa.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
 
 A call with per-utterance flags or lengths is a batch of B independent CHUNK CHAINS (call_plan.py): utterance b runs its own Nb[b] windows
-and leaves the state it would carry alone.  The restatement runs every utterance literally alone (`_torch_chains`); the kernel path sorts
+and leaves the state it would carry alone.  The restatement runs every utterance literally alone (streaming.py's `_torch_call`); the kernel path sorts
 the streams by window count, so the streams still running at window n0 are a prefix, and every pass runs on that prefix only
 (`chain_passes`), the tape tail and the last_conv buffer stopping at each stream's own last window (se_gtsa_tape_rows,
 se_gtsa_lastframes_rows).
@@ -39,11 +40,11 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .call_plan import CallPlan, call_plan, overlap_add_cut, windows
+from .call_plan import CallPlan
+from .streaming import StreamingMixin
 from .train_stages import _ip, _new, _p, _rows, _run, _sig, istft, overlap_add, slab_gather, stft
 
 EPS = 1e-8
-_DEFAULT_MAX_SEGMENTS = 8
 
 
 def chain_passes(Nb_sorted, step):
@@ -152,39 +153,24 @@ class _LastConv(nn.Module):  # TemporalConv1d(activation=None), GTSA.py:11-72
         return self.conv_trans(out) * torch.sigmoid(self.conv_gated(out))
 
 
-class GTSA(nn.Module):
+class GTSA(StreamingMixin, nn.Module):
     def __init__(self, num_mics, num_freqs, segment_length, num_layers, num_heads, model_dim, fn_dim, maxlen=500, dropout=0.0,
                  sample_rate=16000, win_length=25, hop_length=10, n_fft=400):
         super().__init__()
         self.segment_length = segment_length
         self.num_freqs = num_freqs
         self._cfg = dict(num_mics=num_mics, num_layers=num_layers, fn_dim=fn_dim, maxlen=maxlen, dropout=dropout, n_fft=n_fft)
-        self._win = int(round(sample_rate / 1000.0 * win_length))
-        self._hop = int(round(sample_rate / 1000.0 * hop_length))
+        self._init_streaming(num_mics, sample_rate, win_length, hop_length)
+        # _tstate: dict(bk=[...], bv=[...] per layer [heads * Bs, maxlen, D], buf [B, C F, 2]); _kstate: dict(B, k=[...], v=[...] per
+        # layer [(b U + u) Hh + h][maxlen][D], buf [B][C][2][Fs]); taps: feat / att0 / layer1 / last of every forward
         C_ = 2 * num_mics - 1
         # num_heads / model_dim are accepted and ignored, as in the reference (GTSA.py:268-272)
         self.last_conv = _LastConv(num_freqs * C_, num_freqs * 2, dropout)
         self.layers = nn.ModuleList([_Layer(3, num_freqs, fn_dim, maxlen, dropout) if i % 2 == 0 else _Layer(1, C_, fn_dim, maxlen, dropout)
                                      for i in range(num_layers)])
-        self.max_segments = _DEFAULT_MAX_SEGMENTS   # windows per kernel pass (and per restatement tape pass): bounds peak memory
-        self._hip = True
-        self._tstate = None   # restatement: dict(bk=[...], bv=[...] per layer [heads * Bs, maxlen, D], buf [B, C F, 2])
-        self._kstate = None   # kernel path: dict(B, k=[...], v=[...] per layer [(b U + u) Hh + h][maxlen][D], buf [B][C][2][Fs])
-        self._last_path = None
         self._last_passes = None   # kernel path: the passes of the last call, [(first window, windows, streams), ...]
-        self._wcache = {}
-        self.taps = None      # restatement forward(): set to {} to receive feat / att0 / layer1 / last
 
     # ---- reference contract ------------------------------------------------------------------------------------------------
-    def reset(self):
-        self._tstate = None
-        self._kstate = None
-
-    def use_hip_kernels(self, flag=True):
-        """True (default): realtime_process of a GPU tensor with grad disabled, in eval mode, runs on the kernels; False: the restatement."""
-        self._hip = bool(flag)
-        return self
-
     def load_state_dict(self, state_dict, strict=True, **kw):
         """Checkpoints the reference saved after a run carry the rolling buffers (`layers.i.attention.bk` / `.bv`): dropped."""
         sd = {k: v for k, v in state_dict.items() if not k.endswith((".attention.bk", ".attention.bv"))}
@@ -273,80 +259,35 @@ class GTSA(nn.Module):
         Y = self._mask_apply(m, X[:, 0])
         return Y, dict(bk=bk, bv=bv, buf=inp[..., -2:].detach())
 
-    def spectrum(self, seg):
-        """stft_trans of the windows [B, M, N, K] -> [B, M, N, F, T, 2] (torch.stft; speechbrain's STFT wrapper)"""
-        B, M, N, Ks = seg.shape
-        win = torch.hamming_window(self._win, device=seg.device, dtype=seg.dtype)
-        X = torch.stft(seg.reshape(-1, Ks), self._cfg["n_fft"], self._hop, self._win, win, center=True, pad_mode="constant", normalized=False,
-                       onesided=True, return_complex=True)
-        return torch.view_as_real(X).reshape(B, M, N, *X.shape[-2:], 2)
-
-    def _torch_process(self, mixture, plan):
-        B, M, L = mixture.shape
-        if not plan.flag:
-            self._tstate = None
-        if self._tstate is not None and self._tstate["buf"].shape[0] != B:
-            raise ValueError(f"flag=True continues a batch of {self._tstate['buf'].shape[0]} utterances, got {B}")
-        X = self.spectrum(windows(plan, mixture))
-        st = self._tstate if self._tstate is not None else self._fresh_state(X[..., 0, 0, 0], B)
+    def _torch_windows(self, X, st):
+        """tape passes of max_segments windows"""
+        st = st if st is not None else self._fresh_state(X[..., 0, 0, 0], X.shape[0])
         outs = []
         step = max(1, int(self.max_segments))
-        for n0 in range(0, plan.N, step):
+        for n0 in range(0, X.shape[2], step):
             Y, st = self._tape_pass(X[:, :, n0:n0 + step], st)
             outs.append(Y)
-        self._tstate = st
-        Y = torch.cat(outs, dim=1)                    # [B, N, F, T, 2]
-        win = torch.hamming_window(self._win, device=mixture.device, dtype=mixture.dtype)
-        Yc = torch.view_as_complex(Y.reshape(B * plan.N, *Y.shape[2:]).contiguous())
-        y = torch.istft(Yc, self._cfg["n_fft"], self._hop, self._win, win, center=True, normalized=False, onesided=True).reshape(B, plan.N, -1)
-        return overlap_add_cut(plan, y)
+        return torch.cat(outs, dim=1), st
 
-    def _torch_chains(self, mixture, plan):
-        """A batch of chunk chains on the restatement (the oracle of the kernel path): every utterance literally alone - B = 1, its own
-        length and flag, its own rows of the carried state - the outputs padded to the batch width, the states merged row by row.
-        bk / bv are head-major, [heads * B * U, maxlen, D] with row h (B U) + b U + u, so utterance b is [:, b] of [heads, B, U, ..]."""
-        B, Lmax = mixture.shape[0], mixture.shape[-1]
-        st = self._tstate
-        heads = [l.attention.num_heads for l in self.layers]
-        preds, states = [], []
-        try:
-            for b, (f, L) in enumerate(zip(plan.flags, plan.lengths)):
-                self._tstate = dict(buf=st["buf"][b:b + 1], **{k: [t.reshape(h, B, -1, *t.shape[1:])[:, b].reshape(-1, *t.shape[1:])
-                                                                   for t, h in zip(st[k], heads)] for k in ("bk", "bv")}) if f else None
-                own = call_plan(f, None, 1, L, self.segment_length, self._hop, self._cfg["n_fft"])
-                preds.append(Fn.pad(self._torch_process(mixture[b:b + 1, :, :L], own), (0, Lmax - L)))
-                states.append(self._tstate)
-        except BaseException:
-            self._tstate = st   # a call that fails leaves the previous state intact
-            raise
-        self._tstate = dict(buf=torch.cat([s["buf"] for s in states]),
-                            **{k: [torch.cat([s[k][i].reshape(h, 1, -1, *s[k][i].shape[1:]) for s in states], dim=1).flatten(0, 2)
-                                   for i, h in enumerate(heads)] for k in ("bk", "bv")})
-        return torch.cat(preds)
+    def _heads(self):
+        return [l.attention.num_heads for l in self.layers]
 
-    def realtime_process(self, mixture, flag=False, lengths=None):
-        """flag: a bool, one value, or one per utterance ([B] tensor / list); lengths: per-utterance lengths <= mixture.shape[-1] (None:
-        all full).  With either given per utterance the batch is B independent chunk chains (datagen.ChunkChainBatch), the semantics of
-        GeneralBeamformer.realtime_process: utterance b is mixture[b, :, :lengths[b]] (whatever the padding holds), starts from zero state
-        where flag[b] is False and continues row b of the carried state where it is True; pred[b, lengths[b]:] = 0, and the carried state
-        afterwards holds, per utterance, what that utterance alone would carry: rolling K / V buffers advanced by its own Nb[b] windows,
-        the last_conv buffer the last two frames of its own last window.  A batch whose flags and lengths are all alike takes the uniform
-        code path, as a bool flag does."""
-        B, M, L = mixture.shape
-        plan = call_plan(flag, lengths, B, L, self.segment_length, self._hop, self._cfg["n_fft"])
-        path = "kernel" if self._hip and mixture.is_cuda and not torch.is_grad_enabled() and not self.training else "torch"
-        if plan.any_flag and self._last_path not in (None, path):
-            raise RuntimeError("flag=True continues the state of the other path (kernels vs restatement): start with flag=False")
-        if not plan.uniform and plan.any_flag:   # before any state is touched
-            st = self._kstate if path == "kernel" else self._tstate
-            have = None if st is None else st["buf"].shape[0]
-            if have != B:
-                raise ValueError(f"flag=True continues row b of the carried state of a batch of {B} utterances: there is "
-                                 f"{'none' if have is None else 'one of ' + str(have)}")
-        self._last_path = path
-        if path == "kernel":
-            return self._kernel_process(mixture, plan) if plan.uniform else self._kernel_chains(mixture, plan)
-        return self._torch_process(mixture, plan) if plan.uniform else self._torch_chains(mixture, plan)
+    def _state_row(self, st, b, B):
+        """bk / bv are head-major, [heads * B * U, maxlen, D] with row h (B U) + b U + u, so utterance b is [:, b] of [heads, B, U, ..]"""
+        return dict(buf=st["buf"][b:b + 1], **{k: [t.reshape(h, B, -1, *t.shape[1:])[:, b].reshape(-1, *t.shape[1:])
+                                                   for t, h in zip(st[k], self._heads())] for k in ("bk", "bv")})
+
+    def _state_merge(self, rows):
+        return dict(buf=torch.cat([r["buf"] for r in rows]),
+                    **{k: [torch.cat([r[k][i].reshape(h, 1, -1, *r[k][i].shape[1:]) for r in rows], dim=1).flatten(0, 2)
+                           for i, h in enumerate(self._heads())] for k in ("bk", "bv")})
+
+    def _choose_path(self, mixture):
+        return "kernel" if self._hip and mixture.is_cuda and not torch.is_grad_enabled() and not self.training else "torch"
+
+    @staticmethod
+    def _batch_of(state):
+        return state["buf"].shape[0]
 
     # ---- kernel path ---------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -379,14 +320,6 @@ class GTSA(nn.Module):
             return f"fn_dim = {fn}: the GEMM's inner dimension must be a multiple of 8"
         return None
 
-    def _cached(self, name, params, make):
-        """make() of some parameters, once per parameter version"""
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._wcache.get(name, (None,))[0] != key:
-            with torch.no_grad():
-                self._wcache[name] = (key, make())
-        return self._wcache[name][1]
-
     def _weights(self, Fs):
         """GEMM operands: K padded to Fs per F-row, q / k / v stacked, the k = 3 convolution as [2F padded to 8][3 * 5 * Fs]"""
         F = self.num_freqs
@@ -414,7 +347,7 @@ class GTSA(nn.Module):
         """(U sequences per utterance, heads, head width) of layer i"""
         return (5, 3, self.num_freqs // 3) if i % 2 == 0 else (self.num_freqs, 1, 5)
 
-    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, yseg, Fs, taps=None):
+    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, yseg, Fs):
         """Windows [n0, n0 + Nc) of the call: STFT, features, the layers, the output stage, iSTFT into yseg; advances `state`.
         Chunk chains: `plan` holds the streams of this pass (the leading plan.B rows of mixture and of every state tensor; yseg may be
         wider), and the state stops at every stream's own last window of the pass."""
@@ -433,8 +366,6 @@ class GTSA(nn.Module):
         spec = stft(plan, sig, mixture, M, n0, Nc)
         x = _new(S, 5, T, Fs, dev=dev)
         _run("k_gtsa_feat", 0.0, lib.se_gtsa_feat, _p(spec), _p(x), S, M, T, F, Fs, st())
-        if taps is not None:
-            taps["feat"] = x.clone()
         att = torch.zeros(rows, Fs, device=dev)   # even layers write columns < F only: the GEMM reads the pad as zeros
         for i, layer in enumerate(self.layers):
             a = layer.attention
@@ -449,8 +380,6 @@ class GTSA(nn.Module):
                 tape(kn, vn, kc, vc, ko, vo, ldk, U, Hh, D)
                 del qkv
                 o = K._gemm(att, w["wo"], a.linear.bias)                  # [rows][F]
-                if taps is not None and i == 0:
-                    taps["att0"] = o.clone()
                 _run("k_gtsa_addnorm", 0.0, lib.se_gtsa_addnorm, _p(o), F, _p(x), _p(x), _p(layer.norm_a.weight), _p(layer.norm_a.bias), S * 5, T, F, Fs, st())
                 hid = K._gemm(x.view(rows, Fs), w["win"], layer.linear_in.bias, act=1)
                 o = K._gemm(hid, layer.linear_out.weight, layer.linear_out.bias)
@@ -471,8 +400,6 @@ class GTSA(nn.Module):
                      _p(layer.norm_i.weight), _p(layer.norm_i.bias), S, T, F, Fs, fn, st())
                 del at5
             state["k"][i], state["v"][i] = ko, vo
-            if taps is not None and i == 1:
-                taps["layer1"] = x.clone()
         A = _new(S * T, 15 * Fs, dev=dev)
         _run("k_gtsa_gather3", 0.0, lib.se_gtsa_gather3, _p(x), _p(state["buf"]), _p(A), S, B, T, Fs, st())
         if cnt is None:
@@ -486,10 +413,7 @@ class GTSA(nn.Module):
         g2 = K._gemm(g1, conv_w["w2"], conv_w["b2"])                     # [S T][2 * 2F]: conv_trans | conv_gated
         lc = self.last_conv
         Y = _new(S, T, F, 2, dev=dev)
-        tap = _new(S, 2 * F, T, dev=dev) if taps is not None else None
-        _run("k_gtsa_out", 0.0, lib.se_gtsa_out, _p(g2), 4 * F, _p(lc.norm.weight), _p(lc.norm.bias), _p(spec), _p(Y), _p(tap), S, M, T, F, st())
-        if taps is not None:
-            taps["last"] = tap
+        _run("k_gtsa_out", 0.0, lib.se_gtsa_out, _p(g2), 4 * F, _p(lc.norm.weight), _p(lc.norm.bias), _p(spec), _p(Y), None, S, M, T, F, st())
         if yseg.shape[1] == B:
             istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
         else:   # a prefix pass: yseg is window-major at the whole batch's stride, so its rows go in window by window
@@ -498,68 +422,37 @@ class GTSA(nn.Module):
             yseg[n0:n0 + Nc, :B].copy_(part)
 
     @torch.no_grad()
-    def _kernel_process(self, mixture, plan, taps=None):
-        err = self.kernel_geometry_error()
-        if err:
-            raise ValueError(f"GTSA kernel path: {err}")
-        K._need_gpu(mixture, self.last_conv.conv.weight)
-        mixture = mixture.contiguous().float()
+    def _kernel_process(self, mixture, plan):
+        """One call on the kernels.  Chains: the streams are sorted by window count (descending, stable), so the streams with a window
+        at n0 or later are a prefix: pass (n0, Nc, Bp) of chain_passes runs on the leading Bp rows of the sorted mixture, tables and
+        state - every layout is stream-major.  A stream leaves the working state for its row of the new carried state when the prefix
+        drops it; the streams still in the prefix at the end follow.  pred is un-sorted by the same index.  A uniform call is the
+        identity order with all B streams in every pass: nothing is sorted, gathered or scattered, and the working state is the new one."""
         dev = mixture.device
         B, M, L = mixture.shape
-        if M != self._cfg["num_mics"]:
-            raise ValueError(f"GTSA kernel path: {M} microphones, the model is built for {self._cfg['num_mics']}")
-        F, maxlen = self.num_freqs, self._cfg["maxlen"]
-        Fs = (F + 7) // 8 * 8
-        state = self._kstate if plan.flag else None
-        if state is not None and state["B"] != B:
-            raise ValueError(f"flag=True continues a batch of {state['B']} utterances, got {B}")
-        if state is None:
-            shapes = [self._seq_shape(i) for i in range(len(self.layers))]
-            state = dict(B=B, k=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes],
-                         v=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes], buf=torch.zeros(B, 5, 2, Fs, device=dev))
-        else:
-            state = dict(B=B, k=list(state["k"]), v=list(state["v"]), buf=state["buf"])
-        self._kstate = None   # a call that fails leaves no half-advanced state behind
-        sig = _sig(dev, self._cfg["n_fft"], self._win, self._hop, self.segment_length)
-        yseg = _new(plan.N, B, plan.Ks, dev=dev)
-        step = max(1, int(self.max_segments))
-        for n0 in range(0, plan.N, step):
-            self._kernel_pass(mixture, plan, sig, state, n0, min(step, plan.N - n0), yseg, Fs, taps)
-        pred = overlap_add(plan, sig, yseg)
-        self._kstate = state
-        self._last_passes = [(n0, min(step, plan.N - n0), B) for n0 in range(0, plan.N, step)]
-        return pred
-
-    @torch.no_grad()
-    def _kernel_chains(self, mixture, plan):
-        """A batch of chunk chains on the kernels.  The streams are sorted by window count (descending, stable), so the streams with a
-        window at n0 or later are a prefix: pass (n0, Nc, Bp) of chain_passes runs on the leading Bp rows of the sorted mixture, tables
-        and state - every layout is stream-major.  A stream leaves the working state for its row of the new carried state when the
-        prefix drops it; the streams still in the prefix at the end follow.  pred is un-sorted by the same index."""
-        err = self.kernel_geometry_error()
-        if err:
-            raise ValueError(f"GTSA kernel path: {err}")
-        K._need_gpu(mixture, self.last_conv.conv.weight)
-        dev = mixture.device
-        B, M, L = mixture.shape
-        if M != self._cfg["num_mics"]:
-            raise ValueError(f"GTSA kernel path: {M} microphones, the model is built for {self._cfg['num_mics']}")
         F, maxlen, n_fft = self.num_freqs, self._cfg["maxlen"], self._cfg["n_fft"]
         Fs = (F + 7) // 8 * 8
-        order = sorted(range(B), key=lambda b: -plan.Nb[b])
-        order_dev = _rows(order, dev)
-        sub = {B: CallPlan([plan.flags[b] for b in order], [plan.lengths[b] for b in order], L, self.segment_length, self._hop, n_fft, uniform=False)}
-        sp = sub[B]
-        mix = mixture.float().index_select(0, order_dev)
-        shapes = [self._seq_shape(i) for i in range(len(self.layers))]
-        if plan.any_flag:   # the carried row where the flag is set, zeros elsewhere - start_rows' gather, reading the rows in sorted order
-            carry = _rows([b if plan.flags[b] else -1 for b in order], dev)
-            start = lambda t: slab_gather(t, carry, B, t.numel() // B, t.numel() // B, 0).view(t.shape)   # noqa: E731
-            state = dict(k=[start(t) for t in self._kstate["k"]], v=[start(t) for t in self._kstate["v"]], buf=start(self._kstate["buf"]))
-        else:
+        old = self._kstate if plan.any_flag else None
+        if old is None:
+            shapes = [self._seq_shape(i) for i in range(len(self.layers))]
             state = dict(k=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes],
                          v=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes], buf=torch.zeros(B, 5, 2, Fs, device=dev))
-        new = dict(B=B, k=[torch.empty_like(t) for t in state["k"]], v=[torch.empty_like(t) for t in state["v"]], buf=torch.empty_like(state["buf"]))
+        if plan.uniform:
+            sp, mix = plan, mixture
+            if old is not None:
+                state = dict(k=list(old["k"]), v=list(old["v"]), buf=old["buf"])
+            yseg = _new(plan.N, B, plan.Ks, dev=dev)
+        else:
+            order = sorted(range(B), key=lambda b: -plan.Nb[b])
+            order_dev = _rows(order, dev)
+            sp = CallPlan([plan.flags[b] for b in order], [plan.lengths[b] for b in order], L, self.segment_length, self._hop, n_fft, uniform=False)
+            mix = mixture.index_select(0, order_dev)
+            if old is not None:   # the carried row where the flag is set, zeros elsewhere - start_rows' gather, reading the rows in sorted order
+                carry = _rows([b if plan.flags[b] else -1 for b in order], dev)
+                start = lambda t: slab_gather(t, carry, B, t.numel() // B, t.numel() // B, 0).view(t.shape)   # noqa: E731
+                state = dict(k=[start(t) for t in old["k"]], v=[start(t) for t in old["v"]], buf=start(old["buf"]))
+            new = dict(B=B, k=[torch.empty_like(t) for t in state["k"]], v=[torch.empty_like(t) for t in state["v"]], buf=torch.empty_like(state["buf"]))
+            yseg = torch.zeros(sp.N, B, sp.Ks, device=dev)   # windows a prefix pass never writes stay zero
 
         def retire(lo, hi, cur):
             """rows [lo, hi) of the working state (cur streams, sorted) -> their own rows of the new carried state; rows [0, lo) stay"""
@@ -571,17 +464,20 @@ class GTSA(nn.Module):
             state["buf"] = move(state["buf"], new["buf"])
 
         sig = _sig(dev, n_fft, self._win, self._hop, self.segment_length)
-        yseg = torch.zeros(sp.N, B, sp.Ks, device=dev)   # windows a prefix pass never writes stay zero
         passes = chain_passes(sp.Nb, self.max_segments)
-        cur = B
+        sub, cur = {B: sp}, B
         for n0, Nc, Bp in passes:
-            if Bp < cur:
+            if Bp < cur:   # chains only: a uniform plan keeps all B streams to the end
                 retire(Bp, cur, cur)
                 cur = Bp
                 sub[Bp] = CallPlan(sp.flags[:Bp], sp.lengths[:Bp], L, self.segment_length, self._hop, n_fft, uniform=False)
             self._kernel_pass(mix[:Bp], sub[Bp], sig, state, n0, Nc, yseg, Fs)
-        retire(0, cur, cur)
-        pred = torch.empty(B, L, device=dev).index_copy_(0, order_dev, overlap_add(sp, sig, yseg))
+        pred = overlap_add(sp, sig, yseg)
+        if plan.uniform:
+            new = dict(B=B, **state)
+        else:
+            retire(0, cur, cur)
+            pred = torch.empty(B, L, device=dev).index_copy_(0, order_dev, pred)
         self._kstate = new
         self._last_passes = passes
         return pred

@@ -22,7 +22,7 @@ from .crn import TemporalCRN
 from .crn_elu import TemporalCRN as TemporalCRNELU
 from .distillation_crn import TemporalCRN as TemporalStudentCRN
 from .losses import cal_si_snr
-from .call_plan import as_flags, as_lengths, call_plan, overlap_add_cut, segment_geometry, windows
+from .call_plan import as_flags, as_lengths, call_plan, istft_windows, overlap_add_cut, segment_geometry, stft_windows, windows
 
 EPS = 1e-8
 
@@ -68,17 +68,10 @@ class _TrainableMixin:
         return windows(plan, x), plan.gap
 
     def _stft(self, seg):  # [..., K] -> [..., F, T] complex
-        shp = seg.shape[:-1]
-        w = torch.hamming_window(self._win, device=seg.device)
-        s = torch.stft(seg.reshape(-1, seg.shape[-1]), self._nfft, self._hop, self._win, w, center=True, pad_mode="constant",
-                       normalized=False, onesided=True, return_complex=True)
-        return s.reshape(*shp, *s.shape[-2:])
+        return stft_windows(seg, self._nfft, self._hop, self._win, torch.float32)
 
     def _istft(self, spec):  # [..., F, T] complex -> [..., K]
-        shp = spec.shape[:-2]
-        w = torch.hamming_window(self._win, device=spec.device)
-        y = torch.istft(spec.reshape(-1, *spec.shape[-2:]), self._nfft, self._hop, self._win, w, center=True, normalized=False, onesided=True)
-        return y.reshape(*shp, y.shape[-1])
+        return istft_windows(spec, self._nfft, self._hop, self._win, torch.float32)
 
     # ---- one segment, CRN.py:454-496 (variant 0) / CRN_ELU.py:367-407 (variant 1) / distillation_crn.py:337-380 (variant 2) ----
     def _forward_segment(self, X, state, feats=None):

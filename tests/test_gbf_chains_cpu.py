@@ -1,5 +1,6 @@
 """GeneralBeamformer.realtime_process(mixture, flag, lengths) on a batch of chunk chains, torch restatement on the CPU: every utterance
-of a mixed-flag, mixed-length batch gets what it would get alone, the uniform case is the bool call, bad arguments raise."""
+of a mixed-flag, mixed-length batch gets what it would get alone, the uniform case is the bool call, bad arguments raise, and a refused
+call names its cause and leaves the carried state (streaming.StreamingMixin.realtime_process, as for GTSA)."""
 import os
 import sys
 
@@ -87,3 +88,27 @@ def test_bad_flags_and_lengths_raise():
     m.realtime_process(x[:2], False)
     with pytest.raises(ValueError):
         m.realtime_process(x, [True, False, True], lengths=[4800, 3200, 100])   # a carried state of another batch size
+
+
+@torch.no_grad()
+def test_refusals_name_the_cause_and_leave_the_state():
+    m = make_model()
+    mix = torch.from_numpy(synth.synth_utterances(3, 3200, 3, seed=7)[0])
+    with pytest.raises(ValueError, match="there is none"):          # a flag set, nothing carried
+        m.realtime_process(mix, flag=[True, False, True])
+    m.realtime_process(mix[:2], flag=[False, False], lengths=[3200, 1000])
+    kept = m._tstate
+    with pytest.raises(ValueError, match="one of 2"):               # the carried state belongs to another batch size
+        m.realtime_process(mix, flag=[True, False, True])
+    with pytest.raises(ValueError, match="flags for a batch of 2"):  # call_plan: a flag count other than 1 or B
+        m.realtime_process(mix[:2], flag=[True, False, True])
+    with pytest.raises(ValueError, match="lengths must be 2 values"):
+        m.realtime_process(mix[:2], flag=[True, False], lengths=[3200, 3201])
+    assert m._tstate is kept
+    with pytest.raises(ValueError, match="a batch of 2 utterances, got 3"):   # a uniform continuation of another batch size
+        m.realtime_process(mix, flag=True)
+    assert m._tstate is kept
+    m._last_path = "kernel"                                          # the carried state belongs to the other path
+    with pytest.raises(RuntimeError, match="other path"):
+        m.realtime_process(mix[:2], flag=[True, False])
+    assert m._tstate is kept

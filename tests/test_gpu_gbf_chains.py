@@ -209,6 +209,22 @@ def test_mixed_flags_without_a_carried_state_of_that_batch_raise():
             m.realtime_process(chain_batch(1).to(DEV), list(CALLS[1][0]), lengths=list(CALLS[1][1]))
 
 
+def test_a_refused_chains_call_leaves_the_carried_state():
+    """a flag set, a carried batch of 2, a call of 3: refused before the state is touched, and the chain of 2 goes on as if never asked"""
+    m, clean = make_model("tiny"), make_model("tiny")
+    (f0, l0), (f1, l1) = ((list(f), list(l)) for f, l in CALLS)
+    x0, x1 = chain_batch(0).to(DEV), chain_batch(1).to(DEV)
+    with torch.no_grad():
+        m.realtime_process(x0[:2], f0[:2], lengths=l0[:2])
+        kept = m._kstate
+        with pytest.raises(ValueError, match="one of 2"):
+            m.realtime_process(x1, f1, lengths=l1)
+        assert m._kstate is kept
+        y = m.realtime_process(x1[:2], f1[:2], lengths=l1[:2])
+        clean.realtime_process(x0[:2], f0[:2], lengths=l0[:2])
+        assert torch.equal(y, clean.realtime_process(x1[:2], f1[:2], lengths=l1[:2]))
+
+
 # ---- GBFFunction -------------------------------------------------------------------------------------------------------------------------
 def _flat_grad(m):
     return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).flatten() for p in m.parameters()])

@@ -1,7 +1,7 @@
-"""GPU tests of GTSA chunk chains on the kernel path (gtsa.GTSA._kernel_chains, se_gtsa_tape_rows, se_gtsa_lastframes_rows): the two
+"""GPU tests of GTSA chunk chains on the kernel path (gtsa.GTSA._kernel_process, se_gtsa_tape_rows, se_gtsa_lastframes_rows): the two
 per-stream copy kernels exactly against indexing, a batch of chains bit-equal to every stream alone through the uniform kernel path
 (outputs and carried state, whatever the pass split), the pass schedule, the genuine reference's fixture, the restatement's chains
-form, and the refusals.  Window counts at segment_length 3200: a reset of 1600 / 4800 / 6400 / 9600 samples has 4 / 6 / 8 / 10 windows,
+form, the refusals, and the uniform call as the chains runner's identity case.  Window counts at segment_length 3200: a reset of 1600 / 4800 / 6400 / 9600 samples has 4 / 6 / 8 / 10 windows,
 a continuation of <= 1599 / 3200 / 4800 / 8000 samples 2 / 4 / 6 / 8."""
 import os
 
@@ -193,3 +193,35 @@ def test_refusals_leave_the_carried_state():
         m.realtime_process(x1[:2], flag=[True, False], lengths=l1[:2])
     x2 = x1[..., :3200].contiguous()
     assert torch.equal(m.realtime_process(x2, flag=True), clean.realtime_process(x2, flag=True))   # and a uniform continuation
+
+
+@torch.no_grad()
+def test_a_refused_chains_call_leaves_the_carried_state():
+    """a flag set, a carried batch of 2, a call of 3: refused before the state is touched, and the chain of 2 goes on as if never asked"""
+    (_, x0, f0, l0), (_, x1, f1, l1) = scenario(CALLS[:2], 3, 120)
+    m, clean = make_model("tiny"), make_model("tiny")
+    m.realtime_process(x0[:2], flag=f0[:2], lengths=l0[:2])
+    kept = m._kstate
+    with pytest.raises(ValueError, match="one of 2"):
+        m.realtime_process(x1, flag=f1, lengths=l1)
+    assert m._kstate is kept
+    y = m.realtime_process(x1[:2], flag=f1[:2], lengths=l1[:2])
+    clean.realtime_process(x0[:2], flag=f0[:2], lengths=l0[:2])
+    assert torch.equal(y, clean.realtime_process(x1[:2], flag=f1[:2], lengths=l1[:2]))
+
+
+# ---- the uniform call -------------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def test_uniform_call_is_the_chains_runner_with_every_stream_in_every_pass():
+    """B = 2: a reset of 4800 samples (6 windows), then a continuation of 3200 (4 windows), in passes of 3.  Against the same two calls
+    forced onto the chains form - stream 1 one sample short, which leaves its window count as it is - on stream 0's samples."""
+    mix = torch.from_numpy(synth.synth_utterances(2, 8000, 3, seed=130)[0]).to(DEV)
+    uni, chains = make_model("tiny"), make_model("tiny")
+    uni.max_segments = chains.max_segments = 3
+    for (a, b), f, passes in (((0, 4800), False, [(0, 3, 2), (3, 3, 2)]), ((4800, 8000), True, [(0, 3, 2), (3, 1, 2)])):
+        x = mix[..., a:b].contiguous()
+        yu = uni.realtime_process(x, flag=f)
+        assert uni._last_path == "kernel" and uni._last_passes == passes
+        yc = chains.realtime_process(x, flag=[f, f], lengths=[b - a, b - a - 1])
+        assert chains._last_passes == passes
+        assert torch.isfinite(yu).all() and torch.equal(yu[0], yc[0]), f
