@@ -7,6 +7,7 @@
 //   bottleneck (unchanged GEMM / GRU kernels) -> k_gln2_p -> P
 //   3 x ( k_conv_p both parities -> R parity-planar ; k_skip_p, or k_conv_p 1x1 statistics pass + 1x1 with fused skip gate -> P )
 //   k_conv_p (both parities merged, 4 GEMM rows) -> R ; k_final_mask_p
+// (from a waveform: k_stft_feat in place of k_stft + k_featurize_p, k_mask_istft in place of k_final_mask_p + k_istft, io_fused.hip.h)
 //
 // The ring slot r of encoder level i is xinP[i] + r * slot_elems (ONE allocation per level, so that the history slot is
 // addressable through the same buffer descriptor as the current one).
@@ -541,15 +542,32 @@ int alloc_state_p(se_engine *e, hipStream_t st) {
     return 0;
 }
 
+// The fused front end (io_fused.hip.h: k_stft_feat): STFT of the segment at `off` of every stream's microphones -> the feature octets in
+// ring slot `cur` (pinP[0] where the pre-conv blocks run on the plane path, xinP[0] otherwise) and microphone 0's spectrum -> spec0 [b][t][f].
+// Writes the ring slot, so it runs where k_featurize_p would: on the encoder's stream, after the slot's last reader.
+bool stft_feat_route(const se_engine *e) { return e->io_fuse_on && (!e->variant || e->cp->pre_p); }
+
+int stage_stft_feat_p(se_engine *e, int cur, const float *src, long strideB, long strideM, long off, long Lsrc, SigRows rows, cf2 *spec0, hipStream_t st) {
+    se_convp_state &S = *e->cp;
+    const int T = e->T, PL = operand_planes(e->precision), TF = T * e->F[0];
+    uint4 *feat = e->variant ? reinterpret_cast<uint4 *>(S.pinP[0].p) + (long)cur * S.pslot_elems
+                             : reinterpret_cast<uint4 *>(S.xinP[0].p) + (long)cur * S.slot_elems[0];
+    ProfScope ps(e, "k_stft_feat", "stft_feat", 0, st);
+    HIPCHECK(e, sig_stft_feat(e->sig, src, strideB, strideM, e->M, off, Lsrc, rows, e->Bact, spec0, (long)TF, e->F[0], 1, feat, (long)PL * TF, PL,
+                              e->atan2_phase, st));
+    return 0;
+}
+
 // Stage 1 (plane path): features + encoder -> xinP[*][cur], gru_in[cur] (fp32, the bottleneck GEMM's A operand)
-int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st) {
+// feat_done: stage_stft_feat_p has already written the slot's features (spec is then not read)
+int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st, bool feat_done = false) {
     se_convp_state &S = *e->cp;
     const int L = e->L, T = e->T, B = e->B, PL = operand_planes(e->precision);
     const int Ba = e->Bact;  // launch batch: the prefix of streams that take part in this segment (se_realtime_process_ragged), B otherwise
     int rc;
     if (e->variant && S.pre_p) {  // features and the three pre-conv blocks x = m(x) + x on the plane path
         const int TF = T * e->F[0], C0 = e->Ch[0];
-        {
+        if (!feat_done) {
             ProfScope ps(e, "k_featurize_p", "featurize", 0, st);
             FeatPArgs f{spec, sB, sM, sT, sF, reinterpret_cast<uint4 *>(S.pinP[0].p) + (long)cur * S.pslot_elems, (long)PL * TF, e->M, T, e->F[0], e->atan2_phase};
             launch_k_featurize_p(PL, dim3((TF + 255) / 256, Ba), st, f);
@@ -585,7 +603,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
         F32ToPArgs f{e->xin[0][cur].p, reinterpret_cast<uint4 *>(S.xinP[0].p) + (long)cur * S.slot_elems[0], (long)PL * TF, e->Ch[0], TF};
         launch_k_f32_to_p(PL, dim3((TF + 255) / 256, Ba), st, f);
         HIPCHECK(e, hipGetLastError());
-    } else {
+    } else if (!feat_done) {
         ProfScope ps(e, "k_featurize_p", "featurize", 0, st);
         const int TF = T * e->F[0];
         FeatPArgs f{spec, sB, sM, sT, sF, reinterpret_cast<uint4 *>(S.xinP[0].p) + (long)cur * S.slot_elems[0], (long)PL * TF, e->M, T, e->F[0], e->atan2_phase};
@@ -649,7 +667,10 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
 }
 
 // Stage 3 (plane path): decoder + mask.  The bottleneck's k_gln2_p has already written decinP[cur].
-int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, long sF, cf2 *out, long oB, long oT, long oF, hipStream_t st) {
+// wav (optional): the fused back end (io_fused.hip.h: k_mask_istft) takes the place of k_final_mask_p and writes stream b's K samples to
+// wav + b * wav_ld; `out` is then not written.
+int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, long sF, cf2 *out, long oB, long oT, long oF, hipStream_t st,
+                    float *wav = nullptr, long wav_ld = 0) {
     se_convp_state &S = *e->cp;
     const int L = e->L, T = e->T, B = e->B, PL = operand_planes(e->precision);
     const int Ba = e->Bact;  // launch batch: the prefix of streams that take part in this segment (se_realtime_process_ragged), B otherwise
@@ -712,9 +733,14 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
         } else {
             if (Fo != e->F[0]) return fail(e, SE_ERR_ARG, "decoder output has %d bins, spectrum has %d", Fo, e->F[0]);
             MaskPArgs m{S.decR[j].p, (long)T * Fi * 8, Fi, e->lv[j].dec_nw.p, e->lv[j].dec_nb.p, sy, spec, sB, sT, sF, out, oB, oT, oF, T, e->F[0]};
-            ProfScope ps(e, "k_final_mask_p", "final_mask", 0, st);
-            launch_k_final_mask_p(dim3((T * e->F[0] + 1023) / 1024, Ba), st, m);
-            HIPCHECK(e, hipGetLastError());
+            if (wav) {
+                ProfScope ps(e, "k_mask_istft", "mask_istft", 0, st);
+                HIPCHECK(e, sig_mask_istft(e->sig, m, Ba, wav, wav_ld, st));
+            } else {
+                ProfScope ps(e, "k_final_mask_p", "final_mask", 0, st);
+                launch_k_final_mask_p(dim3((T * e->F[0] + 1023) / 1024, Ba), st, m);
+                HIPCHECK(e, hipGetLastError());
+            }
         }
     }
     return 0;

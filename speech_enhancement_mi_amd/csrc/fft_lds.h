@@ -89,6 +89,48 @@ SE_HD void fft_pass(const cf2 *in, cf2 *out, int N, int ld, int nfft, int Ns, co
     }
 }
 
+// ---- the same passes with the geometry as template constants (N/2 = 256 as 4*4*4*4 and N/2 = 200 as 5*5*4*2, the order of
+// fft_plan): q / per, j % Ns and the twiddle index become shifts, masks and constant multiplies.  The butterflies, the twiddle table
+// entries and their order are those of fft_pass (r * k * twstep < N always, so fft_pass's `% N` never changes the index): the two
+// forms give the same bits (tests/test_fft_fixed_host.py).
+template <int R, int N, int Ns, int TWS>
+SE_HD void fft_pass_fixed(const cf2 *in, cf2 *out, int nfft, const cf2 *tw, int tid, int nthreads) {
+    constexpr unsigned per = N / R, twstep = N / (Ns * R);
+    static_assert(per * R == N && twstep * Ns * R == N, "radix plan does not divide N");
+    const unsigned total = per * (unsigned)nfft;
+    for (unsigned q = (unsigned)tid; q < total; q += (unsigned)nthreads) {
+        const unsigned f = q / per, j = q - f * per;
+        const cf2 *src = in + f * N;
+        cf2 *dst = out + f * N;
+        const unsigned k = j % Ns;
+        cf2 v[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            cf2 a = src[j + r * per];
+            if (r > 0 && Ns > 1) a = cmul(a, tw[(r * k * twstep) * TWS]);
+            v[r] = a;
+        }
+        if (R == 2) dft2(v);
+        if (R == 4) dft4(v);
+        if (R == 5) dft5(v);
+        const unsigned j0 = (j - k) * R + k;
+#pragma unroll
+        for (int r = 0; r < R; r++) dst[j0 + r * Ns] = v[r];
+    }
+}
+
+constexpr int kFixedPasses = 4;  // both fixed sizes take four passes: the result is back in the buffer the data started in
+constexpr bool fft_has_fixed(int N2) { return N2 == 256 || N2 == 200; }
+constexpr int fft_fixed_radix(int N2, int p) { return N2 == 256 ? 4 : (p < 2 ? 5 : p == 2 ? 4 : 2); }
+constexpr int fft_fixed_ns(int N2, int p) { return p == 0 ? 1 : fft_fixed_ns(N2, p - 1) * fft_fixed_radix(N2, p - 1); }
+
+// pass P (0 .. kFixedPasses-1) of `nfft` N2-point transforms stored back to back; tw is the 2*N2-point table, read with stride 2
+template <int N2, int P>
+SE_HD void fft_fixed_pass(const cf2 *in, cf2 *out, int nfft, const cf2 *tw, int tid, int nthreads) {
+    static_assert(fft_has_fixed(N2) && P >= 0 && P < kFixedPasses, "no fixed plan");
+    fft_pass_fixed<fft_fixed_radix(N2, P), N2, fft_fixed_ns(N2, P), 2>(in, out, nfft, tw, tid, nthreads);
+}
+
 // ---- real <-> half-length complex packing (each frame is transformed on its own, so an all-zero frame
 // gives exact zeros - the reference's arctan(im/(re+1e-8)) feature is ill-conditioned around 0 and a
 // two-frames-per-transform trick would leak rounding noise of the neighbour frame into silent frames).

@@ -20,13 +20,23 @@
 #include "norm.hip.h"
 #include "stft.hip.h"
 #include "fsn_mask.hip.h"
+#include "io_fused.hip.h"
 #include "sig_chain.h"
 
 namespace se {
 
-void launch_k_stft(dim3 grid, size_t lds, hipStream_t st, const StftArgs &a) { hipLaunchKernelGGL(k_stft, grid, dim3(256), lds, st, a); }
+// n_fft = 512 and 400 have passes with compile-time geometry (fft_lds.h); every other size runs the run-time plan
+void launch_k_stft(dim3 grid, size_t lds, hipStream_t st, const StftArgs &a) {
+    if (a.plan.N == 512) hipLaunchKernelGGL(k_stft<512>, grid, dim3(kFftThreads), lds, st, a);
+    else if (a.plan.N == 400) hipLaunchKernelGGL(k_stft<400>, grid, dim3(kFftThreads), lds, st, a);
+    else hipLaunchKernelGGL(k_stft<0>, grid, dim3(kFftThreads), lds, st, a);
+}
 
-void launch_k_istft(dim3 grid, size_t lds, hipStream_t st, const IstftArgs &a) { hipLaunchKernelGGL(k_istft, grid, dim3(256), lds, st, a); }
+void launch_k_istft(dim3 grid, size_t lds, hipStream_t st, const IstftArgs &a) {
+    if (a.plan.N == 512) hipLaunchKernelGGL(k_istft<512>, grid, dim3(kFftThreads), lds, st, a);
+    else if (a.plan.N == 400) hipLaunchKernelGGL(k_istft<400>, grid, dim3(kFftThreads), lds, st, a);
+    else hipLaunchKernelGGL(k_istft<0>, grid, dim3(kFftThreads), lds, st, a);
+}
 
 void launch_k_overlap_avg(dim3 grid, hipStream_t st, const float *yseg, float *out, int Nseg, int K, long L, long skip, const long *Lrow,
                           const long *skiprow) {
@@ -44,8 +54,10 @@ void aux_set_fft_lds(int stft_bytes, int istft_bytes) {
     if (stft_bytes <= kMaxLds && stft_bytes > cur_stft) cur_stft = stft_bytes;
     if (istft_bytes <= kMaxLds && istft_bytes > cur_istft) cur_istft = istft_bytes;
     stft_bytes = cur_stft; istft_bytes = cur_istft;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stft), hipFuncAttributeMaxDynamicSharedMemorySize, stft_bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_istft), hipFuncAttributeMaxDynamicSharedMemorySize, istft_bytes);
+    for (const void *k : {reinterpret_cast<const void *>(k_stft<512>), reinterpret_cast<const void *>(k_stft<400>), reinterpret_cast<const void *>(k_stft<0>)})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, stft_bytes);
+    for (const void *k : {reinterpret_cast<const void *>(k_istft<512>), reinterpret_cast<const void *>(k_istft<400>), reinterpret_cast<const void *>(k_istft<0>)})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, istft_bytes);
 }
 
 // ---- the signal chain (sig_chain.h) ----
@@ -107,6 +119,85 @@ hipError_t sig_istft(const SigChain &s, const cf2 *spec, long sR, long sT, long 
     a.wav = wav; a.wav_ld = wav_ld; a.window = s.window; a.env = s.env; a.tw = reinterpret_cast<const cf2 *>(s.tw); a.plan = s.plan;
     a.seg_spec = seg_spec; a.seg_wav = seg_wav;
     launch_k_istft(dim3(nrows, nseg), istft_lds_bytes(s.T, s.N), st, a);
+    return hipGetLastError();
+}
+
+// ---- the fused ends (io_fused.hip.h) ----
+namespace {
+
+constexpr int kLdsMax = 160 * 1024, kLdsStatic = 256;
+
+template <int NFFT>
+void stft_feat_instances(const void **k) {
+    k[0] = reinterpret_cast<const void *>(k_stft_feat<NFFT, 1>);
+    k[1] = reinterpret_cast<const void *>(k_stft_feat<NFFT, 2>);
+    k[2] = reinterpret_cast<const void *>(k_stft_feat<NFFT, 3>);
+}
+
+// dynamic-LDS opt-in of every instance: hipFuncSetAttribute is per device, so once per thread and device (as train_conv_attributes)
+void io_fused_attributes() {
+    static thread_local int done_dev = -1;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (done_dev == dev) return;
+    const void *k[12];
+    stft_feat_instances<512>(k);
+    stft_feat_instances<400>(k + 3);
+    stft_feat_instances<0>(k + 6);
+    k[9] = reinterpret_cast<const void *>(k_mask_istft<512>);
+    k[10] = reinterpret_cast<const void *>(k_mask_istft<400>);
+    k[11] = reinterpret_cast<const void *>(k_mask_istft<0>);
+    // (k_mask_istft also has a few static bytes: kLdsStatic below the chip's 160 KB, as sig_io_fused_fits assumes)
+    for (int i = 0; i < 12; i++) (void)hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 9 ? kLdsMax : kLdsMax - kLdsStatic);
+    (void)hipGetLastError();
+    done_dev = dev;
+}
+
+template <int NFFT>
+void launch_stft_feat(int PL, dim3 grid, size_t lds, hipStream_t st, const StftFeatArgs &a) {
+    if (PL == 1) hipLaunchKernelGGL((k_stft_feat<NFFT, 1>), grid, dim3(kFeatThreads), lds, st, a);
+    else if (PL == 2) hipLaunchKernelGGL((k_stft_feat<NFFT, 2>), grid, dim3(kFeatThreads), lds, st, a);
+    else hipLaunchKernelGGL((k_stft_feat<NFFT, 3>), grid, dim3(kFeatThreads), lds, st, a);
+}
+
+}  // namespace
+
+bool sig_io_fused_fits(const SigChain &s, int M) {
+    return M >= 1 && M <= kFeatMaxM && stft_feat_lds_bytes(s.hop, s.N, M) <= (size_t)kLdsMax && mask_istft_lds_bytes(s.T, s.N) + kLdsStatic <= (size_t)kLdsMax;
+}
+
+hipError_t sig_stft_feat(const SigChain &s, const float *src, long strideB, long strideM, int M, long off, long Lsrc, SigRows rows, int nstreams,
+                         cf2 *spec0, long sB, long sT, long sF, uint4 *feat, long feat_stream, int PL, int atan2_phase, hipStream_t st) {
+    if (!sig_io_fused_fits(s, M) || PL < 1 || PL > 3) return hipErrorInvalidValue;
+    StftFeatArgs fa{};
+    StftArgs &a = fa.s;
+    a.src = src; a.strideB = strideB; a.strideM = strideM; a.M = M; a.off = off; a.L = Lsrc;
+    a.K = s.K; a.T = s.T; a.F = s.F; a.hop = s.hop;
+    a.spec = spec0; a.sR = sB; a.sT = sT; a.sF = sF;
+    a.window = s.window; a.tw = reinterpret_cast<const cf2 *>(s.tw); a.plan = s.plan;
+    a.Lrow = rows.len; a.offrow = rows.off0;
+    fa.feat = feat; fa.feat_stream = feat_stream; fa.atan2_phase = atan2_phase;
+    io_fused_attributes();
+    const dim3 grid(nstreams, (s.T + kFeatFrames - 1) / kFeatFrames);
+    const size_t lds = stft_feat_lds_bytes(s.hop, s.N, M);
+    if (s.N == 512) launch_stft_feat<512>(PL, grid, lds, st, fa);
+    else if (s.N == 400) launch_stft_feat<400>(PL, grid, lds, st, fa);
+    else launch_stft_feat<0>(PL, grid, lds, st, fa);
+    return hipGetLastError();
+}
+
+hipError_t sig_mask_istft(const SigChain &s, const MaskPArgs &m, int nstreams, float *wav, long wav_ld, hipStream_t st) {
+    if (!sig_io_fused_fits(s, 1)) return hipErrorInvalidValue;
+    MaskIstftArgs ma{};
+    ma.m = m;
+    IstftArgs &a = ma.i;
+    a.K = s.K; a.T = s.T; a.F = s.F; a.hop = s.hop;
+    a.wav = wav; a.wav_ld = wav_ld; a.window = s.window; a.env = s.env; a.tw = reinterpret_cast<const cf2 *>(s.tw); a.plan = s.plan;
+    io_fused_attributes();
+    const size_t lds = mask_istft_lds_bytes(s.T, s.N);
+    if (s.N == 512) hipLaunchKernelGGL(k_mask_istft<512>, dim3(nstreams), dim3(kFftThreads), lds, st, ma);
+    else if (s.N == 400) hipLaunchKernelGGL(k_mask_istft<400>, dim3(nstreams), dim3(kFftThreads), lds, st, ma);
+    else hipLaunchKernelGGL(k_mask_istft<0>, dim3(nstreams), dim3(kFftThreads), lds, st, ma);
     return hipGetLastError();
 }
 

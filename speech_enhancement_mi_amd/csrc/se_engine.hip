@@ -7,6 +7,9 @@
 //   k_stft -> [CRN_ELU / student: 3x pre-conv block] -> encoder and decoder on the plane path (convp_engine.inc.h:
 //   k_conv_p, k_gln_p, k_skip_p, k_final_mask_p) around the bottleneck (GEMMs + T x k_gru_step per layer) -> k_istft
 //
+// In se_step / se_realtime_process the two ends run fused (io_fused.hip.h): k_stft_feat = k_stft + k_featurize_p where the features
+// go to the plane path, k_mask_istft = k_final_mask_p + k_istft; SE_IO_FUSE=0 keeps the four kernels.
+//
 // k_conv_x6 / k_conv_igemm / k_conv_small (plan_conv, launch_conv) run the student's feature-tap re-runs, the
 // fp32 / bf16x3 pre-conv blocks and (k_conv_igemm) the training path; k_gemm_x / k_gemm_tn are the bottleneck GEMMs where
 // the plane GEMM k_gemm_p does not apply.  Reference: TemporalCRN.forward / realtime_process (CRN.py:454-496, 560-589).
@@ -130,6 +133,8 @@ struct se_engine : EngineHost {
     int skinny_rows = 800;    // SE_GEMM_SKINNY_ROWS: bottleneck GEMMs with up to this many rows run on the skinny fp32 kernel
     int skip_min_batch = 96;  // SE_SKIP_MIN_BATCH: the streaming skip kernel needs at least this many streams
     int dec_pair = 1;         // SE_DEC_PAIR=0: the transposed convolutions above the last level run one k_conv_p launch per parity
+    int io_fuse = 1;          // SE_IO_FUSE=0: k_stft + k_featurize_p and k_final_mask_p + k_istft as four kernels (io_fused.hip.h fuses them)
+    bool io_fuse_on = false;  // io_fuse and the fused kernels' workgroups fit a CU's LDS at this geometry
     int gemm_p_env = 1;
     DevBuf gruinP[kRing], seqP[4][kRing];  // [PL][B*T][D'] / [PL][B*T][H] bf16 planes
     DevBuf wih_xp;                          // W_ih0 planes with K in the engine's feature order (k_gemm_p)
@@ -781,13 +786,14 @@ int stage_bottleneck(se_engine *e, int cur, hipStream_t st, bool overlapped = fa
 
 namespace {
 
-int run_encoder(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st) {
+int run_encoder(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st, bool feat_done = false) {
     if (e->dbg_skip & 4) return 0;
-    return stage_encoder_p(e, cur, prev, spec, sB, sM, sT, sF, st);
+    return stage_encoder_p(e, cur, prev, spec, sB, sM, sT, sF, st, feat_done);
 }
-int run_decoder(se_engine *e, int cur, const cf2 *spec, long sB, long sT, long sF, cf2 *out, long oB, long oT, long oF, hipStream_t st) {
+int run_decoder(se_engine *e, int cur, const cf2 *spec, long sB, long sT, long sF, cf2 *out, long oB, long oT, long oF, hipStream_t st,
+                float *wav = nullptr, long wav_ld = 0) {
     if (e->dbg_skip & 8) return 0;
-    return stage_decoder_p(e, cur, spec, sB, sT, sF, out, oB, oT, oF, st);
+    return stage_decoder_p(e, cur, spec, sB, sT, sF, out, oB, oT, oF, st, wav, wav_ld);
 }
 
 int forward_dev(se_engine *e, const cf2 *spec, long sB, long sM, long sT, long sF, cf2 *out, long oB, long oT, long oF,
@@ -1000,6 +1006,8 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (const char *s = getenv("SE_GEMM_SKINNY_ROWS")) e->skinny_rows = atoi(s);
     if (const char *s = getenv("SE_SKIP_MIN_BATCH")) e->skip_min_batch = atoi(s);
     if (const char *s = getenv("SE_DEC_PAIR")) e->dec_pair = atoi(s) != 0 ? 1 : 0;
+    if (const char *s = getenv("SE_IO_FUSE")) e->io_fuse = atoi(s) != 0 ? 1 : 0;
+    e->io_fuse_on = e->io_fuse && sig_io_fused_fits(e->sig, e->M);
     e->cp = new se_convp_state();
     {
         int ncu = 0;
@@ -1104,8 +1112,8 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
     for (int i = 0; i < SE_MAX_LEVELS; i++)
         for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].pre})
             select_conv_geometry(e, *p);
-    size_t spec_n = (size_t)B * e->M * T * F0 * 2;
-    if ((rc = dev_alloc(e, e->maskspec, (size_t)B * T * F0 * 2))) return rc;
+    size_t spec_n = (size_t)B * (stft_feat_route(e) ? 1 : e->M) * T * F0 * 2;  // the fused front end keeps microphone 0's spectrum only
+    if (!e->io_fuse_on && (rc = dev_alloc(e, e->maskspec, (size_t)B * T * F0 * 2))) return rc;
     for (int r = 0; r < kRing; r++)
         if ((rc = dev_alloc(e, e->spec[r], spec_n)) || (rc = dev_alloc(e, e->gru_in[r], (size_t)B * T * D)) || (rc = dev_alloc(e, e->dec_in[r], (size_t)B * T * D))) return rc;
     for (int i = 0; i < L; i++) {
@@ -1221,10 +1229,20 @@ static int ensure_stage_streams(se_engine *e) {
 static int step_dev(se_engine *e, const float *src, long strideB, long strideM, long off, long Lsrc, SigRows rows, float *wav_out, long wav_ld, hipStream_t st) {
     const long F = e->F[0], T = e->T, M = e->M;
     int rc;
-    cf2 *spec = reinterpret_cast<cf2 *>(e->spec[(e->slot + 1) % kRing].p);
+    const int prev = e->slot, cur = (e->slot + 1) % kRing;
+    cf2 *spec = reinterpret_cast<cf2 *>(e->spec[cur].p);
     cf2 *ms = reinterpret_cast<cf2 *>(e->maskspec.p);
-    if ((rc = launch_stft(e, src, strideB, strideM, (int)M, off, Lsrc, rows, e->Bact * (int)M, spec, T * F, F, 1, st))) return rc;
-    if ((rc = forward_dev(e, spec, M * T * F, T * F, F, 1, ms, T * F, F, 1, st))) return rc;
+    e->slot = cur;
+    // the fused ends (io_fused.hip.h) where the route has them: the spectrum buffer then holds microphone 0 only
+    const bool ffeat = stft_feat_route(e), fmask = e->io_fuse_on;
+    const long sB = ffeat ? T * F : M * T * F;
+    if (ffeat) rc = stage_stft_feat_p(e, cur, src, strideB, strideM, off, Lsrc, rows, spec, st);
+    else rc = launch_stft(e, src, strideB, strideM, (int)M, off, Lsrc, rows, e->Bact * (int)M, spec, T * F, F, 1, st);
+    if (rc) return rc;
+    if ((rc = run_encoder(e, cur, prev, spec, sB, T * F, F, 1, st, ffeat))) return rc;
+    if ((rc = stage_bottleneck(e, cur, st))) return rc;
+    if (fmask) return run_decoder(e, cur, spec, sB, F, 1, nullptr, 0, 0, 0, st, wav_out, wav_ld);
+    if ((rc = run_decoder(e, cur, spec, sB, F, 1, ms, T * F, F, 1, st))) return rc;
     return launch_istft(e, ms, T * F, F, 1, e->Bact, wav_out, wav_ld, st);
 }
 
@@ -1321,11 +1339,13 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
         // GRU launches, the encoder of n+1.. and the decoder of n-1 keep the matrix cores and HBM busy.
         hipStream_t sE = e->stage_stream[0], sD = e->stage_stream[1], sG = e->stage_stream[2];
         const long F = e->F[0], T = e->T, M = e->M;
-        const size_t spec_n = (size_t)e->B * M * T * F * 2, mask_n = (size_t)e->B * T * F * 2;
+        const bool ffeat = stft_feat_route(e), fmask = e->io_fuse_on;  // the fused ends (io_fused.hip.h): one launch per segment each
+        const long Ms = ffeat ? 1 : M;                                 // microphones in the staged spectra
+        const size_t spec_n = (size_t)e->B * Ms * T * F * 2, mask_n = (size_t)e->B * T * F * 2;
         // The STFT of kFftSub segments is one launch on the encoder stream ahead of their encoders, the iSTFT one launch on
         // the decoder stream behind their decoders: both overlap with the other stages of neighbouring segments.
         const long CH = std::min<long>(Nseg, kPipeChunk);
-        if ((rc = dev_alloc(e, e->spec_all, spec_n * CH)) || (rc = dev_alloc(e, e->mask_all, mask_n * CH))) return rc;
+        if ((rc = dev_alloc(e, e->spec_all, spec_n * CH)) || (!fmask && (rc = dev_alloc(e, e->mask_all, mask_n * CH)))) return rc;
         // layer l of a recurrence round works on segment (round - l); SE_GRU_DIRECT=0 pins the LDS-slice step kernel, which has
         // no multi-layer form: layers then run back to back
         const bool lagged = e->gru_direct != 0;
@@ -1342,13 +1362,16 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
                     e->slot = cur;
                     e->Bact = e->bact_slot[cur] = bact_of(c0 + i);
                     const cf2 *spec = reinterpret_cast<const cf2 *>(e->spec_all.p + spec_n * i);
-                    if (i % kFftSub == 0) {
+                    if (!ffeat && i % kFftSub == 0) {
                         const long ns = std::min<long>(kFftSub, cn - i);
                         if ((rc = launch_stft(e, mixture, (long)e->M * length, length, (int)M, off_first + (c0 + i) * P, length, rows, e->Bact * (int)M,
                                               reinterpret_cast<cf2 *>(e->spec_all.p + spec_n * i), T * F, F, 1, sE, (int)ns, P, (long)(spec_n / 2)))) return rc;
                     }
                     if (i >= kRing) HIPCHECK(e, hipStreamWaitEvent(sE, e->ev_dec[cur], 0));  // slot cur was last read by the decoder of segment i - kRing
-                    if ((rc = run_encoder(e, cur, prev, spec, M * T * F, T * F, F, 1, sE))) return rc;
+                    // (the fused front end writes ring slot cur: it runs here, behind the slot's last reader, not kFftSub segments ahead)
+                    if (ffeat && (rc = stage_stft_feat_p(e, cur, mixture, (long)e->M * length, length, off_first + (c0 + i) * P, length, rows,
+                                                         reinterpret_cast<cf2 *>(e->spec_all.p + spec_n * i), sE))) return rc;
+                    if ((rc = run_encoder(e, cur, prev, spec, Ms * T * F, T * F, F, 1, sE, ffeat))) return rc;
                     if ((rc = stage_gru_proj0(e, cur, sE))) return rc;
                     if ((rc = chain_save(e, plan, c0 + i, 1u, sE))) return rc;  // before the encoder stream reuses the slot, kRing segments on
                     HIPCHECK(e, hipEventRecord(e->ev_enc[cur], sE));
@@ -1378,10 +1401,13 @@ static int run_segments(se_engine *e, const float *mixture, int batch, int64_t l
                 HIPCHECK(e, hipEventRecord(e->ev_gru[dcur], sG));
                 HIPCHECK(e, hipStreamWaitEvent(sD, e->ev_gru[dcur], 0));
                 const cf2 *dspec = reinterpret_cast<const cf2 *>(e->spec_all.p + spec_n * done);
-                cf2 *ms = reinterpret_cast<cf2 *>(e->mask_all.p + mask_n * done);
+                cf2 *ms = fmask ? nullptr : reinterpret_cast<cf2 *>(e->mask_all.p + mask_n * done);
                 if ((rc = stage_gru_out(e, dcur, sD))) return rc;
-                if ((rc = run_decoder(e, dcur, dspec, M * T * F, F, 1, ms, T * F, F, 1, sD))) return rc;
-                if (done % kFftSub == kFftSub - 1 || done == cn - 1) {
+                // (the fused back end reads the single dec3 buffer: it runs per segment, inside the decoder stage, before ev_dec)
+                if (fmask) rc = run_decoder(e, dcur, dspec, Ms * T * F, F, 1, nullptr, 0, 0, 0, sD, e->yseg.p + (c0 + done) * K, Nseg * K);
+                else rc = run_decoder(e, dcur, dspec, Ms * T * F, F, 1, ms, T * F, F, 1, sD);
+                if (rc) return rc;
+                if (!fmask && (done % kFftSub == kFftSub - 1 || done == cn - 1)) {
                     const long i0 = done - done % kFftSub;
                     if ((rc = launch_istft(e, reinterpret_cast<const cf2 *>(e->mask_all.p + mask_n * i0), T * F, F, 1, bact_of(c0 + i0) /* (the ring slot of segment i0 has been reused by now) */,
                                            e->yseg.p + (c0 + i0) * K, Nseg * K, sD, (int)(done - i0 + 1), (long)(mask_n / 2), K))) return rc;

@@ -11,6 +11,8 @@
 
 namespace se {
 
+struct MaskPArgs;  // conv_p_args.h
+
 struct SigChain {
     int device = 0, N = 0, win = 0, hop = 0, K = 0, T = 0, F = 0;  // n_fft, window, hop, segment samples, frames 1 + K/hop, bins N/2 + 1
     float *window = nullptr, *env = nullptr, *tw = nullptr;        // device: hamming(win) centred in N [N]; sum_t w^2 [K]; exp(-2 pi i m / N) [N] (cf2)
@@ -36,5 +38,15 @@ hipError_t sig_stft(const SigChain &s, const float *src, long strideB, long stri
 // the inverse: segment y of row r -> wav[y * seg_wav + r * wav_ld + (0 .. K)]
 hipError_t sig_istft(const SigChain &s, const cf2 *spec, long sR, long sT, long sF, int nrows, float *wav, long wav_ld, hipStream_t st, int nseg = 1,
                      long seg_spec = 0, long seg_wav = 0);
+
+// The CRN engine's fused ends (io_fused.hip.h), one segment per launch.
+// sig_stft_feat: the STFT of all M <= 4 microphones of `nstreams` streams (addressing and zero fill as sig_stft, rows = streams); microphone
+// 0's spectrum -> spec0[b * sB + t * sT + f * sF], the feature octets -> feat[b * feat_stream + ...] in the P layout of PL planes.
+hipError_t sig_stft_feat(const SigChain &s, const float *src, long strideB, long strideM, int M, long off, long Lsrc, SigRows rows, int nstreams,
+                         cf2 *spec0, long sB, long sT, long sF, uint4 *feat, long feat_stream, int PL, int atan2_phase, hipStream_t st);
+// sig_mask_istft: m as for k_final_mask_p (its `out` is not used); stream b -> wav[b * wav_ld + (0 .. K)]
+hipError_t sig_mask_istft(const SigChain &s, const MaskPArgs &m, int nstreams, float *wav, long wav_ld, hipStream_t st);
+// whether the two kernels' workgroups fit the LDS of a CU at this geometry (the engine keeps the four-kernel route otherwise)
+bool sig_io_fused_fits(const SigChain &s, int M);
 
 }  // namespace se

@@ -9,13 +9,21 @@
 // into LDS, each of the T real frames becomes one N/2-point complex transform (even/odd packing) run
 // through LDS-resident Stockham radix-5/4/2 passes (fft_lds.h); the onesided spectrum is recovered on the
 // way out.  HBM traffic = K*4 B in + T*F*8 B out per segment; everything else stays in LDS.
+//
+// Work distribution: kFftBatch = 7 frames are resident per round and a workgroup has kFftThreads = 448 threads (7 waves).  T = 21 is three
+// full rounds, and a radix-4 pass of seven 256-point transforms is 7 * 64 = 448 butterflies: one per thread in every pass of every
+// round at n_fft = 512 (at 400 the passes have 280 / 280 / 350 / 700 butterflies: one, one, one and two trips).  The two buffers take
+// 2 * 7 * N/2 * 8 B = 28 KB, so the STFT workgroup needs 50 KB at K = 3200 (three per CU: 21 waves, 5 per SIMD) and the iSTFT one 78 KB
+// (two per CU: 14 waves) - LDS instructions need about 4 waves per SIMD to reach their rates.  n_fft = 512 and 400 run the passes with
+// compile-time geometry (fft_pass_fixed); any other n_fft runs the same kernels on the run-time plan (fft_run).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fft_lds.h"
 
 namespace se {
 
-constexpr int kFftBatch = 11;  // real frames (= N/2-point complex transforms) resident in LDS per round
+constexpr int kFftBatch = 7;      // real frames (= N/2-point complex transforms) resident in LDS per round
+constexpr int kFftThreads = 448;  // threads of an STFT / iSTFT workgroup
 constexpr int kMaxRadices = 12;
 
 struct FftPlan {
@@ -39,6 +47,26 @@ __device__ inline cf2 *fft_run(cf2 *a, cf2 *b, const FftPlan &pl, int nfft, cons
         cf2 *t = a; a = b; b = t;
     }
     return a;
+}
+
+// The same for an n_fft with a fixed plan (NFFT = 512, 400); NFFT = 0 is fft_run.  Four passes: the result is back in a.
+template <int NFFT>
+__device__ inline cf2 *fft_run_t(cf2 *a, cf2 *b, const FftPlan &pl, int nfft, const cf2 *tw) {
+    if constexpr (NFFT == 0) {
+        return fft_run(a, b, pl, nfft, tw);
+    } else {
+        constexpr int N2 = NFFT / 2;
+        const int tid = threadIdx.x, nth = blockDim.x;
+        fft_fixed_pass<N2, 0>(a, b, nfft, tw, tid, nth);
+        __syncthreads();
+        fft_fixed_pass<N2, 1>(b, a, nfft, tw, tid, nth);
+        __syncthreads();
+        fft_fixed_pass<N2, 2>(a, b, nfft, tw, tid, nth);
+        __syncthreads();
+        fft_fixed_pass<N2, 3>(b, a, nfft, tw, tid, nth);
+        __syncthreads();
+        return a;
+    }
 }
 
 struct StftArgs {
@@ -65,9 +93,10 @@ inline size_t stft_lds_bytes(int K, int N) {
 }
 
 #ifdef SE_AUX_KERNELS  // kernel bodies live in se_aux.hip (compiled without SLP vectorisation, see its header)
-__global__ __launch_bounds__(256) void k_stft(StftArgs a) {
+template <int NFFT>  // n_fft where it has a fixed plan (fft_lds.h), 0: any n_fft on the run-time plan
+__global__ __launch_bounds__(kFftThreads) void k_stft(StftArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int N = a.plan.N, N2 = N / 2, K = a.K, T = a.T, F = a.F, pad = N / 2;
+    const int N = NFFT ? NFFT : a.plan.N, N2 = N / 2, K = a.K, T = a.T, F = N2 + 1, pad = N / 2;
     float *sig = reinterpret_cast<float *>(smem);
     float *win = sig + K + N;
     cf2 *tw = reinterpret_cast<cf2 *>(win + N);
@@ -93,7 +122,7 @@ __global__ __launch_bounds__(256) void k_stft(StftArgs a) {
             bufA[i] = cf2{win[2 * n] * s[0], win[2 * n + 1] * s[1]};
         }
         __syncthreads();
-        const cf2 *Z = fft_run(bufA, bufB, a.plan, nf, tw);
+        const cf2 *Z = fft_run_t<NFFT>(bufA, bufB, a.plan, nf, tw);
         for (int i = tid; i < nf * F; i += nth) {
             const int f = i / F, k = i - f * F;
             spec_out[(long)row * a.sR + (long)(t0 + f) * a.sT + (long)k * a.sF] = rfft_post(Z + f * N2, k, N2, tw);
@@ -123,9 +152,10 @@ inline size_t istft_lds_bytes(int T, int N) {
 }
 
 #ifdef SE_AUX_KERNELS
-__global__ __launch_bounds__(256) void k_istft(IstftArgs a) {
+template <int NFFT>
+__global__ __launch_bounds__(kFftThreads) void k_istft(IstftArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int N = a.plan.N, N2 = N / 2, K = a.K, T = a.T, pad = N / 2;
+    const int N = NFFT ? NFFT : a.plan.N, N2 = N / 2, K = a.K, T = a.T, pad = N / 2;
     float *frames = reinterpret_cast<float *>(smem);
     float *win = frames + T * N;
     cf2 *tw = reinterpret_cast<cf2 *>(win + N);
@@ -145,7 +175,7 @@ __global__ __launch_bounds__(256) void k_istft(IstftArgs a) {
             bufA[i] = irfft_pre(xk, xn, k, tw);
         }
         __syncthreads();
-        const cf2 *R = fft_run(bufA, bufB, a.plan, nf, tw);
+        const cf2 *R = fft_run_t<NFFT>(bufA, bufB, a.plan, nf, tw);
         for (int i = tid; i < nf * N2; i += nth) {
             const int f = i / N2, n = i - f * N2;
             const cf2 r = R[i];
