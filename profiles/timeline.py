@@ -17,8 +17,8 @@ def main():
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
     # the timed steps only: from the first pipelined step launch after the warm-up step (1 warm-up + 3 timed steps: the second quarter of the
-    # k_gru_step_multi launches onwards) to the last one; bench.py's extra per-launch-event step (serial order) comes later and is left out
-    multi = [r for r in rows if "gru_step_multi" in r[2]]
+    # k_gru_step_multi / k_gru_step_split_multi launches onwards) to the last one; bench.py's extra per-launch-event step (serial order) comes later and is left out
+    multi = [r for r in rows if "gru_step_multi" in r[2] or "gru_step_split_multi" in r[2]]
     if multi:
         t_lo, t_hi = multi[len(multi) // 4][0], multi[-1][1]
         rows = [r for r in rows if r[0] >= t_lo and r[1] <= t_hi]

@@ -801,4 +801,207 @@ __global__ __launch_bounds__(256) void k_gru_step2(GruStepArgs a) {
     }
 }
 
+// Third-generation step kernel, for the plane route at PL = 3: the recurrent contraction on the bf16 matrix cores as the six
+// split-bf16 products of k_gemm_p (same term order, smallest first) instead of v_mfma_f32_16x16x4_f32.
+//   A  the planes of h_{t-1}: for t >= 1 they are already in memory - row t - 1 of the sequence planes the previous step's epilogue
+//      wrote (`hp`); at t = 0 (`hp` null) the fp32 `hprev` is split on the fly.  split3 is exact, so both give the same operand bits
+//      and no plane state is carried between calls.
+//   B  W_hh packed by the host (gru_pack.h): [unit group][k step][gate][plane] fragments of 64 lanes x 16 bytes.
+// Workgroup = 32 * MT streams x 32 hidden units, v_mfma_f32_32x32x16_bf16, one accumulator tile per gate and row tile.  ONE wave
+// covers all the workgroup's streams, so every W fragment is loaded once per workgroup; the four waves split K and each keeps PF k
+// steps of operands in flight.  The partial sums meet through LDS one gate at a time (reduce-scatter: wave w ends up with rows
+// 8 w .. 8 w + 7 of each row tile, 12 KB * MT, summed in one order for every row), so all four waves share the epilogue.
+// Requires H % 32 == 0 (host-checked).
+// Measured at B = 256, H = 512: MT = 1, PF = 2 (152 VGPRs + 48 AGPRs, 12 KB LDS, no scratch) takes 11.4 us
+// per single-layer launch alone against 12.0 (k_gru_step2) and 14.5 (k_gru_step), 21 us instead of 34 per two-layer launch under
+// overlap, and the pipelined step 52.5 -> 48.9 ms.  On one box PF = 4 (296 registers) took 12.3 us alone and 49.8 ms per step where
+// PF = 2 took 11.5 and 48.2, and MT = 2 - 64 streams per workgroup, 310 registers, 24 KB - 17.4 us and 49.1 ms: the step is bound
+// by its chain of dependent L2 round trips and by what it takes from the co-resident convolutions, not by MFMA issue (1.9 us) or
+// bytes (50 MB per launch).
+struct GruSplitArgs {
+    GruStepArgs s;        // as k_gru_step (gates unused; seqp with 3 planes is required)
+    const uint4 *whp;     // packed W_hh planes
+    const __bf16 *hp;     // planes of h_{t-1}: s.seqp - H for t >= 1, nullptr at t = 0
+};
+struct GruSplitMulti { GruSplitArgs a[4]; };
+
+template <int MT, int PF>
+__device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ float red[4][3][MT * 4][64];  // [source wave][destination wave, the source left out][register][lane]
+    const GruStepArgs &a = ga.s;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = lane >> 5, l31 = lane & 31;
+    const int H = a.H, KS = H >> 4;
+    const int n0 = blockIdx.x * 32, r0 = blockIdx.y * (32 * MT);
+    if (r0 >= a.B) return;  // (uniform, ahead of every barrier: a layer of a multi launch with fewer rows than the grid covers)
+    const int n = n0 + l31;  // < H: the grid is exactly H / 32 wide
+    const int ks0 = KS * wave / 4, ks1 = KS * (wave + 1) / 4;
+    // ---- epilogue operands: requested now, used after the MFMAs.  Wave w, register i, row tile mt: row 32 mt + 8 w + 4 half + i
+    float pgi[MT][4][3], php[MT][4];
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int row = min(r0 + mt * 32 + 8 * wave + 4 * half + i, a.B - 1);  // (clamped rows are never stored)
+            const float *gi = a.gi + (long)row * a.gi_ld + n;
+            pgi[mt][i][0] = gi[0]; pgi[mt][i][1] = gi[H]; pgi[mt][i][2] = gi[2 * H];
+            php[mt][i] = a.hprev[(long)row * H + n];
+        }
+    const float bh_r = a.bhh[n], bh_z = a.bhh[H + n], bh_n = a.bhh[2 * H + n];
+    // ---- operand streams.  One request pattern for both sources of A (a branch here would make the compiler index the operand
+    // ring at run time and spill it): plane p of a k step at abase[p] + ks * astride.  At t = 0 the raw fp32 values travel in
+    // slots 0 and 1 (slot 2 repeats slot 1) and are split when they are used.
+    const bool planes = ga.hp != nullptr;  // uniform
+    const char *abase[MT][3];
+    const long astride = planes ? 32 : 64;  // bytes per k step: 16 bf16 / 16 floats
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++) {
+        const int arow = min(r0 + mt * 32 + l31, a.B - 1);
+        const char *pb = reinterpret_cast<const char *>((planes ? ga.hp : a.seqp) + (long)arow * a.seqp_ld + half * 8);
+        const char *fb = reinterpret_cast<const char *>(a.hprev + (long)arow * H + half * 8);
+#pragma unroll
+        for (int p = 0; p < 3; p++) abase[mt][p] = planes ? pb + p * a.seqp_plane * 2 : fb + (p ? 16 : 0);
+    }
+    const uint4 *wp = ga.whp + (long)blockIdx.x * KS * 9 * 64 + lane;
+    u32x4 qa[PF][MT][3], qw[PF][9];
+    auto request = [&](int i, int ks) {
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int p = 0; p < 3; p++) qa[i][mt][p] = *reinterpret_cast<const u32x4 *>(abase[mt][p] + ks * astride);
+#pragma unroll
+        for (int f = 0; f < 9; f++) qw[i][f] = *reinterpret_cast<const u32x4 *>(wp + ((long)ks * 9 + f) * 64);
+    };
+    f32x16 acc[MT][3];
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int g = 0; g < 3; g++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[mt][g][r] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < PF; i++) request(i, min(ks0 + i, KS - 1));
+    for (int ks = ks0; ks < ks1; ks += PF) {
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            // a slot past the wave's share (shares that are no multiple of PF) holds a valid k step and is multiplied by zero:
+            // no branch around the MFMAs, which would send the accumulators through a copy on every trip
+            const unsigned keep = ks + i < ks1 ? 0xFFFFFFFFu : 0u;  // uniform
+            u32x4 ca[MT][3];
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++) {
+                if (!planes) {
+                    bf16x8 hh, mm, ll;
+#pragma unroll
+                    for (int e = 0; e < 8; e++) {
+                        const float x = __uint_as_float(e < 4 ? qa[i][mt][0][e & 3] : qa[i][mt][1][e & 3]);
+                        __bf16 h1, m1, l1;
+                        split3(x, h1, m1, l1);
+                        hh[e] = h1; mm[e] = m1; ll[e] = l1;
+                    }
+                    ca[mt][0] = __builtin_bit_cast(u32x4, hh);
+                    ca[mt][1] = __builtin_bit_cast(u32x4, mm);
+                    ca[mt][2] = __builtin_bit_cast(u32x4, ll);
+                } else {
+#pragma unroll
+                    for (int p = 0; p < 3; p++) ca[mt][p] = qa[i][mt][p];
+                }
+#pragma unroll
+                for (int p = 0; p < 3; p++) ca[mt][p] &= keep;
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++) {
+                const bf16x8 a0 = __builtin_bit_cast(bf16x8, ca[mt][0]), a1 = __builtin_bit_cast(bf16x8, ca[mt][1]), a2 = __builtin_bit_cast(bf16x8, ca[mt][2]);
+#pragma unroll
+                for (int g = 0; g < 3; g++) {
+                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, qw[i][g * 3]), b1 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 1]), b2 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 2]);
+                    f32x16 c = acc[mt][g];
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
+                    acc[mt][g] = c;
+                }
+            }
+            // the slot's next k step, requested behind the MFMAs that read the slot (nothing past the wave's share)
+            if (ks + i + PF < ks1) request(i, ks + i + PF);
+        }
+    }
+    // ---- split-K reduction, one gate per round through the same 12 KB * MT: a wave hands registers 4 d .. 4 d + 3 of the gate's
+    // tiles to wave d and adds the four shares of its own registers in wave order 0, 1, 2, 3 - the same order for every row, so a
+    // stream's bits do not depend on its place in the batch
+    float gh[MT][3][4];
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        float own[MT][4];
+        if (g) __syncthreads();  // the previous round has been read
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            if (d == wave) {
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                    for (int i = 0; i < 4; i++) own[mt][i] = acc[mt][g][4 * d + i];
+            } else {
+                const int slot = d - (d > wave ? 1 : 0);
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                    for (int i = 0; i < 4; i++) red[wave][slot][mt * 4 + i][lane] = acc[mt][g][4 * d + i];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            float v[MT][4];
+            if (s == wave) {
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                    for (int i = 0; i < 4; i++) v[mt][i] = own[mt][i];
+            } else {
+                const int slot = wave - (wave > s ? 1 : 0);
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                    for (int i = 0; i < 4; i++) v[mt][i] = red[s][slot][mt * 4 + i][lane];
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) gh[mt][g][i] = s ? gh[mt][g][i] + v[mt][i] : v[mt][i];
+        }
+    }
+    // ---- gate math and stores: D layout col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), reg >> 2 = wave here
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int row = r0 + mt * 32 + 8 * wave + 4 * half + i;
+            if (row >= a.B) continue;
+            const float gh_r = gh[mt][0][i] + bh_r;
+            const float gh_z = gh[mt][1][i] + bh_z;
+            const float gh_n = gh[mt][2][i] + bh_n;
+            const float rg = 1.0f / (1.0f + expf(-(pgi[mt][i][0] + gh_r)));
+            const float zg = 1.0f / (1.0f + expf(-(pgi[mt][i][1] + gh_z)));
+            const float ng = tanhf(pgi[mt][i][2] + rg * gh_n);
+            const float hn = (1.0f - zg) * ng + zg * php[mt][i];
+            a.hout[(long)row * H + n] = hn;
+            a.seq[(long)row * a.seq_ld + n] = hn;
+            __bf16 *sp = a.seqp + (long)row * a.seqp_ld + n;
+            __bf16 hh, mm, ll;
+            split3(hn, hh, mm, ll);
+            sp[0] = hh; sp[a.seqp_plane] = mm; sp[2 * a.seqp_plane] = ll;
+        }
+}
+
+template <int MT, int PF>
+__global__ __launch_bounds__(256) void k_gru_step_split(GruSplitArgs a) { gru_split_body<MT, PF>(a); }
+template <int MT, int PF>
+__global__ __launch_bounds__(256) void k_gru_step_split_multi(GruSplitMulti m) { gru_split_body<MT, PF>(m.a[blockIdx.z]); }
+
 }  // namespace se

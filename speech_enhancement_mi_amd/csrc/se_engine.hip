@@ -32,6 +32,7 @@
 #include "fsn.hip.h"
 #include "fft_lds.h"
 #include "gemm.hip.h"
+#include "gru_pack.h"
 #include "norm.hip.h"
 #include "stft.hip.h"
 #include "state_rows.hip.h"
@@ -80,6 +81,8 @@ struct se_engine : EngineHost {
     bool weights_ready = false;
     int gru_direct = -1;      // SE_GRU_DIRECT: 1 = always k_gru_step (W_hh streamed from L2), 0 = always k_gru_step2 (LDS slice),
                               // default -1 = k_gru_step in the overlapped (pipelined) bottleneck stage, k_gru_step2 otherwise
+    int gru_split = -1;       // SE_GRU_SPLIT: the split-bf16 step kernel (k_gru_step_split) where eligible (gru_split_eligible): 1 = everywhere,
+                              // 0 = never, default -1 = in the overlapped stage, and only while SE_GRU_DIRECT is unset
 
     SigChain sig;  // STFT / iSTFT tables and plan (sig_chain.h)
 
@@ -87,6 +90,7 @@ struct se_engine : EngineHost {
     Level lv[SE_MAX_LEVELS];  // enc i at lv[i]; decoder j at lv[j] (dec_* members)
     DevBuf wih[4], whh[4], bih[4], bhh[4], fcw, fcb, gnw, gnb;
     DevBuf wih_x[4], fcw_x;  // bf16x3 planes [3][N][K] of the GEMM weights (k_gemm_bf16x6)
+    DevBuf whh_p[4];         // W_hh as packed bf16 plane fragments (gru_pack.h) for k_gru_step_split: precision 0 and H % 32 == 0 only
     int variant = 0, act = 1, eps_mode = 0, atan2_phase = 0, npre = 0;  // derived from se_config.variant
     int precision = 0;        // se_config.precision: 0 = bf16x6 (3 operand planes), 1 = fp16 operands (1 plane), 2 = bf16x3 (2 planes)
     int num_cu = 256;         // compute units of the device (MI355X: 256)
@@ -471,6 +475,12 @@ int prepare_weights(se_engine *e) {
         if ((rc = dev_upload(e, e->wih[l], *a)) || (rc = dev_upload(e, e->whh[l], *b)) ||
             (rc = dev_upload(e, e->bih[l], *c)) || (rc = dev_upload(e, e->bhh[l], *d)))
             return rc;
+        if (e->precision == 0 && H % 32 == 0) {
+            std::vector<uint16_t> pk;
+            gru_pack_whh(b->data(), H, pk);
+            if ((rc = dev_alloc(e, e->whh_p[l], pk.size() / 2))) return rc;
+            HIPCHECK(e, hipMemcpy(e->whh_p[l].p, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        }
     }
     {
         auto *a = param(e, "gru.fc_output_layer.weight", (size_t)D * H);
@@ -652,7 +662,8 @@ uint4 *decin_p(se_engine *e, int slot);  // convp_engine.inc.h: decoder-input ri
 // `overlapped`: the stage shares the chip with the other streams.  The GRU step then uses the small-footprint kernel
 // (k_gru_step: 54 VGPRs, 6 KB LDS, W_hh straight from L2) whose waves fit next to resident convolution workgroups, instead
 // of k_gru_step2 (188 VGPRs, 96 KB LDS slice of W_hh), which is 15 % faster alone but has to wait for a convolution
-// workgroup to retire on every CU at every step.
+// workgroup to retire on every CU at every step.  On the plane GEMM route at precision 0 the overlapped stage runs the split-bf16
+// step instead (k_gru_step_split: bf16 MFMAs on the planes of h_{t-1}, 200 registers, 12 KB LDS; SE_GRU_SPLIT, gru_split_on).
 int stage_gru_proj0(se_engine *e, int cur, hipStream_t st) {
     const int T = e->T, B = e->B, H = e->H, D = e->D;
     if (e->dbg_skip & 2) return 0;
@@ -660,6 +671,20 @@ int stage_gru_proj0(se_engine *e, int cur, hipStream_t st) {
     (void)B;
     if (e->gemm_p) return launch_gemm_p(e, e->gruinP[cur].p, e->wih_xp.p, e->bih[0].p, e->gi0[cur].p, 3L * H, Ba * T, 3 * H, D, 0, st, "gru_ih0");
     return launch_gemm(e, e->gru_in[cur].p, D, e->wih[0].p, D, e->bih[0].p, e->gi0[cur].p, 3L * H, Ba * T, 3 * H, D, 0, st, "gru_ih0", e->wih_x[0].p);
+}
+
+// The split-bf16 step (k_gru_step_split) reads h_{t-1} as the planes the plane GEMM route writes and W_hh as packed PL = 3 fragments
+bool gru_split_eligible(const se_engine *e) { return e->gemm_p && e->precision == 0 && e->H % 32 == 0 && e->B > 16; }
+bool gru_split_on(const se_engine *e, bool overlapped) {
+    if (!gru_split_eligible(e) || e->gru_split == 0) return false;
+    return e->gru_split == 1 || (overlapped && e->gru_direct < 0);
+}
+// (32 streams per workgroup, two k steps in flight per wave: the variant that won in the pipelined step, gemm.hip.h)
+void launch_gru_split(se_engine *e, const GruSplitArgs &g, int rows, hipStream_t st) {
+    hipLaunchKernelGGL((k_gru_step_split<1, 2>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
+}
+void launch_gru_split_multi(se_engine *e, const GruSplitMulti &m, int rows, int z, hipStream_t st) {
+    hipLaunchKernelGGL((k_gru_step_split_multi<1, 2>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
 }
 
 int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlapped) {
@@ -675,6 +700,7 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
                                    ("gru_ih" + std::to_string(l)).c_str(), e->wih_x[l].p))) return rc;
     }
     float *seq = e->seqr[l][cur].p;
+    const bool split = gru_split_on(e, overlapped);
     for (int t = 0; t < T && !(e->dbg_skip & 1); t++) {
         const int hc = e->hcur[l];
         GruStepArgs g{gi + (long)t * 3 * H, (long)T * 3 * H, e->hbuf[l][hc].p, e->whh[l].p, e->bhh[l].p,
@@ -682,6 +708,12 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
         if (e->gemm_p) {
             g.seqp = reinterpret_cast<__bf16 *>(e->seqP[l][cur].p) + (long)t * H;
             g.seqp_ld = (long)T * H; g.seqp_plane = (long)B * T * H; g.seqp_pl = operand_planes(e->precision);
+        }
+        if (split) {
+            ProfScope ps(e, "k_gru_step_split", "gru_step", 2.0 * B * 3 * H * H, st);
+            launch_gru_split(e, GruSplitArgs{g, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? g.seqp - H : nullptr}, Ba, st);
+            e->hcur[l] = hc ^ 1;
+            continue;
         }
         ProfScope ps(e, "k_gru_step", "gru_step", 2.0 * B * 3 * H * H, st);
         const dim3 grid((H + 15) / 16, (Ba + 31) / 32);
@@ -721,8 +753,10 @@ int stage_gru_round(se_engine *e, const int *slots, hipStream_t st) {
     int bmax = 0;  // every layer's own row count is in its arguments; the grid covers the largest
     for (int l = 0; l < e->NL; l++)
         if (slots[l] >= 0) bmax = std::max(bmax, e->bact_slot[slots[l]]);
+    const bool split = gru_split_on(e, /*overlapped=*/true);
     for (int t = 0; t < T && !(e->dbg_skip & 1); t++) {
         GruStepMulti m{};
+        GruSplitMulti ms{};
         int z = 0;
         for (int l = 0; l < e->NL; l++) {
             if (slots[l] < 0) continue;
@@ -735,6 +769,12 @@ int stage_gru_round(se_engine *e, const int *slots, hipStream_t st) {
                 ga.seqp_ld = (long)T * H; ga.seqp_plane = (long)B * T * H; ga.seqp_pl = operand_planes(e->precision);
             }
             e->hcur[l] = hc ^ 1;
+            if (split) ms.a[z - 1] = GruSplitArgs{ga, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? ga.seqp - H : nullptr};
+        }
+        if (split) {
+            ProfScope ps(e, "k_gru_step_split_multi", "gru_step", 2.0 * B * 3 * H * H * z, st);
+            launch_gru_split_multi(e, ms, bmax, z, st);
+            continue;
         }
         ProfScope ps(e, "k_gru_step", "gru_step", 2.0 * B * 3 * H * H * z, st);
         // (the same arithmetic as the single-stream path: batches of <= 16 streams split K over eight waves)
@@ -996,6 +1036,7 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (e->D != e->F[L] * cfg->channels[L - 1]) return bail(SE_ERR_ARG, "num_freqs/num_levels combination breaks the reference reshape (CRN.py:450,478)");
     if (e->T <= 2 * (1 << (L - 1))) return bail(SE_ERR_ARG, "segment shorter than the largest dilation history (CRN.py:333)");
     if (const char *s = getenv("SE_GRU_DIRECT")) e->gru_direct = atoi(s) != 0 ? 1 : 0;
+    if (const char *s = getenv("SE_GRU_SPLIT")) e->gru_split = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
     if (const char *s = getenv("SE_DBG_SKIP")) { e->dbg_skip = atoi(s); fprintf(stderr, "se_engine: SE_DBG_SKIP=%d - stages are skipped, results are WRONG (timing experiment)\n", e->dbg_skip); }
@@ -1051,7 +1092,7 @@ void se_destroy(se_engine *e) {
         for (hipStream_t q : e->stage_stream) (void)hipStreamDestroy(q);
     }
     for (int i = 0; i < 4; i++) {
-        dev_free(e->wih[i]); dev_free(e->whh[i]); dev_free(e->bih[i]); dev_free(e->bhh[i]); dev_free(e->wih_x[i]);
+        dev_free(e->wih[i]); dev_free(e->whh[i]); dev_free(e->whh_p[i]); dev_free(e->bih[i]); dev_free(e->bhh[i]); dev_free(e->wih_x[i]);
         dev_free(e->hbuf[i][0]); dev_free(e->hbuf[i][1]); dev_free(e->gil[i]);
     }
     for (int i = 0; i < SE_MAX_LEVELS; i++) {
