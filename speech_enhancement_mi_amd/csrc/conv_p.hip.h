@@ -24,6 +24,7 @@
 
 #include "conv_p_args.h"
 #include "split_bf16.h"
+#include "split_f16pair.h"
 
 namespace se {
 
@@ -513,7 +514,9 @@ __global__ __launch_bounds__(256) void k_f32_to_p(F32ToPArgs a) {
 
 // gLN from the producing convolution's partial statistics: R layout -> P layout (normalise, per-channel affine, split)
 
-template <int PL>
+// FMT = kF16Pair: the output planes are the fp16 pair (split_f16pair.h; PL is then 2).  Launched without a residual only (a.res reads
+// the planes of ANOTHER buffer, whose format is its own).
+template <int PL, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(256) void k_gln_p(GlnPArgs a) {
     __shared__ float sm[2];
     const int b = blockIdx.z, o = blockIdx.y;
@@ -537,7 +540,7 @@ __global__ __launch_bounds__(256) void k_gln_p(GlnPArgs a) {
         float v[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
 #pragma unroll
         for (int c = 0; c < 8; c++) v[c] = v[c] * sc[c] + sh[c];  // (x - mean) * inv * w + b; zero for padded channels
-        if (a.res) {  // + x: the planes of x, summed from the smallest, give x back exactly
+        if (FMT == PlaneFmt::kBf16 && a.res) {  // + x: the planes of x, summed from the smallest, give x back exactly
             const uint4 *rp = a.res + (long)b * a.res_stream + (long)o * PL * TF + i;
             float r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -557,8 +560,10 @@ __global__ __launch_bounds__(256) void k_gln_p(GlnPArgs a) {
 #pragma unroll
             for (int c = 0; c < 8; c++) v[c] += r[c];
         }
-        if (a.mode == 0) split_store8<PL>(v, a.y + (long)b * a.y_stream + (long)o * PL * TF + i, TF);
-        else split_store8<PL>(v, a.y + ((long)(b * a.T + t) * a.C8 + o) * a.F + f, a.y_plane);
+        uint4 *dst = a.mode == 0 ? a.y + (long)b * a.y_stream + (long)o * PL * TF + i : a.y + ((long)(b * a.T + t) * a.C8 + o) * a.F + f;
+        const long plane = a.mode == 0 ? TF : a.y_plane;
+        if constexpr (FMT == PlaneFmt::kF16Pair) split_store8_pair(v, dst, plane);
+        else split_store8<PL>(v, dst, plane);
     }
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "conv_p_args.h"
+#include "split_f16pair.h"
 
 namespace se {
 
@@ -10,7 +11,8 @@ int conv_p_launch(int ntap, int ntap2, int NT, int CO, int PL, dim3 grid, size_t
 bool conv_p_has_instance(int ntap, int NT, int CO, int ntap2 = 0);
 void conv_p_set_attributes();
 void launch_k_featurize_p(int PL, dim3 grid, hipStream_t st, const FeatPArgs &a);
-void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a);
+// fmt = kF16Pair: the output planes are the fp16 pair (PL is then not used)
+void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a, PlaneFmt fmt = PlaneFmt::kBf16);
 void launch_k_f32_to_p(int PL, dim3 grid, hipStream_t st, const F32ToPArgs &a);
 void launch_k_gln2_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a);
 void launch_k_gln2_stream_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a);

@@ -654,7 +654,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
             g.mode = 1;
             g.y = reinterpret_cast<uint4 *>(e->gruinP[cur].p);
             g.y_plane = (long)B * T * g.C8 * Fo;
-            launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g);
+            launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g, buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA));
         } else {  // last level feeds the fp32 GEMM of the bottleneck (launch_gemm): [T][C*F] rows
             GlnEwArgs ge{nullptr, e->gru_in[cur].p, g.w, g.b, g.st, 3, Co, T, Fo, nullptr};
             ge.x = S.encR[i].p;

@@ -13,6 +13,7 @@
 
 #include "../../include/se_engine.h"
 #include "chain_plan.h"
+#include "split_f16pair.h"
 
 namespace se {
 
@@ -91,6 +92,29 @@ inline float bf16_to_f32(uint16_t h) {
 // operand planes per precision mode: 0 -> 3 bf16 planes (hi, mid, lo; six products), 1 -> 1 fp16 plane, 2 -> 2 bf16 planes
 // (hi, mid; three products hi*hi + hi*mid + mid*hi)
 inline int operand_planes(int precision) { return precision == 1 ? 1 : (precision == 2 ? 2 : 3); }
+
+// The plane count is a property of the BUFFER, not only of the precision mode: with the fp16 pair format on (split_f16pair.h; precision
+// 0 only, decided when the weights are loaded) the buffers of kind kGemmA hold two fp16 planes.  kFeature: the STFT features and what
+// reads them (xinP[0]) - the magnitude channel scales with the input level, so they stay on bf16 planes; kConvAct: the activation
+// planes of the convolution / skip path (bf16 planes in this revision); kGemmA: the A operands of the bottleneck GEMMs and of the
+// recurrence (gruinP, seqP), bounded by a norm and by the GRU cell.
+enum class PlaneBuf { kFeature, kConvAct, kGemmA };
+inline PlaneFmt buffer_format(int precision, bool pair_on, PlaneBuf kind) {
+    return pair_on && precision == 0 && kind == PlaneBuf::kGemmA ? PlaneFmt::kF16Pair : PlaneFmt::kBf16;
+}
+inline int buffer_planes(int precision, bool pair_on, PlaneBuf kind) {
+    return buffer_format(precision, pair_on, kind) == PlaneFmt::kF16Pair ? kPairPlanesA : operand_planes(precision);
+}
+
+// the fp16-pair planes (2^11 hi, lo, hi) of a [rows][cols] fp32 matrix -> device buffer of 3*rows*cols uint16 (the shape of upload_planes)
+inline int upload_planes_pair(EngineHost *e, DevBuf &b, const std::vector<float> &w) {
+    std::vector<uint16_t> planes((size_t)kPairPlanesW * w.size());
+    pair_weight_matrix(w.data(), w.size(), planes.data());
+    int rc = dev_alloc(e, b, (planes.size() + 1) / 2);
+    if (rc) return rc;
+    HIPCHECK(e, hipMemcpy(b.p, planes.data(), planes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return 0;
+}
 
 // the operand planes of a [rows][cols] fp32 matrix at `precision` -> device buffer of PL*rows*cols uint16
 inline int upload_planes(EngineHost *e, DevBuf &b, const std::vector<float> &w, int precision) {

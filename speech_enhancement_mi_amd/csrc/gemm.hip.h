@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "conv_igemm.hip.h"
 #include "split_bf16.h"
+#include "split_f16pair.h"
 
 namespace se {
 
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(256) void k_gemm_x(GemmX6Args a) {
 //   * workgroup id -> tile is XCD-aware: the eight XCDs (id mod 8) each own a gx x gy block of tiles, so an operand tile is
 //     fetched into as few L2s as possible.
 struct GemmPArgs {
-    const uint4 *Ap;   // [PL][M][K/8] pieces of 8 bf16
+    const uint4 *Ap;   // [PL][M][K/8] pieces of 8 bf16 (kF16Pair: two planes of fp16)
     const uint4 *Wp;   // [PL][N][K/8]
     long a_plane, w_plane;  // uint4 per plane
     const float *bias;
@@ -319,12 +320,18 @@ __device__ __forceinline__ void gemm_p_rowsum16(float (&v)[16], int l31) {
     v[0] += __shfl_xor(v[0], 16, 64);
 }
 
-template <int PL>
+// FMT = kF16Pair (split_f16pair.h; PL = 3 is then the WEIGHT plane count): A arrives as the two fp16 planes (hi, lo), W as the three
+// fp16 planes (2^11 hi, lo, hi); three f16 MFMAs per tile pair accumulate 2^11 (a w) and the epilogue scales by 2^-11 ahead of the
+// bias, the activation and the statistics.  The ring stage shrinks from 72 to 56 KB at the same tile.
+template <int PL, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    extern __shared__ __align__(16) uint4 gl[];  // [stage 2]{A [PL][256 rows][4 pieces], W [PL][128 rows][4 pieces]}
-    constexpr int kPieces = 1536 * PL;           // uint4 per chunk
-    constexpr int kNA = 2 * PL, kNW = PL;        // LDS-DMA instructions per thread per chunk for A / W
+    constexpr bool kPair = FMT == PlaneFmt::kF16Pair;
+    static_assert(!kPair || PL == kPairPlanesW, "the fp16 pair has three weight planes");
+    constexpr int PA = kPair ? kPairPlanesA : PL, PW = PL;  // planes of A / W
+    extern __shared__ __align__(16) uint4 gl[];  // [stage 2]{A [PA][256 rows][4 pieces], W [PW][128 rows][4 pieces]}
+    constexpr int kPieces = 1024 * PA + 512 * PW;  // uint4 per chunk
+    constexpr int kNA = 2 * PA, kNW = PW;          // LDS-DMA instructions per thread per chunk for A / W
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -375,7 +382,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (__attribute__((address_space(3))) void *)(base + i * 512), 16, voa[i] + add, 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < kNW; i++)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void *)(base + 1024 * PL + i * 512), 16, vow[i] + add, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void *)(base + 1024 * PA + i * 512), 16, vow[i] + add, 0, 0, 0);
     };
     // LDS byte addresses of this lane's fragments inside one stage: rows wm + l31 / wn + l31 (+ 32 i and the plane as
     // immediates), K step ks holds pieces 2 ks + half, XOR-swizzled with bits 2-3 of the row (which only l31 contributes to)
@@ -385,7 +392,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) {
         adA[ks] = lds0 + (unsigned)(((wm + l31) * 4 + ((2 * ks + half) ^ sw)) * 16);
-        adB[ks] = lds0 + (unsigned)((1024 * PL + (wn + l31) * 4 + ((2 * ks + half) ^ sw)) * 16);
+        adB[ks] = lds0 + (unsigned)((1024 * PA + (wn + l31) * 4 + ((2 * ks + half) ^ sw)) * 16);
     }
     f32x16 acc[2][2];
 #pragma unroll
@@ -404,7 +411,13 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
 #pragma unroll
             for (int jj = 0; jj < 2; jj++) {
                 f32x16 c = acc[i][jj];
-                if (PL >= 2) {
+                if (kPair) {  // smallest terms first, as below
+                    const f16x8g a0 = __builtin_bit_cast(f16x8g, fa[i][0]), a1 = __builtin_bit_cast(f16x8g, fa[i][P1]);
+                    const f16x8g b0 = __builtin_bit_cast(f16x8g, fb[jj][0]), b1 = __builtin_bit_cast(f16x8g, fb[jj][P1]), b2 = __builtin_bit_cast(f16x8g, fb[jj][P2]);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, c, 0, 0, 0);
+                } else if (PL >= 2) {
                     const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[i][0]), a1 = __builtin_bit_cast(bf16x8, fa[i][P1]), a2 = __builtin_bit_cast(bf16x8, fa[i][P2]);
                     const bf16x8 b0 = __builtin_bit_cast(bf16x8, fb[jj][0]), b1 = __builtin_bit_cast(bf16x8, fb[jj][P1]), b2 = __builtin_bit_cast(bf16x8, fb[jj][P2]);
                     if (PL == 3) {
@@ -428,15 +441,19 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         SE_DS_READ128(fa[1][0], xa, 2048);                          \
         SE_DS_READ128(fb[0][0], xb, 0);                             \
         SE_DS_READ128(fb[1][0], xb, 2048);                          \
-        if constexpr (PL > 1) {                                     \
+        if constexpr (PA > 1) {                                     \
             SE_DS_READ128(fa[0][1], xa, 16384);                     \
             SE_DS_READ128(fa[1][1], xa, 16384 + 2048);              \
+        }                                                           \
+        if constexpr (PW > 1) {                                     \
             SE_DS_READ128(fb[0][1], xb, 8192);                      \
             SE_DS_READ128(fb[1][1], xb, 8192 + 2048);               \
         }                                                           \
-        if constexpr (PL > 2) {                                     \
+        if constexpr (PA > 2) {                                     \
             SE_DS_READ128(fa[0][2], xa, 32768);                     \
             SE_DS_READ128(fa[1][2], xa, 32768 + 2048);              \
+        }                                                           \
+        if constexpr (PW > 2) {                                     \
             SE_DS_READ128(fb[0][2], xb, 16384);                     \
             SE_DS_READ128(fb[1][2], xb, 16384 + 2048);              \
         }                                                           \
@@ -449,6 +466,10 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         asm volatile("s_waitcnt lgkmcnt(" #CNT ")"                                                                             \
                      : "+v"(fa[0][0]), "+v"(fa[1][0]), "+v"(fb[0][0]), "+v"(fb[1][0]), "+v"(fa[0][1]), "+v"(fa[1][1]),         \
                        "+v"(fb[0][1]), "+v"(fb[1][1]));                                                                        \
+    else if constexpr (kPair)                                                                                                  \
+        asm volatile("s_waitcnt lgkmcnt(" #CNT ")"                                                                             \
+                     : "+v"(fa[0][0]), "+v"(fa[1][0]), "+v"(fb[0][0]), "+v"(fb[1][0]), "+v"(fa[0][1]), "+v"(fa[1][1]),         \
+                       "+v"(fb[0][1]), "+v"(fb[1][1]), "+v"(fb[0][2]), "+v"(fb[1][2]));                                        \
     else                                                                                                                       \
         asm volatile("s_waitcnt lgkmcnt(" #CNT ")"                                                                             \
                      : "+v"(fa[0][0]), "+v"(fa[1][0]), "+v"(fb[0][0]), "+v"(fb[1][0]), "+v"(fa[0][1]), "+v"(fa[1][1]),         \
@@ -466,7 +487,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         u32x4 fa0[2][3], fb0[2][3], fa1[2][3], fb1[2][3];
         SE_GEMMP_READ(fa0, fb0, 0, sb)
         SE_GEMMP_READ(fa1, fb1, 1, sb)
-        if constexpr (PL == 1) { SE_GEMMP_WAIT(4, fa0, fb0); } else if constexpr (PL == 2) { SE_GEMMP_WAIT(8, fa0, fb0); } else { SE_GEMMP_WAIT(12, fa0, fb0); }
+        if constexpr (PL == 1) { SE_GEMMP_WAIT(4, fa0, fb0); } else if constexpr (PL == 2) { SE_GEMMP_WAIT(8, fa0, fb0); } else if constexpr (kPair) { SE_GEMMP_WAIT(10, fa0, fb0); } else { SE_GEMMP_WAIT(12, fa0, fb0); }
         multiply(fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);  // keep the first K step's MFMAs above the second wait
         SE_GEMMP_WAIT(0, fa1, fb1);
@@ -499,7 +520,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
             for (int jj = 0; jj < 2; jj++) {
                 const int n = n0 + wn + jj * 32 + l31;
                 if (n >= a.N) continue;
-                const float x = conv_act(acc[i][jj][r] + bsj[jj], a.relu);
+                const float x = conv_act((kPair ? acc[i][jj][r] * kPairInvScale : acc[i][jj][r]) + bsj[jj], a.relu);
                 if (m < a.M) a.C[(long)m * a.ldc + n] = x;
                 ss += x; qq += x * x;
             }
@@ -548,7 +569,25 @@ struct GruStepArgs {
     __bf16 *seqp;        // optional: h_t also as split-bf16 planes [PL][rows][H] (the A operand of the next GEMM, k_gemm_p);
     long seqp_ld, seqp_plane;  // + t*H applied; row stride and plane stride in elements
     int seqp_pl;         // planes: 3, 2, or 1 (fp16)
+    int seqp_pair;       // the planes are the fp16 pair (split_f16pair.h; seqp_pl = 2) instead of bf16
 };
+
+// h_t into the sequence planes (sp = the element of plane 0)
+__device__ __forceinline__ void gru_seqp_store(const GruStepArgs &a, __bf16 *sp, float hn) {
+    if (a.seqp_pair) {
+        uint16_t hh, ll;
+        split2h(hn, hh, ll);
+        sp[0] = __builtin_bit_cast(__bf16, hh); sp[a.seqp_plane] = __builtin_bit_cast(__bf16, ll);
+    } else if (a.seqp_pl == 1) {
+        const _Float16 hv = (_Float16)hn;
+        sp[0] = __builtin_bit_cast(__bf16, hv);
+    } else {
+        __bf16 hh, mm, ll;
+        split3(hn, hh, mm, ll);
+        sp[0] = hh; sp[a.seqp_plane] = mm;
+        if (a.seqp_pl == 3) sp[2 * a.seqp_plane] = ll;
+    }
+}
 
 // Up to four independent steps in ONE launch (blockIdx.z selects the argument set): the pipelined path advances layer l of
 // segment n - l for every layer l at once (layer 1 lags one segment behind layer 0, so both halves of a launch have the
@@ -652,18 +691,7 @@ __device__ __forceinline__ void gru_step_body(const GruStepArgs &a) {
                 float *gs = a.gates + (long)row * a.gates_ld;
                 gs[n] = rg; gs[H + n] = zg; gs[2 * H + n] = ng; gs[3 * H + n] = gh_n;
             }
-            if (a.seqp) {
-                __bf16 *sp = a.seqp + (long)row * a.seqp_ld + n;
-                if (a.seqp_pl == 1) {
-                    const _Float16 hv = (_Float16)hn;
-                    sp[0] = __builtin_bit_cast(__bf16, hv);
-                } else {
-                    __bf16 hh, mm, ll;
-                    split3(hn, hh, mm, ll);
-                    sp[0] = hh; sp[a.seqp_plane] = mm;
-                    if (a.seqp_pl == 3) sp[2 * a.seqp_plane] = ll;
-                }
-            }
+            if (a.seqp) gru_seqp_store(a, a.seqp + (long)row * a.seqp_ld + n, hn);
         }
     }
 }
@@ -785,18 +813,7 @@ __global__ __launch_bounds__(256) void k_gru_step2(GruStepArgs a) {
             const float hn = (1.0f - zg) * ng + zg * hp;
             a.hout[(long)row * H + n] = hn;
             a.seq[(long)row * a.seq_ld + n] = hn;
-            if (a.seqp) {
-                __bf16 *sp = a.seqp + (long)row * a.seqp_ld + n;
-                if (a.seqp_pl == 1) {
-                    const _Float16 hv = (_Float16)hn;
-                    sp[0] = __builtin_bit_cast(__bf16, hv);
-                } else {
-                    __bf16 hh, mm, ll;
-                    split3(hn, hh, mm, ll);
-                    sp[0] = hh; sp[a.seqp_plane] = mm;
-                    if (a.seqp_pl == 3) sp[2 * a.seqp_plane] = ll;
-                }
-            }
+            if (a.seqp) gru_seqp_store(a, a.seqp + (long)row * a.seqp_ld + n, hn);
         }
     }
 }
@@ -819,15 +836,19 @@ __global__ __launch_bounds__(256) void k_gru_step2(GruStepArgs a) {
 // by its chain of dependent L2 round trips and by what it takes from the co-resident convolutions, not by MFMA issue (1.9 us) or
 // bytes (50 MB per launch).
 struct GruSplitArgs {
-    GruStepArgs s;        // as k_gru_step (gates unused; seqp with 3 planes is required)
+    GruStepArgs s;        // as k_gru_step (gates unused; seqp is required: 3 bf16 planes, or the fp16 pair with PAIR)
     const uint4 *whp;     // packed W_hh planes
     const __bf16 *hp;     // planes of h_{t-1}: s.seqp - H for t >= 1, nullptr at t = 0
 };
 struct GruSplitMulti { GruSplitArgs a[4]; };
 
-template <int MT, int PF>
+// PAIR: the fp16 pair format (split_f16pair.h) - two A planes from `hp` (at t = 0 split2h on the fly, which gives the bits the previous
+// epilogue would have stored), W_hh packed as (2^11 hi, lo, hi) fp16 fragments in the same image, three f16 MFMAs per gate, the
+// 2^-11 applied to the reduced sums ahead of the bias, h_t stored as two planes.  Same split-K reduction order.
+template <int MT, int PF, bool PAIR = false>
 __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int NA = PAIR ? kPairPlanesA : 3;  // A planes
     __shared__ float red[4][3][MT * 4][64];  // [source wave][destination wave, the source left out][register][lane]
     const GruStepArgs &a = ga.s;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -854,7 +875,7 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
     // ring at run time and spill it): plane p of a k step at abase[p] + ks * astride.  At t = 0 the raw fp32 values travel in
     // slots 0 and 1 (slot 2 repeats slot 1) and are split when they are used.
     const bool planes = ga.hp != nullptr;  // uniform
-    const char *abase[MT][3];
+    const char *abase[MT][NA];
     const long astride = planes ? 32 : 64;  // bytes per k step: 16 bf16 / 16 floats
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
@@ -862,15 +883,15 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
         const char *pb = reinterpret_cast<const char *>((planes ? ga.hp : a.seqp) + (long)arow * a.seqp_ld + half * 8);
         const char *fb = reinterpret_cast<const char *>(a.hprev + (long)arow * H + half * 8);
 #pragma unroll
-        for (int p = 0; p < 3; p++) abase[mt][p] = planes ? pb + p * a.seqp_plane * 2 : fb + (p ? 16 : 0);
+        for (int p = 0; p < NA; p++) abase[mt][p] = planes ? pb + p * a.seqp_plane * 2 : fb + (p ? 16 : 0);
     }
     const uint4 *wp = ga.whp + (long)blockIdx.x * KS * 9 * 64 + lane;
-    u32x4 qa[PF][MT][3], qw[PF][9];
+    u32x4 qa[PF][MT][NA], qw[PF][9];
     auto request = [&](int i, int ks) {
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-            for (int p = 0; p < 3; p++) qa[i][mt][p] = *reinterpret_cast<const u32x4 *>(abase[mt][p] + ks * astride);
+            for (int p = 0; p < NA; p++) qa[i][mt][p] = *reinterpret_cast<const u32x4 *>(abase[mt][p] + ks * astride);
 #pragma unroll
         for (int f = 0; f < 9; f++) qw[i][f] = *reinterpret_cast<const u32x4 *>(wp + ((long)ks * 9 + f) * 64);
     };
@@ -889,10 +910,22 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
             // a slot past the wave's share (shares that are no multiple of PF) holds a valid k step and is multiplied by zero:
             // no branch around the MFMAs, which would send the accumulators through a copy on every trip
             const unsigned keep = ks + i < ks1 ? 0xFFFFFFFFu : 0u;  // uniform
-            u32x4 ca[MT][3];
+            u32x4 ca[MT][NA];
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
-                if (!planes) {
+                if (!planes && PAIR) {
+                    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+                    u16x8 hh, ll;
+#pragma unroll
+                    for (int e = 0; e < 8; e++) {
+                        const float x = __uint_as_float(e < 4 ? qa[i][mt][0][e & 3] : qa[i][mt][1][e & 3]);
+                        uint16_t h1, l1;
+                        split2h(x, h1, l1);
+                        hh[e] = h1; ll[e] = l1;
+                    }
+                    ca[mt][0] = __builtin_bit_cast(u32x4, hh);
+                    ca[mt][1] = __builtin_bit_cast(u32x4, ll);
+                } else if (!planes) {
                     bf16x8 hh, mm, ll;
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
@@ -903,28 +936,41 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
                     }
                     ca[mt][0] = __builtin_bit_cast(u32x4, hh);
                     ca[mt][1] = __builtin_bit_cast(u32x4, mm);
-                    ca[mt][2] = __builtin_bit_cast(u32x4, ll);
+                    ca[mt][NA - 1] = __builtin_bit_cast(u32x4, ll);  // (NA = 3 on this branch)
                 } else {
 #pragma unroll
-                    for (int p = 0; p < 3; p++) ca[mt][p] = qa[i][mt][p];
+                    for (int p = 0; p < NA; p++) ca[mt][p] = qa[i][mt][p];
                 }
 #pragma unroll
-                for (int p = 0; p < 3; p++) ca[mt][p] &= keep;
+                for (int p = 0; p < NA; p++) ca[mt][p] &= keep;
             }
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
-                const bf16x8 a0 = __builtin_bit_cast(bf16x8, ca[mt][0]), a1 = __builtin_bit_cast(bf16x8, ca[mt][1]), a2 = __builtin_bit_cast(bf16x8, ca[mt][2]);
+                if constexpr (PAIR) {
+                    const f16x8g a0 = __builtin_bit_cast(f16x8g, ca[mt][0]), a1 = __builtin_bit_cast(f16x8g, ca[mt][1]);
 #pragma unroll
-                for (int g = 0; g < 3; g++) {
-                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, qw[i][g * 3]), b1 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 1]), b2 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 2]);
-                    f32x16 c = acc[mt][g];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
-                    acc[mt][g] = c;
+                    for (int g = 0; g < 3; g++) {
+                        const f16x8g b0 = __builtin_bit_cast(f16x8g, qw[i][g * 3]), b1 = __builtin_bit_cast(f16x8g, qw[i][g * 3 + 1]), b2 = __builtin_bit_cast(f16x8g, qw[i][g * 3 + 2]);
+                        f32x16 c = acc[mt][g];
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, c, 0, 0, 0);
+                        acc[mt][g] = c;
+                    }
+                } else {
+                    const bf16x8 a0 = __builtin_bit_cast(bf16x8, ca[mt][0]), a1 = __builtin_bit_cast(bf16x8, ca[mt][1]), a2 = __builtin_bit_cast(bf16x8, ca[mt][NA - 1]);
+#pragma unroll
+                    for (int g = 0; g < 3; g++) {
+                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, qw[i][g * 3]), b1 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 1]), b2 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 2]);
+                        f32x16 c = acc[mt][g];
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
+                        acc[mt][g] = c;
+                    }
                 }
             }
             // the slot's next k step, requested behind the MFMAs that read the slot (nothing past the wave's share)
@@ -983,9 +1029,9 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
         for (int i = 0; i < 4; i++) {
             const int row = r0 + mt * 32 + 8 * wave + 4 * half + i;
             if (row >= a.B) continue;
-            const float gh_r = gh[mt][0][i] + bh_r;
-            const float gh_z = gh[mt][1][i] + bh_z;
-            const float gh_n = gh[mt][2][i] + bh_n;
+            const float gh_r = (PAIR ? gh[mt][0][i] * kPairInvScale : gh[mt][0][i]) + bh_r;
+            const float gh_z = (PAIR ? gh[mt][1][i] * kPairInvScale : gh[mt][1][i]) + bh_z;
+            const float gh_n = (PAIR ? gh[mt][2][i] * kPairInvScale : gh[mt][2][i]) + bh_n;
             const float rg = 1.0f / (1.0f + expf(-(pgi[mt][i][0] + gh_r)));
             const float zg = 1.0f / (1.0f + expf(-(pgi[mt][i][1] + gh_z)));
             const float ng = tanhf(pgi[mt][i][2] + rg * gh_n);
@@ -993,15 +1039,21 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
             a.hout[(long)row * H + n] = hn;
             a.seq[(long)row * a.seq_ld + n] = hn;
             __bf16 *sp = a.seqp + (long)row * a.seqp_ld + n;
-            __bf16 hh, mm, ll;
-            split3(hn, hh, mm, ll);
-            sp[0] = hh; sp[a.seqp_plane] = mm; sp[2 * a.seqp_plane] = ll;
+            if constexpr (PAIR) {
+                uint16_t hh, ll;
+                split2h(hn, hh, ll);
+                sp[0] = __builtin_bit_cast(__bf16, hh); sp[a.seqp_plane] = __builtin_bit_cast(__bf16, ll);
+            } else {
+                __bf16 hh, mm, ll;
+                split3(hn, hh, mm, ll);
+                sp[0] = hh; sp[a.seqp_plane] = mm; sp[2 * a.seqp_plane] = ll;
+            }
         }
 }
 
-template <int MT, int PF>
-__global__ __launch_bounds__(256) void k_gru_step_split(GruSplitArgs a) { gru_split_body<MT, PF>(a); }
-template <int MT, int PF>
-__global__ __launch_bounds__(256) void k_gru_step_split_multi(GruSplitMulti m) { gru_split_body<MT, PF>(m.a[blockIdx.z]); }
+template <int MT, int PF, bool PAIR = false>
+__global__ __launch_bounds__(256) void k_gru_step_split(GruSplitArgs a) { gru_split_body<MT, PF, PAIR>(a); }
+template <int MT, int PF, bool PAIR = false>
+__global__ __launch_bounds__(256) void k_gru_step_split_multi(GruSplitMulti m) { gru_split_body<MT, PF, PAIR>(m.a[blockIdx.z]); }
 
 }  // namespace se

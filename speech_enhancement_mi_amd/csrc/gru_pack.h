@@ -12,6 +12,8 @@
 #include <cstring>
 #include <vector>
 
+#include "split_f16pair.h"
+
 namespace se {
 
 inline uint16_t gru_pack_bf16_rne(float x) {  // round to nearest even, as engine_host.h: bf16_rne
@@ -49,6 +51,18 @@ inline void gru_pack_whh(const float *whh, int H, std::vector<uint16_t> &out) {
                 out[gru_pack_index(H, g, n, k, 0)] = h;
                 out[gru_pack_index(H, g, n, k, 1)] = m;
                 out[gru_pack_index(H, g, n, k, 2)] = l;
+            }
+}
+
+// the same image for the fp16 pair format (split_f16pair.h): plane slots 0, 1, 2 of every fragment hold (2^11 hi, lo, hi) as fp16
+inline void gru_pack_whh_pair(const float *whh, int H, std::vector<uint16_t> &out) {
+    out.assign(gru_pack_size(H), 0);
+    for (int g = 0; g < 3; g++)
+        for (int n = 0; n < H; n++)
+            for (int k = 0; k < H; k++) {
+                uint16_t p[3];
+                pair_weight_planes(whh[((size_t)g * H + n) * H + k], p);
+                for (int pl = 0; pl < 3; pl++) out[gru_pack_index(H, g, n, k, pl)] = p[pl];
             }
 }
 

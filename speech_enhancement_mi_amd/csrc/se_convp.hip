@@ -79,8 +79,9 @@ void launch_k_f32_to_p(int PL, dim3 grid, hipStream_t st, const F32ToPArgs &a) {
     else if (PL == 2) hipLaunchKernelGGL(k_f32_to_p<2>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_f32_to_p<3>, grid, dim3(256), 0, st, a);
 }
-void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a) {
-    if (PL == 1) hipLaunchKernelGGL(k_gln_p<1>, grid, dim3(256), 0, st, a);
+void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a, PlaneFmt fmt) {
+    if (fmt == PlaneFmt::kF16Pair) hipLaunchKernelGGL((k_gln_p<kPairPlanesA, PlaneFmt::kF16Pair>), grid, dim3(256), 0, st, a);
+    else if (PL == 1) hipLaunchKernelGGL(k_gln_p<1>, grid, dim3(256), 0, st, a);
     else if (PL == 2) hipLaunchKernelGGL(k_gln_p<2>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_gln_p<3>, grid, dim3(256), 0, st, a);
 }

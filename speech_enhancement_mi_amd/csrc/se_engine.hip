@@ -90,7 +90,8 @@ struct se_engine : EngineHost {
     Level lv[SE_MAX_LEVELS];  // enc i at lv[i]; decoder j at lv[j] (dec_* members)
     DevBuf wih[4], whh[4], bih[4], bhh[4], fcw, fcb, gnw, gnb;
     DevBuf wih_x[4], fcw_x;  // bf16x3 planes [3][N][K] of the GEMM weights (k_gemm_bf16x6)
-    DevBuf whh_p[4];         // W_hh as packed bf16 plane fragments (gru_pack.h) for k_gru_step_split: precision 0 and H % 32 == 0 only
+    DevBuf whh_p[4];         // W_hh as packed plane fragments (gru_pack.h; bf16, or the fp16 pair's when pair_on) for k_gru_step_split:
+                             // precision 0 and H % 32 == 0 only
     int variant = 0, act = 1, eps_mode = 0, atan2_phase = 0, npre = 0;  // derived from se_config.variant
     int precision = 0;        // se_config.precision: 0 = bf16x6 (3 operand planes), 1 = fp16 operands (1 plane), 2 = bf16x3 (2 planes)
     int num_cu = 256;         // compute units of the device (MI355X: 256)
@@ -140,8 +141,13 @@ struct se_engine : EngineHost {
     int io_fuse = 1;          // SE_IO_FUSE=0: k_stft + k_featurize_p and k_final_mask_p + k_istft as four kernels (io_fused.hip.h fuses them)
     bool io_fuse_on = false;  // io_fuse and the fused kernels' workgroups fit a CU's LDS at this geometry
     int gemm_p_env = 1;
-    DevBuf gruinP[kRing], seqP[4][kRing];  // [PL][B*T][D'] / [PL][B*T][H] bf16 planes
+    DevBuf gruinP[kRing], seqP[4][kRing];  // [PL][B*T][D'] / [PL][B*T][H] planes (PlaneBuf::kGemmA: bf16, or two fp16 planes when pair_on)
     DevBuf wih_xp;                          // W_ih0 planes with K in the engine's feature order (k_gemm_p)
+    // fp16 pair format (split_f16pair.h) on the bottleneck: gruinP / seqP as two fp16 planes, the k_gemm_p weights (wih_xp, wih_h,
+    // fcw_xp) and whh_p as (2^11 hi, lo, hi), three MFMA terms instead of six
+    int f16_pair = 1;         // SE_F16_PAIR=0: the bf16 route (three planes, six terms) everywhere
+    bool pair_on = false;     // decided once per weight load (f16_pair_decide): knob, eligibility and the range guard
+    DevBuf wih_h[4];          // W_ih of layers >= 1 as pair planes (wih_x[l] stays bf16: the fp32-row GEMMs of small batches read it)
     // fc_output_layer + gLN(last) on the plane GEMM route: weight rows, bias and the norm's per-element affine permuted like W_ih0's
     // K axis, so that fc_out column (o * F + f) * 8 + c holds reference feature (8 o + c) * F + f (channels padded to whole octets
     // with zero rows); fc_stats [B][T * column tiles][2] = per-row (sum, sum of squares) partials from the GEMM's epilogue
@@ -354,11 +360,60 @@ bool crn_geometry_supported(const se_engine *e, std::string *why) {
     return true;
 }
 
+// whether the engine's shapes allow the plane GEMM route at all (which batches take it: select_gemm_route)
+bool gemm_p_capable(const se_engine *e) { return e->gemm_p_env && e->D % 32 == 0 && e->H % 32 == 0 && e->Ch[e->L] % 8 == 0; }
+
+// Range guard of the fp16 pair format, from the loaded parameters alone (never a run-time branch in a kernel): every activation that a
+// norm writes into a plane buffer is bounded by max|gamma| sqrt(N) + max|beta| (N elements per stream: |x - mean| <= sqrt(N) sigma),
+// and 2^11 w_hi must stay finite in fp16.  An activation bound above 6e4 or a weight operand of 2^4 or more keeps the whole engine
+// on the bf16 route.  All norms and all weight operands are checked, also those whose buffers do not take the format yet, so the
+// set of eligible checkpoints does not move when the convolution path follows.  (h_t is a convex combination of tanh values and
+// h_{t-1}; a caller-supplied state beyond the fp16 range is clamped by split2h.)
+bool f16_pair_guard(const se_engine *e) {
+    auto absmax = [&](const std::string &key, float &m) {
+        auto it = e->params.find(key);
+        if (it == e->params.end()) return false;
+        for (float v : it->second) {
+            if (!(std::fabs(v) <= 3.0e38f)) return false;  // inf / NaN
+            m = std::max(m, std::fabs(v));
+        }
+        return true;
+    };
+    auto norm_ok = [&](const std::string &prefix, double n) {
+        float g = 0, b = 0;
+        if (!absmax(prefix + "weight", g) || !absmax(prefix + "bias", b)) return false;
+        return (double)g * std::sqrt(n) + (double)b <= 6.0e4;
+    };
+    const int L = e->L, T = e->T;
+    for (int i = 0; i < L; i++)
+        if (!norm_ok("convlist." + std::to_string(i) + ".norm.", (double)e->Ch[i + 1] * T * e->F[i + 1])) return false;
+    for (int j = 0; j < L; j++) {
+        const int lvl = L - 1 - j, Co = lvl == 0 ? 2 : e->Ch[lvl], Fo = 2 * e->F[lvl + 1] - 1;
+        if (!norm_ok("deconvlist." + std::to_string(j) + ".norm.", (double)Co * T * Fo)) return false;
+        if (lvl > 0 && !norm_ok("deconvlist." + std::to_string(j) + ".residualnorm.", (double)Co * T * Fo)) return false;
+    }
+    if (!norm_ok("gru.norm.", (double)T * e->D)) return false;
+    for (const auto &kv : e->params) {  // every weight operand: all *.weight / weight_* that are not a norm's gamma
+        const std::string &k = kv.first;
+        if (k.find("norm") != std::string::npos || k.find("weight") == std::string::npos) continue;
+        float m = 0;
+        if (!absmax(k, m) || m >= 16.0f) return false;
+    }
+    return true;
+}
+
+// whether this weight load runs the fp16 pair format: the knob, eligibility (precision 0, the CRN variant, the plane GEMM route's
+// shapes) and the range guard
+void f16_pair_decide(se_engine *e) {
+    e->pair_on = e->f16_pair && e->precision == 0 && e->variant == 0 && gemm_p_capable(e) && f16_pair_guard(e);
+}
+
 int prepare_weights(se_engine *e) {
     if (e->weights_ready) return 0;
     std::string why;
     if (!crn_geometry_supported(e, &why)) return fail(e, SE_ERR_ARG, "%s", why.c_str());
     const int L = e->L, H = e->H, D = e->D;
+    f16_pair_decide(e);
     for (int i = 0; i < L; i++) {
         const int Ci = e->Ch[i], Co = e->Ch[i + 1], Fi = e->F[i], Fo = e->F[i + 1], d = 1 << i;
         const std::string p = "convlist." + std::to_string(i) + ".";
@@ -475,9 +530,11 @@ int prepare_weights(se_engine *e) {
         if ((rc = dev_upload(e, e->wih[l], *a)) || (rc = dev_upload(e, e->whh[l], *b)) ||
             (rc = dev_upload(e, e->bih[l], *c)) || (rc = dev_upload(e, e->bhh[l], *d)))
             return rc;
+        if (e->pair_on && l > 0 && (rc = upload_planes_pair(e, e->wih_h[l], *a))) return rc;
         if (e->precision == 0 && H % 32 == 0) {
             std::vector<uint16_t> pk;
-            gru_pack_whh(b->data(), H, pk);
+            if (e->pair_on) gru_pack_whh_pair(b->data(), H, pk);
+            else gru_pack_whh(b->data(), H, pk);
             if ((rc = dev_alloc(e, e->whh_p[l], pk.size() / 2))) return rc;
             HIPCHECK(e, hipMemcpy(e->whh_p[l].p, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
@@ -570,7 +627,9 @@ int launch_gemm(se_engine *e, const float *A, long lda, const float *W, long ldw
 // C = act(A W^T + bias) with both operands as split-bf16 planes ([PL][rows][K] bf16, K % 32 == 0): k_gemm_p
 int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *bias, float *C, long ldc, int Mr, int Nc, int Kd, int relu,
                   hipStream_t st, const char *label, float *stats = nullptr) {
-    const int PL = operand_planes(e->precision);
+    // every plane GEMM is a bottleneck GEMM: A is gruinP or seqP (kGemmA), W the matching weight planes (three in both formats at precision 0)
+    const int PL = operand_planes(e->precision), PA = buffer_planes(e->precision, e->pair_on, PlaneBuf::kGemmA);
+    const bool pair = buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA) == PlaneFmt::kF16Pair;
     ProfScope ps(e, "k_gemm_p", label, 2.0 * Mr * Nc * Kd, st);
     const int nrt = (Mr + kGemmPBM - 1) / kGemmPBM, nct = (Nc + kGemmPBN - 1) / kGemmPBN;
     // XCD blocks: the split of the tile grid into 8 equal blocks (gx x gy) that fetches the fewest bytes into the 8 private
@@ -593,10 +652,11 @@ int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *b
     // the A planes are laid out for the ALLOCATION batch ([PL][B * T][K]); a ragged call multiplies a prefix of the rows only (Mr = Bact * T)
     const long Ma = std::max<long>(Mr, (long)e->B * e->T);
     GemmPArgs g{reinterpret_cast<const uint4 *>(Ap), reinterpret_cast<const uint4 *>(Wp), Ma * Kd / 8, (long)Nc * Kd / 8, bias, C, Mr, Nc, Kd, ldc, relu,
-                (unsigned)((size_t)PL * Ma * Kd * 2), (unsigned)((size_t)PL * Nc * Kd * 2), nrt, nct, gx, gy, stats};
+                (unsigned)((size_t)PA * Ma * Kd * 2), (unsigned)((size_t)PL * Nc * Kd * 2), nrt, nct, gx, gy, stats};
     const dim3 grid(nblocks);
-    const size_t lds = (size_t)2 * 1536 * PL * 16;
-    if (PL == 1) hipLaunchKernelGGL(k_gemm_p<1>, grid, dim3(512), lds, st, g);
+    const size_t lds = (size_t)2 * (1024 * PA + 512 * PL) * 16;
+    if (pair) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
+    else if (PL == 1) hipLaunchKernelGGL(k_gemm_p<1>, grid, dim3(512), lds, st, g);
     else if (PL == 2) hipLaunchKernelGGL(k_gemm_p<2>, grid, dim3(512), lds, st, g);
     else hipLaunchKernelGGL(k_gemm_p<3>, grid, dim3(512), lds, st, g);
     HIPCHECK(e, hipGetLastError());
@@ -673,6 +733,14 @@ int stage_gru_proj0(se_engine *e, int cur, hipStream_t st) {
     return launch_gemm(e, e->gru_in[cur].p, D, e->wih[0].p, D, e->bih[0].p, e->gi0[cur].p, 3L * H, Ba * T, 3 * H, D, 0, st, "gru_ih0", e->wih_x[0].p);
 }
 
+// W_ih of layer l >= 1 as the plane GEMM reads it
+const float *wih_planes(const se_engine *e, int l) { return e->pair_on ? e->wih_h[l].p : e->wih_x[l].p; }
+// the sequence planes of a step's arguments: plane count and format of seqP
+void set_seqp_format(const se_engine *e, GruStepArgs &g) {
+    g.seqp_pl = buffer_planes(e->precision, e->pair_on, PlaneBuf::kGemmA);
+    g.seqp_pair = buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA) == PlaneFmt::kF16Pair;
+}
+
 // The split-bf16 step (k_gru_step_split) reads h_{t-1} as the planes the plane GEMM route writes and W_hh as packed PL = 3 fragments
 bool gru_split_eligible(const se_engine *e) { return e->gemm_p && e->precision == 0 && e->H % 32 == 0 && e->B > 16; }
 bool gru_split_on(const se_engine *e, bool overlapped) {
@@ -681,10 +749,12 @@ bool gru_split_on(const se_engine *e, bool overlapped) {
 }
 // (32 streams per workgroup, two k steps in flight per wave: the variant that won in the pipelined step, gemm.hip.h)
 void launch_gru_split(se_engine *e, const GruSplitArgs &g, int rows, hipStream_t st) {
-    hipLaunchKernelGGL((k_gru_step_split<1, 2>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
+    if (e->pair_on) hipLaunchKernelGGL((k_gru_step_split<1, 2, true>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((k_gru_step_split<1, 2>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
 }
 void launch_gru_split_multi(se_engine *e, const GruSplitMulti &m, int rows, int z, hipStream_t st) {
-    hipLaunchKernelGGL((k_gru_step_split_multi<1, 2>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
+    if (e->pair_on) hipLaunchKernelGGL((k_gru_step_split_multi<1, 2, true>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
+    else hipLaunchKernelGGL((k_gru_step_split_multi<1, 2>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
 }
 
 int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlapped) {
@@ -695,7 +765,7 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
     if (l > 0) {
         gi = e->gil[l].p;
         if (e->dbg_skip & 2) {}
-        else if (e->gemm_p) { if ((rc = launch_gemm_p(e, e->seqP[l - 1][cur].p, e->wih_x[l].p, e->bih[l].p, e->gil[l].p, 3L * H, Ba * T, 3 * H, H, 0, st, ("gru_ih" + std::to_string(l)).c_str()))) return rc; }
+        else if (e->gemm_p) { if ((rc = launch_gemm_p(e, e->seqP[l - 1][cur].p, wih_planes(e, l), e->bih[l].p, e->gil[l].p, 3L * H, Ba * T, 3 * H, H, 0, st, ("gru_ih" + std::to_string(l)).c_str()))) return rc; }
         else if ((rc = launch_gemm(e, e->seqr[l - 1][cur].p, H, e->wih[l].p, H, e->bih[l].p, e->gil[l].p, 3L * H, B * T, 3 * H, H, 0, st,
                                    ("gru_ih" + std::to_string(l)).c_str(), e->wih_x[l].p))) return rc;
     }
@@ -707,7 +777,7 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
                       e->hbuf[l][hc ^ 1].p, seq + (long)t * H, (long)T * H, Ba, H};
         if (e->gemm_p) {
             g.seqp = reinterpret_cast<__bf16 *>(e->seqP[l][cur].p) + (long)t * H;
-            g.seqp_ld = (long)T * H; g.seqp_plane = (long)B * T * H; g.seqp_pl = operand_planes(e->precision);
+            g.seqp_ld = (long)T * H; g.seqp_plane = (long)B * T * H; set_seqp_format(e, g);
         }
         if (split) {
             ProfScope ps(e, "k_gru_step_split", "gru_step", 2.0 * B * 3 * H * H, st);
@@ -744,7 +814,7 @@ int stage_gru_round(se_engine *e, const int *slots, hipStream_t st) {
         if (l > 0) {
             gi[l] = e->gil[l].p;
             if (e->dbg_skip & 2) {}
-            else if (e->gemm_p) { if ((rc = launch_gemm_p(e, e->seqP[l - 1][slots[l]].p, e->wih_x[l].p, e->bih[l].p, e->gil[l].p, 3L * H, e->bact_slot[slots[l]] * T, 3 * H, H, 0, st, ("gru_ih" + std::to_string(l)).c_str()))) return rc; }
+            else if (e->gemm_p) { if ((rc = launch_gemm_p(e, e->seqP[l - 1][slots[l]].p, wih_planes(e, l), e->bih[l].p, e->gil[l].p, 3L * H, e->bact_slot[slots[l]] * T, 3 * H, H, 0, st, ("gru_ih" + std::to_string(l)).c_str()))) return rc; }
             else if ((rc = launch_gemm(e, e->seqr[l - 1][slots[l]].p, H, e->wih[l].p, H, e->bih[l].p, e->gil[l].p, 3L * H, B * T, 3 * H, H, 0, st,
                                        ("gru_ih" + std::to_string(l)).c_str(), e->wih_x[l].p))) return rc;
         }
@@ -766,7 +836,7 @@ int stage_gru_round(se_engine *e, const int *slots, hipStream_t st) {
                              e->hbuf[l][hc ^ 1].p, e->seqr[l][slots[l]].p + (long)t * H, (long)T * H, e->bact_slot[slots[l]], H};
             if (e->gemm_p) {
                 ga.seqp = reinterpret_cast<__bf16 *>(e->seqP[l][slots[l]].p) + (long)t * H;
-                ga.seqp_ld = (long)T * H; ga.seqp_plane = (long)B * T * H; ga.seqp_pl = operand_planes(e->precision);
+                ga.seqp_ld = (long)T * H; ga.seqp_plane = (long)B * T * H; set_seqp_format(e, ga);
             }
             e->hcur[l] = hc ^ 1;
             if (split) ms.a[z - 1] = GruSplitArgs{ga, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? ga.seqp - H : nullptr};
@@ -876,7 +946,7 @@ int ensure_ready(se_engine *e) {
         if ((rc = prepare_weights_p(e))) return rc;
         // capability only: whether THIS batch takes the plane GEMMs is select_gemm_route()'s decision (a batch on the skinny route
         // never allocated gruinP / seqP, so a weight reload must not switch the plane route back on behind its back)
-        e->gemm_p_cap = e->gemm_p_env && e->D % 32 == 0 && e->H % 32 == 0 && e->Ch[e->L] % 8 == 0;
+        e->gemm_p_cap = gemm_p_capable(e);
         select_gemm_route(e);
         if (e->gemm_p_cap) {  // W_ih0 with its K axis in the engine's feature order k' = (o * F + f) * 8 + c  (reference d = (8 o + c) * F + f)
             const int Fl = e->F[e->L], D = e->D, H = e->H;
@@ -887,7 +957,7 @@ int ensure_ready(se_engine *e) {
                     const int cabs = d / Fl, f = d - cabs * Fl;
                     wp[(size_t)r * D + ((size_t)(cabs >> 3) * Fl + f) * 8 + (cabs & 7)] = w[(size_t)r * D + d];
                 }
-            if ((rc = upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
+            if ((rc = e->pair_on ? upload_planes_pair(e, e->wih_xp, wp) : upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
             // fc_output_layer rows, its bias and the affine of the norm behind it in the same order (each dot product is unchanged;
             // only where it lands changes), channels padded to whole octets with zero rows.  (gemm_p_cap above asks for whole
             // octets, so today ND == D and no padding row exists; the padding is what a relaxed cap would need, and is untested)
@@ -901,7 +971,7 @@ int ensure_ready(se_engine *e) {
                 std::copy(fw.begin() + (size_t)d * H, fw.begin() + (size_t)(d + 1) * H, fwp.begin() + dp * H);
                 fbp[dp] = fb[d]; nwp[dp] = nw[d]; nbp[dp] = nb[d];
             }
-            if ((rc = upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
+            if ((rc = e->pair_on ? upload_planes_pair(e, e->fcw_xp, fwp) : upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
                 (rc = dev_upload(e, e->gnb_p, nbp)))
                 return rc;
         }
@@ -1037,6 +1107,7 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (e->T <= 2 * (1 << (L - 1))) return bail(SE_ERR_ARG, "segment shorter than the largest dilation history (CRN.py:333)");
     if (const char *s = getenv("SE_GRU_DIRECT")) e->gru_direct = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_GRU_SPLIT")) e->gru_split = atoi(s) != 0 ? 1 : 0;
+    if (const char *s = getenv("SE_F16_PAIR")) e->f16_pair = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
     if (const char *s = getenv("SE_DBG_SKIP")) { e->dbg_skip = atoi(s); fprintf(stderr, "se_engine: SE_DBG_SKIP=%d - stages are skipped, results are WRONG (timing experiment)\n", e->dbg_skip); }
@@ -1060,6 +1131,8 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 1536 * 1 * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 1536 * 2 * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 1536 * 3 * 16);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              2 * (1024 * kPairPlanesA + 512 * kPairPlanesW) * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 512);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 128);
     *out = e;
@@ -1092,7 +1165,7 @@ void se_destroy(se_engine *e) {
         for (hipStream_t q : e->stage_stream) (void)hipStreamDestroy(q);
     }
     for (int i = 0; i < 4; i++) {
-        dev_free(e->wih[i]); dev_free(e->whh[i]); dev_free(e->whh_p[i]); dev_free(e->bih[i]); dev_free(e->bhh[i]); dev_free(e->wih_x[i]);
+        dev_free(e->wih[i]); dev_free(e->whh[i]); dev_free(e->whh_p[i]); dev_free(e->bih[i]); dev_free(e->bhh[i]); dev_free(e->wih_x[i]); dev_free(e->wih_h[i]);
         dev_free(e->hbuf[i][0]); dev_free(e->hbuf[i][1]); dev_free(e->gil[i]);
     }
     for (int i = 0; i < SE_MAX_LEVELS; i++) {
@@ -1185,6 +1258,8 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
     for (int l = 1; l < e->NL; l++)
         if ((rc = dev_alloc(e, e->gil[l], (size_t)B * T * 3 * H))) return rc;
     if (e->gemm_p) {
+        // (sized for the bf16 planes also when the fp16 pair is on: a later weight load may fail the range guard and switch the
+        //  format back without a re-plan of the batch; strides and buffer ranges follow buffer_planes() at every launch)
         const size_t PLn = operand_planes(e->precision);
         for (int r = 0; r < kRing; r++) {
             if ((rc = dev_alloc(e, e->gruinP[r], (PLn * B * T * D + 1) / 2))) return rc;
@@ -1538,7 +1613,8 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         }
         if (sscanf(name, "enc%d", &idx) != 1 || idx != L - 1) return fail(e, SE_ERR_KEY, "unknown tap %s", name);
         // the GRU input: GEMM A planes [PL][B*T][(o*F+f)*8+c] (k_gemm_p) or fp32 rows [B][T][C*F]
-        const int Cl = e->Ch[L], Fl = e->F[L], PLn = operand_planes(e->precision), D = e->D;
+        const int Cl = e->Ch[L], Fl = e->F[L], PLn = buffer_planes(e->precision, e->pair_on, PlaneBuf::kGemmA), D = e->D;
+        const bool pair = buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA) == PlaneFmt::kF16Pair;
         const size_t n = (size_t)B * Cl * T * Fl;
         if (count) *count = (int64_t)n;
         if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
@@ -1559,10 +1635,13 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
                 for (int t = 0; t < T; t++)
                     for (int f = 0; f < Fl; f++) {
                         float v = 0;
+                        uint16_t up[3] = {0, 0, 0};
                         for (int pl = 0; pl < PLn; pl++) {
                             const uint16_t u = h[((size_t)pl * B * T + (size_t)b * T + t) * D + ((size_t)(c >> 3) * Fl + f) * 8 + (c & 7)];
+                            up[pl] = u;
                             if (PLn == 1) { _Float16 hv; memcpy(&hv, &u, 2); v += (float)hv; } else v += bf16_to_f32(u);
                         }
+                        if (pair) v = join2h(up[0], up[1]);
                         host_out[(((size_t)b * Cl + c) * Fl + f) * T + t] = v;
                     }
         return SE_OK;
