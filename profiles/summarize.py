@@ -25,6 +25,12 @@ def base_name(k):
     return k.split("::")[-1]
 
 
+# bench.py looks a kernel up by the engine's profile record (ProfScope), which files every fp32-MFMA GRU step kernel under "k_gru_step";
+# the counter passes see the instance names.  Their rows are summed under that name as well (launch-weighted), so that the lookup of
+# the step finds them whichever instance the serial route ran.
+PROFILE_NAME = {"k_gru_step2": "k_gru_step", "k_gru_step_multi": "k_gru_step", "k_gru_step_multi8": "k_gru_step"}
+
+
 def hbm_json(src, workload, note, out):
     import json
     import os
@@ -34,9 +40,11 @@ def hbm_json(src, workload, note, out):
     for r in csv.DictReader(open(src)):
         if r["counter"] not in ("FETCH_SIZE", "WRITE_SIZE"):
             continue
-        a = acc.setdefault(base_name(r["kernel"]), {"FETCH_SIZE": [0.0, 0], "WRITE_SIZE": [0.0, 0]})
-        a[r["counter"]][0] += float(r["sum_KB"])
-        a[r["counter"]][1] += int(r["launches"])
+        name = base_name(r["kernel"])
+        for key in {name, PROFILE_NAME.get(name, name)}:
+            a = acc.setdefault(key, {"FETCH_SIZE": [0.0, 0], "WRITE_SIZE": [0.0, 0]})
+            a[r["counter"]][0] += float(r["sum_KB"])
+            a[r["counter"]][1] += int(r["launches"])
     kernels = {k: {"fetch_kb": v["FETCH_SIZE"][0] / max(v["FETCH_SIZE"][1], 1), "write_kb": v["WRITE_SIZE"][0] / max(v["WRITE_SIZE"][1], 1),
                    "launches": v["FETCH_SIZE"][1]} for k, v in acc.items() if k.startswith("k_")}
     json.dump({"src_sha": kernel_source_sha(), "workload": workload, "source": note, "kernels": kernels}, open(out, "w"), indent=1)

@@ -57,6 +57,13 @@ __device__ __forceinline__ void split_store8(const float (&v)[8], uint4 *dst, lo
     }
 }
 
+// the planes of 8 channels in the format of the destination buffer (kF16Pair: two fp16 planes, PL is the bf16 route's count and not used)
+template <int PL, PlaneFmt FMT>
+__device__ __forceinline__ void split_store8_fmt(const float (&v)[8], uint4 *dst, long plane_stride) {
+    if constexpr (FMT == PlaneFmt::kF16Pair) split_store8_pair(v, dst, plane_stride);
+    else split_store8<PL>(v, dst, plane_stride);
+}
+
 __device__ __forceinline__ void convp_stats_store(float *stats, int nslot, int slot0, float s, float q, float *red /*[8]*/, int b) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); q += __shfl_down(q, off, 64); }
@@ -84,13 +91,22 @@ __device__ __forceinline__ void convp_stats_store(float *stats, int nslot, int s
 // oo2 / valid_m2 / stats_slot02 describe the second one).  Both parities read the same staged patch: every chunk is staged once
 // and feeds the NTAP-tap K loop into acc and the NTAP2-tap K loop into acc2; each parity then has its own R epilogue.  The
 // second accumulator set doubles the accumulator registers, so occupancy follows 2 NT.
-template <int NTAP, int NT, int CO, int PL, int NTAP2 = 0>
+//
+// FMT = kF16Pair (split_f16pair.h; PL = 3 weight planes): the input patch - and a P-layout output - are the two fp16 planes (hi, lo 2^11)
+// of their buffers, the weight image keeps its shape with the contents (2^11 w_hi, w_lo, w_hi), and a fragment is three
+// v_mfma_f32_32x32x16_f16 into the one accumulator set, in this fixed order: W0 b_hi, W1 b_hi, W2 b_lo.  The accumulators hold
+// 2^11 (w x) and are scaled by 2^-11 (exact) ahead of bias, activation and statistics.  Built for the instances the CRN path runs
+// (R, P and blend outputs); the gate / pre-conv epilogues of CRN_ELU and the student have no pair form.
+template <int NTAP, int NT, int CO, int PL, int NTAP2 = 0, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
+    constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
+    static_assert(!PAIR || PL == kPairPlanesW, "the fp16 pair form has three weight planes");
+    constexpr int APL = PAIR ? kPairPlanesA : PL;  // planes of the activation buffers (input patch, P-layout output)
 #ifdef SE_CP_TRACE
     unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast) :: "memory");
 #endif
-    // LDS patch [PL][CO][Npos] of 16-byte pieces (plane-major: consecutive LDS-DMA lanes copy consecutive 16-byte pieces of one
+    // LDS patch [APL][CO][Npos] of 16-byte pieces (plane-major: consecutive LDS-DMA lanes copy consecutive 16-byte pieces of one
     // plane row, i.e. whole cache lines; an interleaved [pos][plane] image made every wave instruction touch three scattered
     // runs and staged at 9 GB/s per CU)
     extern __shared__ __align__(16) uint4 planes[];
@@ -155,7 +171,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
     }
 
     // ---- LDS-DMA plan: item it = tid + 256 k = (plane, octet-in-chunk, patch position), LDS slot = it ----
-    const int items = PL * CO * Npos;
+    const int items = APL * CO * Npos;
     const int NI = (items + 255) >> 8;
     unsigned voff[kPNiMax];  // byte offset of chunk 0's source piece, or kPOob for the zero halo
     {
@@ -167,12 +183,12 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
         // per workgroup arriving when every workgroup of the launch starts at once (..._after.txt).)
         const int NGp = a.grouped ? a.ngroup : 1, RTp = a.grouped ? RT : R;
         const float invR = 1.0f / (float)R, invSt = 1.0f / (float)St, invRTp = 1.0f / (float)RTp;
-        const long sb = (long)b * a.C8 * PL * a.T * a.Fi;
+        const long sb = (long)b * a.C8 * APL * a.T * a.Fi;
         const unsigned base_cur = (unsigned)((a.cur_off + sb) * 16), base_prev = (unsigned)((a.prev_off + sb) * 16);
         const bool has_prev = a.prev_off >= 0;
         const int d_r = (int)((256.0f + 0.5f) * invSt), d_slot = 256 - d_r * St;  // uniform
         int rr = (int)(((float)tid + 0.5f) * invSt), slot = tid - rr * St;
-        const int rows = PL * CO * R;
+        const int rows = APL * CO * R;
 #pragma unroll
         for (int k = 0; k < kPNiMax; k++) {
             voff[k] = kPOob;
@@ -187,7 +203,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
                     const bool hist = ts < 0;
                     const bool ok = fi >= 0 && fi < a.Fi && (hist ? (has_prev && ts + a.T >= 0) : ts < a.T);
                     if (ok) {
-                        const unsigned row = __umul24((unsigned)(oc * PL + pl), (unsigned)a.T) + (unsigned)(hist ? ts + a.T : ts);
+                        const unsigned row = __umul24((unsigned)(oc * APL + pl), (unsigned)a.T) + (unsigned)(hist ? ts + a.T : ts);
                         voff[k] = (hist ? base_prev : base_cur) + ((__umul24(row, (unsigned)a.Fi) + (unsigned)fi) << 4);
                     }
                 }
@@ -196,7 +212,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
             }
         }
     }
-    const unsigned chunk_bytes = (unsigned)((long)CO * PL * a.T * a.Fi * 16);
+    const unsigned chunk_bytes = (unsigned)((long)CO * APL * a.T * a.Fi * 16);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(a.xbase), 0, a.xbytes, 0x00020000);
     auto stage = [&](int ch) {
         const unsigned add = (unsigned)ch * chunk_bytes;
@@ -216,15 +232,15 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
 
     const char *ldsb = reinterpret_cast<const char *>(planes);
     const int plane_bytes = CO * Npos * 16;
-    // One B fragment = the PL planes of 8 channels at one patch position.  The address is made opaque right before its reads:
+    // One B fragment = the APL planes of 8 channels at one patch position.  The address is made opaque right before its reads:
     // otherwise the compiler hoists all NPAIR x NT x PL fragment addresses out of the chunk loop (hundreds of registers parked
     // in AGPRs and read back one by one) - one v_add per fragment is free next to six MFMAs.
     // (par = 1: the second tap list of a pair instance)
-    auto read_b = [&](int i, int par, int pr, uint4 (&bf)[PL]) {
+    auto read_b = [&](int i, int par, int pr, uint4 (&bf)[APL]) {
         int off = lane_base[i] + (par ? toffL2[pr] : toffL[pr]);
         asm volatile("" : "+v"(off));
 #pragma unroll
-        for (int p = 0; p < PL; p++) bf[p] = *reinterpret_cast<const uint4 *>(ldsb + off + p * plane_bytes);
+        for (int p = 0; p < APL; p++) bf[p] = *reinterpret_cast<const uint4 *>(ldsb + off + p * plane_bytes);
     };
     CPT(0);  // prologue: tile geometry + LDS-DMA plan
     for (int ch = 0; ch < a.nchunk; ch++) {
@@ -250,7 +266,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
 #pragma unroll
                 for (int p = 0; p < PL; p++) fa_n[p] = fa_n2[p];
             }
-            uint4 bcur[PL], bnxt[PL];
+            uint4 bcur[APL], bnxt[APL];
             read_b(0, par, 0, bcur);
 #pragma unroll
             for (int pr = 0; pr < np; pr++) {
@@ -269,7 +285,13 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
                     else if (pr + 1 < np) read_b(0, par, pr + 1, bnxt);
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16 c = par ? acc2[i] : acc[i];
-                    if (PL >= 2) {
+                    if constexpr (PAIR) {
+                        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+                        const h8 bh = __builtin_bit_cast(h8, bcur[0]), bl = __builtin_bit_cast(h8, bcur[APL > 1 ? 1 : 0]);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[0]), bh, c, 0, 0, 0);               // 2^11 w_hi * x_hi
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[PL > 1 ? 1 : 0]), bh, c, 0, 0, 0);  // w_lo * x_hi
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[PL > 2 ? 2 : 0]), bl, c, 0, 0, 0);  // w_hi * x_lo
+                    } else if (PL >= 2) {
                         const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[0]), a1 = __builtin_bit_cast(bf16x8, fa[PL > 1 ? 1 : 0]),
                                      a2 = __builtin_bit_cast(bf16x8, fa[PL > 2 ? 2 : 0]);
                         const bf16x8 b0 = __builtin_bit_cast(bf16x8, bcur[0]), b1 = __builtin_bit_cast(bf16x8, bcur[PL > 1 ? 1 : 0]);
@@ -290,7 +312,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
                     else acc[i] = c;
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int p = 0; p < PL; p++) bcur[p] = bnxt[p];
+                    for (int p = 0; p < APL; p++) bcur[p] = bnxt[p];
                 }
             }
         }
@@ -310,6 +332,15 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
     } trace_out{tr, tlast, a.trace, tid};
 #endif
 
+    if constexpr (PAIR) {  // the accumulators hold 2^11 (w x): the exact 2^-11 ahead of bias, activation and statistics
+#pragma unroll
+        for (int i = 0; i < NT; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                acc[i][r] *= kPairInvScale;
+                if constexpr (NTAP2 > 0) acc2[i][r] *= kPairInvScale;
+            }
+    }
     // ---- epilogue: lane = position (column of the 32x32 tiles), registers = GEMM rows (r & 3) + 8 (r >> 2) + 4 half ----
     float bv[16];
 #pragma unroll
@@ -327,7 +358,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
             cnw[q] = a.bl_nw[c]; cnb[q] = a.bl_nb[c]; cmw[q] = a.bl_mnw[c]; cmb[q] = a.bl_mnb[c];
         }
         const float *ydb = a.bl_ydec + (long)b * a.bl_stream + (long)(c0 >> 3) * a.T * a.bl_oT * 8;
-        uint4 *ypb = a.yp + (long)b * a.yp_stream + (long)(c0 >> 3) * PL * a.T * a.Fy;
+        uint4 *ypb = a.yp + (long)b * a.yp_stream + (long)(c0 >> 3) * APL * a.T * a.Fy;
         const long plane_stride = (long)a.T * a.Fy;
 #pragma unroll
         for (int i = 0; i < NT; i++) {
@@ -351,7 +382,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
                 const float g = 1.0f / (1.0f + expf(-un));
                 o[q] = (c0 + q < a.Cy) ? g * v + (1.0f - g) * yn : 0.0f;
             }
-            split_store8<PL>(o, ypb + (long)t * a.Fy + f, plane_stride);
+            split_store8_fmt<PL, FMT>(o, ypb + (long)t * a.Fy + f, plane_stride);
         }
         return;
     }
@@ -376,12 +407,12 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
                     if (row >= a.relu_lo && row < a.relu_hi) v = convp_act(v, a.act);
                     o[q] = row < a.Cy ? v : 0.0f;
                 }
-                split_store8<PL>(o, a.yp + (long)b * a.yp_stream + (long)oct * PL * plane_stride + (long)t * a.Fy + a.oo + m, plane_stride);
+                split_store8_fmt<PL, FMT>(o, a.yp + (long)b * a.yp_stream + (long)oct * APL * plane_stride + (long)t * a.Fy + a.oo + m, plane_stride);
             }
         }
         return;
     }
-    if (a.out_mode == kPOutPre) {
+    if (!PAIR && a.out_mode == kPOutPre) {
         // <= 8 channels: GEMM rows 0-3 / 8-11 are channels 0-7, i.e. registers 0-7 of lane half 0 (half 1 holds padding rows)
         float *yb = a.y + (long)b * a.y_stream;
         const int C = a.Cy;
@@ -415,7 +446,7 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
         if (a.stats) convp_stats_store(a.stats, a.stats_nslot, a.stats_slot0, ssum, ssq, reinterpret_cast<float *>(planes), b);
         return;
     }
-    if (a.out_mode == kPOutGate) {
+    if (!PAIR && a.out_mode == kPOutGate) {
         // rows are permuted like the blend epilogue: register pair (2q, 2q+1) of lane half h = (conv_trans, conv_gated) of
         // channel gate_c0 + mt*16 + h*8 + q; the product goes to the R layout with its statistics for the block's gLN
         const int c0 = mt * 16 + half * 8;
@@ -571,8 +602,8 @@ __global__ __launch_bounds__(256) void k_gln_p(GlnPArgs a) {
 // The FC weight rows are permuted at load time so that output column (o * F + f) * 8 + c holds reference feature (8 o + c) * F + f:
 // x [b*T + t][o][f][8] is the R-layout shape and a thread's 8 channels are 32 contiguous bytes.  The affine is per ELEMENT
 // (w, b in the same column order), which is the one difference from k_gln_p.
-
-template <int PL>
+// FMT = kF16Pair (here and in k_gln2_stream_p): decinP as the fp16 pair; PL is then its two planes, as in k_gln_p.
+template <int PL, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(256) void k_gln2_p(Gln2PArgs a) {
     __shared__ float sm[2];
     const int b = blockIdx.z, o = blockIdx.y;
@@ -592,14 +623,14 @@ __global__ __launch_bounds__(256) void k_gln2_p(Gln2PArgs a) {
         const float bs[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
         for (int c = 0; c < 8; c++) v[c] = (v[c] - mean) * inv * w[c] + bs[c];  // padded channels: zero column, zero affine
-        split_store8<PL>(v, a.y + (long)b * a.y_stream + (long)o * PL * TF + i, TF);
+        split_store8_fmt<PL, FMT>(v, a.y + (long)b * a.y_stream + (long)o * PL * TF + i, TF);
     }
 }
 
 // The same norm on the fp32 GEMM route (few GEMM rows: skinny / k_gemm_x kernels, no epilogue statistics): exact two-pass
 // statistics in the kernel, one workgroup per stream.  x [b][T][D] fp32, d = c * F + f (the reference's feature order)
 
-template <int PL>
+template <int PL, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(1024) void k_gln2_stream_p(Gln2PArgs a) {
     __shared__ double red[16];
     const int b = blockIdx.x;
@@ -618,7 +649,7 @@ __global__ __launch_bounds__(1024) void k_gln2_stream_p(Gln2PArgs a) {
             const int d = min(ch, a.C - 1) * a.F + f;
             v[c] = ch < a.C ? (x[(long)t * D + d] - mean) * inv * a.w[d] + a.b[d] : 0.0f;
         }
-        split_store8<PL>(v, a.y + (long)b * a.y_stream + (long)o * PL * TF + (long)t * a.F + f, TF);
+        split_store8_fmt<PL, FMT>(v, a.y + (long)b * a.y_stream + (long)o * PL * TF + (long)t * a.F + f, TF);
     }
 }
 

@@ -2,13 +2,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "conv_args.h"
+#include "conv_weight_image.h"
 
 namespace se {
 
 constexpr int kPNiMax = 20;   // LDS-DMA instructions per thread per chunk: PL * CO * Npos <= 256 * kPNiMax (host-checked)
 constexpr unsigned kPOob = 0xFFFFFFF0u;  // buffer offset beyond every ring: the bounds check returns zeros
 
-enum ConvPOut : int { kPOutR = 0, kPOutP = 1, kPOutBlend = 2, kPOutStats = 3, kPOutGate = 4, kPOutPre = 5 };
+// (enum ConvPOut: conv_weight_image.h, with the weight images that depend on it)
 
 struct ConvPArgs {
     // ---- input: P layout, one allocation holding every ring slot ----
@@ -121,7 +122,7 @@ struct MaskPArgs {
 };
 
 struct SkipPArgs {
-    const uint4 *x;       // res: P layout [b][C8][PL][T*F] of this ring slot
+    const uint4 *x;       // res: P layout [b][C8][planes][T*F] of this ring slot (planes: those of the buffer's format)
     long x_stream;        // uint4 per stream
     int C, C8, TF;        // channels (Cin = Cout = C), octets, positions per stream (T * Fr)
     int T, Fr;

@@ -25,6 +25,7 @@ struct ConvPPlan {
     int ngeo = 0, ngpair = 0;  // gpair: tilings of the k_conv_p<.., NTAP2> instances (a.ntap2 > 0: a second tap list, the odd parity of a
                                // transposed convolution, on the same patch)
     int npair = 0, terms = 6, npair2 = 0;
+    PlaneFmt fmt = PlaneFmt::kBf16;  // format of the INPUT planes (and of a P-layout output): which k_conv_p form the launch takes
     double flops_pair = 0;
     std::string name;  // launch-site label ("enc3", "skip0", ...): SE_CONVP_NT_<name>=n forces a tiling for experiments
 };
@@ -42,17 +43,19 @@ struct PLevel {
     ConvPPlan enc, dec_even, dec_odd, skip, skipm;
     ConvPPlan gate[2];  // CRN_ELU / student: conv_trans * sigmoid(conv_gated) after the encoder convolution, <= 64 channels per launch
     SkipPPlan sk;
+    PlaneFmt sk_fmt = PlaneFmt::kBf16;  // format of res and of the gated output (k_skip_p)
     bool dec_merged = false;
     bool dec_pair_on = false;  // this batch: both parities in one launch of dec_even (a.ntap2 > 0), dec_odd not launched
 };
 
-// GEMM row -> logical row of the caller's weight selector, for the epilogue's register ownership (conv_p.hip.h)
-inline int convp_row_logical(int mode, int row) {
-    const int mt = row >> 5, rp = row & 31, h = (rp >> 2) & 1, r = (rp & 3) + 4 * (rp >> 3);
-    if (mode == kPOutPre) return (mt == 0 && h == 0 && r < 8) ? r : (1 << 20);  // channels 0-7 = registers 0-7 of lane half 0
-    if (mode == kPOutP) return mt * 32 + 16 * h + r;                       // registers 0..15 of half h = channels 16 h + r
-    if (mode == kPOutBlend || mode == kPOutGate) return 2 * (mt * 16 + 8 * h + (r >> 1)) + (r & 1);  // pairs (residualmask, residual) / (trans, gated) of channel 8 h + r/2
-    return row;
+// the planes of one weight in the format of the launch that reads it (conv_weight_image.h: `parts`): the fp16 pair's
+// (2^11 w_hi, w_lo, w_hi), one fp16 number, or (hi, mid, lo) bf16
+inline void weight_parts(float x, int PL, PlaneFmt fmt, uint16_t (&p)[3]) {
+    if (fmt == PlaneFmt::kF16Pair) { pair_weight_planes(x, p); return; }
+    const uint16_t h = bf16_rne(x);
+    const float r1 = x - bf16_to_f32(h);
+    const uint16_t md = bf16_rne(r1);
+    p[0] = PL == 1 ? f16_rne(x) : h; p[1] = md; p[2] = bf16_rne(r1 - bf16_to_f32(md));
 }
 
 }  // namespace
@@ -72,6 +75,7 @@ struct se_convp_state {
     DevBuf decinP[kRing];         // decoder input, P layout
     DevBuf decR[SE_MAX_LEVELS];   // [B][Co8][T*2Fi][8] parity-planar
     DevBuf decP[SE_MAX_LEVELS];   // blended decoder level outputs, P layout
+    PlaneFmt ring_fmt = PlaneFmt::kBf16;  // format of what xinP[i >= 1] holds (alloc_state_p, convert_history_p)
     bool ready = false;
 };
 
@@ -80,10 +84,12 @@ namespace {
 template <class WSel>
 int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int s, int colpad, int tlo_off, int ngroup, int dil, int St,
                 const std::vector<std::array<int, 4>> &taps, WSel wsel, const std::vector<float> &bias_logical, int relu_lo, int relu_hi,
-                int act, int out_mode) {
+                int act, int out_mode, PlaneFmt fmt = PlaneFmt::kBf16) {
     pl.active = FP > 0;
+    pl.fmt = fmt;
     if (!pl.active) return 0;
-    const int T = e->T, ntap = (int)taps.size(), PL = operand_planes(e->precision);
+    // PL: weight planes (three in both formats at precision 0); APL: planes of the patch this launch stages
+    const int T = e->T, ntap = (int)taps.size(), PL = operand_planes(e->precision), APL = fmt == PlaneFmt::kF16Pair ? kPairPlanesA : PL;
     const int P = T * FP, tiles = (P + 31) / 32;
     const int CoPad = (Co + 31) / 32 * 32;
     if (CoPad > 128 || CoPad == 96) return fail(e, SE_ERR_ARG, "conv with %d GEMM rows is not supported", Co);
@@ -106,7 +112,7 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
         if (rows_pos > T) rows_pos = T;
         const int grouped = ngroup * rows_pos < rows_pos + (ngroup - 1) * dil;
         const int Rmax = grouped ? ngroup * rows_pos : rows_pos + (ngroup - 1) * dil;
-        const long items = (long)PL * CO * Rmax * St;
+        const long items = (long)APL * CO * Rmax * St;
         if (items > 256L * kPNiMax) continue;
         // whole LDS-DMA instructions: the last one may write zero pieces past `items`, so the allocation covers NI * 256 pieces
         const size_t lds = (size_t)((items + 255) / 256) * 4096;
@@ -130,34 +136,15 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
     a.out_mode = out_mode; a.row_perm = out_mode == kPOutP || out_mode == kPOutBlend || out_mode == kPOutGate;
     a.valid_m = FP; a.par_rows = 0; a.stats = nullptr;
     pl.npair2 = a.ntap2 ? (a.ntap2 * CO + 1) / 2 : 0;
-    pl.CO = CO; pl.npair = npair; pl.terms = PL == 3 ? 6 : (PL == 2 ? 3 : 1);
-    // weights [chunk][pair][plane][mtile][row 32][k 16]: k = half*8 + c <-> entry 2*pair + half = (tap, octet) tap-major
-    std::vector<uint16_t> wx((size_t)nchunk * npair * PL * MT * 32 * 16, 0);
+    pl.CO = CO; pl.npair = npair; pl.terms = fmt == PlaneFmt::kF16Pair ? 3 : (PL == 3 ? 6 : (PL == 2 ? 3 : 1));
+    // weights [chunk][pair][plane][mtile][row 32][k 16] (conv_weight_image.h), the planes of a weight in the launch's format
+    const std::vector<uint16_t> wx = convp_weight_image(out_mode, CO, nchunk, Ci, Co, CoPad, PL, taps, wsel,
+                                                        [=](float x, uint16_t (&p)[3]) { weight_parts(x, PL, fmt, p); });
     std::vector<float> bias(CoPad, 0.0f);
     for (int row = 0; row < CoPad; row++) {
         const int lg = convp_row_logical(out_mode, row);
         if (lg < Co) bias[row] = bias_logical[lg];
     }
-    for (int ch = 0; ch < nchunk; ch++)
-        for (int st = 0; st < npair; st++)
-            for (int m = 0; m < MT; m++)
-                for (int r = 0; r < 32; r++) {
-                    const int lg = convp_row_logical(out_mode, m * 32 + r);
-                    if (lg >= Co) continue;
-                    for (int k = 0; k < 16; k++) {
-                        const int en = 2 * st + k / 8, tp = en / CO, oc = en % CO;
-                        const int ci = (ch * CO + oc) * 8 + k % 8;
-                        if (tp >= ntap || ci >= Ci) continue;
-                        const float x = wsel(ci, lg, taps[tp][0], taps[tp][1]);
-                        const uint16_t h = bf16_rne(x);
-                        const float r1 = x - bf16_to_f32(h);
-                        const uint16_t md = bf16_rne(r1);
-                        const float r2 = r1 - bf16_to_f32(md);
-                        const uint16_t parts[3] = {PL == 1 ? f16_rne(x) : h, md, bf16_rne(r2)};
-                        for (int pln = 0; pln < PL; pln++)
-                            wx[(((((size_t)ch * npair + st) * PL + pln) * MT + m) * 32 + r) * 16 + k] = parts[pln];
-                    }
-                }
     int rc = dev_alloc(e, pl.wx, (wx.size() + 1) / 2);
     if (rc) return rc;
     HIPCHECK(e, hipMemcpy(pl.wx.p, wx.data(), wx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -235,7 +222,7 @@ int launch_conv_p(se_engine *e, const ConvPPlan &pl, const ConvPArgs &a_in, hipS
 #ifdef SE_CP_TRACE
     a.trace = g_cp_trace_sites.get(label, pl.NT, pl.grid_x);
 #endif
-    if (conv_p_launch(a.ntap, a.ntap2, pl.NT, pl.CO, operand_planes(e->precision), dim3(pl.grid_x, e->Bact), pl.lds, st, a))
+    if (conv_p_launch(a.ntap, a.ntap2, pl.NT, pl.CO, operand_planes(e->precision), dim3(pl.grid_x, e->Bact), pl.lds, st, a, pl.fmt))
         return fail(e, SE_ERR_ARG, "no conv_p kernel instance for %d (+ %d) taps x %d tiles x %d octets", a.ntap, a.ntap2, pl.NT, pl.CO);
     HIPCHECK(e, hipGetLastError());
     return 0;
@@ -245,6 +232,10 @@ int launch_conv_p(se_engine *e, const ConvPPlan &pl, const ConvPArgs &a_in, hipS
 int dec_odd_slots(const PLevel &pv) { return pv.dec_pair_on ? pv.dec_even.grid_x : (pv.dec_odd.active ? pv.dec_odd.grid_x : 0); }
 
 uint4 *decin_p(se_engine *e, int slot) { return reinterpret_cast<uint4 *>(e->cp->decinP[slot].p); }
+
+// uint4 per stream of xinP[i] in its current format: the stream stride inside a ring slot (the slot itself, slot_elems, stays sized
+// for the bf16 planes: a later weight load may fail the range guard and switch the format back without a re-plan of the batch)
+long xin_stream_elems(const se_engine *e, int i) { return (long)((e->Ch[i] + 7) / 8) * act_planes(e, xin_kind(i)) * e->T * e->F[i]; }
 
 void select_all_p(se_engine *e) {
     for (int i = 0; i < e->L; i++) {
@@ -329,7 +320,7 @@ int prepare_weights_p(se_engine *e) {
         const float *wp = w->data();
         int rc = plan_conv_p(e, S.pv[i].enc, Ci, Co, Fo, Fi, 2, 2, -2 * d, 3, d, Fi + 4, taps,
                              [=](int ci, int co, int kf, int kt) { return wp[(((size_t)co * Ci + ci) * 5 + kf) * 3 + kt]; }, *b, 0, Co, e->act,
-                             e->variant ? kPOutP : kPOutR);
+                             e->variant ? kPOutP : kPOutR, act_format(e, xin_kind(i)));  // (level 0 reads the features: bf16 planes)
         if (rc) return rc;
         S.pv[i].enc.name = "enc" + std::to_string(i);
         ConvPArgs &a = S.pv[i].enc.a;
@@ -371,6 +362,7 @@ int prepare_weights_p(se_engine *e) {
         const float *wp = w->data();
         auto wsel = [=](int ci, int co, int kf, int kt) { return wp[(((size_t)ci * Co + co) * 5 + kf) * 3 + kt]; };
         PLevel &pv = S.pv[j];
+        const PlaneFmt cfmt = act_format(e, PlaneBuf::kConvAct);  // decinP / decP in, xinP[lvl] in and decP out on the skip path
         int rc;
         pv.dec_even.name = "dec" + std::to_string(j) + "_even"; pv.dec_odd.name = "dec" + std::to_string(j) + "_odd";
         pv.skip.name = "skip" + std::to_string(j); pv.skipm.name = "skipstat" + std::to_string(j);
@@ -384,7 +376,7 @@ int prepare_weights_p(se_engine *e) {
             for (int c = 0; c < Co; c++) bias2[2 * c] = bias2[2 * c + 1] = (*b)[c];
             rc = plan_conv_p(e, pv.dec_even, Ci, 2 * Co, Fi, Fi, 1, 1, 0, 3, d, Fi + 2, tu,
                              [=](int ci, int row, int kf, int kt) { return ((row & 1) == (kf & 1)) ? wsel(ci, row >> 1, kf, kt) : 0.0f; },
-                             bias2, 0, 2 * Co, e->act, kPOutR);
+                             bias2, 0, 2 * Co, e->act, kPOutR, cfmt);
             if (rc) return rc;
             ConvPArgs &a = pv.dec_even.a;
             a.par_rows = 1; a.oT = Fi; a.oo = 0; a.y_npos = T * Fi; a.y_stream = (long)T * Fi * 8;
@@ -404,8 +396,8 @@ int prepare_weights_p(se_engine *e) {
             // the model counts, and the pair launch measured 2 % slower (student, B = 1024, fp16).
             const bool pair = e->dec_pair && operand_planes(e->precision) >= 2;
             pv.dec_even.a.ntap2 = pair ? (int)to.size() : 0;  // before planning: plan_conv_p then also lists the pair tilings
-            if ((rc = plan_conv_p(e, pv.dec_even, Ci, Co, Fi, Fi, 1, 1, 0, 3, d, Fi + 2, te, wsel, *b, 0, Co, e->act, kPOutR))) return rc;
-            if ((rc = plan_conv_p(e, pv.dec_odd, Ci, Co, Fi - 1, Fi, 1, 1, 0, 3, d, Fi + 2, to, wsel, *b, 0, Co, e->act, kPOutR))) return rc;
+            if ((rc = plan_conv_p(e, pv.dec_even, Ci, Co, Fi, Fi, 1, 1, 0, 3, d, Fi + 2, te, wsel, *b, 0, Co, e->act, kPOutR, cfmt))) return rc;
+            if ((rc = plan_conv_p(e, pv.dec_odd, Ci, Co, Fi - 1, Fi, 1, 1, 0, 3, d, Fi + 2, to, wsel, *b, 0, Co, e->act, kPOutR, cfmt))) return rc;
             for (ConvPPlan *q : {&pv.dec_even, &pv.dec_odd}) {
                 ConvPArgs &a = q->a;
                 a.oT = 2 * Fi; a.oo = q == &pv.dec_odd ? Fi : 0; a.y_npos = T * 2 * Fi; a.y_stream = (long)((Co + 7) / 8) * T * 2 * Fi * 8;
@@ -435,9 +427,9 @@ int prepare_weights_p(se_engine *e) {
             for (int c = 0; c < Co; c++) { biasp[2 * c] = (*mb)[c]; biasp[2 * c + 1] = (*rb)[c]; }
             if ((rc = plan_conv_p(e, pv.skip, Co, 2 * Co, Fr, Fr, 1, 0, 0, 1, 0, Fr, t1,
                                   [=](int ci, int row, int, int) { const int c = row >> 1; return (row & 1) ? rwp[(size_t)c * Co + ci] : mwp[(size_t)c * Co + ci]; },
-                                  biasp, 0, 0, e->act, kPOutBlend))) return rc;
+                                  biasp, 0, 0, e->act, kPOutBlend, cfmt))) return rc;
             if ((rc = plan_conv_p(e, pv.skipm, Co, Co, Fr, Fr, 1, 0, 0, 1, 0, Fr, t1,
-                                  [=](int ci, int co, int, int) { return mwp[(size_t)co * Co + ci]; }, *mb, 0, 0, e->act, kPOutR))) return rc;
+                                  [=](int ci, int co, int, int) { return mwp[(size_t)co * Co + ci]; }, *mb, 0, 0, e->act, kPOutR, cfmt))) return rc;
             pv.skipm.a.stats_lo = 0; pv.skipm.a.stats_hi = Co; pv.skipm.a.oT = Fr; pv.skipm.a.oo = 0; pv.skipm.a.y_npos = T * Fr;
             pv.skip.a.Cy = Co; pv.skip.a.Fy = Fr; pv.skip.a.oo = 0;
             pv.skip.flops = 2.0 * 2 * Co * Co * Fr * T;
@@ -450,27 +442,11 @@ int prepare_weights_p(se_engine *e) {
                 if (!mnw || !mnb || !nw || !nb) return SE_ERR_PARAM_MISSING;
                 SkipPPlan &sk = pv.sk;
                 const int PL = operand_planes(e->precision), C8 = (Co + 7) / 8, MTh = (Co + 31) / 32, KP = (C8 + 1) / 2, Cp = MTh * 32;
+                const int APL = cfmt == PlaneFmt::kF16Pair ? kPairPlanesA : PL;  // planes of res and of the gated output
+                pv.sk_fmt = cfmt;
                 sk.active = MTh <= 2 && (KP == 1 || KP == 2 || KP == 4);
                 if (sk.active) {
-                    std::vector<uint16_t> wx((size_t)2 * MTh * KP * PL * 32 * 16, 0);
-                    for (int m2 = 0; m2 < 2 * MTh; m2++)
-                        for (int kp = 0; kp < KP; kp++)
-                            for (int r = 0; r < 32; r++) {
-                                const int mt = m2 % MTh, kind = m2 / MTh;
-                                const int ch = convp_row_logical(kPOutP, mt * 32 + r);
-                                if (ch >= Co) continue;
-                                for (int k = 0; k < 16; k++) {
-                                    const int ci = (2 * kp + k / 8) * 8 + k % 8;
-                                    if (ci >= Co) continue;
-                                    const float x = kind ? rwp[(size_t)ch * Co + ci] : mwp[(size_t)ch * Co + ci];
-                                    const uint16_t h = bf16_rne(x);
-                                    const float r1 = x - bf16_to_f32(h);
-                                    const uint16_t md = bf16_rne(r1);
-                                    const uint16_t parts[3] = {PL == 1 ? f16_rne(x) : h, md, bf16_rne(r1 - bf16_to_f32(md))};
-                                    for (int pln = 0; pln < PL; pln++)
-                                        wx[((((size_t)m2 * KP + kp) * PL + pln) * 32 + r) * 16 + k] = parts[pln];
-                                }
-                            }
+                    const std::vector<uint16_t> wx = skip_weight_image(Co, MTh, KP, PL, mwp, rwp, [=](float x, uint16_t (&p)[3]) { weight_parts(x, PL, cfmt, p); });
                     if ((rc = dev_alloc(e, sk.wx, (wx.size() + 1) / 2))) return rc;
                     HIPCHECK(e, hipMemcpy(sk.wx.p, wx.data(), wx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
                     std::vector<float> cst((size_t)6 * Cp, 0.0f);
@@ -482,7 +458,7 @@ int prepare_weights_p(se_engine *e) {
                     SkipPArgs &a = sk.a;
                     a.C = Co; a.C8 = C8; a.T = T; a.Fr = Fr; a.TF = T * Fr; a.MTh = MTh; a.KP = KP; a.act = e->act;
                     a.wx = reinterpret_cast<const uint4 *>(sk.wx.p); a.cst = sk.cst.p;
-                    a.x_stream = (long)C8 * PL * T * Fr; a.out_stream = a.x_stream;
+                    a.x_stream = (long)C8 * APL * T * Fr; a.out_stream = a.x_stream;
                     a.Fh = Fi; a.Fo = 2 * Fi - 1; a.y_stream = pv.dec_even.a.y_stream; a.eps_mode = e->eps_mode;
                     sk.KP = KP;
                     sk.lds = (size_t)2 * MTh * KP * PL * 64 * 16 + (size_t)6 * Cp * 4;
@@ -497,8 +473,32 @@ int prepare_weights_p(se_engine *e) {
     return 0;
 }
 
+// Statistics slabs of the norms (se_engine::enc_stats / dec_stats / skip_stats): one (sum, sum of squares) slot per workgroup of THIS
+// selection's grids.  The tiling - and with it grid_x - depends on the buffer format (patch bytes, MFMA terms), so a weight load that
+// flips the format of a running batch re-selects and must come back here: called from alloc_state_p and after every select_all_p of
+// ensure_ready.  Grows only; a slab is written and read within one segment, so a re-allocation between calls loses nothing.
+int alloc_stats_p(se_engine *e) {
+    se_convp_state &S = *e->cp;
+    const size_t B = (size_t)e->B;
+    int rc;
+    for (int i = 0; i < e->L; i++) {
+        PLevel &pv = S.pv[i];
+        if ((rc = dev_alloc(e, e->enc_stats[i], B * 2 * (pv.enc.grid_x + (pv.gate[0].active ? pv.gate[0].grid_x : 0) + (pv.gate[1].active ? pv.gate[1].grid_x : 0) + 1)))) return rc;
+        if ((rc = dev_alloc(e, e->dec_stats[i], B * 2 * (pv.dec_even.grid_x + dec_odd_slots(pv) + 1)))) return rc;
+        if ((rc = dev_alloc(e, e->skip_stats[i], B * 2 * ((pv.skipm.active ? pv.skipm.grid_x : 0) + 1)))) return rc;
+    }
+    return 0;
+}
+
+// every launch that writes or reads a slab with `nslot` slots per stream checks it against the allocation first
+int slab_fits(se_engine *e, const DevBuf &slab, int nslot, const char *what) {
+    if ((size_t)e->B * nslot * 2 <= slab.n) return 0;
+    return fail(e, SE_ERR_STATE, "statistics slab of %s holds %zu floats, this tiling needs %zu (batch %d x %d slots)", what, slab.n, (size_t)e->B * nslot * 2, e->B, nslot);
+}
+
 int alloc_state_p(se_engine *e, hipStream_t st) {
     se_convp_state &S = *e->cp;
+    S.ring_fmt = act_format(e, PlaneBuf::kConvAct);  // (the all-zero history is the same bits in both formats)
     const int L = e->L, T = e->T, B = e->B, PL = operand_planes(e->precision);
     int rc;
     for (int i = 0; i < L; i++) {
@@ -532,14 +532,7 @@ int alloc_state_p(se_engine *e, hipStream_t st) {
         HIPCHECK(e, hipMemsetAsync(S.decR[j].p, 0, nR * sizeof(float), st));
         if (lvl > 0 && (rc = dev_alloc(e, S.decP[j], (size_t)B * ((Co + 7) / 8) * PL * T * e->F[lvl] * 4))) return rc;
     }
-    // statistics slabs of the norms (se_engine::enc_stats / dec_stats / skip_stats): one slot per workgroup of this batch's grids
-    for (int i = 0; i < L; i++) {
-        PLevel &pv = S.pv[i];
-        if ((rc = dev_alloc(e, e->enc_stats[i], (size_t)B * 2 * (pv.enc.grid_x + (pv.gate[0].active ? pv.gate[0].grid_x : 0) + (pv.gate[1].active ? pv.gate[1].grid_x : 0) + 1)))) return rc;
-        if ((rc = dev_alloc(e, e->dec_stats[i], (size_t)B * 2 * (pv.dec_even.grid_x + dec_odd_slots(pv) + 1)))) return rc;
-        if ((rc = dev_alloc(e, e->skip_stats[i], (size_t)B * 2 * ((pv.skipm.active ? pv.skipm.grid_x : 0) + 1)))) return rc;
-    }
-    return 0;
+    return alloc_stats_p(e);
 }
 
 // The fused front end (io_fused.hip.h: k_stft_feat): STFT of the segment at `off` of every stream's microphones -> the feature octets in
@@ -582,6 +575,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
             a.prev_off = (long)prev * S.pslot_elems;
             a.y = S.preR.p;
             a.stats = e->pre_stats[i].p; a.stats_nslot = pl.grid_x; a.stats_slot0 = 0;
+            if ((rc = slab_fits(e, e->pre_stats[i], pl.grid_x, "a pre-conv block"))) return rc;
             if ((rc = launch_conv_p(e, pl, a, st, ("pre" + std::to_string(i)).c_str()))) return rc;
             ProfScope ps(e, "k_gln_p", "gln", 0, st);
             GlnPArgs g{};
@@ -619,6 +613,8 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
         a.cur_off = (long)cur * S.slot_elems[i];
         a.prev_off = (long)prev * S.slot_elems[i];
         int nslot = pl.grid_x;
+        if (e->variant) nslot = S.pv[i].gate[0].grid_x + (S.pv[i].gate[1].active ? S.pv[i].gate[1].grid_x : 0);
+        if ((rc = slab_fits(e, e->enc_stats[i], nslot, "an encoder level"))) return rc;
         if (!e->variant) {
             a.y = S.encR[i].p;
             a.stats = e->enc_stats[i].p; a.stats_nslot = pl.grid_x; a.stats_slot0 = 0;
@@ -648,8 +644,8 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
         if (i + 1 < L) {
             g.mode = 0;
             g.y = reinterpret_cast<uint4 *>(S.xinP[i + 1].p) + (long)cur * S.slot_elems[i + 1];
-            g.y_stream = (long)g.C8 * PL * T * Fo;
-            launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g);
+            g.y_stream = (long)g.C8 * act_planes(e, PlaneBuf::kConvAct) * T * Fo;
+            launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g, act_format(e, PlaneBuf::kConvAct));
         } else if (e->gemm_p) {  // last level = A operand of the GRU input projection, as split-bf16 planes (k_gemm_p)
             g.mode = 1;
             g.y = reinterpret_cast<uint4 *>(e->gruinP[cur].p);
@@ -673,15 +669,17 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
                     float *wav = nullptr, long wav_ld = 0) {
     se_convp_state &S = *e->cp;
     const int L = e->L, T = e->T, B = e->B, PL = operand_planes(e->precision);
+    const int APL = act_planes(e, PlaneBuf::kConvAct);  // planes of decinP, decP and of the skip path's xinP[lvl >= 1]
     const int Ba = e->Bact;  // launch batch: the prefix of streams that take part in this segment (se_realtime_process_ragged), B otherwise
     int rc;
     const uint4 *xin = reinterpret_cast<const uint4 *>(S.decinP[cur].p);
-    size_t xin_bytes = (size_t)B * ((e->Ch[L] + 7) / 8) * PL * T * e->F[L] * 16;
+    size_t xin_bytes = (size_t)B * ((e->Ch[L] + 7) / 8) * APL * T * e->F[L] * 16;
     for (int j = 0; j < L; j++) {
         const int lvl = L - 1 - j;
         const int Co = lvl == 0 ? 2 : e->Ch[lvl], Fi = e->F[lvl + 1], Fo = 2 * Fi - 1;
         PLevel &pv = S.pv[j];
         const int ne = pv.dec_even.grid_x, no = dec_odd_slots(pv);
+        if ((rc = slab_fits(e, e->dec_stats[j], ne + no, "a decoder level"))) return rc;
         for (ConvPPlan *q : {&pv.dec_even, &pv.dec_odd}) {
             if (!q->active || (q == &pv.dec_odd && pv.dec_pair_on)) continue;
             ConvPArgs a = q->a;
@@ -707,7 +705,7 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
                 a.sy = sy;
                 a.out = reinterpret_cast<uint4 *>(S.decP[j].p);
                 ProfScope ps(e, "k_skip_p", ("skip" + std::to_string(j)).c_str(), pv.sk.flops * B, st);
-                if (launch_k_skip_p(PL, pv.sk.KP, Ba, pv.sk.lds, st, a)) return fail(e, SE_ERR_ARG, "no k_skip_p instance for %d planes x %d K steps", PL, pv.sk.KP);
+                if (launch_k_skip_p(PL, pv.sk.KP, Ba, pv.sk.lds, st, a, pv.sk_fmt)) return fail(e, SE_ERR_ARG, "no k_skip_p instance for %d planes x %d K steps", PL, pv.sk.KP);
                 HIPCHECK(e, hipGetLastError());
             } else {
             {
@@ -715,13 +713,14 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
                 a.xbase = res; a.xbytes = res_bytes; a.cur_off = (long)cur * S.slot_elems[lvl]; a.prev_off = -1;
                 a.y = nullptr; a.out_mode = kPOutStats;
                 a.stats = e->skip_stats[j].p; a.stats_nslot = pv.skipm.grid_x; a.stats_slot0 = 0;
+                if ((rc = slab_fits(e, e->skip_stats[j], pv.skipm.grid_x, "a skip gate"))) return rc;
                 if ((rc = launch_conv_p(e, pv.skipm, a, st, ("skipstat" + std::to_string(j)).c_str()))) return rc;
             }
             {
                 ConvPArgs a = pv.skip.a;
                 a.xbase = res; a.xbytes = res_bytes; a.cur_off = (long)cur * S.slot_elems[lvl]; a.prev_off = -1;
                 a.yp = reinterpret_cast<uint4 *>(S.decP[j].p);
-                a.yp_stream = (long)((Co + 7) / 8) * PL * T * Fr;
+                a.yp_stream = (long)((Co + 7) / 8) * APL * T * Fr;
                 a.bl_ydec = S.decR[j].p; a.bl_stream = pv.dec_even.a.y_stream; a.bl_oT = 2 * Fi; a.bl_Fh = Fi; a.bl_Fo = Fo;
                 a.bl_nw = e->lv[j].dec_nw.p; a.bl_nb = e->lv[j].dec_nb.p; a.bl_mnw = e->lv[j].dec_mnw.p; a.bl_mnb = e->lv[j].dec_mnb.p;
                 a.bl_sy = sy; a.bl_su = SlabStats{e->skip_stats[j].p, pv.skipm.grid_x, nu, e->eps_mode};
@@ -729,7 +728,7 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
             }
             }
             xin = reinterpret_cast<const uint4 *>(S.decP[j].p);
-            xin_bytes = (size_t)B * ((Co + 7) / 8) * PL * T * Fr * 16;
+            xin_bytes = (size_t)B * ((Co + 7) / 8) * APL * T * Fr * 16;
         } else {
             if (Fo != e->F[0]) return fail(e, SE_ERR_ARG, "decoder output has %d bins, spectrum has %d", Fo, e->F[0]);
             MaskPArgs m{S.decR[j].p, (long)T * Fi * 8, Fi, e->lv[j].dec_nw.p, e->lv[j].dec_nb.p, sy, spec, sB, sT, sF, out, oB, oT, oF, T, e->F[0]};
@@ -747,8 +746,10 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
 }
 
 // P layout (device) -> reference layout [B][C][F][T] on the host (debug taps / state export); fp32 = sum of the planes
-int p_to_host(se_engine *e, const float *dev, int C, int F, float *host_out, hipStream_t st, bool to_bcft) {
-    const int T = e->T, B = e->B, PL = operand_planes(e->precision), C8 = (C + 7) / 8;
+// fmt: the format of the buffer `dev` points into (the fp16 pair is joined as the device readers join it: join2h)
+int p_to_host(se_engine *e, const float *dev, PlaneFmt fmt, int C, int F, float *host_out, hipStream_t st, bool to_bcft) {
+    const bool pair = fmt == PlaneFmt::kF16Pair;
+    const int T = e->T, B = e->B, PL = pair ? kPairPlanesA : operand_planes(e->precision), C8 = (C + 7) / 8;
     const size_t n16 = (size_t)B * C8 * PL * T * F;  // uint4 count
     std::vector<uint16_t> h(n16 * 8);
     HIPCHECK(e, hipStreamSynchronize(st));
@@ -758,20 +759,50 @@ int p_to_host(se_engine *e, const float *dev, int C, int F, float *host_out, hip
             for (int t = 0; t < T; t++)
                 for (int f = 0; f < F; f++) {
                     float v = 0;
+                    uint16_t up[3] = {0, 0, 0};
                     for (int pl = 0; pl < PL; pl++) {
                         const uint16_t u = h[(((((size_t)b * C8 + c / 8) * PL + pl) * T + t) * F + f) * 8 + c % 8];
+                        up[pl] = u;
+                        if (pair) continue;
                         if (PL == 1) { _Float16 hv; memcpy(&hv, &u, 2); v += (float)hv; }
                         else v += bf16_to_f32(u);
                     }
+                    if (pair) v = join2h(up[0], up[1]);
                     if (to_bcft) host_out[(((size_t)b * C + c) * F + f) * T + t] = v;
                     else host_out[(((size_t)b * C + c) * T + t) * F + f] = v;
                 }
     return SE_OK;
 }
 
+int host_to_p(se_engine *e, const std::vector<float> &src, PlaneFmt fmt, int C, int F, float *dev);
+
+// A weight load that changes the format of the convolution path's buffers (the range guard, once per load) between two calls of a
+// running batch: the conv history in the current ring slot of xinP[i >= 1] is re-written in the new format, through the host.  Every
+// other plane buffer is written before it is read within a segment.
+int convert_history_p(se_engine *e) {
+    se_convp_state &S = *e->cp;
+    const PlaneFmt now = act_format(e, PlaneBuf::kConvAct);
+    if (e->B <= 0 || !S.xinP[0].p || S.ring_fmt == now) { S.ring_fmt = now; return 0; }
+    HIPCHECK(e, hipDeviceSynchronize());
+    for (int i = 1; i < e->L; i++) {
+        std::vector<float> h((size_t)e->B * e->Ch[i] * e->T * e->F[i]);
+        float *slot = S.xinP[i].p + (size_t)e->slot * S.slot_elems[i] * 4;
+        int rc = p_to_host(e, slot, S.ring_fmt, e->Ch[i], e->F[i], h.data(), nullptr, false);
+        if (!rc) rc = host_to_p(e, h, now, e->Ch[i], e->F[i], slot);
+        if (rc) return rc;
+    }
+    S.ring_fmt = now;
+    return 0;
+}
+
 // host [B][C][T][F] fp32 -> P layout on the device (state import)
-int host_to_p(se_engine *e, const std::vector<float> &src, int C, int F, float *dev) {
-    const int T = e->T, B = e->B, PL = operand_planes(e->precision), C8 = (C + 7) / 8;
+int p_to_host(se_engine *e, const float *dev, PlaneBuf kind, int C, int F, float *host_out, hipStream_t st, bool to_bcft) {
+    return p_to_host(e, dev, act_format(e, kind), C, F, host_out, st, to_bcft);
+}
+
+int host_to_p(se_engine *e, const std::vector<float> &src, PlaneFmt fmt, int C, int F, float *dev) {
+    const bool pair = fmt == PlaneFmt::kF16Pair;
+    const int T = e->T, B = e->B, PL = pair ? kPairPlanesA : operand_planes(e->precision), C8 = (C + 7) / 8;
     std::vector<uint16_t> h((size_t)B * C8 * PL * T * F * 8, 0);
     for (int b = 0; b < B; b++)
         for (int c = 0; c < C; c++)
@@ -779,7 +810,8 @@ int host_to_p(se_engine *e, const std::vector<float> &src, int C, int F, float *
                 for (int f = 0; f < F; f++) {
                     const float x = src[(((size_t)b * C + c) * T + t) * F + f];
                     uint16_t parts[3];
-                    if (PL == 1) parts[0] = f16_rne(x);
+                    if (pair) split2h(x, parts[0], parts[1]);
+                    else if (PL == 1) parts[0] = f16_rne(x);
                     else {
                         parts[0] = bf16_rne(x);
                         const float r1 = x - bf16_to_f32(parts[0]);
@@ -790,6 +822,10 @@ int host_to_p(se_engine *e, const std::vector<float> &src, int C, int F, float *
                 }
     HIPCHECK(e, hipMemcpy(dev, h.data(), h.size() * 2, hipMemcpyHostToDevice));
     return SE_OK;
+}
+
+int host_to_p(se_engine *e, const std::vector<float> &src, PlaneBuf kind, int C, int F, float *dev) {
+    return host_to_p(e, src, act_format(e, kind), C, F, dev);
 }
 
 }  // namespace

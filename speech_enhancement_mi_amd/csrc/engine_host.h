@@ -96,14 +96,16 @@ inline int operand_planes(int precision) { return precision == 1 ? 1 : (precisio
 // The plane count is a property of the BUFFER, not only of the precision mode: with the fp16 pair format on (split_f16pair.h; precision
 // 0 only, decided when the weights are loaded) the buffers of kind kGemmA hold two fp16 planes.  kFeature: the STFT features and what
 // reads them (xinP[0]) - the magnitude channel scales with the input level, so they stay on bf16 planes; kConvAct: the activation
-// planes of the convolution / skip path (bf16 planes in this revision); kGemmA: the A operands of the bottleneck GEMMs and of the
-// recurrence (gruinP, seqP), bounded by a norm and by the GRU cell.
+// planes of the convolution / skip path (xinP[i >= 1], decinP, decP), bounded by a norm or by the skip gate's convex combination;
+// kGemmA: the A operands of the bottleneck GEMMs and of the recurrence (gruinP, seqP), bounded by a norm and by the GRU cell.
+// conv_on = false (SE_F16_PAIR_CONV=0): the convolution path keeps its bf16 planes while the bottleneck runs the pair.
 enum class PlaneBuf { kFeature, kConvAct, kGemmA };
-inline PlaneFmt buffer_format(int precision, bool pair_on, PlaneBuf kind) {
-    return pair_on && precision == 0 && kind == PlaneBuf::kGemmA ? PlaneFmt::kF16Pair : PlaneFmt::kBf16;
+inline PlaneFmt buffer_format(int precision, bool pair_on, PlaneBuf kind, bool conv_on = true) {
+    const bool takes = kind == PlaneBuf::kGemmA || (kind == PlaneBuf::kConvAct && conv_on);
+    return pair_on && precision == 0 && takes ? PlaneFmt::kF16Pair : PlaneFmt::kBf16;
 }
-inline int buffer_planes(int precision, bool pair_on, PlaneBuf kind) {
-    return buffer_format(precision, pair_on, kind) == PlaneFmt::kF16Pair ? kPairPlanesA : operand_planes(precision);
+inline int buffer_planes(int precision, bool pair_on, PlaneBuf kind, bool conv_on = true) {
+    return buffer_format(precision, pair_on, kind, conv_on) == PlaneFmt::kF16Pair ? kPairPlanesA : operand_planes(precision);
 }
 
 // the fp16-pair planes (2^11 hi, lo, hi) of a [rows][cols] fp32 matrix -> device buffer of 3*rows*cols uint16 (the shape of upload_planes)

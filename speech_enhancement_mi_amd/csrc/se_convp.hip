@@ -57,6 +57,42 @@ int SE_FN(conv_p_launch_pl)(int ntap2, int NT, int CO, dim3 grid, size_t lds, hi
 #undef SE_CP_CASE2
 }
 
+// The fp16 pair form (k_conv_p<.., kF16Pair>: two activation planes, three f16 MFMA terms) rides in the PL = 3 units of the tap counts
+// the CRN path runs: 15, 9 (+ 6: both parities), 6 and 1.  The 25-tap pre-conv blocks belong to CRN_ELU / the student: no pair form.
+#if SE_CP_PL == 3 && SE_CP_NTAP != 25
+#define SE_FNP(name) SE_CAT4(name, _pair, _t, SE_CP_NTAP)
+int SE_FNP(conv_p_launch)(int ntap2, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a) {
+#define SE_CP_CASE(NT_, CO_) \
+    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, 3, 0, PlaneFmt::kF16Pair>), grid, dim3(256), lds, st, a); return 0;
+#define SE_CP_CASE2(NT_, CO_) \
+    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, 3, SE_CP_NTAP2, PlaneFmt::kF16Pair>), grid, dim3(256), lds, st, a); return 0;
+    if (ntap2 == 0) {
+        switch (NT * 8 + CO) {
+            SE_CP_ALL(SE_CP_CASE)
+            default: return 1;
+        }
+    }
+    if (ntap2 != SE_CP_NTAP2) return 1;
+    switch (NT * 8 + CO) {
+        SE_CP_PAIR(SE_CP_CASE2)
+        default: return 1;
+    }
+#undef SE_CP_CASE
+#undef SE_CP_CASE2
+}
+
+void SE_FNP(conv_p_set_attributes)() {
+#define SE_CP_ATTR(NT_, CO_) \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, 3, 0, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SE_CP_ATTR2(NT_, CO_) \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, 3, SE_CP_NTAP2, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    SE_CP_ALL(SE_CP_ATTR)
+    SE_CP_PAIR(SE_CP_ATTR2)
+#undef SE_CP_ATTR
+#undef SE_CP_ATTR2
+}
+#endif
+
 void SE_FN(conv_p_set_attributes_pl)() {
 #define SE_CP_ATTR(NT_, CO_) \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -85,13 +121,15 @@ void launch_k_gln_p(int PL, dim3 grid, hipStream_t st, const GlnPArgs &a, PlaneF
     else if (PL == 2) hipLaunchKernelGGL(k_gln_p<2>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_gln_p<3>, grid, dim3(256), 0, st, a);
 }
-void launch_k_gln2_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a) {
-    if (PL == 1) hipLaunchKernelGGL(k_gln2_p<1>, grid, dim3(256), 0, st, a);
+void launch_k_gln2_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a, PlaneFmt fmt) {
+    if (fmt == PlaneFmt::kF16Pair) hipLaunchKernelGGL((k_gln2_p<kPairPlanesA, PlaneFmt::kF16Pair>), grid, dim3(256), 0, st, a);
+    else if (PL == 1) hipLaunchKernelGGL(k_gln2_p<1>, grid, dim3(256), 0, st, a);
     else if (PL == 2) hipLaunchKernelGGL(k_gln2_p<2>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_gln2_p<3>, grid, dim3(256), 0, st, a);
 }
-void launch_k_gln2_stream_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a) {
-    if (PL == 1) hipLaunchKernelGGL(k_gln2_stream_p<1>, grid, dim3(1024), 0, st, a);
+void launch_k_gln2_stream_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &a, PlaneFmt fmt) {
+    if (fmt == PlaneFmt::kF16Pair) hipLaunchKernelGGL((k_gln2_stream_p<kPairPlanesA, PlaneFmt::kF16Pair>), grid, dim3(1024), 0, st, a);
+    else if (PL == 1) hipLaunchKernelGGL(k_gln2_stream_p<1>, grid, dim3(1024), 0, st, a);
     else if (PL == 2) hipLaunchKernelGGL(k_gln2_stream_p<2>, grid, dim3(1024), 0, st, a);
     else hipLaunchKernelGGL(k_gln2_stream_p<3>, grid, dim3(1024), 0, st, a);
 }

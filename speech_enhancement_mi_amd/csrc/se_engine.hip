@@ -146,6 +146,7 @@ struct se_engine : EngineHost {
     // fp16 pair format (split_f16pair.h) on the bottleneck: gruinP / seqP as two fp16 planes, the k_gemm_p weights (wih_xp, wih_h,
     // fcw_xp) and whh_p as (2^11 hi, lo, hi), three MFMA terms instead of six
     int f16_pair = 1;         // SE_F16_PAIR=0: the bf16 route (three planes, six terms) everywhere
+    int f16_pair_conv = 1;    // SE_F16_PAIR_CONV=0: the pair on the bottleneck only; xinP[i >= 1], decinP, decP and their kernels on bf16 planes
     bool pair_on = false;     // decided once per weight load (f16_pair_decide): knob, eligibility and the range guard
     DevBuf wih_h[4];          // W_ih of layers >= 1 as pair planes (wih_x[l] stays bf16: the fp32-row GEMMs of small batches read it)
     // fc_output_layer + gLN(last) on the plane GEMM route: weight rows, bias and the norm's per-element affine permuted like W_ih0's
@@ -165,6 +166,11 @@ struct se_engine : EngineHost {
 };
 
 namespace {
+
+// format / plane count of an activation plane buffer of this engine (engine_host.h: buffer_format); encoder level i reads xinP[i]
+PlaneFmt act_format(const se_engine *e, PlaneBuf kind) { return buffer_format(e->precision, e->pair_on, kind, e->f16_pair_conv != 0); }
+int act_planes(const se_engine *e, PlaneBuf kind) { return buffer_planes(e->precision, e->pair_on, kind, e->f16_pair_conv != 0); }
+PlaneBuf xin_kind(int level) { return level == 0 ? PlaneBuf::kFeature : PlaneBuf::kConvAct; }
 
 int prof_label(se_engine *e, const char *kernel, const std::string &label, double flops) {
     for (size_t i = 0; i < e->prof_labels.size(); i++)
@@ -365,8 +371,9 @@ bool gemm_p_capable(const se_engine *e) { return e->gemm_p_env && e->D % 32 == 0
 
 // Range guard of the fp16 pair format, from the loaded parameters alone (never a run-time branch in a kernel): every activation that a
 // norm writes into a plane buffer is bounded by max|gamma| sqrt(N) + max|beta| (N elements per stream: |x - mean| <= sqrt(N) sigma),
-// and 2^11 w_hi must stay finite in fp16.  An activation bound above 6e4 or a weight operand of 2^4 or more keeps the whole engine
-// on the bf16 route.  All norms and all weight operands are checked, also those whose buffers do not take the format yet, so the
+// the skip output of a decoder level by the larger of its two branches (pair_skip_bound: the decoder norm's bound, or the row L1 norm
+// of residual.weight times the bound of `res`), and 2^11 w_hi must stay finite in fp16.  An activation bound above 6e4 or a weight
+// operand of 2^4 or more keeps the whole engine on the bf16 route.  All norms and all weight operands are checked, also those whose buffers do not take the format yet, so the
 // set of eligible checkpoints does not move when the convolution path follows.  (h_t is a convex combination of tanh values and
 // h_{t-1}; a caller-supplied state beyond the fp16 range is clamped by split2h.)
 bool f16_pair_guard(const se_engine *e) {
@@ -379,18 +386,27 @@ bool f16_pair_guard(const se_engine *e) {
         }
         return true;
     };
-    auto norm_ok = [&](const std::string &prefix, double n) {
+    auto norm_ok = [&](const std::string &prefix, double n, double *bound = nullptr) {
         float g = 0, b = 0;
         if (!absmax(prefix + "weight", g) || !absmax(prefix + "bias", b)) return false;
-        return (double)g * std::sqrt(n) + (double)b <= 6.0e4;
+        const double bd = pair_norm_bound(g, b, n);
+        if (bound) *bound = bd;
+        return bd <= kPairGuardLimit;
     };
     const int L = e->L, T = e->T;
+    double enc_bound[SE_MAX_LEVELS] = {};  // what convlist.i.norm writes: xinP[i + 1], the `res` of decoder level lvl = i + 1
     for (int i = 0; i < L; i++)
-        if (!norm_ok("convlist." + std::to_string(i) + ".norm.", (double)e->Ch[i + 1] * T * e->F[i + 1])) return false;
+        if (!norm_ok("convlist." + std::to_string(i) + ".norm.", (double)e->Ch[i + 1] * T * e->F[i + 1], &enc_bound[i])) return false;
     for (int j = 0; j < L; j++) {
         const int lvl = L - 1 - j, Co = lvl == 0 ? 2 : e->Ch[lvl], Fo = 2 * e->F[lvl + 1] - 1;
-        if (!norm_ok("deconvlist." + std::to_string(j) + ".norm.", (double)Co * T * Fo)) return false;
+        double dec_bound = 0;
+        if (!norm_ok("deconvlist." + std::to_string(j) + ".norm.", (double)Co * T * Fo, &dec_bound)) return false;
         if (lvl > 0 && !norm_ok("deconvlist." + std::to_string(j) + ".residualnorm.", (double)Co * T * Fo)) return false;
+        if (lvl > 0) {  // the skip output (decP[j]): the larger of its two branches (conv_weight_image.h: pair_skip_bound)
+            auto rw = e->params.find("deconvlist." + std::to_string(j) + ".residual.weight"), rb = e->params.find("deconvlist." + std::to_string(j) + ".residual.bias");
+            if (rw == e->params.end() || rb == e->params.end() || rw->second.size() != (size_t)Co * Co || rb->second.size() != (size_t)Co) return false;
+            if (!(pair_skip_bound(rw->second.data(), rb->second.data(), Co, enc_bound[lvl - 1], dec_bound) <= kPairGuardLimit)) return false;
+        }
     }
     if (!norm_ok("gru.norm.", (double)T * e->D)) return false;
     for (const auto &kv : e->params) {  // every weight operand: all *.weight / weight_* that are not a norm's gamma
@@ -862,21 +878,22 @@ int stage_gru_out(se_engine *e, int cur, hipStream_t st) {
     int rc;
     // decoder input in the plane layout
     const int PL = operand_planes(e->precision), C = e->Ch[L], C8 = (C + 7) / 8, Fl = e->F[L];
-    Gln2PArgs g{e->fc_out.p, e->gnw.p, e->gnb.p, decin_p(e, cur), (long)C8 * PL * T * Fl, T, Fl, C, C8, e->eps_mode, SlabStats{}};
+    const PlaneFmt dfmt = act_format(e, PlaneBuf::kConvAct);  // decinP
+    Gln2PArgs g{e->fc_out.p, e->gnw.p, e->gnb.p, decin_p(e, cur), (long)C8 * act_planes(e, PlaneBuf::kConvAct) * T * Fl, T, Fl, C, C8, e->eps_mode, SlabStats{}};
     if (e->gemm_p) {  // octet-interleaved columns, statistics from the GEMM's epilogue, full-chip one-pass norm
         const int ND = C8 * Fl * 8, nct = (ND + kGemmPBN - 1) / kGemmPBN;
         if (!(e->dbg_skip & 2) && (rc = launch_gemm_p(e, e->seqP[e->NL - 1][cur].p, e->fcw_xp.p, e->fcb_p.p, e->fc_out.p, ND, Ba * T, ND, H, e->act, st, "gru_fc", e->fc_stats.p))) return rc;
         ProfScope ps(e, "k_gln2_p", "gln_fc", 0, st);  // (records are keyed by label: its own, not the conv norms' "gln")
         g.w = e->gnw_p.p; g.b = e->gnb_p.p;
         g.st = SlabStats{e->fc_stats.p, T * nct, (long)T * C * Fl, e->eps_mode};
-        launch_k_gln2_p(PL, dim3((T * Fl + 1023) / 1024, C8, Ba), st, g);
+        launch_k_gln2_p(PL, dim3((T * Fl + 1023) / 1024, C8, Ba), st, g, dfmt);
         HIPCHECK(e, hipGetLastError());
         return 0;
     }
     // fp32 GEMM route (few rows): the reference's column order, two-pass statistics in the norm kernel
     if (!(e->dbg_skip & 2) && (rc = launch_gemm(e, e->seqr[e->NL - 1][cur].p, H, e->fcw.p, H, e->fcb.p, e->fc_out.p, D, Ba * T, D, H, e->act, st, "gru_fc", e->fcw_x.p))) return rc;
     ProfScope ps(e, "k_gln2_stream_p", "gln_fc_stream", 0, st);
-    launch_k_gln2_stream_p(PL, dim3(Ba), st, g);
+    launch_k_gln2_stream_p(PL, dim3(Ba), st, g, dfmt);
     HIPCHECK(e, hipGetLastError());
     return 0;
 }
@@ -943,7 +960,7 @@ int ensure_ready(se_engine *e) {
     int rc = prepare_weights(e);
     if (rc) return rc;
     if (replanned) {
-        if ((rc = prepare_weights_p(e))) return rc;
+        if ((rc = prepare_weights_p(e)) || (rc = convert_history_p(e))) return rc;
         // capability only: whether THIS batch takes the plane GEMMs is select_gemm_route()'s decision (a batch on the skinny route
         // never allocated gruinP / seqP, so a weight reload must not switch the plane route back on behind its back)
         e->gemm_p_cap = gemm_p_capable(e);
@@ -975,7 +992,10 @@ int ensure_ready(se_engine *e) {
                 (rc = dev_upload(e, e->gnb_p, nbp)))
                 return rc;
         }
-        if (e->B > 0) select_all_p(e);
+        if (e->B > 0) {  // the tilings follow the buffer format, which this load may have flipped: slabs for the new grids
+            select_all_p(e);
+            if ((rc = alloc_stats_p(e))) return rc;
+        }
     }
     if (replanned && e->B > 0)  // new weights re-made the plans with their default tiling: restore the per-batch choice
         for (int i = 0; i < SE_MAX_LEVELS; i++)
@@ -988,7 +1008,8 @@ int ensure_ready(se_engine *e) {
 
 namespace {
 // P layout [b][octet][plane][t][f] (16-byte pieces of 8 channels) -> fp32 [b][c][t][f]: the operands of a feature-tap re-run
-template <int PL>
+// PAIR: the planes are the fp16 pair (PL = 2), joined as join2h joins them
+template <int PL, bool PAIR = false>
 __global__ void k_tap_p_to_f32(const uint4 *P, float *dst, int B, int C, int T, int F) {
     const int C8 = (C + 7) >> 3;
     const long n = (long)B * C8 * T * F;
@@ -996,8 +1017,15 @@ __global__ void k_tap_p_to_f32(const uint4 *P, float *dst, int B, int C, int T, 
         const long tf = i % ((long)T * F), bo = i / ((long)T * F);
         const int o = (int)(bo % C8), b = (int)(bo / C8);
         float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if constexpr (PAIR) {
+            typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+            const u16x8 hi = __builtin_bit_cast(u16x8, P[(((long)b * C8 + o) * PL) * T * F + tf]);
+            const u16x8 lo = __builtin_bit_cast(u16x8, P[(((long)b * C8 + o) * PL + 1) * T * F + tf]);
 #pragma unroll
-        for (int pl = 0; pl < PL; pl++) {
+            for (int c = 0; c < 8; c++) v[c] = join2h(hi[c], lo[c]);
+        }
+#pragma unroll
+        for (int pl = 0; pl < (PAIR ? 0 : PL); pl++) {
             const uint4 q = P[(((long)b * C8 + o) * PL + pl) * T * F + tf];
             if (PL == 1) {
                 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -1026,11 +1054,12 @@ __global__ void k_tap_tf_to_ft(const float *src, float *dst, long BC, int T, int
         dst[i] = src[(bc * T + t) * F + f];
     }
 }
-int tap_p_to_f32_dev(se_engine *e, const float *psrc, int C, int F, float *dst, hipStream_t st) {
+int tap_p_to_f32_dev(se_engine *e, const float *psrc, PlaneBuf kind, int C, int F, float *dst, hipStream_t st) {
     const int PL = operand_planes(e->precision);
     const dim3 g(1024), b(256);
     const uint4 *P = reinterpret_cast<const uint4 *>(psrc);
-    if (PL == 1) hipLaunchKernelGGL(k_tap_p_to_f32<1>, g, b, 0, st, P, dst, e->B, C, e->T, F);
+    if (act_format(e, kind) == PlaneFmt::kF16Pair) hipLaunchKernelGGL((k_tap_p_to_f32<kPairPlanesA, true>), g, b, 0, st, P, dst, e->B, C, e->T, F);
+    else if (PL == 1) hipLaunchKernelGGL(k_tap_p_to_f32<1>, g, b, 0, st, P, dst, e->B, C, e->T, F);
     else if (PL == 2) hipLaunchKernelGGL(k_tap_p_to_f32<2>, g, b, 0, st, P, dst, e->B, C, e->T, F);
     else hipLaunchKernelGGL(k_tap_p_to_f32<3>, g, b, 0, st, P, dst, e->B, C, e->T, F);
     HIPCHECK(e, hipGetLastError());
@@ -1046,8 +1075,8 @@ static int state_rows_of(se_engine *e, unsigned which, F &&f) {
     static_assert(SE_MAX_LEVELS + 3 + 4 <= kStateRowsMax, "state row table too small");
     int rc;
     if (which & 1u) {
-        for (int i = 0; i < e->L; i++)  // [slot][b][C8][PL][T][F] pieces of 16 bytes
-            if ((rc = f(e->cp->xinP[i].p + (size_t)e->slot * e->cp->slot_elems[i] * 4, e->carry_x[i], (long)(e->cp->slot_elems[i] / e->B) * 4))) return rc;
+        for (int i = 0; i < e->L; i++)  // [slot][b][C8][planes][T][F] pieces of 16 bytes; the stream stride follows the buffer's format
+            if ((rc = f(e->cp->xinP[i].p + (size_t)e->slot * e->cp->slot_elems[i] * 4, e->carry_x[i], xin_stream_elems(e, i) * 4))) return rc;
         for (int i = 0; i < e->npre; i++) {
             if (e->cp->pre_p) rc = f(e->cp->pinP[i].p + (size_t)e->slot * e->cp->pslot_elems * 4, e->carry_p[i], (long)(e->cp->pslot_elems / e->B) * 4);
             else rc = f(e->pin[i][e->parity].p, e->carry_p[i], (long)e->Ch[0] * e->T * e->F[0]);
@@ -1108,6 +1137,7 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (const char *s = getenv("SE_GRU_DIRECT")) e->gru_direct = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_GRU_SPLIT")) e->gru_split = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_F16_PAIR")) e->f16_pair = atoi(s) != 0 ? 1 : 0;
+    if (const char *s = getenv("SE_F16_PAIR_CONV")) e->f16_pair_conv = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
     if (const char *s = getenv("SE_DBG_SKIP")) { e->dbg_skip = atoi(s); fprintf(stderr, "se_engine: SE_DBG_SKIP=%d - stages are skipped, results are WRONG (timing experiment)\n", e->dbg_skip); }
@@ -1601,7 +1631,8 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
     if (strncmp(name, "ft", 2)) {  // operand tensors are split-bf16 planes, summed back on the host
         se_convp_state &S = *e->cp;
         const float *psrc = nullptr;
-        if (!strcmp(name, "feat")) { psrc = S.xinP[0].p + (size_t)cur * S.slot_elems[0] * 4; C = e->Ch[0]; F = e->F[0]; }
+        PlaneBuf kind = PlaneBuf::kConvAct;
+        if (!strcmp(name, "feat")) { kind = PlaneBuf::kFeature; psrc = S.xinP[0].p + (size_t)cur * S.slot_elems[0] * 4; C = e->Ch[0]; F = e->F[0]; }
         else if (!strcmp(name, "gru")) { psrc = S.decinP[cur].p; C = e->Ch[L]; F = e->F[L]; }
         else if (sscanf(name, "enc%d", &idx) == 1 && idx >= 0 && idx < L - 1) { psrc = S.xinP[idx + 1].p + (size_t)cur * S.slot_elems[idx + 1] * 4; C = e->Ch[idx + 1]; F = e->F[idx + 1]; }
         else if (sscanf(name, "dec%d", &idx) == 1 && idx >= 0 && idx < L - 1) { psrc = S.decP[idx].p; C = e->Ch[L - 1 - idx]; F = e->F[L - 1 - idx]; }
@@ -1609,7 +1640,7 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
             const size_t n = (size_t)B * C * T * F;
             if (count) *count = (int64_t)n;
             if ((int64_t)n > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n);
-            return p_to_host(e, psrc, C, F, host_out, st, true);
+            return p_to_host(e, psrc, kind, C, F, host_out, st, true);
         }
         if (sscanf(name, "enc%d", &idx) != 1 || idx != L - 1) return fail(e, SE_ERR_KEY, "unknown tap %s", name);
         // the GRU input: GEMM A planes [PL][B*T][(o*F+f)*8+c] (k_gemm_p) or fp32 rows [B][T][C*F]
@@ -1658,7 +1689,7 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         DevBuf tmp;
         // The operands of the re-run live in the P layout: k_tap_p_to_f32 sums the planes back into the fp32 buffers the
         // re-run reads (a tap is a training / debugging aid, not part of the hot path).
-        auto p_to_f32 = [&](const float *psrc, int C_, int F_, float *dst) -> int { return tap_p_to_f32_dev(e, psrc, C_, F_, dst, st); };
+        auto p_to_f32 = [&](const float *psrc, PlaneBuf kind, int C_, int F_, float *dst) -> int { return tap_p_to_f32_dev(e, psrc, kind, C_, F_, dst, st); };
         auto finish = [&](int C_, int F_, bool raw_flat) -> int {
             const size_t n_ = (size_t)B * C_ * T * F_;
             if (count) *count = (int64_t)n_;
@@ -1685,8 +1716,8 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         if (idx == 0) {
             const int i = L - 1, Co = e->Ch[L], Fo = e->F[L];
             se_convp_state &S = *e->cp;
-            if ((rc = p_to_f32(S.xinP[i].p + (size_t)cur * S.slot_elems[i] * 4, e->Ch[i], e->F[i], e->xin[i][cur].p)) ||
-                (rc = p_to_f32(S.xinP[i].p + (size_t)prev * S.slot_elems[i] * 4, e->Ch[i], e->F[i], e->xin[i][prev].p))) return rc;
+            if ((rc = p_to_f32(S.xinP[i].p + (size_t)cur * S.slot_elems[i] * 4, xin_kind(i), e->Ch[i], e->F[i], e->xin[i][cur].p)) ||
+                (rc = p_to_f32(S.xinP[i].p + (size_t)prev * S.slot_elems[i] * 4, xin_kind(i), e->Ch[i], e->F[i], e->xin[i][prev].p))) return rc;
             if ((rc = dev_alloc(e, tmp, (size_t)B * Co * T * Fo))) return rc;
             ConvPlan pl = e->lv[i].enc;
             pl.a.relu_lo = pl.a.relu_hi = 0;
@@ -1705,7 +1736,7 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         if ((rc = dev_alloc(e, tmp, (size_t)B * Co * T * Fo))) return rc;
         float *xin = j == 0 ? e->dec_in[cur].p : e->dec_out[j - 1].p;
         se_convp_state &S = *e->cp;
-        if ((rc = p_to_f32(j == 0 ? S.decinP[cur].p : S.decP[j - 1].p, e->Ch[lvl + 1], e->F[lvl + 1], xin))) { dev_free(tmp); return rc; }
+        if ((rc = p_to_f32(j == 0 ? S.decinP[cur].p : S.decP[j - 1].p, PlaneBuf::kConvAct, e->Ch[lvl + 1], e->F[lvl + 1], xin))) { dev_free(tmp); return rc; }
         ConvPlan pe = e->lv[j].dec_even, po = e->lv[j].dec_odd;
         pe.a.relu_lo = pe.a.relu_hi = 0;
         po.a.relu_lo = po.a.relu_hi = 0;
@@ -1739,10 +1770,10 @@ int se_export_state(se_engine *e, const char *name, float *host_out, int64_t cap
         std::vector<float> h(nsrc);
         HIPCHECK(e, hipStreamSynchronize(st));
         if (!is_pbuf) {
-            int rc = p_to_host(e, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4, C, F, h.data(), st, false);
+            int rc = p_to_host(e, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4, xin_kind(idx), C, F, h.data(), st, false);
             if (rc) return rc;
         } else if (e->cp->pre_p) {
-            int rc = p_to_host(e, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4, C, F, h.data(), st, false);
+            int rc = p_to_host(e, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4, PlaneBuf::kFeature, C, F, h.data(), st, false);
             if (rc) return rc;
         } else
         HIPCHECK(e, hipMemcpy(h.data(), e->pin[idx][e->parity].p, nsrc * sizeof(float), hipMemcpyDeviceToHost));
@@ -1776,8 +1807,8 @@ int se_import_state(se_engine *e, const char *name, const float *host_in, int64_
         for (size_t bc = 0; bc < (size_t)B * C; bc++)
             for (int f = 0; f < F; f++)
                 for (int p = 0; p < P; p++) h[(bc * T + (T - P + p)) * F + f] = host_in[(bc * F + f) * P + p];
-        if (!is_pbuf) return host_to_p(e, h, C, F, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4);
-        if (e->cp->pre_p) return host_to_p(e, h, C, F, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4);
+        if (!is_pbuf) return host_to_p(e, h, xin_kind(idx), C, F, e->cp->xinP[idx].p + (size_t)e->slot * e->cp->slot_elems[idx] * 4);
+        if (e->cp->pre_p) return host_to_p(e, h, PlaneBuf::kFeature, C, F, e->cp->pinP[idx].p + (size_t)e->slot * e->cp->pslot_elems * 4);
         HIPCHECK(e, hipMemcpy(e->pin[idx][e->parity].p, h.data(), nsrc * sizeof(float), hipMemcpyHostToDevice));
         return SE_OK;
     }

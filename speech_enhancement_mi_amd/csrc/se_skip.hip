@@ -7,18 +7,31 @@
 
 namespace se {
 
-int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const SkipPArgs &a) {
+// waves per workgroup from KP x planes: 16 (1024 threads, 128 registers) up to 4, 8 above.  The fp16 pair form counts its three WEIGHT
+// planes, as the three-plane bf16 form does: with 16 waves its KP = 2 instance, two activation planes in flight, still needs 12 bytes
+// of scratch per lane in 128 registers (compiler report); with 8 waves it takes what it needs and KP = 1 / 2 / 4 are all scratch-free.
+#define SE_SK_NW(PL_, KP_) (KP_ * PL_ <= 4 ? 16 : 8)
+
+int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, PlaneFmt fmt) {
+#define SE_SKP(KP_) \
+    if (KP == KP_) { hipLaunchKernelGGL((k_skip_p<kPairPlanesW, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), dim3(batch), dim3(SE_SK_NW(kPairPlanesW, KP_) * 64), lds, st, a); return 0; }
+    if (fmt == PlaneFmt::kF16Pair) {
+        SE_SKP(1) SE_SKP(2) SE_SKP(4)
+        return 1;
+    }
 #define SE_SK(PL_, KP_) \
-    if (PL == PL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_p<PL_, KP_, (KP_ * PL_ <= 4 ? 16 : 8)>), dim3(batch), dim3(KP_ * PL_ <= 4 ? 1024 : 512), lds, st, a); return 0; }
+    if (PL == PL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_p<PL_, KP_, SE_SK_NW(PL_, KP_)>), dim3(batch), dim3(SE_SK_NW(PL_, KP_) * 64), lds, st, a); return 0; }
 #define SE_SK3(KP_) SE_SK(1, KP_) SE_SK(2, KP_) SE_SK(3, KP_)
     SE_SK3(1) SE_SK3(2) SE_SK3(4)
     return 1;
 }
 
 void skip_p_set_attributes() {
-#define SE_SKA(PL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<PL_, KP_, (KP_ * PL_ <= 4 ? 16 : 8)>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+#define SE_SKA(PL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<PL_, KP_, SE_SK_NW(PL_, KP_)>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
 #define SE_SKA3(KP_) SE_SKA(1, KP_) SE_SKA(2, KP_) SE_SKA(3, KP_)
     SE_SKA3(1) SE_SKA3(2) SE_SKA3(4)
+#define SE_SKAP(KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<kPairPlanesW, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    SE_SKAP(1) SE_SKAP(2) SE_SKAP(4)
 }
 
 }  // namespace se

@@ -23,8 +23,14 @@ namespace se {
 
 // NW = waves per workgroup: 16 (1024 threads, 128 VGPRs) for KP <= 2, 8 for KP = 4 - the kernel is a latency-bound stream
 // (one workgroup per CU), so bytes in flight = waves x fragments in flight decide its rate
-template <int PL, int KP, int NW>
+// FMT = kF16Pair (PL = 3 weight planes): res and out are two fp16 planes (split_f16pair.h), the weights (2^11 w_hi, w_lo, w_hi), three f16
+// MFMAs per K step in the fixed order W0 b_hi, W1 b_hi, W2 b_lo, and the 2^-11 (exact) on the accumulators before the statistics of
+// pass 1 and before the gate of pass 2.
+template <int PL, int KP, int NW, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
+    constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
+    static_assert(!PAIR || PL == kPairPlanesW, "the fp16 pair form has three weight planes");
+    constexpr int APL = PAIR ? kPairPlanesA : PL;  // planes of res and out
     extern __shared__ __align__(16) uint4 wl[];  // [2*MTh][KP][PL][64] weight fragments, then cst[6][Cp] floats
     __shared__ float sm[4];
     __shared__ double red[2][NW];
@@ -43,24 +49,30 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
     const int tiles = (a.TF + 31) >> 5;
     const long plane = a.TF;  // uint4 per plane of one octet
 
-    // B fragments of one position tile: KP K steps x PL planes; lane half h of step kp holds octet 2 kp + h
-    auto load_b = [&](int tile, uint4 (&bf)[KP][PL]) {
+    // B fragments of one position tile: KP K steps x APL planes; lane half h of step kp holds octet 2 kp + h
+    auto load_b = [&](int tile, uint4 (&bf)[KP][APL]) {
         const int p = min(tile * 32 + l31, a.TF - 1);
 #pragma unroll
         for (int kp = 0; kp < KP; kp++) {
             const int o = min(2 * kp + half, a.C8 - 1);  // a missing odd octet reads a valid one (its weights are zero)
 #pragma unroll
-            for (int pl = 0; pl < PL; pl++) bf[kp][pl] = xb[((long)o * PL + pl) * plane + p];
+            for (int pl = 0; pl < APL; pl++) bf[kp][pl] = xb[((long)o * APL + pl) * plane + p];
         }
     };
-    auto mma_tile = [&](int mt, const uint4 (&bf)[KP][PL]) {
+    auto mma_tile = [&](int mt, const uint4 (&bf)[KP][APL]) {
         f32x16 c;
 #pragma unroll
         for (int r = 0; r < 16; r++) c[r] = 0.0f;
 #pragma unroll
         for (int kp = 0; kp < KP; kp++) {
             const uint4 *wf = wl + ((long)(mt * KP + kp) * PL) * 64 + l31 * 2 + half;
-            if (PL >= 2) {
+            if constexpr (PAIR) {
+                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+                const h8 bh = __builtin_bit_cast(h8, bf[kp][0]), bl = __builtin_bit_cast(h8, bf[kp][APL > 1 ? 1 : 0]);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[0]), bh, c, 0, 0, 0);                  // 2^11 w_hi * x_hi
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[PL > 1 ? 64 : 0]), bh, c, 0, 0, 0);    // w_lo * x_hi
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[PL > 2 ? 128 : 0]), bl, c, 0, 0, 0);   // w_hi * x_lo
+            } else if (PL >= 2) {
                 const bf16x8 a0 = __builtin_bit_cast(bf16x8, wf[0]), a1 = __builtin_bit_cast(bf16x8, wf[PL > 1 ? 64 : 0]);
                 const bf16x8 b0 = __builtin_bit_cast(bf16x8, bf[kp][0]), b1 = __builtin_bit_cast(bf16x8, bf[kp][PL > 1 ? 1 : 0]);
                 if (PL == 3) {
@@ -77,6 +89,10 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
                 c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[0]), __builtin_bit_cast(h8, bf[kp][0]), c, 0, 0, 0);
             }
         }
+        if constexpr (PAIR) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) c[r] *= kPairInvScale;
+        }
         return c;
     };
     // wl fragment layout per (mt, kp, plane): 64 uint4 = [row 32][k half 2]; lane (row l31, half) reads l31*2 + half
@@ -84,7 +100,7 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
     // ---- pass 1: statistics of residualmask(res) ----
     double s1 = 0, s2 = 0;
     {
-        uint4 bcur[KP][PL], bnxt[KP][PL];
+        uint4 bcur[KP][APL], bnxt[KP][APL];
         if (wave < tiles) load_b(wave, bcur);
         for (int tile = wave; tile < tiles; tile += NW) {
             if (tile + NW < tiles) load_b(tile + NW, bnxt);
@@ -104,7 +120,7 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
 #pragma unroll
             for (int kp = 0; kp < KP; kp++)
 #pragma unroll
-                for (int pl = 0; pl < PL; pl++) bcur[kp][pl] = bnxt[kp][pl];
+                for (int pl = 0; pl < APL; pl++) bcur[kp][pl] = bnxt[kp][pl];
         }
     }
 #pragma unroll
@@ -127,7 +143,7 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
     const float invF = 1.0f / (float)a.Fr;
     const float *ydb = a.ydec + (long)b * a.y_stream;
     uint4 *ob = a.out + (long)b * a.out_stream;
-    uint4 bcur[KP][PL], bnxt[KP][PL];
+    uint4 bcur[KP][APL], bnxt[KP][APL];
     if (wave < tiles) load_b(wave, bcur);
     for (int tile = wave; tile < tiles; tile += NW) {
         if (tile + NW < tiles) load_b(tile + NW, bnxt);
@@ -160,13 +176,13 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
                     const float g = 1.0f / (1.0f + expf(-un));
                     o[q] = ch < a.C ? g * v + (1.0f - g) * yn : 0.0f;
                 }
-                if (pos_ok) split_store8<PL>(o, ob + (long)oct * PL * plane + p, plane);
+                if (pos_ok) split_store8_fmt<PL, FMT>(o, ob + (long)oct * APL * plane + p, plane);
             }
         }
 #pragma unroll
         for (int kp = 0; kp < KP; kp++)
 #pragma unroll
-            for (int pl = 0; pl < PL; pl++) bcur[kp][pl] = bnxt[kp][pl];
+            for (int pl = 0; pl < APL; pl++) bcur[kp][pl] = bnxt[kp][pl];
     }
 }
 

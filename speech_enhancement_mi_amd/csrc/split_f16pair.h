@@ -81,6 +81,17 @@ SE_PAIR_HD inline void split2h(float x, uint16_t &hi, uint16_t &lo) {
     if (x != x) x = 0.0f;
     hi = pair_f16_bits(x);
     lo = pair_f16_bits((x - pair_f16_value(hi)) * kPairScale);
+    // Canonical form.  A low part within 2^-12 of half an ulp of hi rounds UP to that half ulp, which puts the stored value hi + lo 2^-11
+    // (exact in fp32: 23 bits) on a tie of the fp16 grid, where an odd hi is not what fp16() of the stored value returns.  The pair is
+    // then re-formed from the stored value - the same value, the other representation - so that split2h(join2h(hi, lo)) == (hi, lo) for
+    // every pair this function returns: a history that goes through export_state / import_state comes back with the same bits.
+    const float stored = pair_f16_value(hi) + pair_f16_value(lo) * kPairInvScale;
+    const uint16_t hi2 = pair_f16_bits(stored);
+    if (hi2 != hi) {
+        hi = hi2;
+        lo = pair_f16_bits((stored - pair_f16_value(hi2)) * kPairScale);  // (+- half an ulp of hi2: exact)
+    }
+    if ((lo & 0x7fffu) == 0) lo = 0;  // (a negative residual below 2^-25 rounds to -0: the stored zero is +0)
 }
 
 // the inverse, one fp32 add (the product is exact): the same expression in the device readers and the host taps
