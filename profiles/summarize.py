@@ -31,6 +31,17 @@ def base_name(k):
 PROFILE_NAME = {"k_gru_step2": "k_gru_step", "k_gru_step_multi": "k_gru_step", "k_gru_step_multi8": "k_gru_step"}
 
 
+def record_name(full):
+    """The profile record's name of a kernel instance.  The fp16 pair's two-stored-plane instances are filed
+    under `<kernel>_w2`: k_gemm_p<2, pair>, k_skip_p<2, .., pair> and k_gru_step_split[_multi]<.., true, 2>."""
+    name = base_name(full)
+    args = full.split("<", 1)[1].split(">(")[0].replace(" ", "") if "<" in full else ""
+    pair = args.endswith("(se::PlaneFmt)1")
+    if (name in ("k_gemm_p", "k_skip_p") and pair and args.startswith("2,")) or (name.startswith("k_gru_step_split") and args.endswith("true,2")):
+        return name + "_w2"
+    return PROFILE_NAME.get(name, name)
+
+
 def hbm_json(src, workload, note, out):
     import json
     import os
@@ -41,7 +52,7 @@ def hbm_json(src, workload, note, out):
         if r["counter"] not in ("FETCH_SIZE", "WRITE_SIZE"):
             continue
         name = base_name(r["kernel"])
-        for key in {name, PROFILE_NAME.get(name, name)}:
+        for key in {name, record_name(r["kernel"])}:
             a = acc.setdefault(key, {"FETCH_SIZE": [0.0, 0], "WRITE_SIZE": [0.0, 0]})
             a[r["counter"]][0] += float(r["sum_KB"])
             a[r["counter"]][1] += int(r["launches"])

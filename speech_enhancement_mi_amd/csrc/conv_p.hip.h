@@ -97,10 +97,14 @@ __device__ __forceinline__ void convp_stats_store(float *stats, int nslot, int s
 // v_mfma_f32_32x32x16_f16 into the one accumulator set, in this fixed order: W0 b_hi, W1 b_hi, W2 b_lo.  The accumulators hold
 // 2^11 (w x) and are scaled by 2^-11 (exact) ahead of bias, activation and statistics.  Built for the instances the CRN path runs
 // (R, P and blend outputs); the gate / pre-conv epilogues of CRN_ELU and the student have no pair form.
+// FMT = kF16Pair, PL = 2: the weight image holds the two STORED planes (w_lo, w_hi) - two fragment loads per (chunk, tap pair, M tile)
+// instead of three - and W0 = 2^11 w_hi is made from the w_hi fragment in registers, once per tap pair (pair_scale_hi), ahead of the
+// tile loop.  Same MFMAs, same order, same bits.
 template <int NTAP, int NT, int CO, int PL, int NTAP2 = 0, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_conv_p(ConvPArgs a) {
     constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
-    static_assert(!PAIR || PL == kPairPlanesW, "the fp16 pair form has three weight planes");
+    static_assert(!PAIR || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair form has three weight planes, or two stored ones");
+    constexpr bool PAIR_W2 = PAIR && PL == kPairPlanesW2;
     constexpr int APL = PAIR ? kPairPlanesA : PL;  // planes of the activation buffers (input patch, P-layout output)
 #ifdef SE_CP_TRACE
     unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
@@ -277,6 +281,10 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
 #pragma unroll
                     for (int p = 0; p < PL; p++) fa_n[p] = wc[(pr + 1) * wx_pair + p * wx_plane];
                 }
+                // the three A operands of the pair in term order (W0, W1, W2); two stored planes: (made here, fa[0], fa[1])
+                uint4 fw[3];
+                if constexpr (PAIR_W2) { fw[0] = pair_scale_hi(fa[1]); fw[1] = fa[0]; fw[2] = fa[1]; }
+                else if constexpr (PAIR) { fw[0] = fa[0]; fw[1] = fa[PL > 1 ? 1 : 0]; fw[2] = fa[PL > 2 ? 2 : 0]; }
 #pragma unroll
                 for (int i = 0; i < NT; i++) {
                     // software pipeline, one fragment deep: the LDS reads of the NEXT (tile, K step) are issued before this
@@ -288,9 +296,9 @@ __global__ __launch_bounds__(256, (NTAP2 ? 2 * NT : NT) <= 6 ? 2 : 1) void k_con
                     if constexpr (PAIR) {
                         typedef _Float16 h8 __attribute__((ext_vector_type(8)));
                         const h8 bh = __builtin_bit_cast(h8, bcur[0]), bl = __builtin_bit_cast(h8, bcur[APL > 1 ? 1 : 0]);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[0]), bh, c, 0, 0, 0);               // 2^11 w_hi * x_hi
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[PL > 1 ? 1 : 0]), bh, c, 0, 0, 0);  // w_lo * x_hi
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fa[PL > 2 ? 2 : 0]), bl, c, 0, 0, 0);  // w_hi * x_lo
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fw[0]), bh, c, 0, 0, 0);  // 2^11 w_hi * x_hi
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fw[1]), bh, c, 0, 0, 0);  // w_lo * x_hi
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, fw[2]), bl, c, 0, 0, 0);  // w_hi * x_lo
                     } else if (PL >= 2) {
                         const bf16x8 a0 = __builtin_bit_cast(bf16x8, fa[0]), a1 = __builtin_bit_cast(bf16x8, fa[PL > 1 ? 1 : 0]),
                                      a2 = __builtin_bit_cast(bf16x8, fa[PL > 2 ? 2 : 0]);

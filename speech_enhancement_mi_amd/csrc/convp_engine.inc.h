@@ -26,6 +26,7 @@ struct ConvPPlan {
                                // transposed convolution, on the same patch)
     int npair = 0, terms = 6, npair2 = 0;
     PlaneFmt fmt = PlaneFmt::kBf16;  // format of the INPUT planes (and of a P-layout output): which k_conv_p form the launch takes
+    int wpl = 3;                     // stored planes of the weight image: the instance's weight-plane parameter
     double flops_pair = 0;
     std::string name;  // launch-site label ("enc3", "skip0", ...): SE_CONVP_NT_<name>=n forces a tiling for experiments
 };
@@ -33,7 +34,7 @@ struct ConvPPlan {
 struct SkipPPlan {  // k_skip_p: the whole skip gate of one decoder level, one workgroup per stream
     SkipPArgs a{};
     DevBuf wx, cst;
-    int KP = 0;
+    int KP = 0, wpl = 3;  // K steps; stored planes of the weight image
     size_t lds = 0;
     bool active = false;
     double flops = 0;
@@ -50,8 +51,9 @@ struct PLevel {
 
 // the planes of one weight in the format of the launch that reads it (conv_weight_image.h: `parts`): the fp16 pair's
 // (2^11 w_hi, w_lo, w_hi), one fp16 number, or (hi, mid, lo) bf16
+// (PL = the stored planes of the image: the pair's two or three, split_f16pair.h)
 inline void weight_parts(float x, int PL, PlaneFmt fmt, uint16_t (&p)[3]) {
-    if (fmt == PlaneFmt::kF16Pair) { pair_weight_planes(x, p); return; }
+    if (fmt == PlaneFmt::kF16Pair) { pair_weight_parts(x, PL, p); return; }
     const uint16_t h = bf16_rne(x);
     const float r1 = x - bf16_to_f32(h);
     const uint16_t md = bf16_rne(r1);
@@ -88,8 +90,10 @@ int plan_conv_p(se_engine *e, ConvPPlan &pl, int Ci, int Co, int FP, int Fi, int
     pl.active = FP > 0;
     pl.fmt = fmt;
     if (!pl.active) return 0;
-    // PL: weight planes (three in both formats at precision 0); APL: planes of the patch this launch stages
-    const int T = e->T, ntap = (int)taps.size(), PL = operand_planes(e->precision), APL = fmt == PlaneFmt::kF16Pair ? kPairPlanesA : PL;
+    // PL: stored weight planes (the pair's two, or three under SE_PAIR_W3); APL: planes of the patch this launch stages
+    const bool fpair = fmt == PlaneFmt::kF16Pair;
+    const int T = e->T, ntap = (int)taps.size(), PL = fpair ? pair_wplanes(e) : operand_planes(e->precision), APL = fpair ? kPairPlanesA : operand_planes(e->precision);
+    pl.wpl = PL;
     const int P = T * FP, tiles = (P + 31) / 32;
     const int CoPad = (Co + 31) / 32 * 32;
     if (CoPad > 128 || CoPad == 96) return fail(e, SE_ERR_ARG, "conv with %d GEMM rows is not supported", Co);
@@ -222,7 +226,7 @@ int launch_conv_p(se_engine *e, const ConvPPlan &pl, const ConvPArgs &a_in, hipS
 #ifdef SE_CP_TRACE
     a.trace = g_cp_trace_sites.get(label, pl.NT, pl.grid_x);
 #endif
-    if (conv_p_launch(a.ntap, a.ntap2, pl.NT, pl.CO, operand_planes(e->precision), dim3(pl.grid_x, e->Bact), pl.lds, st, a, pl.fmt))
+    if (conv_p_launch(a.ntap, a.ntap2, pl.NT, pl.CO, pl.wpl, dim3(pl.grid_x, e->Bact), pl.lds, st, a, pl.fmt))
         return fail(e, SE_ERR_ARG, "no conv_p kernel instance for %d (+ %d) taps x %d tiles x %d octets", a.ntap, a.ntap2, pl.NT, pl.CO);
     HIPCHECK(e, hipGetLastError());
     return 0;
@@ -441,8 +445,10 @@ int prepare_weights_p(se_engine *e) {
                 auto *nb = param(e, p + "norm.bias", Co);
                 if (!mnw || !mnb || !nw || !nb) return SE_ERR_PARAM_MISSING;
                 SkipPPlan &sk = pv.sk;
-                const int PL = operand_planes(e->precision), C8 = (Co + 7) / 8, MTh = (Co + 31) / 32, KP = (C8 + 1) / 2, Cp = MTh * 32;
+                const int PL = cfmt == PlaneFmt::kF16Pair ? pair_wplanes(e) : operand_planes(e->precision);  // stored weight planes
+                const int C8 = (Co + 7) / 8, MTh = (Co + 31) / 32, KP = (C8 + 1) / 2, Cp = MTh * 32;
                 const int APL = cfmt == PlaneFmt::kF16Pair ? kPairPlanesA : PL;  // planes of res and of the gated output
+                sk.wpl = PL;
                 pv.sk_fmt = cfmt;
                 sk.active = MTh <= 2 && (KP == 1 || KP == 2 || KP == 4);
                 if (sk.active) {
@@ -704,8 +710,8 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
                 a.ydec = S.decR[j].p;
                 a.sy = sy;
                 a.out = reinterpret_cast<uint4 *>(S.decP[j].p);
-                ProfScope ps(e, "k_skip_p", ("skip" + std::to_string(j)).c_str(), pv.sk.flops * B, st);
-                if (launch_k_skip_p(PL, pv.sk.KP, Ba, pv.sk.lds, st, a, pv.sk_fmt)) return fail(e, SE_ERR_ARG, "no k_skip_p instance for %d planes x %d K steps", PL, pv.sk.KP);
+                ProfScope ps(e, pv.sk_fmt == PlaneFmt::kF16Pair && pv.sk.wpl == kPairPlanesW2 ? "k_skip_p_w2" : "k_skip_p", ("skip" + std::to_string(j)).c_str(), pv.sk.flops * B, st);
+                if (launch_k_skip_p(pv.sk.wpl, pv.sk.KP, Ba, pv.sk.lds, st, a, pv.sk_fmt)) return fail(e, SE_ERR_ARG, "no k_skip_p instance for %d planes x %d K steps", PL, pv.sk.KP);
                 HIPCHECK(e, hipGetLastError());
             } else {
             {

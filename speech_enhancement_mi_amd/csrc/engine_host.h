@@ -108,10 +108,12 @@ inline int buffer_planes(int precision, bool pair_on, PlaneBuf kind, bool conv_o
     return buffer_format(precision, pair_on, kind, conv_on) == PlaneFmt::kF16Pair ? kPairPlanesA : operand_planes(precision);
 }
 
-// the fp16-pair planes (2^11 hi, lo, hi) of a [rows][cols] fp32 matrix -> device buffer of 3*rows*cols uint16 (the shape of upload_planes)
-inline int upload_planes_pair(EngineHost *e, DevBuf &b, const std::vector<float> &w) {
-    std::vector<uint16_t> planes((size_t)kPairPlanesW * w.size());
-    pair_weight_matrix(w.data(), w.size(), planes.data());
+// the fp16-pair planes (2^11 hi, lo, hi) of a [rows][cols] fp32 matrix -> device buffer of 3*rows*cols uint16 (the shape of upload_planes);
+// wpl = kPairPlanesW2: the two stored planes (lo, hi), 2*rows*cols uint16
+inline int upload_planes_pair(EngineHost *e, DevBuf &b, const std::vector<float> &w, int wpl = kPairPlanesW) {
+    std::vector<uint16_t> planes((size_t)wpl * w.size());
+    if (wpl == kPairPlanesW2) pair_weight_matrix2(w.data(), w.size(), planes.data());
+    else pair_weight_matrix(w.data(), w.size(), planes.data());
     int rc = dev_alloc(e, b, (planes.size() + 1) / 2);
     if (rc) return rc;
     HIPCHECK(e, hipMemcpy(b.p, planes.data(), planes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));

@@ -323,11 +323,14 @@ __device__ __forceinline__ void gemm_p_rowsum16(float (&v)[16], int l31) {
 // FMT = kF16Pair (split_f16pair.h; PL = 3 is then the WEIGHT plane count): A arrives as the two fp16 planes (hi, lo), W as the three
 // fp16 planes (2^11 hi, lo, hi); three f16 MFMAs per tile pair accumulate 2^11 (a w) and the epilogue scales by 2^-11 ahead of the
 // bias, the activation and the statistics.  The ring stage shrinks from 72 to 56 KB at the same tile.
+// FMT = kF16Pair, PL = 2: the two STORED weight planes (w_lo, w_hi); 2^11 w_hi is formed from the w_hi fragments in registers, once per
+// K step (pair_scale_hi), and goes into the same three MFMAs in the same order - the bits of PL = 3 from a 48 KB stage.
 template <int PL, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     constexpr bool kPair = FMT == PlaneFmt::kF16Pair;
-    static_assert(!kPair || PL == kPairPlanesW, "the fp16 pair has three weight planes");
+    static_assert(!kPair || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair has three weight planes, or two stored ones");
+    constexpr bool kPairW2 = kPair && PL == kPairPlanesW2;
     constexpr int PA = kPair ? kPairPlanesA : PL, PW = PL;  // planes of A / W
     extern __shared__ __align__(16) uint4 gl[];  // [stage 2]{A [PA][256 rows][4 pieces], W [PW][128 rows][4 pieces]}
     constexpr int kPieces = 1024 * PA + 512 * PW;  // uint4 per chunk
@@ -412,8 +415,10 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
             for (int jj = 0; jj < 2; jj++) {
                 f32x16 c = acc[i][jj];
                 if (kPair) {  // smallest terms first, as below
-                    const f16x8g a0 = __builtin_bit_cast(f16x8g, fa[i][0]), a1 = __builtin_bit_cast(f16x8g, fa[i][P1]);
-                    const f16x8g b0 = __builtin_bit_cast(f16x8g, fb[jj][0]), b1 = __builtin_bit_cast(f16x8g, fb[jj][P1]), b2 = __builtin_bit_cast(f16x8g, fb[jj][P2]);
+                    // (kPairW2: the stored planes are (w_lo, w_hi) and slot 2 holds the 2^11 w_hi made from the second)
+                    const f16x8g a0 = __builtin_bit_cast(f16x8g, fa[i][0]), a1 = __builtin_bit_cast(f16x8g, fa[i][1]);
+                    const f16x8g b0 = __builtin_bit_cast(f16x8g, fb[jj][kPairW2 ? 2 : 0]), b1 = __builtin_bit_cast(f16x8g, fb[jj][kPairW2 ? 0 : 1]),
+                                 b2 = __builtin_bit_cast(f16x8g, fb[jj][kPairW2 ? 1 : 2]);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, c, 0, 0, 0);
@@ -462,7 +467,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
 #define SE_GEMMP_WAIT(CNT, fa, fb)                                                                                             \
     if constexpr (PL == 1)                                                                                                     \
         asm volatile("s_waitcnt lgkmcnt(" #CNT ")" : "+v"(fa[0][0]), "+v"(fa[1][0]), "+v"(fb[0][0]), "+v"(fb[1][0]));          \
-    else if constexpr (PL == 2)                                                                                                \
+    else if constexpr (PL == 2) /* (two bf16 planes, or the pair's two stored weight planes: the same eight fragments) */      \
         asm volatile("s_waitcnt lgkmcnt(" #CNT ")"                                                                             \
                      : "+v"(fa[0][0]), "+v"(fa[1][0]), "+v"(fb[0][0]), "+v"(fb[1][0]), "+v"(fa[0][1]), "+v"(fa[1][1]),         \
                        "+v"(fb[0][1]), "+v"(fb[1][1]));                                                                        \
@@ -479,6 +484,8 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         const int buf = kc & 1;
         // chunk kc has landed; after the barrier every wave has also finished reading chunk kc - 1, whose stage chunk kc + 1
         // goes into.  The request is unconditional (past the end it re-requests the last chunk into the stage nobody reads).
+        // (A third stage fits the two-plane pair's 48 KB stages - chunk kc + 2 requested here, vmcnt(kNA + kNW) left in flight - and
+        // was measured: 1.3 % per launch alone and a slower pipelined step, DESIGN.md 4 round 10.  Two stages stay.)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         stage(buf ^ 1, min(kc + 1, nk - 1));
@@ -488,9 +495,11 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         SE_GEMMP_READ(fa0, fb0, 0, sb)
         SE_GEMMP_READ(fa1, fb1, 1, sb)
         if constexpr (PL == 1) { SE_GEMMP_WAIT(4, fa0, fb0); } else if constexpr (PL == 2) { SE_GEMMP_WAIT(8, fa0, fb0); } else if constexpr (kPair) { SE_GEMMP_WAIT(10, fa0, fb0); } else { SE_GEMMP_WAIT(12, fa0, fb0); }
+        if constexpr (kPairW2) { fb0[0][2] = pair_scale_hi(fb0[0][1]); fb0[1][2] = pair_scale_hi(fb0[1][1]); }
         multiply(fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);  // keep the first K step's MFMAs above the second wait
         SE_GEMMP_WAIT(0, fa1, fb1);
+        if constexpr (kPairW2) { fb1[0][2] = pair_scale_hi(fb1[0][1]); fb1[1][2] = pair_scale_hi(fb1[1][1]); }
         multiply(fa1, fb1);
 #else
         (void)sb; (void)multiply;
@@ -845,10 +854,16 @@ struct GruSplitMulti { GruSplitArgs a[4]; };
 // PAIR: the fp16 pair format (split_f16pair.h) - two A planes from `hp` (at t = 0 split2h on the fly, which gives the bits the previous
 // epilogue would have stored), W_hh packed as (2^11 hi, lo, hi) fp16 fragments in the same image, three f16 MFMAs per gate, the
 // 2^-11 applied to the reduced sums ahead of the bias, h_t stored as two planes.  Same split-K reduction order.
-template <int MT, int PF, bool PAIR = false>
+// WPL = 2 (PAIR only): W_hh packed with the two stored planes (w_lo, w_hi) per gate - six fragments per k step instead of nine; 2^11 w_hi
+// is made from the w_hi fragment when the slot is multiplied (pair_scale_hi), so the MFMAs see the operands of WPL = 3.
+// Measured at B = 256, H = 512: 9.73 us per single-layer launch alone against 10.38 with nine fragments; with the
+// smaller ring PF = 2 is 119 VGPRs, PF = 3 151 and PF = 4 183 - 9.87 and 9.95 us alone, no gain in the pipelined step - so PF = 2 stays.
+template <int MT, int PF, bool PAIR = false, int WPL = 3>
 __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    static_assert(WPL == 3 || (PAIR && WPL == kPairPlanesW2), "three weight planes, or the fp16 pair's two stored ones");
     constexpr int NA = PAIR ? kPairPlanesA : 3;  // A planes
+    constexpr int NWF = 3 * WPL;                 // W fragments per k step
     __shared__ float red[4][3][MT * 4][64];  // [source wave][destination wave, the source left out][register][lane]
     const GruStepArgs &a = ga.s;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -885,15 +900,15 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
 #pragma unroll
         for (int p = 0; p < NA; p++) abase[mt][p] = planes ? pb + p * a.seqp_plane * 2 : fb + (p ? 16 : 0);
     }
-    const uint4 *wp = ga.whp + (long)blockIdx.x * KS * 9 * 64 + lane;
-    u32x4 qa[PF][MT][NA], qw[PF][9];
+    const uint4 *wp = ga.whp + (long)blockIdx.x * KS * NWF * 64 + lane;
+    u32x4 qa[PF][MT][NA], qw[PF][NWF];
     auto request = [&](int i, int ks) {
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int p = 0; p < NA; p++) qa[i][mt][p] = *reinterpret_cast<const u32x4 *>(abase[mt][p] + ks * astride);
 #pragma unroll
-        for (int f = 0; f < 9; f++) qw[i][f] = *reinterpret_cast<const u32x4 *>(wp + ((long)ks * 9 + f) * 64);
+        for (int f = 0; f < NWF; f++) qw[i][f] = *reinterpret_cast<const u32x4 *>(wp + ((long)ks * NWF + f) * 64);
     };
     f32x16 acc[MT][3];
 #pragma unroll
@@ -944,13 +959,19 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
 #pragma unroll
                 for (int p = 0; p < NA; p++) ca[mt][p] &= keep;
             }
+            u32x4 w0[3];  // WPL = 2: 2^11 w_hi of the three gates, once per k step (dead otherwise)
+            if constexpr (WPL == 2) {
+#pragma unroll
+                for (int g = 0; g < 3; g++) w0[g] = pair_scale_hi(qw[i][g * 2 + 1]);
+            }
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
                 if constexpr (PAIR) {
                     const f16x8g a0 = __builtin_bit_cast(f16x8g, ca[mt][0]), a1 = __builtin_bit_cast(f16x8g, ca[mt][1]);
 #pragma unroll
                     for (int g = 0; g < 3; g++) {
-                        const f16x8g b0 = __builtin_bit_cast(f16x8g, qw[i][g * 3]), b1 = __builtin_bit_cast(f16x8g, qw[i][g * 3 + 1]), b2 = __builtin_bit_cast(f16x8g, qw[i][g * 3 + 2]);
+                        const f16x8g b0 = __builtin_bit_cast(f16x8g, WPL == 2 ? w0[g] : qw[i][g * WPL]), b1 = __builtin_bit_cast(f16x8g, qw[i][g * WPL + (WPL == 2 ? 0 : 1)]),
+                                     b2 = __builtin_bit_cast(f16x8g, qw[i][g * WPL + WPL - 1]);
                         f32x16 c = acc[mt][g];
                         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, c, 0, 0, 0);
                         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, c, 0, 0, 0);
@@ -961,7 +982,7 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
                     const bf16x8 a0 = __builtin_bit_cast(bf16x8, ca[mt][0]), a1 = __builtin_bit_cast(bf16x8, ca[mt][1]), a2 = __builtin_bit_cast(bf16x8, ca[mt][NA - 1]);
 #pragma unroll
                     for (int g = 0; g < 3; g++) {
-                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, qw[i][g * 3]), b1 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 1]), b2 = __builtin_bit_cast(bf16x8, qw[i][g * 3 + 2]);
+                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, qw[i][g * WPL]), b1 = __builtin_bit_cast(bf16x8, qw[i][g * WPL + 1]), b2 = __builtin_bit_cast(bf16x8, qw[i][g * WPL + WPL - 1]);
                         f32x16 c = acc[mt][g];
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
@@ -1051,9 +1072,9 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
         }
 }
 
-template <int MT, int PF, bool PAIR = false>
-__global__ __launch_bounds__(256) void k_gru_step_split(GruSplitArgs a) { gru_split_body<MT, PF, PAIR>(a); }
-template <int MT, int PF, bool PAIR = false>
-__global__ __launch_bounds__(256) void k_gru_step_split_multi(GruSplitMulti m) { gru_split_body<MT, PF, PAIR>(m.a[blockIdx.z]); }
+template <int MT, int PF, bool PAIR = false, int WPL = 3>
+__global__ __launch_bounds__(256) void k_gru_step_split(GruSplitArgs a) { gru_split_body<MT, PF, PAIR, WPL>(a); }
+template <int MT, int PF, bool PAIR = false, int WPL = 3>
+__global__ __launch_bounds__(256) void k_gru_step_split_multi(GruSplitMulti m) { gru_split_body<MT, PF, PAIR, WPL>(m.a[blockIdx.z]); }
 
 }  // namespace se

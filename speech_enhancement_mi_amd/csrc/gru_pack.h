@@ -29,14 +29,15 @@ inline float gru_pack_bf16_f32(uint16_t h) {
     return f;
 }
 
-// position (in bf16 elements) of plane `pl` of W_hh[gate * H + n][k] in the packed image
-inline size_t gru_pack_index(int H, int gate, int n, int k, int pl) {
-    const size_t frag = (((size_t)(n >> 5) * (H >> 4) + (k >> 4)) * 3 + gate) * 3 + pl;
+// position (in bf16 elements) of plane `pl` of W_hh[gate * H + n][k] in the packed image; NP = stored planes per gate (three, or the
+// two of gru_pack_whh_pair2: six fragments per k step)
+inline size_t gru_pack_index(int H, int gate, int n, int k, int pl, int NP = 3) {
+    const size_t frag = (((size_t)(n >> 5) * (H >> 4) + (k >> 4)) * 3 + gate) * NP + pl;
     const int lane = 32 * ((k >> 3) & 1) + (n & 31);
     return (frag * 64 + lane) * 8 + (k & 7);
 }
 
-inline size_t gru_pack_size(int H) { return (size_t)9 * H * H; }  // bf16 elements
+inline size_t gru_pack_size(int H, int NP = 3) { return (size_t)3 * NP * H * H; }  // bf16 elements
 
 inline void gru_pack_whh(const float *whh, int H, std::vector<uint16_t> &out) {
     out.assign(gru_pack_size(H), 0);
@@ -63,6 +64,18 @@ inline void gru_pack_whh_pair(const float *whh, int H, std::vector<uint16_t> &ou
                 uint16_t p[3];
                 pair_weight_planes(whh[((size_t)g * H + n) * H + k], p);
                 for (int pl = 0; pl < 3; pl++) out[gru_pack_index(H, g, n, k, pl)] = p[pl];
+            }
+}
+
+// the pair image with the two STORED planes (split_f16pair.h: pair_weight_planes2): slots 0, 1 of every gate hold (lo, hi)
+inline void gru_pack_whh_pair2(const float *whh, int H, std::vector<uint16_t> &out) {
+    out.assign(gru_pack_size(H, kPairPlanesW2), 0);
+    for (int g = 0; g < 3; g++)
+        for (int n = 0; n < H; n++)
+            for (int k = 0; k < H; k++) {
+                uint16_t p[2];
+                pair_weight_planes2(whh[((size_t)g * H + n) * H + k], p);
+                for (int pl = 0; pl < 2; pl++) out[gru_pack_index(H, g, n, k, pl, kPairPlanesW2)] = p[pl];
             }
 }
 

@@ -59,13 +59,19 @@ int SE_FN(conv_p_launch_pl)(int ntap2, int NT, int CO, dim3 grid, size_t lds, hi
 
 // The fp16 pair form (k_conv_p<.., kF16Pair>: two activation planes, three f16 MFMA terms) rides in the PL = 3 units of the tap counts
 // the CRN path runs: 15, 9 (+ 6: both parities), 6 and 1.  The 25-tap pre-conv blocks belong to CRN_ELU / the student: no pair form.
-#if SE_CP_PL == 3 && SE_CP_NTAP != 25
+// The same instances with the two STORED weight planes (k_conv_p<.., PL = 2, .., kF16Pair>: 2^11 w_hi made in registers) ride in the
+// PL = 2 units, which keeps the units' build times level.  (SE_PAIR_W3=1 keeps the three-plane instances.)
+#if (SE_CP_PL == 3 || SE_CP_PL == 2) && SE_CP_NTAP != 25
+#if SE_CP_PL == 3
 #define SE_FNP(name) SE_CAT4(name, _pair, _t, SE_CP_NTAP)
+#else
+#define SE_FNP(name) SE_CAT4(name, _pair2, _t, SE_CP_NTAP)
+#endif
 int SE_FNP(conv_p_launch)(int ntap2, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a) {
 #define SE_CP_CASE(NT_, CO_) \
-    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, 3, 0, PlaneFmt::kF16Pair>), grid, dim3(256), lds, st, a); return 0;
+    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL, 0, PlaneFmt::kF16Pair>), grid, dim3(256), lds, st, a); return 0;
 #define SE_CP_CASE2(NT_, CO_) \
-    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, 3, SE_CP_NTAP2, PlaneFmt::kF16Pair>), grid, dim3(256), lds, st, a); return 0;
+    case NT_ * 8 + CO_: hipLaunchKernelGGL((k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL, SE_CP_NTAP2, PlaneFmt::kF16Pair>), grid, dim3(256), lds, st, a); return 0;
     if (ntap2 == 0) {
         switch (NT * 8 + CO) {
             SE_CP_ALL(SE_CP_CASE)
@@ -83,9 +89,9 @@ int SE_FNP(conv_p_launch)(int ntap2, int NT, int CO, dim3 grid, size_t lds, hipS
 
 void SE_FNP(conv_p_set_attributes)() {
 #define SE_CP_ATTR(NT_, CO_) \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, 3, 0, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL, 0, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #define SE_CP_ATTR2(NT_, CO_) \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, 3, SE_CP_NTAP2, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_p<SE_CP_NTAP, NT_, CO_, SE_CP_PL, SE_CP_NTAP2, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     SE_CP_ALL(SE_CP_ATTR)
     SE_CP_PAIR(SE_CP_ATTR2)
 #undef SE_CP_ATTR

@@ -14,13 +14,15 @@ SE_DECL3(25) SE_DECL3(15) SE_DECL3(9) SE_DECL3(6) SE_DECL3(1)
 
 #define SE_DECLP(NT_)                                                                                                  \
     int conv_p_launch_pair_t##NT_(int ntap2, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a); \
-    void conv_p_set_attributes_pair_t##NT_();
+    void conv_p_set_attributes_pair_t##NT_();                                                                          \
+    int conv_p_launch_pair2_t##NT_(int ntap2, int NT, int CO, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a); \
+    void conv_p_set_attributes_pair2_t##NT_();
 SE_DECLP(15) SE_DECLP(9) SE_DECLP(6) SE_DECLP(1)
 
 int conv_p_launch(int ntap, int ntap2, int NT, int CO, int PL, dim3 grid, size_t lds, hipStream_t st, const ConvPArgs &a, PlaneFmt fmt) {
-    if (fmt == PlaneFmt::kF16Pair) {  // (PL = 3 weight planes; the instances of se_convp.hip's pair section)
+    if (fmt == PlaneFmt::kF16Pair) {  // (PL = the STORED weight planes, 2 or 3; the instances of se_convp.hip's pair section)
 #define SE_ROUTEP(NT_) \
-    if (ntap == NT_) return conv_p_launch_pair_t##NT_(ntap2, NT, CO, grid, lds, st, a);
+    if (ntap == NT_) return PL == kPairPlanesW2 ? conv_p_launch_pair2_t##NT_(ntap2, NT, CO, grid, lds, st, a) : conv_p_launch_pair_t##NT_(ntap2, NT, CO, grid, lds, st, a);
         SE_ROUTEP(15) SE_ROUTEP(9) SE_ROUTEP(6) SE_ROUTEP(1)
         return 1;
     }
@@ -45,6 +47,7 @@ void conv_p_set_attributes() {
 #define SE_ATTR3(NT_) SE_ATTR(1, NT_) SE_ATTR(2, NT_) SE_ATTR(3, NT_)
     SE_ATTR3(25) SE_ATTR3(15) SE_ATTR3(9) SE_ATTR3(6) SE_ATTR3(1)
     conv_p_set_attributes_pair_t15(); conv_p_set_attributes_pair_t9(); conv_p_set_attributes_pair_t6(); conv_p_set_attributes_pair_t1();
+    conv_p_set_attributes_pair2_t15(); conv_p_set_attributes_pair2_t9(); conv_p_set_attributes_pair2_t6(); conv_p_set_attributes_pair2_t1();
 }
 
 }  // namespace se

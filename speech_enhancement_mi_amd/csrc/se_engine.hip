@@ -148,6 +148,8 @@ struct se_engine : EngineHost {
     int f16_pair = 1;         // SE_F16_PAIR=0: the bf16 route (three planes, six terms) everywhere
     int f16_pair_conv = 1;    // SE_F16_PAIR_CONV=0: the pair on the bottleneck only; xinP[i >= 1], decinP, decP and their kernels on bf16 planes
     bool pair_on = false;     // decided once per weight load (f16_pair_decide): knob, eligibility and the range guard
+    int pair_w3 = 0;          // SE_PAIR_W3=1: pair weights as the three stored planes (2^11 hi, lo, hi) and the kernels' three-plane instances;
+                              // default: two stored planes (lo, hi), 2^11 hi made in registers - the same bits from fewer weight bytes
     DevBuf wih_h[4];          // W_ih of layers >= 1 as pair planes (wih_x[l] stays bf16: the fp32-row GEMMs of small batches read it)
     // fc_output_layer + gLN(last) on the plane GEMM route: weight rows, bias and the norm's per-element affine permuted like W_ih0's
     // K axis, so that fc_out column (o * F + f) * 8 + c holds reference feature (8 o + c) * F + f (channels padded to whole octets
@@ -171,6 +173,8 @@ namespace {
 PlaneFmt act_format(const se_engine *e, PlaneBuf kind) { return buffer_format(e->precision, e->pair_on, kind, e->f16_pair_conv != 0); }
 int act_planes(const se_engine *e, PlaneBuf kind) { return buffer_planes(e->precision, e->pair_on, kind, e->f16_pair_conv != 0); }
 PlaneBuf xin_kind(int level) { return level == 0 ? PlaneBuf::kFeature : PlaneBuf::kConvAct; }
+// stored planes of a weight in the fp16 pair format (split_f16pair.h)
+int pair_wplanes(const se_engine *e) { return e->pair_w3 ? kPairPlanesW : kPairPlanesW2; }
 
 int prof_label(se_engine *e, const char *kernel, const std::string &label, double flops) {
     for (size_t i = 0; i < e->prof_labels.size(); i++)
@@ -546,10 +550,11 @@ int prepare_weights(se_engine *e) {
         if ((rc = dev_upload(e, e->wih[l], *a)) || (rc = dev_upload(e, e->whh[l], *b)) ||
             (rc = dev_upload(e, e->bih[l], *c)) || (rc = dev_upload(e, e->bhh[l], *d)))
             return rc;
-        if (e->pair_on && l > 0 && (rc = upload_planes_pair(e, e->wih_h[l], *a))) return rc;
+        if (e->pair_on && l > 0 && (rc = upload_planes_pair(e, e->wih_h[l], *a, pair_wplanes(e)))) return rc;
         if (e->precision == 0 && H % 32 == 0) {
             std::vector<uint16_t> pk;
-            if (e->pair_on) gru_pack_whh_pair(b->data(), H, pk);
+            if (e->pair_on && !e->pair_w3) gru_pack_whh_pair2(b->data(), H, pk);
+            else if (e->pair_on) gru_pack_whh_pair(b->data(), H, pk);
             else gru_pack_whh(b->data(), H, pk);
             if ((rc = dev_alloc(e, e->whh_p[l], pk.size() / 2))) return rc;
             HIPCHECK(e, hipMemcpy(e->whh_p[l].p, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -643,10 +648,12 @@ int launch_gemm(se_engine *e, const float *A, long lda, const float *W, long ldw
 // C = act(A W^T + bias) with both operands as split-bf16 planes ([PL][rows][K] bf16, K % 32 == 0): k_gemm_p
 int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *bias, float *C, long ldc, int Mr, int Nc, int Kd, int relu,
                   hipStream_t st, const char *label, float *stats = nullptr) {
-    // every plane GEMM is a bottleneck GEMM: A is gruinP or seqP (kGemmA), W the matching weight planes (three in both formats at precision 0)
-    const int PL = operand_planes(e->precision), PA = buffer_planes(e->precision, e->pair_on, PlaneBuf::kGemmA);
+    // every plane GEMM is a bottleneck GEMM: A is gruinP or seqP (kGemmA), W the matching weight planes (the pair's stored planes: two, or three
+    // under SE_PAIR_W3)
     const bool pair = buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA) == PlaneFmt::kF16Pair;
-    ProfScope ps(e, "k_gemm_p", label, 2.0 * Mr * Nc * Kd, st);
+    const int PL = pair ? pair_wplanes(e) : operand_planes(e->precision), PA = buffer_planes(e->precision, e->pair_on, PlaneBuf::kGemmA);
+    // (the profile record names the instance: "_w2" = the pair's two stored weight planes; tests tell the routes apart by it)
+    ProfScope ps(e, pair && PL == kPairPlanesW2 ? "k_gemm_p_w2" : "k_gemm_p", label, 2.0 * Mr * Nc * Kd, st);
     const int nrt = (Mr + kGemmPBM - 1) / kGemmPBM, nct = (Nc + kGemmPBN - 1) / kGemmPBN;
     // XCD blocks: the split of the tile grid into 8 equal blocks (gx x gy) that fetches the fewest bytes into the 8 private
     // L2s - every row tile of A is fetched by the gy XCDs of its block row, every column tile of W by gx
@@ -671,7 +678,8 @@ int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *b
                 (unsigned)((size_t)PA * Ma * Kd * 2), (unsigned)((size_t)PL * Nc * Kd * 2), nrt, nct, gx, gy, stats};
     const dim3 grid(nblocks);
     const size_t lds = (size_t)2 * (1024 * PA + 512 * PL) * 16;
-    if (pair) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
+    if (pair && PL == kPairPlanesW2) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
+    else if (pair) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
     else if (PL == 1) hipLaunchKernelGGL(k_gemm_p<1>, grid, dim3(512), lds, st, g);
     else if (PL == 2) hipLaunchKernelGGL(k_gemm_p<2>, grid, dim3(512), lds, st, g);
     else hipLaunchKernelGGL(k_gemm_p<3>, grid, dim3(512), lds, st, g);
@@ -765,11 +773,13 @@ bool gru_split_on(const se_engine *e, bool overlapped) {
 }
 // (32 streams per workgroup, two k steps in flight per wave: the variant that won in the pipelined step, gemm.hip.h)
 void launch_gru_split(se_engine *e, const GruSplitArgs &g, int rows, hipStream_t st) {
-    if (e->pair_on) hipLaunchKernelGGL((k_gru_step_split<1, 2, true>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
+    if (e->pair_on && !e->pair_w3) hipLaunchKernelGGL((k_gru_step_split<1, 2, true, kPairPlanesW2>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
+    else if (e->pair_on) hipLaunchKernelGGL((k_gru_step_split<1, 2, true>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
     else hipLaunchKernelGGL((k_gru_step_split<1, 2>), dim3(e->H / 32, (rows + 31) / 32), dim3(256), 0, st, g);
 }
 void launch_gru_split_multi(se_engine *e, const GruSplitMulti &m, int rows, int z, hipStream_t st) {
-    if (e->pair_on) hipLaunchKernelGGL((k_gru_step_split_multi<1, 2, true>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
+    if (e->pair_on && !e->pair_w3) hipLaunchKernelGGL((k_gru_step_split_multi<1, 2, true, kPairPlanesW2>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
+    else if (e->pair_on) hipLaunchKernelGGL((k_gru_step_split_multi<1, 2, true>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
     else hipLaunchKernelGGL((k_gru_step_split_multi<1, 2>), dim3(e->H / 32, (rows + 31) / 32, z), dim3(256), 0, st, m);
 }
 
@@ -796,7 +806,7 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
             g.seqp_ld = (long)T * H; g.seqp_plane = (long)B * T * H; set_seqp_format(e, g);
         }
         if (split) {
-            ProfScope ps(e, "k_gru_step_split", "gru_step", 2.0 * B * 3 * H * H, st);
+            ProfScope ps(e, e->pair_on && !e->pair_w3 ? "k_gru_step_split_w2" : "k_gru_step_split", "gru_step", 2.0 * B * 3 * H * H, st);
             launch_gru_split(e, GruSplitArgs{g, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? g.seqp - H : nullptr}, Ba, st);
             e->hcur[l] = hc ^ 1;
             continue;
@@ -858,7 +868,7 @@ int stage_gru_round(se_engine *e, const int *slots, hipStream_t st) {
             if (split) ms.a[z - 1] = GruSplitArgs{ga, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? ga.seqp - H : nullptr};
         }
         if (split) {
-            ProfScope ps(e, "k_gru_step_split_multi", "gru_step", 2.0 * B * 3 * H * H * z, st);
+            ProfScope ps(e, e->pair_on && !e->pair_w3 ? "k_gru_step_split_multi_w2" : "k_gru_step_split_multi", "gru_step", 2.0 * B * 3 * H * H * z, st);
             launch_gru_split_multi(e, ms, bmax, z, st);
             continue;
         }
@@ -974,7 +984,7 @@ int ensure_ready(se_engine *e) {
                     const int cabs = d / Fl, f = d - cabs * Fl;
                     wp[(size_t)r * D + ((size_t)(cabs >> 3) * Fl + f) * 8 + (cabs & 7)] = w[(size_t)r * D + d];
                 }
-            if ((rc = e->pair_on ? upload_planes_pair(e, e->wih_xp, wp) : upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
+            if ((rc = e->pair_on ? upload_planes_pair(e, e->wih_xp, wp, pair_wplanes(e)) : upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
             // fc_output_layer rows, its bias and the affine of the norm behind it in the same order (each dot product is unchanged;
             // only where it lands changes), channels padded to whole octets with zero rows.  (gemm_p_cap above asks for whole
             // octets, so today ND == D and no padding row exists; the padding is what a relaxed cap would need, and is untested)
@@ -988,7 +998,7 @@ int ensure_ready(se_engine *e) {
                 std::copy(fw.begin() + (size_t)d * H, fw.begin() + (size_t)(d + 1) * H, fwp.begin() + dp * H);
                 fbp[dp] = fb[d]; nwp[dp] = nw[d]; nbp[dp] = nb[d];
             }
-            if ((rc = e->pair_on ? upload_planes_pair(e, e->fcw_xp, fwp) : upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
+            if ((rc = e->pair_on ? upload_planes_pair(e, e->fcw_xp, fwp, pair_wplanes(e)) : upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
                 (rc = dev_upload(e, e->gnb_p, nbp)))
                 return rc;
         }
@@ -1138,6 +1148,7 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (const char *s = getenv("SE_GRU_SPLIT")) e->gru_split = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_F16_PAIR")) e->f16_pair = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_F16_PAIR_CONV")) e->f16_pair_conv = atoi(s) != 0 ? 1 : 0;
+    if (const char *s = getenv("SE_PAIR_W3")) e->pair_w3 = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
     if (const char *s = getenv("SE_DBG_SKIP")) { e->dbg_skip = atoi(s); fprintf(stderr, "se_engine: SE_DBG_SKIP=%d - stages are skipped, results are WRONG (timing experiment)\n", e->dbg_skip); }
@@ -1163,6 +1174,8 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 1536 * 3 * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               2 * (1024 * kPairPlanesA + 512 * kPairPlanesW) * 16);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              2 * (1024 * kPairPlanesA + 512 * kPairPlanesW2) * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 512);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 128);
     *out = e;

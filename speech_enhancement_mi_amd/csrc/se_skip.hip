@@ -13,10 +13,12 @@ namespace se {
 #define SE_SK_NW(PL_, KP_) (KP_ * PL_ <= 4 ? 16 : 8)
 
 int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, PlaneFmt fmt) {
-#define SE_SKP(KP_) \
-    if (KP == KP_) { hipLaunchKernelGGL((k_skip_p<kPairPlanesW, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), dim3(batch), dim3(SE_SK_NW(kPairPlanesW, KP_) * 64), lds, st, a); return 0; }
+    // (the two-stored-plane instances keep the wave count of the three-plane ones: they hold the same three weight operands per K step)
+#define SE_SKP(WPL_, KP_) \
+    if (PL == WPL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_p<WPL_, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), dim3(batch), dim3(SE_SK_NW(kPairPlanesW, KP_) * 64), lds, st, a); return 0; }
     if (fmt == PlaneFmt::kF16Pair) {
-        SE_SKP(1) SE_SKP(2) SE_SKP(4)
+        SE_SKP(kPairPlanesW, 1) SE_SKP(kPairPlanesW, 2) SE_SKP(kPairPlanesW, 4)
+        SE_SKP(kPairPlanesW2, 1) SE_SKP(kPairPlanesW2, 2) SE_SKP(kPairPlanesW2, 4)
         return 1;
     }
 #define SE_SK(PL_, KP_) \
@@ -30,8 +32,9 @@ void skip_p_set_attributes() {
 #define SE_SKA(PL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<PL_, KP_, SE_SK_NW(PL_, KP_)>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
 #define SE_SKA3(KP_) SE_SKA(1, KP_) SE_SKA(2, KP_) SE_SKA(3, KP_)
     SE_SKA3(1) SE_SKA3(2) SE_SKA3(4)
-#define SE_SKAP(KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<kPairPlanesW, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    SE_SKAP(1) SE_SKAP(2) SE_SKAP(4)
+#define SE_SKAP(WPL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<WPL_, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    SE_SKAP(kPairPlanesW, 1) SE_SKAP(kPairPlanesW, 2) SE_SKAP(kPairPlanesW, 4)
+    SE_SKAP(kPairPlanesW2, 1) SE_SKAP(kPairPlanesW2, 2) SE_SKAP(kPairPlanesW2, 4)
 }
 
 }  // namespace se

@@ -25,11 +25,12 @@ namespace se {
 // (one workgroup per CU), so bytes in flight = waves x fragments in flight decide its rate
 // FMT = kF16Pair (PL = 3 weight planes): res and out are two fp16 planes (split_f16pair.h), the weights (2^11 w_hi, w_lo, w_hi), three f16
 // MFMAs per K step in the fixed order W0 b_hi, W1 b_hi, W2 b_lo, and the 2^-11 (exact) on the accumulators before the statistics of
-// pass 1 and before the gate of pass 2.
+// pass 1 and before the gate of pass 2.  PL = 2 with kF16Pair: the two stored planes (w_lo, w_hi) in LDS, 2^11 w_hi made when the
+// fragment is read (pair_scale_hi) - the same operands from two thirds of the weight bytes.
 template <int PL, int KP, int NW, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
     constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
-    static_assert(!PAIR || PL == kPairPlanesW, "the fp16 pair form has three weight planes");
+    static_assert(!PAIR || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair form has three weight planes, or two stored ones");
     constexpr int APL = PAIR ? kPairPlanesA : PL;  // planes of res and out
     extern __shared__ __align__(16) uint4 wl[];  // [2*MTh][KP][PL][64] weight fragments, then cst[6][Cp] floats
     __shared__ float sm[4];
@@ -69,9 +70,12 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
             if constexpr (PAIR) {
                 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
                 const h8 bh = __builtin_bit_cast(h8, bf[kp][0]), bl = __builtin_bit_cast(h8, bf[kp][APL > 1 ? 1 : 0]);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[0]), bh, c, 0, 0, 0);                  // 2^11 w_hi * x_hi
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[PL > 1 ? 64 : 0]), bh, c, 0, 0, 0);    // w_lo * x_hi
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[PL > 2 ? 128 : 0]), bl, c, 0, 0, 0);   // w_hi * x_lo
+                uint4 w0, w1, w2;
+                if constexpr (PL == kPairPlanesW2) { w1 = wf[0]; w2 = wf[64]; w0 = pair_scale_hi(w2); }
+                else { w0 = wf[0]; w1 = wf[PL > 1 ? 64 : 0]; w2 = wf[PL > 2 ? 128 : 0]; }
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w0), bh, c, 0, 0, 0);  // 2^11 w_hi * x_hi
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w1), bh, c, 0, 0, 0);  // w_lo * x_hi
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w2), bl, c, 0, 0, 0);  // w_hi * x_lo
             } else if (PL >= 2) {
                 const bf16x8 a0 = __builtin_bit_cast(bf16x8, wf[0]), a1 = __builtin_bit_cast(bf16x8, wf[PL > 1 ? 64 : 0]);
                 const bf16x8 b0 = __builtin_bit_cast(bf16x8, bf[kp][0]), b1 = __builtin_bit_cast(bf16x8, bf[kp][PL > 1 ? 1 : 0]);

@@ -115,7 +115,52 @@ inline void pair_weight_matrix(const float *w, size_t n, uint16_t *planes) {
     }
 }
 
+// ---- two STORED weight planes (w_lo, w_hi) ----
+// Plane 0 of the three is 2^11 times plane 2, exact in fp16 wherever it is finite (|w| < 2^4: the guard), subnormals and zeros
+// included.  The kernels' two-plane instances (weight-plane parameter 2) fetch (w_lo, w_hi) and form 2^11 w_hi in registers with one
+// packed fp16 multiply per dword (pair_scale_hi below): the same operand bits into the same MFMAs, a third fewer weight bytes.
+constexpr int kPairPlanesW2 = 2;
+
+// (w_lo, w_hi): planes 1 and 2 of pair_weight_planes
+inline void pair_weight_planes2(float w, uint16_t (&p)[2]) {
+    uint16_t q[3];
+    pair_weight_planes(w, q);
+    p[0] = q[1];
+    p[1] = q[2];
+}
+
+// `parts` of conv_weight_image.h for either stored plane count (slots past `planes` are left alone)
+inline void pair_weight_parts(float w, int planes, uint16_t (&p)[3]) {
+    uint16_t q[3];
+    pair_weight_planes(w, q);
+    if (planes == kPairPlanesW2) { p[0] = q[1]; p[1] = q[2]; }
+    else { p[0] = q[0]; p[1] = q[1]; p[2] = q[2]; }
+}
+
+// a [rows][cols] weight matrix as planes [2][rows][cols] = (w_lo, w_hi)
+inline void pair_weight_matrix2(const float *w, size_t n, uint16_t *planes) {
+    for (size_t i = 0; i < n; i++) {
+        uint16_t p[2];
+        pair_weight_planes2(w[i], p);
+        planes[i] = p[0]; planes[n + i] = p[1];
+    }
+}
+
+// what the device does to one stored w_hi: ONE fp16 multiply by 2^11 (round to nearest even, subnormals kept).  Host form for the
+// tests; the product is exact, so the fp32 route through pair_f16_bits gives the same bits.
+inline uint16_t pair_scale_hi_bits(uint16_t hi) { return pair_f16_bits(pair_f16_value(hi) * kPairScale); }
+
 #if defined(__HIPCC__)
+// 2^11 w_hi from a w_hi fragment (8 fp16 in four dwords): four v_pk_mul_f16.  A multiply, not an exponent add: zeros and
+// subnormals come out right.
+template <class V4 /* four dwords: uint4 or an ext_vector of 4 unsigned */>
+__device__ __forceinline__ V4 pair_scale_hi(const V4 &hi) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    static_assert(sizeof(V4) == 16, "one 16-byte fragment");
+    const h8 v = __builtin_bit_cast(h8, hi) * (_Float16)2048.0f;
+    return __builtin_bit_cast(V4, v);
+}
+
 // fp32 x 8 -> the two planes of one 16-byte piece (8 channels): the pair flavour of split_store8 (conv_p.hip.h)
 __device__ __forceinline__ void split_store8_pair(const float (&v)[8], uint4 *dst, long plane_stride) {
     typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
