@@ -22,7 +22,7 @@ void launch_k_gln2_stream_p(int PL, dim3 grid, hipStream_t st, const Gln2PArgs &
 void launch_k_final_mask_p(dim3 grid, hipStream_t st, const MaskPArgs &a);
 // k_skip_p<PL, KP[, FMT]> (skip_p.hip.h): one workgroup per stream; 0 = launched, 1 = no such instance.  fmt = the format of res and out
 // (kF16Pair: PL = the stored weight planes, 2 or 3)
-int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const struct SkipPArgs &a, PlaneFmt fmt = PlaneFmt::kBf16);
+int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const struct SkipPArgs &a, PlaneFmt fmt = PlaneFmt::kBf16, int depth = 0);
 void skip_p_set_attributes();
 
 }  // namespace se

@@ -711,7 +711,7 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
                 a.sy = sy;
                 a.out = reinterpret_cast<uint4 *>(S.decP[j].p);
                 ProfScope ps(e, pv.sk_fmt == PlaneFmt::kF16Pair && pv.sk.wpl == kPairPlanesW2 ? "k_skip_p_w2" : "k_skip_p", ("skip" + std::to_string(j)).c_str(), pv.sk.flops * B, st);
-                if (launch_k_skip_p(pv.sk.wpl, pv.sk.KP, Ba, pv.sk.lds, st, a, pv.sk_fmt)) return fail(e, SE_ERR_ARG, "no k_skip_p instance for %d planes x %d K steps", PL, pv.sk.KP);
+                if (launch_k_skip_p(pv.sk.wpl, pv.sk.KP, Ba, pv.sk.lds, st, a, pv.sk_fmt, e->skip_depth)) return fail(e, SE_ERR_ARG, "no k_skip_p instance for %d planes x %d K steps", PL, pv.sk.KP);
                 HIPCHECK(e, hipGetLastError());
             } else {
             {

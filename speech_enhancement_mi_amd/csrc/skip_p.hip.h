@@ -20,6 +20,48 @@
 
 namespace se {
 
+// one 32-row M tile `mt` of the 1x1 convolutions on the B fragments of one position tile (K steps x planes), weights from LDS
+template <int PL, int KP, PlaneFmt FMT, int APL>
+__device__ __forceinline__ f32x16 skip_mma_tile(const uint4 *wl, int mt, const uint4 (&bf)[KP][APL], int l31, int half) {
+    constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
+    f32x16 c;
+#pragma unroll
+    for (int r = 0; r < 16; r++) c[r] = 0.0f;
+#pragma unroll
+    for (int kp = 0; kp < KP; kp++) {
+        const uint4 *wf = wl + ((long)(mt * KP + kp) * PL) * 64 + l31 * 2 + half;
+        if constexpr (PAIR) {
+            typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+            const h8 bh = __builtin_bit_cast(h8, bf[kp][0]), bl = __builtin_bit_cast(h8, bf[kp][APL > 1 ? 1 : 0]);
+            uint4 w0, w1, w2;
+            if constexpr (PL == kPairPlanesW2) { w1 = wf[0]; w2 = wf[64]; w0 = pair_scale_hi(w2); }
+            else { w0 = wf[0]; w1 = wf[PL > 1 ? 64 : 0]; w2 = wf[PL > 2 ? 128 : 0]; }
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w0), bh, c, 0, 0, 0);  // 2^11 w_hi * x_hi
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w1), bh, c, 0, 0, 0);  // w_lo * x_hi
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w2), bl, c, 0, 0, 0);  // w_hi * x_lo
+        } else if (PL >= 2) {
+            const bf16x8 a0 = __builtin_bit_cast(bf16x8, wf[0]), a1 = __builtin_bit_cast(bf16x8, wf[PL > 1 ? 64 : 0]);
+            const bf16x8 b0 = __builtin_bit_cast(bf16x8, bf[kp][0]), b1 = __builtin_bit_cast(bf16x8, bf[kp][PL > 1 ? 1 : 0]);
+            if (PL == 3) {
+                const bf16x8 a2 = __builtin_bit_cast(bf16x8, wf[PL > 2 ? 128 : 0]), b2 = __builtin_bit_cast(bf16x8, bf[kp][PL > 2 ? 2 : 0]);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);
+            }
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
+        } else {
+            typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[0]), __builtin_bit_cast(h8, bf[kp][0]), c, 0, 0, 0);
+        }
+    }
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) c[r] *= kPairInvScale;
+    }
+    return c;
+}
 
 // NW = waves per workgroup: 16 (1024 threads, 128 VGPRs) for KP <= 2, 8 for KP = 4 - the kernel is a latency-bound stream
 // (one workgroup per CU), so bytes in flight = waves x fragments in flight decide its rate
@@ -60,45 +102,7 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
             for (int pl = 0; pl < APL; pl++) bf[kp][pl] = xb[((long)o * APL + pl) * plane + p];
         }
     };
-    auto mma_tile = [&](int mt, const uint4 (&bf)[KP][APL]) {
-        f32x16 c;
-#pragma unroll
-        for (int r = 0; r < 16; r++) c[r] = 0.0f;
-#pragma unroll
-        for (int kp = 0; kp < KP; kp++) {
-            const uint4 *wf = wl + ((long)(mt * KP + kp) * PL) * 64 + l31 * 2 + half;
-            if constexpr (PAIR) {
-                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                const h8 bh = __builtin_bit_cast(h8, bf[kp][0]), bl = __builtin_bit_cast(h8, bf[kp][APL > 1 ? 1 : 0]);
-                uint4 w0, w1, w2;
-                if constexpr (PL == kPairPlanesW2) { w1 = wf[0]; w2 = wf[64]; w0 = pair_scale_hi(w2); }
-                else { w0 = wf[0]; w1 = wf[PL > 1 ? 64 : 0]; w2 = wf[PL > 2 ? 128 : 0]; }
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w0), bh, c, 0, 0, 0);  // 2^11 w_hi * x_hi
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w1), bh, c, 0, 0, 0);  // w_lo * x_hi
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, w2), bl, c, 0, 0, 0);  // w_hi * x_lo
-            } else if (PL >= 2) {
-                const bf16x8 a0 = __builtin_bit_cast(bf16x8, wf[0]), a1 = __builtin_bit_cast(bf16x8, wf[PL > 1 ? 64 : 0]);
-                const bf16x8 b0 = __builtin_bit_cast(bf16x8, bf[kp][0]), b1 = __builtin_bit_cast(bf16x8, bf[kp][PL > 1 ? 1 : 0]);
-                if (PL == 3) {
-                    const bf16x8 a2 = __builtin_bit_cast(bf16x8, wf[PL > 2 ? 128 : 0]), b2 = __builtin_bit_cast(bf16x8, bf[kp][PL > 2 ? 2 : 0]);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);
-                }
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
-            } else {
-                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, wf[0]), __builtin_bit_cast(h8, bf[kp][0]), c, 0, 0, 0);
-            }
-        }
-        if constexpr (PAIR) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) c[r] *= kPairInvScale;
-        }
-        return c;
-    };
+    auto mma_tile = [&](int mt, const uint4 (&bf)[KP][APL]) { return skip_mma_tile<PL, KP, FMT, APL>(wl, mt, bf, l31, half); };
     // wl fragment layout per (mt, kp, plane): 64 uint4 = [row 32][k half 2]; lane (row l31, half) reads l31*2 + half
 
     // ---- pass 1: statistics of residualmask(res) ----
@@ -187,6 +191,217 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
         for (int kp = 0; kp < KP; kp++)
 #pragma unroll
             for (int pl = 0; pl < APL; pl++) bcur[kp][pl] = bnxt[kp][pl];
+    }
+}
+
+// ---- the batched form ------------------------------------------------------------------------------------------------------------
+// k_skip_p exposes one memory round trip per tile and pass (a wave owns 3 to 6 tiles at the headline shapes, a few dozen MFMAs each:
+// the one-ahead prefetch hides nothing), more for the deconvolution values that pass 2 loads where it uses them, and reads res twice.
+// k_skip_pd computes the same sums in the same order and changes only WHEN loads are issued:
+//     - a wave takes its tiles (wave, wave + NW, ...) in batches of up to DEPTH; all B fragments of a batch are requested before
+//       its first MFMA, the first batch before the weight copy and the statistics slab (one round trip for all three)
+//     - where every wave's share fits one batch, the fragments stay in registers across the workgroup reduction and
+//       pass 2 does not read res again; otherwise pass 2 requests its first batch before the reduction and goes on in batches
+//     - pass 2 requests the deconvolution values one tile ahead (the first tile's before the reduction)
+// DEPTH: fragment registers of one batch <= 96 of the 256 at 8 waves, <= 24 of the 128 at 16 (12 tiles at the most).
+template <int KP, int APL, int NW>
+constexpr int skip_depth() {
+    const int d = (NW == 8 ? 96 : 24) / (KP * APL * 4);
+    return d > 12 ? 12 : (d < 1 ? 1 : d);
+}
+
+// `depth` (>= 1) caps a batch below the capacity: SE_SKIP_DEPTH, for tests that want several batches at small shapes.
+// MTh follows from KP for every shape the plan admits (KP = 1, 2: C <= 32, one M tile; KP = 4: 49 <= C <= 64, two).
+template <int PL, int KP, int NW, PlaneFmt FMT = PlaneFmt::kBf16>
+__global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
+    constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
+    static_assert(!PAIR || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair form has three weight planes, or two stored ones");
+    constexpr int APL = PAIR ? kPairPlanesA : PL;  // planes of res and out
+    constexpr int MTH = KP == 4 ? 2 : 1;
+    constexpr int DEPTH = skip_depth<KP, APL, NW>();
+    constexpr bool UNROLL = DEPTH <= 4;  // the tile loop unrolled where a batch is short: a slot is then used in place, not copied
+    extern __shared__ __align__(16) uint4 wl[];  // [2*MTH][KP][PL][64] weight fragments, then cst[6][Cp] floats
+    __shared__ float sm[4];
+    __shared__ double red[2][NW];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
+    const int half = lane >> 5, l31 = lane & 31;
+    const int b = blockIdx.x;
+    const uint4 *xb = a.x + (long)b * a.x_stream;
+    const int tiles = (a.TF + 31) >> 5;
+    const long plane = a.TF;  // uint4 per plane of one octet
+    const int nt = wave < tiles ? (tiles - wave + NW - 1) / NW : 0;  // tiles of this wave: wave + k NW, k < nt
+    const int dcap = min(depth, DEPTH);
+    const bool keep = (tiles + NW - 1) / NW <= dcap;  // (workgroup-uniform: wave 0 owns the most tiles)
+
+    // the B fragments of tiles k0 .. k0 + dcap - 1 of this wave, all requested at once
+    uint4 bf[DEPTH][KP][APL];
+    auto load_batch = [&](int k0) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++) {
+            if (d >= dcap || k0 + d >= nt) continue;
+            const int p = min((wave + (k0 + d) * NW) * 32 + l31, a.TF - 1);
+#pragma unroll
+            for (int kp = 0; kp < KP; kp++) {
+                const int o = min(2 * kp + half, a.C8 - 1);  // a missing odd octet reads a valid one (its weights are zero)
+#pragma unroll
+                for (int pl = 0; pl < APL; pl++) bf[d][kp][pl] = xb[((long)o * APL + pl) * plane + p];
+            }
+        }
+    };
+    // slot d of the batch (d is wave-uniform; the slots are named at compile time so that they stay registers)
+    auto slot = [&](int d, uint4 (&cur)[KP][APL]) {
+#pragma unroll
+        for (int j = 0; j < DEPTH; j++) {
+            if (d != j) continue;
+#pragma unroll
+            for (int kp = 0; kp < KP; kp++)
+#pragma unroll
+                for (int pl = 0; pl < APL; pl++) cur[kp][pl] = bf[j][kp][pl];
+        }
+    };
+    auto mma_tile = [&](int mt, const uint4 (&cur)[KP][APL]) { return skip_mma_tile<PL, KP, FMT, APL>(wl, mt, cur, l31, half); };
+
+    // the tiles of one batch in their order: body(slot, k)
+    auto for_slots = [&](int k0, auto &&body) {
+        if constexpr (UNROLL) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; d++)
+                if (d < dcap && k0 + d < nt) body(d, k0 + d);
+        } else {
+#pragma nounroll
+            for (int d = 0; d < dcap && k0 + d < nt; d++) body(d, k0 + d);
+        }
+    };
+
+    load_batch(0);
+    const int nfrag = 2 * MTH * KP * PL * 64;
+    for (int i = tid; i < nfrag; i += NW * 64) wl[i] = a.wx[i];
+    constexpr int Cp = MTH * 32;
+    float *cst = reinterpret_cast<float *>(wl + nfrag);
+    for (int i = tid; i < 6 * Cp; i += NW * 64) cst[i] = a.cst[i];
+    float my, iy;
+    slab_mean_inv(a.sy, b, sm, my, iy);  // (contains a barrier: the weights are in LDS afterwards)
+
+    // ---- pass 1: statistics of residualmask(res); float per tile, double across a wave's tiles in their order ----
+    double s1 = 0, s2 = 0;
+    auto stat_tile = [&](int d, int k) {
+        uint4 cur[KP][APL];
+        slot(d, cur);
+        const bool pos_ok = (wave + k * NW) * 32 + l31 < a.TF;
+        float ts = 0.0f, tq = 0.0f;
+#pragma nounroll
+        for (int mt = 0; mt < MTH; mt++) {  // (not unrolled: the code of an unrolled batch stays within the instruction cache)
+            const f32x16 c = mma_tile(mt, cur);
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int ch = mt * 32 + 16 * half + r;
+                const float v = c[r] + cst[ch];
+                if (pos_ok && ch < a.C) { ts += v; tq += v * v; }
+            }
+        }
+        s1 += (double)ts;
+        s2 += (double)tq;
+    };
+    for (int k0 = 0; k0 < nt; k0 += dcap) {
+        if (k0) load_batch(k0);
+        for_slots(k0, stat_tile);
+    }
+    if (!keep) load_batch(0);  // pass 2's first batch: in flight across the reduction
+
+    // A lane gates NH octets of 8 channels per M tile: registers 8 hh .. 8 hh + 7 are octet mt * 4 + 2 half + hh.  KP = 1 (C <= 16) has
+    // octets 0 and 1 only, both in lane half 0, and the whole wave would issue the gate of 16 values for half its lanes: there lane
+    // half 1 takes octet 1 over from its partner lane (the same position), and every lane gates one octet.
+    constexpr bool SPLIT = KP == 1;
+    constexpr int NH = SPLIT ? 1 : 2;
+    // the deconvolution values of one M tile of one position tile: [hh] octets of 8 channels, fp32
+    const float invF = 1.0f / (float)a.Fr;
+    const float *ydb = a.ydec + (long)b * a.y_stream;
+    auto load_y = [&](int k, int mt, float4 (&y)[2][2]) {
+        const int pc = min((wave + k * NW) * 32 + l31, a.TF - 1);
+        const int t = (int)(((float)pc + 0.5f) * invF), f = pc - t * a.Fr;
+        const long ypos = (long)t * 2 * a.Fh + (f & 1) * a.Fh + (f >> 1);
+#pragma unroll
+        for (int hh = 0; hh < NH; hh++) {
+            const int oct = SPLIT ? half : mt * 4 + 2 * half + hh;
+            y[hh][0] = y[hh][1] = make_float4(0, 0, 0, 0);
+            if (f < a.Fo && oct * 8 < a.C) {
+                const float4 *src = reinterpret_cast<const float4 *>(ydb + ((long)oct * a.T * 2 * a.Fh + ypos) * 8);
+                y[hh][0] = src[0];
+                y[hh][1] = src[1];
+            }
+        }
+    };
+    float4 ycur[2][2], ynxt[2][2];
+    if (nt > 0) load_y(0, 0, ycur);  // (they do not depend on the mask statistics)
+
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
+    if (lane == 0) { red[0][wave] = s1; red[1][wave] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        double ts = 0, tq = 0;
+        for (int i = 0; i < NW; i++) { ts += red[0][i]; tq += red[1][i]; }
+        const double n = (double)a.C * a.TF, m = ts / n;
+        double var = tq / n - m * m;
+        if (var < 0) var = 0;
+        sm[2] = (float)m;
+        sm[3] = gln_inv((float)var, a.eps_mode);
+    }
+    __syncthreads();
+    const float mu = sm[2], iu = sm[3];
+
+    // ---- pass 2: gate ----
+    uint4 *ob = a.out + (long)b * a.out_stream;
+    auto gate_tile = [&](int d, int k) {
+        uint4 cur[KP][APL];
+        slot(d, cur);
+        const int p = (wave + k * NW) * 32 + l31;
+        const bool pos_ok = p < a.TF;
+        const int pc = min(p, a.TF - 1);
+        const int t = (int)(((float)pc + 0.5f) * invF), f = pc - t * a.Fr;
+        const bool has_y = f < a.Fo;
+#pragma nounroll
+        for (int mt = 0; mt < MTH; mt++) {  // (not unrolled: the code of an unrolled batch stays within the instruction cache)
+            if (mt + 1 < MTH) load_y(k, mt + 1, ynxt);  // one step ahead: the tile's next M tile, or the next tile's first
+            else if (k + 1 < nt) load_y(k + 1, 0, ynxt);
+            const f32x16 cm = mma_tile(mt, cur), cr = mma_tile(MTH + mt, cur);
+#pragma unroll
+            for (int hh = 0; hh < NH; hh++) {
+                const int oct = SPLIT ? half : mt * 4 + 2 * half + hh;
+                float um[8], ur[8];
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    um[q] = cm[hh * 8 + q];
+                    ur[q] = cr[hh * 8 + q];
+                    if constexpr (SPLIT) {  // (every lane of the wave is here: the exchange sits outside the octet test)
+                        const float tm = __shfl_xor(cm[8 + q], 32, 64), tr = __shfl_xor(cr[8 + q], 32, 64);
+                        if (half) { um[q] = tm; ur[q] = tr; }
+                    }
+                }
+                if (oct * 8 >= a.C) continue;
+                const float4 u0 = ycur[hh][0], u1 = ycur[hh][1];
+                const float yv[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
+                float o[8];
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    const int ch = oct * 8 + q;
+                    const float u = um[q] + cst[ch];
+                    const float v = convp_act(ur[q] + cst[Cp + ch], a.act);
+                    const float yn = has_y ? (yv[q] - my) * iy * cst[2 * Cp + ch] + cst[3 * Cp + ch] : 0.0f;
+                    const float un = (u - mu) * iu * cst[4 * Cp + ch] + cst[5 * Cp + ch];
+                    const float g = 1.0f / (1.0f + expf(-un));
+                    o[q] = ch < a.C ? g * v + (1.0f - g) * yn : 0.0f;
+                }
+                if (pos_ok) split_store8_fmt<PL, FMT>(o, ob + (long)oct * APL * plane + p, plane);
+            }
+#pragma unroll
+            for (int hh = 0; hh < NH; hh++) { ycur[hh][0] = ynxt[hh][0]; ycur[hh][1] = ynxt[hh][1]; }
+        }
+    };
+    for (int k0 = 0; k0 < nt; k0 += dcap) {
+        if (k0) load_batch(k0);
+        for_slots(k0, gate_tile);
     }
 }
 
