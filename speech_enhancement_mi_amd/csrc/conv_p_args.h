@@ -128,7 +128,8 @@ struct SkipPArgs {
     int T, Fr;
     const uint4 *wx;      // [MT2][KP][PL][64] fragments: M tiles [0, MTh) = residualmask rows, [MTh, 2 MTh) = residual rows,
                           // rows permuted so that register r of lane half h is channel mt*32 + 16 h + r
-    const float *cst;     // [6][Cp] per channel (Cp = MTh*32): residualmask bias, residual bias, norm w, norm b, residualnorm w, b
+    const float *cst;     // [Cp/8][6][8] per octet (Cp = MTh*32), rows of 8 channels: residualmask bias, residual bias, norm w, norm b,
+                          // residualnorm w, b (SkipCst in skip_p.hip.h); zeros for the padded channels
     int MTh, KP;
     int act;
     const float *ydec;    // R layout of this block's transposed convolution [b][C8][T * 2 Fh][8], parity-planar

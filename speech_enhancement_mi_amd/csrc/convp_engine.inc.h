@@ -245,12 +245,17 @@ void select_all_p(se_engine *e) {
     for (int i = 0; i < e->L; i++) {
         PLevel &pv = e->cp->pv[i];
         for (ConvPPlan *p : {&pv.enc, &pv.skip, &pv.skipm, &pv.gate[0], &pv.gate[1]}) select_convp_geometry(e, *p);
-        // a decoder level runs its two parities in one launch where the model prices that below the two launches of this batch
+        // a decoder level runs its two parities in one launch where the model prices that below the two launches of this batch.
+        // The model prices the rounds of a launch, not its start and drain (about 5 us, 12000 cycles, which no workgroup count hides):
+        // the same for every tiling of one launch, but the two-launch form pays it twice.  Without it the 512-point dec2 at B = 256
+        // was priced 0.7 % below its pair launch and measured 69.3 us against 57.8 us.
+        constexpr double kLaunchCycles = 12000.0;
         pv.dec_pair_on = false;
         if (pv.dec_even.active && pv.dec_even.a.ntap2 && pv.dec_even.ngpair) {
-            const double two = select_convp_geometry(e, pv.dec_even) + select_convp_geometry(e, pv.dec_odd);
+            const double two = select_convp_geometry(e, pv.dec_even) + select_convp_geometry(e, pv.dec_odd) + kLaunchCycles;
             ConvPPlan::Geo keep{pv.dec_even.NT, pv.dec_even.a.tiles_per_wg, pv.dec_even.grid_x, pv.dec_even.a.grouped, pv.dec_even.lds, 0};
-            if (select_convp_geometry(e, pv.dec_even, true) < two) pv.dec_pair_on = true;
+            const double one = select_convp_geometry(e, pv.dec_even, true);
+            if (e->dec_pair_site[i] >= 0 ? e->dec_pair_site[i] == 1 : one < two) pv.dec_pair_on = true;  // (SE_DEC_PAIR_dec<i> beats the model)
             else { pv.dec_even.NT = keep.NT; pv.dec_even.a.tiles_per_wg = keep.tpw; pv.dec_even.grid_x = keep.n_wg; pv.dec_even.a.grouped = keep.grouped; pv.dec_even.lds = keep.lds; }
         } else {
             select_convp_geometry(e, pv.dec_even);
@@ -456,9 +461,10 @@ int prepare_weights_p(se_engine *e) {
                     if ((rc = dev_alloc(e, sk.wx, (wx.size() + 1) / 2))) return rc;
                     HIPCHECK(e, hipMemcpy(sk.wx.p, wx.data(), wx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
                     std::vector<float> cst((size_t)6 * Cp, 0.0f);
-                    for (int c = 0; c < Co; c++) {
-                        cst[c] = (*mb)[c]; cst[Cp + c] = (*rb)[c]; cst[2 * Cp + c] = (*nw)[c]; cst[3 * Cp + c] = (*nb)[c];
-                        cst[4 * Cp + c] = (*mnw)[c]; cst[5 * Cp + c] = (*mnb)[c];
+                    for (int c = 0; c < Co; c++) {  // [octet][constant][8]: a lane reads one constant of its octet as two 16-byte pieces
+                        float *row = &cst[(size_t)(c >> 3) * 6 * 8 + (c & 7)];
+                        row[0] = (*mb)[c]; row[8] = (*rb)[c]; row[16] = (*nw)[c]; row[24] = (*nb)[c];
+                        row[32] = (*mnw)[c]; row[40] = (*mnb)[c];
                     }
                     if ((rc = dev_upload(e, sk.cst, cst))) return rc;
                     SkipPArgs &a = sk.a;

@@ -139,6 +139,7 @@ struct se_engine : EngineHost {
     int skip_min_batch = 96;  // SE_SKIP_MIN_BATCH: the streaming skip kernel needs at least this many streams
     int skip_depth = -1;      // SE_SKIP_DEPTH: tiles per batch of the streaming skip kernel (k_skip_pd); 0: k_skip_p; -1: per instance (se_skip.hip)
     int dec_pair = 1;         // SE_DEC_PAIR=0: the transposed convolutions above the last level run one k_conv_p launch per parity
+    int dec_pair_site[SE_MAX_LEVELS];  // SE_DEC_PAIR_dec<j> = 0 / 1: decoder level j on two launches / on the pair launch, whatever the cost model says; -1: the model
     int io_fuse = 1;          // SE_IO_FUSE=0: k_stft + k_featurize_p and k_final_mask_p + k_istft as four kernels (io_fused.hip.h fuses them)
     bool io_fuse_on = false;  // io_fuse and the fused kernels' workgroups fit a CU's LDS at this geometry
     int gemm_p_env = 1;
@@ -1161,6 +1162,10 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (const char *s = getenv("SE_SKIP_MIN_BATCH")) e->skip_min_batch = atoi(s);
     if (const char *s = getenv("SE_SKIP_DEPTH")) e->skip_depth = atoi(s) > 0 ? atoi(s) : 0;
     if (const char *s = getenv("SE_DEC_PAIR")) e->dec_pair = atoi(s) != 0 ? 1 : 0;
+    for (int j = 0; j < SE_MAX_LEVELS; j++) {
+        const char *s = getenv(("SE_DEC_PAIR_dec" + std::to_string(j)).c_str());
+        e->dec_pair_site[j] = s ? (atoi(s) != 0 ? 1 : 0) : -1;
+    }
     if (const char *s = getenv("SE_IO_FUSE")) e->io_fuse = atoi(s) != 0 ? 1 : 0;
     e->io_fuse_on = e->io_fuse && sig_io_fused_fits(e->sig, e->M);
     e->cp = new se_convp_state();

@@ -16,53 +16,58 @@ namespace se {
 // (KEEP); 16 waves for KP = 1, which is bound by VALU issue and needs the four waves per SIMD (8 waves: 81 instead of 61 us per launch)
 #define SE_SKD_NW(PL_, KP_) (KP_ == 1 ? 16 : 8)
 
-// depth = 0: k_skip_p, the one-ahead loop; depth >= 1: k_skip_pd with batches of min(depth, capacity) tiles; depth < 0: the default -
-// k_skip_pd at its capacity for KP = 1 and 4, k_skip_p for KP = 2: alone the batched KP = 2 instance is 2 us faster, but its 218
-// registers (129 before) leave no room for a second kernel's waves on the CU, and the pipelined step loses 1 %
-int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, PlaneFmt fmt, int depth) {
-    if (depth < 0) depth = KP == 2 ? 0 : 1 << 20;
-    if (depth > 0) {
-#define SE_SKDP(WPL_, KP_) \
-    if (PL == WPL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_pd<WPL_, KP_, SE_SKD_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), dim3(batch), dim3(SE_SKD_NW(kPairPlanesW, KP_) * 64), lds, st, a, depth); return 0; }
-        if (fmt == PlaneFmt::kF16Pair) {
-            SE_SKDP(kPairPlanesW, 1) SE_SKDP(kPairPlanesW, 2) SE_SKDP(kPairPlanesW, 4)
-            SE_SKDP(kPairPlanesW2, 1) SE_SKDP(kPairPlanesW2, 2) SE_SKDP(kPairPlanesW2, 4)
-            return 1;
-        }
-#define SE_SKD(PL_, KP_) \
-    if (PL == PL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_pd<PL_, KP_, SE_SKD_NW(PL_, KP_)>), dim3(batch), dim3(SE_SKD_NW(PL_, KP_) * 64), lds, st, a, depth); return 0; }
-#define SE_SKD3(KP_) SE_SKD(1, KP_) SE_SKD(2, KP_) SE_SKD(3, KP_)
-        SE_SKD3(1) SE_SKD3(2) SE_SKD3(4)
-        return 1;
+// One instance per (format, planes, K steps, activation): the activation is a template parameter of the gate, so that the ReLU
+// instances carry no ELU code.  launch: 0 = launched, 1 = no such instance; attributes only: the dynamic LDS limit of the instance.
+template <int PL, int KP, int ACT, PlaneFmt FMT>
+static void skip_instance(bool batched, bool attributes_only, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, int depth) {
+    constexpr int WPL = FMT == PlaneFmt::kF16Pair ? kPairPlanesW : PL;  // (the two-stored-plane instances keep the wave count of the
+    constexpr int NWP = SE_SK_NW(WPL, KP), NWD = SE_SKD_NW(WPL, KP);    //  three-plane ones: they hold the same three weight operands)
+    if (attributes_only) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<PL, KP, NWP, ACT, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_pd<PL, KP, NWD, ACT, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    } else if (batched) {
+        hipLaunchKernelGGL((k_skip_pd<PL, KP, NWD, ACT, FMT>), dim3(batch), dim3(NWD * 64), lds, st, a, depth);
+    } else {
+        hipLaunchKernelGGL((k_skip_p<PL, KP, NWP, ACT, FMT>), dim3(batch), dim3(NWP * 64), lds, st, a);
     }
-    // (the two-stored-plane instances keep the wave count of the three-plane ones: they hold the same three weight operands per K step)
-#define SE_SKP(WPL_, KP_) \
-    if (PL == WPL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_p<WPL_, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), dim3(batch), dim3(SE_SK_NW(kPairPlanesW, KP_) * 64), lds, st, a); return 0; }
-    if (fmt == PlaneFmt::kF16Pair) {
-        SE_SKP(kPairPlanesW, 1) SE_SKP(kPairPlanesW, 2) SE_SKP(kPairPlanesW, 4)
-        SE_SKP(kPairPlanesW2, 1) SE_SKP(kPairPlanesW2, 2) SE_SKP(kPairPlanesW2, 4)
-        return 1;
-    }
-#define SE_SK(PL_, KP_) \
-    if (PL == PL_ && KP == KP_) { hipLaunchKernelGGL((k_skip_p<PL_, KP_, SE_SK_NW(PL_, KP_)>), dim3(batch), dim3(SE_SK_NW(PL_, KP_) * 64), lds, st, a); return 0; }
-#define SE_SK3(KP_) SE_SK(1, KP_) SE_SK(2, KP_) SE_SK(3, KP_)
-    SE_SK3(1) SE_SK3(2) SE_SK3(4)
+}
+
+template <int PL, PlaneFmt FMT>
+static int skip_dispatch(int KP, int act, bool batched, bool attributes_only, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, int depth) {
+#define SE_SKI(KP_, ACT_) \
+    if (KP == KP_ && act == ACT_) { skip_instance<PL, KP_, ACT_, FMT>(batched, attributes_only, batch, lds, st, a, depth); return 0; }
+    SE_SKI(1, 1) SE_SKI(2, 1) SE_SKI(4, 1) SE_SKI(1, 2) SE_SKI(2, 2) SE_SKI(4, 2)
+#undef SE_SKI
     return 1;
 }
 
+static int skip_dispatch(int PL, PlaneFmt fmt, int KP, int act, bool batched, bool attributes_only, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, int depth) {
+    if (fmt == PlaneFmt::kF16Pair) {
+        if (PL == kPairPlanesW) return skip_dispatch<kPairPlanesW, PlaneFmt::kF16Pair>(KP, act, batched, attributes_only, batch, lds, st, a, depth);
+        if (PL == kPairPlanesW2) return skip_dispatch<kPairPlanesW2, PlaneFmt::kF16Pair>(KP, act, batched, attributes_only, batch, lds, st, a, depth);
+        return 1;
+    }
+    if (PL == 1) return skip_dispatch<1, PlaneFmt::kBf16>(KP, act, batched, attributes_only, batch, lds, st, a, depth);
+    if (PL == 2) return skip_dispatch<2, PlaneFmt::kBf16>(KP, act, batched, attributes_only, batch, lds, st, a, depth);
+    if (PL == 3) return skip_dispatch<3, PlaneFmt::kBf16>(KP, act, batched, attributes_only, batch, lds, st, a, depth);
+    return 1;
+}
+
+// depth = 0: k_skip_p, the one-ahead loop; depth >= 1: k_skip_pd with batches of min(depth, capacity) tiles; depth < 0: the default -
+// k_skip_pd at its capacity for KP = 1 and 4, k_skip_p for KP = 2: alone the batched KP = 2 instance is 2 us faster, but its 218
+// registers (129 before) leave no room for a second kernel's waves on the CU, and the pipelined step loses 1 %.
+// a.act (1 ReLU, 2 ELU) selects the instance; any other value has none.
+int launch_k_skip_p(int PL, int KP, int batch, size_t lds, hipStream_t st, const SkipPArgs &a, PlaneFmt fmt, int depth) {
+    if (depth < 0) depth = KP == 2 ? 0 : 1 << 20;
+    return skip_dispatch(PL, fmt, KP, a.act, depth > 0, false, batch, lds, st, a, depth);
+}
+
 void skip_p_set_attributes() {
-#define SE_SKA(PL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<PL_, KP_, SE_SK_NW(PL_, KP_)>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-#define SE_SKA3(KP_) SE_SKA(1, KP_) SE_SKA(2, KP_) SE_SKA(3, KP_)
-    SE_SKA3(1) SE_SKA3(2) SE_SKA3(4)
-#define SE_SKAP(WPL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_p<WPL_, KP_, SE_SK_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    SE_SKAP(kPairPlanesW, 1) SE_SKAP(kPairPlanesW, 2) SE_SKAP(kPairPlanesW, 4)
-    SE_SKAP(kPairPlanesW2, 1) SE_SKAP(kPairPlanesW2, 2) SE_SKAP(kPairPlanesW2, 4)
-#define SE_SKDA(PL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_pd<PL_, KP_, SE_SKD_NW(PL_, KP_)>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-#define SE_SKDA3(KP_) SE_SKDA(1, KP_) SE_SKDA(2, KP_) SE_SKDA(3, KP_)
-    SE_SKDA3(1) SE_SKDA3(2) SE_SKDA3(4)
-#define SE_SKDAP(WPL_, KP_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_skip_pd<WPL_, KP_, SE_SKD_NW(kPairPlanesW, KP_), PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    SE_SKDAP(kPairPlanesW, 1) SE_SKDAP(kPairPlanesW, 2) SE_SKDAP(kPairPlanesW, 4)
-    SE_SKDAP(kPairPlanesW2, 1) SE_SKDAP(kPairPlanesW2, 2) SE_SKDAP(kPairPlanesW2, 4)
+    const SkipPArgs none{};
+    for (PlaneFmt fmt : {PlaneFmt::kBf16, PlaneFmt::kF16Pair})
+        for (int PL : {1, 2, 3})
+            for (int KP : {1, 2, 4})
+                for (int act : {1, 2}) (void)skip_dispatch(PL, fmt, KP, act, false, true, 0, 0, nullptr, none, 0);
 }
 
 }  // namespace se

@@ -63,18 +63,138 @@ __device__ __forceinline__ f32x16 skip_mma_tile(const uint4 *wl, int mt, const u
     return c;
 }
 
+// Per-channel constants in LDS, one row of 8 floats per (octet, constant): cst[(oct * kSkipCst + k) * 8 + q], channel oct * 8 + q.
+// A lane reads the 8 channels of one constant as two 16-byte pieces, once per (tile, octet).  Padded channels hold zeros.
+enum SkipCst : int { kCstMaskB = 0, kCstResB = 1, kCstNormW = 2, kCstNormB = 3, kCstMaskNormW = 4, kCstMaskNormB = 5, kSkipCst = 6 };
+
+__device__ __forceinline__ void skip_cst8(const float *cst, int oct, int k, float (&v)[8]) {
+    const float4 *src = reinterpret_cast<const float4 *>(cst) + (oct * kSkipCst + k) * 2;
+    const float4 u0 = src[0], u1 = src[1];
+    v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
+}
+
+// kSkipFastGate: the gate of k_skip_p / k_skip_pd on subtract-then-FMA norms and the hardware exp2 / rcp (other bits than the
+// kPOutBlend epilogue of k_conv_p, which keeps the expression below and is the reference of tests/test_gpu_skip_gate.py).  The workgroup
+// then rewrites three constant rows once the mask statistics are known (skip_fold_stats): kCstMaskB = mu - bias, kCstMaskNormW =
+// iu * weight, kCstNormW = iy * weight.  The means stay subtractions: folded into the additive constant they cost 3-30x in gate
+// error at mean / sigma >= 10 (tests/test_skip_gate_cpu.py).
+// Not with two bf16 planes: the gate's output differs from the epilogue's by 2e-7 relative, which the fp16 pair and three bf16 planes
+// carry and one fp16 plane (bars of 1e-4) does not see, while two bf16 planes round it up to 2-3e-6 at the model output, over the 2e-6
+// between two routes.  That mode keeps the epilogue's expression, its contractions written out.
+constexpr bool kSkipFastGate = true;
+template <int PL, PlaneFmt FMT>
+constexpr bool skip_fast_gate() { return kSkipFastGate && (FMT == PlaneFmt::kF16Pair || PL != 2); }
+
+struct SkipNorm { float my, iy, mu, iu; };  // mean and inverse deviation of the deconvolution and of residualmask(res)
+
+// (the four are the same in every lane: kept in scalar registers)
+__device__ __forceinline__ void skip_norm_uniform(SkipNorm &n) {
+    for (float *f : {&n.my, &n.iy, &n.mu, &n.iu}) *f = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, *f)));
+}
+
+template <bool FAST>
+__device__ __forceinline__ void skip_fold_stats(float *cst, int Cp, int tid, int nthreads, const SkipNorm &n) {
+    if constexpr (FAST) {
+        for (int ch = tid; ch < Cp; ch += nthreads) {
+            float *row = cst + (ch >> 3) * kSkipCst * 8 + (ch & 7);
+            row[kCstMaskB * 8] = n.mu - row[kCstMaskB * 8];
+            row[kCstMaskNormW * 8] = n.iu * row[kCstMaskNormW * 8];
+            row[kCstNormW * 8] = n.iy * row[kCstNormW * 8];
+        }
+        __syncthreads();
+    }
+}
+
+// The gate of one octet `oct` (8 channels) at one position: um / ur the residualmask / residual accumulators, yv the deconvolution
+// values (has_y: the column exists, CRN.py:389-392), nv = C - 8 oct valid channels.  bias, activation, the two norms, sigmoid, blend.
+template <int ACT, bool FAST>
+__device__ __forceinline__ void skip_gate_octet(const float *cst, int oct, int nv, const float (&um)[8], const float (&ur)[8], const float (&yv)[8],
+                                                bool has_y, const SkipNorm &n, float (&o)[8]) {
+    static_assert(ACT == 1 || ACT == 2, "ReLU or ELU");
+    // Two halves of 4 values, each in three steps (sigmoid; activation; norm and blend) with the 16-byte pieces of the constant rows
+    // a step needs: 12 registers at the most, where all six rows of the octet would be 48.  The row index passes through
+    // an empty asm together with a result of the step before, so that a step's LDS reads stay behind that step (and the first step's
+    // behind the octet's MFMAs); the pieces pass through one so that they stay 16-byte reads and are not sunk into a branch on has_y.
+    auto piece = [&](int h4, int k, float (&c)[4]) {
+        const float4 u = reinterpret_cast<const float4 *>(cst)[(oct * kSkipCst + k) * 2 + h4];
+        c[0] = u.x; c[1] = u.y; c[2] = u.z; c[3] = u.w;
+        asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
+    };
+    float um0 = um[0];
+    asm volatile("" : "+v"(oct), "+v"(um0));
+#pragma unroll
+    for (int h4 = 0; h4 < 2; h4++) {
+        float g[4], ca[4], cb[4], cc[4];
+        piece(h4, kCstMaskB, ca); piece(h4, kCstMaskNormW, cb); piece(h4, kCstMaskNormB, cc);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int q = h4 * 4 + j;
+            if constexpr (FAST) {
+                const float un = __builtin_fmaf((q ? um[q] : um0) - ca[j], cb[j], cc[j]);
+                g[j] = __builtin_amdgcn_rcpf(1.0f + __expf(-un));  // exp overflows to inf for un < -88: rcp(inf) = 0
+            } else {  // (the contraction written out: every instance of either kernel rounds alike, whatever surrounds the call)
+#pragma clang fp contract(off)
+                const float u = (q ? um[q] : um0) + ca[j];
+                const float un = __builtin_fmaf((u - n.mu) * n.iu, cb[j], cc[j]);
+                g[j] = 1.0f / (1.0f + expf(-un));
+            }
+        }
+        asm volatile("" : "+v"(oct), "+v"(g[3]));
+        float v[4];
+        piece(h4, kCstResB, ca);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float r = ur[h4 * 4 + j] + ca[j];
+            if constexpr (ACT == 1) v[j] = fmaxf(r, 0.0f);
+            else v[j] = r > 0.0f ? r : expf(r) - 1.0f;
+        }
+        asm volatile("" : "+v"(oct), "+v"(v[3]));
+        piece(h4, kCstNormW, cb); piece(h4, kCstNormB, cc);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int q = h4 * 4 + j;
+            float res;
+            if constexpr (FAST) {
+                const float yn = has_y ? __builtin_fmaf(yv[q] - n.my, cb[j], cc[j]) : 0.0f;
+                res = __builtin_fmaf(g[j], v[j] - yn, yn);
+            } else {
+#pragma clang fp contract(off)
+                const float yn = has_y ? __builtin_fmaf((yv[q] - n.my) * n.iy, cb[j], cc[j]) : 0.0f;
+                res = __builtin_fmaf(g[j], v[j], (1.0f - g[j]) * yn);
+            }
+            o[q] = q < nv ? res : 0.0f;
+        }
+        if (h4 == 0) asm volatile("" : "+v"(oct), "+v"(o[3]));
+    }
+}
+
+// pass 1's share of one M tile: sum and sum of squares of residualmask(res) + bias over the 16 channels of this lane (padded channels
+// have zero weight rows and a zero bias: they add exact zeros)
+__device__ __forceinline__ void skip_stat_tile(const float *cst, int mt, int half, const f32x16 &c, float &ts, float &tq) {
+#pragma unroll
+    for (int hh = 0; hh < 2; hh++) {
+        float bm[8];
+        skip_cst8(cst, mt * 4 + 2 * half + hh, kCstMaskB, bm);
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const float v = c[hh * 8 + q] + bm[q];
+            ts += v; tq = __builtin_fmaf(v, v, tq);
+        }
+    }
+}
+
 // NW = waves per workgroup: 16 (1024 threads, 128 VGPRs) for KP <= 2, 8 for KP = 4 - the kernel is a latency-bound stream
 // (one workgroup per CU), so bytes in flight = waves x fragments in flight decide its rate
 // FMT = kF16Pair (PL = 3 weight planes): res and out are two fp16 planes (split_f16pair.h), the weights (2^11 w_hi, w_lo, w_hi), three f16
 // MFMAs per K step in the fixed order W0 b_hi, W1 b_hi, W2 b_lo, and the 2^-11 (exact) on the accumulators before the statistics of
 // pass 1 and before the gate of pass 2.  PL = 2 with kF16Pair: the two stored planes (w_lo, w_hi) in LDS, 2^11 w_hi made when the
 // fragment is read (pair_scale_hi) - the same operands from two thirds of the weight bytes.
-template <int PL, int KP, int NW, PlaneFmt FMT = PlaneFmt::kBf16>
+template <int PL, int KP, int NW, int ACT, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
     constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
     static_assert(!PAIR || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair form has three weight planes, or two stored ones");
     constexpr int APL = PAIR ? kPairPlanesA : PL;  // planes of res and out
-    extern __shared__ __align__(16) uint4 wl[];  // [2*MTh][KP][PL][64] weight fragments, then cst[6][Cp] floats
+    extern __shared__ __align__(16) uint4 wl[];  // [2*MTh][KP][PL][64] weight fragments, then cst[Cp/8][6][8] floats
     __shared__ float sm[4];
     __shared__ double red[2][NW];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -86,20 +206,21 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
     const int Cp = a.MTh * 32;
     float *cst = reinterpret_cast<float *>(wl + nfrag);  // per-channel constants in LDS: global loads between the gate's stores
     for (int i = tid; i < 6 * Cp; i += NW * 64) cst[i] = a.cst[i];  // could not be hoisted (they may alias), LDS reads can
-    float my, iy;
-    slab_mean_inv(a.sy, b, sm, my, iy);  // (contains a barrier: the weights are in LDS afterwards)
+    SkipNorm nrm;
+    slab_mean_inv(a.sy, b, sm, nrm.my, nrm.iy);  // (contains a barrier: the weights are in LDS afterwards)
     const uint4 *xb = a.x + (long)b * a.x_stream;
     const int tiles = (a.TF + 31) >> 5;
     const long plane = a.TF;  // uint4 per plane of one octet
 
     // B fragments of one position tile: KP K steps x APL planes; lane half h of step kp holds octet 2 kp + h
+    // (32-bit offsets from the stream's uniform base here and for ydec and out below: a stream of any of them is below 2^31 bytes)
     auto load_b = [&](int tile, uint4 (&bf)[KP][APL]) {
         const int p = min(tile * 32 + l31, a.TF - 1);
 #pragma unroll
         for (int kp = 0; kp < KP; kp++) {
             const int o = min(2 * kp + half, a.C8 - 1);  // a missing odd octet reads a valid one (its weights are zero)
 #pragma unroll
-            for (int pl = 0; pl < APL; pl++) bf[kp][pl] = xb[((long)o * APL + pl) * plane + p];
+            for (int pl = 0; pl < APL; pl++) bf[kp][pl] = xb[(o * APL + pl) * a.TF + p];
         }
     };
     auto mma_tile = [&](int mt, const uint4 (&bf)[KP][APL]) { return skip_mma_tile<PL, KP, FMT, APL>(wl, mt, bf, l31, half); };
@@ -114,17 +235,9 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
             if (tile + NW < tiles) load_b(tile + NW, bnxt);
             const bool pos_ok = tile * 32 + l31 < a.TF;
             float ts = 0.0f, tq = 0.0f;
-            for (int mt = 0; mt < a.MTh; mt++) {
-                const f32x16 c = mma_tile(mt, bcur);
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int ch = mt * 32 + 16 * half + r;
-                    const float v = c[r] + cst[ch];
-                    if (pos_ok && ch < a.C) { ts += v; tq += v * v; }
-                }
-            }
-            s1 += (double)ts;
-            s2 += (double)tq;
+            for (int mt = 0; mt < a.MTh; mt++) skip_stat_tile(cst, mt, half, mma_tile(mt, bcur), ts, tq);
+            s1 += pos_ok ? (double)ts : 0.0;  // (a lane beyond the last position computed on a clamped one)
+            s2 += pos_ok ? (double)tq : 0.0;
 #pragma unroll
             for (int kp = 0; kp < KP; kp++)
 #pragma unroll
@@ -145,52 +258,53 @@ __global__ __launch_bounds__(NW * 64) void k_skip_p(SkipPArgs a) {
         sm[3] = gln_inv((float)var, a.eps_mode);
     }
     __syncthreads();
-    const float mu = sm[2], iu = sm[3];
+    nrm.mu = sm[2]; nrm.iu = sm[3];
+    skip_norm_uniform(nrm);
+    skip_fold_stats<skip_fast_gate<PL, FMT>()>(cst, Cp, tid, NW * 64, nrm);
 
     // ---- pass 2: gate ----
     const float invF = 1.0f / (float)a.Fr;
     const float *ydb = a.ydec + (long)b * a.y_stream;
     uint4 *ob = a.out + (long)b * a.out_stream;
+    // 16 waves have 128 registers each: there the next tile's fragments are requested into the registers of the current one, once
+    // its last MFMA has read them (the gate of the last M tile covers the round trip), and bnxt is not used
+    constexpr bool INPLACE = NW == 16;
     uint4 bcur[KP][APL], bnxt[KP][APL];
     if (wave < tiles) load_b(wave, bcur);
     for (int tile = wave; tile < tiles; tile += NW) {
-        if (tile + NW < tiles) load_b(tile + NW, bnxt);
+        if (!INPLACE && tile + NW < tiles) load_b(tile + NW, bnxt);
         const int p = tile * 32 + l31;
         const bool pos_ok = p < a.TF;
         const int pc = min(p, a.TF - 1);
         const int t = (int)(((float)pc + 0.5f) * invF), f = pc - t * a.Fr;
         const bool has_y = f < a.Fo;
-        const long ypos = (long)t * 2 * a.Fh + (f & 1) * a.Fh + (f >> 1);
+        const int ypos = t * 2 * a.Fh + (f & 1) * a.Fh + (f >> 1);
         for (int mt = 0; mt < a.MTh; mt++) {
             const f32x16 cm = mma_tile(mt, bcur), cr = mma_tile(a.MTh + mt, bcur);
+            if (INPLACE && mt == a.MTh - 1 && tile + NW < tiles) load_b(tile + NW, bcur);
 #pragma unroll
             for (int hh = 0; hh < 2; hh++) {
                 const int oct = mt * 4 + 2 * half + hh;  // registers 8 hh .. 8 hh + 7 of this lane
                 if (oct * 8 >= a.C) continue;
                 float yv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
                 if (has_y) {
-                    const float4 *src = reinterpret_cast<const float4 *>(ydb + ((long)oct * a.T * 2 * a.Fh + ypos) * 8);
+                    const float4 *src = reinterpret_cast<const float4 *>(ydb + (oct * a.T * 2 * a.Fh + ypos) * 8);
                     const float4 u0 = src[0], u1 = src[1];
                     yv[0] = u0.x; yv[1] = u0.y; yv[2] = u0.z; yv[3] = u0.w; yv[4] = u1.x; yv[5] = u1.y; yv[6] = u1.z; yv[7] = u1.w;
                 }
-                float o[8];
+                float um[8], ur[8], o[8];
 #pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int r = hh * 8 + q, ch = oct * 8 + q;
-                    const float u = cm[r] + cst[ch];
-                    const float v = convp_act(cr[r] + cst[Cp + ch], a.act);
-                    const float yn = has_y ? (yv[q] - my) * iy * cst[2 * Cp + ch] + cst[3 * Cp + ch] : 0.0f;
-                    const float un = (u - mu) * iu * cst[4 * Cp + ch] + cst[5 * Cp + ch];
-                    const float g = 1.0f / (1.0f + expf(-un));
-                    o[q] = ch < a.C ? g * v + (1.0f - g) * yn : 0.0f;
-                }
-                if (pos_ok) split_store8_fmt<PL, FMT>(o, ob + (long)oct * APL * plane + p, plane);
+                for (int q = 0; q < 8; q++) { um[q] = cm[hh * 8 + q]; ur[q] = cr[hh * 8 + q]; }
+                skip_gate_octet<ACT, skip_fast_gate<PL, FMT>()>(cst, oct, a.C - oct * 8, um, ur, yv, has_y, nrm, o);
+                if (pos_ok) split_store8_fmt<PL, FMT>(o, ob + (oct * APL * a.TF + p), plane);
             }
         }
+        if constexpr (!INPLACE) {
 #pragma unroll
-        for (int kp = 0; kp < KP; kp++)
+            for (int kp = 0; kp < KP; kp++)
 #pragma unroll
-            for (int pl = 0; pl < APL; pl++) bcur[kp][pl] = bnxt[kp][pl];
+                for (int pl = 0; pl < APL; pl++) bcur[kp][pl] = bnxt[kp][pl];
+        }
     }
 }
 
@@ -212,7 +326,7 @@ constexpr int skip_depth() {
 
 // `depth` (>= 1) caps a batch below the capacity: SE_SKIP_DEPTH, for tests that want several batches at small shapes.
 // MTh follows from KP for every shape the plan admits (KP = 1, 2: C <= 32, one M tile; KP = 4: 49 <= C <= 64, two).
-template <int PL, int KP, int NW, PlaneFmt FMT = PlaneFmt::kBf16>
+template <int PL, int KP, int NW, int ACT, PlaneFmt FMT = PlaneFmt::kBf16>
 __global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
     constexpr bool PAIR = FMT == PlaneFmt::kF16Pair;
     static_assert(!PAIR || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair form has three weight planes, or two stored ones");
@@ -220,7 +334,7 @@ __global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
     constexpr int MTH = KP == 4 ? 2 : 1;
     constexpr int DEPTH = skip_depth<KP, APL, NW>();
     constexpr bool UNROLL = DEPTH <= 4;  // the tile loop unrolled where a batch is short: a slot is then used in place, not copied
-    extern __shared__ __align__(16) uint4 wl[];  // [2*MTH][KP][PL][64] weight fragments, then cst[6][Cp] floats
+    extern __shared__ __align__(16) uint4 wl[];  // [2*MTH][KP][PL][64] weight fragments, then cst[Cp/8][6][8] floats
     __shared__ float sm[4];
     __shared__ double red[2][NW];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -280,8 +394,8 @@ __global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
     constexpr int Cp = MTH * 32;
     float *cst = reinterpret_cast<float *>(wl + nfrag);
     for (int i = tid; i < 6 * Cp; i += NW * 64) cst[i] = a.cst[i];
-    float my, iy;
-    slab_mean_inv(a.sy, b, sm, my, iy);  // (contains a barrier: the weights are in LDS afterwards)
+    SkipNorm nrm;
+    slab_mean_inv(a.sy, b, sm, nrm.my, nrm.iy);  // (contains a barrier: the weights are in LDS afterwards)
 
     // ---- pass 1: statistics of residualmask(res); float per tile, double across a wave's tiles in their order ----
     double s1 = 0, s2 = 0;
@@ -292,16 +406,10 @@ __global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
         float ts = 0.0f, tq = 0.0f;
 #pragma nounroll
         for (int mt = 0; mt < MTH; mt++) {  // (not unrolled: the code of an unrolled batch stays within the instruction cache)
-            const f32x16 c = mma_tile(mt, cur);
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int ch = mt * 32 + 16 * half + r;
-                const float v = c[r] + cst[ch];
-                if (pos_ok && ch < a.C) { ts += v; tq += v * v; }
-            }
+            skip_stat_tile(cst, mt, half, mma_tile(mt, cur), ts, tq);
         }
-        s1 += (double)ts;
-        s2 += (double)tq;
+        s1 += pos_ok ? (double)ts : 0.0;  // (a lane beyond the last position computed on a clamped one)
+        s2 += pos_ok ? (double)tq : 0.0;
     };
     for (int k0 = 0; k0 < nt; k0 += dcap) {
         if (k0) load_batch(k0);
@@ -349,7 +457,9 @@ __global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
         sm[3] = gln_inv((float)var, a.eps_mode);
     }
     __syncthreads();
-    const float mu = sm[2], iu = sm[3];
+    nrm.mu = sm[2]; nrm.iu = sm[3];
+    skip_norm_uniform(nrm);
+    skip_fold_stats<skip_fast_gate<PL, FMT>()>(cst, Cp, tid, NW * 64, nrm);
 
     // ---- pass 2: gate ----
     uint4 *ob = a.out + (long)b * a.out_stream;
@@ -383,16 +493,7 @@ __global__ __launch_bounds__(NW * 64) void k_skip_pd(SkipPArgs a, int depth) {
                 const float4 u0 = ycur[hh][0], u1 = ycur[hh][1];
                 const float yv[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
                 float o[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int ch = oct * 8 + q;
-                    const float u = um[q] + cst[ch];
-                    const float v = convp_act(ur[q] + cst[Cp + ch], a.act);
-                    const float yn = has_y ? (yv[q] - my) * iy * cst[2 * Cp + ch] + cst[3 * Cp + ch] : 0.0f;
-                    const float un = (u - mu) * iu * cst[4 * Cp + ch] + cst[5 * Cp + ch];
-                    const float g = 1.0f / (1.0f + expf(-un));
-                    o[q] = ch < a.C ? g * v + (1.0f - g) * yn : 0.0f;
-                }
+                skip_gate_octet<ACT, skip_fast_gate<PL, FMT>()>(cst, oct, a.C - oct * 8, um, ur, yv, has_y, nrm, o);
                 if (pos_ok) split_store8_fmt<PL, FMT>(o, ob + (long)oct * APL * plane + p, plane);
             }
 #pragma unroll
