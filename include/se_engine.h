@@ -171,7 +171,7 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
                               additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
-                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference) */
+                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference); se_hifi_* (HiFi-GAN generator inference) */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -530,6 +530,32 @@ int se_gtsa_tail5(const float *att, int lda, const float *x, float *y, const flo
 int se_gtsa_gather3(const float *x, const float *buf, float *A, int S, int B, int T, int Fs, void *stream);
 int se_gtsa_out(const float *g, int ldg, const float *nw, const float *nb, const float *spec, float *Y, float *tap, int S, int M, int T, int F,
                 void *stream);
+
+/* ---- HiFi-GAN generator inference (csrc/se_hifi.hip; reference Hifi-GAN/hifigan.py:444-656) ------------------------------
+ * What the generator needs beyond se_train_conv_w / se_train_gemm and the se_sig_* chain.  Device pointers, fp32, no float atomics,
+ * fixed-order reductions; activations [S][C][T][F], S = Nc windows x B utterances, window-major (s = n B + b).  0 or a negative
+ * se_status, se_train_last_error() = message.
+ * se_hifi_postnet: x [S][2][T][F] -> y [S][2][T][F] through the twelve 1x1 layers, self-gate tanh(v) sigmoid(v) after each; one
+ *   workgroup keeps 128 bins of one stream on chip through all layers (f32-input MFMA for the ten 128 x 128 layers).  pack: layer by
+ *   layer the weight-norm-folded weight [Co][Ci] then the bias: [128][2], [128], 10 x ([128][128], [128]), [2][128], [2].
+ * se_hifi_gate: y[i] = tanh(x[i]) sigmoid(x[i]), n values.
+ * se_hifi_skip: out [S][Co][T][Fr] = sigmoid(v) tanh(u) + (1 - sigmoid(v)) z; z = self-gate of yd [S][Co][T][Fy], zero for f >= Fy
+ *   (Fy <= Fr); uv [S][2 Co][T][Fr] = u (residual) in channels [0, Co), v (residualmask) in [Co, 2 Co).
+ * se_hifi_rows: x [S][C][T][F] -> rows [B][Nc T][C F], row (b, n T + t), column c F + f.
+ * se_hifi_lstm: one LSTM layer over TT steps, one launch per step and no waiting between workgroups: gi [B][TT][4H] = x W_ih^T + b_ih
+ *   + b_hh (gate order i, f, g, o), h0 / c0 [B][H], whh [4H][H] -> out [B][TT][H], hT / cT [B][H] (other memory than h0 / c0); H % 8 == 0, H <= 1024.
+ * se_hifi_seqnorm: o [B][Nc][T][D = C F] (the fc output before its tanh) -> y [S][C][T][F] = (tanh(o) - g) w[d] + bias[d], g the
+ *   running mean of the utterance after the window: g = alpha g + (1 - alpha) mean_{T x D}(tanh(o)), alpha = step / (step + D),
+ *   step += D per window, starting from mean_in [B] and `step` (zeros and 0: nothing carried); wm [B Nc] scratch (receives g per
+ *   window), mean_out [B] = g after the last window. */
+int se_hifi_postnet(const float *x, const float *pack, float *y, int S, int T, int F, void *stream);
+int se_hifi_gate(const float *x, float *y, int64_t n, void *stream);
+int se_hifi_skip(const float *yd, const float *uv, float *out, int S, int Co, int T, int Fy, int Fr, void *stream);
+int se_hifi_rows(const float *x, float *rows, int Nc, int B, int C, int T, int F, void *stream);
+int se_hifi_lstm(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, int B, int TT, int H,
+                 void *stream);
+int se_hifi_seqnorm(const float *o, const float *w, const float *bias, const float *mean_in, double step, float *wm, float *mean_out, float *y,
+                    int Nc, int B, int C, int T, int F, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -18,6 +18,9 @@ last call was.  Refused, in this order and before any state is read or written:
 and a call that is refused or fails leaves the carried state it found: both paths build the new state out of place and store it when
 the call has succeeded (the one exception: a persistent-GRU time-out clears `_kstate`, the output being invalid).
 
+hifigan.Generator shares the mixin too: its `realtime_process(mixture, post, reset)` has two results and `reset` = not `flag`, so it
+parses its own arguments and takes the choice of path and the refusals from `_admit`.
+
 A model provides `segment_length`, `_cfg["n_fft"]` and
     _choose_path(mixture) -> "torch", "kernel" or the name X of a path of its own on the kernel state (`_X_call(mixture, plan)`)
     _plan_channels(M)                  the U-Net levels' channels for the plan's geometry (default: none)
@@ -69,6 +72,12 @@ class StreamingMixin:
         """The contract, the refusals and the rule for the carried state: this module's docstring."""
         B, M, L = mixture.shape
         plan = self._plan(flag, lengths, B, L, M)
+        return getattr(self, f"_{self._admit(mixture, plan)}_call")(mixture, plan)
+
+    def _admit(self, mixture, plan):
+        """The choice of path and the refusals of a call -> the name of the path that runs it (a model whose realtime_process has
+        another signature, hifigan.Generator, parses its own arguments into a plan and comes here)."""
+        B = mixture.shape[0]
         run = self._choose_path(mixture)
         path = "torch" if run == "torch" else "kernel"
         if plan.any_flag:
@@ -82,7 +91,7 @@ class StreamingMixin:
             if have not in (None, B):
                 raise ValueError(f"flag=True continues a batch of {have} utterances, got {B}")
         self._last_path = path
-        return getattr(self, f"_{run}_call")(mixture, plan)
+        return run
 
     # ---- torch restatement ---------------------------------------------------------------------------------------------------
     def spectrum(self, seg):

@@ -227,6 +227,58 @@ def gtsa_state_dict(spec, seed: int = 0) -> Dict[str, np.ndarray]:
     return out
 
 
+HIFIGAN_GAIN = 4.0  # weight_g over its default-initialised value ||v||: see hifigan_state_dict
+
+
+def hifigan_param_spec(num_channels, num_freqs, hidden, num_layers=1, num_inputs=3, kernel_size=3):
+    """(key, shape) list of reference Hifi-GAN Generator.state_dict() (Hifi-GAN/hifigan.py:453-498; checked against the live module,
+    fixture hifigan_keys.json).  Every conv, deconv, 1x1 and the fc are weight-normed: bias, weight_g ([dim 0][1]...), weight_v, in
+    the order torch.nn.utils.weight_norm registers them, and once more under the `net.0.` alias.  The LSTM is nn.LSTM's."""
+    def wn(p, shape, nout, alias=True):
+        g = (shape[0],) + (1,) * (len(shape) - 1)
+        one = lambda q: [(q + "bias", (nout,)), (q + "weight_g", g), (q + "weight_v", tuple(shape))]  # noqa: E731
+        return one(p + "conv.") + one(p + "net.0.") if alias else one(p)
+
+    spec = []
+    L = len(num_channels)
+    c0 = 2 * num_inputs - 1
+    for i in range(L):
+        cin = c0 if i == 0 else num_channels[i - 1]
+        spec += wn(f"convlist.{i}.", (num_channels[i], cin, 5, kernel_size), num_channels[i])
+    for j in range(L):
+        i = L - 1 - j
+        cout = 2 if i == 0 else num_channels[i - 1]
+        p = f"deconvlist.{j}."   # a transposed convolution's weight is [Cin, Cout, 5, k]: weight_g has Cin rows, the bias Cout entries
+        spec += (wn(p, (num_channels[i], cout, 5, kernel_size), cout) + wn(p + "residualmask.", (cout, cout, 1, 1), cout, False)
+                 + wn(p + "residual.", (cout, cout, 1, 1), cout, False))
+    D = (num_freqs // 16 + 1) * num_channels[-1]
+    for l in range(num_layers):
+        ins = D if l == 0 else hidden
+        spec += [(f"gru.sequence_model.weight_ih_l{l}", (4 * hidden, ins)), (f"gru.sequence_model.weight_hh_l{l}", (4 * hidden, hidden)),
+                 (f"gru.sequence_model.bias_ih_l{l}", (4 * hidden,)), (f"gru.sequence_model.bias_hh_l{l}", (4 * hidden,))]
+    spec += wn("gru.fc_output_layer.", (D, hidden), D, False) + [("gru.norm.weight", (1, 1, 1, D)), ("gru.norm.bias", (1, 1, 1, D))]
+    chans = [2] + [128] * 11 + [2]
+    for i in range(12):
+        spec += wn(f"postnet.{i}.", (chans[i + 1], chans[i], 1, 1), chans[i + 1])
+    return spec
+
+
+def hifigan_state_dict(spec, seed: int = 0, gain: float = HIFIGAN_GAIN) -> Dict[str, np.ndarray]:
+    """make_state_dict for a hifigan_param_spec, then every weight_g = gain * ||v|| / 1.7 * (1 + 0.1 u) per dim-0 row: make_state_dict
+    draws v at 1.7 times torch's default scale, so ||v|| / 1.7 is the default-initialised weight_g and `gain` multiplies it.  A
+    self-gate layer passes about half its input times the weight gain, so at torch's own initial values the twelve-layer postnet
+    carries no signal and a broken one would go unnoticed; tests/golden/make_golden_hifigan.py checks that the gain makes the
+    result depend on the postnet's input and that float32 still holds the fixture.  The `net.0.` aliases get the tensors of `conv.`."""
+    out = make_state_dict(spec, seed)
+    for name, shape in spec:
+        if name.endswith("weight_g"):
+            key = name.replace(".net.0.", ".conv.")
+            v = out[key[:-1] + "v"].astype(np.float64)
+            n = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(axis=1)).reshape(shape)
+            out[name] = (gain * n / 1.7 * (1.0 + 0.1 * hash_tensor(key, tuple(shape), seed))).astype(np.float32)
+    return out
+
+
 def synth_utterances(batch: int, length: int, num_mics: int = 3, seed: int = 0,
                      sample_rate: int = 16000):
     """Synthetic noisy multi-mic speech-like audio: returns (mix [B,M,L], clean [B,L]).
