@@ -1,4 +1,4 @@
-// conv_args.h - argument structs and staging budgets of the convolution kernels (conv_igemm.hip.h, conv_x6.hip.h), shared by the
+// conv_args.h - argument structs and staging budgets of the fp32-layout convolution kernels (conv_igemm.hip.h), shared by the
 // engine (se_engine.hip: planning, launches through conv_dispatch.h) and the kernel translation unit (se_conv.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,12 +48,5 @@ struct ConvArgs {
 
 constexpr int kPatchPerThread = 16;   // patch elements staged per thread per chunk  (chunk patch <= 4096 floats)
 constexpr int kWeightPerThread = 8;   // float4 weight slots per thread per chunk      (chunk slab  <= 8192 floats)
-
-constexpr int kX6PosPerThread = 4;  // (patch position, octet) items per thread: CO*R*St <= 1024 (host-checked)
-
-struct ConvX6Args {
-    ConvArgs c;        // geometry, x / xprev / bias / y / stats exactly as for k_conv_igemm (c.w unused, c.CC == 8)
-    const uint4 *wx;   // [nchunk][nstep][3][MT][64] fragments of 16 B
-};
 
 }  // namespace se

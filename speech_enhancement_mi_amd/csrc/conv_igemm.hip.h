@@ -42,7 +42,7 @@ __device__ __forceinline__ float conv_act(float v, int act) {
     return act == 1 ? fmaxf(v, 0.0f) : (act == 2 ? (v > 0.0f ? v : expf(v) - 1.0f) : v);
 }
 
-// Epilogue shared by k_conv_igemm and k_conv_x6 (both leave 32x32 accumulator tiles: column = position on the lane,
+// Epilogue of k_conv_igemm (32x32 accumulator tiles: column = position on the lane,
 // rows = GEMM rows in the 16 registers): bias, activation, store [B][Cy][T][Fy], and the per-workgroup partial
 // (sum, sum of squares) for the global layer norm that follows.
 template <int NT>

@@ -1,6 +1,6 @@
 // conv_p.hip.h - second-generation implicit-GEMM convolution: MFMA operands live in HBM ALREADY SPLIT into bf16 planes.
 //
-// Same GEMM view as conv_x6.hip.h (M = Cout rows, N = output positions of one stream, K = taps x Cin walked in chunks of CO
+// Same GEMM view as its fp32-layout predecessor (M = Cout rows, N = output positions of one stream, K = taps x Cin walked in chunks of CO
 // channel octets; a K step = two (tap, octet) entries x 8 channels; split-bf16 products hi*hi + hi*mid + mid*hi [+ hi*lo +
 // lo*hi + mid*mid]), but the data path around the MFMA loop is different:
 //

@@ -78,6 +78,8 @@ struct se_convp_state {
     DevBuf decR[SE_MAX_LEVELS];   // [B][Co8][T*2Fi][8] parity-planar
     DevBuf decP[SE_MAX_LEVELS];   // blended decoder level outputs, P layout
     PlaneFmt ring_fmt = PlaneFmt::kBf16;  // format of what xinP[i >= 1] holds (alloc_state_p, convert_history_p)
+    ConvPPlan tap_enc;            // CRN_ELU / student, feature tap ft0: the last encoder convolution once more, writing the R layout
+                                  // (tap_enc_plan: built on first use, dropped by prepare_weights_p)
     bool ready = false;
 };
 
@@ -276,14 +278,54 @@ void free_state_p(se_engine *e) {
     }
     for (int r = 0; r < kRing; r++) dev_free(S.decinP[r]);
     for (int i = 0; i < 3; i++) { dev_free(S.pre[i].wx); dev_free(S.pre[i].bias); dev_free(S.pinP[i]); dev_free(S.pre_gw[i]); }
-    dev_free(S.preR);
+    dev_free(S.preR); dev_free(S.tap_enc.wx); dev_free(S.tap_enc.bias);
     delete e->cp;
     e->cp = nullptr;
+}
+
+// The strided convolution of encoder level i (CRN.py:331-336) as a k_conv_p plan that writes `out_mode`
+int plan_enc_conv_p(se_engine *e, int i, ConvPPlan &pl, int out_mode) {
+    const int Ci = e->Ch[i], Co = e->Ch[i + 1], Fi = e->F[i], Fo = e->F[i + 1], d = 1 << i, T = e->T;
+    const std::string p = "convlist." + std::to_string(i) + ".";
+    auto *w = param(e, p + "conv.weight", (size_t)Co * Ci * 15);
+    auto *b = param(e, p + "conv.bias", Co);
+    if (!w || !b) return SE_ERR_PARAM_MISSING;
+    std::vector<std::array<int, 4>> taps;
+    for (int kf = 0; kf < 5; kf++)
+        for (int kt = 0; kt < 3; kt++) taps.push_back({kf, kt, kt, kf});
+    const float *wp = w->data();
+    int rc = plan_conv_p(e, pl, Ci, Co, Fo, Fi, 2, 2, -2 * d, 3, d, Fi + 4, taps,
+                         [=](int ci, int co, int kf, int kt) { return wp[(((size_t)co * Ci + ci) * 5 + kf) * 3 + kt]; }, *b, 0, Co, e->act,
+                         out_mode, act_format(e, xin_kind(i)));  // (level 0 reads the features: bf16 planes)
+    if (rc) return rc;
+    ConvPArgs &a = pl.a;
+    a.oT = Fo; a.oo = 0; a.y_npos = T * Fo; a.y_stream = (long)((Co + 7) / 8) * T * Fo * 8;
+    a.stats_lo = 0; a.stats_hi = Co;
+    pl.flops = 2.0 * Co * Ci * 15 * Fo * T;
+    return 0;
+}
+
+// Feature tap ft0 re-runs the last encoder convolution into the R layout.  The CRN's own plan writes that; CRN_ELU / the student write
+// act(conv) as planes with permuted GEMM rows, so their tap keeps a twin of the plan, tiled for the current batch.
+int tap_enc_plan(se_engine *e, const ConvPPlan **out) {
+    se_convp_state &S = *e->cp;
+    const int i = e->L - 1;
+    *out = &S.pv[i].enc;
+    if (!e->variant) return 0;
+    if (!S.tap_enc.active) {
+        int rc = plan_enc_conv_p(e, i, S.tap_enc, kPOutR);
+        if (rc) return rc;
+        S.tap_enc.name = "tap_enc";
+    }
+    select_convp_geometry(e, S.tap_enc);
+    *out = &S.tap_enc;
+    return 0;
 }
 
 int prepare_weights_p(se_engine *e) {
     se_convp_state &S = *e->cp;
     const int L = e->L, T = e->T;
+    S.tap_enc.active = false;  // planned from the previous weights
     // The pre-conv blocks run on k_conv_p only with fp16 operands: a workgroup stages a 6-7 row x (F + 4 fd) column patch for
     // 1-2 output rows, and with three bf16 planes that staging costs more than the scalar-weight vector-ALU kernel takes
     // (measured, student B = 1024: 760 vs 450 us per block in f32, equal in bf16x3, 0.6x in fp16).  SE_PRE_P=0/1 overrides.
@@ -318,23 +360,12 @@ int prepare_weights_p(se_engine *e) {
         S.pre[i].flops = 2.0 * C0 * C0 * 25 * F0 * T + 2.0 * 2 * C0 * C0 * F0 * T;
     }
     for (int i = 0; i < L; i++) {
-        const int Ci = e->Ch[i], Co = e->Ch[i + 1], Fi = e->F[i], Fo = e->F[i + 1], d = 1 << i;
+        const int Co = e->Ch[i + 1], Fo = e->F[i + 1];
         const std::string p = "convlist." + std::to_string(i) + ".";
-        auto *w = param(e, p + "conv.weight", (size_t)Co * Ci * 15);
-        auto *b = param(e, p + "conv.bias", Co);
-        if (!w || !b) return SE_ERR_PARAM_MISSING;
-        std::vector<std::array<int, 4>> taps;
-        for (int kf = 0; kf < 5; kf++)
-            for (int kt = 0; kt < 3; kt++) taps.push_back({kf, kt, kt, kf});
-        const float *wp = w->data();
-        int rc = plan_conv_p(e, S.pv[i].enc, Ci, Co, Fo, Fi, 2, 2, -2 * d, 3, d, Fi + 4, taps,
-                             [=](int ci, int co, int kf, int kt) { return wp[(((size_t)co * Ci + ci) * 5 + kf) * 3 + kt]; }, *b, 0, Co, e->act,
-                             e->variant ? kPOutP : kPOutR, act_format(e, xin_kind(i)));  // (level 0 reads the features: bf16 planes)
+        int rc = plan_enc_conv_p(e, i, S.pv[i].enc, e->variant ? kPOutP : kPOutR);
         if (rc) return rc;
         S.pv[i].enc.name = "enc" + std::to_string(i);
         ConvPArgs &a = S.pv[i].enc.a;
-        a.oT = Fo; a.oo = 0; a.y_npos = T * Fo; a.y_stream = (long)((Co + 7) / 8) * T * Fo * 8;
-        a.stats_lo = 0; a.stats_hi = Co;
         S.pv[i].gate[0].active = S.pv[i].gate[1].active = false;
         if (e->variant) {  // act(conv) -> P layout -> gated 1x1 pair (CRN_ELU.py:223-224, 240) -> R layout + statistics
             a.Cy = Co; a.Fy = Fo; a.yp_stream = (long)((Co + 7) / 8) * operand_planes(e->precision) * T * Fo;
@@ -359,7 +390,6 @@ int prepare_weights_p(se_engine *e) {
                 g.flops = 2.0 * 2 * cn * Co * Fo * T;
             }
         }
-        S.pv[i].enc.flops = 2.0 * Co * Ci * 15 * Fo * T;
     }
     for (int j = 0; j < L; j++) {
         const int lvl = L - 1 - j;
@@ -563,6 +593,47 @@ int stage_stft_feat_p(se_engine *e, int cur, const float *src, long strideB, lon
     return 0;
 }
 
+// The two convolution launches that the stages and the feature taps (read_tap_impl) share.  y / yp: the output in the plan's layout;
+// stats: the slab of the norm that follows (nullptr: no statistics); act_on = false stores the pre-activation values, what a tap reads.
+//
+// Encoder level i on ring slots cur / prev (the conv time buffer) with `pl`: the level's own plan, or its R-layout twin (tap_enc_plan)
+int launch_enc_conv_p(se_engine *e, int i, const ConvPPlan &pl, int cur, int prev, float *y, uint4 *yp, float *stats, bool act_on, hipStream_t st,
+                      const char *label) {
+    se_convp_state &S = *e->cp;
+    ConvPArgs a = pl.a;
+    a.xbase = reinterpret_cast<const uint4 *>(S.xinP[i].p);
+    a.xbytes = (unsigned)((size_t)S.slot_elems[i] * kRing * 16);
+    a.cur_off = (long)cur * S.slot_elems[i];
+    a.prev_off = (long)prev * S.slot_elems[i];
+    a.y = y; a.yp = yp;
+    if (stats) { a.stats = stats; a.stats_nslot = pl.grid_x; a.stats_slot0 = 0; }
+    if (!act_on) a.relu_lo = a.relu_hi = 0;
+    return launch_conv_p(e, pl, a, st, label);
+}
+
+// The transposed convolution of decoder level j on the planes `xin` ([b][Ci8][planes][T][Fi]: decinP, or decP[j - 1]) -> y (R layout,
+// parity-planar above the last level), in the form select_all_p chose for this batch: the pair launch, or one launch per parity; the
+// merged four-row plan at the last level.  label: one name for every launch (a tap's); nullptr: the stage's per-launch names
+int launch_dec_conv_p(se_engine *e, int j, const uint4 *xin, float *y, float *stats, bool act_on, hipStream_t st, const char *label = nullptr) {
+    const int lvl = e->L - 1 - j;
+    PLevel &pv = e->cp->pv[j];
+    const int ne = pv.dec_even.grid_x, no = dec_odd_slots(pv);
+    const size_t xin_bytes = (size_t)e->B * ((e->Ch[lvl + 1] + 7) / 8) * act_planes(e, PlaneBuf::kConvAct) * e->T * e->F[lvl + 1] * 16;
+    int rc;
+    for (ConvPPlan *q : {&pv.dec_even, &pv.dec_odd}) {
+        if (!q->active || (q == &pv.dec_odd && pv.dec_pair_on)) continue;
+        ConvPArgs a = q->a;
+        if (!pv.dec_pair_on) a.ntap2 = 0;
+        a.xbase = xin; a.xbytes = (unsigned)xin_bytes; a.cur_off = 0; a.prev_off = -1;
+        a.y = y;
+        a.stats = stats; a.stats_nslot = ne + no; a.stats_slot0 = q == &pv.dec_odd ? ne : 0; a.stats_slot02 = ne;
+        if (!act_on) a.relu_lo = a.relu_hi = 0;
+        const char *sfx = a.ntap2 ? "" : (q == &pv.dec_odd ? "_odd" : "_even");
+        if ((rc = launch_conv_p(e, *q, a, st, label ? label : ("dec" + std::to_string(j) + sfx).c_str()))) return rc;
+    }
+    return 0;
+}
+
 // Stage 1 (plane path): features + encoder -> xinP[*][cur], gru_in[cur] (fp32, the bottleneck GEMM's A operand)
 // feat_done: stage_stft_feat_p has already written the slot's features (spec is then not read)
 int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st, bool feat_done = false) {
@@ -606,7 +677,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
         if ((rc = stage_features_pre(e, cur, spec, sB, sM, sT, sF, st))) return rc;
         ProfScope ps(e, "k_f32_to_p", "feat_to_p", 0, st);
         const int TF = T * e->F[0];
-        F32ToPArgs f{e->xin[0][cur].p, reinterpret_cast<uint4 *>(S.xinP[0].p) + (long)cur * S.slot_elems[0], (long)PL * TF, e->Ch[0], TF};
+        F32ToPArgs f{e->pre_out.p, reinterpret_cast<uint4 *>(S.xinP[0].p) + (long)cur * S.slot_elems[0], (long)PL * TF, e->Ch[0], TF};
         launch_k_f32_to_p(PL, dim3((TF + 255) / 256, Ba), st, f);
         HIPCHECK(e, hipGetLastError());
     } else if (!feat_done) {
@@ -619,21 +690,14 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
     for (int i = 0; i < L; i++) {
         const int Co = e->Ch[i + 1], Fo = e->F[i + 1];
         ConvPPlan &pl = S.pv[i].enc;
-        ConvPArgs a = pl.a;
-        a.xbase = reinterpret_cast<const uint4 *>(S.xinP[i].p);
-        a.xbytes = (unsigned)((size_t)S.slot_elems[i] * kRing * 16);
-        a.cur_off = (long)cur * S.slot_elems[i];
-        a.prev_off = (long)prev * S.slot_elems[i];
+        const ConvPArgs &a = pl.a;
         int nslot = pl.grid_x;
         if (e->variant) nslot = S.pv[i].gate[0].grid_x + (S.pv[i].gate[1].active ? S.pv[i].gate[1].grid_x : 0);
         if ((rc = slab_fits(e, e->enc_stats[i], nslot, "an encoder level"))) return rc;
         if (!e->variant) {
-            a.y = S.encR[i].p;
-            a.stats = e->enc_stats[i].p; a.stats_nslot = pl.grid_x; a.stats_slot0 = 0;
-            if ((rc = launch_conv_p(e, pl, a, st, ("enc" + std::to_string(i)).c_str()))) return rc;
+            if ((rc = launch_enc_conv_p(e, i, pl, cur, prev, S.encR[i].p, nullptr, e->enc_stats[i].p, true, st, ("enc" + std::to_string(i)).c_str()))) return rc;
         } else {
-            a.yp = reinterpret_cast<uint4 *>(S.encA[i].p);
-            if ((rc = launch_conv_p(e, pl, a, st, ("enc" + std::to_string(i)).c_str()))) return rc;
+            if ((rc = launch_enc_conv_p(e, i, pl, cur, prev, nullptr, reinterpret_cast<uint4 *>(S.encA[i].p), nullptr, true, st, ("enc" + std::to_string(i)).c_str()))) return rc;
             const int n0 = S.pv[i].gate[0].grid_x, n1 = S.pv[i].gate[1].active ? S.pv[i].gate[1].grid_x : 0;
             nslot = n0 + n1;
             for (int part = 0; part < 2; part++) {
@@ -685,23 +749,13 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
     const int Ba = e->Bact;  // launch batch: the prefix of streams that take part in this segment (se_realtime_process_ragged), B otherwise
     int rc;
     const uint4 *xin = reinterpret_cast<const uint4 *>(S.decinP[cur].p);
-    size_t xin_bytes = (size_t)B * ((e->Ch[L] + 7) / 8) * APL * T * e->F[L] * 16;
     for (int j = 0; j < L; j++) {
         const int lvl = L - 1 - j;
         const int Co = lvl == 0 ? 2 : e->Ch[lvl], Fi = e->F[lvl + 1], Fo = 2 * Fi - 1;
         PLevel &pv = S.pv[j];
         const int ne = pv.dec_even.grid_x, no = dec_odd_slots(pv);
         if ((rc = slab_fits(e, e->dec_stats[j], ne + no, "a decoder level"))) return rc;
-        for (ConvPPlan *q : {&pv.dec_even, &pv.dec_odd}) {
-            if (!q->active || (q == &pv.dec_odd && pv.dec_pair_on)) continue;
-            ConvPArgs a = q->a;
-            if (!pv.dec_pair_on) a.ntap2 = 0;
-            a.xbase = xin; a.xbytes = (unsigned)xin_bytes; a.cur_off = 0; a.prev_off = -1;
-            a.y = S.decR[j].p;
-            a.stats = e->dec_stats[j].p; a.stats_nslot = ne + no; a.stats_slot0 = q == &pv.dec_odd ? ne : 0; a.stats_slot02 = ne;
-            const char *sfx = a.ntap2 ? "" : (q == &pv.dec_odd ? "_odd" : "_even");
-            if ((rc = launch_conv_p(e, *q, a, st, ("dec" + std::to_string(j) + sfx).c_str()))) return rc;
-        }
+        if ((rc = launch_dec_conv_p(e, j, xin, S.decR[j].p, e->dec_stats[j].p, true, st))) return rc;
         const SlabStats sy{e->dec_stats[j].p, ne + no, (long)Co * T * Fo, e->eps_mode};
         if (lvl > 0) {
             const int Fr = e->F[lvl];
@@ -740,7 +794,6 @@ int stage_decoder_p(se_engine *e, int cur, const cf2 *spec, long sB, long sT, lo
             }
             }
             xin = reinterpret_cast<const uint4 *>(S.decP[j].p);
-            xin_bytes = (size_t)B * ((Co + 7) / 8) * APL * T * Fr * 16;
         } else {
             if (Fo != e->F[0]) return fail(e, SE_ERR_ARG, "decoder output has %d bins, spectrum has %d", Fo, e->F[0]);
             MaskPArgs m{S.decR[j].p, (long)T * Fi * 8, Fi, e->lv[j].dec_nw.p, e->lv[j].dec_nb.p, sy, spec, sB, sT, sF, out, oB, oT, oF, T, e->F[0]};

@@ -1,4 +1,4 @@
-// se_conv.hip - translation unit of the convolution kernels (k_conv_x6 / k_conv_igemm / k_conv_small template instances) and
+// se_conv.hip - translation unit of the fp32-layout convolution kernels (k_conv_igemm / k_conv_small / k_preconv_tb instances) and
 // their host-side dispatch (conv_dispatch.h).  Built with -fno-slp-vectorize like every TU of the library (see se_aux.hip).
 #include <hip/hip_runtime.h>
 
@@ -10,18 +10,6 @@
 #include "conv_igemm.hip.h"
 
 namespace se {
-
-int conv_x6_launch_pl1(int ntap, int NT, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
-int conv_x6_launch_pl2(int ntap, int NT, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
-int conv_x6_launch_pl3(int ntap, int NT, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa);
-void conv_x6_set_attributes_pl1();
-void conv_x6_set_attributes_pl2();
-void conv_x6_set_attributes_pl3();
-
-int conv_x6_launch(int ntap, int NT, int PL, dim3 grid, size_t lds, hipStream_t st, const ConvX6Args &xa) {
-    return PL == 1 ? conv_x6_launch_pl1(ntap, NT, grid, lds, st, xa)
-                   : (PL == 2 ? conv_x6_launch_pl2(ntap, NT, grid, lds, st, xa) : conv_x6_launch_pl3(ntap, NT, grid, lds, st, xa));
-}
 
 int conv_igemm_launch(int ntap, int NT, int CoPad, dim3 grid, size_t lds, hipStream_t st, const ConvArgs &a) {
 #define SE_CONV_CASE(NTAP_, NT_) \
@@ -58,9 +46,6 @@ void conv_set_attributes() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_small<NTAP_, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
     SE_CONV_ATTR(15) SE_CONV_ATTR(9) SE_CONV_ATTR(6) SE_CONV_ATTR(1)
 #undef SE_CONV_ATTR
-    conv_x6_set_attributes_pl1();
-    conv_x6_set_attributes_pl2();
-    conv_x6_set_attributes_pl3();
 }
 
 }  // namespace se

@@ -10,9 +10,9 @@
 // In se_step / se_realtime_process the two ends run fused (io_fused.hip.h): k_stft_feat = k_stft + k_featurize_p where the features
 // go to the plane path, k_mask_istft = k_final_mask_p + k_istft; SE_IO_FUSE=0 keeps the four kernels.
 //
-// k_conv_x6 / k_conv_igemm / k_conv_small (plan_conv, launch_conv) run the student's feature-tap re-runs, the
-// fp32 / bf16x3 pre-conv blocks and (k_conv_igemm) the training path; k_gemm_x / k_gemm_tn are the bottleneck GEMMs where
-// the plane GEMM k_gemm_p does not apply.  Reference: TemporalCRN.forward / realtime_process (CRN.py:454-496, 560-589).
+// k_conv_small / k_preconv_tb (plan_conv, launch_conv) run the fp32 / bf16x3 pre-conv blocks, k_conv_igemm the training path;
+// k_gemm_x / k_gemm_tn are the bottleneck GEMMs where the plane GEMM k_gemm_p does not apply.  The student's feature taps re-run
+// the plane path's own launches (read_tap_impl).  Reference: TemporalCRN.forward / realtime_process (CRN.py:454-496, 560-589).
 // No CPU fallback exists: every entry point fails with SE_ERR_HIP if the device path is unavailable.
 #include <hip/hip_runtime.h>
 
@@ -48,25 +48,17 @@ constexpr int kFftSub = 8;      // segments per STFT / iSTFT launch inside the p
 constexpr int kPipeChunk = 64;  // segments per pipelined chunk (bounds spec_all / mask_all)
 constexpr int kRing = 4;  // stage-crossing activation slots (see se_engine::slot)
 
-struct ConvPlan {
+struct ConvPlan {  // one launch of the vector-ALU convolution (k_conv_small / k_preconv_tb)
     ConvArgs a{};  // pointers filled per launch
-    int NT = 1;
     int grid_x = 0;
     size_t lds = 0;
     DevBuf w, bias;
     bool active = false;
-    bool x6 = false;  // bf16x6 kernel (k_conv_x6) instead of the fp32-MFMA k_conv_igemm
-    DevBuf wx;
-    DevBuf gatew;     // k_conv_small: fused gated 1x1 pair weights
-    // k_conv_x6 tilings that fit (index = tiles per wave - 1); the weights do not depend on the tiling, so the one that
-    // fills the chip with the fewest partial rounds is picked per batch size in select_conv_geometry()
-    struct Geo { int NT = 0, tpw = 0, n_wg = 0, grouped = 0; size_t lds = 0; } geo[4];
+    DevBuf gatew;     // fused gated 1x1 pair weights
     double flops = 0;  // algorithmic FLOPs per stream per launch (SURVEY.md 8d accounting)
 };
 
-struct Level {  // one encoder/decoder level
-    ConvPlan enc;          // feature tap ft0 re-runs lv[L-1].enc
-    ConvPlan dec_even, dec_odd;  // feature taps ft2.. re-run decoder blocks
+struct Level {  // one encoder/decoder level: the norm affines, and the pre-conv block that shares the index
     ConvPlan pre;          // CRN_ELU preconv block i (levels 0..2): 5x5 frequency-dilated conv with the gated pair fused in
     DevBuf enc_nw, enc_nb, dec_nw, dec_nb, dec_mnw, dec_mnb, pre_nw, pre_nb;
 };
@@ -103,20 +95,19 @@ struct se_engine : EngineHost {
     // kRing slots, so that in se_realtime_process the encoder of segment n+1.. can run on its own HIP stream while the
     // latency-bound GRU recurrence of segment n and the decoder of segment n-1 are still in flight.  slot = segment % kRing.
     // The plane path's activation rings are in se_convp_state; the fp32 tensors here are the output of the vector-ALU pre-conv
-    // blocks (xin[0]), the fp32 GRU input (gru_in) and the operands of the feature-tap re-runs (xin, dec_in, dec_out).
+    // blocks (pre_out) and the fp32 GRU input (gru_in).
     int slot = 0;
     DevBuf spec[kRing], maskspec;
     DevBuf spec_all, mask_all;         // pipelined se_realtime_process: spectra / masked spectra of one chunk of segments
-    DevBuf xin[SE_MAX_LEVELS][kRing];  // encoder level inputs (xin[0] = features)
-    DevBuf gru_in[kRing], gi0[kRing], gil[4], seqr[4][kRing], hbuf[4][2], fc_out, dec_in[kRing];  // gi0 / seqr cross stage streams: rings
+    DevBuf gru_in[kRing], gi0[kRing], gil[4], seqr[4][kRing], hbuf[4][2], fc_out;  // gi0 / seqr cross stage streams: rings
     int pipeline = 1;                  // SE_PIPELINE=0: one stream, stages back to back
     hipStream_t stage_stream[3]{};      // encoder (+ GRU input projection) / decoder (fc + norm first) / recurrence (all layers)
     hipEvent_t ev_enc[kRing]{}, ev_gru[kRing]{}, ev_dec[kRing]{}, ev_fork{}, ev_join{};
     bool stage_ready = false;
     int hcur[4]{};
-    DevBuf dec_out[SE_MAX_LEVELS];
     DevBuf enc_stats[SE_MAX_LEVELS], dec_stats[SE_MAX_LEVELS], skip_stats[SE_MAX_LEVELS];  // [B][slots][2] norm partials
     DevBuf pin[3][2], pre_g, pre_stats[3];  // CRN_ELU preconv chain (inputs ping-ponged: they carry 4 history columns)
+    DevBuf pre_out;                         // its fp32 output (written and converted to planes on one stream: no ring)
     DevBuf yseg;
     // A ragged / chains call is described by its ChainPlan (chain_plan.h), which run_segments gets as an argument.  What the engine keeps:
     // plan_dev, the device copy of the plan's per-stream vectors (8 * B floats); carry_*, one row per stream in the live tensors' row
@@ -213,137 +204,34 @@ std::string canon(const char *key) {
 }
 
 // ---- conv planning --------------------------------------------------------------------------------
+// The vector-ALU convolution of the pre-conv blocks (up to 8 channels, crn_geometry_supported): one thread per position, direct
+// global reads, weights [tap][ci][CW] in LDS.
 // taps: list of (kf, kt) with their patch offsets; wsel(ci, co, kf, kt) fetches the reference weight.
 template <class WSel>
 int plan_conv(se_engine *e, ConvPlan &pl, int Ci, int Co, int FP, int Fi, int Fy, int s, int os, int oo, int colpad,
               int tlo_off, int ngroup, int dil, int St, const std::vector<std::array<int, 4>> &taps /*kf,kt,rowgrp,coloff*/,
-              WSel wsel, const std::vector<float> &bias, int relu_lo, int relu_hi, int act, int Cy = -1) {
-    if (Cy < 0) Cy = Co;
-    pl.a.par_rows = 0;
-    pl.x6 = false;
+              WSel wsel, const std::vector<float> &bias, int relu_lo, int relu_hi, int act) {
     pl.active = FP > 0;
     if (!pl.active) return 0;
+    if (Co > 8) return fail(e, SE_ERR_ARG, "the vector-ALU convolution supports up to 8 output channels, got %d", Co);
     const int T = e->T;
     const int ntap = (int)taps.size();
-    const int P = T * FP, tiles = (P + 31) / 32;
-    // vector-ALU variant: one thread per position, direct global reads, weights [tap][ci][CW] in LDS.  Also taken by the first
-    // encoder block (5 -> 16 channels at full frequency resolution): K = 75 is too shallow for the matrix pipe to matter and
-    // the patch halo of the MFMA kernels costs more than the arithmetic
-    if (Co <= 8 || (Co <= 16 && Ci <= 8)) {
-        const int CW = Co <= 4 ? 4 : (Co <= 8 ? 8 : 16);
-        ConvArgs &a = pl.a;
-        a.Ci = Ci; a.Co = Co; a.CoPad = CW; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
-        a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = 0;
-        a.ntap = ntap; a.CC = Ci; a.nchunk = 1; a.tiles_per_wg = 8; a.St = St;
-        a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Cy; a.cy0 = 0;
-        for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; }
-        pl.NT = 0;  // marks the small kernel
-        pl.grid_x = (P + 255) / 256;
-        pl.lds = sizeof(float) * (size_t)ntap * Ci * CW;
-        if (pl.lds > 64 * 1024) return fail(e, SE_ERR_ARG, "small-conv weights do not fit LDS");
-        std::vector<float> w((size_t)ntap * Ci * CW, 0.0f);
-        for (int t = 0; t < ntap; t++)
-            for (int ci = 0; ci < Ci; ci++)
-                for (int co = 0; co < Co; co++) w[((size_t)t * Ci + ci) * CW + co] = wsel(ci, co, taps[t][0], taps[t][1]);
-        int rc = dev_upload(e, pl.w, w);
-        if (rc) return rc;
-        return dev_upload(e, pl.bias, bias);
-    }
-    const int CoPad = (Co + 31) / 32 * 32;
-    if (CoPad > 128) return fail(e, SE_ERR_ARG, "conv with %d output channels is not supported (max 128 per GEMM)", Co);
-    const int MT = CoPad / 32;
-    if (MT == 3) return fail(e, SE_ERR_ARG, "conv output channels %d need 3 row tiles (unsupported)", Co);
-    const int NCG = 4 / MT, NTmax = 4;
-    if (Ci % 8 == 0 || Ci >= 5) {  // ---- bf16x6 path: K step = 2 taps x 8 channels (Cin zero-padded to 8s), one octet per chunk ----
-        int tpw = 0, n_wg = 0, NT = 0, Rmax = 0, grouped = 0;
-        for (int k = 0; k < 4; k++) pl.geo[k] = ConvPlan::Geo{};
-        for (int ntmax = 1; ntmax <= NTmax; ntmax++) {  // ends on the largest tiling that fits = the default geometry
-            const int c_wg = (tiles + NCG * ntmax - 1) / (NCG * ntmax);
-            const int c_tpw = (tiles + c_wg - 1) / c_wg;
-            const int c_NT = (c_tpw + NCG - 1) / NCG;
-            int rows_pos = (c_tpw * 32 + FP - 1) / FP + 1;
-            if (rows_pos > T) rows_pos = T;
-            const int c_grouped = ngroup * rows_pos < rows_pos + (ngroup - 1) * dil;
-            const int c_Rmax = c_grouped ? ngroup * rows_pos : rows_pos + (ngroup - 1) * dil;
-            if ((size_t)c_Rmax * St > 256 * kX6PosPerThread) continue;
-            ConvPlan::Geo &g = pl.geo[c_NT - 1];
-            g.NT = c_NT; g.tpw = c_tpw; g.n_wg = c_wg; g.grouped = c_grouped;
-            g.lds = std::max<size_t>((size_t)operand_planes(e->precision) * c_Rmax * St * 16, 64);
-            tpw = c_tpw; n_wg = c_wg; NT = c_NT; Rmax = c_Rmax; grouped = c_grouped;
-        }
-        if (NT > 0) {
-            const int nstep = (ntap + 1) / 2, nchunk = (Ci + 7) / 8;
-            ConvArgs &a = pl.a;
-            a.Ci = Ci; a.Co = Co; a.CoPad = CoPad; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
-            a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = grouped;
-            a.ntap = ntap; a.CC = 8; a.nchunk = nchunk; a.tiles_per_wg = tpw; a.St = St;
-            a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Cy; a.cy0 = 0;
-            for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; }
-            pl.NT = NT; pl.grid_x = n_wg; pl.x6 = true;
-            pl.lds = std::max<size_t>((size_t)operand_planes(e->precision) * Rmax * St * 16, 64);
-            // weights: [chunk][step][plane][mtile][co 32][k 16], k = half*8 + c <-> tap 2*step+half, channel chunk*8 + c
-            const int PL = operand_planes(e->precision);
-            std::vector<uint16_t> wx((size_t)nchunk * nstep * PL * MT * 32 * 16, 0);
-            for (int ch = 0; ch < nchunk; ch++)
-                for (int st = 0; st < nstep; st++)
-                    for (int m = 0; m < MT; m++)
-                        for (int r = 0; r < 32; r++)
-                            for (int k = 0; k < 16; k++) {
-                                const int tp = 2 * st + k / 8, ci = ch * 8 + k % 8, co = m * 32 + r;
-                                if (tp >= ntap || co >= Co || ci >= Ci) continue;
-                                const float x = wsel(ci, co, taps[tp][0], taps[tp][1]);
-                                const uint16_t h = bf16_rne(x);
-                                const float r1 = x - bf16_to_f32(h);
-                                const uint16_t md = bf16_rne(r1);
-                                const float r2 = r1 - bf16_to_f32(md);
-                                const uint16_t parts[3] = {PL == 1 ? f16_rne(x) : h, md, bf16_rne(r2)};
-                                for (int pln = 0; pln < PL; pln++)
-                                    wx[(((((size_t)ch * nstep + st) * PL + pln) * MT + m) * 32 + r) * 16 + k] = parts[pln];
-                            }
-            int rc = dev_alloc(e, pl.wx, (wx.size() + 1) / 2);
-            if (rc) return rc;
-            HIPCHECK(e, hipMemcpy(pl.wx.p, wx.data(), wx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            return dev_upload(e, pl.bias, bias);
-        }
-    }
-    const int n_wg = (tiles + NCG * NTmax - 1) / (NCG * NTmax);
-    const int tpw = (tiles + n_wg - 1) / n_wg;
-    const int NT = (tpw + NCG - 1) / NCG;
-    int rows_pos = (tpw * 32 + FP - 1) / FP + 1;
-    if (rows_pos > T) rows_pos = T;
-    const int grouped = ngroup * rows_pos < rows_pos + (ngroup - 1) * dil;
-    const int Rmax = grouped ? ngroup * rows_pos : rows_pos + (ngroup - 1) * dil;
-    const int CiPad = (Ci + 1) / 2 * 2;
-    auto bytes = [&](int cc) { return sizeof(float) * ((size_t)ntap * cc * CoPad + (size_t)cc * Rmax * St); };
-    int CC = CiPad;
-    auto fits = [&](int cc) {
-        return bytes(cc) <= 48 * 1024 && (size_t)cc * Rmax * St <= 256 * kPatchPerThread &&
-               (size_t)ntap * cc * CoPad <= 256 * 4 * kWeightPerThread;
-    };
-    while (CC > 2 && !fits(CC)) CC -= 2;
-    if (!fits(CC)) return fail(e, SE_ERR_ARG, "conv chunk does not fit the staging registers (Rmax %d, St %d, taps %d, Cout %d)", Rmax, St, ntap, Co);
-    int nchunk = (CiPad + CC - 1) / CC;
-    CC = ((CiPad + nchunk - 1) / nchunk + 1) / 2 * 2;
-    nchunk = (CiPad + CC - 1) / CC;
-    if (bytes(CC) > 150 * 1024) return fail(e, SE_ERR_ARG, "conv tile does not fit LDS (%zu bytes)", bytes(CC));
+    const int P = T * FP;
+    const int CW = Co <= 4 ? 4 : 8;
     ConvArgs &a = pl.a;
-    a.Ci = Ci; a.Co = Co; a.CoPad = CoPad; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
-    a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = grouped;
-    a.ntap = ntap; a.CC = CC; a.nchunk = nchunk; a.tiles_per_wg = tpw; a.St = St;
-    a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Cy; a.cy0 = 0;
+    a.par_rows = 0;
+    a.Ci = Ci; a.Co = Co; a.CoPad = CW; a.T = T; a.Fi = Fi; a.FP = FP; a.Fy = Fy;
+    a.s = s; a.os = os; a.oo = oo; a.colpad = colpad; a.tlo_off = tlo_off; a.ngroup = ngroup; a.dil = dil; a.grouped = 0;
+    a.ntap = ntap; a.CC = Ci; a.nchunk = 1; a.tiles_per_wg = 8; a.St = St;
+    a.relu_lo = relu_lo; a.relu_hi = relu_hi; a.act = act; a.Cy = Co; a.cy0 = 0;
     for (int t = 0; t < ntap; t++) { a.rowgrp[t] = taps[t][2]; a.coloff[t] = taps[t][3]; }
-    pl.NT = NT;
-    pl.grid_x = n_wg;
-    pl.lds = bytes(CC);
-    std::vector<float> w((size_t)nchunk * ntap * CC * CoPad, 0.0f);
-    for (int ch = 0; ch < nchunk; ch++)
-        for (int t = 0; t < ntap; t++)
-            for (int c = 0; c < CC; c++) {
-                const int ci = ch * CC + c;
-                if (ci >= Ci) continue;
-                float *dst = &w[(((size_t)ch * ntap + t) * CC + c) * CoPad];
-                for (int co = 0; co < Co; co++) dst[co] = wsel(ci, co, taps[t][0], taps[t][1]);
-            }
+    pl.grid_x = (P + 255) / 256;
+    pl.lds = sizeof(float) * (size_t)ntap * Ci * CW;
+    if (pl.lds > 64 * 1024) return fail(e, SE_ERR_ARG, "small-conv weights do not fit LDS");
+    std::vector<float> w((size_t)ntap * Ci * CW, 0.0f);
+    for (int t = 0; t < ntap; t++)
+        for (int ci = 0; ci < Ci; ci++)
+            for (int co = 0; co < Co; co++) w[((size_t)t * Ci + ci) * CW + co] = wsel(ci, co, taps[t][0], taps[t][1]);
     int rc = dev_upload(e, pl.w, w);
     if (rc) return rc;
     return dev_upload(e, pl.bias, bias);
@@ -436,67 +324,25 @@ int prepare_weights(se_engine *e) {
     if (!crn_geometry_supported(e, &why)) return fail(e, SE_ERR_ARG, "%s", why.c_str());
     const int L = e->L, H = e->H, D = e->D;
     f16_pair_decide(e);
+    // the norm affines of every level (the convolutions themselves are planned in prepare_weights_p)
     for (int i = 0; i < L; i++) {
-        const int Ci = e->Ch[i], Co = e->Ch[i + 1], Fi = e->F[i], Fo = e->F[i + 1], d = 1 << i;
+        const int Co = e->Ch[i + 1];
         const std::string p = "convlist." + std::to_string(i) + ".";
-        auto *w = param(e, p + "conv.weight", (size_t)Co * Ci * 15);
-        auto *b = param(e, p + "conv.bias", Co);
         auto *nw = param(e, p + "norm.weight", Co);
         auto *nb = param(e, p + "norm.bias", Co);
-        if (!w || !b || !nw || !nb) return SE_ERR_PARAM_MISSING;
-        std::vector<std::array<int, 4>> taps;
-        for (int kf = 0; kf < 5; kf++)
-            for (int kt = 0; kt < 3; kt++) taps.push_back({kf, kt, kt, kf});
-        const float *wp = w->data();
-        int rc = plan_conv(e, e->lv[i].enc, Ci, Co, Fo, Fi, Fo, 2, 1, 0, 2, -2 * d, 3, d, Fi + 4, taps,
-                           [=](int ci, int co, int kf, int kt) { return wp[(((size_t)co * Ci + ci) * 5 + kf) * 3 + kt]; },
-                           *b, 0, Co, e->act);
-        if (rc) return rc;
-        e->lv[i].enc.flops = 2.0 * Co * Ci * 15 * Fo * e->T;
+        if (!nw || !nb) return SE_ERR_PARAM_MISSING;
+        int rc;
         if ((rc = dev_upload(e, e->lv[i].enc_nw, *nw))) return rc;
         if ((rc = dev_upload(e, e->lv[i].enc_nb, *nb))) return rc;
     }
     for (int j = 0; j < L; j++) {
         const int lvl = L - 1 - j;
-        const int Ci = e->Ch[lvl + 1], Co = lvl == 0 ? 2 : e->Ch[lvl], Fi = e->F[lvl + 1], Fo = 2 * Fi - 1, d = 1 << j;
+        const int Co = lvl == 0 ? 2 : e->Ch[lvl];
         const std::string p = "deconvlist." + std::to_string(j) + ".";
-        auto *w = param(e, p + "conv.weight", (size_t)Co * Ci * 15);
-        auto *b = param(e, p + "conv.bias", Co);
         auto *nw = param(e, p + "norm.weight", Co);
         auto *nb = param(e, p + "norm.bias", Co);
-        if (!w || !b || !nw || !nb) return SE_ERR_PARAM_MISSING;
-        const float *wp = w->data();
-        auto wsel = [=](int ci, int co, int kf, int kt) { return wp[(((size_t)ci * Co + co) * 5 + kf) * 3 + kt]; };
-        std::vector<std::array<int, 4>> te, to;
-        for (int kf = 0; kf < 5; kf += 2)
-            for (int kt = 0; kt < 3; kt++) te.push_back({kf, kt, 2 - kt, 2 - kf / 2});
-        for (int kf = 1; kf < 5; kf += 2)
-            for (int kt = 0; kt < 3; kt++) to.push_back({kf, kt, 2 - kt, 1 + (3 - kf) / 2});
-        int rc = 0;
-        bool merged = false;
-        if (Co > 4 && Co <= 16) {
-            // narrow block: both parities in ONE 15-tap launch, rows (2c, 2c+1) = (even, odd) parity of channel c (ConvArgs::par_rows)
-            std::vector<std::array<int, 4>> tu;
-            for (int kf = 0; kf < 5; kf++)
-                for (int kt = 0; kt < 3; kt++) tu.push_back({kf, kt, 2 - kt, (kf & 1) ? 1 + (3 - kf) / 2 : 2 - kf / 2});
-            std::vector<float> bias2(2 * Co);
-            for (int c = 0; c < Co; c++) bias2[2 * c] = bias2[2 * c + 1] = (*b)[c];
-            rc = plan_conv(e, e->lv[j].dec_even, Ci, 2 * Co, Fi, Fi, Fo, 1, 2, 0, 1, 0, 3, d, Fi + 2, tu,
-                           [=](int ci, int row, int kf, int kt) { return ((row & 1) == (kf & 1)) ? wsel(ci, row >> 1, kf, kt) : 0.0f; },
-                           bias2, 0, 2 * Co, e->act, /*Cy=*/Co);
-            if (rc) return rc;
-            merged = e->lv[j].dec_even.x6;
-            if (merged) { e->lv[j].dec_even.a.par_rows = 1; e->lv[j].dec_odd.active = false; e->lv[j].dec_odd.grid_x = 0; }
-        }
-        if (!merged) {
-            rc = plan_conv(e, e->lv[j].dec_even, Ci, Co, Fi, Fi, Fo, 1, 2, 0, 1, 0, 3, d, Fi + 2, te, wsel, *b, 0, Co, e->act);
-            if (rc) return rc;
-            rc = plan_conv(e, e->lv[j].dec_odd, Ci, Co, Fi - 1, Fi, Fo, 1, 2, 1, 1, 0, 3, d, Fi + 2, to, wsel, *b, 0, Co, e->act);
-            if (rc) return rc;
-        }
-        // SURVEY 8d counts a transposed conv as Cin*Cout*15*Fi*T MACs; split 9:6 over the two parity launches
-        e->lv[j].dec_even.flops = 2.0 * Ci * Co * (merged ? 15 : 9) * Fi * e->T;
-        e->lv[j].dec_odd.flops = merged ? 0.0 : 2.0 * Ci * Co * 6 * Fi * e->T;
+        if (!nw || !nb) return SE_ERR_PARAM_MISSING;
+        int rc;
         if ((rc = dev_upload(e, e->lv[j].dec_nw, *nw))) return rc;
         if ((rc = dev_upload(e, e->lv[j].dec_nb, *nb))) return rc;
         if (lvl > 0) {  // skip path (CRN.py:485-487): the residualnorm affine of the gate (the 1x1 pair is planned in prepare_weights_p)
@@ -578,45 +424,17 @@ int prepare_weights(se_engine *e) {
     return 0;
 }
 
-// Picks, for the current batch, the k_conv_x6 tiling with the least modelled time.  Measured on MI355X (NT sweep,
-// profiles/r01_v4_conv_nt_sweep.txt): a workgroup costs ~(NT + 0.28) units (the constant is the first weight fragments and
-// the barriers), and a partial last round of resident workgroups costs about its share (a workgroup alone on a CU gets the
-// matrix pipe to itself), so time ~ workgroups x (NT + 0.28), quantised only when the whole launch is below one round.
-void select_conv_geometry(se_engine *e, ConvPlan &pl) {
-    if (!pl.active || !pl.x6) return;
-    const double slots = 2.0 * e->num_cu;
-    double best = 0;
-    int pick = -1;
-    for (int k = 0; k < 4; k++) {
-        const ConvPlan::Geo &g = pl.geo[k];
-        if (!g.NT) continue;
-        const double rounds = std::max(1.0, (double)g.n_wg * e->B / slots);
-        const double cost = rounds * (g.NT + 0.28);
-        if (pick < 0 || cost <= best) { best = cost; pick = k; }
-    }
-    const ConvPlan::Geo &g = pl.geo[pick];
-    pl.NT = g.NT; pl.grid_x = g.n_wg; pl.lds = g.lds;
-    pl.a.tiles_per_wg = g.tpw; pl.a.grouped = g.grouped;
-}
-
 int launch_conv(se_engine *e, const ConvPlan &pl, const float *x, const float *xprev, float *y, hipStream_t st, const char *label,
                 float *stats = nullptr, int nslot = 0, int slot0 = 0, int stats_lo = 0, int stats_hi = 0) {
     if (!pl.active) return 0;
     // algorithmic MACs of this launch as SURVEY.md 8d counts them are attributed by the caller via pl.flops
-    ProfScope ps(e, pl.x6 ? "k_conv_x6" : (pl.NT == 0 ? "k_conv_small" : "k_conv_igemm"), label, pl.flops * e->B, st);
+    ProfScope ps(e, "k_conv_small", label, pl.flops * e->B, st);
     ConvArgs a = pl.a;
     a.x = x; a.xprev = xprev; a.y = y; a.w = pl.w.p; a.bias = pl.bias.p; a.gatew = pl.gatew.p;
     a.stats = stats; a.stats_nslot = nslot; a.stats_slot0 = slot0; a.stats_lo = stats_lo; a.stats_hi = stats_hi;
     dim3 grid(pl.grid_x, e->B);
-    if (pl.x6) {
-        ConvX6Args xa{a, reinterpret_cast<const uint4 *>(pl.wx.p)};
-        if (conv_x6_launch(a.ntap, pl.NT, operand_planes(e->precision), grid, pl.lds, st, xa))
-            return fail(e, SE_ERR_ARG, "no x6 conv kernel instance for %d taps x %d tiles", a.ntap, pl.NT);
-        HIPCHECK(e, hipGetLastError());
-        return 0;
-    }
-    if (conv_igemm_launch(a.ntap, pl.NT, a.CoPad, grid, pl.lds, st, a))
-        return fail(e, SE_ERR_ARG, "no conv kernel instance for %d taps x %d tiles", a.ntap, pl.NT);
+    if (conv_igemm_launch(a.ntap, /*NT=*/0, a.CoPad, grid, pl.lds, st, a))  // NT 0: the vector-ALU instances
+        return fail(e, SE_ERR_ARG, "no small conv kernel instance for %d taps", a.ntap);
     HIPCHECK(e, hipGetLastError());
     return 0;
 }
@@ -710,7 +528,7 @@ int launch_gln_ew(se_engine *e, const float *x, float *y, const float *w, const 
 // TemporalCRN.forward on device in three stages (stage_encoder_p, the bottleneck below, stage_decoder_p); each reads/writes the
 // ring slot `cur` (history from slot `prev`).  spec: (b, m, t, f) strides; out: (b, t, f) strides (cf2 units).
 // CRN_ELU / student with the pre-conv blocks on the vector-ALU kernel (convp_engine.inc.h: all but fp16 operands): features
-// (CRN.py:463-467) and the three frequency-dilated pre-conv blocks -> xin[0][cur] (fp32)
+// (CRN.py:463-467) and the three frequency-dilated pre-conv blocks -> pre_out (fp32)
 int stage_features_pre(se_engine *e, int cur, const cf2 *spec, long sB, long sM, long sT, long sF, hipStream_t st) {
     const int T = e->T, B = e->B;
     int rc;
@@ -729,7 +547,7 @@ int stage_features_pre(se_engine *e, int cur, const cf2 *spec, long sB, long sM,
         const int ns = e->lv[i].pre.grid_x;
         if ((rc = launch_conv(e, e->lv[i].pre, e->pin[i][pcur].p, e->pin[i][pprev].p, e->pre_g.p, st, ("pre" + std::to_string(i)).c_str(),
                               e->pre_stats[i].p, ns, 0, 0, C0))) return rc;
-        float *dst = i + 1 < e->npre ? e->pin[i + 1][pcur].p : e->xin[0][cur].p;
+        float *dst = i + 1 < e->npre ? e->pin[i + 1][pcur].p : e->pre_out.p;
         if ((rc = launch_gln_ew(e, e->pre_g.p, dst, e->lv[i].pre_nw.p, e->lv[i].pre_nb.p, e->pre_stats[i].p, ns, n, 0, C0, T, F0, st,
                                 e->pin[i][pcur].p))) return rc;
     }
@@ -1009,73 +827,34 @@ int ensure_ready(se_engine *e) {
             if ((rc = alloc_stats_p(e))) return rc;
         }
     }
-    if (replanned && e->B > 0)  // new weights re-made the plans with their default tiling: restore the per-batch choice
-        for (int i = 0; i < SE_MAX_LEVELS; i++)
-            for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].pre})
-                select_conv_geometry(e, *p);
     return 0;
 }
 
 }  // namespace
 
 namespace {
-// P layout [b][octet][plane][t][f] (16-byte pieces of 8 channels) -> fp32 [b][c][t][f]: the operands of a feature-tap re-run
-// PAIR: the planes are the fp16 pair (PL = 2), joined as join2h joins them
-template <int PL, bool PAIR = false>
-__global__ void k_tap_p_to_f32(const uint4 *P, float *dst, int B, int C, int T, int F) {
+// R layout [b][C8][npos][8] fp32 (the pre-norm output of k_conv_p: a feature-tap re-run) -> [b][c][f][t], the reference's feature-map
+// layout (distillation_crn.py:467-477).  (t, f) sits at position t * oT + f, or, parity-planar (Fh > 0: the two output-frequency
+// parities of a transposed convolution side by side), at t * oT + (f & 1) * Fh + (f >> 1).  One thread per (b, octet, f, t): 32 bytes in,
+// eight columns out, coalesced over t.
+__global__ void k_tap_r_to_bcft(const float *R, float *dst, int B, int C, int T, int F, int oT, int Fh) {
     const int C8 = (C + 7) >> 3;
-    const long n = (long)B * C8 * T * F;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const long tf = i % ((long)T * F), bo = i / ((long)T * F);
-        const int o = (int)(bo % C8), b = (int)(bo / C8);
-        float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if constexpr (PAIR) {
-            typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-            const u16x8 hi = __builtin_bit_cast(u16x8, P[(((long)b * C8 + o) * PL) * T * F + tf]);
-            const u16x8 lo = __builtin_bit_cast(u16x8, P[(((long)b * C8 + o) * PL + 1) * T * F + tf]);
-#pragma unroll
-            for (int c = 0; c < 8; c++) v[c] = join2h(hi[c], lo[c]);
-        }
-#pragma unroll
-        for (int pl = 0; pl < (PAIR ? 0 : PL); pl++) {
-            const uint4 q = P[(((long)b * C8 + o) * PL + pl) * T * F + tf];
-            if (PL == 1) {
-                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                const h8 h = __builtin_bit_cast(h8, q);
-#pragma unroll
-                for (int c = 0; c < 8; c++) v[c] += (float)h[c];
-            } else {
-                const bf16x8 h = __builtin_bit_cast(bf16x8, q);
-#pragma unroll
-                for (int c = 0; c < 8; c++) v[c] += (float)h[c];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            if (o * 8 + c < C) dst[((long)b * C + o * 8 + c) * T * F + tf] = v[c];
-    }
-}
-// [b][c][t][f] -> [b][c][f][t] (the reference's feature-map layout, distillation_crn.py:467-477)
-__global__ void k_tap_tf_to_ft(const float *src, float *dst, long BC, int T, int F) {
-    const long n = BC * T * F;
+    const long n = (long)B * C8 * F * T;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int t = (int)(i % T);
-        const long r = i / T;
+        long r = i / T;
         const int f = (int)(r % F);
-        const long bc = r / F;
-        dst[i] = src[(bc * T + t) * F + f];
+        r /= F;
+        const int o = (int)(r % C8);
+        const long b = r / C8;
+        const long pos = (long)t * oT + (Fh ? (f & 1) * Fh + (f >> 1) : f);
+        const float4 *src = reinterpret_cast<const float4 *>(R + ((b * C8 + o) * (long)T * oT + pos) * 8);
+        const float4 lo = src[0], hi = src[1];
+        const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+        for (int c = 0; c < 8; c++)
+            if (o * 8 + c < C) dst[((b * C + o * 8 + c) * F + f) * T + t] = v[c];
     }
-}
-int tap_p_to_f32_dev(se_engine *e, const float *psrc, PlaneBuf kind, int C, int F, float *dst, hipStream_t st) {
-    const int PL = operand_planes(e->precision);
-    const dim3 g(1024), b(256);
-    const uint4 *P = reinterpret_cast<const uint4 *>(psrc);
-    if (act_format(e, kind) == PlaneFmt::kF16Pair) hipLaunchKernelGGL((k_tap_p_to_f32<kPairPlanesA, true>), g, b, 0, st, P, dst, e->B, C, e->T, F);
-    else if (PL == 1) hipLaunchKernelGGL(k_tap_p_to_f32<1>, g, b, 0, st, P, dst, e->B, C, e->T, F);
-    else if (PL == 2) hipLaunchKernelGGL(k_tap_p_to_f32<2>, g, b, 0, st, P, dst, e->B, C, e->T, F);
-    else hipLaunchKernelGGL(k_tap_p_to_f32<3>, g, b, 0, st, P, dst, e->B, C, e->T, F);
-    HIPCHECK(e, hipGetLastError());
-    return 0;
 }
 }  // namespace
 
@@ -1197,17 +976,16 @@ void se_destroy(se_engine *e) {
     g_cp_trace_sites.dump();
 #endif
     DevBuf *singles[] = {&e->fcw, &e->fcb, &e->gnw, &e->gnb, &e->maskspec,
-                         &e->fcw_x, &e->wih_xp, &e->fcw_xp, &e->fcb_p, &e->gnw_p, &e->gnb_p, &e->fc_stats, &e->pre_g, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
+                         &e->fcw_x, &e->wih_xp, &e->fcw_xp, &e->fcb_p, &e->gnw_p, &e->gnb_p, &e->fc_stats, &e->pre_g, &e->pre_out, &e->spec_all, &e->mask_all, &e->fc_out, &e->yseg};
     for (DevBuf *b : singles) dev_free(*b);
     dev_free(e->plan_dev);
     for (DevBuf &b : e->carry_x) dev_free(b);
     for (DevBuf &b : e->carry_p) dev_free(b);
     for (DevBuf &b : e->carry_h) dev_free(b);
     for (int r = 0; r < kRing; r++) {
-        dev_free(e->spec[r]); dev_free(e->gru_in[r]); dev_free(e->dec_in[r]); dev_free(e->gi0[r]); dev_free(e->gruinP[r]);
+        dev_free(e->spec[r]); dev_free(e->gru_in[r]); dev_free(e->gi0[r]); dev_free(e->gruinP[r]);
         for (int l = 0; l < 4; l++) dev_free(e->seqP[l][r]);
         for (int l = 0; l < 4; l++) dev_free(e->seqr[l][r]);
-        for (int i = 0; i < SE_MAX_LEVELS; i++) dev_free(e->xin[i][r]);
         if (e->stage_ready) { (void)hipEventDestroy(e->ev_enc[r]); (void)hipEventDestroy(e->ev_dec[r]); (void)hipEventDestroy(e->ev_gru[r]); }
     }
     if (e->stage_ready) {
@@ -1220,9 +998,8 @@ void se_destroy(se_engine *e) {
     }
     for (int i = 0; i < SE_MAX_LEVELS; i++) {
         Level &l = e->lv[i];
-        for (ConvPlan *p : {&l.enc, &l.dec_even, &l.dec_odd, &l.pre}) { dev_free(p->w); dev_free(p->bias); dev_free(p->wx); dev_free(p->gatew); }
+        dev_free(l.pre.w); dev_free(l.pre.bias); dev_free(l.pre.gatew);
         for (DevBuf *b : {&l.enc_nw, &l.enc_nb, &l.dec_nw, &l.dec_nb, &l.dec_mnw, &l.dec_mnb}) dev_free(*b);
-        dev_free(e->dec_out[i]);
         dev_free(e->enc_stats[i]); dev_free(e->dec_stats[i]); dev_free(e->skip_stats[i]);
         dev_free(l.pre_nw); dev_free(l.pre_nb);
         if (i < 3) { dev_free(e->pin[i][0]); dev_free(e->pin[i][1]); dev_free(e->pre_stats[i]); }
@@ -1273,21 +1050,10 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
     // a few streams give the bottleneck GEMMs a few hundred rows: a 256 x 128 tile per workgroup leaves 12-36 workgroups
     // walking K = 2048 alone (124 us at B = 1); the skinny 32 x 32-tile fp32 kernel (K split over the waves) takes 24
     select_gemm_route(e);
-    for (int i = 0; i < SE_MAX_LEVELS; i++)
-        for (ConvPlan *p : {&e->lv[i].enc, &e->lv[i].dec_even, &e->lv[i].dec_odd, &e->lv[i].pre})
-            select_conv_geometry(e, *p);
     size_t spec_n = (size_t)B * (stft_feat_route(e) ? 1 : e->M) * T * F0 * 2;  // the fused front end keeps microphone 0's spectrum only
     if (!e->io_fuse_on && (rc = dev_alloc(e, e->maskspec, (size_t)B * T * F0 * 2))) return rc;
     for (int r = 0; r < kRing; r++)
-        if ((rc = dev_alloc(e, e->spec[r], spec_n)) || (rc = dev_alloc(e, e->gru_in[r], (size_t)B * T * D)) || (rc = dev_alloc(e, e->dec_in[r], (size_t)B * T * D))) return rc;
-    for (int i = 0; i < L; i++) {
-        const size_t nin = (size_t)B * e->Ch[i] * T * e->F[i];
-        for (int r = 0; r < kRing; r++)
-            if ((rc = dev_alloc(e, e->xin[i][r], nin))) return rc;
-        HIPCHECK(e, hipMemsetAsync(e->xin[i][0].p, 0, nin * sizeof(float), st));  // slot 0 = the all-zero history of the first segment
-        const int lvl = L - 1 - i;  // decoder index i
-        if (lvl > 0 && (rc = dev_alloc(e, e->dec_out[i], (size_t)B * e->Ch[lvl] * T * e->F[lvl]))) return rc;
-    }
+        if ((rc = dev_alloc(e, e->spec[r], spec_n)) || (rc = dev_alloc(e, e->gru_in[r], (size_t)B * T * D))) return rc;
     for (int i = 0; i < e->npre; i++) {
         const size_t nf = (size_t)B * e->Ch[0] * T * F0;
         for (int p = 0; p < 2; p++) {
@@ -1295,7 +1061,7 @@ static int reset_on_stream(se_engine *e, int batch, hipStream_t st) {
             HIPCHECK(e, hipMemsetAsync(e->pin[i][p].p, 0, nf * sizeof(float), st));
         }
         if ((rc = dev_alloc(e, e->pre_stats[i], (size_t)B * 2 * (e->lv[i].pre.grid_x + 1)))) return rc;
-        if ((rc = dev_alloc(e, e->pre_g, nf))) return rc;
+        if ((rc = dev_alloc(e, e->pre_g, nf)) || (rc = dev_alloc(e, e->pre_out, nf))) return rc;
     }
     const size_t fcND = (size_t)(e->Ch[L] + 7) / 8 * e->F[L] * 8;  // fc output columns on the plane GEMM route (channels in whole octets)
     if ((rc = dev_alloc(e, e->fc_out, (size_t)B * T * std::max<size_t>(D, fcND)))) return rc;
@@ -1701,67 +1467,61 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
         // Pre-activation feature maps of the distillation student (distillation_crn.py:222-228, 126-128, 262-264, 467-477):
         // ft0 = last encoder block's convolution output, ft1 = fc_output_layer output ([B, T, D] memory viewed as [B, C, F, T],
         // distillation_crn.py:364), ft2.. = transposed-convolution outputs of decoder blocks 0..L-2 (before activation, norm and
-        // frequency padding).  The hot path fuses the activation into the producing kernel, so the tap RE-RUNS that one kernel
-        // without activation on the inputs still held in the ring slot; nothing on the inference path pays for it.
+        // frequency padding).  The hot path fuses the activation into the producing kernel, so the tap RE-RUNS that one launch
+        // (launch_enc_conv_p / launch_dec_conv_p, as the stage makes it) without activation and statistics on the planes still held
+        // in the ring slot, into a scratch buffer in the R layout; k_tap_r_to_bcft transposes it.  Nothing on the inference path
+        // pays for it.  ft1 is one GEMM on the last layer's sequence.
         const int prev = (cur + kRing - 1) % kRing;
         int rc = ensure_ready(e);
         if (rc) return rc;
-        DevBuf tmp;
-        // The operands of the re-run live in the P layout: k_tap_p_to_f32 sums the planes back into the fp32 buffers the
-        // re-run reads (a tap is a training / debugging aid, not part of the hot path).
-        auto p_to_f32 = [&](const float *psrc, PlaneBuf kind, int C_, int F_, float *dst) -> int { return tap_p_to_f32_dev(e, psrc, kind, C_, F_, dst, st); };
-        auto finish = [&](int C_, int F_, bool raw_flat) -> int {
+        se_convp_state &S = *e->cp;
+        struct AllStreams {  // launch_conv_p covers Bact streams: the tap covers the allocation batch
+            se_engine *e; int keep;
+            ~AllStreams() { e->Bact = keep; }
+        } all_streams{e, e->Bact};
+        e->Bact = B;
+        struct Scratch {
+            DevBuf r, t;  // the re-run's output; the transposed map of the host form
+            ~Scratch() { dev_free(r); dev_free(t); }
+        } tmp;
+        // oT / Fh: the R layout's positions (k_tap_r_to_bcft); oT = 0: tmp.r already holds [B, T, D] = [B, C, F, T] memory (ft1)
+        auto finish = [&](int C_, int F_, int oT, int Fh) -> int {
             const size_t n_ = (size_t)B * C_ * T * F_;
             if (count) *count = (int64_t)n_;
-            if ((int64_t)n_ > capacity) { dev_free(tmp); return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n_); }
-            if (dev_out) {  // stays on the device: a copy (ft1: already [B, T, D] = [B, C, F, T] memory) or one transposition
-                hipError_t er;
-                if (raw_flat) er = hipMemcpyAsync(dev_out, tmp.p, n_ * sizeof(float), hipMemcpyDeviceToDevice, st);
-                else { hipLaunchKernelGGL(k_tap_tf_to_ft, dim3(1024), dim3(256), 0, st, tmp.p, dev_out, (long)B * C_, T, F_); er = hipGetLastError(); }
-                if (er == hipSuccess) er = hipStreamSynchronize(st);  // tmp is freed below (the re-run itself is the expensive part)
-                dev_free(tmp);
-                return er == hipSuccess ? SE_OK : fail(e, SE_ERR_HIP, "tap copy failed: %s", hipGetErrorString(er));
-            }
-            std::vector<float> h(n_);
-            hipError_t st1 = hipStreamSynchronize(st), st2 = hipMemcpy(h.data(), tmp.p, n_ * sizeof(float), hipMemcpyDeviceToHost);
-            dev_free(tmp);
-            if (st1 != hipSuccess || st2 != hipSuccess) return fail(e, SE_ERR_HIP, "tap copy failed");
-            if (raw_flat) { memcpy(host_out, h.data(), n_ * sizeof(float)); return SE_OK; }
-            for (int b = 0; b < B; b++)
-                for (int c = 0; c < C_; c++)
-                    for (int t = 0; t < T; t++)
-                        for (int f = 0; f < F_; f++) host_out[(((size_t)b * C_ + c) * F_ + f) * T + t] = h[(((size_t)b * C_ + c) * T + t) * F_ + f];
+            if ((int64_t)n_ > capacity) return fail(e, SE_ERR_ARG, "buffer too small: need %zu floats", n_);
+            // device form: one transposition (or copy) into dev_out; host form: the same launch into tmp.t, then a copy
+            const float *map = tmp.r.p;
+            if (oT) {
+                if (!dev_out && (rc = dev_alloc(e, tmp.t, n_))) return rc;
+                float *dst = dev_out ? dev_out : tmp.t.p;
+                hipLaunchKernelGGL(k_tap_r_to_bcft, dim3(1024), dim3(256), 0, st, tmp.r.p, dst, B, C_, T, F_, oT, Fh);
+                HIPCHECK(e, hipGetLastError());
+                map = dst;
+            } else if (dev_out) HIPCHECK(e, hipMemcpyAsync(dev_out, map, n_ * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIPCHECK(e, hipStreamSynchronize(st));  // the scratch is freed on return (the re-run itself is the expensive part)
+            if (host_out) HIPCHECK(e, hipMemcpy(host_out, map, n_ * sizeof(float), hipMemcpyDeviceToHost));
             return SE_OK;
         };
         if (idx == 0) {
             const int i = L - 1, Co = e->Ch[L], Fo = e->F[L];
-            se_convp_state &S = *e->cp;
-            if ((rc = p_to_f32(S.xinP[i].p + (size_t)cur * S.slot_elems[i] * 4, xin_kind(i), e->Ch[i], e->F[i], e->xin[i][cur].p)) ||
-                (rc = p_to_f32(S.xinP[i].p + (size_t)prev * S.slot_elems[i] * 4, xin_kind(i), e->Ch[i], e->F[i], e->xin[i][prev].p))) return rc;
-            if ((rc = dev_alloc(e, tmp, (size_t)B * Co * T * Fo))) return rc;
-            ConvPlan pl = e->lv[i].enc;
-            pl.a.relu_lo = pl.a.relu_hi = 0;
-            if ((rc = launch_conv(e, pl, e->xin[i][cur].p, e->xin[i][prev].p, tmp.p, st, "tap_ft"))) { dev_free(tmp); return rc; }
-            return finish(Co, Fo, false);
+            const ConvPPlan *pl;
+            if ((rc = tap_enc_plan(e, &pl)) || (rc = dev_alloc(e, tmp.r, (size_t)B * pl->a.y_stream))) return rc;
+            if ((rc = launch_enc_conv_p(e, i, *pl, cur, prev, tmp.r.p, nullptr, nullptr, false, st, "tap_ft"))) return rc;
+            return finish(Co, Fo, Fo, 0);
         }
         if (idx == 1) {
             const int D = e->D, H = e->H;
-            if ((rc = dev_alloc(e, tmp, (size_t)B * T * D))) return rc;
-            if ((rc = launch_gemm(e, e->seqr[e->NL - 1][cur].p, H, e->fcw.p, H, e->fcb.p, tmp.p, D, B * T, D, H, 0, st, "tap_ft", e->fcw_x.p))) { dev_free(tmp); return rc; }
-            return finish(e->Ch[L], e->F[L], true);
+            if ((rc = dev_alloc(e, tmp.r, (size_t)B * T * D))) return rc;
+            if ((rc = launch_gemm(e, e->seqr[e->NL - 1][cur].p, H, e->fcw.p, H, e->fcb.p, tmp.r.p, D, B * T, D, H, 0, st, "tap_ft", e->fcw_x.p))) return rc;
+            return finish(e->Ch[L], e->F[L], 0, 0);
         }
         const int j = idx - 2, lvl = L - 1 - j;
         if (lvl <= 0) return fail(e, SE_ERR_KEY, "unknown tap %s", name);
-        const int Co = e->Ch[lvl], Fo = 2 * e->F[lvl + 1] - 1;
-        if ((rc = dev_alloc(e, tmp, (size_t)B * Co * T * Fo))) return rc;
-        float *xin = j == 0 ? e->dec_in[cur].p : e->dec_out[j - 1].p;
-        se_convp_state &S = *e->cp;
-        if ((rc = p_to_f32(j == 0 ? S.decinP[cur].p : S.decP[j - 1].p, PlaneBuf::kConvAct, e->Ch[lvl + 1], e->F[lvl + 1], xin))) { dev_free(tmp); return rc; }
-        ConvPlan pe = e->lv[j].dec_even, po = e->lv[j].dec_odd;
-        pe.a.relu_lo = pe.a.relu_hi = 0;
-        po.a.relu_lo = po.a.relu_hi = 0;
-        if ((rc = launch_conv(e, pe, xin, nullptr, tmp.p, st, "tap_ft")) || (rc = launch_conv(e, po, xin, nullptr, tmp.p, st, "tap_ft"))) { dev_free(tmp); return rc; }
-        return finish(Co, Fo, false);
+        const int Co = e->Ch[lvl], Fi = e->F[lvl + 1];
+        if ((rc = dev_alloc(e, tmp.r, (size_t)B * S.pv[j].dec_even.a.y_stream))) return rc;
+        const float *xin = j == 0 ? S.decinP[cur].p : S.decP[j - 1].p;
+        if ((rc = launch_dec_conv_p(e, j, reinterpret_cast<const uint4 *>(xin), tmp.r.p, nullptr, false, st, "tap_ft"))) return rc;
+        return finish(Co, 2 * Fi - 1, 2 * Fi, Fi);
     }
     return fail(e, SE_ERR_KEY, "unknown tap %s", name);
 }

@@ -469,8 +469,9 @@ def test_fsn_window_pipeline_is_bit_identical_to_one_stream(monkeypatch):
 
 @pytest.mark.parametrize("precision", [0, 2, 1])
 def test_student_feature_taps_device_form_equals_host_form(precision):
-    """se_read_tap_dev("ft<k>") (planes summed back by k_tap_p_to_f32, the re-run, one device transposition) writes exactly what the
-    host tap returns, at the full student geometry and in every operand format (3 / 2 bf16 planes, one fp16 plane)."""
+    """se_read_tap_dev("ft<k>") (the k_conv_p re-run on the planes in the ring slot, one device transposition k_tap_r_to_bcft) writes
+    exactly what the host tap returns (the same two launches and a copy), at the full student geometry and in every operand format
+    (3 / 2 bf16 planes, one fp16 plane)."""
     e = _engine(STUDENT400, 2, precision=precision, seed=1)
     mix, _ = synth.synth_utterances(3, 6400, 3, seed=31)
     e.reset(3)
