@@ -547,7 +547,14 @@ int se_gtsa_out(const float *g, int ldg, const float *nw, const float *nb, const
  * se_hifi_seqnorm: o [B][Nc][T][D = C F] (the fc output before its tanh) -> y [S][C][T][F] = (tanh(o) - g) w[d] + bias[d], g the
  *   running mean of the utterance after the window: g = alpha g + (1 - alpha) mean_{T x D}(tanh(o)), alpha = step / (step + D),
  *   step += D per window, starting from mean_in [B] and `step` (zeros and 0: nothing carried); wm [B Nc] scratch (receives g per
- *   window), mean_out [B] = g after the last window. */
+ *   window), mean_out [B] = g after the last window.
+ * Chunk chains (every row / utterance on its own schedule; a row's arithmetic is bit for bit the plain entry point's on that row alone):
+ * se_hifi_lstm_rows: steps = device int32 [B], values in [0, TT], any order: row b runs steps[b] steps; out[b][steps[b]:] = 0,
+ *   hT[b] / cT[b] after its own last step (h0[b] / c0[b] at 0 steps); still one launch per step, TT of them, and a workgroup whose
+ *   eight rows have all finished returns at once.
+ * se_hifi_seqnorm_rows: step, cnt = device int64 [B]: utterance b scans its first cnt[b] of the Nc windows from its own step[b];
+ *   mean_out[b] after its own last window (mean_in[b] at cnt[b] = 0); the windows past cnt[b] are normalised by that mean (finite,
+ *   nobody's result). */
 int se_hifi_postnet(const float *x, const float *pack, float *y, int S, int T, int F, void *stream);
 int se_hifi_gate(const float *x, float *y, int64_t n, void *stream);
 int se_hifi_skip(const float *yd, const float *uv, float *out, int S, int Co, int T, int Fy, int Fr, void *stream);
@@ -556,6 +563,10 @@ int se_hifi_lstm(const float *gi, const float *h0, const float *c0, const float 
                  void *stream);
 int se_hifi_seqnorm(const float *o, const float *w, const float *bias, const float *mean_in, double step, float *wm, float *mean_out, float *y,
                     int Nc, int B, int C, int T, int F, void *stream);
+int se_hifi_lstm_rows(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, const int *steps, int B,
+                      int TT, int H, void *stream);
+int se_hifi_seqnorm_rows(const float *o, const float *w, const float *bias, const float *mean_in, const int64_t *step, const int64_t *cnt, float *wm,
+                         float *mean_out, float *y, int Nc, int B, int C, int T, int F, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -22,6 +22,8 @@
 //   k_hifi_winmean / k_hifi_scan / k_hifi_normapply   the bottleneck's tanh and running-mean norm: the mean of tanh(o) over T x D per
 //                     window (double partial sums, fixed tree), the per-utterance scan g = alpha g + (1 - alpha) mean with
 //                     alpha = step / (step + D) in double, and y = (tanh(o) - g) w + b written back in [S][C][T][F]
+//   k_hifi_lstm_step<true> / k_hifi_scan_rows   chunk chains (se_hifi_lstm_rows, se_hifi_seqnorm_rows): every row its own number of
+//                     steps, every utterance its own window count and its own step; a row's arithmetic is the plain kernels'
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -162,17 +164,36 @@ struct LstmArgs {
     float *out, *cout, *hT;
     long ldgi, ldh, ldo;
     int B, H;
+    const int *steps;   // kRows: row b runs steps[b] steps, this launch is step t of them
+    int t;
 };
 
+// kRows (chunk chains): a row is live at step t while t < steps[row].  A live row computes what it computes in the plain kernel - the
+// dot products of a row never see another row's h - and a finished one writes a zero into out[row][t] (the fc GEMM and the window
+// means read all of out), at t = 0 also its h0 / c0 into hT / cT (steps = 0).  The last live step of a row writes its hT.
+template <bool kRows>
 __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
     __shared__ float pre[4][kLstmBT];
     extern __shared__ float hs[];   // [kLstmBT][H]: the batch tile's h rows, read from memory once per workgroup, zeros past the batch
     const int gate = threadIdx.x >> 6, lane = threadIdx.x & 63;   // wave g: gate g (i, f, g, o) of hidden unit j for 8 batch rows
     const int j = blockIdx.x, b0 = blockIdx.y * kLstmBT;
     const int nb = min(kLstmBT, a.B - b0);
+    if (kRows) {
+        bool any = false;   // the same for every thread of the workgroup
+        for (int b = 0; b < nb; b++) any |= a.t < a.steps[b0 + b];
+        if ((int)threadIdx.x < nb && a.t >= a.steps[b0 + threadIdx.x]) {
+            const long row = b0 + threadIdx.x;
+            a.out[row * a.ldo + j] = 0.0f;
+            if (a.t == 0) {
+                a.hT[row * a.H + j] = a.hin[row * a.ldh + j];
+                a.cout[row * a.H + j] = a.cin[row * a.H + j];
+            }
+        }
+        if (!any) return;   // all eight rows have finished: nothing to stage
+    }
     for (int i = threadIdx.x; i < kLstmBT * a.H; i += kThreads) {
         const int b = i / a.H, k = i - b * a.H;
-        hs[i] = b < nb ? a.hin[(long)(b0 + b) * a.ldh + k] : 0.0f;
+        hs[i] = b < nb && (!kRows || a.t < a.steps[b0 + b]) ? a.hin[(long)(b0 + b) * a.ldh + k] : 0.0f;
     }
     __syncthreads();
     const float *w = a.whh + ((long)gate * a.H + j) * a.H;
@@ -190,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
         if (lane == 0) pre[gate][b] = acc[b];
     }
     __syncthreads();
-    if ((int)threadIdx.x < nb) {
+    if ((int)threadIdx.x < nb && (!kRows || a.t < a.steps[b0 + threadIdx.x])) {
         const int b = threadIdx.x;
         const long row = b0 + b;
         const float *gi = a.gi + row * a.ldgi;
@@ -200,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
         const float h = og * tanhf(c);
         a.cout[row * a.H + j] = c;
         a.out[row * a.ldo + j] = h;
-        if (a.hT) a.hT[row * a.H + j] = h;
+        if (kRows ? a.t == a.steps[row] - 1 : a.hT != nullptr) a.hT[row * a.H + j] = h;
     }
 }
 
@@ -234,6 +255,27 @@ __global__ void k_hifi_scan(float *__restrict__ wm, const float *__restrict__ me
     mean_out[b] = g;
 }
 
+// chunk chains: utterance b scans its own first cnt[b] windows from its own step[b]; a window past them receives the utterance's
+// last running mean (finite values for k_hifi_normapply, which nothing reads), and cnt[b] = 0 hands mean_in[b] on
+__global__ void k_hifi_scan_rows(float *__restrict__ wm, const float *__restrict__ mean_in, float *__restrict__ mean_out, const int64_t *__restrict__ step0,
+                                 const int64_t *__restrict__ cnt, int B, int Nc, int D) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float g = mean_in[b];
+    double step = (double)step0[b];
+    const int64_t c = cnt[b];
+    const int own = c < 0 ? 0 : c > Nc ? Nc : (int)c;
+    for (int n = 0; n < Nc; n++) {
+        if (n < own) {
+            const double alpha = step / (step + (double)D);
+            g = __fadd_rn(__fmul_rn((float)alpha, g), __fmul_rn((float)(1.0 - alpha), wm[b * Nc + n]));
+            step += (double)D;
+        }
+        wm[b * Nc + n] = g;
+    }
+    mean_out[b] = g;
+}
+
 __global__ __launch_bounds__(kThreads) void k_hifi_normapply(const float *__restrict__ o, const float *__restrict__ g, const float *__restrict__ w,
                                                              const float *__restrict__ bias, float *__restrict__ y, int Nc, int B, int C_, int T, int F) {
     const int D = C_ * F, i = blockIdx.x * kThreads + threadIdx.x;
@@ -253,6 +295,30 @@ int blocks_of(const char *what, long n, unsigned *blocks) {
     if (n <= 0 || nb > 0x7fffffffL) return se::train_fail(SE_ERR_ARG, "%s: %ld elements (1 .. 2^31 - 1 workgroups of %d)", what, n, kThreads);
     *blocks = (unsigned)nb;
     return SE_OK;
+}
+
+// one launch per step; steps = null: every row runs all TT steps (k_hifi_lstm_step<false>, which never reads a.steps / a.t)
+int lstm_launch(const char *what, const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, const int *steps,
+                int B, int TT, int H, void *stream) {
+    if (!gi || !h0 || !c0 || !whh || !out || !hT || !cT) return se::train_fail(SE_ERR_ARG, "%s: null argument", what);
+    if (B <= 0 || (B + kLstmBT - 1) / kLstmBT > 65535 || TT <= 0 || H < 8 || H % 8 || H > 1024)
+        return se::train_fail(SE_ERR_ARG, "%s: B = %d rows, %d steps, hidden %d (a multiple of 8, up to 1024)", what, B, TT, H);
+    const dim3 grid(H, (B + kLstmBT - 1) / kLstmBT);
+    for (int t = 0; t < TT; t++) {
+        LstmArgs a;
+        a.gi = gi + (long)t * 4 * H, a.ldgi = (long)TT * 4 * H;
+        a.hin = t ? out + (long)(t - 1) * H : h0, a.ldh = t ? (long)TT * H : H;
+        a.cin = t ? cT : c0, a.cout = cT;   // a cell is read and written by one lane only: in place from the second step on
+        a.whh = whh, a.out = out + (long)t * H, a.ldo = (long)TT * H;
+        a.hT = steps || t == TT - 1 ? hT : nullptr;
+        a.B = B, a.H = H;
+        a.steps = steps, a.t = t;
+        if (steps)
+            hipLaunchKernelGGL(k_hifi_lstm_step<true>, grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
+        else
+            hipLaunchKernelGGL(k_hifi_lstm_step<false>, grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
+    }
+    return launched(what);
 }
 
 }  // namespace
@@ -305,21 +371,13 @@ int se_hifi_rows(const float *x, float *rows, int Nc, int B, int C_, int T, int 
 }
 
 int se_hifi_lstm(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, int B, int TT, int H, void *stream) {
-    if (!gi || !h0 || !c0 || !whh || !out || !hT || !cT) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm: null argument");
-    if (B <= 0 || (B + kLstmBT - 1) / kLstmBT > 65535 || TT <= 0 || H < 8 || H % 8 || H > 1024)
-        return se::train_fail(SE_ERR_ARG, "se_hifi_lstm: B = %d rows, %d steps, hidden %d (a multiple of 8, up to 1024)", B, TT, H);
-    const dim3 grid(H, (B + kLstmBT - 1) / kLstmBT);
-    for (int t = 0; t < TT; t++) {
-        LstmArgs a;
-        a.gi = gi + (long)t * 4 * H, a.ldgi = (long)TT * 4 * H;
-        a.hin = t ? out + (long)(t - 1) * H : h0, a.ldh = t ? (long)TT * H : H;
-        a.cin = t ? cT : c0, a.cout = cT;   // a cell is read and written by one lane only: in place from the second step on
-        a.whh = whh, a.out = out + (long)t * H, a.ldo = (long)TT * H;
-        a.hT = t == TT - 1 ? hT : nullptr;
-        a.B = B, a.H = H;
-        hipLaunchKernelGGL(k_hifi_lstm_step, grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
-    }
-    return launched("se_hifi_lstm");
+    return lstm_launch("se_hifi_lstm", gi, h0, c0, whh, out, hT, cT, nullptr, B, TT, H, stream);
+}
+
+int se_hifi_lstm_rows(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, const int *steps, int B, int TT, int H,
+                      void *stream) {
+    if (!steps) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_rows: null argument");
+    return lstm_launch("se_hifi_lstm_rows", gi, h0, c0, whh, out, hT, cT, steps, B, TT, H, stream);
 }
 
 int se_hifi_seqnorm(const float *o, const float *w, const float *bias, const float *mean_in, double step, float *wm, float *mean_out, float *y, int Nc, int B,
@@ -333,6 +391,19 @@ int se_hifi_seqnorm(const float *o, const float *w, const float *bias, const flo
     hipLaunchKernelGGL(k_hifi_scan, dim3((B + 63) / 64), dim3(64), 0, st, wm, mean_in, mean_out, step, B, Nc, D);
     hipLaunchKernelGGL(k_hifi_normapply, dim3((TD + kThreads - 1) / kThreads, Nc * B), dim3(kThreads), 0, st, o, wm, w, bias, y, Nc, B, C_, T, F);
     return launched("se_hifi_seqnorm");
+}
+
+int se_hifi_seqnorm_rows(const float *o, const float *w, const float *bias, const float *mean_in, const int64_t *step, const int64_t *cnt, float *wm, float *mean_out,
+                         float *y, int Nc, int B, int C_, int T, int F, void *stream) {
+    if (!o || !w || !bias || !mean_in || !step || !cnt || !wm || !mean_out || !y) return se::train_fail(SE_ERR_ARG, "se_hifi_seqnorm_rows: null argument");
+    if (Nc <= 0 || B <= 0 || (long)Nc * B > 65535 || C_ <= 0 || T <= 0 || F <= 0 || (long)T * C_ * F > (1L << 30))
+        return se::train_fail(SE_ERR_ARG, "se_hifi_seqnorm_rows: bad geometry (%d windows x %d utterances <= 65535, C %d, T %d, F %d)", Nc, B, C_, T, F);
+    const int D = C_ * F, TD = T * D;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_hifi_winmean, dim3(Nc * B), dim3(kThreads), 0, st, o, wm, TD);
+    hipLaunchKernelGGL(k_hifi_scan_rows, dim3((B + 63) / 64), dim3(64), 0, st, wm, mean_in, mean_out, step, cnt, B, Nc, D);
+    hipLaunchKernelGGL(k_hifi_normapply, dim3((TD + kThreads - 1) / kThreads, Nc * B), dim3(kThreads), 0, st, o, wm, w, bias, y, Nc, B, C_, T, F);
+    return launched("se_hifi_seqnorm_rows");
 }
 
 }  // extern "C"

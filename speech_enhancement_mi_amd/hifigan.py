@@ -6,8 +6,10 @@ Same constructors, state_dict keys and shapes (`*.weight_g` / `*.weight_v`, the 
 
     Generator.forward(x[B, M, F, T, 2], post=True) -> (y, y_before) [B, F, T, 2]    one window, stateful; post=False: (y, None)
     Generator.realtime_process(mixture[B, M, L], post=True, reset=False) -> (pred, pred_before) [B, L]
-    Generator.reset(), reset_norm(), use_hip_kernels(flag), kernel_geometry_error(), max_segments, _last_path, taps
+    Generator.realtime_process_chains(mixture[B, M, Lmax], resets, lengths=None, post=True) -> (pred, pred_before) [B, Lmax]
+    Generator.reset(), reset_norm(streams=None), use_hip_kernels(flag), kernel_geometry_error(), max_segments, _last_path, _last_passes, taps
     Hifi_GAN.forward(x, post=True) = generator.realtime_process(x, reset=False, post=post)[0]
+    Hifi_GAN.realtime_process_chains(x, resets, lengths=None, post=True) = the generator's, its first result
 
 Quirks of the reference that are kept:
   * `reset=True` prepends half a window of zeros, resets and strips the half window (the `flag=False` of the other models);
@@ -22,8 +24,16 @@ Quirks of the reference that are kept:
   * `Hifi_GAN` holds the generator only: `discriminator.*` checkpoint keys are dropped on load, and there is no remove_weight_norm
     (the reference's calls a method that does not exist).
 
-Two paths (the choice, the refusals and the carried state are streaming.StreamingMixin's; `reset` = not `flag`; uniform calls only -
-a list-valued `reset` is refused):
+`realtime_process_chains` serves B independent callers in one call (chunk chains, call_plan.py; `resets[b]` = not `flag[b]`): stream b is
+mixture[b, :, :lengths[b]], resets or continues row b of the carried state on its own, and leaves what it would carry alone.  The norm's
+quirk is kept PER STREAM: resets[b] does not touch mean[b] or stream b's step count, and streams that advance by different window counts
+have different counts - `_nstate["step"]` is one int while they are all equal and a list of B ints (host values, from the plan) once they
+are not; reset_norm(streams=[b]) zeroes one stream's pair, for a slot handed to a new caller.  The restatement runs every stream literally
+alone; the kernel path sorts the streams by window count and runs every pass on the prefix still alive (gtsa.chain_passes), the LSTM and
+the norm's scan stopping at each stream's own last window (se_hifi_lstm_rows, se_hifi_seqnorm_rows).  Resets and lengths all alike are
+the uniform call - `realtime_process`, which still takes ONE `reset`.
+
+Two paths (the choice, the refusals and the carried state are streaming.StreamingMixin's; `reset` = not `flag`):
   * the torch restatement (CPU, grad enabled, training mode, or after use_hip_kernels(False)): plain torch ops, differentiable.
     Encoder, decoder and postnet run every window of a pass at once (the conv history of window n is the tail of window n - 1's
     input); the LSTM - its cell written out, h and c detached at every window seam as the reference does - and the norm's scan are
@@ -41,9 +51,10 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .call_plan import istft_windows, overlap_add_cut, segment_geometry, windows
+from .call_plan import CallPlan, as_flags, istft_windows, overlap_add_cut, segment_geometry, windows
+from .gtsa import chain_passes
 from .streaming import StreamingMixin
-from .train_stages import _new, _p, _run, _sig, input_features, istft, overlap_add, stft
+from .train_stages import _ip, _new, _p, _rows, _run, _sig, gru_steps, input_features, istft, overlap_add, own_last_slab, slab_gather, stft
 
 EPS = 1e-8
 POST_CHANNELS = 128
@@ -143,6 +154,7 @@ class Generator(StreamingMixin, nn.Module):
         # _nstate: None or dict(mean [B], step int), shared by both paths; taps: enc / seq / dec / post of every forward
         self._init_streaming(num_inputs, sample_rate, win_length, hop_length)
         self._nstate = None
+        self._last_passes = None   # kernel path: the passes of the last call, [(first window, windows, streams), ...]
         L = len(num_channels)
         convs, deconvs = [], []
         for i in range(L):
@@ -156,25 +168,52 @@ class Generator(StreamingMixin, nn.Module):
         self.postnet = nn.ModuleList([_Conv(chans[i], chans[i + 1], (1, 1), (1, 1), 1, (0, 0), 0.0) for i in range(POST_LAYERS)])
 
     # ---- reference contract ------------------------------------------------------------------------------------------------
-    def reset_norm(self):
-        """Forget the bottleneck norm's running mean and step count, which reset() keeps as the reference does."""
-        self._nstate = None
+    def reset_norm(self, streams=None):
+        """Forget the bottleneck norm's running mean and step count, which reset() keeps as the reference does.  streams: the rows to
+        forget (their mean and step become 0, which normalises the row's next window by its own mean as a fresh model does - the slot
+        of a caller that left, handed to the next); None: all of it.  Nothing carried: nothing to do."""
+        ns = self._nstate
+        if streams is None or ns is None:
+            self._nstate = None if streams is None else ns
+            return
+        B = ns["mean"].shape[0]
+        rows = sorted({int(b) for b in (streams.reshape(-1).tolist() if torch.is_tensor(streams) else streams)})
+        if rows and not 0 <= rows[0] <= rows[-1] < B:
+            raise ValueError(f"reset_norm(streams={rows}): the running mean is carried for streams 0 .. {B - 1}")
+        mean, steps = ns["mean"].clone(), self._steps_of(ns, B)
+        for b in rows:
+            mean[b], steps[b] = 0.0, 0
+        self._nstate = self._norm_state(mean, steps)
 
     def forward(self, x, post=True):
         """One window [B, M, F, T, 2] -> (y, y_before) on the torch restatement, carrying the encoder buffers, (h, c) and the running mean."""
-        (Y, Yb), self._tstate, self._nstate = self._pass(x[:, :, None], self._tstate, self._norm_for(x.shape[0]), post)
+        ns = self._norm_for(x.shape[0])
+        if ns is not None and isinstance(ns["step"], list):
+            raise ValueError("forward() runs the batch through one norm step count, and the streams' counts differ after a chunk-chain "
+                             "call: use realtime_process, or reset_norm()")
+        (Y, Yb), self._tstate, self._nstate = self._pass(x[:, :, None], self._tstate, ns, post)
         return Y[:, 0], (Yb[:, 0] if post else None)
 
     def realtime_process(self, mixture, post=True, reset=False):
-        """-> (pred, pred_before) [B, L]; reset is ONE value for the batch (per-utterance chunk chains are not built for this model)."""
+        """-> (pred, pred_before) [B, L]; reset is ONE value for the batch: the uniform call of realtime_process_chains."""
         if isinstance(reset, (list, tuple)) or (torch.is_tensor(reset) and reset.numel() != 1):
-            raise ValueError("Generator.realtime_process takes one `reset` for the whole batch: per-utterance resets (chunk chains) are not supported")
+            raise ValueError("Generator.realtime_process takes one `reset` for the whole batch: per-utterance resets and lengths (chunk "
+                             "chains) are realtime_process_chains(mixture, resets, lengths)")
+        return self.realtime_process_chains(mixture, reset, None, post)
+
+    def realtime_process_chains(self, mixture, resets, lengths=None, post=True):
+        """mixture [B, M, Lmax] -> (pred, pred_before) [B, Lmax]: B independent streams.  resets: a bool, one value or B values;
+        lengths: None or B values in [1, Lmax].  Stream b is mixture[b, :, :lengths[b]] whatever the padding holds; where resets[b] it
+        starts from zero buffers and zero (h, c) behind the reference's half window of zeros, elsewhere it continues row b of the
+        carried state; both outputs are zero at [b, lengths[b]:], and the carried state afterwards holds, per stream, what the stream
+        alone would carry - its running mean and its own norm step count included, which resets[b] does not touch.  Resets and
+        lengths all alike: the uniform call, which is realtime_process."""
         if not post:
             raise TypeError("realtime_process(post=False): the reference cannot either - forward returns None for the result before the "
                             "postnet and realtime_process assigns it into a tensor (hifigan.py:634); use forward(x, post=False)")
         B, M, L = mixture.shape
         self._norm_for(B)
-        plan = self._plan(not bool(reset), None, B, L, M)
+        plan = self._plan([not r for r in as_flags(resets, B)], lengths, B, L, M)
         return getattr(self, f"_{self._admit(mixture, plan)}_call")(mixture, plan)
 
     def _norm_for(self, B):
@@ -184,6 +223,18 @@ class Generator(StreamingMixin, nn.Module):
             raise ValueError(f"the bottleneck norm's running mean is carried for a batch of {ns['mean'].shape[0]} utterances, got {B}: "
                              "reset() keeps it as the reference does, reset_norm() forgets it")
         return ns
+
+    @staticmethod
+    def _steps_of(ns, B):
+        """the norm's step count per stream: B ints, whatever form is carried"""
+        step = 0 if ns is None else ns["step"]
+        return list(step) if isinstance(step, list) else [step] * B
+
+    @staticmethod
+    def _norm_state(mean, step):
+        """`_nstate`: step stays ONE int while every stream's count is the same (a uniform call on such a state keeps it so), else a
+        list of B ints - host values, known from the plan's window counts"""
+        return dict(mean=mean, step=step[0] if isinstance(step, list) and len(set(step)) == 1 else step)
 
     def _choose_path(self, mixture):
         return "kernel" if self._hip and mixture.is_cuda and not torch.is_grad_enabled() and not self.training else "torch"
@@ -276,9 +327,9 @@ class Generator(StreamingMixin, nn.Module):
         Y = self._mask_apply(h, noisy).reshape(B, N, F, T, 2)
         return (Y, Yb), dict(buf=bufs, hc=hc), dict(mean=gm, step=step)
 
-    def _torch_call(self, mixture, plan):
+    def _restate(self, mixture, plan, st, ns):
+        """One uniform call on the restatement, out of place -> ((pred, pred_before) [B, L], state, norm state)"""
         X = self.spectrum(windows(plan, mixture))
-        st, ns = (self._tstate if plan.flag else None), self._norm_for(mixture.shape[0])
         step = max(1, int(self.max_segments)) if all(b.padding < X.shape[4] for b in self.convlist) else 1
         Ys, Ybs = [], []
         for n0 in range(0, X.shape[2], step):
@@ -288,6 +339,34 @@ class Generator(StreamingMixin, nn.Module):
         c = self._cfg
         preds = [overlap_add_cut(plan, istft_windows(torch.view_as_complex(torch.cat(v, dim=1).contiguous()), c["n_fft"], self._hop, self._win, mixture.dtype))
                  for v in (Ys, Ybs)]
+        return preds, st, ns
+
+    @staticmethod
+    def _state_row(st, b, B):
+        return dict(buf=[t[b:b + 1] for t in st["buf"]], hc=[(h[b:b + 1], c[b:b + 1]) for h, c in st["hc"]])
+
+    @staticmethod
+    def _state_merge(rows):
+        return dict(buf=[torch.cat(ts) for ts in zip(*(r["buf"] for r in rows))],
+                    hc=[tuple(torch.cat(v) for v in zip(*layer)) for layer in zip(*(r["hc"] for r in rows))])
+
+    def _torch_call(self, mixture, plan):
+        """Uniform, on ONE carried norm step count: the batch as it stands.  Chains (the oracle of the kernel path), and a uniform call
+        on per-stream step counts: every stream literally alone, as streaming.StreamingMixin._torch_call runs them - B = 1, its own
+        length and reset, its own row of `_tstate` - and with its own (mean[b], step[b]), which the mixin's form has no place for, as
+        it has none for the second result; the outputs padded to the batch width, the states merged row by row."""
+        B, M, Lmax = mixture.shape
+        st, ns = self._tstate, self._norm_for(B)
+        if plan.uniform and not (ns is not None and isinstance(ns["step"], list)):
+            preds, st, ns = self._restate(mixture, plan, st if plan.flag else None, ns)
+        else:
+            steps, alone = self._steps_of(ns, B), []
+            for b, (f, L) in enumerate(zip(plan.flags, plan.lengths)):
+                own = None if ns is None else dict(mean=ns["mean"][b:b + 1] if ns["mean"].shape[0] > 1 else ns["mean"], step=steps[b])
+                alone.append(self._restate(mixture[b:b + 1, :, :L], self._plan(f, None, 1, L, M), self._state_row(st, b, B) if f and st is not None else None, own))
+            preds = [torch.cat([Fn.pad(a[0][i], (0, Lmax - L)) for a, L in zip(alone, plan.lengths)]) for i in range(2)]
+            st = self._state_merge([a[1] for a in alone])
+            ns = self._norm_state(torch.cat([a[2]["mean"] for a in alone]), [a[2]["step"] for a in alone])
         self._tstate, self._nstate = st, ns
         return preds[0], preds[1]
 
@@ -343,13 +422,17 @@ class Generator(StreamingMixin, nn.Module):
         bi, bh = getattr(m, f"bias_ih_l{l}"), getattr(m, f"bias_hh_l{l}")
         return self._cached(("lstm_b", l), [bi, bh], lambda: (bi.detach().float() + bh.detach().float()).contiguous())
 
-    def _kernel_pass(self, mixture, plan, sig, state, ns, n0, Nc, ysegs):
+    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, ysegs):
         """Windows [n0, n0 + Nc) of the call: STFT, features, encoder, bottleneck, decoder, both masks and the postnet, iSTFT into
-        ysegs; advances `state` (a dict this call owns) and returns the norm's new (mean, step)."""
+        ysegs; advances `state` (a dict this call owns: buf, h, c and the norm's mean [B] and step).  Chunk chains: `plan` holds the
+        streams of this pass (the leading plan.B rows of mixture and of every state tensor; ysegs may be wider); a stream runs the
+        LSTM and the norm's scan over its own windows of the pass only, and its encoder buffers stop at its own last window.  The
+        norm's step is an int (one count for all: the scalar kernel) or a list (a count per stream: se_hifi_seqnorm_rows)."""
         lib, st, dev = K._lib(), K._st, mixture.device
         c = self._cfg
         B, M, T, F0, ch, Fq, H, NL, Lv = plan.B, mixture.shape[1], plan.T, plan.F0, plan.ch, plan.Fq, c["hidden"], c["num_layers"], len(self.convlist)
         S, TT = Nc * B, Nc * T
+        steps, live = gru_steps(plan, dev, T, 1, n0, Nc)   # chains: per stream its LSTM steps and its own windows of this pass
         spec = stft(plan, sig, mixture, M, n0, Nc)
         # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input window of level i (its time history)
         xin = []
@@ -379,21 +462,33 @@ class Generator(StreamingMixin, nn.Module):
         for l in range(NL):
             gi = K._gemm(x_l, getattr(m, f"weight_ih_l{l}"), self._lstm_bias(l))
             out, hT, cT = _new(B * TT, H, dev=dev), _new(B, H, dev=dev), _new(B, H, dev=dev)
-            _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm, _p(gi), _p(state["h"][l]), _p(state["c"][l]), _p(getattr(m, f"weight_hh_l{l}")),
-                 _p(out), _p(hT), _p(cT), B, TT, H, st())
+            args = (_p(gi), _p(state["h"][l]), _p(state["c"][l]), _p(getattr(m, f"weight_hh_l{l}")), _p(out), _p(hT), _p(cT))
+            if steps is None:
+                _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm, *args, B, TT, H, st())
+            else:
+                _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_rows, *args, _ip(steps), B, TT, H, st())
             state["h"][l], state["c"][l] = hT, cT
             x_l = out
             del gi
         fc = self.gru.fc_output_layer
         o = K._gemm(x_l, self._folded("fc", fc), fc.bias)           # [B][Nc T][D], before the tanh
         del x_l, out
-        mean_in = torch.zeros(B, device=dev) if ns is None else ns["mean"].to(device=dev, dtype=torch.float32).expand(B).contiguous()
-        step = 0 if ns is None else int(ns["step"])
+        mean_in, step = state["mean"], state["step"]
         mean_out, wm = _new(B, dev=dev), _new(B * Nc, dev=dev)
         h = _new(S, Cl, T, Fl, dev=dev)
         nm = self.gru.norm
-        _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), float(step), _p(wm), _p(mean_out), _p(h),
-             Nc, B, Cl, T, Fl, st())
+        if live is None and not isinstance(step, list):
+            _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), float(step), _p(wm), _p(mean_out), _p(h),
+                 Nc, B, Cl, T, Fl, st())
+            state["step"] = step + Nc * D
+        else:
+            own = plan.live(n0, Nc)
+            step = self._steps_of(state, B)
+            step_dev, cnt = _rows(step, dev), (live if live is not None else _rows(own, dev))
+            _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm_rows, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), _ip(step_dev), _ip(cnt), _p(wm),
+                 _p(mean_out), _p(h), Nc, B, Cl, T, Fl, st())
+            state["step"] = [s + n * D for s, n in zip(step, own)]
+        state["mean"] = mean_out
         del o
         # decoder
         Ci, Fi = Cl, Fl
@@ -420,37 +515,91 @@ class Generator(StreamingMixin, nn.Module):
                 h = _new(S, Co, T, Fy, dev=dev)
                 _run("k_hifi_gate", 0.0, lib.se_hifi_gate, _p(yd), _p(h), yd.numel(), st())
         del yd
+        def to_windows(yseg):
+            if yseg.shape[1] == B:
+                istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
+            else:   # a prefix pass: yseg is window-major at the whole batch's stride, so its rows go in window by window
+                part = _new(Nc, B, plan.Ks, dev=dev)
+                istft(sig, Y, part.view(-1, plan.Ks))
+                yseg[n0:n0 + Nc, :B].copy_(part)
         Y = _new(S, T, F0, 2, dev=dev)
         _run("k_tmask", 0.0, lib.se_train_mask_fwd, _p(h), _p(spec), _p(Y), S, M, T, F0, st())
-        istft(sig, Y, ysegs[1].view(-1, plan.Ks), n0 * B)
+        to_windows(ysegs[1])
         hp = _new(S, 2, T, F0, dev=dev)
         _run("k_hifi_postnet", 2.0 * S * T * F0 * (2 * 2 * POST_CHANNELS + (POST_LAYERS - 2) * POST_CHANNELS * POST_CHANNELS), lib.se_hifi_postnet,
              _p(h), _p(self._postnet_pack()), _p(hp), S, T, F0, st())
         _run("k_tmask", 0.0, lib.se_train_mask_fwd, _p(hp), _p(spec), _p(Y), S, M, T, F0, st())
-        istft(sig, Y, ysegs[0].view(-1, plan.Ks), n0 * B)
-        state["buf"] = [xin[i][-1].clone() for i in range(Lv)]
-        return dict(mean=mean_out, step=step + Nc * D)
+        to_windows(ysegs[0])
+        # every stream's own last window of the pass; slab 0 (what it carried) where it has none
+        state["buf"] = [own_last_slab(plan, xin[i], live, copy=True) for i in range(Lv)]
 
     @torch.no_grad()
     def _kernel_process(self, mixture, plan):
+        """One call on the kernels, gtsa.GTSA._kernel_process's schedule.  Chains: the streams are sorted by window count (descending,
+        stable), so the streams with a window at n0 or later are a prefix: pass (n0, Nc, Bp) of chain_passes runs on the leading Bp
+        rows of the sorted mixture and state.  A stream leaves the working state - buffers, (h, c), its running mean and its step
+        count - for its row of the new carried state when the prefix drops it; the streams still in the prefix at the end follow.
+        Both outputs are un-sorted by the same index.  A uniform call is the identity order with all B streams in every pass:
+        nothing is sorted, gathered or scattered, and the working state is the new one."""
         dev = mixture.device
         B, M, L = mixture.shape
         c = self._cfg
-        H, NL, Lv, T, ch, Fq = c["hidden"], c["num_layers"], len(self.convlist), plan.T, plan.ch, plan.Fq
-        old = self._kstate if plan.flag else None
-        if old is not None:
-            state = dict(B=B, buf=list(old["buf"]), h=list(old["h"]), c=list(old["c"]))
-        else:
-            state = dict(B=B, buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
-                         h=[torch.zeros(B, H, device=dev) for _ in range(NL)], c=[torch.zeros(B, H, device=dev) for _ in range(NL)])
+        H, NL, Lv, T, ch, Fq, n_fft = c["hidden"], c["num_layers"], len(self.convlist), plan.T, plan.ch, plan.Fq, c["n_fft"]
+        old = self._kstate if plan.any_flag else None
         ns = self._norm_for(B)
-        sig = _sig(dev, c["n_fft"], self._win, self._hop, self.segment_length)
-        ysegs = [_new(plan.N, B, plan.Ks, dev=dev) for _ in range(2)]
-        step = max(1, int(self.max_segments))
-        for n0 in range(0, plan.N, step):
-            ns = self._kernel_pass(mixture, plan, sig, state, ns, n0, min(step, plan.N - n0), ysegs)
-        preds = [overlap_add(plan, sig, y) for y in ysegs]
-        self._kstate, self._nstate = state, ns
+        mean = torch.zeros(B, device=dev) if ns is None else ns["mean"].to(device=dev, dtype=torch.float32).expand(B).contiguous()
+        if old is None:
+            state = dict(buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
+                         h=[torch.zeros(B, H, device=dev) for _ in range(NL)], c=[torch.zeros(B, H, device=dev) for _ in range(NL)])
+        if plan.uniform:
+            sp, mix = plan, mixture
+            if old is not None:
+                state = dict(buf=list(old["buf"]), h=list(old["h"]), c=list(old["c"]))
+            state.update(mean=mean, step=0 if ns is None else ns["step"])
+            ysegs = [_new(plan.N, B, plan.Ks, dev=dev) for _ in range(2)]
+        else:
+            order = sorted(range(B), key=lambda b: -plan.Nb[b])
+            order_dev = _rows(order, dev)
+            sp = CallPlan([plan.flags[b] for b in order], [plan.lengths[b] for b in order], L, self.segment_length, self._hop, n_fft, ch, uniform=False)
+            mix = mixture.index_select(0, order_dev)
+            if old is not None:   # the carried row where the stream continues, zeros where it resets - start_rows' gather, reading the rows in sorted order
+                carry = _rows([b if plan.flags[b] else -1 for b in order], dev)
+                start = lambda t: slab_gather(t, carry, B, t.numel() // B, t.numel() // B, 0).view(t.shape)   # noqa: E731
+                state = {k: [start(t) for t in old[k]] for k in ("buf", "h", "c")}
+            steps = self._steps_of(ns, B)
+            state.update(mean=mean.index_select(0, order_dev), step=[steps[b] for b in order])   # the norm goes on whatever the reset says
+            new = dict({k: [torch.empty_like(t) for t in state[k]] for k in ("buf", "h", "c")}, mean=torch.empty_like(mean), step=[0] * B)
+            ysegs = [torch.zeros(sp.N, B, sp.Ks, device=dev) for _ in range(2)]   # windows a prefix pass never writes stay zero
+
+        def retire(lo, hi, cur):
+            """rows [lo, hi) of the working state (cur streams, sorted) -> their own rows of the new carried state; rows [0, lo) stay"""
+            def move(t, o):
+                o.view(B, -1).index_copy_(0, order_dev[lo:hi], t.view(cur, -1)[lo:hi])
+                return t[:lo]
+            for k in ("buf", "h", "c"):
+                state[k] = [move(t, o) for t, o in zip(state[k], new[k])]
+            state["mean"] = move(state["mean"], new["mean"])
+            for i in range(lo, hi):
+                new["step"][order[i]] = state["step"][i]
+            state["step"] = state["step"][:lo]
+
+        sig = _sig(dev, n_fft, self._win, self._hop, self.segment_length)
+        passes = chain_passes(sp.Nb, self.max_segments)
+        sub, cur = {B: sp}, B
+        for n0, Nc, Bp in passes:
+            if Bp < cur:   # chains only: a uniform plan keeps all B streams to the end
+                retire(Bp, cur, cur)
+                cur = Bp
+                sub[Bp] = CallPlan(sp.flags[:Bp], sp.lengths[:Bp], L, self.segment_length, self._hop, n_fft, ch, uniform=False)
+            self._kernel_pass(mix[:Bp], sub[Bp], sig, state, n0, Nc, ysegs)
+        preds = [overlap_add(sp, sig, y) for y in ysegs]
+        if plan.uniform:
+            new = state
+        else:
+            retire(0, cur, cur)
+            preds = [torch.empty(B, L, device=dev).index_copy_(0, order_dev, p) for p in preds]
+        self._kstate, self._nstate = dict(B=B, buf=new["buf"], h=new["h"], c=new["c"]), self._norm_state(new["mean"], new["step"])
+        self._last_passes = passes
         return preds[0], preds[1]
 
 
@@ -470,3 +619,7 @@ class Hifi_GAN(nn.Module):
     def forward(self, x, post=True):
         y, _ = self.generator.realtime_process(x, reset=False, post=post)
         return y
+
+    def realtime_process_chains(self, x, resets, lengths=None, post=True):
+        """the generator's realtime_process_chains, its first result (this project's addition: the reference serves one stream)"""
+        return self.generator.realtime_process_chains(x, resets, lengths, post)[0]

@@ -18,8 +18,9 @@ last call was.  Refused, in this order and before any state is read or written:
 and a call that is refused or fails leaves the carried state it found: both paths build the new state out of place and store it when
 the call has succeeded (the one exception: a persistent-GRU time-out clears `_kstate`, the output being invalid).
 
-hifigan.Generator shares the mixin too: its `realtime_process(mixture, post, reset)` has two results and `reset` = not `flag`, so it
-parses its own arguments and takes the choice of path and the refusals from `_admit`.
+hifigan.Generator shares the mixin too: its `realtime_process(mixture, post, reset)` and `realtime_process_chains(mixture, resets,
+lengths, post)` have two results and `reset` = not `flag`, so it parses its own arguments and takes the choice of path and the refusals
+from `_admit`; its chains on the restatement run every stream alone as `_torch_call` does, with the norm state that no reset clears.
 
 A model provides `segment_length`, `_cfg["n_fft"]` and
     _choose_path(mixture) -> "torch", "kernel" or the name X of a path of its own on the kernel state (`_X_call(mixture, plan)`)
