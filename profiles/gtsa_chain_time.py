@@ -2,7 +2,7 @@
 after a warm-up of every shape (median of `--iters`, the two calls alternating), two ways on this checkout:
 
   chains : `--utts` ChunkChains served by datagen.ChunkChainBatch (chunk lengths 1 .. 3.75 s as data_c.py draws them) as ONE call with
-           per-utterance lengths: the streams sorted by window count, every pass on the prefix still running (gtsa.chain_passes); every
+           per-utterance lengths: the streams sorted by window count, every pass on the prefix still running (call_plan.chain_passes); every
            step of `--steps` is a different batch, all flags reset
   padded : the same batch padded to Lmax through the uniform call (one length, one flag)
 

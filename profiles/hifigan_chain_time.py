@@ -3,7 +3,7 @@
 
   chains : `--utts` ChunkChains served by datagen.ChunkChainBatch (chunk lengths 1 .. 3.75 s as data_c.py draws them) as ONE
            realtime_process_chains call with per-stream lengths: the streams sorted by window count, every pass on the prefix still
-           running (gtsa.chain_passes), the LSTM and the norm's scan per stream; every step of `--steps` is a different batch, all reset
+           running (call_plan.chain_passes), the LSTM and the norm's scan per stream; every step of `--steps` is a different batch, all reset
   padded : the same batches padded to Lmax through realtime_process (one length, one reset)
 
 Next to the times: the share of (stream, window) pairs that are some stream's own, and the share the chains call runs - live windows

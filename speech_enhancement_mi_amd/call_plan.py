@@ -100,7 +100,8 @@ def chain_geometry(lengths, flags, segment_length):
 class CallPlan:
     """One call over B utterances of up to L samples.  `geo` is segment_geometry's dict (uniform) or ragged_geometry's (chains), and its
     entries are attributes too: Ks, P, T, F0, ch, Fq, N, and off0 / skip / Lp / gap - ints when uniform, lists of B when not.  Whatever
-    the kind: flags, lengths, Nb (lists of B), any_flag, flag (the one flag of a uniform call), L (the batch width).  `dev` is
+    the kind: flags, lengths, Nb (lists of B), any_flag, flag (the one flag of a uniform call), L (the batch width).  `rows`: the caller's
+    row of every utterance - the identity, unless the plan is a part of a call (streaming.StreamingMixin._prefix_passes).  `dev` is
     train_stages.row_table's cache of device tables.  uniform=False forces the chains form on a batch that would triage as uniform."""
 
     def __init__(self, flags, lengths, L, segment_length, hop, n_fft, ch=(), uniform=None):
@@ -112,6 +113,7 @@ class CallPlan:
         self.uniform, self.B, self.L = uniform, len(flags), L
         self.flags, self.lengths, self.any_flag, self.flag = list(flags), list(lengths), any(flags), flags[0] if uniform else None
         self.Nb = self.geo.get("Nb", [self.N] * self.B)
+        self.rows = list(range(self.B))
         self.dev = {}
 
     def table(self, key):
@@ -128,6 +130,13 @@ class CallPlan:
 def call_plan(flag, lengths, B, Lmax, segment_length, hop, n_fft, ch=(), uniform=None):
     """The CallPlan of realtime_process(mixture [B, M, Lmax], flag, lengths): parse, validate, triage (unless `uniform` decides)."""
     return CallPlan(as_flags(flag, B), as_lengths(lengths, B, Lmax), Lmax, segment_length, hop, n_fft, ch, uniform)
+
+
+def chain_passes(Nb_sorted, step):
+    """The passes of a chunk-chain call whose streams are sorted by window count, descending: [(n0, Nc, Bp), ...] - windows
+    [n0, n0 + Nc) of the call, run on the Bp leading streams, the ones with a window of their own at n0 or later."""
+    N, step = max(Nb_sorted, default=0), max(1, int(step))
+    return [(n0, min(step, N - n0), sum(nb > n0 for nb in Nb_sorted)) for n0 in range(0, N, step)]
 
 
 # ---- signal glue of the torch restatements (utility.py:312-403): differentiable, dtype-generic -----------------------------------

@@ -31,7 +31,7 @@ from .call_plan import segment_geometry
 from .crn import _Deconv, _Norm as _NormParams, _Seq
 from .streaming import StreamingMixin
 from .train_stages import (_cs, _new, _p, _run, _sig, colsum_tall, decoder_bwd, decoder_fwd, encoder_block_bwd, encoder_block_fwd, gemm_tn,
-                           grads_in_parameter_order, gru_layer_bwd, gru_steps, gru_steps_bwd, input_features, istft, overlap_add, own_last_slab,
+                           grads_in_parameter_order, gru_layer_bwd, gru_steps, gru_steps_bwd, input_features, istft_into, overlap_add, own_last_slab,
                            start_rows, stft, synthesis_adjoint)
 
 EPS = 1e-8
@@ -372,7 +372,7 @@ class GeneralBeamformer(StreamingMixin, nn.Module):
         lin = self.linear
         _run("k_gbf_bf", 0.0, lib.se_gbf_bf_fwd, _p(phi), _p(spec), _p(lin[0].weight), _p(lin[0].bias), _p(lin[2].weight), _p(lin[2].bias),
              _p(lin[3].weight), _p(lin[3].bias), _p(Y), None, S, M, T, F0, H, st())
-        istft(g["sig"], Y, yseg.view(-1, g["Ks"]), n0 * B)
+        istft_into(plan, g["sig"], Y, yseg, n0, Nc)   # every stream in every pass: one launch
         # every utterance's own last live segment of the pass; slab 0 (its previous rows) where it has none
         state["buf"] = [own_last_slab(plan, xin[i], live, copy=True) for i in range(Lv)]
         if keep:

@@ -25,10 +25,9 @@ general_beamformer.GeneralBeamformer):
     csrc/se_gtsa.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
 
 A call with per-utterance flags or lengths is a batch of B independent CHUNK CHAINS (call_plan.py): utterance b runs its own Nb[b] windows
-and leaves the state it would carry alone.  The restatement runs every utterance literally alone (streaming.py's `_torch_call`); the kernel path sorts
-the streams by window count, so the streams still running at window n0 are a prefix, and every pass runs on that prefix only
-(`chain_passes`), the tape tail and the last_conv buffer stopping at each stream's own last window (se_gtsa_tape_rows,
-se_gtsa_lastframes_rows).
+and leaves the state it would carry alone.  The restatement runs every utterance literally alone (streaming.py's `_torch_call`); the kernel
+path runs every pass on the prefix of streams still running (streaming.py's `_prefix_passes`), the tape tail and the last_conv buffer
+stopping at each stream's own last window (se_gtsa_tape_rows, se_gtsa_lastframes_rows).
 """
 from __future__ import annotations
 
@@ -40,18 +39,11 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .call_plan import CallPlan
+from .call_plan import chain_passes  # noqa: F401  (re-exported: the schedule was first written here)
 from .streaming import StreamingMixin
-from .train_stages import _ip, _new, _p, _rows, _run, _sig, istft, overlap_add, slab_gather, stft
+from .train_stages import _ip, _new, _p, _rows, _run, istft_into, stft
 
 EPS = 1e-8
-
-
-def chain_passes(Nb_sorted, step):
-    """The passes of a chunk-chain call whose streams are sorted by window count, descending: [(n0, Nc, Bp), ...] - windows
-    [n0, n0 + Nc) of the call, run on the Bp leading streams, the ones with a window of their own at n0 or later."""
-    N, step = max(Nb_sorted, default=0), max(1, int(step))
-    return [(n0, min(step, N - n0), sum(nb > n0 for nb in Nb_sorted)) for n0 in range(0, N, step)]
 
 
 class _Norm(nn.Module):  # GlobalLayerNorm(time=False), GTSA.py:74-129: denominator sqrt(var + 1e-10) + 1e-8
@@ -282,9 +274,6 @@ class GTSA(StreamingMixin, nn.Module):
                     **{k: [torch.cat([r[k][i].reshape(h, 1, -1, *r[k][i].shape[1:]) for r in rows], dim=1).flatten(0, 2)
                            for i, h in enumerate(self._heads())] for k in ("bk", "bv")})
 
-    def _choose_path(self, mixture):
-        return "kernel" if self._hip and mixture.is_cuda and not torch.is_grad_enabled() and not self.training else "torch"
-
     @staticmethod
     def _batch_of(state):
         return state["buf"].shape[0]
@@ -347,12 +336,13 @@ class GTSA(StreamingMixin, nn.Module):
         """(U sequences per utterance, heads, head width) of layer i"""
         return (5, 3, self.num_freqs // 3) if i % 2 == 0 else (self.num_freqs, 1, 5)
 
-    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, yseg, Fs):
-        """Windows [n0, n0 + Nc) of the call: STFT, features, the layers, the output stage, iSTFT into yseg; advances `state`.
-        Chunk chains: `plan` holds the streams of this pass (the leading plan.B rows of mixture and of every state tensor; yseg may be
-        wider), and the state stops at every stream's own last window of the pass."""
+    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, ysegs):
+        """Windows [n0, n0 + Nc) of the call: STFT, features, the layers, the output stage, iSTFT into ysegs[0]; advances `state`.
+        Chunk chains: `plan` holds the streams of this pass (the leading plan.B rows of mixture and of every state tensor; the window
+        buffer may be wider), and the state stops at every stream's own last window of the pass."""
         lib, st, dev = K._lib(), K._st, mixture.device
         B, M, T, F, maxlen, fn = plan.B, mixture.shape[1], plan.T, plan.F0, self._cfg["maxlen"], self._cfg["fn_dim"]
+        Fs = (F + 7) // 8 * 8
         S = Nc * B
         rows = S * 5 * T
         even_w, conv_w = self._weights(Fs)
@@ -414,70 +404,20 @@ class GTSA(StreamingMixin, nn.Module):
         lc = self.last_conv
         Y = _new(S, T, F, 2, dev=dev)
         _run("k_gtsa_out", 0.0, lib.se_gtsa_out, _p(g2), 4 * F, _p(lc.norm.weight), _p(lc.norm.bias), _p(spec), _p(Y), None, S, M, T, F, st())
-        if yseg.shape[1] == B:
-            istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
-        else:   # a prefix pass: yseg is window-major at the whole batch's stride, so its rows go in window by window
-            part = _new(Nc, B, plan.Ks, dev=dev)
-            istft(sig, Y, part.view(-1, plan.Ks))
-            yseg[n0:n0 + Nc, :B].copy_(part)
+        istft_into(plan, sig, Y, ysegs[0], n0, Nc)
 
     @torch.no_grad()
     def _kernel_process(self, mixture, plan):
-        """One call on the kernels.  Chains: the streams are sorted by window count (descending, stable), so the streams with a window
-        at n0 or later are a prefix: pass (n0, Nc, Bp) of chain_passes runs on the leading Bp rows of the sorted mixture, tables and
-        state - every layout is stream-major.  A stream leaves the working state for its row of the new carried state when the prefix
-        drops it; the streams still in the prefix at the end follow.  pred is un-sorted by the same index.  A uniform call is the
-        identity order with all B streams in every pass: nothing is sorted, gathered or scattered, and the working state is the new one."""
-        dev = mixture.device
-        B, M, L = mixture.shape
-        F, maxlen, n_fft = self.num_freqs, self._cfg["maxlen"], self._cfg["n_fft"]
-        Fs = (F + 7) // 8 * 8
+        """One call on the kernels, uniform or chains: StreamingMixin._prefix_passes' schedule over `_kernel_pass`."""
+        dev, maxlen, Fs = mixture.device, self._cfg["maxlen"], (self.num_freqs + 7) // 8 * 8
         old = self._kstate if plan.any_flag else None
-        if old is None:
+
+        def fresh(B):
             shapes = [self._seq_shape(i) for i in range(len(self.layers))]
-            state = dict(k=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes],
-                         v=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes], buf=torch.zeros(B, 5, 2, Fs, device=dev))
-        if plan.uniform:
-            sp, mix = plan, mixture
-            if old is not None:
-                state = dict(k=list(old["k"]), v=list(old["v"]), buf=old["buf"])
-            yseg = _new(plan.N, B, plan.Ks, dev=dev)
-        else:
-            order = sorted(range(B), key=lambda b: -plan.Nb[b])
-            order_dev = _rows(order, dev)
-            sp = CallPlan([plan.flags[b] for b in order], [plan.lengths[b] for b in order], L, self.segment_length, self._hop, n_fft, uniform=False)
-            mix = mixture.index_select(0, order_dev)
-            if old is not None:   # the carried row where the flag is set, zeros elsewhere - start_rows' gather, reading the rows in sorted order
-                carry = _rows([b if plan.flags[b] else -1 for b in order], dev)
-                start = lambda t: slab_gather(t, carry, B, t.numel() // B, t.numel() // B, 0).view(t.shape)   # noqa: E731
-                state = dict(k=[start(t) for t in old["k"]], v=[start(t) for t in old["v"]], buf=start(old["buf"]))
-            new = dict(B=B, k=[torch.empty_like(t) for t in state["k"]], v=[torch.empty_like(t) for t in state["v"]], buf=torch.empty_like(state["buf"]))
-            yseg = torch.zeros(sp.N, B, sp.Ks, device=dev)   # windows a prefix pass never writes stay zero
-
-        def retire(lo, hi, cur):
-            """rows [lo, hi) of the working state (cur streams, sorted) -> their own rows of the new carried state; rows [0, lo) stay"""
-            def move(t, o):
-                o.view(B, -1).index_copy_(0, order_dev[lo:hi], t.view(cur, -1)[lo:hi])
-                return t[:t.shape[0] // cur * lo]
-            state["k"] = [move(t, o) for t, o in zip(state["k"], new["k"])]
-            state["v"] = [move(t, o) for t, o in zip(state["v"], new["v"])]
-            state["buf"] = move(state["buf"], new["buf"])
-
-        sig = _sig(dev, n_fft, self._win, self._hop, self.segment_length)
-        passes = chain_passes(sp.Nb, self.max_segments)
-        sub, cur = {B: sp}, B
-        for n0, Nc, Bp in passes:
-            if Bp < cur:   # chains only: a uniform plan keeps all B streams to the end
-                retire(Bp, cur, cur)
-                cur = Bp
-                sub[Bp] = CallPlan(sp.flags[:Bp], sp.lengths[:Bp], L, self.segment_length, self._hop, n_fft, uniform=False)
-            self._kernel_pass(mix[:Bp], sub[Bp], sig, state, n0, Nc, yseg, Fs)
-        pred = overlap_add(sp, sig, yseg)
-        if plan.uniform:
-            new = dict(B=B, **state)
-        else:
-            retire(0, cur, cur)
-            pred = torch.empty(B, L, device=dev).index_copy_(0, order_dev, pred)
-        self._kstate = new
+            return dict(k=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes],
+                        v=[torch.zeros(B * U * Hh, maxlen, D, device=dev) for U, Hh, D in shapes], buf=torch.zeros(B, 5, 2, Fs, device=dev))
+        carried = None if old is None else {k: old[k] for k in ("k", "v", "buf")}
+        (pred,), new, passes = self._prefix_passes(mixture, plan, carried, fresh, 1, self._kernel_pass)
+        self._kstate = dict(B=mixture.shape[0], **new)
         self._last_passes = passes
         return pred

@@ -29,7 +29,7 @@ mixture[b, :, :lengths[b]], resets or continues row b of the carried state on it
 quirk is kept PER STREAM: resets[b] does not touch mean[b] or stream b's step count, and streams that advance by different window counts
 have different counts - `_nstate["step"]` is one int while they are all equal and a list of B ints (host values, from the plan) once they
 are not; reset_norm(streams=[b]) zeroes one stream's pair, for a slot handed to a new caller.  The restatement runs every stream literally
-alone; the kernel path sorts the streams by window count and runs every pass on the prefix still alive (gtsa.chain_passes), the LSTM and
+alone; the kernel path runs every pass on the prefix of streams still running (streaming.StreamingMixin._prefix_passes), the LSTM and
 the norm's scan stopping at each stream's own last window (se_hifi_lstm_rows, se_hifi_seqnorm_rows).  Resets and lengths all alike are
 the uniform call - `realtime_process`, which still takes ONE `reset`.
 
@@ -51,10 +51,9 @@ import torch.nn.functional as Fn
 from torch import nn
 
 from . import train_ops as K
-from .call_plan import CallPlan, as_flags, istft_windows, overlap_add_cut, segment_geometry, windows
-from .gtsa import chain_passes
+from .call_plan import as_flags, istft_windows, overlap_add_cut, segment_geometry, windows
 from .streaming import StreamingMixin
-from .train_stages import _ip, _new, _p, _rows, _run, _sig, gru_steps, input_features, istft, overlap_add, own_last_slab, slab_gather, stft
+from .train_stages import _ip, _new, _p, _rows, _run, gru_steps, input_features, istft_into, own_last_slab, stft
 
 EPS = 1e-8
 POST_CHANNELS = 128
@@ -235,9 +234,6 @@ class Generator(StreamingMixin, nn.Module):
         """`_nstate`: step stays ONE int while every stream's count is the same (a uniform call on such a state keeps it so), else a
         list of B ints - host values, known from the plan's window counts"""
         return dict(mean=mean, step=step[0] if isinstance(step, list) and len(set(step)) == 1 else step)
-
-    def _choose_path(self, mixture):
-        return "kernel" if self._hip and mixture.is_cuda and not torch.is_grad_enabled() and not self.training else "torch"
 
     @staticmethod
     def _batch_of(state):
@@ -422,12 +418,13 @@ class Generator(StreamingMixin, nn.Module):
         bi, bh = getattr(m, f"bias_ih_l{l}"), getattr(m, f"bias_hh_l{l}")
         return self._cached(("lstm_b", l), [bi, bh], lambda: (bi.detach().float() + bh.detach().float()).contiguous())
 
-    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, ysegs):
+    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, ysegs, start):
         """Windows [n0, n0 + Nc) of the call: STFT, features, encoder, bottleneck, decoder, both masks and the postnet, iSTFT into
-        ysegs; advances `state` (a dict this call owns: buf, h, c and the norm's mean [B] and step).  Chunk chains: `plan` holds the
-        streams of this pass (the leading plan.B rows of mixture and of every state tensor; ysegs may be wider); a stream runs the
-        LSTM and the norm's scan over its own windows of the pass only, and its encoder buffers stop at its own last window.  The
-        norm's step is an int (one count for all: the scalar kernel) or a list (a count per stream: se_hifi_seqnorm_rows)."""
+        ysegs; advances `state` (a dict this call owns: buf, h, c and the norm's mean [B]).  Chunk chains: `plan` holds the streams
+        of this pass (the leading plan.B rows of mixture and of every state tensor; ysegs may be wider); a stream runs the LSTM and
+        the norm's scan over its own windows of the pass only, and its encoder buffers stop at its own last window.  start: the
+        norm's step count per caller row as the call found it.  A stream that has a window at n0 has run exactly n0 windows of this
+        call, so it enters the pass at start[row] + n0 * D: one count for all takes the scalar kernel, else se_hifi_seqnorm_rows."""
         lib, st, dev = K._lib(), K._st, mixture.device
         c = self._cfg
         B, M, T, F0, ch, Fq, H, NL, Lv = plan.B, mixture.shape[1], plan.T, plan.F0, plan.ch, plan.Fq, c["hidden"], c["num_layers"], len(self.convlist)
@@ -473,21 +470,17 @@ class Generator(StreamingMixin, nn.Module):
         fc = self.gru.fc_output_layer
         o = K._gemm(x_l, self._folded("fc", fc), fc.bias)           # [B][Nc T][D], before the tanh
         del x_l, out
-        mean_in, step = state["mean"], state["step"]
+        mean_in, step = state["mean"], [start[b] + n0 * D for b in plan.rows]
         mean_out, wm = _new(B, dev=dev), _new(B * Nc, dev=dev)
         h = _new(S, Cl, T, Fl, dev=dev)
         nm = self.gru.norm
-        if live is None and not isinstance(step, list):
-            _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), float(step), _p(wm), _p(mean_out), _p(h),
+        if plan.uniform and len(set(step)) == 1:
+            _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), float(step[0]), _p(wm), _p(mean_out), _p(h),
                  Nc, B, Cl, T, Fl, st())
-            state["step"] = step + Nc * D
         else:
-            own = plan.live(n0, Nc)
-            step = self._steps_of(state, B)
-            step_dev, cnt = _rows(step, dev), (live if live is not None else _rows(own, dev))
+            step_dev, cnt = _rows(step, dev), (live if live is not None else _rows(plan.live(n0, Nc), dev))
             _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm_rows, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), _ip(step_dev), _ip(cnt), _p(wm),
                  _p(mean_out), _p(h), Nc, B, Cl, T, Fl, st())
-            state["step"] = [s + n * D for s, n in zip(step, own)]
         state["mean"] = mean_out
         del o
         # decoder
@@ -515,90 +508,36 @@ class Generator(StreamingMixin, nn.Module):
                 h = _new(S, Co, T, Fy, dev=dev)
                 _run("k_hifi_gate", 0.0, lib.se_hifi_gate, _p(yd), _p(h), yd.numel(), st())
         del yd
-        def to_windows(yseg):
-            if yseg.shape[1] == B:
-                istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
-            else:   # a prefix pass: yseg is window-major at the whole batch's stride, so its rows go in window by window
-                part = _new(Nc, B, plan.Ks, dev=dev)
-                istft(sig, Y, part.view(-1, plan.Ks))
-                yseg[n0:n0 + Nc, :B].copy_(part)
         Y = _new(S, T, F0, 2, dev=dev)
         _run("k_tmask", 0.0, lib.se_train_mask_fwd, _p(h), _p(spec), _p(Y), S, M, T, F0, st())
-        to_windows(ysegs[1])
+        istft_into(plan, sig, Y, ysegs[1], n0, Nc)
         hp = _new(S, 2, T, F0, dev=dev)
         _run("k_hifi_postnet", 2.0 * S * T * F0 * (2 * 2 * POST_CHANNELS + (POST_LAYERS - 2) * POST_CHANNELS * POST_CHANNELS), lib.se_hifi_postnet,
              _p(h), _p(self._postnet_pack()), _p(hp), S, T, F0, st())
         _run("k_tmask", 0.0, lib.se_train_mask_fwd, _p(hp), _p(spec), _p(Y), S, M, T, F0, st())
-        to_windows(ysegs[0])
+        istft_into(plan, sig, Y, ysegs[0], n0, Nc)
         # every stream's own last window of the pass; slab 0 (what it carried) where it has none
         state["buf"] = [own_last_slab(plan, xin[i], live, copy=True) for i in range(Lv)]
 
     @torch.no_grad()
     def _kernel_process(self, mixture, plan):
-        """One call on the kernels, gtsa.GTSA._kernel_process's schedule.  Chains: the streams are sorted by window count (descending,
-        stable), so the streams with a window at n0 or later are a prefix: pass (n0, Nc, Bp) of chain_passes runs on the leading Bp
-        rows of the sorted mixture and state.  A stream leaves the working state - buffers, (h, c), its running mean and its step
-        count - for its row of the new carried state when the prefix drops it; the streams still in the prefix at the end follow.
-        Both outputs are un-sorted by the same index.  A uniform call is the identity order with all B streams in every pass:
-        nothing is sorted, gathered or scattered, and the working state is the new one."""
-        dev = mixture.device
-        B, M, L = mixture.shape
+        """One call on the kernels, uniform or chains: StreamingMixin._prefix_passes' schedule over `_kernel_pass`, the running mean as
+        the entry of the working state that no reset clears.  The norm's step counts never travel with it: they follow from the plan."""
+        dev, B = mixture.device, mixture.shape[0]
         c = self._cfg
-        H, NL, Lv, T, ch, Fq, n_fft = c["hidden"], c["num_layers"], len(self.convlist), plan.T, plan.ch, plan.Fq, c["n_fft"]
+        H, NL, Lv, T, ch, Fq = c["hidden"], c["num_layers"], len(self.convlist), plan.T, plan.ch, plan.Fq
         old = self._kstate if plan.any_flag else None
         ns = self._norm_for(B)
         mean = torch.zeros(B, device=dev) if ns is None else ns["mean"].to(device=dev, dtype=torch.float32).expand(B).contiguous()
-        if old is None:
-            state = dict(buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
-                         h=[torch.zeros(B, H, device=dev) for _ in range(NL)], c=[torch.zeros(B, H, device=dev) for _ in range(NL)])
-        if plan.uniform:
-            sp, mix = plan, mixture
-            if old is not None:
-                state = dict(buf=list(old["buf"]), h=list(old["h"]), c=list(old["c"]))
-            state.update(mean=mean, step=0 if ns is None else ns["step"])
-            ysegs = [_new(plan.N, B, plan.Ks, dev=dev) for _ in range(2)]
-        else:
-            order = sorted(range(B), key=lambda b: -plan.Nb[b])
-            order_dev = _rows(order, dev)
-            sp = CallPlan([plan.flags[b] for b in order], [plan.lengths[b] for b in order], L, self.segment_length, self._hop, n_fft, ch, uniform=False)
-            mix = mixture.index_select(0, order_dev)
-            if old is not None:   # the carried row where the stream continues, zeros where it resets - start_rows' gather, reading the rows in sorted order
-                carry = _rows([b if plan.flags[b] else -1 for b in order], dev)
-                start = lambda t: slab_gather(t, carry, B, t.numel() // B, t.numel() // B, 0).view(t.shape)   # noqa: E731
-                state = {k: [start(t) for t in old[k]] for k in ("buf", "h", "c")}
-            steps = self._steps_of(ns, B)
-            state.update(mean=mean.index_select(0, order_dev), step=[steps[b] for b in order])   # the norm goes on whatever the reset says
-            new = dict({k: [torch.empty_like(t) for t in state[k]] for k in ("buf", "h", "c")}, mean=torch.empty_like(mean), step=[0] * B)
-            ysegs = [torch.zeros(sp.N, B, sp.Ks, device=dev) for _ in range(2)]   # windows a prefix pass never writes stay zero
+        start = self._steps_of(ns, B)
 
-        def retire(lo, hi, cur):
-            """rows [lo, hi) of the working state (cur streams, sorted) -> their own rows of the new carried state; rows [0, lo) stay"""
-            def move(t, o):
-                o.view(B, -1).index_copy_(0, order_dev[lo:hi], t.view(cur, -1)[lo:hi])
-                return t[:lo]
-            for k in ("buf", "h", "c"):
-                state[k] = [move(t, o) for t, o in zip(state[k], new[k])]
-            state["mean"] = move(state["mean"], new["mean"])
-            for i in range(lo, hi):
-                new["step"][order[i]] = state["step"][i]
-            state["step"] = state["step"][:lo]
-
-        sig = _sig(dev, n_fft, self._win, self._hop, self.segment_length)
-        passes = chain_passes(sp.Nb, self.max_segments)
-        sub, cur = {B: sp}, B
-        for n0, Nc, Bp in passes:
-            if Bp < cur:   # chains only: a uniform plan keeps all B streams to the end
-                retire(Bp, cur, cur)
-                cur = Bp
-                sub[Bp] = CallPlan(sp.flags[:Bp], sp.lengths[:Bp], L, self.segment_length, self._hop, n_fft, ch, uniform=False)
-            self._kernel_pass(mix[:Bp], sub[Bp], sig, state, n0, Nc, ysegs)
-        preds = [overlap_add(sp, sig, y) for y in ysegs]
-        if plan.uniform:
-            new = state
-        else:
-            retire(0, cur, cur)
-            preds = [torch.empty(B, L, device=dev).index_copy_(0, order_dev, p) for p in preds]
-        self._kstate, self._nstate = dict(B=B, buf=new["buf"], h=new["h"], c=new["c"]), self._norm_state(new["mean"], new["step"])
+        def fresh(B):
+            return dict(buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
+                        h=[torch.zeros(B, H, device=dev) for _ in range(NL)], c=[torch.zeros(B, H, device=dev) for _ in range(NL)], mean=mean)
+        carried = None if old is None else dict(buf=old["buf"], h=old["h"], c=old["c"], mean=mean)
+        preds, new, passes = self._prefix_passes(mixture, plan, carried, fresh, 2, lambda *a: self._kernel_pass(*a, start), unflagged=("mean",))
+        self._kstate = dict(B=B, buf=new["buf"], h=new["h"], c=new["c"])
+        self._nstate = self._norm_state(new["mean"], [s + n * ch[Lv] * Fq[Lv] for s, n in zip(start, plan.Nb)])
         self._last_passes = passes
         return preds[0], preds[1]
 

@@ -137,6 +137,18 @@ def istft(sig, Y, yseg, row0=0):
     _run("k_istft", 0.0, K._lib().se_sig_istft, sig, _p(Y), Y.shape[0], _p(yseg, row0 * yseg.shape[-1]), K._st())
 
 
+def istft_into(plan, sig, Y, yseg, n0, Nc):
+    """Y [Nc * plan.B][T][F0][2], windows [n0, n0 + Nc) of the plan's streams -> yseg [N][B'][Ks], B' >= plan.B: straight in where the
+    pass is as wide as yseg, else (a prefix pass: yseg is window-major at the whole batch's stride) window by window"""
+    B = plan.B
+    if yseg.shape[1] == B:
+        istft(sig, Y, yseg.view(-1, plan.Ks), n0 * B)
+    else:
+        part = _new(Nc, B, plan.Ks, dev=Y.device)
+        istft(sig, Y, part.view(-1, plan.Ks))
+        yseg[n0:n0 + Nc, :B].copy_(part)
+
+
 def overlap_add(plan, sig, yseg):
     """utility.over_add of the segment-major yseg [N*B][Ks] -> pred [B][L]: the first skip[b] samples dropped, pred[b][lengths[b]:] = 0"""
     dev = yseg.device
