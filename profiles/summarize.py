@@ -38,7 +38,7 @@ def record_name(full):
     args = full.split("<", 1)[1].split(">(")[0].replace(" ", "") if "<" in full else ""
     if name == "k_skip_pd":  # the batched form of the skip gate (round 11): the same record
         name = "k_skip_p"
-    pair = args.endswith("(se::PlaneFmt)1")
+    pair = args.endswith("(se::PlaneFmt)1") or args.endswith("(se::PlaneFmt)1,true")  # (", true": k_gemm_p on K-blocked operands, round 13)
     if (name in ("k_gemm_p", "k_skip_p") and pair and args.startswith("2,")) or (name.startswith("k_gru_step_split") and args.endswith("true,2")):
         return name + "_w2"
     return PROFILE_NAME.get(name, name)

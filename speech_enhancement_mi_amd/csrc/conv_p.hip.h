@@ -600,7 +600,12 @@ __global__ __launch_bounds__(256) void k_gln_p(GlnPArgs a) {
             for (int c = 0; c < 8; c++) v[c] += r[c];
         }
         uint4 *dst = a.mode == 0 ? a.y + (long)b * a.y_stream + (long)o * PL * TF + i : a.y + ((long)(b * a.T + t) * a.C8 + o) * a.F + f;
-        const long plane = a.mode == 0 ? TF : a.y_plane;
+        long plane = a.mode == 0 ? TF : a.y_plane;
+        if (FMT == PlaneFmt::kF16Pair && a.mode == 2) {  // K-blocked row (gemm_kblock.h): piece q of the row at (q >> 2) * 8 + (q & 3), planes 4 pieces apart
+            const long q = (long)o * a.F + f;
+            dst = a.y + (long)(b * a.T + t) * a.C8 * a.F * 2 + (q >> 2) * 8 + (q & 3);
+            plane = 4;
+        }
         if constexpr (FMT == PlaneFmt::kF16Pair) split_store8_pair(v, dst, plane);
         else split_store8<PL>(v, dst, plane);
     }

@@ -93,6 +93,7 @@ struct GlnPArgs {
     const uint4 *res;   // optional residual in the P layout of the output (CRN_ELU pre-conv blocks: x = m(x) + x), added after the norm
     long res_stream;    // uint4 per stream
     uint4 *y;           // mode 0: P[b][o][pl][t][f]   mode 1: A planes of the GRU input GEMM, [pl][b*T + t][o][f] (K = C8*F*8)
+                        // mode 2 (fp16 pair only): the same operand K-blocked, [b*T + t][K/32][pl][32] (gemm_kblock.h)
     long y_stream;      // mode 0: uint4 per stream
     long y_plane;       // mode 1: uint4 per plane (= B*T*C8*F)
     int mode;

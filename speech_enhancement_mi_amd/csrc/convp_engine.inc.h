@@ -723,7 +723,7 @@ int stage_encoder_p(se_engine *e, int cur, int prev, const cf2 *spec, long sB, l
             g.y_stream = (long)g.C8 * act_planes(e, PlaneBuf::kConvAct) * T * Fo;
             launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g, act_format(e, PlaneBuf::kConvAct));
         } else if (e->gemm_p) {  // last level = A operand of the GRU input projection, as split-bf16 planes (k_gemm_p)
-            g.mode = 1;
+            g.mode = kblock_on(e) ? 2 : 1;  // (2: the same operand K-blocked, gemm_kblock.h)
             g.y = reinterpret_cast<uint4 *>(e->gruinP[cur].p);
             g.y_plane = (long)B * T * g.C8 * Fo;
             launch_k_gln_p(PL, dim3((T * Fo + 1023) / 1024, g.C8, Ba), st, g, buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA));

@@ -14,6 +14,7 @@
 #include "../../include/se_engine.h"
 #include "chain_plan.h"
 #include "split_f16pair.h"
+#include "gemm_kblock.h"
 
 namespace se {
 
@@ -107,12 +108,20 @@ inline PlaneFmt buffer_format(int precision, bool pair_on, PlaneBuf kind, bool c
 inline int buffer_planes(int precision, bool pair_on, PlaneBuf kind, bool conv_on = true) {
     return buffer_format(precision, pair_on, kind, conv_on) == PlaneFmt::kF16Pair ? kPairPlanesA : operand_planes(precision);
 }
+// The ORDER of the planes is a property of the buffer too: the kGemmA buffers and the weights k_gemm_p multiplies them with are K-blocked
+// ([row][K / 32][plane][32], gemm_kblock.h) where the pair is on with its two stored weight planes (wpl = the stored weight planes of the
+// pair) and the knob (SE_GEMM_KBLOCK) allows it.  Everything else is plane-major [plane][row][K].
+inline bool buffer_kblocked(int precision, bool pair_on, int wpl, bool knob, PlaneBuf kind) {
+    return knob && kind == PlaneBuf::kGemmA && wpl == kPairPlanesW2 && buffer_format(precision, pair_on, kind) == PlaneFmt::kF16Pair;
+}
 
 // the fp16-pair planes (2^11 hi, lo, hi) of a [rows][cols] fp32 matrix -> device buffer of 3*rows*cols uint16 (the shape of upload_planes);
-// wpl = kPairPlanesW2: the two stored planes (lo, hi), 2*rows*cols uint16
-inline int upload_planes_pair(EngineHost *e, DevBuf &b, const std::vector<float> &w, int wpl = kPairPlanesW) {
+// wpl = kPairPlanesW2: the two stored planes (lo, hi), 2*rows*cols uint16; kblock_cols > 0 (two stored planes only): K-blocked rows of
+// that many columns (gemm_kblock.h)
+inline int upload_planes_pair(EngineHost *e, DevBuf &b, const std::vector<float> &w, int wpl = kPairPlanesW, size_t kblock_cols = 0) {
     std::vector<uint16_t> planes((size_t)wpl * w.size());
-    if (wpl == kPairPlanesW2) pair_weight_matrix2(w.data(), w.size(), planes.data());
+    if (wpl == kPairPlanesW2 && kblock_cols) pair_weight_matrix2_kblock(w.data(), w.size() / kblock_cols, kblock_cols, planes.data());
+    else if (wpl == kPairPlanesW2) pair_weight_matrix2(w.data(), w.size(), planes.data());
     else pair_weight_matrix(w.data(), w.size(), planes.data());
     int rc = dev_alloc(e, b, (planes.size() + 1) / 2);
     if (rc) return rc;

@@ -11,6 +11,7 @@
 #include "conv_igemm.hip.h"
 #include "split_bf16.h"
 #include "split_f16pair.h"
+#include "gemm_kblock.h"
 
 namespace se {
 
@@ -274,6 +275,12 @@ __global__ __launch_bounds__(256) void k_gemm_x(GemmX6Args a) {
 //   * LDS image per (operand, plane): [row][4 pieces of 16 B], piece q of row r at slot q ^ ((r >> 2) & 3): the 16-lane
 //     groups of a ds_read_b128 then touch every 16-byte column of every 256-byte bank row once (conflict-free); the LDS-DMA
 //     destination is lane-linear, so the permutation is applied to the SOURCE address.
+//     KB (the pair's two stored weight planes on K-blocked operands, gemm_kblock.h): the image per operand is [row][8 pieces],
+//     both planes of a row side by side, piece p = 4 plane + q at slot p ^ ((r >> 1) & 7).  A bank row holds two image rows; the
+//     eight rows of one parity in a 16-lane group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31}) have all eight residues of r >> 1
+//     mod 8, so a group again touches every 16-byte column once.  The XOR moves plane 1 to +-64 bytes from plane 0 (a per-lane
+//     constant).  A wave's LDS-DMA instruction then copies 8 rows x 128 B - whole lines - where the plane-major image takes
+//     16 rows x 64 B, sixteen half-used lines whose other halves are fetched again a chunk later.
 //   * workgroup id -> tile is XCD-aware: the eight XCDs (id mod 8) each own a gx x gy block of tiles, so an operand tile is
 //     fetched into as few L2s as possible.
 struct GemmPArgs {
@@ -325,12 +332,15 @@ __device__ __forceinline__ void gemm_p_rowsum16(float (&v)[16], int l31) {
 // bias, the activation and the statistics.  The ring stage shrinks from 72 to 56 KB at the same tile.
 // FMT = kF16Pair, PL = 2: the two STORED weight planes (w_lo, w_hi); 2^11 w_hi is formed from the w_hi fragments in registers, once per
 // K step (pair_scale_hi), and goes into the same three MFMAs in the same order - the bits of PL = 3 from a 48 KB stage.
-template <int PL, PlaneFmt FMT = PlaneFmt::kBf16>
+// KB (PL = 2 pair only): both operands K-blocked, [row][K / 32][plane][32] (gemm_kblock.h); a_plane / w_plane are unused.  Same MFMAs on
+// the same fragments in the same order: the bits of the plane-major instance.
+template <int PL, PlaneFmt FMT = PlaneFmt::kBf16, bool KB = false>
 __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     constexpr bool kPair = FMT == PlaneFmt::kF16Pair;
     static_assert(!kPair || PL == kPairPlanesW || PL == kPairPlanesW2, "the fp16 pair has three weight planes, or two stored ones");
     constexpr bool kPairW2 = kPair && PL == kPairPlanesW2;
+    static_assert(!KB || kPairW2, "K-blocked operands: the pair's two stored weight planes only");
     constexpr int PA = kPair ? kPairPlanesA : PL, PW = PL;  // planes of A / W
     extern __shared__ __align__(16) uint4 gl[];  // [stage 2]{A [PA][256 rows][4 pieces], W [PW][128 rows][4 pieces]}
     constexpr int kPieces = 1024 * PA + 512 * PW;  // uint4 per chunk
@@ -363,6 +373,12 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
 #pragma unroll
     for (int i = 0; i < kNA; i++) {
         const int s = tid + 512 * i;
+        if constexpr (KB) {  // slot s = row * 8 + slot of the [256 rows][8 pieces] image; a row of the source is 2 K8 pieces
+            const int row = (s >> 3) & 255;
+            const long r = min(m0 + row, a.M - 1);
+            voa[i] = (unsigned)((r * 2 * K8 + kblock_lds_slot(row, s & 7)) * 16);
+            continue;
+        }
         const int qslot = s & 3, row = (s >> 2) & 255, pl = s >> 10;
         const long r = min(m0 + row, a.M - 1);
         voa[i] = (unsigned)(((long)pl * a.a_plane + r * K8 + (qslot ^ ((row >> 2) & 3))) * 16);
@@ -370,6 +386,12 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
 #pragma unroll
     for (int i = 0; i < kNW; i++) {
         const int s = tid + 512 * i;
+        if constexpr (KB) {
+            const int row = (s >> 3) & 127;
+            const long r = min(n0 + row, a.N - 1);
+            vow[i] = (unsigned)((r * 2 * K8 + kblock_lds_slot(row, s & 7)) * 16);
+            continue;
+        }
         const int qslot = s & 3, row = (s >> 2) & 127, pl = s >> 9;
         const long r = min(n0 + row, a.N - 1);
         vow[i] = (unsigned)(((long)pl * a.w_plane + r * K8 + (qslot ^ ((row >> 2) & 3))) * 16);
@@ -378,7 +400,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         // (the resources are built inside the lambda: a captured __amdgpu_buffer_rsrc_t also drops the host stub)
         const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(a.Ap), 0, a.a_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(a.Wp), 0, a.w_bytes, 0x00020000);
-        const unsigned add = (unsigned)kc * 64;  // 32 bf16 per chunk
+        const unsigned add = (unsigned)kc * (KB ? 128 : 64);  // 32 bf16 per chunk (KB: of both planes)
         uint4 *base = gl + buf * kPieces + wave * 64;
 #pragma unroll
         for (int i = 0; i < kNA; i++)
@@ -394,9 +416,16 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
     unsigned adA[2], adB[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) {
+        if constexpr (KB) {  // plane 0; rows + 32 i are immediates (4096 B), plane 1 is at + dpl
+            adA[ks] = lds0 + kblock_frag_byte(wm + l31, ks, half, 0);
+            adB[ks] = lds0 + (unsigned)(1024 * PA * 16) + kblock_frag_byte(wn + l31, ks, half, 0);
+            continue;
+        }
         adA[ks] = lds0 + (unsigned)(((wm + l31) * 4 + ((2 * ks + half) ^ sw)) * 16);
         adB[ks] = lds0 + (unsigned)((1024 * PA + (wn + l31) * 4 + ((2 * ks + half) ^ sw)) * 16);
     }
+    // KB: plane 1 relative to plane 0, +64 or -64 bytes by bit 3 of the row (the same for A and B, for both K steps and both i)
+    const unsigned dpl = KB ? kblock_frag_byte(l31, 0, 0, 1) - kblock_frag_byte(l31, 0, 0, 0) : 0u;
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; i++)
@@ -440,7 +469,18 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
             }
     };
 #define SE_GEMMP_READ(fa, fb, ks, sb)                               \
-    {                                                               \
+    if constexpr (KB) {                                             \
+        const unsigned xa = adA[ks] + (sb), xb = adB[ks] + (sb);    \
+        const unsigned ya = xa + dpl, yb = xb + dpl;                \
+        SE_DS_READ128(fa[0][0], xa, 0);                             \
+        SE_DS_READ128(fa[1][0], xa, 4096);                          \
+        SE_DS_READ128(fb[0][0], xb, 0);                             \
+        SE_DS_READ128(fb[1][0], xb, 4096);                          \
+        SE_DS_READ128(fa[0][1], ya, 0);                             \
+        SE_DS_READ128(fa[1][1], ya, 4096);                          \
+        SE_DS_READ128(fb[0][1], yb, 0);                             \
+        SE_DS_READ128(fb[1][1], yb, 4096);                          \
+    } else {                                                        \
         const unsigned xa = adA[ks] + (sb), xb = adB[ks] + (sb);    \
         SE_DS_READ128(fa[0][0], xa, 0);                             \
         SE_DS_READ128(fa[1][0], xa, 2048);                          \
@@ -502,7 +542,7 @@ __global__ __launch_bounds__(512) void k_gemm_p(GemmPArgs a) {
         if constexpr (kPairW2) { fb1[0][2] = pair_scale_hi(fb1[0][1]); fb1[1][2] = pair_scale_hi(fb1[1][1]); }
         multiply(fa1, fb1);
 #else
-        (void)sb; (void)multiply;
+        (void)sb; (void)multiply; (void)dpl;
 #endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's redundant request lands before the workgroup's LDS is released
@@ -579,7 +619,12 @@ struct GruStepArgs {
     long seqp_ld, seqp_plane;  // + t*H applied; row stride and plane stride in elements
     int seqp_pl;         // planes: 3, 2, or 1 (fp16)
     int seqp_pair;       // the planes are the fp16 pair (split_f16pair.h; seqp_pl = 2) instead of bf16
+    int seqp_kb;         // the pair K-blocked (gemm_kblock.h): rows of 2 H elements [H / 32][plane][32] - seqp carries + 2 t H, seqp_ld is
+                         // the stride of those rows, seqp_plane = 32 and unit n sits at kblock_col(n)
 };
+
+// unit n of a row of the sequence planes (plane 0)
+__device__ __forceinline__ long gru_seqp_col(const GruStepArgs &a, int n) { return a.seqp_kb ? kblock_col(n) : n; }
 
 // h_t into the sequence planes (sp = the element of plane 0)
 __device__ __forceinline__ void gru_seqp_store(const GruStepArgs &a, __bf16 *sp, float hn) {
@@ -700,7 +745,7 @@ __device__ __forceinline__ void gru_step_body(const GruStepArgs &a) {
                 float *gs = a.gates + (long)row * a.gates_ld;
                 gs[n] = rg; gs[H + n] = zg; gs[2 * H + n] = ng; gs[3 * H + n] = gh_n;
             }
-            if (a.seqp) gru_seqp_store(a, a.seqp + (long)row * a.seqp_ld + n, hn);
+            if (a.seqp) gru_seqp_store(a, a.seqp + (long)row * a.seqp_ld + gru_seqp_col(a, n), hn);
         }
     }
 }
@@ -822,7 +867,7 @@ __global__ __launch_bounds__(256) void k_gru_step2(GruStepArgs a) {
             const float hn = (1.0f - zg) * ng + zg * hp;
             a.hout[(long)row * H + n] = hn;
             a.seq[(long)row * a.seq_ld + n] = hn;
-            if (a.seqp) gru_seqp_store(a, a.seqp + (long)row * a.seqp_ld + n, hn);
+            if (a.seqp) gru_seqp_store(a, a.seqp + (long)row * a.seqp_ld + gru_seqp_col(a, n), hn);
         }
     }
 }
@@ -892,6 +937,9 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
     const bool planes = ga.hp != nullptr;  // uniform
     const char *abase[MT][NA];
     const long astride = planes ? 32 : 64;  // bytes per k step: 16 bf16 / 16 floats
+    // K-blocked planes (seqp_kb): a 32-deep block of a row is one 128-byte line [plane][32], so k step ks starts (ks >> 1) * 64 bytes
+    // further on and a lane's two planes are two 16-byte runs of the same line (seqp_plane = 32 elements)
+    const long akb = planes && a.seqp_kb ? 64 : 0;
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
         const int arow = min(r0 + mt * 32 + l31, a.B - 1);
@@ -906,7 +954,7 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-            for (int p = 0; p < NA; p++) qa[i][mt][p] = *reinterpret_cast<const u32x4 *>(abase[mt][p] + ks * astride);
+            for (int p = 0; p < NA; p++) qa[i][mt][p] = *reinterpret_cast<const u32x4 *>(abase[mt][p] + ks * astride + (ks >> 1) * akb);
 #pragma unroll
         for (int f = 0; f < NWF; f++) qw[i][f] = *reinterpret_cast<const u32x4 *>(wp + ((long)ks * NWF + f) * 64);
     };
@@ -1059,7 +1107,7 @@ __device__ __forceinline__ void gru_split_body(const GruSplitArgs &ga) {
             const float hn = (1.0f - zg) * ng + zg * php[mt][i];
             a.hout[(long)row * H + n] = hn;
             a.seq[(long)row * a.seq_ld + n] = hn;
-            __bf16 *sp = a.seqp + (long)row * a.seqp_ld + n;
+            __bf16 *sp = a.seqp + (long)row * a.seqp_ld + gru_seqp_col(a, n);
             if constexpr (PAIR) {
                 uint16_t hh, ll;
                 split2h(hn, hh, ll);

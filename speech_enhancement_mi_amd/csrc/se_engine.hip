@@ -143,6 +143,7 @@ struct se_engine : EngineHost {
     bool pair_on = false;     // decided once per weight load (f16_pair_decide): knob, eligibility and the range guard
     int pair_w3 = 0;          // SE_PAIR_W3=1: pair weights as the three stored planes (2^11 hi, lo, hi) and the kernels' three-plane instances;
                               // default: two stored planes (lo, hi), 2^11 hi made in registers - the same bits from fewer weight bytes
+    int gemm_kblock = 1;      // SE_GEMM_KBLOCK=0: gruinP / seqP and the k_gemm_p weights stay plane-major where they would be K-blocked (kblock_on)
     DevBuf wih_h[4];          // W_ih of layers >= 1 as pair planes (wih_x[l] stays bf16: the fp32-row GEMMs of small batches read it)
     // fc_output_layer + gLN(last) on the plane GEMM route: weight rows, bias and the norm's per-element affine permuted like W_ih0's
     // K axis, so that fc_out column (o * F + f) * 8 + c holds reference feature (8 o + c) * F + f (channels padded to whole octets
@@ -168,6 +169,9 @@ int act_planes(const se_engine *e, PlaneBuf kind) { return buffer_planes(e->prec
 PlaneBuf xin_kind(int level) { return level == 0 ? PlaneBuf::kFeature : PlaneBuf::kConvAct; }
 // stored planes of a weight in the fp16 pair format (split_f16pair.h)
 int pair_wplanes(const se_engine *e) { return e->pair_w3 ? kPairPlanesW : kPairPlanesW2; }
+// gruinP, seqP and the weights k_gemm_p multiplies them with are K-blocked (engine_host.h: buffer_kblocked, gemm_kblock.h).  Like pair_on it
+// is fixed per weight load; the buffers' sizes do not depend on it
+bool kblock_on(const se_engine *e) { return buffer_kblocked(e->precision, e->pair_on, pair_wplanes(e), e->gemm_kblock != 0, PlaneBuf::kGemmA); }
 
 int prof_label(se_engine *e, const char *kernel, const std::string &label, double flops) {
     for (size_t i = 0; i < e->prof_labels.size(); i++)
@@ -398,7 +402,7 @@ int prepare_weights(se_engine *e) {
         if ((rc = dev_upload(e, e->wih[l], *a)) || (rc = dev_upload(e, e->whh[l], *b)) ||
             (rc = dev_upload(e, e->bih[l], *c)) || (rc = dev_upload(e, e->bhh[l], *d)))
             return rc;
-        if (e->pair_on && l > 0 && (rc = upload_planes_pair(e, e->wih_h[l], *a, pair_wplanes(e)))) return rc;
+        if (e->pair_on && l > 0 && (rc = upload_planes_pair(e, e->wih_h[l], *a, pair_wplanes(e), kblock_on(e) ? (size_t)H : 0))) return rc;
         if (e->precision == 0 && H % 32 == 0) {
             std::vector<uint16_t> pk;
             if (e->pair_on && !e->pair_w3) gru_pack_whh_pair2(b->data(), H, pk);
@@ -498,7 +502,9 @@ int launch_gemm_p(se_engine *e, const float *Ap, const float *Wp, const float *b
                 (unsigned)((size_t)PA * Ma * Kd * 2), (unsigned)((size_t)PL * Nc * Kd * 2), nrt, nct, gx, gy, stats};
     const dim3 grid(nblocks);
     const size_t lds = (size_t)2 * (1024 * PA + 512 * PL) * 16;
-    if (pair && PL == kPairPlanesW2) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
+    // (K-blocked operands: the same buffers, ranges and stage size, whole rows of 2 K fp16 instead of planes)
+    if (pair && PL == kPairPlanesW2 && kblock_on(e)) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair, true>), grid, dim3(512), lds, st, g);
+    else if (pair && PL == kPairPlanesW2) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
     else if (pair) hipLaunchKernelGGL((k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), grid, dim3(512), lds, st, g);
     else if (PL == 1) hipLaunchKernelGGL(k_gemm_p<1>, grid, dim3(512), lds, st, g);
     else if (PL == 2) hipLaunchKernelGGL(k_gemm_p<2>, grid, dim3(512), lds, st, g);
@@ -579,11 +585,20 @@ int stage_gru_proj0(se_engine *e, int cur, hipStream_t st) {
 
 // W_ih of layer l >= 1 as the plane GEMM reads it
 const float *wih_planes(const se_engine *e, int l) { return e->pair_on ? e->wih_h[l].p : e->wih_x[l].p; }
-// the sequence planes of a step's arguments: plane count and format of seqP
-void set_seqp_format(const se_engine *e, GruStepArgs &g) {
+// the sequence planes of a step's arguments at time step t: seqP slot `base` ([PL][B * T][H] for the allocation batch B, or K-blocked
+// rows of 2 H), plane count and format
+void set_seqp(const se_engine *e, GruStepArgs &g, float *base, int t) {
+    const long T = e->T, H = e->H, B = e->B;
     g.seqp_pl = buffer_planes(e->precision, e->pair_on, PlaneBuf::kGemmA);
     g.seqp_pair = buffer_format(e->precision, e->pair_on, PlaneBuf::kGemmA) == PlaneFmt::kF16Pair;
+    g.seqp_kb = kblock_on(e);
+    const long row = g.seqp_kb ? 2 * H : H;  // elements per (stream, time step)
+    g.seqp = reinterpret_cast<__bf16 *>(base) + t * row;
+    g.seqp_ld = T * row;
+    g.seqp_plane = g.seqp_kb ? kKbBlock : B * T * H;
 }
+// row t - 1 of the same planes: h_{t-1} as the split step reads it (t >= 1)
+const __bf16 *seqp_prev(const GruStepArgs &g, int H) { return g.seqp - (g.seqp_kb ? 2 * H : H); }
 
 // The split-bf16 step (k_gru_step_split) reads h_{t-1} as the planes the plane GEMM route writes and W_hh as packed PL = 3 fragments
 bool gru_split_eligible(const se_engine *e) { return e->gemm_p && e->precision == 0 && e->H % 32 == 0 && e->B > 16; }
@@ -621,13 +636,10 @@ int stage_gru_layer(se_engine *e, int l, int cur, hipStream_t st, bool overlappe
         const int hc = e->hcur[l];
         GruStepArgs g{gi + (long)t * 3 * H, (long)T * 3 * H, e->hbuf[l][hc].p, e->whh[l].p, e->bhh[l].p,
                       e->hbuf[l][hc ^ 1].p, seq + (long)t * H, (long)T * H, Ba, H};
-        if (e->gemm_p) {
-            g.seqp = reinterpret_cast<__bf16 *>(e->seqP[l][cur].p) + (long)t * H;
-            g.seqp_ld = (long)T * H; g.seqp_plane = (long)B * T * H; set_seqp_format(e, g);
-        }
+        if (e->gemm_p) set_seqp(e, g, e->seqP[l][cur].p, t);
         if (split) {
             ProfScope ps(e, e->pair_on && !e->pair_w3 ? "k_gru_step_split_w2" : "k_gru_step_split", "gru_step", 2.0 * B * 3 * H * H, st);
-            launch_gru_split(e, GruSplitArgs{g, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? g.seqp - H : nullptr}, Ba, st);
+            launch_gru_split(e, GruSplitArgs{g, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? seqp_prev(g, H) : nullptr}, Ba, st);
             e->hcur[l] = hc ^ 1;
             continue;
         }
@@ -680,12 +692,9 @@ int stage_gru_round(se_engine *e, const int *slots, hipStream_t st) {
             GruStepArgs &ga = m.a[z++];
             ga = GruStepArgs{gi[l] + (long)t * 3 * H, (long)T * 3 * H, e->hbuf[l][hc].p, e->whh[l].p, e->bhh[l].p,
                              e->hbuf[l][hc ^ 1].p, e->seqr[l][slots[l]].p + (long)t * H, (long)T * H, e->bact_slot[slots[l]], H};
-            if (e->gemm_p) {
-                ga.seqp = reinterpret_cast<__bf16 *>(e->seqP[l][slots[l]].p) + (long)t * H;
-                ga.seqp_ld = (long)T * H; ga.seqp_plane = (long)B * T * H; set_seqp_format(e, ga);
-            }
+            if (e->gemm_p) set_seqp(e, ga, e->seqP[l][slots[l]].p, t);
             e->hcur[l] = hc ^ 1;
-            if (split) ms.a[z - 1] = GruSplitArgs{ga, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? ga.seqp - H : nullptr};
+            if (split) ms.a[z - 1] = GruSplitArgs{ga, reinterpret_cast<const uint4 *>(e->whh_p[l].p), t ? seqp_prev(ga, H) : nullptr};
         }
         if (split) {
             ProfScope ps(e, e->pair_on && !e->pair_w3 ? "k_gru_step_split_multi_w2" : "k_gru_step_split_multi", "gru_step", 2.0 * B * 3 * H * H * z, st);
@@ -790,6 +799,9 @@ int ensure_ready(se_engine *e) {
     int rc = prepare_weights(e);
     if (rc) return rc;
     if (replanned) {
+        // (convert_history_p: the conv history rings only.  gruinP and seqP carry nothing from call to call - the recurrent state is fp32
+        // and is split at t = 0 - so a load that flips their format or their K-blocking needs no conversion: every launch derives
+        // strides and layout from the engine's current flags)
         if ((rc = prepare_weights_p(e)) || (rc = convert_history_p(e))) return rc;
         // capability only: whether THIS batch takes the plane GEMMs is select_gemm_route()'s decision (a batch on the skinny route
         // never allocated gruinP / seqP, so a weight reload must not switch the plane route back on behind its back)
@@ -804,7 +816,7 @@ int ensure_ready(se_engine *e) {
                     const int cabs = d / Fl, f = d - cabs * Fl;
                     wp[(size_t)r * D + ((size_t)(cabs >> 3) * Fl + f) * 8 + (cabs & 7)] = w[(size_t)r * D + d];
                 }
-            if ((rc = e->pair_on ? upload_planes_pair(e, e->wih_xp, wp, pair_wplanes(e)) : upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
+            if ((rc = e->pair_on ? upload_planes_pair(e, e->wih_xp, wp, pair_wplanes(e), kblock_on(e) ? (size_t)D : 0) : upload_planes(e, e->wih_xp, wp, e->precision))) return rc;
             // fc_output_layer rows, its bias and the affine of the norm behind it in the same order (each dot product is unchanged;
             // only where it lands changes), channels padded to whole octets with zero rows.  (gemm_p_cap above asks for whole
             // octets, so today ND == D and no padding row exists; the padding is what a relaxed cap would need, and is untested)
@@ -818,7 +830,7 @@ int ensure_ready(se_engine *e) {
                 std::copy(fw.begin() + (size_t)d * H, fw.begin() + (size_t)(d + 1) * H, fwp.begin() + dp * H);
                 fbp[dp] = fb[d]; nwp[dp] = nw[d]; nbp[dp] = nb[d];
             }
-            if ((rc = e->pair_on ? upload_planes_pair(e, e->fcw_xp, fwp, pair_wplanes(e)) : upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
+            if ((rc = e->pair_on ? upload_planes_pair(e, e->fcw_xp, fwp, pair_wplanes(e), kblock_on(e) ? (size_t)H : 0) : upload_planes(e, e->fcw_xp, fwp, e->precision)) || (rc = dev_upload(e, e->fcb_p, fbp)) || (rc = dev_upload(e, e->gnw_p, nwp)) ||
                 (rc = dev_upload(e, e->gnb_p, nbp)))
                 return rc;
         }
@@ -930,6 +942,7 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     if (const char *s = getenv("SE_F16_PAIR")) e->f16_pair = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_F16_PAIR_CONV")) e->f16_pair_conv = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PAIR_W3")) e->pair_w3 = atoi(s) != 0 ? 1 : 0;
+    if (const char *s = getenv("SE_GEMM_KBLOCK")) e->gemm_kblock = atoi(s) != 0 ? 1 : 0;
     if (const char *s = getenv("SE_PIPELINE")) e->pipeline = atoi(s);
 #ifdef SE_DEBUG_KNOBS  // timing-experiment build only (profiles/pipe_split.sh): drops whole stages, the audio is WRONG
     if (const char *s = getenv("SE_DBG_SKIP")) { e->dbg_skip = atoi(s); fprintf(stderr, "se_engine: SE_DBG_SKIP=%d - stages are skipped, results are WRONG (timing experiment)\n", e->dbg_skip); }
@@ -961,6 +974,8 @@ int se_create(const se_config *cfg, int device, se_engine **out) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<kPairPlanesW, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               2 * (1024 * kPairPlanesA + 512 * kPairPlanesW) * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              2 * (1024 * kPairPlanesA + 512 * kPairPlanesW2) * 16);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_p<kPairPlanesW2, PlaneFmt::kF16Pair, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               2 * (1024 * kPairPlanesA + 512 * kPairPlanesW2) * 16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 512);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gru_step2<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 192 * 128);
@@ -1414,6 +1429,12 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int L = e->L, T = e->T, B = e->B, cur = e->slot;
     int C = 0, F = 0, idx = -1;
+    if (host_out && !strcmp(name, "gemm_kblock")) {  // one value, no tensor: 1 where this batch's bottleneck GEMMs run on K-blocked operands
+        if (count) *count = 1;
+        if (capacity < 1) return fail(e, SE_ERR_ARG, "buffer too small: need 1 float");
+        host_out[0] = e->gemm_p && kblock_on(e) ? 1.0f : 0.0f;
+        return SE_OK;
+    }
     if (strncmp(name, "ft", 2)) {  // operand tensors are split-bf16 planes, summed back on the host
         se_convp_state &S = *e->cp;
         const float *psrc = nullptr;
@@ -1454,7 +1475,8 @@ static int read_tap_impl(se_engine *e, const char *name, float *host_out, float 
                         float v = 0;
                         uint16_t up[3] = {0, 0, 0};
                         for (int pl = 0; pl < PLn; pl++) {
-                            const uint16_t u = h[((size_t)pl * B * T + (size_t)b * T + t) * D + ((size_t)(c >> 3) * Fl + f) * 8 + (c & 7)];
+                            const size_t row = (size_t)b * T + t, k = ((size_t)(c >> 3) * Fl + f) * 8 + (c & 7);
+                            const uint16_t u = kblock_on(e) ? h[kblock_index((long)row, D, (long)k, pl)] : h[((size_t)pl * B * T + row) * D + k];
                             up[pl] = u;
                             if (PLn == 1) { _Float16 hv; memcpy(&hv, &u, 2); v += (float)hv; } else v += bf16_to_f32(u);
                         }

@@ -1,0 +1,175 @@
+"""GPU tests of the K-blocked pair operands of the bottleneck GEMMs (csrc/gemm_kblock.h, SE_GEMM_KBLOCK).  Where the fp16 pair
+is on with its two stored weight planes, gruinP / seqP and the k_gemm_p weights are stored [row][K / 32][plane][32] and k_gemm_p stages
+whole 128-byte lines; SE_GEMM_KBLOCK=0 keeps plane-major buffers.  The same fragments go into the same MFMAs in the same order, so the
+two layouts must agree BIT FOR BIT: outputs, every tap and the exported state.
+Shapes: the smallest 512-point and 400-point configurations on the plane GEMM route (last level 32 channels: K = 544 = 17 chunks / 416 = 13,
+hidden 64 / 32) at 40 streams = 840 GEMM rows - above the 800-row skinny crossover, a 72-row M tail, more than 16 streams for the split
+GRU step - and 17 streams, which run the skinny fp32 GEMM and the fp32 step kernels and must ignore the layout.  6400 samples with
+flag=False, then 4800 with the carried state."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import FULL400, FULL512, rel_rms, spec_of
+from speech_enhancement_mi_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+CFG512 = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)
+CFG400 = dict(FULL400, num_channels=[8, 8, 16, 32], hidden=32)
+L1, L2 = 6400, 4800
+TAPS = ["feat", "enc0", "enc1", "enc2", "enc3", "gru", "dec0", "dec1", "dec2"]
+KNOBS = ("SE_F16_PAIR", "SE_F16_PAIR_CONV", "SE_PAIR_W3", "SE_PIPELINE", "SE_SKIP_MIN_BATCH", "SE_DEC_PAIR", "SE_IO_FUSE", "SE_GRU_SPLIT",
+         "SE_GEMM_KBLOCK", "SE_GEMM_SKINNY_ROWS", "SE_GEMM_P")
+OFF = {"SE_GEMM_KBLOCK": "0"}
+
+
+def _engine(cfg, env, monkeypatch, seed=4, sd=None):
+    """An engine created under `env` (the knobs are read at creation)."""
+    from speech_enhancement_mi_amd import engine
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
+                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
+    e = engine.Engine(c, 0)
+    e.load_state_dict(sd if sd is not None else synth.make_state_dict(spec_of(cfg), seed=seed))
+    return e
+
+
+def _cuda(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+
+
+@pytest.fixture(scope="module")
+def audio():
+    mix, _ = synth.synth_utterances(40, L1 + L2, 3, seed=61)
+    mix.setflags(write=False)
+    return mix
+
+
+def _snapshot(e, cfg, y):
+    state = {"h": e.export_state("h"), **{f"buf{i}": e.export_state(f"buf{i}") for i in range(len(cfg["num_channels"]))}}
+    return {"out": y, **{t: e.read_tap(t) for t in TAPS}, **state}
+
+
+def _kblocked(e):
+    """1 where the batch of the last call ran its bottleneck GEMMs on K-blocked operands."""
+    return int(e.read_tap("gemm_kblock")[0])
+
+
+def _assert_same(a, b, what):
+    for k in a:
+        d = np.abs(a[k].astype(np.float64) - b[k])
+        print(f"{what} {k}: max abs diff {d.max():.3g}")
+        assert np.array_equal(a[k], b[k]), (what, k, float(d.max()))
+
+
+SHAPES = {"512pt_40": (CFG512, 40), "400pt_40": (CFG400, 40), "512pt_17": (CFG512, 17)}
+# (settings, K-blocked operands expected at 40 streams)
+SETTINGS = [({}, 1), ({"SE_PIPELINE": "0"}, 1), ({"SE_PIPELINE": "0", "SE_GRU_SPLIT": "1"}, 1), ({"SE_PAIR_W3": "1"}, 0), ({"SE_F16_PAIR": "0"}, 0)]
+
+
+@pytest.mark.parametrize("setting", SETTINGS, ids=lambda s: ",".join(f"{k}={v}" for k, v in s[0].items()) or "default")
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_kblocked_operands_give_the_bits_of_plane_major(shape, setting, audio, monkeypatch):
+    """Default against SE_GEMM_KBLOCK=0 over two calls with carried state.  At 40 streams the default really is K-blocked, except under
+    SE_PAIR_W3=1 and SE_F16_PAIR=0, which keep plane-major either way; at 17 streams (skinny GEMM, fp32 step) nothing is K-blocked."""
+    cfg, batch = SHAPES[shape]
+    env, want = setting
+    e_kb, e_pm = _engine(cfg, env, monkeypatch), _engine(cfg, dict(env, **OFF), monkeypatch)
+    for lo, hi, flag in ((0, L1, False), (L1, L1 + L2, True)):
+        x = _cuda(audio[:batch, :, lo:hi])
+        kb = _snapshot(e_kb, cfg, e_kb.realtime_process(x, flag=flag).cpu().numpy())
+        pm = _snapshot(e_pm, cfg, e_pm.realtime_process(x, flag=flag).cpu().numpy())
+        assert np.isfinite(pm["out"]).all() and np.abs(pm["out"]).max() > 0
+        _assert_same(kb, pm, f"{shape} {env} flag {flag}")
+    assert _kblocked(e_pm) == 0
+    assert _kblocked(e_kb) == (want if batch == 40 else 0), (shape, env)
+
+
+@pytest.mark.parametrize("shape", ["512pt_40", "400pt_40"])
+def test_kblocked_ragged_batch(shape, audio, monkeypatch):
+    """Per-stream lengths (a chains call): the active prefix shrinks from 40 to 10 rows, below the allocation batch, while the K-blocked
+    rows keep the allocation's strides.  Bit-equal to SE_GEMM_KBLOCK=0, the padding zero."""
+    cfg, _ = SHAPES[shape]
+    L = L1 + L2
+    lens = [L - 1600 * (b % 4) - 37 * (b % 3) for b in range(40)]
+    ys = []
+    for env in ({}, OFF):
+        e = _engine(cfg, env, monkeypatch)
+        ys.append(e.realtime_process(_cuda(audio[:, :, :L]), lengths=lens).cpu().numpy())
+        assert _kblocked(e) == (0 if env else 1)
+    assert np.abs(ys[1]).max() > 0
+    assert np.array_equal(ys[0], ys[1])
+    for b in range(40):
+        assert np.all(ys[0][b, lens[b]:] == 0), b
+
+
+def _guard_failing(cfg):
+    sd = {k: np.array(v, dtype=np.float32, copy=True) for k, v in synth.make_state_dict(spec_of(cfg), seed=4).items()}
+    for k in ("convlist.2.conv.weight", "convlist.2.net.0.weight"):  # (one tensor under the reference's two names)
+        if k in sd:
+            sd[k].reshape(-1)[5] = 40.0  # a weight operand of 2^4 or more: f16_pair_guard keeps the bf16 route
+    return sd
+
+
+@pytest.mark.parametrize("first", ["pair_first", "bf16_first"])
+def test_checkpoint_across_the_range_guard_between_two_calls(first, audio, monkeypatch):
+    """A checkpoint on the other side of f16_pair_guard loaded between two calls flips the pair format, and with it the K-blocking of
+    gruinP / seqP and of the GEMM weights, in both directions; the carried state is fp32, so nothing is converted.  Bit-equal to the same
+    sequence under SE_GEMM_KBLOCK=0."""
+    cfg = CFG512
+    good, bad = synth.make_state_dict(spec_of(cfg), seed=4), _guard_failing(cfg)
+    sds = (good, bad) if first == "pair_first" else (bad, good)
+    e_kb, e_pm = _engine(cfg, {}, monkeypatch, sd=sds[0]), _engine(cfg, OFF, monkeypatch, sd=sds[0])
+    seen = []
+    for n, (lo, hi, flag) in enumerate(((0, L1, False), (L1, L1 + L2, True))):
+        if n == 1:
+            e_kb.load_state_dict(sds[1])
+            e_pm.load_state_dict(sds[1])
+        x = _cuda(audio[:40, :, lo:hi])
+        kb = _snapshot(e_kb, cfg, e_kb.realtime_process(x, flag=flag).cpu().numpy())
+        pm = _snapshot(e_pm, cfg, e_pm.realtime_process(x, flag=flag).cpu().numpy())
+        assert np.isfinite(pm["out"]).all() and np.abs(pm["out"]).max() > 0
+        _assert_same(kb, pm, f"{first} call {n}")
+        seen.append(_kblocked(e_kb))
+        assert _kblocked(e_pm) == 0
+    assert seen == ([1, 0] if first == "pair_first" else [0, 1]), seen
+
+
+@pytest.mark.parametrize("batch", [17, 40])
+def test_kblocked_route_forward_against_oracle(batch, audio, monkeypatch):
+    """The bars of test_gpu_f16_pair.py on the default route (no knob set: 40 streams K-blocked, 17 on the skinny GEMM): three frames
+    through forward() with the state carried, output within 1e-4, the decoder-input tap, the GRU-input tap and h within 2e-5."""
+    from oracle import crn_oracle as orc
+    cfg = CFG512
+    e = _engine(cfg, {}, monkeypatch)
+    o = orc.CrnOracle(**cfg)
+    o.load_state_dict(synth.make_state_dict(spec_of(cfg), seed=4))
+    e.reset(batch)
+    o.reset(batch)
+    F = cfg["num_freqs"]
+    for n in range(3):
+        seg = np.ascontiguousarray(audio[:batch, :, n * 1600:n * 1600 + 3200])
+        x = o.stft(seg.reshape(-1, 3200)).reshape(batch, 3, F, 21, 2)
+        yo = o.forward(x)
+        ye = e.forward(_cuda(x)).cpu().numpy()
+        r_out, r_gru, r_enc = rel_rms(ye, yo), rel_rms(e.read_tap("gru"), o.tap("gru")), rel_rms(e.read_tap("enc3"), o.tap("enc3"))
+        print(f"batch {batch} frame {n}: out {r_out:.2e}  gru tap {r_gru:.2e}  enc3 tap {r_enc:.2e}")
+        assert r_out < 1e-4 and r_gru < 2e-5 and r_enc < 2e-5, (n, r_out, r_gru, r_enc)
+    assert rel_rms(e.export_state("h"), o.state("h")) < 2e-5
+    assert _kblocked(e) == (1 if batch == 40 else 0)
+
+
+def test_kblocked_route_against_bf16_route(audio, monkeypatch):
+    """2e-6 between two fp32-accurate routes: the default (K-blocked pair) against SE_F16_PAIR=0, outputs over two calls."""
+    cfg = CFG512
+    e_new, e_old = _engine(cfg, {}, monkeypatch), _engine(cfg, {"SE_F16_PAIR": "0"}, monkeypatch)
+    for lo, hi, flag in ((0, L1, False), (L1, L1 + L2, True)):
+        x = _cuda(audio[:40, :, lo:hi])
+        r = rel_rms(e_new.realtime_process(x, flag=flag).cpu().numpy(), e_old.realtime_process(x, flag=flag).cpu().numpy())
+        print(f"flag {flag}: K-blocked pair vs bf16 route {r:.2e}")
+        assert r < 2e-6
+    assert _kblocked(e_new) == 1 and _kblocked(e_old) == 0
