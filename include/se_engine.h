@@ -171,7 +171,7 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
                               additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
-                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference); se_hifi_* (HiFi-GAN generator inference) */
+                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference); se_hifi_* (HiFi-GAN generator inference, and its training: se_hifi_lstm_train_fwd, se_hifi_*_bwd, se_hifi_chansum) */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -567,6 +567,33 @@ int se_hifi_lstm_rows(const float *gi, const float *h0, const float *c0, const f
                       int TT, int H, void *stream);
 int se_hifi_seqnorm_rows(const float *o, const float *w, const float *bias, const float *mean_in, const int64_t *step, const int64_t *cnt, float *wm,
                          float *mean_out, float *y, int Nc, int B, int C, int T, int F, void *stream);
+/* HiFi-GAN generator training (csrc/se_hifi.hip, csrc/se_hifi_train.hip; hifigan_training.py): uniform calls, no float atomics.
+ * se_hifi_lstm_train_fwd: se_hifi_lstm (the same arithmetic: out, hT, cT bit-equal) that also stores, per step, the activated gates
+ *   [B][TT][4H] (i, f, g, o) and the cell cs [B][TT][H].
+ * se_hifi_lstm_bwd: the backward sweep of one layer over the R = B Nc (utterance, window) rows of a pass, T steps, one launch per step
+ *   from T - 1 down: (h, c) are detached at every window seam, so a row starts from dh_rec = dc = 0.  dout / gates / cs as the forward
+ *   left them (row r T + t of [R T][.] is step t of row r = b Nc + n), cprev [R T][H] = c_{t-1} of every row (cs shifted by one step
+ *   with the pass's entry cell in front of every utterance: se_train_gru_hprev of cs), whht = W_hh^T [H][4H];
+ *   -> dgates [R T][4H], the gradient of gi (and of the recurrent pre-activation); dc [R][H] scratch.
+ * se_hifi_seqnorm_bwd: dy [S][C][T][F] -> dout [B][Nc T][D], the gradient of the fc output o before its tanh, through
+ *   y = (tanh(o) - g_n) w + b with g_{n-1} detached: e = dy w, d tanh = e - (1 - alpha_n) mean_{T x D}(e), alpha_n = step_n /
+ *   (step_n + D), step_n = step + n D; wm [B Nc] = g per window as se_hifi_seqnorm left it; em [S] scratch; pw / pb [S][D] = the
+ *   slabs of dw / db (fold with se_train_colsum).
+ * se_hifi_gate_bwd: dx = dy (sech^2(x) sigmoid(x) + tanh(x) sigmoid(x) (1 - sigmoid(x))).
+ * se_hifi_skip_bwd: the adjoint of se_hifi_skip: duv [S][2 Co][T][Fr], dyd [S][Co][T][Fy] (through the self-gate of yd; the padded
+ *   columns f >= Fy give nothing).  se_hifi_rows_bwd: the adjoint of se_hifi_rows.
+ * se_hifi_chansum: part[r] = the sum of the X values of row r (double partial sums, fixed tree): x [S][C][T F] -> the [S][C] slab of a
+ *   convolution's bias gradient. */
+int se_hifi_lstm_train_fwd(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, float *gates, float *cs, int B,
+                           int TT, int H, void *stream);
+int se_hifi_lstm_bwd(const float *dout, const float *gates, const float *cs, const float *cprev, const float *whht, float *dgates, float *dc, int B, int Nc, int T,
+                     int H, void *stream);
+int se_hifi_seqnorm_bwd(const float *dy, const float *o, const float *w, const float *wm, double step, float *em, float *dout, float *pw, float *pb, int Nc, int B,
+                        int C, int T, int F, void *stream);
+int se_hifi_gate_bwd(const float *dy, const float *x, float *dx, int64_t n, void *stream);
+int se_hifi_skip_bwd(const float *dout, const float *yd, const float *uv, float *duv, float *dyd, int S, int Co, int T, int Fy, int Fr, void *stream);
+int se_hifi_rows_bwd(const float *drows, float *dx, int Nc, int B, int C, int T, int F, void *stream);
+int se_hifi_chansum(const float *x, float *part, int64_t rows, int X, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -22,6 +22,8 @@
 //   k_hifi_winmean / k_hifi_scan / k_hifi_normapply   the bottleneck's tanh and running-mean norm: the mean of tanh(o) over T x D per
 //                     window (double partial sums, fixed tree), the per-utterance scan g = alpha g + (1 - alpha) mean with
 //                     alpha = step / (step + D) in double, and y = (tanh(o) - g) w + b written back in [S][C][T][F]
+//   k_hifi_lstm_step<.., true>   training (se_hifi_lstm_train_fwd): the step also stores its activated gates and cell; the backward
+//                     kernels are csrc/se_hifi_train.hip
 //   k_hifi_lstm_step<true> / k_hifi_scan_rows   chunk chains (se_hifi_lstm_rows, se_hifi_seqnorm_rows): every row its own number of
 //                     steps, every utterance its own window count and its own step; a row's arithmetic is the plain kernels'
 #include <hip/hip_runtime.h>
@@ -166,12 +168,15 @@ struct LstmArgs {
     int B, H;
     const int *steps;   // kRows: row b runs steps[b] steps, this launch is step t of them
     int t;
+    float *gates, *cs;  // kSave: this step's activated gates (i, f, g, o) and cell, rows at ldg / ldc
+    long ldg, ldc;
 };
 
 // kRows (chunk chains): a row is live at step t while t < steps[row].  A live row computes what it computes in the plain kernel - the
 // dot products of a row never see another row's h - and a finished one writes a zero into out[row][t] (the fc GEMM and the window
 // means read all of out), at t = 0 also its h0 / c0 into hT / cT (steps = 0).  The last live step of a row writes its hT.
-template <bool kRows>
+// kSave (training, se_hifi_lstm_train_fwd): the same arithmetic, and the step's activated gates and cell are stored for the backward.
+template <bool kRows, bool kSave>
 __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
     __shared__ float pre[4][kLstmBT];
     extern __shared__ float hs[];   // [kLstmBT][H]: the batch tile's h rows, read from memory once per workgroup, zeros past the batch
@@ -221,6 +226,11 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
         const float h = og * tanhf(c);
         a.cout[row * a.H + j] = c;
         a.out[row * a.ldo + j] = h;
+        if (kSave) {
+            float *g = a.gates + row * a.ldg;
+            g[j] = ig, g[a.H + j] = fg, g[2 * a.H + j] = gg, g[3 * a.H + j] = og;
+            a.cs[row * a.ldc + j] = c;
+        }
         if (kRows ? a.t == a.steps[row] - 1 : a.hT != nullptr) a.hT[row * a.H + j] = h;
     }
 }
@@ -298,8 +308,9 @@ int blocks_of(const char *what, long n, unsigned *blocks) {
 }
 
 // one launch per step; steps = null: every row runs all TT steps (k_hifi_lstm_step<false>, which never reads a.steps / a.t)
+// gates / cs given (both, steps = null): the training forward, which also stores gates [B][TT][4H] and cs [B][TT][H]
 int lstm_launch(const char *what, const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, const int *steps,
-                int B, int TT, int H, void *stream) {
+                int B, int TT, int H, void *stream, float *gates = nullptr, float *cs = nullptr) {
     if (!gi || !h0 || !c0 || !whh || !out || !hT || !cT) return se::train_fail(SE_ERR_ARG, "%s: null argument", what);
     if (B <= 0 || (B + kLstmBT - 1) / kLstmBT > 65535 || TT <= 0 || H < 8 || H % 8 || H > 1024)
         return se::train_fail(SE_ERR_ARG, "%s: B = %d rows, %d steps, hidden %d (a multiple of 8, up to 1024)", what, B, TT, H);
@@ -313,10 +324,14 @@ int lstm_launch(const char *what, const float *gi, const float *h0, const float 
         a.hT = steps || t == TT - 1 ? hT : nullptr;
         a.B = B, a.H = H;
         a.steps = steps, a.t = t;
+        a.gates = gates ? gates + (long)t * 4 * H : nullptr, a.ldg = (long)TT * 4 * H;
+        a.cs = cs ? cs + (long)t * H : nullptr, a.ldc = (long)TT * H;
         if (steps)
-            hipLaunchKernelGGL(k_hifi_lstm_step<true>, grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
+            hipLaunchKernelGGL((k_hifi_lstm_step<true, false>), grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
+        else if (gates)
+            hipLaunchKernelGGL((k_hifi_lstm_step<false, true>), grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
         else
-            hipLaunchKernelGGL(k_hifi_lstm_step<false>, grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
+            hipLaunchKernelGGL((k_hifi_lstm_step<false, false>), grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
     }
     return launched(what);
 }
@@ -372,6 +387,12 @@ int se_hifi_rows(const float *x, float *rows, int Nc, int B, int C_, int T, int 
 
 int se_hifi_lstm(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, int B, int TT, int H, void *stream) {
     return lstm_launch("se_hifi_lstm", gi, h0, c0, whh, out, hT, cT, nullptr, B, TT, H, stream);
+}
+
+int se_hifi_lstm_train_fwd(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, float *gates, float *cs, int B,
+                           int TT, int H, void *stream) {
+    if (!gates || !cs) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_train_fwd: null argument");
+    return lstm_launch("se_hifi_lstm_train_fwd", gi, h0, c0, whh, out, hT, cT, nullptr, B, TT, H, stream, gates, cs);
 }
 
 int se_hifi_lstm_rows(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, const int *steps, int B, int TT, int H,

@@ -8,7 +8,9 @@ Same constructors, state_dict keys and shapes (`*.weight_g` / `*.weight_v`, the 
     Generator.realtime_process(mixture[B, M, L], post=True, reset=False) -> (pred, pred_before) [B, L]
     Generator.realtime_process_chains(mixture[B, M, Lmax], resets, lengths=None, post=True) -> (pred, pred_before) [B, Lmax]
     Generator.reset(), reset_norm(streams=None), use_hip_kernels(flag), kernel_geometry_error(), max_segments, _last_path, _last_passes, taps
+    Generator.use_hip_training(flag), hip_training_error()
     Hifi_GAN.forward(x, post=True) = generator.realtime_process(x, reset=False, post=post)[0]
+    Hifi_GAN.train_stage(x, y, stage=1, y_hat=None, y_before=None, reset=True) -> loss (stages 1 and 2)
     Hifi_GAN.realtime_process_chains(x, resets, lengths=None, post=True) = the generator's, its first result
 
 Quirks of the reference that are kept:
@@ -33,7 +35,7 @@ alone; the kernel path runs every pass on the prefix of streams still running (s
 the norm's scan stopping at each stream's own last window (se_hifi_lstm_rows, se_hifi_seqnorm_rows).  Resets and lengths all alike are
 the uniform call - `realtime_process`, which still takes ONE `reset`.
 
-Two paths (the choice, the refusals and the carried state are streaming.StreamingMixin's; `reset` = not `flag`):
+Three paths (the choice, the refusals and the carried state are streaming.StreamingMixin's; `reset` = not `flag`):
   * the torch restatement (CPU, grad enabled, training mode, or after use_hip_kernels(False)): plain torch ops, differentiable.
     Encoder, decoder and postnet run every window of a pass at once (the conv history of window n is the tail of window n - 1's
     input); the LSTM - its cell written out, h and c detached at every window seam as the reference does - and the norm's scan are
@@ -41,6 +43,10 @@ Two paths (the choice, the refusals and the carried state are streaming.Streamin
   * the kernel path (`realtime_process` of a GPU tensor, eval mode, grad disabled): train_stages.py's signal chain, the convolutions
     on se_train_conv_w and the dense layers on se_train_gemm with the weight norm folded on the host (g * v / ||v|| in float64),
     everything else on csrc/se_hifi.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
+  * HIP training (opt-in, `use_hip_training(True)`; `hip_training_error()` names what it does not cover): `realtime_process` of a GPU
+    tensor with grad enabled is ONE autograd node, hifigan_training.HifiFunction - the kernel path's forward as it stands (bit-equal
+    outputs and carried state, `_last_path` "kernel") and a backward on the same kernels plus csrc/se_hifi_train.hip.  Uniform calls only.
+`Hifi_GAN.train_stage(x, y, stage)` is the reference's training loss on losses.stft_loss for stages 1 and 2 (no discriminators: 3 raises).
 Carried state: the encoder levels' last input window, the LSTM's (h, c) per layer - `_tstate` / `_kstate` - and the norm's
 (mean [B], step) in `_nstate`, which both paths share because nothing but reset_norm() ends it.
 """
@@ -154,6 +160,7 @@ class Generator(StreamingMixin, nn.Module):
         self._init_streaming(num_inputs, sample_rate, win_length, hop_length)
         self._nstate = None
         self._last_passes = None   # kernel path: the passes of the last call, [(first window, windows, streams), ...]
+        self._hip_train = False
         L = len(num_channels)
         convs, deconvs = [], []
         for i in range(L):
@@ -215,6 +222,47 @@ class Generator(StreamingMixin, nn.Module):
         plan = self._plan([not r for r in as_flags(resets, B)], lengths, B, L, M)
         return getattr(self, f"_{self._admit(mixture, plan)}_call")(mixture, plan)
 
+    # ---- HIP training (hifigan_training.HifiFunction) ------------------------------------------------------------------------------
+    def use_hip_training(self, flag=True):
+        """True: realtime_process of a GPU tensor with grad enabled runs forward AND backward on the kernels, as ONE autograd node
+        (hifigan_training.HifiFunction) that returns (pred, pred_before), sharing the carried state with the inference kernel path.
+        False (default): grad-enabled calls take the restatement.  Raises ValueError at once for a geometry or a dropout setting the
+        training kernels do not cover."""
+        if flag:
+            err = self.hip_training_error()
+            if err:
+                raise ValueError(f"Generator HIP training: {err}")
+        self._hip_train = bool(flag)
+        return self
+
+    def hip_training_error(self):
+        """None when HifiFunction can train this model as it stands, else the limit that fails (geometry, or active dropout)."""
+        err = self.kernel_geometry_error()
+        if err:
+            return err
+        if self.training and any(b.dropout.p > 0 for b in list(self.convlist) + list(self.deconvlist) + list(self.postnet)):
+            return "dropout is active in training mode: the training kernels have no dropout (use the restatement, or dropout = 0)"
+        return None
+
+    def _choose_path(self, mixture):
+        if self._hip_train and mixture.is_cuda and torch.is_grad_enabled():
+            return "train"
+        return super()._choose_path(mixture)
+
+    def _train_call(self, mixture, plan):
+        from .hifigan_training import HifiFunction
+        err = self.hip_training_error()
+        if err:
+            raise ValueError(f"Generator HIP training: {err}")
+        ns = self._norm_for(mixture.shape[0])
+        if not plan.uniform or (ns is not None and isinstance(ns["step"], list)):
+            raise ValueError("Generator HIP training runs uniform calls only (one reset, full lengths, one carried norm step count): "
+                             "per-stream resets, lengths or step counts train on the restatement, use_hip_training(False)")
+        K._need_gpu(mixture, self.gru.norm.weight)
+        if mixture.shape[1] != self._mics:
+            raise ValueError(f"Generator HIP training: {mixture.shape[1]} microphones, the model is built for {self._mics}")
+        return HifiFunction.apply(self, mixture, plan, *[p for _, p in self.named_parameters()])
+
     def _norm_for(self, B):
         """the carried (mean, step) for a batch of B; refuses another batch size, except the carried batch of 1 the reference broadcasts"""
         ns = self._nstate
@@ -263,8 +311,8 @@ class Generator(StreamingMixin, nn.Module):
             buf = st["buf"][i] if st is not None else h.new_zeros(B, C_, F_, P)
             if N == 1:
                 prev = buf
-            else:   # the history of window n: the last P frames of window n - 1's input (P < T)
-                prev = torch.cat([buf[:, None], h.reshape(B, N, C_, F_, T)[:, :-1, ..., T - P:]], dim=1).reshape(B * N, C_, F_, P)
+            else:   # the history of window n: the last P frames of window n - 1's input (P < T), detached as the reference's buffer is
+                prev = torch.cat([buf[:, None], h.reshape(B, N, C_, F_, T)[:, :-1, ..., T - P:].detach()], dim=1).reshape(B * N, C_, F_, P)
             inp = torch.cat([prev, h], dim=-1)
             bufs.append(inp.reshape(B, N, C_, F_, P + T)[:, -1, ..., -P:].detach())
             h = _gate(blk.dropout(Fn.conv2d(inp, _w(blk.conv), blk.conv.bias, stride=(2, 1), padding=(2, 0), dilation=blk.conv.dilation)))
@@ -418,17 +466,22 @@ class Generator(StreamingMixin, nn.Module):
         bi, bh = getattr(m, f"bias_ih_l{l}"), getattr(m, f"bias_hh_l{l}")
         return self._cached(("lstm_b", l), [bi, bh], lambda: (bi.detach().float() + bh.detach().float()).contiguous())
 
-    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, ysegs, start):
+    def _kernel_pass(self, mixture, plan, sig, state, n0, Nc, ysegs, start, sv=None):
         """Windows [n0, n0 + Nc) of the call: STFT, features, encoder, bottleneck, decoder, both masks and the postnet, iSTFT into
         ysegs; advances `state` (a dict this call owns: buf, h, c and the norm's mean [B]).  Chunk chains: `plan` holds the streams
         of this pass (the leading plan.B rows of mixture and of every state tensor; ysegs may be wider); a stream runs the LSTM and
         the norm's scan over its own windows of the pass only, and its encoder buffers stop at its own last window.  start: the
         norm's step count per caller row as the call found it.  A stream that has a window at n0 has run exactly n0 windows of this
-        call, so it enters the pass at start[row] + n0 * D: one count for all takes the scalar kernel, else se_hifi_seqnorm_rows."""
+        call, so it enters the pass at start[row] + n0 * D: one count for all takes the scalar kernel, else se_hifi_seqnorm_rows.
+        sv (a dict; uniform calls only): the pass re-run for hifigan_training's backward - the LSTM also stores its gates and cells
+        (se_hifi_lstm_train_fwd, the same arithmetic), sv receives every activation the backward reads, and the pass stops after the
+        decoder: no mask, no postnet, nothing written to ysegs."""
         lib, st, dev = K._lib(), K._st, mixture.device
         c = self._cfg
         B, M, T, F0, ch, Fq, H, NL, Lv = plan.B, mixture.shape[1], plan.T, plan.F0, plan.ch, plan.Fq, c["hidden"], c["num_layers"], len(self.convlist)
         S, TT = Nc * B, Nc * T
+        keep = sv is not None
+        ypre, xs, lstm, dec = [], [], [], []
         steps, live = gru_steps(plan, dev, T, 1, n0, Nc)   # chains: per stream its LSTM steps and its own windows of this pass
         spec = stft(plan, sig, mixture, M, n0, Nc)
         # encoder: xin[i] = [Nc + 1][B][C][T][F], slab 0 = the carried input window of level i (its time history)
@@ -448,6 +501,8 @@ class Generator(StreamingMixin, nn.Module):
                 enc = _new(S, Co, T, Fo, dev=dev)
                 dst = _p(enc)
             _run("k_hifi_gate", 0.0, lib.se_hifi_gate, _p(y), dst, y.numel(), st())
+            if keep:
+                ypre.append(y)
         del y
         # bottleneck
         Cl, Fl = ch[Lv], Fq[Lv]
@@ -460,7 +515,12 @@ class Generator(StreamingMixin, nn.Module):
             gi = K._gemm(x_l, getattr(m, f"weight_ih_l{l}"), self._lstm_bias(l))
             out, hT, cT = _new(B * TT, H, dev=dev), _new(B, H, dev=dev), _new(B, H, dev=dev)
             args = (_p(gi), _p(state["h"][l]), _p(state["c"][l]), _p(getattr(m, f"weight_hh_l{l}")), _p(out), _p(hT), _p(cT))
-            if steps is None:
+            if keep:
+                gates, cs = _new(B * TT, 4 * H, dev=dev), _new(B * TT, H, dev=dev)
+                _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_train_fwd, *args, _p(gates), _p(cs), B, TT, H, st())
+                xs.append(x_l)
+                lstm.append(dict(gates=gates, cs=cs, out=out, h0=state["h"][l], c0=state["c"][l]))
+            elif steps is None:
                 _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm, *args, B, TT, H, st())
             else:
                 _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_rows, *args, _ip(steps), B, TT, H, st())
@@ -482,6 +542,8 @@ class Generator(StreamingMixin, nn.Module):
             _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm_rows, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), _ip(step_dev), _ip(cnt), _p(wm),
                  _p(mean_out), _p(h), Nc, B, Cl, T, Fl, st())
         state["mean"] = mean_out
+        if keep:
+            sv.update(spec=spec, xin=xin, ypre=ypre, xs=xs, lstm=lstm, o=o, wm=wm, step=float(step[0]), dec=dec)
         del o
         # decoder
         Ci, Fi = Cl, Fl
@@ -489,6 +551,8 @@ class Generator(StreamingMixin, nn.Module):
             Co, Fy = blk.conv.weight_v.shape[1], 2 * Fi - 1
             w = self._folded(("deconv", j), blk.conv)
             yd = _new(S, Co, T, Fy, dev=dev)
+            if keep:   # the level's input, transposed-convolution output and (below) 1x1 pair: what its backward reads
+                dec.append(dict(x_in=h, yd=yd, Ci=Ci, Co=Co, Fi=Fi, Fy=Fy))
             for kind in (1, 2):
                 K.conv_w(kind, _p(h), None, w, 15, Co * 15, blk.conv.bias, yd, S, Ci, Co, T, Fi, Fy, 2 ** j)
             if j < Lv - 1:
@@ -502,12 +566,17 @@ class Generator(StreamingMixin, nn.Module):
                 K.conv_w(3, res, None, self._folded(("resmask", j), blk.residualmask), Cr, 1, blk.residualmask.bias, uv, S, Cr, Co, T, Fr, Fr, 0, 0, 2 * Co, Co)
                 h = _new(S, Co, T, Fr, dev=dev)
                 _run("k_hifi_skip", 0.0, lib.se_hifi_skip, _p(yd), _p(uv), _p(h), S, Co, T, Fy, Fr, st())
+                if keep:
+                    dec[-1].update(uv=uv, k=k, Cr=Cr, Fr=Fr)
                 del uv
                 Ci, Fi = Co, Fr
             else:
                 h = _new(S, Co, T, Fy, dev=dev)
                 _run("k_hifi_gate", 0.0, lib.se_hifi_gate, _p(yd), _p(h), yd.numel(), st())
         del yd
+        if keep:
+            sv["hdec"] = h
+            return
         Y = _new(S, T, F0, 2, dev=dev)
         _run("k_tmask", 0.0, lib.se_train_mask_fwd, _p(h), _p(spec), _p(Y), S, M, T, F0, st())
         istft_into(plan, sig, Y, ysegs[1], n0, Nc)
@@ -520,9 +589,11 @@ class Generator(StreamingMixin, nn.Module):
         state["buf"] = [own_last_slab(plan, xin[i], live, copy=True) for i in range(Lv)]
 
     @torch.no_grad()
-    def _kernel_process(self, mixture, plan):
+    def _kernel_process(self, mixture, plan, record=None):
         """One call on the kernels, uniform or chains: StreamingMixin._prefix_passes' schedule over `_kernel_pass`, the running mean as
-        the entry of the working state that no reset clears.  The norm's step counts never travel with it: they follow from the plan."""
+        the entry of the working state that no reset clears.  The norm's step counts never travel with it: they follow from the plan.
+        record (a list; HifiFunction): receives, per pass, (the pass's plan, sig, the state it entered with, n0, Nc, start) - the
+        state's tensors are replaced, never written, so holding them keeps the entry state."""
         dev, B = mixture.device, mixture.shape[0]
         c = self._cfg
         H, NL, Lv, T, ch, Fq = c["hidden"], c["num_layers"], len(self.convlist), plan.T, plan.ch, plan.Fq
@@ -535,7 +606,11 @@ class Generator(StreamingMixin, nn.Module):
             return dict(buf=[torch.zeros(B, ch[i], T, Fq[i], device=dev) for i in range(Lv)],
                         h=[torch.zeros(B, H, device=dev) for _ in range(NL)], c=[torch.zeros(B, H, device=dev) for _ in range(NL)], mean=mean)
         carried = None if old is None else dict(buf=old["buf"], h=old["h"], c=old["c"], mean=mean)
-        preds, new, passes = self._prefix_passes(mixture, plan, carried, fresh, 2, lambda *a: self._kernel_pass(*a, start), unflagged=("mean",))
+        def run_pass(mix, sub, sig, state, n0, Nc, ysegs):
+            if record is not None:
+                record.append((sub, sig, {k: list(v) if isinstance(v, list) else v for k, v in state.items()}, n0, Nc, start))
+            self._kernel_pass(mix, sub, sig, state, n0, Nc, ysegs, start)
+        preds, new, passes = self._prefix_passes(mixture, plan, carried, fresh, 2, run_pass, unflagged=("mean",))
         self._kstate = dict(B=B, buf=new["buf"], h=new["h"], c=new["c"])
         self._nstate = self._norm_state(new["mean"], [s + n * ch[Lv] * Fq[Lv] for s, n in zip(start, plan.Nb)])
         self._last_passes = passes
@@ -562,3 +637,18 @@ class Hifi_GAN(nn.Module):
     def realtime_process_chains(self, x, resets, lengths=None, post=True):
         """the generator's realtime_process_chains, its first result (this project's addition: the reference serves one stream)"""
         return self.generator.realtime_process_chains(x, resets, lengths, post)[0]
+
+    def train_stage(self, x, y, stage=1, y_hat=None, y_before=None, reset=True):
+        """The reference's training loss (hifigan.py:917-956) without its print.  Stage 2: 0.5 * stft_loss(y_hat, y, phase=True) +
+        0.5 * stft_loss(y_before, y, phase=True), (y_hat, y_before) = generator.realtime_process(x, reset=reset) unless y_hat is
+        given.  Stage 1 asks the generator for post=False, which raises TypeError here as it fails in the reference; with y_hat given
+        it is stft_loss(y_hat, y, phase=True).  Stage 3 needs the discriminators, which are not built: NotImplementedError."""
+        from .losses import stft_loss
+        if stage not in (1, 2):
+            raise NotImplementedError(f"train_stage(stage={stage}): the adversarial stage needs the discriminators, which are not built here "
+                                      "(stages 1 and 2 train the generator on stft_loss)")
+        if y_hat is None:
+            y_hat, y_before = self.generator.realtime_process(x, reset=reset, post=stage != 1)
+        if stage == 1:
+            return stft_loss(y_hat, y, phase=True)
+        return 0.5 * stft_loss(y_hat, y, phase=True) + 0.5 * stft_loss(y_before, y, phase=True)
