@@ -567,7 +567,7 @@ int se_hifi_lstm_rows(const float *gi, const float *h0, const float *c0, const f
                       int TT, int H, void *stream);
 int se_hifi_seqnorm_rows(const float *o, const float *w, const float *bias, const float *mean_in, const int64_t *step, const int64_t *cnt, float *wm,
                          float *mean_out, float *y, int Nc, int B, int C, int T, int F, void *stream);
-/* HiFi-GAN generator training (csrc/se_hifi.hip, csrc/se_hifi_train.hip; hifigan_training.py): uniform calls, no float atomics.
+/* HiFi-GAN generator training (csrc/se_hifi.hip, csrc/se_hifi_train.hip; hifigan_training.py): no float atomics.
  * se_hifi_lstm_train_fwd: se_hifi_lstm (the same arithmetic: out, hT, cT bit-equal) that also stores, per step, the activated gates
  *   [B][TT][4H] (i, f, g, o) and the cell cs [B][TT][H].
  * se_hifi_lstm_bwd: the backward sweep of one layer over the R = B Nc (utterance, window) rows of a pass, T steps, one launch per step
@@ -594,6 +594,23 @@ int se_hifi_gate_bwd(const float *dy, const float *x, float *dx, int64_t n, void
 int se_hifi_skip_bwd(const float *dout, const float *yd, const float *uv, float *duv, float *dyd, int S, int Co, int T, int Fy, int Fr, void *stream);
 int se_hifi_rows_bwd(const float *drows, float *dx, int Nc, int B, int C, int T, int F, void *stream);
 int se_hifi_chansum(const float *x, float *part, int64_t rows, int X, void *stream);
+/* HiFi-GAN chunk-chain training (the `_rows` twins of the three entries above that depend on a stream's own schedule; a live row's
+ * arithmetic is bit for bit the plain entry point's):
+ * se_hifi_lstm_train_fwd_rows: se_hifi_lstm_rows (out, hT, cT bit-equal, steps[b] = 0 included) that also stores the activated gates
+ *   and the cell of every live step; a finished row's step stores zeros into gates and cs as well as out, so everything the backward
+ *   and the weight-gradient GEMMs read is finite whatever the workspace held.
+ * se_hifi_lstm_bwd_rows: live = device int32 [B], utterance b's own windows of the pass, 0 .. Nc.  Row r = b Nc + n is swept only
+ *   where n < live[b]; a dead row reads none of dout / gates / cs / cprev and its dgates are exact zeros at every step (a tile of 8
+ *   dead rows returns before the dot products); a live row's dgates are those of se_hifi_lstm_bwd on the live rows alone.
+ * se_hifi_seqnorm_bwd_rows: step, cnt = device int64 [B], as se_hifi_seqnorm_rows takes them: window n of utterance b is at
+ *   step[b] + n D; a window n >= cnt[b] reads neither dy nor o and writes zeros to its dout rows and its pw / pb slabs.  All counts
+ *   Nc and one common step: bit-equal to se_hifi_seqnorm_bwd. */
+int se_hifi_lstm_train_fwd_rows(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, float *gates, float *cs,
+                                const int *steps, int B, int TT, int H, void *stream);
+int se_hifi_lstm_bwd_rows(const float *dout, const float *gates, const float *cs, const float *cprev, const float *whht, float *dgates, float *dc, const int *live,
+                          int B, int Nc, int T, int H, void *stream);
+int se_hifi_seqnorm_bwd_rows(const float *dy, const float *o, const float *w, const float *wm, const int64_t *step, const int64_t *cnt, float *em, float *dout,
+                             float *pw, float *pb, int Nc, int B, int C, int T, int F, void *stream);
 
 /* ---- 8f-4: synthetic multi-microphone training data on the GPU (csrc/se_synth.hip) -------------------------------------
  * Replaces the reference's CPU/gpuRIR input pipeline for DP training: multichannel.py:37-103 (Single2Multi.simulate: shoebox

@@ -26,6 +26,8 @@
 //                     kernels are csrc/se_hifi_train.hip
 //   k_hifi_lstm_step<true> / k_hifi_scan_rows   chunk chains (se_hifi_lstm_rows, se_hifi_seqnorm_rows): every row its own number of
 //                     steps, every utterance its own window count and its own step; a row's arithmetic is the plain kernels'
+//   k_hifi_lstm_step<true, true>   chunk-chain training (se_hifi_lstm_train_fwd_rows): both at once, and a finished row's step stores
+//                     zeros as its gates and cell, so whatever the backward reads of them is finite
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -176,6 +178,8 @@ struct LstmArgs {
 // dot products of a row never see another row's h - and a finished one writes a zero into out[row][t] (the fc GEMM and the window
 // means read all of out), at t = 0 also its h0 / c0 into hT / cT (steps = 0).  The last live step of a row writes its hT.
 // kSave (training, se_hifi_lstm_train_fwd): the same arithmetic, and the step's activated gates and cell are stored for the backward.
+// Both (se_hifi_lstm_train_fwd_rows): a finished row's step stores zeros as its gates and cell - the backward's shifted cell tensor and
+// the weight-gradient GEMMs read every row of the workspace.
 template <bool kRows, bool kSave>
 __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
     __shared__ float pre[4][kLstmBT];
@@ -189,6 +193,11 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_step(LstmArgs a) {
         if ((int)threadIdx.x < nb && a.t >= a.steps[b0 + threadIdx.x]) {
             const long row = b0 + threadIdx.x;
             a.out[row * a.ldo + j] = 0.0f;
+            if (kSave) {
+                float *g = a.gates + row * a.ldg;
+                g[j] = 0.0f, g[a.H + j] = 0.0f, g[2 * a.H + j] = 0.0f, g[3 * a.H + j] = 0.0f;
+                a.cs[row * a.ldc + j] = 0.0f;
+            }
             if (a.t == 0) {
                 a.hT[row * a.H + j] = a.hin[row * a.ldh + j];
                 a.cout[row * a.H + j] = a.cin[row * a.H + j];
@@ -308,7 +317,7 @@ int blocks_of(const char *what, long n, unsigned *blocks) {
 }
 
 // one launch per step; steps = null: every row runs all TT steps (k_hifi_lstm_step<false>, which never reads a.steps / a.t)
-// gates / cs given (both, steps = null): the training forward, which also stores gates [B][TT][4H] and cs [B][TT][H]
+// gates / cs given (both): the training forward, which also stores gates [B][TT][4H] and cs [B][TT][H]
 int lstm_launch(const char *what, const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, const int *steps,
                 int B, int TT, int H, void *stream, float *gates = nullptr, float *cs = nullptr) {
     if (!gi || !h0 || !c0 || !whh || !out || !hT || !cT) return se::train_fail(SE_ERR_ARG, "%s: null argument", what);
@@ -326,7 +335,9 @@ int lstm_launch(const char *what, const float *gi, const float *h0, const float 
         a.steps = steps, a.t = t;
         a.gates = gates ? gates + (long)t * 4 * H : nullptr, a.ldg = (long)TT * 4 * H;
         a.cs = cs ? cs + (long)t * H : nullptr, a.ldc = (long)TT * H;
-        if (steps)
+        if (steps && gates)
+            hipLaunchKernelGGL((k_hifi_lstm_step<true, true>), grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
+        else if (steps)
             hipLaunchKernelGGL((k_hifi_lstm_step<true, false>), grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
         else if (gates)
             hipLaunchKernelGGL((k_hifi_lstm_step<false, true>), grid, dim3(kThreads), (size_t)kLstmBT * H * sizeof(float), static_cast<hipStream_t>(stream), a);
@@ -399,6 +410,12 @@ int se_hifi_lstm_rows(const float *gi, const float *h0, const float *c0, const f
                       void *stream) {
     if (!steps) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_rows: null argument");
     return lstm_launch("se_hifi_lstm_rows", gi, h0, c0, whh, out, hT, cT, steps, B, TT, H, stream);
+}
+
+int se_hifi_lstm_train_fwd_rows(const float *gi, const float *h0, const float *c0, const float *whh, float *out, float *hT, float *cT, float *gates, float *cs,
+                                const int *steps, int B, int TT, int H, void *stream) {
+    if (!gates || !cs || !steps) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_train_fwd_rows: null argument");
+    return lstm_launch("se_hifi_lstm_train_fwd_rows", gi, h0, c0, whh, out, hT, cT, steps, B, TT, H, stream, gates, cs);
 }
 
 int se_hifi_seqnorm(const float *o, const float *w, const float *bias, const float *mean_in, double step, float *wm, float *mean_out, float *y, int Nc, int B,

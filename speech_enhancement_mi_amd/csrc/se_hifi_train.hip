@@ -8,9 +8,13 @@
 //                     stride of k, the wave by the fixed butterfly, the four waves summed as (0 + 1) + (2 + 3); then the unit's four
 //                     gate gradients and the carried dc from the saved gates and cells.  A value of dgates[t + 1] is used once per
 //                     workgroup, so it is read straight from memory (L2), not staged in LDS; no workgroup waits for another (one
-//                     launch per step).
+//                     launch per step).  <true> (se_hifi_lstm_bwd_rows, chunk chains): row r = b Nc + n is swept only where
+//                     n < live[b]; a dead row reads nothing, its dgates are exact zeros at every step, and a tile of 8 dead rows
+//                     returns before the dot products.  A live row's arithmetic is the plain kernel's.
 //   k_hifi_norm_esum / k_hifi_norm_bwd   the running-mean norm and the fc's tanh: e = dy w, d tanh = e - (1 - alpha_n) mean_{T x D}(e),
-//                     do = d tanh (1 - tanh^2) in the fc's row layout [B][Nc T][D]; dw, db as [S][D] slabs (sums over t in order)
+//                     do = d tanh (1 - tanh^2) in the fc's row layout [B][Nc T][D]; dw, db as [S][D] slabs (sums over t in order).
+//                     <true> (se_hifi_seqnorm_bwd_rows): window n of utterance b is at step[b] + n D, and a window n >= cnt[b] reads
+//                     neither dy nor o and writes zeros to its dout rows and its slabs
 //   k_hifi_gate_bwd   dx = dy d/dx (tanh(x) sigmoid(x))
 //   k_hifi_skip_bwd   the gated skip: d(u | v) stacked as the forward reads them, and d yd through the self-gate (the padded
 //                     frequency columns f >= Fy receive nothing)
@@ -49,8 +53,13 @@ struct LstmBwdArgs {
     float *dg;            // dgates of step t
     float *dc;            // [R][H], the carried cell gradient; written at t = T - 1 before it is ever read
     int R, H, T, t;
+    const int *live;      // kRows: [B], utterance b's own windows of this pass; row r = b Nc + n is dead where n >= live[b]
+    int Nc;
 };
 
+__device__ __forceinline__ bool row_live(const LstmBwdArgs &a, int r) { return r % a.Nc < a.live[r / a.Nc]; }
+
+template <bool kRows>
 __global__ __launch_bounds__(kThreads) void k_hifi_lstm_bwd_step(LstmBwdArgs a) {
     __shared__ float red[4][kRowsPerWg];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -58,6 +67,15 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_bwd_step(LstmBwdArgs a) 
     const int nb = min(kRowsPerWg, a.R - r0);
     const int H4 = 4 * a.H;
     const long ldg = (long)a.T * H4;
+    if (kRows) {
+        bool any = false;   // the same for every thread of the workgroup
+        for (int b = 0; b < nb; b++) any |= row_live(a, r0 + b);
+        if ((int)threadIdx.x < nb && !row_live(a, r0 + threadIdx.x)) {
+            float *dg = a.dg + ((long)(r0 + threadIdx.x) * a.T + a.t) * H4;
+            dg[j] = 0.0f, dg[a.H + j] = 0.0f, dg[2 * a.H + j] = 0.0f, dg[3 * a.H + j] = 0.0f;
+        }
+        if (!any) return;   // all eight rows are dead: no dot products
+    }
     if (a.dgnext) {
         const float *w = a.whht + (long)j * H4;
         const float *rows[kRowsPerWg];
@@ -78,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_bwd_step(LstmBwdArgs a) 
         }
         __syncthreads();
     }
-    if ((int)threadIdx.x < nb) {
+    if ((int)threadIdx.x < nb && (!kRows || row_live(a, r0 + threadIdx.x))) {
         const int b = threadIdx.x;
         const long r = r0 + b;
         const long row = r * a.T + a.t;   // the row of step t in the [R T][.] tensors
@@ -103,8 +121,18 @@ __global__ __launch_bounds__(kThreads) void k_hifi_lstm_bwd_step(LstmBwdArgs a) 
 }
 
 // em[s] = mean over (c, t, f) of dy[s] w[c F + f]: per-thread double partial sums over a fixed stride, then a fixed tree
-__global__ __launch_bounds__(kThreads) void k_hifi_norm_esum(const float *__restrict__ dy, const float *__restrict__ w, float *__restrict__ em, int C_, int T, int F) {
+// kRows: stream s = n B + b is dead where n >= cnt[b] (clamped to 0 .. Nc, as k_hifi_scan_rows reads it): em[s] = 0, dy unread
+template <bool kRows>
+__global__ __launch_bounds__(kThreads) void k_hifi_norm_esum(const float *__restrict__ dy, const float *__restrict__ w, float *__restrict__ em,
+                                                             const int64_t *__restrict__ cnt, int B, int C_, int T, int F) {
     __shared__ double part[kThreads];
+    if (kRows) {
+        const int nn = blockIdx.x / B, b = blockIdx.x - nn * B;
+        if ((int64_t)nn >= cnt[b]) {   // the same for every thread of the workgroup
+            if (threadIdx.x == 0) em[blockIdx.x] = 0.0f;
+            return;
+        }
+    }
     const int n = C_ * T * F;
     const float *p = dy + (long)blockIdx.x * n;
     double s = 0.0;
@@ -122,14 +150,25 @@ __global__ __launch_bounds__(kThreads) void k_hifi_norm_esum(const float *__rest
 }
 
 // one thread per (stream s, feature d), the T frames in order
+template <bool kRows>
 __global__ __launch_bounds__(kThreads) void k_hifi_norm_bwd(const float *__restrict__ dy, const float *__restrict__ o, const float *__restrict__ w,
-                                                            const float *__restrict__ g, const float *__restrict__ em, double step, float *__restrict__ dout,
+                                                            const float *__restrict__ g, const float *__restrict__ em, double step,
+                                                            const int64_t *__restrict__ step0, const int64_t *__restrict__ cnt, float *__restrict__ dout,
                                                             float *__restrict__ pw, float *__restrict__ pb, int Nc, int B, int C_, int T, int F) {
     const int D = C_ * F, d = blockIdx.x * kThreads + threadIdx.x;
     if (d >= D) return;
     const int s = blockIdx.y, nn = s / B, b = s - nn * B;
     const int c = d / F, f = d - c * F;
     const long w_ = (long)b * Nc + nn;
+    if (kRows) {
+        if ((int64_t)nn >= cnt[b]) {   // a dead window: zeros to its rows of dout and to its slabs, nothing read
+            for (int t = 0; t < T; t++) dout[(w_ * T + t) * D + d] = 0.0f;
+            pw[(long)s * D + d] = 0.0f;
+            pb[(long)s * D + d] = 0.0f;
+            return;
+        }
+        step = (double)step0[b];
+    }
     const double stepn = step + (double)nn * (double)D;
     const float keep = (float)(1.0 - stepn / (stepn + (double)D));   // 1 - alpha_n
     const float sub = keep * em[s], wd = w[d], gm = g[w_];
@@ -209,16 +248,13 @@ int blocks_of(const char *what, long n, unsigned *blocks) {
     return SE_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int se_hifi_lstm_bwd(const float *dout, const float *gates, const float *cs, const float *cprev, const float *whht, float *dgates, float *dc, int B, int Nc, int T,
-                     int H, void *stream) {
-    if (!dout || !gates || !cs || !cprev || !whht || !dgates || !dc) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_bwd: null argument");
+// live = null: every row is swept (k_hifi_lstm_bwd_step<false>, which never reads a.live / a.Nc)
+int lstm_bwd_launch(const char *what, const float *dout, const float *gates, const float *cs, const float *cprev, const float *whht, float *dgates, float *dc,
+                    const int *live, int B, int Nc, int T, int H, void *stream) {
+    if (!dout || !gates || !cs || !cprev || !whht || !dgates || !dc) return se::train_fail(SE_ERR_ARG, "%s: null argument", what);
     const long R = (long)B * Nc;
     if (B <= 0 || Nc <= 0 || T <= 0 || H < 8 || H % 8 || H > 1024 || (R + kRowsPerWg - 1) / kRowsPerWg > 65535)
-        return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_bwd: %d utterances x %d windows of %d steps, hidden %d (a multiple of 8, up to 1024; up to %d rows)", B, Nc,
+        return se::train_fail(SE_ERR_ARG, "%s: %d utterances x %d windows of %d steps, hidden %d (a multiple of 8, up to 1024; up to %d rows)", what, B, Nc,
                               T, H, 65535 * kRowsPerWg);
     const dim3 grid(H, (unsigned)((R + kRowsPerWg - 1) / kRowsPerWg));
     for (int t = T - 1; t >= 0; t--) {
@@ -226,21 +262,58 @@ int se_hifi_lstm_bwd(const float *dout, const float *gates, const float *cs, con
         a.dout = dout, a.gates = gates, a.cs = cs, a.cprev = cprev, a.whht = whht, a.dg = dgates, a.dc = dc;
         a.dgnext = t == T - 1 ? nullptr : dgates + (long)(t + 1) * 4 * H;
         a.R = (int)R, a.H = H, a.T = T, a.t = t;
-        hipLaunchKernelGGL(k_hifi_lstm_bwd_step, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+        a.live = live, a.Nc = Nc;
+        if (live)
+            hipLaunchKernelGGL(k_hifi_lstm_bwd_step<true>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+        else
+            hipLaunchKernelGGL(k_hifi_lstm_bwd_step<false>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     }
-    return launched("se_hifi_lstm_bwd");
+    return launched(what);
+}
+
+// step0 / cnt = null: one step for all and every window live (the <false> kernels, which never read the tables)
+int seqnorm_bwd_launch(const char *what, const float *dy, const float *o, const float *w, const float *wm, double step, const int64_t *step0, const int64_t *cnt,
+                       float *em, float *dout, float *pw, float *pb, int Nc, int B, int C_, int T, int F, void *stream) {
+    if (!dy || !o || !w || !wm || !em || !dout || !pw || !pb) return se::train_fail(SE_ERR_ARG, "%s: null argument", what);
+    if (Nc <= 0 || B <= 0 || (long)Nc * B > 65535 || C_ <= 0 || T <= 0 || F <= 0 || (long)T * C_ * F > (1L << 30) || step < 0.0)
+        return se::train_fail(SE_ERR_ARG, "%s: bad geometry (%d windows x %d utterances <= 65535, C %d, T %d, F %d, step %g)", what, Nc, B, C_, T, F, step);
+    const int D = C_ * F;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((D + kThreads - 1) / kThreads, Nc * B);
+    if (cnt) {
+        hipLaunchKernelGGL(k_hifi_norm_esum<true>, dim3(Nc * B), dim3(kThreads), 0, st, dy, w, em, cnt, B, C_, T, F);
+        hipLaunchKernelGGL(k_hifi_norm_bwd<true>, grid, dim3(kThreads), 0, st, dy, o, w, wm, em, step, step0, cnt, dout, pw, pb, Nc, B, C_, T, F);
+    } else {
+        hipLaunchKernelGGL(k_hifi_norm_esum<false>, dim3(Nc * B), dim3(kThreads), 0, st, dy, w, em, cnt, B, C_, T, F);
+        hipLaunchKernelGGL(k_hifi_norm_bwd<false>, grid, dim3(kThreads), 0, st, dy, o, w, wm, em, step, step0, cnt, dout, pw, pb, Nc, B, C_, T, F);
+    }
+    return launched(what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int se_hifi_lstm_bwd(const float *dout, const float *gates, const float *cs, const float *cprev, const float *whht, float *dgates, float *dc, int B, int Nc, int T,
+                     int H, void *stream) {
+    return lstm_bwd_launch("se_hifi_lstm_bwd", dout, gates, cs, cprev, whht, dgates, dc, nullptr, B, Nc, T, H, stream);
+}
+
+int se_hifi_lstm_bwd_rows(const float *dout, const float *gates, const float *cs, const float *cprev, const float *whht, float *dgates, float *dc, const int *live,
+                          int B, int Nc, int T, int H, void *stream) {
+    if (!live) return se::train_fail(SE_ERR_ARG, "se_hifi_lstm_bwd_rows: null argument");
+    return lstm_bwd_launch("se_hifi_lstm_bwd_rows", dout, gates, cs, cprev, whht, dgates, dc, live, B, Nc, T, H, stream);
 }
 
 int se_hifi_seqnorm_bwd(const float *dy, const float *o, const float *w, const float *wm, double step, float *em, float *dout, float *pw, float *pb, int Nc, int B,
                         int C_, int T, int F, void *stream) {
-    if (!dy || !o || !w || !wm || !em || !dout || !pw || !pb) return se::train_fail(SE_ERR_ARG, "se_hifi_seqnorm_bwd: null argument");
-    if (Nc <= 0 || B <= 0 || (long)Nc * B > 65535 || C_ <= 0 || T <= 0 || F <= 0 || (long)T * C_ * F > (1L << 30) || step < 0.0)
-        return se::train_fail(SE_ERR_ARG, "se_hifi_seqnorm_bwd: bad geometry (%d windows x %d utterances <= 65535, C %d, T %d, F %d, step %g)", Nc, B, C_, T, F, step);
-    const int D = C_ * F;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_hifi_norm_esum, dim3(Nc * B), dim3(kThreads), 0, st, dy, w, em, C_, T, F);
-    hipLaunchKernelGGL(k_hifi_norm_bwd, dim3((D + kThreads - 1) / kThreads, Nc * B), dim3(kThreads), 0, st, dy, o, w, wm, em, step, dout, pw, pb, Nc, B, C_, T, F);
-    return launched("se_hifi_seqnorm_bwd");
+    return seqnorm_bwd_launch("se_hifi_seqnorm_bwd", dy, o, w, wm, step, nullptr, nullptr, em, dout, pw, pb, Nc, B, C_, T, F, stream);
+}
+
+int se_hifi_seqnorm_bwd_rows(const float *dy, const float *o, const float *w, const float *wm, const int64_t *step, const int64_t *cnt, float *em, float *dout,
+                             float *pw, float *pb, int Nc, int B, int C_, int T, int F, void *stream) {
+    if (!step || !cnt) return se::train_fail(SE_ERR_ARG, "se_hifi_seqnorm_bwd_rows: null argument");
+    return seqnorm_bwd_launch("se_hifi_seqnorm_bwd_rows", dy, o, w, wm, 0.0, step, cnt, em, dout, pw, pb, Nc, B, C_, T, F, stream);
 }
 
 int se_hifi_gate_bwd(const float *dy, const float *x, float *dx, int64_t n, void *stream) {

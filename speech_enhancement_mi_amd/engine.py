@@ -32,7 +32,8 @@ EXPORTS = [
     "se_distill_fwd", "se_distill_bwd", "se_sig_stft_rows", "se_train_ola_fwd_rows", "se_train_ola_bwd_rows", "se_train_slab_gather", "se_gbf_psd_fwd", "se_gbf_seq_fwd", "se_gbf_bf_fwd", "se_gbf_psd_bwd", "se_gbf_seq_bwd", "se_gbf_bf_bwd", "se_gtsa_limits", "se_gtsa_feat", "se_gtsa_attn", "se_gtsa_tape", "se_gtsa_addnorm", "se_gtsa_qkv5", "se_gtsa_tail5",
     "se_gtsa_gather3", "se_gtsa_out", "se_gtsa_tape_rows", "se_gtsa_lastframes_rows", "se_hifi_postnet", "se_hifi_gate", "se_hifi_skip", "se_hifi_rows",
     "se_hifi_lstm", "se_hifi_seqnorm", "se_hifi_lstm_rows", "se_hifi_seqnorm_rows", "se_hifi_lstm_train_fwd", "se_hifi_lstm_bwd", "se_hifi_seqnorm_bwd",
-    "se_hifi_gate_bwd", "se_hifi_skip_bwd", "se_hifi_rows_bwd", "se_hifi_chansum", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
+    "se_hifi_gate_bwd", "se_hifi_skip_bwd", "se_hifi_rows_bwd", "se_hifi_chansum", "se_hifi_lstm_train_fwd_rows",
+    "se_hifi_lstm_bwd_rows", "se_hifi_seqnorm_bwd_rows", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
 ]
 
 
@@ -207,6 +208,9 @@ def load_library():
     L.se_hifi_skip_bwd.argtypes = [vp] * 5 + [i32] * 5 + [vp]
     L.se_hifi_rows_bwd.argtypes = [vp] * 2 + [i32] * 5 + [vp]
     L.se_hifi_chansum.argtypes = [vp, vp, C.c_int64, i32, vp]
+    L.se_hifi_lstm_train_fwd_rows.argtypes = [vp] * 10 + [i32] * 3 + [vp]
+    L.se_hifi_lstm_bwd_rows.argtypes = [vp] * 8 + [i32] * 4 + [vp]
+    L.se_hifi_seqnorm_bwd_rows.argtypes = [vp] * 10 + [i32] * 5 + [vp]
     L.se_synth_last_error.restype = C.c_char_p
     L.se_synth_rir.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [C.c_float, C.c_float, i32, vp, vp]
     L.se_synth_rir_tail.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_uint32, vp]

@@ -8,10 +8,11 @@ Same constructors, state_dict keys and shapes (`*.weight_g` / `*.weight_v`, the 
     Generator.realtime_process(mixture[B, M, L], post=True, reset=False) -> (pred, pred_before) [B, L]
     Generator.realtime_process_chains(mixture[B, M, Lmax], resets, lengths=None, post=True) -> (pred, pred_before) [B, Lmax]
     Generator.reset(), reset_norm(streams=None), use_hip_kernels(flag), kernel_geometry_error(), max_segments, _last_path, _last_passes, taps
-    Generator.use_hip_training(flag), hip_training_error()
+    Generator.use_hip_training(flag, chains=False), hip_training_error()
     Hifi_GAN.forward(x, post=True) = generator.realtime_process(x, reset=False, post=post)[0]
     Hifi_GAN.train_stage(x, y, stage=1, y_hat=None, y_before=None, reset=True) -> loss (stages 1 and 2)
     Hifi_GAN.realtime_process_chains(x, resets, lengths=None, post=True) = the generator's, its first result
+    Hifi_GAN.train_stage_chains(x, y, resets, lengths, stage=2, y_hat=None, y_before=None) -> loss, the mean over the streams
 
 Quirks of the reference that are kept:
   * `reset=True` prepends half a window of zeros, resets and strips the half window (the `flag=False` of the other models);
@@ -45,8 +46,11 @@ Three paths (the choice, the refusals and the carried state are streaming.Stream
     everything else on csrc/se_hifi.hip.  An unsupported geometry raises ValueError naming the limit; there is no fallback.
   * HIP training (opt-in, `use_hip_training(True)`; `hip_training_error()` names what it does not cover): `realtime_process` of a GPU
     tensor with grad enabled is ONE autograd node, hifigan_training.HifiFunction - the kernel path's forward as it stands (bit-equal
-    outputs and carried state, `_last_path` "kernel") and a backward on the same kernels plus csrc/se_hifi_train.hip.  Uniform calls only.
-`Hifi_GAN.train_stage(x, y, stage)` is the reference's training loss on losses.stft_loss for stages 1 and 2 (no discriminators: 3 raises).
+    outputs and carried state, `_last_path` "kernel") and a backward on the same kernels plus csrc/se_hifi_train.hip.  Uniform calls
+    only, unless `use_hip_training(True, chains=True)`: then realtime_process_chains, and a uniform call on per-stream norm step
+    counts, are one node as well - its forward the inference chains path, its backward the sum over the streams of each one alone.
+`Hifi_GAN.train_stage(x, y, stage)` is the reference's training loss on losses.stft_loss for stages 1 and 2 (no discriminators: 3 raises);
+`train_stage_chains(x, y, resets, lengths, stage)` is the mean over the streams of that loss on every stream's own samples.
 Carried state: the encoder levels' last input window, the LSTM's (h, c) per layer - `_tstate` / `_kstate` - and the norm's
 (mean [B], step) in `_nstate`, which both paths share because nothing but reset_norm() ends it.
 """
@@ -161,6 +165,7 @@ class Generator(StreamingMixin, nn.Module):
         self._nstate = None
         self._last_passes = None   # kernel path: the passes of the last call, [(first window, windows, streams), ...]
         self._hip_train = False
+        self._hip_train_chains = False
         L = len(num_channels)
         convs, deconvs = [], []
         for i in range(L):
@@ -223,16 +228,20 @@ class Generator(StreamingMixin, nn.Module):
         return getattr(self, f"_{self._admit(mixture, plan)}_call")(mixture, plan)
 
     # ---- HIP training (hifigan_training.HifiFunction) ------------------------------------------------------------------------------
-    def use_hip_training(self, flag=True):
+    def use_hip_training(self, flag=True, chains=False):
         """True: realtime_process of a GPU tensor with grad enabled runs forward AND backward on the kernels, as ONE autograd node
         (hifigan_training.HifiFunction) that returns (pred, pred_before), sharing the carried state with the inference kernel path.
         False (default): grad-enabled calls take the restatement.  Raises ValueError at once for a geometry or a dropout setting the
-        training kernels do not cover."""
+        training kernels do not cover.  chains=False (default): uniform calls on one carried norm step count only, anything else is
+        refused; chains=True: realtime_process_chains (per-stream resets and lengths) and a uniform call that finds per-stream norm
+        step counts are one HifiFunction node too - forward = the inference chains path, backward = the sum over the streams of what
+        each, run alone, would give every parameter."""
         if flag:
             err = self.hip_training_error()
             if err:
                 raise ValueError(f"Generator HIP training: {err}")
         self._hip_train = bool(flag)
+        self._hip_train_chains = bool(flag) and bool(chains)
         return self
 
     def hip_training_error(self):
@@ -255,7 +264,7 @@ class Generator(StreamingMixin, nn.Module):
         if err:
             raise ValueError(f"Generator HIP training: {err}")
         ns = self._norm_for(mixture.shape[0])
-        if not plan.uniform or (ns is not None and isinstance(ns["step"], list)):
+        if not self._hip_train_chains and (not plan.uniform or (ns is not None and isinstance(ns["step"], list))):
             raise ValueError("Generator HIP training runs uniform calls only (one reset, full lengths, one carried norm step count): "
                              "per-stream resets, lengths or step counts train on the restatement, use_hip_training(False)")
         K._need_gpu(mixture, self.gru.norm.weight)
@@ -473,9 +482,10 @@ class Generator(StreamingMixin, nn.Module):
         the norm's scan over its own windows of the pass only, and its encoder buffers stop at its own last window.  start: the
         norm's step count per caller row as the call found it.  A stream that has a window at n0 has run exactly n0 windows of this
         call, so it enters the pass at start[row] + n0 * D: one count for all takes the scalar kernel, else se_hifi_seqnorm_rows.
-        sv (a dict; uniform calls only): the pass re-run for hifigan_training's backward - the LSTM also stores its gates and cells
-        (se_hifi_lstm_train_fwd, the same arithmetic), sv receives every activation the backward reads, and the pass stops after the
-        decoder: no mask, no postnet, nothing written to ysegs."""
+        sv (a dict): the pass re-run for hifigan_training's backward - the LSTM also stores its gates and cells (se_hifi_lstm_train_fwd,
+        chains: se_hifi_lstm_train_fwd_rows; the same arithmetic), sv receives every activation the backward reads and, where the norm
+        took its `_rows` form, the per-stream step table and live counts, and the pass stops after the decoder: no mask, no postnet,
+        nothing written to ysegs."""
         lib, st, dev = K._lib(), K._st, mixture.device
         c = self._cfg
         B, M, T, F0, ch, Fq, H, NL, Lv = plan.B, mixture.shape[1], plan.T, plan.F0, plan.ch, plan.Fq, c["hidden"], c["num_layers"], len(self.convlist)
@@ -517,7 +527,10 @@ class Generator(StreamingMixin, nn.Module):
             args = (_p(gi), _p(state["h"][l]), _p(state["c"][l]), _p(getattr(m, f"weight_hh_l{l}")), _p(out), _p(hT), _p(cT))
             if keep:
                 gates, cs = _new(B * TT, 4 * H, dev=dev), _new(B * TT, H, dev=dev)
-                _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_train_fwd, *args, _p(gates), _p(cs), B, TT, H, st())
+                if steps is None:
+                    _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_train_fwd, *args, _p(gates), _p(cs), B, TT, H, st())
+                else:
+                    _run("k_hifi_lstm_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_train_fwd_rows, *args, _p(gates), _p(cs), _ip(steps), B, TT, H, st())
                 xs.append(x_l)
                 lstm.append(dict(gates=gates, cs=cs, out=out, h0=state["h"][l], c0=state["c"][l]))
             elif steps is None:
@@ -534,6 +547,7 @@ class Generator(StreamingMixin, nn.Module):
         mean_out, wm = _new(B, dev=dev), _new(B * Nc, dev=dev)
         h = _new(S, Cl, T, Fl, dev=dev)
         nm = self.gru.norm
+        step_dev = cnt = None
         if plan.uniform and len(set(step)) == 1:
             _run("k_hifi_seqnorm", 0.0, lib.se_hifi_seqnorm, _p(o), _p(nm.weight), _p(nm.bias), _p(mean_in), float(step[0]), _p(wm), _p(mean_out), _p(h),
                  Nc, B, Cl, T, Fl, st())
@@ -543,7 +557,9 @@ class Generator(StreamingMixin, nn.Module):
                  _p(mean_out), _p(h), Nc, B, Cl, T, Fl, st())
         state["mean"] = mean_out
         if keep:
-            sv.update(spec=spec, xin=xin, ypre=ypre, xs=xs, lstm=lstm, o=o, wm=wm, step=float(step[0]), dec=dec)
+            # rows: the pass took the `_rows` norm (per-stream step table and live counts, device int64 [B]); else one step for all
+            sv.update(spec=spec, xin=xin, ypre=ypre, xs=xs, lstm=lstm, o=o, wm=wm, step=float(step[0]), dec=dec, rows=step_dev is not None,
+                      step_rows=step_dev, cnt=cnt)
         del o
         # decoder
         Ci, Fi = Cl, Fl
@@ -592,8 +608,9 @@ class Generator(StreamingMixin, nn.Module):
     def _kernel_process(self, mixture, plan, record=None):
         """One call on the kernels, uniform or chains: StreamingMixin._prefix_passes' schedule over `_kernel_pass`, the running mean as
         the entry of the working state that no reset clears.  The norm's step counts never travel with it: they follow from the plan.
-        record (a list; HifiFunction): receives, per pass, (the pass's plan, sig, the state it entered with, n0, Nc, start) - the
-        state's tensors are replaced, never written, so holding them keeps the entry state."""
+        record (a list; HifiFunction): receives, per pass, (the pass's plan, sig, the state it entered with, n0, Nc, start, the pass's
+        mixture rows - the sorted prefix mix[:Bp], a view) - the state's tensors are replaced, never written, so holding them keeps
+        the entry state."""
         dev, B = mixture.device, mixture.shape[0]
         c = self._cfg
         H, NL, Lv, T, ch, Fq = c["hidden"], c["num_layers"], len(self.convlist), plan.T, plan.ch, plan.Fq
@@ -608,7 +625,7 @@ class Generator(StreamingMixin, nn.Module):
         carried = None if old is None else dict(buf=old["buf"], h=old["h"], c=old["c"], mean=mean)
         def run_pass(mix, sub, sig, state, n0, Nc, ysegs):
             if record is not None:
-                record.append((sub, sig, {k: list(v) if isinstance(v, list) else v for k, v in state.items()}, n0, Nc, start))
+                record.append((sub, sig, {k: list(v) if isinstance(v, list) else v for k, v in state.items()}, n0, Nc, start, mix))
             self._kernel_pass(mix, sub, sig, state, n0, Nc, ysegs, start)
         preds, new, passes = self._prefix_passes(mixture, plan, carried, fresh, 2, run_pass, unflagged=("mean",))
         self._kstate = dict(B=B, buf=new["buf"], h=new["h"], c=new["c"])
@@ -652,3 +669,27 @@ class Hifi_GAN(nn.Module):
         if stage == 1:
             return stft_loss(y_hat, y, phase=True)
         return 0.5 * stft_loss(y_hat, y, phase=True) + 0.5 * stft_loss(y_before, y, phase=True)
+
+    def train_stage_chains(self, x, y, resets, lengths, stage=2, y_hat=None, y_before=None):
+        """train_stage for a batch of chunk chains (this project's addition): x [B, M, Lmax], y [B, Lmax], stream b being its first
+        lengths[b] samples, resets[b] as realtime_process_chains takes them.  -> the MEAN OVER THE STREAMS of the reference's loss
+        of every stream alone: stft_loss(y_hat[b:b+1, :lengths[b]], y[b:b+1, :lengths[b]], phase=True), stage 2 the 0.5 / 0.5 pair with
+        y_before.  That is the "every caller alone" rule applied to the loss, and deliberately NOT the reference's whole-batch form:
+        stft_loss divides Frobenius norms taken over the whole batch, which would weigh a stream by its neighbours' energy and read
+        the padding.  (y_hat, y_before) = generator.realtime_process_chains(x, resets, lengths) unless y_hat is given.  Stage 1
+        without y_hat raises TypeError and stage 3 NotImplementedError, as train_stage does.  Plain torch on losses.stft_loss."""
+        from .call_plan import as_lengths
+        from .losses import stft_loss
+        if stage not in (1, 2):
+            raise NotImplementedError(f"train_stage_chains(stage={stage}): the adversarial stage needs the discriminators, which are not built "
+                                      "here (stages 1 and 2 train the generator on stft_loss)")
+        if y_hat is None:
+            y_hat, y_before = self.generator.realtime_process_chains(x, resets, lengths, post=stage != 1)
+        lens = as_lengths(lengths, y.shape[0], y.shape[-1])
+        total = 0.0
+        for b, L in enumerate(lens):
+            one = stft_loss(y_hat[b:b + 1, :L], y[b:b + 1, :L], phase=True)
+            if stage == 2:
+                one = 0.5 * one + 0.5 * stft_loss(y_before[b:b + 1, :L], y[b:b + 1, :L], phase=True)
+            total = total + one
+        return total / len(lens)

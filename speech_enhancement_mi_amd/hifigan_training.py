@@ -15,14 +15,24 @@ twelve pre-activations (the memory rule: 12 x Nc B x 128 x T x F floats, one pas
   dW_ih, dW_hh, dx) -> se_hifi_rows_bwd -> encoder.
 The kernels give the gradient of the FOLDED weights; per-pass gradients are summed in pass order, and (weight_g, weight_v) receive
 theirs on the host through the differentiable fold `hifigan._w`.  No float atomics anywhere: two runs give bit-equal gradients.
-`deconvlist[-1].residual*` are unused by the forward and get None, the mixture gets None."""
+`deconvlist[-1].residual*` are unused by the forward and get None, the mixture gets None.
+
+Chunk chains (`use_hip_training(True, chains=True)`): the forward is `_kernel_process` on the chains plan - the sorted-prefix schedule of
+the inference path, bit for bit - and records each pass's mixture rows as well.  The backward permutes both cotangents into the
+scheduler's sorted order, takes their synthesis adjoint on the sorted plan (nothing beyond a stream's length is read, and the windows
+past a stream's own are exact zeros), and differentiates pass by pass on the pass's Bp leading streams.  DEAD WINDOWS - windows of a
+pass past a stream's own last one - are run, as the inference path runs them, and carry a ZERO cotangent through the convolution
+stack: every activation there is finite, so they add exact zeros to the fixed-order sums.  The kernels whose result depends on a
+stream's own schedule take their `_rows` form: se_hifi_lstm_train_fwd_rows (zeros as a finished step's gates and cell),
+se_hifi_seqnorm_bwd_rows (per-stream step, zeros at dead windows), se_hifi_lstm_bwd_rows (dead rows not swept, zero dgates).  A
+uniform call on one step count runs exactly the launches it ran before."""
 from __future__ import annotations
 
 import torch
 
 from . import train_ops as K
 from .hifigan import POST_LAYERS, _w
-from .train_stages import (_new, _p, _run, colsum3, colsum_tall, conv_w, gemm_tn, grads_in_parameter_order, synthesis_adjoint, transpose, wgrad)
+from .train_stages import (_ip, _new, _p, _rows, _run, colsum3, colsum_tall, conv_w, gemm_tn, grads_in_parameter_order, synthesis_adjoint, transpose, wgrad)
 
 
 def _gate(x):
@@ -77,8 +87,10 @@ def _postnet_bwd(model, hdec, spec, dY, grads, zero_bias, S, M, T, F0, n_fft):
 
 def _pass_backward(model, mixture, rec, dY, dYb, grads):
     """One pass of the call: re-run with the activations kept, then every gradient of the pass into `grads` (names of the folded
-    weights end in `.weight`).  dY / dYb [Nc B][T][F0][2]: the cotangents of the pass's masked spectra, after / before the postnet."""
-    plan, sig, entry, n0, Nc, start = rec
+    weights end in `.weight`).  dY / dYb [Nc B][T][F0][2]: the cotangents of the pass's masked spectra, after / before the postnet.
+    mixture: the pass's rows.  Where the re-run took the norm's `_rows` form (a chains plan, or entry step counts that differ), the
+    norm and the LSTM backward take theirs; a uniform pass takes the scalar kernels, as it always has."""
+    plan, sig, entry, n0, Nc, start = rec[:6]
     lib, st, dev = K._lib(), K._st, mixture.device
     c = model._cfg
     B, M, T, F0, ch, Fq, H, NL, Lv = plan.B, mixture.shape[1], plan.T, plan.F0, plan.ch, plan.Fq, c["hidden"], c["num_layers"], len(model.convlist)
@@ -126,8 +138,14 @@ def _pass_backward(model, mixture, rec, dY, dYb, grads):
     nm, fc, m = model.gru.norm, model.gru.fc_output_layer, model.gru.sequence_model
     do, em = _new(B * TT, D, dev=dev), _new(S, dev=dev)
     pw, pb = _new(S, D, dev=dev), _new(S, D, dev=dev)
-    _run("k_hifi_seqnorm_bwd", 0.0, lib.se_hifi_seqnorm_bwd, _p(dout), _p(sv["o"]), _p(nm.weight), _p(sv["wm"]), sv["step"], _p(em), _p(do), _p(pw), _p(pb),
-         Nc, B, Cl, T, Fl, st())
+    rows = sv["rows"]
+    if rows:   # dead windows: zeros to their rows of `do` and to their slabs, dout unread there
+        _run("k_hifi_seqnorm_bwd", 0.0, lib.se_hifi_seqnorm_bwd_rows, _p(dout), _p(sv["o"]), _p(nm.weight), _p(sv["wm"]), _ip(sv["step_rows"]), _ip(sv["cnt"]),
+             _p(em), _p(do), _p(pw), _p(pb), Nc, B, Cl, T, Fl, st())
+        live = torch.tensor(plan.live(n0, Nc), dtype=torch.int32).to(dev, non_blocking=True)
+    else:
+        _run("k_hifi_seqnorm_bwd", 0.0, lib.se_hifi_seqnorm_bwd, _p(dout), _p(sv["o"]), _p(nm.weight), _p(sv["wm"]), sv["step"], _p(em), _p(do), _p(pw), _p(pb),
+             Nc, B, Cl, T, Fl, st())
     grads["gru.norm.weight"], grads["gru.norm.bias"] = colsum3(S, (pw, D), (pb, D))
     del dout, pw, pb
     wfc = model._folded("fc", fc)
@@ -142,8 +160,12 @@ def _pass_backward(model, mixture, rec, dY, dYb, grads):
         hp, cp = _new(B * TT, H, dev=dev), _new(B * TT, H, dev=dev)   # h_{t-1}, c_{t-1} of every row: shifted by one step, the pass's entry state in front
         _run("k_gru_hprev", 0.0, lib.se_train_gru_hprev, _p(r["out"]), _p(r["h0"]), _p(hp), B, TT, H, TT, 0, TT, st())
         _run("k_gru_hprev", 0.0, lib.se_train_gru_hprev, _p(r["cs"]), _p(r["c0"]), _p(cp), B, TT, H, TT, 0, TT, st())
-        _run("k_hifi_lstm_bwd_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_bwd, _p(dlayer), _p(r["gates"]), _p(r["cs"]), _p(cp), _p(whht), _p(dg), _p(dc),
-             B, Nc, T, H, st())
+        if rows:   # only a stream's own windows are swept; the dgates of the others are exact zeros
+            _run("k_hifi_lstm_bwd_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_bwd_rows, _p(dlayer), _p(r["gates"]), _p(r["cs"]), _p(cp), _p(whht), _p(dg),
+                 _p(dc), _ip(live), B, Nc, T, H, st())
+        else:
+            _run("k_hifi_lstm_bwd_step", 2.0 * B * 4 * H * H * TT, lib.se_hifi_lstm_bwd, _p(dlayer), _p(r["gates"]), _p(r["cs"]), _p(cp), _p(whht), _p(dg), _p(dc),
+                 B, Nc, T, H, st())
         pre = "gru.sequence_model."
         grads[pre + f"weight_ih_l{l}"] = gemm_tn(dg, sv["xs"][l])
         grads[pre + f"weight_hh_l{l}"] = gemm_tn(dg, hp)
@@ -183,7 +205,8 @@ def _normed_modules(model):
 
 class HifiFunction(torch.autograd.Function):
     """(pred, pred_before) = Generator.realtime_process(mixture, post=True, reset) on the kernels, forward AND backward, as one autograd
-    node.  forward(ctx, model, mixture, plan, *params), params in named_parameters() order; plan: the call's (uniform) CallPlan."""
+    node.  forward(ctx, model, mixture, plan, *params), params in named_parameters() order; plan: the call's CallPlan, uniform or
+    (use_hip_training(True, chains=True)) chains."""
 
     @staticmethod
     def forward(ctx, model, mixture, plan, *params):
@@ -197,19 +220,27 @@ class HifiFunction(torch.autograd.Function):
     def backward(ctx, dpred, dbefore):
         model, mix, plan, record = ctx.model, ctx.mix, ctx.plan, ctx.record
         B = plan.B
-        sig = record[0][1]
+        # the first pass runs every stream, so its plan is the call's as the passes see it: the caller's when uniform, else the
+        # scheduler's sorted one, whose `rows` are the caller's rows in sorted order
+        sp, sig = record[0][0], record[0][1]
+        order = None if plan.uniform else _rows(sp.rows, mix.device)
         zeros = None
         cots = []
         for d in (dpred, dbefore):
             if d is None:
                 d = zeros = torch.zeros(B, plan.L, device=mix.device) if zeros is None else zeros
-            cots.append(synthesis_adjoint(plan, sig, d.contiguous().float()))
+            d = d.contiguous().float()
+            cots.append(synthesis_adjoint(sp, sig, d if order is None else d.index_select(0, order)))   # [N B][T][F0][2], window-major
         total = {}
         with torch.no_grad():
             for rec in record:   # in pass order: the sums below have one fixed order
-                n0, Nc = rec[3], rec[4]
+                n0, Nc, Bp = rec[3], rec[4], rec[0].B
                 grads = {}
-                _pass_backward(model, mix, rec, cots[0][n0 * B:(n0 + Nc) * B], cots[1][n0 * B:(n0 + Nc) * B], grads)
+                if Bp == B:
+                    dY, dYb = (c[n0 * B:(n0 + Nc) * B] for c in cots)
+                else:   # a prefix pass: its Bp leading streams of every window
+                    dY, dYb = (c.view(sp.N, B, *c.shape[1:])[n0:n0 + Nc, :Bp].reshape(Nc * Bp, *c.shape[1:]) for c in cots)
+                _pass_backward(model, rec[6], rec, dY, dYb, grads)
                 for k, g in grads.items():
                     total[k] = g if k not in total else total[k] + g
         out = {}
