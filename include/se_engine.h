@@ -171,7 +171,7 @@ int se_abi_version(void);  /* 5: the first-generation training entry points are 
                               4 since round 3 (fsn_config.precision, se_sig_*, fused training stages, se_realtime_process_ragged, se_read_tap_dev, se_loss_stoi_*);
                               additions at 4: fsn_train_ws_bytes, fsn_train_fwd, fsn_train_bwd; se_train_add_csum, se_distill_*, se_gbf_* (forward and backward);
                               additions at 5: se_realtime_process_chains; fsn_realtime_process_chains, fsn_reset_stream, fsn_export_state,
-                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference); se_hifi_* (HiFi-GAN generator inference, and its training: se_hifi_lstm_train_fwd, se_hifi_*_bwd, se_hifi_chansum) */
+                              fsn_import_state; se_chunk_geometry; fsn_train_ws_bytes_chains, fsn_train_fwd_chains, fsn_train_bwd_chains; se_gtsa_* (GTSA inference); se_hifi_* (HiFi-GAN generator inference, and its training: se_hifi_lstm_train_fwd, se_hifi_*_bwd, se_hifi_chansum); se_loss_pesq_* (the perceptual term of GTSA.compute_loss) */
 /* sizeof(se_config) / sizeof(fsn_config) as this library was built: a binding checks its own struct mirror against these
  * before the first se_create (a short struct would leave `precision` reading whatever follows it). */
 int se_config_size(void);
@@ -288,6 +288,20 @@ int se_loss_stoi_fwd(const float *clean, const float *pred, const int64_t *lens,
 int se_loss_stoi_bwd(const float *gD, const int64_t *lens, int batch, int64_t length, const float *rs_w, const int *rs_first, int W, const float *hann_sym,
                      const float *hann_per, const int *band_lo, const int *band_hi, float *ws, float *dpred, void *stream);
 const char *se_loss_stoi_last_error(void);
+/* Perceptual term of GTSA.compute_loss (utility.pesq_loss, utility.py:615-814; GTSA.py:411-433) as kernels, forward and backward w.r.t.
+ * the prediction.  Row b is scored on its first lens[b] samples alone (reflect padding at its own end); a row of fewer than 20
+ * spectrogram frames (lens[b] < 4864) gets a NaN value and a zero gradient.  Tables (device memory, built by the caller once:
+ * losses._pesq_plan): win [512] = periodic Hann of Spectrogram(1024, 512, 256) (utility.py:727), edges [50] = Bark band bin edges
+ * (bark2hz, utility.py:639-648), band_of [513] = bin -> band or -1, band_tab [5][49] = power density correction * Sp, absolute threshold
+ * * 1e4, Zwicker exponent, (2 * threshold) ** exponent, band width in Bark (utility.py:653-710, 745, 772).  ws = se_loss_pesq_ws_floats
+ * floats of scratch that carry the forward's intermediates to the backward.  value [batch] = -(4.5 - 0.1 sres - 0.0309 asres)
+ * (utility.py:813-814); gvalue = d loss / d value; dpred [batch][length].  length >= 4864 and at most 896 frames (14.3 s). */
+int64_t se_loss_pesq_ws_floats(int batch, int64_t length);
+int se_loss_pesq_fwd(const float *clean, const float *pred, const int64_t *lens, int batch, int64_t length, const float *win, const int *edges,
+                     const float *band_tab, float *ws, float *value, void *stream);
+int se_loss_pesq_bwd(const float *gvalue, const int64_t *lens, int batch, int64_t length, const float *win, const int *band_of, const float *band_tab, float *ws,
+                     float *dpred, void *stream);
+const char *se_loss_pesq_last_error(void);
 int se_loss_sisnr_bwd(const float *separated, const float *source, const int64_t *lens, int batch, int64_t length, const double *stats,
                       const float *gscale, float *grad, void *stream);
 

@@ -25,6 +25,7 @@ EXPORTS = [
     "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
     "fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state",
     "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "fsn_train_ws_bytes_chains", "fsn_train_fwd_chains", "fsn_train_bwd_chains", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
+    "se_loss_pesq_ws_floats", "se_loss_pesq_fwd", "se_loss_pesq_bwd", "se_loss_pesq_last_error",
     "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd", "se_train_gru_pseq_fwd_rows", "se_train_gru_pseq_bwd_rows",
     "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
     "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
@@ -128,6 +129,11 @@ def load_library():
     L.se_loss_stoi_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.se_loss_stoi_bwd.argtypes = [vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.se_loss_stoi_last_error.restype = C.c_char_p
+    L.se_loss_pesq_ws_floats.argtypes = [C.c_int, C.c_int64]
+    L.se_loss_pesq_ws_floats.restype = C.c_int64
+    L.se_loss_pesq_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.se_loss_pesq_bwd.argtypes = [vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.se_loss_pesq_last_error.restype = C.c_char_p
     L.se_loss_sisnr_bwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
     i32, i64 = C.c_int, C.c_int64
     L.se_train_last_error.restype = C.c_char_p

@@ -169,8 +169,11 @@ class GTSA(StreamingMixin, nn.Module):
         return super().load_state_dict(sd, strict=strict, **kw)
 
     def compute_loss(self, source, pred_source, length):
-        raise NotImplementedError("GTSA.compute_loss is 0.7 * pesq_loss + 0.3 * (-SI-SNR) (GTSA.py:411-433); pesq_loss is not restated "
-                                  "in this project yet")
+        """(loss, mae, sisnr), loss = 0.7 * pesq_loss + 0.3 * (-SI-SNR) (GTSA.py:411-433), on CPU or GPU tensors; a NaN loss turns all
+        three into zeros without a gradient.  Inputs of fewer than 20 spectrogram frames (4864 samples) raise NotImplementedError:
+        the reference's pesq_loss has no value for them (losses.pesq_loss)."""
+        from .losses import gtsa_compute_loss
+        return gtsa_compute_loss(source, pred_source, length)
 
     # ---- torch restatement ---------------------------------------------------------------------------------------------------
     @staticmethod

@@ -14,6 +14,11 @@
   5-phase strided convolution; Spectrogram(512, 256, 128, power=2) over torch.fft.  PARITY UNPINNED AT THE TORCHAUDIO
   BOUNDARY; pinned above it by tests/golden/loss_golden.npz (the reference's own stoi_loss / compute_loss code run on these
   restated transforms, values AND the gradient w.r.t. the prediction).
+* `pesq_loss` (utility.py:615-814) and `gtsa_compute_loss` = GTSA.compute_loss (GTSA.py:411-433: 0.7 * pesq_loss + 0.3 * (-SI-SNR)).  On
+  CUDA tensors the `se_loss_pesq_*` kernels (csrc/se_pesq.hip: 2 launches forward, 3 backward; `_PesqHip`); `_pesq_d` restates the
+  reference's per-utterance CPU code with its Python loop over frames as batched, differentiable torch code in float32 or float64: the
+  CPU path and the checker (PESQ_KERNELS = False).  torchaudio's Spectrogram(1024, 512, 256, power=2) is restated over torch.fft:
+  PARITY UNPINNED AT THE TORCHAUDIO BOUNDARY, pinned above it by tests/golden/pesq_golden.npz.
 """
 from __future__ import annotations
 
@@ -337,6 +342,276 @@ def compute_loss(source, pred_source, length):
     bad = torch.isnan(loss)
     zero = torch.zeros_like(loss)  # no gradient, like the reference's fill_(0.0)
     return torch.where(bad, zero, loss), torch.where(bad, zero, stoi), torch.where(bad, zero, sisnr)
+
+
+# =====================================================================================================================
+# PESQ loss (utility.py:615-814) and GTSA.compute_loss (GTSA.py:411-433)
+# =====================================================================================================================
+PESQ_MIN_SAMPLES = 4864  # 20 spectrogram frames (1 + L // 256): the shortest input the reference's 20-frame syllables have a value for
+_PESQ_NB, _PESQ_NFFT, _PESQ_HOP, _PESQ_BINS = 49, 1024, 256, 513
+_PESQ_LOW_F, _PESQ_HIGH_F = int(2 * 300 / 16000 * 513), int(2 * 3000 / 16000 * 513)  # level alignment over bins [19, 192)
+_PESQ_SP, _PESQ_SL, _PESQ_ZWICKER = 6.910853e-1, 1.866055e-1, 0.23
+# utility.py:668-710, the tables of ITU-T P.862 at 16 kHz: absolute hearing threshold, power density correction, band widths in Bark
+_PESQ_ABS_THRESH = (
+    51286152.000000, 2454709.500000, 70794.593750, 4897.788574, 1174.897705, 389.045166, 104.712860, 45.708820, 17.782795, 9.772372,
+    4.897789, 3.090296, 1.905461, 1.258925, 0.977237, 0.724436, 0.562341, 0.457088, 0.389045, 0.331131, 0.295121, 0.269153, 0.257040,
+    0.251189, 0.251189, 0.251189, 0.251189, 0.263027, 0.288403, 0.309030, 0.338844, 0.371535, 0.398107, 0.436516, 0.467735, 0.489779,
+    0.501187, 0.501187, 0.512861, 0.524807, 0.524807, 0.524807, 0.512861, 0.478630, 0.426580, 0.371535, 0.363078, 0.416869, 0.537032)
+_PESQ_POW_DENS = (
+    100.000000, 99.999992, 100.000000, 100.000008, 100.000008, 100.000015, 99.999992, 99.999969, 50.000027, 100.000000, 99.999969,
+    100.000015, 99.999947, 100.000061, 53.047077, 110.000046, 117.991989, 65.000000, 68.760147, 69.999931, 71.428818, 75.000038,
+    76.843384, 80.968781, 88.646126, 63.864388, 68.155350, 72.547775, 75.584831, 58.379192, 80.950836, 64.135651, 54.384785, 73.821884,
+    64.437073, 59.176456, 65.521278, 61.399822, 58.144047, 57.004543, 64.126297, 54.311001, 61.114979, 55.077751, 56.849335, 55.628868,
+    53.137054, 54.985844, 79.546974)
+_PESQ_ZW_H = (2.00, 2.00, 2.00, 2.00, 1.82, 1.66, 1.51, 1.39, 1.29, 1.20, 1.12, 1.05) + (1.00,) * 37
+_PESQ_WIDTH = (
+    0.157344, 0.317994, 0.322441, 0.326934, 0.331474, 0.336061, 0.340697, 0.345381, 0.350114, 0.354897, 0.359729, 0.364611, 0.369544,
+    0.374529, 0.379565, 0.384653, 0.389794, 0.394989, 0.400236, 0.405538, 0.410894, 0.416306, 0.421773, 0.427297, 0.432877, 0.438514,
+    0.444209, 0.449962, 0.455774, 0.461645, 0.467577, 0.473569, 0.479621, 0.485736, 0.491912, 0.498151, 0.504454, 0.510819, 0.517250,
+    0.523745, 0.530308, 0.536934, 0.543629, 0.550390, 0.557220, 0.564119, 0.571085, 0.578125, 0.585232)
+
+
+def _pesq_band_edges():
+    """The 50 integer bin edges of the 49 Bark bands (bark2hz, utility.py:639-648); neighbours may coincide (an empty band)."""
+    edges = []
+    for z in np.linspace(0, 21, _PESQ_NB + 1):
+        if z < 2:
+            z = (z - 0.3) / 0.85
+        elif z > 20.1:
+            z = (z + 4.422) / 1.22
+        edges.append(int(2 * (1960 * (z + 0.53) / (26.28 - z)) / 16000 * _PESQ_BINS))
+    return edges
+
+
+_PESQ_PLAN = {}
+
+
+def _pesq_plan(device):
+    """Per-device tables, built once.  All of them are the float32 numbers the reference's float32 tensors hold; a float64 run of
+    `_pesq_d` widens those, so it is the exact value of the function the float32 reference rounds."""
+    key = str(device)
+    if key not in _PESQ_PLAN:
+        f32 = np.float32
+        edges = _pesq_band_edges()
+        thr = np.asarray(_PESQ_ABS_THRESH, f32) * f32(1e4)
+        zp = (np.asarray(_PESQ_ZW_H, f32) ** f32(0.15) * f32(_PESQ_ZWICKER)).astype(f32)
+        win = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(512) / 512)).astype(f32)  # periodic Hann(512), centred in 1024 points
+        bandmat = np.zeros((_PESQ_NB, _PESQ_BINS), f32)
+        band_of = np.full(_PESQ_BINS, -1, np.int32)
+        for j in range(_PESQ_NB):
+            bandmat[j, edges[j]:edges[j + 1]] = 1
+            band_of[edges[j]:edges[j + 1]] = j
+        cfac = (np.asarray(_PESQ_POW_DENS, f32) * f32(_PESQ_SP)).astype(f32)
+        k2 = ((f32(2) * thr) ** zp).astype(f32)
+        width = np.asarray(_PESQ_WIDTH, f32)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        _PESQ_PLAN[key] = dict(edges=edges, thr=t(thr), zp=t(zp), win=t(win), bandmat=t(bandmat), cfac=t(cfac), k2=t(k2), width=t(width),
+                               # tables of the kernel form (csrc/se_pesq.hip): band edges [50], bin -> band [513], [5][49] band constants
+                               edges_dev=t(np.asarray(edges, np.int32)), band_of=t(band_of),
+                               band_tab=t(np.stack([cfac, thr, zp, k2, width]).astype(f32)))
+    return _PESQ_PLAN[key]
+
+
+def _pesq_d(y_true, y_pred, lens, margins=None):
+    """-PESQ-like score of utility.py:723-814 for every row at once: [B] values on the inputs' device, in the inputs' dtype (float32
+    or float64), differentiable w.r.t. y_pred.  Row b is the reference's value for y[b, :lens[b]] run alone: reflect padding at the
+    row's own end, nothing at or beyond lens[b] is read (NaN there is harmless).  A row with fewer than 20 frames (lens[b] < 4864)
+    yields NaN with a zero gradient.  The CPU path and the checker of the se_loss_pesq_* kernels (PESQ_KERNELS = False).
+
+    `margins`, a dict, receives per branch family the smallest relative distance of any comparison from its threshold (the fixture
+    maker's condition that float32 and float64 take the same branches)."""
+    dev, dt = y_pred.device, y_pred.dtype
+    P = _pesq_plan(dev)
+    y_true = y_true.detach().to(dt)
+    B, L = y_pred.shape
+    Tm = 1 + L // _PESQ_HOP
+    Tb = 1 + torch.div(lens, _PESQ_HOP, rounding_mode="floor")
+    bad = Tb < 20
+    Tb = torch.where(bad, torch.full_like(Tb, 20), Tb)
+    tv = (torch.arange(Tm, device=dev)[None, :] < Tb[:, None]) & ~bad[:, None]  # [B, Tm]
+    Tf = Tb.to(dt)
+    thr, zp, k2, w = (P[k].to(dt)[None, :, None] for k in ("thr", "zp", "k2", "width"))
+    cfac = P["cfac"].to(dt)[None, :, None]
+    # ---- Spectrogram(1024, 512, 256, power=2): the 512 samples under the window, gathered through the reflect rule of the row's own end
+    n = (torch.arange(Tm, device=dev) * _PESQ_HOP - 256)[:, None] + torch.arange(512, device=dev)[None, :]  # [Tm, 512]
+    m = n.abs()[None]
+    ln = lens[:, None, None]
+    m = torch.where(m >= ln, 2 * (ln - 1) - m, m).clamp(0, L - 1)  # [B, Tm, 512]
+
+    def bands(y):
+        fr = torch.gather(y, 1, m.reshape(B, -1)).reshape(B, Tm, 512)
+        fr = torch.where(tv[..., None], fr, torch.zeros_like(fr)) * P["win"].to(dt)
+        S = torch.fft.rfft(Fn.pad(fr, (256, 256)), dim=-1)
+        pw = S.real ** 2 + S.imag ** 2  # [B, Tm, 513], zero beyond the row's frames
+        level = pw[..., _PESQ_LOW_F:_PESQ_HIGH_F].sum((1, 2)) / ((_PESQ_HIGH_F - _PESQ_LOW_F) * Tf) + 1e-14
+        raw = (pw @ P["bandmat"].to(dt).T).transpose(1, 2)  # [B, 49, Tm]
+        return raw * (1e7 / level)[:, None, None] * cfac
+
+    def note(name, x, c, sel=None):
+        if margins is not None:  # x [B, 49, Tm] or [B, Tm] against the threshold c, over the rows' own frames
+            r = (x.detach() - c).abs() / c
+            ok = tv[:, None, :].expand_as(r) if r.dim() == 3 else tv
+            r = r[ok if sel is None else ok & sel]
+            if r.numel():
+                margins[name] = min(margins.get(name, float("inf")), float(r.min()))
+
+    Bt, Bp = bands(y_true), bands(y_pred)
+    tvb = tv[:, None, :]
+    mt = (Bt > thr).to(dt)
+    mp = (Bp > thr).to(dt)
+    note("band_true", Bt, thr)
+    note("band_pred", Bp, thr)
+    tt = (Bt * mt).sum(1)
+    note("silence", tt, 1e7)
+    ns = (tt > 1e7).to(dt)[:, None, :]
+    # ---- band equalisation of the clean signal by the ratio of time means
+    at = (Bt * mt * ns).sum(2, keepdim=True) / Tf[:, None, None]
+    ap = (Bp * mp * ns).sum(2, keepdim=True) / Tf[:, None, None]
+    eq = (ap + 1e3) / (at + 1e3)
+    if margins is not None:
+        for c in (0.01, 100.0):
+            margins["eq_clamp"] = min(margins.get("eq_clamp", float("inf")), float(((eq.detach() - c).abs() / c)[~bad].min()))
+    eq = torch.clamp(eq, 0.01, 100)
+    Bt = Bt * eq
+    mt = (Bt > thr).to(dt)
+    note("band_true_eq", Bt, thr)
+    tt = (Bt * mt).sum(1)
+    tp = (Bp * mp).sum(1)
+    # ---- time recurrence s_t = 0.2 s_{t-1} + (total_true_t + 5e3) / (total_pred_t + 5e3), s_{-1} = 1
+    r = (tt + 5e3) / (tp + 5e3)
+    s, ss = torch.ones(B, dtype=dt, device=dev), []
+    for t in range(Tm):
+        s = 0.2 * s + r[:, t]
+        ss.append(s)
+    s = torch.stack(ss, 1)
+    note("s_lo", s, 3e-4)
+    note("s_hi", s, 5.0)
+    Bp = Bp * torch.clamp(s, 3e-4, 5.0)[:, None, :]
+    # ---- loudness (Zwicker), disturbances
+    Lp = k2 * ((0.5 + 0.5 * Bp / thr) ** zp - 1) * mp * _PESQ_SL
+    Lt = k2 * ((0.5 + 0.5 * Bt / thr) ** zp - 1) * mt * _PESQ_SL
+    d = Lp - Lt
+    mm = torch.where(Lp < Lt, Lp, Lt) * 0.25
+    live = ((d != 0) | (mm != 0)).detach()  # both loudnesses exactly zero: 0 > 0 is false in every arithmetic
+    if margins is not None:
+        sc = torch.maximum(d.detach().abs(), mm.detach().abs()).clamp(min=1e-300)
+        for name, x in (("dead_hi", d - mm), ("dead_lo", d + mm)):
+            rr = (x.detach().abs() / sc)[live & tvb.expand_as(live)]
+            if rr.numel():
+                margins[name] = min(margins.get(name, float("inf")), float(rr.min()))
+    zero = torch.zeros_like(d)
+    dist = torch.where(d > mm, d - mm, zero) + torch.where(d < -mm, d + mm, zero)
+    wsum = w.sum()
+    sym = ((dist.abs() * w) ** 2).sum(1) / wsum
+    sym = sym ** 0.5 * wsum
+    h = ((Lp + 50) / (Lt + 50)) ** 1.2
+    moved = (dist != 0).detach()  # the asymmetry factor multiplies the disturbance: where that is zero its branch decides nothing
+    note("asym_3", h, 3.0, moved)
+    note("asym_12", h, 12.0, moved)
+    h = torch.clamp(torch.where(h < 3, torch.zeros_like(h), h), 0, 12)
+    asym = ((dist * h).abs() * w).sum(1) / wsum
+    asym = asym * wsum
+    hh = ((tt + 1e5) / 1e7) ** 0.04
+    note("cap_sym", sym / hh, 45.0)
+    note("cap_asym", asym / hh, 45.0)
+    sym = torch.clamp(sym / hh, max=45.0)
+    asym = torch.clamp(asym / hh, max=45.0)
+    # ---- syllables of 20 frames every 10 (power-6 mean) and the tail block of the last `left` frames; power-2 mean over them
+    nb = torch.div(Tb - 20, 10, rounding_mode="floor") + 1
+    left = Tb - 10 * nb
+    ti = torch.arange(Tm, device=dev)[None, :]
+    tail = (ti >= (Tb - left)[:, None]) & (ti < Tb[:, None])
+    kvalid = torch.arange((Tm - 20) // 10 + 1, device=dev)[None, :] < nb[:, None]
+
+    def aggregate(x):
+        x6 = x ** 6
+        blocks = x6.unfold(1, 20, 10).mean(-1)  # [B, NBm]
+        last = torch.where(tail, x6, torch.zeros_like(x6)).sum(1) / left.to(dt)
+        blocks = (blocks + 1e-8) ** (1.0 / 6)
+        last = (last + 1e-8) ** (1.0 / 6)
+        tot = torch.where(kvalid, blocks ** 2, torch.zeros_like(blocks)).sum(1) + last ** 2
+        return (tot / (nb + 1).to(dt) + 1e-8) ** 0.5
+
+    res = 4.5 - 0.1 * aggregate(sym) - 0.0309 * aggregate(asym)
+    return torch.where(bad, torch.full_like(res, float("nan")), -res)
+
+
+PESQ_KERNELS = True  # CUDA tensors: csrc/se_pesq.hip (2 launches forward, 3 backward); False: the batched torch restatement _pesq_d, the checker
+
+
+class _PesqHip(torch.autograd.Function):
+    """Per-row value of utility.py:723-814 on the se_loss_pesq_* kernels; gradient to the prediction only."""
+
+    @staticmethod
+    def forward(ctx, y_true, y_pred, lens):
+        from . import engine as _engine
+        lib = _engine.load_library()
+        P = _pesq_plan(y_pred.device)
+        B, L = y_pred.shape
+        yt, yp, ln = y_true.detach().contiguous().float(), y_pred.detach().contiguous().float(), lens.contiguous().to(torch.int64)
+        ws = torch.empty(int(lib.se_loss_pesq_ws_floats(B, L)), dtype=torch.float32, device=y_pred.device)
+        val = torch.empty(B, dtype=torch.float32, device=y_pred.device)
+        st = C.c_void_p(torch.cuda.current_stream(y_pred.device).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        if lib.se_loss_pesq_fwd(p(yt), p(yp), p(ln), B, L, p(P["win"]), p(P["edges_dev"]), p(P["band_tab"]), p(ws), p(val), st):
+            raise RuntimeError(lib.se_loss_pesq_last_error().decode())
+        ctx.save_for_backward(ln, ws)
+        ctx.shape = (B, L)
+        ctx.dev = y_pred.device
+        return val
+
+    @staticmethod
+    def backward(ctx, gv):
+        from . import engine as _engine
+        lib = _engine.load_library()
+        ln, ws = ctx.saved_tensors
+        B, L = ctx.shape
+        P = _pesq_plan(ctx.dev)
+        g = gv.contiguous().float()
+        dpred = torch.empty(B, L, dtype=torch.float32, device=ctx.dev)
+        st = C.c_void_p(torch.cuda.current_stream(ctx.dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        if lib.se_loss_pesq_bwd(p(g), p(ln), B, L, p(P["win"]), p(P["band_of"]), p(P["band_tab"]), p(ws), p(dpred), st):
+            raise RuntimeError(lib.se_loss_pesq_last_error().decode())
+        return None, dpred, None
+
+
+def pesq_loss(y_true_batch, y_pred_batch, lens=None, reduction="mean"):
+    """utility.pesq_loss (utility.py:615-814): minus the differentiable PESQ-like score of the enhanced waveform against the clean one.
+    Row b is the reference's value for y[b, :lens[b]] run ALONE (reflect padding at the row's own end; samples at or beyond lens[b]
+    are never read); "mean" returns the batch mean, anything else the per-row vector; lens=None means the full rows.  Gradients
+    flow to `y_pred_batch` only.  Stays on the device of `y_pred_batch`: the se_loss_pesq_* kernels on GPU tensors, `_pesq_d` else.
+
+    Deviations from the reference, on purpose: it ignores `lens`; at B > 1 it reuses the name `h` across its loop over the batch and
+    fails with a shape error unless T is 49, and would return the last row's value only.  Where it has a value (B = 1, lens[0] = L)
+    this one equals it.  Fewer than 20 spectrogram frames (4864 samples) have no value there (its 20-frame unfold raises): refused
+    here with NotImplementedError, for L and for `lens` given on the host; `lens` on the device is not synchronised on, such a row
+    yields NaN with a zero gradient.  The kernels hold a row's frames in LDS: rows of more than 896 frames (14.3 s) raise RuntimeError
+    on GPU tensors (PESQ_KERNELS = False runs them on the restatement)."""
+    y_pred_batch = torch.squeeze(y_pred_batch, dim=-1) if y_pred_batch.dim() == 3 else y_pred_batch
+    y_true_batch = torch.squeeze(y_true_batch, dim=-1) if y_true_batch.dim() == 3 else y_true_batch
+    B, L = y_pred_batch.shape
+    host_lens = lens is not None and not (torch.is_tensor(lens) and lens.is_cuda)
+    if L < PESQ_MIN_SAMPLES or (host_lens and int(torch.as_tensor(lens).min()) < PESQ_MIN_SAMPLES):
+        raise NotImplementedError(f"pesq_loss has no value for fewer than 20 spectrogram frames ({PESQ_MIN_SAMPLES} samples); "
+                                  f"got L = {L}, lens = {None if lens is None else [int(v) for v in torch.as_tensor(lens).reshape(-1)] if host_lens else 'on device'}")
+    lens_t = _lens_tensor(lens, B, L, y_pred_batch.device)
+    if PESQ_KERNELS and y_pred_batch.is_cuda:
+        v = _PesqHip.apply(y_true_batch.to(y_pred_batch.device), y_pred_batch, lens_t)
+    else:
+        v = _pesq_d(y_true_batch.to(y_pred_batch.device), y_pred_batch, lens_t)
+    return v.mean() if reduction == "mean" else v
+
+
+def gtsa_compute_loss(source, pred_source, length):
+    """GTSA.compute_loss (GTSA.py:411-433): (loss, mae, sisnr) with loss = 0.7 * pesq_loss + 0.3 * sisnr, sisnr = -SI-SNR; a NaN loss
+    is replaced by zeros without a gradient, all three (GTSA.py:429-432).  The reference's print of sisnr is dropped."""
+    mae = pesq_loss(source, pred_source, length)
+    sisnr = -cal_si_snr(pred_source, source, length)
+    loss = 0.7 * mae + 0.3 * sisnr
+    bad = torch.isnan(loss)
+    zero = torch.zeros_like(loss)
+    return torch.where(bad, zero, loss), torch.where(bad, zero, mae), torch.where(bad, zero, sisnr)
 
 
 # =====================================================================================================================
