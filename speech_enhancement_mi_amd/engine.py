@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Dict, Optional
 
 import numpy as np
@@ -18,24 +19,60 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libse_engine.so")
 SE_MAX_LEVELS = 8
 
-EXPORTS = [
-    "se_abi_version", "se_config_size", "fsn_config_size", "se_create", "se_destroy", "se_last_error", "se_load_param", "se_reset", "se_reset_stream", "se_step",
-    "se_realtime_process", "se_realtime_process_ragged", "se_realtime_process_chains", "se_chunk_geometry", "se_stft", "se_istft", "se_forward", "se_read_tap", "se_read_tap_dev", "se_export_state",
-    "se_import_state", "se_flops_per_frame", "se_frames_per_segment", "se_profile", "se_profile_read",
-    "fsn_create", "fsn_destroy", "fsn_last_error", "fsn_load_param", "fsn_reset", "fsn_forward", "fsn_realtime_process",
-    "fsn_realtime_process_chains", "fsn_reset_stream", "fsn_export_state", "fsn_import_state",
-    "fsn_read_tap", "fsn_flops_per_frame", "fsn_train_ws_bytes", "fsn_train_fwd", "fsn_train_bwd", "fsn_train_ws_bytes_chains", "fsn_train_fwd_chains", "fsn_train_bwd_chains", "se_loss_sisnr_fwd", "se_loss_sisnr_bwd", "se_loss_stoi_ws_floats", "se_loss_stoi_fwd", "se_loss_stoi_bwd", "se_loss_stoi_last_error",
-    "se_loss_pesq_ws_floats", "se_loss_pesq_fwd", "se_loss_pesq_bwd", "se_loss_pesq_last_error",
-    "se_train_last_error", "se_train_gemm", "se_train_gru_seq_fwd", "se_train_gru_seq_bwd", "se_train_gru_pseq_supported", "se_train_gru_pseq_scratch_floats", "se_train_gru_pseq_fwd", "se_train_gru_pseq_bwd", "se_train_gru_pseq_fwd_rows", "se_train_gru_pseq_bwd_rows",
-    "se_sig_create", "se_sig_destroy", "se_sig_stft", "se_sig_istft", "se_train_ola_fwd", "se_train_ola_bwd", "se_train_feat", "se_train_mask_fwd",
-    "se_train_mask_bwd", "se_train_gln_fwd", "se_train_gln_bwd", "se_train_colsum", "se_train_colsum_tall", "se_train_skip_fwd", "se_train_skip_bwd",
-    "se_train_add", "se_train_add3", "se_train_gate_fwd", "se_train_gate_bwd", "se_train_elu_bwd", "se_train_pre5", "se_train_gru_hprev", "se_train_conv_ws_floats", "se_train_conv_w", "se_train_conv_wgrad_det", "se_train_gemm_tn_det", "se_train_add_csum", "se_distill_ws_bytes",
-    "se_distill_fwd", "se_distill_bwd", "se_sig_stft_rows", "se_train_ola_fwd_rows", "se_train_ola_bwd_rows", "se_train_slab_gather", "se_gbf_psd_fwd", "se_gbf_seq_fwd", "se_gbf_bf_fwd", "se_gbf_psd_bwd", "se_gbf_seq_bwd", "se_gbf_bf_bwd", "se_gtsa_limits", "se_gtsa_feat", "se_gtsa_attn", "se_gtsa_tape", "se_gtsa_addnorm", "se_gtsa_qkv5", "se_gtsa_tail5",
-    "se_gtsa_gather3", "se_gtsa_out", "se_gtsa_tape_rows", "se_gtsa_lastframes_rows", "se_hifi_postnet", "se_hifi_gate", "se_hifi_skip", "se_hifi_rows",
-    "se_hifi_lstm", "se_hifi_seqnorm", "se_hifi_lstm_rows", "se_hifi_seqnorm_rows", "se_hifi_lstm_train_fwd", "se_hifi_lstm_bwd", "se_hifi_seqnorm_bwd",
-    "se_hifi_gate_bwd", "se_hifi_skip_bwd", "se_hifi_rows_bwd", "se_hifi_chansum", "se_hifi_lstm_train_fwd_rows",
-    "se_hifi_lstm_bwd_rows", "se_hifi_seqnorm_bwd_rows", "se_synth_last_error", "se_synth_rir", "se_synth_rir_tail", "se_synth_fir", "se_synth_mix",
-]
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "se_engine.h")
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float, "double": C.c_double}
+
+
+def _ctype(decl, is_return=False):
+    """One C parameter (`const float *x`, `int64_t n`) or return type -> its ctypes type; raises on anything it does not know."""
+    m = re.fullmatch(r"(\w+)\s*((?:\*\s*)*)(\w+)?", re.sub(r"\bconst\b", " ", decl).strip())
+    if not m or (is_return and m.group(3)):
+        raise ValueError(f"se_engine.h: cannot read the type of `{decl.strip()}`")
+    base, stars = m.group(1), m.group(2).count("*")
+    if stars:
+        return C.c_char_p if (base, stars) == ("char", 1) else C.c_void_p
+    if is_return and base == "void":
+        return None
+    if base not in _SCALARS:
+        raise ValueError(f"se_engine.h: unknown type `{base}` in `{decl.strip()}`")
+    return _SCALARS[base]
+
+
+def prototypes(header_text) -> Dict[str, tuple]:
+    """{name: (restype, [argtypes])} of every `ret name(args);` of the header whose name starts with se_ or fsn_.  int / int32_t ->
+    c_int, int64_t -> c_int64, uint32_t -> c_uint32, float, double, void return -> None, (const) char * -> c_char_p, every other
+    pointer -> c_void_p (which takes None, integers, byref(), ctypes arrays and typed pointers alike).  Comments, preprocessor lines,
+    the typedefs and the extern "C" brace are dropped first; whatever is left and is no such declaration, or has a type outside
+    this list, raises: nothing is guessed."""
+    t = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text, flags=re.S)
+    t = re.sub(r"^[ \t]*#.*$", " ", t, flags=re.M)
+    t = re.sub(r"\btypedef\b[^;{]*(\{[^}]*\}[^;]*)?;", " ", t)
+    t = re.sub(r'\bextern\s+"C"\s*\{(.*)\}', r"\1", t, flags=re.S)
+    table = {}
+    for stmt in filter(None, (" ".join(x.split()) for x in t.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise ValueError(f"se_engine.h: `{stmt}` is not a function declaration")
+        ret, name, args = m.groups()
+        if not name.startswith(("se_", "fsn_")):
+            continue
+        if name in table:
+            raise ValueError(f"se_engine.h declares {name} twice")
+        table[name] = (_ctype(ret, True), [] if args.strip() == "void" else [_ctype(a) for a in args.split(",")])
+    return table
+
+
+def _header_prototypes():
+    try:
+        with open(HEADER_PATH) as f:
+            return prototypes(f.read())
+    except OSError as e:
+        raise RuntimeError(f"{HEADER_PATH} is missing ({e}): the binding derives every ctypes prototype from it and has no copy") from None
+
+
+PROTOTYPES = _header_prototypes()
+EXPORTS = sorted(PROTOTYPES)
 
 
 class SeDistillMap(C.Structure):  # se_distill_map
@@ -70,160 +107,13 @@ def load_library():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C speech_enhancement_mi_amd/csrc).  The engine has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, fp, i64p = C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)
-    L.se_abi_version.restype = C.c_int
     # a struct mirror shorter than the library's se_config would leave its tail fields (precision) reading garbage
     if L.se_config_size() != C.sizeof(SeConfig) or L.fsn_config_size() != C.sizeof(FsnConfig):
         raise RuntimeError(f"libse_engine.so was built with sizeof(se_config) = {L.se_config_size()}, sizeof(fsn_config) = "
                            f"{L.fsn_config_size()}; this binding has {C.sizeof(SeConfig)} / {C.sizeof(FsnConfig)}: rebuild the library")
-    L.se_create.argtypes = [C.POINTER(SeConfig), C.c_int, C.POINTER(vp)]
-    L.se_destroy.argtypes = [vp]
-    L.se_destroy.restype = None
-    L.se_last_error.argtypes = [vp]
-    L.se_last_error.restype = C.c_char_p
-    L.se_load_param.argtypes = [vp, C.c_char_p, fp, i64p, C.c_int]
-    L.se_reset.argtypes = [vp, C.c_int]
-    L.se_reset_stream.argtypes = [vp, C.c_int, vp]
-    L.se_step.argtypes = [vp, fp, fp, vp]
-    L.se_realtime_process.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, fp, vp]
-    L.se_realtime_process_ragged.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.c_int, fp, vp]
-    L.se_realtime_process_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), fp, vp]
-    L.se_chunk_geometry.argtypes = [C.c_int, C.c_int64, C.c_int, i64p, i64p, i64p]
-    L.se_stft.argtypes = [vp, fp, C.c_int, fp, vp]
-    L.se_istft.argtypes = [vp, fp, C.c_int, fp, vp]
-    L.se_forward.argtypes = [vp, fp, fp, vp]
-    L.se_read_tap.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
-    L.se_read_tap_dev.argtypes = [vp, C.c_char_p, vp, C.c_int64, i64p, vp]
-    L.se_export_state.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
-    L.se_import_state.argtypes = [vp, C.c_char_p, fp, C.c_int64, vp]
-    L.se_flops_per_frame.argtypes = [vp]
-    L.se_flops_per_frame.restype = C.c_double
-    L.se_frames_per_segment.argtypes = [vp]
-    L.fsn_create.argtypes = [C.POINTER(FsnConfig), C.c_int, C.POINTER(vp)]
-    L.fsn_destroy.argtypes = [vp]
-    L.fsn_destroy.restype = None
-    L.fsn_last_error.argtypes = [vp]
-    L.fsn_last_error.restype = C.c_char_p
-    L.fsn_load_param.argtypes = [vp, C.c_char_p, fp, i64p, C.c_int]
-    L.fsn_reset.argtypes = [vp, C.c_int]
-    L.fsn_forward.argtypes = [vp, fp, fp, vp]
-    L.fsn_realtime_process.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, fp, vp]
-    L.fsn_realtime_process_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), fp, vp]
-    L.fsn_reset_stream.argtypes = [vp, C.c_int, vp]
-    L.fsn_export_state.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
-    L.fsn_import_state.argtypes = [vp, C.c_char_p, fp, C.c_int64, vp]
-    L.fsn_read_tap.argtypes = [vp, C.c_char_p, fp, C.c_int64, i64p, vp]
-    L.fsn_flops_per_frame.argtypes = [vp]
-    L.fsn_flops_per_frame.restype = C.c_double
-    L.fsn_train_ws_bytes.argtypes = [vp, C.c_int, C.c_int]
-    L.fsn_train_ws_bytes.restype = C.c_int64
-    L.fsn_train_fwd.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, vp, fp, vp]
-    L.fsn_train_bwd.argtypes = [vp, fp, C.c_int, C.c_int, vp, C.POINTER(vp), C.c_int, vp]
-    L.fsn_train_ws_bytes_chains.argtypes = [vp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8)]
-    L.fsn_train_ws_bytes_chains.restype = C.c_int64
-    L.fsn_train_fwd_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), vp, fp, vp]
-    L.fsn_train_bwd_chains.argtypes = [vp, fp, C.c_int, C.c_int64, i64p, C.POINTER(C.c_uint8), vp, C.POINTER(vp), C.c_int, vp]
-    L.se_loss_sisnr_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp]
-    L.se_loss_stoi_ws_floats.argtypes = [C.c_int, C.c_int64]
-    L.se_loss_stoi_ws_floats.restype = C.c_int64
-    L.se_loss_stoi_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    L.se_loss_stoi_bwd.argtypes = [vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    L.se_loss_stoi_last_error.restype = C.c_char_p
-    L.se_loss_pesq_ws_floats.argtypes = [C.c_int, C.c_int64]
-    L.se_loss_pesq_ws_floats.restype = C.c_int64
-    L.se_loss_pesq_fwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
-    L.se_loss_pesq_bwd.argtypes = [vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
-    L.se_loss_pesq_last_error.restype = C.c_char_p
-    L.se_loss_sisnr_bwd.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
-    i32, i64 = C.c_int, C.c_int64
-    L.se_train_last_error.restype = C.c_char_p
-    L.se_train_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.se_train_gru_seq_fwd.argtypes = [vp] * 8 + [i32, i32, i32, vp]
-    L.se_train_gru_seq_bwd.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp]
-    L.se_train_gru_pseq_supported.argtypes = [i32, i32]
-    L.se_train_gru_pseq_scratch_floats.argtypes = [i32, i32]
-    L.se_train_gru_pseq_fwd.argtypes = [vp] * 8 + [i32, i32, i32, i32, i64, i64, vp]
-    L.se_train_gru_pseq_bwd.argtypes = [vp] * 9 + [i32, i32, i32, i32, i64, i64, i32, vp]
-    L.se_train_gru_pseq_fwd_rows.argtypes = [vp] * 8 + [i32, i32, i32, i32, i64, i64, vp, vp]
-    L.se_train_gru_pseq_bwd_rows.argtypes = [vp] * 9 + [i32, i32, i32, i32, i64, i64, i32, vp, vp]
-    L.se_sig_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-    L.se_sig_destroy.argtypes = [vp]
-    L.se_sig_destroy.restype = None
-    L.se_sig_stft.argtypes = [vp, vp, i32, i32, i64, i64, i64, i32, vp, vp]
-    L.se_sig_istft.argtypes = [vp, vp, i32, vp, vp]
-    L.se_train_ola_fwd.argtypes = [vp, vp, vp, i32, i64, i64, vp]
-    L.se_train_ola_bwd.argtypes = [vp, vp, vp, i32, i32, i64, i64, vp]
-    L.se_sig_stft_rows.argtypes = [vp, vp, i32, i32, i64, vp, vp, i64, i32, vp, vp]
-    L.se_train_ola_fwd_rows.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
-    L.se_train_ola_bwd_rows.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp]
-    L.se_train_slab_gather.argtypes = [vp, vp, vp, i32, i64, i64, i64, vp]
-    L.se_train_feat.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    L.se_train_mask_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.se_train_mask_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.se_train_gln_fwd.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp] + [i32] * 8 + [vp]
-    L.se_train_gln_bwd.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp]
-    L.se_train_colsum.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]
-    L.se_train_colsum_tall.argtypes = [vp, i64, i32, vp, vp, i32, vp]
-    L.se_train_skip_fwd.argtypes = [vp] * 6 + [i32] * 6 + [vp]
-    L.se_train_skip_bwd.argtypes = [vp] * 11 + [i32] * 6 + [vp]
-    L.se_train_add.argtypes = [vp, vp, i64, vp]
-    L.se_train_add3.argtypes = [vp, vp, vp, i64, vp]
-    L.se_train_gate_fwd.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp] + [i32] * 5 + [vp]
-    L.se_train_gate_bwd.argtypes = [vp, i64, i64, i64] + [vp] * 7 + [i32] * 5 + [vp]
-    L.se_train_elu_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.se_train_pre5.argtypes = [i32] + [vp] * 6 + [i32] * 6 + [vp]
-    L.se_train_gru_hprev.argtypes = [vp, vp, vp, i32, i32, i32, i32, i64, i64, vp]
-    L.se_train_conv_ws_floats.argtypes = [i32] * 7
-    L.se_train_conv_w.argtypes = [i32, vp, vp, vp, i64, i64, vp, vp, vp] + [i32] * 10 + [vp]
-    L.se_train_conv_wgrad_det.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)] + [i32] * 8 + [vp]
-    L.se_train_gemm_tn_det.argtypes = [vp, vp, vp, C.POINTER(C.c_int), i64, i32, i32, vp]
-    L.se_train_add_csum.argtypes = [vp, vp, vp, i32, i32, i64, vp]
-    L.se_distill_ws_bytes.argtypes = [C.POINTER(SeDistillMap), i32, i32]
-    L.se_distill_ws_bytes.restype = i64
-    L.se_distill_fwd.argtypes = [C.POINTER(SeDistillMap), i32, i32, i32, vp, vp, vp]
-    L.se_distill_bwd.argtypes = [C.POINTER(SeDistillMap), i32, i32, i32, vp, vp, vp]
-    L.se_gbf_psd_fwd.argtypes = [vp] * 8 + [i32] * 5 + [vp]
-    L.se_gbf_seq_fwd.argtypes = [vp] * 13 + [i32] * 5 + [vp]
-    L.se_gbf_bf_fwd.argtypes = [vp] * 10 + [i32] * 5 + [vp]
-    L.se_gbf_psd_bwd.argtypes = [vp] * 10 + [i32] * 5 + [vp]
-    L.se_gbf_seq_bwd.argtypes = [vp] * 16 + [i32] * 5 + [vp]
-    L.se_gbf_bf_bwd.argtypes = [vp] * 14 + [i32] * 6 + [vp]
-    L.se_gtsa_limits.argtypes = [C.POINTER(C.c_int)] * 3
-    L.se_gtsa_feat.argtypes = [vp] * 2 + [i32] * 5 + [vp]
-    L.se_gtsa_attn.argtypes = [vp] * 7 + [i32] * 11 + [vp]
-    L.se_gtsa_tape.argtypes = [vp] * 6 + [i32] * 8 + [vp]
-    L.se_gtsa_tape_rows.argtypes = [vp] * 7 + [i32] * 8 + [vp]
-    L.se_gtsa_lastframes_rows.argtypes = [vp] * 4 + [i32] * 4 + [vp]
-    L.se_gtsa_addnorm.argtypes =[vp, i32] + [vp] * 4 + [i32] * 4 + [vp]
-    L.se_gtsa_qkv5.argtypes = [vp] * 8 + [i32] * 4 + [vp]
-    L.se_gtsa_tail5.argtypes = [vp, i32] + [vp] * 12 + [i32] * 5 + [vp]
-    L.se_gtsa_gather3.argtypes = [vp] * 3 + [i32] * 4 + [vp]
-    L.se_gtsa_out.argtypes = [vp, i32] + [vp] * 5 + [i32] * 4 + [vp]
-    L.se_hifi_postnet.argtypes = [vp] * 3 + [i32] * 3 + [vp]
-    L.se_hifi_gate.argtypes = [vp, vp, C.c_int64, vp]
-    L.se_hifi_skip.argtypes = [vp] * 3 + [i32] * 5 + [vp]
-    L.se_hifi_rows.argtypes = [vp] * 2 + [i32] * 5 + [vp]
-    L.se_hifi_lstm.argtypes = [vp] * 7 + [i32] * 3 + [vp]
-    L.se_hifi_seqnorm.argtypes = [vp] * 4 + [C.c_double] + [vp] * 3 + [i32] * 5 + [vp]
-    L.se_hifi_lstm_rows.argtypes = [vp] * 8 + [i32] * 3 + [vp]
-    L.se_hifi_seqnorm_rows.argtypes = [vp] * 9 + [i32] * 5 + [vp]
-    L.se_hifi_lstm_train_fwd.argtypes = [vp] * 9 + [i32] * 3 + [vp]
-    L.se_hifi_lstm_bwd.argtypes = [vp] * 7 + [i32] * 4 + [vp]
-    L.se_hifi_seqnorm_bwd.argtypes = [vp] * 4 + [C.c_double] + [vp] * 4 + [i32] * 5 + [vp]
-    L.se_hifi_gate_bwd.argtypes = [vp, vp, vp, C.c_int64, vp]
-    L.se_hifi_skip_bwd.argtypes = [vp] * 5 + [i32] * 5 + [vp]
-    L.se_hifi_rows_bwd.argtypes = [vp] * 2 + [i32] * 5 + [vp]
-    L.se_hifi_chansum.argtypes = [vp, vp, C.c_int64, i32, vp]
-    L.se_hifi_lstm_train_fwd_rows.argtypes = [vp] * 10 + [i32] * 3 + [vp]
-    L.se_hifi_lstm_bwd_rows.argtypes = [vp] * 8 + [i32] * 4 + [vp]
-    L.se_hifi_seqnorm_bwd_rows.argtypes = [vp] * 10 + [i32] * 5 + [vp]
-    L.se_synth_last_error.restype = C.c_char_p
-    L.se_synth_rir.argtypes = [vp, vp, vp, vp] + [i32] * 6 + [C.c_float, C.c_float, i32, vp, vp]
-    L.se_synth_rir_tail.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_uint32, vp]
-    L.se_synth_fir.argtypes = [vp, vp, i32, i32, i32, i64, i32, vp, vp]
-    L.se_synth_mix.argtypes = [vp, vp, i32, i32, i32, i64, C.c_float, vp, vp, vp, vp]
-    L.se_profile.argtypes = [vp, C.c_int]
-    L.se_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_double), i64p, C.POINTER(C.c_double)]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -26,6 +26,46 @@ def test_header_symbols_exported():
     assert lib.se_abi_version() == 5
 
 
+def _table():
+    from speech_enhancement_mi_amd import engine
+    return engine.prototypes(open(os.path.join(ROOT, "include", "se_engine.h")).read())
+
+
+def test_derived_prototypes_one_function_per_scalar_kind():
+    """engine.prototypes reads the ctypes table out of the header; written out here: a double in the middle, two floats, a uint32_t,
+    char * outputs, an int64_t return, a const char * return, void."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_void_p as vp
+    table = _table()
+    assert table["se_hifi_seqnorm"] == (c_int, [vp] * 4 + [c_double] + [vp] * 3 + [c_int] * 5 + [vp])
+    assert table["se_synth_rir"] == (c_int, [vp] * 4 + [c_int] * 6 + [c_float, c_float, c_int, vp, vp])
+    assert table["se_synth_rir_tail"] == (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_float, c_uint32, vp])
+    assert table["se_profile_read"] == (c_int, [vp, c_int, c_char_p, c_char_p, c_int, vp, vp, vp])
+    assert table["fsn_train_ws_bytes_chains"] == (c_int64, [vp, c_int, c_int64, vp, vp])
+    assert table["se_last_error"] == (c_char_p, [vp])
+    assert table["se_destroy"] == (None, [vp])
+
+
+def test_every_declared_function_has_a_prototype():
+    """Two separate parses of the header (_declared above, the binding's) name the same functions, and load_library() has applied the
+    binding's table to the library."""
+    from speech_enhancement_mi_amd import engine
+    table = _table()
+    assert sorted(table) == _declared() == engine.EXPORTS
+    lib = engine.load_library()
+    for name, (restype, argtypes) in table.items():
+        assert (getattr(lib, name).restype, list(getattr(lib, name).argtypes)) == (restype, argtypes), name
+
+
+def test_prototypes_raise_on_a_type_they_do_not_know():
+    from speech_enhancement_mi_amd import engine
+    for line in ("int se_new(unsigned n);", "int se_new(size_t n, void *stream);", "long se_new(void);", "int se_new(float x[4]);",
+                 "int se_new(se_config cfg);", "int se_new(int (*cb)(int));"):
+        with pytest.raises(ValueError):
+            engine.prototypes("int se_abi_version(void);\n" + line)
+    # comments are no declarations
+    assert engine.prototypes("/* int se_old(size_t n); */\nint se_abi_version(void);  // int se_older(long n);\n") == {"se_abi_version": (ctypes.c_int, [])}
+
+
 def test_no_cpu_fallback():
     """Without a GPU the engine must fail loudly, never compute on the host."""
     import torch

@@ -5,14 +5,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import FULL400, FULL512, STUDENT400, spec_of_variant
+from conftest import FULL400, FULL512, STUDENT400
+from engine_cases import cuda as _cuda, make_engine
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
 def _rel(a, b):
@@ -20,15 +17,7 @@ def _rel(a, b):
 
 
 def _engine(cfg, monkeypatch, pair, variant=0, precision=0, seed=0):
-    from speech_enhancement_mi_amd import engine
-    monkeypatch.setenv("SE_DEC_PAIR", "1" if pair else "0")  # read when the engine is created
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of_variant(cfg, variant), seed=seed))
-    monkeypatch.delenv("SE_DEC_PAIR")
-    return e
+    return make_engine(cfg, monkeypatch, {"SE_DEC_PAIR": "1" if pair else "0"}, variant=variant, precision=precision, seed=seed)
 
 
 def _pair_vs_two_launches(monkeypatch, cfg, B, precision=0, variant=0, lengths=None, seed=0, pair_expected=True):

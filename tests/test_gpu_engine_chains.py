@@ -7,7 +7,8 @@ import pytest
 import torch
 
 import chain_cases as cc
-from conftest import FULL400, TINY, rel_rms, spec_of_variant
+from conftest import FULL400, TINY, rel_rms
+from engine_cases import cuda as _cuda, make_engine as _engine
 from speech_enhancement_mi_amd import synth
 from speech_enhancement_mi_amd.engine import chain_geometry
 
@@ -21,20 +22,6 @@ BAR_ALONE = 2e-6      # batch against each stream alone: the bar of test_gpu_rou
 # 60000 then 48000 samples, flag=False then flag=True, batch against alone) measures 0.0 / 0.0 as well, so BAR_ALONE needs no
 # allowance for two calls accumulating.
 BAR_BF16X3 = 2 * 0.0
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def _engine(cfg, variant=0, precision=0, seed=0):  # as tests/test_gpu_round3.py::_engine
-    from speech_enhancement_mi_amd import engine
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of_variant(cfg, variant), seed=seed))
-    return e
 
 
 # ---- 1. the reference fixture ------------------------------------------------------------------------------------------------
@@ -267,12 +254,11 @@ def test_ragged_call_is_a_chains_call_state_included():
 def test_engine_and_training_handle_share_one_signal_chain(n_fft):
     """Engine.stft / istft (se_stft, se_istft) and the training signal handle (train_stages._sig + se_sig_stft / se_sig_istft) on the same
     6 rows of 3200 samples: one table builder and one launcher behind both, so after the layout transpose the results are bit-equal."""
-    from speech_enhancement_mi_amd import engine, train_stages as ts
+    from speech_enhancement_mi_amd import train_stages as ts
     from speech_enhancement_mi_amd import train_ops as K
     cfg = dict(TINY, n_fft=n_fft, num_freqs=n_fft // 2 + 1)
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"], cfg["num_inputs"],
-                           cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
-    e = engine.Engine(c, 0)
+    e = _engine(cfg)
+    c = e.cfg
     n, Ks = 6, cfg["segment_length"]
     seg = torch.from_numpy(np.random.default_rng(9).standard_normal((n, Ks)).astype(np.float32)).cuda()
     sig = ts._sig(seg.device, n_fft, c.win, c.hop, Ks)

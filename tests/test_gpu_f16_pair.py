@@ -4,48 +4,30 @@ scaled fp16 planes, k_gemm_p and the GRU step on three f16 MFMA terms.  The smal
 step kernels) and FULL512 at 4 streams; three segments, flag False then True."""
 import numpy as np
 import pytest
-import torch
 
-from conftest import FSN_TINY, FULL512, STUDENT400, TINY, fsn_spec, rel_rms, spec_of, spec_of_variant
+from conftest import FSN_TINY, FULL512, STUDENT400, TINY, rel_rms, spec_of
+from engine_cases import SMALL as CFG, cuda as _cuda, carried_state, make_engine, make_fsn_engine, utterances
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-CFG = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)
 L1, L2 = 6400, 4800  # three segments, then two more with the carried state
 TAPS = ["gru", "dec0", "dec2", "enc0", "enc1", "enc2", "enc3"]
 
 
 def _engine(cfg, env, monkeypatch, seed=4, precision=0, variant=0, sd=None):
     """An engine created under `env` (the knobs are read at creation; every engine here is on the plane GEMM route)."""
-    from speech_enhancement_mi_amd import engine
-    monkeypatch.setenv("SE_GEMM_SKINNY_ROWS", "0")
-    monkeypatch.setenv("SE_SKIP_MIN_BATCH", "1")
-    for k in ("SE_F16_PAIR", "SE_PIPELINE"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(sd if sd is not None else synth.make_state_dict(spec_of_variant(cfg, variant) if variant else spec_of(cfg), seed=seed))
-    return e
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    return make_engine(cfg, monkeypatch, dict({"SE_GEMM_SKINNY_ROWS": "0", "SE_SKIP_MIN_BATCH": "1"}, **env), seed=seed, precision=precision,
+                       variant=variant, sd=sd)
 
 
 @pytest.fixture(scope="module")
 def audio():
-    mix, _ = synth.synth_utterances(40, L1 + L2, 3, seed=61)
-    mix.setflags(write=False)
-    return mix
+    return utterances(40, L1 + L2, seed=61)
 
 
 def _state(e, cfg):
-    return [e.export_state("h")] + [e.export_state(f"buf{i}") for i in range(len(cfg["num_channels"]))]
+    return list(carried_state(e, cfg).values())  # h, buf0, buf1, ...
 
 
 @pytest.mark.parametrize("name,cfg,batch", [("small17", CFG, 17), ("small40", CFG, 40), ("full512", FULL512, 4)])
@@ -174,15 +156,11 @@ def test_knob_leaves_other_routes_alone(case, audio, monkeypatch):
 
 
 def test_knob_leaves_fullsubnet_alone(audio, monkeypatch):
-    from speech_enhancement_mi_amd import engine
     cfg = FSN_TINY
     ys = []
     for v in ("1", "0"):
         monkeypatch.setenv("SE_F16_PAIR", v)
-        e = engine.FsnEngine(cfg["num_freqs"], cfg["num_mics"], cfg["fb_model_hidden_size"], cfg["sb_model_hidden_size"], cfg["num_layers"],
-                             cfg["sb_num_neighbors"], cfg["fb_num_neighbors"], cfg["look_ahead"], cfg["sample_rate"], cfg["segment_length"],
-                             cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
-        e.load_state_dict(synth.make_state_dict(fsn_spec(cfg), seed=0))
+        e = make_fsn_engine(cfg)
         ys.append(e.realtime_process(_cuda(audio[:2, :, :6400])).cpu().numpy())
     assert np.abs(ys[0]).max() > 0
     assert np.array_equal(ys[0], ys[1])

@@ -5,53 +5,30 @@ of 17 and 40) and FULL512 at 4 streams; three segments, flag False then True.  S
 the bottleneck only), SE_F16_PAIR=0 the bf16 route everywhere."""
 import numpy as np
 import pytest
-import torch
 
-from conftest import FULL512, STUDENT400, TINY, rel_rms, spec_of, spec_of_variant
+from conftest import FULL512, STUDENT400, TINY, rel_rms, spec_of
+from engine_cases import SMALL as CFG, carried_state as _state, cuda as _cuda, make_engine, snapshot, utterances
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-CFG = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)
 L1, L2 = 6400, 4800  # three segments, then two more with the carried state
 TAPS = ["feat", "enc0", "enc1", "enc2", "enc3", "gru", "dec0", "dec1", "dec2"]
-KNOBS = ("SE_F16_PAIR", "SE_F16_PAIR_CONV", "SE_PIPELINE", "SE_SKIP_MIN_BATCH", "SE_DEC_PAIR", "SE_IO_FUSE")
 SKIP_STREAM = {"SE_SKIP_MIN_BATCH": "1"}  # k_skip_p at every batch; without it batches below 96 take the two-launch kPOutBlend form
 
 
 def _engine(cfg, env, monkeypatch, seed=4, precision=0, variant=0, sd=None):
     """An engine created under `env` (the knobs are read at creation; every engine here is on the plane GEMM route)."""
-    from speech_enhancement_mi_amd import engine
-    monkeypatch.setenv("SE_GEMM_SKINNY_ROWS", "0")
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(sd if sd is not None else synth.make_state_dict(spec_of_variant(cfg, variant) if variant else spec_of(cfg), seed=seed))
-    return e
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    return make_engine(cfg, monkeypatch, dict({"SE_GEMM_SKINNY_ROWS": "0"}, **env), seed=seed, precision=precision, variant=variant, sd=sd)
 
 
 @pytest.fixture(scope="module")
 def audio():
-    mix, _ = synth.synth_utterances(40, L1 + L2, 3, seed=61)
-    mix.setflags(write=False)
-    return mix
-
-
-def _state(e, cfg):
-    return {"h": e.export_state("h"), **{f"buf{i}": e.export_state(f"buf{i}") for i in range(len(cfg["num_channels"]))}}
+    return utterances(40, L1 + L2, seed=61)
 
 
 def _snapshot(e, cfg, y):
-    return {"out": y, **{t: e.read_tap(t) for t in TAPS}, **_state(e, cfg)}
+    return snapshot(e, cfg, y, TAPS)
 
 
 @pytest.mark.parametrize("name,cfg,batch,env", [("small17", CFG, 17, SKIP_STREAM), ("small40", CFG, 40, {}), ("full512", FULL512, 4, SKIP_STREAM),

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import FULL400, FULL512, STUDENT400, rel_rms, spec_of_variant
+from engine_cases import cuda as _cuda, make_engine
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +21,6 @@ pytestmark = pytest.mark.gpu
 TOL, TOL_TAP, TOL_F16 = 1e-4, 2e-5, 3e-3
 CASES = {"crn512": (FULL512, 0), "crn400": (FULL400, 0), "elu400": (FULL400, 1), "student400": (STUDENT400, 2)}
 PICK = [0, 11, 12]  # streams the oracle restates: first tile, last whole stream of row tile 0, the stream that straddles the tiles
-
-
-def _cuda(a):
-    return torch.from_numpy(np.array(a, dtype=np.float32, order="C")).cuda()  # (a copy: the shared references are read-only)
 
 
 def _state_dict(cfg, variant):
@@ -40,16 +37,8 @@ def _state_dict(cfg, variant):
 
 
 def _engine(monkeypatch, case, precision=0):
-    from speech_enhancement_mi_amd import engine
     cfg, variant = CASES[case]
-    monkeypatch.setenv("SE_GEMM_SKINNY_ROWS", "0")
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    monkeypatch.delenv("SE_GEMM_SKINNY_ROWS")
-    e.load_state_dict(_state_dict(cfg, variant))
-    return e
+    return make_engine(cfg, monkeypatch, {"SE_GEMM_SKINNY_ROWS": "0"}, variant=variant, precision=precision, sd=_state_dict(cfg, variant))
 
 
 def _oracle(case):
@@ -140,13 +129,9 @@ def test_bf16x3_and_fp16(monkeypatch, case):
 
 def test_default_route_small_batch_unchanged(monkeypatch):
     """Without the override a batch of 13 streams stays on the fp32 GEMM route (reference column order, two-pass statistics)."""
-    from speech_enhancement_mi_amd import engine
     cfg, variant = CASES["crn400"]
     x, yo, tapo = _reference("crn400")
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
-    e = engine.Engine(c, 0)
-    e.load_state_dict(_state_dict(cfg, variant))
+    e = make_engine(cfg, variant=variant, sd=_state_dict(cfg, variant))
     y, tap = _forward(e, x)
     assert _norm_kernels(e, x) == {"k_gln2_stream_p"}
     for i, b in enumerate(PICK):

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as Fn
 
 from conftest import FULL400, STUDENT400, TINY, rel_rms, spec_of_variant
+from engine_cases import cuda as _cuda, make_engine
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -16,19 +17,9 @@ TOL_TAP = 2e-5  # the project's tap bar (test_student_feature_taps_golden, test_
 B = 2
 
 
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
 def _engine(cfg, seed):
-    from speech_enhancement_mi_amd import engine
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=0, precision=0)
-    e = engine.Engine(c, 0)
     sd = synth.make_state_dict(spec_of_variant(cfg, 0), seed=seed)
-    e.load_state_dict(sd)
-    return e, sd
+    return make_engine(cfg, sd=sd), sd
 
 
 @pytest.mark.parametrize("case", ["full400", "full400_bf16", "tiny"])

@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import FSN_FULL, FSN_TINY, ROOT, fsn_spec, rel_rms
+from conftest import FSN_FULL, FSN_TINY, ROOT, rel_rms
+from engine_cases import cuda as _cuda, make_fsn_engine as _engine
 from speech_enhancement_mi_amd import synth
-from speech_enhancement_mi_amd.engine import FsnEngine, chain_geometry
+from speech_enhancement_mi_amd.engine import chain_geometry
 
 pytestmark = pytest.mark.gpu
 
@@ -23,18 +24,6 @@ SE_ERR_ARG, SE_ERR_KEY, SE_ERR_STATE = -1, -2, -4
 # the cases of tests/golden/make_golden_fsn_chain.py
 SEED, TOTAL = 21, 12800
 CALLS = (((False, False, False), (8000, 5200, 3400)), ((True, False, True), (4800, 7000, 3300)))
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def _engine(cfg, precision=0, seed=0):
-    e = FsnEngine(cfg["num_freqs"], cfg["num_mics"], cfg["fb_model_hidden_size"], cfg["sb_model_hidden_size"], cfg["num_layers"],
-                  cfg["sb_num_neighbors"], cfg["fb_num_neighbors"], cfg["look_ahead"], cfg["sample_rate"], cfg["segment_length"],
-                  cfg["win_length"], cfg["hop_length"], cfg["n_fft"], precision=precision)
-    e.load_state_dict(synth.make_state_dict(fsn_spec(cfg), seed=seed))
-    return e
 
 
 def _batches(calls, seed, pad):
@@ -58,7 +47,7 @@ def _stream_state(e, cfg, B, b):
 
 
 def _run_batch(cfg, calls, xs, precision=0, seed=0, states=True):
-    e = _engine(cfg, precision, seed)
+    e = _engine(cfg, precision=precision, seed=seed)
     B = len(calls[0][0])
     ys, sts = [], []
     for c, (lens, flags) in enumerate(calls):
@@ -69,7 +58,7 @@ def _run_batch(cfg, calls, xs, precision=0, seed=0, states=True):
 
 def _run_alone(cfg, calls, xs, streams, precision=0, seed=0, states=True):
     """every listed stream's chain by itself on one batch-1 engine -> ys[c][b], sts[c][b][name]"""
-    e1 = _engine(cfg, precision, seed)
+    e1 = _engine(cfg, precision=precision, seed=seed)
     ys, sts = [dict() for _ in calls], [dict() for _ in calls]
     for b in streams:
         for c, (lens, flags) in enumerate(calls):

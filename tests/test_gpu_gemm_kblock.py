@@ -8,50 +8,30 @@ GRU step - and 17 streams, which run the skinny fp32 GEMM and the fp32 step kern
 flag=False, then 4800 with the carried state."""
 import numpy as np
 import pytest
-import torch
 
-from conftest import FULL400, FULL512, rel_rms, spec_of
+from conftest import FULL400, rel_rms, spec_of
+from engine_cases import SMALL as CFG512, cuda as _cuda, make_engine, snapshot, utterances
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-CFG512 = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)
 CFG400 = dict(FULL400, num_channels=[8, 8, 16, 32], hidden=32)
 L1, L2 = 6400, 4800
 TAPS = ["feat", "enc0", "enc1", "enc2", "enc3", "gru", "dec0", "dec1", "dec2"]
-KNOBS = ("SE_F16_PAIR", "SE_F16_PAIR_CONV", "SE_PAIR_W3", "SE_PIPELINE", "SE_SKIP_MIN_BATCH", "SE_DEC_PAIR", "SE_IO_FUSE", "SE_GRU_SPLIT",
-         "SE_GEMM_KBLOCK", "SE_GEMM_SKINNY_ROWS", "SE_GEMM_P")
 OFF = {"SE_GEMM_KBLOCK": "0"}
 
 
-def _engine(cfg, env, monkeypatch, seed=4, sd=None):
-    """An engine created under `env` (the knobs are read at creation)."""
-    from speech_enhancement_mi_amd import engine
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"])
-    e = engine.Engine(c, 0)
-    e.load_state_dict(sd if sd is not None else synth.make_state_dict(spec_of(cfg), seed=seed))
-    return e
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+def _engine(cfg, env, monkeypatch, sd=None):
+    return make_engine(cfg, monkeypatch, env, seed=4, sd=sd)
 
 
 @pytest.fixture(scope="module")
 def audio():
-    mix, _ = synth.synth_utterances(40, L1 + L2, 3, seed=61)
-    mix.setflags(write=False)
-    return mix
+    return utterances(40, L1 + L2, seed=61)
 
 
 def _snapshot(e, cfg, y):
-    state = {"h": e.export_state("h"), **{f"buf{i}": e.export_state(f"buf{i}") for i in range(len(cfg["num_channels"]))}}
-    return {"out": y, **{t: e.read_tap(t) for t in TAPS}, **state}
+    return snapshot(e, cfg, y, TAPS)
 
 
 def _kblocked(e):

@@ -4,29 +4,14 @@ k_gemm_p), batches of 17 and 40 streams (more than 16, a partial 32-row tile, tw
 a flag=True continuation (the t = 0 hand-over from the fp32 state, ring-slot reuse)."""
 import numpy as np
 import pytest
-import torch
 
-from conftest import FULL512, rel_rms, spec_of
+from conftest import rel_rms, spec_of
+from engine_cases import SMALL as CFG, cuda as _cuda, make_engine as _engine, utterances
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-CFG = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)
 L1, L2 = 11200, 6400
-
-
-def _engine(cfg, seed=0, precision=0):
-    from speech_enhancement_mi_amd import engine
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of(cfg), seed=seed))
-    return e
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
 def _pair(monkeypatch, env_a, env_b, cfg=CFG, precision=0, seed=4):
@@ -42,9 +27,7 @@ def _pair(monkeypatch, env_a, env_b, cfg=CFG, precision=0, seed=4):
 
 @pytest.fixture(scope="module")
 def audio():
-    mix, _ = synth.synth_utterances(40, L1 + L2, 3, seed=61)
-    mix.setflags(write=False)
-    return mix
+    return utterances(40, L1 + L2, seed=61)
 
 
 @pytest.mark.parametrize("batch", [17, 40])

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import TINY, spec_of_variant
+from conftest import TINY
+from engine_cases import cuda as _cuda, make_engine
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -14,24 +15,11 @@ TINY512 = dict(TINY, num_freqs=257, n_fft=512)
 CFGS = [pytest.param(TINY, id="400"), pytest.param(TINY512, id="512")]
 
 
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
 def _engine(cfg, monkeypatch, fuse, variant=0, precision=0, pipeline=None, seed=0):
-    from speech_enhancement_mi_amd import engine
-    if not fuse:
-        monkeypatch.setenv("SE_IO_FUSE", "0")  # read when the engine is created; the default engine is made with nothing set
+    env = {} if fuse else {"SE_IO_FUSE": "0"}  # the default engine is made with nothing set
     if pipeline is not None:
-        monkeypatch.setenv("SE_PIPELINE", str(pipeline))
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of_variant(cfg, variant), seed=seed))
-    monkeypatch.delenv("SE_IO_FUSE", raising=False)
-    monkeypatch.delenv("SE_PIPELINE", raising=False)
-    return e
+        env["SE_PIPELINE"] = str(pipeline)
+    return make_engine(cfg, monkeypatch, env, variant=variant, precision=precision, seed=seed)
 
 
 def _pair(cfg, monkeypatch, **kw):

@@ -6,26 +6,13 @@ import pytest
 import torch
 
 from conftest import FSN_FULL, FULL400, FULL512, STUDENT400, TINY, fsn_spec, rel_rms, spec_of, spec_of_variant
+from engine_cases import cuda as _cuda, make_engine as _engine
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4       # north_star: waveforms within 1e-4 RMS of the reference CPU path (relative form, see test_gpu_parity.py)
 TOL_DB = 0.02    # north_star: SI-SDR within +-0.02 dB
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def _engine(cfg, variant=0, precision=0, seed=0):
-    from speech_enhancement_mi_amd import engine
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of_variant(cfg, variant), seed=seed))
-    return e
 
 
 # ---- 8f-3: state hand-over -----------------------------------------------------------------------------------------
@@ -35,7 +22,7 @@ def test_import_state_into_fresh_engine(cfg, variant):
     bit-equal (CRN.py:568-575 carried state: conv time buffers + GRU h; the variants add the preconv buffers).  Then one
     stream of A moves into batch slot 0 of a 1-stream engine C (a caller changes servers): same output within rounding."""
     B, L = 2, len(cfg["num_channels"])
-    a, b, c = (_engine(cfg, variant, seed=3) for _ in range(3))
+    a, b, c = (_engine(cfg, variant=variant, seed=3) for _ in range(3))
     mix, _ = synth.synth_utterances(B, 3200 * 4, 3, seed=61)
     a.reset(B)
     for k in range(3):
@@ -122,7 +109,7 @@ def test_bf16x3_mode_vs_reference_goldens(golden, vgolden, tag, cfg, variant, L)
     """precision = 2 (hi*hi + hi*mid + mid*hi on the bf16 matrix cores, fp32 accumulation; recurrence, norms and storage
     fp32) against the outputs of the genuine reference modules, at north_star's bar: relative RMS < 1e-4 and SI-SDR of
     build and reference against the clean signal within 0.02 dB."""
-    e = _engine(cfg, variant, precision=2)
+    e = _engine(cfg, variant=variant, precision=2)
     mix, clean = synth.synth_utterances(2, L + (3200 if tag == "full400" else 0), 3, seed=7)
     y = e.realtime_process(_cuda(mix[..., :L])).cpu().numpy()
     ref = (vgolden if variant else golden)[f"{tag}_out"]
@@ -139,7 +126,7 @@ def test_student_batch1024_bf16x3():
     """BASELINE configs[4] size: the distilled student at B = 1024 in the fast mode.  Stream i of the big batch equals the
     same utterance in a batch of 4 run by the fp32-accurate engine to 1e-4 (parity of the mode is pinned against the
     reference goldens above; this checks the B = 1024 launch geometry), deterministic, finite."""
-    e3, e6 = _engine(STUDENT400, 2, precision=2, seed=1), _engine(STUDENT400, 2, precision=0, seed=1)
+    e3, e6 = _engine(STUDENT400, variant=2, precision=2, seed=1), _engine(STUDENT400, variant=2, precision=0, seed=1)
     L = 9600
     base, clean = synth.synth_utterances(4, L, 3, seed=71)
     big = np.ascontiguousarray(np.tile(base, (256, 1, 1)))
@@ -343,7 +330,6 @@ def test_plane_gemm_matches_first_generation_gemm(monkeypatch):
     """k_gemm_p (split-bf16 A planes written by the producers, LDS-DMA ring) against k_gemm_x (fp32 A split in the
     kernel) on the whole bottleneck: same products, different summation grouping -> fp32 round-off only.  Also the
     'enc{L-1}' tap, which the plane path reconstructs from the GEMM's A planes."""
-    from test_gpu_parity import FULL512, _engine, _cuda, rel_rms
     mix, _ = synth.synth_utterances(4, 9600, 3, seed=77)
     x = _cuda(mix)
     last = "enc%d" % (len(FULL512["num_channels"]) - 1)
@@ -364,14 +350,13 @@ def test_preconv_blocks_on_plane_path_match_vector_kernel(monkeypatch, variant):
     """CRN_ELU / student: the three 5x5 pre-conv blocks on k_conv_p<25,...> (default only with fp16 operands, SE_PRE_P=1 forces
     it) against the fp32 vector-ALU kernel, fp32-accurate mode: outputs, the pre-chain output tap and the exported
     4-frame pre-conv buffers agree to fp32 round-off (CRN_ELU.py:335-340, 375-376)."""
-    from test_gpu_parity import FULL400, STUDENT400, _engine_v, _cuda, rel_rms
     cfg = FULL400 if variant == 1 else STUDENT400
     mix, _ = synth.synth_utterances(3, 9600, 3, seed=91)
     x = _cuda(mix)
     res = {}
     for flag in ("0", "1"):
         monkeypatch.setenv("SE_PRE_P", flag)
-        e = _engine_v(cfg, variant, seed=4)
+        e = _engine(cfg, variant=variant, seed=4)
         y = e.realtime_process(x).cpu().numpy()
         e.reset(3)
         for k in range(2):
@@ -411,9 +396,8 @@ def test_fused_training_forward_equals_per_segment_autograd():
 def test_reset_single_stream_student_plane_path(monkeypatch, pre_p):
     """se_reset_stream on the student (pre-conv rings of the plane path with SE_PRE_P=1, fp32 pre-conv buffers otherwise):
     after resetting stream 1 only, stream 1 behaves like a freshly reset engine and stream 0 like an untouched one."""
-    from test_gpu_parity import STUDENT400, _engine_v, _cuda, rel_rms
     monkeypatch.setenv("SE_PRE_P", pre_p)
-    e, e_fresh, e_cont = (_engine_v(STUDENT400, 2, seed=3) for _ in range(3))
+    e, e_fresh, e_cont = (_engine(STUDENT400, variant=2, seed=3) for _ in range(3))
     a, _ = synth.synth_utterances(2, 3200 * 3, 3, seed=41)
     bnew, _ = synth.synth_utterances(1, 3200 * 2, 3, seed=42)
     e.reset(2); e_cont.reset(2); e_fresh.reset(1)
@@ -435,7 +419,6 @@ def test_small_batch_routes_match_large_batch_kernels(monkeypatch):
     """Small batches route the bottleneck GEMMs to the skinny fp32 kernel and the skip gate to the two-launch k_conv_p form
     (se_reset decides by batch); the large-batch kernels (k_gemm_p, k_skip_p) forced onto the same small batch must agree
     to fp32 round-off, end to end and on the decoder taps."""
-    from test_gpu_parity import FULL512, _engine, _cuda, rel_rms
     mix, _ = synth.synth_utterances(3, 9600, 3, seed=55)
     x = _cuda(mix)
     res = {}

@@ -6,27 +6,14 @@ import pytest
 import torch
 
 from conftest import FULL400, FULL512, STUDENT400, TINY, rel_rms, spec_of, spec_of_variant
+from engine_cases import cuda as _cuda, make_engine as _engine
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
 def _rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def _engine(cfg, variant=0, precision=0, seed=0):
-    from speech_enhancement_mi_amd import engine
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of_variant(cfg, variant), seed=seed))
-    return e
 
 
 # ---- a weight reload must not switch the plane GEMM route back on for a small batch ---------------------
@@ -472,7 +459,7 @@ def test_student_feature_taps_device_form_equals_host_form(precision):
     """se_read_tap_dev("ft<k>") (the k_conv_p re-run on the planes in the ring slot, one device transposition k_tap_r_to_bcft) writes
     exactly what the host tap returns (the same two launches and a copy), at the full student geometry and in every operand format
     (3 / 2 bf16 planes, one fp16 plane)."""
-    e = _engine(STUDENT400, 2, precision=precision, seed=1)
+    e = _engine(STUDENT400, variant=2, precision=precision, seed=1)
     mix, _ = synth.synth_utterances(3, 6400, 3, seed=31)
     e.reset(3)
     for n in range(2):
@@ -546,7 +533,7 @@ def test_student_batch1024_fp16_named_dtype():
     """BASELINE configs[4] names fp16: precision = 1 (fp16 MFMA operands, fp32 accumulation and storage of the recurrence / norms) at
     B = 1024: finite, bit-repeatable, batch-independent, and within the documented 3e-3 of the fp32-accurate engine (outside
     north_star's 1e-4 bar by design: bf16x3 is the in-bar fast mode, pinned against the reference goldens)."""
-    e16, e32 = _engine(STUDENT400, 2, precision=1, seed=1), _engine(STUDENT400, 2, precision=0, seed=1)
+    e16, e32 = _engine(STUDENT400, variant=2, precision=1, seed=1), _engine(STUDENT400, variant=2, precision=0, seed=1)
     L = 9600
     base, clean = synth.synth_utterances(4, L, 3, seed=71)
     big = np.ascontiguousarray(np.tile(base, (256, 1, 1)))

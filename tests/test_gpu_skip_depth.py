@@ -5,18 +5,13 @@ Engines as in test_gpu_f16_pair.py: SE_GEMM_SKINNY_ROWS=0, SE_SKIP_MIN_BATCH=1 (
 before creation; three segments with flag=False, then two more with flag=True."""
 import numpy as np
 import pytest
-import torch
 
 from conftest import FULL512, rel_rms, spec_of
+from engine_cases import SHORT, SMALL, cuda as _cuda, make_engine, two_call_snapshots, utterances
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-SMALL = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)  # a single octet on levels 1 and 2: the clamped odd octet is read
-# Some waves own no tile: a segment has at least 17 frames (the largest dilation history), so fewer than 8 tiles of 32 positions need
-# at most 13 bins on the deepest skip level.  128-point FFT at 4 kHz (25 ms window = 100 samples, 17 frames): 65 bins, 33 / 17 / 9 on
-# levels 1 to 3, 17 x 9 = 153 positions = 5 tiles for the 8 waves of a workgroup.
-SHORT = dict(SMALL, sample_rate=4000, n_fft=128, num_freqs=65, segment_length=640)
 TAPS = ["dec0", "dec1", "dec2"]
 # the one-ahead loop (the reference); several batches (one and two tiles); the capacity on every level; the default (the capacity on the
 # levels with KP = 1 and 4, the one-ahead loop on those with KP = 2)
@@ -24,42 +19,19 @@ DEPTHS = ["0", "1", "2", "64", None]
 
 
 def _engine(cfg, depth, monkeypatch, precision=0):
-    from speech_enhancement_mi_amd import engine
-    monkeypatch.setenv("SE_GEMM_SKINNY_ROWS", "0")
-    monkeypatch.setenv("SE_SKIP_MIN_BATCH", "1")
-    for k in ("SE_F16_PAIR", "SE_PIPELINE", "SE_SKIP_DEPTH"):
-        monkeypatch.delenv(k, raising=False)
-    if depth is not None:
-        monkeypatch.setenv("SE_SKIP_DEPTH", depth)
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(synth.make_state_dict(spec_of(cfg), seed=4))
-    return e
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    env = {"SE_GEMM_SKINNY_ROWS": "0", "SE_SKIP_MIN_BATCH": "1"}
+    return make_engine(cfg, monkeypatch, env if depth is None else dict(env, SE_SKIP_DEPTH=depth), precision=precision, seed=4)
 
 
 @pytest.fixture(scope="module")
 def audio():
-    mix, _ = synth.synth_utterances(17, 6400 + 3200, 3, seed=67)
-    mix.setflags(write=False)
-    return mix
+    return utterances(17, 6400 + 3200, seed=67)
 
 
 def _run(e, cfg, x):
     """Three segments with flag=False, then two more with flag=True: after each call the output, the decoder taps and the carried state."""
     seg = cfg["segment_length"]
-    l1, l2 = 2 * seg, seg + seg // 2
-    got = []
-    for lo, hi, flag in ((0, l1, False), (l1, l1 + l2, True)):
-        got.append(e.realtime_process(_cuda(x[:, :, lo:hi]), flag=flag).cpu().numpy())
-        got += [np.array(e.read_tap(t), copy=True) for t in TAPS]
-        got += [np.array(e.export_state(k), copy=True) for k in ["h"] + [f"buf{i}" for i in range(len(cfg["num_channels"]))]]
-    return got
+    return [a for snap in two_call_snapshots(e, cfg, x, (2 * seg, seg + seg // 2), TAPS) for a in snap.values()]
 
 
 @pytest.mark.parametrize("name,cfg,batch,precision", [

@@ -7,15 +7,13 @@ function, so they must agree within the project's bar between two such routes, 2
 state.  SE_SKIP_MIN_BATCH picks the form (1: streaming at every batch, 100000: two launches); engines as in test_gpu_skip_depth.py."""
 import numpy as np
 import pytest
-import torch
 
 from conftest import FULL512, rel_rms, spec_of_variant
+from engine_cases import SHORT, SMALL, cuda as _cuda, make_engine, two_call_snapshots, utterances
 from speech_enhancement_mi_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-SMALL = dict(FULL512, num_channels=[8, 8, 16, 32], hidden=64)  # a single octet on levels 1 and 2
-SHORT = dict(SMALL, sample_rate=4000, n_fft=128, num_freqs=65, segment_length=640)  # 5 tiles for 8 waves: waves without a tile
 TAPS = ["dec0", "dec1", "dec2"]
 BAR = 2e-6
 STREAM, BLEND = "1", "100000"
@@ -32,43 +30,21 @@ def _state_dict(cfg, variant, scale_residualnorm=None):
 
 
 def _engine(cfg, min_batch, monkeypatch, mode="pair", variant=0, sd=None):
-    from speech_enhancement_mi_amd import engine
     precision, f16_pair = MODES[mode]
-    monkeypatch.setenv("SE_GEMM_SKINNY_ROWS", "0")
-    monkeypatch.setenv("SE_SKIP_MIN_BATCH", min_batch)
-    for k in ("SE_F16_PAIR", "SE_PIPELINE", "SE_SKIP_DEPTH"):
-        monkeypatch.delenv(k, raising=False)
-    if f16_pair is not None:
-        monkeypatch.setenv("SE_F16_PAIR", f16_pair)
-    c = engine.make_config(cfg["num_channels"], cfg["num_freqs"], cfg["hidden"], cfg["segment_length"], cfg["num_layers"],
-                           cfg["num_inputs"], cfg["kernel_size"], cfg["sample_rate"], cfg["win_length"], cfg["hop_length"], cfg["n_fft"],
-                           variant=variant, precision=precision)
-    e = engine.Engine(c, 0)
-    e.load_state_dict(sd if sd is not None else _state_dict(cfg, variant))
-    return e
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    env = {"SE_GEMM_SKINNY_ROWS": "0", "SE_SKIP_MIN_BATCH": min_batch}
+    return make_engine(cfg, monkeypatch, env if f16_pair is None else dict(env, SE_F16_PAIR=f16_pair), variant=variant, precision=precision,
+                       sd=sd if sd is not None else _state_dict(cfg, variant))
 
 
 @pytest.fixture(scope="module")
 def audio():
-    mix, _ = synth.synth_utterances(17, 6400 + 3200, 3, seed=67)
-    mix.setflags(write=False)
-    return mix
+    return utterances(17, 6400 + 3200, seed=67)
 
 
 def _run(e, cfg, x):
     """Three segments with flag=False, then two more with flag=True: after each call the output, the decoder taps and the carried state."""
     seg = cfg["segment_length"]
-    l1, l2 = 2 * seg, seg + seg // 2
-    got = []
-    for lo, hi, flag in ((0, l1, False), (l1, l1 + l2, True)):
-        got.append(("out", e.realtime_process(_cuda(x[:, :, lo:hi]), flag=flag).cpu().numpy()))
-        got += [(t, np.array(e.read_tap(t), copy=True)) for t in TAPS]
-        got += [(k, np.array(e.export_state(k), copy=True)) for k in ["h"] + [f"buf{i}" for i in range(len(cfg["num_channels"]))]]
-    return got
+    return [kv for snap in two_call_snapshots(e, cfg, x, (2 * seg, seg + seg // 2), TAPS) for kv in snap.items()]
 
 
 def _compare(tag, cfg, x, monkeypatch, **kw):
